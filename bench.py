@@ -13,8 +13,13 @@ Philox noise; conditioning tensors are already resident in HBM when the timed re
                                                               # over the ranks, result all-gathered inside the timed region
 
 Default is weak scaling (512 clips per GPU, no data-path collective).  Rank 0 prints ONE JSON line (driver contract) with,
-besides the contract's keys:
-  "roofline"       fused step kernel vs the gfx950 FP32-matrix MFMA peak; duration from HIP events on the engine's own stream
+besides the contract's keys, "roofline": the step kernel of the timed calls vs the gfx950 FP32-matrix MFMA peak; duration
+from HIP events on the engine's own stream.
+
+A plain run does only what the headline needs: set up, warm up, time --steps calls, write the last call's output if
+--dump-outputs DIR is given (DIR/samples.npy, float32, rank 0's view: the gathered global batch under --global-batch),
+print the line.  Everything else is measured or checked only with --full:
+  "roofline.traffic"  HBM bytes per step-kernel launch from two rocprofv3 PMC passes of a child process
   "parity_in_run"  two samples of the FIRST TIMED call replayed through the CPU oracle on the restated Philox noise
   "single_pass"    the guidance-scale-1 workload (uncond pass legitimately skipped), own FLOP count -- never mixed into `value`
   "livelyspeaker"  BASELINE configs[2] as the reference runs it: SAG decode + ddim100 / skip 80 refine, own roofline
@@ -24,6 +29,8 @@ besides the contract's keys:
   "shard_check"    the config-4 premise on hardware: every rank re-generates ANOTHER rank's shard via sample_offset
   "split_precision", "train_step"   secondary legs
   "cpu_baseline"   torch-CPU port of the reference algorithm timed on this box's host cores (bounded sample)
+  "ranks", "gather"   per-rank diagnostics of an N > 1 run and the cost of the result gather
+The --no-* / --legs options below narrow what --full runs.
 """
 import argparse
 import hashlib
@@ -85,7 +92,29 @@ def parse():
     ap.add_argument("--no-traffic-pass", action="store_true", help="do not spawn the two rocprofv3 PMC passes that measure roofline.traffic")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3"],
                     help="fp32 = exact (headline); bf16x3 = opt-in split-precision channel mixing")
+    ap.add_argument("--full", action="store_true", help="besides the headline: in-run parity, shard cross-check, secondary legs, "
+                    "PMC traffic passes, CPU baselines, per-rank diagnostics (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed calls, write what the last one returned as DIR/<name>.npy (float32)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32.  An array over the budget keeps a fixed, seeded sample of its
+    leading-axis rows (sorted), whose indices go to DIR/<name>_rows.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, v in arrays.items():
+        v = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+        if v.nbytes > budget:
+            keep = max(1, budget // max(v[:1].nbytes, 1))
+            rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(v.shape[0], size=keep, replace=False))
+            np.save(os.path.join(dirname, f"{name}_rows.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(dirname, f"{name}.npy"), v)
 
 
 def mk_args(cfg, steps):
@@ -649,7 +678,7 @@ def threads_main(a):
             for i in range(n):
                 e.prepare(conds[r])
                 o = e.sample(sampler=sampler, philox_seed=seed, sample_offset=spans[r][0], skip_timesteps=a.skip, use_graph=not a.no_graph)
-                if keep and i == 0:
+                if keep and i == n - 1:         # (every call has the same key and offset: the same result)
                     outs[r] = o
             bar.wait()
             times[r] = time.perf_counter() - t0
@@ -672,12 +701,18 @@ def threads_main(a):
     elapsed = run(a.steps, True)
     whole = np.concatenate(outs, axis=0)
     assert whole.shape[0] == total and np.isfinite(whole).all()
-    # cross-check: device 0 re-generates the NEXT shard by itself (same Philox key, that shard's conditioning, sample_offset)
-    nb = 1 % world
-    engines[0].prepare(conds[nb])
-    redo = engines[0].sample(sampler=sampler, philox_seed=seed, sample_offset=spans[nb][0], skip_timesteps=a.skip, use_graph=not a.no_graph)
-    diff = float(np.abs(redo - outs[nb]).max())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"samples": whole})
     tm = engines[0].timing()
+    shard_check = None
+    if a.full:
+        # cross-check: device 0 re-generates the NEXT shard by itself (same Philox key, that shard's conditioning, sample_offset)
+        nb = 1 % world
+        engines[0].prepare(conds[nb])
+        redo = engines[0].sample(sampler=sampler, philox_seed=seed, sample_offset=spans[nb][0], skip_timesteps=a.skip, use_graph=not a.no_graph)
+        diff = float(np.abs(redo - outs[nb]).max())
+        shard_check = {"what": "device 0 re-generated the next shard via sample_offset and compared it with that handle's result",
+                       "max_abs_diff": diff, "bitwise_equal": diff == 0.0, "ranks": world}
     n_exec = sch.num_timesteps - a.skip
     rec = {"metric": "pose-frames/sec denoised", "value": round(total * cfg.nframes * a.steps / elapsed, 2), "unit": "pose-frames/s",
            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True,
@@ -690,10 +725,10 @@ def threads_main(a):
                       "global_batch": total, "frames": cfg.nframes, "denoise_steps": n_exec, "guidance_scale": a.scale,
                       "parallelism": f"batch-sharded x{world}, no collective", "hipgraph": not a.no_graph},
            "collective_backend": "none", "rccl_ranks": 0,
-           "shard_check": {"what": "device 0 re-generated the next shard via sample_offset and compared it with that handle's result",
-                           "max_abs_diff": diff, "bitwise_equal": diff == 0.0, "ranks": world},
            "roofline": {"bound": "mfma", "kernel_ms_device0": round(tm["loop_ms"] / max(tm["n_step_launches"], 1), 4), "peak": MFMA_F32_PEAK_TFLOPS,
                         "unit": "TFLOP/s", "note": "per-device kernel time of the last call on device 0; the headline roofline object is the torchrun launcher's"}}
+    if shard_check is not None:
+        rec["shard_check"] = shard_check
     if a.ranks_share_device:
         rec["ranks_share_device"] = "TEST MODE: every handle on cuda:0 (the handles time-share one GPU); `value` is not a scaling number"
     for e in engines:
@@ -799,8 +834,9 @@ def main():
         return float(t.item())
 
     def timed(n, yy=None):
-        """n calls bracketed by barrier + synchronize; max over ranks.  Returns (elapsed, loop_ms, launches, prep_ms, first_out, seed)."""
-        loop_ms, launches, prep_ms, first_out, seed, gathered = 0.0, 0, 0.0, None, None, None
+        """n calls bracketed by barrier + synchronize; max over ranks.  Returns (elapsed, loop_ms, launches, prep_ms, first_out, seed,
+        gathered, out): the last call's gathered result (strong scaling) and its local one."""
+        loop_ms, launches, prep_ms, first_out, seed, gathered, out = 0.0, 0, 0.0, None, None, None, None
         fence()
         t0 = time.perf_counter()
         for i in range(n):
@@ -814,14 +850,16 @@ def main():
         fence()
         el = time.perf_counter() - t0
         el = max_over_ranks(el)
-        return el, loop_ms, launches, prep_ms, first_out, seed, gathered
+        return el, loop_ms, launches, prep_ms, first_out, seed, gathered, out
 
     torch.manual_seed(233)                  # every rank draws the same Philox key per call
     for _ in range(a.warmup):
         one_call()
     eng = model.engine()
-    elapsed, loop_ms, launches, prep_ms, first_out, first_seed, gathered = timed(a.steps)
+    elapsed, loop_ms, launches, prep_ms, first_out, first_seed, gathered, last_out = timed(a.steps)
     assert first_out is not None and bool(torch.isfinite(first_out).all()), "non-finite samples"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"samples": gathered if strong else last_out})
     main_tm = eng.timing()                  # what the headline's step loop ran on (later legs re-plan the same engine)
     single_pass_main = bool(main_tm["single_pass"])
 
@@ -829,7 +867,7 @@ def main():
     # with sample_offset, and compares it with what that rank produced (strong mode: the gathered tensor; weak mode: a P2P-free
     # all_gather of the per-rank results).  Bitwise equality expected: the streams depend on the global index only.
     shard_check = None
-    if use_dist or strong:
+    if a.full and (use_dist or strong):
         try:
             def regenerate(first_idx, count, shard_index):
                 y_sh = {k: torch.from_numpy(v).to(dev) for k, v in cond_of(shard_index, a.scale).items()}
@@ -849,7 +887,7 @@ def main():
     # diagnostics of a multi-rank run, so that the first run on N real GPUs can be read from its one line: every rank's device, CU count,
     # kernel plan and own timings (collected over the gloo control plane), and what the result gather costs on the data group
     rank_recs = gather_rec = None
-    if use_dist:
+    if a.full and use_dist:
         try:
             prop = torch.cuda.get_device_properties(dev)
             rank_recs = shard.rank_reports({"device": f"cuda:{local}", "name": prop.name, "n_cus": int(main_tm["n_cus"]), "batch": B,
@@ -860,7 +898,7 @@ def main():
         except Exception as e:          # noqa: BLE001  (symmetric on every rank)
             rank_recs, gather_rec = [{"error": repr(e)[:300]}], None
 
-    extra = not a.no_extra_legs and a.precision == "fp32" and a.legs != "none"
+    extra = a.full and not a.no_extra_legs and a.precision == "fp32" and a.legs != "none"
     legs = set(("single", "split", "lively", "beat", "train", "seeds", "small", "mid") if a.legs in ("all", "none") else a.legs.split(","))
 
     # Secondary object: guidance scale 1 (what the reference's callers run): the uncond pass is legitimately skipped
@@ -869,7 +907,7 @@ def main():
         y1 = dict(y, scale=torch.ones(B, device=dev))
         one_call(y1)
         n1 = max(1, min(a.steps, 2))
-        e1, l1, k1, _, o1, _, _ = timed(n1, y1)
+        e1, l1, k1, _, o1, _, _, _ = timed(n1, y1)
         assert bool(eng.timing()["single_pass"]) and bool(torch.isfinite(o1).all())
         km = l1 / max(k1, 1)
         ach1 = FLOP_PER_FORWARD[a.dataset] * B / (km * 1e-3) / 1e12
@@ -887,7 +925,7 @@ def main():
         model.precision = "bf16x3"
         one_call()
         n2 = max(1, min(a.steps, 2))
-        e2, l2, k2, _, _, _, _ = timed(n2)
+        e2, l2, k2, _, _, _, _, _ = timed(n2)
         split = {"mode": "bf16x3: channel/token mixing as 3 bf16 MFMAs per fp32 product (hi.hi+hi.lo+lo.hi), fp32 accumulate",
                  "value": round(total * cfg.nframes * n2 / e2, 2), "unit": "pose-frames/s",
                  "kernel_ms": round(l2 / max(k2, 1), 4),
@@ -1030,8 +1068,8 @@ def main():
         # fp32: FP32-matrix MFMA peak.  bf16x3: three bf16 MFMAs per algorithmic product -> dense bf16 peak / 3.
         peak = MFMA_F32_PEAK_TFLOPS if a.precision == "fp32" else round(2500.0 / 3.0, 1)
         committed, committed_src = pmc_traffic(a.dataset, B)
-        traffic, traffic_src = None, "not measured (--no-traffic-pass)"
-        if world == 1 and not a.no_traffic_pass and a.dataset != "beat150" and a.precision == "fp32":
+        traffic, traffic_src = None, "not measured (--no-traffic-pass)" if a.full else "not measured (measured with --full)"
+        if a.full and world == 1 and not a.no_traffic_pass and a.dataset != "beat150" and a.precision == "fp32":
             traffic, traffic_src = measure_traffic(a, B)
         rec = {
             "metric": "pose-frames/sec denoised", "value": round(frames / elapsed, 2), "unit": "pose-frames/s",
@@ -1065,16 +1103,19 @@ def main():
         if rank_recs is not None:
             rec["ranks"] = rank_recs
             rec["gather"] = gather_rec
-        if shard_check is not None:
-            rec["shard_check"] = shard_check
-            rec["rccl_ranks"] = shard_check["rccl_ranks"]
+        if use_dist or strong:
+            if shard_check is not None:
+                rec["shard_check"] = shard_check
+                rec["rccl_ranks"] = shard_check["rccl_ranks"]
+            else:
+                rec["rccl_ranks"] = groups["rccl_ranks"] if groups is not None else 0
             rec["collective_backend"] = backend
             if groups is not None and groups.get("rccl_error"):
                 rec["rccl_error"] = groups["rccl_error"]
             if a.ranks_share_device:
                 rec["ranks_share_device"] = ("TEST MODE: all ranks on cuda:0 (RCCL rejects duplicate devices, so its probe fails and the "
                                              "collectives fall back to gloo on host copies -- the fallback path itself); `value` is not a scaling number")
-        if not a.no_parity:
+        if a.full and not a.no_parity:
             try:
                 rec["parity_in_run"] = parity_in_run(cfg, a, first_out.detach().cpu().numpy(), first_seed, first, y_np, a.parity_samples)
             except Exception as e:
@@ -1095,7 +1136,7 @@ def main():
             rec["split_precision"] = split
         if train is not None:
             rec["train_step"] = train
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 rec["cpu_baseline"] = cpu_baseline(cfg, a)
             except Exception as e:

@@ -150,7 +150,7 @@ def test_bench_strong_scaling_path_under_torch_distributed_run(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--diffusion-steps", "100", "--no-cpu-baseline", "--no-extra-legs"]
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--diffusion-steps", "100", "--full", "--no-cpu-baseline", "--no-extra-legs"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r1 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                          "--master-port", "29611", os.path.join(root, "bench.py"), "--global-batch", "512"] + common,
@@ -189,7 +189,7 @@ def test_bench_launches_its_own_ranks_and_runs_the_n_rank_path_with_two_ranks_on
     streams keyed by the global sample index, shard cross-check of the neighbour's shard, max-over-ranks timing, rank 0's single
     JSON line; and configs[2]'s leg with the CLIP-feature broadcast + all_gather in its timed region."""
     root = ROOT
-    common = ["--steps", "1", "--warmup", "1", "--diffusion-steps", "60", "--no-cpu-baseline", "--batch", "128"]
+    common = ["--steps", "1", "--warmup", "1", "--diffusion-steps", "60", "--full", "--no-cpu-baseline", "--batch", "128"]
     two = _bench(root, ["--gpus", "2", "--ranks-share-device", "--legs", "lively"] + common)
     assert two["n_gpus"] == 2 and two["scaling"] == "weak" and two["config"]["global_batch"] == 256
     assert two["collective_backend"] == "gloo" and two["rccl_ranks"] == 0 and two["shard_check"]["ranks"] == 2
@@ -212,7 +212,7 @@ def test_bench_threads_launcher_two_handles_on_one_gpu():
     """`--launcher threads`: one process, one engine handle per device driven by one Python thread each, no process group and no
     collective -- the independent N-device number / cross-check of the torchrun path.  On this one-GPU box both handles sit on
     cuda:0 (--ranks-share-device): same shards, same Philox streams as two torchrun ranks would produce."""
-    common = ["--steps", "1", "--warmup", "1", "--diffusion-steps", "60", "--batch", "128"]
+    common = ["--steps", "1", "--warmup", "1", "--diffusion-steps", "60", "--full", "--batch", "128"]
     thr = _bench(ROOT, ["--gpus", "2", "--launcher", "threads", "--ranks-share-device"] + common)
     assert thr["n_gpus"] == 2 and thr["config"]["global_batch"] == 256 and thr["collective_backend"] == "none" and thr["rccl_ranks"] == 0
     assert thr["shard_check"]["bitwise_equal"] and thr["launcher"].startswith("threads")
@@ -221,17 +221,48 @@ def test_bench_threads_launcher_two_handles_on_one_gpu():
     print("threads launcher, 2 handles on one GPU:", thr["value"], "| strong 300:", strong["value"])
 
 
+def test_bench_plain_run_times_the_headline_only_and_dumps_its_last_call(tmp_path):
+    """A plain run (no --full) times --steps calls and adds no checker or secondary leg to its line; --dump-outputs writes the last
+    timed call's samples, which are the same from run to run with the same arguments and are the oracle's result for that call's
+    Philox key (the key of call k is the k-th draw after torch.manual_seed(233))."""
+    import torch
+    from livelyspeaker_amd import synth
+    from oracle import philox_oracle as po
+    from oracle import rag_oracle as orc
+    common = ["--steps", "2", "--warmup", "1", "--diffusion-steps", "20", "--batch", "8"]
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        line = _bench(ROOT, common + ["--dump-outputs", str(d)])
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+        assert not {"parity_in_run", "cpu_baseline", "single_pass", "livelyspeaker", "train_step", "shard_check"} & set(line), sorted(line)
+        runs.append(np.load(d / "samples.npy"))
+    cfg = synth.TED
+    assert runs[0].dtype == np.float32 and runs[0].shape == (8, cfg.njoints, cfg.nfeats, cfg.nframes)
+    assert np.array_equal(runs[0], runs[1])
+    g = torch.Generator().manual_seed(233)
+    seed = [int(torch.randint(0, 2 ** 62, (1,), generator=g).item()) for _ in range(3)][-1]          # warm-up, timed 1, timed 2
+    pick = np.array([0, 7])
+    sch = orc.Schedule(20, "")
+    eps, noise = po.step_tapes(seed, pick, sch.num_timesteps, (cfg.njoints, cfg.nfeats, cfg.nframes))
+    x_T = po.x_init(seed, pick, cfg.jf, cfg.nframes, (cfg.njoints, cfg.nfeats))
+    oracle = orc.RagOracle(synth.make_state_dict(cfg, seed=synth.SEED_WEIGHTS), cfg.njoints, cfg.nfeats, cfg.n_prefix_tokens, nframes=cfg.nframes)
+    y = {k: v[pick] for k, v in synth.make_cond(cfg, 8, scale=1.5, seed=synth.SEED_COND).items()}
+    want = orc.sample_loop(oracle, sch, y, x_T, eps, noise)
+    assert np.abs(runs[0][pick].astype(np.float64) - want).max() <= 3e-4
+
+
 def test_eight_launchers_on_one_gpu_both_ways():
     """What one GPU allows of the driver's N = 8 run: eight torchrun ranks on cuda:0 (gloo control plane, RCCL probed and refused,
     every rank re-generating its neighbour's shard bitwise, ONE JSON line), and eight engine handles driven by eight threads of one
     process.  Throughput here is eight step loops time-sharing one GPU (eight streams over the runtime's hardware queues), not a
     scaling number; what is checked is that nothing deadlocks or serialises completely: the eight handles together reach at least
     half of what one handle does with the same 512 clips."""
-    common = ["--steps", "1", "--warmup", "1", "--diffusion-steps", "40", "--no-cpu-baseline", "--legs", "none"]
+    common = ["--steps", "1", "--warmup", "1", "--diffusion-steps", "40", "--full", "--no-cpu-baseline", "--legs", "none"]
     eight = _bench(ROOT, ["--gpus", "8", "--ranks-share-device", "--batch", "16"] + common, timeout=1800)
     assert eight["n_gpus"] == 8 and eight["config"]["global_batch"] == 128 and eight["collective_backend"] == "gloo" and eight["rccl_error"]
     assert eight["shard_check"]["ranks"] == 8 and eight["shard_check"]["bitwise_equal"] and eight["parity_in_run"]["ok"]
-    thr_common = ["--steps", "2", "--warmup", "1", "--diffusion-steps", "100"]
+    thr_common = ["--steps", "2", "--warmup", "1", "--diffusion-steps", "100", "--full"]
     thr = _bench(ROOT, ["--gpus", "8", "--launcher", "threads", "--ranks-share-device", "--batch", "64", "--path", "pass"] + thr_common)
     one = _bench(ROOT, ["--gpus", "1", "--launcher", "threads", "--batch", "512"] + thr_common)
     assert thr["n_gpus"] == 8 and thr["config"]["global_batch"] == 512 and thr["shard_check"]["bitwise_equal"] and thr["shard_check"]["ranks"] == 8

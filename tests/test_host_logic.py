@@ -274,6 +274,24 @@ def test_bench_stdout_carries_only_the_result_line():
     assert "banner written to fd 1" in r.stderr and "python-level noise" in r.stderr
 
 
+def test_bench_dump_outputs_is_float32_and_samples_rows_over_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs writes each array as DIR/<name>.npy in float32; one over the size budget keeps a fixed, seeded sample of its
+    rows (the same on every run) and their indices (float64) beside it."""
+    import bench
+    x = np.arange(40 * 6, dtype=np.float64).reshape(40, 6)
+    bench.dump_outputs(str(tmp_path / "a"), {"samples": x})
+    got = np.load(tmp_path / "a" / "samples.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.astype(np.float32)) and not (tmp_path / "a" / "samples_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * 6 * 4)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"samples": x})
+    rows = np.load(tmp_path / "b" / "samples_rows.npy")
+    got = np.load(tmp_path / "b" / "samples.npy")
+    assert rows.dtype == np.float64 and len(rows) == 10 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got, x[rows.astype(int)].astype(np.float32)) and got.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "samples_rows.npy"))
+
+
 def test_build_staleness_is_content_based(tmp_path, monkeypatch):
     """The library is rebuilt when its sources changed, judged by the content hash the build leaves beside it (file times do not
     survive every copy of the tree); without the stamp the check falls back to modification times."""
@@ -293,10 +311,9 @@ def test_build_staleness_is_content_based(tmp_path, monkeypatch):
 def test_checkpoint_files_interchange_with_the_reference(tmp_path):
     """model%09d.pt must pass the reference's `load_model_wo_clip` (no unexpected keys, only clip_model.* may be missing) and
     opt%09d.pt must load into a `torch.optim.AdamW` over the reference model's parameters; and a file written by the reference's
-    optimizer must load back into the engine's layout.  Runs the reference's own loader when /root/reference is present (build
-    container); the layout checks against the mirror model run everywhere."""
-    import subprocess
-    import sys
+    optimizer must load back into the engine's layout.  The reference's side is its recorded checkpoint layout
+    (tests/golden/ckpt_layout_ted.json: state_dict and optimizer parameter list, names and shapes)."""
+    import json
     from livelyspeaker_amd import synth, train_loop as tl
     from livelyspeaker_amd.model_util import create_model_and_diffusion
     cfg = synth.TED
@@ -321,33 +338,26 @@ def test_checkpoint_files_interchange_with_the_reference(tmp_path):
         assert np.array_equal(np.asarray(back["exp_avg_sq"][k]).ravel(), opt["exp_avg_sq"][k])
     old, lr_old = tl.unpack_optimizer_state(model, {"step": 3, "exp_avg": {"a": 1}, "exp_avg_sq": {"a": 2}})   # round-1 layout
     assert old["step"] == 3 and lr_old is None
-    if not os.path.isdir("/root/reference/scripts"):
-        return
+    # the reference's side, from its recorded layout (tests/golden/make_golden_ckpt.py): load_model_wo_clip asserts no unexpected
+    # key and only clip_model.* missing (and load_state_dict refuses other shapes); the optimizer is torch's AdamW over
+    # model.parameters_wo_clip(), which is rebuilt here from the recorded parameter list
+    with open(os.path.join(ROOT, "tests", "golden", "ckpt_layout_ted.json")) as f:
+        ref = json.load(f)
     torch.save(msd, tmp_path / "model000000007.pt")
     torch.save(ost, tmp_path / "opt000000007.pt")
-    code = f'''
-import sys, types, torch
-sys.dont_write_bytecode = True
-sys.modules["clip"] = types.ModuleType("clip")
-sys.path.insert(0, "/root/reference/scripts")
-from types import SimpleNamespace
-from mdm_utils.model_util import create_model_and_diffusion, load_model_wo_clip
-args = SimpleNamespace(mdm_condm="text", latent_dim=512, ff_size=1024, layers=8, cond_mask_prob=0.1, arch="trans_enc", emb_trans_dec=False,
-    dataset="humanml", lang_model=None, mlpact="silu", diffusion_steps=1000, noise_schedule="cosine", sigma_small=True, lambda_vel=1.0,
-    lambda_rcxyz=0.0, lambda_fc=0.0)
-model, _ = create_model_and_diffusion(args, "")
-load_model_wo_clip(model, torch.load(r"{tmp_path}/model000000007.pt", map_location="cpu"))        # asserts on unexpected / missing keys
-opt = torch.optim.AdamW(model.parameters_wo_clip() if hasattr(model, "parameters_wo_clip") else model.parameters(), lr=1e-4, weight_decay=0.0)
-opt.load_state_dict(torch.load(r"{tmp_path}/opt000000007.pt", map_location="cpu"))
-names = [k for k, _ in model.named_parameters()]
-assert float(opt.state[model.get_parameter(names[0])]["step"]) == 7.0
-assert tuple(opt.state[model.get_parameter("input_mapping.weight")]["exp_avg"].shape) == (512, 311)
-torch.save(opt.state_dict(), r"{tmp_path}/ref_opt.pt")
-print("REFERENCE-LOADER-OK", len(names))
-'''
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "REFERENCE-LOADER-OK" in r.stdout, r.stderr[-2000:]
-    assert int(r.stdout.split("REFERENCE-LOADER-OK")[1].split()[0]) == len(keys)       # same parameter list, same order
+    ref_sd = {k: tuple(s) for k, s in ref["state_dict"]}
+    loaded = torch.load(tmp_path / "model000000007.pt", map_location="cpu")
+    assert not [k for k in loaded if k not in ref_sd]
+    assert all(k.startswith("clip_model.") for k in ref_sd if k not in loaded)
+    assert all(tuple(v.shape) == ref_sd[k] for k, v in loaded.items())
+    names = [k for k, _ in ref["parameters"]]
+    params = [torch.nn.Parameter(torch.zeros(s)) for _, s in ref["parameters"]]
+    ref_model_opt = torch.optim.AdamW(params, lr=1e-4, weight_decay=0.0)
+    ref_model_opt.load_state_dict(torch.load(tmp_path / "opt000000007.pt", map_location="cpu"))
+    assert float(ref_model_opt.state[params[0]]["step"]) == 7.0
+    assert tuple(ref_model_opt.state[params[names.index("input_mapping.weight")]]["exp_avg"].shape) == (512, 311)
+    assert ref["all_parameters"] == len(keys) and names == keys                # same parameter list, same order
+    torch.save(ref_model_opt.state_dict(), tmp_path / "ref_opt.pt")
     back2, _ = tl.unpack_optimizer_state(model, torch.load(tmp_path / "ref_opt.pt", map_location="cpu"))
     assert np.array_equal(np.asarray(back2["exp_avg"]["speaker_mu.bias"]).ravel(), opt["exp_avg"]["speaker_mu.bias"])
 
