@@ -39,10 +39,17 @@ enum {
 
 enum { LS_SAMPLER_DDPM = 0, LS_SAMPLER_DDIM = 1 };
 enum { LS_NOISE_TAPE = 0, LS_NOISE_PHILOX = 1 };
-/* Arithmetic of the channel-mixing GEMM (92 % of the FLOPs). FP32 (default): v_mfma_f32_16x16x4_f32, exact fp32
- * products.  BF16X3 (opt-in): each fp32 operand split into bf16 hi+lo, three v_mfma_f32_16x16x32_bf16 per product
- * (hi.hi + hi.lo + lo.hi, fp32 accumulate): ~2^-16 relative product error, parity-gated at the 1e-3 contract. */
-enum { LS_PRECISION_FP32 = 0, LS_PRECISION_BF16X3 = 1 };
+/* Arithmetic of the channel-mixing GEMM (92 % of the FLOPs).
+ * FP32 (default): in the fused step kernel, split-fp32: both fp32 operands split exactly into three bf16 parts
+ *   (a = a0 + a1 + a2, round-to-nearest splits) and the partial products of v_mfma_f32_16x16x32_bf16 kept down to the
+ *   terms of order 2^-16 (six of the nine), accumulated in fp32 smallest first; an fp32-class product error (bound: DESIGN.md section 2,
+ *   measured accuracy: section 4).  The other
+ *   step kernels (sample-split, one-pass-per-workgroup, batch-level) run it on v_mfma_f32_16x16x4_f32.  A non-finite operand
+ *   makes the split residuals NaN, so an Inf input gives NaN where the fp32 MFMA may give Inf: non-finite either way.
+ * FP32_MFMA: v_mfma_f32_16x16x4_f32 everywhere (exact fp32 products, the pre-split kernel; kept for A/B runs and audits).
+ * BF16X3 (opt-in): each fp32 operand split into bf16 hi+lo, three v_mfma_f32_16x16x32_bf16 per product
+ *   (hi.hi + hi.lo + lo.hi, fp32 accumulate): ~2^-16 relative product error, parity-gated at the 1e-3 contract. */
+enum { LS_PRECISION_FP32 = 0, LS_PRECISION_BF16X3 = 1, LS_PRECISION_FP32_MFMA = 2 };
 
 typedef struct ls_handle ls_handle;
 

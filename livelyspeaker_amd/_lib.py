@@ -352,7 +352,7 @@ def plan_query(batch, dataset="ted", single_pass=False, precision="fp32", n_cus=
     lib = load_library()
     out = (C.c_int * 10)()
     ms = C.c_float()
-    rc = lib.ls_plan_query(int(dataset != "ted"), int(batch), int(bool(single_pass)), {"fp32": 0, "bf16x3": 1}.get(precision, precision), int(n_cus), out, C.byref(ms))
+    rc = lib.ls_plan_query(int(dataset != "ted"), int(batch), int(bool(single_pass)), {"fp32": 0, "bf16x3": 1, "fp32_mfma": 2}.get(precision, precision), int(n_cus), out, C.byref(ms))
     if rc != 0:
         raise EngineError(f"ls_plan_query failed ({rc})")
     return [(out[1 + 3 * i], out[2 + 3 * i], out[3 + 3 * i]) for i in range(out[0])], float(ms.value)
@@ -415,8 +415,9 @@ class Engine:
         return rc
 
     def set_precision(self, mode):
-        """'fp32' (exact, default) or 'bf16x3' (split-precision channel mixing on the bf16 matrix cores)."""
-        code = {"fp32": 0, "bf16x3": 1}.get(mode, mode)
+        """'fp32' (default: fp32-accurate split-bf16 channel mixing in the fused step kernel, fp32 MFMA elsewhere), 'fp32_mfma'
+        (fp32 MFMA everywhere, the pre-split arithmetic) or 'bf16x3' (split-precision channel mixing on the bf16 matrix cores)."""
+        code = {"fp32": 0, "bf16x3": 1, "fp32_mfma": 2}.get(mode, mode)
         self._check(self.lib.ls_set_precision(self.h, int(code)), "ls_set_precision")
         self.precision = mode
 

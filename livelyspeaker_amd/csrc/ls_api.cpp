@@ -120,7 +120,7 @@ struct ls_handle {
     unsigned weights_version = 0;
 
     // device weights
-    DevBuf wch_hi_img, wch_lo_img, ww_hi_img, ww_lo_img;
+    DevBuf wch_hi_img, wch_lo_img, wch_lo2_img, ww_hi_img, ww_lo_img;
     DevBuf wch_img, bch, ln1a, ln1b, ln2a, ln2b, ww_img, btok_rows, winx_img, wout_img, wout_reg_img, bout, devw;
     DevBuf conv_img[4];     // MFMA operand images of the stride-6 conv layers (ls_conv.hip)
     DevBuf conv_w[4], conv_b[4], win_full, win_pre, win_aud, win_bias, spk_emb, ml_w, ml_b, emo_emb;
@@ -157,7 +157,7 @@ struct ls_handle {
     ls_timing timing{};
     CallParams call_host{0, 0, 0, 0};
     unsigned tag_base = 0;  // sample-split kernel: base of the current call's hand-off tags (CallParams::tag_base)
-    int precision = 0;      // 0 exact fp32 MFMA, 1 bf16x3 split-precision channel mixing (ls_set_precision)
+    int precision = 0;      // LS_PRECISION_*: 0 fp32 (split-fp32 channel mixing in k_step), 1 bf16x3, 2 fp32 MFMA throughout (ls_set_precision)
 #ifdef LS_DEBUG             // profiling variant of the library only (build_library(defines=['LS_DEBUG'])); never in the shipped .so
     DevBuf prof, wgt;       // wgt: [1024][2] start / end stamps of every workgroup of the last step launch
     bool prof_on = false;   // LS_PROF=<workgroup index>: in-kernel s_memtime phase stamps, read with ls_read("prof")
@@ -232,7 +232,7 @@ int build_fused_images(ls_handle* h) {
     const int MK = h->MK, KXQ = h->KXQ, NOB = h->NOB, KIN = h->KIN;
     std::vector<float> wch((size_t)L * D * D), bch((size_t)L * D), l1a((size_t)L * D), l1b((size_t)L * D),
         l2a((size_t)L * D), l2b((size_t)L * D), ww((size_t)L * kNT * MK * 64), bt((size_t)L * 80, 0.f);
-    std::vector<unsigned short> wch_hi((size_t)L * D * D), wch_lo((size_t)L * D * D);
+    std::vector<unsigned short> wch_hi((size_t)L * D * D), wch_lo((size_t)L * D * D), wch_lo2((size_t)L * D * D);
     const int KS = (R + 31) / 32;
     const int MK1 = (S + 3) / 4;
     const int MQ1 = (MK1 + 3) / 4;
@@ -265,7 +265,9 @@ int build_fused_images(ls_handle* h) {
                                 const int k = 16 * q + 4 * (lane >> 4) + j;
                                 wch[o++] = (*W)[(size_t)n * D + k] * (*a2)[k];        // W' = W . diag(alpha2)
                             }
-        // bf16x3 images: W' = hi + lo, operand order of v_mfma_f32_16x16x32_bf16: [l][w][p][q16][c2][lane][8 k]
+        // bf16 images, operand order of v_mfma_f32_16x16x32_bf16: [l][w][p][q16][c2][lane][8 k].  W' = hi + mid + lo exactly, each
+        // round-to-nearest-even: hi = bf16(W'), mid = bf16(W' - hi), lo = bf16(W' - hi - mid) (both differences are exact in fp32).
+        // bf16x3 uses hi and mid (its "lo" plane, wch_lo_img); split-fp32 (k_step PREC 2) all three.
         {
             size_t oh = (size_t)l * D * D;
             for (int w = 0; w < kWaves; ++w)
@@ -279,7 +281,9 @@ int build_fused_images(ls_handle* h) {
                                     const float v = (*W)[(size_t)n * D + k] * (*a2)[k];
                                     const unsigned short hi = f32_to_bf16(v);
                                     wch_hi[oh] = hi;
-                                    wch_lo[oh] = f32_to_bf16(v - bf16_to_f32(hi));
+                                    const float r = v - bf16_to_f32(hi);
+                                    wch_lo[oh] = f32_to_bf16(r);
+                                    wch_lo2[oh] = f32_to_bf16(r - bf16_to_f32(wch_lo[oh]));
                                     ++oh;
                                 }
         }
@@ -385,6 +389,7 @@ int build_fused_images(ls_handle* h) {
 #define UP(buf, vec) if ((rc = upload(h, h->buf, (vec).data(), (vec).size() * sizeof(float))) != LS_OK) return rc
     if ((rc = upload(h, h->wch_hi_img, wch_hi.data(), wch_hi.size() * sizeof(unsigned short))) != LS_OK) return rc;
     if ((rc = upload(h, h->wch_lo_img, wch_lo.data(), wch_lo.size() * sizeof(unsigned short))) != LS_OK) return rc;
+    if ((rc = upload(h, h->wch_lo2_img, wch_lo2.data(), wch_lo2.size() * sizeof(unsigned short))) != LS_OK) return rc;
     if ((rc = upload(h, h->ww_hi_img, wwh.data(), wwh.size() * sizeof(unsigned short))) != LS_OK) return rc;
     if ((rc = upload(h, h->ww_lo_img, wwl.data(), wwl.size() * sizeof(unsigned short))) != LS_OK) return rc;
     if ((rc = upload(h, h->wtok1_hi_img, wt1h.data(), wt1h.size() * sizeof(unsigned short))) != LS_OK) return rc;
@@ -397,6 +402,7 @@ int build_fused_images(ls_handle* h) {
     dw.wch_img = h->wch_img.f(); dw.bch = h->bch.f(); dw.wsum = h->lw_wsum.f();
     dw.wch_hi_img = static_cast<const unsigned short*>(h->wch_hi_img.p);
     dw.wch_lo_img = static_cast<const unsigned short*>(h->wch_lo_img.p);
+    dw.wch_lo2_img = static_cast<const unsigned short*>(h->wch_lo2_img.p);
     dw.ww_hi_img = static_cast<const unsigned short*>(h->ww_hi_img.p);
     dw.ww_lo_img = static_cast<const unsigned short*>(h->ww_lo_img.p);
     dw.ln1a = h->ln1a.f(); dw.ln1b = h->ln1b.f(); dw.ln2a = h->ln2a.f(); dw.ln2b = h->ln2b.f();
@@ -783,8 +789,10 @@ long long plan_code(const ls_handle* h) {
 }
 
 // One diffusion step of the prepared batch on the kernels decide_path chose.
-// precision 0: exact fp32 (k_step<..,0>); 1: bf16x3 inside the same one-workgroup-per-sample kernel (k_step<..,1>)
+// precision 0 (fp32): split-fp32 channel mixing on the bf16 matrix cores (k_step<..,2>); 1: bf16x3 (k_step<..,1>); 2 (fp32_mfma):
+// every contraction on the fp32 MFMA (k_step<..,0>).  The other step kernels have no split-fp32 form: modes 0 and 2 run them as fp32.
 // pair: the single-pass variant (two samples' cond pass per workgroup), legal when every guidance scale is 1
+int step_prec(const ls_handle* h) { return h->precision == LS_PRECISION_BF16X3 ? 1 : h->precision == LS_PRECISION_FP32_MFMA ? 0 : 2; }
 bool plan_applies(const ls_handle* h, const StepArgs& s, bool pair) {
     if (!h->fused) return true;                                        // batch-level kernels only
     if (s.trace) return false;                                         // the residual-stream trace exists in the fused kernel only
@@ -796,13 +804,13 @@ bool plan_applies(const ls_handle* h, const StepArgs& s, bool pair) {
 hipError_t run_step(ls_handle* h, StepArgs& s, int B, bool pair, hipStream_t st) {
     s.batch = B;
     if (!h->fused) return run_long(h, s, 0, B, st);
-    if (!plan_applies(h, s, pair)) return launch_step(h->var, h->precision == 1 ? 1 : 0, pair ? 1 : 0, s, B, st);
+    if (!plan_applies(h, s, pair)) return launch_step(h->var, step_prec(h), pair ? 1 : 0, s, B, st);
     for (int i = 0; i < h->nseg; ++i) {
         const Seg& g = h->seg[i];
         const int n = h->nseg == 1 ? B : g.n;
         hipError_t e;
         switch (g.path) {
-        case 0: s.batch = n; e = g.first == 0 ? launch_step(h->var, h->precision == 1 ? 1 : 0, pair ? 1 : 0, s, n, st) : hipErrorInvalidValue; s.batch = B; break;
+        case 0: s.batch = n; e = g.first == 0 ? launch_step(h->var, step_prec(h), pair ? 1 : 0, s, n, st) : hipErrorInvalidValue; s.batch = B; break;
         case 1: e = run_long(h, s, g.first, n, st); break;
         case 2: e = run_coop(h, s, g.first, n, pair, st); break;
         default: e = run_pass(h, s, g.first, n, pair, st); break;
@@ -918,11 +926,11 @@ PlanOut plan_steps(const PlanIn& in) {
     if (!in.fused) { o.seg[0].path = 1; return o; }
     if (in.path_mode == 1) return o;
     if (in.path_mode == 4) { o.seg[0].path = 3; return o; }
-    if (in.precision != 0 && in.path_mode != 0) return o;
+    if (in.precision == 1 && in.path_mode != 0) return o;
     if (in.path_mode == 2) { o.seg[0].path = in.have_long ? 1 : 0; return o; }
     if (in.path_mode == 3) { o.seg[0].path = 2; return o; }
     if (in.B <= 0) return o;
-    const bool bf = in.precision != 0;
+    const bool bf = in.precision == 1;      // bf16x3; the two fp32 modes share the exact-fp32 costs
     const PathCost& c = bf ? (in.ted ? kCostTedBf : kCostBeatBf) : (in.ted ? kCostTed : kCostBeat);
     const int B = in.B, np = in.pair ? 1 : 2, round = 2 * in.n_cu / np, unit = in.n_cu / np;     // round: samples of one fused round; unit: samples that put ONE pass workgroup on every CU
     const float thr = 256.0f / (float)in.n_cu;          // throughput-bound terms (measured on 256 CUs) on a smaller / larger device
@@ -1284,7 +1292,7 @@ void ls_destroy(ls_handle* h) {
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     free_graph(h);
-    DevBuf* all[] = {&h->wch_hi_img, &h->wch_lo_img, &h->ww_hi_img, &h->ww_lo_img, &h->wch_img, &h->bch, &h->ln1a, &h->ln1b, &h->ln2a, &h->ln2b, &h->ww_img, &h->btok_rows, &h->winx_img,
+    DevBuf* all[] = {&h->wch_hi_img, &h->wch_lo_img, &h->wch_lo2_img, &h->ww_hi_img, &h->ww_lo_img, &h->wch_img, &h->bch, &h->ln1a, &h->ln1b, &h->ln2a, &h->ln2b, &h->ww_img, &h->btok_rows, &h->winx_img,
                      &h->wout_img, &h->wout_reg_img, &h->bout, &h->devw, &h->win_full, &h->win_pre, &h->win_aud, &h->win_bias, &h->spk_emb, &h->ml_w, &h->ml_b,
                      &h->emo_emb, &h->te_w0, &h->te_b0, &h->te_w2, &h->te_b2, &h->pe, &h->temb, &h->temb_tmp,
                      &h->tmap_dev, &h->audio, &h->origin_x, &h->vid, &h->emo, &h->scale, &h->c1, &h->c2, &h->c3, &h->c4,
@@ -1337,9 +1345,9 @@ int ls_commit_weights(ls_handle* h) {
 
 int ls_set_precision(ls_handle* h, int mode) {
     if (!h) return LS_EINVAL;
-    if (mode != LS_PRECISION_FP32 && mode != LS_PRECISION_BF16X3)
+    if (mode != LS_PRECISION_FP32 && mode != LS_PRECISION_BF16X3 && mode != LS_PRECISION_FP32_MFMA)
         return fail(h, LS_EINVAL, "unknown precision mode %d", mode);
-    if (!h->fused && mode != LS_PRECISION_FP32) return fail(h, LS_EUNSUPPORTED, "the long-sequence path (nframes != %d) is exact fp32 only", kT);
+    if (!h->fused && mode == LS_PRECISION_BF16X3) return fail(h, LS_EUNSUPPORTED, "the long-sequence path (nframes != %d) is exact fp32 only", kT);
     if (mode != h->precision) free_graph(h);
     h->precision = mode;
     if (h->prepared) {      // the plan may move to kernels whose workspaces the last ls_prepare did not allocate: prepare again then
@@ -1384,7 +1392,7 @@ int ls_set_path(ls_handle* h, int mode) {
         return LS_OK;
     }
     if (mode >= 3 && !h->fused) return fail(h, LS_EUNSUPPORTED, "nframes != %d has neither the sample-split nor the one-pass-per-workgroup kernel", kT);
-    if (mode == 3 && h->precision != 0) return fail(h, LS_EUNSUPPORTED, "the sample-split kernel is exact fp32 only");
+    if (mode == 3 && h->precision == LS_PRECISION_BF16X3) return fail(h, LS_EUNSUPPORTED, "the sample-split kernel is exact fp32 only");
     if (mode == 3 && 2 * h->cfg.layers + 2 > (int)kCoopEpochStride)
         return fail(h, LS_EUNSUPPORTED, "the sample-split kernel tags its hand-offs with %u values per launch: %d layers need %d", kCoopEpochStride, h->cfg.layers, 2 * h->cfg.layers + 2);
     if (mode == 3 && h->coop_groups_max < 2)

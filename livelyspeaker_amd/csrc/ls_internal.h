@@ -35,6 +35,7 @@ struct DevWeights {
     // v_mfma_f32_16x16x32_bf16 (lane (n, g) holds k = 32q + 8g .. +7): [L][8][2 passes][16 q][2 cb][64 lanes][8]
     const unsigned short* wch_hi_img;
     const unsigned short* wch_lo_img;
+    const unsigned short* wch_lo2_img;   // split-fp32 (PREC 2): third plane, W' = hi + lo + lo2 exactly (lo2 = bf16(W' - hi - lo))
     const unsigned short* ww_hi_img;   // [L][5][KS][64][8]  block-diagonal token weights, bf16 hi / lo planes
     const unsigned short* ww_lo_img;
     const float* ln1a; const float* ln1b; const float* ln2a; const float* ln2b;   // [L][512]
@@ -211,7 +212,8 @@ hipError_t launch_step_coop(Variant v, int ncb, const StepArgs& a, int nsamples,
 hipError_t init_pass_kernels();
 hipError_t launch_step_pass(Variant v, int prec, int waves, const StepArgs& a, int nsamples, hipStream_t st);
 
-// prec: 0 = exact fp32 MFMA (default), 1 = bf16x3 split-precision channel mixing (opt-in, parity-gated at 1e-3)
+// prec: 0 = exact fp32 MFMA, 1 = bf16x3 split-precision channel mixing (opt-in, parity-gated at 1e-3), 2 = split-fp32 channel
+// mixing (bf16 MFMAs on exactly split operands; launch_step only, the fp32 default of the fused kernel)
 // pair: 0 = CFG (cond + uncond pass of one sample per workgroup), 1 = single pass (guidance scale 1: two samples per workgroup)
 hipError_t launch_step(Variant v, int prec, int pair, const StepArgs& a, int batch, hipStream_t st);
 hipError_t launch_step_ted(int prec, int pair, const StepArgs& a, int batch, hipStream_t st);     // ls_step.hip

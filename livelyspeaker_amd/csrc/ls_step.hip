@@ -14,7 +14,8 @@ size_t step_lds_bytes(Variant v) {
 hipError_t init_step_kernels_ted() {
     const void* ks[] = {reinterpret_cast<const void*>(k_step<35, 1, 27, 0>), reinterpret_cast<const void*>(k_step<35, 1, 27, 1>),
                         reinterpret_cast<const void*>(k_step<35, 1, 27, 0, 1>), reinterpret_cast<const void*>(k_step<35, 1, 27, 0, 0, 1>),
-                        reinterpret_cast<const void*>(k_step<35, 1, 27, 1, 0, 1>)};
+                        reinterpret_cast<const void*>(k_step<35, 1, 27, 1, 0, 1>),
+                        reinterpret_cast<const void*>(k_step<35, 1, 27, 2>), reinterpret_cast<const void*>(k_step<35, 1, 27, 2, 0, 1>)};
     for (const void* k : ks) {
         hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds_bytes(kTED));
         if (e != hipSuccess) return e;
@@ -31,8 +32,11 @@ hipError_t launch_step_ted(int prec, int pair, const StepArgs& a, int batch, hip
     const size_t lds = step_lds_bytes(kTED);
     if (pair) {
         const dim3 grid((batch + 1) / 2);
-        if (prec == 0) hipLaunchKernelGGL((k_step<35, 1, 27, 0, 0, 1>), grid, dim3(512), lds, st, a);
+        if (prec == 2) hipLaunchKernelGGL((k_step<35, 1, 27, 2, 0, 1>), grid, dim3(512), lds, st, a);
+        else if (prec == 0) hipLaunchKernelGGL((k_step<35, 1, 27, 0, 0, 1>), grid, dim3(512), lds, st, a);
         else hipLaunchKernelGGL((k_step<35, 1, 27, 1, 0, 1>), grid, dim3(512), lds, st, a);
+    } else if (prec == 2) {
+        hipLaunchKernelGGL((k_step<35, 1, 27, 2>), dim3(batch), dim3(512), lds, st, a);
     } else if (prec == 0) {
         hipLaunchKernelGGL((k_step<35, 1, 27, 0>), dim3(batch), dim3(512), lds, st, a);
     } else {

@@ -86,6 +86,47 @@ __device__ __forceinline__ float wload1(wrsrc_t r, int lane_bytes, int wave_byte
 }
 
 
+// Split-fp32 (k_step PREC 2): x = hi + mid + lo exactly, each part round-to-nearest-even bf16 (v_cvt_pk_bf16_f32):
+// hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid); both differences are exact in fp32.  Inf / NaN give NaN residuals.
+// Written pair by pair so that each rounding is one v_cvt_pk_bf16_f32 for two values and each part goes back to fp32 with one
+// shift or mask: 11 VALU per pair (a per-element form compiles to ~15).
+__device__ __forceinline__ unsigned cvt_pk_bf16(float x, float y) {
+    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){x, y}, bf2));
+}
+__device__ __forceinline__ float bf16_lo_f32(unsigned p) { return __builtin_bit_cast(float, p << 16); }
+__device__ __forceinline__ float bf16_hi_f32(unsigned p) { return __builtin_bit_cast(float, p & 0xFFFF0000u); }
+__device__ __forceinline__ void split3_bf16(f4 x0, f4 x1, bf8& hi, bf8& mid, bf8& lo) {
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    u4 h, m, l;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float v0 = e < 2 ? x0[2 * e] : x1[2 * e - 4], v1 = e < 2 ? x0[2 * e + 1] : x1[2 * e - 3];
+        h[e] = cvt_pk_bf16(v0, v1);
+        const float r0 = v0 - bf16_lo_f32(h[e]), r1 = v1 - bf16_hi_f32(h[e]);
+        m[e] = cvt_pk_bf16(r0, r1);
+        l[e] = cvt_pk_bf16(r0 - bf16_lo_f32(m[e]), r1 - bf16_hi_f32(m[e]));
+    }
+    hi = __builtin_bit_cast(bf8, h);
+    mid = __builtin_bit_cast(bf8, m);
+    lo = __builtin_bit_cast(bf8, l);
+}
+// The partial products kept, as (weight part, operand part) with 0 = hi, 1 = mid, 2 = lo, in accumulation order (smallest
+// first, hi.hi last).  6 terms (default): every term with i + j <= 2; each dropped one is at most 2^-24 of |W'||u| (2^-8 x 2^-16),
+// the three together at most ~2^-23, the order of the fp32 product's own rounding.
+// 9 terms (-DLS_SPLIT_TERMS=9): every term, products exact.
+#ifndef LS_SPLIT_TERMS
+#define LS_SPLIT_TERMS 6
+#endif
+#if LS_SPLIT_TERMS == 9
+constexpr int kSplitTerms = 9;
+constexpr int kSplitA[9] = {2, 2, 1, 2, 1, 0, 1, 0, 0}, kSplitB[9] = {2, 1, 2, 0, 1, 2, 0, 1, 0};
+#else
+static_assert(LS_SPLIT_TERMS == 6, "LS_SPLIT_TERMS is 6 or 9");
+constexpr int kSplitTerms = 6;
+constexpr int kSplitA[6] = {2, 1, 0, 1, 0, 0}, kSplitB[6] = {0, 1, 2, 0, 1, 0};
+#endif
+
 // which (tile, k step) pairs of the block-diagonal token-mixing GEMM touch a non-zero block
 __host__ __device__ constexpr bool tokmix_needed(int S, int t, int m) {
     const int R = 2 * S;

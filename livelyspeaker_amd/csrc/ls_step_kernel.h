@@ -11,7 +11,8 @@
 //     R = 2*S rows (70 TED / 72 BEAT) -> 5 token tiles of 16, so the CFG lerp and the sampler update fuse
 //     into the same launch and nothing but x_t (3.7 KB) round-trips through HBM between steps.
 //   * every contraction runs on v_mfma_f32_16x16x4_f32 (exact fp32; bf16/fp16 inputs fail the 1e-3
-//     parity budget) in the TRANSPOSED form D[channel][token]: channels on the
+//     parity budget) -- except the channel mixing of PREC 2, the fp32 default, which runs on
+//     v_mfma_f32_16x16x32_bf16 with both operands split exactly into three bf16 parts -- in the TRANSPOSED form D[channel][token]: channels on the
 //     MFMA M axis, tokens on N.  The MFMA C/D layout (lane&15 = token, 4*(lane>>4)+reg = channel) is then
 //     ALSO the layout of the residual stream, which therefore lives in registers for the whole forward:
 //     wave w owns channels [64w, 64w+64) of all 80 rows = 80 VGPRs.
@@ -659,6 +660,71 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
                         if (valid_of(t)) {
                             X[2 * p + c2][t] = silu_acc4(acc[c2][t], X[2 * p + c2][t]);
                         }
+                if (p == 0) stamp(7 + 8 * l);
+            }
+        } else if constexpr (PREC == 2) {
+            // ---- split-fp32: W'.u with both operands split exactly into three bf16 parts, a = a0 + a1 + a2 (round-to-nearest:
+            // |a1| <= 2^-8 |a|, |a2| <= 2^-16 |a|); every bf16 x bf16 product is exact in fp32.  The weight planes come split from the
+            // host (wch_hi / wch_lo / wch_lo2); the operand stays fp32 in LDS (its three planes would not fit) and each B fragment is
+            // split in registers after its ds_read (split3_bf16, 44 VALU per 8 values).  The terms kept (kSplitA / kSplitB,
+            // ls_step_common.h) are accumulated smallest first so hi.hi lands last.  All 5 token tiles run on v_mfma_f32_16x16x32_bf16 (pad rows read the clamped last row, their
+            // outputs are dropped), no ragged-row VALU path: the bf16 MFMAs leave the fp32 lanes to the split.
+            // Non-finite operands: Inf - Inf residuals are NaN, so an Inf in u or W' gives NaN (the fp32 MFMA may give Inf).
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                fresh();
+                f4 acc[2][kNT];
+#pragma unroll
+                for (int c2 = 0; c2 < 2; ++c2) {
+                    const f4 bc = wload4(wrsrc(a.W->bch), chw * 4, (l * kD + 16 * (2 * p + c2)) * 4);
+#pragma unroll
+                    for (int t = 0; t < kNT; ++t) acc[c2][t] = bc;
+                }
+                const wrsrc_t wr0 = wrsrc(a.W->wch_hi_img), wr1 = wrsrc(a.W->wch_lo_img), wr2 = wrsrc(a.W->wch_lo2_img);
+                const int wsb = (((l * kWaves + w) * 2 + p) * 16) * 2 * 1024;
+                typedef const __attribute__((address_space(3))) f4* ldsp4;
+                ldsp4 ub[kNT];                            // lane (token, g) reads k = 32q + 8g .. +7 of its (clamped) row
+#pragma unroll
+                for (int t = 0; t < kNT; ++t) ub[t] = (ldsp4)(U + rowc_of(t) * kUStride + 8 * g);
+                bf8 An[3][2];
+#pragma unroll
+                for (int c2 = 0; c2 < 2; ++c2) {
+                    An[0][c2] = wload8h(wr0, lane * 16, wsb + c2 * 1024);
+                    An[1][c2] = wload8h(wr1, lane * 16, wsb + c2 * 1024);
+                    An[2][c2] = wload8h(wr2, lane * 16, wsb + c2 * 1024);
+                }
+                if (!LS_ABLATED(a, 1))
+#pragma unroll 1
+                for (int q = 0; q < 16; ++q) {
+                    bf8 A[3][2];
+#pragma unroll
+                    for (int s = 0; s < 3; ++s)
+#pragma unroll
+                        for (int c2 = 0; c2 < 2; ++c2) A[s][c2] = An[s][c2];
+                    const int qn = (q + 1 < 16) ? q + 1 : 15;
+#pragma unroll
+                    for (int c2 = 0; c2 < 2; ++c2) {
+                        An[0][c2] = wload8h(wr0, lane * 16, wsb + (qn * 2 + c2) * 1024);
+                        An[1][c2] = wload8h(wr1, lane * 16, wsb + (qn * 2 + c2) * 1024);
+                        An[2][c2] = wload8h(wr2, lane * 16, wsb + (qn * 2 + c2) * 1024);
+                    }
+#pragma unroll
+                    for (int t = 0; t < kNT; ++t) {
+                        bf8 B[3];
+                        split3_bf16(ub[t][8 * q], ub[t][8 * q + 1], B[0], B[1], B[2]);
+#pragma unroll
+                        for (int i = 0; i < kSplitTerms; ++i)
+#pragma unroll
+                            for (int c2 = 0; c2 < 2; ++c2)
+                                acc[c2][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[kSplitA[i]][c2], B[kSplitB[i]], acc[c2][t], 0, 0, 0);
+                    }
+                }
+                fresh();
+#pragma unroll
+                for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+                    for (int t = 0; t < kNT; ++t)
+                        if (valid_of(t)) X[2 * p + c2][t] = silu_acc4(acc[c2][t], X[2 * p + c2][t]);
                 if (p == 0) stamp(7 + 8 * l);
             }
         } else {

@@ -122,8 +122,9 @@ class RAG(nn.Module):
         #: reuse the prepared conditioning when the same ``y`` tensors are passed again (the sampling loop calls
         #: the model T times with one ``y``); set False to re-run the once-per-call stage on every call.
         self.cache_conditioning = True
-        #: 'fp32' = exact fp32 MFMA (default, what parity/bench numbers refer to); 'bf16x3' = opt-in split-precision
-        #: channel mixing (3 bf16 MFMAs per fp32 product, ~2^-16 relative; parity-tested against the 1e-3 contract)
+        #: 'fp32' = default, what parity/bench numbers refer to (the fused kernel's channel mixing as fp32-accurate split-bf16
+        #: MFMAs, fp32 MFMA elsewhere); 'fp32_mfma' = fp32 MFMA everywhere; 'bf16x3' = opt-in split-precision channel mixing
+        #: (3 bf16 MFMAs per fp32 product, ~2^-16 relative; parity-tested against the 1e-3 contract)
         self.precision = "fp32"
         #: which kernels the diffusion steps run on: None = the engine's default ("auto": chosen per batch from a step-time model --
         #: the sample-split kernel for small batches, batch-level kernels in the middle, one workgroup per sample from ~176 clips),
