@@ -59,7 +59,8 @@ def make_inputs(cfg, B, device="cuda:0", guidance_param=2.5, seed=0):
 
 def infer(model, diffusion, sag_decoder, batch, cond, skip_steps=80, seed=233, noise_source="torch_cpu"):
     """SAG decode -> guided refinement (:88-113).  noise_source 'torch_cpu' replays the reference's CPU random stream draw by
-    draw (slow: ~1.3 s of host RNG at B=512); 'philox' generates the noise inside the step kernel."""
+    draw (slow: ~1.3 s of host RNG at B=512); 'torch_device' replays the reference's random stream of a GPU run, generated on the
+    device inside the loop; 'philox' generates the noise inside the step kernel."""
     diffusion.noise_source = noise_source
     B = batch["x"].shape[0]
     if hasattr(model, "prefetch_condition"):          # optional: the refinement's once-per-call stage overlaps the SAG decode
@@ -102,15 +103,20 @@ def infer_pipelined(models, diffusion, sag_decoder, batches, conds, skip_steps=8
 
 
 def main():
+    noise_source = "philox"
+    if "--noise-source" in sys.argv:                                                        # philox | torch_device | torch_cpu
+        i = sys.argv.index("--noise-source")
+        noise_source = sys.argv[i + 1]
+        del sys.argv[i:i + 2]
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
     if len(sys.argv) > 2:                                                                   # python examples/livelyspeaker_ted.py B N: N batches, pipelined
         return main_pipelined(B, int(sys.argv[2]))
     cfg, model, diffusion, sag_decoder, evaluator = build()
     vec_seq, batch, cond = make_inputs(cfg, B)
-    infer(model, diffusion, sag_decoder, batch, cond, noise_source="philox")                # warm-up (graph capture, allocations)
+    infer(model, diffusion, sag_decoder, batch, cond, noise_source=noise_source)            # warm-up (graph capture, allocations)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    decoded, sample = infer(model, diffusion, sag_decoder, batch, cond, noise_source="philox")
+    decoded, sample = infer(model, diffusion, sag_decoder, batch, cond, noise_source=noise_source)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     post = ted_postprocess(sample)                                                          # test_RAG_ted.py:84-111
@@ -119,7 +125,7 @@ def main():
         evaluator.push_samples(post["aligned_motions"][i:i + 64], real[i:i + 64])
     fgd, feat_dist = evaluator.get_scores() if B > 32 else (float("nan"), float("nan"))
     n_beats = sum(len(b) for b in post["motion_beat_times"])
-    print(f"B={B}: SAG decode + 20-step guided refinement {dt * 1e3:.1f} ms ({B * 34 / dt:.0f} pose-frames/s); "
+    print(f"B={B} ({noise_source}): SAG decode + 20-step guided refinement {dt * 1e3:.1f} ms ({B * 34 / dt:.0f} pose-frames/s); "
           f"motion beats {n_beats}; FGD {fgd:.4f}, feature distance {feat_dist:.4f} (synthetic weights: numbers are not quality)")
     assert bool(torch.isfinite(sample).all())
 

@@ -38,7 +38,10 @@ enum {
 };
 
 enum { LS_SAMPLER_DDPM = 0, LS_SAMPLER_DDIM = 1 };
-enum { LS_NOISE_TAPE = 0, LS_NOISE_PHILOX = 1 };
+/* TORCH_DEVICE: the reference's draws as a GPU run of it makes them, from torch's device generator (Philox4x32-10 behind torch's
+ * grid-stride launch geometry, ls_torch_randn), generated on the device inside the loop: bitwise torch.randn / randn_like on the
+ * handle's GPU, in the reference's order, shapes and memory orders (as the TAPE tapes of the torch_cpu mode are drawn). */
+enum { LS_NOISE_TAPE = 0, LS_NOISE_PHILOX = 1, LS_NOISE_TORCH_DEVICE = 2 };
 /* Arithmetic of the channel-mixing GEMM (92 % of the FLOPs).
  * FP32 (default): in the fused step kernel, split-fp32: both fp32 operands split exactly into three bf16 parts
  *   (a = a0 + a1 + a2, round-to-nearest splits) and the partial products of v_mfma_f32_16x16x32_bf16 kept down to the
@@ -108,7 +111,7 @@ typedef struct ls_sample_args {
     int32_t sampler;            /* LS_SAMPLER_*                                     */
     int32_t noise_mode;         /* LS_NOISE_*                                       */
     int32_t skip_timesteps;     /* gaussian_diffusion.py:712 / :982                 */
-    int32_t const_noise;        /* :545-546 / :706-707 (TAPE mode only)             */
+    int32_t const_noise;        /* :545-546 / :706-707 (TAPE and TORCH_DEVICE modes) */
     int32_t on_device;
     int32_t use_graph;          /* 1: capture the step loop in a hipGraph and replay */
     int32_t clip_denoised;      /* clamp pred_xstart to [-1,1] (callers pass False)  */
@@ -121,12 +124,17 @@ typedef struct ls_sample_args {
     int32_t n_dump;             /* dump_steps (DDPM only, :660-671)                 */
     const int32_t* dump_steps;  /* executed-step counters (0 = first executed step), host memory */
     float* dump_out;            /* [n_dump, B, J, F, T] pred_xstart                 */
-    const float* x_init;        /* [B,J,F,T] x_T = the loop's first randn; NULL only with PHILOX */
+    const float* x_init;        /* [B,J,F,T] x_T = the loop's first randn; NULL only with PHILOX or TORCH_DEVICE (the loop draws x_T;
+                                   given = the reference's `noise=`, no x_T draw) */
     const float* init_image;    /* [B,J,F,T] or NULL (zeros when skip_timesteps>0)  */
     const float* eps_tape;      /* TAPE: [n_exec, 2, B, latent_dim] style eps (cond, uncond) */
     const float* noise_tape;    /* TAPE: [n_exec, B, J, F, T] per-step randn_like(x) */
-    uint64_t seed;              /* PHILOX key                                       */
-    uint64_t sample_offset;     /* PHILOX: global index of sample 0 (shard-invariant streams) */
+    uint64_t seed;              /* PHILOX key; TORCH_DEVICE: the torch device generator's seed (initial_seed())          */
+    uint64_t sample_offset;     /* PHILOX: global index of sample 0 (shard-invariant streams); TORCH_DEVICE: the generator's
+                                   Philox offset (get_offset(), a multiple of 4) before the loop's first draw.  The draws of
+                                   the loop advance it by a total that depends on the shapes only (ls_torch_randn_advance per
+                                   draw); the caller sets the generator there afterwards.  Both values are read from device
+                                   memory by the captured loop: a replay takes new ones without a recapture. */
     float* out;                 /* [B, J, F, T]                                     */
     /* Segmented TAPE mode (seg_count > 0): this call runs the executed-step counters [seg_begin, seg_begin + seg_count) of the loop
      * and eps_tape / noise_tape hold THOSE steps only ([seg_count, 2, B, D] / [seg_count, B, J, F, T]) -- the reference's
@@ -269,6 +277,18 @@ int ls_q_sample(ls_handle* h, int index, int on_device, size_t n, const float* x
 /* The x_T draw of PHILOX mode on its own (what ls_sample uses when x_init == NULL): out [batch,J,F,T] ~ N(0,1),
  * stream keyed by (seed, sample_offset + b). Lets tests check the device RNG's moments and shard-invariance. */
 int ls_philox_x_init(ls_handle* h, int batch, uint64_t seed, uint64_t sample_offset, int on_device, float* out);
+
+/* ---- torch's device normal stream (LS_NOISE_TORCH_DEVICE) -----------------------------------------------------------------
+ * ls_torch_randn_advance: how far torch.randn(n) (float32) on a device of n_cu compute units and max_threads_per_cu threads per CU
+ * (hipDeviceProp multiProcessorCount / maxThreadsPerMultiProcessor) moves the device generator's offset: 4 * ceil(n / (4 * 256 * G)),
+ * G = min(ceil(n / 256), n_cu * (max_threads_per_cu / 256)); 0 for n <= 0 or a geometry torch cannot launch.  Host arithmetic only.
+ * ls_torch_randn: fill DEVICE memory out_device[n] with what torch.randn(n) draws from a generator at (seed, offset) on the handle's
+ * GPU (n < 2^31, offset a multiple of 4); the caller moves the generator on by ls_torch_randn_advance.  no_sync: do not wait for it.
+ * ls_set_torch_ring_bytes: device memory a TORCH_DEVICE loop keeps its draws in (default 256 MB): the ring holds as many steps as fit
+ * (at least one) and is refilled by one generator launch per that many steps. */
+uint64_t ls_torch_randn_advance(int64_t n, int32_t n_cu, int32_t max_threads_per_cu);
+int ls_torch_randn(ls_handle* h, uint64_t seed, uint64_t offset, int64_t n, float* out_device, int no_sync);
+int ls_set_torch_ring_bytes(ls_handle* h, uint64_t bytes);
 
 /* Read back a prepared intermediate into host memory (parity tests of the once-per-call stages):
  * "audio_feat" [B,T,256], "static_c"/"static_u" [B,T,D], "z_mu"/"z_logvar"/"z_std" [B,D],

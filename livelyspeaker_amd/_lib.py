@@ -18,7 +18,7 @@ c_i64p = C.POINTER(C.c_int64)
 c_i32p = C.POINTER(C.c_int32)
 
 LS_SAMPLER_DDPM, LS_SAMPLER_DDIM = 0, 1
-LS_NOISE_TAPE, LS_NOISE_PHILOX = 0, 1
+LS_NOISE_TAPE, LS_NOISE_PHILOX, LS_NOISE_TORCH_DEVICE = 0, 1, 2
 LS_PRECISION_FP32, LS_PRECISION_BF16X3 = 0, 1
 
 
@@ -103,7 +103,7 @@ class LsEvalConfig(C.Structure):
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
            "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_sample", "ls_forward", "ls_step", "ls_q_sample", "ls_read",
-           "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
+           "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms", "ls_ted_post", "ls_beat_post",
            "ls_train_create", "ls_train_destroy", "ls_train_last_error", "ls_train_set_schedule", "ls_train_param_count",
            "ls_train_flat_size", "ls_train_param_info", "ls_train_set_weight", "ls_train_get_weight", "ls_train_forward_backward",
@@ -131,6 +131,11 @@ def use_library(path: str) -> None:
 
 def library_path() -> str:
     return _lib_override or _build.LIB
+
+
+def torch_randn_advance(n, n_cu, max_threads_per_cu) -> int:
+    """Offset advance of torch's device generator for one float32 ``torch.randn(n)`` (ls_torch_randn_advance; no GPU needed)."""
+    return int(load_library().ls_torch_randn_advance(int(n), int(n_cu), int(max_threads_per_cu)))
 
 
 def load_library(build_if_missing: bool = True):
@@ -179,6 +184,10 @@ def load_library(build_if_missing: bool = True):
         getattr(lib, fn).argtypes = [C.c_void_p]
         getattr(lib, fn).restype = C.c_void_p
     lib.ls_philox_x_init.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
+    lib.ls_torch_randn_advance.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    lib.ls_torch_randn_advance.restype = C.c_uint64
+    lib.ls_torch_randn.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_int]
+    lib.ls_set_torch_ring_bytes.argtypes = [C.c_void_p, C.c_uint64]
     lib.ls_set_precision.argtypes = [C.c_void_p, C.c_int]
     lib.ls_set_path.argtypes = [C.c_void_p, C.c_int]
     lib.ls_plan_query.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]
@@ -545,9 +554,12 @@ class Engine:
 
     def sample(self, sampler=LS_SAMPLER_DDPM, x_init=None, eps_tape=None, noise_tape=None, init_image=None,
                skip_timesteps=0, eta=0.0, const_noise=False, dump_steps=None, philox_seed=None, sample_offset=0,
-               use_graph=True, clip_denoised=False, device_out=False, two_pass_always=False, segment=None, inpaint=None):
-        """Run the whole loop. TAPE mode when tapes are given, PHILOX mode when ``philox_seed`` is.
-        Outputs are torch CUDA tensors if any input is one (or ``device_out``), else numpy."""
+               use_graph=True, clip_denoised=False, device_out=False, two_pass_always=False, segment=None, inpaint=None,
+               torch_state=None, torch_ring_bytes=256 << 20):
+        """Run the whole loop. TAPE mode when tapes are given, PHILOX mode when ``philox_seed`` is, TORCH_DEVICE mode when
+        ``torch_state`` = (seed, offset) of torch's device generator is (the loop makes torch's device draws itself; ``x_init`` None =
+        it draws x_T too; the caller moves the generator on).  Outputs are torch CUDA tensors if any input is one (or ``device_out``),
+        else numpy."""
         inp = inpaint or (None, None, None, False)     # (mask, motion, q_sample noise tape or None, re-noise?): the inpainting branch
         members = [x_init, eps_tape, noise_tape, init_image, inp[1]]
         if device_out:
@@ -564,7 +576,11 @@ class Engine:
             n_tape, last = a.seg_count, a.seg_begin + a.seg_count == n_exec
         else:
             n_tape, last = n_exec, True
-        if philox_seed is None:
+        if torch_state is not None:
+            a.noise_mode = LS_NOISE_TORCH_DEVICE
+            a.seed, a.sample_offset = int(torch_state[0]) & 0xFFFFFFFFFFFFFFFF, int(torch_state[1])
+            self._check(self.lib.ls_set_torch_ring_bytes(self.h, int(torch_ring_bytes)), "ls_set_torch_ring_bytes")
+        elif philox_seed is None:
             a.noise_mode = LS_NOISE_TAPE
             a.eps_tape = m.f32(eps_tape, (n_tape, 2, self.batch, self.D))
             a.noise_tape = m.f32(noise_tape, (n_tape,) + self._xshape())
@@ -600,6 +616,17 @@ class Engine:
         n = int(np.prod(x_start.shape))
         m.ready()
         self._check(self.lib.ls_q_sample(self.h, index, int(m.on_device), n, m.f32(x_start), m.f32(noise), pout), "ls_q_sample")
+        return out
+
+    def torch_randn(self, seed, offset, out):
+        """Fill the CUDA float32 tensor ``out`` (contiguous, on this engine's GPU) with what ``torch.randn(out.numel())`` draws from a
+        device generator at (seed, offset); the generator is neither read nor moved.  Waits for the GPU."""
+        import torch
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()):
+            raise EngineError("torch_randn: out must be a contiguous float32 CUDA tensor")
+        torch.cuda.synchronize(out.device)
+        self._check(self.lib.ls_torch_randn(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), out.numel(), C.c_void_p(out.data_ptr()), 0),
+                    "ls_torch_randn")
         return out
 
     def philox_x_init(self, batch, seed, sample_offset=0) -> np.ndarray:

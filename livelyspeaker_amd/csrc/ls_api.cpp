@@ -86,6 +86,7 @@ struct ls_handle {
     unsigned coop_launches = 0;                        // launches since the granule words were zeroed: epoch = 64 * ordinal
     unsigned coop_err_host = 0;
     int n_cu = 256;         // compute units of the device (hipDeviceProp.multiProcessorCount): residency of the sample-split kernel, round sizes of the plans
+    int max_thr_cu = 2048;  // hipDeviceProp.maxThreadsPerMultiProcessor: with n_cu, the geometry of torch's randn launches (LS_NOISE_TORCH_DEVICE)
     int coop_groups_max = kCoopMaxGroups, coop_groups = 0;   // (sample, pass) groups per launch: cap of the 8-slice form (two workgroups per CU, eight per group), and what the workspaces hold
     int coop_ncb = 0;       // slicing of the sample-split kernel: 0 = by the step-time model; 1 | 2 | 4 = 8 | 4 | 2 slice workgroups per (sample, pass) (ls_set_path 8 | 6 | 7)
 #ifndef LS_MIX_POSE_DEFAULT
@@ -147,6 +148,10 @@ struct ls_handle {
     DevBuf eps_tape, noise_tape;
     DevBuf inp_m8, inp_maskf, inp_motion, inp_tape;     // inpainting branch: mask bytes / mask as 0-1 floats and motion in the internal layout, q_sample noise tape
     DevBuf eps_slot[2], noise_slot[2], coef;
+    // LS_NOISE_TORCH_DEVICE: a ring of K steps' draws (eps [K][2][B][D], noise [K][B][J][F][T], inpainting re-noise [K][B][J][F][T]),
+    // refilled by one generator launch per K steps inside the loop; K = what fits in trng_ring_bytes (ls_set_torch_ring_bytes)
+    DevBuf trng_eps, trng_noise, trng_inz;
+    size_t trng_ring_bytes = (size_t)256 << 20;
     std::string coef_key;   // (sampler, eta, schedule) the per-index coefficient table `coef` was built for
 
     // cached graph of the step loop
@@ -1216,6 +1221,7 @@ int ls_create(const ls_config* cfg, ls_handle** out) {
         e = hipGetDeviceProperties(&prop, cfg->device);
         if (e != hipSuccess) { delete h; return fail(nullptr, LS_EHIP, "hipGetDeviceProperties(%d): %s", cfg->device, hipGetErrorString(e)); }
         h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        h->max_thr_cu = prop.maxThreadsPerMultiProcessor;
         h->coop_groups_max = 2 * h->n_cu / 8 < kCoopMaxGroups ? 2 * h->n_cu / 8 : kCoopMaxGroups;       // every slice of a launch must be resident: they wait for each other
         h->timing.n_cus = h->n_cu;
     }
@@ -1316,6 +1322,7 @@ void ls_destroy(ls_handle* h) {
     }
     h->coef.release();
     h->inp_m8.release(); h->inp_maskf.release(); h->inp_motion.release(); h->inp_tape.release();
+    h->trng_eps.release(); h->trng_noise.release(); h->trng_inz.release();
     if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1785,14 +1792,17 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
     if (!h->prepared) return fail(h, LS_ESTATE, "ls_sample before ls_prepare");
     if (!h->have_sched) return fail(h, LS_ESTATE, "ls_sample before ls_set_schedule");
     if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM) return fail(h, LS_EINVAL, "bad sampler");
-    if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EINVAL, "bad noise_mode");
+    if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX && a->noise_mode != LS_NOISE_TORCH_DEVICE)
+        return fail(h, LS_EINVAL, "bad noise_mode");
     if (a->skip_timesteps < 0 || a->skip_timesteps >= h->n_steps) return fail(h, LS_EINVAL, "skip_timesteps out of range");
     if (a->seg_count > 0) return sample_segment(h, a);
     h->seg_next = -1;
     if (!a->out) return fail(h, LS_EINVAL, "ls_sample: null out");
     const bool tape = a->noise_mode == LS_NOISE_TAPE;
+    const bool tdev = a->noise_mode == LS_NOISE_TORCH_DEVICE;
     if (tape && (!a->x_init || !a->eps_tape || !a->noise_tape)) return fail(h, LS_EINVAL, "TAPE mode needs x_init, eps_tape and noise_tape");
-    if (!tape && a->const_noise) return fail(h, LS_EUNSUPPORTED, "const_noise is supported in TAPE mode only");
+    if (!tape && !tdev && a->const_noise) return fail(h, LS_EUNSUPPORTED, "const_noise is supported in TAPE and TORCH_DEVICE modes only");
+    if (tdev && (a->sample_offset & 3)) return fail(h, LS_EINVAL, "TORCH_DEVICE: the generator offset %llu is not a multiple of 4", (unsigned long long)a->sample_offset);
     if (a->n_dump > 0 && (a->sampler != LS_SAMPLER_DDPM || !a->dump_steps || !a->dump_out))
         return fail(h, LS_EINVAL, "dump_steps: DDPM only (ddim_sample_loop raises NotImplementedError, gaussian_diffusion.py:919-920)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1809,8 +1819,19 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
     if ((rc = advance_tags(h, st)) != LS_OK) return rc;          // uploads call_host with this call's tag base
 
     // x_T (gaussian_diffusion.py:700-707 / :972-977)
+    TorchDrawArgs tda{};            // TORCH_DEVICE: the per-step draws (filled in below), x_T's draw first when the call makes it
+    tda.call = static_cast<const CallParams*>(h->callp.p);
+    tda.B = B; tda.JF = JF; tda.T = h->T; tda.last_step = n_exec - 1;
+    const unsigned long long x_adv = (tdev && !a->x_init) ? torch_randn_advance((long long)nelem, h->n_cu, h->max_thr_cu, nullptr) : 0ull;
     if (a->x_init) {
         if ((rc = ingest(h, h->xio, a->x_init, nx, od)) != LS_OK) return rc;
+        HIPCHK(h, launch_to_internal(h->xio.f(), h->xa.f(), B, JF, st, h->T));
+    } else if (tdev) {
+        TorchDrawArgs xa = tda;     // randn(*shape) at the generator's offset, then (const_noise) [[0]].repeat(B, 1, 1, 1)
+        xa.k0 = 0; xa.nsteps = 1; xa.ndraw = 1; xa.last_step = -1;
+        xa.d[0] = torch_draw(h->xio.f(), 0, (long long)nelem, h->n_cu, h->max_thr_cu, 0, 0);
+        HIPCHK(h, launch_torch_draws(xa, st));
+        if (a->const_noise) HIPCHK(h, launch_bcast_first(h->xio.f(), B, JF * h->T, st));
         HIPCHK(h, launch_to_internal(h->xio.f(), h->xa.f(), B, JF, st, h->T));
     } else {
         HIPCHK(h, launch_randn_fill(h->xa.f(), B, JF, static_cast<const CallParams*>(h->callp.p), 0u, st, h->T));
@@ -1848,6 +1869,29 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
         HIPCHK(h, h->fwd_cfg.ensure(nx));
         if (oldc != h->fwd_cfg.p) free_graph(h);
     }
+    int ring_k = 0;                 // TORCH_DEVICE: steps per ring refill
+    if (tdev) {
+        const size_t eps_step = (size_t)2 * B * kD;
+        const size_t per_step = (eps_step + nelem * (inp_noised ? 2 : 1)) * sizeof(float);
+        const size_t fit = h->trng_ring_bytes / per_step;
+        ring_k = fit < 1 ? 1 : fit > (size_t)n_exec ? n_exec : (int)fit;
+        const void* old[3] = {h->trng_eps.p, h->trng_noise.p, h->trng_inz.p};
+        HIPCHK(h, h->trng_eps.ensure(eps_step * ring_k * sizeof(float)));
+        HIPCHK(h, h->trng_noise.ensure(nx * ring_k));
+        if (inp_noised) HIPCHK(h, h->trng_inz.ensure(nx * ring_k));
+        if (old[0] != h->trng_eps.p || old[1] != h->trng_noise.p || old[2] != h->trng_inz.p) free_graph(h);
+        // per step, in the reference's order: the style eps of the cond and the uncond pass (RAG.py:10-13, 120: randn_like of a
+        // [B, 1, 512] std), the inpainting branch's q_sample re-noise while t > 0 (gaussian_diffusion.py:318), the step noise randn_like(x)
+        // in x's memory order (:543 / :787; [T][B][J][F] from the second step on, _ref_strides in gaussian_diffusion.py)
+        int nd = 0;
+        tda.d[nd++] = torch_draw(h->trng_eps.f(), eps_step, (long long)B * kD, h->n_cu, h->max_thr_cu, 0, 0);
+        tda.d[nd++] = torch_draw(h->trng_eps.f() + (size_t)B * kD, eps_step, (long long)B * kD, h->n_cu, h->max_thr_cu, 0, 0);
+        if (inp_noised) tda.d[nd++] = torch_draw(h->trng_inz.f(), nelem, (long long)nelem, h->n_cu, h->max_thr_cu, 0, 1);
+        tda.d[nd++] = torch_draw(h->trng_noise.f(), nelem, (long long)nelem, h->n_cu, h->max_thr_cu, 1, 0);
+        tda.ndraw = nd;
+        tda.step_adv = 0;
+        for (int d = 0; d < nd; ++d) tda.step_adv += tda.d[d].adv;
+    }
 
     // ---- the loop: for i = T-1-skip ... 0 (gaussian_diffusion.py:724-743 / :994-1014) ----------------
     const bool pair = h->fused && !h->use_long && h->all_scale_one && !a->two_pass_always;
@@ -1858,6 +1902,7 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
                  a->skip_timesteps, a->noise_mode, a->const_noise, a->clip_denoised, h->weights_version, h->sched_version, (int)pair, a->n_dump, plan_code(h));
         key = keybuf;
         if (inpaint) key += inp_noised ? " I2" : " I1";
+        if (tdev) key += " R" + std::to_string(ring_k) + (a->x_init ? "x" : "X");
         for (int d = 0; d < a->n_dump; ++d) key += "," + std::to_string(a->dump_steps[d]);      // the whole list, however long
     }
     auto enqueue_loop = [&]() -> int {
@@ -1878,6 +1923,19 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
                 s.noise = h->noise_tape.f() + (size_t)k * nelem;
                 s.const_noise = a->const_noise;
             }
+            const int slot = tdev ? k % ring_k : 0;
+            if (tdev) {
+                if (slot == 0) {        // refill the ring with steps k .. k + K - 1 (stream order: the steps that read it before are done)
+                    TorchDrawArgs g = tda;
+                    g.k0 = k; g.nsteps = n_exec - k < ring_k ? n_exec - k : ring_k;
+                    g.rel0 = x_adv + (unsigned long long)k * tda.step_adv;
+                    HIPCHK(h, launch_torch_draws(g, st));
+                }
+                s.eps_c = h->trng_eps.f() + ((size_t)slot * 2 + 0) * B * kD;
+                s.eps_u = h->trng_eps.f() + ((size_t)slot * 2 + 1) * B * kD;
+                s.noise = h->trng_noise.f() + (size_t)slot * nelem;
+                s.const_noise = a->const_noise;
+            }
             float* dump_at = nullptr;
             for (int d = 0; d < a->n_dump; ++d)
                 if (a->dump_steps[d] == k) dump_at = h->dump.f() + (size_t)d * nelem;
@@ -1886,7 +1944,8 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
                 StepArgs m = s;
                 m.sampler = kNone; m.clip_denoised = 0; m.x0_out = h->fwd_cfg.f(); m.x_out = nullptr; m.noise = nullptr;
                 HIPCHK(h, run_step(h, m, B, pair, st));
-                HIPCHK(h, run_inpaint_update(h, s, i, inp_noised, tape ? h->inp_tape.f() + (size_t)k * nelem : nullptr, s.noise, s.const_noise,
+                const float* inz = tape ? h->inp_tape.f() + (size_t)k * nelem : tdev && inp_noised ? h->trng_inz.f() + (size_t)slot * nelem : nullptr;
+                HIPCHK(h, run_inpaint_update(h, s, i, inp_noised, inz, s.noise, s.const_noise,
                                              s.x_out, dump_at, (unsigned)k, a->clip_denoised, B, st));
                 continue;
             }
@@ -1965,6 +2024,31 @@ int ls_philox_x_init(ls_handle* h, int batch, uint64_t seed, uint64_t sample_off
     int rc = egress(h, out, h->xio.f(), nx, on_device);
     if (rc != LS_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return LS_OK;
+}
+
+uint64_t ls_torch_randn_advance(int64_t n, int32_t n_cu, int32_t max_threads_per_cu) {
+    return torch_randn_advance(n, n_cu, max_threads_per_cu, nullptr);
+}
+
+int ls_torch_randn(ls_handle* h, uint64_t seed, uint64_t offset, int64_t n, float* out_device, int no_sync) {
+    if (!h || !out_device || n < 1 || n >= (1ll << 31)) return fail(h, LS_EINVAL, "ls_torch_randn: bad argument");
+    if (offset & 3) return fail(h, LS_EINVAL, "ls_torch_randn: the generator offset %llu is not a multiple of 4", (unsigned long long)offset);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->call_host = CallParams{seed, offset, h->tag_base, 0u};
+    HIPCHK(h, hipMemcpyAsync(h->callp.p, &h->call_host, sizeof(CallParams), hipMemcpyHostToDevice, h->stream));
+    TorchDrawArgs a{};
+    a.call = static_cast<const CallParams*>(h->callp.p);
+    a.nsteps = 1; a.ndraw = 1; a.last_step = -1; a.B = 1; a.JF = 1; a.T = 1;
+    a.d[0] = torch_draw(out_device, 0, n, h->n_cu, h->max_thr_cu, 0, 0);
+    HIPCHK(h, launch_torch_draws(a, h->stream));
+    if (!no_sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return LS_OK;
+}
+
+int ls_set_torch_ring_bytes(ls_handle* h, uint64_t bytes) {
+    if (!h || bytes < 1) return fail(h, LS_EINVAL, "ls_set_torch_ring_bytes: bad argument");
+    h->trng_ring_bytes = (size_t)bytes;
     return LS_OK;
 }
 

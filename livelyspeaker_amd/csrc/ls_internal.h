@@ -268,6 +268,34 @@ hipError_t launch_randn_fill(float* out_btc, int B, int JF, const CallParams* ca
                              hipStream_t st, int T = kT);
 hipError_t launch_transpose_feat(const float* conv4, float* out_btc, int B, hipStream_t st, int T = kT);
 
+// ---- torch's device normal stream (ls_torch_philox.hip; LS_NOISE_TORCH_DEVICE) ---------------------------------------------
+// One torch.randn / randn_like of n float32 elements per step: written to dst + r * dst_stride for step r of the launch.
+struct TorchDraw {
+    float* dst;
+    size_t dst_stride;
+    unsigned long long n;       // elements (< 2^31)
+    unsigned long long work;    // threads: S * rounds (one per Philox block), or n with perm (one per element)
+    unsigned long long adv;     // generator offset advance: 4 * rounds
+    unsigned S;                 // threads of torch's grid-stride launch for n elements
+    int perm;                   // 1: from the loop's second step on, the draw follows x's [T][B][J][F] memory order (stored as [B][J][F][T]);
+                                //    computed per tape element (coalesced stores)
+    int skip_last;              // 1: not drawn at the loop's last step (the inpainting re-noise, t == 0)
+};
+// Draws of loop steps [k0, k0 + nsteps), in the reference's order within a step (d[0], d[1], ...).  The generator state comes from
+// device memory (CallParams: seed, sample_offset = offset before the loop's first draw), so a captured graph replays with new values;
+// step k0's first draw sits rel0 past it, and every step but the loop's last advances the offset by step_adv.
+struct TorchDrawArgs {
+    const CallParams* call;
+    unsigned long long rel0, step_adv;
+    int k0, nsteps, last_step, ndraw;
+    int B, JF, T;
+    TorchDraw d[4];
+};
+hipError_t launch_torch_draws(const TorchDrawArgs& a, hipStream_t st);
+unsigned long long torch_randn_advance(long long n, int n_cu, int max_threads_per_cu, unsigned* S);
+TorchDraw torch_draw(float* dst, size_t dst_stride, long long n, int n_cu, int max_threads_per_cu, int perm, int skip_last);
+hipError_t launch_bcast_first(float* x, int B, int per, hipStream_t st);
+
 // ---- SAG decoder kernels (ls_sag.hip) ----------------------------------------------------------
 hipError_t launch_sag_queries(const float* x, const float* wmap, const float* bmap, const float* pe, float* q, float* qc, int B,
                               int JF, int n_pre, int D, hipStream_t st);

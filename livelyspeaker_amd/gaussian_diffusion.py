@@ -16,7 +16,11 @@ RNG contract ("identical seeds"): with ``noise_source='torc
 draw the reference would make is made here from torch's CPU generator, in the same order and
 shape -- ``randn(*shape)`` once, then per step ``randn(B,1,512)`` x2 (style eps of the cond and
 uncond passes) and ``randn_like(x)`` with x's strides (contiguous at the first step, [T][B][J][F] memory
-order afterwards) -- so ``torch.manual_seed(s)`` reproduces the reference's CPU-path samples (fixture G7).  ``noise_source='philox'`` draws one 64-bit key from the torch generator and
+order afterwards) -- so ``torch.manual_seed(s)`` reproduces the reference's CPU-path samples (fixture G7).  ``noise_source='torch_device'``
+makes the same draws from torch's generator of the model's GPU, as the reference's callers run it (scripts/test_RAG_ted.py:21): the loops
+generate them on the device inside the captured loop (csrc/ls_torch_philox.hip restates torch's Philox launch bit for bit, checked
+against torch once per process) and leave the generator at the offset the reference's draws would have left; the per-step entry points
+draw with torch on x's device.  The CPU generator is not touched.  ``noise_source='philox'`` draws one 64-bit key from the torch generator and
 generates all noise on the device (throughput mode; statistically equivalent, not bitwise).
 """
 from __future__ import annotations
@@ -31,6 +35,39 @@ import torch as th
 from . import _lib
 
 _TH_RANDN, _TH_RANDN_LIKE = th.randn, th.randn_like      # as imported: a caller (or test) that replaces them wants to see every draw
+
+_DEVICE_RNG_OK = {}      # device index -> does ls_torch_randn reproduce torch.randn on it (checked once per process)
+
+
+def _device_rng_check(eng, dev) -> bool:
+    """Once per process and device: ls_torch_randn against torch.randn on a PRIVATE generator (the default one is not moved) at sizes
+    of one and of several grid-stride rounds.  False sends noise_source='torch_device' loops to torch's own device draws."""
+    if dev.index in _DEVICE_RNG_OK:
+        return _DEVICE_RNG_OK[dev.index]
+    props = th.cuda.get_device_properties(dev)
+    g = th.Generator(device=dev)
+    ok = True
+    for seed, off, n in ((0, 0, 3), (2 ** 63 + 5, 4, 4099), (233, 49380, 470016), (7, 1 << 40, 2454528)):
+        g.manual_seed(seed)
+        g.set_offset(off)
+        want = _TH_RANDN(n, device=dev, generator=g)
+        got = eng.torch_randn(seed, off, th.empty(n, device=dev))
+        adv = _lib.torch_randn_advance(n, props.multi_processor_count, props.max_threads_per_multi_processor)
+        ok = ok and bool(th.equal(got, want)) and g.get_offset() == off + adv
+    _DEVICE_RNG_OK[dev.index] = ok
+    return ok
+
+
+def _torch_device(dev, what):
+    """The GPU whose torch generator noise_source='torch_device' draws from; refuses what that mode cannot reproduce."""
+    dev = th.device(dev)
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: noise_source='torch_device' draws from torch's generator of the model's GPU, "
+                         f"but the model / tensors are on {dev}")
+    if th.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{what}: noise_source='torch_device' cannot run inside torch.cuda.graph capture (the generator's "
+                           "offset is read and set on the host)")
+    return th.device("cuda", th.cuda.current_device() if dev.index is None else dev.index)
 
 
 def get_named_beta_schedule(schedule_name, num_diffusion_timesteps, scale_betas=1.0):
@@ -95,7 +132,7 @@ class GaussianDiffusion:
     """Schedule tables + sampling entry points; the RAG path supports START_X + FIXED_SMALL only
     (what create_gaussian_diffusion builds, scripts/mdm_utils/model_util.py:40-74)."""
 
-    noise_source = "torch_cpu"      # or "philox"
+    noise_source = "torch_cpu"      # or "torch_device" / "philox"
     use_graph = True
     #: evaluate both CFG passes even when every guidance scale is 1 (ls_sample_args.two_pass_always).  Default False: scale 1
     #: runs ONE pass (out_u + 1 * (out_c - out_u) = out_c up to one fp32 rounding -- the two settings agree to ~1e-5, not bitwise)
@@ -109,6 +146,12 @@ class GaussianDiffusion:
     #: native restatement reproduces this torch build; False = always call torch's generator
     native_host_rng = True
     last_host_rng_native = False
+    #: torch_device mode: generate the draws natively on the device when ls_torch_randn reproduces torch.randn there (checked once per
+    #: process); False = draw the tape with torch's device calls (K-step device segments through the TAPE path; same values, slower)
+    native_device_rng = True
+    last_device_rng_native = False
+    #: torch_device mode: device memory of the loop's ring of draws (K steps refilled by one generator launch per K steps)
+    device_ring_bytes = 256 << 20
     philox_seed = None              # philox mode: None = draw the key from torch's generator per call
     last_philox_seed = None
 
@@ -212,6 +255,9 @@ class GaussianDiffusion:
         step runs exactly the launches the whole-loop entry points run.  mean_only: p_mean_variance -- the step's own noise is neither
         drawn nor added, so 'sample' is the posterior mean."""
         self._reject(denoised_fn, cond_fn, False, False)
+        tdev = self.noise_source == "torch_device"
+        # torch_device: the draws below are made with torch itself on x's device (what the reference's GPU run draws, RAG.py:10-13)
+        rdev = _torch_device(x.device, "p_sample/ddim_sample") if tdev else th.device("cpu")
         eng = self._engine_for(model, model_kwargs, "p_sample/ddim_sample")
         B = x.shape[0]
         t = th.as_tensor(t)
@@ -223,8 +269,8 @@ class GaussianDiffusion:
             if not bool((t_host == t_host[0]).all()):
                 raise NotImplementedError("nframes != 34 runs on the batch-level kernels, which take ONE timestep for the batch")
             index = int(t_host[0])
-        eps_c = th.randn(B, 1, eng.D)           # cond pass reparameterize (RAG.py:12), then uncond pass
-        eps_u = th.randn(B, 1, eng.D)
+        eps_c = th.randn(B, 1, eng.D, device=rdev)           # cond pass reparameterize (RAG.py:12), then uncond pass
+        eps_u = th.randn(B, 1, eng.D, device=rdev)
         inp = self._inpainting(model, model_kwargs, tuple(x.shape))
         inp_arg = None
         if inp is not None:
@@ -232,17 +278,17 @@ class GaussianDiffusion:
             t_host = t.detach().cpu()
             if not bool((t_host == t_host[0]).all()):
                 raise NotImplementedError("the inpainting branch tests t[0] only (gaussian_diffusion.py:318): pass one timestep for the batch")
-            inz = th.randn_like(inp[1], device="cpu", dtype=th.float32) if (inp[2] and int(t_host[0]) > 0) else None
+            inz = th.randn_like(inp[1], device=rdev, dtype=th.float32) if (inp[2] and int(t_host[0]) > 0) else None
             inp_arg = (inp[0], inp[1], inz)
             t = t_host
         if mean_only:
-            noise = th.zeros(tuple(x.shape), dtype=th.float32)
+            noise = th.zeros(tuple(x.shape), dtype=th.float32, device=rdev)
         else:
-            noise = th.randn_like(x, device="cpu", dtype=th.float32)    # follows x's strides like the reference's randn_like(x)
+            noise = th.randn_like(x, device=rdev, dtype=th.float32)    # follows x's strides like the reference's randn_like(x)
             if const_noise:
                 noise = noise[[0]].repeat(B, 1, 1, 1)
         dev = x.device
-        if x.is_cuda and inp is None:
+        if x.is_cuda and inp is None and not tdev:
             eps_c, eps_u, noise = self._stage_step_draws(dev, eps_c, eps_u, noise)
         # `t` may differ per sample (the reference's signature).  A CUDA `t` is handed to the engine as it is -- never read back, so
         # a step-by-step caller has no device -> host round trip per step, and with device tensors the call does not wait for the GPU
@@ -301,6 +347,8 @@ class GaussianDiffusion:
     # ------------------------------------------------------------------ loops
     def _loop(self, sampler, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image,
               dump_steps, const_noise, eta):
+        if self.noise_source == "torch_device":     # refused before the engine is touched
+            _torch_device(device if device is not None else next(model.parameters()).device, "sample loop")
         eng = self._engine_for(model, model_kwargs, "sample loop")
         assert isinstance(shape, (tuple, list))
         shape = tuple(int(s) for s in shape)
@@ -311,8 +359,11 @@ class GaussianDiffusion:
         n_exec = self.num_timesteps - skip_timesteps
         B = shape[0]
         philox = self.noise_source == "philox"
-        if self.noise_source not in ("torch_cpu", "philox"):
+        if self.noise_source not in ("torch_cpu", "torch_device", "philox"):
             raise ValueError(f"noise_source {self.noise_source!r}")
+        if self.noise_source == "torch_device":
+            return self._loop_torch_device(eng, sampler, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps,
+                                           init_image, dump_steps, const_noise, eta)
         x_init = None
         if noise is not None:
             x_init = noise
@@ -413,6 +464,96 @@ class GaussianDiffusion:
             return [_as_tensor(d, device).clone() for d in res[1]] if dump_steps else []
         return _ref_strides(_as_tensor(res, device))
 
+    def _loop_torch_device(self, eng, sampler, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image,
+                           dump_steps, const_noise, eta):
+        """noise_source='torch_device': the draws of _loop's torch_cpu mode, same order, shapes and memory orders, from torch's generator
+        of the model's GPU.  Natively (ls_sample TORCH_DEVICE: generated on the device inside the captured loop from the generator's
+        (seed, offset), which is then set where the reference's draws leave it) when ls_torch_randn reproduces torch there and the
+        memory orders are the loop's usual ones; otherwise drawn with torch's device calls into device tapes."""
+        dev = _torch_device(device if device is not None else next(model.parameters()).device, "sample loop")
+        if dev.index != eng.device:
+            raise ValueError(f"noise_source='torch_device': the model's engine runs on cuda:{eng.device}, the draws would come from {dev}")
+        n_exec = self.num_timesteps - skip_timesteps
+        B, D = shape[0], eng.D
+        nelem = int(np.prod(shape))
+        want_dumps = dump_steps is not None
+        dump_steps = sorted({int(d) for d in dump_steps if 0 <= int(d) < n_exec}) if dump_steps else None
+        inp = self._inpainting(model, model_kwargs, shape)
+        inz_on = inp is not None and inp[2]
+        first_given = noise is not None and init_image is None and not skip_timesteps     # x of the first step is the caller's `noise`
+        gen = th.cuda.default_generators[dev.index]
+        seed, off0 = gen.initial_seed(), gen.get_offset()
+        intercepted = th.randn is not _TH_RANDN or th.randn_like is not _TH_RANDN_LIKE
+        native = (self.native_device_rng and not intercepted and off0 % 4 == 0
+                  and not (first_given and not noise.is_contiguous())
+                  and not (inz_on and th.is_tensor(inp[1]) and not inp[1].is_contiguous())
+                  and _device_rng_check(eng, dev))
+        self.last_device_rng_native = bool(native)
+        kw = dict(sampler=sampler, init_image=init_image, skip_timesteps=skip_timesteps, eta=eta, const_noise=const_noise,
+                  dump_steps=dump_steps or None, clip_denoised=clip_denoised, two_pass_always=self.two_pass_always, device_out=True)
+        if native:
+            props = th.cuda.get_device_properties(dev)
+            adv = lambda n: _lib.torch_randn_advance(n, props.multi_processor_count, props.max_threads_per_multi_processor)    # noqa: E731
+            if inp is not None:
+                kw["inpaint"] = (inp[0], inp[1], None, inp[2])
+            res = eng.sample(x_init=noise, use_graph=self.use_graph, torch_state=(seed, off0), torch_ring_bytes=self.device_ring_bytes, **kw)
+            total = ((adv(nelem) if noise is None else 0) + n_exec * (2 * adv(B * D) + adv(nelem))
+                     + (max(n_exec - 1, 0) * adv(nelem) if inz_on else 0))
+            gen.set_offset(off0 + total)
+            self.last_tape_segments = 1
+        else:
+            res = self._loop_torch_device_tape(eng, dev, shape, noise, init_image, skip_timesteps, const_noise, n_exec, inp, kw)
+        if want_dumps:
+            return [_as_tensor(d, dev).clone() for d in res[1]] if dump_steps else []
+        return _ref_strides(_as_tensor(res, dev))
+
+    def _loop_torch_device_tape(self, eng, dev, shape, noise, init_image, skip_timesteps, const_noise, n_exec, inp, kw):
+        """The torch_device draws made with torch's own device calls (th.randn / randn_like as the module sees them), in the reference's
+        order, into device tapes: one piece, or K-step segments of at most tape_segment_bytes through the segmented TAPE path."""
+        B, D = shape[0], eng.D
+        J, F, T = shape[1:]
+        x_init = noise
+        if x_init is None:
+            x_init = th.randn(*shape, device=dev)
+            if const_noise:
+                x_init = x_init[[0]].repeat(B, 1, 1, 1)
+        first_proto = noise if (noise is not None and init_image is None and not skip_timesteps) else th.empty(shape, device=dev)
+        later_proto = th.empty(T, B, J, F, device=dev).permute(1, 2, 3, 0)
+        inz = None
+        if inp is not None and inp[2]:
+            inz = th.zeros((n_exec,) + tuple(shape), device=dev)
+            inp_proto = inp[1] if th.is_tensor(inp[1]) else th.empty(shape, device=dev)
+
+        def draw(k, eps_k, nz_k):          # the reference's per-step draw order
+            eps_k[0] = th.randn(B, 1, D, device=dev)[:, 0]
+            eps_k[1] = th.randn(B, 1, D, device=dev)[:, 0]
+            if inz is not None and n_exec - 1 - k > 0:
+                inz[k] = th.randn_like(inp_proto, device=dev, dtype=th.float32)
+            nz_k.copy_(th.randn_like(first_proto if k == 0 else later_proto, device=dev, dtype=th.float32))
+
+        kw = dict(kw, x_init=x_init)
+        per_step = (2 * B * D + int(np.prod(shape))) * 4
+        if per_step * n_exec > self.tape_segment_bytes and n_exec > 1 and inp is None:
+            K = max(1, min(n_exec, self.tape_segment_bytes // per_step))
+            eps, nz = th.empty(K, 2, B, D, device=dev), th.empty((K,) + tuple(shape), device=dev)
+            res = None
+            for k0 in range(0, n_exec, K):
+                n = min(K, n_exec - k0)
+                for r in range(n):
+                    draw(k0 + r, eps[r], nz[r])
+                res = eng.sample(eps_tape=eps[:n], noise_tape=nz[:n], segment=(k0, n), **kw)
+                # the segment's copy of the tapes runs on the engine's stream: the next segment's draws (torch's stream) wait for it
+                _lib.load_library().ls_stream_order(eng.device, eng._stream, th.cuda.current_stream(dev).cuda_stream)
+            self.last_tape_segments = -(-n_exec // K)
+            return res
+        eps, nz = th.empty(n_exec, 2, B, D, device=dev), th.empty((n_exec,) + tuple(shape), device=dev)
+        for k in range(n_exec):
+            draw(k, eps[k], nz[k])
+        if inp is not None:
+            kw["inpaint"] = (inp[0], inp[1], inz, inp[2])
+        self.last_tape_segments = 1
+        return eng.sample(eps_tape=eps, noise_tape=nz, use_graph=self.use_graph, **kw)
+
     def _tape_ring(self, K, B, D, shape):
         """Two page-locked (eps [K,2,B,D], noise [K,B,J,F,T]) segments, kept between calls (pinning 100 MB takes tens of ms)."""
         key = (K, B, D, tuple(shape))
@@ -435,8 +576,14 @@ class GaussianDiffusion:
         tensors device-resident when the model is (no host synchronisation between yields)."""
         if device is None:
             device = next(model.parameters()).device
+        if self.noise_source == "torch_device":
+            device = _torch_device(device, "sample loop")
         if noise is not None:
             img = noise
+        elif self.noise_source == "torch_device":
+            img = th.randn(*shape, device=device)   # the reference's GPU run: torch's device generator
+            if const_noise:
+                img = img[[0]].repeat(img.shape[0], 1, 1, 1)
         else:
             img = th.randn(*shape)                  # torch's CPU generator, like every draw of this module ("identical seeds")
             if const_noise:

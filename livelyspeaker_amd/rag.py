@@ -130,6 +130,9 @@ class RAG(nn.Module):
         #: the sample-split kernel for small batches, batch-level kernels in the middle, one workgroup per sample from ~176 clips),
         #: "fused", "batch", "coop" (ls_set_path; same arithmetic, results agree to ~1e-5)
         self.step_path = None
+        #: where a direct model(x, t, y) call draws its style eps (RAG.py:10-13): "torch_cpu" = torch's CPU generator (default),
+        #: "torch_device" = torch's generator of x's GPU, as the reference's forward does on a GPU model
+        self.noise_source = "torch_cpu"
         self._engine = None
         self._weights_dirty = True
         self._cond_key = None
@@ -214,14 +217,19 @@ class RAG(nn.Module):
         return eng
 
     def _forward_engine(self, x, timesteps, y, want):
+        if self.noise_source not in ("torch_cpu", "torch_device"):
+            raise ValueError(f"noise_source {self.noise_source!r}")
+        if self.noise_source == "torch_device" and not x.is_cuda:
+            raise ValueError(f"noise_source='torch_device' draws from torch's generator of x's GPU, but x is on {x.device}")
         eng = self._engine_prepared(y)
         B = x.shape[0]
         uncond = bool(y.get('uncond', False))
+        rdev = x.device if self.noise_source == "torch_device" else torch.device("cpu")
         if want == "cfg":
-            eps_c = torch.randn(B, 1, self.latent_dim)
-            eps_u = torch.randn(B, 1, self.latent_dim)
+            eps_c = torch.randn(B, 1, self.latent_dim, device=rdev)
+            eps_u = torch.randn(B, 1, self.latent_dim, device=rdev)
         else:                                   # one pass only: a single reparameterize draw (RAG.py:120)
-            eps_c = eps_u = torch.randn(B, 1, self.latent_dim)
+            eps_c = eps_u = torch.randn(B, 1, self.latent_dim, device=rdev)
         oc, ou, og = eng.forward(x, timesteps, eps_c, eps_u)
         pick = og if want == "cfg" else (ou if uncond else oc)
         return (pick if isinstance(pick, torch.Tensor) else torch.from_numpy(pick)).to(x.device)

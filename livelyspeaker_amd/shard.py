@@ -299,6 +299,10 @@ def sample_sharded(sample_fn, model, global_shape, y_global: dict, diffusion=Non
     """Run ``sample_fn`` (``diffusion.p_sample_loop`` / ``ddim_sample_loop``) on this rank's contiguous
     shard of the batch and return the gathered global result.  ``diffusion.sample_offset`` is set so the
     Philox streams follow the global sample index."""
+    owner = diffusion if diffusion is not None else getattr(sample_fn, "__self__", None)
+    if getattr(owner, "noise_source", None) == "torch_device":
+        raise NotImplementedError("noise_source='torch_device' reproduces a single-GPU run of the reference (which has no multi-GPU "
+                                  "sampling); sharded sampling runs noise_source='philox'")
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     total = int(global_shape[0])
