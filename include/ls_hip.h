@@ -37,7 +37,9 @@ enum {
     LS_EUNSUPPORTED = -5
 };
 
-enum { LS_SAMPLER_DDPM = 0, LS_SAMPLER_DDIM = 1 };
+/* PLMS: plms_sample_loop (gaussian_diffusion.py:1016-1211), ls_sample only (single steps: ls_plms_step).
+ * DDIM_REVERSE: ddim_reverse_sample (:857-893), ls_step only. */
+enum { LS_SAMPLER_DDPM = 0, LS_SAMPLER_DDIM = 1, LS_SAMPLER_PLMS = 2, LS_SAMPLER_DDIM_REVERSE = 3 };
 /* TORCH_DEVICE: the reference's draws as a GPU run of it makes them, from torch's device generator (Philox4x32-10 behind torch's
  * grid-stride launch geometry, ls_torch_randn), generated on the device inside the loop: bitwise torch.randn / randn_like on the
  * handle's GPU, in the reference's order, shapes and memory orders (as the TAPE tapes of the torch_cpu mode are drawn). */
@@ -156,7 +158,13 @@ typedef struct ls_sample_args {
     const float* inpainted_motion;       /* [B,J,F,T]                                                            */
     const float* inpaint_noise;          /* TAPE + inpaint_noised: [n_exec,B,J,F,T]; entries of steps with t == 0 unused */
     int32_t inpaint_noised;
-    int32_t reserved2;
+    /* LS_SAMPLER_PLMS: the order of the multistep method, 2..4 (0 with every other sampler).  The loop makes n_exec + 1 model
+     * evaluations: the first executed step evaluates at (x, i) and at (mean_pred, i - 1) (the pseudo improved Euler start, :1066-1073),
+     * every later step once, with Adams-Bashforth over the last min(order, steps so far) eps (:1075-1090).  TAPE mode: eps_tape is
+     * [n_exec + 1, 2, B, latent_dim] in evaluation order and noise_tape is NULL (PLMS draws no step noise); PHILOX mode: evaluation e
+     * uses the style-eps streams of step_id = e.  At least two executed steps.  Not combined with TORCH_DEVICE, dump_steps,
+     * const_noise, eta, segments or the inpainting arguments. */
+    int32_t plms_order;
 } ls_sample_args;
 
 /* One RAG.forward pair (cond / uncond) and optionally the CFG combination, for model(x,t,y)
@@ -177,7 +185,8 @@ typedef struct ls_forward_args {
 /* One p_sample / ddim_sample step (gaussian_diffusion.py:507-558, 745-798) at schedule index i -- or, as the reference's
  * signature allows (`t` is a [B] tensor), at one schedule index PER SAMPLE (`indices`). */
 typedef struct ls_step_args {
-    int32_t sampler;
+    int32_t sampler;            /* LS_SAMPLER_DDPM | DDIM | DDIM_REVERSE (x_{t+1} of the deterministic DDIM ODE: the DDIM arithmetic with
+                                   alphas_cumprod_next = append(alphas_cumprod[1:], 0) in place of alphas_cumprod_prev, eta and noise unused) */
     int32_t index;              /* schedule index i (model sees timestep_map[i]); ignored when indices != NULL */
     int32_t on_device;
     float eta;
@@ -186,7 +195,7 @@ typedef struct ls_step_args {
     const float* x;             /* [B,J,F,T]                                        */
     const float* eps_cond;
     const float* eps_uncond;
-    const float* noise;         /* [B,J,F,T]                                        */
+    const float* noise;         /* [B,J,F,T]; may be NULL with DDIM_REVERSE         */
     float* sample;              /* [B,J,F,T]                                        */
     float* pred_xstart;         /* [B,J,F,T] or NULL                                */
     const int64_t* indices;     /* [B] schedule index per sample, or NULL (uniform `index`).  When the entries differ the denoiser runs
@@ -202,11 +211,35 @@ typedef struct ls_step_args {
     const float* inpaint_noise;          /* [B,J,F,T] the randn_like of q_sample(inpainted_motion, t - 1), or NULL = un-noised */
 } ls_step_args;
 
+/* One plms_sample step (gaussian_diffusion.py:1016-1098) at the uniform schedule index `index`.  n_hist = entries of old_out["old_eps"]
+ * handed in (0..3, oldest first; a longer list: its last three).  n_hist == 0 is the first call of a loop (order > 1, index >= 1): two
+ * model evaluations, the second at (mean_pred, index - 1) with its own style eps (eps_cond2 / eps_uncond2).  Otherwise one evaluation
+ * and Adams-Bashforth of order min(order, n_hist + 1).  Launches what an LS_SAMPLER_PLMS loop launches for that step. */
+typedef struct ls_plms_step_args {
+    int32_t index;
+    int32_t order;              /* 1..4 (1 needs n_hist >= 1: the reference fails without a history)            */
+    int32_t n_hist;
+    int32_t on_device;
+    int32_t clip_denoised;      /* clamps pred_xstart BEFORE eps is derived from it (p_mean_variance, :365-371) */
+    int32_t two_pass_always;
+    int32_t no_sync;            /* on_device only, as in ls_step_args                                           */
+    int32_t reserved;
+    const float* x;             /* [B,J,F,T]                                                                    */
+    const float* eps_cond;      /* [B, latent_dim] style eps of the (first) evaluation                          */
+    const float* eps_uncond;
+    const float* eps_cond2;     /* second evaluation (n_hist == 0), else NULL                                   */
+    const float* eps_uncond2;
+    const float* hist[3];       /* [B,J,F,T] each, oldest first                                                 */
+    float* sample;              /* [B,J,F,T]                                                                    */
+    float* pred_xstart;         /* [B,J,F,T] of the first evaluation, or NULL                                   */
+    float* eps_out;             /* [B,J,F,T] this step's eps (first evaluation), the entry appended to old_eps; or NULL */
+} ls_plms_step_args;
+
 typedef struct ls_timing {
     float prepare_ms;           /* last ls_prepare, GPU time (HIP events on the handle's stream); -1 while an ls_prepare_async is in flight */
     float loop_ms;              /* last ls_sample: first step launch .. last step done */
     float total_ms;             /* last ls_sample incl. layout conversion and copies */
-    int32_t n_step_launches;
+    int32_t n_step_launches;    /* model evaluations of the last loop (PLMS: executed steps + 1) */
     int32_t graph_replayed;     /* 1 if the loop ran as a hipGraph replay           */
     int32_t single_pass;        /* 1 if the loop ran the single-pass (scale == 1) kernel */
     float tape_upload_ms;       /* segmented TAPE mode: summed GPU-side duration of the tape uploads of the last loop (copy stream) */
@@ -270,6 +303,7 @@ int ls_prepare_async(ls_handle* h, const ls_cond* c);
 int ls_sample(ls_handle* h, const ls_sample_args* a);
 int ls_forward(ls_handle* h, const ls_forward_args* a);
 int ls_step(ls_handle* h, const ls_step_args* a);
+int ls_plms_step(ls_handle* h, const ls_plms_step_args* a);
 /* elementwise q_sample (gaussian_diffusion.py:240-258) at schedule index i; pointers per on_device */
 int ls_q_sample(ls_handle* h, int index, int on_device, size_t n, const float* x_start,
                 const float* noise, float* out);

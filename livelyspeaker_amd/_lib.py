@@ -17,7 +17,7 @@ c_f64p = C.POINTER(C.c_double)
 c_i64p = C.POINTER(C.c_int64)
 c_i32p = C.POINTER(C.c_int32)
 
-LS_SAMPLER_DDPM, LS_SAMPLER_DDIM = 0, 1
+LS_SAMPLER_DDPM, LS_SAMPLER_DDIM, LS_SAMPLER_PLMS, LS_SAMPLER_DDIM_REVERSE = 0, 1, 2, 3
 LS_NOISE_TAPE, LS_NOISE_PHILOX, LS_NOISE_TORCH_DEVICE = 0, 1, 2
 LS_PRECISION_FP32, LS_PRECISION_BF16X3 = 0, 1
 
@@ -47,7 +47,7 @@ class LsSampleArgs(C.Structure):
                 ("x_init", C.c_void_p), ("init_image", C.c_void_p), ("eps_tape", C.c_void_p),
                 ("noise_tape", C.c_void_p), ("seed", C.c_uint64), ("sample_offset", C.c_uint64),
                 ("out", C.c_void_p), ("seg_begin", C.c_int32), ("seg_count", C.c_int32), ("inpaint_mask", C.c_void_p),
-                ("inpainted_motion", C.c_void_p), ("inpaint_noise", C.c_void_p), ("inpaint_noised", C.c_int32), ("reserved2", C.c_int32)]
+                ("inpainted_motion", C.c_void_p), ("inpaint_noise", C.c_void_p), ("inpaint_noised", C.c_int32), ("plms_order", C.c_int32)]
 
 
 class LsForwardArgs(C.Structure):
@@ -61,6 +61,12 @@ class LsStepArgs(C.Structure):
                 ("clip_denoised", C.c_int32), ("two_pass_always", C.c_int32), ("x", C.c_void_p), ("eps_cond", C.c_void_p), ("eps_uncond", C.c_void_p), ("noise", C.c_void_p),
                 ("sample", C.c_void_p), ("pred_xstart", C.c_void_p), ("indices", C.c_void_p), ("no_sync", C.c_int32),
                 ("indices_on_device", C.c_int32), ("inpaint_mask", C.c_void_p), ("inpainted_motion", C.c_void_p), ("inpaint_noise", C.c_void_p)]
+
+
+class LsPlmsStepArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("index", "order", "n_hist", "on_device", "clip_denoised", "two_pass_always", "no_sync", "reserved")] + [
+        ("x", C.c_void_p), ("eps_cond", C.c_void_p), ("eps_uncond", C.c_void_p), ("eps_cond2", C.c_void_p), ("eps_uncond2", C.c_void_p),
+        ("hist", C.c_void_p * 3), ("sample", C.c_void_p), ("pred_xstart", C.c_void_p), ("eps_out", C.c_void_p)]
 
 
 class LsSagConfig(C.Structure):
@@ -102,7 +108,7 @@ class LsEvalConfig(C.Structure):
 
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
-           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_sample", "ls_forward", "ls_step", "ls_q_sample", "ls_read",
+           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms", "ls_ted_post", "ls_beat_post",
            "ls_train_create", "ls_train_destroy", "ls_train_last_error", "ls_train_set_schedule", "ls_train_param_count",
@@ -174,6 +180,7 @@ def load_library(build_if_missing: bool = True):
     lib.ls_sample.argtypes = [C.c_void_p, C.POINTER(LsSampleArgs)]
     lib.ls_forward.argtypes = [C.c_void_p, C.POINTER(LsForwardArgs)]
     lib.ls_step.argtypes = [C.c_void_p, C.POINTER(LsStepArgs)]
+    lib.ls_plms_step.argtypes = [C.c_void_p, C.POINTER(LsPlmsStepArgs)]
     lib.ls_q_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ls_read.argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
     lib.ls_read.restype = C.c_longlong
@@ -552,10 +559,39 @@ class Engine:
             self._inflight = m          # marshalled copies stay referenced until the next call replaces them
         return out, x0
 
+    def plms_step(self, index, order, x, eps, hist=(), eps2=None, clip_denoised=False, two_pass_always=False, no_sync=False):
+        """One plms_sample step at the uniform schedule ``index``.  ``eps`` = (cond, uncond) style draws of the evaluation, ``eps2`` those
+        of the second evaluation of a loop's first step (``hist`` empty); ``hist``: the old eps planes, oldest first (at most the last
+        three are read).  Returns (sample, pred_xstart, eps plane of this step)."""
+        hist = list(hist)[-3:]
+        e2 = eps2 or (None, None)
+        m = _Marshal(self.device, x, eps[0], eps[1], e2[0], e2[1], *hist, stream=self._stream)
+        B, D = self.batch, self.D
+        out, pout = m.out(self._xshape())
+        x0, px0 = m.out(self._xshape())
+        ep, pep = m.out(self._xshape())
+        nosync = int(bool(no_sync) and m.on_device)
+        a = LsPlmsStepArgs()
+        a.index, a.order, a.n_hist, a.on_device = int(index), int(order), len(hist), int(m.on_device)
+        a.clip_denoised, a.two_pass_always, a.no_sync = int(clip_denoised), int(two_pass_always), nosync
+        a.x = m.f32(x, self._xshape())
+        a.eps_cond, a.eps_uncond = m.f32(eps[0].reshape(B, D)), m.f32(eps[1].reshape(B, D))
+        if eps2 is not None:
+            a.eps_cond2, a.eps_uncond2 = m.f32(eps2[0].reshape(B, D)), m.f32(eps2[1].reshape(B, D))
+        for j, hp in enumerate(hist):
+            a.hist[j] = m.f32(hp, self._xshape())
+        a.sample, a.pred_xstart, a.eps_out = pout, px0, pep
+        m.ready()
+        self._check(self.lib.ls_plms_step(self.h, C.byref(a)), "ls_plms_step")
+        if nosync:
+            m.done_async()
+            self._inflight = m
+        return out, x0, ep
+
     def sample(self, sampler=LS_SAMPLER_DDPM, x_init=None, eps_tape=None, noise_tape=None, init_image=None,
                skip_timesteps=0, eta=0.0, const_noise=False, dump_steps=None, philox_seed=None, sample_offset=0,
                use_graph=True, clip_denoised=False, device_out=False, two_pass_always=False, segment=None, inpaint=None,
-               torch_state=None, torch_ring_bytes=256 << 20):
+               torch_state=None, torch_ring_bytes=256 << 20, plms_order=0):
         """Run the whole loop. TAPE mode when tapes are given, PHILOX mode when ``philox_seed`` is, TORCH_DEVICE mode when
         ``torch_state`` = (seed, offset) of torch's device generator is (the loop makes torch's device draws itself; ``x_init`` None =
         it draws x_T too; the caller moves the generator on).  Outputs are torch CUDA tensors if any input is one (or ``device_out``),
@@ -571,6 +607,7 @@ class Engine:
         a.use_graph, a.eta, a.clip_denoised = int(use_graph), eta, int(clip_denoised)
         a.two_pass_always = int(two_pass_always)
         n_exec = self.n_steps - skip_timesteps
+        a.plms_order = int(plms_order)  # LS_SAMPLER_PLMS: eps_tape holds n_exec + 1 evaluations, there is no step noise
         if segment is not None:         # (first executed-step counter, count): one piece of a TAPE-mode loop, tapes hold these steps only
             a.seg_begin, a.seg_count = int(segment[0]), int(segment[1])
             n_tape, last = a.seg_count, a.seg_begin + a.seg_count == n_exec
@@ -582,7 +619,7 @@ class Engine:
             self._check(self.lib.ls_set_torch_ring_bytes(self.h, int(torch_ring_bytes)), "ls_set_torch_ring_bytes")
         elif philox_seed is None:
             a.noise_mode = LS_NOISE_TAPE
-            a.eps_tape = m.f32(eps_tape, (n_tape, 2, self.batch, self.D))
+            a.eps_tape = m.f32(eps_tape, (n_tape + (sampler == LS_SAMPLER_PLMS), 2, self.batch, self.D))
             a.noise_tape = m.f32(noise_tape, (n_tape,) + self._xshape())
         else:
             a.noise_mode = LS_NOISE_PHILOX

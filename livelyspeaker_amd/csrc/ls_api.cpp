@@ -148,6 +148,8 @@ struct ls_handle {
     DevBuf eps_tape, noise_tape;
     DevBuf inp_m8, inp_maskf, inp_motion, inp_tape;     // inpainting branch: mask bytes / mask as 0-1 floats and motion in the internal layout, q_sample noise tape
     DevBuf eps_slot[2], noise_slot[2], coef;
+    DevBuf plms_buf;        // LS_SAMPLER_PLMS: five planes [B][T][JF] (each padded to whole 16-byte groups): a ring of four eps planes (step k
+                            // writes plane k & 3 and reads the up to three before it) + mean_pred of the two-evaluation first step
     // LS_NOISE_TORCH_DEVICE: a ring of K steps' draws (eps [K][2][B][D], noise [K][B][J][F][T], inpainting re-noise [K][B][J][F][T]),
     // refilled by one generator launch per K steps inside the loop; K = what fits in trng_ring_bytes (ls_set_torch_ring_bytes)
     DevBuf trng_eps, trng_noise, trng_inz;
@@ -851,6 +853,17 @@ void fill_sampler(ls_handle* h, StepArgs& a, int sampler, int i, float eta) {
         a.c0 = (float)h->t_c1[i];                                  // posterior_mean_coef1 (:268-271)
         a.c1 = (float)h->t_c2[i];
         a.c2 = expf(0.5f * (float)h->t_plv[i]);                    // exp(0.5*log_variance) (:556)
+    } else if (sampler == LS_SAMPLER_DDIM_REVERSE) {
+        // ddim_reverse_sample (:857-893): the DDIM epilogue's form with alphas_cumprod_next = append(alphas_cumprod[1:], 0.0) (:178) in
+        // place of alphas_cumprod_prev, no noise term at any t
+        a.sampler = kDDIM;
+        a.t_nonzero = 0;
+        const float abn = i + 1 < h->n_steps ? (float)h->t_ac[i + 1] : 0.0f;
+        a.c0 = (float)h->t_srac[i];
+        a.c1 = (float)h->t_srm1ac[i];
+        a.c2 = sqrtf(abn);                                         // (:888-891), fp32 on the cast value
+        a.c3 = sqrtf(1.0f - abn);
+        a.c4 = 0.0f;
     } else {
         a.sampler = kDDIM;
         const float ab = (float)h->t_ac[i], abp = (float)h->t_acp[i];
@@ -887,6 +900,35 @@ int stage_inpainting(ls_handle* h, const unsigned char* mask, const float* motio
     if (noise && (rc = ingest(h, h->inp_tape, noise, noise_elems * sizeof(float), on_device)) != LS_OK) return rc;
     if (old[0] != h->inp_m8.p || old[1] != h->inp_maskf.p || old[2] != h->inp_motion.p || old[3] != h->inp_tape.p) free_graph(h);
     return LS_OK;
+}
+
+// LS_SAMPLER_PLMS: the planes of plms_buf (stride in floats through *stride); a captured loop holds their addresses
+int plms_planes(ls_handle* h, size_t nelem, size_t* stride) {
+    const size_t ps = (nelem + 3) & ~(size_t)3;
+    const void* old = h->plms_buf.p;
+    HIPCHK(h, h->plms_buf.ensure(5 * ps * sizeof(float)));
+    if (old != h->plms_buf.p) free_graph(h);
+    *stride = ps;
+    return LS_OK;
+}
+
+// the launch behind a denoiser launch with sampler = kNone that left the model output in fwd_cfg: plms_sample's update at schedule index i
+// (:1059-1096).  Tables cast fp64 -> fp32 per step like _extract_into_tensor, the two square roots in fp32 on the cast value.
+hipError_t run_plms_update(ls_handle* h, int mode, int i, int nh, const float* x_t, const float* x_mid, const float* const* hist, float* out,
+                           float* eps_out, float* pred_out, int clip, size_t nelem, hipStream_t st) {
+    PlmsArgs p{};
+    p.x_t = x_t; p.x0 = h->fwd_cfg.f(); p.x_mid = x_mid;
+    for (int j = 0; j < 3; ++j) p.hist[j] = (hist && j < (mode == kPlmsEulerB ? 1 : nh)) ? hist[j] : nullptr;
+    p.out = out; p.eps_out = eps_out; p.pred_out = pred_out;
+    p.n = nelem; p.mode = mode; p.nh = nh; p.clip = clip; p.t_nonzero = i != 0;
+    const float abp = (float)h->t_acp[i];
+    p.c0 = (float)h->t_srac[i]; p.c1 = (float)h->t_srm1ac[i];
+    p.c2 = sqrtf(abp); p.c3 = sqrtf(1.0f - abp);
+    if (mode == kPlmsEulerB) {
+        if (i < 1) return hipErrorInvalidValue;
+        p.d0 = (float)h->t_srac[i - 1]; p.d1 = (float)h->t_srm1ac[i - 1];
+    }
+    return launch_plms_update(p, st);
 }
 
 // the launch behind a denoiser launch with sampler = kNone: mix, clamp, update (coefficients as fill_sampler left them in `s`)
@@ -1321,6 +1363,7 @@ void ls_destroy(ls_handle* h) {
         if (h->ev_seg[i]) (void)hipEventDestroy(h->ev_seg[i]);
     }
     h->coef.release();
+    h->plms_buf.release();
     h->inp_m8.release(); h->inp_maskf.release(); h->inp_motion.release(); h->inp_tape.release();
     h->trng_eps.release(); h->trng_noise.release(); h->trng_inz.release();
     if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
@@ -1673,8 +1716,12 @@ int ls_step(ls_handle* h, const ls_step_args* a) {
     if (!h->prepared) return fail(h, LS_ESTATE, "ls_step before ls_prepare");
     if (!h->have_sched) return fail(h, LS_ESTATE, "ls_step before ls_set_schedule");
     if (!a->indices && (a->index < 0 || a->index >= h->n_steps)) return fail(h, LS_EINVAL, "step index %d outside [0,%d)", a->index, h->n_steps);
-    if (!a->x || !a->eps_cond || !a->eps_uncond || !a->noise || !a->sample) return fail(h, LS_EINVAL, "ls_step: null pointer");
-    if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM) return fail(h, LS_EINVAL, "bad sampler");
+    const bool reverse = a->sampler == LS_SAMPLER_DDIM_REVERSE;
+    if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM && !reverse)
+        return fail(h, LS_EINVAL, a->sampler == LS_SAMPLER_PLMS ? "ls_step: PLMS steps go through ls_plms_step" : "bad sampler");
+    if (!a->x || !a->eps_cond || !a->eps_uncond || (!a->noise && !reverse) || !a->sample) return fail(h, LS_EINVAL, "ls_step: null pointer");
+    if (reverse && a->eta != 0.0f) return fail(h, LS_EINVAL, "DDIM_REVERSE: the reverse ODE is the deterministic path only (eta == 0)");
+    if (reverse && a->inpaint_mask) return fail(h, LS_EUNSUPPORTED, "DDIM_REVERSE is not combined with the inpainting branch");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, JF = h->JF, od = a->on_device;
     const size_t nx = (size_t)B * JF * h->T * sizeof(float);
@@ -1707,7 +1754,12 @@ int ls_step(ls_handle* h, const ls_step_args* a) {
     const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     HIPCHK(h, hipMemcpyAsync(h->eps.f(), a->eps_cond, (size_t)B * kD * sizeof(float), kind, st));
     HIPCHK(h, hipMemcpyAsync(h->eps.f() + (size_t)B * kD, a->eps_uncond, (size_t)B * kD * sizeof(float), kind, st));
-    if ((rc = ingest(h, h->noise, a->noise, nx, od)) != LS_OK) return rc;
+    if (a->noise) {
+        if ((rc = ingest(h, h->noise, a->noise, nx, od)) != LS_OK) return rc;
+    } else {                    // DDIM_REVERSE: no noise term (t_nonzero = 0); the kernels still get a valid plane
+        HIPCHK(h, h->noise.ensure(nx));
+        HIPCHK(h, hipMemsetAsync(h->noise.p, 0, nx, st));
+    }
     if ((rc = advance_tags(h, st)) != LS_OK) return rc;
     HIPCHK(h, coop_reset(h, st));
     StepArgs s;
@@ -1791,16 +1843,29 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
     if (!h || !a) return fail(h, LS_EINVAL, "ls_sample: null argument");
     if (!h->prepared) return fail(h, LS_ESTATE, "ls_sample before ls_prepare");
     if (!h->have_sched) return fail(h, LS_ESTATE, "ls_sample before ls_set_schedule");
-    if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM) return fail(h, LS_EINVAL, "bad sampler");
+    const bool plms = a->sampler == LS_SAMPLER_PLMS;
+    if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM && !plms)
+        return fail(h, LS_EINVAL, a->sampler == LS_SAMPLER_DDIM_REVERSE ? "ls_sample: DDIM_REVERSE is a single step (ls_step); the reference has no reverse loop" : "bad sampler");
     if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX && a->noise_mode != LS_NOISE_TORCH_DEVICE)
         return fail(h, LS_EINVAL, "bad noise_mode");
     if (a->skip_timesteps < 0 || a->skip_timesteps >= h->n_steps) return fail(h, LS_EINVAL, "skip_timesteps out of range");
+    if (!plms && a->plms_order != 0) return fail(h, LS_EINVAL, "plms_order is for LS_SAMPLER_PLMS only");
+    if (plms) {
+        if (a->plms_order == 1) return fail(h, LS_EINVAL, "PLMS: a loop of order 1 fails in the reference at its first step (no history); order 1 is DDIM with eta = 0");
+        if (a->plms_order < 2 || a->plms_order > 4) return fail(h, LS_EINVAL, "PLMS: order %d outside 1..4", a->plms_order);
+        if (h->n_steps - a->skip_timesteps < 2) return fail(h, LS_EINVAL, "PLMS needs at least two executed steps (the first one evaluates the model at t - 1)");
+        if (a->n_dump > 0 || a->dump_steps || a->const_noise || a->eta != 0.0f) return fail(h, LS_EINVAL, "PLMS takes no dump_steps, const_noise or eta");
+        if (a->seg_count > 0 || a->seg_begin != 0) return fail(h, LS_EUNSUPPORTED, "PLMS: segmented tapes are not built");
+        if (a->inpaint_mask || a->inpainted_motion || a->inpaint_noise) return fail(h, LS_EUNSUPPORTED, "PLMS is not combined with the inpainting branch");
+        if (a->noise_mode == LS_NOISE_TORCH_DEVICE) return fail(h, LS_EUNSUPPORTED, "PLMS: TORCH_DEVICE draws are not generated in the loop; hand them in as device tapes (TAPE mode)");
+        if (a->noise_mode == LS_NOISE_TAPE && a->noise_tape) return fail(h, LS_EINVAL, "PLMS draws no step noise: noise_tape must be NULL");
+    }
     if (a->seg_count > 0) return sample_segment(h, a);
     h->seg_next = -1;
     if (!a->out) return fail(h, LS_EINVAL, "ls_sample: null out");
     const bool tape = a->noise_mode == LS_NOISE_TAPE;
     const bool tdev = a->noise_mode == LS_NOISE_TORCH_DEVICE;
-    if (tape && (!a->x_init || !a->eps_tape || !a->noise_tape)) return fail(h, LS_EINVAL, "TAPE mode needs x_init, eps_tape and noise_tape");
+    if (tape && (!a->x_init || !a->eps_tape || (!a->noise_tape && !plms))) return fail(h, LS_EINVAL, "TAPE mode needs x_init, eps_tape and noise_tape");
     if (!tape && !tdev && a->const_noise) return fail(h, LS_EUNSUPPORTED, "const_noise is supported in TAPE and TORCH_DEVICE modes only");
     if (tdev && (a->sample_offset & 3)) return fail(h, LS_EINVAL, "TORCH_DEVICE: the generator offset %llu is not a multiple of 4", (unsigned long long)a->sample_offset);
     if (a->n_dump > 0 && (a->sampler != LS_SAMPLER_DDPM || !a->dump_steps || !a->dump_out))
@@ -1808,6 +1873,7 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, JF = h->JF, od = a->on_device;
     const int n_exec = h->n_steps - a->skip_timesteps;
+    const int n_eval = n_exec + (plms ? 1 : 0);           // model evaluations = pairs of style eps
     const size_t nelem = (size_t)B * JF * h->T;
     const size_t nx = nelem * sizeof(float);
     hipStream_t st = h->stream;
@@ -1849,9 +1915,16 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
     }
     if (tape) {
         const void* old_e = h->eps_tape.p; const void* old_n = h->noise_tape.p;
-        if ((rc = ingest(h, h->eps_tape, a->eps_tape, (size_t)n_exec * 2 * B * kD * sizeof(float), od)) != LS_OK) return rc;
-        if ((rc = ingest(h, h->noise_tape, a->noise_tape, (size_t)n_exec * nx, od)) != LS_OK) return rc;
+        if ((rc = ingest(h, h->eps_tape, a->eps_tape, (size_t)n_eval * 2 * B * kD * sizeof(float), od)) != LS_OK) return rc;
+        if (!plms && (rc = ingest(h, h->noise_tape, a->noise_tape, (size_t)n_exec * nx, od)) != LS_OK) return rc;
         if (old_e != h->eps_tape.p || old_n != h->noise_tape.p) free_graph(h);
+    }
+    size_t plms_stride = 0;
+    if (plms) {
+        if ((rc = plms_planes(h, nelem, &plms_stride)) != LS_OK) return rc;
+        const void* oldc = h->fwd_cfg.p;
+        HIPCHK(h, h->fwd_cfg.ensure(nx));
+        if (oldc != h->fwd_cfg.p) free_graph(h);
     }
     if (a->n_dump > 0) {
         const void* old = h->dump.p;
@@ -1902,6 +1975,7 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
                  a->skip_timesteps, a->noise_mode, a->const_noise, a->clip_denoised, h->weights_version, h->sched_version, (int)pair, a->n_dump, plan_code(h));
         key = keybuf;
         if (inpaint) key += inp_noised ? " I2" : " I1";
+        if (plms) key += " O" + std::to_string(a->plms_order);
         if (tdev) key += " R" + std::to_string(ring_k) + (a->x_init ? "x" : "X");
         for (int d = 0; d < a->n_dump; ++d) key += "," + std::to_string(a->dump_steps[d]);      // the whole list, however long
     }
@@ -1955,13 +2029,55 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
         }
         return LS_OK;
     };
+    // LS_SAMPLER_PLMS (:1016-1211): per executed step the denoiser alone (model output -> fwd_cfg) and k_plms_update; the first step
+    // evaluates twice.  One linear chain on the handle's stream, like the loop above.
+    auto enqueue_plms = [&]() -> int {
+        HIPCHK(h, coop_reset(h, st));
+        float* const ring = h->plms_buf.f();
+        float* const mid = ring + 4 * plms_stride;
+        unsigned e = 0;                                 // evaluation counter: index into eps_tape / Philox step_id
+        auto denoise = [&](const float* x, int i) -> int {
+            StepArgs m;
+            fill_common(h, m);
+            m.x_in = x; m.x0_out = h->fwd_cfg.f();
+            m.temb = h->temb.f() + (size_t)i * kD; m.temb_stride = 0;     // model timestep timestep_map[i] (_WrappedModel)
+            m.step_id = e;
+            if (tape) {
+                m.eps_c = h->eps_tape.f() + ((size_t)e * 2 + 0) * B * kD;
+                m.eps_u = h->eps_tape.f() + ((size_t)e * 2 + 1) * B * kD;
+            }
+            ++e;
+            HIPCHK(h, run_step(h, m, B, pair, st));
+            return LS_OK;
+        };
+        for (int k = 0; k < n_exec; ++k) {
+            const int i = n_exec - 1 - k;
+            const float* x_in = (k & 1) ? h->xb.f() : h->xa.f();
+            float* x_out = (k & 1) ? h->xa.f() : h->xb.f();
+            float* plane = ring + (size_t)(k & 3) * plms_stride;
+            int rc2;
+            if ((rc2 = denoise(x_in, i)) != LS_OK) return rc2;
+            if (k == 0) {
+                HIPCHK(h, run_plms_update(h, kPlmsEulerA, i, 0, x_in, nullptr, nullptr, mid, plane, nullptr, a->clip_denoised, nelem, st));
+                if ((rc2 = denoise(mid, i - 1)) != LS_OK) return rc2;
+                const float* h1[3] = {plane, nullptr, nullptr};
+                HIPCHK(h, run_plms_update(h, kPlmsEulerB, i, 1, x_in, mid, h1, x_out, nullptr, nullptr, a->clip_denoised, nelem, st));
+                continue;
+            }
+            const int nh = (a->plms_order < k + 1 ? a->plms_order : k + 1) - 1;
+            const float* hist[3] = {nullptr, nullptr, nullptr};
+            for (int j = 0; j < nh; ++j) hist[j] = ring + (size_t)((k - 1 - j) & 3) * plms_stride;
+            HIPCHK(h, run_plms_update(h, kPlmsMulti, i, nh, x_in, nullptr, hist, x_out, plane, nullptr, a->clip_denoised, nelem, st));
+        }
+        return LS_OK;
+    };
     h->timing.graph_replayed = 0;
     HIPCHK(h, hipEventRecord(h->ev[1], st));
     if (a->use_graph) {
         if (!h->graph_exec || h->graph_key != key) {
             free_graph(h);
             HIPCHK(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            rc = enqueue_loop();
+            rc = plms ? enqueue_plms() : enqueue_loop();
             hipGraph_t g = nullptr;
             hipError_t e = hipStreamEndCapture(st, &g);
             if (rc != LS_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
@@ -1975,7 +2091,7 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
         }
         HIPCHK(h, hipGraphLaunch(h->graph_exec, st));
     } else {
-        if ((rc = enqueue_loop()) != LS_OK) return rc;
+        if ((rc = plms ? enqueue_plms() : enqueue_loop()) != LS_OK) return rc;
     }
     HIPCHK(h, hipEventRecord(h->ev[2], st));
     const float* final_x = (n_exec & 1) ? h->xb.f() : h->xa.f();
@@ -1992,10 +2108,91 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
     report_path(h, pair);
     HIPCHK(h, hipEventElapsedTime(&h->timing.loop_ms, h->ev[1], h->ev[2]));
     HIPCHK(h, hipEventElapsedTime(&h->timing.total_ms, h->ev[0], h->ev[3]));
-    h->timing.n_step_launches = n_exec;
+    h->timing.n_step_launches = n_eval;
     h->timing.single_pass = pair ? 1 : 0;
     h->timing.tape_upload_ms = 0.f;
     h->timing.n_segments = 1;
+    return LS_OK;
+}
+
+// One plms_sample (gaussian_diffusion.py:1016-1098): the launches an LS_SAMPLER_PLMS loop makes for that step, on caller-held tensors.
+int ls_plms_step(ls_handle* h, const ls_plms_step_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_plms_step: null argument");
+    if (!h->prepared) return fail(h, LS_ESTATE, "ls_plms_step before ls_prepare");
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_plms_step before ls_set_schedule");
+    if (a->index < 0 || a->index >= h->n_steps) return fail(h, LS_EINVAL, "step index %d outside [0,%d)", a->index, h->n_steps);
+    if (a->order < 1 || a->order > 4) return fail(h, LS_EINVAL, "PLMS: order %d outside 1..4", a->order);
+    if (a->n_hist < 0 || a->n_hist > 3) return fail(h, LS_EINVAL, "PLMS: n_hist %d outside 0..3", a->n_hist);
+    if (!a->x || !a->eps_cond || !a->eps_uncond || !a->sample) return fail(h, LS_EINVAL, "ls_plms_step: null pointer");
+    const bool first = a->n_hist == 0;
+    if (first && a->order == 1) return fail(h, LS_EINVAL, "PLMS: order 1 without a history fails in the reference (old_out is None)");
+    if (first && a->index < 1) return fail(h, LS_EINVAL, "PLMS: the first step of a loop evaluates the model at index - 1; index must be >= 1");
+    if (first && (!a->eps_cond2 || !a->eps_uncond2)) return fail(h, LS_EINVAL, "PLMS: the first step needs the style eps of its second evaluation");
+    for (int j = 0; j < a->n_hist; ++j) if (!a->hist[j]) return fail(h, LS_EINVAL, "PLMS: hist[%d] is null", j);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int B = h->B, JF = h->JF, od = a->on_device;
+    const size_t nelem = (size_t)B * JF * h->T, nx = nelem * sizeof(float);
+    hipStream_t st = h->stream;
+    int rc;
+    size_t ps = 0;
+    if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
+    if ((rc = plms_planes(h, nelem, &ps)) != LS_OK) return rc;
+    HIPCHK(h, h->xa.ensure(nx)); HIPCHK(h, h->xb.ensure(nx)); HIPCHK(h, h->fwd_cfg.ensure(nx)); HIPCHK(h, h->xtmp.ensure(nx));
+    float* const ring = h->plms_buf.f();
+    float* const mid = ring + 4 * ps;
+    if ((rc = ingest(h, h->xio, a->x, nx, od)) != LS_OK) return rc;
+    HIPCHK(h, launch_to_internal(h->xio.f(), h->xa.f(), B, JF, st, h->T));
+    // old_eps, newest first, into planes 0 .. n_hist - 1; this step's eps goes to plane 3
+    const int nh = (a->order < a->n_hist + 1 ? a->order : a->n_hist + 1) - 1;
+    const float* hist[3] = {nullptr, nullptr, nullptr};
+    for (int j = 0; j < nh; ++j) {
+        if ((rc = ingest(h, h->xio, a->hist[a->n_hist - 1 - j], nx, od)) != LS_OK) return rc;
+        HIPCHK(h, launch_to_internal(h->xio.f(), ring + (size_t)j * ps, B, JF, st, h->T));
+        hist[j] = ring + (size_t)j * ps;
+    }
+    float* const plane = ring + 3 * ps;
+    const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const size_t ne = (size_t)B * kD;
+    HIPCHK(h, h->eps.ensure(4 * ne * sizeof(float)));
+    HIPCHK(h, hipMemcpyAsync(h->eps.f(), a->eps_cond, ne * sizeof(float), kind, st));
+    HIPCHK(h, hipMemcpyAsync(h->eps.f() + ne, a->eps_uncond, ne * sizeof(float), kind, st));
+    if (first) {
+        HIPCHK(h, hipMemcpyAsync(h->eps.f() + 2 * ne, a->eps_cond2, ne * sizeof(float), kind, st));
+        HIPCHK(h, hipMemcpyAsync(h->eps.f() + 3 * ne, a->eps_uncond2, ne * sizeof(float), kind, st));
+    }
+    if ((rc = advance_tags(h, st)) != LS_OK) return rc;
+    HIPCHK(h, coop_reset(h, st));
+    const bool pair = h->fused && !h->use_long && h->all_scale_one && !a->two_pass_always;
+    auto denoise = [&](const float* x, int i, int e) -> int {
+        StepArgs m;
+        fill_common(h, m);
+        m.x_in = x; m.x0_out = h->fwd_cfg.f();
+        m.temb = h->temb.f() + (size_t)i * kD; m.temb_stride = 0;
+        m.eps_c = h->eps.f() + (size_t)(2 * e) * ne; m.eps_u = h->eps.f() + (size_t)(2 * e + 1) * ne;
+        HIPCHK(h, run_step(h, m, B, pair, st));
+        return LS_OK;
+    };
+    float* const pred = h->xtmp.f();                  // pred_xstart of the FIRST evaluation (clamped), internal layout
+    if ((rc = denoise(h->xa.f(), a->index, 0)) != LS_OK) return rc;
+    if (first) {
+        HIPCHK(h, run_plms_update(h, kPlmsEulerA, a->index, 0, h->xa.f(), nullptr, nullptr, mid, plane, pred, a->clip_denoised, nelem, st));
+        if ((rc = denoise(mid, a->index - 1, 1)) != LS_OK) return rc;
+        const float* h1[3] = {plane, nullptr, nullptr};
+        HIPCHK(h, run_plms_update(h, kPlmsEulerB, a->index, 1, h->xa.f(), mid, h1, h->xb.f(), nullptr, nullptr, a->clip_denoised, nelem, st));
+    } else {
+        HIPCHK(h, run_plms_update(h, kPlmsMulti, a->index, nh, h->xa.f(), nullptr, hist, h->xb.f(), plane, pred, a->clip_denoised, nelem, st));
+    }
+    HIPCHK(h, launch_from_internal(h->xb.f(), h->xio.f(), B, JF, st, h->T));
+    if ((rc = egress(h, a->sample, h->xio.f(), nx, od)) != LS_OK) return rc;
+    if (a->pred_xstart) {
+        HIPCHK(h, launch_from_internal(pred, h->xio.f(), B, JF, st, h->T));
+        if ((rc = egress(h, a->pred_xstart, h->xio.f(), nx, od)) != LS_OK) return rc;
+    }
+    if (a->eps_out) {
+        HIPCHK(h, launch_from_internal(plane, h->xio.f(), B, JF, st, h->T));
+        if ((rc = egress(h, a->eps_out, h->xio.f(), nx, od)) != LS_OK) return rc;
+    }
+    if (!(a->no_sync && od)) { HIPCHK(h, hipStreamSynchronize(st)); if ((rc = coop_check(h)) != LS_OK) return rc; }
     return LS_OK;
 }
 

@@ -262,6 +262,23 @@ struct InpaintArgs {
     float qa, qb, c0, c1, c2, c3, c4;
 };
 hipError_t launch_inpaint_update(const InpaintArgs& a, int B, hipStream_t st);
+// ---- PLMS update (ls_plms.hip): plms_sample's arithmetic (gaussian_diffusion.py:1059-1096) after a denoiser launch with sampler = kNone.
+// Elementwise on flat arrays of n floats (every operand in the internal [B][T][JF] layout, 16-byte aligned):
+//   kPlmsMulti   x0 = clamp?(x0); eps = (c0 * x_t - x0) / c1; eps' = Adams-Bashforth over (eps, hist[0], hist[1], hist[2]) of order nh + 1
+//                (hist[0] = the newest OLD eps); out = t_nonzero ? (c0 * x_t - c1 * eps') * c2 + c3 * eps' : x0; eps_out = eps
+//   kPlmsEulerA  eps as above; out = x0 * c2 + c3 * eps (mean_pred, the second evaluation's input); eps_out = eps
+//   kPlmsEulerB  x0 = the SECOND evaluation's output, taken at x_mid = mean_pred with the coefficients d0, d1 of t - 1:
+//                eps_2 = (d0 * x_mid - x0) / d1; eps' = (hist[0] + eps_2) / 2 applied to the original x_t as in kPlmsMulti
+// pred_out (nullable): the clamped x0 (kPlmsMulti / kPlmsEulerA: what plms_sample returns as pred_xstart).
+enum PlmsMode { kPlmsMulti = 0, kPlmsEulerA = 1, kPlmsEulerB = 2 };
+struct PlmsArgs {
+    const float* x_t; const float* x0; const float* x_mid; const float* hist[3];
+    float* out; float* eps_out; float* pred_out;
+    size_t n;
+    int mode, nh, clip, t_nonzero;
+    float c0, c1, c2, c3, d0, d1;
+};
+hipError_t launch_plms_update(const PlmsArgs& a, hipStream_t st);
 // bytes [n] -> 0.f / 1.f
 hipError_t launch_bytes_to_float(const unsigned char* src, float* dst, size_t n, hipStream_t st);
 hipError_t launch_randn_fill(float* out_btc, int B, int JF, const CallParams* call, unsigned stream_id,

@@ -5,7 +5,8 @@ Mirrors (names, argument meaning, error behaviour) of
 ``betas_for_alpha_bar`` (:52-70), ``GaussianDiffusion`` tables (:168-204), ``q_sample`` (:240-258),
 ``q_posterior_mean_variance`` (:260-282), ``p_mean_variance`` (:284-399), ``p_sample`` (:507-558), ``p_sample_loop`` (:608-671),
 ``p_sample_loop_progressive`` (:673-743), ``ddim_sample`` (:745-798), ``ddim_sample_loop`` (:895-943),
-``ddim_sample_loop_progressive`` (:945-1014) and ``_extract_into_tensor`` (:1651-1664).
+``ddim_sample_loop_progressive`` (:945-1014), ``ddim_reverse_sample`` (:857-893), ``plms_sample`` (:1016-1098), ``plms_sample_loop`` (:1100-1140),
+``plms_sample_loop_progressive`` (:1142-1211) and ``_extract_into_tensor`` (:1651-1664).
 
 Only the schedule tables live here (fp64 numpy, as in the reference).  All per-step arithmetic
 (CFG'd model evaluation + posterior / DDIM update) runs in the fused gfx950 step kernel behind the
@@ -343,6 +344,165 @@ class GaussianDiffusion:
                     eta=0.0, const_noise=False):
         return self._one_step(_lib.LS_SAMPLER_DDIM, model, x, t, clip_denoised, model_kwargs, eta, const_noise,
                               denoised_fn, cond_fn)
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
+        """x_{t+1} of the deterministic DDIM ODE (gaussian_diffusion.py:857-893): p_mean_variance's model call (two style draws, no step
+        noise) and the DDIM epilogue's arithmetic with alphas_cumprod_next -- one launch of the step kernel.  `t` may differ per sample
+        (34-frame models), as in ddim_sample."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        self._reject(denoised_fn, None, False, False)
+        self._no_inpainting(model_kwargs, "ddim_reverse_sample")
+        return self._one_step(_lib.LS_SAMPLER_DDIM_REVERSE, model, x, t, clip_denoised, model_kwargs, 0.0, False, None, None, mean_only=True)
+
+    # ------------------------------------------------------------------ PLMS
+    @staticmethod
+    def _no_inpainting(model_kwargs, what):
+        y = (model_kwargs or {}).get('y') or {}
+        if 'inpainting_mask' in y and 'inpainted_motion' in y:
+            raise NotImplementedError(f"{what}: the inpainting branch of p_mean_variance is built for p_sample / ddim_sample only "
+                                      "(no reference caller combines it with this sampler)")
+
+    @staticmethod
+    def _plms_order(order, loop, n_exec=None):
+        """The reference's check of `order` (:1034-1035; a non-integer is refused here too), and the two refusals of the loops: order 1
+        (the reference dies at its first step: old_out is None) and a single executed step (the reference evaluates the model at t = -1)."""
+        if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or not 1 <= order <= 4:
+            raise ValueError('order is invalid (should be int from 1-4).')
+        if loop and order == 1:
+            raise ValueError("plms_sample_loop with order=1 fails in the reference at its first step (old_out is None, "
+                             "gaussian_diffusion.py:1076); order 1 is the same sampler as ddim_sample_loop with eta=0: use that")
+        if loop and n_exec < 2:
+            raise ValueError(f"PLMS needs at least two executed steps (the first one evaluates the model at t - 1), got {n_exec}: "
+                             "lower skip_timesteps")
+        return int(order)
+
+    def plms_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, cond_fn_with_grad=False,
+                    order=2, old_out=None, *, index=None):
+        """One pseudo-linear-multistep step (gaussian_diffusion.py:1016-1098).  Without `old_out` (the first call of a loop) the model is
+        evaluated twice -- at (x, t) and at (mean_pred, t - 1) -- otherwise once; every evaluation draws its two style eps in the
+        reference's order, and there is no step noise.  Returns {"sample", "pred_xstart", "old_eps"}; "old_eps" is the list the reference
+        carries forward (the caller's list, appended to and trimmed in place as the reference does).  `t` is one value for the batch."""
+        order = self._plms_order(order, False)
+        self._reject(denoised_fn, cond_fn, False, cond_fn_with_grad)
+        self._no_inpainting(model_kwargs, "plms_sample")
+        first = old_out is None
+        if first and order == 1:
+            raise ValueError("plms_sample with order=1 needs old_out (the reference fails on old_out['old_eps'] with old_out None); "
+                             "order 1 is ddim_sample with eta=0")
+        old_eps = [] if first else old_out["old_eps"]
+        if not first and not old_eps and order > 1:
+            raise NotImplementedError("plms_sample: an EMPTY old_out['old_eps'] with order > 1 (no loop of the reference produces it)")
+        tdev = self.noise_source == "torch_device"
+        rdev = _torch_device(x.device, "plms_sample") if tdev else th.device("cpu")
+        eng = self._engine_for(model, model_kwargs, "plms_sample")
+        B = x.shape[0]
+        if index is None:
+            t_host = th.as_tensor(t).detach().cpu()
+            assert t_host.shape == (B,)             # gaussian_diffusion.py:311
+            if not bool((t_host == t_host[0]).all()):
+                raise NotImplementedError("plms_sample takes ONE timestep for the batch (the history is one plane per step)")
+            index = int(t_host[0])
+        if first and index < 1:
+            raise ValueError("plms_sample without old_out evaluates the model at t - 1: t must be >= 1")
+        draws = [th.randn(B, 1, eng.D, device=rdev) for _ in range(4 if first else 2)]     # (cond, uncond) per evaluation, in order
+        if x.is_cuda and not tdev:
+            draws = self._stage_step_draws(x.device, *draws)
+        out, x0, eps = eng.plms_step(index, order, x, (draws[0], draws[1]), hist=old_eps[-3:], eps2=(draws[2], draws[3]) if first else None,
+                                     clip_denoised=clip_denoised, two_pass_always=self.two_pass_always, no_sync=x.is_cuda)
+        dev = x.device
+        old_eps.append(_as_tensor(eps, dev))
+        if len(old_eps) >= order:                   # :1092-1093
+            old_eps.pop(0)
+        return {"sample": _ref_strides(_as_tensor(out, dev)), "pred_xstart": _ref_strides(_as_tensor(x0, dev)), "old_eps": old_eps}
+
+    def _plms_progressive(self, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image, order):
+        if device is None:
+            device = next(model.parameters()).device
+        if self.noise_source == "torch_device":
+            device = _torch_device(device, "sample loop")
+        if noise is not None:
+            img = noise
+        elif self.noise_source == "torch_device":
+            img = th.randn(*shape, device=device)
+        else:
+            img = th.randn(*shape)
+        img = img.to(device)
+        if skip_timesteps and init_image is None:
+            init_image = th.zeros_like(img)
+        indices = list(range(self.num_timesteps - skip_timesteps))[::-1]
+        if init_image is not None:
+            eng = self._engine_for(model, model_kwargs, "sample loop")
+            img = _as_tensor(eng.q_sample(indices[0], _as_tensor(init_image, img.device).float().contiguous(), img.float().contiguous()), img.device)
+        old_out = None
+        for i in indices:
+            t = th.full((shape[0],), i, dtype=th.long)
+            out = self.plms_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, order=order, old_out=old_out, index=i)
+            yield out
+            old_out = out
+            img = out["sample"]
+
+    def plms_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                     model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
+                                     randomize_class=False, cond_fn_with_grad=False, order=2):
+        """gaussian_diffusion.py:1142-1211; one yield per executed step, each the launches the whole loop makes for it."""
+        order = self._plms_order(order, True, self.num_timesteps - skip_timesteps)
+        shape, model_kwargs = self._progressive_args(model, shape, denoised_fn, cond_fn, model_kwargs, randomize_class, cond_fn_with_grad)
+        self._no_inpainting(model_kwargs, "plms_sample_loop_progressive")
+        return self._plms_progressive(model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image, order)
+
+    def plms_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
+                         device=None, progress=False, skip_timesteps=0, init_image=None, randomize_class=False,
+                         cond_fn_with_grad=False, order=2):
+        """gaussian_diffusion.py:1100-1140: the whole loop as one ls_sample call (LS_SAMPLER_PLMS: a captured graph of denoiser and
+        k_plms_update launches, n_exec + 1 model evaluations).  Draws, in the reference's order: x_T (unless `noise`), then the two
+        style eps of every evaluation."""
+        n_exec = self.num_timesteps - skip_timesteps
+        order = self._plms_order(order, True, n_exec)
+        self._reject(denoised_fn, cond_fn, randomize_class, cond_fn_with_grad)
+        self._no_inpainting(model_kwargs, "plms_sample_loop")
+        if self.noise_source not in ("torch_cpu", "torch_device", "philox"):
+            raise ValueError(f"noise_source {self.noise_source!r}")
+        tdev = self.noise_source == "torch_device"
+        if tdev:                                    # refused before the engine is touched
+            _torch_device(device if device is not None else next(model.parameters()).device, "sample loop")
+        eng = self._engine_for(model, model_kwargs, "sample loop")
+        assert isinstance(shape, (tuple, list))
+        shape = tuple(int(v) for v in shape)
+        if shape != (eng.batch, eng.J, eng.F, eng.T):
+            raise ValueError(f"shape {shape} does not match the prepared conditioning {(eng.batch, eng.J, eng.F, eng.T)}")
+        if device is None:
+            device = next(model.parameters()).device
+        B, D, n_eval = shape[0], eng.D, n_exec + 1
+        kw = dict(sampler=_lib.LS_SAMPLER_PLMS, plms_order=order, x_init=noise, init_image=init_image, skip_timesteps=skip_timesteps,
+                  use_graph=self.use_graph, clip_denoised=clip_denoised, two_pass_always=self.two_pass_always,
+                  device_out=th.device(device).type == "cuda")
+        if self.noise_source == "philox":
+            drawn = int(th.randint(0, 2 ** 62, (1,)).item())
+            self.last_philox_seed = drawn if self.philox_seed is None else int(self.philox_seed)
+            kw["philox_seed"] = self.last_philox_seed
+            kw["sample_offset"] = int(getattr(self, "sample_offset", 0))
+        else:
+            tape_bytes = n_eval * 2 * B * D * 4
+            if tape_bytes > self.tape_segment_bytes:
+                raise ValueError(f"plms_sample_loop: the style-eps tape of this call is {tape_bytes} bytes, tape_segment_bytes is "
+                                 f"{self.tape_segment_bytes}; segmented tapes are not built for PLMS (raise tape_segment_bytes or "
+                                 "use noise_source='philox')")
+            rdev = th.device("cpu")
+            if tdev:
+                rdev = _torch_device(device, "sample loop")
+                if rdev.index != eng.device:
+                    raise ValueError(f"noise_source='torch_device': the model's engine runs on cuda:{eng.device}, the draws would come from {rdev}")
+                self.last_device_rng_native = False     # torch's own device draws, handed in as a device tape
+            if noise is None:
+                kw["x_init"] = th.randn(*shape, device=rdev)
+            eps = th.empty(n_eval, 2, B, D, device=rdev)
+            for e in range(n_eval):                 # ClassifierFreeSampleModel: cond pass, then uncond pass (RAG.py:10-13)
+                eps[e, 0] = th.randn(B, 1, D, device=rdev)[:, 0]
+                eps[e, 1] = th.randn(B, 1, D, device=rdev)[:, 0]
+            kw["eps_tape"] = eps
+            self.last_tape_segments = 1
+        res = eng.sample(**kw)
+        return _ref_strides(_as_tensor(res, device))
 
     # ------------------------------------------------------------------ loops
     def _loop(self, sampler, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image,
