@@ -1,0 +1,246 @@
+// Host-only declarations shared by the translation units behind include/ls_hip.h (ls_api.cpp: handle, weights, schedule, preparation;
+// ls_plan.cpp: the step plan and the step launchers; ls_sample.cpp: the diffusion loop and the single-step entries): the handle,
+// error reporting, copies between caller and internal buffers, and the guard of buffers a captured loop holds by address.
+#pragma once
+#include "ls_hip.h"
+#include "ls_internal.h"
+
+#include <map>
+#include <string>
+#include <vector>
+
+namespace ls {
+
+// a device allocation that only grows; freed with its owner (the handle's device must be current)
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    hipError_t ensure(size_t n) {
+        if (n <= bytes) return hipSuccess;
+        if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; bytes = 0; }
+        hipError_t e = hipMalloc(&p, n);
+        if (e == hipSuccess) bytes = n;
+        return e;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    float* f() const { return static_cast<float*>(p); }
+};
+
+// one piece of a step plan: samples [first, first + n) of the prepared batch on one kernel family
+// (0 fused: one workgroup per sample, 1 batch-level kernels, 2 sample-split kernel, 3 one workgroup per (sample, pass))
+struct Seg { int path, first, n; };
+
+}  // namespace ls
+using ls::DevBuf; using ls::Seg;
+
+struct ls_handle {
+    ls_config cfg{};
+    ls::Variant var = ls::kTED;
+    int JF = 0, S = 0, R = 0, NOB = 0, KXQ = 0, MK = 0, KIN = 0;
+    int T = ls::kT;             // frames; 34 = the reference's (fused step kernel), anything else = the long-sequence path (ls_long.hip)
+    bool fused = true;      // the model HAS the fused kernel (34 frames)
+    bool use_long = false;  // the prepared batch runs the batch-level kernels (always when !fused; small batches of a fused model)
+    int path_mode = 0;      // ls_set_path: 0 auto, 1 one workgroup per sample (fused kernel), 2 batch-level kernels, 3 sample-split kernel, 4 one workgroup per (sample, pass)
+    DevBuf pa_out, pa_cnt;  // CFG hand-off of the one-pass-per-workgroup kernel (ls_pass_kernel.h: two independent workgroups per CU): pass outputs [n][2][T][J*F], arrival tickets [n]
+    int pass_n = 0;         // samples the hand-off buffers hold
+    int pass_waves = 0;     // 0: 8-wave workgroups when the grid fits the chip once, 4-wave otherwise; 4: ls_set_path(5) forces the 4-wave form
+    int pass_waves_env = 0; // LS_PASS_WAVES = 4 | 8 forces one (-DLS_DEBUG builds only)
+    // the step plan of the prepared batch (decide_path): up to three pieces, e.g. 416 clips = 256 on the fused kernel + 128 on the
+    // one-pass-per-workgroup kernel (one workgroup per CU) + 32 on the sample-split kernel (ls_coop_kernel.h: 16 workgroups per sample).
+    int nseg = 1;
+    Seg seg[3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    bool plan_pair = false; // the plan assumed the single-pass form (every guidance scale 1)
+    DevBuf wtok1_img;       // token-mix operand of one pass (sample-split kernel)
+    DevBuf wtail;           // [L][S][4] token-mix weights of the ragged output rows 32 .. 35 (one-pass-per-workgroup kernel)
+    DevBuf wtok1_hi_img, wtok1_lo_img;   // the same as bf16 hi / lo planes (one-pass-per-workgroup kernel, bf16x3)
+    DevBuf co_x, co_part, co_gran, co_flag, co_err;      // its exchange workspaces (one launch's worth), granules / flags, timeout word
+    unsigned coop_launches = 0;                        // launches since the granule words were zeroed: epoch = 64 * ordinal
+    int n_cu = 256;         // compute units of the device (hipDeviceProp.multiProcessorCount): residency of the sample-split kernel, round sizes of the plans
+    int max_thr_cu = 2048;  // hipDeviceProp.maxThreadsPerMultiProcessor: with n_cu, the geometry of torch's randn launches (LS_NOISE_TORCH_DEVICE)
+    int coop_groups_max = ls::kCoopMaxGroups, coop_groups = 0;   // (sample, pass) groups per launch: cap of the 8-slice form (two workgroups per CU, eight per group), and what the workspaces hold
+    int coop_ncb = 0;       // slicing of the sample-split kernel: 0 = by the step-time model; 1 | 2 | 4 = 8 | 4 | 2 slice workgroups per (sample, pass) (ls_set_path 8 | 6 | 7)
+#ifndef LS_MIX_POSE_DEFAULT
+#define LS_MIX_POSE_DEFAULT 1
+#endif
+#ifndef LS_COOP_XMAP_DEFAULT
+#define LS_COOP_XMAP_DEFAULT -1
+#endif
+    int coop_xmap = LS_COOP_XMAP_DEFAULT;      // -1: by grid size (run_coop); otherwise the blockIdx -> (group, slice) mapping of the sample-split kernel (speed only; LS_COOP_XMAP in -DLS_DEBUG builds)
+    int tokpad = 160;       // token axis of lw_wtp
+    int JFP = 0;            // JF padded to a multiple of 32 (long path: K of the x_t projection)
+    DevBuf lw_wt, lw_wtp, lw_bt, lw_wc, lw_bc, lw_wcf, lw_bcf, lw_wsum, lw_winx, lw_wout;     // long path: row-major weights (wtp: Wt zero-padded to 160 x 160 in k_long_tokmix's per-lane fragment order)
+    DevBuf mx_wtok, mx_wch, mx_wpose, mx_pout, mx_xg, mx_gran;             // long-sequence mixer kernel (ls_mix_kernel.h): operand images, exchange workspace, granules
+    bool mix_pose = LS_MIX_POSE_DEFAULT;                            // env LS_MIX_POSE=0: poseFinal as a GEMM behind the mixer (A/B runs)
+    int mx_npt = 0;                                     // 16-column tiles of poseFinal inside the mixer; 0: poseFinal stays a GEMM
+    int mix_cap = 0;                                    // (sample, pass) groups per mixer launch; 0: the model has no such kernel (or ls_set_path(2) asked for the batch-level kernels)
+    DevBuf lx_proj, lx_X, lx_U, lx_OUT, lx_part1, lx_part2, lx_xpad;   // long path: workspaces (xpad: x_t rows padded to whole GEMM tiles)
+    int convL[5] = {0, 0, 0, 0, 0};
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};     // [0..3] sample / step timing, [4..5] ls_prepare, [6] host-input copies of ls_prepare_async
+    // segmented TAPE mode (ls_sample_args.seg_count > 0): tapes arrive in pieces, uploaded on a second stream into two device slots
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ev_cs[2] = {nullptr, nullptr}, ev_cd[2] = {nullptr, nullptr}, ev_seg[2] = {nullptr, nullptr};   // upload start / done, steps done (per slot)
+    bool slot_used[2] = {false, false}, upload_open[2] = {false, false};
+    int seg_next = -1, seg_index = 0, seg_skip = 0, seg_sampler = 0;
+    float seg_upload_ms = 0.f;
+    bool prepare_pending = false;                                                  // ls_prepare_async enqueued, prepare_ms not read back yet
+    std::string err;
+
+    std::map<std::string, std::vector<float>> w;   // host copies under the reference's state-dict keys
+    bool committed = false;
+    unsigned weights_version = 0;
+
+    // device weights
+    DevBuf wch_hi_img, wch_lo_img, wch_lo2_img, ww_hi_img, ww_lo_img;
+    DevBuf wch_img, bch, ln1a, ln1b, ln2a, ln2b, ww_img, btok_rows, winx_img, wout_img, wout_reg_img, bout, devw;
+    DevBuf conv_img[4];     // MFMA operand images of the stride-6 conv layers (ls_conv.hip)
+    DevBuf conv_w[4], conv_b[4], win_pre, win_aud, win_bias, spk_emb, ml_w, ml_b, emo_emb;
+    int KPP = 0;            // prefix-pose + bit columns of input_mapping, padded to the GEMM's K tile
+    DevBuf te_w0, te_b0, te_w2, te_b2, pe;
+
+    // schedule
+    bool have_sched = false;
+    unsigned sched_version = 0;
+    int n_steps = 0;
+    std::vector<long long> tmap;
+    std::vector<double> t_sac, t_s1mac, t_c1, t_c2, t_plv, t_ac, t_acp, t_srac, t_srm1ac;
+    DevBuf temb, temb_tmp, tmap_dev;
+    bool temb_valid = false;
+
+    // per-call state
+    int B = 0;              // prepared batch
+    bool prepared = false;
+    bool all_scale_one = false;   // every y['scale'] == 1: the CFG combination equals the cond output -> single-pass kernel
+    DevBuf audio, origin_x, vid, emo, scale;
+    DevBuf c1, c2, c3, c4, st1, st2, st3, feat_c, feat_u, static_c, static_u, z, z_ml, z_mu, z_logvar, z_std, emo_tok;
+    DevBuf audio_feat, spart;
+    DevBuf xa, xb, xtmp, xio, fwd_c, fwd_u, fwd_cfg, eps, noise, tfwd, tfwd_tmp, tidx, dump, trace, callp;
+    DevBuf eps_tape, noise_tape;
+    DevBuf inp_m8, inp_maskf, inp_motion, inp_tape;     // inpainting branch: mask bytes / mask as 0-1 floats and motion in the internal layout, q_sample noise tape
+    DevBuf eps_slot[2], noise_slot[2], coef;
+    DevBuf plms_buf;        // LS_SAMPLER_PLMS: five planes [B][T][JF] (each padded to whole 16-byte groups): a ring of four eps planes (step k
+                            // writes plane k & 3 and reads the up to three before it) + mean_pred of the two-evaluation first step
+    // LS_NOISE_TORCH_DEVICE: a ring of K steps' draws (eps [K][2][B][D], noise [K][B][J][F][T], inpainting re-noise [K][B][J][F][T]),
+    // refilled by one generator launch per K steps inside the loop; K = what fits in trng_ring_bytes (ls_set_torch_ring_bytes)
+    DevBuf trng_eps, trng_noise, trng_inz;
+    size_t trng_ring_bytes = (size_t)256 << 20;
+    std::string coef_key;   // (sampler, eta, schedule) the per-index coefficient table `coef` was built for
+
+    // cached graph of the step loop
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t graph_exec = nullptr;
+    std::string graph_key;
+
+    ls_timing timing{};
+    ls::CallParams call_host{0, 0, 0, 0};
+    unsigned tag_base = 0;  // sample-split kernel: base of the current call's hand-off tags (CallParams::tag_base)
+    int precision = 0;      // LS_PRECISION_*: 0 fp32 (split-fp32 channel mixing in k_step), 1 bf16x3, 2 fp32 MFMA throughout (ls_set_precision)
+#ifdef LS_DEBUG             // profiling variant of the library only (build_library(defines=['LS_DEBUG'])); never in the shipped .so
+    DevBuf prof, wgt;       // wgt: [1024][2] start / end stamps of every workgroup of the last step launch
+    bool prof_on = false;   // LS_PROF=<workgroup index>: in-kernel s_memtime phase stamps, read with ls_read("prof")
+    int prof_wg = 0;
+    int ablate = 0;         // LS_ABLATE (results are wrong when non-zero)
+#endif
+};
+
+namespace ls {
+
+// ---- defined in ls_api.cpp
+int fail(ls_handle* h, int code, const char* fmt, ...);     // records the message (h == nullptr: this thread's ls_create error), returns code
+int ensure_temb_table(ls_handle* h);
+int build_temb_rows(ls_handle* h, const long long* idx_dev, int n, DevBuf& tmp, DevBuf& out);
+void resolve_prepare_timing(ls_handle* h, bool block);
+// ---- defined in ls_plan.cpp
+int seg_n(const ls_handle* h, int path);
+long long plan_code(const ls_handle* h);
+int coop_cap(int n_cu, int ncb);
+void decide_path(ls_handle* h);
+hipError_t run_step(ls_handle* h, StepArgs& s, int B, bool pair, hipStream_t st);
+hipError_t coop_reset(ls_handle* h, hipStream_t st);
+int advance_tags(ls_handle* h, hipStream_t st);
+int coop_check(ls_handle* h);
+void report_path(ls_handle* h, bool pair);
+
+#define HIPCHK(h, expr)                                                                         \
+    do {                                                                                        \
+        hipError_t e__ = (expr);                                                                \
+        if (e__ != hipSuccess)                                                                  \
+            return ::ls::fail((h), LS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+    } while (0)
+
+// copy a caller buffer (host or device) into an internal device buffer
+inline int ingest(ls_handle* h, DevBuf& d, const void* src, size_t bytes, int on_device) {
+    HIPCHK(h, d.ensure(bytes ? bytes : 4));
+    if (bytes) HIPCHK(h, hipMemcpyAsync(d.p, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    return LS_OK;
+}
+// the same from a host temporary: finished before it dies
+inline int upload(ls_handle* h, DevBuf& d, const void* src, size_t bytes) {
+    const int rc = ingest(h, d, src, bytes, 0);
+    if (rc == LS_OK && bytes) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return rc;
+}
+inline int egress(ls_handle* h, void* dst, const void* src, size_t bytes, int on_device) {
+    HIPCHK(h, hipMemcpyAsync(dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    return LS_OK;
+}
+
+inline void free_graph(ls_handle* h) {
+    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
+    if (h->graph) (void)hipGraphDestroy(h->graph);
+    h->graph_exec = nullptr;
+    h->graph = nullptr;
+    h->graph_key.clear();
+}
+
+// A captured loop holds raw device addresses.  Every buffer its launches can read or write grows through here: a buffer that moved
+// drops the graph, so a replay never runs against freed memory.  *moved (optional): the memory is fresh.
+inline int ensure_pinned(ls_handle* h, DevBuf& d, size_t bytes, bool* moved = nullptr) {
+    const void* const was = d.p;
+    HIPCHK(h, d.ensure(bytes));
+    if (moved) *moved = was != d.p;
+    if (was != d.p) free_graph(h);
+    return LS_OK;
+}
+inline int ingest_pinned(ls_handle* h, DevBuf& d, const void* src, size_t bytes, int on_device) {
+    const int rc = ensure_pinned(h, d, bytes ? bytes : 4);
+    return rc != LS_OK ? rc : ingest(h, d, src, bytes, on_device);
+}
+
+// a caller tensor [B][J][F][T] -> the internal layout [B][T][JF] at dst (through xio), and back (through `stage`, xio unless given)
+inline int ingest_internal(ls_handle* h, const float* src, float* dst, int B, int on_device) {
+    const int rc = ingest(h, h->xio, src, (size_t)B * h->JF * h->T * sizeof(float), on_device);
+    if (rc != LS_OK) return rc;
+    HIPCHK(h, launch_to_internal(h->xio.f(), dst, B, h->JF, h->stream, h->T));
+    return LS_OK;
+}
+inline int egress_internal(ls_handle* h, const float* src, float* dst, int B, int on_device, float* stage = nullptr) {
+    if (!stage) stage = h->xio.f();
+    HIPCHK(h, launch_from_internal(src, stage, B, h->JF, h->stream, h->T));
+    return egress(h, dst, stage, (size_t)B * h->JF * h->T * sizeof(float), on_device);
+}
+
+// the cond / uncond pair of style eps of one model evaluation -> dst[0 .. B*kD), dst[B*kD .. 2*B*kD)
+inline int ingest_eps_pair(ls_handle* h, float* dst, const float* eps_cond, const float* eps_uncond, int on_device) {
+    const size_t ne = (size_t)h->B * kD;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    HIPCHK(h, hipMemcpyAsync(dst, eps_cond, ne * sizeof(float), kind, h->stream));
+    HIPCHK(h, hipMemcpyAsync(dst + ne, eps_uncond, ne * sizeof(float), kind, h->stream));
+    return LS_OK;
+}
+
+// the single-pass form of a step (two samples' cond pass per workgroup): legal when every guidance scale is 1
+inline bool single_pass(const ls_handle* h, int two_pass_always) { return h->fused && !h->use_long && h->all_scale_one && !two_pass_always; }
+
+// the tail of a single-step entry: wait and check, unless the caller keeps everything on the device and asked not to
+inline int sync_and_check(ls_handle* h, int no_sync, int on_device) {
+    if (no_sync && on_device) return LS_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return coop_check(h);
+}
+
+}  // namespace ls

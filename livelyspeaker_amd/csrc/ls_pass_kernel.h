@@ -11,7 +11,7 @@
 // Mapping:
 //   * workgroup = (sample b, pass p), blockIdx = b * npass + p.  Two forms of the one template (NW waves):
 //       NW = 8   64 channels per wave, as in k_step; ONE workgroup per CU (its registers leave no room for a second).  Two waves per SIMD
-//                hide each other's LDS / L2 round trips.  Used when the grid fits the chip once (ls_api.cpp run_pass).
+//                hide each other's LDS / L2 round trips.  Used when the grid fits the chip once (ls_plan.cpp run_pass).
 //       NW = 4   128 channels per wave, up to 256 VGPRs; TWO independent workgroups per CU, not phase-locked by a common barrier (wave
 //                priority keeps them level).  Used for grids beyond one workgroup per CU.
 //     Wave w owns channels [CHW w, CHW w + CHW) of all rows in the MFMA C/D layout (lane & 15 = row of the tile, 4 (lane >> 4) + reg = channel

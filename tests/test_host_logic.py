@@ -97,8 +97,11 @@ def test_shipped_library_has_no_debug_switches():
     assert b"getenv" not in blob
     src = open(os.path.join(ROOT, "livelyspeaker_amd", "_lib.py")).read()
     assert "os.environ" not in src
-    for f in ("ls_api.cpp", "ls_sag_api.cpp", "ls_train_api.cpp"):
-        text = open(os.path.join(ROOT, "livelyspeaker_amd", "csrc", f)).read()
+    csrc = os.path.join(ROOT, "livelyspeaker_amd", "csrc")
+    host = sorted(f for f in os.listdir(csrc) if f.endswith(".cpp"))
+    assert {"ls_api.cpp", "ls_plan.cpp", "ls_sample.cpp", "ls_sag_api.cpp", "ls_train_api.cpp"} <= set(host)
+    for f in host:
+        text = open(os.path.join(csrc, f)).read()
         for m in re.finditer(r"getenv", text):
             before = text[:m.start()]
             assert before.rfind("#ifdef LS_DEBUG") > before.rfind("#endif"), f"{f}: getenv outside an LS_DEBUG block"

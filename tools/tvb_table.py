@@ -10,7 +10,7 @@ FAM = {"coop8": "sample-split x8", "coop4": "sample-split x4", "coop2": "sample-
 NAMES = {0: "fused", 1: "batch-level", 2: "sample-split", 3: "one-pass-per-workgroup"}
 out = [f"# {title}: step time vs batch, by kernel family (MI355X, 30-step DDPM, CFG 1.5, Philox noise, hipGraph replay)", "",
        "`python tools/coop_time.py <ds> 30 <batches> coop8,coop4,coop2,batch,pass,fused,auto` (sample-split with 8 / 4 / 2 slice workgroups per (clip, CFG pass)) in the round's final measurement set (one box, one run; ms per step | pose-frames/s",
-       "extrapolated to a 1000-step call = B * 34 / ms).  `auto` = the plan `plan_steps` (ls_api.cpp) makes from its step-time model; the last column",
+       "extrapolated to a 1000-step call = B * 34 / ms).  `auto` = the plan `plan_steps` (ls_plan.cpp) makes from its step-time model; the last column",
        "says which pieces it ran: family, then `+ n clips on family` for the second / third piece.  one-pass-per-workgroup = `k_pass`: 8-wave",
        "workgroups, one per CU, while the grid fits the chip once (B <= 128), 4-wave workgroups, two per CU, beyond.", ""]
 for ds, fname in (("TED (S = 35, J*F = 27)", "tvb_ted.txt"), ("BEAT (S = 36, J*F = 282)", "tvb_beat.txt")):
