@@ -7,6 +7,9 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     ->  post-processing (aligned motions, poses, motion beats)  ->  FGD / diversity against the "real" clips
 
     python examples/livelyspeaker_ted.py [batch]
+    python examples/livelyspeaker_ted.py [batch] --from-motion
+--from-motion edits a RECORDED clip instead: no text feature is needed, the SAG encoder turns the clip into the CLIP-aligned latent
+(recorded clip -> SAG(batch) = MOTIONCLIP.forward -> init_image -> the same 20-step refinement).
 With real data: load RAG.pt / SAG.pth / the auto-encoder checkpoint with load_model_wo_clip / load_state_dict and build `cond`
 exactly as the reference script does; everything below the weight loading is unchanged.
 """
@@ -21,6 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from livelyspeaker_amd import synth                                                   # noqa: E402
 from livelyspeaker_amd.cfg_sampler import ClassifierFreeSampleModel                   # noqa: E402
 from livelyspeaker_amd.model_util import create_model_and_diffusion, load_model_wo_clip   # noqa: E402
+from livelyspeaker_amd.motionclip import get_SAG                                      # noqa: E402
 from livelyspeaker_amd.motionclip_module import Decoder_TRANSFORMER                   # noqa: E402
 from livelyspeaker_amd.postprocess import ted_postprocess                             # noqa: E402
 from livelyspeaker_amd.ted_evaluator import EmbeddingSpaceEvaluator                   # noqa: E402
@@ -45,6 +49,15 @@ def build(device="cuda:0"):
     return cfg, model, diffusion, sag_decoder, evaluator
 
 
+def build_sag(device="cuda:0"):
+    """The whole SAG model, loaded the way SAG.pth is loaded (encoder.* / decoder.* keys): motionclip.py:86-92."""
+    sag, _ = get_SAG(SimpleNamespace(n_pre_poses=4, use_style=False))          # second item: the CLIP text encoder in the reference
+    sag.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_sag_checkpoint(synth.TED).items()}, strict=False)
+    sag.to(device)
+    sag.eval()
+    return sag
+
+
 def make_inputs(cfg, B, device="cuda:0", guidance_param=2.5, seed=0):
     """What the reference's data loader + CLIP text encoder hand to the loop body (:63-100), on the device (`seed`: which loader batch)."""
     y = synth.make_cond(cfg, B, scale=guidance_param, seed=synth.SEED_COND + seed)
@@ -66,6 +79,19 @@ def infer(model, diffusion, sag_decoder, batch, cond, skip_steps=80, seed=233, n
     if hasattr(model, "prefetch_condition"):          # optional: the refinement's once-per-call stage overlaps the SAG decode
         model.prefetch_condition(cond["y"] if "y" in cond else cond)
     decoded_motions = sag_decoder(batch)["output"]
+    torch.manual_seed(seed)
+    sample = diffusion.ddim_sample_loop(model, (B, 9, 3, 34), clip_denoised=False, model_kwargs=cond, skip_timesteps=skip_steps,
+                                        init_image=decoded_motions, progress=False, dump_steps=None, noise=None, const_noise=False)
+    return decoded_motions, sample
+
+
+def infer_from_motion(model, diffusion, sag, batch, cond, skip_steps=80, seed=233, noise_source="philox"):
+    """Recorded clip -> SAG(batch) (encode to mu, z = mu, decode) -> guided refinement: batch needs 'x' and 'mask' only."""
+    diffusion.noise_source = noise_source
+    B = batch["x"].shape[0]
+    if hasattr(model, "prefetch_condition"):
+        model.prefetch_condition(cond["y"] if "y" in cond else cond)
+    decoded_motions = sag(batch)["output_xyz"]
     torch.manual_seed(seed)
     sample = diffusion.ddim_sample_loop(model, (B, 9, 3, 34), clip_denoised=False, model_kwargs=cond, skip_timesteps=skip_steps,
                                         init_image=decoded_motions, progress=False, dump_steps=None, noise=None, const_noise=False)
@@ -108,7 +134,12 @@ def main():
         i = sys.argv.index("--noise-source")
         noise_source = sys.argv[i + 1]
         del sys.argv[i:i + 2]
+    from_motion = "--from-motion" in sys.argv
+    if from_motion:
+        sys.argv.remove("--from-motion")
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+    if from_motion:
+        return main_from_motion(B, noise_source)
     if len(sys.argv) > 2:                                                                   # python examples/livelyspeaker_ted.py B N: N batches, pipelined
         return main_pipelined(B, int(sys.argv[2]))
     cfg, model, diffusion, sag_decoder, evaluator = build()
@@ -128,6 +159,25 @@ def main():
     print(f"B={B} ({noise_source}): SAG decode + 20-step guided refinement {dt * 1e3:.1f} ms ({B * 34 / dt:.0f} pose-frames/s); "
           f"motion beats {n_beats}; FGD {fgd:.4f}, feature distance {feat_dist:.4f} (synthetic weights: numbers are not quality)")
     assert bool(torch.isfinite(sample).all())
+
+
+def main_from_motion(B, noise_source):
+    cfg, model, diffusion, _, _ = build()
+    sag = build_sag()
+    vec_seq, batch, cond = make_inputs(cfg, B)
+    lengths = torch.full((B,), 34, device=vec_seq.device)
+    lengths[1::2] = 28                                                                      # every other recording is shorter
+    batch = {"x": batch["x"], "mask": sag.lengths_to_mask(lengths)}                         # no text feature: z comes from the encoder
+    infer_from_motion(model, diffusion, sag, dict(batch), cond, noise_source=noise_source)  # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    decoded, sample = infer_from_motion(model, diffusion, sag, batch, cond, noise_source=noise_source)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    print(f"B={B} ({noise_source}), from motion: SAG encode + decode + 20-step guided refinement {dt * 1e3:.1f} ms; encode "
+          f"{sag.encoder.engine().last_encode_ms():.3f} ms, decode {sag.decoder.engine().last_decode_ms():.3f} ms; "
+          f"|mu| mean {float(batch['mu'].norm(dim=-1).mean()):.3f}")
+    assert bool(torch.isfinite(sample).all()) and bool((decoded[1, :, :, 28:] == 0).all())
 
 
 def main_pipelined(B, N):

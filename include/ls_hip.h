@@ -405,6 +405,26 @@ int ls_sag_decode_async(ls_sag* h, int batch, const float* x, const float* z, co
 float ls_sag_last_decode_ms(const ls_sag* h);   /* GPU time of the last decode (HIP events on the handle's stream); waits for an asynchronous one */
 void* ls_sag_stream(const ls_sag* h);
 
+/* ---- SAG encoder -----------------------------------------------------------------------------------------
+ * Encoder_TRANSFORMER (scripts/model/motionclip_module.py:33-95, eval mode), the other half of MOTIONCLIP
+ * (scripts/model/motionclip.py:75-83): a motion clip -> the CLIP-aligned latent mu = z that the decoder consumes.
+ * Separate handle, configured by the decoder's config struct; its n_pre_poses field is ignored.  Weight keys are the module's own
+ * (muQuery, sigmaQuery, skelEmbedding.*, seqTransEncoder.layers.N.*; in SAG.pth they carry the prefix 'encoder.'); '*.pe' is ignored.
+ * A missing or mis-sized key fails in the commit call with the key named. */
+typedef struct ls_sag_enc ls_sag_enc;
+int ls_sag_enc_create(const ls_sag_config* cfg, ls_sag_enc** out);
+void ls_sag_enc_destroy(ls_sag_enc* h);
+const char* ls_sag_enc_last_error(const ls_sag_enc* h);
+int ls_sag_enc_set_weight(ls_sag_enc* h, const char* key, const float* data, size_t n);
+int ls_sag_enc_commit_weights(ls_sag_enc* h);
+/* batch['x'] [B,J,F,T], batch['mask'] [B,T] bytes (0 = padded frame: never attended to) or NULL (all true) -> mu [B,latent] */
+int ls_sag_enc_encode(ls_sag_enc* h, int batch, int on_device, const float* x, const unsigned char* mask, float* mu_out);
+/* The same, enqueued only (device pointers): `mu_out` is complete once ls_sag_enc_stream() has reached this point; a decoder handle
+ * consumes it without a host round trip after ls_stream_order(device, ls_sag_enc_stream(enc), ls_sag_stream(dec)). */
+int ls_sag_enc_encode_async(ls_sag_enc* h, int batch, const float* x, const unsigned char* mask, float* mu_out);
+float ls_sag_enc_last_encode_ms(const ls_sag_enc* h);   /* GPU time of the last encode; waits for an asynchronous one */
+void* ls_sag_enc_stream(const ls_sag_enc* h);
+
 /* ---- caller-side post-processing of sampled clips ---------------------------------
  * scripts/test_RAG_ted.py:84-111 (layout change, mean add, per-bone normalisation, joint-angle change curve, motion
  * beats) and convert_dir_vec_to_pose (scripts/utils/data_utils.py:77-97).  Stateless; dataset constants are passed in. */

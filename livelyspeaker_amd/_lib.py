@@ -110,7 +110,9 @@ class LsEvalConfig(C.Structure):
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
            "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
-           "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms", "ls_ted_post", "ls_beat_post",
+           "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
+           "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
+           "ls_sag_enc_encode", "ls_sag_enc_encode_async", "ls_sag_enc_last_encode_ms", "ls_sag_enc_stream", "ls_ted_post", "ls_beat_post",
            "ls_train_create", "ls_train_destroy", "ls_train_last_error", "ls_train_set_schedule", "ls_train_param_count",
            "ls_train_flat_size", "ls_train_param_info", "ls_train_set_weight", "ls_train_get_weight", "ls_train_forward_backward",
            "ls_train_adamw", "ls_train_read", "ls_train_get_moment", "ls_train_set_moment", "ls_train_get_step", "ls_train_set_step",
@@ -187,7 +189,7 @@ def load_library(build_if_missing: bool = True):
     lib.ls_get_timing.argtypes = [C.c_void_p, C.POINTER(LsTiming)]
     lib.ls_synchronize.argtypes = [C.c_void_p]
     lib.ls_stream_order.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-    for fn in ("ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream"):
+    for fn in ("ls_stream", "ls_sag_stream", "ls_sag_enc_stream", "ls_train_stream", "ls_eval_stream"):
         getattr(lib, fn).argtypes = [C.c_void_p]
         getattr(lib, fn).restype = C.c_void_p
     lib.ls_philox_x_init.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
@@ -215,6 +217,17 @@ def load_library(build_if_missing: bool = True):
     lib.ls_sag_decode_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ls_sag_last_decode_ms.argtypes = [C.c_void_p]
     lib.ls_sag_last_decode_ms.restype = C.c_float
+    lib.ls_sag_enc_create.argtypes = [C.POINTER(LsSagConfig), C.POINTER(C.c_void_p)]
+    lib.ls_sag_enc_destroy.argtypes = [C.c_void_p]
+    lib.ls_sag_enc_destroy.restype = None
+    lib.ls_sag_enc_last_error.argtypes = [C.c_void_p]
+    lib.ls_sag_enc_last_error.restype = C.c_char_p
+    lib.ls_sag_enc_set_weight.argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
+    lib.ls_sag_enc_commit_weights.argtypes = [C.c_void_p]
+    lib.ls_sag_enc_encode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ls_sag_enc_encode_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ls_sag_enc_last_encode_ms.argtypes = [C.c_void_p]
+    lib.ls_sag_enc_last_encode_ms.restype = C.c_float
     lib.ls_ted_post.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(LsPostConfig), C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]
     lib.ls_beat_post.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -756,6 +769,73 @@ class SagEngine:
             return out
         self._check(self.lib.ls_sag_decode(self.h, B, int(m.on_device), m.f32(x, (B, self.J, self.F, self.T)),
                                            m.f32(z, (B, self.D)), pmask, pout), "ls_sag_decode")
+        self._async_inputs = None
+        return out
+
+
+class SagEncoderEngine:
+    """ctypes wrapper of the SAG encoder handle (ls_sag_enc_*): Encoder_TRANSFORMER.forward (eval mode) on the GPU."""
+
+    def __init__(self, njoints=9, nfeats=3, nframes=34, latent_dim=512, ff_size=1024, num_layers=3, num_heads=4, device=0):
+        self.lib = load_library()
+        self.cfg = LsSagConfig(njoints, nfeats, nframes, latent_dim, ff_size, num_layers, num_heads, 0, device, 0)
+        self.h = C.c_void_p()
+        rc = self.lib.ls_sag_enc_create(C.byref(self.cfg), C.byref(self.h))
+        if rc != 0:
+            raise EngineError(f"ls_sag_enc_create failed ({rc}): {self.lib.ls_sag_enc_last_error(None).decode()}")
+        self.J, self.F, self.T, self.D, self.device = njoints, nfeats, nframes, latent_dim, device
+        self._stream = self.lib.ls_sag_enc_stream(self.h)
+        self._async_inputs = None
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.ls_sag_enc_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise EngineError(f"{what} failed ({rc}): {self.lib.ls_sag_enc_last_error(self.h).decode()}")
+
+    def load_state_dict(self, sd: dict):
+        for k, v in sd.items():
+            a = _np32(v)
+            self._check(self.lib.ls_sag_enc_set_weight(self.h, k.encode(), a.ctypes.data_as(c_f32p), a.size), f"ls_sag_enc_set_weight({k})")
+        self._check(self.lib.ls_sag_enc_commit_weights(self.h), "ls_sag_enc_commit_weights")
+
+    def last_encode_ms(self) -> float:
+        return float(self.lib.ls_sag_enc_last_encode_ms(self.h))
+
+    def encode(self, x, mask=None, wait=True):
+        """x [B, J, F, T], mask [B, T] bool (False = padded frame) or None -> mu [B, latent]: numpy in, numpy out; device tensors in, a
+        device tensor out.  ``wait=False`` (device tensors only): enqueue on the encoder's stream and return at once, without a host
+        wait.  torch's current stream is ordered behind the encode, so torch operations on ``mu`` issued from now on see it complete; a
+        consumer on another stream (the decoder's) is put behind it with ``stream_order(device, self._stream, that_stream)``."""
+        shape = tuple(int(s) for s in x.shape)
+        if len(shape) != 4 or shape[1:] != (self.J, self.F, self.T):
+            raise ValueError(f"x must be [B, {self.J}, {self.F}, {self.T}], got {list(shape)}")
+        B = shape[0]
+        if B < 1:
+            raise ValueError("x holds no clip")
+        if mask is not None and tuple(int(s) for s in mask.shape) != (B, self.T):
+            raise ValueError(f"mask must be [{B}, {self.T}], got {list(mask.shape)}")
+        m = _Marshal(self.device, x, mask, stream=self._stream)
+        if not wait and not m.on_device:
+            raise EngineError("encode(wait=False) needs device tensors")
+        px, pmask = m.f32(x, shape), m.u8(mask, (B, self.T))
+        out, pout = m.out((B, self.D))
+        m.ready()
+        if not wait:
+            self._check(self.lib.ls_sag_enc_encode_async(self.h, B, px, pmask, pout), "ls_sag_enc_encode_async")
+            m.done_async()
+            self._async_inputs = m          # the marshalled inputs stay referenced until the next encode on this (in-order) stream
+            return out
+        self._check(self.lib.ls_sag_enc_encode(self.h, B, int(m.on_device), px, pmask, pout), "ls_sag_enc_encode")
         self._async_inputs = None
         return out
 

@@ -29,7 +29,7 @@ namespace ls {
 typedef float f4 __attribute__((ext_vector_type(4)));
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-constexpr int kTM = 128, kTK = 32, kLdK = kTK + 4, kLdR = kTM + 4;
+constexpr int kTM = 128, kTK = kGemmTileK, kLdK = kTK + 4, kLdR = kTM + 4;
 #ifndef LS_GEMM_HALF_MAX
 #define LS_GEMM_HALF_MAX 768      // LDS-DMA grids of at most this many 64-row tiles run as 32-row half tiles (see launch_gemm_tr)
 #endif

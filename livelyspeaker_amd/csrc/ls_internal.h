@@ -325,4 +325,15 @@ hipError_t launch_layernorm512x2(const float* x, const float* w1, const float* b
 hipError_t launch_sag_final(const float* xh, const float* wf, const float* bf, const unsigned char* mask, float* out, int B,
                             int JF, int D, hipStream_t st);
 
+// ---- SAG encoder kernels (ls_sag_enc.hip; the attention is ls_sag.hip's, instantiated for 36 tokens with a key mask) ----
+constexpr int kSagEncS = kT + 2;     // tokens per sample: mu query, sigma query, 34 frames
+// tok rows [B*36][D]: rows 0, 1 = muQuery + pe[0], sigmaQuery + pe[1]; rows 2 + f = pe[f + 2] (the skelEmbedding GEMM adds itself onto them);
+// xt [B*34][KP] = x[b, :, f] zero-padded to KP columns; kmask [B][36] = (1, 1, mask[b]) (all ones when mask is null)
+hipError_t launch_sag_enc_prepare(const float* x, const unsigned char* mask, const float* mu_q, const float* sigma_q, const float* pe,
+                                  float* tok, float* xt, unsigned char* kmask, int B, int JF, int KP, hipStream_t st);
+hipError_t launch_sag_enc_attention(const float* qkv, const unsigned char* kmask, float* out, int B, int heads, int D, hipStream_t st);
+// the last layer's attention of token 0 alone: q0 [B][D] against kv rows [B*36][2D] = [k | v]
+hipError_t launch_sag_enc_attention_row0(const float* q0, const float* kv, const unsigned char* kmask, float* out, int B, int heads, int D,
+                                         hipStream_t st);
+
 }  // namespace ls

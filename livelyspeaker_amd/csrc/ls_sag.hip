@@ -37,36 +37,43 @@ __global__ void k_sag_queries(const float* __restrict__ x, const float* __restri
     }
 }
 
-// nn.MultiheadAttention self-attention of one (sample, head): softmax(q k^T / sqrt(hd)) v over the T = 34 queries -- the only
+// nn.MultiheadAttention self-attention of one (sample, head): softmax(q k^T / sqrt(hd)) v over its S tokens (the decoder's T = 34 frame queries, the encoder's 36) -- the only
 // QK^T / softmax / attn.V in the model (motionclip_module.py:98-183).  qkv rows are [q | k | v] of width 3*D (packed in_proj).
 // Workgroup = one sample, 4 waves, looping over its heads: the NEXT head's Q / K / V are fetched into registers while the current
 // head is computed (as one workgroup per (sample, head) the kernel was a chain of latencies -- global load, LDS, three barriers --
 // repeated over four rounds of 512 resident workgroups: 46 us at B = 512 for 2.4 MFLOP and 52 KB per pair).  Q (pre-scaled), K, V
-// [34][HD] are staged in LDS with row stride HD + 4 (conflict-free
-// ds_read_b128); both contractions run on v_mfma_f32_16x16x4_f32 with T padded to 3 tiles of 16 (rows past 33 are clamped on the
+// [S][HD] are staged in LDS with row stride HD + 4 (conflict-free
+// ds_read_b128); both contractions run on v_mfma_f32_16x16x4_f32 with S padded to 3 tiles of 16 (rows past S - 1 are clamped on the
 // read and never stored / masked):
 //   scores = Q K^T : 3 x 3 tiles, K-dim = HD in the k-permuted float4 order (lane (row, g) holds d = 16q + 4g + e for step e)
 //   softmax        : one wave per query row, lane = key; row max and row sum are wavefront reductions (DPP / readlane)
-//   out = P V      : 3 x (HD/16) tiles, K-dim = 36 keys (P's columns 34, 35 are written as zero)
-template <int HD>
+//   out = P V      : 3 x (HD/16) tiles, K-dim = KP = 36 keys (P's columns S..35 are written as zero: none at S = 36)
 // n_pre_c > 0: qkv holds the distinct rows only (k_sag_queries' qc order): sample b's frame t lives at row b * n_pre_c + t for
 // t < n_pre_c and at the shared row B * n_pre_c + (t - n_pre_c) otherwise.
-__global__ __launch_bounds__(256) void k_sag_attention(const float* __restrict__ qkv, float* __restrict__ out, int D, int heads, int n_pre_c) {
+// S = tokens per sample: 34 (the decoder's frame queries) or 36 (the encoder's mu / sigma tokens + 34 frames, ls_sag_enc.hip); both fit
+// the 3 x 3 score tiles and the KP = 36 padded keys.  MASK: kmask [B][S] bytes, 0 = padded key (src_key_padding_mask): its score is
+// -inf before the row maximum, so its probability is exactly 0.
+template <int HD, int S, bool MASK>
+__global__ __launch_bounds__(256) void k_sag_attention(const float* __restrict__ qkv, float* __restrict__ out, int D, int heads, int n_pre_c,
+                                                       const unsigned char* __restrict__ kmask) {
+    static_assert(S <= 36 && S % 2 == 0, "scores: 3 x 3 tiles of 16; P.V: 36 padded keys");
     constexpr int LQ = HD + 4, LP = 37, KP = 36;
-    __shared__ __attribute__((aligned(16))) float sq[kT * LQ], sk[kT * LQ], sv[kT * LQ];
-    __shared__ float sp[kT * LP];
+    __shared__ __attribute__((aligned(16))) float sq[S * LQ], sk[S * LQ], sv[S * LQ];
+    __shared__ float sp[S * LP];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int s16 = lane & 15, g = lane >> 4;
     const float scale = rsqrtf((float)HD);
-    constexpr int kF4 = kT * HD / 4, kPer = (kF4 + 255) / 256;
+    bool keep = true;                                             // lane = key in the softmax
+    if constexpr (MASK) keep = lane < S && kmask[b * S + lane] != 0;
+    constexpr int kF4 = S * HD / 4, kPer = (kF4 + 255) / 256;
     f4 vq[kPer], vk[kPer], vv[kPer];
     // this thread's share of one head's Q / K / V: float4 loads with a clamped index (branch-free, all in flight together)
     auto fetch = [&](int h) {
 #pragma unroll
         for (int j = 0; j < kPer; ++j) {
             const int idx = min(tid + 256 * j, kF4 - 1), t = idx / (HD / 4), d4 = idx % (HD / 4);
-            const int rr = n_pre_c <= 0 ? b * kT + t : (t < n_pre_c ? b * n_pre_c + t : (int)gridDim.x * n_pre_c + (t - n_pre_c));
+            const int rr = n_pre_c <= 0 ? b * S + t : (t < n_pre_c ? b * n_pre_c + t : (int)gridDim.x * n_pre_c + (t - n_pre_c));
             const float* row = qkv + (size_t)rr * 3 * D + h * HD + 4 * d4;
             vq[j] = *reinterpret_cast<const f4*>(row);
             vk[j] = *reinterpret_cast<const f4*>(row + D);
@@ -90,8 +97,8 @@ __global__ __launch_bounds__(256) void k_sag_attention(const float* __restrict__
         // ---- scores: tile (mt, nt) = w, w + 4, w + 8 of the 3 x 3 grid; lane holds S[a = 16 mt + 4 g + r][c = 16 nt + s16]
         for (int tile = w; tile < 9; tile += 4) {
             const int mt = tile / 3, nt = tile % 3;
-            const float* qa = sq + min(16 * mt + s16, kT - 1) * LQ + 4 * g;
-            const float* kb = sk + min(16 * nt + s16, kT - 1) * LQ + 4 * g;
+            const float* qa = sq + min(16 * mt + s16, S - 1) * LQ + 4 * g;
+            const float* kb = sk + min(16 * nt + s16, S - 1) * LQ + 4 * g;
             f4 acc = (f4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int q = 0; q < HD / 16; ++q) {
@@ -103,17 +110,18 @@ __global__ __launch_bounds__(256) void k_sag_attention(const float* __restrict__
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int a = 16 * mt + 4 * g + r;
-                if (a < kT && c < kT) sp[a * LP + c] = acc[r];
+                if (a < S && c < S) sp[a * LP + c] = acc[r];
             }
         }
         __syncthreads();
         // ---- softmax over the keys of each query row: one wave per row, lane = key
-        for (int a = w; a < kT; a += 4) {
-            const float v = lane < kT ? sp[a * LP + lane] : -INFINITY;
+        for (int a = w; a < S; a += 4) {
+            float v = lane < S ? sp[a * LP + lane] : -INFINITY;
+            if constexpr (MASK) { if (!keep) v = -INFINITY; }
             const float m = wave_max(v);
-            const float e = lane < kT ? expf(v - m) : 0.f;
+            const float e = lane < S ? expf(v - m) : 0.f;
             const float inv = 1.0f / wave_sum(e);
-            if (lane < KP) sp[a * LP + lane] = e * inv;                   // columns 34, 35: zero (K padding of the P.V product)
+            if (lane < KP) sp[a * LP + lane] = e * inv;                   // columns S..35: zero (K padding of the P.V product)
         }
         __syncthreads();
         // ---- out = P V: wave w owns feature tiles w, w + 4 of HD / 16; lane holds O[a = 16 mt + 4 g + r][d = 16 nt + s16]
@@ -123,10 +131,10 @@ __global__ __launch_bounds__(256) void k_sag_attention(const float* __restrict__
             for (int mt = 0; mt < 3; ++mt) acc[mt] = (f4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KP / 4; ++ks) {
-                const float bv = sv[min(4 * ks + g, kT - 1) * LQ + 16 * nt + s16];    // rows 34, 35 meet P's zero columns
+                const float bv = sv[min(4 * ks + g, S - 1) * LQ + 16 * nt + s16];    // rows S..35 (clamped) meet P's zero columns
 #pragma unroll
                 for (int mt = 0; mt < 3; ++mt) {
-                    const float av = sp[min(16 * mt + s16, kT - 1) * LP + 4 * ks + g];
+                    const float av = sp[min(16 * mt + s16, S - 1) * LP + 4 * ks + g];
                     acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[mt], 0, 0, 0);
                 }
             }
@@ -135,7 +143,7 @@ __global__ __launch_bounds__(256) void k_sag_attention(const float* __restrict__
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int a = 16 * mt + 4 * g + r;
-                    if (a < kT) out[(size_t)(b * kT + a) * D + h * HD + 16 * nt + s16] = acc[mt][r];
+                    if (a < S) out[(size_t)(b * S + a) * D + h * HD + 16 * nt + s16] = acc[mt][r];
                 }
         }
     }
@@ -269,7 +277,12 @@ hipError_t launch_sag_queries(const float* x, const float* wmap, const float* bm
 }
 hipError_t launch_sag_attention(const float* qkv, float* out, int B, int heads, int D, int n_pre_c, hipStream_t st) {
     if (D / heads != 128) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_sag_attention<128>), dim3(B), dim3(256), 0, st, qkv, out, D, heads, n_pre_c);
+    hipLaunchKernelGGL((k_sag_attention<128, kT, false>), dim3(B), dim3(256), 0, st, qkv, out, D, heads, n_pre_c, nullptr);
+    return hipGetLastError();
+}
+hipError_t launch_sag_enc_attention(const float* qkv, const unsigned char* kmask, float* out, int B, int heads, int D, hipStream_t st) {
+    if (D / heads != 128 || !kmask) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_sag_attention<128, kSagEncS, true>), dim3(B), dim3(256), 0, st, qkv, out, D, heads, 0, kmask);
     return hipGetLastError();
 }
 hipError_t launch_layernorm512(const float* x, const float* bc, int bc_stride, const float* w, const float* beta, float* y, int rows,

@@ -2,9 +2,9 @@
 // scripts/test_LivelySpeaker_ted.py:88 = Decoder_TRANSFORMER.forward (scripts/model/motionclip_module.py:138-183).
 #include "ls_hip.h"
 #include "ls_internal.h"
+#include "ls_sag_host.h"
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -15,19 +15,6 @@ using namespace ls;
 
 namespace {
 std::string g_sag_create_error;
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= bytes) return hipSuccess;
-        if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; bytes = 0; }
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    float* f() const { return static_cast<float*>(p); }
-};
 }  // namespace
 
 struct ls_sag {
@@ -36,10 +23,10 @@ struct ls_sag {
     hipStream_t stream = nullptr;
     std::string err;
     std::map<std::string, std::vector<float>> w;
-    std::map<std::string, Buf> dw;      // device copies under the same keys
+    std::map<std::string, DeviceBuf> dw;      // device copies under the same keys
     bool committed = false;
-    Buf pe, xin, zin, mask, q, qc, qkv, attn, t1, ca, x2, hid, t3, out;
-    Buf wcross, bcross;      // cross-attention of ALL layers as one [L*D][D] matrix (see ls_sag_commit_weights)
+    DeviceBuf pe, xin, zin, mask, q, qc, qkv, attn, t1, ca, x2, hid, t3, out;
+    DeviceBuf wcross, bcross;      // cross-attention of ALL layers as one [L*D][D] matrix (see ls_sag_commit_weights)
     hipEvent_t ev[2] = {nullptr, nullptr};
     float last_ms = 0.f;
     bool pending_ms = false;   // ls_sag_decode_async enqueued: last_ms is read from the events when asked for
@@ -47,20 +34,13 @@ struct ls_sag {
 
 namespace {
 int sfail(ls_sag* h, int code, const char* fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    const int rc = sag_fail(h, g_sag_create_error, code, fmt, ap);
     va_end(ap);
-    if (h) h->err = buf; else g_sag_create_error = buf;
-    return code;
+    return rc;
 }
-#define SCHK(h, expr)                                                                                          \
-    do {                                                                                                       \
-        hipError_t e__ = (expr);                                                                               \
-        if (e__ != hipSuccess)                                                                                 \
-            return sfail((h), LS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-    } while (0)
+#define SCHK(h, expr) LS_SAG_CHK(sfail, h, expr)
 }  // namespace
 
 extern "C" {
@@ -109,9 +89,9 @@ void ls_sag_destroy(ls_sag* h) {
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto& kv : h->dw) kv.second.release();
-    Buf* all[] = {&h->pe, &h->xin, &h->zin, &h->mask, &h->q, &h->qc, &h->qkv, &h->attn, &h->t1, &h->ca, &h->x2, &h->hid, &h->t3, &h->out,
+    DeviceBuf* all[] = {&h->pe, &h->xin, &h->zin, &h->mask, &h->q, &h->qc, &h->qkv, &h->attn, &h->t1, &h->ca, &h->x2, &h->hid, &h->t3, &h->out,
                   &h->wcross, &h->bcross};
-    for (Buf* b : all) b->release();
+    for (DeviceBuf* b : all) b->release();
     for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -134,7 +114,7 @@ int ls_sag_commit_weights(ls_sag* h) {
         auto it = h->w.find(key);
         if (it == h->w.end()) return sfail(h, LS_ESTATE, "missing weight '%s'", key.c_str());
         if (it->second.size() != want) return sfail(h, LS_EINVAL, "weight '%s' has %zu elements, expected %zu", key.c_str(), it->second.size(), want);
-        Buf& b = h->dw[key];
+        DeviceBuf& b = h->dw[key];
         SCHK(h, b.ensure(want * sizeof(float)));
         SCHK(h, hipMemcpy(b.p, it->second.data(), want * sizeof(float), hipMemcpyHostToDevice));
         return LS_OK;

@@ -16,6 +16,8 @@ struct GemmOperand {
     int vec;                 // float4 loads along the contiguous index are legal (set by gemm_operand())
 };
 
+constexpr int kGemmTileK = 32;      // K tile of k_gemm_tr / k_gemm_dma: the full-tile (LDS-DMA) path needs K to be a multiple of it
+
 struct GemmArgs {
     GemmOperand A, B;        // C[m][n] = sum_k A(m,k) * B(n,k)
     float* C;                // element (m, n) at C[(m / cri) * cro + (m % cri) * crs + n * cns]; Cpre and R share the addressing

@@ -184,6 +184,48 @@ def make_sag_state_dict(cfg: PathConfig = None, seed: int = SEED_WEIGHTS + 100, 
     return sd
 
 
+def make_sag_encoder_state_dict(cfg: PathConfig = None, seed: int = SEED_WEIGHTS + 300, latent: int = 512, ff: int = 1024,
+                                layers: int = 3) -> dict:
+    """SAG encoder weights under Encoder_TRANSFORMER's state-dict keys (scripts/model/motionclip_module.py:33-68; in the SAG.pth
+    checkpoint they carry an 'encoder.' prefix).  The layers are drawn like make_sag_state_dict's; the two query tokens ~ N(0, 1) as
+    the reference initialises them."""
+    cfg = cfg or TED
+    g = _rng(seed)
+    D = latent
+    sd = {}
+
+    def uni(shape, fan_in):
+        b = 1.0 / np.sqrt(fan_in)
+        return _f32(g.uniform(-b, b, size=shape))
+
+    sd["muQuery"] = _f32(g.standard_normal((1, D)))
+    sd["sigmaQuery"] = _f32(g.standard_normal((1, D)))
+    sd["skelEmbedding.weight"] = uni((D, cfg.jf), cfg.jf)
+    sd["skelEmbedding.bias"] = uni((D,), cfg.jf)
+    for i in range(layers):
+        p = f"seqTransEncoder.layers.{i}."
+        sd[p + "self_attn.in_proj_weight"] = _f32(g.standard_normal((3 * D, D)) / np.sqrt(D))
+        sd[p + "self_attn.in_proj_bias"] = _f32(0.05 * g.standard_normal((3 * D,)))
+        sd[p + "self_attn.out_proj.weight"] = uni((D, D), D)
+        sd[p + "self_attn.out_proj.bias"] = _f32(0.05 * g.standard_normal((D,)))
+        sd[p + "linear1.weight"] = uni((ff, D), D)
+        sd[p + "linear1.bias"] = uni((ff,), D)
+        sd[p + "linear2.weight"] = uni((D, ff), ff)
+        sd[p + "linear2.bias"] = uni((D,), ff)
+        for n in ("norm1", "norm2"):
+            sd[p + n + ".weight"] = _f32(1.0 + 0.1 * g.standard_normal((D,)))
+            sd[p + n + ".bias"] = _f32(0.05 * g.standard_normal((D,)))
+    return sd
+
+
+def make_sag_checkpoint(cfg: PathConfig = None) -> dict:
+    """Both halves in the layout of SAG.pth: the encoder's entries under 'encoder.', the decoder's under 'decoder.'
+    (MOTIONCLIP's submodule names, scripts/model/motionclip.py:13-20)."""
+    sd = {"encoder." + k: v for k, v in make_sag_encoder_state_dict(cfg).items()}
+    sd.update({"decoder." + k: v for k, v in make_sag_state_dict(cfg).items()})
+    return sd
+
+
 def make_text_features(batch: int, seed: int = SEED_COND + 2000, latent: int = 512) -> np.ndarray:
     """Stand-in for clip_model.encode_text(...) (CLIP is an absent third-party package): z ~ 0.3 N(0,1) [B,512]."""
     return _f32(0.3 * _rng(seed).standard_normal((batch, latent)))
