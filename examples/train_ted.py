@@ -2,7 +2,9 @@
 """A few optimisation steps of the RAG denoiser with the TrainLoop drop-in (scripts/train_RAG.py:37-43 of the reference) on
 SYNTHETIC batches, then sampling with the trained weights.  Single GPU:
 
-    python examples/train_ted.py [steps] [batch]
+    python examples/train_ted.py [steps] [batch] [--bpd]
+--bpd: after training, the mean total_bpd (variational bound in bits per dimension, calc_bpd_loop over the ddim100 schedule) of a
+held-out synthetic batch under the trained weights.
 Data parallel over the GPUs of one node (one process per GPU, RCCL gradient all-reduce):
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_ted.py 20 512
 """
@@ -23,8 +25,10 @@ from livelyspeaker_amd.train_loop import TrainLoop                              
 
 
 def main():
-    steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-    B = int(sys.argv[2]) if len(sys.argv) > 2 else 512
+    want_bpd = "--bpd" in sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a != "--bpd"]
+    steps = int(argv[0]) if len(argv) > 0 else 10
+    B = int(argv[1]) if len(argv) > 1 else 512
     rank, world, local = 0, 1, 0
     if "RANK" in os.environ:
         rank, world, local = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"]), int(os.environ["LOCAL_RANK"])
@@ -69,6 +73,13 @@ def main():
         out = diff_s.ddim_sample_loop(ClassifierFreeSampleModel(model), (8, 9, 3, 34), clip_denoised=False, model_kwargs=cond,
                                       skip_timesteps=0, init_image=None, progress=False, dump_steps=None, noise=None, const_noise=False)
         print("sampled with the trained weights:", tuple(out.shape), "finite:", bool(torch.isfinite(out).all()))
+        if want_bpd:
+            # a batch no training step has seen (draw 7 of the synthetic stream; the steps above used draws 0..3)
+            x_held, y_held, _, _, _ = synth.make_train_batch(cfg, 8, 7)
+            held = {"y": {k: torch.from_numpy(v).to(dev) for k, v in y_held.items()}}
+            r = diff_s.calc_bpd_loop(ClassifierFreeSampleModel(model), torch.from_numpy(x_held).to(dev), clip_denoised=True, model_kwargs=held)
+            print(f"held-out batch of 8: mean total_bpd {float(r['total_bpd'].mean()):.2f} bits/dim over {diff_s.num_timesteps} schedule "
+                  f"indices (prior {float(r['prior_bpd'].mean()):.2e}, t = 0 term {float(r['vb'][:, -1].mean()):.2f})")
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

@@ -308,6 +308,66 @@ int ls_plms_step(ls_handle* h, const ls_plms_step_args* a);
 int ls_q_sample(ls_handle* h, int index, int on_device, size_t n, const float* x_start,
                 const float* noise, float* out);
 
+/* ---- the variational bound in bits per dimension (calc_bpd_loop, gaussian_diffusion.py:1591-1646) -------------------------------
+ * Under START_X + FIXED_SMALL the model's variance is the true posterior's, so a column of the bound needs x_0, x_t, the model's
+ * pred_xstart and the q_sample noise only.  k_vb_terms (csrc/ls_bpd.hip) evaluates, per sample and in fp32 in the reference's
+ * operation order (losses.py:33-39, :62-75),
+ *   vb         = mean(normal_kl(q_posterior(x_0, x_t), p(x_t))) / ln 2 when t > 0, the discretized decoder NLL / ln 2 when t == 0
+ *                (chosen per sample, as th.where(t == 0, ...) does, :1245),
+ *   xstart_mse = mean((pred_xstart - x_0)^2)                                                                   (:1630),
+ *   mse        = mean((_predict_eps_from_xstart(x_t, t, pred_xstart) - noise)^2)                               (:1631-1632),
+ * with one deterministic fixed-tree reduction per sample (no atomics: a graph replay equals plain launches bit for bit).
+ *
+ * ls_vb_terms: that kernel alone on caller-given planes [B,J,F,T] (B = the prepared batch): the second half of _vb_terms_bpd.
+ * Schedule index: `indices` [B] int64 (per sample; host values are validated, device values clamped into the table) or, when it is
+ * NULL, the uniform `index`.  noise NULL: mse is not computed (mse_out is then ignored).  clip_denoised: pred_xstart is clamped to
+ * [-1, 1] first (process_xstart); pred_out (nullable) receives the plane the terms were computed from.  Outputs [B]. */
+typedef struct ls_vb_terms_args {
+    int32_t index;
+    int32_t on_device;
+    int32_t indices_on_device;
+    int32_t clip_denoised;
+    const int64_t* indices;
+    const float* x_start;
+    const float* x_t;
+    const float* pred_xstart;
+    const float* noise;
+    float* vb_out;
+    float* xstart_mse_out;
+    float* mse_out;
+    float* pred_out;
+} ls_vb_terms_args;
+int ls_vb_terms(ls_handle* h, const ls_vb_terms_args* a);
+
+/* ls_bpd: columns [col_begin, col_begin + col_count) of calc_bpd_loop on the schedule of ls_set_schedule; column k belongs to schedule
+ * index n_steps - 1 - k.  Per column: q_sample(x_start, t, noise_k), one denoiser launch (sampler = none: whatever kernel family and
+ * plan the prepared batch gets, as a PLMS evaluation) and k_vb_terms.  Columns do not depend on each other: a call over a sub-range
+ * gives bitwise the columns of the whole call.
+ * Noise: TAPE -- noise_tape [col_count,B,J,F,T] and eps_tape [col_count,2,B,latent_dim] hold THIS call's columns, in the reference's
+ * draw order per column (randn_like(x_start), then the style eps of the cond and the uncond pass); PHILOX -- column k uses step_id = k
+ * of the step-noise stream (3) and the style-eps streams (1, 2), keyed by sample_offset + b (shard-invariant); TORCH_DEVICE returns
+ * LS_EUNSUPPORTED.  vb / xstart_mse / mse: [B, n_steps] row-major (host or device per on_device); only this call's columns are
+ * written.  use_graph: the column loop is captured and replayed like ls_sample's.  ls_timing: n_step_launches = col_count. */
+typedef struct ls_bpd_args {
+    int32_t noise_mode;         /* LS_NOISE_TAPE | LS_NOISE_PHILOX                   */
+    int32_t on_device;
+    int32_t use_graph;
+    int32_t clip_denoised;
+    int32_t two_pass_always;    /* as in ls_sample_args                              */
+    int32_t col_begin;
+    int32_t col_count;
+    int32_t reserved;
+    const float* x_start;       /* [B,J,F,T]                                         */
+    const float* noise_tape;
+    const float* eps_tape;
+    uint64_t seed;              /* PHILOX key                                        */
+    uint64_t sample_offset;     /* PHILOX: global index of sample 0                  */
+    float* vb;
+    float* xstart_mse;
+    float* mse;
+} ls_bpd_args;
+int ls_bpd(ls_handle* h, const ls_bpd_args* a);
+
 /* The x_T draw of PHILOX mode on its own (what ls_sample uses when x_init == NULL): out [batch,J,F,T] ~ N(0,1),
  * stream keyed by (seed, sample_offset + b). Lets tests check the device RNG's moments and shard-invariance. */
 int ls_philox_x_init(ls_handle* h, int batch, uint64_t seed, uint64_t sample_offset, int on_device, float* out);

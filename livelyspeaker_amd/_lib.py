@@ -69,6 +69,18 @@ class LsPlmsStepArgs(C.Structure):
         ("hist", C.c_void_p * 3), ("sample", C.c_void_p), ("pred_xstart", C.c_void_p), ("eps_out", C.c_void_p)]
 
 
+class LsVbTermsArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("index", "on_device", "indices_on_device", "clip_denoised")] + [
+        (n, C.c_void_p) for n in ("indices", "x_start", "x_t", "pred_xstart", "noise", "vb_out", "xstart_mse_out", "mse_out", "pred_out")]
+
+
+class LsBpdArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("noise_mode", "on_device", "use_graph", "clip_denoised", "two_pass_always", "col_begin", "col_count",
+                                         "reserved")] + [("x_start", C.c_void_p), ("noise_tape", C.c_void_p), ("eps_tape", C.c_void_p),
+                                                         ("seed", C.c_uint64), ("sample_offset", C.c_uint64), ("vb", C.c_void_p),
+                                                         ("xstart_mse", C.c_void_p), ("mse", C.c_void_p)]
+
+
 class LsSagConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("njoints", "nfeats", "nframes", "latent_dim", "ff_size", "num_layers",
                                          "num_heads", "n_pre_poses", "device", "reserved")]
@@ -108,7 +120,7 @@ class LsEvalConfig(C.Structure):
 
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
-           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_read",
+           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
@@ -184,6 +196,8 @@ def load_library(build_if_missing: bool = True):
     lib.ls_step.argtypes = [C.c_void_p, C.POINTER(LsStepArgs)]
     lib.ls_plms_step.argtypes = [C.c_void_p, C.POINTER(LsPlmsStepArgs)]
     lib.ls_q_sample.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ls_vb_terms.argtypes = [C.c_void_p, C.POINTER(LsVbTermsArgs)]
+    lib.ls_bpd.argtypes = [C.c_void_p, C.POINTER(LsBpdArgs)]
     lib.ls_read.argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
     lib.ls_read.restype = C.c_longlong
     lib.ls_get_timing.argtypes = [C.c_void_p, C.POINTER(LsTiming)]
@@ -666,6 +680,69 @@ class Engine:
         n = int(np.prod(x_start.shape))
         m.ready()
         self._check(self.lib.ls_q_sample(self.h, index, int(m.on_device), n, m.f32(x_start), m.f32(noise), pout), "ls_q_sample")
+        return out
+
+    def vb_terms(self, x_start, x_t, pred_xstart, noise=None, index=0, indices=None, clip_denoised=False):
+        """k_vb_terms alone on caller-given planes [B, J, F, T] (ls_vb_terms): the second half of _vb_terms_bpd plus the two MSEs of
+        calc_bpd_loop.  ``indices`` ([B] int64, numpy / CPU tensor = validated on the host, CUDA tensor = clamped on the device) or the
+        uniform ``index``.  Returns (vb [B], xstart_mse [B], mse [B] or None without ``noise``, the pred_xstart plane used)."""
+        m = _Marshal(self.device, x_start, x_t, pred_xstart, noise, stream=self._stream)
+        B = self.batch
+        vb, pvb = m.out((B,))
+        xs, pxs = m.out((B,))
+        ms, pms = m.out((B,)) if noise is not None else (None, None)
+        px, ppx = m.out(self._xshape())
+        a = LsVbTermsArgs()
+        a.index, a.on_device, a.clip_denoised = int(index), int(m.on_device), int(bool(clip_denoised))
+        if indices is not None:
+            if _is_cuda(indices):
+                if not m.on_device:
+                    raise EngineError("device `indices` need device tensors for the other arguments")
+                t = indices.to(dtype=m.torch.int64).contiguous()
+                shape, a.indices, a.indices_on_device = tuple(t.shape), C.c_void_p(t.data_ptr()), 1
+            else:
+                t = np.ascontiguousarray(indices.detach().cpu().numpy() if hasattr(indices, "detach") else indices, dtype=np.int64)
+                shape, a.indices = t.shape, t.ctypes.data_as(C.c_void_p)
+            if tuple(shape) != (B,):
+                raise EngineError(f"indices must be [{B}], got {tuple(shape)}")
+            m.keep.append(t)
+        a.x_start, a.x_t = m.f32(x_start, self._xshape()), m.f32(x_t, self._xshape())
+        a.pred_xstart, a.noise = m.f32(pred_xstart, self._xshape()), m.f32(noise, self._xshape())
+        a.vb_out, a.xstart_mse_out, a.mse_out, a.pred_out = pvb, pxs, pms, ppx
+        m.ready()
+        self._check(self.lib.ls_vb_terms(self.h, C.byref(a)), "ls_vb_terms")
+        return vb, xs, ms, px
+
+    def bpd(self, x_start, out, columns=None, noise_tape=None, eps_tape=None, philox_seed=None, sample_offset=0, use_graph=True,
+            clip_denoised=True, two_pass_always=False):
+        """Columns ``columns`` = (first, count) (default: all) of calc_bpd_loop (ls_bpd) into ``out`` = (vb, xstart_mse, mse), three
+        float32 C-contiguous [B, n_steps] arrays (all numpy, or all torch CUDA tensors on this GPU) of which only those columns are
+        written.  TAPE mode with ``noise_tape`` [count, B, J, F, T] and ``eps_tape`` [count, 2, B, D]; PHILOX mode with ``philox_seed``."""
+        k0, n = (0, self.n_steps) if columns is None else (int(columns[0]), int(columns[1]))
+        m = _Marshal(self.device, x_start, noise_tape, eps_tape, *out, stream=self._stream)
+        a = LsBpdArgs()
+        a.on_device, a.use_graph, a.clip_denoised = int(m.on_device), int(bool(use_graph)), int(bool(clip_denoised))
+        a.two_pass_always, a.col_begin, a.col_count = int(bool(two_pass_always)), k0, n
+        a.x_start = m.f32(x_start, self._xshape())
+        if philox_seed is None:
+            a.noise_mode = LS_NOISE_TAPE
+            a.noise_tape = m.f32(noise_tape, (n,) + self._xshape())
+            a.eps_tape = m.f32(eps_tape, (n, 2, self.batch, self.D))
+        else:
+            a.noise_mode = LS_NOISE_PHILOX
+            a.seed, a.sample_offset = int(philox_seed), int(sample_offset)
+        ptrs = []
+        for o in out:
+            ok = (tuple(o.shape) == (self.batch, self.n_steps) and
+                  (_is_cuda(o) and o.is_contiguous() and str(o.dtype) == "torch.float32" if m.on_device else
+                   isinstance(o, np.ndarray) and o.dtype == np.float32 and o.flags.c_contiguous))
+            if not ok:
+                raise EngineError(f"bpd: outputs must be float32 C-contiguous [{self.batch}, {self.n_steps}] "
+                                  f"{'CUDA tensors' if m.on_device else 'numpy arrays'}")
+            ptrs.append(C.c_void_p(o.data_ptr()) if m.on_device else o.ctypes.data_as(C.c_void_p))
+        a.vb, a.xstart_mse, a.mse = ptrs
+        m.ready()
+        self._check(self.lib.ls_bpd(self.h, C.byref(a)), "ls_bpd")
         return out
 
     def torch_randn(self, seed, offset, out):

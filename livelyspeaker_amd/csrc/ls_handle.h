@@ -128,6 +128,11 @@ struct ls_handle {
     // refilled by one generator launch per K steps inside the loop; K = what fits in trng_ring_bytes (ls_set_torch_ring_bytes)
     DevBuf trng_eps, trng_noise, trng_inz;
     size_t trng_ring_bytes = (size_t)256 << 20;
+    // ls_bpd / ls_vb_terms: x_start, the column's q_sample noise and x_t (internal layout), the noise tape in the internal layout, the
+    // per-index coefficient table of k_vb_terms (built for schedule bpd_coef_version) and the [3][B][n_steps] results
+    DevBuf bpd_x0, bpd_nz, bpd_xt, bpd_tape, bpd_coef, bpd_out;
+    unsigned bpd_coef_version = 0;
+    bool bpd_coef_valid = false;
     std::string coef_key;   // (sampler, eta, schedule) the per-index coefficient table `coef` was built for
 
     // cached graph of the step loop

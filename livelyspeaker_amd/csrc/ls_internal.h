@@ -279,6 +279,25 @@ struct PlmsArgs {
     float c0, c1, c2, c3, d0, d1;
 };
 hipError_t launch_plms_update(const PlmsArgs& a, hipStream_t st);
+// ---- variational-bound terms (ls_bpd.hip): one column of calc_bpd_loop (gaussian_diffusion.py:1591-1646) after a denoiser launch with
+// sampler = kNone.  One workgroup per sample over n = T * JF elements; every plane in the same layout (the reduction is layout-blind).
+// table [n_steps][8] = {posterior_mean_coef1, posterior_mean_coef2, posterior_log_variance_clipped, sqrt_recip_alphas_cumprod,
+// sqrt_recipm1_alphas_cumprod, -, -, -}, cast fp64 -> fp32 like _extract_into_tensor; sample b takes row indices[b] (clamped into the
+// table) or, when indices is null, row `index`.  vb / xstart_mse / mse: sample b's result goes to [b * out_stride + out_col].
+struct VbArgs {
+    const float* x_start; const float* x_t; const float* noise;      // noise null: mse is not computed
+    float* pred;                                                     // in: the model's x_0 prediction; out (clip): clamped to [-1, 1]
+    float* pred_copy;                                                // nullable: the plane the terms were computed from
+    const float* table; const int64_t* indices;
+    float* vb; float* xstart_mse; float* mse;
+    int n, n_steps, index, clip;
+    int out_stride, out_col;
+};
+hipError_t launch_vb_terms(const VbArgs& a, int B, hipStream_t st);
+// PHILOX mode of ls_bpd: the step-noise stream (3) of step_id as a plane in the internal layout [B][T][JF], and x_t = a * x0 + b * noise
+// (q_sample) from it in the same launch
+hipError_t launch_q_sample_philox(const float* x0_btc, float* noise_out, float* xt_out, int B, int JF, int T, const CallParams* call,
+                                  unsigned step_id, float a, float b, hipStream_t st);
 // bytes [n] -> 0.f / 1.f
 hipError_t launch_bytes_to_float(const unsigned char* src, float* dst, size_t n, hipStream_t st);
 hipError_t launch_randn_fill(float* out_btc, int B, int JF, const CallParams* call, unsigned stream_id,

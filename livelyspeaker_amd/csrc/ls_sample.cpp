@@ -1,6 +1,7 @@
 // Host side of the C-ABI declared in include/ls_hip.h: everything that runs diffusion steps.  The sampling loop exists once (begin_loop ->
 // enqueue_loop | enqueue_plms -> finish_loop; stream launches or a captured hipGraph; draws from whole-call tapes, segmented tapes, Philox or
-// torch's GPU stream), next to the single-step entries that enqueue the same launches on caller-held tensors (ls_forward, ls_step, ls_plms_step).
+// torch's GPU stream), next to the single-step entries that enqueue the same launches on caller-held tensors (ls_forward, ls_step, ls_plms_step),
+// and the likelihood loop (ls_bpd: per schedule index q_sample, the denoiser alone and k_vb_terms, through the same capture-or-enqueue) with ls_vb_terms.
 #include "ls_handle.h"
 
 #include <cmath>
@@ -392,13 +393,12 @@ std::string loop_key(const ls_handle* h, const LoopCall& c) {
     return key;
 }
 
-// the loop as stream launches, or as a captured graph (captured when the key changed, replayed otherwise)
-int run_loop(ls_handle* h, const LoopCall& c, int* graph_replayed) {
+// a chain of launches as stream launches, or as a captured graph (captured when the key changed, replayed otherwise)
+template <class Enqueue>
+int run_captured(ls_handle* h, bool use_graph, const std::string& key, Enqueue enqueue, int* graph_replayed) {
     hipStream_t st = h->stream;
-    auto enqueue = [&]() { return c.plms ? enqueue_plms(h, c) : enqueue_loop(h, c); };
     *graph_replayed = 0;
-    if (!c.a->use_graph) return enqueue();
-    const std::string key = loop_key(h, c);
+    if (!use_graph) return enqueue();
     if (!h->graph_exec || h->graph_key != key) {
         free_graph(h);
         HIPCHK(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -415,6 +415,60 @@ int run_loop(ls_handle* h, const LoopCall& c, int* graph_replayed) {
         *graph_replayed = 1;
     }
     HIPCHK(h, hipGraphLaunch(h->graph_exec, st));
+    return LS_OK;
+}
+
+// the sampling loop through run_captured
+int run_loop(ls_handle* h, const LoopCall& c, int* graph_replayed) {
+    return run_captured(h, c.a->use_graph != 0, c.a->use_graph ? loop_key(h, c) : std::string(),
+                        [&]() { return c.plms ? enqueue_plms(h, c) : enqueue_loop(h, c); }, graph_replayed);
+}
+
+// ---- the variational bound (ls_bpd / ls_vb_terms) ----------------------------------------------------------------------------
+// k_vb_terms' coefficient rows, cast fp64 -> fp32 like _extract_into_tensor; held by address in a captured column loop
+int ensure_bpd_coef(ls_handle* h) {
+    if (h->bpd_coef_valid && h->bpd_coef_version == h->sched_version) return LS_OK;
+    std::vector<float> coef((size_t)h->n_steps * 8, 0.f);
+    for (int i = 0; i < h->n_steps; ++i) {
+        float* c = &coef[(size_t)i * 8];
+        c[0] = (float)h->t_c1[i]; c[1] = (float)h->t_c2[i]; c[2] = (float)h->t_plv[i]; c[3] = (float)h->t_srac[i]; c[4] = (float)h->t_srm1ac[i];
+    }
+    int rc;
+    if ((rc = ensure_pinned(h, h->bpd_coef, coef.size() * sizeof(float))) != LS_OK) return rc;
+    if ((rc = upload(h, h->bpd_coef, coef.data(), coef.size() * sizeof(float))) != LS_OK) return rc;
+    h->bpd_coef_version = h->sched_version;
+    h->bpd_coef_valid = true;
+    return LS_OK;
+}
+
+// columns [k0, k0 + n) of calc_bpd_loop (:1615-1632): per column q_sample (PHILOX: with the draw of its noise), the denoiser alone, k_vb_terms.  One linear chain.
+int enqueue_bpd(ls_handle* h, const ls_bpd_args* a, bool pair, size_t nelem) {
+    hipStream_t st = h->stream;
+    const int B = h->B, T = h->n_steps;
+    const bool tape = a->noise_mode == LS_NOISE_TAPE;
+    const size_t ne = (size_t)B * kD;
+    float* const out = h->bpd_out.f();
+    HIPCHK(h, coop_reset(h, st));
+    for (int r = 0; r < a->col_count; ++r) {
+        const int k = a->col_begin + r, i = T - 1 - k;
+        const float* nz = tape ? h->bpd_tape.f() + (size_t)r * nelem : h->bpd_nz.f();
+        if (tape)
+            HIPCHK(h, launch_q_sample(h->bpd_x0.f(), nz, h->bpd_xt.f(), nelem, (float)h->t_sac[i], (float)h->t_s1mac[i], st));
+        else        // the draw and q_sample in one launch
+            HIPCHK(h, launch_q_sample_philox(h->bpd_x0.f(), h->bpd_nz.f(), h->bpd_xt.f(), B, h->JF, h->T, static_cast<const CallParams*>(h->callp.p),
+                                             (unsigned)k, (float)h->t_sac[i], (float)h->t_s1mac[i], st));
+        const Draws d = tape ? Draws{h->eps_tape.f() + 2 * r * ne, h->eps_tape.f() + (2 * r + 1) * ne, nullptr, nullptr, (unsigned)k}
+                             : Draws{nullptr, nullptr, nullptr, nullptr, (unsigned)k};
+        StepArgs m = eval_args(h, i, h->bpd_xt.f(), d);
+        m.x0_out = h->fwd_cfg.f();
+        HIPCHK(h, run_step(h, m, B, pair, st));
+        VbArgs v{};
+        v.x_start = h->bpd_x0.f(); v.x_t = h->bpd_xt.f(); v.noise = nz; v.pred = h->fwd_cfg.f();
+        v.table = h->bpd_coef.f(); v.index = i; v.n_steps = T; v.n = (int)(nelem / B); v.clip = a->clip_denoised;
+        v.vb = out; v.xstart_mse = out + (size_t)B * T; v.mse = out + (size_t)2 * B * T;
+        v.out_stride = T; v.out_col = k;
+        HIPCHK(h, launch_vb_terms(v, B, st));
+    }
     return LS_OK;
 }
 
@@ -739,6 +793,112 @@ int ls_plms_step(ls_handle* h, const ls_plms_step_args* a) {
     if (a->pred_xstart && (rc = egress_internal(h, p.pred_out, a->pred_xstart, B, od)) != LS_OK) return rc;
     if (a->eps_out && (rc = egress_internal(h, p.eps_out, a->eps_out, B, od)) != LS_OK) return rc;
     return sync_and_check(h, a->no_sync, od);
+}
+
+// _vb_terms_bpd's arithmetic (gaussian_diffusion.py:1226-1246) and the two MSEs of calc_bpd_loop (:1630-1632) on caller-held planes
+int ls_vb_terms(ls_handle* h, const ls_vb_terms_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_vb_terms: null argument");
+    if (!h->prepared) return fail(h, LS_ESTATE, "ls_vb_terms before ls_prepare");
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_vb_terms before ls_set_schedule");
+    if (!a->x_start || !a->x_t || !a->pred_xstart || !a->vb_out || !a->xstart_mse_out || (a->noise && !a->mse_out))
+        return fail(h, LS_EINVAL, "ls_vb_terms: null pointer");
+    if (!a->indices && (a->index < 0 || a->index >= h->n_steps)) return fail(h, LS_EINVAL, "schedule index %d outside [0,%d)", a->index, h->n_steps);
+    const int B = h->B, od = a->on_device;
+    if (a->indices && !a->indices_on_device)
+        for (int b = 0; b < B; ++b)
+            if (a->indices[b] < 0 || a->indices[b] >= h->n_steps)
+                return fail(h, LS_EINVAL, "indices[%d] = %lld outside [0,%d)", b, (long long)a->indices[b], h->n_steps);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t nelem = (size_t)B * h->JF * h->T, nx = nelem * sizeof(float);
+    hipStream_t st = h->stream;
+    int rc;
+    if ((rc = ensure_bpd_coef(h)) != LS_OK) return rc;
+    if ((rc = ensure_pinned(h, h->bpd_x0, nx)) != LS_OK || (rc = ensure_pinned(h, h->bpd_xt, nx)) != LS_OK ||
+        (rc = ensure_pinned(h, h->bpd_nz, nx)) != LS_OK || (rc = ensure_pinned(h, h->fwd_cfg, nx)) != LS_OK) return rc;
+    HIPCHK(h, h->xtmp.ensure((size_t)3 * B * sizeof(float)));
+    if ((rc = ingest_internal(h, a->x_start, h->bpd_x0.f(), B, od)) != LS_OK) return rc;
+    if ((rc = ingest_internal(h, a->x_t, h->bpd_xt.f(), B, od)) != LS_OK) return rc;
+    if ((rc = ingest_internal(h, a->pred_xstart, h->fwd_cfg.f(), B, od)) != LS_OK) return rc;
+    if (a->noise && (rc = ingest_internal(h, a->noise, h->bpd_nz.f(), B, od)) != LS_OK) return rc;
+    if (a->indices) {
+        if ((rc = ingest(h, h->tidx, a->indices, (size_t)B * sizeof(int64_t), a->indices_on_device)) != LS_OK) return rc;
+        if (!a->indices_on_device) HIPCHK(h, hipStreamSynchronize(st));        // a host index vector may be a temporary of the caller
+    }
+    VbArgs v{};
+    v.x_start = h->bpd_x0.f(); v.x_t = h->bpd_xt.f(); v.noise = a->noise ? h->bpd_nz.f() : nullptr; v.pred = h->fwd_cfg.f();
+    v.table = h->bpd_coef.f(); v.indices = a->indices ? static_cast<const int64_t*>(h->tidx.p) : nullptr;
+    v.index = a->indices ? 0 : a->index; v.n_steps = h->n_steps; v.n = h->JF * h->T; v.clip = a->clip_denoised;
+    float* const out = h->xtmp.f();
+    v.vb = out; v.xstart_mse = out + B; v.mse = out + 2 * B; v.out_stride = 1; v.out_col = 0;
+    HIPCHK(h, launch_vb_terms(v, B, st));
+    if ((rc = egress(h, a->vb_out, out, (size_t)B * sizeof(float), od)) != LS_OK) return rc;
+    if ((rc = egress(h, a->xstart_mse_out, out + B, (size_t)B * sizeof(float), od)) != LS_OK) return rc;
+    if (a->noise && (rc = egress(h, a->mse_out, out + 2 * B, (size_t)B * sizeof(float), od)) != LS_OK) return rc;
+    if (a->pred_out && (rc = egress_internal(h, h->fwd_cfg.f(), a->pred_out, B, od)) != LS_OK) return rc;
+    HIPCHK(h, hipStreamSynchronize(st));
+    return LS_OK;
+}
+
+// validate -> stage x_start and the tapes -> capture-or-enqueue the column loop -> the call's columns back
+int ls_bpd(ls_handle* h, const ls_bpd_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_bpd: null argument");
+    if (!h->prepared) return fail(h, LS_ESTATE, "ls_bpd before ls_prepare");
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_bpd before ls_set_schedule");
+    if (a->noise_mode == LS_NOISE_TORCH_DEVICE) return fail(h, LS_EUNSUPPORTED, "ls_bpd: TORCH_DEVICE draws are not generated in the column loop");
+    if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EINVAL, "bad noise_mode");
+    if (a->col_begin < 0 || a->col_count < 1 || a->col_count > h->n_steps - a->col_begin)
+        return fail(h, LS_EINVAL, "columns [%d, %d + %d) outside the schedule's %d", a->col_begin, a->col_begin, a->col_count, h->n_steps);
+    if (!a->x_start || !a->vb || !a->xstart_mse || !a->mse) return fail(h, LS_EINVAL, "ls_bpd: null pointer");
+    const bool tape = a->noise_mode == LS_NOISE_TAPE;
+    if (tape && (!a->noise_tape || !a->eps_tape)) return fail(h, LS_EINVAL, "TAPE mode needs noise_tape and eps_tape");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->seg_next = -1;
+    const int B = h->B, T = h->n_steps, od = a->on_device, n = a->col_count;
+    const size_t nelem = (size_t)B * h->JF * h->T, nx = nelem * sizeof(float);
+    const bool pair = single_pass(h, a->two_pass_always);
+    hipStream_t st = h->stream;
+    int rc;
+    if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
+    if ((rc = ensure_bpd_coef(h)) != LS_OK) return rc;
+    h->call_host = CallParams{a->seed, a->sample_offset, h->tag_base, 0u};
+    HIPCHK(h, hipEventRecord(h->ev[0], st));
+    if ((rc = ensure_pinned(h, h->bpd_x0, nx)) != LS_OK || (rc = ensure_pinned(h, h->bpd_xt, nx)) != LS_OK ||
+        (rc = ensure_pinned(h, h->fwd_cfg, nx)) != LS_OK || (rc = ensure_pinned(h, h->bpd_out, (size_t)3 * B * T * sizeof(float))) != LS_OK) return rc;
+    HIPCHK(h, h->xio.ensure(nx));
+    if ((rc = advance_tags(h, st)) != LS_OK) return rc;
+    if ((rc = ingest_internal(h, a->x_start, h->bpd_x0.f(), B, od)) != LS_OK) return rc;
+    if (tape) {
+        if ((rc = ingest_pinned(h, h->eps_tape, a->eps_tape, (size_t)n * 2 * B * kD * sizeof(float), od)) != LS_OK) return rc;
+        if ((rc = ingest_pinned(h, h->noise_tape, a->noise_tape, (size_t)n * nx, od)) != LS_OK) return rc;
+        if ((rc = ensure_pinned(h, h->bpd_tape, (size_t)n * nx)) != LS_OK) return rc;
+        HIPCHK(h, launch_to_internal(h->noise_tape.f(), h->bpd_tape.f(), n * B, h->JF, st, h->T));      // every column's plane at once
+    } else if ((rc = ensure_pinned(h, h->bpd_nz, nx)) != LS_OK) {
+        return rc;
+    }
+    char key[192];
+    snprintf(key, sizeof key, "BPD P%d B%d n%d cl%d w%u v%u p%d L%lld b%d k%d", h->precision, B, a->noise_mode, a->clip_denoised,
+             h->weights_version, h->sched_version, (int)pair, plan_code(h), a->col_begin, n);
+    int replayed = 0;
+    HIPCHK(h, hipEventRecord(h->ev[1], st));
+    if ((rc = run_captured(h, a->use_graph != 0, key, [&]() { return enqueue_bpd(h, a, pair, nelem); }, &replayed)) != LS_OK) return rc;
+    HIPCHK(h, hipEventRecord(h->ev[2], st));
+    float* const outs[3] = {a->vb, a->xstart_mse, a->mse};
+    for (int j = 0; j < 3; ++j)
+        HIPCHK(h, hipMemcpy2DAsync(outs[j] + a->col_begin, (size_t)T * sizeof(float), h->bpd_out.f() + (size_t)j * B * T + a->col_begin,
+                                   (size_t)T * sizeof(float), (size_t)n * sizeof(float), (size_t)B, od ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipEventRecord(h->ev[3], st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    resolve_prepare_timing(h, true);
+    if ((rc = coop_check(h)) != LS_OK) return rc;
+    report_path(h, pair);
+    HIPCHK(h, hipEventElapsedTime(&h->timing.loop_ms, h->ev[1], h->ev[2]));
+    HIPCHK(h, hipEventElapsedTime(&h->timing.total_ms, h->ev[0], h->ev[3]));
+    h->timing.n_step_launches = n;
+    h->timing.single_pass = pair ? 1 : 0;
+    h->timing.graph_replayed = replayed;
+    h->timing.tape_upload_ms = 0.f;
+    h->timing.n_segments = 1;
+    return LS_OK;
 }
 
 }  // extern "C"

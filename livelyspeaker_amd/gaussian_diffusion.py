@@ -6,7 +6,8 @@ Mirrors (names, argument meaning, error behaviour) of
 ``q_posterior_mean_variance`` (:260-282), ``p_mean_variance`` (:284-399), ``p_sample`` (:507-558), ``p_sample_loop`` (:608-671),
 ``p_sample_loop_progressive`` (:673-743), ``ddim_sample`` (:745-798), ``ddim_sample_loop`` (:895-943),
 ``ddim_sample_loop_progressive`` (:945-1014), ``ddim_reverse_sample`` (:857-893), ``plms_sample`` (:1016-1098), ``plms_sample_loop`` (:1100-1140),
-``plms_sample_loop_progressive`` (:1142-1211) and ``_extract_into_tensor`` (:1651-1664).
+``plms_sample_loop_progressive`` (:1142-1211), ``q_mean_variance`` (:223-238), ``_vb_terms_bpd`` (:1213-1246), ``_prior_bpd`` (:1573-1589),
+``calc_bpd_loop`` (:1591-1646) and ``_extract_into_tensor`` (:1651-1664).
 
 Only the schedule tables live here (fp64 numpy, as in the reference).  All per-step arithmetic
 (CFG'd model evaluation + posterior / DDIM update) runs in the fused gfx950 step kernel behind the
@@ -503,6 +504,109 @@ class GaussianDiffusion:
             self.last_tape_segments = 1
         res = eng.sample(**kw)
         return _ref_strides(_as_tensor(res, device))
+
+    # ------------------------------------------------------------------ likelihood
+    def q_mean_variance(self, x_start, t):
+        """The distribution q(x_t | x_0) (gaussian_diffusion.py:223-238): elementwise on the caller's tensors."""
+        mean = _extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
+        variance = _extract_into_tensor(1.0 - self.alphas_cumprod, t, x_start.shape)
+        log_variance = _extract_into_tensor(self.log_one_minus_alphas_cumprod, t, x_start.shape)
+        return mean, variance, log_variance
+
+    def _prior_bpd(self, x_start):
+        """The prior KL term of the variational bound in bits per dimension (gaussian_diffusion.py:1573-1589): normal_kl
+        (losses.py:12-39) of q(x_T | x_0) against N(0, I) in the reference's expression order, on the caller's device.  Once per call."""
+        batch_size = x_start.shape[0]
+        t = th.tensor([self.num_timesteps - 1] * batch_size, device=x_start.device)
+        qt_mean, _, qt_log_variance = self.q_mean_variance(x_start, t)
+        logvar2 = th.tensor(0.0).to(qt_mean)
+        kl_prior = 0.5 * (-1.0 + logvar2 - qt_log_variance + th.exp(qt_log_variance - logvar2)
+                          + ((qt_mean - 0.0) ** 2) * th.exp(-logvar2))
+        return kl_prior.mean(dim=list(range(1, len(kl_prior.shape)))) / np.log(2.0)
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """One term of the variational bound in bits (gaussian_diffusion.py:1213-1246): p_mean_variance's launch (its two style draws),
+        then k_vb_terms on its pred_xstart -- the KL of the two posteriors where t > 0, the discretized decoder NLL where t == 0, chosen
+        per sample.  Returns {"output": [B], "pred_xstart"}; `t` may differ per sample wherever p_mean_variance allows it."""
+        self._no_inpainting(model_kwargs, "_vb_terms_bpd")
+        out = self.p_mean_variance(model, x_t, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs)
+        eng = self._engine_for(model, model_kwargs, "_vb_terms_bpd")
+        t = th.as_tensor(t)
+        dev = x_t.device
+        vb, _, _, _ = eng.vb_terms(_as_tensor(x_start, dev).float(), x_t, out["pred_xstart"], None,
+                                   indices=t.detach() if (t.is_cuda and x_t.is_cuda) else t.detach().cpu())
+        return {"output": _as_tensor(vb, dev), "pred_xstart": out["pred_xstart"]}
+
+    def _bpd_host_draws(self, nz, eps, proto):
+        """The torch_cpu draws of nz.shape[0] columns of calc_bpd_loop, in the reference's order per column (:1617, then RAG.py:10-13):
+        randn_like(x_start), randn(B, 1, D) of the cond pass, of the uncond pass.  Natively (ls_trng_randn continues torch's CPU
+        stream and hands the advanced state back) when the restatement reproduces this torch build, x_start is contiguous and nobody
+        has replaced torch's draw functions; with torch's own calls otherwise.  Either way the generator ends where the reference's does."""
+        from . import torch_rng
+        n, B, D = nz.shape[0], eps.shape[2], eps.shape[3]
+        intercepted = th.randn is not _TH_RANDN or th.randn_like is not _TH_RANDN_LIKE
+        native = torch_rng.variant() if (self.native_host_rng and proto.is_contiguous() and not intercepted) else -1
+        self.last_host_rng_native = native >= 0
+        if native >= 0:
+            lib = _lib.load_library()
+            st = th.get_rng_state()
+            for r in range(n):
+                for dst in (nz[r], eps[r, 0], eps[r, 1]):
+                    rc = lib.ls_trng_randn(st.data_ptr(), st.numel(), dst.data_ptr(), dst.numel(), int(native), torch_rng.n_threads())
+                    if rc != 0:
+                        raise _lib.EngineError(f"ls_trng_randn failed ({rc})")
+            th.set_rng_state(st)
+            return
+        for r in range(n):
+            nz[r].copy_(th.randn_like(proto, dtype=th.float32))
+            eps[r, 0] = th.randn(B, 1, D)[:, 0]
+            eps[r, 1] = th.randn(B, 1, D)[:, 0]
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None):
+        """The whole variational bound in bits per dimension and its per-timestep terms (gaussian_diffusion.py:1591-1646) as one device
+        loop (ls_bpd): per schedule index T-1 .. 0 a q_sample, one CFG-guided model evaluation and the per-sample reduction k_vb_terms,
+        captured in a hipGraph.  Returns total_bpd [B], prior_bpd [B], vb / xstart_mse / mse [B, T] (column k belongs to t = T - 1 - k)
+        on x_start's device.  noise_source 'torch_cpu' makes the reference's draws from torch's CPU generator (tapes larger than
+        tape_segment_bytes go through in column segments), 'philox' draws on the device; 'torch_device' is not built for this loop."""
+        self._no_inpainting(model_kwargs, "calc_bpd_loop")
+        if self.noise_source not in ("torch_cpu", "torch_device", "philox"):
+            raise ValueError(f"noise_source {self.noise_source!r}")
+        if self.noise_source == "torch_device":
+            raise NotImplementedError("calc_bpd_loop: noise_source='torch_device' is not built for the likelihood loop; use "
+                                      "'torch_cpu' (the reference's CPU draws) or 'philox'")
+        eng = self._engine_for(model, model_kwargs, "calc_bpd_loop")
+        shape = tuple(int(s) for s in x_start.shape)
+        if shape != (eng.batch, eng.J, eng.F, eng.T):
+            raise ValueError(f"x_start's shape {shape} does not match the prepared conditioning {(eng.batch, eng.J, eng.F, eng.T)}")
+        device = x_start.device
+        B, D, T = shape[0], eng.D, self.num_timesteps
+        x0 = x_start.detach().float()
+        if x0.is_cuda:
+            outs = tuple(th.empty(B, T, dtype=th.float32, device=th.device("cuda", eng.device)) for _ in range(3))
+        else:
+            outs = tuple(np.empty((B, T), np.float32) for _ in range(3))
+        kw = dict(clip_denoised=clip_denoised, two_pass_always=self.two_pass_always)
+        if self.noise_source == "philox":
+            drawn = int(th.randint(0, 2 ** 62, (1,)).item())
+            self.last_philox_seed = drawn if self.philox_seed is None else int(self.philox_seed)
+            eng.bpd(x0, outs, philox_seed=self.last_philox_seed, sample_offset=int(getattr(self, "sample_offset", 0)),
+                    use_graph=self.use_graph, **kw)
+            self.last_tape_segments = 1
+        else:
+            per_col = (2 * B * D + int(np.prod(shape))) * 4
+            K = T if per_col * T <= self.tape_segment_bytes else max(1, min(T, self.tape_segment_bytes // per_col))
+            proto = th.empty_strided(shape, x_start.stride())       # randn_like(x_start) follows x_start's memory order
+            nz, eps = th.empty((K,) + shape), th.empty(K, 2, B, D)
+            for k0 in range(0, T, K):
+                n = min(K, T - k0)
+                self._bpd_host_draws(nz[:n], eps[:n], proto)
+                # columns are independent: a segment is the same launches over its own columns (plain launches unless it is the whole loop)
+                eng.bpd(x0, outs, columns=(k0, n), noise_tape=nz[:n], eps_tape=eps[:n], use_graph=self.use_graph and K == T, **kw)
+            self.last_tape_segments = -(-T // K)
+        vb, xstart_mse, mse = (_as_tensor(o, device) for o in outs)
+        prior_bpd = self._prior_bpd(x_start)
+        total_bpd = vb.sum(dim=1) + prior_bpd
+        return {"total_bpd": total_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
 
     # ------------------------------------------------------------------ loops
     def _loop(self, sampler, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image,
