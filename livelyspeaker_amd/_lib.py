@@ -410,7 +410,48 @@ def plan_coop_slices(groups, dataset="ted", n_cus=256):
     return rc
 
 
-class Engine:
+class _Handle:
+    """What the five wrappers share: one C handle of the ``ls_<prefix>*`` family (``_prefix`` is ``"ls_"``, ``"ls_sag_"``, ...)."""
+
+    _prefix = "ls_"
+
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    def _create(self, cfg):
+        self.lib = load_library()
+        self.cfg = cfg
+        self.h = C.c_void_p()
+        rc = self._fn("create")(C.byref(self.cfg), C.byref(self.h))
+        if rc != 0:
+            raise EngineError(f"{self._prefix}create failed ({rc}): {self._fn('last_error')(None).decode()}")
+        self._stream = self._fn("stream")(self.h)
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self._fn("destroy")(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise EngineError(f"{what} failed ({rc}): {self._fn('last_error')(self.h).decode()}")
+        return rc
+
+    def _set_weights(self, sd: dict, commit=True):
+        for k, v in sd.items():
+            a = _np32(v)
+            self._check(self._fn("set_weight")(self.h, k.encode(), a.ctypes.data_as(c_f32p), a.size), f"{self._prefix}set_weight({k})")
+        if commit:
+            self._check(self._fn("commit_weights")(self.h), f"{self._prefix}commit_weights")
+
+
+class Engine(_Handle):
     """One handle = one GPU. Thin, typed wrapper over the C-ABI; all arrays in/out are host numpy
     (torch CUDA tensors on the same device may be passed to ``sample``/``prepare`` via ``*_device``)."""
 
@@ -420,14 +461,8 @@ class Engine:
 
     def __init__(self, njoints, nfeats, n_prefix_tokens, audio_len, n_emotions=0, nframes=34, n_pre_seq=4,
                  latent_dim=512, layers=8, n_speakers=1400, device=0, path=None):
-        self.lib = load_library()
-        self.cfg = LsConfig(njoints, nfeats, nframes, n_prefix_tokens, n_pre_seq, latent_dim, layers, audio_len,
-                            n_speakers, n_emotions, device, 0)
-        self.h = C.c_void_p()
-        rc = self.lib.ls_create(C.byref(self.cfg), C.byref(self.h))
-        if rc != 0:
-            raise EngineError(f"ls_create failed ({rc}): {self.lib.ls_last_error(None).decode()}")
-        self._stream = self.lib.ls_stream(self.h)
+        self._create(LsConfig(njoints, nfeats, nframes, n_prefix_tokens, n_pre_seq, latent_dim, layers, audio_len,
+                              n_speakers, n_emotions, device, 0))
         self.path = path or Engine.default_path
         if nframes != 34:
             self.path = "batch"                       # other frame counts have only the batch-level kernels (ls_set_path refuses the rest)
@@ -440,22 +475,6 @@ class Engine:
         self.batch = 0
         self.n_steps = 0
         self._keep = []
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.ls_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise EngineError(f"{what} failed ({rc}): {self.lib.ls_last_error(self.h).decode()}")
-        return rc
 
     def set_precision(self, mode):
         """'fp32' (default: fp32-accurate split-bf16 channel mixing in the fused step kernel, fp32 MFMA elsewhere), 'fp32_mfma'
@@ -478,10 +497,7 @@ class Engine:
 
     # ---- weights / schedule --------------------------------------------------------------------
     def load_state_dict(self, sd: dict):
-        for k, v in sd.items():
-            a = _np32(v)
-            self._check(self.lib.ls_set_weight(self.h, k.encode(), a.ctypes.data_as(c_f32p), a.size), f"ls_set_weight({k})")
-        self._check(self.lib.ls_commit_weights(self.h), "ls_commit_weights")
+        self._set_weights(sd)
 
     def set_schedule(self, sched):
         """sched: object with the GaussianDiffusion table attributes + timestep_map."""
@@ -781,40 +797,19 @@ class Engine:
         return {k: getattr(t, k) for k, _ in LsTiming._fields_}
 
 
-class SagEngine:
+class SagEngine(_Handle):
     """ctypes wrapper of the SAG decoder handle (ls_sag_*): Decoder_TRANSFORMER.forward on the GPU."""
+
+    _prefix = "ls_sag_"
 
     def __init__(self, njoints=9, nfeats=3, nframes=34, latent_dim=512, ff_size=1024, num_layers=3, num_heads=4,
                  n_pre_poses=4, device=0):
-        self.lib = load_library()
-        self.cfg = LsSagConfig(njoints, nfeats, nframes, latent_dim, ff_size, num_layers, num_heads, n_pre_poses, device, 0)
-        self.h = C.c_void_p()
-        rc = self.lib.ls_sag_create(C.byref(self.cfg), C.byref(self.h))
-        if rc != 0:
-            raise EngineError(f"ls_sag_create failed ({rc}): {self.lib.ls_sag_last_error(None).decode()}")
+        self._create(LsSagConfig(njoints, nfeats, nframes, latent_dim, ff_size, num_layers, num_heads, n_pre_poses, device, 0))
         self.J, self.F, self.T, self.D, self.device = njoints, nfeats, nframes, latent_dim, device
-        self._stream = self.lib.ls_sag_stream(self.h)
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.ls_sag_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise EngineError(f"{what} failed ({rc}): {self.lib.ls_sag_last_error(self.h).decode()}")
+        self._async_inputs = None
 
     def load_state_dict(self, sd: dict):
-        for k, v in sd.items():
-            a = _np32(v)
-            self._check(self.lib.ls_sag_set_weight(self.h, k.encode(), a.ctypes.data_as(c_f32p), a.size), f"ls_sag_set_weight({k})")
-        self._check(self.lib.ls_sag_commit_weights(self.h), "ls_sag_commit_weights")
+        self._set_weights(sd)
 
     def last_decode_ms(self) -> float:
         return float(self.lib.ls_sag_last_decode_ms(self.h))
@@ -825,17 +820,7 @@ class SagEngine:
         m = _Marshal(self.device, x, z, mask, stream=self._stream)
         B = int(x.shape[0])
         out, pout = m.out((B, self.J, self.F, self.T))
-        pmask = None
-        if mask is not None:
-            if m.on_device:
-                t = m.torch.as_tensor(mask).to(device=m.dev, dtype=m.torch.uint8).contiguous()
-                m.keep.append(t)
-                pmask = C.c_void_p(t.data_ptr())
-            else:
-                a = mask.detach().cpu().numpy() if hasattr(mask, "detach") else mask
-                a = np.ascontiguousarray(a, dtype=np.uint8)
-                m.keep.append(a)
-                pmask = a.ctypes.data_as(C.c_void_p)
+        pmask = m.u8(mask)
         m.ready()
         if not wait:
             if not m.on_device:
@@ -850,40 +835,18 @@ class SagEngine:
         return out
 
 
-class SagEncoderEngine:
+class SagEncoderEngine(_Handle):
     """ctypes wrapper of the SAG encoder handle (ls_sag_enc_*): Encoder_TRANSFORMER.forward (eval mode) on the GPU."""
 
+    _prefix = "ls_sag_enc_"
+
     def __init__(self, njoints=9, nfeats=3, nframes=34, latent_dim=512, ff_size=1024, num_layers=3, num_heads=4, device=0):
-        self.lib = load_library()
-        self.cfg = LsSagConfig(njoints, nfeats, nframes, latent_dim, ff_size, num_layers, num_heads, 0, device, 0)
-        self.h = C.c_void_p()
-        rc = self.lib.ls_sag_enc_create(C.byref(self.cfg), C.byref(self.h))
-        if rc != 0:
-            raise EngineError(f"ls_sag_enc_create failed ({rc}): {self.lib.ls_sag_enc_last_error(None).decode()}")
+        self._create(LsSagConfig(njoints, nfeats, nframes, latent_dim, ff_size, num_layers, num_heads, 0, device, 0))
         self.J, self.F, self.T, self.D, self.device = njoints, nfeats, nframes, latent_dim, device
-        self._stream = self.lib.ls_sag_enc_stream(self.h)
         self._async_inputs = None
 
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.ls_sag_enc_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise EngineError(f"{what} failed ({rc}): {self.lib.ls_sag_enc_last_error(self.h).decode()}")
-
     def load_state_dict(self, sd: dict):
-        for k, v in sd.items():
-            a = _np32(v)
-            self._check(self.lib.ls_sag_enc_set_weight(self.h, k.encode(), a.ctypes.data_as(c_f32p), a.size), f"ls_sag_enc_set_weight({k})")
-        self._check(self.lib.ls_sag_enc_commit_weights(self.h), "ls_sag_enc_commit_weights")
+        self._set_weights(sd)
 
     def last_encode_ms(self) -> float:
         return float(self.lib.ls_sag_enc_last_encode_ms(self.h))
@@ -917,23 +880,19 @@ class SagEncoderEngine:
         return out
 
 
-class Trainer:
+class Trainer(_Handle):
     """ctypes wrapper of the training-step handle (ls_train_*).  Master parameters, gradients and Adam moments are flat
     device arrays; ``grad`` is a torch CUDA tensor owned by this object so a data-parallel caller can all-reduce it
     (RCCL) between ``forward_backward`` and ``adamw``."""
 
+    _prefix = "ls_train_"
+
     def __init__(self, njoints, nfeats, n_prefix_tokens, audio_len, n_emotions=0, nframes=34, n_pre_seq=4, layers=8,
                  n_speakers=1400, device=0, diffusion_steps=1000, lambda_vel=1.0, kld_weight=0.01):
         import torch
-        self.lib = load_library()
-        self.cfg = LsTrainConfig(LsConfig(njoints, nfeats, nframes, n_prefix_tokens, n_pre_seq, 512, layers, audio_len, n_speakers,
-                                          n_emotions, device, 0), lambda_vel, kld_weight, diffusion_steps, 0)
-        self.h = C.c_void_p()
-        rc = self.lib.ls_train_create(C.byref(self.cfg), C.byref(self.h))
-        if rc != 0:
-            raise EngineError(f"ls_train_create failed ({rc}): {self.lib.ls_train_last_error(None).decode()}")
+        self._create(LsTrainConfig(LsConfig(njoints, nfeats, nframes, n_prefix_tokens, n_pre_seq, 512, layers, audio_len, n_speakers,
+                                            n_emotions, device, 0), lambda_vel, kld_weight, diffusion_steps, 0))
         self.J, self.F, self.T, self.device, self.n_prefix = njoints, nfeats, nframes, device, n_prefix_tokens
-        self._stream = self.lib.ls_train_stream(self.h)
         self.params = {}
         key = C.create_string_buffer(256)
         off, num = C.c_int64(), C.c_int64()
@@ -944,26 +903,9 @@ class Trainer:
         self.grad = torch.zeros(self.flat_size, dtype=torch.float32, device=torch.device("cuda", device))
         self.shapes = {}
 
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.ls_train_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise EngineError(f"{what} failed ({rc}): {self.lib.ls_train_last_error(self.h).decode()}")
-
     def load_state_dict(self, sd: dict):
-        for k, v in sd.items():
-            a = _np32(v)
-            self.shapes[k] = tuple(a.shape)
-            self._check(self.lib.ls_train_set_weight(self.h, k.encode(), a.ctypes.data_as(c_f32p), a.size), f"ls_train_set_weight({k})")
+        self.shapes.update((k, tuple(np.shape(v))) for k, v in sd.items())
+        self._set_weights(sd, commit=False)      # ls_train_set_weight writes the master parameters directly
 
     def state_dict(self) -> dict:
         out = {}
@@ -1034,39 +976,17 @@ class Trainer:
         return a
 
 
-class EvalEngine:
+class EvalEngine(_Handle):
     """ctypes wrapper of the FGD feature extractor (ls_eval_*): PoseEncoderConv in eval mode on the GPU."""
 
+    _prefix = "ls_eval_"
+
     def __init__(self, pose_dim=27, n_frames=34, base=32, hidden=(256, 128), device=0):
-        self.lib = load_library()
-        self.cfg = LsEvalConfig(pose_dim, n_frames, base, hidden[0], hidden[1], device)
-        self.h = C.c_void_p()
-        rc = self.lib.ls_eval_create(C.byref(self.cfg), C.byref(self.h))
-        if rc != 0:
-            raise EngineError(f"ls_eval_create failed ({rc}): {self.lib.ls_eval_last_error(None).decode()}")
+        self._create(LsEvalConfig(pose_dim, n_frames, base, hidden[0], hidden[1], device))
         self.pose_dim, self.T, self.base, self.device = pose_dim, n_frames, base, device
-        self._stream = self.lib.ls_eval_stream(self.h)
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.ls_eval_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc < 0:
-            raise EngineError(f"{what} failed ({rc}): {self.lib.ls_eval_last_error(self.h).decode()}")
 
     def load_state_dict(self, sd: dict):
-        for k, v in sd.items():
-            a = _np32(v).ravel()
-            self._check(self.lib.ls_eval_set_weight(self.h, k.encode(), a.ctypes.data_as(c_f32p), a.size), f"ls_eval_set_weight({k})")
-        self._check(self.lib.ls_eval_commit_weights(self.h), "ls_eval_commit_weights")
+        self._set_weights(sd)
 
     def features(self, poses):
         m = _Marshal(self.device, poses, stream=self._stream)

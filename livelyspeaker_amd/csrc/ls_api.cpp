@@ -4,7 +4,6 @@
 #include "ls_handle.h"
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,8 +11,6 @@
 using namespace ls;
 
 namespace {
-
-thread_local std::string g_create_error;     // message of this thread's last failed ls_create (handles may be created from several threads)
 
 const int kConvCin[4] = {1, 32, 64, 128};
 const int kConvCout[4] = {32, 64, 128, 256};
@@ -299,15 +296,7 @@ int build_shared_weights(ls_handle* h) {
     }
     // PositionalEncoding buffer (mlp_module.py:104-116), fp32 like the torch buffer
     {
-        std::vector<float> pe((size_t)kPeRows * D);
-        const float cexp = (float)(-std::log(10000.0) / D);
-        for (int i = 0; i < D / 2; ++i) {
-            const float div = expf((float)(2 * i) * cexp);
-            for (int p = 0; p < kPeRows; ++p) {
-                pe[(size_t)p * D + 2 * i] = sinf((float)p * div);
-                pe[(size_t)p * D + 2 * i + 1] = cosf((float)p * div);
-            }
-        }
+        const std::vector<float> pe = pe_table(kPeRows, D);
         if ((rc = upload(h, h->pe, pe.data(), pe.size() * sizeof(float))) != LS_OK) return rc;
     }
     return LS_OK;
@@ -454,16 +443,6 @@ int ls::build_temb_rows(ls_handle* h, const long long* idx_dev, int n, DevBuf& t
     return LS_OK;
 }
 
-int ls::fail(ls_handle* h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf; else g_create_error = buf;
-    return code;
-}
-
 int ls::ensure_temb_table(ls_handle* h) {
     if (h->temb_valid) return LS_OK;
     int rc = upload(h, h->tmap_dev, h->tmap.data(), h->tmap.size() * sizeof(long long));
@@ -485,21 +464,21 @@ extern "C" {
 
 int ls_abi_version(void) { return LS_ABI_VERSION; }
 
-const char* ls_last_error(const ls_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+const char* ls_last_error(const ls_handle* h) { return last_error(h); }
 
 int ls_create(const ls_config* cfg, ls_handle** out) {
-    if (!cfg || !out) return fail(nullptr, LS_EINVAL, "ls_create: null argument");
+    if (!cfg || !out) return fail<ls_handle>(nullptr, LS_EINVAL, "ls_create: null argument");
     *out = nullptr;
-    if (cfg->latent_dim != kD) return fail(nullptr, LS_EUNSUPPORTED, "latent_dim must be %d", kD);
-    if (cfg->nframes < cfg->n_pre_seq || cfg->nframes < 1 || cfg->nframes > 4096) return fail(nullptr, LS_EINVAL, "nframes out of range");
+    if (cfg->latent_dim != kD) return fail<ls_handle>(nullptr, LS_EUNSUPPORTED, "latent_dim must be %d", kD);
+    if (cfg->nframes < cfg->n_pre_seq || cfg->nframes < 1 || cfg->nframes > 4096) return fail<ls_handle>(nullptr, LS_EINVAL, "nframes out of range");
     const int JF = cfg->njoints * cfg->nfeats;
     Variant var;
     if (JF == 27 && cfg->n_prefix_tokens == 1) var = kTED;
     else if (JF == 282 && cfg->n_prefix_tokens == 2) var = kBEAT;
-    else return fail(nullptr, LS_EUNSUPPORTED, "unsupported shape: J*F=%d with %d prefix tokens (built: 27/1 TED, 282/2 BEAT)",
+    else return fail<ls_handle>(nullptr, LS_EUNSUPPORTED, "unsupported shape: J*F=%d with %d prefix tokens (built: 27/1 TED, 282/2 BEAT)",
                      JF, cfg->n_prefix_tokens);
-    if (cfg->layers < 1 || cfg->layers > 64) return fail(nullptr, LS_EINVAL, "layers out of range");
-    if (cfg->n_prefix_tokens == 2 && cfg->n_emotions <= 0) return fail(nullptr, LS_EINVAL, "BEAT variant needs n_emotions > 0");
+    if (cfg->layers < 1 || cfg->layers > 64) return fail<ls_handle>(nullptr, LS_EINVAL, "layers out of range");
+    if (cfg->n_prefix_tokens == 2 && cfg->n_emotions <= 0) return fail<ls_handle>(nullptr, LS_EINVAL, "BEAT variant needs n_emotions > 0");
     int L = cfg->audio_len;
     int convL[5];
     convL[0] = L;
@@ -507,15 +486,15 @@ int ls_create(const ls_config* cfg, ls_handle** out) {
         L = (L + 2 * kConvPad[i] - 15) / kConvStride[i] + 1;
         convL[i + 1] = L;
     }
-    if (L != cfg->nframes) return fail(nullptr, LS_EINVAL, "audio_len %d yields %d audio frames, need %d", cfg->audio_len, L, cfg->nframes);
+    if (L != cfg->nframes) return fail<ls_handle>(nullptr, LS_EINVAL, "audio_len %d yields %d audio frames, need %d", cfg->audio_len, L, cfg->nframes);
     hipError_t e = hipSetDevice(cfg->device);
-    if (e != hipSuccess) return fail(nullptr, LS_EHIP, "hipSetDevice(%d): %s", cfg->device, hipGetErrorString(e));
+    if (e != hipSuccess) return fail<ls_handle>(nullptr, LS_EHIP, "hipSetDevice(%d): %s", cfg->device, hipGetErrorString(e));
     ls_handle* h = new ls_handle();
     h->cfg = *cfg;
     {   // chip geometry: the step-time models were measured on 256 CUs; rounds, residency and the throughput-bound terms follow the device
         hipDeviceProp_t prop;
         e = hipGetDeviceProperties(&prop, cfg->device);
-        if (e != hipSuccess) { delete h; return fail(nullptr, LS_EHIP, "hipGetDeviceProperties(%d): %s", cfg->device, hipGetErrorString(e)); }
+        if (e != hipSuccess) return abandon(h, ls_destroy, fail<ls_handle>(nullptr, LS_EHIP, "hipGetDeviceProperties(%d): %s", cfg->device, hipGetErrorString(e)));
         h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         h->max_thr_cu = prop.maxThreadsPerMultiProcessor;
         h->coop_groups_max = 2 * h->n_cu / 8 < kCoopMaxGroups ? 2 * h->n_cu / 8 : kCoopMaxGroups;       // every slice of a launch must be resident: they wait for each other
@@ -538,39 +517,39 @@ int ls_create(const ls_config* cfg, ls_handle** out) {
     memcpy(h->convL, convL, sizeof convL);
     for (hipStream_t* ps : {&h->stream, &h->copy_stream}) {
         e = hipStreamCreateWithFlags(ps, hipStreamNonBlocking);
-        if (e != hipSuccess) { delete h; return fail(nullptr, LS_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return abandon(h, ls_destroy, fail<ls_handle>(nullptr, LS_EHIP, "hipStreamCreate: %s", hipGetErrorString(e)));
     }
     std::vector<hipEvent_t*> evs = {&h->ev_cs[0], &h->ev_cd[0], &h->ev_seg[0], &h->ev_cs[1], &h->ev_cd[1], &h->ev_seg[1]};
     for (auto& ev : h->ev) evs.push_back(&ev);
     for (hipEvent_t* pe : evs) {
         e = hipEventCreate(pe);
-        if (e != hipSuccess) { delete h; return fail(nullptr, LS_EHIP, "hipEventCreate: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return abandon(h, ls_destroy, fail<ls_handle>(nullptr, LS_EHIP, "hipEventCreate: %s", hipGetErrorString(e)));
     }
     e = init_step_kernels();
-    if (e != hipSuccess) { delete h; return fail(nullptr, LS_EHIP, "hipFuncSetAttribute(step kernel LDS): %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return abandon(h, ls_destroy, fail<ls_handle>(nullptr, LS_EHIP, "hipFuncSetAttribute(step kernel LDS): %s", hipGetErrorString(e)));
     if (!h->fused && mix_supports(cfg->nframes + cfg->n_prefix_tokens)) {
         e = init_mix_kernels();
         if (e == hipSuccess) e = h->co_err.ensure(sizeof(unsigned));
         if (e == hipSuccess) e = hipMemsetAsync(h->co_err.p, 0, sizeof(unsigned), h->stream);
-        if (e != hipSuccess) { delete h; return fail(nullptr, LS_EHIP, "long-sequence mixer kernel setup: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return abandon(h, ls_destroy, fail<ls_handle>(nullptr, LS_EHIP, "long-sequence mixer kernel setup: %s", hipGetErrorString(e)));
     }
     if (h->fused) {         // sample-split kernel: LDS opt-in and one launch's worth of exchange workspaces (independent of the batch)
         e = init_coop_kernels();
         if (e == hipSuccess) e = init_pass_kernels();
         if (e == hipSuccess) e = h->co_err.ensure(sizeof(unsigned));
         if (e == hipSuccess) e = hipMemsetAsync(h->co_err.p, 0, sizeof(unsigned), h->stream);
-        if (e != hipSuccess) { delete h; return fail(nullptr, LS_EHIP, "sample-split kernel setup: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return abandon(h, ls_destroy, fail<ls_handle>(nullptr, LS_EHIP, "sample-split kernel setup: %s", hipGetErrorString(e)));
     }
 #ifdef LS_DEBUG
     if (h->prof_on) {
         std::vector<unsigned long long> z((size_t)kWaves * kProfPoints, 0ull);
-        if (upload(h, h->prof, z.data(), z.size() * sizeof(unsigned long long)) != LS_OK) { g_create_error = h->err; delete h; return LS_EHIP; }
+        if (upload(h, h->prof, z.data(), z.size() * sizeof(unsigned long long)) != LS_OK) { create_error<ls_handle>() = h->err; return abandon(h, ls_destroy, LS_EHIP); }
         std::vector<unsigned long long> zw(4096, 0ull);      // [1024][2] stamps | [2048] hardware ids (k_pass)
-        if (upload(h, h->wgt, zw.data(), zw.size() * sizeof(unsigned long long)) != LS_OK) { g_create_error = h->err; delete h; return LS_EHIP; }
+        if (upload(h, h->wgt, zw.data(), zw.size() * sizeof(unsigned long long)) != LS_OK) { create_error<ls_handle>() = h->err; return abandon(h, ls_destroy, LS_EHIP); }
     }
 #endif
     CallParams cp{0, 0, 0, 0};
-    if (upload(h, h->callp, &cp, sizeof cp) != LS_OK) { g_create_error = h->err; delete h; return LS_EHIP; }
+    if (upload(h, h->callp, &cp, sizeof cp) != LS_OK) { create_error<ls_handle>() = h->err; return abandon(h, ls_destroy, LS_EHIP); }
     *out = h;
     return LS_OK;
 }

@@ -6,13 +6,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/ls_hip.h"
+#include "ls_host.h"
 #include "ls_internal.h"
 #include "ls_train.h"
 
@@ -45,33 +45,11 @@ struct ls_eval {
     std::string err;
     std::map<std::string, std::vector<float>> w;
     bool committed = false;
-    float* cw[4] = {nullptr, nullptr, nullptr, nullptr};
-    float* cb[4] = {nullptr, nullptr, nullptr, nullptr};
-    float* lw[4] = {nullptr, nullptr, nullptr, nullptr};
-    float* lb[4] = {nullptr, nullptr, nullptr, nullptr};
-    float *in = nullptr, *a[4] = {nullptr, nullptr, nullptr, nullptr}, *h[4] = {nullptr, nullptr, nullptr, nullptr};
-    int capB = 0;
+    DevBuf cw[4], cb[4], lw[4], lb[4];      // folded conv / linear weights and biases
+    DevBuf in, a[4], h[4];                  // the batch's poses, conv outputs, linear outputs
 };
 
 namespace {
-
-std::string g_eval_create_error;
-
-int efail(ls_eval* h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf; else g_eval_create_error = buf;
-    return code;
-}
-
-#define EHIP(h, expr)                                                                                                     \
-    do {                                                                                                                  \
-        hipError_t e__ = (expr);                                                                                          \
-        if (e__ != hipSuccess) return efail((h), LS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-    } while (0)
 
 struct ConvShape { int cin, cout, k, stride, lin, lout; };
 
@@ -88,10 +66,9 @@ void shapes(const ls_eval_config& c, ConvShape (&cs)[4], int (&lin)[4][2]) {
     for (int i = 0; i < 4; ++i) { lin[i][0] = dims[i]; lin[i][1] = dims[i + 1]; }
 }
 
-int upload(ls_eval* h, float*& dst, const std::vector<float>& v) {
-    if (dst) { EHIP(h, hipFree(dst)); dst = nullptr; }
-    EHIP(h, hipMalloc(reinterpret_cast<void**>(&dst), v.size() * 4));
-    EHIP(h, hipMemcpy(dst, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+int upload(ls_eval* h, DevBuf& dst, const std::vector<float>& v) {
+    HIPCHK(h, dst.ensure(v.size() * 4));
+    HIPCHK(h, hipMemcpy(dst.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
     return LS_OK;
 }
 
@@ -100,18 +77,16 @@ int upload(ls_eval* h, float*& dst, const std::vector<float>& v) {
 extern "C" {
 
 int ls_eval_create(const ls_eval_config* cfg, ls_eval** out) {
-    if (!cfg || !out) return efail(nullptr, LS_EINVAL, "ls_eval_create: null argument");
+    if (!cfg || !out) return fail<ls_eval>(nullptr, LS_EINVAL, "ls_eval_create: null argument");
     if (cfg->pose_dim <= 0 || cfg->base <= 0 || cfg->hidden1 <= 0 || cfg->hidden2 <= 0 || cfg->n_frames < 12)
-        return efail(nullptr, LS_EINVAL, "ls_eval_create: bad configuration");
+        return fail<ls_eval>(nullptr, LS_EINVAL, "ls_eval_create: bad configuration");
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return efail(nullptr, LS_EHIP, "ls_eval_create: no HIP device (no CPU path exists)");
-    if (cfg->device < 0 || cfg->device >= n) return efail(nullptr, LS_EINVAL, "ls_eval_create: device %d out of range", cfg->device);
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail<ls_eval>(nullptr, LS_EHIP, "ls_eval_create: no HIP device (no CPU path exists)");
+    if (cfg->device < 0 || cfg->device >= n) return fail<ls_eval>(nullptr, LS_EINVAL, "ls_eval_create: device %d out of range", cfg->device);
     ls_eval* h = new ls_eval();
     h->cfg = *cfg;
-    if (hipSetDevice(cfg->device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete h;
-        return efail(nullptr, LS_EHIP, "ls_eval_create: stream creation failed");
-    }
+    if (hipSetDevice(cfg->device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
+        return abandon(h, ls_eval_destroy, fail<ls_eval>(nullptr, LS_EHIP, "ls_eval_create: stream creation failed"));
     *out = h;
     return LS_OK;
 }
@@ -120,21 +95,18 @@ void ls_eval_destroy(ls_eval* h) {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < 4; ++i)
-        for (float* p : {h->cw[i], h->cb[i], h->lw[i], h->lb[i], h->a[i], h->h[i]}) if (p) (void)hipFree(p);
-    if (h->in) (void)hipFree(h->in);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
-const char* ls_eval_last_error(const ls_eval* h) { return h ? h->err.c_str() : g_eval_create_error.c_str(); }
+const char* ls_eval_last_error(const ls_eval* h) { return last_error(h); }
 
 int ls_eval_set_weight(ls_eval* h, const char* key, const float* data, size_t n) {
-    if (!h || !key || !data) return efail(h, LS_EINVAL, "ls_eval_set_weight: null argument");
+    if (!h || !key || !data) return fail(h, LS_EINVAL, "ls_eval_set_weight: null argument");
     const std::string k(key);
     // the auto-encoder checkpoint also holds the decoder and fc_logvar: accepted and ignored (never on this path)
     if (k.rfind("decoder.", 0) == 0 || k.find("fc_logvar") != std::string::npos || k.find("num_batches_tracked") != std::string::npos) return LS_OK;
-    if (k.rfind("pose_encoder.", 0) != 0) return efail(h, LS_EINVAL, "ls_eval_set_weight: unexpected key '%s'", key);
+    if (k.rfind("pose_encoder.", 0) != 0) return fail(h, LS_EINVAL, "ls_eval_set_weight: unexpected key '%s'", key);
     h->w[k].assign(data, data + n);
     h->committed = false;
     return LS_OK;
@@ -142,14 +114,14 @@ int ls_eval_set_weight(ls_eval* h, const char* key, const float* data, size_t n)
 
 int ls_eval_commit_weights(ls_eval* h) {
     if (!h) return LS_EINVAL;
-    EHIP(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipSetDevice(h->cfg.device));
     ConvShape cs[4];
     int lin[4][2];
     shapes(h->cfg, cs, lin);
     auto get = [&](const std::string& k, size_t n, const std::vector<float>** out) -> int {
         auto it = h->w.find(k);
-        if (it == h->w.end()) return efail(h, LS_ESTATE, "ls_eval_commit_weights: missing key '%s'", k.c_str());
-        if (it->second.size() != n) return efail(h, LS_EINVAL, "ls_eval_commit_weights: '%s' has %zu elements, expected %zu", k.c_str(), it->second.size(), n);
+        if (it == h->w.end()) return fail(h, LS_ESTATE, "ls_eval_commit_weights: missing key '%s'", k.c_str());
+        if (it->second.size() != n) return fail(h, LS_EINVAL, "ls_eval_commit_weights: '%s' has %zu elements, expected %zu", k.c_str(), it->second.size(), n);
         *out = &it->second;
         return LS_OK;
     };
@@ -191,53 +163,45 @@ int ls_eval_commit_weights(ls_eval* h) {
 }
 
 int ls_eval_features(ls_eval* h, int batch, int on_device, const float* poses, float* feat) {
-    if (!h || !poses || !feat) return efail(h, LS_EINVAL, "ls_eval_features: null argument");
-    if (!h->committed) return efail(h, LS_ESTATE, "ls_eval_features: weights are not committed");
-    if (batch <= 0) return efail(h, LS_EINVAL, "ls_eval_features: batch must be positive");
-    EHIP(h, hipSetDevice(h->cfg.device));
+    if (!h || !poses || !feat) return fail(h, LS_EINVAL, "ls_eval_features: null argument");
+    if (!h->committed) return fail(h, LS_ESTATE, "ls_eval_features: weights are not committed");
+    if (batch <= 0) return fail(h, LS_EINVAL, "ls_eval_features: batch must be positive");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
     ConvShape cs[4];
     int lin[4][2];
     shapes(h->cfg, cs, lin);
     const int B = batch, T = h->cfg.n_frames, D = h->cfg.pose_dim;
-    if (B > h->capB) {
-        for (int i = 0; i < 4; ++i) {
-            if (h->a[i]) EHIP(h, hipFree(h->a[i]));
-            if (h->h[i]) EHIP(h, hipFree(h->h[i]));
-            h->a[i] = h->h[i] = nullptr;
-            EHIP(h, hipMalloc(reinterpret_cast<void**>(&h->a[i]), (size_t)B * cs[i].cout * cs[i].lout * 4));
-            EHIP(h, hipMalloc(reinterpret_cast<void**>(&h->h[i]), (size_t)B * lin[i][1] * 4));
-        }
-        if (h->in) EHIP(h, hipFree(h->in));
-        h->in = nullptr;
-        EHIP(h, hipMalloc(reinterpret_cast<void**>(&h->in), (size_t)B * T * D * 4));
-        h->capB = B;
+    for (int i = 0; i < 4; ++i) {
+        HIPCHK(h, h->a[i].ensure((size_t)B * cs[i].cout * cs[i].lout * 4));
+        HIPCHK(h, h->h[i].ensure((size_t)B * lin[i][1] * 4));
     }
+    HIPCHK(h, h->in.ensure((size_t)B * T * D * 4));
     hipStream_t st = h->stream;
-    EHIP(h, hipMemcpyAsync(h->in, poses, (size_t)B * T * D * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->in.p, poses, (size_t)B * T * D * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     for (int i = 0; i < 4; ++i) {
         // layer 0 reads poses [B][T][D] as (b, c = d, l = t): poses.transpose(1, 2) (embedding_net.py:71)
-        const float* src = i == 0 ? h->in : h->a[i - 1];
+        const float* src = i == 0 ? h->in.f() : h->a[i - 1].f();
         const long long sb = i == 0 ? (long long)T * D : (long long)cs[i].cin * cs[i].lin;
         const long long sc = i == 0 ? 1 : cs[i].lin, sl = i == 0 ? D : 1;
         const size_t total = (size_t)B * cs[i].cout * cs[i].lout;
-        hipLaunchKernelGGL(k_conv_small, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, sb, sc, sl, h->cw[i], h->cb[i], h->a[i],
+        hipLaunchKernelGGL(k_conv_small, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, sb, sc, sl, h->cw[i].f(), h->cb[i].f(), h->a[i].f(),
                            cs[i].cin, cs[i].cout, cs[i].k, cs[i].stride, cs[i].lout, i < 3 ? 0.2f : 1.0f, total);
-        EHIP(h, hipGetLastError());
+        HIPCHK(h, hipGetLastError());
     }
-    const float* x = h->a[3];                     // flatten(1): [B][base][12] is already [B][12*base]
+    const float* x = h->a[3].f();                     // flatten(1): [B][base][12] is already [B][12*base]
     for (int i = 0; i < 4; ++i) {
         GemmArgs a{};
         a.A = op_rows(x, lin[i][0], B, lin[i][0]);
-        a.B = op_rows(h->lw[i], lin[i][0], lin[i][1], lin[i][0]);
-        a.C = h->h[i];
+        a.B = op_rows(h->lw[i].f(), lin[i][0], lin[i][1], lin[i][0]);
+        a.C = h->h[i].f();
         a.cri = INT_MAX; a.cro = 0; a.crs = lin[i][1]; a.cns = 1;
-        a.bias = h->lb[i];
+        a.bias = h->lb[i].f();
         a.M = B; a.N = lin[i][1]; a.K = lin[i][0];
-        EHIP(h, launch_gemm_tr(a, true, true, 1, st));
-        x = h->h[i];
+        HIPCHK(h, launch_gemm_tr(a, true, true, 1, st));
+        x = h->h[i].f();
     }
-    EHIP(h, hipMemcpyAsync(feat, h->h[3], (size_t)B * h->cfg.base * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-    EHIP(h, hipStreamSynchronize(st));
+    HIPCHK(h, hipMemcpyAsync(feat, h->h[3].p, (size_t)B * h->cfg.base * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
     return LS_OK;
 }
 

@@ -1,8 +1,10 @@
-// Host-only declarations shared by the translation units behind include/ls_hip.h (ls_api.cpp: handle, weights, schedule, preparation;
-// ls_plan.cpp: the step plan and the step launchers; ls_sample.cpp: the diffusion loop and the single-step entries): the handle,
-// error reporting, copies between caller and internal buffers, and the guard of buffers a captured loop holds by address.
+// Host-only declarations shared by the translation units behind the sampling ABI of include/ls_hip.h (ls_api.cpp: handle, weights,
+// schedule, preparation; ls_plan.cpp: the step plan and the step launchers; ls_sample.cpp: the diffusion loop and the single-step
+// entries): the handle, copies between caller and internal buffers, and the guard of buffers a captured loop holds by address.
+// The device buffer (DevBuf) and the error path (fail, HIPCHK) are those of every handle: ls_host.h.
 #pragma once
 #include "ls_hip.h"
+#include "ls_host.h"
 #include "ls_internal.h"
 
 #include <map>
@@ -10,25 +12,6 @@
 #include <vector>
 
 namespace ls {
-
-// a device allocation that only grows; freed with its owner (the handle's device must be current)
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { release(); }
-    hipError_t ensure(size_t n) {
-        if (n <= bytes) return hipSuccess;
-        if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; bytes = 0; }
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    float* f() const { return static_cast<float*>(p); }
-};
 
 // one piece of a step plan: samples [first, first + n) of the prepared batch on one kernel family
 // (0 fused: one workgroup per sample, 1 batch-level kernels, 2 sample-split kernel, 3 one workgroup per (sample, pass))
@@ -155,7 +138,6 @@ struct ls_handle {
 namespace ls {
 
 // ---- defined in ls_api.cpp
-int fail(ls_handle* h, int code, const char* fmt, ...);     // records the message (h == nullptr: this thread's ls_create error), returns code
 int ensure_temb_table(ls_handle* h);
 int build_temb_rows(ls_handle* h, const long long* idx_dev, int n, DevBuf& tmp, DevBuf& out);
 void resolve_prepare_timing(ls_handle* h, bool block);
@@ -169,13 +151,6 @@ hipError_t coop_reset(ls_handle* h, hipStream_t st);
 int advance_tags(ls_handle* h, hipStream_t st);
 int coop_check(ls_handle* h);
 void report_path(ls_handle* h, bool pair);
-
-#define HIPCHK(h, expr)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess)                                                                  \
-            return ::ls::fail((h), LS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-    } while (0)
 
 // copy a caller buffer (host or device) into an internal device buffer
 inline int ingest(ls_handle* h, DevBuf& d, const void* src, size_t bytes, int on_device) {

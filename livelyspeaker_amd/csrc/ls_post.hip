@@ -5,6 +5,7 @@
 // Tiny and latency-bound (918 floats per clip); it exists so the sampled tensor never has to leave the GPU in the
 // reference's [B,J,F,T] layout just to be transposed and scanned on the host.
 #include "ls_hip.h"
+#include "ls_host.h"
 #include "ls_internal.h"
 
 namespace ls {
@@ -103,16 +104,17 @@ extern "C" int ls_ted_post(int device, int on_device, int batch, const ls_post_c
     const size_t n_in = (size_t)batch * JF * kT, n_pose = (size_t)batch * kT * c->n_pose_joints * 3, n_t = (size_t)batch * kT;
     float *d_in = nullptr, *d_al = nullptr, *d_pose = nullptr, *d_diff = nullptr;
     unsigned char* d_mask = nullptr;
+    DevBuf t_in, t_al, t_pose, t_diff, t_mask;      // the host path's device temporaries, freed on return
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
     if (on_device) {
         d_in = const_cast<float*>(sample); d_al = aligned; d_pose = pose; d_diff = angle_diff; d_mask = beat_mask;
     } else {
-        chk(hipMalloc(&d_in, n_in * 4));
-        if (aligned) chk(hipMalloc(&d_al, n_in * 4));
-        if (pose) chk(hipMalloc(&d_pose, n_pose * 4));
-        if (angle_diff) chk(hipMalloc(&d_diff, n_t * 4));
-        if (beat_mask) chk(hipMalloc(&d_mask, n_t));
+        chk(t_in.ensure(n_in * 4)); d_in = t_in.f();
+        if (aligned) { chk(t_al.ensure(n_in * 4)); d_al = t_al.f(); }
+        if (pose) { chk(t_pose.ensure(n_pose * 4)); d_pose = t_pose.f(); }
+        if (angle_diff) { chk(t_diff.ensure(n_t * 4)); d_diff = t_diff.f(); }
+        if (beat_mask) { chk(t_mask.ensure(n_t)); d_mask = static_cast<unsigned char*>(t_mask.p); }
         if (e == hipSuccess) chk(hipMemcpy(d_in, sample, n_in * 4, hipMemcpyHostToDevice));
     }
     if (e == hipSuccess) {
@@ -125,8 +127,6 @@ extern "C" int ls_ted_post(int device, int on_device, int batch, const ls_post_c
         if (e == hipSuccess && pose) chk(hipMemcpy(pose, d_pose, n_pose * 4, hipMemcpyDeviceToHost));
         if (e == hipSuccess && angle_diff) chk(hipMemcpy(angle_diff, d_diff, n_t * 4, hipMemcpyDeviceToHost));
         if (e == hipSuccess && beat_mask) chk(hipMemcpy(beat_mask, d_mask, n_t, hipMemcpyDeviceToHost));
-        (void)hipFree(d_in); if (d_al) (void)hipFree(d_al); if (d_pose) (void)hipFree(d_pose);
-        if (d_diff) (void)hipFree(d_diff); if (d_mask) (void)hipFree(d_mask);
     }
     return e == hipSuccess ? LS_OK : LS_EHIP;
 }
@@ -174,14 +174,15 @@ extern "C" int ls_beat_post(int device, int on_device, int batch, int njoints, c
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;
     const size_t n_in = (size_t)batch * njoints * 6 * kT, n_eu = (size_t)batch * kT * njoints * 3, total = (size_t)batch * kT * njoints;
     float *d_in = nullptr, *d_dec = nullptr, *d_eu = nullptr;
+    DevBuf t_in, t_dec, t_eu;      // the host path's device temporaries, freed on return
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
     if (on_device) {
         d_in = const_cast<float*>(sample); d_dec = decoded; d_eu = euler_deg;
     } else {
-        chk(hipMalloc(&d_in, n_in * 4));
-        if (decoded) chk(hipMalloc(&d_dec, n_in * 4));
-        if (euler_deg) chk(hipMalloc(&d_eu, n_eu * 4));
+        chk(t_in.ensure(n_in * 4)); d_in = t_in.f();
+        if (decoded) { chk(t_dec.ensure(n_in * 4)); d_dec = t_dec.f(); }
+        if (euler_deg) { chk(t_eu.ensure(n_eu * 4)); d_eu = t_eu.f(); }
         if (e == hipSuccess) chk(hipMemcpy(d_in, sample, n_in * 4, hipMemcpyHostToDevice));
     }
     if (e == hipSuccess) {
@@ -192,7 +193,6 @@ extern "C" int ls_beat_post(int device, int on_device, int batch, int njoints, c
     if (!on_device) {
         if (e == hipSuccess && decoded) chk(hipMemcpy(decoded, d_dec, n_in * 4, hipMemcpyDeviceToHost));
         if (e == hipSuccess && euler_deg) chk(hipMemcpy(euler_deg, d_eu, n_eu * 4, hipMemcpyDeviceToHost));
-        (void)hipFree(d_in); if (d_dec) (void)hipFree(d_dec); if (d_eu) (void)hipFree(d_eu);
     }
     return e == hipSuccess ? LS_OK : LS_EHIP;
 }

@@ -5,7 +5,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -13,6 +12,7 @@
 #include <vector>
 
 #include "../../include/ls_hip.h"
+#include "ls_host.h"
 #include "ls_internal.h"
 #include "ls_train.h"
 
@@ -20,25 +20,12 @@ using namespace ls;
 
 namespace {
 
-std::string g_train_create_error;
-
-struct Buf {
-    void* p = nullptr;       // what the kernels read: the buffer's own allocation, or a caller's device tensor for the duration of a call
-    void* own = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t n) {
-        if (n > bytes) {
-            if (own) { hipError_t e = hipFree(own); if (e != hipSuccess) return e; own = nullptr; bytes = 0; }
-            hipError_t e = hipMalloc(&own, n);
-            if (e != hipSuccess) return e;
-            bytes = n;
-        }
-        p = own;
-        return hipSuccess;
-    }
-    void alias(const void* q) { p = const_cast<void*>(q); }
-    void release() { if (own) (void)hipFree(own); p = own = nullptr; bytes = 0; }
-    float* f() const { return static_cast<float*>(p); }
+// A batch input: the handle's copy of a host array, or a caller's device tensor read in place for the duration of a call.
+struct BatchIn {
+    DevBuf own;
+    const void* p = nullptr;      // what the kernels read
+    const float* f() const { return static_cast<const float*>(p); }
+    const int64_t* i64() const { return static_cast<const int64_t*>(p); }
 };
 
 struct Param { std::string key; int64_t off, n; };
@@ -65,51 +52,33 @@ struct ls_trainer {
     bool fork = LS_TRAIN_FORK_DEFAULT != 0;
     // this step's batch: the caller's device tensors in place, or the handle's copies of host inputs (ls_train_forward_backward
     // synchronises before it returns, so nothing is read after the call)
-    const float *audio_in = nullptr, *in_x = nullptr, *in_noise = nullptr, *in_origin = nullptr, *in_drop = nullptr, *in_eps = nullptr;
-    const int64_t *in_vid = nullptr, *in_emo = nullptr;
-    Buf wpad, waT;                                             // input_mapping.weight zero-padded to [512][KFP]; its audio columns transposed [256][512]
-    Buf hostpack;                                              // q_sample coefficients + timestep rows of the batch: [ca | cb | tidx], one upload
+    BatchIn x_start, noise, origin_x, drop, eps, audio, vid, emo;
+    DevBuf wpad, waT;                                             // input_mapping.weight zero-padded to [512][KFP]; its audio columns transposed [256][512]
+    DevBuf hostpack;                                              // q_sample coefficients + timestep rows of the batch: [ca | cb | tidx], one upload
     std::string err;
     std::vector<Param> table;
     std::map<std::string, int> index;
     int64_t flat = 0;
-    Buf P, M, V;                         // master params, Adam moments
+    DevBuf P, M, V;                         // master params, Adam moments
     int64_t adam_step = 0;
     bool have_sched = false;
     std::vector<double> sac, s1mac;
     std::vector<int64_t> tmap;
-    Buf pe;
+    DevBuf pe;
     // batch-sized buffers
     int capB = 0;
-    Buf x_start, noise, drop, eps, audio, origin_x, vid, emo, ca, cb, tidx;
-    Buf c[4], st[3], img[4], dimg[4], feat, x_t, zc, mu, lv, pe_rows, pre1, hid, emb, xcur;
-    Buf X1, A1, X2, A2, S1, S2, dA2, dA1, colpart, dembp;      // [L][B*S][512] (S1/S2: [L][B*S][2]) written by the fused training forward; X1 / X2 hold x-hat
-    Buf twch, tbch, tww, tbtok, tl1a, tl1b, tl2a, tl2b, tdevw, twchT, twwT;    // mixer weight images + the DevWeights block k_step reads
+    DevBuf ca, cb, tidx;
+    DevBuf c[4], st[3], img[4], dimg[4], feat, x_t, zc, mu, lv, pe_rows, pre1, hid, emb, xcur;
+    DevBuf X1, A1, X2, A2, S1, S2, dA2, dA1, colpart, dembp;      // [L][B*S][512] (S1/S2: [L][B*S][2]) written by the fused training forward; X1 / X2 hold x-hat
+    DevBuf twch, tbch, tww, tbtok, tl1a, tl1b, tl2a, tl2b, tdevw, twchT, twwT;    // mixer weight images + the DevWeights block k_step reads
     TrainImgArgs img_args{};
-    Buf out, dout, lossp, kldp, terms, G, part, pw, pb, demb, dmu, dlv, dzc, dhid, dAf, dAt, col, dc[3], wmom, ws, part2, ws2;
+    DevBuf out, dout, lossp, kldp, terms, G, part, pw, pb, demb, dmu, dlv, dzc, dhid, dAf, dAt, col, dc[3], wmom, ws, part2, ws2;
     size_t ws_floats = 0;
     int B = 0;
     bool have_forward = false;
 };
 
 namespace {
-
-int fail(ls_trainer* h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf; else g_train_create_error = buf;
-    return code;
-}
-
-#define HIPCHK(h, expr)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess)                                                                  \
-            return fail((h), LS_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-    } while (0)
 
 void add_param(ls_trainer* h, const std::string& key, int64_t n) {
     h->index[key] = (int)h->table.size();
@@ -123,13 +92,18 @@ std::string lk(int l, const char* s) { return "backbone.mlps." + std::to_string(
 std::string ck(int i, const char* s) { return "audio_encoder.feat_extractor." + std::to_string(kKey[i]) + "." + s; }
 
 // Batch inputs: host arrays are copied in; device tensors are read in place (the call is synchronous, the caller's tensors outlive it,
-// and no kernel writes them) -- ten device-to-device copies per step otherwise, the 74 MB waveform among them.
-int ingest(ls_trainer* h, Buf& dst, const void* src, size_t bytes, bool on_device) {
-    if (on_device && bytes && ((uintptr_t)src & 15) == 0) { dst.alias(src); return LS_OK; }       // (an unaligned view is copied)
-    HIPCHK(h, dst.ensure(bytes ? bytes : 4));
-    if (bytes) HIPCHK(h, hipMemcpyAsync(dst.p, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+// and no kernel writes them) -- ten device-to-device copies per step otherwise, the 74 MB waveform among them.  A host input points
+// the kernels back at the handle's own memory, so it never reads the device tensor of an earlier call.
+int ingest(ls_trainer* h, BatchIn& dst, const void* src, size_t bytes, bool on_device) {
+    if (on_device) { dst.p = src; return LS_OK; }
+    HIPCHK(h, dst.own.ensure(bytes ? bytes : 4));
+    dst.p = dst.own.p;
+    if (bytes) HIPCHK(h, hipMemcpyAsync(dst.own.p, src, bytes, hipMemcpyHostToDevice, h->stream));
     return LS_OK;
 }
+
+// the side branch borrows the names of the main branch's workspaces for its launches
+void swap_bufs(DevBuf& a, DevBuf& b) { std::swap(a.p, b.p); std::swap(a.bytes, b.bytes); }
 
 int splits_for(int M, int N, int K) {
     const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
@@ -189,10 +163,10 @@ int ensure_batch(ls_trainer* h, int B) {
     const TrainDims& d0 = h->d;
     const size_t R = (size_t)B * d0.S, nx = (size_t)B * d0.JF * d0.T;
     const int* L = h->convL;
-    auto E = [&](Buf& b, size_t floats) { return b.ensure(floats * sizeof(float)); };
-    HIPCHK(h, E(h->x_start, nx)); HIPCHK(h, E(h->noise, nx)); HIPCHK(h, E(h->origin_x, nx)); HIPCHK(h, E(h->x_t, nx));
-    HIPCHK(h, E(h->drop, B)); HIPCHK(h, E(h->eps, (size_t)B * kD)); HIPCHK(h, E(h->audio, (size_t)B * L[0]));
-    HIPCHK(h, h->vid.ensure((size_t)B * 8)); HIPCHK(h, h->emo.ensure((size_t)B * d0.T * 8)); HIPCHK(h, h->tidx.ensure((size_t)B * 8));
+    auto E = [&](DevBuf& b, size_t floats) { return b.ensure(floats * sizeof(float)); };
+    HIPCHK(h, E(h->x_start.own, nx)); HIPCHK(h, E(h->noise.own, nx)); HIPCHK(h, E(h->origin_x.own, nx)); HIPCHK(h, E(h->x_t, nx));
+    HIPCHK(h, E(h->drop.own, B)); HIPCHK(h, E(h->eps.own, (size_t)B * kD)); HIPCHK(h, E(h->audio.own, (size_t)B * L[0]));
+    HIPCHK(h, h->vid.own.ensure((size_t)B * 8)); HIPCHK(h, h->emo.own.ensure((size_t)B * d0.T * 8)); HIPCHK(h, h->tidx.ensure((size_t)B * 8));
     HIPCHK(h, E(h->ca, B)); HIPCHK(h, E(h->cb, B));
     for (int i = 0; i < 4; ++i) HIPCHK(h, E(h->c[i], (size_t)B * kCout[i] * L[i + 1]));
     // (dc[0], the gradient of conv1's output, is never materialised: its only consumer, conv1's weight gradient, is folded into the
@@ -201,11 +175,11 @@ int ensure_batch(ls_trainer* h, int B) {
     HIPCHK(h, E(h->wmom, (size_t)B * wav_moment_parts(L[1]) * 256));
     HIPCHK(h, E(h->feat, (size_t)B * d0.T * d0.KFP)); HIPCHK(h, E(h->wpad, (size_t)kD * d0.KFP)); HIPCHK(h, E(h->waT, (size_t)kAud * kD));
     HIPCHK(h, E(h->zc, (size_t)B * kSpk)); HIPCHK(h, E(h->dzc, (size_t)B * kSpk));
-    for (Buf* b : {&h->mu, &h->lv, &h->pe_rows, &h->pre1, &h->hid, &h->emb, &h->demb, &h->dmu, &h->dlv, &h->dhid}) HIPCHK(h, E(*b, (size_t)B * kD));
-    for (Buf* b : {&h->xcur, &h->G}) HIPCHK(h, E(*b, R * kD));
-    for (Buf* b : {&h->X1, &h->A1, &h->X2, &h->A2, &h->dA2, &h->dA1}) HIPCHK(h, E(*b, (size_t)d0.L * R * kD));
+    for (DevBuf* b : {&h->mu, &h->lv, &h->pe_rows, &h->pre1, &h->hid, &h->emb, &h->demb, &h->dmu, &h->dlv, &h->dhid}) HIPCHK(h, E(*b, (size_t)B * kD));
+    for (DevBuf* b : {&h->xcur, &h->G}) HIPCHK(h, E(*b, R * kD));
+    for (DevBuf* b : {&h->X1, &h->A1, &h->X2, &h->A2, &h->dA2, &h->dA1}) HIPCHK(h, E(*b, (size_t)d0.L * R * kD));
     HIPCHK(h, E(h->colpart, (size_t)((B + 1) / 2) * d0.L * 5 * kD)); HIPCHK(h, E(h->dembp, (size_t)d0.L * B * kD));
-    for (Buf* b : {&h->S1, &h->S2}) HIPCHK(h, E(*b, (size_t)d0.L * R * 2));
+    for (DevBuf* b : {&h->S1, &h->S2}) HIPCHK(h, E(*b, (size_t)d0.L * R * 2));
     HIPCHK(h, E(h->out, (size_t)B * d0.T * d0.JF)); HIPCHK(h, E(h->dout, (size_t)B * d0.T * d0.JF));
     HIPCHK(h, E(h->lossp, 2 * ((size_t)B * d0.JF / 256 + 2))); HIPCHK(h, E(h->kldp, B)); HIPCHK(h, E(h->terms, 8));
     HIPCHK(h, E(h->part, (size_t)kNW * 2 * kD + (size_t)B * 128 + 4096 * 512 + (size_t)B * 32 * 2 * 2 * ((L[1] + 5) / 6 / 64 + 1)));
@@ -233,8 +207,8 @@ int ensure_batch(ls_trainer* h, int B) {
 }
 
 // layer l of a saved-activation family [L][R][512] / statistics [L][R][2]
-static inline float* lay(const Buf& b, int l, int R) { return b.f() + (size_t)l * R * kD; }
-static inline float* lay2(const Buf& b, int l, int R) { return b.f() + (size_t)l * R * 2; }
+static inline float* lay(const DevBuf& b, int l, int R) { return b.f() + (size_t)l * R * kD; }
+static inline float* lay2(const DevBuf& b, int l, int R) { return b.f() + (size_t)l * R * 2; }
 
 // locals shared by the stages of one step
 #define TRAIN_LOCALS(h, d)                                                                                   \
@@ -259,7 +233,7 @@ static int train_forward(ls_trainer* h, const TrainDims& d) {
     TRAIN_LOCALS(h, d);
     // WavEncoder (audio_enc.py:9-25): raw conv outputs + InstanceNorm statistics are kept for the backward
     // (the column buffer is free during the forward: it serves as the statistics-partials workspace)
-    HIPCHK(h, launch_conv1_fwd(h->audio_in, P(h, ck(0, "weight")), P(h, ck(0, "bias")), h->c[0].f(), h->st[0].f(), h->col.f(), B, L[0], L[1],
+    HIPCHK(h, launch_conv1_fwd(h->audio.f(), P(h, ck(0, "weight")), P(h, ck(0, "bias")), h->c[0].f(), h->st[0].f(), h->col.f(), B, L[0], L[1],
                                kPad[0], st));
     {   // the stride-6 layers' operand images (forward / weight gradient and data gradient), rebuilt from the master weights: one launch
         const float* w3[3] = {P(h, ck(1, "weight")), P(h, ck(2, "weight")), P(h, ck(3, "weight"))};
@@ -271,7 +245,7 @@ static int train_forward(ls_trainer* h, const TrainDims& d) {
         HIPCHK(h, launch_conv1d_mfma(h->c[i - 1].f(), h->st[i - 1].f(), h->img[i].f(), P(h, ck(i, "bias")), h->c[i].f(), i < 3 ? h->st[i].f() : nullptr,
                                      h->col.f(), B, kCin[i], kCout[i], L[i], L[i + 1], st));
     }
-    HIPCHK(h, launch_build_feat_train(h->in_x, h->in_noise, h->in_origin, h->c[3].f(), h->in_drop, h->hostpack.f(), h->hostpack.f() + B, h->feat.f(),
+    HIPCHK(h, launch_build_feat_train(h->x_start.f(), h->noise.f(), h->origin_x.f(), h->c[3].f(), h->drop.f(), h->hostpack.f(), h->hostpack.f() + B, h->feat.f(),
                                       h->x_t.f(), d, h->cfg.model.n_pre_seq, st));
     {   // input_mapping (RAG.py:114) -> frame rows of the token sequence
         // operands with 16-byte-aligned rows and a reduction length of whole K tiles (the master weight's rows are 311 floats: that product
@@ -283,7 +257,7 @@ static int train_forward(ls_trainer* h, const TrainDims& d) {
         a.bias = P(h, "input_mapping.bias");
         HIPCHK(h, gemm_run(h, a, true, true));
     }
-    HIPCHK(h, launch_gather_rows(P(h, "speaker_embedding.weight"), h->in_vid, h->zc.f(), B, kSpk,
+    HIPCHK(h, launch_gather_rows(P(h, "speaker_embedding.weight"), h->vid.i64(), h->zc.f(), B, kSpk,
                                  h->cfg.model.n_speakers, st));
     for (int k = 0; k < 2; ++k) {
         GemmArgs a = gemm(op_rows(h->zc.f(), kSpk, B, kSpk), op_rows(P(h, k ? "speaker_logvar.weight" : "speaker_mu.weight"), kSpk, kD, kSpk),
@@ -291,8 +265,8 @@ static int train_forward(ls_trainer* h, const TrainDims& d) {
         a.bias = P(h, k ? "speaker_logvar.bias" : "speaker_mu.bias");
         HIPCHK(h, gemm_run(h, a, true, true));
     }
-    HIPCHK(h, launch_style_fwd(h->mu.f(), h->lv.f(), h->in_eps, d.NPRE == 2 ? P(h, "emotion_embedding.weight") : nullptr,
-                               h->in_emo, T, h->xcur.f(), h->kldp.f(), B, S, d.NPRE, st));
+    HIPCHK(h, launch_style_fwd(h->mu.f(), h->lv.f(), h->eps.f(), d.NPRE == 2 ? P(h, "emotion_embedding.weight") : nullptr,
+                               h->emo.i64(), T, h->xcur.f(), h->kldp.f(), B, S, d.NPRE, st));
     // TimestepEmbedder (mlp_module.py:123-136)
     HIPCHK(h, launch_gather_rows(h->pe.f(), reinterpret_cast<const int64_t*>(h->hostpack.f() + 2 * B), h->pe_rows.f(), B, kD, kPeRows, st));
     {
@@ -327,7 +301,7 @@ static int train_forward(ls_trainer* h, const TrainDims& d) {
         HIPCHK(h, gemm_run(h, a, true, true));
     }
     const int nlb = (B * JF + 255) / 256;
-    HIPCHK(h, launch_loss(h->out.f(), h->in_x, h->dout.f(), h->lossp.f(), d, h->cfg.lambda_vel, st));
+    HIPCHK(h, launch_loss(h->out.f(), h->x_start.f(), h->dout.f(), h->lossp.f(), d, h->cfg.lambda_vel, st));
     HIPCHK(h, launch_finish_terms(h->lossp.f(), nlb, h->kldp.f(), B, h->terms.f(), d, h->cfg.lambda_vel, h->cfg.kld_weight, st));
     return LS_OK;
 }
@@ -392,7 +366,7 @@ static int train_backward_mixer_params(ls_trainer* h, const TrainDims& d, float*
 static int train_backward_inputs(ls_trainer* h, const TrainDims& d, float* grad) {
     TRAIN_LOCALS(h, d);
     // G = d loss / d [style | (emotion) | input_mapping rows]
-    HIPCHK(h, launch_style_bwd(h->G.f(), h->mu.f(), h->lv.f(), h->in_eps, h->dmu.f(), h->dlv.f(), B, S, h->cfg.kld_weight, st));
+    HIPCHK(h, launch_style_bwd(h->G.f(), h->mu.f(), h->lv.f(), h->eps.f(), h->dmu.f(), h->dlv.f(), B, S, h->cfg.kld_weight, st));
     for (int k = 0; k < 2; ++k) {
         const float* dz = k ? h->dlv.f() : h->dmu.f();
         const char* wk = k ? "speaker_logvar.weight" : "speaker_mu.weight";
@@ -402,9 +376,9 @@ static int train_backward_inputs(ls_trainer* h, const TrainDims& d, float* grad)
         a.accumulate = k;
         HIPCHK(h, gemm_run(h, a, true, false));
     }
-    HIPCHK(h, launch_scatter_rows(h->dzc.f(), kSpk, h->in_vid, 1, B, kSpk, Gr(h, grad, "speaker_embedding.weight"), st));
+    HIPCHK(h, launch_scatter_rows(h->dzc.f(), kSpk, h->vid.i64(), 1, B, kSpk, Gr(h, grad, "speaker_embedding.weight"), st));
     if (d.NPRE == 2)
-        HIPCHK(h, launch_scatter_rows(h->G.f() + kD, (long long)S * kD, h->in_emo, T, B, kD,
+        HIPCHK(h, launch_scatter_rows(h->G.f() + kD, (long long)S * kD, h->emo.i64(), T, B, kD,
                                       Gr(h, grad, "emotion_embedding.weight"), st));
     // input_mapping
     const float* dH = h->G.f() + (size_t)d.NPRE * kD;
@@ -415,7 +389,7 @@ static int train_backward_inputs(ls_trainer* h, const TrainDims& d, float* grad)
         GemmArgs a = gemm(gemm_operand(dH, T, (long long)S * kD, kD, INT_MAX, 0, 1, true, BT, kD),
                           op_rows(h->waT.f(), kD, kAud, kD), h->dAf.f(), kAud, BT, kAud, kD);
         HIPCHK(h, gemm_run(h, a, true, true));
-        HIPCHK(h, launch_scale_rows(h->dAf.f(), h->in_drop, B, T * kAud, st));
+        HIPCHK(h, launch_scale_rows(h->dAf.f(), h->drop.f(), B, T * kAud, st));
     }
     return LS_OK;
 }
@@ -473,9 +447,9 @@ static int train_backward_audio(ls_trainer* h, const TrainDims& d, float* grad) 
             // gradient tensor itself is never written (k_conv_dgrad<FUSE1>); per-sample results are summed over the batch in index order
             float* outp = nullptr;
             // (on a side stream under the forward's first convs this latency-bound 50 us kernel cost the forward 200 us: measured, not kept)
-            HIPCHK(h, launch_wav_moments(h->audio_in, h->wmom.f(), B, L[0], L[1], kPad[0], st));
+            HIPCHK(h, launch_wav_moments(h->audio.f(), h->wmom.f(), B, L[0], L[1], kPad[0], st));
             HIPCHK(h, launch_conv_dgrad_conv1(h->dc[i].f(), (long long)C * Lo, Lo, 1, h->dimg[i].f(), h->c[0].f(), h->st[0].f(), part, B, C, L[1], Lo,
-                                              h->audio_in, L[0], kPad[0], h->wmom.f(), P(h, ck(0, "weight")), P(h, ck(0, "bias")), h->col.f(), &outp, st));
+                                              h->audio.f(), L[0], kPad[0], h->wmom.f(), P(h, ck(0, "weight")), P(h, ck(0, "bias")), h->col.f(), &outp, st));
             HIPCHK(h, launch_partial_reduce(outp, B, 480, 480, Gr(h, grad, ck(0, "weight")), 0, st));
         }
     }
@@ -487,15 +461,15 @@ static int train_backward_audio(ls_trainer* h, const TrainDims& d, float* grad) 
 extern "C" {
 
 int ls_train_create(const ls_train_config* cfg, ls_trainer** out) {
-    if (!cfg || !out) return fail(nullptr, LS_EINVAL, "ls_train_create: null argument");
+    if (!cfg || !out) return fail<ls_trainer>(nullptr, LS_EINVAL, "ls_train_create: null argument");
     const ls_config& m = cfg->model;
     if (m.latent_dim != kD || m.nframes != 34 || m.layers < 1 || m.layers > 16 || (m.n_prefix_tokens != 1 && m.n_prefix_tokens != 2) ||
         (m.n_prefix_tokens == 2 && m.n_emotions <= 0) || m.njoints <= 0 || m.nfeats <= 0 || m.n_speakers <= 0 || cfg->diffusion_steps <= 0)
-        return fail(nullptr, LS_EUNSUPPORTED, "ls_train_create: unsupported configuration");
+        return fail<ls_trainer>(nullptr, LS_EUNSUPPORTED, "ls_train_create: unsupported configuration");
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return fail(nullptr, LS_EHIP, "ls_train_create: no HIP device (the training step has no CPU path)");
-    if (m.device < 0 || m.device >= n) return fail(nullptr, LS_EINVAL, "ls_train_create: device %d out of range", m.device);
+        return fail<ls_trainer>(nullptr, LS_EHIP, "ls_train_create: no HIP device (the training step has no CPU path)");
+    if (m.device < 0 || m.device >= n) return fail<ls_trainer>(nullptr, LS_EINVAL, "ls_train_create: device %d out of range", m.device);
     ls_trainer* h = new ls_trainer();
     h->cfg = *cfg;
     TrainDims& d = h->d;
@@ -503,7 +477,7 @@ int ls_train_create(const ls_train_config* cfg, ls_trainer** out) {
     d.KF = 2 * d.JF + 1 + kAud; d.KFP = (d.KF + 31) / 32 * 32; d.D = kD; d.L = m.layers;      // KFP: whole 32-deep K tiles (the input_mapping product takes the GEMM's LDS-DMA path)
     h->convL[0] = m.audio_len;
     for (int i = 0; i < 4; ++i) h->convL[i + 1] = (h->convL[i] + 2 * kPad[i] - 15) / kStride[i] + 1;
-    if (h->convL[4] != d.T) { delete h; return fail(nullptr, LS_EINVAL, "ls_train_create: audio_len %d gives %d audio frames, need %d", m.audio_len, h->convL[4], d.T); }
+    if (h->convL[4] != d.T) return abandon(h, ls_train_destroy, fail<ls_trainer>(nullptr, LS_EINVAL, "ls_train_create: audio_len %d gives %d audio frames, need %d", m.audio_len, h->convL[4], d.T));
     for (int l = 0; l < d.L; ++l) {
         add_param(h, lk(l, "block1.0.alpha"), kD); add_param(h, lk(l, "block1.0.beta"), kD);
         add_param(h, lk(l, "block1.1.weight"), (int64_t)d.S * d.S); add_param(h, lk(l, "block1.1.bias"), d.S);
@@ -523,7 +497,7 @@ int ls_train_create(const ls_train_config* cfg, ls_trainer** out) {
     if (d.NPRE == 2) add_param(h, "emotion_embedding.weight", (int64_t)m.n_emotions * kD);
 
     auto bail = [&](const char* what, hipError_t e) {
-        fail(nullptr, LS_EHIP, "ls_train_create: %s: %s", what, hipGetErrorString(e));
+        fail<ls_trainer>(nullptr, LS_EHIP, "ls_train_create: %s: %s", what, hipGetErrorString(e));
         ls_train_destroy(h);
         return LS_EHIP;
     };
@@ -539,18 +513,12 @@ int ls_train_create(const ls_train_config* cfg, ls_trainer** out) {
         if ((e = hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, hi)) != hipSuccess) return bail("hipStreamCreateWithPriority", e);
     }
     for (auto& ev : h->evs) if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    for (Buf* b : {&h->P, &h->M, &h->V}) {
+    for (DevBuf* b : {&h->P, &h->M, &h->V}) {
         if ((e = b->ensure((size_t)h->flat * 4)) != hipSuccess) return bail("hipMalloc(params)", e);
         if ((e = hipMemsetAsync(b->p, 0, (size_t)h->flat * 4, h->stream)) != hipSuccess) return bail("hipMemset", e);
     }
     // PositionalEncoding.pe (mlp_module.py:104-116), a buffer, recomputed
-    std::vector<float> pe((size_t)kPeRows * kD);
-    for (int p = 0; p < kPeRows; ++p)
-        for (int i = 0; i < kD / 2; ++i) {
-            const float div = expf((float)(2 * i) * (-logf(10000.0f) / (float)kD));
-            pe[(size_t)p * kD + 2 * i] = sinf((float)p * div);
-            pe[(size_t)p * kD + 2 * i + 1] = cosf((float)p * div);
-        }
+    const std::vector<float> pe = pe_table(kPeRows, kD);
     if ((e = h->pe.ensure(pe.size() * 4)) != hipSuccess) return bail("hipMalloc(pe)", e);
     if ((e = hipMemcpy(h->pe.p, pe.data(), pe.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy(pe)", e);
     for (int i = 1; i < 4; ++i) {
@@ -561,7 +529,7 @@ int ls_train_create(const ls_train_config* cfg, ls_trainer** out) {
         const int MK = (2 * d.S + 3) / 4;
         const size_t nimg[8] = {(size_t)d.L * kD * kD, (size_t)d.L * kD, (size_t)d.L * 5 * MK * 64, (size_t)d.L * 80,
                                 (size_t)d.L * kD, (size_t)d.L * kD, (size_t)d.L * kD, (size_t)d.L * kD};
-        Buf* ib[8] = {&h->twch, &h->tbch, &h->tww, &h->tbtok, &h->tl1a, &h->tl1b, &h->tl2a, &h->tl2b};
+        DevBuf* ib[8] = {&h->twch, &h->tbch, &h->tww, &h->tbtok, &h->tl1a, &h->tl1b, &h->tl2a, &h->tl2b};
         for (int i = 0; i < 8; ++i)
             if ((e = ib[i]->ensure(nimg[i] * 4)) != hipSuccess) return bail("hipMalloc(train images)", e);
         DevWeights dw{};
@@ -592,24 +560,14 @@ void ls_train_destroy(ls_trainer* h) {
     if (!h) return;
     (void)hipSetDevice(h->cfg.model.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    std::vector<Buf*> all = {&h->P, &h->M, &h->V, &h->pe, &h->x_start, &h->noise, &h->drop, &h->eps, &h->audio, &h->origin_x, &h->vid, &h->emo, &h->hostpack, &h->wpad, &h->waT,
-                             &h->ca, &h->cb, &h->tidx, &h->feat, &h->x_t, &h->zc, &h->mu, &h->lv, &h->pe_rows, &h->pre1, &h->hid, &h->emb, &h->xcur,
-                             &h->out, &h->dout, &h->lossp, &h->kldp, &h->terms, &h->G, &h->part, &h->pw, &h->pb, &h->demb, &h->dmu,
-                             &h->dlv, &h->dzc, &h->dhid, &h->dAf, &h->dAt, &h->col, &h->wmom, &h->ws, &h->part2, &h->ws2};
-    for (int i = 0; i < 4; ++i) { all.push_back(&h->c[i]); all.push_back(&h->img[i]); all.push_back(&h->dimg[i]); }
-    for (int i = 0; i < 3; ++i) { all.push_back(&h->st[i]); all.push_back(&h->dc[i]); }
-    for (Buf* b : {&h->X1, &h->A1, &h->X2, &h->A2, &h->S1, &h->S2, &h->twch, &h->tbch, &h->tww, &h->tbtok, &h->tl1a, &h->tl1b, &h->tl2a,
-                   &h->tl2b, &h->tdevw, &h->twchT, &h->twwT, &h->dA2, &h->dA1, &h->colpart, &h->dembp})
-        all.push_back(b);
-    for (Buf* b : all) b->release();
     for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : h->evs) if (ev) (void)hipEventDestroy(ev);
     if (h->side) (void)hipStreamDestroy(h->side);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;              // every DevBuf frees its memory
 }
 
-const char* ls_train_last_error(const ls_trainer* h) { return h ? h->err.c_str() : g_train_create_error.c_str(); }
+const char* ls_train_last_error(const ls_trainer* h) { return last_error(h); }
 
 int ls_train_set_schedule(ls_trainer* h, const double* sac, const double* s1mac, const int64_t* tmap) {
     if (!h || !sac || !s1mac || !tmap) return fail(h, LS_EINVAL, "ls_train_set_schedule: null argument");
@@ -709,22 +667,16 @@ int ls_train_forward_backward(ls_trainer* h, const ls_train_batch* tb, float* gr
         if (t < 0 || t >= h->cfg.diffusion_steps) return fail(h, LS_EINVAL, "ls_train_forward_backward: t[%d] = %lld out of range", b, (long long)t);
         pack[b] = (float)h->sac[t]; pack[B + b] = (float)h->s1mac[t]; tm[b] = h->tmap[t];
     }
-    if ((rc = ingest(h, h->hostpack, pack.data(), (size_t)16 * B, false))) return rc;
+    HIPCHK(h, h->hostpack.ensure((size_t)16 * B));
+    HIPCHK(h, hipMemcpyAsync(h->hostpack.p, pack.data(), (size_t)16 * B, hipMemcpyHostToDevice, st));
     // device-resident batch tensors are read in place (rounds 1-2 copied each into the handle: nine 4 us copies in front of every step)
-    auto in_place = [&](Buf& own, const void* src, size_t bytes, const void** out) -> int {
-        if (od) { *out = src; return LS_OK; }
-        int r = ingest(h, own, src, bytes, false);
-        *out = own.p;
-        return r;
-    };
-    if ((rc = in_place(h->x_start, tb->x_start, nx, (const void**)&h->in_x)) || (rc = in_place(h->noise, tb->noise, nx, (const void**)&h->in_noise)) ||
-        (rc = in_place(h->origin_x, tb->origin_x, nx, (const void**)&h->in_origin)) || (rc = in_place(h->drop, tb->drop, B * 4, (const void**)&h->in_drop)) ||
-        (rc = in_place(h->eps, tb->eps, (size_t)B * kD * 4, (const void**)&h->in_eps)) ||
-        (rc = in_place(h->audio, tb->audio_input, (size_t)B * L[0] * 4, (const void**)&h->audio_in)) ||
-        (rc = in_place(h->vid, tb->vid_indices, B * 8, (const void**)&h->in_vid)))
+    if ((rc = ingest(h, h->x_start, tb->x_start, nx, od)) || (rc = ingest(h, h->noise, tb->noise, nx, od)) ||
+        (rc = ingest(h, h->origin_x, tb->origin_x, nx, od)) || (rc = ingest(h, h->drop, tb->drop, B * 4, od)) ||
+        (rc = ingest(h, h->eps, tb->eps, (size_t)B * kD * 4, od)) || (rc = ingest(h, h->audio, tb->audio_input, (size_t)B * L[0] * 4, od)) ||
+        (rc = ingest(h, h->vid, tb->vid_indices, B * 8, od)))
         return rc;
-    h->in_emo = nullptr;
-    if (d.NPRE == 2 && (rc = in_place(h->emo, tb->emo, (size_t)B * T * 8, (const void**)&h->in_emo))) return rc;
+    h->emo.p = nullptr;
+    if (d.NPRE == 2 && (rc = ingest(h, h->emo, tb->emo, (size_t)B * T * 8, od))) return rc;
     HIPCHK(h, hipStreamSynchronize(st));      // host staging vectors go out of scope below
     HIPCHK(h, hipEventRecord(h->ev[0], st));
     HIPCHK(h, hipMemsetAsync(grad, 0, (size_t)h->flat * 4, st));
@@ -736,10 +688,10 @@ int ls_train_forward_backward(ls_trainer* h, const ls_train_batch* tb, float* gr
         HIPCHK(h, hipEventRecord(h->evs[0], st));
         HIPCHK(h, hipStreamWaitEvent(h->side, h->evs[0], 0));
         {   // the helpers launch on h->stream with h->ws / h->part: the side branch borrows the names for its launches
-            std::swap(h->stream, h->side); std::swap(h->ws, h->ws2); std::swap(h->part, h->part2);
+            std::swap(h->stream, h->side); swap_bufs(h->ws, h->ws2); swap_bufs(h->part, h->part2);
             rc = train_backward_mixer_params(h, d, grad);
             if (rc == LS_OK) rc = train_backward_temb(h, d, grad);
-            std::swap(h->stream, h->side); std::swap(h->ws, h->ws2); std::swap(h->part, h->part2);
+            std::swap(h->stream, h->side); swap_bufs(h->ws, h->ws2); swap_bufs(h->part, h->part2);
             if (rc != LS_OK) return rc;
         }
         HIPCHK(h, hipEventRecord(h->evs[1], h->side));

@@ -50,6 +50,26 @@ def test_hip_pose_encoder_matches_fixture_ted_and_beat():
 
 
 @pytest.mark.gpu
+def test_features_do_not_depend_on_earlier_batch_sizes():
+    """The handle's buffers only grow: B = 3, then 5, then 2 on one engine, each equal to a fresh engine's result, bit for bit."""
+    from livelyspeaker_amd import _lib
+    sd = synth.make_embedding_net_state_dict(27, 32)
+    gen, _ = synth.make_pose_sets(5)
+
+    def engine():
+        eng = _lib.EvalEngine(27, 34, 32, (256, 128))
+        eng.load_state_dict(sd)
+        return eng
+
+    eng = engine()
+    for B in (3, 5, 2):
+        fresh = engine()
+        assert np.array_equal(eng.features(gen[:B]), fresh.features(gen[:B])), B
+        fresh.close()
+    eng.close()
+
+
+@pytest.mark.gpu
 def test_embedding_space_evaluator_dropin_reproduces_reference_scores():
     import torch
     from livelyspeaker_amd.ted_evaluator import EmbeddingSpaceEvaluator

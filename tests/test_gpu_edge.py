@@ -299,3 +299,28 @@ def test_emo_accepts_the_callers_frame_tensor_and_a_bare_id_vector():
         assert not np.array_equal(a, eng.sample(**kw))                                    # the token really depends on it
     finally:
         eng.close()
+
+
+def _wrappers():
+    """(constructor, state dict) of the five handle wrappers at TED shapes"""
+    from livelyspeaker_amd import _lib
+    cfg = synth.TED
+    return [(lambda: _lib.Engine(cfg.njoints, cfg.nfeats, cfg.n_prefix_tokens, cfg.audio_len), synth.make_state_dict(cfg)),
+            (lambda: _lib.SagEngine(), synth.make_sag_state_dict()),
+            (lambda: _lib.SagEncoderEngine(), synth.make_sag_encoder_state_dict(cfg)),
+            (lambda: _lib.Trainer(cfg.njoints, cfg.nfeats, cfg.n_prefix_tokens, cfg.audio_len), synth.make_state_dict(cfg)),
+            (lambda: _lib.EvalEngine(27, 34, 32, (256, 128)), synth.make_embedding_net_state_dict(27, 32))]
+
+
+def test_handle_lifecycle_of_every_wrapper():
+    """close() twice, and a loaded handle dropped without a run: every buffer goes with the handle, nothing raises."""
+    import gc
+    for make, sd in _wrappers():
+        eng = make()
+        eng.close()
+        eng.close()
+        assert not eng.h.value
+        eng = make()
+        eng.load_state_dict(sd)
+        del eng
+        gc.collect()

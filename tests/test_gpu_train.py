@@ -331,6 +331,30 @@ def test_batch_size_may_change_between_steps():
     assert torch.equal(a, fresh.grad)
 
 
+def test_device_and_host_inputs_alternate_on_one_trainer():
+    """Device tensors are read in place, host arrays through the handle's copies: a host-input call after a device-input call must read
+    its copy (not the earlier call's tensors), and the next device-input call the caller's tensors again -- same values, same bits."""
+    import torch
+    cfg, sd, tr = make("ted")
+    x_start, y, noise, drop, eps = synth.make_train_batch(cfg, 2, 5)
+    t = np.array([11, 640])
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    runs = []
+    for on_device in (True, False, True):
+        if on_device:       # fresh tensors every time: the first call's are gone (and poisoned) before the host-input call runs
+            args = [dev(x_start), t, dev(noise), {k: dev(v) for k, v in y.items()}, dev(drop), dev(eps)]
+        else:
+            args = [x_start, t, noise, y, drop, eps]
+        terms = tr.forward_backward(*args)
+        runs.append(([terms[k] for k in ("rot_mse", "vel_mse", "kld", "loss", "total")], tr.grad.clone()))
+        if on_device:
+            for a in [args[0], args[2], args[4], args[5]] + list(args[3].values()):
+                a.fill_(3) if a.dtype == torch.float32 else a.zero_()
+    assert np.isfinite(runs[0][0]).all() and float(runs[0][1].abs().max()) > 0
+    for terms, grad in runs[1:]:
+        assert terms == runs[0][0] and torch.equal(grad, runs[0][1])
+
+
 def test_trainloop_beat_variant_runs_and_matches_oracle_loss():
     """BEAT (47x6 pose features, style + emotion prefix tokens) through the TrainLoop drop-in: first-step loss vs the oracle."""
     import torch

@@ -160,6 +160,45 @@ def test_no_gpu_fails_loudly_not_silently():
     assert lib.ls_create(ctypes.byref(bad), ctypes.byref(h)) == -1
 
 
+def _create_calls(latent_dim=512):
+    """(prefix, config) of the five *_create entries; latent_dim = 256 (pose_dim = 0 for ls_eval) is refused before any device call."""
+    model = _lib.LsConfig(9, 3, 34, 1, 4, latent_dim, 8, 36267, 1400, 0, 0, 0)
+    sag = _lib.LsSagConfig(9, 3, 34, latent_dim, 1024, 3, 4, 4, 0, 0)
+    return [("ls_", model), ("ls_sag_", sag), ("ls_sag_enc_", sag), ("ls_train_", _lib.LsTrainConfig(model, 1.0, 0.01, 1000, 0)),
+            ("ls_eval_", _lib.LsEvalConfig(27 if latent_dim == 512 else 0, 34, 32, 256, 128, 0))]
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
+def test_every_create_fails_cleanly_without_a_device():
+    """A valid configuration on a machine without a device: non-zero, no handle, a message -- and whatever the create had made
+    by then went through the handle's own destroy."""
+    lib = _lib.load_library()
+    for prefix, cfg in _create_calls():
+        h = ctypes.c_void_p()
+        rc = getattr(lib, prefix + "create")(ctypes.byref(cfg), ctypes.byref(h))
+        assert rc != 0 and not h.value, (prefix, rc, h.value)
+        assert getattr(lib, prefix + "last_error")(None), prefix
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
+def test_create_errors_are_per_thread():
+    """The message of a failed create belongs to the thread that made the call: another thread reads its own (empty) one."""
+    import threading
+    lib = _lib.load_library()
+    for prefix, cfg in _create_calls(latent_dim=256):
+        last_error = getattr(lib, prefix + "last_error")
+        h = ctypes.c_void_p()
+        assert getattr(lib, prefix + "create")(ctypes.byref(cfg), ctypes.byref(h)) != 0
+        mine = last_error(None)
+        assert mine, prefix
+        seen = []
+        t = threading.Thread(target=lambda: seen.append(last_error(None)))
+        t.start()
+        t.join()
+        assert seen == [b""], (prefix, seen)
+        assert last_error(None) == mine, prefix
+
+
 class _FakeEngine:
     """Records what the sampler hands to the engine; stands in for libls_hip.so in RNG-order tests."""
     J, F, T, D, batch, n_steps = 9, 3, 34, 512, 2, 0

@@ -65,6 +65,26 @@ def test_hip_decoder_vs_golden_and_oracle(g6):
         eng.close()
 
 
+@pytest.mark.gpu
+def test_decode_batch_history_and_async_timing():
+    """B = 2, then 5, then 2 on one engine: the buffers grow and are reused, the first and last results are the same bits; an enqueued
+    decode (wait=False) reports its span once asked for."""
+    import torch
+    from livelyspeaker_amd import _lib
+    x, z = _inputs(5)
+    eng = _lib.SagEngine()
+    try:
+        eng.load_state_dict(synth.make_sag_state_dict())
+        first = eng.decode(x[:2], z[:2])
+        eng.decode(x, z)
+        assert np.array_equal(eng.decode(x[:2], z[:2]), first) and np.abs(first).max() > 0
+        out = eng.decode(torch.from_numpy(x[:2]).cuda(), torch.from_numpy(z[:2]).cuda(), wait=False)
+        assert eng.last_decode_ms() > 0.0            # waits for the enqueued decode
+        assert np.array_equal(out.cpu().numpy(), first)
+    finally:
+        eng.close()
+
+
 # ---- BEAT twin (scripts_beat/model/motionclip_module.py:98-183: 47 joints x 6 features, mapping = Linear(283, 512)) ----
 @pytest.fixture(scope="module")
 def g6_beat():

@@ -252,6 +252,24 @@ def test_motionclip_forward(ds):
 
 
 @pytest.mark.gpu
+def test_encode_batch_history_and_async_timing():
+    """B = 2, then 5, then 2 on one engine: the buffers grow and are reused, the first and last results are the same bits; an enqueued
+    encode (wait=False) reports its span once asked for."""
+    import torch
+    x = _x(synth.TED, 5)
+    eng = _engine(synth.TED)
+    try:
+        first = eng.encode(x[:2])
+        eng.encode(x)
+        assert np.array_equal(eng.encode(x[:2]), first) and np.abs(first).max() > 0
+        mu = eng.encode(torch.from_numpy(x[:2]).cuda(), wait=False)
+        assert eng.last_encode_ms() > 0.0            # waits for the enqueued encode
+        assert np.array_equal(mu.cpu().numpy(), first)
+    finally:
+        eng.close()
+
+
+@pytest.mark.gpu
 def test_error_paths_reach_no_kernel():
     from livelyspeaker_amd import _lib
     cfg = synth.TED
