@@ -510,6 +510,54 @@ int ls_ted_post(int device, int on_device, int batch, const ls_post_config* c, c
  * Gram-Schmidt on the two 3-vectors, then (atan2(-m12, m22), asin(m02), atan2(-m01, m00))).  Either output may be NULL. */
 int ls_beat_post(int device, int on_device, int batch, int njoints, const float* sample, float* decoded, float* euler_deg);
 
+/* The BEAT evaluation metrics of a batch (scripts_beat/utils/metric.py: SRGR.run :27-51, alignment.load_pose :76-98, GAHR and
+ * calculate_align :162-193) on the Euler planes [B,34,J*3] in degrees that ls_beat_post writes; one workgroup per clip, every
+ * per-clip sum a fixed tree, so a clip's numbers do not depend on the batch it travels in.
+ *   success[B,34,J]   1 where sum_k |pred - target| < threshold
+ *   srgr_sum[B]       sum over (frame, joint) of success * semantic[frame] * scale (semantic NULL: weight 1); the caller divides by
+ *                     34 * J * B for SRGR.run's rate
+ *   vel[B,6,33]       per series s, the norm of the frame-to-frame difference of the three angles of joint series_joint[s] (raw
+ *                     degrees, no wrapping)
+ *   beat_mask[B,6,33] strict local minima of vel as scipy.signal.argrelextrema(x, np.less, order) finds them in its default
+ *                     mode='clip': x[i] < x[clip(i - k)] and x[i] < x[clip(i + k)] for k = 1..order (the end frames never are)
+ *   align[B]          mean over the clip's onsets of exp(-min_m (onset - m / fps)^2 / (2 sigma^2)), m over the beats of series
+ *                     align_series; 0 for a clip without a motion beat
+ * pred is required; target, semantic and every output may be NULL (success and srgr_sum need target, align needs the onsets).
+ * Tensor pointers are device pointers iff on_device; onset_offsets is read by the host in both modes.  LS_EINVAL without a launch:
+ * NULL pred, batch < 1, order < 1, a series joint outside [0, njoints), onset_offsets not starting at 0 or a clip without an onset
+ * when align is asked for. */
+typedef struct ls_beat_metrics_args {
+    int32_t batch;
+    int32_t njoints;              /* J: 47 on BEAT                                                               */
+    int32_t on_device;
+    int32_t order;                /* argrelextrema order: 2 (test_RAG_beat.py:43)                                */
+    int32_t align_series;         /* the series align reads: 2, the right wrist (metric.py:189)                  */
+    int32_t reserved;
+    int32_t series_joint[6];      /* right arm, right shoulder, right wrist, left arm, left shoulder, left wrist */
+    float threshold;              /* 4 (test_LivelySpeaker_beat.py: SRGR(4, 47))                                 */
+    float scale;                  /* 1 / 0.165 (metric.py:41)                                                    */
+    float sigma;                  /* 0.3                                                                         */
+    float fps;                    /* 15                                                                          */
+    const float* pred;            /* [B,34,J*3]                                                                  */
+    const float* target;          /* [B,34,J*3] or NULL                                                          */
+    const float* semantic;        /* [B,34] or NULL                                                              */
+    const float* onset_times;     /* flat, seconds; clip b owns [onset_offsets[b], onset_offsets[b+1])           */
+    const int64_t* onset_offsets; /* [B+1] HOST                                                                  */
+    unsigned char* success;
+    float* srgr_sum;
+    float* vel;
+    unsigned char* beat_mask;
+    float* align;
+} ls_beat_metrics_args;
+int ls_beat_metrics(int device, const ls_beat_metrics_args* a);
+
+/* L1div.run (metric.py:12-24): *sum_out = sum over rows and columns of |x - column mean| of x [rows, dim].  The column means are
+ * reduced in a fixed order and rounded to fp32 (np.mean of an fp32 array), |x - mean| is fp32, the total float64; x is only read
+ * (the reference overwrites it).  x is a device pointer iff on_device, sum_out a host pointer.
+ * The name spells "l1div" without its digit: exported names in this header are lower-case letters and underscores only, which
+ * is what the export check of the test suite collects them by. */
+int ls_beat_ldiv(int device, int on_device, int64_t rows, int dim, const float* x, double* sum_out);
+
 /* ---- training step ----------------------------------------------------------------
  * One optimisation step of the RAG denoiser as TrainLoop.run_step runs it (scripts/train_utils/train_loop.py:146-186):
  *   x_t = q_sample(x_start, t, noise)                                  gaussian_diffusion.py:1281-1282

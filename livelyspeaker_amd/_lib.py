@@ -93,6 +93,13 @@ class LsPostConfig(C.Structure):
                 ("mean_dir_vec", C.c_float * 48)]
 
 
+class LsBeatMetricsArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("batch", "njoints", "on_device", "order", "align_series", "reserved")] + [
+        ("series_joint", C.c_int32 * 6)] + [(n, C.c_float) for n in ("threshold", "scale", "sigma", "fps")] + [
+        (n, C.c_void_p) for n in ("pred", "target", "semantic", "onset_times", "onset_offsets", "success", "srgr_sum", "vel",
+                                  "beat_mask", "align")]
+
+
 class LsTiming(C.Structure):
     _fields_ = [("prepare_ms", C.c_float), ("loop_ms", C.c_float), ("total_ms", C.c_float),
                 ("n_step_launches", C.c_int32), ("graph_replayed", C.c_int32), ("single_pass", C.c_int32),
@@ -124,7 +131,7 @@ EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
-           "ls_sag_enc_encode", "ls_sag_enc_encode_async", "ls_sag_enc_last_encode_ms", "ls_sag_enc_stream", "ls_ted_post", "ls_beat_post",
+           "ls_sag_enc_encode", "ls_sag_enc_encode_async", "ls_sag_enc_last_encode_ms", "ls_sag_enc_stream", "ls_ted_post", "ls_beat_post", "ls_beat_metrics", "ls_beat_ldiv",
            "ls_train_create", "ls_train_destroy", "ls_train_last_error", "ls_train_set_schedule", "ls_train_param_count",
            "ls_train_flat_size", "ls_train_param_info", "ls_train_set_weight", "ls_train_get_weight", "ls_train_forward_backward",
            "ls_train_adamw", "ls_train_read", "ls_train_get_moment", "ls_train_set_moment", "ls_train_get_step", "ls_train_set_step",
@@ -245,6 +252,8 @@ def load_library(build_if_missing: bool = True):
     lib.ls_ted_post.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(LsPostConfig), C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]
     lib.ls_beat_post.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ls_beat_metrics.argtypes = [C.c_int, C.POINTER(LsBeatMetricsArgs)]
+    lib.ls_beat_ldiv.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, c_f64p]
     lib.ls_train_create.argtypes = [C.POINTER(LsTrainConfig), C.POINTER(C.c_void_p)]
     lib.ls_train_destroy.argtypes = [C.c_void_p]
     lib.ls_train_destroy.restype = None

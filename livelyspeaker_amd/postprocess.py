@@ -67,7 +67,8 @@ def beat_postprocess(sample, device: int = 0, want_euler: bool = True) -> dict:
     """BEAT caller plumbing (scripts_beat/test_RAG_beat.py:86, 101).  sample: [B, 47, 6, 34] (numpy, CPU tensor or CUDA tensor as
     returned by the sampler).  Returns decoded_motions [B, 34, 282] (the rot6d pose sequence the evaluator and the metrics
     consume) and pred_euler [B, 34, 141]: Euler XYZ angles in degrees of every joint (rot_utils.matrix_to_euler_angles(
-    rot_utils.rotation_6d_to_matrix(.), "XYZ") / pi * 180).  Audio onsets / the alignment score stay with the caller."""
+    rot_utils.rotation_6d_to_matrix(.), "XYZ") / pi * 180).  ``beat_metrics`` scores these planes (SRGR, motion beats, BeatAlign, L1
+    diversity); audio onsets stay with the caller."""
     lib = _lib.load_library()
     m = _lib._Marshal(device, sample)
     B, J = int(sample.shape[0]), int(sample.shape[1])
