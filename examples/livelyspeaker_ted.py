@@ -8,8 +8,12 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
 
     python examples/livelyspeaker_ted.py [batch]
     python examples/livelyspeaker_ted.py [batch] --from-motion
+    python examples/livelyspeaker_ted.py [batch] --long-seconds N
 --from-motion edits a RECORDED clip instead: no text feature is needed, the SAG encoder turns the clip into the CLIP-aligned latent
 (recorded clip -> SAG(batch) = MOTIONCLIP.forward -> init_image -> the same 20-step refinement).
+--long-seconds N synthesises N seconds of gesture for N seconds of speech in ONE call (livelyspeaker_amd.long_form.sample_long): the
+34-frame windows are chained on the device, each conditioned on the last four poses of the one before it, the SAG decoder's output for
+the window's text feature as its init_image, and stitched into one timeline.
 With real data: load RAG.pt / SAG.pth / the auto-encoder checkpoint with load_model_wo_clip / load_state_dict and build `cond`
 exactly as the reference script does; everything below the weight loading is unchanged.
 """
@@ -134,6 +138,11 @@ def main():
         i = sys.argv.index("--noise-source")
         noise_source = sys.argv[i + 1]
         del sys.argv[i:i + 2]
+    if "--long-seconds" in sys.argv:
+        i = sys.argv.index("--long-seconds")
+        seconds = float(sys.argv[i + 1])
+        del sys.argv[i:i + 2]
+        return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source)
     from_motion = "--from-motion" in sys.argv
     if from_motion:
         sys.argv.remove("--from-motion")
@@ -178,6 +187,32 @@ def main_from_motion(B, noise_source):
           f"{sag.encoder.engine().last_encode_ms():.3f} ms, decode {sag.decoder.engine().last_decode_ms():.3f} ms; "
           f"|mu| mean {float(batch['mu'].norm(dim=-1).mean()):.3f}")
     assert bool(torch.isfinite(sample).all()) and bool((decoded[1, :, :, 28:] == 0).all())
+
+
+def main_long(B, seconds, noise_source):
+    """`seconds` of 16 kHz speech per clip -> one stitched timeline at 15 fps (the LivelySpeaker chain, window after window on the device)."""
+    import numpy as np
+    from livelyspeaker_amd import long_form
+    cfg, model, diffusion, sag_decoder, _ = build()
+    diffusion.noise_source = noise_source
+    g = np.random.Generator(np.random.PCG64(synth.SEED_COND))
+    audio = torch.from_numpy(0.1 * g.standard_normal((B, max(1, int(round(seconds * 16000))))).astype(np.float32)).cuda()
+    W, _, n_frames = long_form.plan_windows(audio.shape[1], cfg)
+    y = {k: torch.from_numpy(v).cuda() for k, v in synth.make_long_cond(cfg, B, W, scale=2.5).items()}
+    text = torch.from_numpy(synth.make_text_features(B * W).reshape(B, W, 512)).cuda()          # one text feature per window
+    run = lambda: long_form.sample_long(diffusion, model, audio, y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim",      # noqa: E731
+                                        skip_timesteps=80, sag=sag_decoder, text_features=text)
+    torch.manual_seed(233)
+    run()                                                                                   # warm-up (graph capture, allocations)
+    torch.cuda.synchronize()
+    torch.manual_seed(233)
+    t0 = time.perf_counter()
+    timeline = run()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert timeline.shape == (B, 9, 3, n_frames) and bool(torch.isfinite(timeline).all())
+    print(f"B={B} ({noise_source}): {seconds:g} s of speech -> {W} chained windows, {n_frames} frames ({n_frames / 15:.1f} s of gesture) in "
+          f"{dt * 1e3:.1f} ms ({B * n_frames / dt:.0f} pose-frames/s)")
 
 
 def main_pipelined(B, N):

@@ -302,6 +302,54 @@ int ls_prepare(ls_handle* h, const ls_cond* c);           /* once per sampling c
 int ls_prepare_async(ls_handle* h, const ls_cond* c);
 int ls_sample(ls_handle* h, const ls_sample_args* a);
 int ls_forward(ls_handle* h, const ls_forward_args* a);
+
+/* ---- Long-form synthesis: W windows of T = nframes frames chained on the device.  Window w reads the audio samples
+ * [w * audio_stride, w * audio_stride + audio_len) of every clip (audio_stride = 32000: T - n_pre_seq = 30 frames at 15 fps of 16 kHz
+ * audio) and is conditioned on the last n_pre_seq poses of window w - 1 (window 0: on seed_poses), the way origin_x[..., :n_pre_seq]
+ * conditions one clip (RAG.py:110-112).  ls_long_prepare runs the WavEncoder over all W * B clip-windows once, in chunks, and the
+ * per-batch stages of ls_prepare (speaker style, guidance scales, step plan, workspaces) once at batch B; it replaces the handle's
+ * prepared conditioning.  ls_long_sample then runs, per window, with no copy from the device and no synchronisation in
+ * between: the hand-off kernel (ls_chain.hip), the two static projections of ls_prepare, and the loop of ls_sample (its captured
+ * graph is replayed per window).  Fused 34-frame models only. */
+#define LS_LONG_AUDIO_STRIDE 32000
+typedef struct ls_long_cond {
+    int32_t batch;
+    int32_t n_windows;          /* W >= 1                                                                             */
+    int32_t on_device;
+    int32_t encoder_chunk;      /* clip-windows per WavEncoder pass (bounds its workspaces: ~1.5 MB per clip); 0: 256 */
+    int64_t audio_samples;      /* L: samples per clip in `audio`; shorter than audio_len + (W-1) * audio_stride = zero-padded at the
+                                   end, longer = the rest is not read                                                 */
+    const float* audio;         /* [B, L]                                                                             */
+    const float* seed_poses;    /* [B, J, F, n_pre_seq]: origin_x[..., :n_pre_seq] of window 0                        */
+    const int64_t* vid_indices; /* [B]                                                                                */
+    const int64_t* emo;         /* [W, B] one emotion id per window and clip (y['emo'][:, 0] of that window), or NULL (TED) */
+    const float* scale;         /* [B]                                                                                */
+} ls_long_cond;
+int ls_long_prepare(ls_handle* h, const ls_long_cond* c);
+
+struct ls_sag;
+typedef struct ls_long_sample_args {
+    int32_t sampler;            /* LS_SAMPLER_DDPM | LS_SAMPLER_DDIM                                                  */
+    int32_t noise_mode;         /* LS_NOISE_TAPE | LS_NOISE_PHILOX                                                    */
+    int32_t skip_timesteps;
+    int32_t on_device;
+    int32_t use_graph;
+    int32_t clip_denoised;
+    int32_t two_pass_always;
+    float eta;
+    const float* x_init;        /* TAPE: [W, B, J, F, T] x_T of every window; PHILOX: NULL                            */
+    const float* eps_tape;      /* TAPE: [W, n_exec, 2, B, latent_dim]                                                */
+    const float* noise_tape;    /* TAPE: [W, n_exec, B, J, F, T]                                                      */
+    uint64_t seed;              /* PHILOX: one key per call                                                           */
+    uint64_t sample_offset;     /* PHILOX: global index of clip 0; window w draws the streams of global sample index
+                                   sample_offset + b + (w << 48) (ls_philox.h), so batch + sample_offset < 2^48       */
+    struct ls_sag* sag;         /* LivelySpeaker chain: window w starts from q_sample(decoder(x = origin_x_w, z = text_features[w],
+                                   mask = ones)) as ls_sample's init_image; NULL: from zeros when skip_timesteps > 0  */
+    const float* text_features; /* with sag: [W, B, latent_dim]                                                       */
+    float* timeline;            /* [B, J, F, T + (W - 1) * (T - n_pre_seq)]: window 0's frames, then frames n_pre_seq.. of each later one */
+    float* windows;             /* [W, B, J, F, T] the raw windows, or NULL                                           */
+} ls_long_sample_args;
+int ls_long_sample(ls_handle* h, const ls_long_sample_args* a);
 int ls_step(ls_handle* h, const ls_step_args* a);
 int ls_plms_step(ls_handle* h, const ls_plms_step_args* a);
 /* elementwise q_sample (gaussian_diffusion.py:240-258) at schedule index i; pointers per on_device */

@@ -50,6 +50,19 @@ class LsSampleArgs(C.Structure):
                 ("inpainted_motion", C.c_void_p), ("inpaint_noise", C.c_void_p), ("inpaint_noised", C.c_int32), ("plms_order", C.c_int32)]
 
 
+class LsLongCond(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("n_windows", C.c_int32), ("on_device", C.c_int32), ("encoder_chunk", C.c_int32),
+                ("audio_samples", C.c_int64), ("audio", C.c_void_p), ("seed_poses", C.c_void_p), ("vid_indices", C.c_void_p),
+                ("emo", C.c_void_p), ("scale", C.c_void_p)]
+
+
+class LsLongSampleArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sampler", "noise_mode", "skip_timesteps", "on_device", "use_graph", "clip_denoised",
+                                         "two_pass_always")] + [
+        ("eta", C.c_float), ("x_init", C.c_void_p), ("eps_tape", C.c_void_p), ("noise_tape", C.c_void_p), ("seed", C.c_uint64),
+        ("sample_offset", C.c_uint64), ("sag", C.c_void_p), ("text_features", C.c_void_p), ("timeline", C.c_void_p), ("windows", C.c_void_p)]
+
+
 class LsForwardArgs(C.Structure):
     _fields_ = [("on_device", C.c_int32), ("no_sync", C.c_int32), ("x", C.c_void_p), ("timesteps", C.c_void_p),
                 ("eps_cond", C.c_void_p), ("eps_uncond", C.c_void_p), ("out_cond", C.c_void_p),
@@ -127,7 +140,7 @@ class LsEvalConfig(C.Structure):
 
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
-           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
+           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_sample", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
@@ -199,6 +212,8 @@ def load_library(build_if_missing: bool = True):
     lib.ls_prepare.argtypes = [C.c_void_p, C.POINTER(LsCond)]
     lib.ls_prepare_async.argtypes = [C.c_void_p, C.POINTER(LsCond)]
     lib.ls_sample.argtypes = [C.c_void_p, C.POINTER(LsSampleArgs)]
+    lib.ls_long_prepare.argtypes = [C.c_void_p, C.POINTER(LsLongCond)]
+    lib.ls_long_sample.argtypes = [C.c_void_p, C.POINTER(LsLongSampleArgs)]
     lib.ls_forward.argtypes = [C.c_void_p, C.POINTER(LsForwardArgs)]
     lib.ls_step.argtypes = [C.c_void_p, C.POINTER(LsStepArgs)]
     lib.ls_plms_step.argtypes = [C.c_void_p, C.POINTER(LsPlmsStepArgs)]
@@ -698,6 +713,57 @@ class Engine(_Handle):
             return None
         self._segment_inputs = None
         return (out, dumps) if dump_steps else out
+
+    # ---- long-form synthesis ---------------------------------------------------------------------
+    def long_prepare(self, audio, seed_poses, vid_indices, scale, emo=None, n_windows=1, encoder_chunk=None):
+        """Once-per-call stage of a long-form call (ls_long_prepare): ``audio`` [B, L] is encoded once for all ``n_windows`` windows
+        (zero-padded at the end when short), ``seed_poses`` [B, J, F, n_pre_seq] condition window 0, ``emo`` [W, B] (BEAT).  Replaces
+        whatever ``prepare`` left resident."""
+        B, W = int(audio.shape[0]), int(n_windows)
+        npre = int(self.cfg.n_pre_seq)
+        m = _Marshal(self.device, audio, seed_poses, vid_indices, scale, emo, stream=self._stream)
+        c = LsLongCond(B, W, int(m.on_device), int(encoder_chunk or 0), int(audio.shape[1]), m.f32(audio, (B, int(audio.shape[1]))),
+                       m.f32(seed_poses, (B, self.J, self.F, npre)), m.i64(vid_indices, (B,)), m.i64(emo, (W, B)), m.f32(scale, (B,)))
+        m.ready()
+        self._check(self.lib.ls_long_prepare(self.h, C.byref(c)), "ls_long_prepare")
+        self.batch, self.n_windows = B, W
+
+    def long_sample(self, sampler=LS_SAMPLER_DDIM, x_init=None, eps_tape=None, noise_tape=None, skip_timesteps=0, eta=0.0,
+                    philox_seed=None, sample_offset=0, use_graph=True, clip_denoised=False, two_pass_always=False, device_out=False,
+                    sag=None, text_features=None, return_windows=False):
+        """The chained windows of the last ``long_prepare`` (ls_long_sample).  TAPE mode with ``x_init`` [W, B, J, F, T], ``eps_tape``
+        [W, n_exec, 2, B, D] and ``noise_tape`` [W, n_exec, B, J, F, T]; PHILOX mode with ``philox_seed``.  ``sag``: a SagEngine whose
+        decode of (origin_x_w, ``text_features`` [W, B, D]) starts every window.  Returns the timeline [B, J, F, T + (W-1)(T-n_pre)]
+        (and the raw windows [W, B, J, F, T])."""
+        B, W, D = self.batch, self.n_windows, self.D
+        members = [x_init, eps_tape, noise_tape, text_features]
+        if device_out:
+            import torch
+            members.append(torch.empty(1, device=torch.device("cuda", self.device)))
+        m = _Marshal(self.device, *members, stream=self._stream)
+        n_exec = self.n_steps - skip_timesteps
+        a = LsLongSampleArgs()
+        a.sampler, a.skip_timesteps, a.on_device, a.use_graph = int(sampler), int(skip_timesteps), int(m.on_device), int(bool(use_graph))
+        a.clip_denoised, a.two_pass_always, a.eta = int(bool(clip_denoised)), int(bool(two_pass_always)), float(eta)
+        if philox_seed is None:
+            a.noise_mode = LS_NOISE_TAPE
+            a.x_init = m.f32(x_init, (W,) + self._xshape())
+            a.eps_tape = m.f32(eps_tape, (W, n_exec, 2, B, D))
+            a.noise_tape = m.f32(noise_tape, (W, n_exec) + self._xshape())
+        else:
+            a.noise_mode = LS_NOISE_PHILOX
+            a.seed, a.sample_offset = int(philox_seed), int(sample_offset)
+        if sag is not None:
+            a.sag = sag.h
+            a.text_features = m.f32(text_features, (W, B, D))
+        n_frames = self.T + (W - 1) * (self.T - int(self.cfg.n_pre_seq))
+        timeline, a.timeline = m.out((B, self.J, self.F, n_frames))
+        windows = None
+        if return_windows:
+            windows, a.windows = m.out((W,) + self._xshape())
+        m.ready()
+        self._check(self.lib.ls_long_sample(self.h, C.byref(a)), "ls_long_sample")
+        return (timeline, windows) if return_windows else timeline
 
     def q_sample(self, index, x_start, noise):
         m = _Marshal(self.device, x_start, noise, stream=self._stream)

@@ -460,6 +460,146 @@ void ls::resolve_prepare_timing(ls_handle* h, bool block) {
     if (hipEventElapsedTime(&h->timing.prepare_ms, h->ev[4], h->ev[5]) == hipSuccess) h->prepare_pending = false;
 }
 
+// guidance scale 1 for the whole batch (what the reference's callers run: test_RAG_ted.py:183): out_u + 1 * (out_c - out_u) is out_c,
+// so the sampling loop may skip the uncond pass (ls_sample_args.two_pass_always keeps both).  `scale`: the caller's [B] (host unless od)
+int ls::prepare_scale(ls_handle* h, const float* scale, int B, int od) {
+    hipStream_t st = h->stream;
+    std::vector<float> sc((size_t)B);
+    if (od) {           // read back the ingested copy on the handle's own stream: ordered behind the caller's stream (ls_stream_order)
+        HIPCHK(h, hipMemcpyAsync(sc.data(), h->scale.p, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+    } else {
+        memcpy(sc.data(), scale, (size_t)B * sizeof(float));
+    }
+    h->all_scale_one = true;
+    for (float v : sc) if (v != 1.0f) { h->all_scale_one = false; break; }
+    return LS_OK;
+}
+
+// WavEncoder (audio_enc.py:6-25) over B clips [B][audio_len] at `in`: conv -> [IN + LReLU fused into the next conv's staging] x3 -> conv;
+// the audio features are left in c4 [B][256][T]
+int ls::run_wav_encoder(ls_handle* h, const float* in, int B) {
+    hipStream_t st = h->stream;
+    const int* Lc = h->convL;
+    DevBuf* outs[4] = {&h->c1, &h->c2, &h->c3, &h->c4};
+    DevBuf* stats[3] = {&h->st1, &h->st2, &h->st3};
+    const float* in_stats = nullptr;
+    // every conv kernel also produces the InstanceNorm statistics of its own output (partials -> k_stats_merge), so the
+    // activations are written once and read once
+    {
+        size_t need = 0;
+        for (int i = 0; i < 3; ++i) {
+            const size_t n = (size_t)B * kConvCout[i] * ((Lc[i + 1] + 63) / 64) * 4 * 3;
+            if (n > need) need = n;
+        }
+        HIPCHK(h, h->spart.ensure(need * sizeof(float)));
+    }
+    for (int i = 0; i < 4; ++i) {
+        HIPCHK(h, outs[i]->ensure((size_t)B * kConvCout[i] * Lc[i + 1] * sizeof(float)));
+        float* ostats = nullptr;
+        if (i < 3) {
+            HIPCHK(h, stats[i]->ensure((size_t)B * kConvCout[i] * 2 * sizeof(float)));
+            ostats = stats[i]->f();
+        }
+        if (i == 0)     // Cin = 1: a 15-tap FIR per channel, bound by the output write
+            HIPCHK(h, launch_conv1_fwd(in, h->conv_w[0].f(), h->conv_b[0].f(), outs[0]->f(), ostats, h->spart.f(), B, Lc[0], Lc[1], kConvPad[0], st));
+        else
+            HIPCHK(h, launch_conv1d_mfma(in, in_stats, h->conv_img[i].f(), h->conv_b[i].f(), outs[i]->f(), ostats, h->spart.f(), B, kConvCin[i],
+                                         kConvCout[i], Lc[i], Lc[i + 1], st));
+        in_stats = ostats;
+        in = outs[i]->f();
+    }
+    return LS_OK;
+}
+
+// speaker style (RAG.py:116-119): z = Embedding[vid]; mu, logvar = Linear(z); std = exp(0.5*logvar)
+int ls::prepare_style(ls_handle* h, int B) {
+    hipStream_t st = h->stream;
+    HIPCHK(h, h->z.ensure((size_t)B * 256 * sizeof(float)));
+    HIPCHK(h, h->z_mu.ensure((size_t)B * kD * sizeof(float)));
+    HIPCHK(h, h->z_logvar.ensure((size_t)B * kD * sizeof(float)));
+    HIPCHK(h, h->z_std.ensure((size_t)B * kD * sizeof(float)));
+    HIPCHK(h, launch_gather_rows(h->spk_emb.f(), static_cast<const int64_t*>(h->vid.p), h->z.f(), B, 256, h->cfg.n_speakers, st));
+    HIPCHK(h, h->z_ml.ensure((size_t)B * 2 * kD * sizeof(float)));
+    HIPCHK(h, launch_gemm_nt(h->z.f(), 256, h->ml_w.f(), 256, h->ml_b.f(), nullptr, 0, h->z_ml.f(), 2 * kD, B, 2 * kD, 256, 0, st));
+    HIPCHK(h, launch_split_style(h->z_ml.f(), h->z_mu.f(), h->z_logvar.f(), h->z_std.f(), B, st));
+    return LS_OK;
+}
+
+// the step plan of a batch of B clips and the workspaces of its kernel families (every one held by address in a captured loop)
+int ls::prepare_plan(ls_handle* h, int B) {
+    hipStream_t st = h->stream;
+    int rc;
+    { const int keepB = h->B; h->B = B; decide_path(h); h->B = keepB; }
+    if (seg_n(h, 2) > 0) {      // exchange workspaces of the sample-split kernel: one launch's worth of (sample, pass) groups
+        const int nco = seg_n(h, 2);
+        int gcap = h->coop_groups_max;                  // the most groups any slicing keeps resident (LS_COOP_GROUPS caps all of them in -DLS_DEBUG builds)
+        if (gcap == coop_cap(h->n_cu, 1))
+            for (int ncb = 2; ncb <= 4; ncb *= 2) if (coop_cap(h->n_cu, ncb) > gcap) gcap = coop_cap(h->n_cu, ncb);
+        const int groups = 2 * nco < gcap ? 2 * nco : gcap;
+        bool fresh = false;
+        if ((rc = ensure_pinned(h, h->co_x, (size_t)groups * 36 * kD * sizeof(float), &fresh)) != LS_OK) return rc;
+        if (fresh) HIPCHK(h, hipMemsetAsync(h->co_x.p, 0, h->co_x.bytes, st));     // rows a 35-row pass never writes are pulled into LDS (never read)
+        if ((rc = ensure_pinned(h, h->co_part, (size_t)groups * 8 * 36 * (size_t)h->NOB * 16 * sizeof(float))) != LS_OK) return rc;
+        if ((rc = ensure_pinned(h, h->co_gran, (size_t)groups * 2 * 36 * 8 * 2 * sizeof(unsigned long long))) != LS_OK) return rc;
+        if ((rc = ensure_pinned(h, h->co_flag, (size_t)groups * 16 * sizeof(unsigned long long))) != LS_OK) return rc;
+        h->coop_groups = groups;
+    }
+    if (seg_n(h, 3) > 0) {      // CFG hand-off of the one-pass-per-workgroup kernel: each pass's output, one ticket word per sample
+        const int npa = seg_n(h, 3);
+        if ((rc = ensure_pinned(h, h->pa_out, (size_t)npa * 2 * h->T * h->JF * sizeof(float))) != LS_OK) return rc;
+        if ((rc = ensure_pinned(h, h->pa_cnt, (size_t)npa * sizeof(unsigned))) != LS_OK) return rc;
+        HIPCHK(h, hipMemsetAsync(h->pa_cnt.p, 0, h->pa_cnt.bytes, st));
+        h->pass_n = npa;
+    }
+    if (seg_n(h, 1) > 0) {      // workspaces of the batch-level path: token sequences of both passes (two buffers), row partials, poseFinal output
+        const size_t nlo = seg_n(h, 1);
+        const size_t rows = ((size_t)2 * nlo * h->S + 127) / 128 * 128;      // whole 128-row GEMM tiles (the fused channel-mixing product runs over the pad rows too)
+        const size_t mpad = ((size_t)nlo * h->T + 127) / 128 * 128;           // x_t projection on whole 128-row tiles (k_long_padx)
+        bool fresh1 = false, fresh2 = false;
+        if ((rc = ensure_pinned(h, h->lx_proj, mpad * kD * sizeof(float))) != LS_OK) return rc;
+        if ((rc = ensure_pinned(h, h->lx_xpad, mpad * h->JFP * sizeof(float))) != LS_OK) return rc;
+        if ((rc = ensure_pinned(h, h->lx_X, rows * kD * sizeof(float), &fresh1)) != LS_OK) return rc;
+        if ((rc = ensure_pinned(h, h->lx_U, rows * kD * sizeof(float), &fresh2)) != LS_OK) return rc;
+        if (fresh1 || fresh2) {                                               // fresh memory: the pad rows must hold finite values (their products are computed and discarded)
+            HIPCHK(h, hipMemsetAsync(h->lx_X.p, 0, h->lx_X.bytes, st)); HIPCHK(h, hipMemsetAsync(h->lx_U.p, 0, h->lx_U.bytes, st));
+        }
+        if ((rc = ensure_pinned(h, h->lx_OUT, rows * (size_t)((h->JF + 127) / 128 * 128) * sizeof(float))) != LS_OK) return rc;
+        if ((rc = ensure_pinned(h, h->lx_part1, rows * 16 * sizeof(float), &fresh1)) != LS_OK) return rc;
+        if ((rc = ensure_pinned(h, h->lx_part2, rows * 16 * sizeof(float), &fresh2)) != LS_OK) return rc;
+        if (fresh1 || fresh2) {
+            HIPCHK(h, hipMemsetAsync(h->lx_part1.p, 0, h->lx_part1.bytes, st)); HIPCHK(h, hipMemsetAsync(h->lx_part2.p, 0, h->lx_part2.bytes, st));
+        }
+        // the one-launch mixer (a model whose token count it supports, unless ls_set_path(2) asked for the batch-level kernels): as many
+        // (sample, pass) groups per launch as fit the chip with four workgroups each, a multiple of eight (the grid is dealt in sets of eight groups)
+        const int was_cap = h->mix_cap;
+        h->mix_cap = 0;
+        // Measured on MI355X (profiles/r06_mixer_150_frames.md): a mixer launch costs ~0.50 ms however few of its 64 groups are used, the
+        // batch-level kernels 0.25 ms + ~13-17 us per clip: `auto` (mode 0) takes the mixer when every launch is at least 7/8 full and the batch
+        // is at most three launches (28-32, 60-64, 92-96 clips under CFG); ls_set_path(3) forces it, (2) forces the batch-level kernels.
+        bool want_mix = !h->fused && h->mx_wch.p && h->path_mode != 2 && 2 * h->cfg.layers + 2 <= (int)kCoopEpochStride;
+        if (want_mix && h->path_mode == 0) {
+            const int full = h->n_cu / kMixSlices / 8 * 8, groups = (int)(2 * nlo), last = groups % full;
+            want_mix = full >= 8 && groups <= 3 * full && groups >= full * 7 / 8 && (last == 0 || last >= full * 7 / 8);
+        }
+        if (want_mix) {
+            int cap = h->n_cu / kMixSlices / 8 * 8;
+            const int need = (int)((2 * nlo + 7) / 8 * 8);
+            if (cap > need) cap = need;
+            if (cap >= 8) {
+                if ((rc = ensure_pinned(h, h->mx_xg, (size_t)cap * 32 * kMixRows * 16 * sizeof(float), &fresh1)) != LS_OK) return rc;
+                if ((rc = ensure_pinned(h, h->mx_gran, (size_t)cap * (2 * kMixRows + 1) * kMixSlices * 2 * sizeof(unsigned long long))) != LS_OK) return rc;
+                if (fresh1) HIPCHK(h, hipMemsetAsync(h->mx_xg.p, 0, h->mx_xg.bytes, st));       // rows a pass never writes are pulled into LDS (finite, never used)
+                // partial poseFinal products of the whole batch: [2 B][4 slices][S][16 npt]
+                if (h->mx_npt > 0 && (rc = ensure_pinned(h, h->mx_pout, (size_t)2 * nlo * kMixSlices * h->S * 16 * h->mx_npt * sizeof(float))) != LS_OK) return rc;
+                h->mix_cap = cap;
+            }
+        }
+        if (was_cap != h->mix_cap) free_graph(h);
+    }
+    return LS_OK;
+}
+
 extern "C" {
 
 int ls_abi_version(void) { return LS_ABI_VERSION; }
@@ -636,50 +776,9 @@ static int prepare_impl(ls_handle* h, const ls_cond* c, bool wait) {
         HIPCHK(h, hipEventSynchronize(h->ev[6]));
     }
     h->seg_next = -1;       // a new conditioning ends any segmented loop in progress
-    {   // guidance scale 1 for the whole batch (what the reference's callers run: test_RAG_ted.py:183): out_u + 1 * (out_c - out_u)
-        // is out_c, so the sampling loop may skip the uncond pass (ls_sample_args.two_pass_always keeps both)
-        std::vector<float> sc((size_t)B);
-        if (od) {           // read back the ingested copy on the handle's own stream: ordered behind the caller's stream (ls_stream_order)
-            HIPCHK(h, hipMemcpyAsync(sc.data(), h->scale.p, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
-            HIPCHK(h, hipStreamSynchronize(st));
-        } else {
-            memcpy(sc.data(), c->scale, (size_t)B * sizeof(float));
-        }
-        h->all_scale_one = true;
-        for (float v : sc) if (v != 1.0f) { h->all_scale_one = false; break; }
-    }
-
-    // ---- WavEncoder (audio_enc.py:6-25): conv -> [IN + LReLU fused into the next conv's staging] x3 -> conv
-    const int* Lc = h->convL;
-    DevBuf* outs[4] = {&h->c1, &h->c2, &h->c3, &h->c4};
-    DevBuf* stats[3] = {&h->st1, &h->st2, &h->st3};
-    const float* in = od ? static_cast<const float*>(c->audio_input) : h->audio.f();
-    const float* in_stats = nullptr;
-    // every conv kernel also produces the InstanceNorm statistics of its own output (partials -> k_stats_merge), so the
-    // activations are written once and read once
-    {
-        size_t need = 0;
-        for (int i = 0; i < 3; ++i) {
-            const size_t n = (size_t)B * kConvCout[i] * ((Lc[i + 1] + 63) / 64) * 4 * 3;
-            if (n > need) need = n;
-        }
-        HIPCHK(h, h->spart.ensure(need * sizeof(float)));
-    }
-    for (int i = 0; i < 4; ++i) {
-        HIPCHK(h, outs[i]->ensure((size_t)B * kConvCout[i] * Lc[i + 1] * sizeof(float)));
-        float* ostats = nullptr;
-        if (i < 3) {
-            HIPCHK(h, stats[i]->ensure((size_t)B * kConvCout[i] * 2 * sizeof(float)));
-            ostats = stats[i]->f();
-        }
-        if (i == 0)     // Cin = 1: a 15-tap FIR per channel, bound by the output write
-            HIPCHK(h, launch_conv1_fwd(in, h->conv_w[0].f(), h->conv_b[0].f(), outs[0]->f(), ostats, h->spart.f(), B, Lc[0], Lc[1], kConvPad[0], st));
-        else
-            HIPCHK(h, launch_conv1d_mfma(in, in_stats, h->conv_img[i].f(), h->conv_b[i].f(), outs[i]->f(), ostats, h->spart.f(), B, kConvCin[i],
-                                         kConvCout[i], Lc[i], Lc[i + 1], st));
-        in_stats = ostats;
-        in = outs[i]->f();
-    }
+    h->lg_prepared = false; // ... and replaces a long-form call's
+    if ((rc = prepare_scale(h, c->scale, B, od)) != LS_OK) return rc;
+    if ((rc = run_wav_encoder(h, od ? static_cast<const float*>(c->audio_input) : h->audio.f(), B)) != LS_OK) return rc;
     // ---- static part of input_mapping (RAG.py:110-114): columns JF.. of W_in act on [prefix poses | bit | audio]
     const int KPP = h->KPP;
     HIPCHK(h, h->feat_c.ensure((size_t)B * h->T * kAudioFeat * sizeof(float)));       // audio features [B*T][256]
@@ -690,86 +789,12 @@ static int prepare_impl(ls_handle* h, const ls_cond* c, bool wait) {
     // static_u = [prefix poses | bit] . Wpre^T + b;  static_c = static_u + audio . Waud^T  (K = KPP + 256 instead of 2 x that)
     HIPCHK(h, launch_gemm_nt(h->feat_u.f(), KPP, h->win_pre.f(), KPP, h->win_bias.f(), nullptr, 0, h->static_u.f(), kD, B * h->T, kD, KPP, 0, st));
     HIPCHK(h, launch_gemm_nt(h->feat_c.f(), kAudioFeat, h->win_aud.f(), kAudioFeat, nullptr, h->static_u.f(), kD, h->static_c.f(), kD, B * h->T, kD, kAudioFeat, 0, st));
-    // ---- speaker style (RAG.py:116-119): z = Embedding[vid]; mu, logvar = Linear(z); std = exp(0.5*logvar)
-    HIPCHK(h, h->z.ensure((size_t)B * 256 * sizeof(float)));
-    HIPCHK(h, h->z_mu.ensure((size_t)B * kD * sizeof(float)));
-    HIPCHK(h, h->z_logvar.ensure((size_t)B * kD * sizeof(float)));
-    HIPCHK(h, h->z_std.ensure((size_t)B * kD * sizeof(float)));
-    HIPCHK(h, launch_gather_rows(h->spk_emb.f(), static_cast<const int64_t*>(h->vid.p), h->z.f(), B, 256, h->cfg.n_speakers, st));
-    HIPCHK(h, h->z_ml.ensure((size_t)B * 2 * kD * sizeof(float)));
-    HIPCHK(h, launch_gemm_nt(h->z.f(), 256, h->ml_w.f(), 256, h->ml_b.f(), nullptr, 0, h->z_ml.f(), 2 * kD, B, 2 * kD, 256, 0, st));
-    HIPCHK(h, launch_split_style(h->z_ml.f(), h->z_mu.f(), h->z_logvar.f(), h->z_std.f(), B, st));
+    if ((rc = prepare_style(h, B)) != LS_OK) return rc;
     if (h->cfg.n_prefix_tokens == 2) {   // scripts_beat/model/RAG.py:125
         HIPCHK(h, h->emo_tok.ensure((size_t)B * kD * sizeof(float)));
         HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->emo.p), h->emo_tok.f(), B, kD, h->cfg.n_emotions, st, h->T));   // y['emo'][:, 0]
     }
-    { const int keepB = h->B; h->B = B; decide_path(h); h->B = keepB; }
-    if (seg_n(h, 2) > 0) {      // exchange workspaces of the sample-split kernel: one launch's worth of (sample, pass) groups
-        const int nco = seg_n(h, 2);
-        int gcap = h->coop_groups_max;                  // the most groups any slicing keeps resident (LS_COOP_GROUPS caps all of them in -DLS_DEBUG builds)
-        if (gcap == coop_cap(h->n_cu, 1))
-            for (int ncb = 2; ncb <= 4; ncb *= 2) if (coop_cap(h->n_cu, ncb) > gcap) gcap = coop_cap(h->n_cu, ncb);
-        const int groups = 2 * nco < gcap ? 2 * nco : gcap;
-        bool fresh = false;
-        if ((rc = ensure_pinned(h, h->co_x, (size_t)groups * 36 * kD * sizeof(float), &fresh)) != LS_OK) return rc;
-        if (fresh) HIPCHK(h, hipMemsetAsync(h->co_x.p, 0, h->co_x.bytes, st));     // rows a 35-row pass never writes are pulled into LDS (never read)
-        if ((rc = ensure_pinned(h, h->co_part, (size_t)groups * 8 * 36 * (size_t)h->NOB * 16 * sizeof(float))) != LS_OK) return rc;
-        if ((rc = ensure_pinned(h, h->co_gran, (size_t)groups * 2 * 36 * 8 * 2 * sizeof(unsigned long long))) != LS_OK) return rc;
-        if ((rc = ensure_pinned(h, h->co_flag, (size_t)groups * 16 * sizeof(unsigned long long))) != LS_OK) return rc;
-        h->coop_groups = groups;
-    }
-    if (seg_n(h, 3) > 0) {      // CFG hand-off of the one-pass-per-workgroup kernel: each pass's output, one ticket word per sample
-        const int npa = seg_n(h, 3);
-        if ((rc = ensure_pinned(h, h->pa_out, (size_t)npa * 2 * h->T * h->JF * sizeof(float))) != LS_OK) return rc;
-        if ((rc = ensure_pinned(h, h->pa_cnt, (size_t)npa * sizeof(unsigned))) != LS_OK) return rc;
-        HIPCHK(h, hipMemsetAsync(h->pa_cnt.p, 0, h->pa_cnt.bytes, st));
-        h->pass_n = npa;
-    }
-    if (seg_n(h, 1) > 0) {      // workspaces of the batch-level path: token sequences of both passes (two buffers), row partials, poseFinal output
-        const size_t nlo = seg_n(h, 1);
-        const size_t rows = ((size_t)2 * nlo * h->S + 127) / 128 * 128;      // whole 128-row GEMM tiles (the fused channel-mixing product runs over the pad rows too)
-        const size_t mpad = ((size_t)nlo * h->T + 127) / 128 * 128;           // x_t projection on whole 128-row tiles (k_long_padx)
-        bool fresh1 = false, fresh2 = false;
-        if ((rc = ensure_pinned(h, h->lx_proj, mpad * kD * sizeof(float))) != LS_OK) return rc;
-        if ((rc = ensure_pinned(h, h->lx_xpad, mpad * h->JFP * sizeof(float))) != LS_OK) return rc;
-        if ((rc = ensure_pinned(h, h->lx_X, rows * kD * sizeof(float), &fresh1)) != LS_OK) return rc;
-        if ((rc = ensure_pinned(h, h->lx_U, rows * kD * sizeof(float), &fresh2)) != LS_OK) return rc;
-        if (fresh1 || fresh2) {                                               // fresh memory: the pad rows must hold finite values (their products are computed and discarded)
-            HIPCHK(h, hipMemsetAsync(h->lx_X.p, 0, h->lx_X.bytes, st)); HIPCHK(h, hipMemsetAsync(h->lx_U.p, 0, h->lx_U.bytes, st));
-        }
-        if ((rc = ensure_pinned(h, h->lx_OUT, rows * (size_t)((h->JF + 127) / 128 * 128) * sizeof(float))) != LS_OK) return rc;
-        if ((rc = ensure_pinned(h, h->lx_part1, rows * 16 * sizeof(float), &fresh1)) != LS_OK) return rc;
-        if ((rc = ensure_pinned(h, h->lx_part2, rows * 16 * sizeof(float), &fresh2)) != LS_OK) return rc;
-        if (fresh1 || fresh2) {
-            HIPCHK(h, hipMemsetAsync(h->lx_part1.p, 0, h->lx_part1.bytes, st)); HIPCHK(h, hipMemsetAsync(h->lx_part2.p, 0, h->lx_part2.bytes, st));
-        }
-        // the one-launch mixer (a model whose token count it supports, unless ls_set_path(2) asked for the batch-level kernels): as many
-        // (sample, pass) groups per launch as fit the chip with four workgroups each, a multiple of eight (the grid is dealt in sets of eight groups)
-        const int was_cap = h->mix_cap;
-        h->mix_cap = 0;
-        // Measured on MI355X (profiles/r06_mixer_150_frames.md): a mixer launch costs ~0.50 ms however few of its 64 groups are used, the
-        // batch-level kernels 0.25 ms + ~13-17 us per clip: `auto` (mode 0) takes the mixer when every launch is at least 7/8 full and the batch
-        // is at most three launches (28-32, 60-64, 92-96 clips under CFG); ls_set_path(3) forces it, (2) forces the batch-level kernels.
-        bool want_mix = !h->fused && h->mx_wch.p && h->path_mode != 2 && 2 * h->cfg.layers + 2 <= (int)kCoopEpochStride;
-        if (want_mix && h->path_mode == 0) {
-            const int full = h->n_cu / kMixSlices / 8 * 8, groups = (int)(2 * nlo), last = groups % full;
-            want_mix = full >= 8 && groups <= 3 * full && groups >= full * 7 / 8 && (last == 0 || last >= full * 7 / 8);
-        }
-        if (want_mix) {
-            int cap = h->n_cu / kMixSlices / 8 * 8;
-            const int need = (int)((2 * nlo + 7) / 8 * 8);
-            if (cap > need) cap = need;
-            if (cap >= 8) {
-                if ((rc = ensure_pinned(h, h->mx_xg, (size_t)cap * 32 * kMixRows * 16 * sizeof(float), &fresh1)) != LS_OK) return rc;
-                if ((rc = ensure_pinned(h, h->mx_gran, (size_t)cap * (2 * kMixRows + 1) * kMixSlices * 2 * sizeof(unsigned long long))) != LS_OK) return rc;
-                if (fresh1) HIPCHK(h, hipMemsetAsync(h->mx_xg.p, 0, h->mx_xg.bytes, st));       // rows a pass never writes are pulled into LDS (finite, never used)
-                // partial poseFinal products of the whole batch: [2 B][4 slices][S][16 npt]
-                if (h->mx_npt > 0 && (rc = ensure_pinned(h, h->mx_pout, (size_t)2 * nlo * kMixSlices * h->S * 16 * h->mx_npt * sizeof(float))) != LS_OK) return rc;
-                h->mix_cap = cap;
-            }
-        }
-        if (was_cap != h->mix_cap) free_graph(h);
-    }
+    if ((rc = prepare_plan(h, B)) != LS_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev[5], st));
     if (wait) {
         HIPCHK(h, hipStreamSynchronize(st));
@@ -791,6 +816,80 @@ int ls_prepare(ls_handle* h, const ls_cond* c) { return prepare_impl(h, c, true)
 // SAG decode, which needs none of it (scripts/test_LivelySpeaker_ted.py:88-113 runs the two back to back).  Device-resident inputs
 // must stay valid until the next call on this handle that synchronises; host inputs are staged as in ls_prepare.
 int ls_prepare_async(ls_handle* h, const ls_cond* c) { return prepare_impl(h, c, false); }
+
+// Once-per-call stage of a long-form call (ls_long_cond in ls_hip.h).  The WavEncoder has no term that couples clips (InstanceNorm is per
+// clip and channel), so the W * B clip-windows go through it in chunks of any size and leave the features ls_prepare would compute for
+// each window at batch B; k_build_feats turns a chunk's conv4 block into its rows of the feature store (its feat_p half goes to a scratch:
+// the prefix rows are k_chain_window's).  Everything else is ls_prepare's own stage at batch B.
+int ls_long_prepare(ls_handle* h, const ls_long_cond* c) {
+    if (!h || !c) return fail(h, LS_EINVAL, "ls_long_prepare: null argument");
+    if (!h->committed) return fail(h, LS_ESTATE, "ls_long_prepare before ls_commit_weights");
+    if (!h->fused) return fail(h, LS_EUNSUPPORTED, "long-form synthesis chains the reference's %d-frame windows", kT);
+    if (c->batch < 1 || c->n_windows < 1) return fail(h, LS_EINVAL, "batch and n_windows must be >= 1");
+    if (c->audio_samples < 1 || c->encoder_chunk < 0) return fail(h, LS_EINVAL, "ls_long_prepare: bad audio_samples / encoder_chunk");
+    if (!c->audio || !c->seed_poses || !c->vid_indices || !c->scale) return fail(h, LS_EINVAL, "ls_long_prepare: null conditioning pointer");
+    if (h->cfg.n_prefix_tokens == 2 && !c->emo) return fail(h, LS_EINVAL, "BEAT variant needs emo ids");
+    if (h->cfg.n_pre_seq < 1) return fail(h, LS_EINVAL, "long-form synthesis needs n_pre_seq >= 1 (the hand-off poses)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int B = c->batch, W = c->n_windows, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, od = c->on_device;
+    const size_t L = (size_t)AL + (size_t)(W - 1) * LS_LONG_AUDIO_STRIDE, Lin = (size_t)c->audio_samples < L ? (size_t)c->audio_samples : L;
+    const int chunk = c->encoder_chunk > 0 ? c->encoder_chunk : 256;
+    const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    hipStream_t st = h->stream;
+    int rc;
+    h->prepared = h->lg_prepared = false;
+    h->seg_next = -1;
+    HIPCHK(h, hipEventRecord(h->ev[4], st));
+    HIPCHK(h, h->lg_audio.ensure((size_t)B * L * sizeof(float)));
+    if (Lin < L) HIPCHK(h, hipMemsetAsync(h->lg_audio.p, 0, (size_t)B * L * sizeof(float), st));
+    HIPCHK(h, hipMemcpy2DAsync(h->lg_audio.p, L * sizeof(float), c->audio, (size_t)c->audio_samples * sizeof(float), Lin * sizeof(float), B, kind, st));
+    if ((rc = ingest(h, h->lg_seed, c->seed_poses, (size_t)B * JF * h->cfg.n_pre_seq * sizeof(float), od)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->vid, c->vid_indices, (size_t)B * sizeof(int64_t), od)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->scale, c->scale, (size_t)B * sizeof(float), od)) != LS_OK) return rc;
+    if (c->emo && (rc = ingest(h, h->lg_emo_ids, c->emo, (size_t)W * B * sizeof(int64_t), od)) != LS_OK) return rc;
+    if ((rc = prepare_scale(h, c->scale, B, od)) != LS_OK) return rc;
+    if (!od) HIPCHK(h, hipStreamSynchronize(st));       // host inputs are the caller's again
+    // ---- WavEncoder over the clip-windows cw = w * B + b, `chunk` at a time
+    const int ncw = W * B, nmax = chunk < ncw ? chunk : ncw;
+    HIPCHK(h, h->lg_clips.ensure((size_t)nmax * AL * sizeof(float)));
+    HIPCHK(h, h->lg_featc.ensure((size_t)ncw * T * kAudioFeat * sizeof(float)));
+    HIPCHK(h, h->lg_featp.ensure((size_t)nmax * T * KPP * sizeof(float)));
+    HIPCHK(h, h->origin_x.ensure((size_t)B * JF * T * sizeof(float)));
+    HIPCHK(h, hipMemsetAsync(h->origin_x.p, 0, (size_t)B * JF * T * sizeof(float), st));     // frames n_pre.. are zero (RAG.py:110); also k_build_feats' (unused) pose source
+    for (int cw0 = 0; cw0 < ncw; cw0 += chunk) {
+        const int n = ncw - cw0 < chunk ? ncw - cw0 : chunk;
+        for (int cw = cw0; cw < cw0 + n;) {             // one strided copy per run of clips of the same window
+            const int w = cw / B, b = cw - w * B, run = (B - b) < (cw0 + n - cw) ? (B - b) : (cw0 + n - cw);
+            HIPCHK(h, hipMemcpy2DAsync(h->lg_clips.f() + (size_t)(cw - cw0) * AL, (size_t)AL * sizeof(float),
+                                       h->lg_audio.f() + (size_t)b * L + (size_t)w * LS_LONG_AUDIO_STRIDE, L * sizeof(float), (size_t)AL * sizeof(float), run,
+                                       hipMemcpyDeviceToDevice, st));
+            cw += run;
+        }
+        if ((rc = run_wav_encoder(h, h->lg_clips.f(), n)) != LS_OK) return rc;
+        HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f() + (size_t)cw0 * T * kAudioFeat, n, JF, KPP, 0, st, T));
+    }
+    // ---- per-batch stages, once: feat_u with every row zero (k_chain_window writes the prefix rows per window), style, emotion tokens, plan
+    HIPCHK(h, h->feat_u.ensure((size_t)B * T * KPP * sizeof(float)));
+    HIPCHK(h, hipMemsetAsync(h->feat_u.p, 0, (size_t)B * T * KPP * sizeof(float), st));
+    HIPCHK(h, h->static_c.ensure((size_t)B * T * kD * sizeof(float)));
+    HIPCHK(h, h->static_u.ensure((size_t)B * T * kD * sizeof(float)));
+    if ((rc = prepare_style(h, B)) != LS_OK) return rc;
+    if (h->cfg.n_prefix_tokens == 2) {
+        HIPCHK(h, h->emo_tok.ensure((size_t)B * kD * sizeof(float)));
+        HIPCHK(h, h->lg_emotok.ensure((size_t)W * B * kD * sizeof(float)));
+        HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->lg_emo_ids.p), h->lg_emotok.f(), W * B, kD, h->cfg.n_emotions, st));
+    }
+    if ((rc = prepare_plan(h, B)) != LS_OK) return rc;
+    HIPCHK(h, hipEventRecord(h->ev[5], st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    HIPCHK(h, hipEventElapsedTime(&h->timing.prepare_ms, h->ev[4], h->ev[5]));
+    h->prepare_pending = false;
+    if (h->B != B) free_graph(h);
+    h->B = B;
+    h->lg_W = W; h->lg_L = L;
+    h->lg_prepared = true;      // `prepared` stays false: the static projections exist per window, inside ls_long_sample only
+    return LS_OK;
+}
 
 int ls_stream_order(int device, void* first, void* then) {
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;

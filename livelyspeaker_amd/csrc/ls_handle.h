@@ -118,6 +118,14 @@ struct ls_handle {
     bool bpd_coef_valid = false;
     std::string coef_key;   // (sampler, eta, schedule) the per-index coefficient table `coef` was built for
 
+    // long-form synthesis (ls_long_prepare / ls_long_sample): lg_W chained windows of the prepared batch.  The zero-padded waveform [B][lg_L]
+    // and one encoder chunk's clip-windows [chunk][audio_len]; per-call stores of the windows' audio features [W][B][T][256] and emotion
+    // tokens [W][B][512]; the seed poses [B][JF][n_pre]; the call's tapes, text features, SAG output and outputs when the caller's are host memory
+    int lg_W = 0;
+    size_t lg_L = 0;
+    bool lg_prepared = false;
+    DevBuf lg_audio, lg_clips, lg_featc, lg_featp, lg_emo_ids, lg_emotok, lg_seed;
+    DevBuf lg_x, lg_eps, lg_nz, lg_text, lg_init, lg_mask, lg_timeline, lg_windows;
     // cached graph of the step loop
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
@@ -141,6 +149,11 @@ namespace ls {
 int ensure_temb_table(ls_handle* h);
 int build_temb_rows(ls_handle* h, const long long* idx_dev, int n, DevBuf& tmp, DevBuf& out);
 void resolve_prepare_timing(ls_handle* h, bool block);
+// the stages of ls_prepare that ls_long_prepare runs too, on the handle's stream
+int prepare_scale(ls_handle* h, const float* scale, int B, int on_device);
+int run_wav_encoder(ls_handle* h, const float* in, int B);
+int prepare_style(ls_handle* h, int B);
+int prepare_plan(ls_handle* h, int B);
 // ---- defined in ls_plan.cpp
 int seg_n(const ls_handle* h, int path);
 long long plan_code(const ls_handle* h);

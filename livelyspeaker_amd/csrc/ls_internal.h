@@ -304,6 +304,17 @@ hipError_t launch_randn_fill(float* out_btc, int B, int JF, const CallParams* ca
                              hipStream_t st, int T = kT);
 hipError_t launch_transpose_feat(const float* conv4, float* out_btc, int B, hipStream_t st, int T = kT);
 
+// ---- window hand-off of long-form synthesis (ls_chain.hip): one workgroup per clip.  prev: the finished window's sample in the internal
+// layout [B][T][JF], or null ahead of the call's first window (the prefix poses are then seed [B][JF][n_pre]).  feat_u != null: write
+// the coming window's n_pre prefix rows of feat_u [B*T][KPP] and prefix columns of origin_x [B][JF][T].  prev != null: frames f0 .. T-1
+// of it go to timeline [B][JF][T_total] at frame t_off (timeline nullable) and the whole window to window [B][JF][T] (nullable).
+struct ChainArgs {
+    const float* prev; const float* seed;
+    float* feat_u; float* origin_x; float* timeline; float* window;
+    int JF, T, KPP, n_pre, T_total, t_off, f0;
+};
+hipError_t launch_chain_window(const ChainArgs& a, int B, hipStream_t st);
+
 // ---- torch's device normal stream (ls_torch_philox.hip; LS_NOISE_TORCH_DEVICE) ---------------------------------------------
 // One torch.randn / randn_like of n float32 elements per step: written to dst + r * dst_stride for step r of the launch.
 struct TorchDraw {

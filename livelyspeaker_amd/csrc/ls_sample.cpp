@@ -749,6 +749,114 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
     return finish_loop(h, c, c.n_exec + (c.plms ? 1 : 0), replayed, false);      // model evaluations: PLMS's first step makes two
 }
 
+// Long-form synthesis (ls_long_sample_args in ls_hip.h): per window the hand-off kernel, ls_prepare's two static projections at ls_prepare's
+// shapes, and ls_sample's own begin_loop -> stage_loop_inputs -> run_loop on device-resident inputs; one wait at the end.  The loop's
+// launches read the handle's buffers only (static_c / static_u, the tape buffers, xa / xb, callp), none of which moves between windows,
+// so the graph captured for window 0 (or by an earlier call with the same key) is replayed for every later one.
+int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_sample: null argument");
+    if (!h->lg_prepared) return fail(h, LS_ESTATE, "ls_long_sample before ls_long_prepare");
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_sample before ls_set_schedule");
+    if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM) return fail(h, LS_EUNSUPPORTED, "ls_long_sample: DDPM and DDIM loops only");
+    if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EUNSUPPORTED, "ls_long_sample: TAPE and PHILOX noise only");
+    if (!a->timeline) return fail(h, LS_EINVAL, "ls_long_sample: null timeline");
+    if (a->sag && !a->text_features) return fail(h, LS_EINVAL, "ls_long_sample: sag without text_features");
+    const int B = h->B, W = h->lg_W, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, od = a->on_device, dev = h->cfg.device;
+    const int Tt = T + (W - 1) * (T - npre);
+    ls_sample_args wa{};
+    wa.sampler = a->sampler; wa.noise_mode = a->noise_mode; wa.skip_timesteps = a->skip_timesteps; wa.on_device = 1;
+    wa.use_graph = a->use_graph; wa.clip_denoised = a->clip_denoised; wa.two_pass_always = a->two_pass_always; wa.eta = a->eta;
+    int rc;
+    if ((rc = check_sampler_args(h, &wa)) != LS_OK) return rc;
+    const bool tape = a->noise_mode == LS_NOISE_TAPE;
+    if (tape && (!a->x_init || !a->eps_tape || !a->noise_tape)) return fail(h, LS_EINVAL, "TAPE mode needs x_init, eps_tape and noise_tape");
+    if (!tape && (a->sample_offset >> 48 || (a->sample_offset + (unsigned long long)B) >> 48)) return fail(h, LS_EINVAL, "PHILOX: sample_offset + batch must stay below 2^48 (the window index sits above)");
+    HIPCHK(h, hipSetDevice(dev));
+    if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
+    h->seg_next = -1;
+    hipStream_t st = h->stream;
+    const int n_exec = h->n_steps - a->skip_timesteps;
+    const size_t nelem = (size_t)B * JF * T, nx = nelem * sizeof(float), ne = (size_t)n_exec * 2 * B * kD, nn = (size_t)n_exec * nelem;
+    // host tapes / text features: one upload per call; device ones are read in place
+    const float *xs = a->x_init, *es = a->eps_tape, *ns = a->noise_tape, *tx = a->text_features;
+    if (tape && !od) {
+        if ((rc = ingest(h, h->lg_x, xs, W * nx, 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, W * ne * sizeof(float), 0)) != LS_OK ||
+            (rc = ingest(h, h->lg_nz, ns, W * nn * sizeof(float), 0)) != LS_OK) return rc;
+        xs = h->lg_x.f(); es = h->lg_eps.f(); ns = h->lg_nz.f();
+    }
+    ls_sag* const sag = a->sag;
+    void* const sag_st = sag ? ls_sag_stream(sag) : nullptr;
+    if (sag) {
+        if (!od) { if ((rc = ingest(h, h->lg_text, tx, (size_t)W * B * kD * sizeof(float), 0)) != LS_OK) return rc; tx = h->lg_text.f(); }
+        HIPCHK(h, h->lg_init.ensure(nx)); HIPCHK(h, h->lg_mask.ensure((size_t)B * T));
+        HIPCHK(h, hipMemsetAsync(h->lg_mask.p, 1, (size_t)B * T, st));
+        wa.init_image = h->lg_init.f();
+    }
+    float* tl = a->timeline;
+    float* wd = a->windows;
+    if (!od) {
+        HIPCHK(h, h->lg_timeline.ensure((size_t)B * JF * Tt * sizeof(float)));
+        if (wd) HIPCHK(h, h->lg_windows.ensure(W * nx));
+        tl = h->lg_timeline.f();
+        if (wd) wd = h->lg_windows.f();
+    }
+    ChainArgs ca{};
+    ca.seed = h->lg_seed.f(); ca.timeline = tl;
+    ca.JF = JF; ca.T = T; ca.KPP = h->KPP; ca.n_pre = npre; ca.T_total = Tt;
+    LoopCall c{};
+    int replayed = 0, replays = 0;
+    for (int w = 0; w <= W; ++w) {
+        // hand-off: window w - 1 leaves through the timeline, window w's prefix poses enter feat_u / origin_x
+        ca.prev = w ? x_plane(h, n_exec) : nullptr;
+        ca.feat_u = w < W ? h->feat_u.f() : nullptr; ca.origin_x = h->origin_x.f();
+        ca.f0 = w == 1 ? 0 : npre; ca.t_off = w <= 1 ? 0 : T + (w - 2) * (T - npre);
+        ca.window = (w && wd) ? wd + (size_t)(w - 1) * nelem : nullptr;
+        HIPCHK(h, launch_chain_window(ca, B, st));
+        if (w == W) break;
+        // the static projections with ls_prepare's arithmetic and shapes: static_u = feat_u . Wpre^T + b; static_c = static_u + feat_c[w] . Waud^T
+        HIPCHK(h, launch_gemm_nt(h->feat_u.f(), h->KPP, h->win_pre.f(), h->KPP, h->win_bias.f(), nullptr, 0, h->static_u.f(), kD, B * T, kD, h->KPP, 0, st));
+        HIPCHK(h, launch_gemm_nt(h->lg_featc.f() + (size_t)w * B * T * kAudioFeat, kAudioFeat, h->win_aud.f(), kAudioFeat, nullptr, h->static_u.f(), kD,
+                                 h->static_c.f(), kD, B * T, kD, kAudioFeat, 0, st));
+        if (h->cfg.n_prefix_tokens == 2)
+            HIPCHK(h, hipMemcpyAsync(h->emo_tok.p, h->lg_emotok.f() + (size_t)w * B * kD, (size_t)B * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (sag) {      // the decoder runs on its own handle's stream, ordered behind the hand-off and ahead of the loop by events
+            if (ls_stream_order(dev, st, sag_st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
+            if (ls_sag_decode_async(sag, B, h->origin_x.f(), tx + (size_t)w * B * kD, static_cast<const unsigned char*>(h->lg_mask.p), h->lg_init.f()) != LS_OK)
+                return fail(h, LS_EHIP, "SAG decode of window %d: %s", w, ls_sag_last_error(sag));
+            if (ls_stream_order(dev, sag_st, st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
+        }
+        if (tape) { wa.x_init = xs + (size_t)w * nelem; wa.eps_tape = es + (size_t)w * ne; wa.noise_tape = ns + (size_t)w * nn; }
+        c = loop_call(h, &wa);
+        // begin_loop's advance_tags uploads call_host (24 bytes of pageable memory) as every ls_sample does: the runtime takes such a
+        // source into its staging memory before hipMemcpyAsync returns, which is what makes rewriting it for the next window safe.  It is
+        // the one host -> device copy per window; whether the runtime waits inside it is the runtime's business (not measured).
+        h->call_host = CallParams{a->seed, a->sample_offset + ((unsigned long long)w << 48), h->tag_base, 0u};
+        if ((rc = begin_loop(h, c, true)) != LS_OK) return rc;
+        if (w == 0) HIPCHK(h, hipEventRecord(h->ev[6], st));        // ev[0] is re-recorded by every window's begin_loop
+        if ((rc = stage_loop_inputs(h, c)) != LS_OK) return rc;
+        if (w == 0) HIPCHK(h, hipEventRecord(h->ev[1], st));
+        if ((rc = run_loop(h, c, &replayed)) != LS_OK) return rc;
+        replays += replayed;
+    }
+    HIPCHK(h, hipEventRecord(h->ev[2], st));
+    if (!od) {
+        if ((rc = egress(h, a->timeline, tl, (size_t)B * JF * Tt * sizeof(float), 0)) != LS_OK) return rc;
+        if (wd && (rc = egress(h, a->windows, wd, W * nx, 0)) != LS_OK) return rc;
+    }
+    HIPCHK(h, hipEventRecord(h->ev[3], st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if ((rc = coop_check(h)) != LS_OK) return rc;
+    report_path(h, c.pair);
+    HIPCHK(h, hipEventElapsedTime(&h->timing.loop_ms, h->ev[1], h->ev[2]));
+    HIPCHK(h, hipEventElapsedTime(&h->timing.total_ms, h->ev[6], h->ev[3]));
+    h->timing.n_step_launches = W * n_exec;
+    h->timing.single_pass = c.pair ? 1 : 0;
+    h->timing.graph_replayed = replays;          // windows served by a replay: W - 1 after a capture, W on a warm handle
+    h->timing.tape_upload_ms = 0.f;
+    h->timing.n_segments = W;
+    return LS_OK;
+}
+
 // One plms_sample (gaussian_diffusion.py:1016-1098): the launches an LS_SAMPLER_PLMS loop makes for that step, on caller-held tensors.
 int ls_plms_step(ls_handle* h, const ls_plms_step_args* a) {
     if (!h || !a) return fail(h, LS_EINVAL, "ls_plms_step: null argument");

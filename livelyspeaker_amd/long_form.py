@@ -1,0 +1,202 @@
+"""Long-form synthesis: 34-frame windows chained on the device into one stitched timeline.
+
+The RAG denoiser is built to be continued: ``origin_x[..., :n_pre_seq]`` (RAG.py:110-112), the indicator bit ``InputProcess`` appends
+and the SAG decoder's ``n_pre_poses`` exist so that the last four poses of one clip condition the next.  ``sample_long`` runs that
+chain as ONE engine call (``ls_long_prepare`` + ``ls_long_sample``):
+
+* window ``w`` reads ``audio[:, w * AUDIO_STRIDE : w * AUDIO_STRIDE + audio_len]`` (32000 samples = 30 frames at 15 fps of 16 kHz
+  audio); the whole waveform goes through the WavEncoder once, in chunks of ``encoder_chunk`` clip-windows;
+* window 0 is conditioned on ``seed_poses``, window ``w >= 1`` on ``sample_{w-1}[..., T - n_pre : T]``; the hand-off
+  (``k_chain_window``, csrc/ls_chain.hip) happens on the device, the host neither copies nor waits between windows;
+* window 0 contributes its 34 frames to the timeline, every later window its frames ``n_pre..33``.
+
+With ``noise_source='torch_cpu'`` the draws are those ``GaussianDiffusion._loop`` makes for one call, window after window, and the
+result is bit for bit what the same windows give through ``ddim_sample_loop`` / ``p_sample_loop`` (and ``Decoder_TRANSFORMER.forward``
+with ``sag``) called once per window with ``origin_x`` rebuilt in between (tests/test_gpu_long_form.py).  ``'philox'`` draws one key per
+call; the window index is folded into the Philox counter (csrc/ls_philox.h).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch as th
+
+from . import _lib
+from . import gaussian_diffusion as gd
+
+AUDIO_STRIDE = 32000        # audio samples between two windows: T - n_pre_seq = 30 frames at 15 fps of 16 kHz audio
+_UNSUPPORTED = ("const_noise", "dump_steps", "inpainting_mask", "inpainted_motion")
+
+
+def plan_windows(n_audio_samples, cfg):
+    """(W, padded_len, n_frames) for a waveform of ``n_audio_samples`` samples: the windows that cover it, the length it is zero-padded
+    to, the frames of the stitched timeline.  ``cfg``: anything with audio_len / nframes / n_pre_seq (synth.PathConfig, RAG)."""
+    L, AL = int(n_audio_samples), int(cfg.audio_len)
+    if L < 1:
+        raise ValueError(f"the waveform holds no sample ({L})")
+    W = max(1, -(-(L - AL) // AUDIO_STRIDE) + 1)
+    return (W,) + _window_sizes(W, cfg)
+
+
+def _window_sizes(W, cfg):
+    T, npre = int(cfg.nframes), int(cfg.n_pre_seq)
+    return int(cfg.audio_len) + (W - 1) * AUDIO_STRIDE, T + (W - 1) * (T - npre)
+
+
+def window_audio(audio, w, cfg):
+    """The ``[B, audio_len]`` waveform window ``w`` reads, zero-padded at the end where ``audio`` [B, L] runs out."""
+    AL, lo = int(cfg.audio_len), int(w) * AUDIO_STRIDE
+    if w < 0:
+        raise ValueError(f"window index {w}")
+    piece = audio[:, lo:lo + AL]
+    short = AL - int(piece.shape[1])
+    if short <= 0:
+        return piece
+    if isinstance(audio, np.ndarray):
+        return np.concatenate([piece, np.zeros((audio.shape[0], short), audio.dtype)], axis=1)
+    return th.cat([piece, piece.new_zeros((audio.shape[0], short))], dim=1)
+
+
+def _shape(a):
+    return tuple(int(s) for s in a.shape)
+
+
+def _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, n_windows, sampler, skip_timesteps, sag, text_features,
+                encoder_chunk, unsupported):
+    """Everything that can be refused without an engine (no GPU is touched)."""
+    from .cfg_sampler import ClassifierFreeSampleModel
+    for k, v in unsupported.items():
+        if k not in _UNSUPPORTED:
+            raise TypeError(f"sample_long() got an unexpected keyword argument {k!r}")
+        if v is not None and v is not False:
+            raise NotImplementedError(f"sample_long: {k} is not built for chained windows")
+    if not isinstance(model, ClassifierFreeSampleModel):
+        raise TypeError(f"sample_long: pass livelyspeaker_amd.ClassifierFreeSampleModel(RAG), got {type(model).__name__}")
+    if diffusion.noise_source == "torch_device":
+        raise NotImplementedError("sample_long: noise_source='torch_device' is not built for chained windows; use 'torch_cpu' or 'philox'")
+    if diffusion.noise_source not in ("torch_cpu", "philox"):
+        raise ValueError(f"noise_source {diffusion.noise_source!r}")
+    if sampler not in ("ddim", "ddpm"):
+        raise ValueError(f"sampler must be 'ddim' or 'ddpm', got {sampler!r}")
+    rag = model.model
+    if rag.nframes != 34:
+        raise NotImplementedError("sample_long chains the reference's 34-frame windows")
+    if audio.ndim != 2:
+        raise ValueError(f"audio must be [B, L], got {list(audio.shape)}")
+    B, L = _shape(audio)
+    if B < 1 or L < 1:
+        raise ValueError(f"audio must be [B, L] with B, L >= 1, got {[B, L]}")
+    W = plan_windows(L, rag)[0] if n_windows is None else int(n_windows)
+    if W < 1:
+        raise ValueError(f"n_windows must be >= 1, got {n_windows}")
+    if seed_poses.ndim != 4 or _shape(seed_poses) != (B, rag.njoints, rag.nfeats, rag.n_pre_seq):
+        raise ValueError(f"seed_poses must be {[B, rag.njoints, rag.nfeats, rag.n_pre_seq]}, got {list(seed_poses.shape)}")
+    if vid_indices.ndim != 1 or _shape(vid_indices) != (B,):
+        raise ValueError(f"vid_indices must be [{B}], got {list(vid_indices.shape)}")
+    if scale.ndim != 1 or _shape(scale) != (B,):
+        raise ValueError(f"scale must be [{B}], got {list(scale.shape)}")
+    if rag.n_prefix_tokens == 2:
+        if emo is None:
+            raise ValueError("the BEAT model needs emo: [B] (one id per clip) or [B, W] (one per window)")
+        if emo.ndim not in (1, 2) or _shape(emo) not in ((B,), (B, W)):
+            raise ValueError(f"emo must be [{B}] or [{B}, {W}], got {list(emo.shape)}")
+    elif emo is not None:
+        raise ValueError("emo is a BEAT conditioning; the TED model takes none")
+    if text_features is not None and sag is None:
+        raise ValueError("text_features without sag: the SAG decoder turns them into every window's init_image")
+    if sag is not None:
+        if text_features is None:
+            raise ValueError("sag needs text_features [B, W, 512]")
+        if text_features.ndim != 3 or _shape(text_features) != (B, W, rag.latent_dim):
+            raise ValueError(f"text_features must be {[B, W, rag.latent_dim]}, got {list(text_features.shape)}")
+        if (sag.njoints, sag.nfeats, sag.num_frames, sag.n_pre_poses) != (rag.njoints, rag.nfeats, rag.nframes, rag.n_pre_seq):
+            raise ValueError("the SAG decoder's (njoints, nfeats, num_frames, n_pre_poses) do not match the RAG model's")
+    if not 0 <= int(skip_timesteps) < diffusion.num_timesteps:
+        raise ValueError(f"skip_timesteps {skip_timesteps} outside [0, {diffusion.num_timesteps})")
+    if encoder_chunk is not None and int(encoder_chunk) < 1:
+        raise ValueError(f"encoder_chunk must be >= 1, got {encoder_chunk}")
+    return B, W
+
+
+def _host_tapes(diffusion, W, n_exec, shape, D):
+    """The torch_cpu draws of W calls of GaussianDiffusion._loop, in its order: per window randn(*shape), then per step the style eps
+    of the cond and the uncond pass and randn_like(x) in x's memory order (contiguous at a window's first step, [T][B][J][F] afterwards).
+    Natively from torch's generator state when _loop would (same values, same final state)."""
+    from . import torch_rng
+    B = shape[0]
+    x = th.empty((W,) + shape)
+    eps = th.empty(W, n_exec, 2, B, D)
+    nz = th.empty((W, n_exec) + shape)
+    intercepted = th.randn is not gd._TH_RANDN or th.randn_like is not gd._TH_RANDN_LIKE
+    native = torch_rng.variant() if (diffusion.native_host_rng and not intercepted) else -1
+    diffusion.last_host_rng_native = native >= 0
+    first_proto = th.empty(shape)
+    later_proto = th.empty(shape[3], shape[0], shape[1], shape[2]).permute(1, 2, 3, 0)
+    for w in range(W):
+        x[w] = th.randn(*shape)
+        if native >= 0:
+            torch_rng.fill_steps(eps[w], nz[w], True, native)
+            continue
+        for k in range(n_exec):
+            eps[w, k, 0] = th.randn(B, 1, D)[:, 0]
+            eps[w, k, 1] = th.randn(B, 1, D)[:, 0]
+            nz[w, k].copy_(th.randn_like(first_proto if k == 0 else later_proto, dtype=th.float32))
+    return x, eps, nz
+
+
+def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=None, n_windows=None, sampler='ddim', skip_timesteps=0,
+                eta=0.0, clip_denoised=False, sag=None, text_features=None, encoder_chunk=None, return_windows=False, **unsupported):
+    """``n_windows`` chained windows for ``audio`` [B, L] (default: the windows that cover it, ``plan_windows``) as one timeline
+    ``[B, J, F, T + (W - 1) * (T - n_pre)]`` on the inputs' device; ``return_windows=True`` adds the raw windows ``[W, B, J, F, T]``.
+
+    ``seed_poses`` [B, J, F, n_pre] condition window 0; ``vid_indices`` [B] and ``scale`` [B] hold for all windows; ``emo`` (BEAT) is
+    [B] or [B, W].  ``sampler``: 'ddim' (``eta``) or 'ddpm'; ``skip_timesteps`` as in the sample loops.  ``sag`` (a
+    ``Decoder_TRANSFORMER``) with ``text_features`` [B, W, 512] is the LivelySpeaker chain: window w starts from
+    ``sag({'x': origin_x_w, 'z': text_features[:, w], 'mask': ones})['output']`` as its ``init_image``.  The noise source is the
+    diffusion object's (``'torch_cpu'`` or ``'philox'``); ``const_noise``, ``dump_steps`` and the inpainting inputs are refused."""
+    as_t = lambda a: a if (a is None or th.is_tensor(a)) else th.as_tensor(np.asarray(a))      # noqa: E731
+    audio, seed_poses, vid_indices, scale, emo, text_features = (as_t(a) for a in (audio, seed_poses, vid_indices, scale, emo, text_features))
+    B, W = _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, n_windows, sampler, skip_timesteps, sag, text_features,
+                       encoder_chunk, unsupported)
+    if diffusion.model_mean_type != gd.ModelMeanType.START_X or diffusion.model_var_type != gd.ModelVarType.FIXED_SMALL:
+        raise NotImplementedError("only START_X + FIXED_SMALL (create_gaussian_diffusion's setting) is built")
+    rag = model.model
+    if rag.cond_mask_prob <= 0:
+        raise ValueError("ClassifierFreeSampleModel returns None when cond_mask_prob == 0 (cfg_sampler.py:24-31)")
+    out_dev = audio.device
+    eng = rag.engine()
+    key = (id(diffusion), diffusion.num_timesteps)
+    if getattr(eng, "_sched_key", None) != key:
+        eng.set_schedule(diffusion)
+        eng._sched_key = key
+    rag._cond_key = rag._prefetched_key = None        # the engine's resident conditioning is this call's from here on
+    if emo is not None:
+        emo = (emo[None, :].expand(W, B) if emo.ndim == 1 else emo.t()).contiguous()
+    eng.long_prepare(audio.float(), seed_poses.float(), vid_indices, scale.float(), emo=emo, n_windows=W, encoder_chunk=encoder_chunk)
+    n_exec = diffusion.num_timesteps - int(skip_timesteps)
+    shape = (B, rag.njoints, rag.nfeats, rag.nframes)
+    kw = dict(sampler=_lib.LS_SAMPLER_DDIM if sampler == "ddim" else _lib.LS_SAMPLER_DDPM, skip_timesteps=int(skip_timesteps),
+              eta=float(eta) if sampler == "ddim" else 0.0, use_graph=diffusion.use_graph, clip_denoised=clip_denoised,
+              two_pass_always=diffusion.two_pass_always, device_out=out_dev.type == "cuda", return_windows=return_windows)
+    if sag is not None:
+        sag_eng = sag.engine()
+        if sag_eng.device != eng.device:
+            raise ValueError(f"the SAG decoder runs on cuda:{sag_eng.device}, the RAG model on cuda:{eng.device}")
+        kw["sag"] = sag_eng
+        kw["text_features"] = text_features.float().permute(1, 0, 2).contiguous()
+    if diffusion.noise_source == "philox":
+        drawn = int(th.randint(0, 2 ** 62, (1,)).item())
+        diffusion.last_philox_seed = drawn if diffusion.philox_seed is None else int(diffusion.philox_seed)
+        kw["philox_seed"] = diffusion.last_philox_seed
+        kw["sample_offset"] = int(getattr(diffusion, "sample_offset", 0))
+    else:
+        per_window = n_exec * (2 * B * eng.D + int(np.prod(shape))) * 4
+        if per_window > diffusion.tape_segment_bytes:
+            raise ValueError(f"sample_long: one window's noise tape is {per_window} bytes, tape_segment_bytes is "
+                             f"{diffusion.tape_segment_bytes}; segmented tapes are not built for chained windows (raise "
+                             "tape_segment_bytes or use noise_source='philox')")
+        kw["x_init"], kw["eps_tape"], kw["noise_tape"] = _host_tapes(diffusion, W, n_exec, shape, eng.D)
+        diffusion.last_tape_segments = 1
+    res = eng.long_sample(**kw)
+    timeline, windows = res if return_windows else (res, None)
+    timeline = gd._as_tensor(timeline, out_dev)
+    return (timeline, gd._as_tensor(windows, out_dev)) if return_windows else timeline

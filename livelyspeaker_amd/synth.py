@@ -144,6 +144,20 @@ def make_cond(cfg: PathConfig, batch: int, seed: int = SEED_COND, scale: float =
     return y
 
 
+def make_long_cond(cfg: PathConfig, batch: int, n_windows: int, seed: int = SEED_COND + 4000, scale: float = 1.5) -> dict:
+    """Synthetic inputs of a long-form call (long_form.sample_long): a waveform that covers ``n_windows`` windows exactly
+    (audio_len + (W - 1) * 32000 samples), the seed poses of window 0, speakers, guidance scales and (BEAT) one emotion id per window."""
+    g = _rng(seed)
+    n_audio = cfg.audio_len + (n_windows - 1) * 32000
+    y = {"audio": _f32(0.1 * g.standard_normal((batch, n_audio))),
+         "seed_poses": _f32(0.3 * g.standard_normal((batch, cfg.njoints, cfg.nfeats, cfg.n_pre_seq))),
+         "vid_indices": g.integers(0, 1370 if cfg.name == "ted" else 30, size=(batch,)).astype(np.int64),
+         "scale": np.full((batch,), scale, dtype=np.float32)}
+    if cfg.n_emotions:
+        y["emo"] = g.integers(0, cfg.n_emotions, size=(batch, n_windows)).astype(np.int64)
+    return y
+
+
 def make_init_image(cfg: PathConfig, batch: int, seed: int = SEED_COND + 1000) -> np.ndarray:
     """Stand-in for the SAG decoder output (config 3 until the SAG row is built)."""
     g = _rng(seed)
