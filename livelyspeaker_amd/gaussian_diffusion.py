@@ -15,7 +15,7 @@ C-ABI; the loops below just draw noise in the reference's order and hand the who
 ``ls_sample`` (a captured hipGraph of step-kernel launches).
 
 RNG contract ("identical seeds"): with ``noise_source='torch_cpu'`` (default) every
-draw the reference would make is made here from torch's CPU generator, in the same order and
+draw the reference would make is made (by ref_draws.py, the one statement of that order) from torch's CPU generator, in the same order and
 shape -- ``randn(*shape)`` once, then per step ``randn(B,1,512)`` x2 (style eps of the cond and
 uncond passes) and ``randn_like(x)`` with x's strides (contiguous at the first step, [T][B][J][F] memory
 order afterwards) -- so ``torch.manual_seed(s)`` reproduces the reference's CPU-path samples (fixture G7).  ``noise_source='torch_device'``
@@ -34,7 +34,7 @@ import time
 import numpy as np
 import torch as th
 
-from . import _lib
+from . import _lib, ref_draws
 
 _TH_RANDN, _TH_RANDN_LIKE = th.randn, th.randn_like      # as imported: a caller (or test) that replaces them wants to see every draw
 
@@ -193,7 +193,7 @@ class GaussianDiffusion:
     # ------------------------------------------------------------------ elementwise helpers
     def q_sample(self, x_start, t, noise=None):
         if noise is None:
-            noise = th.randn_like(x_start)
+            noise = ref_draws.RefDraws(x_start.device).like(x_start, x_start.dtype)
         assert noise.shape == x_start.shape
         return (_extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
                 + _extract_into_tensor(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
@@ -225,12 +225,47 @@ class GaussianDiffusion:
             raise ValueError("ClassifierFreeSampleModel returns None when cond_mask_prob == 0 (cfg_sampler.py:24-31)")
         if not model_kwargs or 'y' not in model_kwargs:
             raise ValueError("model_kwargs={'y': {...}} is required")
-        eng = model.model._engine_prepared(model_kwargs['y'])
+        return self._bind_schedule(model.model._engine_prepared(model_kwargs['y']))
+
+    def _bind_schedule(self, eng):
+        """Hand this object's tables to the engine unless they are the ones it holds."""
         key = (id(self), self.num_timesteps)
         if getattr(eng, "_sched_key", None) != key:
             eng.set_schedule(self)
             eng._sched_key = key
         return eng
+
+    def _check_noise_source(self):
+        if self.noise_source not in ("torch_cpu", "torch_device", "philox"):
+            raise ValueError(f"noise_source {self.noise_source!r}")
+
+    @staticmethod
+    def _prepared_shape(eng, shape, what="shape"):
+        assert isinstance(shape, (tuple, list))
+        shape = tuple(int(s) for s in shape)
+        if shape != (eng.batch, eng.J, eng.F, eng.T):
+            raise ValueError(f"{what} {shape} does not match the prepared conditioning {(eng.batch, eng.J, eng.F, eng.T)}")
+        return shape
+
+    def _philox_key(self):
+        """philox mode: one 62-bit key per call from torch's generator (torch.manual_seed reproduces a run) -- drawn also when
+        `philox_seed` pins the key instead (replaying a call, e.g. a shard of a multi-GPU batch on another GPU), so the generator moves
+        the same either way; the key used is kept for checkers.  Returns the engine's two keyword arguments."""
+        drawn = ref_draws.philox_key()
+        self.last_philox_seed = drawn if self.philox_seed is None else int(self.philox_seed)
+        return {"philox_seed": self.last_philox_seed, "sample_offset": int(getattr(self, "sample_offset", 0))}
+
+    @staticmethod
+    def _dump_steps(dump_steps, n_exec):
+        """(were dumps asked for, the steps to dump): the reference appends pred_xstart whenever the loop counter is `in dump_steps`
+        (gaussian_diffusion.py:660-671) -- execution order, duplicates and out-of-range entries have no effect."""
+        return dump_steps is not None, (sorted({int(d) for d in dump_steps if 0 <= int(d) < n_exec}) if dump_steps else None)
+
+    @staticmethod
+    def _loop_result(res, want_dumps, dump_steps, device):
+        if want_dumps:
+            return [_as_tensor(d, device).clone() for d in res[1]] if dump_steps else []
+        return _ref_strides(_as_tensor(res, device))
 
     @staticmethod
     def _inpainting(model, model_kwargs, shape):
@@ -271,8 +306,8 @@ class GaussianDiffusion:
             if not bool((t_host == t_host[0]).all()):
                 raise NotImplementedError("nframes != 34 runs on the batch-level kernels, which take ONE timestep for the batch")
             index = int(t_host[0])
-        eps_c = th.randn(B, 1, eng.D, device=rdev)           # cond pass reparameterize (RAG.py:12), then uncond pass
-        eps_u = th.randn(B, 1, eng.D, device=rdev)
+        draws = ref_draws.RefDraws(rdev)
+        eps_c, eps_u = draws.pair(B, eng.D)                   # the model call's style eps: cond pass, then uncond pass
         inp = self._inpainting(model, model_kwargs, tuple(x.shape))
         inp_arg = None
         if inp is not None:
@@ -280,13 +315,13 @@ class GaussianDiffusion:
             t_host = t.detach().cpu()
             if not bool((t_host == t_host[0]).all()):
                 raise NotImplementedError("the inpainting branch tests t[0] only (gaussian_diffusion.py:318): pass one timestep for the batch")
-            inz = th.randn_like(inp[1], device=rdev, dtype=th.float32) if (inp[2] and int(t_host[0]) > 0) else None
+            inz = draws.like(inp[1]) if (inp[2] and int(t_host[0]) > 0) else None
             inp_arg = (inp[0], inp[1], inz)
             t = t_host
         if mean_only:
             noise = th.zeros(tuple(x.shape), dtype=th.float32, device=rdev)
         else:
-            noise = th.randn_like(x, device=rdev, dtype=th.float32)    # follows x's strides like the reference's randn_like(x)
+            noise = draws.like(x)                           # follows x's strides like the reference's randn_like(x)
             if const_noise:
                 noise = noise[[0]].repeat(B, 1, 1, 1)
         dev = x.device
@@ -405,7 +440,8 @@ class GaussianDiffusion:
             index = int(t_host[0])
         if first and index < 1:
             raise ValueError("plms_sample without old_out evaluates the model at t - 1: t must be >= 1")
-        draws = [th.randn(B, 1, eng.D, device=rdev) for _ in range(4 if first else 2)]     # (cond, uncond) per evaluation, in order
+        rd = ref_draws.RefDraws(rdev)
+        draws = [e for _ in range(2 if first else 1) for e in rd.pair(B, eng.D)]     # (cond, uncond) per evaluation, in order
         if x.is_cuda and not tdev:
             draws = self._stage_step_draws(x.device, *draws)
         out, x0, eps = eng.plms_step(index, order, x, (draws[0], draws[1]), hist=old_eps[-3:], eps2=(draws[2], draws[3]) if first else None,
@@ -416,32 +452,6 @@ class GaussianDiffusion:
             old_eps.pop(0)
         return {"sample": _ref_strides(_as_tensor(out, dev)), "pred_xstart": _ref_strides(_as_tensor(x0, dev)), "old_eps": old_eps}
 
-    def _plms_progressive(self, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image, order):
-        if device is None:
-            device = next(model.parameters()).device
-        if self.noise_source == "torch_device":
-            device = _torch_device(device, "sample loop")
-        if noise is not None:
-            img = noise
-        elif self.noise_source == "torch_device":
-            img = th.randn(*shape, device=device)
-        else:
-            img = th.randn(*shape)
-        img = img.to(device)
-        if skip_timesteps and init_image is None:
-            init_image = th.zeros_like(img)
-        indices = list(range(self.num_timesteps - skip_timesteps))[::-1]
-        if init_image is not None:
-            eng = self._engine_for(model, model_kwargs, "sample loop")
-            img = _as_tensor(eng.q_sample(indices[0], _as_tensor(init_image, img.device).float().contiguous(), img.float().contiguous()), img.device)
-        old_out = None
-        for i in indices:
-            t = th.full((shape[0],), i, dtype=th.long)
-            out = self.plms_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, order=order, old_out=old_out, index=i)
-            yield out
-            old_out = out
-            img = out["sample"]
-
     def plms_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
                                      randomize_class=False, cond_fn_with_grad=False, order=2):
@@ -449,7 +459,9 @@ class GaussianDiffusion:
         order = self._plms_order(order, True, self.num_timesteps - skip_timesteps)
         shape, model_kwargs = self._progressive_args(model, shape, denoised_fn, cond_fn, model_kwargs, randomize_class, cond_fn_with_grad)
         self._no_inpainting(model_kwargs, "plms_sample_loop_progressive")
-        return self._plms_progressive(model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image, order)
+        def step(img, t, i, old_out):
+            return self.plms_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, order=order, old_out=old_out, index=i)
+        return self._progressive(step, model, shape, noise, model_kwargs, device, skip_timesteps, init_image)
 
     def plms_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,
                          device=None, progress=False, skip_timesteps=0, init_image=None, randomize_class=False,
@@ -461,16 +473,12 @@ class GaussianDiffusion:
         order = self._plms_order(order, True, n_exec)
         self._reject(denoised_fn, cond_fn, randomize_class, cond_fn_with_grad)
         self._no_inpainting(model_kwargs, "plms_sample_loop")
-        if self.noise_source not in ("torch_cpu", "torch_device", "philox"):
-            raise ValueError(f"noise_source {self.noise_source!r}")
+        self._check_noise_source()
         tdev = self.noise_source == "torch_device"
         if tdev:                                    # refused before the engine is touched
             _torch_device(device if device is not None else next(model.parameters()).device, "sample loop")
         eng = self._engine_for(model, model_kwargs, "sample loop")
-        assert isinstance(shape, (tuple, list))
-        shape = tuple(int(v) for v in shape)
-        if shape != (eng.batch, eng.J, eng.F, eng.T):
-            raise ValueError(f"shape {shape} does not match the prepared conditioning {(eng.batch, eng.J, eng.F, eng.T)}")
+        shape = self._prepared_shape(eng, shape)
         if device is None:
             device = next(model.parameters()).device
         B, D, n_eval = shape[0], eng.D, n_exec + 1
@@ -478,10 +486,7 @@ class GaussianDiffusion:
                   use_graph=self.use_graph, clip_denoised=clip_denoised, two_pass_always=self.two_pass_always,
                   device_out=th.device(device).type == "cuda")
         if self.noise_source == "philox":
-            drawn = int(th.randint(0, 2 ** 62, (1,)).item())
-            self.last_philox_seed = drawn if self.philox_seed is None else int(self.philox_seed)
-            kw["philox_seed"] = self.last_philox_seed
-            kw["sample_offset"] = int(getattr(self, "sample_offset", 0))
+            kw.update(self._philox_key())
         else:
             tape_bytes = n_eval * 2 * B * D * 4
             if tape_bytes > self.tape_segment_bytes:
@@ -494,13 +499,10 @@ class GaussianDiffusion:
                 if rdev.index != eng.device:
                     raise ValueError(f"noise_source='torch_device': the model's engine runs on cuda:{eng.device}, the draws would come from {rdev}")
                 self.last_device_rng_native = False     # torch's own device draws, handed in as a device tape
+            draws = ref_draws.RefDraws(rdev)
             if noise is None:
-                kw["x_init"] = th.randn(*shape, device=rdev)
-            eps = th.empty(n_eval, 2, B, D, device=rdev)
-            for e in range(n_eval):                 # ClassifierFreeSampleModel: cond pass, then uncond pass (RAG.py:10-13)
-                eps[e, 0] = th.randn(B, 1, D, device=rdev)[:, 0]
-                eps[e, 1] = th.randn(B, 1, D, device=rdev)[:, 0]
-            kw["eps_tape"] = eps
+                kw["x_init"] = draws.x_T(shape)
+            kw["eps_tape"] = draws.plms_tape(n_eval, B, D)
             self.last_tape_segments = 1
         res = eng.sample(**kw)
         return _ref_strides(_as_tensor(res, device))
@@ -537,31 +539,6 @@ class GaussianDiffusion:
                                    indices=t.detach() if (t.is_cuda and x_t.is_cuda) else t.detach().cpu())
         return {"output": _as_tensor(vb, dev), "pred_xstart": out["pred_xstart"]}
 
-    def _bpd_host_draws(self, nz, eps, proto):
-        """The torch_cpu draws of nz.shape[0] columns of calc_bpd_loop, in the reference's order per column (:1617, then RAG.py:10-13):
-        randn_like(x_start), randn(B, 1, D) of the cond pass, of the uncond pass.  Natively (ls_trng_randn continues torch's CPU
-        stream and hands the advanced state back) when the restatement reproduces this torch build, x_start is contiguous and nobody
-        has replaced torch's draw functions; with torch's own calls otherwise.  Either way the generator ends where the reference's does."""
-        from . import torch_rng
-        n, B, D = nz.shape[0], eps.shape[2], eps.shape[3]
-        intercepted = th.randn is not _TH_RANDN or th.randn_like is not _TH_RANDN_LIKE
-        native = torch_rng.variant() if (self.native_host_rng and proto.is_contiguous() and not intercepted) else -1
-        self.last_host_rng_native = native >= 0
-        if native >= 0:
-            lib = _lib.load_library()
-            st = th.get_rng_state()
-            for r in range(n):
-                for dst in (nz[r], eps[r, 0], eps[r, 1]):
-                    rc = lib.ls_trng_randn(st.data_ptr(), st.numel(), dst.data_ptr(), dst.numel(), int(native), torch_rng.n_threads())
-                    if rc != 0:
-                        raise _lib.EngineError(f"ls_trng_randn failed ({rc})")
-            th.set_rng_state(st)
-            return
-        for r in range(n):
-            nz[r].copy_(th.randn_like(proto, dtype=th.float32))
-            eps[r, 0] = th.randn(B, 1, D)[:, 0]
-            eps[r, 1] = th.randn(B, 1, D)[:, 0]
-
     def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None):
         """The whole variational bound in bits per dimension and its per-timestep terms (gaussian_diffusion.py:1591-1646) as one device
         loop (ls_bpd): per schedule index T-1 .. 0 a q_sample, one CFG-guided model evaluation and the per-sample reduction k_vb_terms,
@@ -569,15 +546,12 @@ class GaussianDiffusion:
         on x_start's device.  noise_source 'torch_cpu' makes the reference's draws from torch's CPU generator (tapes larger than
         tape_segment_bytes go through in column segments), 'philox' draws on the device; 'torch_device' is not built for this loop."""
         self._no_inpainting(model_kwargs, "calc_bpd_loop")
-        if self.noise_source not in ("torch_cpu", "torch_device", "philox"):
-            raise ValueError(f"noise_source {self.noise_source!r}")
+        self._check_noise_source()
         if self.noise_source == "torch_device":
             raise NotImplementedError("calc_bpd_loop: noise_source='torch_device' is not built for the likelihood loop; use "
                                       "'torch_cpu' (the reference's CPU draws) or 'philox'")
         eng = self._engine_for(model, model_kwargs, "calc_bpd_loop")
-        shape = tuple(int(s) for s in x_start.shape)
-        if shape != (eng.batch, eng.J, eng.F, eng.T):
-            raise ValueError(f"x_start's shape {shape} does not match the prepared conditioning {(eng.batch, eng.J, eng.F, eng.T)}")
+        shape = self._prepared_shape(eng, x_start.shape, "x_start's shape")
         device = x_start.device
         B, D, T = shape[0], eng.D, self.num_timesteps
         x0 = x_start.detach().float()
@@ -587,19 +561,16 @@ class GaussianDiffusion:
             outs = tuple(np.empty((B, T), np.float32) for _ in range(3))
         kw = dict(clip_denoised=clip_denoised, two_pass_always=self.two_pass_always)
         if self.noise_source == "philox":
-            drawn = int(th.randint(0, 2 ** 62, (1,)).item())
-            self.last_philox_seed = drawn if self.philox_seed is None else int(self.philox_seed)
-            eng.bpd(x0, outs, philox_seed=self.last_philox_seed, sample_offset=int(getattr(self, "sample_offset", 0)),
-                    use_graph=self.use_graph, **kw)
+            eng.bpd(x0, outs, use_graph=self.use_graph, **self._philox_key(), **kw)
             self.last_tape_segments = 1
         else:
             per_col = (2 * B * D + int(np.prod(shape))) * 4
             K = T if per_col * T <= self.tape_segment_bytes else max(1, min(T, self.tape_segment_bytes // per_col))
             proto = th.empty_strided(shape, x_start.stride())       # randn_like(x_start) follows x_start's memory order
-            nz, eps = th.empty((K,) + shape), th.empty(K, 2, B, D)
+            nz, eps, draws = th.empty((K,) + shape), th.empty(K, 2, B, D), ref_draws.RefDraws("cpu")
             for k0 in range(0, T, K):
                 n = min(K, T - k0)
-                self._bpd_host_draws(nz[:n], eps[:n], proto)
+                draws.bpd_columns(self, nz[:n], eps[:n], proto)
                 # columns are independent: a segment is the same launches over its own columns (plain launches unless it is the whole loop)
                 eng.bpd(x0, outs, columns=(k0, n), noise_tape=nz[:n], eps_tape=eps[:n], use_graph=self.use_graph and K == T, **kw)
             self.last_tape_segments = -(-T // K)
@@ -611,150 +582,93 @@ class GaussianDiffusion:
     # ------------------------------------------------------------------ loops
     def _loop(self, sampler, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image,
               dump_steps, const_noise, eta):
-        if self.noise_source == "torch_device":     # refused before the engine is touched
+        tdev, philox = self.noise_source == "torch_device", self.noise_source == "philox"
+        if tdev:                                    # refused before the engine is touched
             _torch_device(device if device is not None else next(model.parameters()).device, "sample loop")
         eng = self._engine_for(model, model_kwargs, "sample loop")
-        assert isinstance(shape, (tuple, list))
-        shape = tuple(int(s) for s in shape)
-        if shape != (eng.batch, eng.J, eng.F, eng.T):
-            raise ValueError(f"shape {shape} does not match the prepared conditioning {(eng.batch, eng.J, eng.F, eng.T)}")
+        shape = self._prepared_shape(eng, shape)
         if device is None:
             device = next(model.parameters()).device
         n_exec = self.num_timesteps - skip_timesteps
-        B = shape[0]
-        philox = self.noise_source == "philox"
-        if self.noise_source not in ("torch_cpu", "torch_device", "philox"):
-            raise ValueError(f"noise_source {self.noise_source!r}")
-        if self.noise_source == "torch_device":
-            return self._loop_torch_device(eng, sampler, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps,
-                                           init_image, dump_steps, const_noise, eta)
-        x_init = None
-        if noise is not None:
-            x_init = noise
-        elif not philox:
-            x_init = th.randn(*shape)
-            if const_noise:
-                x_init = x_init[[0]].repeat(B, 1, 1, 1)
-        # the reference appends pred_xstart whenever the loop counter is `in dump_steps` (gaussian_diffusion.py:660-671): execution
-        # order, duplicates and out-of-range entries have no effect
-        want_dumps = dump_steps is not None
-        dump_steps = sorted({int(d) for d in dump_steps if 0 <= int(d) < n_exec}) if dump_steps else None
-        kw = dict(sampler=sampler, x_init=x_init, init_image=init_image, skip_timesteps=skip_timesteps, eta=eta,
-                  const_noise=const_noise, dump_steps=dump_steps or None,
-                  use_graph=self.use_graph, clip_denoised=clip_denoised)
+        self._check_noise_source()
+        # x of the first executed step is the caller's `noise`, strides included, when nothing is mixed into it before
+        first = noise if (noise is not None and init_image is None and not skip_timesteps) else None
+        kw = dict(sampler=sampler, init_image=init_image, skip_timesteps=skip_timesteps, eta=eta, const_noise=const_noise,
+                  clip_denoised=clip_denoised, two_pass_always=self.two_pass_always)
+        if tdev:
+            return self._loop_torch_device(eng, model, shape, noise, first, model_kwargs, device, n_exec, dump_steps, kw)
+        draws = ref_draws.RefDraws("cpu")
+        x_init = noise if (noise is not None or philox) else draws.x_T(shape, const_noise)
+        want_dumps, dump_steps = self._dump_steps(dump_steps, n_exec)
+        kw.update(x_init=x_init, dump_steps=dump_steps or None)
         inp = self._inpainting(model, model_kwargs, shape)
         if philox:
             if const_noise:
                 raise NotImplementedError("const_noise needs noise_source='torch_cpu'")
-            # one 62-bit key per call from torch's generator (torch.manual_seed reproduces a run); `philox_seed` pins it
-            # instead (replaying a call, e.g. a shard of a multi-GPU batch on another GPU); the key used is kept for checkers
-            drawn = int(th.randint(0, 2 ** 62, (1,)).item())
-            self.last_philox_seed = drawn if self.philox_seed is None else int(self.philox_seed)
-            kw["philox_seed"] = self.last_philox_seed
-            kw["sample_offset"] = int(getattr(self, "sample_offset", 0))
+            kw.update(self._philox_key())
             if inp is not None:
                 kw["inpaint"] = (inp[0], inp[1], None, inp[2])           # the re-noising draws come from the device stream too
         else:
-            # p_sample/ddim_sample draw `randn_like(x)` (gaussian_diffusion.py:543/787).  x is contiguous at the first
-            # executed step, but from then on it is the model-output-shaped view whose memory order is
-            # [T][B][J][F] (OutputProcess permutes, RAG.py:209-210), and randn_like preserves strides: the generator
-            # stream is consumed in MEMORY order through torch's non-contiguous CPU path.  Reproduce exactly that.
-            first_proto = noise.cpu() if (noise is not None and init_image is None and not skip_timesteps) else th.empty(shape)
-            later_proto = th.empty(shape[3], shape[0], shape[1], shape[2]).permute(1, 2, 3, 0)
-
-            inz = None
-            if inp is not None and inp[2]:
-                inz = th.zeros((n_exec,) + shape)   # q_sample(inpainted_motion, t - 1)'s randn_like, steps with t > 0 (:318)
-                inp_proto = inp[1].detach().cpu() if th.is_tensor(inp[1]) else th.empty(shape)
-
-            def draw(k, eps_k, nz_k):          # the reference's per-step draw order
-                eps_k[0] = th.randn(B, 1, eng.D)[:, 0]
-                eps_k[1] = th.randn(B, 1, eng.D)[:, 0]
-                if inz is not None and n_exec - 1 - k > 0:
-                    inz[k] = th.randn_like(inp_proto, dtype=th.float32)
-                nz_k.copy_(th.randn_like(first_proto if k == 0 else later_proto, dtype=th.float32))
-
-            # The same draws made natively from torch's generator state (torch_rng.py: mt19937 + torch's two normal transforms restated
-            # in C++, the transcendental part on worker threads) when the restatement reproduces this torch build bit for bit -- checked
-            # once per process -- and the loop draws nothing else in between (no inpainting draws, contiguous first x).
-            from . import torch_rng
-            intercepted = th.randn is not _TH_RANDN or th.randn_like is not _TH_RANDN_LIKE      # someone patched torch's draw functions
-            native = torch_rng.variant() if (self.native_host_rng and inz is None and first_proto.is_contiguous() and not intercepted) else -1
-            self.last_host_rng_native = native >= 0
-
-            def draw_steps(k0, eps_seg, nz_seg):            # steps k0 .. k0 + len(eps_seg) into (eps [n,2,B,D], noise [n,B,J,F,T])
-                if native >= 0:
-                    torch_rng.fill_steps(eps_seg, nz_seg, k0 == 0, native)
-                else:
-                    for r in range(eps_seg.shape[0]):
-                        draw(k0 + r, eps_seg[r], nz_seg[r])
-
+            steps = draws.steps(shape, eng.D, n_exec, first, inp[1] if (inp is not None and inp[2]) else None, diffusion=self)
             if inp is not None:
-                kw["inpaint"] = (inp[0], inp[1], inz, inp[2])
-            per_step = (2 * B * eng.D + int(np.prod(shape))) * 4
-            t_rng = 0.0
-            if per_step * n_exec > self.tape_segment_bytes and th.cuda.is_available() and n_exec > 1 and inp is None:
+                kw["inpaint"] = (inp[0], inp[1], steps.inz, inp[2])
+            if steps.per_step_bytes * n_exec > self.tape_segment_bytes and th.cuda.is_available() and n_exec > 1 and inp is None:
                 # 4 GB at 512 clips x 1000 steps if drawn in one piece: K-step segments through two page-locked buffers instead; the
                 # engine uploads segment i+1 on its copy stream while segment i's steps run (ls_sample_args.seg_begin / seg_count)
-                K = max(1, min(n_exec, self.tape_segment_bytes // (2 * per_step)))
-                ring = self._tape_ring(K, B, eng.D, shape)
-                kw.pop("use_graph")
+                K = max(1, min(n_exec, self.tape_segment_bytes // (2 * steps.per_step_bytes)))
                 kw["x_init"] = x_init.cpu() if th.is_tensor(x_init) else x_init
                 if th.is_tensor(init_image):
                     kw["init_image"] = init_image.detach().cpu()
-                kw["two_pass_always"] = self.two_pass_always
-                res = None
-                for si, k0 in enumerate(range(0, n_exec, K)):
-                    n = min(K, n_exec - k0)
-                    eps, nz = ring[si & 1]
-                    t0 = time.perf_counter()
-                    draw_steps(k0, eps[:n], nz[:n])
-                    t_rng += time.perf_counter() - t0
-                    res = eng.sample(eps_tape=eps[:n], noise_tape=nz[:n], segment=(k0, n), **kw)
-                self.last_host_rng_ms, self.last_tape_segments = t_rng * 1e3, -(-n_exec // K)
-                if want_dumps:
-                    return [_as_tensor(d, device).clone() for d in res[1]] if dump_steps else []
-                return _ref_strides(_as_tensor(res, device))
-            eps = th.empty(n_exec, 2, B, eng.D)
-            nz = th.empty((n_exec,) + shape)
+                res, t_rng = self._sample_segments(eng, kw, n_exec, K, self._tape_ring(K, shape[0], eng.D, shape), steps.run)
+                self.last_host_rng_ms = t_rng * 1e3
+                return self._loop_result(res, want_dumps, dump_steps, device)
+            eps, nz = steps.buffers(n_exec)
             t0 = time.perf_counter()
-            draw_steps(0, eps, nz)
+            steps.run(0, eps, nz)
             self.last_host_rng_ms, self.last_tape_segments = (time.perf_counter() - t0) * 1e3, 1
             kw["eps_tape"], kw["noise_tape"] = eps, nz
-        kw["two_pass_always"] = self.two_pass_always
-        kw["device_out"] = th.device(device).type == "cuda"
-        res = eng.sample(**kw)
-        if want_dumps:
-            return [_as_tensor(d, device).clone() for d in res[1]] if dump_steps else []
-        return _ref_strides(_as_tensor(res, device))
+        res = eng.sample(use_graph=self.use_graph, device_out=th.device(device).type == "cuda", **kw)
+        return self._loop_result(res, want_dumps, dump_steps, device)
 
-    def _loop_torch_device(self, eng, sampler, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image,
-                           dump_steps, const_noise, eta):
+    def _sample_segments(self, eng, kw, n_exec, K, bufs, draw, after=None):
+        """A TAPE-mode loop in K-step segments: segment i is drawn into bufs[i % len(bufs)] = (eps [K,2,B,D], noise [K,B,J,F,T]) by
+        draw(first step, eps, noise) and handed over as plain launches (no graph); `after` runs behind every hand-over.  Returns the last
+        segment's result and the seconds spent in the draws."""
+        res, t_rng = None, 0.0
+        for si, k0 in enumerate(range(0, n_exec, K)):
+            n = min(K, n_exec - k0)
+            eps, nz = bufs[si % len(bufs)]
+            t0 = time.perf_counter()
+            draw(k0, eps[:n], nz[:n])
+            t_rng += time.perf_counter() - t0
+            res = eng.sample(eps_tape=eps[:n], noise_tape=nz[:n], segment=(k0, n), **kw)
+            if after is not None:
+                after()
+        self.last_tape_segments = -(-n_exec // K)
+        return res, t_rng
+
+    def _loop_torch_device(self, eng, model, shape, noise, first, model_kwargs, device, n_exec, dump_steps, kw):
         """noise_source='torch_device': the draws of _loop's torch_cpu mode, same order, shapes and memory orders, from torch's generator
         of the model's GPU.  Natively (ls_sample TORCH_DEVICE: generated on the device inside the captured loop from the generator's
         (seed, offset), which is then set where the reference's draws leave it) when ls_torch_randn reproduces torch there and the
-        memory orders are the loop's usual ones; otherwise drawn with torch's device calls into device tapes."""
-        dev = _torch_device(device if device is not None else next(model.parameters()).device, "sample loop")
+        memory orders are the loop's usual ones; otherwise drawn with torch's own device calls (th.randn / randn_like as the module sees
+        them) into device tapes: one piece, or K-step segments of at most tape_segment_bytes through the segmented TAPE path."""
+        dev = _torch_device(device, "sample loop")
         if dev.index != eng.device:
             raise ValueError(f"noise_source='torch_device': the model's engine runs on cuda:{eng.device}, the draws would come from {dev}")
-        n_exec = self.num_timesteps - skip_timesteps
         B, D = shape[0], eng.D
         nelem = int(np.prod(shape))
-        want_dumps = dump_steps is not None
-        dump_steps = sorted({int(d) for d in dump_steps if 0 <= int(d) < n_exec}) if dump_steps else None
+        want_dumps, dump_steps = self._dump_steps(dump_steps, n_exec)
         inp = self._inpainting(model, model_kwargs, shape)
         inz_on = inp is not None and inp[2]
-        first_given = noise is not None and init_image is None and not skip_timesteps     # x of the first step is the caller's `noise`
         gen = th.cuda.default_generators[dev.index]
         seed, off0 = gen.initial_seed(), gen.get_offset()
-        intercepted = th.randn is not _TH_RANDN or th.randn_like is not _TH_RANDN_LIKE
-        native = (self.native_device_rng and not intercepted and off0 % 4 == 0
-                  and not (first_given and not noise.is_contiguous())
+        native = (self.native_device_rng and not ref_draws.intercepted() and off0 % 4 == 0
+                  and not (first is not None and not noise.is_contiguous())
                   and not (inz_on and th.is_tensor(inp[1]) and not inp[1].is_contiguous())
                   and _device_rng_check(eng, dev))
         self.last_device_rng_native = bool(native)
-        kw = dict(sampler=sampler, init_image=init_image, skip_timesteps=skip_timesteps, eta=eta, const_noise=const_noise,
-                  dump_steps=dump_steps or None, clip_denoised=clip_denoised, two_pass_always=self.two_pass_always, device_out=True)
+        kw = dict(kw, dump_steps=dump_steps or None, device_out=True)
         if native:
             props = th.cuda.get_device_properties(dev)
             adv = lambda n: _lib.torch_randn_advance(n, props.multi_processor_count, props.max_threads_per_multi_processor)    # noqa: E731
@@ -765,58 +679,24 @@ class GaussianDiffusion:
                      + (max(n_exec - 1, 0) * adv(nelem) if inz_on else 0))
             gen.set_offset(off0 + total)
             self.last_tape_segments = 1
-        else:
-            res = self._loop_torch_device_tape(eng, dev, shape, noise, init_image, skip_timesteps, const_noise, n_exec, inp, kw)
-        if want_dumps:
-            return [_as_tensor(d, dev).clone() for d in res[1]] if dump_steps else []
-        return _ref_strides(_as_tensor(res, dev))
-
-    def _loop_torch_device_tape(self, eng, dev, shape, noise, init_image, skip_timesteps, const_noise, n_exec, inp, kw):
-        """The torch_device draws made with torch's own device calls (th.randn / randn_like as the module sees them), in the reference's
-        order, into device tapes: one piece, or K-step segments of at most tape_segment_bytes through the segmented TAPE path."""
-        B, D = shape[0], eng.D
-        J, F, T = shape[1:]
-        x_init = noise
-        if x_init is None:
-            x_init = th.randn(*shape, device=dev)
-            if const_noise:
-                x_init = x_init[[0]].repeat(B, 1, 1, 1)
-        first_proto = noise if (noise is not None and init_image is None and not skip_timesteps) else th.empty(shape, device=dev)
-        later_proto = th.empty(T, B, J, F, device=dev).permute(1, 2, 3, 0)
-        inz = None
-        if inp is not None and inp[2]:
-            inz = th.zeros((n_exec,) + tuple(shape), device=dev)
-            inp_proto = inp[1] if th.is_tensor(inp[1]) else th.empty(shape, device=dev)
-
-        def draw(k, eps_k, nz_k):          # the reference's per-step draw order
-            eps_k[0] = th.randn(B, 1, D, device=dev)[:, 0]
-            eps_k[1] = th.randn(B, 1, D, device=dev)[:, 0]
-            if inz is not None and n_exec - 1 - k > 0:
-                inz[k] = th.randn_like(inp_proto, device=dev, dtype=th.float32)
-            nz_k.copy_(th.randn_like(first_proto if k == 0 else later_proto, device=dev, dtype=th.float32))
-
-        kw = dict(kw, x_init=x_init)
-        per_step = (2 * B * D + int(np.prod(shape))) * 4
-        if per_step * n_exec > self.tape_segment_bytes and n_exec > 1 and inp is None:
-            K = max(1, min(n_exec, self.tape_segment_bytes // per_step))
-            eps, nz = th.empty(K, 2, B, D, device=dev), th.empty((K,) + tuple(shape), device=dev)
-            res = None
-            for k0 in range(0, n_exec, K):
-                n = min(K, n_exec - k0)
-                for r in range(n):
-                    draw(k0 + r, eps[r], nz[r])
-                res = eng.sample(eps_tape=eps[:n], noise_tape=nz[:n], segment=(k0, n), **kw)
-                # the segment's copy of the tapes runs on the engine's stream: the next segment's draws (torch's stream) wait for it
+            return self._loop_result(res, want_dumps, dump_steps, dev)
+        draws = ref_draws.RefDraws(dev)
+        kw["x_init"] = noise if noise is not None else draws.x_T(shape, kw["const_noise"])
+        steps = draws.steps(shape, D, n_exec, first, inp[1] if inz_on else None)
+        if steps.per_step_bytes * n_exec > self.tape_segment_bytes and n_exec > 1 and inp is None:
+            K = max(1, min(n_exec, self.tape_segment_bytes // steps.per_step_bytes))
+            # the segment's copy of the tapes runs on the engine's stream: the next segment's draws (torch's stream) wait for it
+            def order():
                 _lib.load_library().ls_stream_order(eng.device, eng._stream, th.cuda.current_stream(dev).cuda_stream)
-            self.last_tape_segments = -(-n_exec // K)
-            return res
-        eps, nz = th.empty(n_exec, 2, B, D, device=dev), th.empty((n_exec,) + tuple(shape), device=dev)
-        for k in range(n_exec):
-            draw(k, eps[k], nz[k])
-        if inp is not None:
-            kw["inpaint"] = (inp[0], inp[1], inz, inp[2])
-        self.last_tape_segments = 1
-        return eng.sample(eps_tape=eps, noise_tape=nz, use_graph=self.use_graph, **kw)
+            res = self._sample_segments(eng, kw, n_exec, K, [steps.buffers(K)], steps.run, after=order)[0]
+        else:
+            eps, nz = steps.buffers(n_exec)
+            steps.run(0, eps, nz)
+            if inp is not None:
+                kw["inpaint"] = (inp[0], inp[1], steps.inz, inp[2])
+            self.last_tape_segments = 1
+            res = eng.sample(eps_tape=eps, noise_tape=nz, use_graph=self.use_graph, **kw)
+        return self._loop_result(res, want_dumps, dump_steps, dev)
 
     def _tape_ring(self, K, B, D, shape):
         """Two page-locked (eps [K,2,B,D], noise [K,B,J,F,T]) segments, kept between calls (pinning 100 MB takes tens of ms)."""
@@ -833,39 +713,41 @@ class GaussianDiffusion:
         return self._loop(_lib.LS_SAMPLER_DDPM, model, shape, noise, clip_denoised, model_kwargs, device,
                           skip_timesteps, init_image, dump_steps, const_noise, 0.0)
 
-    def _progressive(self, sampler, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device, skip_timesteps,
-                     init_image, randomize_class, cond_fn_with_grad, const_noise, eta):
-        """p_sample_loop_progressive / ddim_sample_loop_progressive (gaussian_diffusion.py:673-743, 945-1014): the same draws in the same
-        order as the reference's generator -- x_T, then per step what p_sample / ddim_sample draws -- one step-kernel launch per yield,
-        tensors device-resident when the model is (no host synchronisation between yields)."""
+    def _start_image(self, model, shape, noise, model_kwargs, device, skip_timesteps, init_image, const_noise):
+        """What a progressive generator starts from (gaussian_diffusion.py:700-716): `noise`, or x_T from torch's CPU generator like every
+        draw of this module ("identical seeds") -- torch_device: the device generator of the reference's GPU run -- and, with an
+        init_image, q_sample(init_image, indices[0], x_T) on the engine's elementwise kernel -- the one the whole-loop entry points use,
+        so a generator's yields are bitwise theirs."""
         if device is None:
             device = next(model.parameters()).device
-        if self.noise_source == "torch_device":
+        tdev = self.noise_source == "torch_device"
+        if tdev:
             device = _torch_device(device, "sample loop")
-        if noise is not None:
-            img = noise
-        elif self.noise_source == "torch_device":
-            img = th.randn(*shape, device=device)   # the reference's GPU run: torch's device generator
-            if const_noise:
-                img = img[[0]].repeat(img.shape[0], 1, 1, 1)
-        else:
-            img = th.randn(*shape)                  # torch's CPU generator, like every draw of this module ("identical seeds")
-            if const_noise:
-                img = img[[0]].repeat(img.shape[0], 1, 1, 1)
+        img = noise if noise is not None else ref_draws.RefDraws(device if tdev else "cpu").x_T(shape, const_noise)
         img = img.to(device)
         if skip_timesteps and init_image is None:
             init_image = th.zeros_like(img)
-        indices = list(range(self.num_timesteps - skip_timesteps))[::-1]
         if init_image is not None:
-            # q_sample(init_image, indices[0], img) on the engine's elementwise kernel -- the one the whole-loop entry points use, so a
-            # generator's yields are bitwise theirs
             eng = self._engine_for(model, model_kwargs, "sample loop")
-            img = _as_tensor(eng.q_sample(indices[0], _as_tensor(init_image, img.device).float().contiguous(), img.float().contiguous()), img.device)
-        for i in indices:
-            t = th.full((shape[0],), i, dtype=th.long)
-            out = self._one_step(sampler, model, img, t, clip_denoised, model_kwargs, eta, const_noise, None, None, index=i)
+            img = _as_tensor(eng.q_sample(self.num_timesteps - skip_timesteps - 1, _as_tensor(init_image, img.device).float().contiguous(),
+                                          img.float().contiguous()), img.device)
+        return img
+
+    def _progressive(self, step, model, shape, noise, model_kwargs, device, skip_timesteps, init_image, const_noise=False):
+        """The *_sample_loop_progressive generators (gaussian_diffusion.py:673-743, 945-1014, 1142-1211): the same draws in the same order
+        as the reference's generator -- x_T, then per step what step(x, t, index, previous yield) draws -- one step launch per yield,
+        tensors device-resident when the model is (no host synchronisation between yields)."""
+        img, out = self._start_image(model, shape, noise, model_kwargs, device, skip_timesteps, init_image, const_noise), None
+        for i in reversed(range(self.num_timesteps - skip_timesteps)):
+            out = step(img, th.full((shape[0],), i, dtype=th.long), i, out)
             yield out
             img = out["sample"]
+
+    def _step_progressive(self, sampler, eta, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image,
+                          const_noise):
+        def step(img, t, i, _):
+            return self._one_step(sampler, model, img, t, clip_denoised, model_kwargs, eta, const_noise, None, None, index=i)
+        return self._progressive(step, model, shape, noise, model_kwargs, device, skip_timesteps, init_image, const_noise)
 
     def _progressive_args(self, model, shape, denoised_fn, cond_fn, model_kwargs, randomize_class, cond_fn_with_grad):
         """What can be refused is refused when the generator is REQUESTED, not at its first ``next()`` (a generator body does not run
@@ -887,15 +769,15 @@ class GaussianDiffusion:
                                   model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
                                   randomize_class=False, cond_fn_with_grad=False, const_noise=False):
         shape, model_kwargs = self._progressive_args(model, shape, denoised_fn, cond_fn, model_kwargs, randomize_class, cond_fn_with_grad)
-        return self._progressive(_lib.LS_SAMPLER_DDPM, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
-                                 skip_timesteps, init_image, randomize_class, cond_fn_with_grad, const_noise, 0.0)
+        return self._step_progressive(_lib.LS_SAMPLER_DDPM, 0.0, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps,
+                                      init_image, const_noise)
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
                                      randomize_class=False, cond_fn_with_grad=False, const_noise=False):
         shape, model_kwargs = self._progressive_args(model, shape, denoised_fn, cond_fn, model_kwargs, randomize_class, cond_fn_with_grad)
-        return self._progressive(_lib.LS_SAMPLER_DDIM, model, shape, noise, clip_denoised, denoised_fn, cond_fn, model_kwargs, device,
-                                 skip_timesteps, init_image, randomize_class, cond_fn_with_grad, const_noise, eta)
+        return self._step_progressive(_lib.LS_SAMPLER_DDIM, eta, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps,
+                                      init_image, const_noise)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,

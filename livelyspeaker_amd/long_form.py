@@ -10,17 +10,17 @@ chain as ONE engine call (``ls_long_prepare`` + ``ls_long_sample``):
   (``k_chain_window``, csrc/ls_chain.hip) happens on the device, the host neither copies nor waits between windows;
 * window 0 contributes its 34 frames to the timeline, every later window its frames ``n_pre..33``.
 
-With ``noise_source='torch_cpu'`` the draws are those ``GaussianDiffusion._loop`` makes for one call, window after window, and the
-result is bit for bit what the same windows give through ``ddim_sample_loop`` / ``p_sample_loop`` (and ``Decoder_TRANSFORMER.forward``
-with ``sag``) called once per window with ``origin_x`` rebuilt in between (tests/test_gpu_long_form.py).  ``'philox'`` draws one key per
-call; the window index is folded into the Philox counter (csrc/ls_philox.h).
+With ``noise_source='torch_cpu'`` the draws are those ``GaussianDiffusion._loop`` makes for one call, window after window
+(``ref_draws.RefDraws.windows``), and the result is bit for bit what the same windows give through ``ddim_sample_loop`` /
+``p_sample_loop`` (and ``Decoder_TRANSFORMER.forward`` with ``sag``) called once per window with ``origin_x`` rebuilt in between
+(tests/test_gpu_long_form.py).  ``'philox'`` draws one key per call; the window index is folded into the Philox counter (csrc/ls_philox.h).
 """
 from __future__ import annotations
 
 import numpy as np
 import torch as th
 
-from . import _lib
+from . import _lib, ref_draws
 from . import gaussian_diffusion as gd
 
 AUDIO_STRIDE = 32000        # audio samples between two windows: T - n_pre_seq = 30 frames at 15 fps of 16 kHz audio
@@ -73,8 +73,7 @@ def _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, n_
         raise TypeError(f"sample_long: pass livelyspeaker_amd.ClassifierFreeSampleModel(RAG), got {type(model).__name__}")
     if diffusion.noise_source == "torch_device":
         raise NotImplementedError("sample_long: noise_source='torch_device' is not built for chained windows; use 'torch_cpu' or 'philox'")
-    if diffusion.noise_source not in ("torch_cpu", "philox"):
-        raise ValueError(f"noise_source {diffusion.noise_source!r}")
+    diffusion._check_noise_source()
     if sampler not in ("ddim", "ddpm"):
         raise ValueError(f"sampler must be 'ddim' or 'ddpm', got {sampler!r}")
     rag = model.model
@@ -117,32 +116,6 @@ def _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, n_
     return B, W
 
 
-def _host_tapes(diffusion, W, n_exec, shape, D):
-    """The torch_cpu draws of W calls of GaussianDiffusion._loop, in its order: per window randn(*shape), then per step the style eps
-    of the cond and the uncond pass and randn_like(x) in x's memory order (contiguous at a window's first step, [T][B][J][F] afterwards).
-    Natively from torch's generator state when _loop would (same values, same final state)."""
-    from . import torch_rng
-    B = shape[0]
-    x = th.empty((W,) + shape)
-    eps = th.empty(W, n_exec, 2, B, D)
-    nz = th.empty((W, n_exec) + shape)
-    intercepted = th.randn is not gd._TH_RANDN or th.randn_like is not gd._TH_RANDN_LIKE
-    native = torch_rng.variant() if (diffusion.native_host_rng and not intercepted) else -1
-    diffusion.last_host_rng_native = native >= 0
-    first_proto = th.empty(shape)
-    later_proto = th.empty(shape[3], shape[0], shape[1], shape[2]).permute(1, 2, 3, 0)
-    for w in range(W):
-        x[w] = th.randn(*shape)
-        if native >= 0:
-            torch_rng.fill_steps(eps[w], nz[w], True, native)
-            continue
-        for k in range(n_exec):
-            eps[w, k, 0] = th.randn(B, 1, D)[:, 0]
-            eps[w, k, 1] = th.randn(B, 1, D)[:, 0]
-            nz[w, k].copy_(th.randn_like(first_proto if k == 0 else later_proto, dtype=th.float32))
-    return x, eps, nz
-
-
 def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=None, n_windows=None, sampler='ddim', skip_timesteps=0,
                 eta=0.0, clip_denoised=False, sag=None, text_features=None, encoder_chunk=None, return_windows=False, **unsupported):
     """``n_windows`` chained windows for ``audio`` [B, L] (default: the windows that cover it, ``plan_windows``) as one timeline
@@ -163,11 +136,7 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
     if rag.cond_mask_prob <= 0:
         raise ValueError("ClassifierFreeSampleModel returns None when cond_mask_prob == 0 (cfg_sampler.py:24-31)")
     out_dev = audio.device
-    eng = rag.engine()
-    key = (id(diffusion), diffusion.num_timesteps)
-    if getattr(eng, "_sched_key", None) != key:
-        eng.set_schedule(diffusion)
-        eng._sched_key = key
+    eng = diffusion._bind_schedule(rag.engine())
     rag._cond_key = rag._prefetched_key = None        # the engine's resident conditioning is this call's from here on
     if emo is not None:
         emo = (emo[None, :].expand(W, B) if emo.ndim == 1 else emo.t()).contiguous()
@@ -184,17 +153,14 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
         kw["sag"] = sag_eng
         kw["text_features"] = text_features.float().permute(1, 0, 2).contiguous()
     if diffusion.noise_source == "philox":
-        drawn = int(th.randint(0, 2 ** 62, (1,)).item())
-        diffusion.last_philox_seed = drawn if diffusion.philox_seed is None else int(diffusion.philox_seed)
-        kw["philox_seed"] = diffusion.last_philox_seed
-        kw["sample_offset"] = int(getattr(diffusion, "sample_offset", 0))
+        kw.update(diffusion._philox_key())
     else:
         per_window = n_exec * (2 * B * eng.D + int(np.prod(shape))) * 4
         if per_window > diffusion.tape_segment_bytes:
             raise ValueError(f"sample_long: one window's noise tape is {per_window} bytes, tape_segment_bytes is "
                              f"{diffusion.tape_segment_bytes}; segmented tapes are not built for chained windows (raise "
                              "tape_segment_bytes or use noise_source='philox')")
-        kw["x_init"], kw["eps_tape"], kw["noise_tape"] = _host_tapes(diffusion, W, n_exec, shape, eng.D)
+        kw["x_init"], kw["eps_tape"], kw["noise_tape"] = ref_draws.RefDraws("cpu").windows(diffusion, W, n_exec, shape, eng.D)
         diffusion.last_tape_segments = 1
     res = eng.long_sample(**kw)
     timeline, windows = res if return_windows else (res, None)

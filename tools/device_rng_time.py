@@ -35,9 +35,7 @@ rag.to(dev).eval()
 model = ClassifierFreeSampleModel(rag)
 y = {k: torch.from_numpy(v).to(dev) for k, v in synth.make_cond(cfg, B).items()}
 shape = (B, cfg.njoints, cfg.nfeats, cfg.nframes)
-eng = rag._engine_prepared(y)
-eng.set_schedule(diffusion)
-eng._sched_key = (id(diffusion), diffusion.num_timesteps)     # what GaussianDiffusion._engine_for would set
+eng = diffusion._bind_schedule(rag._engine_prepared(y))
 
 for mode in modes:
     if mode == "tape_device":
