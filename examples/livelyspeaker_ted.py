@@ -9,6 +9,9 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py [batch]
     python examples/livelyspeaker_ted.py [batch] --from-motion
     python examples/livelyspeaker_ted.py [batch] --long-seconds N
+    python examples/livelyspeaker_ted.py [batch] --clip-text
+--clip-text starts from TOKENS instead of a stand-in feature: synthetic clip.tokenize output -> CLIPTextEncoder (the text tower of CLIP
+on the GPU, synthetic weights) -> text features -> SAG decoder -> the same refinement, with no host wait between the two engines.
 --from-motion edits a RECORDED clip instead: no text feature is needed, the SAG encoder turns the clip into the CLIP-aligned latent
 (recorded clip -> SAG(batch) = MOTIONCLIP.forward -> init_image -> the same 20-step refinement).
 --long-seconds N synthesises N seconds of gesture for N seconds of speech in ONE call (livelyspeaker_amd.long_form.sample_long): the
@@ -143,6 +146,9 @@ def main():
         seconds = float(sys.argv[i + 1])
         del sys.argv[i:i + 2]
         return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source)
+    if "--clip-text" in sys.argv:
+        sys.argv.remove("--clip-text")
+        return main_clip_text(int(sys.argv[1]) if len(sys.argv) > 1 else 64, noise_source)
     from_motion = "--from-motion" in sys.argv
     if from_motion:
         sys.argv.remove("--from-motion")
@@ -187,6 +193,35 @@ def main_from_motion(B, noise_source):
           f"{sag.encoder.engine().last_encode_ms():.3f} ms, decode {sag.decoder.engine().last_decode_ms():.3f} ms; "
           f"|mu| mean {float(batch['mu'].norm(dim=-1).mean()):.3f}")
     assert bool(torch.isfinite(sample).all()) and bool((decoded[1, :, :, 28:] == 0).all())
+
+
+def main_clip_text(B, noise_source):
+    """Tokens -> text features -> SAG decode -> refinement.  The encode is enqueued only (wait=False) and the decoder's stream is ordered
+    behind the encoder's, so the features never pass through the host."""
+    import numpy as np
+    from livelyspeaker_amd import _lib
+    from livelyspeaker_amd.motionclip import get_clip
+    cfg, model, diffusion, sag_decoder, _ = build()
+    clip_model = get_clip({k: torch.from_numpy(v) for k, v in synth.synth_clip_text_state().items()}, "cuda:0")
+    vec_seq, batch, cond = make_inputs(cfg, B)
+    lengths = [int(n) for n in np.random.Generator(np.random.PCG64(13)).integers(6, 25, B)]     # a sentence inside a 2.3 s clip: about a dozen tokens
+    text = torch.from_numpy(synth.synth_clip_tokens(lengths))                                   # what clip.tokenize returns: host int64 [B, 77]
+
+    def run():
+        batch["z"] = clip_model.encode_text(text, wait=False)
+        _lib.stream_order(0, clip_model.engine()._stream, sag_decoder.engine()._stream)
+        return infer(model, diffusion, sag_decoder, batch, cond, noise_source=noise_source)
+
+    run()                                                                                   # warm-up (graph capture, allocations)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    decoded, sample = run()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    print(f"B={B} ({noise_source}), from tokens: CLIP text encode + SAG decode + 20-step guided refinement {dt * 1e3:.1f} ms; encode "
+          f"{clip_model.engine().last_encode_ms():.3f} ms for {sum(lengths)} of {77 * B} rows, decode {sag_decoder.engine().last_decode_ms():.3f} ms; "
+          f"|z| mean {float(batch['z'].norm(dim=-1).mean()):.3f}")
+    assert bool(torch.isfinite(sample).all()) and bool(torch.isfinite(decoded).all())
 
 
 def main_long(B, seconds, noise_source):

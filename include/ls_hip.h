@@ -533,6 +533,44 @@ int ls_sag_enc_encode_async(ls_sag_enc* h, int batch, const float* x, const unsi
 float ls_sag_enc_last_encode_ms(const ls_sag_enc* h);   /* GPU time of the last encode; waits for an asynchronous one */
 void* ls_sag_enc_stream(const ls_sag_enc* h);
 
+/* ---- CLIP text encoder -----------------------------------------------------------------------------------
+ * clip_model.encode_text(text).float() of scripts/test_LivelySpeaker_ted.py:85-86 and scripts/model/motionclip.py:52-53: the text
+ * tower of CLIP ViT-B/32 in fp32 -- token + positional embedding, `layers` pre-norm blocks (causal nn.MultiheadAttention, MLP with
+ * QuickGELU), ln_final, the row at text.argmax(-1) times text_projection.  Tokens are what clip.tokenize returns: [B, context_length]
+ * int64.  Weight keys are CLIP's own state-dict names (token_embedding.weight, positional_embedding, transformer.resblocks.N.*,
+ * ln_final.*, text_projection); a missing or mis-sized key fails in the commit call with the key named.
+ * Supported: width = embed_dim = 512, heads = 8, context_length 1..77, layers 1..24, vocab_size >= 1; anything else is
+ * LS_EUNSUPPORTED, decided before the device is touched.
+ * prune != 0: only rows 0 .. eot of every sample are computed, packed back to back (the mask is causal and only the EOT row is read
+ * out, so this is exact); prune = 0 computes all context_length rows of every sample.  Both give the same bits. */
+typedef struct ls_clip_text ls_clip_text;
+typedef struct ls_clip_text_config {
+    int32_t device;
+    int32_t vocab_size, context_length;     /* 49408, 77 */
+    int32_t width, heads, layers;           /* 512, 8, 12 */
+    int32_t embed_dim;                      /* 512        */
+} ls_clip_text_config;
+int ls_clip_text_create(const ls_clip_text_config* cfg, ls_clip_text** out);
+void ls_clip_text_destroy(ls_clip_text* h);
+const char* ls_clip_text_last_error(const ls_clip_text* h);
+int ls_clip_text_set_weight(ls_clip_text* h, const char* key, const float* data, size_t n);
+int ls_clip_text_commit_weights(ls_clip_text* h);
+/* tokens [B, context_length] int64 -> out [B, embed_dim] fp32.  on_device: 0 = tokens and out are host memory, 1 = both are device
+ * memory, 2 = host tokens, device out.  Host tokens are planned on the host (no device round trip).  Device tokens are planned by a
+ * small kernel whose B + 1 ints the host reads back, because the GEMM grids need the packed row count: that copy is the call's one
+ * host wait, also in the asynchronous form.  A token id outside [0, vocab_size) is LS_EINVAL, found by the plan before any gather. */
+int ls_clip_text_encode(ls_clip_text* h, int batch, int on_device, const int64_t* tokens, int prune, float* out);
+/* The same, enqueued only (`out` is device memory; tokens_on_device says where the tokens are): `out` is complete once
+ * ls_clip_text_stream() has reached this point; a SAG decoder handle consumes it after
+ * ls_stream_order(device, ls_clip_text_stream(clip), ls_sag_stream(dec)). */
+int ls_clip_text_encode_async(ls_clip_text* h, int batch, int tokens_on_device, const int64_t* tokens, int prune, float* out);
+float ls_clip_text_last_encode_ms(const ls_clip_text* h);   /* GPU time of the last encode; waits for an asynchronous one */
+void* ls_clip_text_stream(const ls_clip_text* h);
+/* The plan alone, on the host (needs no GPU): eot_out[b] = first position of row b's maximum (torch.argmax), row0_out[b] = the sum
+ * of eot + 1 over the rows before b, *total_out = the packed row count.  LS_EINVAL if an id lies outside [0, vocab_size). */
+int ls_clip_text_plan(const int64_t* tokens, int batch, int context_length, int vocab_size, int32_t* eot_out, int32_t* row0_out,
+                      int64_t* total_out);
+
 /* ---- caller-side post-processing of sampled clips ---------------------------------
  * scripts/test_RAG_ted.py:84-111 (layout change, mean add, per-bone normalisation, joint-angle change curve, motion
  * beats) and convert_dir_vec_to_pose (scripts/utils/data_utils.py:77-97).  Stateless; dataset constants are passed in. */

@@ -99,6 +99,10 @@ class LsSagConfig(C.Structure):
                                          "num_heads", "n_pre_poses", "device", "reserved")]
 
 
+class LsClipTextConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("device", "vocab_size", "context_length", "width", "heads", "layers", "embed_dim")]
+
+
 class LsPostConfig(C.Structure):
     _fields_ = [("njoints", C.c_int32), ("n_pairs", C.c_int32), ("n_pose_joints", C.c_int32), ("thres", C.c_float),
                 ("pair_a", C.c_int32 * 8), ("pair_b", C.c_int32 * 8), ("change_angle", C.c_float * 8),
@@ -144,7 +148,9 @@ EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
-           "ls_sag_enc_encode", "ls_sag_enc_encode_async", "ls_sag_enc_last_encode_ms", "ls_sag_enc_stream", "ls_ted_post", "ls_beat_post", "ls_beat_metrics", "ls_beat_ldiv",
+           "ls_sag_enc_encode", "ls_sag_enc_encode_async", "ls_sag_enc_last_encode_ms", "ls_sag_enc_stream",
+           "ls_clip_text_create", "ls_clip_text_destroy", "ls_clip_text_last_error", "ls_clip_text_set_weight", "ls_clip_text_commit_weights",
+           "ls_clip_text_encode", "ls_clip_text_encode_async", "ls_clip_text_last_encode_ms", "ls_clip_text_stream", "ls_clip_text_plan", "ls_ted_post", "ls_beat_post", "ls_beat_metrics", "ls_beat_ldiv",
            "ls_train_create", "ls_train_destroy", "ls_train_last_error", "ls_train_set_schedule", "ls_train_param_count",
            "ls_train_flat_size", "ls_train_param_info", "ls_train_set_weight", "ls_train_get_weight", "ls_train_forward_backward",
            "ls_train_adamw", "ls_train_read", "ls_train_get_moment", "ls_train_set_moment", "ls_train_get_step", "ls_train_set_step",
@@ -225,7 +231,7 @@ def load_library(build_if_missing: bool = True):
     lib.ls_get_timing.argtypes = [C.c_void_p, C.POINTER(LsTiming)]
     lib.ls_synchronize.argtypes = [C.c_void_p]
     lib.ls_stream_order.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-    for fn in ("ls_stream", "ls_sag_stream", "ls_sag_enc_stream", "ls_train_stream", "ls_eval_stream"):
+    for fn in ("ls_stream", "ls_sag_stream", "ls_sag_enc_stream", "ls_clip_text_stream", "ls_train_stream", "ls_eval_stream"):
         getattr(lib, fn).argtypes = [C.c_void_p]
         getattr(lib, fn).restype = C.c_void_p
     lib.ls_philox_x_init.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
@@ -264,6 +270,18 @@ def load_library(build_if_missing: bool = True):
     lib.ls_sag_enc_encode_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ls_sag_enc_last_encode_ms.argtypes = [C.c_void_p]
     lib.ls_sag_enc_last_encode_ms.restype = C.c_float
+    lib.ls_clip_text_create.argtypes = [C.POINTER(LsClipTextConfig), C.POINTER(C.c_void_p)]
+    lib.ls_clip_text_destroy.argtypes = [C.c_void_p]
+    lib.ls_clip_text_destroy.restype = None
+    lib.ls_clip_text_last_error.argtypes = [C.c_void_p]
+    lib.ls_clip_text_last_error.restype = C.c_char_p
+    lib.ls_clip_text_set_weight.argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
+    lib.ls_clip_text_commit_weights.argtypes = [C.c_void_p]
+    lib.ls_clip_text_encode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.ls_clip_text_encode_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.ls_clip_text_last_encode_ms.argtypes = [C.c_void_p]
+    lib.ls_clip_text_last_encode_ms.restype = C.c_float
+    lib.ls_clip_text_plan.argtypes = [c_i64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     lib.ls_ted_post.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(LsPostConfig), C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]
     lib.ls_beat_post.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -435,7 +453,7 @@ def plan_coop_slices(groups, dataset="ted", n_cus=256):
 
 
 class _Handle:
-    """What the five wrappers share: one C handle of the ``ls_<prefix>*`` family (``_prefix`` is ``"ls_"``, ``"ls_sag_"``, ...)."""
+    """What the six wrappers share: one C handle of the ``ls_<prefix>*`` family (``_prefix`` is ``"ls_"``, ``"ls_sag_"``, ...)."""
 
     _prefix = "ls_"
 
@@ -951,6 +969,74 @@ class SagEncoderEngine(_Handle):
             self._async_inputs = m          # the marshalled inputs stay referenced until the next encode on this (in-order) stream
             return out
         self._check(self.lib.ls_sag_enc_encode(self.h, B, int(m.on_device), px, pmask, pout), "ls_sag_enc_encode")
+        self._async_inputs = None
+        return out
+
+
+def clip_text_plan(tokens, vocab_size=49408):
+    """The packing plan of ``tokens`` [B, context] int64 (ls_clip_text_plan; no GPU needed): ``(eot [B], row0 [B], total)`` with
+    ``eot = tokens.argmax(-1)`` (first position of the maximum), ``row0`` the exclusive prefix of ``eot + 1`` and ``total`` the packed row
+    count.  Raises on an id outside ``[0, vocab_size)``."""
+    if hasattr(tokens, "detach"):
+        tokens = tokens.detach().cpu().numpy()
+    t = np.ascontiguousarray(tokens, dtype=np.int64)
+    if t.ndim != 2 or t.shape[0] < 1:
+        raise ValueError(f"tokens must be [B, context], got {list(t.shape)}")
+    B = t.shape[0]
+    eot, row0, total = np.empty(B, np.int32), np.empty(B, np.int32), C.c_int64()
+    rc = load_library().ls_clip_text_plan(t.ctypes.data_as(c_i64p), B, t.shape[1], int(vocab_size), eot.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          row0.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(total))
+    if rc != 0:
+        raise EngineError(f"ls_clip_text_plan failed ({rc}): a token id lies outside [0, {int(vocab_size)})")
+    return eot, row0, int(total.value)
+
+
+class ClipTextEngine(_Handle):
+    """ctypes wrapper of the CLIP text encoder handle (ls_clip_text_*): ``clip_model.encode_text(text).float()`` on the GPU."""
+
+    _prefix = "ls_clip_text_"
+
+    def __init__(self, vocab_size=49408, context_length=77, width=512, heads=8, layers=12, embed_dim=512, device=0):
+        self._create(LsClipTextConfig(device, vocab_size, context_length, width, heads, layers, embed_dim))
+        self.context, self.E, self.device = context_length, embed_dim, device
+        self._async_inputs = None
+
+    def load_state_dict(self, sd: dict):
+        self._set_weights(sd)
+
+    def last_encode_ms(self) -> float:
+        return float(self.lib.ls_clip_text_last_encode_ms(self.h))
+
+    def encode(self, tokens, wait=True, prune=True, device_out=False):
+        """tokens [B, context] integer ids -> features [B, embed_dim].  Host tokens are planned on the host; device tokens cost the
+        call's one host wait (the plan's B + 1 ints come back, because the GEMM grids need the packed row count).  The output is a
+        device tensor when the tokens are one or ``device_out`` is set, numpy otherwise.  ``wait=False`` (device output only): the
+        rest of the encode is enqueued on the encoder's stream; torch's current stream is ordered behind it, a consumer on another
+        stream with ``stream_order(device, self._stream, that_stream)``.  ``prune=False`` computes all context rows of every sample
+        (same bits; there to test and time the packing against)."""
+        shape = tuple(int(s) for s in tokens.shape)
+        if len(shape) != 2 or shape[1] != self.context:
+            raise ValueError(f"tokens must be [B, {self.context}], got {list(shape)}")
+        B = shape[0]
+        if B < 1:
+            raise ValueError("tokens hold no sentence")
+        m = _Marshal(self.device, tokens, stream=self._stream)
+        tokens_dev = m.on_device
+        ptok = m.i64(tokens, shape)
+        if device_out and not tokens_dev:          # host tokens, device output: the output side of the marshal alone is on the device
+            import torch
+            m.on_device, m.torch, m.dev = True, torch, torch.device("cuda", self.device)
+        if not wait and not m.on_device:
+            raise EngineError("encode(wait=False) needs a device output")
+        out, pout = m.out((B, self.E))
+        m.ready()
+        if not wait:
+            self._check(self.lib.ls_clip_text_encode_async(self.h, B, int(tokens_dev), ptok, int(bool(prune)), pout), "ls_clip_text_encode_async")
+            m.done_async()
+            self._async_inputs = m          # the marshalled inputs stay referenced until the next encode on this (in-order) stream
+            return out
+        mode = 1 if tokens_dev else (2 if m.on_device else 0)
+        self._check(self.lib.ls_clip_text_encode(self.h, B, mode, ptok, int(bool(prune)), pout), "ls_clip_text_encode")
         self._async_inputs = None
         return out
 

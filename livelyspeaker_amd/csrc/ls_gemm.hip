@@ -34,11 +34,14 @@ constexpr int kTM = 128, kTK = kGemmTileK, kLdK = kTK + 4, kLdR = kTM + 4;
 #define LS_GEMM_HALF_MAX 768      // LDS-DMA grids of at most this many 64-row tiles run as 32-row half tiles (see launch_gemm_tr)
 #endif
 
-// epilogue activations: 0 none, 1 SiLU, 2 exp(0.5 y) (std from log-variance), 3 exact GELU (F.gelu default)
+// epilogue activations: 0 none, 1 SiLU, 2 exp(0.5 y) (std from log-variance), 3 exact GELU (F.gelu default),
+// 4 QuickGELU v * sigmoid(1.702 v) (the CLIP text tower's MLP), in the form of code 1
+constexpr float kQuickGeluLog2e = 1.702f * 1.4426950408889634f;
 __device__ __forceinline__ float gemm_act(float v, int act) {
     if (act == 1) return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));   // the step kernel's SiLU (v_exp_f32 + v_rcp_f32)
     if (act == 2) return expf(0.5f * v);
     if (act == 3) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+    if (act == 4) return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-kQuickGeluLog2e * v));
     return v;
 }
 
@@ -66,6 +69,17 @@ __device__ __forceinline__ f4 gemm_act4(f4 v, int act) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = 0.5f * v[j] * (1.0f + erff(v[j] * 0.70710678118654752f));
         return v;
+    }
+    if (act == 4) {
+        const f4 t = v * -kQuickGeluLog2e;
+        f4 e;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) e[j] = __builtin_amdgcn_exp2f(t[j]);
+        e = e + 1.0f;
+        f4 s;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = __builtin_amdgcn_rcpf(e[j]);
+        return v * s;
     }
     return v;
 }
@@ -592,7 +606,7 @@ hipError_t launch_gemm_tr(GemmArgs a, bool a_kcontig, bool b_kcontig, int splits
 
 // nn.Linear-shaped entry (y = x W^T + b) used by the sampler's once-per-call stage, the SAG decoder and the FGD evaluator:
 //     C[m][n] = act( sum_k A[m][k] * W[n][k] + bias[n] ) (+ R[m][n]),   both operands K-contiguous
-// act: 0 none, 1 SiLU, 2 exp(0.5 y), 3 exact GELU (F.gelu default, nn.TransformerDecoderLayer activation="gelu")
+// act: 0 none, 1 SiLU, 2 exp(0.5 y), 3 exact GELU (F.gelu default, nn.TransformerDecoderLayer activation="gelu"), 4 QuickGELU (CLIP's MLP)
 hipError_t launch_gemm_nt(const float* A, int lda, const float* W, int ldw, const float* bias, const float* R, int ldr,
                           float* C, int ldc, int M, int N, int K, int act, hipStream_t st) {
     if (R && ldr != ldc) return hipErrorInvalidValue;           // the residual shares C's addressing

@@ -233,7 +233,7 @@ hipError_t launch_conv1d_mfma(const float* in, const float* stats, const float* 
 // conv1 (Cin = 1, k 15, stride 5) + output statistics in one pass (spart: B*32*ceil(Lout/256)*12 floats)
 hipError_t launch_conv1_fwd(const float* wav, const float* w, const float* bias, float* out, float* out_stats, float* spart, int B, int Lin,
                             int Lout, int pad, hipStream_t st);
-// C[M][N] = act(A[M][K] . W[N][K]^T + bias) (+ R): fp32 MFMA GEMM (ls_gemm.hip); act 3 = exact GELU
+// C[M][N] = act(A[M][K] . W[N][K]^T + bias) (+ R): fp32 MFMA GEMM (ls_gemm.hip); act 3 = exact GELU, 4 = QuickGELU
 hipError_t launch_gemm_nt(const float* A, int lda, const float* W, int ldw, const float* bias, const float* R, int ldr,
                           float* C, int ldc, int M, int N, int K, int act, hipStream_t st);
 // out[r] = table[idx[r * idx_stride]] (rows clamped into the table)
@@ -365,5 +365,19 @@ hipError_t launch_sag_enc_attention(const float* qkv, const unsigned char* kmask
 // the last layer's attention of token 0 alone: q0 [B][D] against kv rows [B*36][2D] = [k | v]
 hipError_t launch_sag_enc_attention_row0(const float* q0, const float* kv, const unsigned char* kmask, float* out, int B, int heads, int D,
                                          hipStream_t st);
+
+// ---- CLIP text encoder kernels (ls_clip_text.hip): packed rows, sample b = rows row0[b] .. row0[b] + len[b] - 1 ----
+constexpr int kClipCtx = 77;         // largest context_length (the attention pads a sample to at most 5 tiles of 16 rows)
+constexpr int kClipLP = 81;          // LDS row stride of the attention's score / probability rows
+// device tokens [B][ctx] int64 -> plan[0 .. B) = first position of the row maximum (torch.argmax), plan[B] = ids outside [0, vocab)
+hipError_t launch_clip_plan(const long long* tok, int* plan, int B, int ctx, int vocab, hipStream_t st);
+// x[row0[b] + t] = temb[tok[b][t]] + pemb[t], t < len[b]; ids must have been range-checked (the plan does)
+hipError_t launch_clip_embed(const long long* tok, const int* row0, const int* len, const float* temb, const float* pemb, float* x, int B,
+                             int ctx, hipStream_t st);
+// causal self-attention over packed qkv rows [q | k | v]; heads of 64; max_len = the batch's largest len[b] (sizes the LDS only)
+hipError_t launch_clip_attention(const float* qkv, float* out, const int* row0, const int* len, int B, int heads, int D, int max_len,
+                                 hipStream_t st);
+// e[b] = x[row0[b] + eot[b]]
+hipError_t launch_clip_gather_eot(const float* x, const int* row0, const int* eot, float* e, int B, hipStream_t st);
 
 }  // namespace ls

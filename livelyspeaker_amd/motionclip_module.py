@@ -3,9 +3,8 @@ constructors, state-dict keys and ``forward(batch)`` contracts as ``scripts/mode
 evaluated by the gfx950 engines (``ls_sag_enc_encode`` / ``ls_sag_decode``).  The torch submodules only hold parameters under the
 reference's key names and consume the RNG in the reference's constructor order; there is no CPU execution path.
 
-The CLIP text encoder that produces ``batch['z']`` is a third-party package (openai-clip @ a9b1bf5,
-requirements.txt:10) that is absent from this image: callers pass the text feature in ``batch['z']`` as the
-reference's decoder expects."""
+The CLIP text encoder that produces ``batch['z']`` is ``clip_text.CLIPTextEncoder`` (``motionclip.get_clip``); callers pass its
+output, or any other text feature, in ``batch['z']`` as the reference's decoder expects."""
 from __future__ import annotations
 
 import torch

@@ -245,6 +245,50 @@ def make_text_features(batch: int, seed: int = SEED_COND + 2000, latent: int = 5
     return _f32(0.3 * _rng(seed).standard_normal((batch, latent)))
 
 
+def synth_clip_text_state(seed: int = SEED_WEIGHTS + 400, layers: int = 12, vocab_size: int = 49408, context_length: int = 77,
+                          width: int = 512, embed_dim: int = 512) -> dict:
+    """The CLIP text tower under CLIP's own state-dict keys, drawn the way ``CLIP.initialize_parameters`` draws it: standard deviation
+    0.02 for the token embedding, 0.01 for the positional one, ``width^-0.5`` for ``in_proj`` and ``text_projection``,
+    ``width^-0.5 (2 layers)^-0.5`` for ``out_proj`` / ``c_proj`` and ``(2 width)^-0.5`` for ``c_fc``.  Where CLIP starts from constants
+    (LayerNorm 1 / 0, attention biases 0) the values are spread a little (LayerNorm weight 1 + 0.1 N, every bias 0.02 N), so that a
+    dropped bias or scale shows in the output."""
+    r = _rng(seed)
+    n = lambda std, *shape: _f32(std * r.standard_normal(shape, dtype=np.float32))
+    attn_std, proj_std, fc_std = width ** -0.5, width ** -0.5 * (2 * layers) ** -0.5, (2 * width) ** -0.5
+    sd = {"token_embedding.weight": n(0.02, vocab_size, width), "positional_embedding": n(0.01, context_length, width)}
+    for i in range(layers):
+        p = f"transformer.resblocks.{i}."
+        for ln in ("ln_1", "ln_2"):
+            sd[p + ln + ".weight"] = _f32(1.0 + n(0.1, width))
+            sd[p + ln + ".bias"] = n(0.02, width)
+        sd[p + "attn.in_proj_weight"] = n(attn_std, 3 * width, width)
+        sd[p + "attn.in_proj_bias"] = n(0.02, 3 * width)
+        sd[p + "attn.out_proj.weight"] = n(proj_std, width, width)
+        sd[p + "attn.out_proj.bias"] = n(0.02, width)
+        sd[p + "mlp.c_fc.weight"] = n(fc_std, 4 * width, width)
+        sd[p + "mlp.c_fc.bias"] = n(0.02, 4 * width)
+        sd[p + "mlp.c_proj.weight"] = n(proj_std, width, 4 * width)
+        sd[p + "mlp.c_proj.bias"] = n(0.02, width)
+    sd["ln_final.weight"] = _f32(1.0 + n(0.1, width))
+    sd["ln_final.bias"] = n(0.02, width)
+    sd["text_projection"] = n(attn_std, width, embed_dim)
+    return sd
+
+
+def synth_clip_tokens(lengths, seed: int = SEED_COND + 5000, context_length: int = 77) -> np.ndarray:
+    """[len(lengths), context_length] int64 in ``clip.tokenize``'s layout: start-of-text 49406, ``length - 2`` word ids below 49000,
+    end-of-text 49407 at position ``length - 1``, zeros behind.  ``length`` counts both marks: 2 .. context_length."""
+    r = _rng(seed)
+    tok = np.zeros((len(lengths), context_length), np.int64)
+    for b, n in enumerate(lengths):
+        if not 2 <= n <= context_length:
+            raise ValueError(f"a tokenised sentence has 2 .. {context_length} tokens, got {n}")
+        tok[b, 0] = 49406
+        tok[b, 1:n - 1] = r.integers(1, 49000, n - 2)
+        tok[b, n - 1] = 49407
+    return tok
+
+
 def make_embedding_net_state_dict(pose_dim: int = 27, base: int = 32, seed: int = SEED_WEIGHTS + 200, hidden=(8, 4)) -> dict:
     """Pose-encoder part of the FGD auto-encoder under EmbeddingNet's state-dict keys (scripts/model/embedding_net.py:41-66,
     checkpoint entry 'gen_dict'; hidden = out_net widths in units of base: (8, 4) TED 384-256-128-32, (4, 2) BEAT
