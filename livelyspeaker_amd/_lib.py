@@ -207,13 +207,6 @@ def load_library(build_if_missing: bool = True):
         raise EngineError(f"{path} not found: run `python -m livelyspeaker_amd.build` (no CPU fallback exists)")
     lib = C.CDLL(path)
     lib.ls_abi_version.restype = C.c_int
-    lib.ls_create.argtypes = [C.POINTER(LsConfig), C.POINTER(C.c_void_p)]
-    lib.ls_destroy.argtypes = [C.c_void_p]
-    lib.ls_destroy.restype = None
-    lib.ls_last_error.argtypes = [C.c_void_p]
-    lib.ls_last_error.restype = C.c_char_p
-    lib.ls_set_weight.argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
-    lib.ls_commit_weights.argtypes = [C.c_void_p]
     lib.ls_set_schedule.argtypes = [C.c_void_p, C.POINTER(LsSchedule)]
     lib.ls_prepare.argtypes = [C.c_void_p, C.POINTER(LsCond)]
     lib.ls_prepare_async.argtypes = [C.c_void_p, C.POINTER(LsCond)]
@@ -231,9 +224,18 @@ def load_library(build_if_missing: bool = True):
     lib.ls_get_timing.argtypes = [C.c_void_p, C.POINTER(LsTiming)]
     lib.ls_synchronize.argtypes = [C.c_void_p]
     lib.ls_stream_order.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-    for fn in ("ls_stream", "ls_sag_stream", "ls_sag_enc_stream", "ls_clip_text_stream", "ls_train_stream", "ls_eval_stream"):
-        getattr(lib, fn).argtypes = [C.c_void_p]
-        getattr(lib, fn).restype = C.c_void_p
+    # what every handle family declares alike (include/ls_hip.h); the trainer has no commit_weights, its set_weight writes the master parameters
+    for pre, cfg in (("ls_", LsConfig), ("ls_sag_", LsSagConfig), ("ls_sag_enc_", LsSagConfig), ("ls_clip_text_", LsClipTextConfig),
+                     ("ls_train_", LsTrainConfig), ("ls_eval_", LsEvalConfig)):
+        def fn(name, pre=pre):
+            return getattr(lib, pre + name)
+        fn("create").argtypes = [C.POINTER(cfg), C.POINTER(C.c_void_p)]
+        fn("destroy").argtypes, fn("destroy").restype = [C.c_void_p], None
+        fn("last_error").argtypes, fn("last_error").restype = [C.c_void_p], C.c_char_p
+        fn("set_weight").argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
+        if pre != "ls_train_":
+            fn("commit_weights").argtypes = [C.c_void_p]
+        fn("stream").argtypes, fn("stream").restype = [C.c_void_p], C.c_void_p
     lib.ls_philox_x_init.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
     lib.ls_torch_randn_advance.argtypes = [C.c_int64, C.c_int32, C.c_int32]
     lib.ls_torch_randn_advance.restype = C.c_uint64
@@ -248,35 +250,14 @@ def load_library(build_if_missing: bool = True):
     lib.ls_trng_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.ls_trng_pairs_debug.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
     lib.ls_shard_range.argtypes = [C.c_int64, C.c_int32, C.c_int32, c_i64p, c_i64p]
-    lib.ls_sag_create.argtypes = [C.POINTER(LsSagConfig), C.POINTER(C.c_void_p)]
-    lib.ls_sag_destroy.argtypes = [C.c_void_p]
-    lib.ls_sag_destroy.restype = None
-    lib.ls_sag_last_error.argtypes = [C.c_void_p]
-    lib.ls_sag_last_error.restype = C.c_char_p
-    lib.ls_sag_set_weight.argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
-    lib.ls_sag_commit_weights.argtypes = [C.c_void_p]
     lib.ls_sag_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ls_sag_decode_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ls_sag_last_decode_ms.argtypes = [C.c_void_p]
     lib.ls_sag_last_decode_ms.restype = C.c_float
-    lib.ls_sag_enc_create.argtypes = [C.POINTER(LsSagConfig), C.POINTER(C.c_void_p)]
-    lib.ls_sag_enc_destroy.argtypes = [C.c_void_p]
-    lib.ls_sag_enc_destroy.restype = None
-    lib.ls_sag_enc_last_error.argtypes = [C.c_void_p]
-    lib.ls_sag_enc_last_error.restype = C.c_char_p
-    lib.ls_sag_enc_set_weight.argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
-    lib.ls_sag_enc_commit_weights.argtypes = [C.c_void_p]
     lib.ls_sag_enc_encode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ls_sag_enc_encode_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ls_sag_enc_last_encode_ms.argtypes = [C.c_void_p]
     lib.ls_sag_enc_last_encode_ms.restype = C.c_float
-    lib.ls_clip_text_create.argtypes = [C.POINTER(LsClipTextConfig), C.POINTER(C.c_void_p)]
-    lib.ls_clip_text_destroy.argtypes = [C.c_void_p]
-    lib.ls_clip_text_destroy.restype = None
-    lib.ls_clip_text_last_error.argtypes = [C.c_void_p]
-    lib.ls_clip_text_last_error.restype = C.c_char_p
-    lib.ls_clip_text_set_weight.argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
-    lib.ls_clip_text_commit_weights.argtypes = [C.c_void_p]
     lib.ls_clip_text_encode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.ls_clip_text_encode_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.ls_clip_text_last_encode_ms.argtypes = [C.c_void_p]
@@ -287,17 +268,11 @@ def load_library(build_if_missing: bool = True):
     lib.ls_beat_post.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ls_beat_metrics.argtypes = [C.c_int, C.POINTER(LsBeatMetricsArgs)]
     lib.ls_beat_ldiv.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, c_f64p]
-    lib.ls_train_create.argtypes = [C.POINTER(LsTrainConfig), C.POINTER(C.c_void_p)]
-    lib.ls_train_destroy.argtypes = [C.c_void_p]
-    lib.ls_train_destroy.restype = None
-    lib.ls_train_last_error.argtypes = [C.c_void_p]
-    lib.ls_train_last_error.restype = C.c_char_p
     lib.ls_train_set_schedule.argtypes = [C.c_void_p, c_f64p, c_f64p, c_i64p]
     lib.ls_train_param_count.argtypes = [C.c_void_p]
     lib.ls_train_flat_size.argtypes = [C.c_void_p]
     lib.ls_train_flat_size.restype = C.c_int64
     lib.ls_train_param_info.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t, c_i64p, c_i64p]
-    lib.ls_train_set_weight.argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
     lib.ls_train_get_weight.argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
     lib.ls_train_forward_backward.argtypes = [C.c_void_p, C.POINTER(LsTrainBatch), C.c_void_p, C.POINTER(LsTrainTerms)]
     lib.ls_train_adamw.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float]
@@ -307,13 +282,6 @@ def load_library(build_if_missing: bool = True):
     lib.ls_train_get_step.argtypes = [C.c_void_p]
     lib.ls_train_get_step.restype = C.c_int64
     lib.ls_train_set_step.argtypes = [C.c_void_p, C.c_int64]
-    lib.ls_eval_create.argtypes = [C.POINTER(LsEvalConfig), C.POINTER(C.c_void_p)]
-    lib.ls_eval_destroy.argtypes = [C.c_void_p]
-    lib.ls_eval_destroy.restype = None
-    lib.ls_eval_last_error.argtypes = [C.c_void_p]
-    lib.ls_eval_last_error.restype = C.c_char_p
-    lib.ls_eval_set_weight.argtypes = [C.c_void_p, C.c_char_p, c_f32p, C.c_size_t]
-    lib.ls_eval_commit_weights.argtypes = [C.c_void_p]
     lib.ls_eval_features.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     if lib.ls_abi_version() != 5:
         raise EngineError("libls_hip.so ABI version mismatch")

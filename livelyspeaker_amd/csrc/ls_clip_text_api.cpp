@@ -1,10 +1,7 @@
 // C-ABI of the CLIP text encoder (include/ls_hip.h, "ls_clip_text_*"): replaces clip_model.encode_text(text).float()
-// (scripts/test_LivelySpeaker_ted.py:85-86, scripts/model/motionclip.py:52-53).  The handle is the SAG handles' (ls_sag_core.h):
-// stream, timing events, host / device weight maps, error path.  Kernels: ls_clip_text.hip; linears: ls_gemm.hip; LayerNorm: ls_sag.hip.
-#include "ls_sag_core.h"
-
-#include <cstdio>
-#include <cstring>
+// (scripts/test_LivelySpeaker_ted.py:85-86, scripts/model/motionclip.py:52-53).  The handle is an XfmrCore (ls_xfmr_core.h):
+// stream, timing events, weight maps resolved to pointers at commit, error path.  Kernels: ls_clip_text.hip; linears: ls_gemm.hip; LayerNorm: ls_sag.hip.
+#include "ls_xfmr_core.h"
 
 using namespace ls;
 
@@ -29,10 +26,18 @@ bool plan_rows(const int64_t* tok, int B, int ctx, int vocab, int* eot) {
     return ok;
 }
 
+// ResidualAttentionBlock parameters, in the order they are checked (pre-norm: ln_1 in front of the attention, ln_2 in front of the MLP)
+const LayerRow kClipRows[] = {
+    {"ln_1.weight", kD, 0, &Layer::ln_att_w}, {"ln_1.bias", kD, 0, &Layer::ln_att_b}, {"attn.in_proj_weight", (size_t)3 * kD * kD, 0, &Layer::in_w},
+    {"attn.in_proj_bias", (size_t)3 * kD, 0, &Layer::in_b}, {"attn.out_proj.weight", (size_t)kD * kD, 0, &Layer::out_w}, {"attn.out_proj.bias", kD, 0, &Layer::out_b},
+    {"ln_2.weight", kD, 0, &Layer::ln_ffn_w}, {"ln_2.bias", kD, 0, &Layer::ln_ffn_b}, {"mlp.c_fc.weight", 0, kD, &Layer::fc1_w}, {"mlp.c_fc.bias", 0, 1, &Layer::fc1_b},
+    {"mlp.c_proj.weight", 0, kD, &Layer::fc2_w}, {"mlp.c_proj.bias", kD, 0, &Layer::fc2_b}};
+
 }  // namespace
 
-struct ls_clip_text : SagCore {
-    ls_clip_text_config c{};
+struct ls_clip_text : XfmrCore {
+    ls_clip_text_config cfg{};
+    const float *tok_emb = nullptr, *pos_emb = nullptr, *lnf_w = nullptr, *lnf_b = nullptr;      // token_embedding.weight, positional_embedding, ln_final.*
     DevBuf proj_t;                        // text_projection transposed: [embed][width], the GEMM's W[n][k]
     DevBuf tok, plan;                     // tokens [B][ctx] int64; plan [3][B] ints: eot, row0, len (device tokens: k_clip_plan's [B + 1] first)
     DevBuf x, ln, qkv, attn, hid;         // packed rows, padded to whole GEMM tiles
@@ -64,55 +69,35 @@ int ls_clip_text_create(const ls_clip_text_config* cfg, ls_clip_text** out) {
         return fail<ls_clip_text>(nullptr, LS_EUNSUPPORTED, "context_length must be 1..%d", kClipCtx);
     if (cfg->layers < 1 || cfg->layers > 24) return fail<ls_clip_text>(nullptr, LS_EUNSUPPORTED, "layers must be 1..24");
     if (cfg->vocab_size < 1) return fail<ls_clip_text>(nullptr, LS_EINVAL, "vocab_size must be >= 1");
-    ls_sag_config sc{};
-    sc.latent_dim = kD; sc.ff_size = 4 * kD; sc.num_layers = cfg->layers; sc.num_heads = cfg->heads; sc.device = cfg->device;
-    const int rc = sag_open(&sc, out, 1, ls_clip_text_destroy);
-    if (rc != LS_OK) return rc;
-    (*out)->c = *cfg;
-    return LS_OK;
+    const int rc = xfmr_open(cfg->device, out, ls_clip_text_destroy);
+    if (rc == LS_OK) (*out)->cfg = *cfg;
+    return rc;
 }
 
-void ls_clip_text_destroy(ls_clip_text* h) {
-    if (!h) return;
-    sag_close(h);
-    delete h;
-}
+void ls_clip_text_destroy(ls_clip_text* h) { xfmr_close(h); }
 
-int ls_clip_text_set_weight(ls_clip_text* h, const char* key, const float* data, size_t n) { return sag_set_weight(h, "ls_clip_text_set_weight", key, data, n); }
+int ls_clip_text_set_weight(ls_clip_text* h, const char* key, const float* data, size_t n) { return xfmr_set_weight(h, "ls_clip_text_set_weight", key, data, n); }
 
 int ls_clip_text_commit_weights(ls_clip_text* h) {
     if (!h) return LS_EINVAL;
-    HIPCHK(h, hipSetDevice(h->c.device));
-    h->committed = false;
-    const size_t D = kD, FF = 4 * kD;
-    auto need = [&](const std::string& key, size_t want) { return sag_need(h, key, want); };
-    int rc;
-    char key[160];
-    if ((rc = need("token_embedding.weight", (size_t)h->c.vocab_size * D)) != LS_OK) return rc;
-    if ((rc = need("positional_embedding", (size_t)h->c.context_length * D)) != LS_OK) return rc;
-    for (int l = 0; l < h->c.layers; ++l) {
-        struct { const char* s; size_t n; } items[] = {
-            {"ln_1.weight", D}, {"ln_1.bias", D}, {"attn.in_proj_weight", 3 * D * D}, {"attn.in_proj_bias", 3 * D},
-            {"attn.out_proj.weight", D * D}, {"attn.out_proj.bias", D}, {"ln_2.weight", D}, {"ln_2.bias", D},
-            {"mlp.c_fc.weight", FF * D}, {"mlp.c_fc.bias", FF}, {"mlp.c_proj.weight", D * FF}, {"mlp.c_proj.bias", D}};
-        for (auto& it : items) {
-            snprintf(key, sizeof key, "transformer.resblocks.%d.%s", l, it.s);
-            if ((rc = need(key, it.n)) != LS_OK) return rc;
-        }
-    }
-    if ((rc = need("ln_final.weight", D)) != LS_OK) return rc;
-    if ((rc = need("ln_final.bias", D)) != LS_OK) return rc;
-    if ((rc = need("text_projection", D * D)) != LS_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t D = kD;
+    Commit<ls_clip_text> c(h);
+    if (const int rc = c.need("token_embedding.weight", (size_t)h->cfg.vocab_size * D, &h->tok_emb)) return rc;
+    if (const int rc = c.need("positional_embedding", (size_t)h->cfg.context_length * D, &h->pos_emb)) return rc;
+    if (const int rc = c.layers("transformer.resblocks.", h->cfg.layers, 4 * D, kClipRows)) return rc;
+    if (const int rc = c.need("ln_final.weight", D, &h->lnf_w)) return rc;
+    if (const int rc = c.need("ln_final.bias", D, &h->lnf_b)) return rc;
+    if (const int rc = c.need("text_projection", D * D, nullptr)) return rc;      // the device reads its transposed copy, proj_t
     {   // features = x @ P: as the GEMM's W[n][k] that is P transposed, once
-        const std::vector<float>& p = h->w["text_projection"];
+        const std::vector<float>& p = h->w.at("text_projection");
         std::vector<float> pt(D * D);
         for (size_t k = 0; k < D; ++k)
             for (size_t n = 0; n < D; ++n) pt[n * D + k] = p[k * D + n];
         HIPCHK(h, h->proj_t.ensure(pt.size() * sizeof(float)));
         HIPCHK(h, hipMemcpy(h->proj_t.p, pt.data(), pt.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    h->committed = true;
-    return LS_OK;
+    return c.done();
 }
 
 // tokens_dev / out_dev: where the caller's tokens and output live
@@ -120,10 +105,10 @@ static int clip_encode_impl(ls_clip_text* h, int batch, bool tokens_dev, bool ou
     if (!h || !tokens || !out) return fail(h, LS_EINVAL, "ls_clip_text_encode: null argument");
     if (!h->committed) return fail(h, LS_ESTATE, "ls_clip_text_encode before ls_clip_text_commit_weights");
     if (batch < 1) return fail(h, LS_EINVAL, "batch must be >= 1");
-    const int B = batch, D = kD, FF = 4 * kD, ctx = h->c.context_length, H = h->c.heads, L = h->c.layers;
+    const int B = batch, D = kD, FF = 4 * kD, ctx = h->cfg.context_length, H = h->cfg.heads, L = h->cfg.layers;
     // the LDS-DMA GEMM addresses an operand through 31-bit byte offsets: rows * 2048 floats must stay below 2^29
     if ((long long)pad_rows((long long)B * ctx) * FF >= (1ll << 29)) return fail(h, LS_EINVAL, "batch %d is too large for one encode", batch);
-    HIPCHK(h, hipSetDevice(h->c.device));
+    HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = h->stream;
     const size_t ntok = (size_t)B * ctx * sizeof(int64_t);
     // an earlier asynchronous encode may still be reading the host copies of its plan and tokens, which this call rewrites
@@ -140,12 +125,12 @@ static int clip_encode_impl(ls_clip_text* h, int batch, bool tokens_dev, bool ou
     if (tokens_dev) {
         // the one host wait of the call: the GEMM grids below need the packed row count
         dtok = reinterpret_cast<const long long*>(tokens);
-        HIPCHK(h, launch_clip_plan(dtok, dplan, B, ctx, h->c.vocab_size, st));
+        HIPCHK(h, launch_clip_plan(dtok, dplan, B, ctx, h->cfg.vocab_size, st));
         HIPCHK(h, hipMemcpyAsync(eot, dplan, ((size_t)B + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipStreamSynchronize(st));
-        if (eot[B] != 0) return fail(h, LS_EINVAL, "%d token id(s) outside [0, %d)", eot[B], h->c.vocab_size);
+        if (eot[B] != 0) return fail(h, LS_EINVAL, "%d token id(s) outside [0, %d)", eot[B], h->cfg.vocab_size);
     } else {
-        if (!plan_rows(tokens, B, ctx, h->c.vocab_size, eot)) return fail(h, LS_EINVAL, "token id outside [0, %d)", h->c.vocab_size);
+        if (!plan_rows(tokens, B, ctx, h->cfg.vocab_size, eot)) return fail(h, LS_EINVAL, "token id outside [0, %d)", h->cfg.vocab_size);
         h->htok.assign(tokens, tokens + (size_t)B * ctx);       // the caller's buffer may go before an asynchronous copy has read it
         HIPCHK(h, hipMemcpyAsync(h->tok.p, h->htok.data(), ntok, hipMemcpyHostToDevice, st));
         dtok = static_cast<const long long*>(h->tok.p);
@@ -174,28 +159,25 @@ static int clip_encode_impl(ls_clip_text* h, int batch, bool tokens_dev, bool ou
         HIPCHK(h, hipMemsetAsync(h->attn.f() + (size_t)M * D, 0, (MP - M) * row, st));
     }
     if (BP > B) HIPCHK(h, hipMemsetAsync(h->eln.f() + (size_t)B * D, 0, (BP - B) * row, st));
-    auto W = [&](const std::string& k) { return h->dw[k].f(); };
-    HIPCHK(h, launch_clip_embed(dtok, d_row0, d_len, W("token_embedding.weight"), W("positional_embedding"), h->x.f(), B, ctx, st));
-    char pre[96];
+    HIPCHK(h, launch_clip_embed(dtok, d_row0, d_len, h->tok_emb, h->pos_emb, h->x.f(), B, ctx, st));
     float* x = h->x.f();
     for (int l = 0; l < L; ++l) {
-        snprintf(pre, sizeof pre, "transformer.resblocks.%d.", l);
-        const std::string P(pre);
+        const Layer& w = h->layer[l];
         // x = x + out_proj(MHA(ln_1(x)))
-        HIPCHK(h, launch_layernorm512(x, nullptr, 0, W(P + "ln_1.weight"), W(P + "ln_1.bias"), h->ln.f(), M, st));
-        HIPCHK(h, launch_gemm_nt(h->ln.f(), D, W(P + "attn.in_proj_weight"), D, W(P + "attn.in_proj_bias"), nullptr, 0, h->qkv.f(), 3 * D, MP, 3 * D, D, 0, st));
+        HIPCHK(h, launch_layernorm512(x, nullptr, 0, w.ln_att_w, w.ln_att_b, h->ln.f(), M, st));
+        HIPCHK(h, launch_gemm_nt(h->ln.f(), D, w.in_w, D, w.in_b, nullptr, 0, h->qkv.f(), 3 * D, MP, 3 * D, D, 0, st));
         HIPCHK(h, launch_clip_attention(h->qkv.f(), h->attn.f(), d_row0, d_len, B, H, D, max_len, st));
-        HIPCHK(h, launch_gemm_nt(h->attn.f(), D, W(P + "attn.out_proj.weight"), D, W(P + "attn.out_proj.bias"), x, D, x, D, MP, D, D, 0, st));
+        HIPCHK(h, launch_gemm_nt(h->attn.f(), D, w.out_w, D, w.out_b, x, D, x, D, MP, D, D, 0, st));
         // x = x + c_proj(QuickGELU(c_fc(ln_2(x))))
-        HIPCHK(h, launch_layernorm512(x, nullptr, 0, W(P + "ln_2.weight"), W(P + "ln_2.bias"), h->ln.f(), M, st));
-        HIPCHK(h, launch_gemm_nt(h->ln.f(), D, W(P + "mlp.c_fc.weight"), D, W(P + "mlp.c_fc.bias"), nullptr, 0, h->hid.f(), FF, MP, FF, D, 4, st));
-        HIPCHK(h, launch_gemm_nt(h->hid.f(), FF, W(P + "mlp.c_proj.weight"), FF, W(P + "mlp.c_proj.bias"), x, D, x, D, MP, D, FF, 0, st));
+        HIPCHK(h, launch_layernorm512(x, nullptr, 0, w.ln_ffn_w, w.ln_ffn_b, h->ln.f(), M, st));
+        HIPCHK(h, launch_gemm_nt(h->ln.f(), D, w.fc1_w, D, w.fc1_b, nullptr, 0, h->hid.f(), FF, MP, FF, D, 4, st));
+        HIPCHK(h, launch_gemm_nt(h->hid.f(), FF, w.fc2_w, FF, w.fc2_b, x, D, x, D, MP, D, FF, 0, st));
     }
     // ln_final is row-wise, so it runs on the B rows that leave the tower only
     HIPCHK(h, launch_clip_gather_eot(x, d_row0, d_eot, h->e.f(), B, st));
-    HIPCHK(h, launch_layernorm512(h->e.f(), nullptr, 0, W("ln_final.weight"), W("ln_final.bias"), h->eln.f(), B, st));
+    HIPCHK(h, launch_layernorm512(h->e.f(), nullptr, 0, h->lnf_w, h->lnf_b, h->eln.f(), B, st));
     HIPCHK(h, launch_gemm_nt(h->eln.f(), D, h->proj_t.f(), D, nullptr, nullptr, 0, h->feat.f(), D, BP, D, D, 0, st));
-    return sag_finish(h, out, h->feat.p, (size_t)B * row, out_dev ? 1 : 0, wait);
+    return xfmr_finish(h, out, h->feat.p, (size_t)B * row, out_dev ? 1 : 0, wait);
 }
 
 int ls_clip_text_encode(ls_clip_text* h, int batch, int on_device, const int64_t* tokens, int prune, float* out) {
@@ -207,8 +189,8 @@ int ls_clip_text_encode_async(ls_clip_text* h, int batch, int tokens_on_device, 
     return clip_encode_impl(h, batch, tokens_on_device != 0, true, tokens, prune, out, false);
 }
 
-float ls_clip_text_last_encode_ms(const ls_clip_text* h) { return sag_last_ms(h); }
+float ls_clip_text_last_encode_ms(const ls_clip_text* h) { return xfmr_last_ms(h); }
 
-void* ls_clip_text_stream(const ls_clip_text* h) { return sag_stream(h); }
+void* ls_clip_text_stream(const ls_clip_text* h) { return xfmr_stream(h); }
 
 }  // extern "C"

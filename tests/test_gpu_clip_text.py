@@ -118,6 +118,27 @@ def test_token_placement_and_chaining():
     assert m.engine().last_encode_ms() > 0.0
 
 
+def test_reload_with_layers_exchanged():
+    """The encoder reads its weights through pointers resolved at commit.  A second load_state_dict -- the same keys and shapes, every
+    weight of block 0 exchanged with the last block's -- re-resolves all of them: same bits as an engine that only ever saw it."""
+    sd = state(2)
+    a, b = "transformer.resblocks.0.", "transformer.resblocks.1."
+    other = {k: sd[b + k[len(a):]] if k.startswith(a) else sd[a + k[len(b):]] if k.startswith(b) else v for k, v in sd.items()}
+    tok = np.array(_case(2)[0][:2])
+    eng, fresh = _lib.ClipTextEngine(layers=2), _lib.ClipTextEngine(layers=2)
+    try:
+        eng.load_state_dict(sd)
+        first = eng.encode(tok)
+        eng.load_state_dict(other)
+        second = eng.encode(tok)
+        fresh.load_state_dict(other)
+        assert np.array_equal(second, fresh.encode(tok))
+        assert not np.array_equal(second, first)
+    finally:
+        eng.close()
+        fresh.close()
+
+
 def test_errors():
     tok, _, _ = _case(2)
     m = _model(2)

@@ -85,6 +85,29 @@ def test_decode_batch_history_and_async_timing():
         eng.close()
 
 
+@pytest.mark.gpu
+def test_reload_with_layers_exchanged():
+    """The decoder reads its weights through pointers resolved at commit.  A second load_state_dict -- the same keys and shapes, every
+    weight of layer 0 exchanged with the last layer's -- re-resolves all of them: same bits as an engine that only ever saw it."""
+    from livelyspeaker_amd import _lib
+    sd = synth.make_sag_state_dict()
+    a, b = "seqTransDecoder.layers.0.", "seqTransDecoder.layers.2."
+    other = {k: sd[b + k[len(a):]] if k.startswith(a) else sd[a + k[len(b):]] if k.startswith(b) else v for k, v in sd.items()}
+    x, z = _inputs(2)
+    eng, fresh = _lib.SagEngine(), _lib.SagEngine()
+    try:
+        eng.load_state_dict(sd)
+        first = eng.decode(x, z)
+        eng.load_state_dict(other)
+        second = eng.decode(x, z)
+        fresh.load_state_dict(other)
+        assert np.array_equal(second, fresh.decode(x, z))
+        assert not np.array_equal(second, first)
+    finally:
+        eng.close()
+        fresh.close()
+
+
 # ---- BEAT twin (scripts_beat/model/motionclip_module.py:98-183: 47 joints x 6 features, mapping = Linear(283, 512)) ----
 @pytest.fixture(scope="module")
 def g6_beat():

@@ -270,6 +270,28 @@ def test_encode_batch_history_and_async_timing():
 
 
 @pytest.mark.gpu
+def test_reload_with_layers_exchanged():
+    """The encoder reads its weights through pointers resolved at commit.  A second load_state_dict -- the same keys and shapes, every
+    weight of layer 0 exchanged with the last layer's (the one that runs on token 0 only) -- re-resolves all of them: same bits as an
+    engine that only ever saw it."""
+    sd = synth.make_sag_encoder_state_dict(synth.TED)
+    a, b = "seqTransEncoder.layers.0.", "seqTransEncoder.layers.2."
+    other = {k: sd[b + k[len(a):]] if k.startswith(a) else sd[a + k[len(b):]] if k.startswith(b) else v for k, v in sd.items()}
+    x = _x(synth.TED, 2)
+    eng, fresh = _engine(synth.TED), _engine(synth.TED)
+    try:
+        first = eng.encode(x)
+        eng.load_state_dict(other)
+        second = eng.encode(x)
+        fresh.load_state_dict(other)
+        assert np.array_equal(second, fresh.encode(x))
+        assert not np.array_equal(second, first)
+    finally:
+        eng.close()
+        fresh.close()
+
+
+@pytest.mark.gpu
 def test_error_paths_reach_no_kernel():
     from livelyspeaker_amd import _lib
     cfg = synth.TED
