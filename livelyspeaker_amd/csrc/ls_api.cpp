@@ -1,10 +1,10 @@
-// Host side of the C-ABI declared in include/ls_hip.h: the handle's life cycle, weight images in MFMA operand order, the schedule,
-// once-per-call preparation and the small utility exports.  The step plan and its launchers are in ls_plan.cpp, the diffusion loop and the
-// single-step entries in ls_sample.cpp; ls_handle.h holds what the three share.  No torch types here; livelyspeaker_amd/_lib.py binds these symbols with ctypes.
+// Host side of the C-ABI declared in include/ls_hip.h: the handle's life cycle, the commit that uploads the weight images, the schedule,
+// once-per-call preparation and the small utility exports.  The images themselves (MFMA operand order) are built on the host by
+// ls_weights.cpp; the step plan and its launchers are in ls_plan.cpp, the diffusion loop and the single-step entries in ls_sample.cpp;
+// ls_handle.h holds what the three share.  No torch types here; livelyspeaker_amd/_lib.py binds these symbols with ctypes.
 #include "ls_handle.h"
+#include "ls_weights.h"
 
-#include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -12,420 +12,80 @@ using namespace ls;
 
 namespace {
 
-const int kConvCin[4] = {1, 32, 64, 128};
-const int kConvCout[4] = {32, 64, 128, 256};
-const int kConvStride[4] = {5, 6, 6, 6};
-const int kConvPad[4] = {1600, 0, 0, 0};
-const int kConvKey[4] = {0, 3, 6, 9};
+// ls_commit_weights: resolve every key (a faulty one returns before anything is uploaded), build the host images the model needs
+// (ls_weights.cpp), upload them, fill DevWeights, wait once.  A 34-frame model carries both forms: the fused kernels (one workgroup per
+// sample) and the batch-level kernels small batches run on.  (Kernel comments that name build_fused_images or build_shared_weights mean
+// fused_images and the once-per-call group below; each layout is stated once, in ls_weights.cpp.)
+int build_images(ls_handle* h) {
+    const WeightDims d{h->cfg.layers, h->S, h->R, h->JF, h->KIN, h->KPP, h->JFP, h->MK, h->KXQ, h->NOB, h->cfg.n_speakers, h->cfg.n_emotions,
+                       h->fused, !h->fused && mix_supports(h->S)};
+    Weights w;
+    std::string msg;
+    if (const int rc = resolve_weights(h->w, d, w, msg)) return fail(h, rc, "%s", msg.c_str());
 
-// bf16 round-to-nearest-even, as v_cvt_pk_bf16_f32 does on the device side of the split
-unsigned short f32_to_bf16(float f) {
-    unsigned u;
-    memcpy(&u, &f, 4);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-float bf16_to_f32(unsigned short h) {
-    const unsigned u = (unsigned)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-// upload a host vector into the handle's buffer `buf` (any element type); needs `int rc` in scope
-#define UP(buf, vec) if ((rc = upload(h, h->buf, (vec).data(), (vec).size() * sizeof((vec)[0]))) != LS_OK) return rc
-
-const std::vector<float>* find_w(ls_handle* h, const std::string& key, size_t want) {
-    auto it = h->w.find(key);
-    if (it == h->w.end()) { fail(h, LS_ESTATE, "missing weight '%s'", key.c_str()); return nullptr; }
-    if (it->second.size() != want) {
-        fail(h, LS_EINVAL, "weight '%s' has %zu elements, expected %zu", key.c_str(), it->second.size(), want);
-        return nullptr;
-    }
-    return &it->second;
-}
-
-// Device images whose element order is the per-lane MFMA operand order of the fused step kernel (ls_step_kernel.h).
-int build_fused_images(ls_handle* h) {
-    const int L = h->cfg.layers, S = h->S, R = h->R, JF = h->JF, D = kD;
-    const int MK = h->MK, KXQ = h->KXQ, NOB = h->NOB, KIN = h->KIN;
-    std::vector<float> wch((size_t)L * D * D), bch((size_t)L * D), l1a((size_t)L * D), l1b((size_t)L * D),
-        l2a((size_t)L * D), l2b((size_t)L * D), ww((size_t)L * kNT * MK * 64), bt((size_t)L * 80, 0.f);
-    std::vector<unsigned short> wch_hi((size_t)L * D * D), wch_lo((size_t)L * D * D), wch_lo2((size_t)L * D * D);
-    const int KS = (R + 31) / 32;
-    const int MK1 = (S + 3) / 4;
-    const int MQ1 = (MK1 + 3) / 4;
-    std::vector<float> wt1((size_t)L * 3 * MQ1 * 256);
-    std::vector<unsigned short> wwh((size_t)L * kNT * KS * 64 * 8), wwl((size_t)L * kNT * KS * 64 * 8);
-    const int KS1 = (S + 31) / 32;
-    std::vector<unsigned short> wt1h((size_t)L * 3 * KS1 * 64 * 8), wt1l((size_t)L * 3 * KS1 * 64 * 8);
-    std::vector<float> wtl((size_t)L * S * 4, 0.f);
-    char key[160];
-    for (int l = 0; l < L; ++l) {
-        auto K = [&](const char* suffix) { snprintf(key, sizeof key, "backbone.mlps.%d.%s", l, suffix); return std::string(key); };
-        const auto* W = find_w(h, K("block2.1.weight"), (size_t)D * D);        // Linear(512,512) [out][in], mlp_module.py:58-60
-        const auto* b2 = find_w(h, K("block2.1.bias"), D);
-        const auto* Wt = find_w(h, K("block1.1.weight"), (size_t)S * S);       // Conv1d(S,S,1) [out tok][in tok][1], :51-55
-        const auto* b1 = find_w(h, K("block1.1.bias"), S);
-        const auto* a1 = find_w(h, K("block1.0.alpha"), D);
-        const auto* be1 = find_w(h, K("block1.0.beta"), D);
-        const auto* a2 = find_w(h, K("block2.0.alpha"), D);
-        const auto* be2 = find_w(h, K("block2.0.beta"), D);
-        if (!W || !b2 || !Wt || !b1 || !a1 || !be1 || !a2 || !be2) return LS_ESTATE;
-        // wch_img[l][w][p][q][c2][lane][j] = W[n = 64w + 16(2p+c2) + (lane&15)][k = 16q + 4(lane>>4) + j]
-        size_t o = (size_t)l * D * D;
-        for (int w = 0; w < kWaves; ++w)
-            for (int p = 0; p < 2; ++p)
-                for (int q = 0; q < 32; ++q)
-                    for (int c2 = 0; c2 < 2; ++c2)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 4; ++j) {
-                                const int n = 64 * w + 16 * (2 * p + c2) + (lane & 15);
-                                const int k = 16 * q + 4 * (lane >> 4) + j;
-                                wch[o++] = (*W)[(size_t)n * D + k] * (*a2)[k];        // W' = W . diag(alpha2)
-                            }
-        // bf16 images, operand order of v_mfma_f32_16x16x32_bf16: [l][w][p][q16][c2][lane][8 k].  W' = hi + mid + lo exactly, each
-        // round-to-nearest-even: hi = bf16(W'), mid = bf16(W' - hi), lo = bf16(W' - hi - mid) (both differences are exact in fp32).
-        // bf16x3 uses hi and mid (its "lo" plane, wch_lo_img); split-fp32 (k_step PREC 2) all three.
-        {
-            size_t oh = (size_t)l * D * D;
-            for (int w = 0; w < kWaves; ++w)
-                for (int p = 0; p < 2; ++p)
-                    for (int q = 0; q < 16; ++q)
-                        for (int c2 = 0; c2 < 2; ++c2)
-                            for (int lane = 0; lane < 64; ++lane)
-                                for (int e = 0; e < 8; ++e) {
-                                    const int n = 64 * w + 16 * (2 * p + c2) + (lane & 15);
-                                    const int k = 32 * q + 8 * (lane >> 4) + e;
-                                    const float v = (*W)[(size_t)n * D + k] * (*a2)[k];
-                                    const unsigned short hi = f32_to_bf16(v);
-                                    wch_hi[oh] = hi;
-                                    const float r = v - bf16_to_f32(hi);
-                                    wch_lo[oh] = f32_to_bf16(r);
-                                    wch_lo2[oh] = f32_to_bf16(r - bf16_to_f32(wch_lo[oh]));
-                                    ++oh;
-                                }
-        }
-        for (int n = 0; n < D; ++n) {                                                    // b' = b + W . beta2
-            double acc = (*b2)[n];
-            for (int k = 0; k < D; ++k) acc += (double)(*W)[(size_t)n * D + k] * (double)(*be2)[k];
-            bch[(size_t)l * D + n] = (float)acc;
-        }
-        memcpy(&l1a[(size_t)l * D], a1->data(), D * sizeof(float));
-        memcpy(&l1b[(size_t)l * D], be1->data(), D * sizeof(float));
-        memcpy(&l2a[(size_t)l * D], a2->data(), D * sizeof(float));
-        memcpy(&l2b[(size_t)l * D], be2->data(), D * sizeof(float));
-        // ww_img[l][t][m][lane] = WW[r = 16t + (lane&15)][r' = 4m + (lane>>4)], WW = blockdiag(Wt, Wt) on packed rows
-        for (int t = 0; t < kNT; ++t)
-            for (int m = 0; m < MK; ++m)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int r = 16 * t + (lane & 15), rp = 4 * m + (lane >> 4);
-                    float v = 0.f;
-                    if (r < R && rp < R && r / S == rp / S) v = (*Wt)[(size_t)(r % S) * S + (rp % S)];
-                    ww[(((size_t)l * kNT + t) * MK + m) * 64 + lane] = v;
-                }
-        // bf16x3 token-mix images: [l][t][ks][lane][e] = WW[r = 16t + (lane&15)][r' = 32ks + 8(lane>>4) + e]
-        for (int t = 0; t < kNT; ++t)
-            for (int ks = 0; ks < KS; ++ks)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 8; ++e) {
-                        const int r = 16 * t + (lane & 15), rp = 32 * ks + 8 * (lane >> 4) + e;
-                        float v = 0.f;
-                        if (r < R && rp < R && r / S == rp / S) v = (*Wt)[(size_t)(r % S) * S + (rp % S)];
-                        const size_t o = ((((size_t)l * kNT + t) * KS + ks) * 64 + lane) * 8 + e;
-                        wwh[o] = f32_to_bf16(v);
-                        wwl[o] = f32_to_bf16(v - bf16_to_f32(wwh[o]));
-                    }
-        for (int r = 0; r < R; ++r) bt[(size_t)l * 80 + r] = (*b1)[r % S];
-        // wtail[l][k][i] = Wt[32 + i][k] (zero beyond the last row): the A operand of the ragged rows' 4x4x1 MFMAs (ls_pass_kernel.h)
-        for (int k = 0; k < S; ++k)
-            for (int i = 0; i < 4; ++i)
-                if (32 + i < S) wtl[((size_t)l * S + k) * 4 + i] = (*Wt)[(size_t)(32 + i) * S + k];
-        // wtok1_hi / lo [l][t][ks][lane][e] = Wt[r = 16t + (lane&15)][r' = 32ks + 8(lane>>4) + e] of ONE pass as bf16 hi / lo planes (ls_pass_kernel.h)
-        for (int t = 0; t < 3; ++t)
-            for (int ks = 0; ks < KS1; ++ks)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 8; ++e) {
-                        const int r = 16 * t + (lane & 15), rp = 32 * ks + 8 * (lane >> 4) + e;
-                        const float v = (r < S && rp < S) ? (*Wt)[(size_t)r * S + rp] : 0.f;
-                        const size_t o = ((((size_t)l * 3 + t) * KS1 + ks) * 64 + lane) * 8 + e;
-                        wt1h[o] = f32_to_bf16(v);
-                        wt1l[o] = f32_to_bf16(v - bf16_to_f32(wt1h[o]));
-                    }
-        // wtok1_img[l][t][mq][lane][j] = Wt[r = 16t + (lane&15)][r' = 4(4mq + j) + (lane>>4)] of ONE pass, zero outside S x S (ls_coop_kernel.h)
-        for (int t = 0; t < 3; ++t)
-            for (int m = 0; m < 4 * MQ1; ++m)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int r = 16 * t + (lane & 15), rp = 4 * m + (lane >> 4);
-                    wt1[((((size_t)l * 3 + t) * MQ1 + (m >> 2)) * 64 + lane) * 4 + (m & 3)] = (r < S && rp < S) ? (*Wt)[(size_t)r * S + rp] : 0.f;
-                }
-    }
-    const auto* Win = find_w(h, "input_mapping.weight", (size_t)D * KIN);        // RAG.py:62
-    const auto* bin = find_w(h, "input_mapping.bias", D);
-    const auto* Wout = find_w(h, "output_process.poseFinal.weight", (size_t)JF * D);   // RAG.py:203
-    const auto* bo = find_w(h, "output_process.poseFinal.bias", JF);
-    if (!Win || !bin || !Wout || !bo) return LS_ESTATE;
-    std::vector<float> winx((size_t)kWaves * 2 * KXQ * 2 * 64 * 4), wout((size_t)NOB * 32 * 64 * 4), bout((size_t)NOB * 16, 0.f);
-    {
-        size_t o = 0;
-        for (int w = 0; w < kWaves; ++w)
-            for (int p = 0; p < 2; ++p)
-                for (int q = 0; q < KXQ; ++q)
-                    for (int c2 = 0; c2 < 2; ++c2)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 4; ++j) {
-                                const int n = 64 * w + 16 * (2 * p + c2) + (lane & 15);
-                                const int k = 16 * q + 4 * (lane >> 4) + j;
-                                winx[o++] = k < JF ? (*Win)[(size_t)n * KIN + k] : 0.f;
-                            }
-        o = 0;
-        for (int ob = 0; ob < NOB; ++ob)
-            for (int q = 0; q < 32; ++q)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j) {
-                        const int c = 16 * ob + (lane & 15);
-                        const int k = 16 * q + 4 * (lane >> 4) + j;
-                        wout[o++] = c < JF ? (*Wout)[(size_t)c * D + k] : 0.f;
-                    }
-        for (int c = 0; c < JF; ++c) bout[c] = (*bo)[c];
-    }
-    // wout_reg_img[w][ob][cb][lane][j] = Wout[c = 16ob + (lane&15)][k = 64w + 16cb + 4(lane>>4) + j]: the k order in which
-    // wave w's residual registers X[cb][.][j] present the hidden state as an MFMA B operand
-    std::vector<float> woutr((size_t)kWaves * NOB * kCB * 64 * 4);
-    {
-        size_t o = 0;
-        for (int w = 0; w < kWaves; ++w)
-            for (int ob = 0; ob < NOB; ++ob)
-                for (int cb = 0; cb < kCB; ++cb)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j) {
-                            const int c = 16 * ob + (lane & 15);
-                            const int k = 64 * w + 16 * cb + 4 * (lane >> 4) + j;
-                            woutr[o++] = c < JF ? (*Wout)[(size_t)c * D + k] : 0.f;
-                        }
-    }
-    int rc;
-    UP(wch_hi_img, wch_hi); UP(wch_lo_img, wch_lo); UP(wch_lo2_img, wch_lo2); UP(ww_hi_img, wwh); UP(ww_lo_img, wwl); UP(wtok1_hi_img, wt1h); UP(wtok1_lo_img, wt1l);
-    UP(wch_img, wch); UP(bch, bch); UP(ln1a, l1a); UP(ln1b, l1b); UP(ln2a, l2a); UP(ln2b, l2b);
-    UP(wtail, wtl);
-    UP(ww_img, ww); UP(wtok1_img, wt1); UP(btok_rows, bt); UP(winx_img, winx); UP(wout_img, wout); UP(wout_reg_img, woutr); UP(bout, bout);
-    DevWeights dw{};
-    dw.wch_img = h->wch_img.f(); dw.bch = h->bch.f(); dw.wsum = h->lw_wsum.f();
-    dw.wch_hi_img = static_cast<const unsigned short*>(h->wch_hi_img.p);
-    dw.wch_lo_img = static_cast<const unsigned short*>(h->wch_lo_img.p);
-    dw.wch_lo2_img = static_cast<const unsigned short*>(h->wch_lo2_img.p);
-    dw.ww_hi_img = static_cast<const unsigned short*>(h->ww_hi_img.p);
-    dw.ww_lo_img = static_cast<const unsigned short*>(h->ww_lo_img.p);
-    dw.ln1a = h->ln1a.f(); dw.ln1b = h->ln1b.f(); dw.ln2a = h->ln2a.f(); dw.ln2b = h->ln2b.f();
-    dw.ww_img = h->ww_img.f(); dw.wtok1_img = h->wtok1_img.f(); dw.btok_rows = h->btok_rows.f();
-    dw.wtail = h->wtail.f();
-    dw.wtok1_hi_img = static_cast<const unsigned short*>(h->wtok1_hi_img.p); dw.wtok1_lo_img = static_cast<const unsigned short*>(h->wtok1_lo_img.p);
-    dw.winx_img = h->winx_img.f(); dw.wout_img = h->wout_img.f(); dw.wout_reg_img = h->wout_reg_img.f(); dw.bout = h->bout.f();
-    if ((rc = upload(h, h->devw, &dw, sizeof dw)) != LS_OK) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return LS_OK;
-}
-
-
-// Weights of the once-per-call stage (audio encoder, static input projection, speaker style, timestep embedder): the same for the
-// fused (34-frame) and the long-sequence path.
-int build_shared_weights(ls_handle* h) {
-    const int JF = h->JF, D = kD, KIN = h->KIN;
-    char key[160];
-    int rc;
-    const auto* Win = find_w(h, "input_mapping.weight", (size_t)D * KIN);        // RAG.py:62
-    const auto* bin = find_w(h, "input_mapping.bias", D);
-    if (!Win || !bin) return LS_ESTATE;
-    UP(win_bias, *bin);
-    {   // the static columns JF.. of input_mapping, split by the features they multiply: [prefix poses | bit] (shared by both CFG
-        // passes; zero-padded to a whole number of K tiles so the projection takes the GEMM's fast path) and the 256 audio columns
-        // (cond pass only)
-        std::vector<float> wp((size_t)D * h->KPP, 0.f), wa((size_t)D * kAudioFeat);
-        for (int n = 0; n < D; ++n) {
-            for (int k = 0; k < JF + 1; ++k) wp[(size_t)n * h->KPP + k] = (*Win)[(size_t)n * KIN + JF + k];
-            for (int k = 0; k < kAudioFeat; ++k) wa[(size_t)n * kAudioFeat + k] = (*Win)[(size_t)n * KIN + 2 * JF + 1 + k];
-        }
-        UP(win_pre, wp); UP(win_aud, wa);
-    }
-    // raw weights used by the once-per-call kernels
-    for (int i = 0; i < 4; ++i) {
-        snprintf(key, sizeof key, "audio_encoder.feat_extractor.%d.weight", kConvKey[i]);
-        const auto* cw = find_w(h, key, (size_t)kConvCout[i] * kConvCin[i] * 15);   // audio_enc.py:9-20
-        snprintf(key, sizeof key, "audio_encoder.feat_extractor.%d.bias", kConvKey[i]);
-        const auto* cb = find_w(h, key, kConvCout[i]);
-        if (!cw || !cb) return LS_ESTATE;
-        UP(conv_w[i], *cw); UP(conv_b[i], *cb);
-        if (i > 0) {
-            // image [co tile][chunk][k][lane][cig]: W[co = 16*ct + (lane&15)][ci = 16*chunk + 4*cig + (lane>>4)][k]
-            const int Cin = kConvCin[i], Cout = kConvCout[i], nchunk = Cin / 16;
-            std::vector<float> img((size_t)Cout * Cin * 15 / 16 * 16);
-            size_t o = 0;
-            for (int ct = 0; ct < Cout / 16; ++ct)
-                for (int ch = 0; ch < nchunk; ++ch)
-                    for (int k = 0; k < 15; ++k)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int cig = 0; cig < 4; ++cig) {
-                                const int co = 16 * ct + (lane & 15), ci = 16 * ch + 4 * cig + (lane >> 4);
-                                img[o++] = (*cw)[((size_t)co * Cin + ci) * 15 + k];
-                            }
-            UP(conv_img[i], img);
-        }
-    }
-    const auto* se = find_w(h, "speaker_embedding.weight", (size_t)h->cfg.n_speakers * 256);   // RAG.py:65-69
-    const auto* mw = find_w(h, "speaker_mu.weight", (size_t)D * 256);
-    const auto* mb = find_w(h, "speaker_mu.bias", D);
-    const auto* lw = find_w(h, "speaker_logvar.weight", (size_t)D * 256);
-    const auto* lb = find_w(h, "speaker_logvar.bias", D);
-    const auto* t0w = find_w(h, "backbone.embed_timestep.time_embed.0.weight", (size_t)D * D);   // mlp_module.py:129-133
-    const auto* t0b = find_w(h, "backbone.embed_timestep.time_embed.0.bias", D);
-    const auto* t2w = find_w(h, "backbone.embed_timestep.time_embed.2.weight", (size_t)D * D);
-    const auto* t2b = find_w(h, "backbone.embed_timestep.time_embed.2.bias", D);
-    if (!se || !mw || !mb || !lw || !lb || !t0w || !t0b || !t2w || !t2b) return LS_ESTATE;
-    UP(spk_emb, *se);
-    {   // speaker_mu and speaker_logvar as ONE [1024][256] projection (rows 0..511 mu, 512..1023 logvar): one launch instead of three
-        std::vector<float> w2(mw->begin(), mw->end()), b2(mb->begin(), mb->end());
-        w2.insert(w2.end(), lw->begin(), lw->end());
-        b2.insert(b2.end(), lb->begin(), lb->end());
-        UP(ml_w, w2); UP(ml_b, b2);
-    }
-    UP(te_w0, *t0w); UP(te_b0, *t0b); UP(te_w2, *t2w); UP(te_b2, *t2b);
-    if (h->cfg.n_emotions > 0) {
-        const auto* ee = find_w(h, "emotion_embedding.weight", (size_t)h->cfg.n_emotions * D);   // scripts_beat/model/RAG.py:72
-        if (!ee) return LS_ESTATE;
-        UP(emo_emb, *ee);
-    }
-    // PositionalEncoding buffer (mlp_module.py:104-116), fp32 like the torch buffer
-    {
-        const std::vector<float> pe = pe_table(kPeRows, D);
-        if ((rc = upload(h, h->pe, pe.data(), pe.size() * sizeof(float))) != LS_OK) return rc;
-    }
-    return LS_OK;
-}
-
-// Long-sequence path (nframes != 34, ls_long.hip): plain row-major weights for the batch-level kernels.
-int build_long_weights(ls_handle* h) {
-    const int L = h->cfg.layers, S = h->S, JF = h->JF, D = kD, KIN = h->KIN, JFP = h->JFP;
-    std::vector<float> wt((size_t)L * S * S), bt((size_t)L * S), wc((size_t)L * D * D), bc((size_t)L * D), l1a((size_t)L * D), l1b((size_t)L * D),
-        l2a((size_t)L * D), l2b((size_t)L * D);
-    char key[160];
-    for (int l = 0; l < L; ++l) {
-        auto K = [&](const char* suffix) { snprintf(key, sizeof key, "backbone.mlps.%d.%s", l, suffix); return std::string(key); };
-        const auto* W = find_w(h, K("block2.1.weight"), (size_t)D * D);
-        const auto* b2 = find_w(h, K("block2.1.bias"), D);
-        const auto* Wt = find_w(h, K("block1.1.weight"), (size_t)S * S);
-        const auto* b1 = find_w(h, K("block1.1.bias"), S);
-        const auto* a1 = find_w(h, K("block1.0.alpha"), D);
-        const auto* be1 = find_w(h, K("block1.0.beta"), D);
-        const auto* a2 = find_w(h, K("block2.0.alpha"), D);
-        const auto* be2 = find_w(h, K("block2.0.beta"), D);
-        if (!W || !b2 || !Wt || !b1 || !a1 || !be1 || !a2 || !be2) return LS_ESTATE;
-        memcpy(&wc[(size_t)l * D * D], W->data(), (size_t)D * D * sizeof(float));
-        memcpy(&bc[(size_t)l * D], b2->data(), D * sizeof(float));
-        memcpy(&wt[(size_t)l * S * S], Wt->data(), (size_t)S * S * sizeof(float));
-        memcpy(&bt[(size_t)l * S], b1->data(), S * sizeof(float));
-        memcpy(&l1a[(size_t)l * D], a1->data(), D * sizeof(float));
-        memcpy(&l1b[(size_t)l * D], be1->data(), D * sizeof(float));
-        memcpy(&l2a[(size_t)l * D], a2->data(), D * sizeof(float));
-        memcpy(&l2b[(size_t)l * D], be2->data(), D * sizeof(float));
-    }
-    const auto* Win = find_w(h, "input_mapping.weight", (size_t)D * KIN);
-    const auto* Wout = find_w(h, "output_process.poseFinal.weight", (size_t)JF * D);
-    const auto* bo = find_w(h, "output_process.poseFinal.bias", JF);
-    if (!Win || !Wout || !bo) return LS_ESTATE;
-    std::vector<float> winx((size_t)D * JFP, 0.f);                                      // x_t columns, K padded to whole GEMM tiles
-    for (int n = 0; n < D; ++n)
-        for (int k = 0; k < JF; ++k) winx[(size_t)n * JFP + k] = (*Win)[(size_t)n * KIN + k];
-    int rc;
-    if (S <= 160) {                                                                     // operand image of the fused token-mixing kernel
-        // per-lane fragment order: img[l][q][mt][lane = s16 + 16 g][e] = Wt[l][16 mt + s16][16 q + 4 g + e], zero beyond S; the token
-        // axis is padded to 48 (three tiles: the reference's 35 / 36 tokens) or to 160
-        const int P = S <= 48 ? 48 : 160, NT = P / 16;
-        h->tokpad = P;
-        std::vector<float> wtp((size_t)L * P * P, 0.f);
-        for (int l = 0; l < L; ++l)
-            for (int q = 0; q < NT; ++q)
-                for (int mt = 0; mt < NT; ++mt)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 4; ++e) {
-                            const int r = 16 * mt + (lane & 15), k = 16 * q + 4 * (lane >> 4) + e;
-                            if (r < S && k < S) wtp[(size_t)l * P * P + (((size_t)q * NT + mt) * 64 + lane) * 4 + e] = wt[((size_t)l * S + r) * S + k];
-                        }
-        UP(lw_wtp, wtp);
+    // one upload: a handle buffer and the host bytes that go into it (every source lives until the closing wait)
+    struct Up { DevBuf* buf; const void* src; size_t bytes; };
+    std::vector<Up> ups;
+    auto up = [&](DevBuf& b, const auto& v) { ups.push_back({&b, v.data(), v.size() * sizeof(v[0])}); };
+    auto raw = [&](DevBuf& b, const float* p, size_t n) { ups.push_back({&b, p, n * sizeof(float)}); };
+    const LongImages lg = long_images(w, d);
+    const Ln2Fold f = fold_ln2(w, d);
+    up(h->lw_wt, lg.lw_wt); up(h->lw_bt, lg.lw_bt); up(h->lw_wc, lg.lw_wc); up(h->lw_bc, lg.lw_bc); up(h->lw_winx, lg.lw_winx); up(h->lw_wout, lg.lw_wout);
+    up(h->ln1a, lg.ln1a); up(h->ln1b, lg.ln1b); up(h->ln2a, lg.ln2a); up(h->ln2b, lg.ln2b);
+    Img wtp;
+    if (d.S <= 160) {       // the fused token-mixing kernel's operand, its token axis padded to 48 (three tiles: the reference's 35 / 36 tokens)
+                            // or to 160, and LayerNorm 2 folded around the channel-mixing product (ls_long.hip)
+        h->tokpad = d.S <= 48 ? 48 : 160;
+        wtp = lw_wtp(w, d, h->tokpad);
+        up(h->lw_wtp, wtp); up(h->lw_wcf, f.w); up(h->lw_bcf, f.b); up(h->lw_wsum, f.wsum);
     } else {
         h->lw_wtp.release();
     }
-    UP(lw_wt, wt); UP(lw_bt, bt); UP(lw_wc, wc); UP(lw_bc, bc); UP(ln1a, l1a); UP(ln1b, l1b); UP(ln2a, l2a); UP(ln2b, l2b);
-    if (!h->fused && mix_supports(S)) {
-        // operand images of the one-launch mixer (ls_mix_kernel.h).  wtok[l][q][mt][lane][e] = Wt[16 mt + s16][16 q + 4 e + g] (zero beyond S):
-        // the four lane groups of an MFMA k step read four CONSECUTIVE rows of the LDS operand; wch[l][gb][q][lane][j] = W'[16 gb + s16][16 q + 4 g + j]
-        std::vector<float> wtk((size_t)L * 100 * 256, 0.f), wch((size_t)L * D * D);
-        for (int l = 0; l < L; ++l) {
-            for (int q = 0; q < 10; ++q)
-                for (int mt = 0; mt < 10; ++mt)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 4; ++e) {
-                            const int r = 16 * mt + (lane & 15), k = 16 * q + 4 * e + (lane >> 4);
-                            if (r < S && k < S) wtk[(size_t)l * 25600 + (((size_t)q * 10 + mt) * 64 + lane) * 4 + e] = wt[((size_t)l * S + r) * S + k];
-                        }
-            for (int gb = 0; gb < 32; ++gb)
-                for (int q = 0; q < 32; ++q)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j) {
-                            const int n = 16 * gb + (lane & 15), k = 16 * q + 4 * (lane >> 4) + j;
-                            wch[(size_t)l * D * D + (((size_t)gb * 32 + q) * 64 + lane) * 4 + j] = wc[((size_t)l * D + n) * D + k] * l2a[(size_t)l * D + k];
-                        }
-        }
-        UP(mx_wtok, wtk); UP(mx_wch, wch);
+    const MixerImages mx = d.mixer ? mixer_images(w, f, d) : MixerImages{};
+    if (d.mixer) { up(h->mx_wtok, mx.mx_wtok); up(h->mx_wch, mx.mx_wch); }
+    h->mx_npt = d.mixer && (d.JF + 15) / 16 <= 20 ? (d.JF + 15) / 16 : 0;     // poseFinal runs inside the mixer, or stays a GEMM (0)
+    const Img wpose = mx_wpose(w, d, h->mx_npt);
+    if (h->mx_npt > 0) up(h->mx_wpose, wpose);
+    const FusedImages fu = d.fused ? fused_images(w, f, d) : FusedImages{};
+    if (d.fused) {
+        up(h->wch_hi_img, fu.wch_hi_img); up(h->wch_lo_img, fu.wch_lo_img); up(h->wch_lo2_img, fu.wch_lo2_img); up(h->ww_hi_img, fu.ww_hi_img);
+        up(h->ww_lo_img, fu.ww_lo_img); up(h->wtok1_hi_img, fu.wtok1_hi_img); up(h->wtok1_lo_img, fu.wtok1_lo_img);
+        up(h->wch_img, fu.wch_img); up(h->bch, f.b); up(h->wtail, fu.wtail); up(h->ww_img, fu.ww_img); up(h->wtok1_img, fu.wtok1_img);
+        up(h->btok_rows, fu.btok_rows); up(h->winx_img, fu.winx_img); up(h->wout_img, fu.wout_img); up(h->wout_reg_img, fu.wout_reg_img); up(h->bout, fu.bout);
+    } else {
+        raw(h->bout, w.b_out, d.JF);
     }
-    if (S <= 160) {     // fused form: LayerNorm 2 folded around the channel-mixing product (ls_long.hip): W' = W diag(alpha2), bias' = b + W beta2,
-                        // wsum[n] = sum_k W'[n][k] (the row's mean enters the epilogue as  - mean * wsum)
-        std::vector<float> wcf((size_t)L * D * D), bcf((size_t)L * D), wsum((size_t)L * D);
-        for (int l = 0; l < L; ++l)
-            for (int n = 0; n < D; ++n) {
-                double sb = bc[(size_t)l * D + n], sw = 0.0;
-                for (int k = 0; k < D; ++k) {
-                    const float wv = wc[((size_t)l * D + n) * D + k];
-                    const float wf = wv * l2a[(size_t)l * D + k];
-                    wcf[((size_t)l * D + n) * D + k] = wf;
-                    sb += (double)wv * (double)l2b[(size_t)l * D + k];
-                    sw += (double)wf;
-                }
-                bcf[(size_t)l * D + n] = (float)sb;
-                wsum[(size_t)l * D + n] = (float)sw;
-            }
-        UP(lw_wcf, wcf); UP(lw_bcf, bcf); UP(lw_wsum, wsum);
+    // once-per-call stage (audio encoder, static input projection, speaker style, timestep embedder): the same for both paths
+    const CallImages ca = call_images(w, d);
+    const size_t D = kD;
+    raw(h->win_bias, w.b_in, D); up(h->win_pre, ca.win_pre); up(h->win_aud, ca.win_aud);
+    for (int i = 0; i < 4; ++i) {
+        raw(h->conv_w[i], w.conv_w[i], (size_t)kConvCout[i] * kConvCin[i] * 15); raw(h->conv_b[i], w.conv_b[i], kConvCout[i]);
+        if (i > 0) up(h->conv_img[i], ca.conv_img[i]);
     }
-    // poseFinal rows padded with zero rows to whole 128-column GEMM tiles: N = 282 would send the product down the general staging
-    // path (41 TFLOP/s at 9728 rows); as 384 columns it is a full-tile LDS-DMA product, the extra columns are never read
-    const int JFN = (JF + 127) / 128 * 128;
-    std::vector<float> woutp((size_t)JFN * D, 0.f);
-    memcpy(woutp.data(), Wout->data(), (size_t)JF * D * sizeof(float));
-    UP(lw_winx, winx); UP(lw_wout, woutp); UP(bout, *bo);
-    h->mx_npt = 0;
-    if (!h->fused && mix_supports(S) && (JF + 15) / 16 <= 20) {
-        // poseFinal inside the mixer: wpose[nb][q][lane][j] = Wout[16 nb + s16][16 q + 4 g + j], zero rows beyond JF
-        const int npt = (JF + 15) / 16;
-        std::vector<float> wp((size_t)npt * 32 * 256, 0.f);
-        for (int nb = 0; nb < npt; ++nb)
-            for (int q = 0; q < 32; ++q)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j) {
-                        const int n = 16 * nb + (lane & 15), k = 16 * q + 4 * (lane >> 4) + j;
-                        if (n < JF) wp[(((size_t)nb * 32 + q) * 64 + lane) * 4 + j] = (*Wout)[(size_t)n * D + k];
-                    }
-        UP(mx_wpose, wp);
-        h->mx_npt = npt;
-    }
-    return LS_OK;
-}
+    raw(h->spk_emb, w.spk_emb, (size_t)d.n_speakers * 256); up(h->ml_w, ca.ml_w); up(h->ml_b, ca.ml_b);
+    raw(h->te_w0, w.te_w0, D * D); raw(h->te_b0, w.te_b0, D); raw(h->te_w2, w.te_w2, D * D); raw(h->te_b2, w.te_b2, D);
+    if (d.n_emotions > 0) raw(h->emo_emb, w.emo_emb, (size_t)d.n_emotions * D);
+    const Img pe = pe_table(kPeRows, kD);      // PositionalEncoding buffer (mlp_module.py:104-116), fp32 like the torch buffer
+    up(h->pe, pe);
 
-int build_images(ls_handle* h) {
-    // a 34-frame model carries both forms: the fused kernel (one workgroup per sample) and the batch-level kernels small batches run on
-    int rc = build_long_weights(h);
+    int rc = LS_OK;
+    for (const Up& u : ups)
+        if ((rc = ingest(h, *u.buf, u.src, u.bytes, 0)) != LS_OK) break;
+    if (rc == LS_OK && d.fused) {
+        DevWeights dw{};
+        auto u16 = [](const DevBuf& b) { return static_cast<const unsigned short*>(b.p); };
+        dw.wch_img = h->wch_img.f(); dw.bch = h->bch.f(); dw.wsum = h->lw_wsum.f();
+        dw.wch_hi_img = u16(h->wch_hi_img); dw.wch_lo_img = u16(h->wch_lo_img); dw.wch_lo2_img = u16(h->wch_lo2_img);
+        dw.ww_hi_img = u16(h->ww_hi_img); dw.ww_lo_img = u16(h->ww_lo_img); dw.wtok1_hi_img = u16(h->wtok1_hi_img); dw.wtok1_lo_img = u16(h->wtok1_lo_img);
+        dw.ln1a = h->ln1a.f(); dw.ln1b = h->ln1b.f(); dw.ln2a = h->ln2a.f(); dw.ln2b = h->ln2b.f();
+        dw.ww_img = h->ww_img.f(); dw.wtok1_img = h->wtok1_img.f(); dw.btok_rows = h->btok_rows.f(); dw.wtail = h->wtail.f();
+        dw.winx_img = h->winx_img.f(); dw.wout_img = h->wout_img.f(); dw.wout_reg_img = h->wout_reg_img.f(); dw.bout = h->bout.f();
+        rc = ingest(h, h->devw, &dw, sizeof dw, 0);
+    }
+    const hipError_t e = hipStreamSynchronize(h->stream);      // the copies read host memory that dies with this call: wait on every exit
     if (rc != LS_OK) return rc;
-    if (h->fused && (rc = build_fused_images(h)) != LS_OK) return rc;
-    if ((rc = build_shared_weights(h)) != LS_OK) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, e);
     return LS_OK;
 }
 

@@ -1,5 +1,5 @@
-// Host-only declarations shared by the translation units behind the sampling ABI of include/ls_hip.h (ls_api.cpp: handle, weights,
-// schedule, preparation; ls_plan.cpp: the step plan and the step launchers; ls_sample.cpp: the diffusion loop and the single-step
+// Host-only declarations shared by the translation units behind the sampling ABI of include/ls_hip.h (ls_api.cpp: handle, weight commit,
+// schedule, preparation -- the weight images themselves are built by ls_weights.cpp, which sees neither HIP nor this header; ls_plan.cpp: the step plan and the step launchers; ls_sample.cpp: the diffusion loop and the single-step
 // entries): the handle, copies between caller and internal buffers, and the guard of buffers a captured loop holds by address.
 // The device buffer (DevBuf) and the error path (fail, HIPCHK) are those of every handle: ls_host.h.
 #pragma once

@@ -15,6 +15,7 @@
 #include "ls_host.h"
 #include "ls_internal.h"
 #include "ls_train.h"
+#include "ls_weights.h"
 
 using namespace ls;
 
@@ -30,7 +31,6 @@ struct BatchIn {
 
 struct Param { std::string key; int64_t off, n; };
 
-const int kCin[4] = {1, 32, 64, 128}, kCout[4] = {32, 64, 128, 256}, kStride[4] = {5, 6, 6, 6}, kPad[4] = {1600, 0, 0, 0}, kKey[4] = {0, 3, 6, 9};
 #ifndef LS_TRAIN_FORK_DEFAULT
 #define LS_TRAIN_FORK_DEFAULT 1      // A/B builds: 0 = the whole backward on one stream
 #endif
@@ -88,8 +88,6 @@ void add_param(ls_trainer* h, const std::string& key, int64_t n) {
 
 float* P(ls_trainer* h, const std::string& key) { return h->P.f() + h->table[h->index.at(key)].off; }
 float* Gr(ls_trainer* h, float* grad, const std::string& key) { return grad + h->table[h->index.at(key)].off; }
-std::string lk(int l, const char* s) { return "backbone.mlps." + std::to_string(l) + "." + s; }
-std::string ck(int i, const char* s) { return "audio_encoder.feat_extractor." + std::to_string(kKey[i]) + "." + s; }
 
 // Batch inputs: host arrays are copied in; device tensors are read in place (the call is synchronous, the caller's tensors outlive it,
 // and no kernel writes them) -- ten device-to-device copies per step otherwise, the 74 MB waveform among them.  A host input points
@@ -168,10 +166,10 @@ int ensure_batch(ls_trainer* h, int B) {
     HIPCHK(h, E(h->drop.own, B)); HIPCHK(h, E(h->eps.own, (size_t)B * kD)); HIPCHK(h, E(h->audio.own, (size_t)B * L[0]));
     HIPCHK(h, h->vid.own.ensure((size_t)B * 8)); HIPCHK(h, h->emo.own.ensure((size_t)B * d0.T * 8)); HIPCHK(h, h->tidx.ensure((size_t)B * 8));
     HIPCHK(h, E(h->ca, B)); HIPCHK(h, E(h->cb, B));
-    for (int i = 0; i < 4; ++i) HIPCHK(h, E(h->c[i], (size_t)B * kCout[i] * L[i + 1]));
+    for (int i = 0; i < 4; ++i) HIPCHK(h, E(h->c[i], (size_t)B * kConvCout[i] * L[i + 1]));
     // (dc[0], the gradient of conv1's output, is never materialised: its only consumer, conv1's weight gradient, is folded into the
     //  epilogue of conv2's data gradient -- 517 MB at B = 512)
-    for (int i = 0; i < 3; ++i) { HIPCHK(h, E(h->st[i], (size_t)B * kCout[i] * 2)); if (i) HIPCHK(h, E(h->dc[i], (size_t)B * kCout[i] * L[i + 1])); }
+    for (int i = 0; i < 3; ++i) { HIPCHK(h, E(h->st[i], (size_t)B * kConvCout[i] * 2)); if (i) HIPCHK(h, E(h->dc[i], (size_t)B * kConvCout[i] * L[i + 1])); }
     HIPCHK(h, E(h->wmom, (size_t)B * wav_moment_parts(L[1]) * 256));
     HIPCHK(h, E(h->feat, (size_t)B * d0.T * d0.KFP)); HIPCHK(h, E(h->wpad, (size_t)kD * d0.KFP)); HIPCHK(h, E(h->waT, (size_t)kAud * kD));
     HIPCHK(h, E(h->zc, (size_t)B * kSpk)); HIPCHK(h, E(h->dzc, (size_t)B * kSpk));
@@ -189,13 +187,13 @@ int ensure_batch(ls_trainer* h, int B) {
     // runs does not grow with the batch) and of conv1's, and the InstanceNorm partials of the forward convs
     size_t colmax = 0;
     for (int i = 1; i < 4; ++i) {
-        const size_t need = (size_t)conv_wgrad_groups(kCin[i], kCout[i]) * kCout[i] * kCin[i] * 15;
+        const size_t need = (size_t)conv_wgrad_groups(kConvCin[i], kConvCout[i]) * kConvCout[i] * kConvCin[i] * 15;
         if (need > colmax) colmax = need;
     }
     const size_t c1need = (size_t)B * (2 * (((L[1] + 5) / 6 + 63) / 64) * 512 + 128 + 480);     // conv1's S1 tile partials + row coefficients + per-sample gradients
     if (c1need > colmax) colmax = c1need;
     for (int i = 0; i < 3; ++i) {       // InstanceNorm partials of the forward convs
-        const size_t need = (size_t)B * kCout[i] * ((L[i + 1] + 63) / 64) * 4 * 3;
+        const size_t need = (size_t)B * kConvCout[i] * ((L[i + 1] + 63) / 64) * 4 * 3;
         if (need > colmax) colmax = need;
     }
     HIPCHK(h, E(h->col, colmax));
@@ -233,17 +231,17 @@ static int train_forward(ls_trainer* h, const TrainDims& d) {
     TRAIN_LOCALS(h, d);
     // WavEncoder (audio_enc.py:9-25): raw conv outputs + InstanceNorm statistics are kept for the backward
     // (the column buffer is free during the forward: it serves as the statistics-partials workspace)
-    HIPCHK(h, launch_conv1_fwd(h->audio.f(), P(h, ck(0, "weight")), P(h, ck(0, "bias")), h->c[0].f(), h->st[0].f(), h->col.f(), B, L[0], L[1],
-                               kPad[0], st));
+    HIPCHK(h, launch_conv1_fwd(h->audio.f(), P(h, conv_key(0, "weight")), P(h, conv_key(0, "bias")), h->c[0].f(), h->st[0].f(), h->col.f(), B, L[0], L[1],
+                               kConvPad[0], st));
     {   // the stride-6 layers' operand images (forward / weight gradient and data gradient), rebuilt from the master weights: one launch
-        const float* w3[3] = {P(h, ck(1, "weight")), P(h, ck(2, "weight")), P(h, ck(3, "weight"))};
+        const float* w3[3] = {P(h, conv_key(1, "weight")), P(h, conv_key(2, "weight")), P(h, conv_key(3, "weight"))};
         float* im[3] = {h->img[1].f(), h->img[2].f(), h->img[3].f()};
         float* dm[3] = {h->dimg[1].f(), h->dimg[2].f(), h->dimg[3].f()};
-        HIPCHK(h, launch_build_conv_imgs(w3, im, dm, kCin + 1, kCout + 1, st));
+        HIPCHK(h, launch_build_conv_imgs(w3, im, dm, kConvCin + 1, kConvCout + 1, st));
     }
     for (int i = 1; i < 4; ++i) {
-        HIPCHK(h, launch_conv1d_mfma(h->c[i - 1].f(), h->st[i - 1].f(), h->img[i].f(), P(h, ck(i, "bias")), h->c[i].f(), i < 3 ? h->st[i].f() : nullptr,
-                                     h->col.f(), B, kCin[i], kCout[i], L[i], L[i + 1], st));
+        HIPCHK(h, launch_conv1d_mfma(h->c[i - 1].f(), h->st[i - 1].f(), h->img[i].f(), P(h, conv_key(i, "bias")), h->c[i].f(), i < 3 ? h->st[i].f() : nullptr,
+                                     h->col.f(), B, kConvCin[i], kConvCout[i], L[i], L[i + 1], st));
     }
     HIPCHK(h, launch_build_feat_train(h->x_start.f(), h->noise.f(), h->origin_x.f(), h->c[3].f(), h->drop.f(), h->hostpack.f(), h->hostpack.f() + B, h->feat.f(),
                                       h->x_t.f(), d, h->cfg.model.n_pre_seq, st));
@@ -417,40 +415,40 @@ static int train_backward_audio(ls_trainer* h, const TrainDims& d, float* grad) 
     TRAIN_LOCALS(h, d);
     // WavEncoder backward, last layer first.  dC4(b, co, p) = dAf[(b*T + p)][co]
     {
-        const int W4 = kCin[3] * 15;
+        const int W4 = kConvCin[3] * 15;
         // dC4(b, co, p) = dAf[(b*T + p)][co]: transposed once to [b][co][p] so that both gradients stage position-contiguous rows
         // (rounds 1-2 read it in place: a 1 KB stride between the lanes of every load)
         HIPCHK(h, launch_transpose_rc(h->dAf.f(), h->dAt.f(), B, T, kAud, st));
         int ng = 0;                       // implicit GEMM like conv2 / conv3 (rounds 1-2: im2col + GEMM, 105 + 188 us at B = 512)
-        HIPCHK(h, launch_conv_wgrad(h->dAt.f(), (long long)T * kAud, T, h->c[2].f(), h->st[2].f(), h->col.f(), B, kCin[3], kCout[3], L[3], L[4], &ng, st));
-        HIPCHK(h, launch_partial_reduce(h->col.f(), ng, (long long)kCout[3] * W4, kCout[3] * W4, Gr(h, grad, ck(3, "weight")), 0, st));
-        HIPCHK(h, colsum_to(h, h->dAf.f(), INT_MAX, 0, kAud, BT, kAud, Gr(h, grad, ck(3, "bias"))));
+        HIPCHK(h, launch_conv_wgrad(h->dAt.f(), (long long)T * kAud, T, h->c[2].f(), h->st[2].f(), h->col.f(), B, kConvCin[3], kConvCout[3], L[3], L[4], &ng, st));
+        HIPCHK(h, launch_partial_reduce(h->col.f(), ng, (long long)kConvCout[3] * W4, kConvCout[3] * W4, Gr(h, grad, conv_key(3, "weight")), 0, st));
+        HIPCHK(h, colsum_to(h, h->dAf.f(), INT_MAX, 0, kAud, BT, kAud, Gr(h, grad, conv_key(3, "bias"))));
         // data gradient: implicit GEMM + LeakyReLU' + InstanceNorm backward
         HIPCHK(h, launch_conv_dgrad(h->dAt.f(), (long long)T * kAud, T, 1, h->dimg[3].f(), h->c[2].f(), h->st[2].f(), h->dc[2].f(), part, B,
-                                    kCin[3], kCout[3], L[3], L[4], true, nullptr, st));
+                                    kConvCin[3], kConvCout[3], L[3], L[4], true, nullptr, st));
     }
     for (int i = 2; i >= 1; --i) {      // conv3 (i=2), conv2 (i=1): dC_i = dc[i] [B][Cout_i][L_{i+1}]
-        const int C = kCout[i], Lo = L[i + 1], W = kCin[i] * 15;
+        const int C = kConvCout[i], Lo = L[i + 1], W = kConvCin[i] * 15;
         {   // weight gradient: implicit GEMM straight from the raw conv output of the layer below (no im2col)
             int ng = 0;
-            HIPCHK(h, launch_conv_wgrad(h->dc[i].f(), (long long)C * Lo, Lo, h->c[i - 1].f(), h->st[i - 1].f(), h->col.f(), B, kCin[i], C, L[i], Lo, &ng,
+            HIPCHK(h, launch_conv_wgrad(h->dc[i].f(), (long long)C * Lo, Lo, h->c[i - 1].f(), h->st[i - 1].f(), h->col.f(), B, kConvCin[i], C, L[i], Lo, &ng,
                                         st));
-            HIPCHK(h, launch_partial_reduce(h->col.f(), ng, (long long)C * W, C * W, Gr(h, grad, ck(i, "weight")), 0, st));
+            HIPCHK(h, launch_partial_reduce(h->col.f(), ng, (long long)C * W, C * W, Gr(h, grad, conv_key(i, "weight")), 0, st));
         }
         // (bias gradients of conv1..3 stay exactly 0: a bias that feeds an InstanceNorm cannot change the output; the
         //  reference's autograd returns rounding noise of ~1e-7 there)
         if (i == 2) {
             HIPCHK(h, launch_conv_dgrad(h->dc[i].f(), (long long)C * Lo, Lo, 1, h->dimg[i].f(), h->c[i - 1].f(), h->st[i - 1].f(), h->dc[i - 1].f(), part, B,
-                                        kCin[i], C, L[i], Lo, true, nullptr, st));
+                                        kConvCin[i], C, L[i], Lo, true, nullptr, st));
         } else {
             // conv2's data gradient is consumed only by conv1's weight gradient (conv1's input is data): folded into its epilogue, the
             // gradient tensor itself is never written (k_conv_dgrad<FUSE1>); per-sample results are summed over the batch in index order
             float* outp = nullptr;
             // (on a side stream under the forward's first convs this latency-bound 50 us kernel cost the forward 200 us: measured, not kept)
-            HIPCHK(h, launch_wav_moments(h->audio.f(), h->wmom.f(), B, L[0], L[1], kPad[0], st));
+            HIPCHK(h, launch_wav_moments(h->audio.f(), h->wmom.f(), B, L[0], L[1], kConvPad[0], st));
             HIPCHK(h, launch_conv_dgrad_conv1(h->dc[i].f(), (long long)C * Lo, Lo, 1, h->dimg[i].f(), h->c[0].f(), h->st[0].f(), part, B, C, L[1], Lo,
-                                              h->audio.f(), L[0], kPad[0], h->wmom.f(), P(h, ck(0, "weight")), P(h, ck(0, "bias")), h->col.f(), &outp, st));
-            HIPCHK(h, launch_partial_reduce(outp, B, 480, 480, Gr(h, grad, ck(0, "weight")), 0, st));
+                                              h->audio.f(), L[0], kConvPad[0], h->wmom.f(), P(h, conv_key(0, "weight")), P(h, conv_key(0, "bias")), h->col.f(), &outp, st));
+            HIPCHK(h, launch_partial_reduce(outp, B, 480, 480, Gr(h, grad, conv_key(0, "weight")), 0, st));
         }
     }
     return LS_OK;
@@ -476,13 +474,13 @@ int ls_train_create(const ls_train_config* cfg, ls_trainer** out) {
     d.B = 0; d.T = m.nframes; d.NPRE = m.n_prefix_tokens; d.S = d.T + d.NPRE; d.JF = m.njoints * m.nfeats;
     d.KF = 2 * d.JF + 1 + kAud; d.KFP = (d.KF + 31) / 32 * 32; d.D = kD; d.L = m.layers;      // KFP: whole 32-deep K tiles (the input_mapping product takes the GEMM's LDS-DMA path)
     h->convL[0] = m.audio_len;
-    for (int i = 0; i < 4; ++i) h->convL[i + 1] = (h->convL[i] + 2 * kPad[i] - 15) / kStride[i] + 1;
+    for (int i = 0; i < 4; ++i) h->convL[i + 1] = (h->convL[i] + 2 * kConvPad[i] - 15) / kConvStride[i] + 1;
     if (h->convL[4] != d.T) return abandon(h, ls_train_destroy, fail<ls_trainer>(nullptr, LS_EINVAL, "ls_train_create: audio_len %d gives %d audio frames, need %d", m.audio_len, h->convL[4], d.T));
     for (int l = 0; l < d.L; ++l) {
-        add_param(h, lk(l, "block1.0.alpha"), kD); add_param(h, lk(l, "block1.0.beta"), kD);
-        add_param(h, lk(l, "block1.1.weight"), (int64_t)d.S * d.S); add_param(h, lk(l, "block1.1.bias"), d.S);
-        add_param(h, lk(l, "block2.0.alpha"), kD); add_param(h, lk(l, "block2.0.beta"), kD);
-        add_param(h, lk(l, "block2.1.weight"), (int64_t)kD * kD); add_param(h, lk(l, "block2.1.bias"), kD);
+        add_param(h, layer_key(l, "block1.0.alpha"), kD); add_param(h, layer_key(l, "block1.0.beta"), kD);
+        add_param(h, layer_key(l, "block1.1.weight"), (int64_t)d.S * d.S); add_param(h, layer_key(l, "block1.1.bias"), d.S);
+        add_param(h, layer_key(l, "block2.0.alpha"), kD); add_param(h, layer_key(l, "block2.0.beta"), kD);
+        add_param(h, layer_key(l, "block2.1.weight"), (int64_t)kD * kD); add_param(h, layer_key(l, "block2.1.bias"), kD);
     }
     for (int j : {0, 2}) {
         add_param(h, "backbone.embed_timestep.time_embed." + std::to_string(j) + ".weight", (int64_t)kD * kD);
@@ -492,7 +490,7 @@ int ls_train_create(const ls_train_config* cfg, ls_trainer** out) {
     add_param(h, "speaker_embedding.weight", (int64_t)m.n_speakers * kSpk);
     add_param(h, "speaker_mu.weight", (int64_t)kD * kSpk); add_param(h, "speaker_mu.bias", kD);
     add_param(h, "speaker_logvar.weight", (int64_t)kD * kSpk); add_param(h, "speaker_logvar.bias", kD);
-    for (int i = 0; i < 4; ++i) { add_param(h, ck(i, "weight"), (int64_t)kCout[i] * kCin[i] * 15); add_param(h, ck(i, "bias"), kCout[i]); }
+    for (int i = 0; i < 4; ++i) { add_param(h, conv_key(i, "weight"), (int64_t)kConvCout[i] * kConvCin[i] * 15); add_param(h, conv_key(i, "bias"), kConvCout[i]); }
     add_param(h, "output_process.poseFinal.weight", (int64_t)d.JF * kD); add_param(h, "output_process.poseFinal.bias", d.JF);
     if (d.NPRE == 2) add_param(h, "emotion_embedding.weight", (int64_t)m.n_emotions * kD);
 
@@ -522,8 +520,8 @@ int ls_train_create(const ls_train_config* cfg, ls_trainer** out) {
     if ((e = h->pe.ensure(pe.size() * 4)) != hipSuccess) return bail("hipMalloc(pe)", e);
     if ((e = hipMemcpy(h->pe.p, pe.data(), pe.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy(pe)", e);
     for (int i = 1; i < 4; ++i) {
-        if ((e = h->img[i].ensure((size_t)kCout[i] * kCin[i] * 15 * 4)) != hipSuccess) return bail("hipMalloc(img)", e);
-        if ((e = h->dimg[i].ensure((size_t)kCout[i] * kCin[i] * 16 * 4)) != hipSuccess) return bail("hipMalloc(dimg)", e);
+        if ((e = h->img[i].ensure((size_t)kConvCout[i] * kConvCin[i] * 15 * 4)) != hipSuccess) return bail("hipMalloc(img)", e);
+        if ((e = h->dimg[i].ensure((size_t)kConvCout[i] * kConvCin[i] * 16 * 4)) != hipSuccess) return bail("hipMalloc(dimg)", e);
     }
     {   // mixer weight images of the fused training forward (rebuilt from the master parameters every step)
         const int MK = (2 * d.S + 3) / 4;
@@ -537,7 +535,7 @@ int ls_train_create(const ls_train_config* cfg, ls_trainer** out) {
         dw.ln1a = h->tl1a.f(); dw.ln1b = h->tl1b.f(); dw.ln2a = h->tl2a.f(); dw.ln2b = h->tl2b.f();
         if ((e = h->tdevw.ensure(sizeof dw)) != hipSuccess) return bail("hipMalloc(DevWeights)", e);
         if ((e = hipMemcpy(h->tdevw.p, &dw, sizeof dw, hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy(DevWeights)", e);
-        auto off = [&](int l, const char* sfx) { return h->table[h->index.at(lk(l, sfx))].off; };
+        auto off = [&](int l, const char* sfx) { return h->table[h->index.at(layer_key(l, sfx))].off; };
         TrainImgArgs& ia = h->img_args;
         ia.base = off(0, "block1.0.alpha");
         ia.lstride = d.L > 1 ? off(1, "block1.0.alpha") - ia.base : 0;
@@ -743,10 +741,10 @@ int ls_train_read(ls_trainer* h, const char* what, float* out, size_t n) {
     else if (w == "x_last") { src = h->xcur.f(); need = B * d.S * kD; }
     else if (w.size() == 2 && w[0] == 'c' && w[1] >= '1' && w[1] <= '4') {          // raw conv outputs [B][Cout][L]
         const int i = w[1] - '1';
-        src = h->c[i].f(); need = B * kCout[i] * h->convL[i + 1];
+        src = h->c[i].f(); need = B * kConvCout[i] * h->convL[i + 1];
     } else if (w.size() == 3 && w[0] == 's' && w[1] == 't' && w[2] >= '1' && w[2] <= '3') {   // (mean, rstd) per (sample, channel)
         const int i = w[2] - '1';
-        src = h->st[i].f(); need = B * kCout[i] * 2;
+        src = h->st[i].f(); need = B * kConvCout[i] * 2;
     }
     else return fail(h, LS_EINVAL, "ls_train_read: unknown tensor '%s'", what);
     if (n != need) return fail(h, LS_EINVAL, "ls_train_read: '%s' has %zu elements, buffer has %zu", what, need, n);

@@ -324,3 +324,59 @@ def test_handle_lifecycle_of_every_wrapper():
         eng.load_state_dict(sd)
         del eng
         gc.collect()
+
+
+# ------------------------------------------------------------------------------------------------
+# ls_commit_weights resolves, builds and uploads in that order: a second commit on a live handle must leave nothing of the first
+def _swap_layers(sd):
+    out = dict(sd)
+    for k, v in sd.items():
+        if k.startswith("backbone.mlps.0."):
+            other = "backbone.mlps.1." + k[len("backbone.mlps.0."):]
+            out[k], out[other] = sd[other], v
+    return out
+
+
+@pytest.mark.engine_path_auto
+@pytest.mark.parametrize("model,B,path,precision", [
+    ("ted", 3, "fused", "fp32"), ("ted", 3, "pass", "fp32"), ("ted", 3, "coop", "fp32"), ("ted", 3, "batch", "fp32"),
+    ("ted", 3, "pass", "bf16x3"), ("beat150", 2, "coop", "fp32"), ("beat150", 2, "batch", "fp32")])
+def test_reloaded_weights_equal_a_fresh_engine(model, B, path, precision):
+    """Every image family is read once: fused / pass / coop / batch of a 34-frame model (pass under bf16x3 reads the hi / lo planes),
+    the mixer (coop) and the batch-level kernels of the 150-frame one.  Batch 3 has a paired workgroup and a single tail."""
+    import dataclasses
+    from livelyspeaker_amd import _lib
+    from oracle import rag_oracle as orc
+    cfg = dataclasses.replace(synth.CONFIGS[model], layers=2)
+    sd = synth.make_state_dict(cfg)
+    swapped = _swap_layers(sd)
+    assert not np.array_equal(sd["backbone.mlps.0.block2.1.weight"], swapped["backbone.mlps.0.block2.1.weight"])
+    y = synth.make_cond(cfg, B)
+
+    def engine(weights):
+        eng = _lib.Engine(cfg.njoints, cfg.nfeats, cfg.n_prefix_tokens, cfg.audio_len, n_emotions=cfg.n_emotions, nframes=cfg.nframes,
+                          layers=cfg.layers)
+        eng.set_path(path)
+        eng.set_precision(precision)
+        eng.load_state_dict(weights)
+        eng.set_schedule(orc.Schedule(3, ""))
+        return eng
+
+    def sample(eng):
+        eng.prepare(y)
+        return eng.sample(sampler=_lib.LS_SAMPLER_DDPM, philox_seed=1234, sample_offset=2)
+
+    eng = engine(sd)
+    try:
+        first = sample(eng)
+        eng.load_state_dict(swapped)
+        second = sample(eng)
+    finally:
+        eng.close()
+    fresh_eng = engine(swapped)
+    try:
+        fresh = sample(fresh_eng)
+    finally:
+        fresh_eng.close()
+    assert np.isfinite(second).all() and np.array_equal(second, fresh)
+    assert not np.array_equal(second, first)

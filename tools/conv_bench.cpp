@@ -48,7 +48,7 @@ int main(int argc, char** argv) {
         for (size_t i = 0; i < nw; ++i) hw[i] = frand(i, 40503u) * 0.2f;
         for (int i = 0; i < co; ++i) hb[i] = frand(i, 97u);
         for (size_t r = 0; r < (size_t)B * ci; ++r) { hst[2 * r] = frand(r, 31u) * 0.1f; hst[2 * r + 1] = 1.5f + frand(r, 17u); }
-        // image [co tile][chunk][k][lane][cig] = W[co = 16 ct + (lane & 15)][ci = 16 chunk + 4 cig + (lane >> 4)][k]  (ls_api.cpp build_shared_weights)
+        // image [co tile][chunk][k][lane][cig] = W[co = 16 ct + (lane & 15)][ci = 16 chunk + 4 cig + (lane >> 4)][k]  (ls_weights.cpp conv_img)
         size_t o = 0;
         for (int ct = 0; ct < co / 16; ++ct)
             for (int ch = 0; ch < ci / 16; ++ch)
