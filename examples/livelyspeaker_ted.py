@@ -4,7 +4,8 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
 
     CLIP text feature z (stand-in)  ->  SAG decoder (script-guided motion)  ->  init_image
     RAG + classifier-free guidance, ddim100, skip_timesteps=80 (20 refinement steps conditioned on audio / speaker / prefix poses)
-    ->  post-processing (aligned motions, poses, motion beats)  ->  FGD / diversity against the "real" clips
+    ->  post-processing (aligned motions, poses, motion beats)  ->  FGD / diversity against the "real" clips, and the
+        beat-consistency score against the onsets detected in the clips' audio on the device
 
     python examples/livelyspeaker_ted.py [batch]
     python examples/livelyspeaker_ted.py [batch] --from-motion
@@ -33,7 +34,7 @@ from livelyspeaker_amd.cfg_sampler import ClassifierFreeSampleModel             
 from livelyspeaker_amd.model_util import create_model_and_diffusion, load_model_wo_clip   # noqa: E402
 from livelyspeaker_amd.motionclip import get_SAG                                      # noqa: E402
 from livelyspeaker_amd.motionclip_module import Decoder_TRANSFORMER                   # noqa: E402
-from livelyspeaker_amd.postprocess import ted_postprocess                             # noqa: E402
+from livelyspeaker_amd.postprocess import BeatConsistency, ted_postprocess            # noqa: E402
 from livelyspeaker_amd.ted_evaluator import EmbeddingSpaceEvaluator                   # noqa: E402
 
 
@@ -171,8 +172,12 @@ def main():
         evaluator.push_samples(post["aligned_motions"][i:i + 64], real[i:i + 64])
     fgd, feat_dist = evaluator.get_scores() if B > 32 else (float("nan"), float("nan"))
     n_beats = sum(len(b) for b in post["motion_beat_times"])
+    bc = BeatConsistency()                                                                  # test_RAG_ted.py:112-127
+    bc.push(post["motion_beat_times"], audio=cond["y"]["audio_input"], sr=16000)           # onset_detect(y, sr=16000, units='time') per clip, on the device
+    beat_score = bc.score() if bc.num_beats else float("nan")
     print(f"B={B} ({noise_source}): SAG decode + 20-step guided refinement {dt * 1e3:.1f} ms ({B * 34 / dt:.0f} pose-frames/s); "
-          f"motion beats {n_beats}; FGD {fgd:.4f}, feature distance {feat_dist:.4f} (synthetic weights: numbers are not quality)")
+          f"motion beats {n_beats}, audio onsets {bc.num_beats}, BC {beat_score:.4f}; FGD {fgd:.4f}, feature distance {feat_dist:.4f} "
+          f"(synthetic weights and audio: numbers are not quality)")
     assert bool(torch.isfinite(sample).all())
 
 

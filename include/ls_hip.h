@@ -644,6 +644,56 @@ int ls_beat_metrics(int device, const ls_beat_metrics_args* a);
  * is what the export check of the test suite collects them by. */
 int ls_beat_ldiv(int device, int on_device, int64_t rows, int dim, const float* x, double* sum_out);
 
+/* ---- audio onsets for the beat-alignment scores ------------------------------------------------------------
+ * What the reference's scripts take from librosa 0.9.2 (scripts/test_RAG_ted.py:113 onset_detect(y, sr=16000, units='time');
+ * scripts_beat/utils/metric.py:60-74 alignment.load_audio), for a batch of equally long clips:
+ *   frames     y padded by 1024 on both sides (pad_mode), n_fft 2048, hop 512, periodic Hann: F = 1 + length / 512 frames
+ *   mel_db     10 log10(max(1e-10, W P)) with P the power spectrum and W 128 Slaney mel filters on [0, fmax], BEFORE the clip-wide
+ *              clamp to (max - 80) that the envelope applies
+ *   rms        librosa.feature.rms(S=|stft|): sqrt(2 sum_k P'[k] / 2048^2), P' = P with rows 0 and 1024 halved
+ *   oenv       concat(zeros(3), mean over the mels of max(0, S[t+1] - S[t]))[:F], S the clamped mel_db
+ *   onset_raw  util.peak_pick on (oenv - min) / (max + tiny) with onset_detect's default windows for sr_pick and hop 512, and delta
+ *   onset_bt, onset_bt_rms   onset_backtrack(onset_raw, oenv) and (onset_raw, rms): the nearest minimum at or before each onset
+ * Two kernels: one wave per frame for the spectrum (a 1024-point complex FFT in LDS, mel sums gathered per filter in a fixed
+ * order), one workgroup per clip for everything after it; a clip's numbers do not depend on the batch it travels in.
+ * With `envelope` instead of `audio`, `length` counts frames and the pick runs on the given envelope (onset_detect(onset_envelope=)).
+ * The onset slabs are [B,F] int32 of which the first count[b] entries of row b are valid (the rest is -1).  Every output may be
+ * NULL; kernel_ms is a HOST pointer in both modes.  LS_EINVAL without a launch: NULL args, neither or both inputs, batch < 1,
+ * length < 1, reflect padding with length <= 1024, more than 4096 frames, an unknown pad_mode, fmax <= 0, sr <= 0, sr_pick <= 0,
+ * and mel_db, rms or onset_bt_rms asked for with a given envelope. */
+#define LS_ONSETS_PAD_CONSTANT 0
+#define LS_ONSETS_PAD_REFLECT 1
+#define LS_ONSETS_MAX_FRAMES 4096
+typedef struct ls_onsets_args {
+    int32_t batch;
+    int32_t length;          /* samples per clip; frames per clip when envelope is given                         */
+    int32_t on_device;
+    int32_t pad_mode;        /* LS_ONSETS_PAD_CONSTANT (0.9.2's default) | LS_ONSETS_PAD_REFLECT                   */
+    float sr;                /* of the audio: 16000                                                              */
+    float sr_pick;           /* of the picking windows: 16000 on TED, 22050 on BEAT (load_audio passes no sr)    */
+    float fmax;              /* 11025 in 0.9.x, sr / 2 from 0.10 on                                              */
+    float delta;             /* 0.07                                                                             */
+    const float* audio;      /* [B,length] or NULL                                                               */
+    const float* envelope;   /* [B,length] or NULL                                                               */
+    float* mel_db;           /* [B,F,128]                                                                        */
+    float* rms;              /* [B,F]                                                                            */
+    float* oenv;             /* [B,F]                                                                            */
+    int32_t* count;          /* [B]                                                                              */
+    int32_t* onset_raw;      /* [B,F]                                                                            */
+    int32_t* onset_bt;       /* [B,F]                                                                            */
+    int32_t* onset_bt_rms;   /* [B,F]                                                                            */
+    float* kernel_ms;        /* HOST [2]: the spectrum and the pick kernel, timed with events (0 for one not run) */
+} ls_onsets_args;
+int ls_onsets(int device, const ls_onsets_args* a);
+
+/* The tables ls_onsets computes with, built on the host in double and rounded to float32: window [n_fft] (periodic Hann), twiddle
+ * [n_fft][2] (exp(-2 pi i n / n_fft)), and librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax, htk=False, norm='slaney') in CSR
+ * form: mel_ptr [n_mels + 1], mel_col and mel_w [nnz] (weights that round to 0 are left out).  *nnz_out receives nnz; every
+ * pointer may be NULL, so a first call can ask for nnz alone.  LS_EINVAL: n_fft no power of two, sr <= 0, fmax <= fmin, fmin < 0,
+ * n_mels < 1, nnz_cap < nnz when the CSR arrays are asked for.  No device is touched. */
+int ls_onsets_tables(float sr, int n_fft, int n_mels, float fmin, float fmax, float* window, float* twiddle, int32_t* mel_ptr,
+                     int32_t* mel_col, float* mel_w, int32_t nnz_cap, int32_t* nnz_out);
+
 /* ---- training step ----------------------------------------------------------------
  * One optimisation step of the RAG denoiser as TrainLoop.run_step runs it (scripts/train_utils/train_loop.py:146-186):
  *   x_t = q_sample(x_start, t, noise)                                  gaussian_diffusion.py:1281-1282

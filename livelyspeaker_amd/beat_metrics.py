@@ -5,8 +5,9 @@ planes ``ls_beat_post`` writes.  ``from utils import metric`` becomes ``from liv
 from which only per-clip scalars come back to the host.
 
 Two documented differences: ``L1div.run`` does not overwrite its argument (the reference replaces the caller's rows by
-``|row - mean|``), and audio onsets are an INPUT, as onset times in seconds -- ``alignment.load_audio`` is librosa onset detection,
-a third-party package that is not part of this path (``postprocess.BeatConsistency`` draws the same line on TED).
+``|row - mean|``), and audio onsets are an INPUT here, as onset times in seconds -- ``alignment.load_audio`` of this module
+raises; ``audio_onsets.alignment`` is the subclass that detects them on the device (``ls_onsets``), and ``BeatEvaluator.push`` takes
+``audio=`` through it (``postprocess.BeatConsistency`` does the same on TED).
 """
 from __future__ import annotations
 
@@ -240,14 +241,22 @@ class BeatEvaluator:
         self.latent_out_all, self.latent_ori_all = [], []
         self._out, self._ori = _Moments(), _Moments()
 
-    def push(self, sample, tar_pose, semantic=None, onset_times=None):
+    def push(self, sample, tar_pose, semantic=None, onset_times=None, audio=None, sr_audio=16000, **onset_options):
         """sample [B, joints, 6, 34] as the sampler returns it, tar_pose [B, 34, joints*6] (both CUDA tensors), semantic [B, 34] or
-        None (no SRGR), onset_times: one sequence of seconds per clip or None (no alignment).  Returns this batch's per-clip scalars."""
+        None (no SRGR), onset_times: one sequence of seconds per clip or None (no alignment).  ``audio`` [B, L] instead of
+        onset_times: the onsets are detected on the device as ``alignment.load_audio`` finds them (``audio_onsets``; its pad_mode
+        and fmax pass through ``onset_options``) and scored as frames_to_time(onset_bt_rms).  Returns this batch's per-clip scalars."""
         from .postprocess import beat_postprocess
         B, J = int(sample.shape[0]), self.joints
         if tuple(sample.shape[1:]) != (J, 6, T) or tuple(tar_pose.shape) != (B, T, J * 6):
             raise ValueError(f"expected sample [B, {J}, 6, {T}] and tar_pose [B, {T}, {J * 6}], got {list(sample.shape)} and "
                              f"{list(tar_pose.shape)}")
+        if audio is not None:
+            if onset_times is not None:
+                raise ValueError("pass either onset_times or audio")
+            from . import audio_onsets
+            onset_times = audio_onsets.onset_times(audio, sr_audio, 22050, which="onset_bt_rms", time_sr=22050, device=self.device,
+                                                   **onset_options)
         # a clip without an onset is refused before anything is launched
         ragged = _ragged(onset_times, B) if onset_times is not None else None
         pred = beat_postprocess(sample, self.device)

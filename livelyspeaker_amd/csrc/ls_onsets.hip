@@ -1,0 +1,418 @@
+// Audio onsets for the beat-alignment scores: what the reference's scripts take from librosa 0.9.2 (onset_detect of
+// scripts/test_RAG_ted.py:113, alignment.load_audio of scripts_beat/utils/metric.py:60-74), on the device.
+//   k_onset_spectrum  one wave per frame, four frames per workgroup: gather 2048 samples (the centre padding is index arithmetic),
+//                     window, a 2048-point real FFT as a 1024-point complex Stockham radix-4 FFT in LDS plus the real-FFT post-pass,
+//                     power, rms, and the 128 mel sums gathered per filter from a CSR table in a fixed order -> dB
+//   k_onset_pick      one workgroup per clip: clip-wide clamp, spectral flux, normalisation, peak picking, both backtracks
+// Every sum is a fixed tree (per-lane order, wave butterfly) and a frame never looks at another clip, so a clip's numbers do not
+// depend on the batch it travels in.  The tables come from the host-only unit ls_onsets_tables.cpp.
+#include "ls_hip.h"
+#include "ls_host.h"
+#include "ls_onsets.h"
+
+namespace ls {
+namespace {
+
+constexpr int kNfft = 2048, kHop = 512, kHalf = kNfft / 2, kQuarter = kHalf / 4, kMels = 128;
+constexpr int kWavesPerBlock = 4;
+constexpr int kMaxF = LS_ONSETS_MAX_FRAMES;
+constexpr int kLagShift = 1 + kNfft / (2 * kHop);
+// One padding slot after every 16 complex numbers: the pass with output stride 4 writes 32-byte groups 128 bytes apart, which
+// without the padding all land on the same 8 of the 32 banks a ds_write sees; with it every pass spreads evenly over the banks.
+constexpr int kFrameSlots = kHalf + kHalf / 16;
+
+__device__ __forceinline__ int slot(int i) { return i + (i >> 4); }
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
+
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m));
+    return v;
+}
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+
+struct SpectrumParams {
+    int B, L, F, pad_mode;
+    const float* audio;        // [B, L]
+    const float* window;       // [2048]
+    const float2* twiddle;     // [2048] exp(-2 pi i n / 2048)
+    const int* mel_ptr;        // [129]
+    const int* mel_col;
+    const float* mel_w;
+    float* mel_db;             // [B, F, 128]
+    float* rms;                // [B, F] or NULL
+};
+
+// One Stockham radix-4 pass over the 1024 complex numbers of this wave's frame; v holds the lane's 16 inputs x[j + 256 t] for its
+// four butterflies j = lane + 64 q.  Output t of butterfly j goes to expand(j) + t * Ns, with twiddles exp(-2 pi i k t / (4 Ns)).
+template <int Ns>
+__device__ __forceinline__ void radix4_pass(const float2 (&v)[16], float2* buf, const float2* __restrict__ tw, int lane) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = lane + 64 * q, k = j & (Ns - 1);
+        float2 a0 = v[4 * q], a1 = v[4 * q + 1], a2 = v[4 * q + 2], a3 = v[4 * q + 3];
+        if (Ns > 1) {
+            const int m = 2 * k * (kQuarter / Ns);        // index into the 2048-entry table; 3 m < 1536
+            a1 = cmul(a1, tw[m]);
+            a2 = cmul(a2, tw[2 * m]);
+            a3 = cmul(a3, tw[3 * m]);
+        }
+        const float2 s02 = make_float2(a0.x + a2.x, a0.y + a2.y), d02 = make_float2(a0.x - a2.x, a0.y - a2.y);
+        const float2 s13 = make_float2(a1.x + a3.x, a1.y + a3.y), d13 = make_float2(a1.x - a3.x, a1.y - a3.y);
+        const int j0 = ((j - k) << 2) + k;
+        buf[slot(j0)] = make_float2(s02.x + s13.x, s02.y + s13.y);
+        buf[slot(j0 + Ns)] = make_float2(d02.x + d13.y, d02.y - d13.x);            // d02 - i d13
+        buf[slot(j0 + 2 * Ns)] = make_float2(s02.x - s13.x, s02.y - s13.y);
+        buf[slot(j0 + 3 * Ns)] = make_float2(d02.x - d13.y, d02.y + d13.x);        // d02 + i d13
+    }
+}
+
+__device__ __forceinline__ void load_pass_inputs(float2 (&v)[16], const float2* buf, int lane) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[4 * q + t] = buf[slot(lane + 64 * q + kQuarter * t)];
+}
+
+}  // namespace
+
+// Every wave of a workgroup runs the same sequence of barriers: a wave whose frame lies past the end computes on zeros and
+// stores nothing.
+__global__ __launch_bounds__(64 * kWavesPerBlock) void k_onset_spectrum(const SpectrumParams p) {
+    __shared__ float2 sbuf[kWavesPerBlock][kFrameSlots];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long g = (long long)blockIdx.x * kWavesPerBlock + wave, total = (long long)p.B * p.F;
+    const bool live = g < total;
+    const int b = live ? (int)(g / p.F) : 0, t = live ? (int)(g - (long long)b * p.F) : 0;
+    float2* buf = sbuf[wave];
+    const float* y = p.audio + (size_t)b * p.L;
+
+    // ---- gather and window: complex point n is (y[2n], y[2n + 1]); the lane loads exactly the inputs of its first pass ----
+    float2 v[16];
+    const int base = t * kHop - kHalf;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = lane + 64 * q + kQuarter * r;
+            float s[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                int i = base + 2 * n + h;
+                if (p.pad_mode == LS_ONSETS_PAD_REFLECT) {          // numpy's 'reflect': the edge sample is not repeated
+                    if (i < 0) i = -i;
+                    else if (i >= p.L) i = 2 * (p.L - 1) - i;
+                }
+                s[h] = (live && i >= 0 && i < p.L) ? y[i] * p.window[2 * n + h] : 0.0f;
+            }
+            v[4 * q + r] = make_float2(s[0], s[1]);
+        }
+
+    // ---- 1024-point complex FFT: five radix-4 passes, each reading everything into registers before it writes ----
+    radix4_pass<1>(v, buf, p.twiddle, lane);
+    __syncthreads();
+    load_pass_inputs(v, buf, lane);
+    __syncthreads();
+    radix4_pass<4>(v, buf, p.twiddle, lane);
+    __syncthreads();
+    load_pass_inputs(v, buf, lane);
+    __syncthreads();
+    radix4_pass<16>(v, buf, p.twiddle, lane);
+    __syncthreads();
+    load_pass_inputs(v, buf, lane);
+    __syncthreads();
+    radix4_pass<64>(v, buf, p.twiddle, lane);
+    __syncthreads();
+    load_pass_inputs(v, buf, lane);
+    __syncthreads();
+    radix4_pass<256>(v, buf, p.twiddle, lane);
+    __syncthreads();
+
+    // ---- real-FFT post-pass: X[k] = E + W^k O and X[1024 - k] = conj(E - W^k O), E = (Z[k] + conj Z[1024 - k]) / 2,
+    //      O = -i (Z[k] - conj Z[1024 - k]) / 2; the lane takes k = lane + 64 i, lane 0 also k = 512 ----
+    float pk[9], pn[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const int k = i < 8 ? lane + 64 * i : kHalf / 2;
+        const float2 zk = buf[slot(k)], zn = buf[slot((kHalf - k) & (kHalf - 1))];
+        const float2 e = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
+        const float2 o = make_float2(0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x));
+        const float2 wo = cmul(p.twiddle[k], o);
+        const float ar = e.x + wo.x, ai = e.y + wo.y, br = e.x - wo.x, bi = e.y - wo.y;
+        pk[i] = ar * ar + ai * ai;
+        pn[i] = br * br + bi * bi;
+    }
+    __syncthreads();
+    float* P = reinterpret_cast<float*>(buf);       // 1025 powers over the frame's FFT buffer
+    float s = 0.0f;                                  // rms: rows 0 and 1024 halved, lane order then the wave butterfly
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int k = lane + 64 * i;
+        P[k] = pk[i];
+        P[kHalf - k] = pn[i];
+        s += (k == 0) ? (0.5f * pk[i] + 0.5f * pn[i]) : (pk[i] + pn[i]);
+    }
+    if (lane == 0) {
+        P[kHalf / 2] = pk[8];
+        s += pk[8];
+    }
+    s = wave_sum(s);
+    if (live && p.rms && lane == 0) p.rms[g] = sqrtf(2.0f * s / ((float)kNfft * (float)kNfft));
+    __syncthreads();
+
+    // ---- mel: the lane owns filters lane and 127 - lane (a narrow and a wide one) and adds each one's bins in table order ----
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int f = h == 0 ? lane : kMels - 1 - lane;
+        const int i0 = p.mel_ptr[f], i1 = p.mel_ptr[f + 1];
+        float m = 0.0f;
+        int i = i0;
+        for (; i + 4 <= i1; i += 4) {          // four table entries in flight, added in table order
+            const float w0 = p.mel_w[i], w1 = p.mel_w[i + 1], w2 = p.mel_w[i + 2], w3 = p.mel_w[i + 3];
+            const int c0 = p.mel_col[i], c1 = p.mel_col[i + 1], c2 = p.mel_col[i + 2], c3 = p.mel_col[i + 3];
+            m += w0 * P[c0];
+            m += w1 * P[c1];
+            m += w2 * P[c2];
+            m += w3 * P[c3];
+        }
+        for (; i < i1; ++i) m += p.mel_w[i] * P[p.mel_col[i]];
+        if (live) p.mel_db[(size_t)g * kMels + f] = 10.0f * log10f(fmaxf(1e-10f, m));
+    }
+}
+
+namespace {
+
+struct PickParams {
+    int F, pre_max, post_max, pre_avg, post_avg, wait, given;
+    float delta;
+    const float* mel_db;       // [B, F, 128] (given == 0)
+    const float* envelope;     // [B, F]      (given == 1)
+    const float* rms;          // [B, F] or NULL
+    float* oenv;
+    int *count, *onset_raw, *onset_bt, *onset_bt_rms;
+};
+
+// the four wave partials of a 256-thread block combined in wave order; every thread receives the result
+template <class Op>
+__device__ __forceinline__ float block_combine(float v, float* part, Op op) {
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return op(op(op(part[0], part[1]), part[2]), part[3]);
+}
+
+// minima of onset_backtrack: frame 0, and i + 1 where e[i + 1] <= e[i] and e[i + 1] < e[i + 2]
+__device__ __forceinline__ bool is_minimum(const float* e, int n, int F) {
+    return n == 0 || (n + 1 < F && e[n] <= e[n - 1] && e[n] < e[n + 1]);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_onset_pick(const PickParams p) {
+    __shared__ float senv[kMaxF];            // the envelope
+    __shared__ float sx[kMaxF];              // normalised; once the detections are marked, the picked frames (sraw)
+    __shared__ float srms[kMaxF];
+    __shared__ unsigned char sdet[kMaxF];    // passes the maximum and the threshold test
+    __shared__ float part[4];
+    __shared__ int scount;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, F = p.F;
+
+    if (p.given) {
+        for (int n = tid; n < F; n += 256) senv[n] = p.envelope[(size_t)b * F + n];
+    } else {
+        // ---- S = max(S, clip max - 80); d[t] = mean over the mels of max(0, S[t + 1] - S[t]); the envelope is d shifted by 3 ----
+        const float* S = p.mel_db + (size_t)b * F * kMels;
+        float mx = -INFINITY;
+        for (int i = tid; i < F * kMels; i += 256) mx = fmaxf(mx, S[i]);
+        mx = block_combine(wave_max(mx), part, [](float a, float c) { return fmaxf(a, c); });
+        const float floor_db = mx - 80.0f;
+        for (int n = tid; n < kLagShift && n < F; n += 256) senv[n] = 0.0f;
+        for (int t = wave; t + kLagShift < F; t += 4) {         // one wave per frame pair: two mels per lane, then the butterfly
+            const float* s0 = S + (size_t)t * kMels;
+            const float* s1 = s0 + kMels;
+            const float d0 = fmaxf(0.0f, fmaxf(s1[lane], floor_db) - fmaxf(s0[lane], floor_db));
+            const float d1 = fmaxf(0.0f, fmaxf(s1[lane + 64], floor_db) - fmaxf(s0[lane + 64], floor_db));
+            const float d = wave_sum(d0 + d1) / (float)kMels;
+            if (lane == 0) senv[t + kLagShift] = d;
+        }
+    }
+    if (p.rms)
+        for (int n = tid; n < F; n += 256) srms[n] = p.rms[(size_t)b * F + n];
+    __syncthreads();
+
+    // ---- x = (oenv - min) / (max(oenv - min) + tiny); an envelope without a non-zero entry has no onsets ----
+    float lo = INFINITY, hi = -INFINITY;
+    for (int n = tid; n < F; n += 256) {
+        lo = fminf(lo, senv[n]);
+        hi = fmaxf(hi, senv[n]);
+        if (p.oenv) p.oenv[(size_t)b * F + n] = senv[n];
+    }
+    lo = block_combine(wave_min(lo), part, [](float a, float c) { return fminf(a, c); });
+    hi = block_combine(wave_max(hi), part, [](float a, float c) { return fmaxf(a, c); });
+    const bool any = lo != 0.0f || hi != 0.0f;
+    const float denom = (hi - lo) + 1.17549435e-38f;
+    for (int n = tid; n < F; n += 256) sx[n] = (senv[n] - lo) / denom;
+    __syncthreads();
+
+    // ---- x[n] == max(x[n - pre_max : n + post_max]), x[n] != 0, x[n] >= mean(x[n - pre_avg : n + post_avg]) + delta; both
+    //      windows are cut at the ends of the clip, the mean is added left to right ----
+    for (int n = tid; n < F; n += 256) {
+        const float x = sx[n];
+        float mx = x, sum = 0.0f;
+        for (int i = max(0, n - p.pre_max); i < min(F, n + p.post_max); ++i) mx = fmaxf(mx, sx[i]);
+        const int a0 = max(0, n - p.pre_avg), a1 = min(F, n + p.post_avg);
+        for (int i = a0; i < a1; ++i) sum += sx[i];
+        sdet[n] = any && x == mx && x != 0.0f && x >= sum / (float)(a1 - a0) + p.delta;
+    }
+    __syncthreads();
+
+    // ---- greedy left to right: keep n when n > last + wait ----
+    int* sraw = reinterpret_cast<int*>(sx);
+    if (tid == 0) {
+        int c = 0;
+        long long last = -(long long)kMaxF - 2;
+        for (int n = 0; n < F; ++n)
+            if (sdet[n] && n > last + p.wait) {
+                sraw[c++] = n;
+                last = n;
+            }
+        scount = c;
+        if (p.count) p.count[b] = c;
+    }
+    __syncthreads();
+    const int c = scount;
+    for (int n = tid; n < F; n += 256)
+        if (p.onset_raw) p.onset_raw[(size_t)b * F + n] = n < c ? sraw[n] : -1;
+
+    // ---- backtracks: the nearest minimum at or before each onset, one serial walk per energy (wave 0: oenv, wave 1: rms) ----
+    if (lane == 0 && wave < 2) {
+        const float* e = wave == 0 ? senv : srms;
+        int* out = wave == 0 ? p.onset_bt : p.onset_bt_rms;
+        if (out) {
+            int cur = 0, i = 0;
+            for (int n = 0; n < F && i < c; ++n) {
+                if (is_minimum(e, n, F)) cur = n;
+                while (i < c && sraw[i] == n) out[(size_t)b * F + i++] = cur;
+            }
+            for (; i < F; ++i) out[(size_t)b * F + i] = -1;
+        }
+    }
+}
+
+}  // namespace ls
+
+extern "C" int ls_onsets(int device, const ls_onsets_args* a) {
+    using namespace ls;
+    if (!a || a->batch < 1 || a->length < 1) return LS_EINVAL;
+    if ((a->audio == nullptr) == (a->envelope == nullptr)) return LS_EINVAL;          // exactly one input
+    const bool given = a->envelope != nullptr;
+    if (!(a->sr_pick > 0.f)) return LS_EINVAL;
+    if (!given) {
+        if (a->pad_mode != LS_ONSETS_PAD_CONSTANT && a->pad_mode != LS_ONSETS_PAD_REFLECT) return LS_EINVAL;
+        if (a->pad_mode == LS_ONSETS_PAD_REFLECT && a->length <= kHalf) return LS_EINVAL;
+        if (!(a->sr > 0.f) || !(a->fmax > 0.f)) return LS_EINVAL;
+    } else if (a->mel_db || a->rms || a->onset_bt_rms) {
+        return LS_EINVAL;
+    }
+    const long long F64 = given ? a->length : 1 + a->length / kHop;
+    if (F64 > kMaxF) return LS_EINVAL;
+    const int B = a->batch, L = a->length, F = (int)F64;
+    const bool want_pick = given || a->oenv || a->count || a->onset_raw || a->onset_bt || a->onset_bt_rms;
+    const size_t n_bf = (size_t)B * F;
+    if ((n_bf + kWavesPerBlock - 1) / kWavesPerBlock > 0x7fffffffull) return LS_EINVAL;
+    if (hipSetDevice(device) != hipSuccess) return LS_EHIP;
+
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
+    DevBuf t_in, t_win, t_tw, t_ptr, t_col, t_w, t_db, t_rms, t_env, t_cnt, t_raw, t_bt, t_btr;      // device temporaries, freed on return
+    auto up = [&](DevBuf& buf, const void* src, size_t bytes) -> void* {
+        chk(buf.ensure(bytes ? bytes : 4));        // a filterbank may be empty (fmax below the first bin)
+        if (e == hipSuccess && bytes) chk(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice));
+        return buf.p;
+    };
+    auto tmp = [&](DevBuf& buf, size_t bytes) -> void* { chk(buf.ensure(bytes)); return buf.p; };
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (a->kernel_ms)
+        for (auto& v : ev) chk(hipEventCreate(&v));
+
+    SpectrumParams sp{};
+    PickParams pp{};
+    pp.F = F; pp.given = given ? 1 : 0; pp.delta = a->delta;
+    // onset_detect's defaults in frames of 512 samples: 0.03 s and 0.10 s before, one frame and pre_avg + 1 after
+    pp.pre_max = (int)std::floor(0.03 * (double)a->sr_pick / kHop);
+    pp.post_max = 1;
+    pp.pre_avg = (int)std::floor(0.10 * (double)a->sr_pick / kHop);
+    pp.post_avg = pp.pre_avg + 1;
+    pp.wait = pp.pre_max;
+    if (given) {
+        pp.envelope = a->on_device ? a->envelope : static_cast<const float*>(up(t_in, a->envelope, n_bf * 4));
+    } else {
+        const OnsetTables tab = make_onset_tables(a->sr, kNfft, kMels, 0.0, a->fmax);
+        sp.B = B; sp.L = L; sp.F = F; sp.pad_mode = a->pad_mode;
+        sp.audio = a->on_device ? a->audio : static_cast<const float*>(up(t_in, a->audio, (size_t)B * L * 4));
+        sp.window = static_cast<const float*>(up(t_win, tab.window.data(), tab.window.size() * 4));
+        sp.twiddle = static_cast<const float2*>(up(t_tw, tab.twiddle.data(), tab.twiddle.size() * 4));
+        sp.mel_ptr = static_cast<const int*>(up(t_ptr, tab.mel_ptr.data(), tab.mel_ptr.size() * 4));
+        sp.mel_col = static_cast<const int*>(up(t_col, tab.mel_col.data(), tab.mel_col.size() * 4));
+        sp.mel_w = static_cast<const float*>(up(t_w, tab.mel_w.data(), tab.mel_w.size() * 4));
+        sp.mel_db = (a->on_device && a->mel_db) ? a->mel_db : static_cast<float*>(tmp(t_db, n_bf * kMels * 4));
+        const bool want_rms = a->rms || a->onset_bt_rms;
+        sp.rms = !want_rms ? nullptr : (a->on_device && a->rms) ? a->rms : static_cast<float*>(tmp(t_rms, n_bf * 4));
+        pp.mel_db = sp.mel_db;
+        pp.rms = a->onset_bt_rms ? sp.rms : nullptr;
+    }
+    if (a->on_device) {
+        pp.oenv = a->oenv; pp.count = a->count; pp.onset_raw = a->onset_raw; pp.onset_bt = a->onset_bt; pp.onset_bt_rms = a->onset_bt_rms;
+    } else {
+        if (a->oenv) pp.oenv = static_cast<float*>(tmp(t_env, n_bf * 4));
+        if (a->count) pp.count = static_cast<int*>(tmp(t_cnt, (size_t)B * 4));
+        if (a->onset_raw) pp.onset_raw = static_cast<int*>(tmp(t_raw, n_bf * 4));
+        if (a->onset_bt) pp.onset_bt = static_cast<int*>(tmp(t_bt, n_bf * 4));
+        if (a->onset_bt_rms) pp.onset_bt_rms = static_cast<int*>(tmp(t_btr, n_bf * 4));
+    }
+    if (e == hipSuccess) {
+        if (!given) {
+            const long long blocks = ((long long)n_bf + kWavesPerBlock - 1) / kWavesPerBlock;
+            if (ev[0]) chk(hipEventRecord(ev[0], 0));
+            hipLaunchKernelGGL(k_onset_spectrum, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, 0, sp);
+            if (ev[1]) chk(hipEventRecord(ev[1], 0));
+        }
+        if (want_pick) {
+            if (ev[2]) chk(hipEventRecord(ev[2], 0));
+            hipLaunchKernelGGL(k_onset_pick, dim3(B), dim3(256), 0, 0, pp);
+            if (ev[3]) chk(hipEventRecord(ev[3], 0));
+        }
+        chk(hipGetLastError());
+        chk(hipDeviceSynchronize());
+    }
+    if (a->kernel_ms) {
+        a->kernel_ms[0] = a->kernel_ms[1] = 0.0f;
+        if (e == hipSuccess && !given) chk(hipEventElapsedTime(&a->kernel_ms[0], ev[0], ev[1]));
+        if (e == hipSuccess && want_pick) chk(hipEventElapsedTime(&a->kernel_ms[1], ev[2], ev[3]));
+        for (auto& v : ev)
+            if (v) (void)hipEventDestroy(v);
+    }
+    if (!a->on_device) {
+        auto down = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess && dst) chk(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); };
+        down(a->mel_db, sp.mel_db, n_bf * kMels * 4);
+        down(a->rms, sp.rms, n_bf * 4);
+        down(a->oenv, pp.oenv, n_bf * 4);
+        down(a->count, pp.count, (size_t)B * 4);
+        down(a->onset_raw, pp.onset_raw, n_bf * 4);
+        down(a->onset_bt, pp.onset_bt, n_bf * 4);
+        down(a->onset_bt_rms, pp.onset_bt_rms, n_bf * 4);
+    }
+    return e == hipSuccess ? LS_OK : LS_EHIP;
+}

@@ -85,8 +85,8 @@ def beat_postprocess(sample, device: int = 0, want_euler: bool = True) -> dict:
 class BeatConsistency:
     """Running beat-alignment (BC) score over clips, as the evaluation loop accumulates it (test_RAG_ted.py:113-127): for every
     audio onset, exp(-min_m (onset - m)^2 / (2 sigma^2)) over the clip's motion beats; clips without a motion beat contribute
-    nothing (not even their onsets).  Audio onset times are an INPUT here: the reference gets them from
-    librosa.onset.onset_detect, a third-party package that is not part of this path."""
+    nothing (not even their onsets).  Audio onset times are an input, or are detected on the device from ``audio``
+    (``audio_onsets``: the reference's librosa.onset.onset_detect(y, sr=16000, units='time'))."""
 
     def __init__(self, sigma: float = TED_BEAT_SIGMA):
         self.sigma = float(sigma)
@@ -94,8 +94,15 @@ class BeatConsistency:
         self.num_beats = 0
         self.motion_beats_sum = 0
 
-    def push(self, motion_beat_times, audio_beat_times):
-        """Both arguments: one sequence of times (seconds) per clip."""
+    def push(self, motion_beat_times, audio_beat_times=None, audio=None, sr=16000, device=0, **onset_options):
+        """motion_beat_times and audio_beat_times: one sequence of times (seconds) per clip.  ``audio`` [B, L] instead of
+        audio_beat_times: the onsets are detected on the device (``onset_options``: pad_mode, fmax, delta of ``audio_onsets``); a
+        clip without an onset contributes nothing, as in the reference."""
+        if (audio_beat_times is None) == (audio is None):
+            raise ValueError("pass either audio_beat_times or audio")
+        if audio is not None:
+            from .audio_onsets import onset_times
+            audio_beat_times = onset_times(audio, sr, device=device, **onset_options)
         if len(motion_beat_times) != len(audio_beat_times):
             raise ValueError("one list of motion beats and one list of audio onsets per clip")
         for mb, ab in zip(motion_beat_times, audio_beat_times):
