@@ -17,7 +17,8 @@ on the GPU, synthetic weights) -> text features -> SAG decoder -> the same refin
 (recorded clip -> SAG(batch) = MOTIONCLIP.forward -> init_image -> the same 20-step refinement).
 --long-seconds N synthesises N seconds of gesture for N seconds of speech in ONE call (livelyspeaker_amd.long_form.sample_long): the
 34-frame windows are chained on the device, each conditioned on the last four poses of the one before it, the SAG decoder's output for
-the window's text feature as its init_image, and stitched into one timeline.
+the window's text feature as its init_image, and stitched into one timeline, which long_form.score_timeline then turns into poses,
+motion beats and the beat-consistency score against the speech it was generated from (up to 131 s: the onset detector's 4096 frames).
 With real data: load RAG.pt / SAG.pth / the auto-encoder checkpoint with load_model_wo_clip / load_state_dict and build `cond`
 exactly as the reference script does; everything below the weight loading is unchanged.
 """
@@ -253,6 +254,12 @@ def main_long(B, seconds, noise_source):
     assert timeline.shape == (B, 9, 3, n_frames) and bool(torch.isfinite(timeline).all())
     print(f"B={B} ({noise_source}): {seconds:g} s of speech -> {W} chained windows, {n_frames} frames ({n_frames / 15:.1f} s of gesture) in "
           f"{dt * 1e3:.1f} ms ({B * n_frames / dt:.0f} pose-frames/s)")
+    # the timeline as one series per clip: joint positions, motion beats and the beat-consistency score against the speech, on the device
+    scored = long_form.score_timeline(timeline, audio)
+    n_beats = sum(len(b) for b in scored["motion_beat_times"])
+    print(f"pose {tuple(scored['pose'].shape)}, motion beats {n_beats}, BC {scored['bc']:.4f} (synthetic weights and audio: numbers are "
+          f"not quality)")
+    assert tuple(scored["pose"].shape) == (B, n_frames, 10, 3) and bool(torch.isfinite(scored["pose"]).all())
 
 
 def main_pipelined(B, N):

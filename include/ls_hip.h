@@ -644,6 +644,54 @@ int ls_beat_metrics(int device, const ls_beat_metrics_args* a);
  * is what the export check of the test suite collects them by. */
 int ls_beat_ldiv(int device, int on_device, int64_t rows, int dim, const float* x, double* sum_out);
 
+/* ---- the same post-processing and scores on a stitched timeline of n_frames frames ---------------------------
+ * ls_long_sample returns [B,J,F,N] with N = 34 + 30 (W - 1).  These are the loop bodies above with 34 replaced by N = n_frames and
+ * 33 by N - 1 (no counterpart in the reference, which scores 34-frame clips): a timeline clip is ONE series, nothing resets at a
+ * window seam.  The kernels run over (clip, tile of LS_TIMELINE_TILE frames) with a recomputed halo; a frame's numbers are those of
+ * the 34-frame kernels' own per-frame functions and do not depend on the batch, the tile size or the tile the frame lands in, and at
+ * n_frames = 34 every output equals ls_ted_post's / ls_beat_post's / ls_beat_metrics's bit for bit.
+ *   ls_ted_post_timeline      timeline [B,J,3,N] -> aligned [B,N,J*3], pose [B,N,n_pose_joints,3], angle_diff [B,N] (0 at frame 0),
+ *                             beat_mask [B,N] (bytes; beats at t in [2, N-2]); any output may be NULL
+ *   ls_beat_post_timeline     timeline [B,J,6,N] -> decoded [B,N,J*6], euler_deg [B,N,J*3]; either may be NULL
+ *   ls_beat_metrics_timeline  ls_beat_metrics_args with pred / target [B,N,J*3], semantic [B,N], success [B,N,J], vel and
+ *                             beat_mask [B,6,N-1] (mode='clip' clamps at 0 and N-2; beat time m / fps), srgr_sum and align [B]
+ *   ls_ted_beat_align         the TED beat-consistency sum of every clip (scripts/test_RAG_ted.py:113-123) in float64:
+ *                             align_sum[b] = sum over the first onset_count[b] entries a = frame * hop / sr of row b of onset_frames
+ *                             [B,onset_cols] (the slab ls_onsets writes) of exp(-min_m (a - m)^2 / (2 sigma^2)), m = t / fps over the
+ *                             set frames t of beat_mask [B,N]; n_beats[b] = the number of set frames; a clip without one has
+ *                             align_sum 0 (the caller leaves its onsets out of the running count, as the reference's `continue`
+ *                             does).  fps, sigma and sr are doubles: the host loop this restates computes with Python floats.
+ *                             Either output may be NULL.
+ * Pointers are device pointers iff on_device (onset_offsets: host, as in ls_beat_metrics).  LS_EINVAL without a HIP call: a NULL
+ * input, batch < 1, n_frames > LS_TIMELINE_MAX_FRAMES, n_frames < 4 (TED post and align), < 2 (BEAT post), < 2 order + 2 (BEAT
+ * metrics), whatever ls_ted_post / ls_beat_metrics refuse, and for ls_ted_beat_align onset_cols < 1, a host onset_count entry
+ * outside [0, onset_cols] (device-resident counts are clamped), fps, sigma or sr not positive, hop < 1.
+ * Not built: clips of different valid lengths in one call, timelines longer than LS_TIMELINE_MAX_FRAMES. */
+#define LS_TIMELINE_MAX_FRAMES 4096
+#define LS_TIMELINE_TILE 64
+int ls_ted_post_timeline(int device, int on_device, int batch, int n_frames, const ls_post_config* c, const float* timeline,
+                         float* aligned, float* pose, float* angle_diff, unsigned char* beat_mask);
+int ls_beat_post_timeline(int device, int on_device, int batch, int njoints, int n_frames, const float* timeline, float* decoded,
+                          float* euler_deg);
+int ls_beat_metrics_timeline(int device, int n_frames, const ls_beat_metrics_args* a);
+typedef struct ls_ted_align_args {
+    int32_t batch;
+    int32_t n_frames;
+    int32_t on_device;
+    int32_t onset_cols;                /* F: columns of the onset slab                                       */
+    double fps;                        /* 15                                                                 */
+    double sigma;                      /* 0.1 (test_RAG_ted.py:33)                                           */
+    double sr;                         /* 16000                                                              */
+    int32_t hop;                       /* 512                                                                */
+    int32_t reserved;
+    const unsigned char* beat_mask;    /* [B,N]                                                              */
+    const int32_t* onset_frames;       /* [B,onset_cols]                                                     */
+    const int32_t* onset_count;        /* [B]                                                                */
+    double* align_sum;                 /* [B]                                                                */
+    int32_t* n_beats;                  /* [B]                                                                */
+} ls_ted_align_args;
+int ls_ted_beat_align(int device, const ls_ted_align_args* a);
+
 /* ---- audio onsets for the beat-alignment scores ------------------------------------------------------------
  * What the reference's scripts take from librosa 0.9.2 (scripts/test_RAG_ted.py:113 onset_detect(y, sr=16000, units='time');
  * scripts_beat/utils/metric.py:60-74 alignment.load_audio), for a batch of equally long clips:

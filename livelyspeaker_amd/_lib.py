@@ -124,6 +124,12 @@ class LsOnsetsArgs(C.Structure):
                                   "kernel_ms")]
 
 
+class LsTedAlignArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("batch", "n_frames", "on_device", "onset_cols")] + [
+        (n, C.c_double) for n in ("fps", "sigma", "sr")] + [("hop", C.c_int32), ("reserved", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("beat_mask", "onset_frames", "onset_count", "align_sum", "n_beats")]
+
+
 class LsTiming(C.Structure):
     _fields_ = [("prepare_ms", C.c_float), ("loop_ms", C.c_float), ("total_ms", C.c_float),
                 ("n_step_launches", C.c_int32), ("graph_replayed", C.c_int32), ("single_pass", C.c_int32),
@@ -158,6 +164,7 @@ EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set
            "ls_sag_enc_encode", "ls_sag_enc_encode_async", "ls_sag_enc_last_encode_ms", "ls_sag_enc_stream",
            "ls_clip_text_create", "ls_clip_text_destroy", "ls_clip_text_last_error", "ls_clip_text_set_weight", "ls_clip_text_commit_weights",
            "ls_clip_text_encode", "ls_clip_text_encode_async", "ls_clip_text_last_encode_ms", "ls_clip_text_stream", "ls_clip_text_plan", "ls_ted_post", "ls_beat_post", "ls_beat_metrics", "ls_beat_ldiv", "ls_onsets", "ls_onsets_tables",
+           "ls_ted_post_timeline", "ls_beat_post_timeline", "ls_beat_metrics_timeline", "ls_ted_beat_align",
            "ls_train_create", "ls_train_destroy", "ls_train_last_error", "ls_train_set_schedule", "ls_train_param_count",
            "ls_train_flat_size", "ls_train_param_info", "ls_train_set_weight", "ls_train_get_weight", "ls_train_forward_backward",
            "ls_train_adamw", "ls_train_read", "ls_train_get_moment", "ls_train_set_moment", "ls_train_get_step", "ls_train_set_step",
@@ -276,6 +283,11 @@ def load_library(build_if_missing: bool = True):
     lib.ls_beat_metrics.argtypes = [C.c_int, C.POINTER(LsBeatMetricsArgs)]
     lib.ls_beat_ldiv.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, c_f64p]
     lib.ls_onsets.argtypes = [C.c_int, C.POINTER(LsOnsetsArgs)]
+    lib.ls_ted_post_timeline.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(LsPostConfig), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]
+    lib.ls_beat_post_timeline.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ls_beat_metrics_timeline.argtypes = [C.c_int, C.c_int, C.POINTER(LsBeatMetricsArgs)]
+    lib.ls_ted_beat_align.argtypes = [C.c_int, C.POINTER(LsTedAlignArgs)]
     lib.ls_onsets_tables.argtypes = [C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     lib.ls_train_set_schedule.argtypes = [C.c_void_p, c_f64p, c_f64p, c_i64p]

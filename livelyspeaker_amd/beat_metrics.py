@@ -51,8 +51,29 @@ def beat_metrics(pred_euler, target_euler=None, semantic=None, onset_times=None,
     """``ls_beat_metrics`` on Euler planes [B, 34, joints*3] in degrees (numpy, or CUDA tensors: then the outputs stay on the device).
     ``onset_times``: one sequence of seconds per clip.  Returns a dict of the outputs named in ``want`` whose inputs were given:
     success [B,34,J] and beat_mask [B,6,33] as bytes, srgr_sum [B], vel [B,6,33], align [B]."""
+    return _beat_metrics(None, pred_euler, target_euler, semantic, onset_times, joints, threshold, scale, series_joints, order, sigma, fps,
+                         align_series, device, want, _ragged_onsets)
+
+
+def beat_metrics_timeline(pred_euler, target_euler=None, semantic=None, onset_times=None, *, joints=47, threshold=4.0, scale=SRGR_SCALE,
+                          series_joints=BEAT_SERIES_JOINTS, order=2, sigma=0.3, fps=BEAT_FPS, align_series=2, device=0,
+                          want=("success", "srgr_sum", "vel", "beat_mask", "align"), _ragged_onsets=None):
+    """``beat_metrics`` on the Euler planes of a stitched timeline, [B, N, joints*3] with 2 * order + 2 <= N <= 4096
+    (``ls_beat_metrics_timeline``): every clip is one series of N frames.  success [B,N,J] and beat_mask [B,6,N-1] as bytes,
+    srgr_sum [B], vel [B,6,N-1], align [B]; semantic, if given, is [B, N]; a motion beat at velocity index m lies at m / fps seconds."""
+    if len(pred_euler.shape) != 3:
+        raise ValueError(f"expected Euler planes [B, N, joints*3], got {list(pred_euler.shape)}")
+    return _beat_metrics(int(pred_euler.shape[1]), pred_euler, target_euler, semantic, onset_times, joints, threshold, scale, series_joints,
+                         order, sigma, fps, align_series, device, want, _ragged_onsets)
+
+
+def _beat_metrics(n_frames, pred_euler, target_euler, semantic, onset_times, joints, threshold, scale, series_joints, order, sigma, fps,
+                  align_series, device, want, _ragged_onsets):
+    """Both entry points: ``n_frames`` None is the 34-frame ``ls_beat_metrics``."""
     lib = _lib.load_library()
     B = int(pred_euler.shape[0])
+    T = 34 if n_frames is None else n_frames
+    V = T - 1
     m = _lib._Marshal(device, pred_euler, target_euler, semantic)
     a = _lib.LsBeatMetricsArgs()
     a.batch, a.njoints, a.on_device, a.order, a.align_series = B, int(joints), int(m.on_device), int(order), int(align_series)
@@ -86,9 +107,12 @@ def beat_metrics(pred_euler, target_euler=None, semantic=None, onset_times=None,
     if onset_times is not None and "align" in want:
         out["align"], a.align = m.out((B,))
     m.ready()
-    rc = lib.ls_beat_metrics(device, C.byref(a))
+    if n_frames is None:
+        rc, name = lib.ls_beat_metrics(device, C.byref(a)), "ls_beat_metrics"
+    else:
+        rc, name = lib.ls_beat_metrics_timeline(device, n_frames, C.byref(a)), "ls_beat_metrics_timeline"
     if rc != 0:
-        raise _lib.EngineError(f"ls_beat_metrics failed ({rc})")
+        raise _lib.EngineError(f"{name} failed ({rc})")
     return out
 
 

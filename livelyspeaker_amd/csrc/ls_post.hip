@@ -7,22 +7,9 @@
 #include "ls_hip.h"
 #include "ls_host.h"
 #include "ls_internal.h"
+#include "ls_post_frame.h"
 
 namespace ls {
-
-constexpr int kMaxBones = 16, kMaxPairs = 8;
-
-struct PostParams {
-    int njoints;                       // bones (direction vectors), 9 for TED
-    int n_pairs;
-    int pair_a[kMaxPairs], pair_b[kMaxPairs];
-    float change_angle[kMaxPairs];
-    float thres;
-    int n_pose_joints;                 // 10
-    int bone_parent[kMaxBones], bone_child[kMaxBones];
-    float bone_len[kMaxBones];
-    float mean_dir_vec[kMaxBones * 3];
-};
 
 __global__ __launch_bounds__(64) void k_ted_post(const float* __restrict__ sample, PostParams p, float* __restrict__ aligned,
                                                  float* __restrict__ pose, float* __restrict__ angle_diff,
@@ -42,47 +29,27 @@ __global__ __launch_bounds__(64) void k_ted_post(const float* __restrict__ sampl
     __syncthreads();
     for (int i = tid; i < kT * p.njoints; i += 64) {                    // F.normalize(dim=-1): x / max(||x||, 1e-12)
         const int f = i / p.njoints, j = i - f * p.njoints;
-        const float x = sv[f][3 * j], y = sv[f][3 * j + 1], z = sv[f][3 * j + 2];
-        const float inv = 1.0f / fmaxf(sqrtf(x * x + y * y + z * z), 1e-12f);
-        sn[f][3 * j] = x * inv; sn[f][3 * j + 1] = y * inv; sn[f][3 * j + 2] = z * inv;
+        ted_unit(&sv[f][3 * j], &sn[f][3 * j]);
     }
     __syncthreads();
     for (int i = tid; i < kT * p.n_pairs; i += 64) {                    // angle between the two bones of each pair
         const int k = i / kT, f = i - k * kT;
-        const float* u = &sn[f][3 * p.pair_a[k]];
-        const float* v = &sn[f][3 * p.pair_b[k]];
-        float ip = u[0] * v[0] + u[1] * v[1] + u[2] * v[2];
-        ip = fminf(fmaxf(ip, -1.0f), 1.0f);
-        sang[k][f] = acosf(ip) * 0.3183098861837907f;
+        sang[k][f] = ted_pair_angle(&sn[f][3 * p.pair_a[k]], &sn[f][3 * p.pair_b[k]]);
     }
     __syncthreads();
     if (tid < kT) {
-        float d = 0.f;
-        if (tid > 0)
-            for (int k = 0; k < p.n_pairs; ++k)
-                d += fabsf(sang[k][tid] - sang[k][tid - 1]) / p.change_angle[k] / (float)p.n_pairs;
+        const float d = tid > 0 ? ted_angle_change(p, &sang[0][tid], &sang[0][tid - 1], kT) : 0.f;
         sdiff[tid] = d;
         if (angle_diff) angle_diff[(size_t)b * kT + tid] = d;
     }
     __syncthreads();
     if (beat_mask && tid < kT) {                                        // local minima of the change curve, t in [2, 32]
         bool beat = false;
-        if (tid >= 2 && tid <= kT - 2) {
-            const float c = sdiff[tid], l = sdiff[tid - 1], r = sdiff[tid + 1];
-            beat = (c < l && c < r) && (l - c >= p.thres || r - c >= p.thres);
-        }
+        if (tid >= 2 && tid <= kT - 2) beat = ted_is_beat(sdiff[tid], sdiff[tid - 1], sdiff[tid + 1], p.thres);
         beat_mask[(size_t)b * kT + tid] = beat ? 1 : 0;
     }
     if (pose) {                                                         // joint positions along the bone tree
-        for (int f = tid; f < kT; f += 64) {
-            float jp[kMaxBones + 1][3];
-            for (int j = 0; j < p.n_pose_joints; ++j) jp[j][0] = jp[j][1] = jp[j][2] = 0.f;
-            for (int j = 0; j < p.njoints; ++j)
-                for (int e = 0; e < 3; ++e) jp[p.bone_child[j]][e] = jp[p.bone_parent[j]][e] + p.bone_len[j] * sv[f][3 * j + e];
-            float* o = pose + ((size_t)b * kT + f) * p.n_pose_joints * 3;
-            for (int j = 0; j < p.n_pose_joints; ++j)
-                for (int e = 0; e < 3; ++e) o[3 * j + e] = jp[j][e];
-        }
+        for (int f = tid; f < kT; f += 64) ted_pose_frame(p, sv[f], pose + ((size_t)b * kT + f) * p.n_pose_joints * 3);
     }
 }
 
@@ -150,20 +117,7 @@ __global__ __launch_bounds__(256) void k_beat_post(const float* __restrict__ sam
         for (int f = 0; f < 6; ++f) decoded[(bt * J + j) * 6 + f] = d6[f];
     }
     if (!euler) return;
-    // rotation_6d_to_matrix (rot_utils.py:529-534): b1 = normalize(a1), b2 = normalize(a2 - (b1.a2) b1), b3 = b1 x b2; rows of M
-    const float n1 = fmaxf(sqrtf(d6[0] * d6[0] + d6[1] * d6[1] + d6[2] * d6[2]), 1e-12f);      // F.normalize: x / max(|x|, eps)
-    const float b1x = d6[0] / n1, b1y = d6[1] / n1, b1z = d6[2] / n1;
-    const float dt = b1x * d6[3] + b1y * d6[4] + b1z * d6[5];
-    float b2x = d6[3] - dt * b1x, b2y = d6[4] - dt * b1y, b2z = d6[5] - dt * b1z;
-    const float n2 = fmaxf(sqrtf(b2x * b2x + b2y * b2y + b2z * b2z), 1e-12f);
-    b2x /= n2; b2y /= n2; b2z /= n2;
-    const float b3z = b1x * b2y - b1y * b2x;                           // only m22 of the third row is needed
-    // matrix_to_euler_angles(M, "XYZ") (rot_utils.py:238-257): (atan2(-m12, m22), asin(m02), atan2(-m01, m00))
-    const float k = 57.29577951308232f;                                // / pi * 180
-    float* o = euler + (bt * J + j) * 3;
-    o[0] = atan2f(-b2z, b3z) * k;
-    o[1] = asinf(b1z) * k;
-    o[2] = atan2f(-b1y, b1x) * k;
+    beat_rot6d_to_euler(d6, euler + (bt * J + j) * 3);
 }
 
 }  // namespace ls

@@ -166,3 +166,60 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
     timeline, windows = res if return_windows else (res, None)
     timeline = gd._as_tensor(timeline, out_dev)
     return (timeline, gd._as_tensor(windows, out_dev)) if return_windows else timeline
+
+
+def timeline_clips(x, stride=34):
+    """Frame-major timeline planes [B, N, C] (``aligned_motions``, ``decoded_motions``, ``pred_euler``) cut into 34-frame clips
+    [B * K, 34, C], one every ``stride`` frames (K = (N - 34) // stride + 1; clip b * K + k starts at frame k * stride of timeline b), so
+    that a timeline feeds ``EmbeddingSpaceEvaluator.push_samples`` / ``BeatEvaluator.push`` unchanged.  Tail frames that do not fill a
+    clip are dropped.  torch ``unfold`` plus a reshape; numpy in, numpy out."""
+    as_np = isinstance(x, np.ndarray)
+    t = th.as_tensor(x)
+    if t.ndim != 3 or int(t.shape[1]) < 34:
+        raise ValueError(f"expected [B, N, C] with N >= 34, got {list(t.shape)}")
+    if int(stride) < 1:
+        raise ValueError(f"stride must be >= 1, got {stride}")
+    B, _, Cn = _shape(t)
+    clips = t.unfold(1, 34, int(stride)).permute(0, 1, 3, 2).reshape(-1, 34, Cn).contiguous()       # [B, K, C, 34] -> [B*K, 34, C]
+    return clips.numpy() if as_np else clips
+
+
+def score_timeline(timeline, audio, dataset="ted", sr=16000, device=0, target_euler=None, semantic=None, bc=None, **options):
+    """The whole chain behind ``sample_long``: post-process a stitched timeline [B, J, F, N] and score it against the ``audio`` [B, L] it
+    was generated from, on the device (N up to 4096 frames; audio up to the onset detector's 4096 audio frames, 131 s at 16 kHz).
+
+    ``dataset='ted'``: ``ted_postprocess_timeline``, onsets as ``librosa.onset.onset_detect(y, sr=16000)`` finds them, and the
+    beat-consistency score; returns pose, beat_mask, motion_beat_times and bc (this call's score, or the running score of the
+    ``BeatConsistency`` passed as ``bc``).  ``dataset='beat'``: ``beat_postprocess_timeline``, onsets as ``alignment.load_audio``
+    finds them, ``beat_metrics_timeline``; returns pred_euler, beat_mask, align [B], and srgr (the rate over the call) when
+    ``target_euler`` [B, N, J*3] is given (``semantic`` [B, N] weighs its frames).  ``options`` go to the metric calls (BEAT: order,
+    sigma, threshold, ...; TED: pad_mode, fmax, delta of the onset detector)."""
+    from . import audio_onsets as ao
+    from . import beat_metrics as bm
+    from . import postprocess as pp
+    if dataset not in ("ted", "beat"):
+        raise ValueError(f"dataset must be 'ted' or 'beat', got {dataset!r}")
+    if len(audio.shape) != 2 or int(audio.shape[0]) != int(timeline.shape[0]):
+        raise ValueError(f"audio must be [B, L] with one row per timeline clip, got {list(audio.shape)}")
+    frames = 1 + int(audio.shape[1]) // ao.HOP
+    if frames > ao.MAX_FRAMES:
+        raise NotImplementedError(f"the onset detector takes at most {ao.MAX_FRAMES} audio frames ({ao.MAX_FRAMES * ao.HOP / float(sr):.0f} s "
+                                  f"at {sr} Hz); this audio has {frames}")
+    if dataset == "ted":
+        post = pp.ted_postprocess_timeline(timeline, device=device)
+        acc = bc if bc is not None else pp.BeatConsistency()
+        acc.push_timeline(post["beat_mask"], audio=audio, sr=sr, device=device, **options)
+        return {"pose": post["pose"], "beat_mask": post["beat_mask"], "motion_beat_times": post["motion_beat_times"],
+                "bc": acc.score() if acc.num_beats else float("nan")}
+    onset_opts = {k: options.pop(k) for k in ("pad_mode", "fmax") if k in options}
+    post = pp.beat_postprocess_timeline(timeline, device=device)
+    onsets = ao.onset_times(audio, sr, 22050, which="onset_bt_rms", time_sr=22050, device=device, **onset_opts)
+    want = ("beat_mask", "align") + (("srgr_sum",) if target_euler is not None else ())
+    got = bm.beat_metrics_timeline(post["pred_euler"], target_euler, semantic, onsets, joints=int(timeline.shape[1]), device=device,
+                                   want=want, **options)
+    res = {"pred_euler": post["pred_euler"], "beat_mask": got["beat_mask"], "align": got["align"]}
+    if target_euler is not None:
+        s = got["srgr_sum"]
+        s = s.detach().cpu().numpy() if hasattr(s, "detach") else np.asarray(s)
+        res["srgr"] = float(s.astype(np.float64).sum()) / (int(timeline.shape[0]) * int(timeline.shape[3]) * int(timeline.shape[1]))
+    return res

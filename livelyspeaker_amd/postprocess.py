@@ -82,6 +82,106 @@ def beat_postprocess(sample, device: int = 0, want_euler: bool = True) -> dict:
     return {"decoded_motions": dec, "pred_euler": eul}
 
 
+TIMELINE_TILE = 64            # frames per workgroup of the timeline kernels (LS_TIMELINE_TILE); no result depends on it
+TIMELINE_MAX_FRAMES = 4096    # LS_TIMELINE_MAX_FRAMES
+
+
+def _bytes_out(m, shape):
+    if m.on_device:
+        t = m.torch.empty(tuple(shape), dtype=m.torch.uint8, device=m.dev)
+        return t, C.c_void_p(t.data_ptr())
+    n = np.empty(tuple(shape), np.uint8)
+    return n, n.ctypes.data_as(C.c_void_p)
+
+
+def _timeline_frames(timeline, feats, least):
+    if len(timeline.shape) != 4 or int(timeline.shape[2]) != feats:
+        raise ValueError(f"expected a timeline [B, J, {feats}, N], got {list(timeline.shape)}")
+    N = int(timeline.shape[3])
+    if not least <= N <= TIMELINE_MAX_FRAMES:
+        raise ValueError(f"a timeline holds {least} to {TIMELINE_MAX_FRAMES} frames, got {N} (longer timelines are not built)")
+    return N
+
+
+def ted_postprocess_timeline(timeline, device: int = 0, want_pose: bool = True) -> dict:
+    """``ted_postprocess`` on a stitched timeline [B, 9, 3, N] of any length N in [4, 4096] (``long_form.sample_long``), as ONE series
+    per clip: nothing resets at a window seam (``ls_ted_post_timeline``).  Returns aligned_motions [B,N,27], pose [B,N,10,3],
+    angle_diff [B,N], beat_mask [B,N] (bool; beats at t in [2, N-2]) and motion_beat_times (one list of seconds, t/15, per clip).
+    All clips of a call have the same length."""
+    lib = _lib.load_library()
+    N = _timeline_frames(timeline, 3, 4)
+    m = _lib._Marshal(device, timeline)
+    B = int(timeline.shape[0])
+    cfg = ted_post_config()
+    aligned, p_al = m.out((B, N, 27))
+    pose, p_pose = m.out((B, N, 10, 3)) if want_pose else (None, None)
+    diff, p_diff = m.out((B, N))
+    mask, p_mask = _bytes_out(m, (B, N))
+    p_in = m.f32(timeline, (B, 9, 3, N))
+    m.ready()
+    rc = lib.ls_ted_post_timeline(device, int(m.on_device), B, N, C.byref(cfg), p_in, p_al, p_pose, p_diff, p_mask)
+    if rc != 0:
+        raise _lib.EngineError(f"ls_ted_post_timeline failed ({rc})")
+    mask_np = mask.cpu().numpy() if m.on_device else mask
+    beats = [[float(t) / TED_FPS for t in np.nonzero(mask_np[b])[0]] for b in range(B)]
+    return {"aligned_motions": aligned, "pose": pose, "angle_diff": diff,
+            "beat_mask": mask.bool() if m.on_device else mask.astype(bool), "motion_beat_times": beats}
+
+
+def beat_postprocess_timeline(timeline, device: int = 0, want_euler: bool = True) -> dict:
+    """``beat_postprocess`` on a stitched timeline [B, J, 6, N], N in [2, 4096] (``ls_beat_post_timeline``): decoded_motions
+    [B, N, J*6] and pred_euler [B, N, J*3] in degrees, which ``beat_metrics.beat_metrics_timeline`` scores."""
+    lib = _lib.load_library()
+    N = _timeline_frames(timeline, 6, 2)
+    m = _lib._Marshal(device, timeline)
+    B, J = int(timeline.shape[0]), int(timeline.shape[1])
+    dec, p_dec = m.out((B, N, J * 6))
+    eul, p_eul = m.out((B, N, J * 3)) if want_euler else (None, None)
+    p_in = m.f32(timeline, (B, J, 6, N))
+    m.ready()
+    rc = lib.ls_beat_post_timeline(device, int(m.on_device), B, J, N, p_in, p_dec, p_eul)
+    if rc != 0:
+        raise _lib.EngineError(f"ls_beat_post_timeline failed ({rc})")
+    return {"decoded_motions": dec, "pred_euler": eul}
+
+
+def ted_beat_align(beat_mask, onset_frames, onset_count, sigma=TED_BEAT_SIGMA, fps=TED_FPS, sr=16000, hop=512, device=0):
+    """``ls_ted_beat_align``: per clip, the beat-consistency sum and the number of motion beats.  beat_mask [B, N] (bool or bytes),
+    onset_frames [B, F] int32 and onset_count [B] int32 as ``audio_onsets`` returns them (numpy, or CUDA tensors: then nothing but
+    the results' host copies leaves the device).  Returns (align_sum [B] float64, n_beats [B] int32) as host arrays."""
+    lib = _lib.load_library()
+    if len(beat_mask.shape) != 2 or len(onset_frames.shape) != 2:
+        raise ValueError(f"expected beat_mask [B, N] and onset_frames [B, F], got {list(beat_mask.shape)} and {list(onset_frames.shape)}")
+    B, N, F = int(beat_mask.shape[0]), int(beat_mask.shape[1]), int(onset_frames.shape[1])
+    if int(onset_frames.shape[0]) != B or tuple(int(v) for v in onset_count.shape) != (B,):
+        raise ValueError(f"one row of onsets and one count per clip: {list(onset_frames.shape)} and {list(onset_count.shape)} for {B} clips")
+    m = _lib._Marshal(device, beat_mask, onset_frames, onset_count)
+    a = _lib.LsTedAlignArgs()
+    a.batch, a.n_frames, a.on_device, a.onset_cols, a.hop = B, N, int(m.on_device), F, int(hop)
+    a.fps, a.sigma, a.sr = float(fps), float(sigma), float(sr)
+    a.beat_mask = m.u8(beat_mask, (B, N))
+    if m.on_device:
+        th = m.torch
+        fr = th.as_tensor(onset_frames).to(device=m.dev, dtype=th.int32).contiguous()
+        cn = th.as_tensor(onset_count).to(device=m.dev, dtype=th.int32).contiguous()
+        total = th.empty((B,), dtype=th.float64, device=m.dev)
+        beats = th.empty((B,), dtype=th.int32, device=m.dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr())        # noqa: E731
+    else:
+        host = lambda v: v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)        # noqa: E731
+        fr, cn = np.ascontiguousarray(host(onset_frames), np.int32), np.ascontiguousarray(host(onset_count), np.int32)
+        total, beats = np.empty(B, np.float64), np.empty(B, np.int32)
+        ptr = lambda n: n.ctypes.data_as(C.c_void_p)    # noqa: E731
+    a.onset_frames, a.onset_count, a.align_sum, a.n_beats = ptr(fr), ptr(cn), ptr(total), ptr(beats)
+    m.ready()
+    rc = lib.ls_ted_beat_align(device, C.byref(a))
+    if rc != 0:
+        raise _lib.EngineError(f"ls_ted_beat_align failed ({rc})")
+    if m.on_device:
+        return total.cpu().numpy(), beats.cpu().numpy()
+    return total, beats
+
+
 class BeatConsistency:
     """Running beat-alignment (BC) score over clips, as the evaluation loop accumulates it (test_RAG_ted.py:113-127): for every
     audio onset, exp(-min_m (onset - m)^2 / (2 sigma^2)) over the clip's motion beats; clips without a motion beat contribute
@@ -113,6 +213,33 @@ class BeatConsistency:
             for a in np.asarray(ab, np.float64).reshape(-1):
                 self.align_sum += float(np.exp(-np.min((a - mb) ** 2) / (2.0 * self.sigma * self.sigma)))
             self.num_beats += len(ab)
+
+    def push_timeline(self, beat_mask, onset_frames=None, onset_count=None, audio=None, sr=16000, device=0, **onset_options):
+        """``push`` for device-resident clips of any length: beat_mask [B, N] as ``ted_postprocess_timeline`` returns it, and either
+        the onset slab ``onset_frames`` [B, F] with ``onset_count`` [B] (``audio_onsets``'s onset_raw and count) or ``audio``
+        [B, L], whose onsets are then detected on the device.  The clip sums are formed on the device in float64
+        (``ls_ted_beat_align``); only the per-clip scalars come to the host, into the accumulators ``push`` feeds.  Returns them:
+        (align_sum [B], n_beats [B], onset_count [B])."""
+        if (onset_frames is None) == (audio is None):
+            raise ValueError("pass either onset_frames (with onset_count) or audio")
+        if audio is not None:
+            from . import audio_onsets as ao
+            frames = 1 + int(audio.shape[1]) // ao.HOP
+            if frames > ao.MAX_FRAMES:
+                raise NotImplementedError(f"the onset detector takes at most {ao.MAX_FRAMES} audio frames "
+                                          f"({ao.MAX_FRAMES * ao.HOP / float(sr):.0f} s at {sr} Hz); this audio has {frames}")
+            got = ao.audio_onsets(audio, sr, device=device, want=("count", "onset_raw"), **onset_options)
+            onset_frames, onset_count, counts = got["onset_raw"], got["count"], got["counts"]
+        else:
+            if onset_count is None:
+                raise ValueError("onset_frames needs onset_count [B]")
+            counts = onset_count.cpu().numpy() if hasattr(onset_count, "detach") else np.asarray(onset_count)
+        total, beats = ted_beat_align(beat_mask, onset_frames, onset_count, sigma=self.sigma, sr=sr, device=device)
+        counts = np.asarray(counts).astype(np.int64)
+        self.motion_beats_sum += int(beats.sum())
+        self.align_sum += float(total.sum())
+        self.num_beats += int(counts[beats > 0].sum())
+        return total, beats, counts
 
     def score(self) -> float:
         return self.align_sum / self.num_beats
