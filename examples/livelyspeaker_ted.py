@@ -10,6 +10,7 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py [batch]
     python examples/livelyspeaker_ted.py [batch] --from-motion
     python examples/livelyspeaker_ted.py [batch] --long-seconds N
+    python examples/livelyspeaker_ted.py --long-seconds A,B,...
     python examples/livelyspeaker_ted.py [batch] --clip-text
 --clip-text starts from TOKENS instead of a stand-in feature: synthetic clip.tokenize output -> CLIPTextEncoder (the text tower of CLIP
 on the GPU, synthetic weights) -> text features -> SAG decoder -> the same refinement, with no host wait between the two engines.
@@ -19,6 +20,9 @@ on the GPU, synthetic weights) -> text features -> SAG decoder -> the same refin
 34-frame windows are chained on the device, each conditioned on the last four poses of the one before it, the SAG decoder's output for
 the window's text feature as its init_image, and stitched into one timeline, which long_form.score_timeline then turns into poses,
 motion beats and the beat-consistency score against the speech it was generated from (up to 131 s: the onset detector's 4096 frames).
+--long-seconds A,B,... (a comma list) is a RAGGED batch: one speech per entry, each of its own duration, synthesised and scored in one
+call each (sample_long(audio_lengths=) -> (timeline, frames) -> score_timeline(frames=, audio_lengths=)); it prints every clip's
+frames and beats and the batch's beat-consistency score.
 With real data: load RAG.pt / SAG.pth / the auto-encoder checkpoint with load_model_wo_clip / load_state_dict and build `cond`
 exactly as the reference script does; everything below the weight loading is unchanged.
 """
@@ -145,8 +149,11 @@ def main():
         del sys.argv[i:i + 2]
     if "--long-seconds" in sys.argv:
         i = sys.argv.index("--long-seconds")
-        seconds = float(sys.argv[i + 1])
+        arg = sys.argv[i + 1]
         del sys.argv[i:i + 2]
+        if "," in arg:
+            return main_long_ragged([float(v) for v in arg.split(",") if v], noise_source)
+        seconds = float(arg)
         return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source)
     if "--clip-text" in sys.argv:
         sys.argv.remove("--clip-text")
@@ -260,6 +267,33 @@ def main_long(B, seconds, noise_source):
     print(f"pose {tuple(scored['pose'].shape)}, motion beats {n_beats}, BC {scored['bc']:.4f} (synthetic weights and audio: numbers are "
           f"not quality)")
     assert tuple(scored["pose"].shape) == (B, n_frames, 10, 3) and bool(torch.isfinite(scored["pose"]).all())
+
+
+def main_long_ragged(seconds, noise_source):
+    """One speech per entry of `seconds`, each of its own length, through one sample_long call and one score_timeline call."""
+    import numpy as np
+    from livelyspeaker_amd import long_form
+    cfg, model, diffusion, sag_decoder, _ = build()
+    diffusion.noise_source = noise_source
+    B = len(seconds)
+    lengths = [max(1, int(round(s * 16000))) for s in seconds]
+    plans = long_form.plan_lengths(lengths, cfg)
+    W = max(w for w, _ in plans)
+    g = np.random.Generator(np.random.PCG64(synth.SEED_COND))
+    audio = torch.from_numpy(0.1 * g.standard_normal((B, max(lengths))).astype(np.float32)).cuda()       # rows padded to the longest speech
+    y = {k: torch.from_numpy(v).cuda() for k, v in synth.make_long_cond(cfg, B, W, scale=2.5).items()}
+    text = torch.from_numpy(synth.make_text_features(B * W).reshape(B, W, 512)).cuda()
+    torch.manual_seed(233)
+    timeline, frames = long_form.sample_long(diffusion, model, audio, y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim",
+                                             skip_timesteps=80, sag=sag_decoder, text_features=text, audio_lengths=lengths)
+    assert frames.tolist() == [f for _, f in plans] and bool(torch.isfinite(timeline).all())
+    scored = long_form.score_timeline(timeline, audio, frames=frames, audio_lengths=lengths)
+    print(f"B={B} ({noise_source}): {W} chained windows for the longest speech, timeline {tuple(timeline.shape)}")
+    for b in range(B):
+        print(f"  clip {b}: {seconds[b]:g} s of speech -> {plans[b][0]} windows, {int(frames[b])} frames, "
+              f"{len(scored['motion_beat_times'][b])} motion beats")
+    print(f"BC {scored['bc']:.4f} over the batch (synthetic weights and audio: numbers are not quality)")
+    assert all(not bool(scored["pose"][b, int(frames[b]):].any()) for b in range(B))
 
 
 def main_pipelined(B, N):

@@ -666,7 +666,11 @@ int ls_beat_ldiv(int device, int on_device, int64_t rows, int dim, const float* 
  * input, batch < 1, n_frames > LS_TIMELINE_MAX_FRAMES, n_frames < 4 (TED post and align), < 2 (BEAT post), < 2 order + 2 (BEAT
  * metrics), whatever ls_ted_post / ls_beat_metrics refuse, and for ls_ted_beat_align onset_cols < 1, a host onset_count entry
  * outside [0, onset_cols] (device-resident counts are clamped), fps, sigma or sr not positive, hop < 1.
- * Not built: clips of different valid lengths in one call, timelines longer than LS_TIMELINE_MAX_FRAMES. */
+ * ls_ted_beat_align needs no ragged twin: on a beat mask that is zero beyond each clip's valid frames (what
+ * ls_ted_post_timeline_ragged writes) with per-clip onset counts, its sums and n_beats are those of the solo call at the clip's own
+ * length, bit for bit -- a frame without a beat enters the minimum as +inf and changes nothing, and the onsets are partitioned over the
+ * threads by their index alone.
+ * Not built: timelines longer than LS_TIMELINE_MAX_FRAMES. */
 #define LS_TIMELINE_MAX_FRAMES 4096
 #define LS_TIMELINE_TILE 64
 int ls_ted_post_timeline(int device, int on_device, int batch, int n_frames, const ls_post_config* c, const float* timeline,
@@ -692,9 +696,27 @@ typedef struct ls_ted_align_args {
 } ls_ted_align_args;
 int ls_ted_beat_align(int device, const ls_ted_align_args* a);
 
+/* ---- clips of different lengths in one call ---------------------------------------------------------------
+ * The timeline entries above for a padded batch: n_frames is the ROW STRIDE N_max of every tensor (vel and the BEAT beat_mask keep
+ * row stride N_max - 1) and frames [B] (HOST, in both modes) holds each clip's valid frames.  On clip b's valid range every output
+ * equals, bit for bit, what the equal-length entry returns for that clip alone (batch 1, n_frames = frames[b]); srgr_sum[b] and
+ * align[b] are the clip's own.  Beyond the valid range the outputs are 0 and the inputs are never read.  Work follows the valid
+ * frames: the per-frame kernels run over the tile table of ls_ragged_tiles.  LS_EINVAL without a HIP call: whatever the equal-length
+ * entry refuses, a NULL frames, an entry above n_frames or below the entry's minimum (4 TED, 2 BEAT post, 2 order + 2 metrics).
+ * Not built: device-resident length arrays. */
+int ls_ted_post_timeline_ragged(int device, int on_device, int batch, int n_frames, const int32_t* frames, const ls_post_config* c,
+                                const float* timeline, float* aligned, float* pose, float* angle_diff, unsigned char* beat_mask);
+int ls_beat_post_timeline_ragged(int device, int on_device, int batch, int njoints, int n_frames, const int32_t* frames,
+                                 const float* timeline, float* decoded, float* euler_deg);
+int ls_beat_metrics_timeline_ragged(int device, int n_frames, const int32_t* frames, const ls_beat_metrics_args* a);
+/* The launch plan of the per-frame timeline kernels, on the host (no device is touched): the (clip, first frame) of every tile of
+ * `tile` frames that holds at least one valid frame, clip-major, into clip_out / start_out [cap]; *n_out receives their number.
+ * The outputs may be NULL to ask for the count alone.  LS_EINVAL: batch < 1, a NULL frames, tile < 1, an entry < 1, cap too small. */
+int ls_ragged_tiles(int batch, const int32_t* frames, int tile, int32_t* clip_out, int32_t* start_out, int32_t cap, int32_t* n_out);
+
 /* ---- audio onsets for the beat-alignment scores ------------------------------------------------------------
  * What the reference's scripts take from librosa 0.9.2 (scripts/test_RAG_ted.py:113 onset_detect(y, sr=16000, units='time');
- * scripts_beat/utils/metric.py:60-74 alignment.load_audio), for a batch of equally long clips:
+ * scripts_beat/utils/metric.py:60-74 alignment.load_audio), for a batch of equally long clips (ls_onsets_ragged: of any lengths):
  *   frames     y padded by 1024 on both sides (pad_mode), n_fft 2048, hop 512, periodic Hann: F = 1 + length / 512 frames
  *   mel_db     10 log10(max(1e-10, W P)) with P the power spectrum and W 128 Slaney mel filters on [0, fmax], BEFORE the clip-wide
  *              clamp to (max - 80) that the envelope applies
@@ -733,6 +755,15 @@ typedef struct ls_onsets_args {
     float* kernel_ms;        /* HOST [2]: the spectrum and the pick kernel, timed with events (0 for one not run) */
 } ls_onsets_args;
 int ls_onsets(int device, const ls_onsets_args* a);
+/* ls_onsets for clips of different lengths: a->length is the ROW STRIDE of audio (or envelope) and lengths [B] (HOST, in both modes)
+ * holds each clip's valid samples (frames, with `envelope`), each in [1, a->length].  The outputs keep F = 1 + length / 512 columns
+ * (length columns with `envelope`); clip b has F_b = 1 + lengths[b] / 512 frames (lengths[b] with `envelope`).  On its F_b frames
+ * every output equals, bit for bit, what ls_onsets returns for that clip alone at its own length: the centre padding reflects or
+ * zeroes at the clip's own last sample, the 80 dB clamp and the normalisation use the clip's own maximum, the windows are cut at
+ * F_b.  Beyond them the float outputs are 0 and the onset slabs -1; input beyond a clip's valid length is never read.  The spectrum
+ * runs one wave per valid frame (sum of F_b).  LS_EINVAL without a launch: a NULL lengths, an entry outside [1, length], reflect
+ * padding with an entry <= 1024, and whatever ls_onsets refuses.  Not built: device-resident length arrays. */
+int ls_onsets_ragged(int device, const ls_onsets_args* a, const int32_t* lengths);
 
 /* The tables ls_onsets computes with, built on the host in double and rounded to float32: window [n_fft] (periodic Hann), twiddle
  * [n_fft][2] (exp(-2 pi i n / n_fft)), and librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax, htk=False, norm='slaney') in CSR

@@ -165,6 +165,7 @@ EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set
            "ls_clip_text_create", "ls_clip_text_destroy", "ls_clip_text_last_error", "ls_clip_text_set_weight", "ls_clip_text_commit_weights",
            "ls_clip_text_encode", "ls_clip_text_encode_async", "ls_clip_text_last_encode_ms", "ls_clip_text_stream", "ls_clip_text_plan", "ls_ted_post", "ls_beat_post", "ls_beat_metrics", "ls_beat_ldiv", "ls_onsets", "ls_onsets_tables",
            "ls_ted_post_timeline", "ls_beat_post_timeline", "ls_beat_metrics_timeline", "ls_ted_beat_align",
+           "ls_onsets_ragged", "ls_ted_post_timeline_ragged", "ls_beat_post_timeline_ragged", "ls_beat_metrics_timeline_ragged", "ls_ragged_tiles",
            "ls_train_create", "ls_train_destroy", "ls_train_last_error", "ls_train_set_schedule", "ls_train_param_count",
            "ls_train_flat_size", "ls_train_param_info", "ls_train_set_weight", "ls_train_get_weight", "ls_train_forward_backward",
            "ls_train_adamw", "ls_train_read", "ls_train_get_moment", "ls_train_set_moment", "ls_train_get_step", "ls_train_set_step",
@@ -288,6 +289,12 @@ def load_library(build_if_missing: bool = True):
     lib.ls_beat_post_timeline.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ls_beat_metrics_timeline.argtypes = [C.c_int, C.c_int, C.POINTER(LsBeatMetricsArgs)]
     lib.ls_ted_beat_align.argtypes = [C.c_int, C.POINTER(LsTedAlignArgs)]
+    lib.ls_onsets_ragged.argtypes = [C.c_int, C.POINTER(LsOnsetsArgs), C.c_void_p]
+    lib.ls_ted_post_timeline_ragged.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(LsPostConfig), C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ls_beat_post_timeline_ragged.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ls_beat_metrics_timeline_ragged.argtypes = [C.c_int, C.c_int, C.c_void_p, C.POINTER(LsBeatMetricsArgs)]
+    lib.ls_ragged_tiles.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     lib.ls_onsets_tables.argtypes = [C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     lib.ls_train_set_schedule.argtypes = [C.c_void_p, c_f64p, c_f64p, c_i64p]
@@ -397,6 +404,18 @@ class _Marshal:
             return t, C.c_void_p(t.data_ptr())
         n = np.empty(tuple(shape), np.float32)
         return n, n.ctypes.data_as(C.c_void_p)
+
+
+def host_lengths(values, batch, least, most, name):
+    """The valid lengths of a ragged call as a contiguous host int32 [batch] (the engine reads them on the host in both modes)."""
+    if hasattr(values, "detach"):
+        values = values.detach().cpu().numpy()
+    n = np.ascontiguousarray(np.asarray(values).reshape(-1), dtype=np.int64)
+    if n.shape != (batch,):
+        raise ValueError(f"{name} must hold one length per clip: got {n.size} for {batch} clips")
+    if n.size and (n.min() < least or n.max() > most):
+        raise ValueError(f"{name} must lie in [{least}, {most}], got {n.min()} .. {n.max()}")
+    return n.astype(np.int32)
 
 
 def stream_order(device_index: int, first, then) -> None:

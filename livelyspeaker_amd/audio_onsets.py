@@ -59,13 +59,18 @@ def _i32(m, shape):
 
 
 def audio_onsets(audio=None, sr=16000, sr_pick=None, *, onset_envelope=None, pad_mode="constant", fmax=11025.0, delta=0.07,
-                 device=0, want=("oenv", "count", "onset_raw", "onset_bt", "onset_bt_rms"), timing=None):
-    """``ls_onsets`` on a batch of equally long clips: audio [B, L] (numpy, or a CUDA tensor: then the outputs stay on the device), or
+                 device=0, want=("oenv", "count", "onset_raw", "onset_bt", "onset_bt_rms"), timing=None, lengths=None):
+    """``ls_onsets`` on a batch of clips: audio [B, L] (numpy, or a CUDA tensor: then the outputs stay on the device), or
     ``onset_envelope`` [B, F] for the pick alone.  ``sr_pick`` is the rate onset_detect's picking windows are sized by: ``sr`` when
     the caller passes it to onset_detect (TED), 22050 when it does not (BEAT's load_audio).  Returns a dict of the outputs named in
     ``want``: mel_db [B, F, 128], rms [B, F], oenv [B, F], count [B] and the int32 slabs onset_raw, onset_bt, onset_bt_rms [B, F] of
     which the first count[b] entries of row b are valid; with ``count`` wanted, ``counts`` is its host copy (the one host wait).
-    ``timing``: a list that receives the two kernel times in ms."""
+    ``timing``: a list that receives the two kernel times in ms.
+
+    ``lengths`` (a host sequence [B]): clips of different lengths in one call (``ls_onsets_ragged``).  Clip b holds ``lengths[b]`` valid
+    samples (frames, with ``onset_envelope``) of its row; what follows them is never read.  The outputs keep their [B, F] shapes; on
+    clip b's own ``1 + lengths[b] // 512`` frames they are bit for bit those of the clip alone at its own length, beyond them 0 (floats)
+    and -1 (the slabs).  ``None`` is the equal-length call."""
     if (audio is None) == (onset_envelope is None):
         raise ValueError("pass either audio or onset_envelope")
     if pad_mode not in PAD_MODES:
@@ -85,6 +90,11 @@ def audio_onsets(audio=None, sr=16000, sr_pick=None, *, onset_envelope=None, pad
         raise ValueError(f"need at least one clip and one sample, and at most {MAX_FRAMES} frames: got B={B}, length {L}")
     if not given and pad_mode == "reflect" and L <= N_FFT // 2:
         raise ValueError(f"reflect padding needs more than {N_FFT // 2} samples, got {L}")
+    lens = None
+    if lengths is not None:
+        lens = _lib.host_lengths(lengths, B, 1, L, "lengths")
+        if not given and pad_mode == "reflect" and int(lens.min()) <= N_FFT // 2:
+            raise ValueError(f"reflect padding needs more than {N_FFT // 2} samples in every clip, got {int(lens.min())}")
     lib = _lib.load_library()
     m = _lib._Marshal(device, src)
     a = _lib.LsOnsetsArgs()
@@ -104,9 +114,12 @@ def audio_onsets(audio=None, sr=16000, sr_pick=None, *, onset_envelope=None, pad
     if timing is not None:
         a.kernel_ms = C.cast(ms, C.c_void_p)
     m.ready()
-    rc = lib.ls_onsets(device, C.byref(a))
+    if lens is None:
+        rc, name = lib.ls_onsets(device, C.byref(a)), "ls_onsets"
+    else:
+        rc, name = lib.ls_onsets_ragged(device, C.byref(a), lens.ctypes.data_as(C.c_void_p)), "ls_onsets_ragged"
     if rc != 0:
-        raise _lib.EngineError(f"ls_onsets failed ({rc})")
+        raise _lib.EngineError(f"{name} failed ({rc})")
     if timing is not None:
         timing[:] = [float(ms[0]), float(ms[1])]
     if "count" in out:
@@ -167,9 +180,10 @@ def onset_backtrack(events, energy):
     return m[np.searchsorted(m, events, side="right") - 1]
 
 
-def onset_times(audio, sr=16000, sr_pick=None, which="onset_raw", time_sr=None, **kw):
-    """One array of onset times in seconds per clip of ``audio`` [B, L]: ``which`` frames * 512 / ``time_sr`` (default ``sr``)."""
-    got = audio_onsets(audio, sr, sr_pick, want=("count", which), **kw)
+def onset_times(audio, sr=16000, sr_pick=None, which="onset_raw", time_sr=None, lengths=None, **kw):
+    """One array of onset times in seconds per clip of ``audio`` [B, L]: ``which`` frames * 512 / ``time_sr`` (default ``sr``).
+    ``lengths`` [B]: the clips' valid samples (``audio_onsets``); every clip gets its own onsets."""
+    got = audio_onsets(audio, sr, sr_pick, want=("count", which), lengths=lengths, **kw)
     return [r * HOP / float(time_sr or sr) for r in _rows(got[which], got["counts"])]
 
 

@@ -57,19 +57,24 @@ def beat_metrics(pred_euler, target_euler=None, semantic=None, onset_times=None,
 
 def beat_metrics_timeline(pred_euler, target_euler=None, semantic=None, onset_times=None, *, joints=47, threshold=4.0, scale=SRGR_SCALE,
                           series_joints=BEAT_SERIES_JOINTS, order=2, sigma=0.3, fps=BEAT_FPS, align_series=2, device=0,
-                          want=("success", "srgr_sum", "vel", "beat_mask", "align"), _ragged_onsets=None):
+                          want=("success", "srgr_sum", "vel", "beat_mask", "align"), _ragged_onsets=None, frames=None):
     """``beat_metrics`` on the Euler planes of a stitched timeline, [B, N, joints*3] with 2 * order + 2 <= N <= 4096
     (``ls_beat_metrics_timeline``): every clip is one series of N frames.  success [B,N,J] and beat_mask [B,6,N-1] as bytes,
-    srgr_sum [B], vel [B,6,N-1], align [B]; semantic, if given, is [B, N]; a motion beat at velocity index m lies at m / fps seconds."""
+    srgr_sum [B], vel [B,6,N-1], align [B]; semantic, if given, is [B, N]; a motion beat at velocity index m lies at m / fps seconds.
+    ``frames`` (a host sequence [B], each in [2 * order + 2, N]): the clips' valid frames (``ls_beat_metrics_timeline_ragged``).  N
+    is then the row stride; clip b's numbers are bit for bit those of the clip alone at its own length (mode='clip' clamps at its own
+    last velocity, srgr_sum[b] and align[b] are its own), and success, vel and beat_mask are 0 beyond its valid range."""
     if len(pred_euler.shape) != 3:
         raise ValueError(f"expected Euler planes [B, N, joints*3], got {list(pred_euler.shape)}")
+    if frames is not None:
+        frames = _lib.host_lengths(frames, int(pred_euler.shape[0]), 2 * int(order) + 2, int(pred_euler.shape[1]), "frames")
     return _beat_metrics(int(pred_euler.shape[1]), pred_euler, target_euler, semantic, onset_times, joints, threshold, scale, series_joints,
-                         order, sigma, fps, align_series, device, want, _ragged_onsets)
+                         order, sigma, fps, align_series, device, want, _ragged_onsets, frames)
 
 
 def _beat_metrics(n_frames, pred_euler, target_euler, semantic, onset_times, joints, threshold, scale, series_joints, order, sigma, fps,
-                  align_series, device, want, _ragged_onsets):
-    """Both entry points: ``n_frames`` None is the 34-frame ``ls_beat_metrics``."""
+                  align_series, device, want, _ragged_onsets, frames=None):
+    """All entry points: ``n_frames`` None is the 34-frame ``ls_beat_metrics``, ``frames`` (host int32 [B]) the ragged timeline call."""
     lib = _lib.load_library()
     B = int(pred_euler.shape[0])
     T = 34 if n_frames is None else n_frames
@@ -109,8 +114,11 @@ def _beat_metrics(n_frames, pred_euler, target_euler, semantic, onset_times, joi
     m.ready()
     if n_frames is None:
         rc, name = lib.ls_beat_metrics(device, C.byref(a)), "ls_beat_metrics"
-    else:
+    elif frames is None:
         rc, name = lib.ls_beat_metrics_timeline(device, n_frames, C.byref(a)), "ls_beat_metrics_timeline"
+    else:
+        rc = lib.ls_beat_metrics_timeline_ragged(device, n_frames, frames.ctypes.data_as(C.c_void_p), C.byref(a))
+        name = "ls_beat_metrics_timeline_ragged"
     if rc != 0:
         raise _lib.EngineError(f"{name} failed ({rc})")
     return out

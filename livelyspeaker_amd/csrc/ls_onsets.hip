@@ -6,6 +6,11 @@
 //   k_onset_pick      one workgroup per clip: clip-wide clamp, spectral flux, normalisation, peak picking, both backtracks
 // Every sum is a fixed tree (per-lane order, wave butterfly) and a frame never looks at another clip, so a clip's numbers do not
 // depend on the batch it travels in.  The tables come from the host-only unit ls_onsets_tables.cpp.
+// Ragged batches (ls_onsets_ragged): clip b holds lens[b] valid samples (frames, with a given envelope) in a row of stride L; the same
+// kernel bodies are instantiated with kRagged.  The spectrum runs one wave per VALID frame: wave g finds its clip by a binary search
+// in the prefix sums of the clips' frame counts.  Padding, reflection, the clip-wide maximum, the windows and the backtracks use the
+// clip's own L_b / F_b; only the addresses use the strides L and F.  What lies beyond a clip is never read; its outputs are set by a
+// memset ahead of the launch (0, and 0xFF bytes for the -1 of the onset slabs).
 #include "ls_hip.h"
 #include "ls_host.h"
 #include "ls_onsets.h"
@@ -53,6 +58,8 @@ struct SpectrumParams {
     const float* mel_w;
     float* mel_db;             // [B, F, 128]
     float* rms;                // [B, F] or NULL
+    const int* lens;           // ragged: [B] valid samples of a clip
+    const int* frame_off;      // ragged: [B + 1] prefix sums of the clips' frame counts
 };
 
 // One Stockham radix-4 pass over the 1024 complex numbers of this wave's frame; v holds the lane's 16 inputs x[j + 256 t] for its
@@ -90,12 +97,29 @@ __device__ __forceinline__ void load_pass_inputs(float2 (&v)[16], const float2* 
 
 // Every wave of a workgroup runs the same sequence of barriers: a wave whose frame lies past the end computes on zeros and
 // stores nothing.
+template <bool kRagged>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void k_onset_spectrum(const SpectrumParams p) {
     __shared__ float2 sbuf[kWavesPerBlock][kFrameSlots];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long g = (long long)blockIdx.x * kWavesPerBlock + wave, total = (long long)p.B * p.F;
+    const long long g = (long long)blockIdx.x * kWavesPerBlock + wave, total = kRagged ? (long long)p.frame_off[p.B] : (long long)p.B * p.F;
     const bool live = g < total;
-    const int b = live ? (int)(g / p.F) : 0, t = live ? (int)(g - (long long)b * p.F) : 0;
+    int b = 0, t = 0, L = p.L;                       // L: the clip's own samples; p.L and p.F are the row strides
+    if (kRagged) {
+        if (live) {                                  // the last clip whose first frame is at or before g (wave-uniform)
+            int lo = 0, hi = p.B - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if ((long long)p.frame_off[mid] <= g) lo = mid; else hi = mid - 1;
+            }
+            b = lo;
+            t = (int)(g - p.frame_off[b]);
+        }
+        L = p.lens[b];
+    } else if (live) {
+        b = (int)(g / p.F);
+        t = (int)(g - (long long)b * p.F);
+    }
+    const size_t row = kRagged ? (size_t)b * p.F + t : (size_t)g;      // the frame's place in the [B, F] outputs
     float2* buf = sbuf[wave];
     const float* y = p.audio + (size_t)b * p.L;
 
@@ -113,9 +137,9 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_onset_spectrum(const Sp
                 int i = base + 2 * n + h;
                 if (p.pad_mode == LS_ONSETS_PAD_REFLECT) {          // numpy's 'reflect': the edge sample is not repeated
                     if (i < 0) i = -i;
-                    else if (i >= p.L) i = 2 * (p.L - 1) - i;
+                    else if (i >= L) i = 2 * (L - 1) - i;
                 }
-                s[h] = (live && i >= 0 && i < p.L) ? y[i] * p.window[2 * n + h] : 0.0f;
+                s[h] = (live && i >= 0 && i < L) ? y[i] * p.window[2 * n + h] : 0.0f;
             }
             v[4 * q + r] = make_float2(s[0], s[1]);
         }
@@ -169,7 +193,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_onset_spectrum(const Sp
         s += pk[8];
     }
     s = wave_sum(s);
-    if (live && p.rms && lane == 0) p.rms[g] = sqrtf(2.0f * s / ((float)kNfft * (float)kNfft));
+    if (live && p.rms && lane == 0) p.rms[row] = sqrtf(2.0f * s / ((float)kNfft * (float)kNfft));
     __syncthreads();
 
     // ---- mel: the lane owns filters lane and 127 - lane (a narrow and a wide one) and adds each one's bins in table order ----
@@ -188,7 +212,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void k_onset_spectrum(const Sp
             m += w3 * P[c3];
         }
         for (; i < i1; ++i) m += p.mel_w[i] * P[p.mel_col[i]];
-        if (live) p.mel_db[(size_t)g * kMels + f] = 10.0f * log10f(fmaxf(1e-10f, m));
+        if (live) p.mel_db[row * kMels + f] = 10.0f * log10f(fmaxf(1e-10f, m));
     }
 }
 
@@ -202,6 +226,7 @@ struct PickParams {
     const float* rms;          // [B, F] or NULL
     float* oenv;
     int *count, *onset_raw, *onset_bt, *onset_bt_rms;
+    const int* frame_off;      // ragged: [B + 1] prefix sums of the clips' frame counts; F is the row stride
 };
 
 // the four wave partials of a 256-thread block combined in wave order; every thread receives the result
@@ -220,6 +245,7 @@ __device__ __forceinline__ bool is_minimum(const float* e, int n, int F) {
 
 }  // namespace
 
+template <bool kRagged>
 __global__ __launch_bounds__(256) void k_onset_pick(const PickParams p) {
     __shared__ float senv[kMaxF];            // the envelope
     __shared__ float sx[kMaxF];              // normalised; once the detections are marked, the picked frames (sraw)
@@ -227,13 +253,14 @@ __global__ __launch_bounds__(256) void k_onset_pick(const PickParams p) {
     __shared__ unsigned char sdet[kMaxF];    // passes the maximum and the threshold test
     __shared__ float part[4];
     __shared__ int scount;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, F = p.F;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, FS = p.F;
+    const int F = kRagged ? p.frame_off[b + 1] - p.frame_off[b] : FS;          // the clip's own frames
 
     if (p.given) {
-        for (int n = tid; n < F; n += 256) senv[n] = p.envelope[(size_t)b * F + n];
+        for (int n = tid; n < F; n += 256) senv[n] = p.envelope[(size_t)b * FS + n];
     } else {
         // ---- S = max(S, clip max - 80); d[t] = mean over the mels of max(0, S[t + 1] - S[t]); the envelope is d shifted by 3 ----
-        const float* S = p.mel_db + (size_t)b * F * kMels;
+        const float* S = p.mel_db + (size_t)b * FS * kMels;
         float mx = -INFINITY;
         for (int i = tid; i < F * kMels; i += 256) mx = fmaxf(mx, S[i]);
         mx = block_combine(wave_max(mx), part, [](float a, float c) { return fmaxf(a, c); });
@@ -249,7 +276,7 @@ __global__ __launch_bounds__(256) void k_onset_pick(const PickParams p) {
         }
     }
     if (p.rms)
-        for (int n = tid; n < F; n += 256) srms[n] = p.rms[(size_t)b * F + n];
+        for (int n = tid; n < F; n += 256) srms[n] = p.rms[(size_t)b * FS + n];
     __syncthreads();
 
     // ---- x = (oenv - min) / (max(oenv - min) + tiny); an envelope without a non-zero entry has no onsets ----
@@ -257,7 +284,7 @@ __global__ __launch_bounds__(256) void k_onset_pick(const PickParams p) {
     for (int n = tid; n < F; n += 256) {
         lo = fminf(lo, senv[n]);
         hi = fmaxf(hi, senv[n]);
-        if (p.oenv) p.oenv[(size_t)b * F + n] = senv[n];
+        if (p.oenv) p.oenv[(size_t)b * FS + n] = senv[n];
     }
     lo = block_combine(wave_min(lo), part, [](float a, float c) { return fminf(a, c); });
     hi = block_combine(wave_max(hi), part, [](float a, float c) { return fmaxf(a, c); });
@@ -294,7 +321,7 @@ __global__ __launch_bounds__(256) void k_onset_pick(const PickParams p) {
     __syncthreads();
     const int c = scount;
     for (int n = tid; n < F; n += 256)
-        if (p.onset_raw) p.onset_raw[(size_t)b * F + n] = n < c ? sraw[n] : -1;
+        if (p.onset_raw) p.onset_raw[(size_t)b * FS + n] = n < c ? sraw[n] : -1;
 
     // ---- backtracks: the nearest minimum at or before each onset, one serial walk per energy (wave 0: oenv, wave 1: rms) ----
     if (lane == 0 && wave < 2) {
@@ -304,17 +331,17 @@ __global__ __launch_bounds__(256) void k_onset_pick(const PickParams p) {
             int cur = 0, i = 0;
             for (int n = 0; n < F && i < c; ++n) {
                 if (is_minimum(e, n, F)) cur = n;
-                while (i < c && sraw[i] == n) out[(size_t)b * F + i++] = cur;
+                while (i < c && sraw[i] == n) out[(size_t)b * FS + i++] = cur;
             }
-            for (; i < F; ++i) out[(size_t)b * F + i] = -1;
+            for (; i < F; ++i) out[(size_t)b * FS + i] = -1;
         }
     }
 }
 
-}  // namespace ls
+namespace {
 
-extern "C" int ls_onsets(int device, const ls_onsets_args* a) {
-    using namespace ls;
+// both entry points: `lengths` [B] (HOST) is read by the ragged one alone
+int onsets(int device, const ls_onsets_args* a, const int32_t* lengths, bool ragged) {
     if (!a || a->batch < 1 || a->length < 1) return LS_EINVAL;
     if ((a->audio == nullptr) == (a->envelope == nullptr)) return LS_EINVAL;          // exactly one input
     const bool given = a->envelope != nullptr;
@@ -329,6 +356,18 @@ extern "C" int ls_onsets(int device, const ls_onsets_args* a) {
     const long long F64 = given ? a->length : 1 + a->length / kHop;
     if (F64 > kMaxF) return LS_EINVAL;
     const int B = a->batch, L = a->length, F = (int)F64;
+    std::vector<int32_t> frame_off;                  // ragged: prefix sums of the clips' frame counts
+    if (ragged) {
+        if (!lengths) return LS_EINVAL;
+        frame_off.assign((size_t)B + 1, 0);
+        for (int b = 0; b < B; ++b) {
+            if (lengths[b] < 1 || lengths[b] > L) return LS_EINVAL;
+            if (!given && a->pad_mode == LS_ONSETS_PAD_REFLECT && lengths[b] <= kHalf) return LS_EINVAL;
+            const long long next = (long long)frame_off[b] + (given ? lengths[b] : 1 + lengths[b] / kHop);
+            if (next > 0x7fffffffLL) return LS_EINVAL;
+            frame_off[b + 1] = (int32_t)next;
+        }
+    }
     const bool want_pick = given || a->oenv || a->count || a->onset_raw || a->onset_bt || a->onset_bt_rms;
     const size_t n_bf = (size_t)B * F;
     if ((n_bf + kWavesPerBlock - 1) / kWavesPerBlock > 0x7fffffffull) return LS_EINVAL;
@@ -336,7 +375,7 @@ extern "C" int ls_onsets(int device, const ls_onsets_args* a) {
 
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-    DevBuf t_in, t_win, t_tw, t_ptr, t_col, t_w, t_db, t_rms, t_env, t_cnt, t_raw, t_bt, t_btr;      // device temporaries, freed on return
+    DevBuf t_in, t_win, t_tw, t_ptr, t_col, t_w, t_db, t_rms, t_env, t_cnt, t_raw, t_bt, t_btr, t_len, t_off;      // device temporaries, freed on return
     auto up = [&](DevBuf& buf, const void* src, size_t bytes) -> void* {
         chk(buf.ensure(bytes ? bytes : 4));        // a filterbank may be empty (fmax below the first bin)
         if (e == hipSuccess && bytes) chk(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice));
@@ -382,16 +421,30 @@ extern "C" int ls_onsets(int device, const ls_onsets_args* a) {
         if (a->onset_bt) pp.onset_bt = static_cast<int*>(tmp(t_bt, n_bf * 4));
         if (a->onset_bt_rms) pp.onset_bt_rms = static_cast<int*>(tmp(t_btr, n_bf * 4));
     }
+    if (ragged) {                                    // the lengths are host data in both modes; the padding values go in ahead of the launch
+        pp.frame_off = sp.frame_off = static_cast<const int*>(up(t_off, frame_off.data(), frame_off.size() * 4));
+        if (!given) sp.lens = static_cast<const int*>(up(t_len, lengths, (size_t)B * 4));
+        auto fill = [&](void* d, int byte, size_t bytes) { if (d && e == hipSuccess) chk(hipMemset(d, byte, bytes)); };
+        if (a->mel_db) fill(sp.mel_db, 0, n_bf * kMels * 4);
+        if (a->rms) fill(sp.rms, 0, n_bf * 4);
+        fill(pp.oenv, 0, n_bf * 4);
+        fill(pp.onset_raw, 0xFF, n_bf * 4);
+        fill(pp.onset_bt, 0xFF, n_bf * 4);
+        fill(pp.onset_bt_rms, 0xFF, n_bf * 4);
+    }
     if (e == hipSuccess) {
         if (!given) {
-            const long long blocks = ((long long)n_bf + kWavesPerBlock - 1) / kWavesPerBlock;
+            const long long waves = ragged ? (long long)frame_off[B] : (long long)n_bf;
+            const long long blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
             if (ev[0]) chk(hipEventRecord(ev[0], 0));
-            hipLaunchKernelGGL(k_onset_spectrum, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, 0, sp);
+            if (ragged) hipLaunchKernelGGL(k_onset_spectrum<true>, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, 0, sp);
+            else hipLaunchKernelGGL(k_onset_spectrum<false>, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, 0, sp);
             if (ev[1]) chk(hipEventRecord(ev[1], 0));
         }
         if (want_pick) {
             if (ev[2]) chk(hipEventRecord(ev[2], 0));
-            hipLaunchKernelGGL(k_onset_pick, dim3(B), dim3(256), 0, 0, pp);
+            if (ragged) hipLaunchKernelGGL(k_onset_pick<true>, dim3(B), dim3(256), 0, 0, pp);
+            else hipLaunchKernelGGL(k_onset_pick<false>, dim3(B), dim3(256), 0, 0, pp);
             if (ev[3]) chk(hipEventRecord(ev[3], 0));
         }
         chk(hipGetLastError());
@@ -416,3 +469,10 @@ extern "C" int ls_onsets(int device, const ls_onsets_args* a) {
     }
     return e == hipSuccess ? LS_OK : LS_EHIP;
 }
+
+}  // namespace
+}  // namespace ls
+
+extern "C" int ls_onsets(int device, const ls_onsets_args* a) { return ls::onsets(device, a, nullptr, false); }
+
+extern "C" int ls_onsets_ragged(int device, const ls_onsets_args* a, const int32_t* lengths) { return ls::onsets(device, a, lengths, true); }

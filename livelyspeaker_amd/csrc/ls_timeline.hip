@@ -14,6 +14,10 @@
 // an odd row stride (ds_write banks are (a/4) % 32: 32 lanes at an odd stride touch 32 banks), as k_chain_window does; every output
 // leaves along its own innermost axis.  Sums are fixed trees (per-thread stride order, wave butterfly, four wave partials in order).
 // Algorithmic bytes per clip (fp32): TED reads 108 N and writes 108 N + 120 N + 5 N; BEAT post reads 1128 N and writes 1692 N.
+// Ragged batches (the *_ragged entries): clip b holds frames[b] valid frames in rows of stride N_max.  The per-frame kernels are the
+// same bodies instantiated with kRagged: a 1-D grid over the (clip, first frame) table of ls_ragged_tiles, so work follows the valid
+// frames, and every clamp, halo and beat range uses the clip's own N_b; only the addresses use the stride.  What lies beyond a clip's
+// valid range is never read and is zeroed by a memset ahead of the launch.
 #include <deque>
 
 #include "ls_hip.h"
@@ -51,27 +55,49 @@ __device__ __forceinline__ int wave_sum(int v) {
     return v;
 }
 
+// device arrays of a ragged call: the clips' valid frames [B] and the tile table [grid] (all NULL in an equal-length call)
+struct RaggedPlan {
+    const int *frames, *tile_clip, *tile_start;
+};
+
+// the workgroup's clip, first frame and the clip's frame count; `stride` is the row stride in frames (equal lengths: the count itself)
+template <bool kRagged>
+__device__ __forceinline__ void tile_of(const RaggedPlan& r, int dense_clip, int stride, int& b, int& t0, int& N) {
+    if (kRagged) {
+        b = r.tile_clip[blockIdx.x];
+        t0 = r.tile_start[blockIdx.x];
+        N = r.frames[b];
+    } else {
+        b = dense_clip;
+        t0 = blockIdx.x * kTile;
+        N = stride;
+    }
+}
+
 }  // namespace
 
-__global__ __launch_bounds__(256) void k_ted_timeline(const float* __restrict__ sample, PostParams p, int N, float* __restrict__ aligned,
-                                                      float* __restrict__ pose, float* __restrict__ angle_diff,
-                                                      unsigned char* __restrict__ beat_mask) {
+template <bool kRagged>
+__global__ __launch_bounds__(256) void k_ted_timeline(const float* __restrict__ sample, PostParams p, int NS, RaggedPlan rp,
+                                                      float* __restrict__ aligned, float* __restrict__ pose,
+                                                      float* __restrict__ angle_diff, unsigned char* __restrict__ beat_mask) {
     __shared__ float sv[kStage][kLd];           // raw, then aligned + mean (un-normalised)
     __shared__ float sn[kStage][kLd];           // per-bone unit vectors, later the tile's poses
     __shared__ float sang[kMaxPairs][kStage];
     __shared__ float sdiff[kStage];
-    const int b = blockIdx.y, t0 = blockIdx.x * kTile, tid = threadIdx.x;
+    int b, t0, N;                                                       // N: the clip's own frames; NS: the row stride
+    tile_of<kRagged>(rp, blockIdx.y, NS, b, t0, N);
+    const int tid = threadIdx.x;
     const int JF = p.njoints * 3, f_lo = t0 - 2;                       // staged row l holds frame f_lo + l
     for (int i = tid; i < JF * kStage; i += 256) {                      // lanes along the frame axis
         const int c = i / kStage, l = i - c * kStage, f = f_lo + l;
-        if (f >= 0 && f < N) sv[l][c] = sample[((size_t)b * JF + c) * N + f];
+        if (f >= 0 && f < N) sv[l][c] = sample[((size_t)b * JF + c) * NS + f];
     }
     __syncthreads();
     for (int i = tid; i < kStage * JF; i += 256) {                      // [B,J,F,N] -> [B,N,J*F]: lanes along the channel axis
         const int l = i / JF, c = i - l * JF, f = f_lo + l;
         if (f < 0 || f >= N) continue;
         const float v = sv[l][c];
-        if (aligned && l >= 2 && l < 2 + kTile) aligned[((size_t)b * N + f) * JF + c] = v;
+        if (aligned && l >= 2 && l < 2 + kTile) aligned[((size_t)b * NS + f) * JF + c] = v;
         sv[l][c] = v + p.mean_dir_vec[c];
     }
     __syncthreads();
@@ -90,7 +116,7 @@ __global__ __launch_bounds__(256) void k_ted_timeline(const float* __restrict__ 
         if (f >= 0 && f < N) {
             const float d = f > 0 ? ted_angle_change(p, &sang[0][l], &sang[0][l - 1], kStage) : 0.f;
             sdiff[l] = d;
-            if (angle_diff && l >= 2 && l < 2 + kTile) angle_diff[(size_t)b * N + f] = d;
+            if (angle_diff && l >= 2 && l < 2 + kTile) angle_diff[(size_t)b * NS + f] = d;
         }
     }
     __syncthreads();
@@ -98,7 +124,7 @@ __global__ __launch_bounds__(256) void k_ted_timeline(const float* __restrict__ 
         const int l = tid + 2, f = t0 + tid;
         bool beat = false;
         if (f >= 2 && f <= N - 2) beat = ted_is_beat(sdiff[l], sdiff[l - 1], sdiff[l + 1], p.thres);
-        beat_mask[(size_t)b * N + f] = beat ? 1 : 0;
+        beat_mask[(size_t)b * NS + f] = beat ? 1 : 0;
     }
     if (!pose) return;
     if (tid < kTile && t0 + tid < N) ted_pose_frame(p, sv[tid + 2], sn[tid + 2]);      // sn: every reader is past the barrier above
@@ -106,25 +132,28 @@ __global__ __launch_bounds__(256) void k_ted_timeline(const float* __restrict__ 
     const int PJ = p.n_pose_joints * 3;
     for (int i = tid; i < kTile * PJ; i += 256) {
         const int l = i / PJ, c = i - l * PJ, f = t0 + l;
-        if (f < N) pose[((size_t)b * N + f) * PJ + c] = sn[l + 2][c];
+        if (f < N) pose[((size_t)b * NS + f) * PJ + c] = sn[l + 2][c];
     }
 }
 
+template <bool kRagged>
 __global__ __launch_bounds__(256) void k_beat_post_timeline(const float* __restrict__ sample, float* __restrict__ decoded,
-                                                            float* __restrict__ euler, int J, int N) {
+                                                            float* __restrict__ euler, int J, int NS, RaggedPlan rp) {
     __shared__ float s6[kTile][kLd6];
     __shared__ float s3[kTile][kLd3];
-    const int t0 = blockIdx.x * kTile, j0 = blockIdx.y * kJChunk, b = blockIdx.z, tid = threadIdx.x;
+    int b, t0, N;
+    tile_of<kRagged>(rp, blockIdx.z, NS, b, t0, N);
+    const int j0 = blockIdx.y * kJChunk, tid = threadIdx.x;
     const int nj = J - j0 < kJChunk ? J - j0 : kJChunk, C = nj * 6, E = nj * 3;
     for (int i = tid; i < C * kTile; i += 256) {                        // lanes along the frame axis
         const int c = i / kTile, l = i - c * kTile, f = t0 + l;
-        if (f < N) s6[l][c] = sample[(((size_t)b * J + j0) * 6 + c) * N + f];
+        if (f < N) s6[l][c] = sample[(((size_t)b * J + j0) * 6 + c) * NS + f];
     }
     __syncthreads();
     if (decoded) {
         for (int i = tid; i < kTile * C; i += 256) {
             const int l = i / C, c = i - l * C, f = t0 + l;
-            if (f < N) decoded[(((size_t)b * N + f) * J + j0) * 6 + c] = s6[l][c];
+            if (f < N) decoded[(((size_t)b * NS + f) * J + j0) * 6 + c] = s6[l][c];
         }
     }
     if (!euler) return;
@@ -140,7 +169,7 @@ __global__ __launch_bounds__(256) void k_beat_post_timeline(const float* __restr
     __syncthreads();
     for (int i = tid; i < kTile * E; i += 256) {
         const int l = i / E, c = i - l * E, f = t0 + l;
-        if (f < N) euler[(((size_t)b * N + f) * J + j0) * 3 + c] = s3[l][c];
+        if (f < N) euler[(((size_t)b * NS + f) * J + j0) * 3 + c] = s3[l][c];
     }
 }
 
@@ -154,6 +183,7 @@ struct TimelineMetricsParams {
     const long long* onset_offsets;
     unsigned char *success, *beat_mask;
     float *srgr_sum, *vel, *align;
+    RaggedPlan rp;              // N is the row stride of a ragged call
 };
 
 struct TedAlignParams {
@@ -169,20 +199,23 @@ struct TedAlignParams {
 
 // k_beat_metrics's per-entry expressions on frames [t0, t0 + kTile) of clip b; the velocities of a series are staged with `order`
 // neighbours on either side of the tile, clamped to the clip as argrelextrema's mode='clip' clamps them
+template <bool kRagged>
 __global__ __launch_bounds__(256) void k_beat_metrics_timeline(const TimelineMetricsParams p) {
 #pragma clang fp contract(off)
     __shared__ float svel[kTile + kMaxN];
-    const int b = blockIdx.y, t0 = blockIdx.x * kTile, tid = threadIdx.x;
-    const int N = p.N, V = N - 1, JC = p.J * 3;
-    const float* pred = p.pred + (size_t)b * N * JC;
+    int b, t0, N;
+    tile_of<kRagged>(p.rp, blockIdx.y, p.N, b, t0, N);
+    const int tid = threadIdx.x;
+    const int NS = p.N, VS = NS - 1, V = N - 1, JC = p.J * 3;
+    const float* pred = p.pred + (size_t)b * NS * JC;
     if (p.target && p.success) {
-        const float* tar = p.target + (size_t)b * N * JC;
+        const float* tar = p.target + (size_t)b * NS * JC;
         const int e1 = (t0 + kTile < N ? t0 + kTile : N) * p.J;
         for (int e = t0 * p.J + tid; e < e1; e += 256) {
             const float* a = pred + (size_t)e * 3;
             const float* t = tar + (size_t)e * 3;
             const float diff = (fabsf(a[0] - t[0]) + fabsf(a[1] - t[1])) + fabsf(a[2] - t[2]);
-            p.success[(size_t)b * N * p.J + e] = diff < p.threshold ? 1 : 0;
+            p.success[(size_t)b * NS * p.J + e] = diff < p.threshold ? 1 : 0;
         }
     }
     if ((!p.vel && !p.beat_mask) || t0 >= V) return;
@@ -196,7 +229,7 @@ __global__ __launch_bounds__(256) void k_beat_metrics_timeline(const TimelineMet
             const float dx = c[0] - a[0], dy = c[1] - a[1], dz = c[2] - a[2];
             const float v = sqrtf((dx * dx + dy * dy) + dz * dz);
             svel[i] = v;
-            if (p.vel && f >= t0 && f < t0 + kTile) p.vel[((size_t)b * kSeries + s) * V + f] = v;
+            if (p.vel && f >= t0 && f < t0 + kTile) p.vel[((size_t)b * kSeries + s) * VS + f] = v;
         }
         __syncthreads();
         if (p.beat_mask && tid < kTile && t0 + tid < V) {
@@ -207,24 +240,25 @@ __global__ __launch_bounds__(256) void k_beat_metrics_timeline(const TimelineMet
                 const int l = f - k < 0 ? 0 : f - k, h = f + k > V - 1 ? V - 1 : f + k;
                 beat = x < svel[l - lo] && x < svel[h - lo];
             }
-            p.beat_mask[((size_t)b * kSeries + s) * V + f] = beat ? 1 : 0;
+            p.beat_mask[((size_t)b * kSeries + s) * VS + f] = beat ? 1 : 0;
         }
         __syncthreads();
     }
 }
 
 // the clip's two sums, in k_beat_metrics's order, from the masks k_beat_metrics_timeline left in global memory
+template <bool kRagged>
 __global__ __launch_bounds__(256) void k_beat_reduce_timeline(const TimelineMetricsParams p) {
 #pragma clang fp contract(off)
     __shared__ float sbeat[kMaxN];              // the time of a beat of the series the alignment uses, +inf where there is none
     __shared__ float part[4];
     const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
-    const int N = p.N, V = N - 1;
+    const int NS = p.N, VS = NS - 1, N = kRagged ? p.rp.frames[b] : NS, V = N - 1;
     if (p.srgr_sum) {
-        const unsigned char* ok = p.success + (size_t)b * N * p.J;
+        const unsigned char* ok = p.success + (size_t)b * NS * p.J;
         float s = 0.f;
         for (int e = tid; e < N * p.J; e += 256)
-            if (ok[e]) s += (p.semantic ? p.semantic[(size_t)b * N + e / p.J] : 1.0f) * p.scale;
+            if (ok[e]) s += (p.semantic ? p.semantic[(size_t)b * NS + e / p.J] : 1.0f) * p.scale;
         s = wave_sum(s);
         if ((tid & 63) == 0) part[wave] = s;
         __syncthreads();
@@ -233,7 +267,7 @@ __global__ __launch_bounds__(256) void k_beat_reduce_timeline(const TimelineMetr
     }
     if (!p.align) return;
     for (int i = tid; i < V; i += 256)
-        sbeat[i] = p.beat_mask[((size_t)b * kSeries + p.align_series) * V + i] ? (float)i / p.fps : INFINITY;
+        sbeat[i] = p.beat_mask[((size_t)b * kSeries + p.align_series) * VS + i] ? (float)i / p.fps : INFINITY;
     __syncthreads();
     const long long o0 = p.onset_offsets[b], o1 = p.onset_offsets[b + 1];
     const float two_var = 2.0f * (p.sigma * p.sigma);
@@ -327,6 +361,9 @@ struct Staging {
         if (dst) downs.push_back({dst, d, count * sizeof(T)});
         return d;
     }
+    void zero(void* d, size_t bytes) {             // the padding value of a ragged call's output, ahead of the launch
+        if (d && bytes && e == hipSuccess) chk(hipMemset(d, 0, bytes));
+    }
     int finish() {
         chk(hipGetLastError());
         chk(hipDeviceSynchronize());
@@ -338,12 +375,36 @@ struct Staging {
 
 inline unsigned tiles_of(int n_frames) { return (unsigned)((n_frames + kTile - 1) / kTile); }
 
-}  // namespace
-}  // namespace ls
+// the launch plan of a ragged call: frames[b] in [least, stride] is checked by the caller; the table is ls_ragged_tiles's
+struct TilePlan {
+    std::vector<int32_t> table;                   // frames [B], then the tiles' clips [n] and first frames [n]: one upload
+    size_t n = 0;
+    RaggedPlan dev{};
+    bool build(int batch, const int32_t* frames) {
+        int32_t count = 0;
+        if (ls_ragged_tiles(batch, frames, kTile, nullptr, nullptr, 0, &count) != LS_OK) return false;
+        n = (size_t)count;
+        table.assign(frames, frames + batch);
+        table.resize((size_t)batch + 2 * n);
+        return ls_ragged_tiles(batch, frames, kTile, table.data() + batch, table.data() + batch + n, count, &count) == LS_OK;
+    }
+    void upload(Staging& st, int batch) {         // lengths are host data in both modes
+        dev.frames = st.upload(table.data(), table.size());
+        dev.tile_clip = dev.frames + batch;
+        dev.tile_start = dev.tile_clip + n;
+    }
+    unsigned tiles() const { return (unsigned)n; }
+};
 
-extern "C" int ls_ted_post_timeline(int device, int on_device, int batch, int n_frames, const ls_post_config* c, const float* timeline,
-                                    float* aligned, float* pose, float* angle_diff, unsigned char* beat_mask) {
-    using namespace ls;
+inline bool frames_within(int batch, const int32_t* frames, long long least, int stride) {
+    if (!frames) return false;
+    for (int b = 0; b < batch; ++b)
+        if (frames[b] < least || frames[b] > stride) return false;
+    return true;
+}
+
+int ted_post_timeline(int device, int on_device, int batch, int n_frames, const int32_t* frames, bool ragged, const ls_post_config* c,
+                      const float* timeline, float* aligned, float* pose, float* angle_diff, unsigned char* beat_mask) {
     if (!c || !timeline || batch < 1 || n_frames < 4 || n_frames > kMaxN) return LS_EINVAL;
     if (c->njoints < 1 || c->njoints > kMaxBones || c->n_pairs < 0 || c->n_pairs > kMaxPairs || c->n_pose_joints < 0 ||
         c->n_pose_joints > kMaxBones + 1)
@@ -352,6 +413,8 @@ extern "C" int ls_ted_post_timeline(int device, int on_device, int batch, int n_
         if (c->bone_parent[j] < 0 || c->bone_parent[j] > kMaxBones || c->bone_child[j] < 0 || c->bone_child[j] > kMaxBones) return LS_EINVAL;
     for (int k = 0; k < c->n_pairs; ++k)
         if (c->pair_a[k] < 0 || c->pair_a[k] >= c->njoints || c->pair_b[k] < 0 || c->pair_b[k] >= c->njoints) return LS_EINVAL;
+    TilePlan plan;
+    if (ragged && (!frames_within(batch, frames, 4, n_frames) || !plan.build(batch, frames))) return LS_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;
     PostParams p{};
     p.njoints = c->njoints; p.n_pairs = c->n_pairs; p.thres = c->thres; p.n_pose_joints = c->n_pose_joints;
@@ -365,30 +428,48 @@ extern "C" int ls_ted_post_timeline(int device, int on_device, int batch, int n_
     float* d_pose = st.out(pose, n_t * c->n_pose_joints * 3);
     float* d_diff = st.out(angle_diff, n_t);
     unsigned char* d_mask = st.out(beat_mask, n_t);
-    if (st.e == hipSuccess)
-        hipLaunchKernelGGL(k_ted_timeline, dim3(tiles_of(n_frames), batch), dim3(256), 0, 0, d_in, p, n_frames, d_al, d_pose, d_diff, d_mask);
+    if (ragged) {
+        plan.upload(st, batch);
+        st.zero(d_al, n_in * 4);
+        st.zero(d_pose, n_t * c->n_pose_joints * 3 * 4);
+        st.zero(d_diff, n_t * 4);
+        st.zero(d_mask, n_t);
+        if (st.e == hipSuccess)
+            hipLaunchKernelGGL(k_ted_timeline<true>, dim3(plan.tiles()), dim3(256), 0, 0, d_in, p, n_frames, plan.dev, d_al, d_pose, d_diff, d_mask);
+    } else if (st.e == hipSuccess) {
+        hipLaunchKernelGGL(k_ted_timeline<false>, dim3(tiles_of(n_frames), batch), dim3(256), 0, 0, d_in, p, n_frames, RaggedPlan{}, d_al, d_pose,
+                           d_diff, d_mask);
+    }
     return st.finish();
 }
 
-extern "C" int ls_beat_post_timeline(int device, int on_device, int batch, int njoints, int n_frames, const float* timeline,
-                                     float* decoded, float* euler_deg) {
-    using namespace ls;
+int beat_post_timeline(int device, int on_device, int batch, int njoints, int n_frames, const int32_t* frames, bool ragged,
+                       const float* timeline, float* decoded, float* euler_deg) {
     if (!timeline || batch < 1 || njoints < 1 || n_frames < 2 || n_frames > kMaxN) return LS_EINVAL;
     const unsigned chunks = (unsigned)((njoints + kJChunk - 1) / kJChunk);
     if (chunks > 65535u || batch > 65535) return LS_EINVAL;              // grid dimensions y and z
+    TilePlan plan;
+    if (ragged && (!frames_within(batch, frames, 2, n_frames) || !plan.build(batch, frames))) return LS_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;
     const size_t n_in = (size_t)batch * njoints * 6 * n_frames;
     Staging st(on_device != 0);
     const float* d_in = st.in(timeline, n_in);
     float* d_dec = st.out(decoded, n_in);
     float* d_eu = st.out(euler_deg, n_in / 2);
-    if (st.e == hipSuccess)
-        hipLaunchKernelGGL(k_beat_post_timeline, dim3(tiles_of(n_frames), chunks, batch), dim3(256), 0, 0, d_in, d_dec, d_eu, njoints, n_frames);
+    if (ragged) {
+        plan.upload(st, batch);
+        st.zero(d_dec, n_in * 4);
+        st.zero(d_eu, n_in / 2 * 4);
+        if (st.e == hipSuccess)
+            hipLaunchKernelGGL(k_beat_post_timeline<true>, dim3(plan.tiles(), chunks), dim3(256), 0, 0, d_in, d_dec, d_eu, njoints, n_frames, plan.dev);
+    } else if (st.e == hipSuccess) {
+        hipLaunchKernelGGL(k_beat_post_timeline<false>, dim3(tiles_of(n_frames), chunks, batch), dim3(256), 0, 0, d_in, d_dec, d_eu, njoints, n_frames,
+                           RaggedPlan{});
+    }
     return st.finish();
 }
 
-extern "C" int ls_beat_metrics_timeline(int device, int n_frames, const ls_beat_metrics_args* a) {
-    using namespace ls;
+int beat_metrics_timeline(int device, int n_frames, const int32_t* frames, bool ragged, const ls_beat_metrics_args* a) {
     if (!a || !a->pred || a->batch < 1 || a->njoints < 1 || a->order < 1) return LS_EINVAL;
     if (n_frames > kMaxN || (long long)n_frames < 2LL * a->order + 2) return LS_EINVAL;
     if (!a->target && (a->success || a->srgr_sum)) return LS_EINVAL;          // SRGR needs the target planes
@@ -407,6 +488,8 @@ extern "C" int ls_beat_metrics_timeline(int device, int n_frames, const ls_beat_
         if (!(a->sigma > 0.f) || !(a->fps > 0.f)) return LS_EINVAL;
     }
     if (B > 65535) return LS_EINVAL;                                           // grid dimension y
+    TilePlan plan;
+    if (ragged && (!frames_within(B, frames, 2LL * a->order + 2, N) || !plan.build(B, frames))) return LS_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;
     const size_t n_eu = (size_t)B * N * a->njoints * 3, n_tj = (size_t)B * N * a->njoints, n_v = (size_t)B * kSeries * V;
     TimelineMetricsParams p{};
@@ -426,10 +509,74 @@ extern "C" int ls_beat_metrics_timeline(int device, int n_frames, const ls_beat_
     p.vel = st.out(a->vel, n_v);
     p.beat_mask = st.out(a->beat_mask, n_v, a->align != nullptr);
     p.align = st.out(a->align, (size_t)B);
-    if (st.e == hipSuccess && ((p.target && p.success) || p.vel || p.beat_mask))
-        hipLaunchKernelGGL(k_beat_metrics_timeline, dim3(tiles_of(N), B), dim3(256), 0, 0, p);
-    if (st.e == hipSuccess && (p.srgr_sum || p.align)) hipLaunchKernelGGL(k_beat_reduce_timeline, dim3(B), dim3(256), 0, 0, p);
+    const bool frame_pass = (p.target && p.success) || p.vel || p.beat_mask, reduce = p.srgr_sum || p.align;
+    if (ragged) {
+        plan.upload(st, B);
+        p.rp = plan.dev;
+        st.zero(p.success, n_tj);
+        st.zero(p.vel, n_v * 4);
+        st.zero(p.beat_mask, n_v);
+        if (st.e == hipSuccess && frame_pass) hipLaunchKernelGGL(k_beat_metrics_timeline<true>, dim3(plan.tiles()), dim3(256), 0, 0, p);
+        if (st.e == hipSuccess && reduce) hipLaunchKernelGGL(k_beat_reduce_timeline<true>, dim3(B), dim3(256), 0, 0, p);
+    } else {
+        if (st.e == hipSuccess && frame_pass) hipLaunchKernelGGL(k_beat_metrics_timeline<false>, dim3(tiles_of(N), B), dim3(256), 0, 0, p);
+        if (st.e == hipSuccess && reduce) hipLaunchKernelGGL(k_beat_reduce_timeline<false>, dim3(B), dim3(256), 0, 0, p);
+    }
     return st.finish();
+}
+
+}  // namespace
+}  // namespace ls
+
+extern "C" int ls_ragged_tiles(int batch, const int32_t* frames, int tile, int32_t* clip_out, int32_t* start_out, int32_t cap,
+                               int32_t* n_out) {
+    if (batch < 1 || !frames || tile < 1) return LS_EINVAL;
+    long long n = 0;
+    for (int b = 0; b < batch; ++b) {
+        if (frames[b] < 1) return LS_EINVAL;
+        n += ((long long)frames[b] + tile - 1) / tile;
+    }
+    if (n > 0x7fffffffLL) return LS_EINVAL;
+    if (clip_out || start_out) {
+        if ((long long)cap < n) return LS_EINVAL;
+        long long i = 0;
+        for (int b = 0; b < batch; ++b)
+            for (long long t0 = 0; t0 < frames[b]; t0 += tile, ++i) {
+                if (clip_out) clip_out[i] = b;
+                if (start_out) start_out[i] = (int32_t)t0;
+            }
+    }
+    if (n_out) *n_out = (int32_t)n;
+    return LS_OK;
+}
+
+extern "C" int ls_ted_post_timeline(int device, int on_device, int batch, int n_frames, const ls_post_config* c, const float* timeline,
+                                    float* aligned, float* pose, float* angle_diff, unsigned char* beat_mask) {
+    return ls::ted_post_timeline(device, on_device, batch, n_frames, nullptr, false, c, timeline, aligned, pose, angle_diff, beat_mask);
+}
+
+extern "C" int ls_ted_post_timeline_ragged(int device, int on_device, int batch, int n_frames, const int32_t* frames,
+                                           const ls_post_config* c, const float* timeline, float* aligned, float* pose, float* angle_diff,
+                                           unsigned char* beat_mask) {
+    return ls::ted_post_timeline(device, on_device, batch, n_frames, frames, true, c, timeline, aligned, pose, angle_diff, beat_mask);
+}
+
+extern "C" int ls_beat_post_timeline(int device, int on_device, int batch, int njoints, int n_frames, const float* timeline,
+                                     float* decoded, float* euler_deg) {
+    return ls::beat_post_timeline(device, on_device, batch, njoints, n_frames, nullptr, false, timeline, decoded, euler_deg);
+}
+
+extern "C" int ls_beat_post_timeline_ragged(int device, int on_device, int batch, int njoints, int n_frames, const int32_t* frames,
+                                            const float* timeline, float* decoded, float* euler_deg) {
+    return ls::beat_post_timeline(device, on_device, batch, njoints, n_frames, frames, true, timeline, decoded, euler_deg);
+}
+
+extern "C" int ls_beat_metrics_timeline(int device, int n_frames, const ls_beat_metrics_args* a) {
+    return ls::beat_metrics_timeline(device, n_frames, nullptr, false, a);
+}
+
+extern "C" int ls_beat_metrics_timeline_ragged(int device, int n_frames, const int32_t* frames, const ls_beat_metrics_args* a) {
+    return ls::beat_metrics_timeline(device, n_frames, frames, true, a);
 }
 
 extern "C" int ls_ted_beat_align(int device, const ls_ted_align_args* a) {

@@ -37,6 +37,13 @@ def plan_windows(n_audio_samples, cfg):
     return (W,) + _window_sizes(W, cfg)
 
 
+def plan_lengths(audio_lengths, cfg):
+    """Per clip of a ragged batch: ``(W_b, frames_b)`` -- the windows that cover ``audio_lengths[b]`` samples and the frames of that
+    clip's stitched timeline, both from ``plan_windows``."""
+    plans = [plan_windows(int(n), cfg) for n in np.asarray(audio_lengths).reshape(-1)]
+    return [(W, frames) for W, _, frames in plans]
+
+
 def _window_sizes(W, cfg):
     T, npre = int(cfg.nframes), int(cfg.n_pre_seq)
     return int(cfg.audio_len) + (W - 1) * AUDIO_STRIDE, T + (W - 1) * (T - npre)
@@ -117,7 +124,8 @@ def _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, n_
 
 
 def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=None, n_windows=None, sampler='ddim', skip_timesteps=0,
-                eta=0.0, clip_denoised=False, sag=None, text_features=None, encoder_chunk=None, return_windows=False, **unsupported):
+                eta=0.0, clip_denoised=False, sag=None, text_features=None, encoder_chunk=None, return_windows=False, audio_lengths=None,
+                **unsupported):
     """``n_windows`` chained windows for ``audio`` [B, L] (default: the windows that cover it, ``plan_windows``) as one timeline
     ``[B, J, F, T + (W - 1) * (T - n_pre)]`` on the inputs' device; ``return_windows=True`` adds the raw windows ``[W, B, J, F, T]``.
 
@@ -125,9 +133,29 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
     [B] or [B, W].  ``sampler``: 'ddim' (``eta``) or 'ddpm'; ``skip_timesteps`` as in the sample loops.  ``sag`` (a
     ``Decoder_TRANSFORMER``) with ``text_features`` [B, W, 512] is the LivelySpeaker chain: window w starts from
     ``sag({'x': origin_x_w, 'z': text_features[:, w], 'mask': ones})['output']`` as its ``init_image``.  The noise source is the
-    diffusion object's (``'torch_cpu'`` or ``'philox'``); ``const_noise``, ``dump_steps`` and the inpainting inputs are refused."""
+    diffusion object's (``'torch_cpu'`` or ``'philox'``); ``const_noise``, ``dump_steps`` and the inpainting inputs are refused.
+
+    ``audio_lengths`` (a host sequence [B], each in [1, L]): speeches of different lengths in one call.  ``audio[b, audio_lengths[b]:]``
+    counts as silence (a zero-filled copy is sampled from; the caller's tensor is not modified), the call runs the windows of the
+    longest clip (``W_max`` of ``plan_lengths``; ``emo`` [B, W] and ``text_features`` [B, W, 512] are sized by it), clip b's timeline
+    is zero beyond its own ``frames_b``, and the result is ``(timeline, frames)`` -- ``(timeline, frames, windows)`` with
+    ``return_windows`` -- with ``frames`` the host int32 [B] that ``score_timeline(frames=, audio_lengths=)`` takes.  Together with
+    ``n_windows`` it raises ``ValueError``.  Not built: dropping finished clips from later windows.  The engine plans one batch size
+    per call, so a short clip still pays for ``W_max`` windows; running a shrinking prefix of length-sorted clips is a follow-up."""
+    if audio_lengths is not None and n_windows is not None:
+        raise ValueError("sample_long: audio_lengths decide the windows of every clip; pass either n_windows or audio_lengths")
     as_t = lambda a: a if (a is None or th.is_tensor(a)) else th.as_tensor(np.asarray(a))      # noqa: E731
     audio, seed_poses, vid_indices, scale, emo, text_features = (as_t(a) for a in (audio, seed_poses, vid_indices, scale, emo, text_features))
+    frames = None
+    if audio_lengths is not None and hasattr(model, "model"):      # another model type is _check_args's to refuse
+        if audio.ndim != 2:
+            raise ValueError(f"audio must be [B, L], got {list(audio.shape)}")
+        lens = _lib.host_lengths(audio_lengths, int(audio.shape[0]), 1, int(audio.shape[1]), "audio_lengths")
+        plans = plan_lengths(lens, model.model)
+        n_windows = max(W for W, _ in plans)
+        frames = np.array([f for _, f in plans], np.int32)
+        valid = th.arange(int(audio.shape[1]))[None, :] < th.from_numpy(lens.astype(np.int64))[:, None]
+        audio = th.where(valid.to(audio.device), audio, th.zeros((), dtype=audio.dtype, device=audio.device))       # a copy; NaN tails become 0
     B, W = _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, n_windows, sampler, skip_timesteps, sag, text_features,
                        encoder_chunk, unsupported)
     if diffusion.model_mean_type != gd.ModelMeanType.START_X or diffusion.model_var_type != gd.ModelVarType.FIXED_SMALL:
@@ -165,26 +193,49 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
     res = eng.long_sample(**kw)
     timeline, windows = res if return_windows else (res, None)
     timeline = gd._as_tensor(timeline, out_dev)
+    if frames is not None:
+        keep = th.arange(int(timeline.shape[3]))[None, :] < th.from_numpy(frames.astype(np.int64))[:, None]
+        timeline = th.where(keep.to(timeline.device)[:, None, None, :], timeline, th.zeros((), dtype=timeline.dtype, device=timeline.device))
+        return (timeline, frames, gd._as_tensor(windows, out_dev)) if return_windows else (timeline, frames)
     return (timeline, gd._as_tensor(windows, out_dev)) if return_windows else timeline
 
 
-def timeline_clips(x, stride=34):
+def timeline_clips(x, stride=34, frames=None):
     """Frame-major timeline planes [B, N, C] (``aligned_motions``, ``decoded_motions``, ``pred_euler``) cut into 34-frame clips
     [B * K, 34, C], one every ``stride`` frames (K = (N - 34) // stride + 1; clip b * K + k starts at frame k * stride of timeline b), so
     that a timeline feeds ``EmbeddingSpaceEvaluator.push_samples`` / ``BeatEvaluator.push`` unchanged.  Tail frames that do not fill a
-    clip are dropped.  torch ``unfold`` plus a reshape; numpy in, numpy out."""
+    clip are dropped.  torch ``unfold`` plus a reshape; numpy in, numpy out.
+
+    ``frames`` (a host sequence [B], each in [1, N]): clip b holds ``frames[b]`` valid frames.  The result is then the pair (packed
+    clips [sum K_b, 34, C], offsets [B + 1] host int64) with K_b = (frames[b] - 34) // stride + 1, and 0 for a clip shorter than 34
+    frames; timeline b owns clips offsets[b] .. offsets[b + 1].  One advanced-indexing gather from indices built on the host."""
     as_np = isinstance(x, np.ndarray)
     t = th.as_tensor(x)
-    if t.ndim != 3 or int(t.shape[1]) < 34:
-        raise ValueError(f"expected [B, N, C] with N >= 34, got {list(t.shape)}")
     if int(stride) < 1:
         raise ValueError(f"stride must be >= 1, got {stride}")
+    if frames is not None:
+        if t.ndim != 3:
+            raise ValueError(f"expected [B, N, C], got {list(t.shape)}")
+        B, N, Cn = _shape(t)
+        fr = _lib.host_lengths(frames, B, 1, N, "frames").astype(np.int64)
+        K = np.where(fr >= 34, (fr - 34) // int(stride) + 1, 0)
+        offsets = np.zeros(B + 1, np.int64)
+        np.cumsum(K, out=offsets[1:])
+        rows = np.repeat(np.arange(B), K)
+        first = (np.arange(int(offsets[-1])) - offsets[rows]) * int(stride)
+        ri = th.from_numpy(rows).to(t.device)[:, None]
+        fi = th.from_numpy(first[:, None] + np.arange(34)[None, :]).to(t.device)
+        clips = t[ri, fi].contiguous()                                   # [sum K_b, 34, C]
+        return (clips.numpy() if as_np else clips), offsets
+    if t.ndim != 3 or int(t.shape[1]) < 34:
+        raise ValueError(f"expected [B, N, C] with N >= 34, got {list(t.shape)}")
     B, _, Cn = _shape(t)
     clips = t.unfold(1, 34, int(stride)).permute(0, 1, 3, 2).reshape(-1, 34, Cn).contiguous()       # [B, K, C, 34] -> [B*K, 34, C]
     return clips.numpy() if as_np else clips
 
 
-def score_timeline(timeline, audio, dataset="ted", sr=16000, device=0, target_euler=None, semantic=None, bc=None, **options):
+def score_timeline(timeline, audio, dataset="ted", sr=16000, device=0, target_euler=None, semantic=None, bc=None, frames=None,
+                   audio_lengths=None, **options):
     """The whole chain behind ``sample_long``: post-process a stitched timeline [B, J, F, N] and score it against the ``audio`` [B, L] it
     was generated from, on the device (N up to 4096 frames; audio up to the onset detector's 4096 audio frames, 131 s at 16 kHz).
 
@@ -193,7 +244,12 @@ def score_timeline(timeline, audio, dataset="ted", sr=16000, device=0, target_eu
     ``BeatConsistency`` passed as ``bc``).  ``dataset='beat'``: ``beat_postprocess_timeline``, onsets as ``alignment.load_audio``
     finds them, ``beat_metrics_timeline``; returns pred_euler, beat_mask, align [B], and srgr (the rate over the call) when
     ``target_euler`` [B, N, J*3] is given (``semantic`` [B, N] weighs its frames).  ``options`` go to the metric calls (BEAT: order,
-    sigma, threshold, ...; TED: pad_mode, fmax, delta of the onset detector)."""
+    sigma, threshold, ...; TED: pad_mode, fmax, delta of the onset detector).
+
+    ``frames`` [B] with ``audio_lengths`` [B] (host sequences, as ``sample_long(audio_lengths=)`` returns and takes them): clips of
+    different lengths in one call.  N and L are then row strides, every clip is post-processed and scored at its own length (the
+    ragged engine entries), the outputs are 0 beyond a clip's valid frames, BEAT's srgr divides by sum(frames) * J, and the limits of
+    4096 frames apply per clip.  One without the other raises ``ValueError``."""
     from . import audio_onsets as ao
     from . import beat_metrics as bm
     from . import postprocess as pp
@@ -201,25 +257,35 @@ def score_timeline(timeline, audio, dataset="ted", sr=16000, device=0, target_eu
         raise ValueError(f"dataset must be 'ted' or 'beat', got {dataset!r}")
     if len(audio.shape) != 2 or int(audio.shape[0]) != int(timeline.shape[0]):
         raise ValueError(f"audio must be [B, L] with one row per timeline clip, got {list(audio.shape)}")
-    frames = 1 + int(audio.shape[1]) // ao.HOP
-    if frames > ao.MAX_FRAMES:
+    if (frames is None) != (audio_lengths is None):
+        raise ValueError("frames and audio_lengths go together: the valid frames of every timeline and the valid samples of its audio")
+    B = int(timeline.shape[0])
+    longest = int(audio.shape[1])
+    if audio_lengths is not None:
+        audio_lengths = _lib.host_lengths(audio_lengths, B, 1, longest, "audio_lengths")
+        frames = _lib.host_lengths(frames, B, 1, int(timeline.shape[3]), "frames")
+        longest = int(audio_lengths.max())
+        audio = audio[:, :longest]                        # the row stride: nothing past the longest clip is looked at
+    audio_frames = 1 + longest // ao.HOP
+    if audio_frames > ao.MAX_FRAMES:
         raise NotImplementedError(f"the onset detector takes at most {ao.MAX_FRAMES} audio frames ({ao.MAX_FRAMES * ao.HOP / float(sr):.0f} s "
-                                  f"at {sr} Hz); this audio has {frames}")
+                                  f"at {sr} Hz); this audio has {audio_frames}")
     if dataset == "ted":
-        post = pp.ted_postprocess_timeline(timeline, device=device)
+        post = pp.ted_postprocess_timeline(timeline, device=device, frames=frames)
         acc = bc if bc is not None else pp.BeatConsistency()
-        acc.push_timeline(post["beat_mask"], audio=audio, sr=sr, device=device, **options)
+        acc.push_timeline(post["beat_mask"], audio=audio, sr=sr, device=device, frames=frames, audio_lengths=audio_lengths, **options)
         return {"pose": post["pose"], "beat_mask": post["beat_mask"], "motion_beat_times": post["motion_beat_times"],
                 "bc": acc.score() if acc.num_beats else float("nan")}
     onset_opts = {k: options.pop(k) for k in ("pad_mode", "fmax") if k in options}
-    post = pp.beat_postprocess_timeline(timeline, device=device)
-    onsets = ao.onset_times(audio, sr, 22050, which="onset_bt_rms", time_sr=22050, device=device, **onset_opts)
+    post = pp.beat_postprocess_timeline(timeline, device=device, frames=frames)
+    onsets = ao.onset_times(audio, sr, 22050, which="onset_bt_rms", time_sr=22050, device=device, lengths=audio_lengths, **onset_opts)
     want = ("beat_mask", "align") + (("srgr_sum",) if target_euler is not None else ())
     got = bm.beat_metrics_timeline(post["pred_euler"], target_euler, semantic, onsets, joints=int(timeline.shape[1]), device=device,
-                                   want=want, **options)
+                                   want=want, frames=frames, **options)
     res = {"pred_euler": post["pred_euler"], "beat_mask": got["beat_mask"], "align": got["align"]}
     if target_euler is not None:
         s = got["srgr_sum"]
         s = s.detach().cpu().numpy() if hasattr(s, "detach") else np.asarray(s)
-        res["srgr"] = float(s.astype(np.float64).sum()) / (int(timeline.shape[0]) * int(timeline.shape[3]) * int(timeline.shape[1]))
+        total_frames = B * int(timeline.shape[3]) if frames is None else int(frames.astype(np.int64).sum())
+        res["srgr"] = float(s.astype(np.float64).sum()) / (total_frames * int(timeline.shape[1]))
     return res

@@ -103,15 +103,22 @@ def _timeline_frames(timeline, feats, least):
     return N
 
 
-def ted_postprocess_timeline(timeline, device: int = 0, want_pose: bool = True) -> dict:
+def _clip_frames(frames, B, least, N):
+    return None if frames is None else _lib.host_lengths(frames, B, least, N, "frames")
+
+
+def ted_postprocess_timeline(timeline, device: int = 0, want_pose: bool = True, frames=None) -> dict:
     """``ted_postprocess`` on a stitched timeline [B, 9, 3, N] of any length N in [4, 4096] (``long_form.sample_long``), as ONE series
     per clip: nothing resets at a window seam (``ls_ted_post_timeline``).  Returns aligned_motions [B,N,27], pose [B,N,10,3],
     angle_diff [B,N], beat_mask [B,N] (bool; beats at t in [2, N-2]) and motion_beat_times (one list of seconds, t/15, per clip).
-    All clips of a call have the same length."""
+    ``frames`` (a host sequence [B], each in [4, N]): clips of different lengths in one call (``ls_ted_post_timeline_ragged``); N is
+    then the row stride.  On clip b's first ``frames[b]`` frames every output is bit for bit that of the clip alone at its own length
+    (beats at t in [2, frames[b] - 2]); beyond them the outputs are 0 and the input is never read."""
     lib = _lib.load_library()
     N = _timeline_frames(timeline, 3, 4)
     m = _lib._Marshal(device, timeline)
     B = int(timeline.shape[0])
+    fr = _clip_frames(frames, B, 4, N)
     cfg = ted_post_config()
     aligned, p_al = m.out((B, N, 27))
     pose, p_pose = m.out((B, N, 10, 3)) if want_pose else (None, None)
@@ -119,29 +126,40 @@ def ted_postprocess_timeline(timeline, device: int = 0, want_pose: bool = True) 
     mask, p_mask = _bytes_out(m, (B, N))
     p_in = m.f32(timeline, (B, 9, 3, N))
     m.ready()
-    rc = lib.ls_ted_post_timeline(device, int(m.on_device), B, N, C.byref(cfg), p_in, p_al, p_pose, p_diff, p_mask)
+    if fr is None:
+        rc, name = lib.ls_ted_post_timeline(device, int(m.on_device), B, N, C.byref(cfg), p_in, p_al, p_pose, p_diff, p_mask), "ls_ted_post_timeline"
+    else:
+        rc = lib.ls_ted_post_timeline_ragged(device, int(m.on_device), B, N, fr.ctypes.data_as(C.c_void_p), C.byref(cfg), p_in, p_al, p_pose,
+                                             p_diff, p_mask)
+        name = "ls_ted_post_timeline_ragged"
     if rc != 0:
-        raise _lib.EngineError(f"ls_ted_post_timeline failed ({rc})")
+        raise _lib.EngineError(f"{name} failed ({rc})")
     mask_np = mask.cpu().numpy() if m.on_device else mask
     beats = [[float(t) / TED_FPS for t in np.nonzero(mask_np[b])[0]] for b in range(B)]
     return {"aligned_motions": aligned, "pose": pose, "angle_diff": diff,
             "beat_mask": mask.bool() if m.on_device else mask.astype(bool), "motion_beat_times": beats}
 
 
-def beat_postprocess_timeline(timeline, device: int = 0, want_euler: bool = True) -> dict:
+def beat_postprocess_timeline(timeline, device: int = 0, want_euler: bool = True, frames=None) -> dict:
     """``beat_postprocess`` on a stitched timeline [B, J, 6, N], N in [2, 4096] (``ls_beat_post_timeline``): decoded_motions
-    [B, N, J*6] and pred_euler [B, N, J*3] in degrees, which ``beat_metrics.beat_metrics_timeline`` scores."""
+    [B, N, J*6] and pred_euler [B, N, J*3] in degrees, which ``beat_metrics.beat_metrics_timeline`` scores.  ``frames`` (a host
+    sequence [B], each in [2, N]): the clips' valid frames (``ls_beat_post_timeline_ragged``); the outputs are 0 beyond them."""
     lib = _lib.load_library()
     N = _timeline_frames(timeline, 6, 2)
     m = _lib._Marshal(device, timeline)
     B, J = int(timeline.shape[0]), int(timeline.shape[1])
+    fr = _clip_frames(frames, B, 2, N)
     dec, p_dec = m.out((B, N, J * 6))
     eul, p_eul = m.out((B, N, J * 3)) if want_euler else (None, None)
     p_in = m.f32(timeline, (B, J, 6, N))
     m.ready()
-    rc = lib.ls_beat_post_timeline(device, int(m.on_device), B, J, N, p_in, p_dec, p_eul)
+    if fr is None:
+        rc, name = lib.ls_beat_post_timeline(device, int(m.on_device), B, J, N, p_in, p_dec, p_eul), "ls_beat_post_timeline"
+    else:
+        rc = lib.ls_beat_post_timeline_ragged(device, int(m.on_device), B, J, N, fr.ctypes.data_as(C.c_void_p), p_in, p_dec, p_eul)
+        name = "ls_beat_post_timeline_ragged"
     if rc != 0:
-        raise _lib.EngineError(f"ls_beat_post_timeline failed ({rc})")
+        raise _lib.EngineError(f"{name} failed ({rc})")
     return {"decoded_motions": dec, "pred_euler": eul}
 
 
@@ -214,21 +232,36 @@ class BeatConsistency:
                 self.align_sum += float(np.exp(-np.min((a - mb) ** 2) / (2.0 * self.sigma * self.sigma)))
             self.num_beats += len(ab)
 
-    def push_timeline(self, beat_mask, onset_frames=None, onset_count=None, audio=None, sr=16000, device=0, **onset_options):
+    def push_timeline(self, beat_mask, onset_frames=None, onset_count=None, audio=None, sr=16000, device=0, frames=None,
+                      audio_lengths=None, **onset_options):
         """``push`` for device-resident clips of any length: beat_mask [B, N] as ``ted_postprocess_timeline`` returns it, and either
         the onset slab ``onset_frames`` [B, F] with ``onset_count`` [B] (``audio_onsets``'s onset_raw and count) or ``audio``
         [B, L], whose onsets are then detected on the device.  The clip sums are formed on the device in float64
         (``ls_ted_beat_align``); only the per-clip scalars come to the host, into the accumulators ``push`` feeds.  Returns them:
-        (align_sum [B], n_beats [B], onset_count [B])."""
+        (align_sum [B], n_beats [B], onset_count [B]).
+
+        Clips of different lengths: ``frames`` [B] are the clips' valid frames -- beat_mask must be 0 beyond them, which is what
+        ``ted_postprocess_timeline(frames=)`` returns -- and ``audio_lengths`` [B] the valid samples of the rows of ``audio``, whose
+        onsets then come from ``ls_onsets_ragged``.  ``ls_ted_beat_align`` itself needs no lengths: a frame without a beat
+        contributes nothing, so the sums and the running counts hold the valid beats and onsets alone."""
         if (onset_frames is None) == (audio is None):
             raise ValueError("pass either onset_frames (with onset_count) or audio")
+        if audio_lengths is not None and audio is None:
+            raise ValueError("audio_lengths are the valid samples of audio: pass audio")
+        if frames is not None:
+            _clip_frames(frames, int(beat_mask.shape[0]), 4, int(beat_mask.shape[1]))
         if audio is not None:
             from . import audio_onsets as ao
-            frames = 1 + int(audio.shape[1]) // ao.HOP
-            if frames > ao.MAX_FRAMES:
+            longest = int(audio.shape[1])
+            if audio_lengths is not None:
+                audio_lengths = _lib.host_lengths(audio_lengths, int(audio.shape[0]), 1, longest, "audio_lengths")
+                longest = int(audio_lengths.max())
+                audio = audio[:, :longest]                # the row stride: nothing past the longest clip is uploaded
+            n_audio_frames = 1 + longest // ao.HOP
+            if n_audio_frames > ao.MAX_FRAMES:
                 raise NotImplementedError(f"the onset detector takes at most {ao.MAX_FRAMES} audio frames "
-                                          f"({ao.MAX_FRAMES * ao.HOP / float(sr):.0f} s at {sr} Hz); this audio has {frames}")
-            got = ao.audio_onsets(audio, sr, device=device, want=("count", "onset_raw"), **onset_options)
+                                          f"({ao.MAX_FRAMES * ao.HOP / float(sr):.0f} s at {sr} Hz); this audio has {n_audio_frames}")
+            got = ao.audio_onsets(audio, sr, device=device, want=("count", "onset_raw"), lengths=audio_lengths, **onset_options)
             onset_frames, onset_count, counts = got["onset_raw"], got["count"], got["counts"]
         else:
             if onset_count is None:
