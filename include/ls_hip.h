@@ -586,7 +586,10 @@ typedef struct ls_post_config {
     float mean_dir_vec[48];     /* (:22)                                                         */
 } ls_post_config;
 /* sample [B,J,3,34] -> aligned [B,34,J*3], pose [B,34,n_pose_joints,3], angle_diff [B,34], beat_mask [B,34] (bytes);
- * any output may be NULL.  Pointers are device pointers iff on_device. */
+ * any output may be NULL.  Pointers are device pointers iff on_device.  LS_EINVAL without a HIP call (the one check the timeline
+ * entries share): a NULL config or sample, batch < 1, njoints outside [1, 16], n_pairs outside [0, 8], n_pose_joints outside
+ * [0, 17], a bone_parent or bone_child of the first njoints bones outside [0, 16], a pair index of the first n_pairs pairs outside
+ * [0, njoints).  (Earlier versions passed an out-of-range bone or pair index on to the kernel.) */
 int ls_ted_post(int device, int on_device, int batch, const ls_post_config* c, const float* sample, float* aligned,
                 float* pose, float* angle_diff, unsigned char* beat_mask);
 

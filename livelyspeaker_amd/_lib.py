@@ -322,6 +322,10 @@ def _is_cuda(a) -> bool:
     return hasattr(a, "is_cuda") and bool(a.is_cuda)
 
 
+# torch's name of a marshalled dtype, by table: numpy's own dtype.name costs microseconds per call
+_TORCH_NAMES = {np.float32: "float32", np.float64: "float64", np.int32: "int32", np.int64: "int64", np.uint8: "uint8"}
+
+
 class _Marshal:
     """Turns a group of arrays (numpy / torch CPU / torch CUDA) into raw pointers for one ABI call.
     If ANY member is a CUDA tensor the whole group is passed as device pointers (on_device=1) and outputs
@@ -343,30 +347,19 @@ class _Marshal:
     def i64(self, a, shape=None):
         return self._conv(a, np.int64, shape)
 
+    def i32(self, a, shape=None):
+        return self._conv(a, np.int32, shape)
+
     def u8(self, a, shape=None):
         """bool / byte mask -> bytes"""
-        if a is None:
-            return None
-        if self.on_device:
-            t = self.torch.as_tensor(a).to(device=self.dev, dtype=self.torch.uint8).contiguous()
-            if shape is not None:
-                assert tuple(t.shape) == tuple(shape), (tuple(t.shape), tuple(shape))
-            self.keep.append(t)
-            return C.c_void_p(t.data_ptr())
-        if hasattr(a, "detach"):
-            a = a.detach().cpu().numpy()
-        n = np.ascontiguousarray(a, dtype=np.uint8)
-        if shape is not None:
-            assert tuple(n.shape) == tuple(shape), (n.shape, tuple(shape))
-        self.keep.append(n)
-        return n.ctypes.data_as(C.c_void_p)
+        return self._conv(a, np.uint8, shape)
 
     def _conv(self, a, dtype, shape):
         if a is None:
             return None
         if self.on_device:
             t = self.torch.as_tensor(a)
-            t = t.to(device=self.dev, dtype=self.torch.float32 if dtype == np.float32 else self.torch.int64).contiguous()
+            t = t.to(device=self.dev, dtype=getattr(self.torch, _TORCH_NAMES[dtype])).contiguous()
             if shape is not None:
                 assert tuple(t.shape) == tuple(shape), (tuple(t.shape), tuple(shape))
             self.keep.append(t)
@@ -385,9 +378,9 @@ class _Marshal:
         the BEAT callers) and the allocation of the outputs -- belong to torch's current stream: the handle's stream is made to
         wait for that stream's work so far (an event, ls_stream_order) instead of the host waiting for it."""
         if self.on_device:
-            ts = self.torch.cuda.current_stream(self.dev).cuda_stream
-            if self.stream is None or load_library().ls_stream_order(self.device_index, C.c_void_p(ts), C.c_void_p(self.stream)) != 0:
-                self.torch.cuda.current_stream(self.dev).synchronize()
+            ts = self.torch.cuda.current_stream(self.dev)
+            if self.stream is None or load_library().ls_stream_order(self.device_index, C.c_void_p(ts.cuda_stream), C.c_void_p(self.stream)) != 0:
+                ts.synchronize()
 
     def done_async(self):
         """After a no_sync ABI call: torch's current stream waits for the handle's work (outputs, and inputs it still reads), so
@@ -397,13 +390,20 @@ class _Marshal:
             if self.stream is None or load_library().ls_stream_order(self.device_index, C.c_void_p(self.stream), C.c_void_p(ts)) != 0:
                 raise EngineError("ls_stream_order failed")
 
-    def out(self, shape):
-        """(object, pointer) for an fp32 output of this call."""
+    def out(self, shape, dtype=np.float32):
+        """(object, pointer) for an output of this call: float32, uint8, int32 or float64."""
         if self.on_device:
-            t = self.torch.empty(tuple(shape), dtype=self.torch.float32, device=self.dev)
+            t = self.torch.empty(tuple(shape), dtype=getattr(self.torch, _TORCH_NAMES[dtype]), device=self.dev)
             return t, C.c_void_p(t.data_ptr())
-        n = np.empty(tuple(shape), np.float32)
+        n = np.empty(tuple(shape), dtype)
         return n, n.ctypes.data_as(C.c_void_p)
+
+
+def call(name, *args):
+    """Call the handle-less export ``name``; a non-zero return raises.  The export is looked up by name at every call."""
+    rc = getattr(load_library(), name)(*args)
+    if rc != 0:
+        raise EngineError(f"{name} failed ({rc})")
 
 
 def host_lengths(values, batch, least, most, name):

@@ -50,14 +50,6 @@ def mel_filterbank(sr=16000, n_fft=N_FFT, n_mels=N_MELS, fmin=0.0, fmax=11025.0)
     return W
 
 
-def _i32(m, shape):
-    if m.on_device:
-        t = m.torch.empty(tuple(shape), dtype=m.torch.int32, device=m.dev)
-        return t, C.c_void_p(t.data_ptr())
-    n = np.empty(tuple(shape), np.int32)
-    return n, n.ctypes.data_as(C.c_void_p)
-
-
 def audio_onsets(audio=None, sr=16000, sr_pick=None, *, onset_envelope=None, pad_mode="constant", fmax=11025.0, delta=0.07,
                  device=0, want=("oenv", "count", "onset_raw", "onset_bt", "onset_bt_rms"), timing=None, lengths=None):
     """``ls_onsets`` on a batch of clips: audio [B, L] (numpy, or a CUDA tensor: then the outputs stay on the device), or
@@ -95,7 +87,6 @@ def audio_onsets(audio=None, sr=16000, sr_pick=None, *, onset_envelope=None, pad
         lens = _lib.host_lengths(lengths, B, 1, L, "lengths")
         if not given and pad_mode == "reflect" and int(lens.min()) <= N_FFT // 2:
             raise ValueError(f"reflect padding needs more than {N_FFT // 2} samples in every clip, got {int(lens.min())}")
-    lib = _lib.load_library()
     m = _lib._Marshal(device, src)
     a = _lib.LsOnsetsArgs()
     a.batch, a.length, a.on_device, a.pad_mode = B, L, int(m.on_device), PAD_MODES[pad_mode]
@@ -108,18 +99,16 @@ def audio_onsets(audio=None, sr=16000, sr_pick=None, *, onset_envelope=None, pad
     shapes = {"mel_db": (B, F, N_MELS), "rms": (B, F), "oenv": (B, F)}
     for name in OUTPUTS:
         if name in want:
-            out[name], ptr = m.out(shapes[name]) if name in shapes else _i32(m, (B,) if name == "count" else (B, F))
+            out[name], ptr = m.out(shapes[name]) if name in shapes else m.out((B,) if name == "count" else (B, F), np.int32)
             setattr(a, name, ptr)
     ms = (C.c_float * 2)()
     if timing is not None:
         a.kernel_ms = C.cast(ms, C.c_void_p)
     m.ready()
     if lens is None:
-        rc, name = lib.ls_onsets(device, C.byref(a)), "ls_onsets"
+        _lib.call("ls_onsets", device, C.byref(a))
     else:
-        rc, name = lib.ls_onsets_ragged(device, C.byref(a), lens.ctypes.data_as(C.c_void_p)), "ls_onsets_ragged"
-    if rc != 0:
-        raise _lib.EngineError(f"{name} failed ({rc})")
+        _lib.call("ls_onsets_ragged", device, C.byref(a), lens.ctypes.data_as(C.c_void_p))
     if timing is not None:
         timing[:] = [float(ms[0]), float(ms[1])]
     if "count" in out:

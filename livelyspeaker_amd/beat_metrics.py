@@ -75,7 +75,6 @@ def beat_metrics_timeline(pred_euler, target_euler=None, semantic=None, onset_ti
 def _beat_metrics(n_frames, pred_euler, target_euler, semantic, onset_times, joints, threshold, scale, series_joints, order, sigma, fps,
                   align_series, device, want, _ragged_onsets, frames=None):
     """All entry points: ``n_frames`` None is the 34-frame ``ls_beat_metrics``, ``frames`` (host int32 [B]) the ragged timeline call."""
-    lib = _lib.load_library()
     B = int(pred_euler.shape[0])
     T = 34 if n_frames is None else n_frames
     V = T - 1
@@ -92,49 +91,36 @@ def _beat_metrics(n_frames, pred_euler, target_euler, semantic, onset_times, joi
         a.onset_times = m.f32(flat, (flat.size,))
         a.onset_offsets = off.ctypes.data_as(C.c_void_p)
 
-    def u8(shp):
-        if m.on_device:
-            t = m.torch.empty(shp, dtype=m.torch.uint8, device=m.dev)
-            return t, C.c_void_p(t.data_ptr())
-        n = np.empty(shp, np.uint8)
-        return n, n.ctypes.data_as(C.c_void_p)
-
     out = {}
     if target_euler is not None:
         if "success" in want:
-            out["success"], a.success = u8((B, T, joints))
+            out["success"], a.success = m.out((B, T, joints), np.uint8)
         if "srgr_sum" in want:
             out["srgr_sum"], a.srgr_sum = m.out((B,))
     if "vel" in want:
         out["vel"], a.vel = m.out((B, 6, V))
     if "beat_mask" in want:
-        out["beat_mask"], a.beat_mask = u8((B, 6, V))
+        out["beat_mask"], a.beat_mask = m.out((B, 6, V), np.uint8)
     if onset_times is not None and "align" in want:
         out["align"], a.align = m.out((B,))
     m.ready()
     if n_frames is None:
-        rc, name = lib.ls_beat_metrics(device, C.byref(a)), "ls_beat_metrics"
+        _lib.call("ls_beat_metrics", device, C.byref(a))
     elif frames is None:
-        rc, name = lib.ls_beat_metrics_timeline(device, n_frames, C.byref(a)), "ls_beat_metrics_timeline"
+        _lib.call("ls_beat_metrics_timeline", device, n_frames, C.byref(a))
     else:
-        rc = lib.ls_beat_metrics_timeline_ragged(device, n_frames, frames.ctypes.data_as(C.c_void_p), C.byref(a))
-        name = "ls_beat_metrics_timeline_ragged"
-    if rc != 0:
-        raise _lib.EngineError(f"{name} failed ({rc})")
+        _lib.call("ls_beat_metrics_timeline_ragged", device, n_frames, frames.ctypes.data_as(C.c_void_p), C.byref(a))
     return out
 
 
 def l1div_sum(rows, device=0) -> float:
     """``ls_beat_ldiv``: sum of |x - column mean| over rows [N, D] (numpy or a CUDA tensor), which are only read."""
-    lib = _lib.load_library()
     m = _lib._Marshal(device, rows)
     n, d = int(rows.shape[0]), int(rows.shape[1])
     total = C.c_double()
     px = m.f32(rows, (n, d))
     m.ready()
-    rc = lib.ls_beat_ldiv(device, int(m.on_device), n, d, px, C.byref(total))
-    if rc != 0:
-        raise _lib.EngineError(f"ls_beat_ldiv failed ({rc})")
+    _lib.call("ls_beat_ldiv", device, int(m.on_device), n, d, px, C.byref(total))
     return float(total.value)
 
 

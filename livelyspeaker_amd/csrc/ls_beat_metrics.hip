@@ -7,8 +7,8 @@
 // that only per-clip scalars leave the GPU); the L1 diversity takes three small launches over row blocks.  Every sum is a fixed tree
 // (per-thread stride order, wave butterfly, four wave partials added in order), so a clip's numbers do not depend on the batch size.
 #include "ls_hip.h"
-#include "ls_host.h"
 #include "ls_internal.h"
+#include "ls_staging.h"
 
 namespace ls {
 namespace {
@@ -159,66 +159,31 @@ __global__ __launch_bounds__(256) void k_l1div_abs(const float* __restrict__ x, 
 
 extern "C" int ls_beat_metrics(int device, const ls_beat_metrics_args* a) {
     using namespace ls;
-    if (!a || !a->pred || a->batch < 1 || a->njoints < 1 || a->order < 1) return LS_EINVAL;
-    if (!a->target && (a->success || a->srgr_sum)) return LS_EINVAL;          // SRGR needs the target planes
-    if (a->align && (!a->onset_times || !a->onset_offsets)) return LS_EINVAL;
-    if (a->align_series < 0 || a->align_series >= kSeries) return LS_EINVAL;
-    const bool motion = a->vel || a->beat_mask || a->align;
-    for (int s = 0; s < kSeries; ++s)
-        if (motion && (a->series_joint[s] < 0 || a->series_joint[s] >= a->njoints)) return LS_EINVAL;
-    const int B = a->batch;
-    long long n_onsets = 0;
-    if (a->align) {                                                            // offsets are host data in both modes
-        if (a->onset_offsets[0] != 0) return LS_EINVAL;
-        for (int b = 0; b < B; ++b)
-            if (a->onset_offsets[b + 1] <= a->onset_offsets[b]) return LS_EINVAL;     // a clip without an onset has no score (0 / 0)
-        n_onsets = a->onset_offsets[B];
-        if (!(a->sigma > 0.f) || !(a->fps > 0.f)) return LS_EINVAL;
-    }
+    bool motion;
+    long long n_onsets;
+    if (!beat_metrics_args_ok(a, &motion, &n_onsets)) return LS_EINVAL;       // any order >= 1: the kernel clamps at the clip's ends
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;
+    const int B = a->batch;
     const size_t n_eu = (size_t)B * kT * a->njoints * 3, n_tj = (size_t)B * kT * a->njoints, n_v = (size_t)B * kSeries * kV;
     BeatMetricsParams p{};
     p.J = a->njoints; p.order = a->order; p.align_series = a->align_series;
     for (int s = 0; s < kSeries; ++s) p.joint[s] = motion ? a->series_joint[s] : 0;
     p.threshold = a->threshold; p.scale = a->scale; p.sigma = a->sigma; p.fps = a->fps;
-    DevBuf t_pred, t_tar, t_sem, t_on, t_off, t_succ, t_sum, t_vel, t_mask, t_al;      // device temporaries, freed on return
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-    auto up = [&](DevBuf& buf, const void* src, size_t bytes) -> void* {       // host array -> device temporary
-        chk(buf.ensure(bytes));
-        if (e == hipSuccess) chk(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice));
-        return buf.p;
-    };
-    if (a->align) p.onset_offsets = static_cast<const long long*>(up(t_off, a->onset_offsets, (size_t)(B + 1) * sizeof(int64_t)));
-    if (a->on_device) {
-        p.pred = a->pred; p.target = a->target; p.semantic = a->target ? a->semantic : nullptr;
-        p.onset_times = a->align ? a->onset_times : nullptr;
-        p.success = a->success; p.srgr_sum = a->srgr_sum; p.vel = a->vel; p.beat_mask = a->beat_mask; p.align = a->align;
-    } else {
-        p.pred = static_cast<const float*>(up(t_pred, a->pred, n_eu * 4));
-        if (a->target) p.target = static_cast<const float*>(up(t_tar, a->target, n_eu * 4));
-        if (a->target && a->semantic) p.semantic = static_cast<const float*>(up(t_sem, a->semantic, (size_t)B * kT * 4));
-        if (a->align) p.onset_times = static_cast<const float*>(up(t_on, a->onset_times, (size_t)n_onsets * 4));
-        if (a->success) { chk(t_succ.ensure(n_tj)); p.success = static_cast<unsigned char*>(t_succ.p); }
-        if (a->srgr_sum) { chk(t_sum.ensure((size_t)B * 4)); p.srgr_sum = t_sum.f(); }
-        if (a->vel) { chk(t_vel.ensure(n_v * 4)); p.vel = t_vel.f(); }
-        if (a->beat_mask) { chk(t_mask.ensure(n_v)); p.beat_mask = static_cast<unsigned char*>(t_mask.p); }
-        if (a->align) { chk(t_al.ensure((size_t)B * 4)); p.align = t_al.f(); }
+    Staging st(a->on_device != 0);
+    if (a->align) {
+        p.onset_offsets = reinterpret_cast<const long long*>(st.upload(a->onset_offsets, (size_t)B + 1));       // host data in both modes
+        p.onset_times = st.in(a->onset_times, (size_t)n_onsets);
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_beat_metrics, dim3(B), dim3(256), 0, 0, p);
-        chk(hipGetLastError());
-        chk(hipDeviceSynchronize());
-    }
-    if (!a->on_device) {
-        auto down = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess && dst) chk(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); };
-        down(a->success, p.success, n_tj);
-        down(a->srgr_sum, p.srgr_sum, (size_t)B * 4);
-        down(a->vel, p.vel, n_v * 4);
-        down(a->beat_mask, p.beat_mask, n_v);
-        down(a->align, p.align, (size_t)B * 4);
-    }
-    return e == hipSuccess ? LS_OK : LS_EHIP;
+    p.pred = st.in(a->pred, n_eu);
+    p.target = st.in(a->target, n_eu);
+    p.semantic = a->target ? st.in(a->semantic, (size_t)B * kT) : nullptr;
+    p.success = st.out(a->success, n_tj);
+    p.srgr_sum = st.out(a->srgr_sum, (size_t)B);
+    p.vel = st.out(a->vel, n_v);
+    p.beat_mask = st.out(a->beat_mask, n_v);
+    p.align = st.out(a->align, (size_t)B);
+    if (st.e == hipSuccess) hipLaunchKernelGGL(k_beat_metrics, dim3(B), dim3(256), 0, 0, p);
+    return st.finish();
 }
 
 extern "C" int ls_beat_ldiv(int device, int on_device, int64_t rows, int dim, const float* x, double* sum_out) {
@@ -227,30 +192,21 @@ extern "C" int ls_beat_ldiv(int device, int on_device, int64_t rows, int dim, co
     const long long n_blocks = (rows + kL1Rows - 1) / kL1Rows;
     if (n_blocks > 0x7fffffffLL) return LS_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;
-    DevBuf t_x, t_col, t_mean, t_part;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t v) { if (e == hipSuccess) e = v; };
-    const float* d_x = x;
-    if (!on_device) {
-        chk(t_x.ensure((size_t)rows * dim * 4));
-        if (e == hipSuccess) chk(hipMemcpy(t_x.p, x, (size_t)rows * dim * 4, hipMemcpyHostToDevice));
-        d_x = t_x.f();
-    }
-    chk(t_col.ensure((size_t)n_blocks * dim * sizeof(double)));
-    chk(t_mean.ensure((size_t)dim * 4));
-    chk(t_part.ensure((size_t)n_blocks * sizeof(double)));
+    Staging st(on_device != 0);
+    const float* d_x = st.in(x, (size_t)rows * dim);
+    double* colsum = static_cast<double*>(st.temp((size_t)n_blocks * dim * sizeof(double)));
+    float* mean = static_cast<float*>(st.temp((size_t)dim * 4));
+    double* d_part = static_cast<double*>(st.temp((size_t)n_blocks * sizeof(double)));
     std::vector<double> partial((size_t)n_blocks);
-    if (e == hipSuccess) {
+    if (st.e == hipSuccess) {
         const unsigned cb = (unsigned)((dim + 255) / 256);
-        double* colsum = static_cast<double*>(t_col.p);
         hipLaunchKernelGGL(k_l1div_colsum, dim3((unsigned)n_blocks, cb), dim3(256), 0, 0, d_x, (long long)rows, dim, colsum);
-        hipLaunchKernelGGL(k_l1div_mean, dim3(cb), dim3(256), 0, 0, colsum, n_blocks, (long long)rows, dim, t_mean.f());
-        hipLaunchKernelGGL(k_l1div_abs, dim3((unsigned)n_blocks), dim3(256), 0, 0, d_x, t_mean.f(), (long long)rows, dim,
-                           static_cast<double*>(t_part.p));
-        chk(hipGetLastError());
-        chk(hipMemcpy(partial.data(), t_part.p, (size_t)n_blocks * sizeof(double), hipMemcpyDeviceToHost));
+        hipLaunchKernelGGL(k_l1div_mean, dim3(cb), dim3(256), 0, 0, colsum, n_blocks, (long long)rows, dim, mean);
+        hipLaunchKernelGGL(k_l1div_abs, dim3((unsigned)n_blocks), dim3(256), 0, 0, d_x, mean, (long long)rows, dim, d_part);
+        st.chk(hipGetLastError());
+        st.chk(hipMemcpy(partial.data(), d_part, (size_t)n_blocks * sizeof(double), hipMemcpyDeviceToHost));      // the one wait
     }
-    if (e != hipSuccess) return LS_EHIP;
+    if (st.e != hipSuccess) return LS_EHIP;
     double s = 0.0;
     for (double v : partial) s += v;        // block order, float64
     *sum_out = s;

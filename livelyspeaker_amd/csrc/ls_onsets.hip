@@ -12,8 +12,8 @@
 // clip's own L_b / F_b; only the addresses use the strides L and F.  What lies beyond a clip is never read; its outputs are set by a
 // memset ahead of the launch (0, and 0xFF bytes for the -1 of the onset slabs).
 #include "ls_hip.h"
-#include "ls_host.h"
 #include "ls_onsets.h"
+#include "ls_staging.h"
 
 namespace ls {
 namespace {
@@ -373,18 +373,10 @@ int onsets(int device, const ls_onsets_args* a, const int32_t* lengths, bool rag
     if ((n_bf + kWavesPerBlock - 1) / kWavesPerBlock > 0x7fffffffull) return LS_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;
 
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-    DevBuf t_in, t_win, t_tw, t_ptr, t_col, t_w, t_db, t_rms, t_env, t_cnt, t_raw, t_bt, t_btr, t_len, t_off;      // device temporaries, freed on return
-    auto up = [&](DevBuf& buf, const void* src, size_t bytes) -> void* {
-        chk(buf.ensure(bytes ? bytes : 4));        // a filterbank may be empty (fmax below the first bin)
-        if (e == hipSuccess && bytes) chk(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice));
-        return buf.p;
-    };
-    auto tmp = [&](DevBuf& buf, size_t bytes) -> void* { chk(buf.ensure(bytes)); return buf.p; };
+    Staging st(a->on_device != 0);
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     if (a->kernel_ms)
-        for (auto& v : ev) chk(hipEventCreate(&v));
+        for (auto& v : ev) st.chk(hipEventCreate(&v));
 
     SpectrumParams sp{};
     PickParams pp{};
@@ -396,78 +388,61 @@ int onsets(int device, const ls_onsets_args* a, const int32_t* lengths, bool rag
     pp.post_avg = pp.pre_avg + 1;
     pp.wait = pp.pre_max;
     if (given) {
-        pp.envelope = a->on_device ? a->envelope : static_cast<const float*>(up(t_in, a->envelope, n_bf * 4));
+        pp.envelope = st.in(a->envelope, n_bf);
     } else {
         const OnsetTables tab = make_onset_tables(a->sr, kNfft, kMels, 0.0, a->fmax);
         sp.B = B; sp.L = L; sp.F = F; sp.pad_mode = a->pad_mode;
-        sp.audio = a->on_device ? a->audio : static_cast<const float*>(up(t_in, a->audio, (size_t)B * L * 4));
-        sp.window = static_cast<const float*>(up(t_win, tab.window.data(), tab.window.size() * 4));
-        sp.twiddle = static_cast<const float2*>(up(t_tw, tab.twiddle.data(), tab.twiddle.size() * 4));
-        sp.mel_ptr = static_cast<const int*>(up(t_ptr, tab.mel_ptr.data(), tab.mel_ptr.size() * 4));
-        sp.mel_col = static_cast<const int*>(up(t_col, tab.mel_col.data(), tab.mel_col.size() * 4));
-        sp.mel_w = static_cast<const float*>(up(t_w, tab.mel_w.data(), tab.mel_w.size() * 4));
-        sp.mel_db = (a->on_device && a->mel_db) ? a->mel_db : static_cast<float*>(tmp(t_db, n_bf * kMels * 4));
-        const bool want_rms = a->rms || a->onset_bt_rms;
-        sp.rms = !want_rms ? nullptr : (a->on_device && a->rms) ? a->rms : static_cast<float*>(tmp(t_rms, n_bf * 4));
+        sp.audio = st.in(a->audio, (size_t)B * L);
+        sp.window = st.upload(tab.window.data(), tab.window.size());
+        sp.twiddle = reinterpret_cast<const float2*>(st.upload(tab.twiddle.data(), tab.twiddle.size()));
+        sp.mel_ptr = st.upload(tab.mel_ptr.data(), tab.mel_ptr.size());
+        sp.mel_col = st.upload(tab.mel_col.data(), tab.mel_col.size());      // a filterbank may be empty (fmax below the first bin)
+        sp.mel_w = st.upload(tab.mel_w.data(), tab.mel_w.size());
+        sp.mel_db = st.out(a->mel_db, n_bf * kMels, /*needed=*/true);         // the pick reads it
+        sp.rms = st.out(a->rms, n_bf, /*needed=*/a->onset_bt_rms != nullptr);
         pp.mel_db = sp.mel_db;
         pp.rms = a->onset_bt_rms ? sp.rms : nullptr;
     }
-    if (a->on_device) {
-        pp.oenv = a->oenv; pp.count = a->count; pp.onset_raw = a->onset_raw; pp.onset_bt = a->onset_bt; pp.onset_bt_rms = a->onset_bt_rms;
-    } else {
-        if (a->oenv) pp.oenv = static_cast<float*>(tmp(t_env, n_bf * 4));
-        if (a->count) pp.count = static_cast<int*>(tmp(t_cnt, (size_t)B * 4));
-        if (a->onset_raw) pp.onset_raw = static_cast<int*>(tmp(t_raw, n_bf * 4));
-        if (a->onset_bt) pp.onset_bt = static_cast<int*>(tmp(t_bt, n_bf * 4));
-        if (a->onset_bt_rms) pp.onset_bt_rms = static_cast<int*>(tmp(t_btr, n_bf * 4));
-    }
+    pp.oenv = st.out(a->oenv, n_bf);
+    pp.count = st.out(a->count, (size_t)B);
+    pp.onset_raw = st.out(a->onset_raw, n_bf);
+    pp.onset_bt = st.out(a->onset_bt, n_bf);
+    pp.onset_bt_rms = st.out(a->onset_bt_rms, n_bf);
     if (ragged) {                                    // the lengths are host data in both modes; the padding values go in ahead of the launch
-        pp.frame_off = sp.frame_off = static_cast<const int*>(up(t_off, frame_off.data(), frame_off.size() * 4));
-        if (!given) sp.lens = static_cast<const int*>(up(t_len, lengths, (size_t)B * 4));
-        auto fill = [&](void* d, int byte, size_t bytes) { if (d && e == hipSuccess) chk(hipMemset(d, byte, bytes)); };
-        if (a->mel_db) fill(sp.mel_db, 0, n_bf * kMels * 4);
-        if (a->rms) fill(sp.rms, 0, n_bf * 4);
-        fill(pp.oenv, 0, n_bf * 4);
-        fill(pp.onset_raw, 0xFF, n_bf * 4);
-        fill(pp.onset_bt, 0xFF, n_bf * 4);
-        fill(pp.onset_bt_rms, 0xFF, n_bf * 4);
+        pp.frame_off = sp.frame_off = st.upload(frame_off.data(), frame_off.size());
+        if (!given) sp.lens = st.upload(lengths, (size_t)B);
+        if (a->mel_db) st.fill(sp.mel_db, 0, n_bf * kMels * 4);
+        if (a->rms) st.fill(sp.rms, 0, n_bf * 4);
+        st.fill(pp.oenv, 0, n_bf * 4);
+        st.fill(pp.onset_raw, 0xFF, n_bf * 4);
+        st.fill(pp.onset_bt, 0xFF, n_bf * 4);
+        st.fill(pp.onset_bt_rms, 0xFF, n_bf * 4);
     }
-    if (e == hipSuccess) {
+    if (st.e == hipSuccess) {
         if (!given) {
             const long long waves = ragged ? (long long)frame_off[B] : (long long)n_bf;
             const long long blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
-            if (ev[0]) chk(hipEventRecord(ev[0], 0));
+            if (ev[0]) st.chk(hipEventRecord(ev[0], 0));
             if (ragged) hipLaunchKernelGGL(k_onset_spectrum<true>, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, 0, sp);
             else hipLaunchKernelGGL(k_onset_spectrum<false>, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, 0, sp);
-            if (ev[1]) chk(hipEventRecord(ev[1], 0));
+            if (ev[1]) st.chk(hipEventRecord(ev[1], 0));
         }
         if (want_pick) {
-            if (ev[2]) chk(hipEventRecord(ev[2], 0));
+            if (ev[2]) st.chk(hipEventRecord(ev[2], 0));
             if (ragged) hipLaunchKernelGGL(k_onset_pick<true>, dim3(B), dim3(256), 0, 0, pp);
             else hipLaunchKernelGGL(k_onset_pick<false>, dim3(B), dim3(256), 0, 0, pp);
-            if (ev[3]) chk(hipEventRecord(ev[3], 0));
+            if (ev[3]) st.chk(hipEventRecord(ev[3], 0));
         }
-        chk(hipGetLastError());
-        chk(hipDeviceSynchronize());
+        st.sync();
     }
-    if (a->kernel_ms) {
+    if (a->kernel_ms) {                              // events destroyed, then the copy-backs
         a->kernel_ms[0] = a->kernel_ms[1] = 0.0f;
-        if (e == hipSuccess && !given) chk(hipEventElapsedTime(&a->kernel_ms[0], ev[0], ev[1]));
-        if (e == hipSuccess && want_pick) chk(hipEventElapsedTime(&a->kernel_ms[1], ev[2], ev[3]));
+        if (st.e == hipSuccess && !given) st.chk(hipEventElapsedTime(&a->kernel_ms[0], ev[0], ev[1]));
+        if (st.e == hipSuccess && want_pick) st.chk(hipEventElapsedTime(&a->kernel_ms[1], ev[2], ev[3]));
         for (auto& v : ev)
             if (v) (void)hipEventDestroy(v);
     }
-    if (!a->on_device) {
-        auto down = [&](void* dst, const void* src, size_t bytes) { if (e == hipSuccess && dst) chk(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); };
-        down(a->mel_db, sp.mel_db, n_bf * kMels * 4);
-        down(a->rms, sp.rms, n_bf * 4);
-        down(a->oenv, pp.oenv, n_bf * 4);
-        down(a->count, pp.count, (size_t)B * 4);
-        down(a->onset_raw, pp.onset_raw, n_bf * 4);
-        down(a->onset_bt, pp.onset_bt, n_bf * 4);
-        down(a->onset_bt_rms, pp.onset_bt_rms, n_bf * 4);
-    }
-    return e == hipSuccess ? LS_OK : LS_EHIP;
+    return st.copy_back();
 }
 
 }  // namespace

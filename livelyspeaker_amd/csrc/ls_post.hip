@@ -5,9 +5,9 @@
 // Tiny and latency-bound (918 floats per clip); it exists so the sampled tensor never has to leave the GPU in the
 // reference's [B,J,F,T] layout just to be transposed and scanned on the host.
 #include "ls_hip.h"
-#include "ls_host.h"
 #include "ls_internal.h"
 #include "ls_post_frame.h"
+#include "ls_staging.h"
 
 namespace ls {
 
@@ -58,44 +58,18 @@ __global__ __launch_bounds__(64) void k_ted_post(const float* __restrict__ sampl
 extern "C" int ls_ted_post(int device, int on_device, int batch, const ls_post_config* c, const float* sample,
                            float* aligned, float* pose, float* angle_diff, unsigned char* beat_mask) {
     using namespace ls;
-    if (!c || !sample || batch < 1) return LS_EINVAL;
-    if (c->njoints < 1 || c->njoints > kMaxBones || c->n_pairs < 0 || c->n_pairs > kMaxPairs || c->n_pose_joints > kMaxBones + 1)
-        return LS_EINVAL;
+    PostParams p;
+    if (!sample || batch < 1 || !post_params(c, &p)) return LS_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;
-    PostParams p{};
-    p.njoints = c->njoints; p.n_pairs = c->n_pairs; p.thres = c->thres; p.n_pose_joints = c->n_pose_joints;
-    for (int k = 0; k < c->n_pairs; ++k) { p.pair_a[k] = c->pair_a[k]; p.pair_b[k] = c->pair_b[k]; p.change_angle[k] = c->change_angle[k]; }
-    for (int j = 0; j < c->njoints; ++j) { p.bone_parent[j] = c->bone_parent[j]; p.bone_child[j] = c->bone_child[j]; p.bone_len[j] = c->bone_len[j]; }
-    for (int j = 0; j < c->njoints * 3; ++j) p.mean_dir_vec[j] = c->mean_dir_vec[j];
-    const int JF = c->njoints * 3;
-    const size_t n_in = (size_t)batch * JF * kT, n_pose = (size_t)batch * kT * c->n_pose_joints * 3, n_t = (size_t)batch * kT;
-    float *d_in = nullptr, *d_al = nullptr, *d_pose = nullptr, *d_diff = nullptr;
-    unsigned char* d_mask = nullptr;
-    DevBuf t_in, t_al, t_pose, t_diff, t_mask;      // the host path's device temporaries, freed on return
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-    if (on_device) {
-        d_in = const_cast<float*>(sample); d_al = aligned; d_pose = pose; d_diff = angle_diff; d_mask = beat_mask;
-    } else {
-        chk(t_in.ensure(n_in * 4)); d_in = t_in.f();
-        if (aligned) { chk(t_al.ensure(n_in * 4)); d_al = t_al.f(); }
-        if (pose) { chk(t_pose.ensure(n_pose * 4)); d_pose = t_pose.f(); }
-        if (angle_diff) { chk(t_diff.ensure(n_t * 4)); d_diff = t_diff.f(); }
-        if (beat_mask) { chk(t_mask.ensure(n_t)); d_mask = static_cast<unsigned char*>(t_mask.p); }
-        if (e == hipSuccess) chk(hipMemcpy(d_in, sample, n_in * 4, hipMemcpyHostToDevice));
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_ted_post, dim3(batch), dim3(64), 0, 0, d_in, p, d_al, d_pose, d_diff, d_mask);
-        chk(hipGetLastError());
-        chk(hipDeviceSynchronize());
-    }
-    if (!on_device) {
-        if (e == hipSuccess && aligned) chk(hipMemcpy(aligned, d_al, n_in * 4, hipMemcpyDeviceToHost));
-        if (e == hipSuccess && pose) chk(hipMemcpy(pose, d_pose, n_pose * 4, hipMemcpyDeviceToHost));
-        if (e == hipSuccess && angle_diff) chk(hipMemcpy(angle_diff, d_diff, n_t * 4, hipMemcpyDeviceToHost));
-        if (e == hipSuccess && beat_mask) chk(hipMemcpy(beat_mask, d_mask, n_t, hipMemcpyDeviceToHost));
-    }
-    return e == hipSuccess ? LS_OK : LS_EHIP;
+    const size_t n_in = (size_t)batch * p.njoints * 3 * kT, n_t = (size_t)batch * kT;
+    Staging st(on_device != 0);
+    const float* d_in = st.in(sample, n_in);
+    float* d_al = st.out(aligned, n_in);
+    float* d_pose = st.out(pose, n_t * p.n_pose_joints * 3);
+    float* d_diff = st.out(angle_diff, n_t);
+    unsigned char* d_mask = st.out(beat_mask, n_t);
+    if (st.e == hipSuccess) hipLaunchKernelGGL(k_ted_post, dim3(batch), dim3(64), 0, 0, d_in, p, d_al, d_pose, d_diff, d_mask);
+    return st.finish();
 }
 
 // ---- BEAT: rot6d -> rotation matrix -> Euler XYZ (degrees), plus the [B,J,6,T] -> [B,T,J*6] layout change --------------------
@@ -126,27 +100,12 @@ extern "C" int ls_beat_post(int device, int on_device, int batch, int njoints, c
     using namespace ls;
     if (!sample || batch < 1 || njoints < 1) return LS_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;
-    const size_t n_in = (size_t)batch * njoints * 6 * kT, n_eu = (size_t)batch * kT * njoints * 3, total = (size_t)batch * kT * njoints;
-    float *d_in = nullptr, *d_dec = nullptr, *d_eu = nullptr;
-    DevBuf t_in, t_dec, t_eu;      // the host path's device temporaries, freed on return
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-    if (on_device) {
-        d_in = const_cast<float*>(sample); d_dec = decoded; d_eu = euler_deg;
-    } else {
-        chk(t_in.ensure(n_in * 4)); d_in = t_in.f();
-        if (decoded) { chk(t_dec.ensure(n_in * 4)); d_dec = t_dec.f(); }
-        if (euler_deg) { chk(t_eu.ensure(n_eu * 4)); d_eu = t_eu.f(); }
-        if (e == hipSuccess) chk(hipMemcpy(d_in, sample, n_in * 4, hipMemcpyHostToDevice));
-    }
-    if (e == hipSuccess) {
+    const size_t n_in = (size_t)batch * njoints * 6 * kT, total = (size_t)batch * kT * njoints;
+    Staging st(on_device != 0);
+    const float* d_in = st.in(sample, n_in);
+    float* d_dec = st.out(decoded, n_in);
+    float* d_eu = st.out(euler_deg, total * 3);
+    if (st.e == hipSuccess)
         hipLaunchKernelGGL(k_beat_post, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, d_in, d_dec, d_eu, njoints, total);
-        chk(hipGetLastError());
-        chk(hipDeviceSynchronize());
-    }
-    if (!on_device) {
-        if (e == hipSuccess && decoded) chk(hipMemcpy(decoded, d_dec, n_in * 4, hipMemcpyDeviceToHost));
-        if (e == hipSuccess && euler_deg) chk(hipMemcpy(euler_deg, d_eu, n_eu * 4, hipMemcpyDeviceToHost));
-    }
-    return e == hipSuccess ? LS_OK : LS_EHIP;
+    return st.finish();
 }

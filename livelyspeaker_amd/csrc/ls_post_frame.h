@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ls_hip.h"
+
 namespace ls {
 
 constexpr int kMaxBones = 16, kMaxPairs = 8;
@@ -19,6 +21,24 @@ struct PostParams {
     float bone_len[kMaxBones];
     float mean_dir_vec[kMaxBones * 3];
 };
+
+// host: the one check and copy of a caller's configuration (ls_ted_post and the timeline entries).  false, and LS_EINVAL from the
+// entry, for what would index outside a frame: the bone tree indexes ted_pose_frame's kMaxBones + 1 joints, a pair the frame's bones
+inline bool post_params(const ls_post_config* c, PostParams* p) {
+    if (!c || c->njoints < 1 || c->njoints > kMaxBones || c->n_pairs < 0 || c->n_pairs > kMaxPairs || c->n_pose_joints < 0 ||
+        c->n_pose_joints > kMaxBones + 1)
+        return false;
+    for (int j = 0; j < c->njoints; ++j)
+        if (c->bone_parent[j] < 0 || c->bone_parent[j] > kMaxBones || c->bone_child[j] < 0 || c->bone_child[j] > kMaxBones) return false;
+    for (int k = 0; k < c->n_pairs; ++k)
+        if (c->pair_a[k] < 0 || c->pair_a[k] >= c->njoints || c->pair_b[k] < 0 || c->pair_b[k] >= c->njoints) return false;
+    *p = PostParams{};
+    p->njoints = c->njoints; p->n_pairs = c->n_pairs; p->thres = c->thres; p->n_pose_joints = c->n_pose_joints;
+    for (int k = 0; k < c->n_pairs; ++k) { p->pair_a[k] = c->pair_a[k]; p->pair_b[k] = c->pair_b[k]; p->change_angle[k] = c->change_angle[k]; }
+    for (int j = 0; j < c->njoints; ++j) { p->bone_parent[j] = c->bone_parent[j]; p->bone_child[j] = c->bone_child[j]; p->bone_len[j] = c->bone_len[j]; }
+    for (int j = 0; j < c->njoints * 3; ++j) p->mean_dir_vec[j] = c->mean_dir_vec[j];
+    return true;
+}
 
 // F.normalize(dim=-1) of one bone: x / max(||x||, 1e-12); in: the un-normalised vector, out: the unit vector
 __device__ __forceinline__ void ted_unit(const float* in, float* out) {

@@ -18,11 +18,9 @@
 // same bodies instantiated with kRagged: a 1-D grid over the (clip, first frame) table of ls_ragged_tiles, so work follows the valid
 // frames, and every clamp, halo and beat range uses the clip's own N_b; only the addresses use the stride.  What lies beyond a clip's
 // valid range is never read and is zeroed by a memset ahead of the launch.
-#include <deque>
-
 #include "ls_hip.h"
-#include "ls_host.h"
 #include "ls_post_frame.h"
+#include "ls_staging.h"
 
 namespace ls {
 namespace {
@@ -329,50 +327,6 @@ __global__ __launch_bounds__(256) void k_ted_align(const TedAlignParams p) {
 
 namespace {
 
-// host <-> device staging of one call: with on_device the caller's pointers pass through (an output the kernels need although the
-// caller left it out becomes a temporary); otherwise inputs are uploaded and outputs come back in finish().  Temporaries are freed
-// with the object.
-struct Staging {
-    const bool on_device;
-    hipError_t e = hipSuccess;
-    std::deque<DevBuf> bufs;
-    struct Down { void* dst; const void* src; size_t bytes; };
-    std::vector<Down> downs;
-    explicit Staging(bool dev) : on_device(dev) {}
-    void chk(hipError_t x) { if (e == hipSuccess) e = x; }
-    void* temp(size_t bytes) {
-        bufs.emplace_back();
-        chk(bufs.back().ensure(bytes ? bytes : 1));
-        return bufs.back().p;
-    }
-    template <class T>
-    const T* upload(const T* src, size_t count) {
-        void* d = temp(count * sizeof(T));
-        if (e == hipSuccess) chk(hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice));
-        return static_cast<const T*>(d);
-    }
-    template <class T>
-    const T* in(const T* src, size_t count) { return !src || on_device ? src : upload(src, count); }
-    template <class T>
-    T* out(T* dst, size_t count, bool needed = false) {
-        if (on_device) return dst || !needed ? dst : static_cast<T*>(temp(count * sizeof(T)));
-        if (!dst && !needed) return nullptr;
-        T* d = static_cast<T*>(temp(count * sizeof(T)));
-        if (dst) downs.push_back({dst, d, count * sizeof(T)});
-        return d;
-    }
-    void zero(void* d, size_t bytes) {             // the padding value of a ragged call's output, ahead of the launch
-        if (d && bytes && e == hipSuccess) chk(hipMemset(d, 0, bytes));
-    }
-    int finish() {
-        chk(hipGetLastError());
-        chk(hipDeviceSynchronize());
-        for (const Down& d : downs)
-            if (e == hipSuccess) chk(hipMemcpy(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost));
-        return e == hipSuccess ? LS_OK : LS_EHIP;
-    }
-};
-
 inline unsigned tiles_of(int n_frames) { return (unsigned)((n_frames + kTile - 1) / kTile); }
 
 // the launch plan of a ragged call: frames[b] in [least, stride] is checked by the caller; the table is ls_ragged_tiles's
@@ -405,22 +359,11 @@ inline bool frames_within(int batch, const int32_t* frames, long long least, int
 
 int ted_post_timeline(int device, int on_device, int batch, int n_frames, const int32_t* frames, bool ragged, const ls_post_config* c,
                       const float* timeline, float* aligned, float* pose, float* angle_diff, unsigned char* beat_mask) {
-    if (!c || !timeline || batch < 1 || n_frames < 4 || n_frames > kMaxN) return LS_EINVAL;
-    if (c->njoints < 1 || c->njoints > kMaxBones || c->n_pairs < 0 || c->n_pairs > kMaxPairs || c->n_pose_joints < 0 ||
-        c->n_pose_joints > kMaxBones + 1)
-        return LS_EINVAL;
-    for (int j = 0; j < c->njoints; ++j)          // the bone tree indexes a frame's joints
-        if (c->bone_parent[j] < 0 || c->bone_parent[j] > kMaxBones || c->bone_child[j] < 0 || c->bone_child[j] > kMaxBones) return LS_EINVAL;
-    for (int k = 0; k < c->n_pairs; ++k)
-        if (c->pair_a[k] < 0 || c->pair_a[k] >= c->njoints || c->pair_b[k] < 0 || c->pair_b[k] >= c->njoints) return LS_EINVAL;
+    PostParams p;
+    if (!timeline || batch < 1 || n_frames < 4 || n_frames > kMaxN || !post_params(c, &p)) return LS_EINVAL;
     TilePlan plan;
     if (ragged && (!frames_within(batch, frames, 4, n_frames) || !plan.build(batch, frames))) return LS_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;
-    PostParams p{};
-    p.njoints = c->njoints; p.n_pairs = c->n_pairs; p.thres = c->thres; p.n_pose_joints = c->n_pose_joints;
-    for (int k = 0; k < c->n_pairs; ++k) { p.pair_a[k] = c->pair_a[k]; p.pair_b[k] = c->pair_b[k]; p.change_angle[k] = c->change_angle[k]; }
-    for (int j = 0; j < c->njoints; ++j) { p.bone_parent[j] = c->bone_parent[j]; p.bone_child[j] = c->bone_child[j]; p.bone_len[j] = c->bone_len[j]; }
-    for (int j = 0; j < c->njoints * 3; ++j) p.mean_dir_vec[j] = c->mean_dir_vec[j];
     const size_t n_in = (size_t)batch * c->njoints * 3 * n_frames, n_t = (size_t)batch * n_frames;
     Staging st(on_device != 0);
     const float* d_in = st.in(timeline, n_in);
@@ -430,10 +373,10 @@ int ted_post_timeline(int device, int on_device, int batch, int n_frames, const 
     unsigned char* d_mask = st.out(beat_mask, n_t);
     if (ragged) {
         plan.upload(st, batch);
-        st.zero(d_al, n_in * 4);
-        st.zero(d_pose, n_t * c->n_pose_joints * 3 * 4);
-        st.zero(d_diff, n_t * 4);
-        st.zero(d_mask, n_t);
+        st.fill(d_al, 0, n_in * 4);
+        st.fill(d_pose, 0, n_t * c->n_pose_joints * 3 * 4);
+        st.fill(d_diff, 0, n_t * 4);
+        st.fill(d_mask, 0, n_t);
         if (st.e == hipSuccess)
             hipLaunchKernelGGL(k_ted_timeline<true>, dim3(plan.tiles()), dim3(256), 0, 0, d_in, p, n_frames, plan.dev, d_al, d_pose, d_diff, d_mask);
     } else if (st.e == hipSuccess) {
@@ -458,8 +401,8 @@ int beat_post_timeline(int device, int on_device, int batch, int njoints, int n_
     float* d_eu = st.out(euler_deg, n_in / 2);
     if (ragged) {
         plan.upload(st, batch);
-        st.zero(d_dec, n_in * 4);
-        st.zero(d_eu, n_in / 2 * 4);
+        st.fill(d_dec, 0, n_in * 4);
+        st.fill(d_eu, 0, n_in / 2 * 4);
         if (st.e == hipSuccess)
             hipLaunchKernelGGL(k_beat_post_timeline<true>, dim3(plan.tiles(), chunks), dim3(256), 0, 0, d_in, d_dec, d_eu, njoints, n_frames, plan.dev);
     } else if (st.e == hipSuccess) {
@@ -470,23 +413,11 @@ int beat_post_timeline(int device, int on_device, int batch, int njoints, int n_
 }
 
 int beat_metrics_timeline(int device, int n_frames, const int32_t* frames, bool ragged, const ls_beat_metrics_args* a) {
-    if (!a || !a->pred || a->batch < 1 || a->njoints < 1 || a->order < 1) return LS_EINVAL;
+    bool motion;
+    long long n_onsets;
+    if (!beat_metrics_args_ok(a, &motion, &n_onsets)) return LS_EINVAL;
     if (n_frames > kMaxN || (long long)n_frames < 2LL * a->order + 2) return LS_EINVAL;
-    if (!a->target && (a->success || a->srgr_sum)) return LS_EINVAL;          // SRGR needs the target planes
-    if (a->align && (!a->onset_times || !a->onset_offsets)) return LS_EINVAL;
-    if (a->align_series < 0 || a->align_series >= kSeries) return LS_EINVAL;
-    const bool motion = a->vel || a->beat_mask || a->align;
-    for (int s = 0; s < kSeries; ++s)
-        if (motion && (a->series_joint[s] < 0 || a->series_joint[s] >= a->njoints)) return LS_EINVAL;
     const int B = a->batch, N = n_frames, V = N - 1;
-    long long n_onsets = 0;
-    if (a->align) {                                                            // offsets are host data in both modes
-        if (a->onset_offsets[0] != 0) return LS_EINVAL;
-        for (int b = 0; b < B; ++b)
-            if (a->onset_offsets[b + 1] <= a->onset_offsets[b]) return LS_EINVAL;     // a clip without an onset has no score (0 / 0)
-        n_onsets = a->onset_offsets[B];
-        if (!(a->sigma > 0.f) || !(a->fps > 0.f)) return LS_EINVAL;
-    }
     if (B > 65535) return LS_EINVAL;                                           // grid dimension y
     TilePlan plan;
     if (ragged && (!frames_within(B, frames, 2LL * a->order + 2, N) || !plan.build(B, frames))) return LS_EINVAL;
@@ -513,9 +444,9 @@ int beat_metrics_timeline(int device, int n_frames, const int32_t* frames, bool 
     if (ragged) {
         plan.upload(st, B);
         p.rp = plan.dev;
-        st.zero(p.success, n_tj);
-        st.zero(p.vel, n_v * 4);
-        st.zero(p.beat_mask, n_v);
+        st.fill(p.success, 0, n_tj);
+        st.fill(p.vel, 0, n_v * 4);
+        st.fill(p.beat_mask, 0, n_v);
         if (st.e == hipSuccess && frame_pass) hipLaunchKernelGGL(k_beat_metrics_timeline<true>, dim3(plan.tiles()), dim3(256), 0, 0, p);
         if (st.e == hipSuccess && reduce) hipLaunchKernelGGL(k_beat_reduce_timeline<true>, dim3(B), dim3(256), 0, 0, p);
     } else {

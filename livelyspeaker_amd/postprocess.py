@@ -37,30 +37,29 @@ def ted_post_config() -> "_lib.LsPostConfig":
     return c
 
 
+def _ted_result(m, B, aligned, pose, diff, mask) -> dict:
+    """What both TED wrappers return: the mask as bool, the beats as seconds (t / 15)."""
+    mask_np = mask.cpu().numpy() if m.on_device else mask
+    beats = [[float(t) / TED_FPS for t in np.nonzero(mask_np[b])[0]] for b in range(B)]
+    return {"aligned_motions": aligned, "pose": pose, "angle_diff": diff,
+            "beat_mask": mask.bool() if m.on_device else mask.astype(bool), "motion_beat_times": beats}
+
+
 def ted_postprocess(sample, device: int = 0, want_pose: bool = True) -> dict:
     """sample: [B, 9, 3, 34] (numpy, CPU tensor or CUDA tensor as returned by the sampler).
     Returns aligned_motions [B,34,27], pose [B,34,10,3], angle_diff [B,34], beat_mask [B,34] (bool) and
     motion_beat_times (list of lists of seconds, t/15 as in test_RAG_ted.py:111)."""
-    lib = _lib.load_library()
     m = _lib._Marshal(device, sample)
     B = int(sample.shape[0])
     cfg = ted_post_config()
     aligned, p_al = m.out((B, 34, 27))
     pose, p_pose = m.out((B, 34, 10, 3)) if want_pose else (None, None)
     diff, p_diff = m.out((B, 34))
-    if m.on_device:
-        mask = m.torch.empty((B, 34), dtype=m.torch.uint8, device=m.dev)
-        p_mask = C.c_void_p(mask.data_ptr())
-    else:
-        mask = np.empty((B, 34), np.uint8)
-        p_mask = mask.ctypes.data_as(C.c_void_p)
-    rc = lib.ls_ted_post(device, int(m.on_device), B, C.byref(cfg), m.f32(sample, (B, 9, 3, 34)), p_al, p_pose, p_diff, p_mask)
-    if rc != 0:
-        raise _lib.EngineError(f"ls_ted_post failed ({rc})")
-    mask_np = mask.cpu().numpy() if m.on_device else mask
-    beats = [[float(t) / TED_FPS for t in np.nonzero(mask_np[b])[0]] for b in range(B)]
-    return {"aligned_motions": aligned, "pose": pose, "angle_diff": diff,
-            "beat_mask": mask.bool() if m.on_device else mask.astype(bool), "motion_beat_times": beats}
+    mask, p_mask = m.out((B, 34), np.uint8)
+    p_in = m.f32(sample, (B, 9, 3, 34))
+    m.ready()
+    _lib.call("ls_ted_post", device, int(m.on_device), B, C.byref(cfg), p_in, p_al, p_pose, p_diff, p_mask)
+    return _ted_result(m, B, aligned, pose, diff, mask)
 
 
 def beat_postprocess(sample, device: int = 0, want_euler: bool = True) -> dict:
@@ -69,29 +68,20 @@ def beat_postprocess(sample, device: int = 0, want_euler: bool = True) -> dict:
     consume) and pred_euler [B, 34, 141]: Euler XYZ angles in degrees of every joint (rot_utils.matrix_to_euler_angles(
     rot_utils.rotation_6d_to_matrix(.), "XYZ") / pi * 180).  ``beat_metrics`` scores these planes (SRGR, motion beats, BeatAlign, L1
     diversity); audio onsets stay with the caller."""
-    lib = _lib.load_library()
     m = _lib._Marshal(device, sample)
     B, J = int(sample.shape[0]), int(sample.shape[1])
     if tuple(sample.shape[2:]) != (6, 34):
         raise ValueError(f"expected [B, J, 6, 34], got {tuple(sample.shape)}")
     dec, p_dec = m.out((B, 34, J * 6))
     eul, p_eul = m.out((B, 34, J * 3)) if want_euler else (None, None)
-    rc = lib.ls_beat_post(device, int(m.on_device), B, J, m.f32(sample, (B, J, 6, 34)), p_dec, p_eul)
-    if rc != 0:
-        raise _lib.EngineError(f"ls_beat_post failed ({rc})")
+    p_in = m.f32(sample, (B, J, 6, 34))
+    m.ready()
+    _lib.call("ls_beat_post", device, int(m.on_device), B, J, p_in, p_dec, p_eul)
     return {"decoded_motions": dec, "pred_euler": eul}
 
 
 TIMELINE_TILE = 64            # frames per workgroup of the timeline kernels (LS_TIMELINE_TILE); no result depends on it
 TIMELINE_MAX_FRAMES = 4096    # LS_TIMELINE_MAX_FRAMES
-
-
-def _bytes_out(m, shape):
-    if m.on_device:
-        t = m.torch.empty(tuple(shape), dtype=m.torch.uint8, device=m.dev)
-        return t, C.c_void_p(t.data_ptr())
-    n = np.empty(tuple(shape), np.uint8)
-    return n, n.ctypes.data_as(C.c_void_p)
 
 
 def _timeline_frames(timeline, feats, least):
@@ -114,7 +104,6 @@ def ted_postprocess_timeline(timeline, device: int = 0, want_pose: bool = True, 
     ``frames`` (a host sequence [B], each in [4, N]): clips of different lengths in one call (``ls_ted_post_timeline_ragged``); N is
     then the row stride.  On clip b's first ``frames[b]`` frames every output is bit for bit that of the clip alone at its own length
     (beats at t in [2, frames[b] - 2]); beyond them the outputs are 0 and the input is never read."""
-    lib = _lib.load_library()
     N = _timeline_frames(timeline, 3, 4)
     m = _lib._Marshal(device, timeline)
     B = int(timeline.shape[0])
@@ -123,28 +112,21 @@ def ted_postprocess_timeline(timeline, device: int = 0, want_pose: bool = True, 
     aligned, p_al = m.out((B, N, 27))
     pose, p_pose = m.out((B, N, 10, 3)) if want_pose else (None, None)
     diff, p_diff = m.out((B, N))
-    mask, p_mask = _bytes_out(m, (B, N))
+    mask, p_mask = m.out((B, N), np.uint8)
     p_in = m.f32(timeline, (B, 9, 3, N))
     m.ready()
     if fr is None:
-        rc, name = lib.ls_ted_post_timeline(device, int(m.on_device), B, N, C.byref(cfg), p_in, p_al, p_pose, p_diff, p_mask), "ls_ted_post_timeline"
+        _lib.call("ls_ted_post_timeline", device, int(m.on_device), B, N, C.byref(cfg), p_in, p_al, p_pose, p_diff, p_mask)
     else:
-        rc = lib.ls_ted_post_timeline_ragged(device, int(m.on_device), B, N, fr.ctypes.data_as(C.c_void_p), C.byref(cfg), p_in, p_al, p_pose,
-                                             p_diff, p_mask)
-        name = "ls_ted_post_timeline_ragged"
-    if rc != 0:
-        raise _lib.EngineError(f"{name} failed ({rc})")
-    mask_np = mask.cpu().numpy() if m.on_device else mask
-    beats = [[float(t) / TED_FPS for t in np.nonzero(mask_np[b])[0]] for b in range(B)]
-    return {"aligned_motions": aligned, "pose": pose, "angle_diff": diff,
-            "beat_mask": mask.bool() if m.on_device else mask.astype(bool), "motion_beat_times": beats}
+        _lib.call("ls_ted_post_timeline_ragged", device, int(m.on_device), B, N, fr.ctypes.data_as(C.c_void_p), C.byref(cfg), p_in, p_al,
+                  p_pose, p_diff, p_mask)
+    return _ted_result(m, B, aligned, pose, diff, mask)
 
 
 def beat_postprocess_timeline(timeline, device: int = 0, want_euler: bool = True, frames=None) -> dict:
     """``beat_postprocess`` on a stitched timeline [B, J, 6, N], N in [2, 4096] (``ls_beat_post_timeline``): decoded_motions
     [B, N, J*6] and pred_euler [B, N, J*3] in degrees, which ``beat_metrics.beat_metrics_timeline`` scores.  ``frames`` (a host
     sequence [B], each in [2, N]): the clips' valid frames (``ls_beat_post_timeline_ragged``); the outputs are 0 beyond them."""
-    lib = _lib.load_library()
     N = _timeline_frames(timeline, 6, 2)
     m = _lib._Marshal(device, timeline)
     B, J = int(timeline.shape[0]), int(timeline.shape[1])
@@ -154,12 +136,9 @@ def beat_postprocess_timeline(timeline, device: int = 0, want_euler: bool = True
     p_in = m.f32(timeline, (B, J, 6, N))
     m.ready()
     if fr is None:
-        rc, name = lib.ls_beat_post_timeline(device, int(m.on_device), B, J, N, p_in, p_dec, p_eul), "ls_beat_post_timeline"
+        _lib.call("ls_beat_post_timeline", device, int(m.on_device), B, J, N, p_in, p_dec, p_eul)
     else:
-        rc = lib.ls_beat_post_timeline_ragged(device, int(m.on_device), B, J, N, fr.ctypes.data_as(C.c_void_p), p_in, p_dec, p_eul)
-        name = "ls_beat_post_timeline_ragged"
-    if rc != 0:
-        raise _lib.EngineError(f"{name} failed ({rc})")
+        _lib.call("ls_beat_post_timeline_ragged", device, int(m.on_device), B, J, N, fr.ctypes.data_as(C.c_void_p), p_in, p_dec, p_eul)
     return {"decoded_motions": dec, "pred_euler": eul}
 
 
@@ -167,7 +146,6 @@ def ted_beat_align(beat_mask, onset_frames, onset_count, sigma=TED_BEAT_SIGMA, f
     """``ls_ted_beat_align``: per clip, the beat-consistency sum and the number of motion beats.  beat_mask [B, N] (bool or bytes),
     onset_frames [B, F] int32 and onset_count [B] int32 as ``audio_onsets`` returns them (numpy, or CUDA tensors: then nothing but
     the results' host copies leaves the device).  Returns (align_sum [B] float64, n_beats [B] int32) as host arrays."""
-    lib = _lib.load_library()
     if len(beat_mask.shape) != 2 or len(onset_frames.shape) != 2:
         raise ValueError(f"expected beat_mask [B, N] and onset_frames [B, F], got {list(beat_mask.shape)} and {list(onset_frames.shape)}")
     B, N, F = int(beat_mask.shape[0]), int(beat_mask.shape[1]), int(onset_frames.shape[1])
@@ -177,24 +155,11 @@ def ted_beat_align(beat_mask, onset_frames, onset_count, sigma=TED_BEAT_SIGMA, f
     a = _lib.LsTedAlignArgs()
     a.batch, a.n_frames, a.on_device, a.onset_cols, a.hop = B, N, int(m.on_device), F, int(hop)
     a.fps, a.sigma, a.sr = float(fps), float(sigma), float(sr)
-    a.beat_mask = m.u8(beat_mask, (B, N))
-    if m.on_device:
-        th = m.torch
-        fr = th.as_tensor(onset_frames).to(device=m.dev, dtype=th.int32).contiguous()
-        cn = th.as_tensor(onset_count).to(device=m.dev, dtype=th.int32).contiguous()
-        total = th.empty((B,), dtype=th.float64, device=m.dev)
-        beats = th.empty((B,), dtype=th.int32, device=m.dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())        # noqa: E731
-    else:
-        host = lambda v: v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)        # noqa: E731
-        fr, cn = np.ascontiguousarray(host(onset_frames), np.int32), np.ascontiguousarray(host(onset_count), np.int32)
-        total, beats = np.empty(B, np.float64), np.empty(B, np.int32)
-        ptr = lambda n: n.ctypes.data_as(C.c_void_p)    # noqa: E731
-    a.onset_frames, a.onset_count, a.align_sum, a.n_beats = ptr(fr), ptr(cn), ptr(total), ptr(beats)
+    a.beat_mask, a.onset_frames, a.onset_count = m.u8(beat_mask, (B, N)), m.i32(onset_frames), m.i32(onset_count)
+    total, a.align_sum = m.out((B,), np.float64)
+    beats, a.n_beats = m.out((B,), np.int32)
     m.ready()
-    rc = lib.ls_ted_beat_align(device, C.byref(a))
-    if rc != 0:
-        raise _lib.EngineError(f"ls_ted_beat_align failed ({rc})")
+    _lib.call("ls_ted_beat_align", device, C.byref(a))
     if m.on_device:
         return total.cpu().numpy(), beats.cpu().numpy()
     return total, beats

@@ -142,6 +142,51 @@ def test_invalid_arguments_are_refused_without_a_launch():
         assert ali() == -1, c
 
 
+def _config(**fields):
+    c = pp.ted_post_config()
+    for k, v in fields.items():
+        if isinstance(v, tuple):
+            getattr(c, k)[v[0]] = v[1]
+        else:
+            setattr(c, k, v)
+    return c
+
+
+BAD_CONFIGS = {"bone_child[0]=17": dict(bone_child=(0, 17)), "bone_parent[0]=-1": dict(bone_parent=(0, -1)), "pair_a[0]=9": dict(pair_a=(0, 9)),
+               "pair_b[0]=-1": dict(pair_b=(0, -1)), "n_pose_joints=-1": dict(n_pose_joints=-1), "n_pose_joints=18": dict(n_pose_joints=18),
+               "njoints=0": dict(njoints=0), "njoints=17": dict(njoints=17), "n_pairs=9": dict(n_pairs=9)}
+
+
+def test_both_ted_post_entries_refuse_the_same_configurations():
+    """One check (post_params) serves ls_ted_post and ls_ted_post_timeline: a bone or pair index outside a frame is LS_EINVAL (-1) in
+    front of hipSetDevice, not an out-of-bounds access on the device.  Without a GPU, reaching hipSetDevice gives LS_EHIP (-3)."""
+    lib = _lib.load_library()
+    x = np.zeros(2 * 47 * 6 * 34, np.float32)
+    out = np.zeros(2 * 34 * 47 * 6, np.float32)
+    px, po = x.ctypes.data, out.ctypes.data
+    ref = lambda c: ctypes.byref(c) if c is not None else None  # noqa: E731
+    ted = lambda c, B=1, src=px: lib.ls_ted_post(0, 0, B, ref(c), src, po, None, None, None)  # noqa: E731
+    tl = lambda c, B=1, src=px: lib.ls_ted_post_timeline(0, 0, B, 34, ref(c), src, po, None, None, None)  # noqa: E731
+    for name, fields in BAD_CONFIGS.items():
+        assert ted(_config(**fields)) == -1 and tl(_config(**fields)) == -1, name
+    good = pp.ted_post_config()
+    for entry in (ted, tl):
+        assert entry(None) == -1 and entry(good, src=None) == -1 and entry(good, B=0) == -1
+    beat = lambda B=1, J=47, src=px: lib.ls_beat_post(0, 0, B, J, src, po, None)  # noqa: E731
+    assert beat(src=None) == -1 and beat(B=0) == -1 and beat(J=0) == -1
+
+
+def test_marshal_out_makes_every_output_dtype_on_the_host():
+    m = _lib._Marshal(0, np.zeros(3, np.float32))
+    assert not m.on_device
+    arr, ptr = m.out((2, 3))
+    assert arr.dtype == np.float32 and arr.shape == (2, 3)
+    for dtype in (np.float32, np.uint8, np.int32, np.float64):
+        arr, ptr = m.out((2, 5, 3), dtype)
+        assert isinstance(arr, np.ndarray) and arr.dtype == dtype and arr.shape == (2, 5, 3) and arr.flags.c_contiguous
+        assert ptr.value == arr.ctypes.data
+
+
 def test_python_wrappers_refuse_other_shapes():
     with pytest.raises(ValueError, match="timeline"):
         pp.ted_postprocess_timeline(np.zeros((1, 9, 6, 40), np.float32))
