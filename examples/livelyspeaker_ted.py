@@ -10,7 +10,7 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py [batch]
     python examples/livelyspeaker_ted.py [batch] --from-motion
     python examples/livelyspeaker_ted.py [batch] --long-seconds N
-    python examples/livelyspeaker_ted.py --long-seconds A,B,...
+    python examples/livelyspeaker_ted.py --long-seconds A,B,... [--drop-finished]
     python examples/livelyspeaker_ted.py [batch] --clip-text
 --clip-text starts from TOKENS instead of a stand-in feature: synthetic clip.tokenize output -> CLIPTextEncoder (the text tower of CLIP
 on the GPU, synthetic weights) -> text features -> SAG decoder -> the same refinement, with no host wait between the two engines.
@@ -22,7 +22,9 @@ the window's text feature as its init_image, and stitched into one timeline, whi
 motion beats and the beat-consistency score against the speech it was generated from (up to 131 s: the onset detector's 4096 frames).
 --long-seconds A,B,... (a comma list) is a RAGGED batch: one speech per entry, each of its own duration, synthesised and scored in one
 call each (sample_long(audio_lengths=) -> (timeline, frames) -> score_timeline(frames=, audio_lengths=)); it prints every clip's
-frames and beats and the batch's beat-consistency score.
+frames and beats and the batch's beat-consistency score.  With --drop-finished a speech leaves the batch once its own audio has ended
+(sample_long(drop_finished=True)): window w runs only the speeches that still have audio, and the line printed first says how many
+clip-windows that saves.
 With real data: load RAG.pt / SAG.pth / the auto-encoder checkpoint with load_model_wo_clip / load_state_dict and build `cond`
 exactly as the reference script does; everything below the weight loading is unchanged.
 """
@@ -151,8 +153,13 @@ def main():
         i = sys.argv.index("--long-seconds")
         arg = sys.argv[i + 1]
         del sys.argv[i:i + 2]
+        drop = "--drop-finished" in sys.argv
+        if drop:
+            sys.argv.remove("--drop-finished")
         if "," in arg:
-            return main_long_ragged([float(v) for v in arg.split(",") if v], noise_source)
+            return main_long_ragged([float(v) for v in arg.split(",") if v], noise_source, drop)
+        if drop:
+            raise SystemExit("--drop-finished goes with a comma list of durations: equally long speeches finish together")
         seconds = float(arg)
         return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source)
     if "--clip-text" in sys.argv:
@@ -269,7 +276,7 @@ def main_long(B, seconds, noise_source):
     assert tuple(scored["pose"].shape) == (B, n_frames, 10, 3) and bool(torch.isfinite(scored["pose"]).all())
 
 
-def main_long_ragged(seconds, noise_source):
+def main_long_ragged(seconds, noise_source, drop_finished=False):
     """One speech per entry of `seconds`, each of its own length, through one sample_long call and one score_timeline call."""
     import numpy as np
     from livelyspeaker_amd import long_form
@@ -285,10 +292,14 @@ def main_long_ragged(seconds, noise_source):
     text = torch.from_numpy(synth.make_text_features(B * W).reshape(B, W, 512)).cuda()
     torch.manual_seed(233)
     timeline, frames = long_form.sample_long(diffusion, model, audio, y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim",
-                                             skip_timesteps=80, sag=sag_decoder, text_features=text, audio_lengths=lengths)
+                                             skip_timesteps=80, sag=sag_decoder, text_features=text, audio_lengths=lengths,
+                                             drop_finished=drop_finished)
     assert frames.tolist() == [f for _, f in plans] and bool(torch.isfinite(timeline).all())
     scored = long_form.score_timeline(timeline, audio, frames=frames, audio_lengths=lengths)
     print(f"B={B} ({noise_source}): {W} chained windows for the longest speech, timeline {tuple(timeline.shape)}")
+    if drop_finished:
+        active = long_form.plan_drop(lengths, cfg)[2]
+        print(f"  finished speeches dropped: clips per window {active.tolist()}, {int(active.sum())} clip-windows sampled instead of {B * W}")
     for b in range(B):
         print(f"  clip {b}: {seconds[b]:g} s of speech -> {plans[b][0]} windows, {int(frames[b])} frames, "
               f"{len(scored['motion_beat_times'][b])} motion beats")

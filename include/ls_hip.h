@@ -327,6 +327,33 @@ typedef struct ls_long_cond {
 } ls_long_cond;
 int ls_long_prepare(ls_handle* h, const ls_long_cond* c);
 
+/* ---- Clips of different lengths in one long-form call: a clip's windows stop when its audio has ended.
+ * Clip b of audio_lengths[b] samples runs W_b = max(1, ceil((audio_lengths[b] - audio_len) / audio_stride) + 1) windows.  The clips
+ * are held in SLOTS, stably sorted by W_b, longest first (ties keep the caller's order), so the B_w clips with W_b > w that run window w
+ * are slots [0, B_w) of every per-clip buffer, and window w is a sampling call at batch B_w: its own step plan, its own single-pass
+ * decision (the scales of its clips), its own captured loop.  ls_long_plan_drop is that plan (no handle, no GPU): slot_row [batch] =
+ * the caller's clip behind each slot, slot_windows [batch] = its W_b, active[w] = B_w for w < min(W_max, active_capacity) (B_0 = batch),
+ * *n_windows = W_max.  slot_row, slot_windows and active may be NULL (active: with active_capacity 0).
+ *
+ * ls_long_prepare_ragged takes c->audio [B, L] (L = c->audio_samples), c->seed_poses and audio_lengths (host, [B], each in [1, L]) in
+ * the CALLER's clip order -- it reads them through the slot table -- and c->vid_indices [B], c->scale [B] and c->emo [W_max, B] in
+ * SLOT order (row s = clip slot_row[s]); c->n_windows must be W_max.  Samples at and beyond audio_lengths[b] are never read and count
+ * as zero.  Only the sum of B_w clip-windows that exist go through the WavEncoder.  ls_long_sample then runs window w at batch B_w:
+ *   - text_features [W_max, B, latent_dim] is in slot order too; entries of (w, slot) pairs that do not run are not read;
+ *   - TAPE: the tapes are packed, window after window: x_init [sum B_w, J, F, T], then per window eps [n_exec, 2, B_w, latent_dim] and
+ *     noise [n_exec, B_w, J, F, T], each concatenated over the windows -- the draws of one sampling call per window at batch B_w;
+ *   - PHILOX: slot s of window w draws the streams of global sample index sample_offset + s + (w << 48): the streams follow the
+ *     slot, so a batch that is already longest-first gets the draws of the equal-length call;
+ *   - timeline and windows are in the caller's order and zeroed first: clip b's timeline is 0 from frame T + (W_b - 1)(T - n_pre_seq)
+ *     on, its raw windows w >= W_b are 0;
+ *   - ls_timing: n_segments = W_max, n_step_launches = W_max * n_exec, graph_replayed = the windows served by a replay.  A window batch
+ *     that serves two or more windows is captured once (the handle caches a few graphs); one that serves a single window runs as
+ *     stream launches, which give the same bits.
+ * Device-resident length arrays are not built. */
+int ls_long_plan_drop(int32_t batch, int32_t audio_len, const int64_t* audio_lengths, int32_t* slot_row, int32_t* slot_windows,
+                      int32_t* active, int32_t active_capacity, int32_t* n_windows);
+int ls_long_prepare_ragged(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths);
+
 struct ls_sag;
 typedef struct ls_long_sample_args {
     int32_t sampler;            /* LS_SAMPLER_DDPM | LS_SAMPLER_DDIM                                                  */

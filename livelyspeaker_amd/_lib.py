@@ -157,7 +157,7 @@ class LsEvalConfig(C.Structure):
 
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
-           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_sample", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
+           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
@@ -228,6 +228,8 @@ def load_library(build_if_missing: bool = True):
     lib.ls_sample.argtypes = [C.c_void_p, C.POINTER(LsSampleArgs)]
     lib.ls_long_prepare.argtypes = [C.c_void_p, C.POINTER(LsLongCond)]
     lib.ls_long_sample.argtypes = [C.c_void_p, C.POINTER(LsLongSampleArgs)]
+    lib.ls_long_prepare_ragged.argtypes = [C.c_void_p, C.POINTER(LsLongCond), C.c_void_p]
+    lib.ls_long_plan_drop.argtypes = [C.c_int32, C.c_int32, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_int32, c_i32p]
     lib.ls_forward.argtypes = [C.c_void_p, C.POINTER(LsForwardArgs)]
     lib.ls_step.argtypes = [C.c_void_p, C.POINTER(LsStepArgs)]
     lib.ls_plms_step.argtypes = [C.c_void_p, C.POINTER(LsPlmsStepArgs)]
@@ -450,6 +452,21 @@ def plan_query(batch, dataset="ted", single_pass=False, precision="fp32", n_cus=
     if rc != 0:
         raise EngineError(f"ls_plan_query failed ({rc})")
     return [(out[1 + 3 * i], out[2 + 3 * i], out[3 + 3 * i]) for i in range(out[0])], float(ms.value)
+
+
+def long_plan_drop(audio_lengths, audio_len):
+    """ls_long_plan_drop (no GPU needed): (slot -> clip int32 [B], windows per slot int32 [B], active clips per window int32 [W_max])."""
+    lib = load_library()
+    lens = np.ascontiguousarray(np.asarray(audio_lengths).reshape(-1), dtype=np.int64)
+    B = int(lens.size)
+    row, wins, nw = np.empty(B, np.int32), np.empty(B, np.int32), C.c_int32()
+    ptr = lambda a: a.ctypes.data_as(c_i32p)      # noqa: E731
+    if B < 1 or lib.ls_long_plan_drop(B, int(audio_len), lens.ctypes.data_as(C.c_void_p), ptr(row), ptr(wins), None, 0, C.byref(nw)) != 0:
+        raise ValueError(f"audio_lengths must hold at least one length, each >= 1: got {lens.tolist()}")
+    active = np.empty(int(nw.value), np.int32)
+    if lib.ls_long_plan_drop(B, int(audio_len), lens.ctypes.data_as(C.c_void_p), None, None, ptr(active), int(nw.value), C.byref(nw)) != 0:
+        raise EngineError("ls_long_plan_drop failed")
+    return row, wins, active
 
 
 def plan_coop_slices(groups, dataset="ted", n_cus=256):
@@ -742,17 +759,29 @@ class Engine(_Handle):
         return (out, dumps) if dump_steps else out
 
     # ---- long-form synthesis ---------------------------------------------------------------------
-    def long_prepare(self, audio, seed_poses, vid_indices, scale, emo=None, n_windows=1, encoder_chunk=None):
+    def long_prepare(self, audio, seed_poses, vid_indices, scale, emo=None, n_windows=1, encoder_chunk=None, audio_lengths=None):
         """Once-per-call stage of a long-form call (ls_long_prepare): ``audio`` [B, L] is encoded once for all ``n_windows`` windows
         (zero-padded at the end when short), ``seed_poses`` [B, J, F, n_pre_seq] condition window 0, ``emo`` [W, B] (BEAT).  Replaces
-        whatever ``prepare`` left resident."""
+        whatever ``prepare`` left resident.
+
+        ``audio_lengths`` (host [B]): ls_long_prepare_ragged -- every clip runs only the windows its own length needs
+        (``long_plan_drop``); ``audio``, ``seed_poses`` and ``audio_lengths`` are in the caller's clip order, ``vid_indices``, ``scale``
+        and ``emo`` in slot order, ``n_windows`` is the longest clip's count.  ``long_sample`` then takes packed tapes and slot-ordered
+        ``text_features`` (include/ls_hip.h)."""
         B, W = int(audio.shape[0]), int(n_windows)
         npre = int(self.cfg.n_pre_seq)
         m = _Marshal(self.device, audio, seed_poses, vid_indices, scale, emo, stream=self._stream)
         c = LsLongCond(B, W, int(m.on_device), int(encoder_chunk or 0), int(audio.shape[1]), m.f32(audio, (B, int(audio.shape[1]))),
                        m.f32(seed_poses, (B, self.J, self.F, npre)), m.i64(vid_indices, (B,)), m.i64(emo, (W, B)), m.f32(scale, (B,)))
         m.ready()
-        self._check(self.lib.ls_long_prepare(self.h, C.byref(c)), "ls_long_prepare")
+        if audio_lengths is None:
+            self._check(self.lib.ls_long_prepare(self.h, C.byref(c)), "ls_long_prepare")
+            self.window_batches = None
+        else:
+            lens = np.ascontiguousarray(np.asarray(audio_lengths).reshape(-1), dtype=np.int64)
+            assert lens.shape == (B,), (lens.shape, B)
+            self._check(self.lib.ls_long_prepare_ragged(self.h, C.byref(c), lens.ctypes.data_as(C.c_void_p)), "ls_long_prepare_ragged")
+            self.window_batches = [int(n) for n in long_plan_drop(lens, self.cfg.audio_len)[2]]
         self.batch, self.n_windows = B, W
 
     def long_sample(self, sampler=LS_SAMPLER_DDIM, x_init=None, eps_tape=None, noise_tape=None, skip_timesteps=0, eta=0.0,
@@ -763,6 +792,8 @@ class Engine(_Handle):
         decode of (origin_x_w, ``text_features`` [W, B, D]) starts every window.  Returns the timeline [B, J, F, T + (W-1)(T-n_pre)]
         (and the raw windows [W, B, J, F, T])."""
         B, W, D = self.batch, self.n_windows, self.D
+        bw = getattr(self, "window_batches", None)      # a ragged call: packed tapes, window after window at its own batch
+        total = sum(bw) if bw else W * B
         members = [x_init, eps_tape, noise_tape, text_features]
         if device_out:
             import torch
@@ -774,9 +805,10 @@ class Engine(_Handle):
         a.clip_denoised, a.two_pass_always, a.eta = int(bool(clip_denoised)), int(bool(two_pass_always)), float(eta)
         if philox_seed is None:
             a.noise_mode = LS_NOISE_TAPE
-            a.x_init = m.f32(x_init, (W,) + self._xshape())
-            a.eps_tape = m.f32(eps_tape, (W, n_exec, 2, B, D))
-            a.noise_tape = m.f32(noise_tape, (W, n_exec) + self._xshape())
+            per_x = self.J * self.F * self.T
+            a.x_init = m.f32(x_init, (total,) + self._xshape()[1:] if bw else (W,) + self._xshape())
+            a.eps_tape = m.f32(eps_tape, (total * n_exec * 2 * D,) if bw else (W, n_exec, 2, B, D))
+            a.noise_tape = m.f32(noise_tape, (total * n_exec * per_x,) if bw else (W, n_exec) + self._xshape())
         else:
             a.noise_mode = LS_NOISE_PHILOX
             a.seed, a.sample_offset = int(philox_seed), int(sample_offset)

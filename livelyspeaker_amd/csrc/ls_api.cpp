@@ -5,6 +5,7 @@
 #include "ls_handle.h"
 #include "ls_weights.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -122,7 +123,7 @@ void ls::resolve_prepare_timing(ls_handle* h, bool block) {
 
 // guidance scale 1 for the whole batch (what the reference's callers run: test_RAG_ted.py:183): out_u + 1 * (out_c - out_u) is out_c,
 // so the sampling loop may skip the uncond pass (ls_sample_args.two_pass_always keeps both).  `scale`: the caller's [B] (host unless od)
-int ls::prepare_scale(ls_handle* h, const float* scale, int B, int od) {
+int ls::prepare_scale(ls_handle* h, const float* scale, int B, int od, int* leading_ones) {
     hipStream_t st = h->stream;
     std::vector<float> sc((size_t)B);
     if (od) {           // read back the ingested copy on the handle's own stream: ordered behind the caller's stream (ls_stream_order)
@@ -133,6 +134,7 @@ int ls::prepare_scale(ls_handle* h, const float* scale, int B, int od) {
     }
     h->all_scale_one = true;
     for (float v : sc) if (v != 1.0f) { h->all_scale_one = false; break; }
+    if (leading_ones) { int n = 0; while (n < B && sc[(size_t)n] == 1.0f) ++n; *leading_ones = n; }
     return LS_OK;
 }
 
@@ -188,9 +190,13 @@ int ls::prepare_style(ls_handle* h, int B) {
 
 // the step plan of a batch of B clips and the workspaces of its kernel families (every one held by address in a captured loop)
 int ls::prepare_plan(ls_handle* h, int B) {
+    { const int keepB = h->B; h->B = B; decide_path(h); h->B = keepB; }
+    return plan_workspaces(h);
+}
+
+int ls::plan_workspaces(ls_handle* h) {
     hipStream_t st = h->stream;
     int rc;
-    { const int keepB = h->B; h->B = B; decide_path(h); h->B = keepB; }
     if (seg_n(h, 2) > 0) {      // exchange workspaces of the sample-split kernel: one launch's worth of (sample, pass) groups
         const int nco = seg_n(h, 2);
         int gcap = h->coop_groups_max;                  // the most groups any slicing keeps resident (LS_COOP_GROUPS caps all of them in -DLS_DEBUG builds)
@@ -497,7 +503,7 @@ int ls_long_prepare(ls_handle* h, const ls_long_cond* c) {
     const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipStream_t st = h->stream;
     int rc;
-    h->prepared = h->lg_prepared = false;
+    h->prepared = h->lg_prepared = h->lg_ragged = false;
     h->seg_next = -1;
     HIPCHK(h, hipEventRecord(h->ev[4], st));
     HIPCHK(h, h->lg_audio.ensure((size_t)B * L * sizeof(float)));
@@ -548,6 +554,138 @@ int ls_long_prepare(ls_handle* h, const ls_long_cond* c) {
     h->B = B;
     h->lg_W = W; h->lg_L = L;
     h->lg_prepared = true;      // `prepared` stays false: the static projections exist per window, inside ls_long_sample only
+    return LS_OK;
+}
+
+// The plan of a ragged long-form call (ls_long_plan_drop): windows per clip from plan_windows' arithmetic (long_form.py), the clips
+// stably sorted by them, longest first, and per window the clips that run it.
+static void long_plan_drop(int B, int AL, const int64_t* lengths, std::vector<int>& row, std::vector<int>& wins, std::vector<int>& bw) {
+    std::vector<int> wb((size_t)B);
+    int wmax = 1;
+    for (int b = 0; b < B; ++b) {
+        const long long over = (long long)lengths[b] - AL;
+        wb[(size_t)b] = over <= 0 ? 1 : (int)((over + LS_LONG_AUDIO_STRIDE - 1) / LS_LONG_AUDIO_STRIDE) + 1;
+        if (wb[(size_t)b] > wmax) wmax = wb[(size_t)b];
+    }
+    row.resize((size_t)B); wins.resize((size_t)B);
+    for (int b = 0; b < B; ++b) row[(size_t)b] = b;
+    std::stable_sort(row.begin(), row.end(), [&](int x, int y) { return wb[(size_t)x] > wb[(size_t)y]; });      // descending; ties keep the caller's order
+    for (int s = 0; s < B; ++s) wins[(size_t)s] = wb[(size_t)row[(size_t)s]];
+    bw.assign((size_t)wmax, 0);                     // B_w = clips with W_b > w: count the clips that END at each w, then a running sum from the back
+    for (int b = 0; b < B; ++b) ++bw[(size_t)wb[(size_t)b] - 1];
+    for (int w = wmax - 2; w >= 0; --w) bw[(size_t)w] += bw[(size_t)w + 1];
+}
+
+int ls_long_plan_drop(int32_t batch, int32_t audio_len, const int64_t* audio_lengths, int32_t* slot_row, int32_t* slot_windows,
+                      int32_t* active, int32_t active_capacity, int32_t* n_windows) {
+    if (batch < 1 || audio_len < 1 || !audio_lengths || !n_windows || active_capacity < 0 || (active_capacity > 0 && !active)) return LS_EINVAL;
+    for (int b = 0; b < batch; ++b)
+        if (audio_lengths[b] < 1 || (audio_lengths[b] - audio_len) / LS_LONG_AUDIO_STRIDE > (1 << 20)) return LS_EINVAL;
+    std::vector<int> row, wins, bw;
+    long_plan_drop(batch, audio_len, audio_lengths, row, wins, bw);
+    for (int s = 0; s < batch; ++s) {
+        if (slot_row) slot_row[s] = row[(size_t)s];
+        if (slot_windows) slot_windows[s] = wins[(size_t)s];
+    }
+    for (int w = 0; w < (int)bw.size() && w < active_capacity; ++w) active[w] = bw[(size_t)w];
+    *n_windows = (int32_t)bw.size();
+    return LS_OK;
+}
+
+// ls_long_prepare for clips of different lengths (ls_hip.h): the encoder sees only the clip-windows that exist, gathered from the
+// caller's waveform by k_long_gather_clips and stored packed, window-major in slot order; every window batch is planned and every
+// workspace a captured loop holds by address is sized for all of them here, so that nothing moves once ls_long_sample has begun.
+// The speaker style is ls_long_sample's (per window batch).
+int ls_long_prepare_ragged(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths) {
+    if (!h || !c || !audio_lengths) return fail(h, LS_EINVAL, "ls_long_prepare_ragged: null argument");
+    if (!h->committed) return fail(h, LS_ESTATE, "ls_long_prepare_ragged before ls_commit_weights");
+    if (!h->fused) return fail(h, LS_EUNSUPPORTED, "long-form synthesis chains the reference's %d-frame windows", kT);
+    if (c->batch < 1 || c->n_windows < 1) return fail(h, LS_EINVAL, "batch and n_windows must be >= 1");
+    if (c->audio_samples < 1 || c->encoder_chunk < 0) return fail(h, LS_EINVAL, "ls_long_prepare_ragged: bad audio_samples / encoder_chunk");
+    if (!c->audio || !c->seed_poses || !c->vid_indices || !c->scale) return fail(h, LS_EINVAL, "ls_long_prepare_ragged: null conditioning pointer");
+    if (h->cfg.n_prefix_tokens == 2 && !c->emo) return fail(h, LS_EINVAL, "BEAT variant needs emo ids");
+    if (h->cfg.n_pre_seq < 1) return fail(h, LS_EINVAL, "long-form synthesis needs n_pre_seq >= 1 (the hand-off poses)");
+    if (c->audio_samples > 0x7fffffffLL) return fail(h, LS_EINVAL, "ls_long_prepare_ragged: audio_samples beyond 2^31 - 1");
+    const int B = c->batch, W = c->n_windows, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, od = c->on_device;
+    for (int b = 0; b < B; ++b)
+        if (audio_lengths[b] < 1 || audio_lengths[b] > c->audio_samples)
+            return fail(h, LS_EINVAL, "audio_lengths[%d] = %lld outside [1, %lld]", b, (long long)audio_lengths[b], (long long)c->audio_samples);
+    std::vector<int> row, wins, bw;
+    long_plan_drop(B, AL, audio_lengths, row, wins, bw);
+    if ((int)bw.size() != W) return fail(h, LS_EINVAL, "n_windows is %d, the longest clip needs %d", W, (int)bw.size());
+    std::vector<int> off((size_t)W + 1, 0);
+    for (int w = 0; w < W; ++w) off[(size_t)w + 1] = off[(size_t)w] + bw[(size_t)w];
+    const int total = off[(size_t)W];
+    std::vector<int> table((size_t)total * 2), lens((size_t)B);
+    for (int w = 0, p = 0; w < W; ++w)
+        for (int s = 0; s < bw[(size_t)w]; ++s, ++p) { table[(size_t)2 * p] = row[(size_t)s]; table[(size_t)2 * p + 1] = w; }
+    for (int b = 0; b < B; ++b) lens[(size_t)b] = (int)audio_lengths[b];          // <= audio_samples, checked; the kernel compares in 64 bits
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int chunk = c->encoder_chunk > 0 ? c->encoder_chunk : 256;
+    if (chunk > 32768) chunk = 32768;                   // one grid row per clip-window of a chunk
+    hipStream_t st = h->stream;
+    int rc;
+    h->prepared = h->lg_prepared = h->lg_ragged = false;
+    h->seg_next = -1;
+    HIPCHK(h, hipEventRecord(h->ev[4], st));
+    // a device-resident waveform is read in place (the call waits before it returns); a host one is uploaded as it is, unpadded
+    const float* audio = c->audio;
+    if (!od) {
+        if ((rc = ingest(h, h->lg_audio, c->audio, (size_t)B * (size_t)c->audio_samples * sizeof(float), 0)) != LS_OK) return rc;
+        audio = h->lg_audio.f();
+    }
+    if ((rc = ingest(h, h->lg_seed, c->seed_poses, (size_t)B * JF * h->cfg.n_pre_seq * sizeof(float), od)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->vid, c->vid_indices, (size_t)B * sizeof(int64_t), od)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->scale, c->scale, (size_t)B * sizeof(float), od)) != LS_OK) return rc;
+    if (c->emo && (rc = ingest(h, h->lg_emo_ids, c->emo, (size_t)W * B * sizeof(int64_t), od)) != LS_OK) return rc;
+    if ((rc = prepare_scale(h, c->scale, B, od, &h->lg_scale_ones)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->lg_row, row.data(), (size_t)B * sizeof(int), 0)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->lg_lens, lens.data(), (size_t)B * sizeof(int), 0)) != LS_OK) return rc;
+    if ((rc = upload(h, h->lg_table, table.data(), table.size() * sizeof(int))) != LS_OK) return rc;      // waits: host inputs and these temporaries are free again
+    // ---- WavEncoder over the packed clip-windows p = lg_off[w] + slot, `chunk` at a time
+    const int nmax = chunk < total ? chunk : total;
+    HIPCHK(h, h->lg_clips.ensure((size_t)nmax * AL * sizeof(float)));
+    HIPCHK(h, h->lg_featc.ensure((size_t)total * T * kAudioFeat * sizeof(float)));
+    HIPCHK(h, h->lg_featp.ensure((size_t)nmax * T * KPP * sizeof(float)));
+    HIPCHK(h, h->origin_x.ensure((size_t)B * JF * T * sizeof(float)));
+    HIPCHK(h, hipMemsetAsync(h->origin_x.p, 0, (size_t)B * JF * T * sizeof(float), st));
+    for (int p0 = 0; p0 < total; p0 += chunk) {
+        const int n = total - p0 < chunk ? total - p0 : chunk;
+        HIPCHK(h, launch_long_gather_clips(audio, static_cast<const int*>(h->lg_table.p) + (size_t)2 * p0, static_cast<const int*>(h->lg_lens.p), h->lg_clips.f(), n, AL,
+                                           (long long)c->audio_samples, LS_LONG_AUDIO_STRIDE, st));
+        if ((rc = run_wav_encoder(h, h->lg_clips.f(), n)) != LS_OK) return rc;
+        HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f() + (size_t)p0 * T * kAudioFeat, n, JF, KPP, 0, st, T));
+    }
+    // ---- per-batch stages: the buffers at the whole batch (window 0's), the emotion tokens of every window's active clips
+    HIPCHK(h, h->feat_u.ensure((size_t)B * T * KPP * sizeof(float)));
+    HIPCHK(h, hipMemsetAsync(h->feat_u.p, 0, (size_t)B * T * KPP * sizeof(float), st));
+    HIPCHK(h, h->static_c.ensure((size_t)B * T * kD * sizeof(float)));
+    HIPCHK(h, h->static_u.ensure((size_t)B * T * kD * sizeof(float)));
+    if (h->cfg.n_prefix_tokens == 2) {
+        HIPCHK(h, h->emo_tok.ensure((size_t)B * kD * sizeof(float)));
+        HIPCHK(h, h->lg_emotok.ensure((size_t)W * B * kD * sizeof(float)));
+        for (int w = 0; w < W; ++w)                     // ids of (window, slot) pairs that do not run are never read
+            HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->lg_emo_ids.p) + (size_t)w * B, h->lg_emotok.f() + (size_t)w * B * kD,
+                                         bw[(size_t)w], kD, h->cfg.n_emotions, st));
+    }
+    // every buffer a captured loop reads moves only when the batch changes (as in ls_prepare): drop the graphs then, keep them otherwise --
+    // their keys hold the batch and the plan, so the windows of this call find the graphs of the last one
+    if (h->B != B) free_graph(h);
+    // ---- the plan and the workspaces of every window batch, smallest first: the handle is left planned for the whole batch
+    for (int w = W - 1; w >= 0; --w) {
+        if (w + 1 < W && bw[(size_t)w] == bw[(size_t)w + 1]) continue;
+        h->all_scale_one = h->lg_scale_ones >= bw[(size_t)w];
+        set_plan(h, bw[(size_t)w]);
+        if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+    }
+    HIPCHK(h, hipEventRecord(h->ev[5], st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    HIPCHK(h, hipEventElapsedTime(&h->timing.prepare_ms, h->ev[4], h->ev[5]));
+    h->prepare_pending = false;
+    h->B = B;
+    h->lg_W = W; h->lg_L = (size_t)c->audio_samples;
+    h->lg_bw = bw; h->lg_off = off;
+    h->lg_prepared = h->lg_ragged = true;
     return LS_OK;
 }
 

@@ -126,10 +126,22 @@ struct ls_handle {
     bool lg_prepared = false;
     DevBuf lg_audio, lg_clips, lg_featc, lg_featp, lg_emo_ids, lg_emotok, lg_seed;
     DevBuf lg_x, lg_eps, lg_nz, lg_text, lg_init, lg_mask, lg_timeline, lg_windows;
-    // cached graph of the step loop
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    std::string graph_key;
+    // a ragged long-form call (ls_long_prepare_ragged): clips held longest-first.  lg_bw[w] clips run window w (slots [0, lg_bw[w]) of
+    // every per-clip buffer), lg_off[w] = sum of lg_bw[v], v < w, is window w's offset in the packed stores (lg_featc, the tapes);
+    // lg_row [B] on the device maps slot -> the caller's clip; lg_scale_ones = leading slots whose guidance scale is 1.
+    bool lg_ragged = false;
+    std::vector<int> lg_bw, lg_off;
+    int lg_scale_ones = 0;
+    DevBuf lg_row, lg_table, lg_lens;
+    // Cached graphs of the step loop, by loop key (ls_sample.cpp: loop_key holds everything a captured loop bakes in besides device
+    // addresses, the batch and its step plan included).  At most kGraphCacheMax entries: a plain call whose key is missing drops them
+    // all and captures its own (one entry, as before the cache); a ragged long-form call keeps one per window batch that serves two or
+    // more windows, and never evicts while its own launches are in flight -- a key that does not fit runs as stream launches.
+    // coop_launches: the sample-split launches the captured loop makes (a replay does not run the code that counts them).
+    static constexpr int kGraphCacheMax = 8;
+    struct CachedGraph { std::string key; hipGraph_t graph; hipGraphExec_t exec; unsigned coop_launches; };
+    std::vector<CachedGraph> graphs;
+    std::vector<int> graphs_for;      // the window batches (lg_bw) of the ragged call that last made room in the cache
 
     ls_timing timing{};
     ls::CallParams call_host{0, 0, 0, 0};
@@ -150,19 +162,21 @@ int ensure_temb_table(ls_handle* h);
 int build_temb_rows(ls_handle* h, const long long* idx_dev, int n, DevBuf& tmp, DevBuf& out);
 void resolve_prepare_timing(ls_handle* h, bool block);
 // the stages of ls_prepare that ls_long_prepare runs too, on the handle's stream
-int prepare_scale(ls_handle* h, const float* scale, int B, int on_device);
+int prepare_scale(ls_handle* h, const float* scale, int B, int on_device, int* leading_ones = nullptr);     // leading_ones: clips ahead of the first scale != 1
 int run_wav_encoder(ls_handle* h, const float* in, int B);
 int prepare_style(ls_handle* h, int B);
 int prepare_plan(ls_handle* h, int B);
+int plan_workspaces(ls_handle* h);          // the workspaces of the CURRENT plan's kernel families (grow only; what prepare_plan does behind decide_path)
 // ---- defined in ls_plan.cpp
 int seg_n(const ls_handle* h, int path);
 long long plan_code(const ls_handle* h);
 int coop_cap(int n_cu, int ncb);
 void decide_path(ls_handle* h);
+void set_plan(ls_handle* h, int B);         // decide_path's plan for a batch of B, without touching the cached graphs (their keys hold the plan)
 hipError_t run_step(ls_handle* h, StepArgs& s, int B, bool pair, hipStream_t st);
 hipError_t coop_reset(ls_handle* h, hipStream_t st);
 int advance_tags(ls_handle* h, hipStream_t st);
-int coop_check(ls_handle* h);
+int coop_check(ls_handle* h, bool force = false);      // force: the call ran the sample-split kernel under a plan that is no longer current
 void report_path(ls_handle* h, bool pair);
 
 // copy a caller buffer (host or device) into an internal device buffer
@@ -182,12 +196,13 @@ inline int egress(ls_handle* h, void* dst, const void* src, size_t bytes, int on
     return LS_OK;
 }
 
-inline void free_graph(ls_handle* h) {
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    if (h->graph) (void)hipGraphDestroy(h->graph);
-    h->graph_exec = nullptr;
-    h->graph = nullptr;
-    h->graph_key.clear();
+inline void free_graph(ls_handle* h) {        // every cached graph: whatever invalidates one invalidates all
+    for (auto& g : h->graphs) {
+        if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        if (g.graph) (void)hipGraphDestroy(g.graph);
+    }
+    h->graphs.clear();
+    h->graphs_for.clear();
 }
 
 // A captured loop holds raw device addresses.  Every buffer its launches can read or write grows through here: a buffer that moved

@@ -312,8 +312,16 @@ struct ChainArgs {
     const float* prev; const float* seed;
     float* feat_u; float* origin_x; float* timeline; float* window;
     int JF, T, KPP, n_pre, T_total, t_off, f0;
+    // ragged call (ls_long_prepare_ragged): workgroup b is SLOT b.  prev / feat_u / origin_x are indexed by slot, seed / timeline /
+    // window by the caller's clip row[b]; only slots below n_next continue (write feat_u / origin_x).  row == nullptr: row[b] = b and
+    // every launched slot continues (the equal-length call).
+    const int* row; int n_next;
 };
 hipError_t launch_chain_window(const ChainArgs& a, int B, hipStream_t st);
+// One encoder chunk of a ragged long-form call: clips[p][i] = audio[row][w * stride + i] for the n (row, w) pairs of `table`, 0 where
+// that sample index is >= lengths[row] (nothing beyond a clip's length is read).  audio [.][L], clips [n][AL].
+hipError_t launch_long_gather_clips(const float* audio, const int* table, const int* lengths, float* clips, int n, int AL, long long L,
+                                    int stride, hipStream_t st);
 
 // ---- torch's device normal stream (ls_torch_philox.hip; LS_NOISE_TORCH_DEVICE) ---------------------------------------------
 // One torch.randn / randn_like of n float32 elements per step: written to dst + r * dst_stride for step r of the launch.

@@ -32,6 +32,9 @@ __device__ __forceinline__ void box_muller(unsigned a, unsigned b, float& zc, fl
 // A long-form call (ls_long_sample) has one key for all of its windows and puts the window index into bits 48.. of gidx
 // (sample_offset_w = sample_offset + (w << 48), i.e. bits 16.. of c[3]): no two (window, step) pairs share a counter, the window's
 // streams do not depend on the other windows, and sample_offset keeps its meaning (clips [o, o + n) of a call are a call of n clips at offset o).
+// A ragged long-form call (ls_long_prepare_ragged) holds its clips longest-first and runs window w on the slots [0, B_w): b above is the
+// SLOT, in every kernel family, so the streams follow the slot and not the caller's row.  A batch that is already longest-first draws
+// what the equal-length call draws; another order draws what the call on the slot-ordered batch draws.  No table reaches the step kernels.
 // Elements 4*blk .. 4*blk+3 of stream (step_id, stream) of global sample gidx: ONE Philox block, two Box-Muller pairs.
 // Keyed by the global sample index, so the streams are invariant to how the batch is sharded over GPUs.
 __device__ __forceinline__ void philox_normal4(const CallParams* cp, unsigned long long gidx, unsigned step_id, unsigned stream,

@@ -259,14 +259,18 @@ int ls::coop_cap(int n_cu, int ncb) {
     return ncb == 1 && cap > kCoopMaxGroups ? kCoopMaxGroups : cap;
 }
 
-void ls::decide_path(ls_handle* h) {
-    const long long before = plan_code(h);
+void ls::set_plan(ls_handle* h, int B) {
     h->plan_pair = h->all_scale_one;
-    const PlanOut o = plan_steps(PlanIn{h->var == kTED, h->fused, h->lw_wtp.p != nullptr, h->plan_pair, h->B, h->precision, h->path_mode, h->n_cu,
+    const PlanOut o = plan_steps(PlanIn{h->var == kTED, h->fused, h->lw_wtp.p != nullptr, h->plan_pair, B, h->precision, h->path_mode, h->n_cu,
                                         h->coop_groups_max, h->cfg.layers, h->coop_ncb});
     h->nseg = o.nseg;
     for (int i = 0; i < 3; ++i) h->seg[i] = o.seg[i];
     h->use_long = h->nseg == 1 && h->seg[0].path == 1;
+}
+
+void ls::decide_path(ls_handle* h) {
+    const long long before = plan_code(h);
+    set_plan(h, h->B);
     if (before != plan_code(h)) free_graph(h);
 }
 
@@ -307,8 +311,8 @@ int ls::advance_tags(ls_handle* h, hipStream_t st) {
 
 // after a stream synchronisation: did a hand-off spin of the sample-split kernel run out?  (Never observed; a result computed past a
 // timeout is garbage, so the call fails loudly.)
-int ls::coop_check(ls_handle* h) {
-    if (seg_n(h, 2) == 0 && h->mix_cap == 0) return LS_OK;
+int ls::coop_check(ls_handle* h, bool force) {
+    if (!force && seg_n(h, 2) == 0 && h->mix_cap == 0) return LS_OK;
     unsigned v = 0;
     HIPCHK(h, hipMemcpy(&v, h->co_err.p, sizeof v, hipMemcpyDeviceToHost));
     if (!v) return LS_OK;

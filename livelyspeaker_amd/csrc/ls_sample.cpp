@@ -393,35 +393,45 @@ std::string loop_key(const ls_handle* h, const LoopCall& c) {
     return key;
 }
 
-// a chain of launches as stream launches, or as a captured graph (captured when the key changed, replayed otherwise)
+// a chain of launches as stream launches, or as a captured graph (captured when the key is not cached, replayed otherwise).  What a
+// missing key does to the cache (ls_handle.h): kReplace drops every cached graph and captures (every call but the ragged long-form
+// one: the handle then holds one graph, as it always did); kKeep captures beside the others while the cache has room and runs stream
+// launches when it has none; kReplayOnly never captures.  The last two never destroy a graph, so they are safe with replays in flight.
+enum CachePolicy { kReplace, kKeep, kReplayOnly };
 template <class Enqueue>
-int run_captured(ls_handle* h, bool use_graph, const std::string& key, Enqueue enqueue, int* graph_replayed) {
+int run_captured(ls_handle* h, bool use_graph, const std::string& key, Enqueue enqueue, int* graph_replayed, CachePolicy policy = kReplace) {
     hipStream_t st = h->stream;
     *graph_replayed = 0;
     if (!use_graph) return enqueue();
-    if (!h->graph_exec || h->graph_key != key) {
-        free_graph(h);
+    size_t at = 0;
+    while (at < h->graphs.size() && h->graphs[at].key != key) ++at;
+    if (at == h->graphs.size()) {
+        if (policy == kReplayOnly || (policy == kKeep && (int)h->graphs.size() >= ls_handle::kGraphCacheMax)) return enqueue();
+        if (policy == kReplace) free_graph(h);
         HIPCHK(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
         const int rc = enqueue();
         hipGraph_t g = nullptr;
         hipError_t e = hipStreamEndCapture(st, &g);
         if (rc != LS_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
         if (e != hipSuccess) return fail(h, LS_EHIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-        h->graph = g;
-        HIPCHK(h, hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
-        h->graph_key = key;
-        HIPCHK(h, hipEventRecord(h->ev[1], st));    // exclude capture/instantiate from loop_ms
+        hipGraphExec_t x = nullptr;
+        e = hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
+        if (e != hipSuccess) { (void)hipGraphDestroy(g); return fail(h, LS_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
+        at = h->graphs.size();
+        h->graphs.push_back({key, g, x, h->coop_launches});
+        if (policy == kReplace) HIPCHK(h, hipEventRecord(h->ev[1], st));    // exclude capture/instantiate from loop_ms
     } else {
         *graph_replayed = 1;
+        h->coop_launches = h->graphs[at].coop_launches;     // what enqueue() would have counted: advance_tags sizes the next call's tag range by it
     }
-    HIPCHK(h, hipGraphLaunch(h->graph_exec, st));
+    HIPCHK(h, hipGraphLaunch(h->graphs[at].exec, st));
     return LS_OK;
 }
 
 // the sampling loop through run_captured
-int run_loop(ls_handle* h, const LoopCall& c, int* graph_replayed) {
+int run_loop(ls_handle* h, const LoopCall& c, int* graph_replayed, CachePolicy policy = kReplace) {
     return run_captured(h, c.a->use_graph != 0, c.a->use_graph ? loop_key(h, c) : std::string(),
-                        [&]() { return c.plms ? enqueue_plms(h, c) : enqueue_loop(h, c); }, graph_replayed);
+                        [&]() { return c.plms ? enqueue_plms(h, c) : enqueue_loop(h, c); }, graph_replayed, policy);
 }
 
 // ---- the variational bound (ls_bpd / ls_vb_terms) ----------------------------------------------------------------------------
@@ -753,6 +763,13 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
 // shapes, and ls_sample's own begin_loop -> stage_loop_inputs -> run_loop on device-resident inputs; one wait at the end.  The loop's
 // launches read the handle's buffers only (static_c / static_u, the tape buffers, xa / xb, callp), none of which moves between windows,
 // so the graph captured for window 0 (or by an earlier call with the same key) is replayed for every later one.
+//
+// After ls_long_prepare_ragged window w runs the lg_bw[w] clips that still have audio: slots [0, lg_bw[w]) of every per-clip buffer
+// (the clips are held longest-first), the packed stores at lg_off[w].  Each window is then, decision for decision, a call at batch
+// lg_bw[w]: its scales decide the single-pass form, its batch the step plan (set_plan), the plan the workspaces' accounting
+// (plan_workspaces; ls_long_prepare_ragged sized them for every window, so nothing a captured loop holds moves here), and the speaker
+// style runs at that batch.  A window batch that serves two or more windows is captured once and replayed; one that serves a single
+// window runs as stream launches unless an earlier call left its graph behind.
 int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
     if (!h || !a) return fail(h, LS_EINVAL, "ls_long_sample: null argument");
     if (!h->lg_prepared) return fail(h, LS_ESTATE, "ls_long_sample before ls_long_prepare");
@@ -761,8 +778,12 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
     if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EUNSUPPORTED, "ls_long_sample: TAPE and PHILOX noise only");
     if (!a->timeline) return fail(h, LS_EINVAL, "ls_long_sample: null timeline");
     if (a->sag && !a->text_features) return fail(h, LS_EINVAL, "ls_long_sample: sag without text_features");
+    const bool rg = h->lg_ragged;
     const int B = h->B, W = h->lg_W, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, od = a->on_device, dev = h->cfg.device;
     const int Tt = T + (W - 1) * (T - npre);
+    if (rg && ((int)h->lg_bw.size() != W || (int)h->lg_off.size() != W + 1 || h->lg_bw[0] != B)) return fail(h, LS_ESTATE, "ls_long_sample: the ragged plan does not match the prepared batch");
+    auto batch_of = [&](int w) { return rg ? h->lg_bw[(size_t)w] : B; };                      // clips that run window w
+    auto first_of = [&](int w) { return (size_t)(rg ? h->lg_off[(size_t)w] : w * B); };       // clip-windows ahead of window w in the packed stores
     ls_sample_args wa{};
     wa.sampler = a->sampler; wa.noise_mode = a->noise_mode; wa.skip_timesteps = a->skip_timesteps; wa.on_device = 1;
     wa.use_graph = a->use_graph; wa.clip_denoised = a->clip_denoised; wa.two_pass_always = a->two_pass_always; wa.eta = a->eta;
@@ -776,12 +797,13 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
     h->seg_next = -1;
     hipStream_t st = h->stream;
     const int n_exec = h->n_steps - a->skip_timesteps;
-    const size_t nelem = (size_t)B * JF * T, nx = nelem * sizeof(float), ne = (size_t)n_exec * 2 * B * kD, nn = (size_t)n_exec * nelem;
+    const size_t per_x = (size_t)JF * T, per_e = (size_t)n_exec * 2 * kD, per_n = (size_t)n_exec * per_x;     // floats per clip-window: x_T, eps tape, noise tape
+    const size_t nelem = (size_t)B * per_x, nx = nelem * sizeof(float), total = first_of(W);
     // host tapes / text features: one upload per call; device ones are read in place
     const float *xs = a->x_init, *es = a->eps_tape, *ns = a->noise_tape, *tx = a->text_features;
     if (tape && !od) {
-        if ((rc = ingest(h, h->lg_x, xs, W * nx, 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, W * ne * sizeof(float), 0)) != LS_OK ||
-            (rc = ingest(h, h->lg_nz, ns, W * nn * sizeof(float), 0)) != LS_OK) return rc;
+        if ((rc = ingest(h, h->lg_x, xs, total * per_x * sizeof(float), 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, total * per_e * sizeof(float), 0)) != LS_OK ||
+            (rc = ingest(h, h->lg_nz, ns, total * per_n * sizeof(float), 0)) != LS_OK) return rc;
         xs = h->lg_x.f(); es = h->lg_eps.f(); ns = h->lg_nz.f();
     }
     ls_sag* const sag = a->sag;
@@ -800,33 +822,61 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
         tl = h->lg_timeline.f();
         if (wd) wd = h->lg_windows.f();
     }
+    if (rg) {
+        // what a clip does not reach stays zero: its timeline beyond its own frames, its raw windows from its window count on
+        HIPCHK(h, hipMemsetAsync(tl, 0, (size_t)B * JF * Tt * sizeof(float), st));
+        if (wd) HIPCHK(h, hipMemsetAsync(wd, 0, W * nx, st));
+        // Room in the graph cache for the batches this call captures (at most the cache's bound; the rest run as stream launches), made
+        // now: nothing of this call is in flight yet.  The same window batches as the last ragged call: its graphs are this call's.
+        if (h->graphs_for != h->lg_bw) {
+            int repeated = 0;
+            for (int w = 1; w < W; ++w) if (h->lg_bw[(size_t)w] == h->lg_bw[(size_t)w - 1] && (w < 2 || h->lg_bw[(size_t)w - 1] != h->lg_bw[(size_t)w - 2])) ++repeated;
+            if (repeated > ls_handle::kGraphCacheMax) repeated = ls_handle::kGraphCacheMax;
+            if ((int)h->graphs.size() + repeated > ls_handle::kGraphCacheMax) free_graph(h);
+            h->graphs_for = h->lg_bw;
+        }
+    }
     ChainArgs ca{};
     ca.seed = h->lg_seed.f(); ca.timeline = tl;
     ca.JF = JF; ca.T = T; ca.KPP = h->KPP; ca.n_pre = npre; ca.T_total = Tt;
+    ca.row = rg ? static_cast<const int*>(h->lg_row.p) : nullptr;
     LoopCall c{};
-    int replayed = 0, replays = 0;
+    int replayed = 0, replays = 0, styled = 0;
+    bool pair0 = false, coop_used = false;
     for (int w = 0; w <= W; ++w) {
+        const int Bw = w < W ? batch_of(w) : 0, Bprev = w ? batch_of(w - 1) : 0;
         // hand-off: window w - 1 leaves through the timeline, window w's prefix poses enter feat_u / origin_x
         ca.prev = w ? x_plane(h, n_exec) : nullptr;
         ca.feat_u = w < W ? h->feat_u.f() : nullptr; ca.origin_x = h->origin_x.f();
         ca.f0 = w == 1 ? 0 : npre; ca.t_off = w <= 1 ? 0 : T + (w - 2) * (T - npre);
         ca.window = (w && wd) ? wd + (size_t)(w - 1) * nelem : nullptr;
-        HIPCHK(h, launch_chain_window(ca, B, st));
+        ca.n_next = Bw;
+        HIPCHK(h, launch_chain_window(ca, w ? Bprev : Bw, st));
         if (w == W) break;
+        if (rg) {           // from here on the handle is prepared for a batch of Bw
+            h->B = Bw;
+            h->all_scale_one = h->lg_scale_ones >= Bw;
+            set_plan(h, Bw);
+            if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+            if (styled != Bw && (rc = prepare_style(h, Bw)) != LS_OK) return rc;
+            styled = Bw;
+        }
+        coop_used = coop_used || seg_n(h, 2) > 0;
         // the static projections with ls_prepare's arithmetic and shapes: static_u = feat_u . Wpre^T + b; static_c = static_u + feat_c[w] . Waud^T
-        HIPCHK(h, launch_gemm_nt(h->feat_u.f(), h->KPP, h->win_pre.f(), h->KPP, h->win_bias.f(), nullptr, 0, h->static_u.f(), kD, B * T, kD, h->KPP, 0, st));
-        HIPCHK(h, launch_gemm_nt(h->lg_featc.f() + (size_t)w * B * T * kAudioFeat, kAudioFeat, h->win_aud.f(), kAudioFeat, nullptr, h->static_u.f(), kD,
-                                 h->static_c.f(), kD, B * T, kD, kAudioFeat, 0, st));
+        HIPCHK(h, launch_gemm_nt(h->feat_u.f(), h->KPP, h->win_pre.f(), h->KPP, h->win_bias.f(), nullptr, 0, h->static_u.f(), kD, Bw * T, kD, h->KPP, 0, st));
+        HIPCHK(h, launch_gemm_nt(h->lg_featc.f() + first_of(w) * T * kAudioFeat, kAudioFeat, h->win_aud.f(), kAudioFeat, nullptr, h->static_u.f(), kD,
+                                 h->static_c.f(), kD, Bw * T, kD, kAudioFeat, 0, st));
         if (h->cfg.n_prefix_tokens == 2)
-            HIPCHK(h, hipMemcpyAsync(h->emo_tok.p, h->lg_emotok.f() + (size_t)w * B * kD, (size_t)B * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(h->emo_tok.p, h->lg_emotok.f() + (size_t)w * B * kD, (size_t)Bw * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
         if (sag) {      // the decoder runs on its own handle's stream, ordered behind the hand-off and ahead of the loop by events
             if (ls_stream_order(dev, st, sag_st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
-            if (ls_sag_decode_async(sag, B, h->origin_x.f(), tx + (size_t)w * B * kD, static_cast<const unsigned char*>(h->lg_mask.p), h->lg_init.f()) != LS_OK)
+            if (ls_sag_decode_async(sag, Bw, h->origin_x.f(), tx + (size_t)w * B * kD, static_cast<const unsigned char*>(h->lg_mask.p), h->lg_init.f()) != LS_OK)
                 return fail(h, LS_EHIP, "SAG decode of window %d: %s", w, ls_sag_last_error(sag));
             if (ls_stream_order(dev, sag_st, st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
         }
-        if (tape) { wa.x_init = xs + (size_t)w * nelem; wa.eps_tape = es + (size_t)w * ne; wa.noise_tape = ns + (size_t)w * nn; }
+        if (tape) { wa.x_init = xs + first_of(w) * per_x; wa.eps_tape = es + first_of(w) * per_e; wa.noise_tape = ns + first_of(w) * per_n; }
         c = loop_call(h, &wa);
+        if (w == 0) pair0 = c.pair;
         // begin_loop's advance_tags uploads call_host (24 bytes of pageable memory) as every ls_sample does: the runtime takes such a
         // source into its staging memory before hipMemcpyAsync returns, which is what makes rewriting it for the next window safe.  It is
         // the one host -> device copy per window; whether the runtime waits inside it is the runtime's business (not measured).
@@ -835,8 +885,20 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
         if (w == 0) HIPCHK(h, hipEventRecord(h->ev[6], st));        // ev[0] is re-recorded by every window's begin_loop
         if ((rc = stage_loop_inputs(h, c)) != LS_OK) return rc;
         if (w == 0) HIPCHK(h, hipEventRecord(h->ev[1], st));
-        if ((rc = run_loop(h, c, &replayed)) != LS_OK) return rc;
+        CachePolicy policy = kReplace;
+        if (rg) {
+            int serves = 0;
+            for (int v = 0; v < W; ++v) serves += h->lg_bw[(size_t)v] == Bw;
+            policy = serves >= 2 ? kKeep : kReplayOnly;
+        }
+        if ((rc = run_loop(h, c, &replayed, policy)) != LS_OK) return rc;
         replays += replayed;
+    }
+    if (rg) {               // leave the handle as ls_long_prepare_ragged left it: prepared for the whole batch
+        h->B = B;
+        h->all_scale_one = h->lg_scale_ones >= B;
+        set_plan(h, B);
+        if ((rc = plan_workspaces(h)) != LS_OK) return rc;
     }
     HIPCHK(h, hipEventRecord(h->ev[2], st));
     if (!od) {
@@ -845,12 +907,12 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
     }
     HIPCHK(h, hipEventRecord(h->ev[3], st));
     HIPCHK(h, hipStreamSynchronize(st));
-    if ((rc = coop_check(h)) != LS_OK) return rc;
-    report_path(h, c.pair);
+    if ((rc = coop_check(h, coop_used)) != LS_OK) return rc;
+    report_path(h, pair0);
     HIPCHK(h, hipEventElapsedTime(&h->timing.loop_ms, h->ev[1], h->ev[2]));
     HIPCHK(h, hipEventElapsedTime(&h->timing.total_ms, h->ev[6], h->ev[3]));
     h->timing.n_step_launches = W * n_exec;
-    h->timing.single_pass = c.pair ? 1 : 0;
+    h->timing.single_pass = pair0 ? 1 : 0;
     h->timing.graph_replayed = replays;          // windows served by a replay: W - 1 after a capture, W on a warm handle
     h->timing.tape_upload_ms = 0.f;
     h->timing.n_segments = W;

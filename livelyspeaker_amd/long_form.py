@@ -14,6 +14,9 @@ With ``noise_source='torch_cpu'`` the draws are those ``GaussianDiffusion._loop`
 (``ref_draws.RefDraws.windows``), and the result is bit for bit what the same windows give through ``ddim_sample_loop`` /
 ``p_sample_loop`` (and ``Decoder_TRANSFORMER.forward`` with ``sag``) called once per window with ``origin_x`` rebuilt in between
 (tests/test_gpu_long_form.py).  ``'philox'`` draws one key per call; the window index is folded into the Philox counter (csrc/ls_philox.h).
+
+Clips of different lengths (``audio_lengths=``) run the longest clip's windows; with ``drop_finished=True`` a clip leaves the batch once
+its own audio has ended (``plan_drop``; ``ls_long_prepare_ragged``), and window ``w`` is a sampling call on the clips that remain.
 """
 from __future__ import annotations
 
@@ -42,6 +45,26 @@ def plan_lengths(audio_lengths, cfg):
     clip's stitched timeline, both from ``plan_windows``."""
     plans = [plan_windows(int(n), cfg) for n in np.asarray(audio_lengths).reshape(-1)]
     return [(W, frames) for W, _, frames in plans]
+
+
+def plan_drop(audio_lengths, cfg):
+    """The batch plan of ``sample_long(audio_lengths=, drop_finished=True)``, from the lengths alone (no GPU):
+    ``(order, windows, active, offsets)``, numpy int arrays.
+
+    * ``order`` [B]: slot -> clip.  The clips are held in slots, stably sorted by their window count ``W_b`` (``plan_lengths``),
+      longest first; clips with the same count keep the caller's order.
+    * ``windows`` [B]: ``W_b`` of the clip in each slot (non-increasing).
+    * ``active`` [W_max]: ``B_w``, the clips that run window ``w`` -- those with ``W_b > w``, which are the slots ``[0, B_w)``.
+      ``active[0] == B``.
+    * ``offsets`` [W_max + 1]: running sums of ``active``; window ``w`` owns the entries ``offsets[w] .. offsets[w + 1]`` of everything
+      that is packed window after window (the noise tapes; ``offsets[-1]`` clip-windows in all, against ``B * W_max``).
+
+    One definition for the engine and for this module (``ls_long_plan_drop``)."""
+    lens = np.asarray(audio_lengths).reshape(-1)
+    order, windows, active = _lib.long_plan_drop(lens, int(cfg.audio_len))
+    offsets = np.zeros(active.size + 1, np.int64)
+    np.cumsum(active, out=offsets[1:])
+    return order.astype(np.int64), windows.astype(np.int64), active.astype(np.int64), offsets
 
 
 def _window_sizes(W, cfg):
@@ -125,7 +148,7 @@ def _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, n_
 
 def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=None, n_windows=None, sampler='ddim', skip_timesteps=0,
                 eta=0.0, clip_denoised=False, sag=None, text_features=None, encoder_chunk=None, return_windows=False, audio_lengths=None,
-                **unsupported):
+                drop_finished=False, **unsupported):
     """``n_windows`` chained windows for ``audio`` [B, L] (default: the windows that cover it, ``plan_windows``) as one timeline
     ``[B, J, F, T + (W - 1) * (T - n_pre)]`` on the inputs' device; ``return_windows=True`` adds the raw windows ``[W, B, J, F, T]``.
 
@@ -140,10 +163,29 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
     longest clip (``W_max`` of ``plan_lengths``; ``emo`` [B, W] and ``text_features`` [B, W, 512] are sized by it), clip b's timeline
     is zero beyond its own ``frames_b``, and the result is ``(timeline, frames)`` -- ``(timeline, frames, windows)`` with
     ``return_windows`` -- with ``frames`` the host int32 [B] that ``score_timeline(frames=, audio_lengths=)`` takes.  Together with
-    ``n_windows`` it raises ``ValueError``.  Not built: dropping finished clips from later windows.  The engine plans one batch size
-    per call, so a short clip still pays for ``W_max`` windows; running a shrinking prefix of length-sorted clips is a follow-up."""
+    ``n_windows`` it raises ``ValueError``.  Every clip runs all ``W_max`` windows unless ``drop_finished`` is set.
+
+    ``drop_finished=True`` (needs ``audio_lengths``): a clip runs only its own ``W_b`` windows.  The clips are held longest-first
+    (``plan_drop``) and window w is a sampling call on the ``B_w`` clips that still have audio, at that batch: its own kernel plan,
+    and the single-pass shortcut when the scales of THOSE clips are all 1.  Inputs, shapes and the return value are those of
+    ``audio_lengths`` alone, in the caller's clip order; the raw windows are zero for ``w >= W_b``; entries of ``emo`` and
+    ``text_features`` for windows a clip does not run are ignored, and so is ``audio`` beyond a clip's length (it is never read: no
+    zero-filled copy is made).  The noise contract:
+
+    * ``'torch_cpu'``: the draws are those of one public sampling call per window at batch ``B_w`` on the active clips in slot
+      order, window after window (``RefDraws.windows(batches=)``), and the result is bit for bit that loop's
+      (tests/test_gpu_long_drop.py).  The one-window tape bound (``tape_segment_bytes``) is checked for window 0, the largest.
+    * ``'philox'``: the clip in slot s draws, in window w, the streams of global sample index ``sample_offset + s + (w << 48)``: the
+      streams follow the slot, not the caller's row.  A batch that is already longest-first gets exactly the draws of the same call
+      without ``drop_finished`` (and, where no kernel choice differs between the batch sizes, its bits on every clip's valid
+      range); any other order gets the draws of the call on the slot-ordered batch.
+    * ``'torch_device'`` stays refused.
+
+    Not built: device-resident length arrays."""
     if audio_lengths is not None and n_windows is not None:
         raise ValueError("sample_long: audio_lengths decide the windows of every clip; pass either n_windows or audio_lengths")
+    if drop_finished and audio_lengths is None:
+        raise ValueError("sample_long: drop_finished drops a clip when its audio_lengths entry is used up; pass audio_lengths")
     as_t = lambda a: a if (a is None or th.is_tensor(a)) else th.as_tensor(np.asarray(a))      # noqa: E731
     audio, seed_poses, vid_indices, scale, emo, text_features = (as_t(a) for a in (audio, seed_poses, vid_indices, scale, emo, text_features))
     frames = None
@@ -154,8 +196,9 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
         plans = plan_lengths(lens, model.model)
         n_windows = max(W for W, _ in plans)
         frames = np.array([f for _, f in plans], np.int32)
-        valid = th.arange(int(audio.shape[1]))[None, :] < th.from_numpy(lens.astype(np.int64))[:, None]
-        audio = th.where(valid.to(audio.device), audio, th.zeros((), dtype=audio.dtype, device=audio.device))       # a copy; NaN tails become 0
+        if not drop_finished:
+            valid = th.arange(int(audio.shape[1]))[None, :] < th.from_numpy(lens.astype(np.int64))[:, None]
+            audio = th.where(valid.to(audio.device), audio, th.zeros((), dtype=audio.dtype, device=audio.device))       # a copy; NaN tails become 0
     B, W = _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, n_windows, sampler, skip_timesteps, sag, text_features,
                        encoder_chunk, unsupported)
     if diffusion.model_mean_type != gd.ModelMeanType.START_X or diffusion.model_var_type != gd.ModelVarType.FIXED_SMALL:
@@ -168,7 +211,16 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
     rag._cond_key = rag._prefetched_key = None        # the engine's resident conditioning is this call's from here on
     if emo is not None:
         emo = (emo[None, :].expand(W, B) if emo.ndim == 1 else emo.t()).contiguous()
-    eng.long_prepare(audio.float(), seed_poses.float(), vid_indices, scale.float(), emo=emo, n_windows=W, encoder_chunk=encoder_chunk)
+    batches = None
+    if drop_finished:       # the engine reads audio and seed poses through its slot table; the B- and W*B-row inputs are put in slot order here
+        order, _, active, _ = plan_drop(lens, rag)
+        batches = [int(n) for n in active]
+        slot = lambda a, dim: a.index_select(dim, th.from_numpy(order).to(a.device))      # noqa: E731
+        vid_indices, scale = slot(vid_indices, 0), slot(scale, 0)
+        emo = None if emo is None else slot(emo, 1).contiguous()
+        text_features = None if text_features is None else slot(text_features, 0)
+    eng.long_prepare(audio.float(), seed_poses.float(), vid_indices, scale.float(), emo=emo, n_windows=W, encoder_chunk=encoder_chunk,
+                     audio_lengths=lens if drop_finished else None)
     n_exec = diffusion.num_timesteps - int(skip_timesteps)
     shape = (B, rag.njoints, rag.nfeats, rag.nframes)
     kw = dict(sampler=_lib.LS_SAMPLER_DDIM if sampler == "ddim" else _lib.LS_SAMPLER_DDPM, skip_timesteps=int(skip_timesteps),
@@ -188,11 +240,13 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
             raise ValueError(f"sample_long: one window's noise tape is {per_window} bytes, tape_segment_bytes is "
                              f"{diffusion.tape_segment_bytes}; segmented tapes are not built for chained windows (raise "
                              "tape_segment_bytes or use noise_source='philox')")
-        kw["x_init"], kw["eps_tape"], kw["noise_tape"] = ref_draws.RefDraws("cpu").windows(diffusion, W, n_exec, shape, eng.D)
+        kw["x_init"], kw["eps_tape"], kw["noise_tape"] = ref_draws.RefDraws("cpu").windows(diffusion, W, n_exec, shape, eng.D, batches=batches)
         diffusion.last_tape_segments = 1
     res = eng.long_sample(**kw)
     timeline, windows = res if return_windows else (res, None)
     timeline = gd._as_tensor(timeline, out_dev)
+    if drop_finished:       # the engine zero-filled both outputs ahead of window 0
+        return (timeline, frames, gd._as_tensor(windows, out_dev)) if return_windows else (timeline, frames)
     if frames is not None:
         keep = th.arange(int(timeline.shape[3]))[None, :] < th.from_numpy(frames.astype(np.int64))[:, None]
         timeline = th.where(keep.to(timeline.device)[:, None, None, :], timeline, th.zeros((), dtype=timeline.dtype, device=timeline.device))

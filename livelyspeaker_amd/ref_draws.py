@@ -77,13 +77,33 @@ class RefDraws:
     def steps(self, shape, D, n_exec, first=None, inpainted=None, diffusion=None):
         return _Steps(self, shape, D, n_exec, first, inpainted, diffusion)
 
-    def windows(self, diffusion, W, n_exec, shape, D):
-        """Long-form: W calls of the sample loop, window after window -- x_T, then that window's steps (contiguous first x)."""
-        steps = self.steps(shape, D, n_exec, diffusion=diffusion)
-        x, eps, nz = th.empty((W,) + shape), th.empty(W, n_exec, 2, shape[0], D), th.empty((W, n_exec) + shape)
-        for w in range(W):
-            x[w] = self.x_T(shape)
-            steps.run(0, eps[w], nz[w])
+    def windows(self, diffusion, W, n_exec, shape, D, batches=None):
+        """Long-form: W calls of the sample loop, window after window -- x_T, then that window's steps (contiguous first x).
+
+        ``batches`` (one batch size per window; ``shape[0]`` is then ignored): window w is a call at batch ``batches[w]``, and the
+        tapes come back packed -- x [sum batches, J, F, T], and flat eps / noise holding per window [n_exec, 2, B_w, D] /
+        [n_exec, B_w, J, F, T], concatenated.  What W single-window calls at those batches draw one after the other."""
+        if batches is None:
+            steps = self.steps(shape, D, n_exec, diffusion=diffusion)
+            x, eps, nz = th.empty((W,) + shape), th.empty(W, n_exec, 2, shape[0], D), th.empty((W, n_exec) + shape)
+            for w in range(W):
+                x[w] = self.x_T(shape)
+                steps.run(0, eps[w], nz[w])
+            return x, eps, nz
+        batches = [int(b) for b in batches]
+        if len(batches) != W or min(batches) < 1:
+            raise ValueError(f"batches must hold {W} batch sizes >= 1, got {batches}")
+        rest, total = tuple(shape[1:]), sum(batches)
+        per_x = int(np.prod(rest))
+        x, eps, nz = th.empty((total,) + rest), th.empty(total * n_exec * 2 * D), th.empty(total * n_exec * per_x)
+        first = 0
+        for Bw in batches:
+            wshape = (Bw,) + rest
+            x[first:first + Bw] = self.x_T(wshape)
+            self.steps(wshape, D, n_exec, diffusion=diffusion).run(
+                0, eps[first * n_exec * 2 * D:(first + Bw) * n_exec * 2 * D].view(n_exec, 2, Bw, D),
+                nz[first * n_exec * per_x:(first + Bw) * n_exec * per_x].view((n_exec,) + wshape))
+            first += Bw
         return x, eps, nz
 
     def bpd_columns(self, diffusion, nz, eps, proto):
