@@ -90,26 +90,48 @@ __device__ __forceinline__ float wload1(wrsrc_t r, int lane_bytes, int wave_byte
 // hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid); both differences are exact in fp32.  Inf / NaN give NaN residuals.
 // Written pair by pair so that each rounding is one v_cvt_pk_bf16_f32 for two values and each part goes back to fp32 with one
 // shift or mask: 11 VALU per pair (a per-element form compiles to ~15).
+// Two callers, one arithmetic (split3_pair): split3_f4 is the producer's form -- the wave that owns a channel splits its float4 once
+// while writing LayerNorm 2's output and stores the three parts as bf16 planes in LDS (k_step PREC 2, LS_SPLIT_SHARED 1, the default) --
+// and split3_bf16 is the consumer's form, which splits a B fragment in registers after its ds_read (LS_SPLIT_SHARED 0: every wave
+// then splits every value again, 16 times per value and layer).
 __device__ __forceinline__ unsigned cvt_pk_bf16(float x, float y) {
     typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(unsigned, __builtin_convertvector((f2){x, y}, bf2));
 }
 __device__ __forceinline__ float bf16_lo_f32(unsigned p) { return __builtin_bit_cast(float, p << 16); }
 __device__ __forceinline__ float bf16_hi_f32(unsigned p) { return __builtin_bit_cast(float, p & 0xFFFF0000u); }
+__device__ __forceinline__ void split3_pair(float v0, float v1, unsigned& h, unsigned& m, unsigned& l) {
+    h = cvt_pk_bf16(v0, v1);
+    const float r0 = v0 - bf16_lo_f32(h), r1 = v1 - bf16_hi_f32(h);
+    m = cvt_pk_bf16(r0, r1);
+    l = cvt_pk_bf16(r0 - bf16_lo_f32(m), r1 - bf16_hi_f32(m));
+}
 __device__ __forceinline__ void split3_bf16(f4 x0, f4 x1, bf8& hi, bf8& mid, bf8& lo) {
     typedef unsigned u4 __attribute__((ext_vector_type(4)));
     u4 h, m, l;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const float v0 = e < 2 ? x0[2 * e] : x1[2 * e - 4], v1 = e < 2 ? x0[2 * e + 1] : x1[2 * e - 3];
-        h[e] = cvt_pk_bf16(v0, v1);
-        const float r0 = v0 - bf16_lo_f32(h[e]), r1 = v1 - bf16_hi_f32(h[e]);
-        m[e] = cvt_pk_bf16(r0, r1);
-        l[e] = cvt_pk_bf16(r0 - bf16_lo_f32(m[e]), r1 - bf16_hi_f32(m[e]));
+        unsigned hh, mm, ll;
+        split3_pair(v0, v1, hh, mm, ll);
+        h[e] = hh; m[e] = mm; l[e] = ll;
     }
     hi = __builtin_bit_cast(bf8, h);
     mid = __builtin_bit_cast(bf8, m);
     lo = __builtin_bit_cast(bf8, l);
+}
+__device__ __forceinline__ void split3_f4(f4 x, bf4& hi, bf4& mid, bf4& lo) {
+    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+    u2 h, m, l;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        unsigned hh, mm, ll;
+        split3_pair(x[2 * e], x[2 * e + 1], hh, mm, ll);
+        h[e] = hh; m[e] = mm; l[e] = ll;
+    }
+    hi = __builtin_bit_cast(bf4, h);
+    mid = __builtin_bit_cast(bf4, m);
+    lo = __builtin_bit_cast(bf4, l);
 }
 // The partial products kept, as (weight part, operand part) with 0 = hi, 1 = mid, 2 = lo, in accumulation order (smallest
 // first, hi.hi last).  6 terms (default): every term with i + j <= 2; each dropped one is at most 2^-24 of |W'||u| (2^-8 x 2^-16),

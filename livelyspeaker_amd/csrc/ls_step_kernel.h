@@ -20,6 +20,10 @@
 //     U[row][k] with row stride 520 floats: lane (token, g) fetches k = 16q+4g..+3 with one conflict-free
 //     ds_read_b128 and feeds 4 consecutive MFMAs; the weight operand uses the same k permutation and is
 //     pre-swizzled on the host so each wave-instruction reads 1 KiB contiguous from L2.
+//     PREC 2 stages LN2(x) differently: the wave that owns a channel splits it into its three bf16 parts ONCE while writing it, and
+//     the parts lie in LDS as three planes [48][520] of bf16 -- one 48-row chunk (token tiles 0-2, then tiles 3-4) at a time, because
+//     the planes of all R rows would not fit.  The consumers read ready bf16 fragments (ds_read_b128 at row * 520 + 8g + 32q, the
+//     PREC 1 address) and do no conversion work; each wave streams its weight slice once per chunk, i.e. twice per layer.
 //   * token mixing (Conv1d(S,S,1) over the token axis) is a second small MFMA GEMM against a
 //     block-diagonal [R x R] operand; its output lands directly in the residual layout.
 #pragma once
@@ -67,6 +71,18 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
 #define LS_TOK_TR 1
 #endif
     constexpr bool kTokTr = LS_TOK_TR != 0;
+    // Split-fp32 channel mixing (PREC 2): 1 = the LayerNorm-2 operand is split into its three bf16 parts once, by the wave that owns the
+    // channel, and staged as three bf16 planes per 48-row chunk; 0 = it is staged as fp32 and every wave splits every fragment it reads
+    // (the earlier form, kept for same-tree A/B: tools/ab_variants.py build old=LS_SPLIT_SHARED=0 new=).  Both give the same bits.
+#ifndef LS_SPLIT_SHARED
+#define LS_SPLIT_SHARED 1
+#endif
+    constexpr bool kSplitShared = PREC == 2 && LS_SPLIT_SHARED != 0;
+    constexpr int kChunkTiles = 3;             // token tiles of chunk 0 (rows 0..47); chunk 1 = tiles 3..4 (rows 48..R-1)
+    constexpr int kChunkRows = 16 * kChunkTiles;
+    constexpr int kPlane = kChunkRows * kUStride;      // bf16 per plane
+    static_assert(!kSplitShared || 3 * kPlane * 2 <= (R * kUStride + kWaves * 2 * NREM * 16) * 4, "three bf16 planes of a chunk must fit U + REM");
+    static_assert(R > kChunkRows && R - kChunkRows <= kChunkRows, "two chunks cover the rows");
     constexpr int kGrpStride = kD * 8 + 16;    // bf16 per 8-row group (+32 B so the two row halves of a tile miss each other's banks)
     static_assert(2 * NG * kGrpStride * 2 <= (R * kUStride + kWaves * 2 * NREM * 16) * 4, "bf16 token-mix planes must fit U + REM");
     static_assert(NREM > 0 && NREM <= 16, "ragged tile");
@@ -424,6 +440,94 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
         }
     };
 
+    // PREC 2 form of LN2's store (kSplitShared): token tiles [t0, t1) of one 48-row chunk, u = (x - mean) * rstd as above, split by its
+    // owner into hi / mid / lo (split3_f4: the arithmetic of split3_bf16) and written as three 8-byte stores into the bf16 planes
+    // P[part][row - first row of the chunk][520] that overlay U (+ REM).  Padding rows are not written: their lanes read the clamped last row.
+    auto ln_store_split = [&](auto t0c, auto t1c) {
+        constexpr int t0 = decltype(t0c)::value, t1 = decltype(t1c)::value;
+        __bf16* P = reinterpret_cast<__bf16*>(U);
+#pragma unroll
+        for (int t = t0; t < t1; ++t)
+            if (valid_of(t)) {
+                const float nmr = -mean[t] * rstd[t];
+                const f4 rs = (f4){rstd[t], rstd[t], rstd[t], rstd[t]}, nm = (f4){nmr, nmr, nmr, nmr};
+                __bf16* dst = P + (row_of(t) - 16 * t0) * kUStride + chw;
+#pragma unroll
+                for (int cb = 0; cb < kCB; ++cb) {
+                    const f4 u = __builtin_elementwise_fma(X[cb][t], rs, nm);          // packed f32
+                    bf4 hi, mid, lo;
+                    split3_f4(u, hi, mid, lo);
+                    *reinterpret_cast<bf4*>(dst + 16 * cb) = hi;
+                    *reinterpret_cast<bf4*>(dst + kPlane + 16 * cb) = mid;
+                    *reinterpret_cast<bf4*>(dst + 2 * kPlane + 16 * cb) = lo;
+                }
+            }
+    };
+    // the channel mixing of tiles [t0, t1) of the chunk that ln_store_split has staged, for both channel halves p of this wave; the six
+    // terms of every (q, t) in the order of kSplitA / kSplitB (smallest first, c2 innermost), q ascending: each accumulator adds the same
+    // sequence as in the in-register form.  The weight slice is prefetched one k block ahead.
+    auto chmix_split_chunk = [&](int l, auto t0c, auto t1c) {
+        constexpr int t0 = decltype(t0c)::value, t1 = decltype(t1c)::value, NTC = t1 - t0;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            fresh();
+            f4 acc[2][NTC];
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2) {
+                const f4 bc = wload4(wrsrc(a.W->bch), chw * 4, (l * kD + 16 * (2 * p + c2)) * 4);
+#pragma unroll
+                for (int t = 0; t < NTC; ++t) acc[c2][t] = bc;
+            }
+            const wrsrc_t wr0 = wrsrc(a.W->wch_hi_img), wr1 = wrsrc(a.W->wch_lo_img), wr2 = wrsrc(a.W->wch_lo2_img);
+            const int wsb = (((l * kWaves + w) * 2 + p) * 16) * 2 * 1024;
+            typedef const __attribute__((address_space(3))) bf8* ldsp8;
+            typedef const __attribute__((address_space(3))) __bf16* ldspb;
+            ldspb pb[NTC];                            // lane (token, g) reads k = 32q + 8g .. +7 of its (clamped) row, per part
+#pragma unroll
+            for (int t = 0; t < NTC; ++t) pb[t] = (ldspb)(reinterpret_cast<const __bf16*>(U) + (rowc_of(t0 + t) - 16 * t0) * kUStride + 8 * g);
+            bf8 An[3][2];
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2) {
+                An[0][c2] = wload8h(wr0, lane * 16, wsb + c2 * 1024);
+                An[1][c2] = wload8h(wr1, lane * 16, wsb + c2 * 1024);
+                An[2][c2] = wload8h(wr2, lane * 16, wsb + c2 * 1024);
+            }
+            if (!LS_ABLATED(a, 1))
+#pragma unroll 1
+            for (int q = 0; q < 16; ++q) {
+                bf8 A[3][2];
+#pragma unroll
+                for (int s = 0; s < 3; ++s)
+#pragma unroll
+                    for (int c2 = 0; c2 < 2; ++c2) A[s][c2] = An[s][c2];
+                const int qn = (q + 1 < 16) ? q + 1 : 15;
+#pragma unroll
+                for (int c2 = 0; c2 < 2; ++c2) {
+                    An[0][c2] = wload8h(wr0, lane * 16, wsb + (qn * 2 + c2) * 1024);
+                    An[1][c2] = wload8h(wr1, lane * 16, wsb + (qn * 2 + c2) * 1024);
+                    An[2][c2] = wload8h(wr2, lane * 16, wsb + (qn * 2 + c2) * 1024);
+                }
+#pragma unroll
+                for (int t = 0; t < NTC; ++t) {
+                    bf8 B[3];
+#pragma unroll
+                    for (int s = 0; s < 3; ++s) B[s] = *(ldsp8)(pb[t] + s * kPlane + 32 * q);
+#pragma unroll
+                    for (int i = 0; i < kSplitTerms; ++i)
+#pragma unroll
+                        for (int c2 = 0; c2 < 2; ++c2)
+                            acc[c2][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[kSplitA[i]][c2], B[kSplitB[i]], acc[c2][t], 0, 0, 0);
+                }
+            }
+            fresh();
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+                for (int t = 0; t < NTC; ++t)
+                    if (valid_of(t0 + t)) X[2 * p + c2][t0 + t] = silu_acc4(acc[c2][t], X[2 * p + c2][t0 + t]);
+        }
+    };
+
     // ================= TransMLP: 8 x MLPblock (mlp_module.py:67-91) ================================
     for (int l = 0; l < a.layers; ++l) {
         fresh();
@@ -590,10 +694,34 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
         }
         ln_stats(TRAIN ? a.tr_s2 + (size_t)l * a.tr_B * S * 2 : nullptr);
         stamp(5 + 8 * l);      // its two barriers also order every wave's token-mix reads before the stores below
-        ln_store(std::integral_constant<bool, TRAIN>{}, alv2, bev2, TRAIN ? a.tr_x2 + (size_t)l * a.tr_B * S * kD : nullptr);
-        __syncthreads();
-        stamp(6 + 8 * l);
-        if constexpr (PREC == 1) {
+        if constexpr (!kSplitShared) {
+            ln_store(std::integral_constant<bool, TRAIN>{}, alv2, bev2, TRAIN ? a.tr_x2 + (size_t)l * a.tr_B * S * kD : nullptr);
+            __syncthreads();
+            stamp(6 + 8 * l);
+        }
+        if constexpr (kSplitShared) {
+            // ---- split-fp32, operand split once: W'.u with both operands split exactly into three bf16 parts, a = a0 + a1 + a2
+            // (round-to-nearest: |a1| <= 2^-8 |a|, |a2| <= 2^-16 |a|); every bf16 x bf16 product is exact in fp32.  The weight planes come
+            // split from the host (wch_hi / wch_lo / wch_lo2); the operand's three planes are written by ln_store_split, 48 rows at a
+            // time (all R rows would need 3 * R * 1040 B = 218 KB), so a layer is: chunk 0 staged | barrier | tiles 0-2 mixed and added
+            // to X | barrier (every wave is done reading chunk 0) | chunk 1 staged from the still unnormalised X of tiles 3-4 | barrier
+            // | tiles 3-4 mixed.  mean / rstd of all rows come from the one ln_stats above.  All 5 token tiles run on
+            // v_mfma_f32_16x16x32_bf16 (pad rows read the clamped last row, their outputs are dropped), no ragged-row VALU path.
+            // Non-finite operands: Inf - Inf residuals are NaN, so an Inf in u or W' gives NaN (the fp32 MFMA may give Inf).
+            typedef std::integral_constant<int, 0> T0;
+            typedef std::integral_constant<int, kChunkTiles> T1;
+            typedef std::integral_constant<int, kNT> T2;
+            ln_store_split(T0{}, T1{});
+            __syncthreads();
+            stamp(6 + 8 * l);
+            chmix_split_chunk(l, T0{}, T1{});
+            stamp(7 + 8 * l);
+            __syncthreads();
+            ln_store_split(T1{}, T2{});
+            __syncthreads();
+            stamp(8 + 8 * l);
+            chmix_split_chunk(l, T1{}, T2{});
+        } else if constexpr (PREC == 1) {
             // ---- bf16x3 split precision: W'.u ~= hi_w.hi_u + hi_w.lo_u + lo_w.hi_u on v_mfma_f32_16x16x32_bf16 (fp32
             // accumulate; bf16 x bf16 products are exact in fp32; the dropped lo.lo term and the split residuals are
             // O(2^-16) relative).  These MFMAs run on the bf16 matrix cores, which do NOT share lanes with the fp32
@@ -663,10 +791,10 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
                 if (p == 0) stamp(7 + 8 * l);
             }
         } else if constexpr (PREC == 2) {
-            // ---- split-fp32: W'.u with both operands split exactly into three bf16 parts, a = a0 + a1 + a2 (round-to-nearest:
-            // |a1| <= 2^-8 |a|, |a2| <= 2^-16 |a|); every bf16 x bf16 product is exact in fp32.  The weight planes come split from the
-            // host (wch_hi / wch_lo / wch_lo2); the operand stays fp32 in LDS (its three planes would not fit) and each B fragment is
-            // split in registers after its ds_read (split3_bf16, 44 VALU per 8 values).  The terms kept (kSplitA / kSplitB,
+            // ---- split-fp32, -DLS_SPLIT_SHARED=0 (the earlier form, built for A/B only): the same arithmetic as above, but the operand
+            // stays fp32 in LDS, all R rows at once, and each B fragment is
+            // split in registers after its ds_read (split3_bf16, 44 VALU per 8 values) -- by every wave, for both p: 16 times per
+            // value.  The terms kept (kSplitA / kSplitB,
             // ls_step_common.h) are accumulated smallest first so hi.hi lands last.  All 5 token tiles run on v_mfma_f32_16x16x32_bf16 (pad rows read the clamped last row, their
             // outputs are dropped), no ragged-row VALU path: the bf16 MFMAs leave the fp32 lanes to the split.
             // Non-finite operands: Inf - Inf residuals are NaN, so an Inf in u or W' gives NaN (the fp32 MFMA may give Inf).

@@ -41,14 +41,19 @@ names = ["LN1 stats(+temb)", "LN1 store+bar", "token-mix", "LN2 stats", "LN2 sto
 print(f"{ds} B={B} path={PATH}: total cycles (wave mean) = {np.mean(st[:, 4 + 8 * L] - st[:, 0]):.0f}")
 print(f"  embed                : {np.mean(st[:, 1] - st[:, 0]):9.0f}")
 prev = st[:, 1].copy()
-acc = np.zeros(7)
+# the split-fp32 form that stages LN2 per 48-row chunk stamps point 8 too: 6 -> 7 = tiles 0-2 (both channel halves), 7 -> 8 = barrier +
+# store of chunk 1 + barrier, 8 -> 9 = tiles 3-4; every other form stamps 7 after its first channel half and never 8
+chunked = bool(st[:, 8].any())
+if chunked:
+    names = names[:5] + ["chunk 0 (tiles 0-2)", "bar+store 1+bar", "chunk 1 (tiles 3-4)"]
+pts = [2, 3, 4, 5, 6, 7, 8, 9] if chunked else [2, 3, 4, 5, 6, 7, 9]
+acc = np.zeros(len(pts))
 for l in range(L):
-    pts = [2, 3, 4, 5, 6, 7, 9]
     for i, pnt in enumerate(pts):
         cur = st[:, pnt + 8 * l]
         acc[i] += np.mean(cur - prev)
         prev = cur
-for i in range(7):
+for i in range(len(pts)):
     print(f"  {names[i]:21s}: {acc[i] / L:9.0f} /layer")
 print(f"  X->U + barrier       : {np.mean(st[:, 2 + 8 * L] - prev):9.0f}")
 print(f"  out-proj MFMA        : {np.mean(st[:, 3 + 8 * L] - st[:, 2 + 8 * L]):9.0f}")
@@ -59,4 +64,4 @@ if os.environ.get("LS_PROF_RAW"):
     base = st[:, 1 + 8 * l].min()
     print("per-wave stamps of layer 3 (cycles since earliest previous-layer end):")
     for wv in range(NWV):
-        print(f"  wave {wv}:", [int(st[wv, p + 8 * l] - base) for p in (1, 2, 3, 4, 5, 6, 7, 9)])
+        print(f"  wave {wv}:", [int(st[wv, p + 8 * l] - base) for p in [1] + pts])
