@@ -8,14 +8,17 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
         beat-consistency score against the onsets detected in the clips' audio on the device
 
     python examples/livelyspeaker_ted.py [batch]
-    python examples/livelyspeaker_ted.py [batch] --from-motion
+    python examples/livelyspeaker_ted.py [batch] --from-motion [--raw-poses]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N
     python examples/livelyspeaker_ted.py --long-seconds A,B,... [--drop-finished]
     python examples/livelyspeaker_ted.py [batch] --clip-text
 --clip-text starts from TOKENS instead of a stand-in feature: synthetic clip.tokenize output -> CLIPTextEncoder (the text tower of CLIP
 on the GPU, synthetic weights) -> text features -> SAG decoder -> the same refinement, with no host wait between the two engines.
 --from-motion edits a RECORDED clip instead: no text feature is needed, the SAG encoder turns the clip into the CLIP-aligned latent
-(recorded clip -> SAG(batch) = MOTIONCLIP.forward -> init_image -> the same 20-step refinement).
+(recorded clip -> SAG(batch) = MOTIONCLIP.forward -> init_image -> the same 20-step refinement).  With --raw-poses the clip starts as a
+RAW recording: joint positions at 25 fps and a waveform go through livelyspeaker_amd.ingest.ted_ingest (resampling to 15 fps, bone
+directions, the motion filter's verdicts, 34-frame windows and their 36 267 audio samples, all on the device) and its windows are the
+recorded clips and the audio condition.
 --long-seconds N synthesises N seconds of gesture for N seconds of speech in ONE call (livelyspeaker_amd.long_form.sample_long): the
 34-frame windows are chained on the device, each conditioned on the last four poses of the one before it, the SAG decoder's output for
 the window's text feature as its init_image, and stitched into one timeline, which long_form.score_timeline then turns into poses,
@@ -168,9 +171,14 @@ def main():
     from_motion = "--from-motion" in sys.argv
     if from_motion:
         sys.argv.remove("--from-motion")
+    raw_poses = "--raw-poses" in sys.argv
+    if raw_poses:
+        sys.argv.remove("--raw-poses")
+        if not from_motion:
+            raise SystemExit("--raw-poses goes with --from-motion: it is the recorded clip that is ingested")
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
     if from_motion:
-        return main_from_motion(B, noise_source)
+        return main_from_motion(B, noise_source, raw_poses)
     if len(sys.argv) > 2:                                                                   # python examples/livelyspeaker_ted.py B N: N batches, pipelined
         return main_pipelined(B, int(sys.argv[2]))
     cfg, model, diffusion, sag_decoder, evaluator = build()
@@ -196,10 +204,41 @@ def main():
     assert bool(torch.isfinite(sample).all())
 
 
-def main_from_motion(B, noise_source):
+def raw_recordings(B, device="cuda:0", seconds=6.0, raw_fps=25):
+    """Synthetic RAW recordings, as a motion-capture file and its sound track hold them: joint positions [n, 10, 3] at 25 fps (the
+    mean pose with swinging arms) and a 16 kHz waveform each, enough of them for B windows; and ingest.ted_ingest's arguments for them."""
+    import numpy as np
+    from livelyspeaker_amd.postprocess import TED_DIR_VEC_PAIRS, TED_MEAN_DIR_VEC
+    mean_pose = np.zeros((10, 3))
+    for j, (parent, child, length) in enumerate(TED_DIR_VEC_PAIRS):
+        mean_pose[child] = mean_pose[parent] + length * TED_MEAN_DIR_VEC[3 * j:3 * j + 3]
+    n = int(seconds * raw_fps)
+    per_recording = (int(seconds * 15) - 42) // 10 + 1                                      # windows of 42 resampled frames, stride 10
+    rng = np.random.Generator(np.random.PCG64(synth.SEED_COND + 6000))
+    skeletons, audio = [], []
+    for _ in range(-(-B // per_recording)):
+        t = np.linspace(0.0, seconds, n)[:, None, None]
+        pose = np.repeat(mean_pose[None], n, 0)
+        pose[:, 4:] += 0.1 * np.sin(2 * np.pi * rng.uniform(0.4, 1.0, (1, 6, 3)) * t + rng.uniform(0, 2 * np.pi, (1, 6, 3)))
+        skeletons.append(torch.from_numpy(pose.astype(np.float32)).to(device))
+        audio.append(torch.from_numpy((0.1 * rng.standard_normal(int(seconds * 16000))).astype(np.float32)).to(device))
+    return skeletons, audio, [0.0] * len(skeletons), [seconds] * len(skeletons), mean_pose.astype(np.float32), TED_MEAN_DIR_VEC
+
+
+def main_from_motion(B, noise_source, raw_poses=False):
     cfg, model, diffusion, _, _ = build()
     sag = build_sag()
     vec_seq, batch, cond = make_inputs(cfg, B)
+    if raw_poses:                                                                           # the recorded clip comes from RAW poses and audio
+        from livelyspeaker_amd.ingest import VERDICTS, ted_ingest
+        got = ted_ingest(*raw_recordings(B), disable_filtering=True)                        # resample 25 -> 15 fps, directions, windows, audio: on the device
+        verdicts = got["verdict"].cpu().numpy()
+        print(f"ingest: {len(verdicts)} windows from {int(got['clip'].max()) + 1} raw recordings at 25 fps; verdicts "
+              + ", ".join(f"{VERDICTS[v]} {int((verdicts == v).sum())}" for v in sorted(set(verdicts.tolist()))))
+        batch["x"] = got["x"][:B].contiguous()
+        cond["y"]["origin_x"] = batch["x"].clone()
+        cond["y"]["audio_input"] = got["audio"][:B].contiguous()
+        assert batch["x"].shape == vec_seq.shape and cond["y"]["audio_input"].shape == (B, 36267)
     lengths = torch.full((B,), 34, device=vec_seq.device)
     lengths[1::2] = 28                                                                      # every other recording is shorter
     batch = {"x": batch["x"], "mask": sag.lengths_to_mask(lengths)}                         # no text feature: z comes from the encoder

@@ -803,6 +803,119 @@ int ls_onsets_ragged(int device, const ls_onsets_args* a, const int32_t* lengths
 int ls_onsets_tables(float sr, int n_fft, int n_mels, float fmin, float fmax, float* window, float* twiddle, int32_t* mel_ptr,
                      int32_t* mel_col, float* mel_w, int32_t nnz_cap, int32_t* nnz_out);
 
+/* ---- dataset ingest: recorded poses and audio -> model inputs ----------------------------------------------
+ * The forward direction of the pose transforms above, as the reference's offline pipeline computes it: TED
+ * DataPreprocessor._sample_from_clip (scripts/data_loader/data_preprocessor.py:69-167) with resample_pose_seq,
+ * convert_pose_seq_to_dir_vec and make_audio_fixed_length (scripts/utils/data_utils.py:46-120), MotionPreprocessor
+ * (data_loader/motion_preprocessor.py) and the clipping of SpeechMotionDataset.__getitem__ (lmdb_data_loader.py:166-174); BEAT
+ * CustomDataset._sample_from_clip (scripts_beat/dataloaders/beat.py:365-485) and scripts_beat/data_libs/process_cache.py:38-45.
+ * A batch of recordings of different lengths goes in as concatenated arrays; every window comes out in the layouts the other entry
+ * points take.  The plan is host-only and exact (double); the kernels read nothing beyond a recording's own frames and samples. */
+#define LS_INGEST_PASS 0          /* verdicts, MotionPreprocessor's filtering_message */
+#define LS_INGEST_POSE 1          /* "pose": mean |pose - mean_pose| < 0.02                                   */
+#define LS_INGEST_SPINE 2         /* "spine angle": max > 30 degrees or mean > 20 degrees                     */
+#define LS_INGEST_MOTION 3        /* "motion": both wrist variances < 0.0014                                  */
+#define LS_INGEST_WORDS 4         /* fewer than two words in the window; the filter is then never evaluated   */
+#define LS_INGEST_MAX_POSES 64    /* n_poses at most                                                          */
+#define LS_INGEST_MAX_EXT 128     /* n_ext at most                                                            */
+#define LS_INGEST_N_STATS 5       /* pose difference, spine max, spine mean (degrees), left and right wrist variance */
+typedef struct ls_ingest_plan_args {
+    int32_t batch;
+    int32_t n_poses;            /* 34: frames of a sample                                                              */
+    int32_t n_ext;              /* frames of a window: int(round(n_poses * 1.25)) = 42 for TED, n_poses for BEAT       */
+    int32_t stride;             /* 10                                                                                  */
+    int32_t beat;               /* 0: the TED arithmetic, 1: BEAT's (no resampling; times are whole seconds)           */
+    int32_t frame_cap, window_cap; /* rows the frame and window arrays hold; 0 with NULL arrays asks for the counts alone */
+    int32_t n_frames, n_windows;   /* OUT: rows of the two tables                                                      */
+    int32_t reserved;
+    double fps;                 /* 15                                                                                  */
+    double sr;                  /* 16000                                                                               */
+    const int32_t* n_raw;       /* [B] raw frames of each recording (>= 2)                                             */
+    const double* start_time;   /* [B] seconds; BEAT: clip_s_t = clean_first_seconds                                   */
+    const double* end_time;     /* [B] seconds; BEAT: clip_e_t = round_seconds - clean_final_seconds                   */
+    const int64_t* audio_len;   /* [B] samples                                                                         */
+    const int64_t* word_offsets;/* [B + 1] or NULL: rows of word_times of each recording; NULL: every window has words */
+    const double* word_times;   /* [n_words][2] (start, end), sorted by start within a recording                       */
+    int32_t* frame_offsets;     /* OUT [B + 1]: first row of each recording's resampled frames                         */
+    int32_t* frame_clip;        /* OUT [n_frames]                                                                      */
+    int32_t* frame_lo;          /* OUT [n_frames] raw frame below, within the recording                                */
+    int32_t* frame_hi;          /* OUT [n_frames] lo + 1                                                               */
+    float* frame_frac;          /* OUT [n_frames] x_new - lo, rounded to float once; 1 at whole positions, > 1 in the extrapolated tail */
+    int32_t* window_offsets;    /* OUT [B + 1]                                                                         */
+    int32_t* win_clip;          /* OUT [n_windows]                                                                     */
+    int32_t* win_first;         /* OUT [n_windows] first frame within the recording (TED: resampled frames; BEAT: raw) */
+    int64_t* win_audio_start;   /* OUT [n_windows] first sample within the recording                                   */
+    int32_t* win_n_pad;         /* OUT [n_windows] samples np.pad(mode='symmetric') would append                       */
+    unsigned char* win_has_words; /* OUT [n_windows] get_words_in_time_range found at least 2                          */
+} ls_ingest_plan_args;
+/* TED: the frame table restates np.arange(0, n, n / (duration * fps)) (length ceil(n / step), values i * step) and interp1d(
+ * kind='linear', fill_value='extrapolate') (searchsorted left, clipped to [1, n - 1]); per recording floor((K - n_ext) / stride) + 1
+ * windows (none for K < n_ext), audio_start = floor(start_idx / K * L), window length int(n_ext / fps * sr).  BEAT: beat.py:364-372,
+ * 392-395.  Any OUT array may be NULL.  LS_EINVAL: a NULL input, batch < 1, n_poses outside [1, 64], n_ext outside [n_poses, 128],
+ * stride < 1, fps or sr <= 0, n_raw < 2, end_time <= start_time (TED), a BEAT clip beyond its recording, an empty audio, a padding longer than the audio itself, unsorted
+ * word offsets, a cap below the count when the arrays are given.  No device is touched. */
+int ls_ingest_plan(ls_ingest_plan_args* a);
+
+typedef struct ls_ted_ingest_args {
+    int32_t batch, on_device;
+    int32_t n_poses, n_ext;
+    int32_t n_frames, n_windows;   /* rows of the plan's tables                                                        */
+    int32_t audio_out_len;         /* int(round(n_poses / fps * sr)) = 36267                                           */
+    int32_t reserved;
+    const ls_post_config* cfg;     /* the bone table and mean_dir_vec; njoints 9 and n_pose_joints 10                  */
+    const float* mean_pose;        /* [30], host                                                                       */
+    /* the plan: host arrays in both modes */
+    const int32_t* n_raw;
+    const int64_t* audio_len;
+    const int32_t* frame_offsets;
+    const int32_t* frame_clip;
+    const int32_t* frame_lo;
+    const int32_t* frame_hi;
+    const float* frame_frac;
+    const int32_t* win_clip;
+    const int32_t* win_first;
+    const int64_t* win_audio_start;
+    const unsigned char* win_has_words;
+    /* the recordings, concatenated: device pointers iff on_device */
+    const float* raw_poses;        /* [sum n_raw][10][3]                                                               */
+    const float* audio;            /* [sum audio_len]                                                                  */
+    /* outputs, device pointers iff on_device; any may be NULL */
+    float* resampled;              /* [n_frames][30]                                                                   */
+    float* dir_vec;                /* [n_frames][27] unit bone directions                                              */
+    float* pose_seq;               /* [n_windows][n_poses][30]                                                         */
+    float* vec_seq;                /* [n_windows][n_poses][27] directions minus mean_dir_vec                           */
+    float* x;                      /* [n_windows][9][3][n_poses], the model's layout                                   */
+    float* audio_out;              /* [n_windows][audio_out_len]                                                       */
+    float* stats;                  /* [n_windows][LS_INGEST_N_STATS], over the window's n_ext frames                   */
+    int32_t* verdict;              /* [n_windows] LS_INGEST_*                                                          */
+} ls_ted_ingest_args;
+/* The tables are checked on the host before anything is launched (LS_EINVAL): every frame row and window must lie inside its
+ * recording, and the symmetric padding inside its audio.  n_windows == 0 or n_frames == 0 is legal. */
+int ls_ted_ingest(int device, const ls_ted_ingest_args* a);
+
+typedef struct ls_beat_ingest_args {
+    int32_t batch, on_device;
+    int32_t n_poses;               /* 1 .. 34                                                                          */
+    int32_t njoints;               /* 1 .. 47                                                                          */
+    int32_t n_windows;
+    int32_t audio_out_len;         /* floor(n_poses / fps * sr) = 36266                                                */
+    const float* mean_pose;        /* [njoints * 3] degrees, host                                                      */
+    const float* std_pose;         /* [njoints * 3], host                                                              */
+    const int32_t* n_raw;          /* host, like the window table                                                      */
+    const int64_t* audio_len;
+    const int32_t* win_clip;
+    const int32_t* win_first;
+    const int64_t* win_audio_start;
+    const unsigned char* win_has_words;  /* the caller's per-window byte: 0 gives LS_INGEST_WORDS; NULL keeps every window */
+    const float* poses;            /* [sum n_raw][njoints * 3] normalised Euler angles; device pointer iff on_device   */
+    const float* audio;            /* [sum audio_len]                                                                  */
+    float* rot6d;                  /* [n_windows][n_poses][njoints * 6]                                                */
+    float* x;                      /* [n_windows][njoints][6][n_poses]                                                 */
+    float* audio_out;              /* [n_windows][audio_out_len]                                                       */
+    int32_t* verdict;              /* [n_windows] LS_INGEST_PASS or LS_INGEST_WORDS                                    */
+} ls_beat_ingest_args;
+int ls_beat_ingest(int device, const ls_beat_ingest_args* a);
+
 /* ---- training step ----------------------------------------------------------------
  * One optimisation step of the RAG denoiser as TrainLoop.run_step runs it (scripts/train_utils/train_loop.py:146-186):
  *   x_t = q_sample(x_start, t, noise)                                  gaussian_diffusion.py:1281-1282

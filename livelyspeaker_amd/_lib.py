@@ -130,6 +130,28 @@ class LsTedAlignArgs(C.Structure):
         (n, C.c_void_p) for n in ("beat_mask", "onset_frames", "onset_count", "align_sum", "n_beats")]
 
 
+class LsIngestPlanArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("batch", "n_poses", "n_ext", "stride", "beat", "frame_cap", "window_cap", "n_frames",
+                                         "n_windows", "reserved")] + [("fps", C.c_double), ("sr", C.c_double)] + [
+        (n, C.c_void_p) for n in ("n_raw", "start_time", "end_time", "audio_len", "word_offsets", "word_times", "frame_offsets",
+                                  "frame_clip", "frame_lo", "frame_hi", "frame_frac", "window_offsets", "win_clip", "win_first",
+                                  "win_audio_start", "win_n_pad", "win_has_words")]
+
+
+class LsTedIngestArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("batch", "on_device", "n_poses", "n_ext", "n_frames", "n_windows", "audio_out_len",
+                                         "reserved")] + [("cfg", C.POINTER(LsPostConfig))] + [
+        (n, C.c_void_p) for n in ("mean_pose", "n_raw", "audio_len", "frame_offsets", "frame_clip", "frame_lo", "frame_hi",
+                                  "frame_frac", "win_clip", "win_first", "win_audio_start", "win_has_words", "raw_poses", "audio",
+                                  "resampled", "dir_vec", "pose_seq", "vec_seq", "x", "audio_out", "stats", "verdict")]
+
+
+class LsBeatIngestArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("batch", "on_device", "n_poses", "njoints", "n_windows", "audio_out_len")] + [
+        (n, C.c_void_p) for n in ("mean_pose", "std_pose", "n_raw", "audio_len", "win_clip", "win_first", "win_audio_start",
+                                  "win_has_words", "poses", "audio", "rot6d", "x", "audio_out", "verdict")]
+
+
 class LsTiming(C.Structure):
     _fields_ = [("prepare_ms", C.c_float), ("loop_ms", C.c_float), ("total_ms", C.c_float),
                 ("n_step_launches", C.c_int32), ("graph_replayed", C.c_int32), ("single_pass", C.c_int32),
@@ -166,6 +188,7 @@ EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set
            "ls_clip_text_encode", "ls_clip_text_encode_async", "ls_clip_text_last_encode_ms", "ls_clip_text_stream", "ls_clip_text_plan", "ls_ted_post", "ls_beat_post", "ls_beat_metrics", "ls_beat_ldiv", "ls_onsets", "ls_onsets_tables",
            "ls_ted_post_timeline", "ls_beat_post_timeline", "ls_beat_metrics_timeline", "ls_ted_beat_align",
            "ls_onsets_ragged", "ls_ted_post_timeline_ragged", "ls_beat_post_timeline_ragged", "ls_beat_metrics_timeline_ragged", "ls_ragged_tiles",
+           "ls_ingest_plan", "ls_ted_ingest", "ls_beat_ingest",
            "ls_train_create", "ls_train_destroy", "ls_train_last_error", "ls_train_set_schedule", "ls_train_param_count",
            "ls_train_flat_size", "ls_train_param_info", "ls_train_set_weight", "ls_train_get_weight", "ls_train_forward_backward",
            "ls_train_adamw", "ls_train_read", "ls_train_get_moment", "ls_train_set_moment", "ls_train_get_step", "ls_train_set_step",
@@ -299,6 +322,9 @@ def load_library(build_if_missing: bool = True):
     lib.ls_ragged_tiles.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     lib.ls_onsets_tables.argtypes = [C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+    lib.ls_ingest_plan.argtypes = [C.POINTER(LsIngestPlanArgs)]
+    lib.ls_ted_ingest.argtypes = [C.c_int, C.POINTER(LsTedIngestArgs)]
+    lib.ls_beat_ingest.argtypes = [C.c_int, C.POINTER(LsBeatIngestArgs)]
     lib.ls_train_set_schedule.argtypes = [C.c_void_p, c_f64p, c_f64p, c_i64p]
     lib.ls_train_param_count.argtypes = [C.c_void_p]
     lib.ls_train_flat_size.argtypes = [C.c_void_p]
