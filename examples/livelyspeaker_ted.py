@@ -11,6 +11,7 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py [batch] --from-motion [--raw-poses]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N
     python examples/livelyspeaker_ted.py --long-seconds A,B,... [--drop-finished]
+    python examples/livelyspeaker_ted.py [batch] --long-seconds N --edit-frames LO,HI [--edit-joints J0,J1,...]
     python examples/livelyspeaker_ted.py [batch] --clip-text
 --clip-text starts from TOKENS instead of a stand-in feature: synthetic clip.tokenize output -> CLIPTextEncoder (the text tower of CLIP
 on the GPU, synthetic weights) -> text features -> SAG decoder -> the same refinement, with no host wait between the two engines.
@@ -28,6 +29,9 @@ call each (sample_long(audio_lengths=) -> (timeline, frames) -> score_timeline(f
 frames and beats and the batch's beat-consistency score.  With --drop-finished a speech leaves the batch once its own audio has ended
 (sample_long(drop_finished=True)): window w runs only the speeches that still have audio, and the line printed first says how many
 clip-windows that saves.
+--edit-frames LO,HI (with --long-seconds N) then EDITS the timeline it has just made: the frames [LO, HI) -- with --edit-joints only
+the listed joints (0..8) -- are re-synthesised from the existing motion (long_form.edit_long: the inpainting branch on the windows the
+range touches, 20 refinement steps each), everything else is kept bit for bit, and the line printed says how many of the W windows ran.
 With real data: load RAG.pt / SAG.pth / the auto-encoder checkpoint with load_model_wo_clip / load_state_dict and build `cond`
 exactly as the reference script does; everything below the weight loading is unchanged.
 """
@@ -156,15 +160,30 @@ def main():
         i = sys.argv.index("--long-seconds")
         arg = sys.argv[i + 1]
         del sys.argv[i:i + 2]
+        edit = None
+        if "--edit-frames" in sys.argv:
+            j = sys.argv.index("--edit-frames")
+            edit = {"frames": tuple(int(v) for v in sys.argv[j + 1].split(","))}
+            del sys.argv[j:j + 2]
+            if len(edit["frames"]) != 2:
+                raise SystemExit("--edit-frames takes LO,HI")
+        if "--edit-joints" in sys.argv:
+            j = sys.argv.index("--edit-joints")
+            if edit is None:
+                raise SystemExit("--edit-joints goes with --edit-frames")
+            edit["joints"] = [int(v) for v in sys.argv[j + 1].split(",") if v]
+            del sys.argv[j:j + 2]
         drop = "--drop-finished" in sys.argv
         if drop:
             sys.argv.remove("--drop-finished")
+        if edit is not None and ("," in arg or drop):
+            raise SystemExit("--edit-frames edits the timeline of --long-seconds N (one duration; ragged batches are not edited)")
         if "," in arg:
             return main_long_ragged([float(v) for v in arg.split(",") if v], noise_source, drop)
         if drop:
             raise SystemExit("--drop-finished goes with a comma list of durations: equally long speeches finish together")
         seconds = float(arg)
-        return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source)
+        return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source, edit)
     if "--clip-text" in sys.argv:
         sys.argv.remove("--clip-text")
         return main_clip_text(int(sys.argv[1]) if len(sys.argv) > 1 else 64, noise_source)
@@ -283,7 +302,7 @@ def main_clip_text(B, noise_source):
     assert bool(torch.isfinite(sample).all()) and bool(torch.isfinite(decoded).all())
 
 
-def main_long(B, seconds, noise_source):
+def main_long(B, seconds, noise_source, edit=None):
     """`seconds` of 16 kHz speech per clip -> one stitched timeline at 15 fps (the LivelySpeaker chain, window after window on the device)."""
     import numpy as np
     from livelyspeaker_amd import long_form
@@ -313,6 +332,31 @@ def main_long(B, seconds, noise_source):
     print(f"pose {tuple(scored['pose'].shape)}, motion beats {n_beats}, BC {scored['bc']:.4f} (synthetic weights and audio: numbers are "
           f"not quality)")
     assert tuple(scored["pose"].shape) == (B, n_frames, 10, 3) and bool(torch.isfinite(scored["pose"]).all())
+    if edit is not None:
+        edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit)
+
+
+def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit):
+    """Re-synthesise the frames [lo, hi) of the timeline main_long made (on the listed joints, or all): only the windows that own a
+    frame of the range are sampled, starting from the existing motion."""
+    import numpy as np
+    lo, hi = edit["frames"]
+    joints = None
+    if edit.get("joints"):
+        joints = np.zeros(cfg.njoints, bool)
+        joints[edit["joints"]] = True
+    torch.manual_seed(377)
+    t0 = time.perf_counter()
+    edited, ran, _ = long_form.edit_long(diffusion, model, timeline, (lo, hi), audio, y["seed_poses"], y["vid_indices"], y["scale"],
+                                         joints=joints, sampler="ddim", skip_timesteps=80, return_windows=True)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    kept = torch.ones_like(timeline, dtype=torch.bool)
+    kept[:, :, :, lo:hi] = False if joints is None else torch.from_numpy(~joints).to(kept.device)[None, :, None, None]
+    assert torch.equal(edited[kept], timeline[kept]) and bool(torch.isfinite(edited).all())
+    changed = int((edited != timeline).sum())
+    print(f"edit of frames [{lo}, {hi}){'' if joints is None else ' on joints ' + str(edit['joints'])}: {len(ran)} of {W} windows ran "
+          f"({ran}) in {dt * 1e3:.1f} ms; {changed} of {timeline.numel()} values changed, every other one kept bit for bit")
 
 
 def main_long_ragged(seconds, noise_source, drop_finished=False):

@@ -377,6 +377,51 @@ typedef struct ls_long_sample_args {
     float* windows;             /* [W, B, J, F, T] the raw windows, or NULL                                           */
 } ls_long_sample_args;
 int ls_long_sample(ls_handle* h, const ls_long_sample_args* a);
+
+/* ---- Edit a stretch of a long-form timeline: masked re-synthesis of the windows it touches (ls_long_edit, after ls_long_prepare with
+ * the conditioning of the call that made the timeline).  With S = T - n_pre_seq, window w covers the timeline frames [w S, w S + T) and
+ * OWNS [0, T) for w = 0, [w S + n_pre_seq, w S + T) otherwise (the stitching of ls_long_sample).  Element (b, c, f) of window w is
+ * EDITABLE iff channels[b][c] is set, frame_lo[b] <= w S + f < frame_hi[b], and frame w S + f is owned by w.  The windows with at least
+ * one editable element of at least one clip run, in ascending order, all B clips each (ls_long_edit_plan is that set; no handle, no
+ * GPU): the window's T frames are read from the timeline as it stands by then; they are ls_sample's inpainted_motion, with
+ * inpaint_mask = not editable, its first n_pre_seq frames condition the window as origin_x (window 0: the prepared seed_poses), and with
+ * skip_timesteps > 0 they are its init_image as well; the loop is ls_sample's (two launches per step, see inpaint_mask there); the
+ * editable elements of its result are stored into the timeline and nothing else of the timeline is written.  A window behind the last
+ * one that ran is not resampled even where its conditioning frames changed (widen the range to have it resampled), and a clip whose
+ * range misses a running window runs in it with every element kept.
+ * Not built: handles of ls_long_prepare_ragged, a SAG decoder, PLMS, const_noise, dump_steps, encoding only the edited windows' audio. */
+typedef struct ls_long_edit_args {
+    int32_t sampler;            /* LS_SAMPLER_DDPM | LS_SAMPLER_DDIM                                                  */
+    int32_t noise_mode;         /* LS_NOISE_TAPE | LS_NOISE_PHILOX                                                    */
+    int32_t skip_timesteps;
+    int32_t on_device;          /* timeline, windows and the tapes are device pointers                                */
+    int32_t use_graph;
+    int32_t clip_denoised;
+    int32_t two_pass_always;
+    float eta;
+    int32_t inpaint_noised;     /* the given motion is re-noised with q_sample(., t - 1) while t > 0 (the TED tree)   */
+    int32_t windows_capacity;   /* entries of windows_run (0 with NULL)                                               */
+    const int32_t* frame_lo;    /* HOST [B]: clip b is edited on the frames [frame_lo[b], frame_hi[b]), 0 <= lo <= hi <= T_total */
+    const int32_t* frame_hi;    /* HOST [B]; lo == hi: the clip is not edited                                         */
+    const unsigned char* channels; /* HOST bytes [B, J*F] (non-zero = the channel is edited), or NULL: every channel  */
+    float* timeline;            /* [B, J, F, T + (W - 1) S], edited in place (a host one: uploaded, edited, downloaded) */
+    float* windows;             /* [We, B, J, F, T] the raw samples of the We windows that ran, or NULL               */
+    int32_t* windows_run;       /* HOST, nullable: the first min(We, windows_capacity) windows that ran, ascending    */
+    int32_t* n_windows_run;     /* HOST, nullable: We                                                                  */
+    /* TAPE: the draws of the We windows that ran, in ascending window order */
+    const float* x_init;        /* [We, B, J, F, T]                                                                   */
+    const float* eps_tape;      /* [We, n_exec, 2, B, latent_dim]                                                     */
+    const float* noise_tape;    /* [We, n_exec, B, J, F, T]                                                           */
+    const float* inpaint_noise; /* [We, n_exec, B, J, F, T] with inpaint_noised                                       */
+    uint64_t seed;              /* PHILOX: one key per call                                                           */
+    uint64_t sample_offset;     /* PHILOX: window w draws at sample_offset + b + (w << 48), as in ls_long_sample: a window's
+                                   streams do not depend on which other windows run                                   */
+} ls_long_edit_args;
+/* window_flags [n_windows] (nullable): 1 where the window runs; *n_out: how many do.  LS_EINVAL on a range outside [0, T + (W - 1) S]
+ * or with lo > hi. */
+int ls_long_edit_plan(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const int32_t* lo, const int32_t* hi,
+                      int32_t* window_flags, int32_t* n_out);
+int ls_long_edit(ls_handle* h, const ls_long_edit_args* a);
 int ls_step(ls_handle* h, const ls_step_args* a);
 int ls_plms_step(ls_handle* h, const ls_plms_step_args* a);
 /* elementwise q_sample (gaussian_diffusion.py:240-258) at schedule index i; pointers per on_device */

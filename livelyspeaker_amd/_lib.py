@@ -63,6 +63,15 @@ class LsLongSampleArgs(C.Structure):
         ("sample_offset", C.c_uint64), ("sag", C.c_void_p), ("text_features", C.c_void_p), ("timeline", C.c_void_p), ("windows", C.c_void_p)]
 
 
+class LsLongEditArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sampler", "noise_mode", "skip_timesteps", "on_device", "use_graph", "clip_denoised",
+                                         "two_pass_always")] + [
+        ("eta", C.c_float), ("inpaint_noised", C.c_int32), ("windows_capacity", C.c_int32), ("frame_lo", c_i32p), ("frame_hi", c_i32p),
+        ("channels", C.c_void_p), ("timeline", C.c_void_p), ("windows", C.c_void_p), ("windows_run", c_i32p), ("n_windows_run", c_i32p),
+        ("x_init", C.c_void_p), ("eps_tape", C.c_void_p), ("noise_tape", C.c_void_p), ("inpaint_noise", C.c_void_p),
+        ("seed", C.c_uint64), ("sample_offset", C.c_uint64)]
+
+
 class LsForwardArgs(C.Structure):
     _fields_ = [("on_device", C.c_int32), ("no_sync", C.c_int32), ("x", C.c_void_p), ("timesteps", C.c_void_p),
                 ("eps_cond", C.c_void_p), ("eps_uncond", C.c_void_p), ("out_cond", C.c_void_p),
@@ -179,7 +188,7 @@ class LsEvalConfig(C.Structure):
 
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
-           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
+           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
@@ -253,6 +262,8 @@ def load_library(build_if_missing: bool = True):
     lib.ls_long_sample.argtypes = [C.c_void_p, C.POINTER(LsLongSampleArgs)]
     lib.ls_long_prepare_ragged.argtypes = [C.c_void_p, C.POINTER(LsLongCond), C.c_void_p]
     lib.ls_long_plan_drop.argtypes = [C.c_int32, C.c_int32, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_int32, c_i32p]
+    lib.ls_long_edit.argtypes = [C.c_void_p, C.POINTER(LsLongEditArgs)]
+    lib.ls_long_edit_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p, c_i32p, c_i32p]
     lib.ls_forward.argtypes = [C.c_void_p, C.POINTER(LsForwardArgs)]
     lib.ls_step.argtypes = [C.c_void_p, C.POINTER(LsStepArgs)]
     lib.ls_plms_step.argtypes = [C.c_void_p, C.POINTER(LsPlmsStepArgs)]
@@ -493,6 +504,21 @@ def long_plan_drop(audio_lengths, audio_len):
     if lib.ls_long_plan_drop(B, int(audio_len), lens.ctypes.data_as(C.c_void_p), None, None, ptr(active), int(nw.value), C.byref(nw)) != 0:
         raise EngineError("ls_long_plan_drop failed")
     return row, wins, active
+
+
+def long_edit_plan(lo, hi, n_windows, n_frames=34, n_pre=4):
+    """ls_long_edit_plan (no GPU needed): the windows a timeline edit of the per-clip frame ranges [lo[b], hi[b]) runs, ascending, as a
+    list.  A range outside the timeline or with lo > hi raises ``ValueError``."""
+    lib = load_library()
+    lo = np.ascontiguousarray(np.asarray(lo).reshape(-1), dtype=np.int32)
+    hi = np.ascontiguousarray(np.asarray(hi).reshape(-1), dtype=np.int32)
+    W = int(n_windows)
+    flags, n = np.zeros(max(W, 1), np.int32), C.c_int32()
+    ptr = lambda a: a.ctypes.data_as(c_i32p)      # noqa: E731
+    if lo.shape != hi.shape or lib.ls_long_edit_plan(int(lo.size), W, int(n_frames), int(n_pre), ptr(lo), ptr(hi), ptr(flags), C.byref(n)) != 0:
+        raise ValueError(f"frame ranges must hold one 0 <= lo <= hi <= {int(n_frames) + (W - 1) * (int(n_frames) - int(n_pre))} per clip, "
+                         f"got lo {lo.tolist()} hi {hi.tolist()} for {W} windows")
+    return [w for w in range(W) if flags[w]]
 
 
 def plan_coop_slices(groups, dataset="ted", n_cus=256):
@@ -849,6 +875,72 @@ class Engine(_Handle):
         m.ready()
         self._check(self.lib.ls_long_sample(self.h, C.byref(a)), "ls_long_sample")
         return (timeline, windows) if return_windows else timeline
+
+    def long_edit(self, timeline, frame_lo, frame_hi, channels=None, sampler=LS_SAMPLER_DDIM, x_init=None, eps_tape=None, noise_tape=None,
+                  inpaint_noise=None, inpaint_noised=False, skip_timesteps=0, eta=0.0, philox_seed=None, sample_offset=0, use_graph=True,
+                  clip_denoised=False, two_pass_always=False, device_out=False, return_windows=False):
+        """Re-synthesise the frames [frame_lo[b], frame_hi[b]) (host int [B]) of ``timeline`` [B, J, F, T + (W-1)(T-n_pre)] on the
+        channels ``channels`` (host bytes [B, J*F]; None = all) with the conditioning of the last ``long_prepare`` (ls_long_edit): only
+        the windows of ``long_edit_plan`` run, everything else is kept bit for bit.  TAPE mode takes the draws of those We windows,
+        ascending: ``x_init`` [We, B, J, F, T], ``eps_tape`` [We, n_exec, 2, B, D], ``noise_tape`` and (``inpaint_noised``)
+        ``inpaint_noise`` [We, n_exec, B, J, F, T]; PHILOX mode ``philox_seed``.  Returns (a new timeline, the windows that ran) and, with
+        ``return_windows``, their raw samples [We, B, J, F, T]; the caller's timeline is not written."""
+        B, W, D = self.batch, self.n_windows, self.D
+        npre = int(self.cfg.n_pre_seq)
+        n_frames = self.T + (W - 1) * (self.T - npre)
+        lo = np.ascontiguousarray(np.asarray(frame_lo).reshape(-1), dtype=np.int32)
+        hi = np.ascontiguousarray(np.asarray(frame_hi).reshape(-1), dtype=np.int32)
+        assert lo.shape == hi.shape == (B,), (lo.shape, hi.shape, B)
+        ch = None
+        if channels is not None:
+            ch = np.ascontiguousarray(np.asarray(channels).reshape(B, self.J * self.F) != 0, dtype=np.uint8)
+        try:        # a clip without a selected channel is not edited; what the plan cannot take is the engine's to refuse
+            plan = long_edit_plan(lo, np.where(ch.any(axis=1), hi, lo) if ch is not None else hi, W, self.T, npre)
+        except ValueError:
+            plan = []
+        We = len(plan)
+        members = [timeline, x_init, eps_tape, noise_tape, inpaint_noise]
+        if device_out:
+            import torch
+            members.append(torch.empty(1, device=torch.device("cuda", self.device)))
+        m = _Marshal(self.device, *members, stream=self._stream)
+        n_exec = self.n_steps - skip_timesteps
+        a = LsLongEditArgs()
+        a.sampler, a.skip_timesteps, a.on_device, a.use_graph = int(sampler), int(skip_timesteps), int(m.on_device), int(bool(use_graph))
+        a.clip_denoised, a.two_pass_always, a.eta = int(bool(clip_denoised)), int(bool(two_pass_always)), float(eta)
+        a.inpaint_noised = int(bool(inpaint_noised))
+        a.frame_lo, a.frame_hi = lo.ctypes.data_as(c_i32p), hi.ctypes.data_as(c_i32p)
+        if ch is not None:
+            a.channels = ch.ctypes.data_as(C.c_void_p)
+        if philox_seed is None:
+            a.noise_mode = LS_NOISE_TAPE
+            a.x_init = m.f32(x_init, (We,) + self._xshape())
+            a.eps_tape = m.f32(eps_tape, (We, n_exec, 2, B, D))
+            a.noise_tape = m.f32(noise_tape, (We, n_exec) + self._xshape())
+            if inpaint_noised:
+                a.inpaint_noise = m.f32(inpaint_noise, (We, n_exec) + self._xshape())
+        else:
+            a.noise_mode = LS_NOISE_PHILOX
+            a.seed, a.sample_offset = int(philox_seed), int(sample_offset)
+        shape = (B, self.J, self.F, n_frames)
+        assert tuple(int(s) for s in timeline.shape) == shape, (tuple(timeline.shape), shape)
+        if m.on_device:         # a copy of the caller's timeline: the engine edits it in place
+            out = m.torch.empty(shape, dtype=m.torch.float32, device=m.dev)
+            out.copy_(m.torch.as_tensor(timeline))
+            a.timeline = C.c_void_p(out.data_ptr())
+        else:
+            out = np.array(timeline.detach().cpu().numpy() if hasattr(timeline, "detach") else timeline, dtype=np.float32, order="C", copy=True)
+            a.timeline = out.ctypes.data_as(C.c_void_p)
+        windows = None
+        if return_windows and We:
+            windows, a.windows = m.out((We,) + self._xshape())
+        ran, n_ran = np.full(max(W, 1), -1, np.int32), C.c_int32(0)
+        a.windows_run, a.windows_capacity, a.n_windows_run = ran.ctypes.data_as(c_i32p), W, C.pointer(n_ran)
+        m.ready()
+        self._check(self.lib.ls_long_edit(self.h, C.byref(a)), "ls_long_edit")
+        ran = [int(w) for w in ran[:int(n_ran.value)]]
+        assert ran == plan, (ran, plan)
+        return (out, ran, windows) if return_windows else (out, ran)
 
     def q_sample(self, index, x_start, noise):
         m = _Marshal(self.device, x_start, noise, stream=self._stream)

@@ -10,6 +10,9 @@
 // through LDS once (row stride JF | 1: odd, the transposed reads touch every bank once) and every global store runs along the frame axis.
 // Algorithmic bytes per clip (fp32): read T*JF (window 0: n_pre*JF seed poses), write n_pre*(KPP + JF) + (T - n_pre)*JF (+ T*JF raw
 // window; window 0 writes all T frames): 7.9 KB TED, 81 KB BEAT.
+// k_edit_gather / k_edit_scatter (further down) are the same cut and stitch for a timeline EDIT (ls_long_edit): a window's frames leave
+// the timeline as the loop's inpainting inputs and its editable elements return.  Algorithmic bytes per clip (fp32): gather 15.7 KB TED,
+// 163 KB BEAT (with the init plane); scatter at most 11.0 KB TED, 115 KB BEAT (with the raw window); the terms are spelled out at the kernels.
 #include "ls_internal.h"
 
 namespace ls {
@@ -59,6 +62,95 @@ hipError_t launch_chain_window(const ChainArgs& a, int B, hipStream_t st) {
     if (lds > 64 * 1024 || a.n_pre > a.T || a.f0 < 0 || a.f0 > a.T || a.t_off < 0 || a.t_off + (a.T - a.f0) > a.T_total) return hipErrorInvalidValue;
     if (B < 1 || (a.row && (a.n_next < 0 || a.n_next > B))) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_chain_window, dim3(B), dim3(256), lds, st, a);
+    return hipGetLastError();
+}
+
+// One window of a timeline edit (ls_long_edit, ls_sample.cpp; EditArgs in ls_internal.h): the loop's inpainting inputs are cut out of the
+// timeline on the device and its result goes back the same way, so a window costs two launches beside its loop and no host round trip.
+// Stream order makes the next window's gather see this window's scatter.  One workgroup per clip, the tile of k_chain_window (row stride
+// JF | 1); the timeline, the init plane and the raw window are walked along the frame axis, the internal-layout planes along the channels,
+// the seed poses along their n_pre axis (window 0 stages them in n_pre more tile rows).  No atomics: every element has one writer.
+// Algorithmic bytes per clip (fp32), k_edit_gather: read T*JF (+ n_pre*JF seed poses in window 0) + JF channel bytes + 8, write 2*T*JF
+// (motion, mask) + n_pre*(KPP + JF) (+ T*JF init plane with skip_timesteps > 0): 15.7 KB TED, 163 KB BEAT with the init plane.
+// k_edit_scatter: read T*JF + JF bytes + 8, write the editable elements (at most (T - n_pre)*JF, window 0: T*JF) (+ T*JF raw window): at
+// most 11.0 KB TED, 115 KB BEAT.
+__device__ __forceinline__ bool edit_editable(const EditArgs& a, int lo, int hi, bool chan, int f) {
+    const int t = a.w * (a.T - a.n_pre) + f;
+    return chan && t >= lo && t < hi && (a.w == 0 || f >= a.n_pre);
+}
+
+__global__ __launch_bounds__(256) void k_edit_gather(const EditArgs a) {
+    extern __shared__ float tile[];                 // [T (+ n_pre in window 0)][JF | 1]
+    const int b = blockIdx.x, tid = threadIdx.x, JF = a.JF, T = a.T, ld = JF | 1, npre = a.n_pre;
+    const float* tl = a.timeline + (size_t)b * JF * a.T_total + a.w * (T - npre);
+    float* init = a.init ? a.init + (size_t)b * JF * T : nullptr;
+    for (int i = tid; i < JF * T; i += 256) {
+        const int c = i / T, f = i - c * T;
+        const float v = tl[(size_t)c * a.T_total + f];
+        tile[f * ld + c] = v;
+        if (init) init[i] = v;
+    }
+    const float* pre = tile;                        // prefix pose j of channel c: pre[j * ld + c]; the slice's own first frames, or the seed poses
+    if (a.w == 0) {
+        float* sp = tile + T * ld;
+        const float* seed = a.seed + (size_t)b * JF * npre;
+        for (int i = tid; i < JF * npre; i += 256) sp[(i % npre) * ld + i / npre] = seed[i];
+        pre = sp;
+    }
+    __syncthreads();
+    const int lo = a.range[2 * b], hi = a.range[2 * b + 1];
+    const unsigned char* ch = a.chan + (size_t)b * JF;
+    float* mo = a.motion + (size_t)b * T * JF;
+    float* mk = a.maskf + (size_t)b * T * JF;
+    for (int i = tid; i < T * JF; i += 256) {
+        const int f = i / JF, c = i - f * JF;
+        mo[i] = tile[f * ld + c];
+        mk[i] = edit_editable(a, lo, hi, ch[c] != 0, f) ? 0.f : 1.f;      // inpainting_mask: true = keep the given motion
+    }
+    float* fu = a.feat_u + (size_t)b * T * a.KPP;
+    for (int i = tid; i < npre * a.KPP; i += 256) {
+        const int j = i / a.KPP, c = i - j * a.KPP;
+        fu[i] = c < JF ? pre[j * ld + c] : c == JF ? 1.f : 0.f;
+    }
+    float* ox = a.origin_x + (size_t)b * JF * T;
+    for (int i = tid; i < JF * npre; i += 256) {
+        const int c = i / npre, j = i - c * npre;
+        ox[(size_t)c * T + j] = pre[j * ld + c];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_edit_scatter(const EditArgs a) {
+    extern __shared__ float tile[];                 // [T][JF | 1]
+    const int b = blockIdx.x, tid = threadIdx.x, JF = a.JF, T = a.T, ld = JF | 1;
+    const float* src = a.sample + (size_t)b * T * JF;
+    for (int i = tid; i < T * JF; i += 256) tile[(i / JF) * ld + i % JF] = src[i];
+    __syncthreads();
+    const int lo = a.range[2 * b], hi = a.range[2 * b + 1];
+    const unsigned char* ch = a.chan + (size_t)b * JF;
+    float* tl = a.timeline + (size_t)b * JF * a.T_total + a.w * (T - a.n_pre);
+    float* wd = a.window ? a.window + (size_t)b * JF * T : nullptr;
+    for (int i = tid; i < JF * T; i += 256) {
+        const int c = i / T, f = i - c * T;
+        const float v = tile[f * ld + c];
+        if (wd) wd[i] = v;
+        if (edit_editable(a, lo, hi, ch[c] != 0, f)) tl[(size_t)c * a.T_total + f] = v;
+    }
+}
+
+static bool edit_args_ok(const EditArgs& a, int B, int rows) {
+    const size_t lds = (size_t)rows * (a.JF | 1) * sizeof(float);
+    return B >= 1 && lds <= 64 * 1024 && a.n_pre >= 1 && a.n_pre <= a.T && a.w >= 0 && (long long)a.w * (a.T - a.n_pre) + a.T <= a.T_total &&
+           a.timeline && a.range && a.chan;
+}
+hipError_t launch_edit_gather(const EditArgs& a, int B, hipStream_t st) {
+    const int rows = a.T + (a.w == 0 ? a.n_pre : 0);
+    if (!edit_args_ok(a, B, rows) || a.KPP <= a.JF || !a.motion || !a.maskf || !a.feat_u || !a.origin_x || (a.w == 0 && !a.seed)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_edit_gather, dim3(B), dim3(256), (size_t)rows * (a.JF | 1) * sizeof(float), st, a);
+    return hipGetLastError();
+}
+hipError_t launch_edit_scatter(const EditArgs& a, int B, hipStream_t st) {
+    if (!edit_args_ok(a, B, a.T) || !a.sample) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_edit_scatter, dim3(B), dim3(256), (size_t)a.T * (a.JF | 1) * sizeof(float), st, a);
     return hipGetLastError();
 }
 

@@ -318,6 +318,20 @@ struct ChainArgs {
     const int* row; int n_next;
 };
 hipError_t launch_chain_window(const ChainArgs& a, int B, hipStream_t st);
+// ---- one window of a timeline edit (ls_long_edit; ls_chain.hip): one workgroup per clip.  Element (c, f) of window w is editable iff
+// chan[b][c] != 0, range[2b] <= w * (T - n_pre) + f < range[2b + 1], and w == 0 or f >= n_pre.  launch_edit_gather reads the T frames
+// of timeline [B][JF][T_total] from frame w * (T - n_pre) and writes what the loop reads: motion and maskf (1 = keep) in the internal
+// layout [B][T][JF], the prefix rows of feat_u / prefix columns of origin_x (w == 0: from seed [B][JF][n_pre]), and the slice itself in
+// the reference layout [B][JF][T] to init (nullable).  launch_edit_scatter stores the editable elements of `sample` (internal layout)
+// into the timeline and the whole sample to window [B][JF][T] (nullable).
+struct EditArgs {
+    float* timeline; const float* seed; const int* range; const unsigned char* chan;
+    float* motion; float* maskf; float* feat_u; float* origin_x; float* init;      // gather
+    const float* sample; float* window;                                             // scatter
+    int JF, T, KPP, n_pre, T_total, w;
+};
+hipError_t launch_edit_gather(const EditArgs& a, int B, hipStream_t st);
+hipError_t launch_edit_scatter(const EditArgs& a, int B, hipStream_t st);
 // One encoder chunk of a ragged long-form call: clips[p][i] = audio[row][w * stride + i] for the n (row, w) pairs of `table`, 0 where
 // that sample index is >= lengths[row] (nothing beyond a clip's length is read).  audio [.][L], clips [n][AL].
 hipError_t launch_long_gather_clips(const float* audio, const int* table, const int* lengths, float* clips, int n, int AL, long long L,

@@ -1,6 +1,6 @@
 // Host side of the C-ABI declared in include/ls_hip.h: everything that runs diffusion steps.  The sampling loop exists once (begin_loop ->
 // enqueue_loop | enqueue_plms -> finish_loop; stream launches or a captured hipGraph; draws from whole-call tapes, segmented tapes, Philox or
-// torch's GPU stream), next to the single-step entries that enqueue the same launches on caller-held tensors (ls_forward, ls_step, ls_plms_step),
+// torch's GPU stream; per window of a long-form call or of a timeline edit: ls_long_sample, ls_long_edit), next to the single-step entries that enqueue the same launches on caller-held tensors (ls_forward, ls_step, ls_plms_step),
 // and the likelihood loop (ls_bpd: per schedule index q_sample, the denoiser alone and k_vb_terms, through the same capture-or-enqueue) with ls_vb_terms.
 #include "ls_handle.h"
 
@@ -62,6 +62,15 @@ void fill_sampler(ls_handle* h, StepArgs& a, int sampler, int i, float eta) {
 }
 
 // p_mean_variance's inpainting inputs (gaussian_diffusion.py:314-320) -> device, mask and motion in the internal [B][T][JF] layout
+// The first half: the two planes the update kernel reads, and the re-noise tape.  It is all of the staging when the planes are filled on
+// the device (ls_long_edit: k_edit_gather wrote them ahead of the loop).
+int stage_inpaint_planes(ls_handle* h, const float* noise, size_t noise_elems, int on_device) {
+    const size_t nx = (size_t)h->B * h->JF * h->T * sizeof(float);
+    int rc;
+    if ((rc = ensure_pinned(h, h->inp_maskf, nx)) != LS_OK || (rc = ensure_pinned(h, h->inp_motion, nx)) != LS_OK) return rc;
+    if (noise && (rc = ingest_pinned(h, h->inp_tape, noise, noise_elems * sizeof(float), on_device)) != LS_OK) return rc;
+    return LS_OK;
+}
 int stage_inpainting(ls_handle* h, const unsigned char* mask, const float* motion, const float* noise, size_t noise_elems, int on_device) {
     const int B = h->B, JF = h->JF;
     const size_t nelem = (size_t)B * JF * h->T, nx = nelem * sizeof(float);
@@ -69,12 +78,10 @@ int stage_inpainting(ls_handle* h, const unsigned char* mask, const float* motio
     int rc;
     if ((rc = ingest_pinned(h, h->inp_m8, mask, nelem, on_device)) != LS_OK) return rc;
     HIPCHK(h, h->xtmp.ensure(nx)); HIPCHK(h, h->xio.ensure(nx));
-    if ((rc = ensure_pinned(h, h->inp_maskf, nx)) != LS_OK || (rc = ensure_pinned(h, h->inp_motion, nx)) != LS_OK) return rc;
+    if ((rc = stage_inpaint_planes(h, noise, noise_elems, on_device)) != LS_OK) return rc;
     HIPCHK(h, launch_bytes_to_float(static_cast<const unsigned char*>(h->inp_m8.p), h->xio.f(), nelem, st));
     HIPCHK(h, launch_to_internal(h->xio.f(), h->inp_maskf.f(), B, JF, st, h->T));
-    if ((rc = ingest_internal(h, motion, h->inp_motion.f(), B, on_device)) != LS_OK) return rc;
-    if (noise && (rc = ingest_pinned(h, h->inp_tape, noise, noise_elems * sizeof(float), on_device)) != LS_OK) return rc;
-    return LS_OK;
+    return ingest_internal(h, motion, h->inp_motion.f(), B, on_device);
 }
 
 // LS_SAMPLER_PLMS: the planes of plms_buf (stride in floats through *stride); a captured loop holds their addresses
@@ -138,6 +145,7 @@ struct LoopCall {
     int B, n_exec;                  // n_exec executed steps: ordinal k = 0 .. n_exec - 1 runs schedule index n_exec - 1 - k
     size_t nelem;                   // elements of one x plane
     bool pair, tape, tdev, plms, inpaint, inp_noised;
+    bool inp_resident;              // the inpainting planes were filled on the device ahead of the loop (ls_long_edit): no mask / motion to ingest
     int ring_k;                     // TORCH_DEVICE: steps per ring refill
     size_t plms_stride;             // PLMS: floats between the planes of plms_buf
     TorchDrawArgs tda;              // TORCH_DEVICE: the per-step draws (stage_loop_inputs), and what x_T's draw shares with them
@@ -349,10 +357,12 @@ int stage_loop_inputs(ls_handle* h, LoopCall& c) {
     }
     if (c.plms && (rc = plms_planes(h, nelem, &c.plms_stride)) != LS_OK) return rc;
     if (c.inpaint) {
-        if (!a->inpainted_motion) return fail(h, LS_EINVAL, "inpaint_mask without inpainted_motion");
+        if (!c.inp_resident && !a->inpainted_motion) return fail(h, LS_EINVAL, "inpaint_mask without inpainted_motion");
         if (c.tape && c.inp_noised && !a->inpaint_noise) return fail(h, LS_EINVAL, "TAPE mode with inpaint_noised needs inpaint_noise");
-        if ((rc = stage_inpainting(h, a->inpaint_mask, a->inpainted_motion, (c.tape && c.inp_noised) ? a->inpaint_noise : nullptr,
-                                   (size_t)c.n_exec * nelem, od)) != LS_OK) return rc;
+        const float* inz = (c.tape && c.inp_noised) ? a->inpaint_noise : nullptr;
+        rc = c.inp_resident ? stage_inpaint_planes(h, inz, (size_t)c.n_exec * nelem, od)
+                            : stage_inpainting(h, a->inpaint_mask, a->inpainted_motion, inz, (size_t)c.n_exec * nelem, od);
+        if (rc != LS_OK) return rc;
     }
     if ((c.plms || c.inpaint) && (rc = ensure_pinned(h, h->fwd_cfg, nx)) != LS_OK) return rc;      // the denoiser alone leaves the model output here
     if (c.tdev) {
@@ -916,6 +926,154 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
     h->timing.graph_replayed = replays;          // windows served by a replay: W - 1 after a capture, W on a warm handle
     h->timing.tape_upload_ms = 0.f;
     h->timing.n_segments = W;
+    return LS_OK;
+}
+
+// The windows a timeline edit runs (ls_long_edit_args in ls_hip.h): window w owns the frames [w S + n_pre, w S + T) ([0, T) for w = 0) and
+// runs when the range of some clip meets them.  Host only; the single definition for ls_long_edit and for Python.
+int ls_long_edit_plan(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const int32_t* lo, const int32_t* hi, int32_t* window_flags,
+                      int32_t* n_out) {
+    if (batch < 1 || n_windows < 1 || n_pre < 1 || T <= n_pre || !lo || !hi || !n_out) return LS_EINVAL;
+    const long long S = T - n_pre, Tt = T + (long long)(n_windows - 1) * S;
+    for (int b = 0; b < batch; ++b)
+        if (lo[b] < 0 || lo[b] > hi[b] || hi[b] > Tt) return LS_EINVAL;
+    int n = 0;
+    for (int w = 0; w < n_windows; ++w) {
+        const long long own_lo = w ? w * S + n_pre : 0, own_hi = w * S + T;
+        bool run = false;
+        for (int b = 0; b < batch && !run; ++b) run = (lo[b] > own_lo ? lo[b] : own_lo) < (hi[b] < own_hi ? hi[b] : own_hi);
+        if (window_flags) window_flags[w] = run ? 1 : 0;
+        n += run ? 1 : 0;
+    }
+    *n_out = n;
+    return LS_OK;
+}
+
+// Timeline edit (ls_long_edit_args in ls_hip.h): ls_long_sample's per-window body over the windows of ls_long_edit_plan, with the
+// hand-off kernel replaced by k_edit_gather ahead of the loop and k_edit_scatter behind it, and the loop run with the inpainting branch
+// on planes that are already on the device.  The loop's launches read the handle's buffers only and none of them moves between windows,
+// so the first window's captured graph (its key holds the inpainting form) is replayed for the others.  One wait at the end.
+int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_edit: null argument");
+    if (!h->lg_prepared) return fail(h, LS_ESTATE, "ls_long_edit before ls_long_prepare");
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_edit before ls_set_schedule");
+    if (h->lg_ragged) return fail(h, LS_EUNSUPPORTED, "ls_long_edit: a handle prepared by ls_long_prepare_ragged is not edited (ragged batches are not built)");
+    if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM) return fail(h, LS_EUNSUPPORTED, "ls_long_edit: DDPM and DDIM loops only");
+    if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EUNSUPPORTED, "ls_long_edit: TAPE and PHILOX noise only");
+    if (!a->timeline) return fail(h, LS_EINVAL, "ls_long_edit: null timeline");
+    if (!a->frame_lo || !a->frame_hi) return fail(h, LS_EINVAL, "ls_long_edit: null frame_lo / frame_hi");
+    if (a->windows_capacity < 0 || (a->windows_capacity > 0 && !a->windows_run)) return fail(h, LS_EINVAL, "ls_long_edit: windows_capacity without windows_run");
+    const int B = h->B, W = h->lg_W, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, od = a->on_device;
+    const int Tt = T + (W - 1) * (T - npre);
+    // per clip [lo, hi) and the channel bytes; a clip with no channel selected is not edited
+    std::vector<int32_t> lo((size_t)B), hi((size_t)B), range((size_t)2 * B), flags((size_t)W);
+    std::vector<unsigned char> chan((size_t)B * JF, 1);
+    for (int b = 0; b < B; ++b) {
+        lo[(size_t)b] = a->frame_lo[b]; hi[(size_t)b] = a->frame_hi[b];
+        if (lo[(size_t)b] < 0 || lo[(size_t)b] > hi[(size_t)b] || hi[(size_t)b] > Tt)
+            return fail(h, LS_EINVAL, "ls_long_edit: clip %d: frames [%d, %d) are no range inside [0, %d]", b, lo[(size_t)b], hi[(size_t)b], Tt);
+        if (a->channels) {
+            bool any = false;
+            for (int c = 0; c < JF; ++c) any |= (chan[(size_t)b * JF + c] = a->channels[(size_t)b * JF + c] ? 1 : 0) != 0;
+            if (!any) hi[(size_t)b] = lo[(size_t)b];
+        }
+        range[(size_t)2 * b] = lo[(size_t)b]; range[(size_t)2 * b + 1] = hi[(size_t)b];
+    }
+    int32_t We = 0;
+    if (ls_long_edit_plan(B, W, T, npre, lo.data(), hi.data(), flags.data(), &We) != LS_OK) return fail(h, LS_EINVAL, "ls_long_edit: bad frame ranges");
+    if (We < 1) return fail(h, LS_EINVAL, "ls_long_edit: no window holds an editable element (every range is empty)");
+    ls_sample_args wa{};
+    wa.sampler = a->sampler; wa.noise_mode = a->noise_mode; wa.skip_timesteps = a->skip_timesteps; wa.on_device = 1;
+    wa.use_graph = a->use_graph; wa.clip_denoised = a->clip_denoised; wa.two_pass_always = a->two_pass_always; wa.eta = a->eta;
+    int rc;
+    if ((rc = check_sampler_args(h, &wa)) != LS_OK) return rc;
+    const bool tape = a->noise_mode == LS_NOISE_TAPE, noised = a->inpaint_noised != 0;
+    if (tape && (!a->x_init || !a->eps_tape || !a->noise_tape)) return fail(h, LS_EINVAL, "TAPE mode needs x_init, eps_tape and noise_tape");
+    if (tape && noised && !a->inpaint_noise) return fail(h, LS_EINVAL, "TAPE mode with inpaint_noised needs inpaint_noise");
+    if (!tape && (a->sample_offset >> 48 || (a->sample_offset + (unsigned long long)B) >> 48)) return fail(h, LS_EINVAL, "PHILOX: sample_offset + batch must stay below 2^48 (the window index sits above)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
+    h->seg_next = -1;
+    hipStream_t st = h->stream;
+    const int n_exec = h->n_steps - a->skip_timesteps;
+    const size_t per_x = (size_t)JF * T, nelem = (size_t)B * per_x, nx = nelem * sizeof(float);
+    const size_t per_e = (size_t)n_exec * 2 * B * kD, per_n = (size_t)n_exec * nelem;      // floats per window: eps tape, noise tape
+    // the ranges and channel bytes: one upload per call
+    if ((rc = upload(h, h->lg_edit_range, range.data(), range.size() * sizeof(int32_t))) != LS_OK) return rc;
+    if ((rc = upload(h, h->lg_edit_chan, chan.data(), chan.size())) != LS_OK) return rc;
+    const float *xs = a->x_init, *es = a->eps_tape, *ns = a->noise_tape, *iz = noised ? a->inpaint_noise : nullptr;
+    if (tape && !od) {
+        if ((rc = ingest(h, h->lg_x, xs, We * nx, 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, We * per_e * sizeof(float), 0)) != LS_OK ||
+            (rc = ingest(h, h->lg_nz, ns, We * per_n * sizeof(float), 0)) != LS_OK) return rc;
+        xs = h->lg_x.f(); es = h->lg_eps.f(); ns = h->lg_nz.f();
+        if (iz) { if ((rc = ingest(h, h->lg_inz, iz, We * per_n * sizeof(float), 0)) != LS_OK) return rc; iz = h->lg_inz.f(); }
+    }
+    float* tl = a->timeline;
+    float* wd = a->windows;
+    if (!od) {
+        if ((rc = ingest(h, h->lg_timeline, a->timeline, (size_t)B * JF * Tt * sizeof(float), 0)) != LS_OK) return rc;
+        tl = h->lg_timeline.f();
+        if (wd) { HIPCHK(h, h->lg_windows.ensure(We * nx)); wd = h->lg_windows.f(); }
+    }
+    const bool from_image = a->skip_timesteps > 0;
+    if (from_image) HIPCHK(h, h->lg_init.ensure(nx));
+    // the planes k_edit_gather fills are held by address in the captured loop: sized before the first window
+    if ((rc = ensure_pinned(h, h->inp_maskf, nx)) != LS_OK || (rc = ensure_pinned(h, h->inp_motion, nx)) != LS_OK) return rc;
+    EditArgs ea{};
+    ea.timeline = tl; ea.seed = h->lg_seed.f();
+    ea.range = static_cast<const int*>(h->lg_edit_range.p); ea.chan = static_cast<const unsigned char*>(h->lg_edit_chan.p);
+    ea.feat_u = h->feat_u.f(); ea.origin_x = h->origin_x.f(); ea.init = from_image ? h->lg_init.f() : nullptr;
+    ea.JF = JF; ea.T = T; ea.KPP = h->KPP; ea.n_pre = npre; ea.T_total = Tt;
+    wa.init_image = ea.init;
+    wa.inpaint_noised = noised ? 1 : 0;
+    LoopCall c{};
+    int replayed = 0, replays = 0, e = 0;
+    for (int w = 0; w < W; ++w) {
+        if (!flags[(size_t)w]) continue;
+        ea.w = w; ea.motion = h->inp_motion.f(); ea.maskf = h->inp_maskf.f();
+        HIPCHK(h, launch_edit_gather(ea, B, st));
+        // the static projections with ls_prepare's arithmetic and shapes, as in ls_long_sample
+        HIPCHK(h, launch_gemm_nt(h->feat_u.f(), h->KPP, h->win_pre.f(), h->KPP, h->win_bias.f(), nullptr, 0, h->static_u.f(), kD, B * T, kD, h->KPP, 0, st));
+        HIPCHK(h, launch_gemm_nt(h->lg_featc.f() + (size_t)w * B * T * kAudioFeat, kAudioFeat, h->win_aud.f(), kAudioFeat, nullptr, h->static_u.f(), kD,
+                                 h->static_c.f(), kD, B * T, kD, kAudioFeat, 0, st));
+        if (h->cfg.n_prefix_tokens == 2)
+            HIPCHK(h, hipMemcpyAsync(h->emo_tok.p, h->lg_emotok.f() + (size_t)w * B * kD, (size_t)B * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (tape) {
+            wa.x_init = xs + (size_t)e * nelem; wa.eps_tape = es + (size_t)e * per_e; wa.noise_tape = ns + (size_t)e * per_n;
+            wa.inpaint_noise = iz ? iz + (size_t)e * per_n : nullptr;
+        }
+        c = loop_call(h, &wa);
+        c.inpaint = true; c.inp_noised = noised; c.inp_resident = true;
+        h->call_host = CallParams{a->seed, a->sample_offset + ((unsigned long long)w << 48), h->tag_base, 0u};      // see ls_long_sample
+        if ((rc = begin_loop(h, c, true)) != LS_OK) return rc;
+        if (e == 0) HIPCHK(h, hipEventRecord(h->ev[6], st));
+        if ((rc = stage_loop_inputs(h, c)) != LS_OK) return rc;
+        if (e == 0) HIPCHK(h, hipEventRecord(h->ev[1], st));
+        if ((rc = run_loop(h, c, &replayed)) != LS_OK) return rc;
+        replays += replayed;
+        ea.sample = x_plane(h, n_exec); ea.window = wd ? wd + (size_t)e * nelem : nullptr;
+        HIPCHK(h, launch_edit_scatter(ea, B, st));
+        ++e;
+    }
+    HIPCHK(h, hipEventRecord(h->ev[2], st));
+    if (!od) {
+        if ((rc = egress(h, a->timeline, tl, (size_t)B * JF * Tt * sizeof(float), 0)) != LS_OK) return rc;
+        if (wd && (rc = egress(h, a->windows, wd, We * nx, 0)) != LS_OK) return rc;
+    }
+    HIPCHK(h, hipEventRecord(h->ev[3], st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if ((rc = coop_check(h)) != LS_OK) return rc;
+    report_path(h, c.pair);
+    HIPCHK(h, hipEventElapsedTime(&h->timing.loop_ms, h->ev[1], h->ev[2]));
+    HIPCHK(h, hipEventElapsedTime(&h->timing.total_ms, h->ev[6], h->ev[3]));
+    h->timing.n_step_launches = We * n_exec;
+    h->timing.single_pass = c.pair ? 1 : 0;
+    h->timing.graph_replayed = replays;
+    h->timing.tape_upload_ms = 0.f;
+    h->timing.n_segments = We;               // the windows that ran
+    for (int w = 0, k = 0; w < W && a->windows_run; ++w)
+        if (flags[(size_t)w] && k < a->windows_capacity) a->windows_run[k++] = w;
+    if (a->n_windows_run) *a->n_windows_run = We;
     return LS_OK;
 }
 

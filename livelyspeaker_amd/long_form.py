@@ -17,6 +17,11 @@ With ``noise_source='torch_cpu'`` the draws are those ``GaussianDiffusion._loop`
 
 Clips of different lengths (``audio_lengths=``) run the longest clip's windows; with ``drop_finished=True`` a clip leaves the batch once
 its own audio has ended (``plan_drop``; ``ls_long_prepare_ragged``), and window ``w`` is a sampling call on the clips that remain.
+
+A finished timeline is corrected with ``edit_long``: a frame range per clip (optionally some joints only) is re-synthesised by the
+windows that own one of its frames (``edit_plan``), each through the sampling loop's inpainting branch with the window's slice of the
+timeline as the given motion (``edit_window``; ``ls_long_edit``, ``k_edit_gather`` / ``k_edit_scatter``); everything else is kept bit
+for bit.
 """
 from __future__ import annotations
 
@@ -252,6 +257,160 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
         timeline = th.where(keep.to(timeline.device)[:, None, None, :], timeline, th.zeros((), dtype=timeline.dtype, device=timeline.device))
         return (timeline, frames, gd._as_tensor(windows, out_dev)) if return_windows else (timeline, frames)
     return (timeline, gd._as_tensor(windows, out_dev)) if return_windows else timeline
+
+
+def _edit_ranges(frames, B, n_frames):
+    """``frames`` -- one (lo, hi) pair for every clip, or [B, 2] -- as host int32 (lo [B], hi [B]) with 0 <= lo <= hi <= n_frames."""
+    if hasattr(frames, "detach"):
+        frames = frames.detach().cpu().numpy()
+    fr = np.asarray(frames)
+    if fr.shape == (2,):
+        fr = np.broadcast_to(fr, (B, 2))
+    if fr.shape != (B, 2) or fr.dtype.kind not in "iu":
+        raise ValueError(f"frames must be one integer (lo, hi) pair or [{B}, 2], got shape {list(fr.shape)} of {fr.dtype}")
+    lo, hi = fr[:, 0].astype(np.int64), fr[:, 1].astype(np.int64)
+    if (lo < 0).any() or (lo > hi).any() or (hi > n_frames).any():
+        raise ValueError(f"every frame range must satisfy 0 <= lo <= hi <= {n_frames}, got {fr.tolist()}")
+    return lo.astype(np.int32), hi.astype(np.int32)
+
+
+def _edit_joints(joints, B, cfg):
+    """``joints`` (None = all, or bool [J] / [B, J]) as a host bool [B, J]."""
+    J = int(cfg.njoints)
+    if joints is None:
+        return np.ones((B, J), bool)
+    if hasattr(joints, "detach"):
+        joints = joints.detach().cpu().numpy()
+    sel = np.asarray(joints)
+    if sel.shape == (J,):
+        sel = np.broadcast_to(sel, (B, J))
+    if sel.shape != (B, J) or sel.dtype != np.bool_:
+        raise ValueError(f"joints must be a bool mask [{J}] or [{B}, {J}], got shape {list(sel.shape)} of {sel.dtype}")
+    return np.ascontiguousarray(sel)
+
+
+def edit_plan(ranges, n_windows, cfg):
+    """The windows ``edit_long`` runs for the per-clip frame ranges ``ranges`` ((lo, hi) or [B, 2]) of a timeline of ``n_windows``
+    windows, as a sorted list: window w runs when some clip's range meets the frames it OWNS -- [0, T) for w = 0,
+    [w * S + n_pre, w * S + T) with S = T - n_pre otherwise, the frames it contributes to the stitched timeline.  No range meets any
+    (all are empty): ``ValueError``.  One definition for the engine and for this module (``ls_long_edit_plan``)."""
+    T, npre, W = int(cfg.nframes), int(cfg.n_pre_seq), int(n_windows)
+    fr = np.asarray(ranges.detach().cpu().numpy() if hasattr(ranges, "detach") else ranges)
+    lo, hi = _edit_ranges(fr, 1 if fr.ndim == 1 else int(fr.shape[0]), _window_sizes(W, cfg)[1])
+    windows = _lib.long_edit_plan(lo, hi, W, T, npre)
+    if not windows:
+        raise ValueError("edit_plan: every frame range is empty, no window would run")
+    return windows
+
+
+def edit_window(timeline, w, ranges, joints, seed_poses, cfg):
+    """Window ``w`` of a timeline edit in plain torch: ``(origin_x, inpainting_mask, inpainted_motion)``, each [B, J, F, T], as
+    ``edit_long`` hands them to the sampling loop.
+
+    * ``inpainted_motion`` is the slice ``timeline[..., w * S : w * S + T]`` (a contiguous copy) -- of the timeline as the earlier
+      windows of the call left it.
+    * ``origin_x[..., :n_pre]`` is the slice's first ``n_pre`` frames for w > 0 (the hand-off ``sample_long`` makes) and ``seed_poses``
+      for w = 0; beyond the prefix it is zero.
+    * ``inpainting_mask`` is True where the given motion is KEPT (the reference's meaning): False exactly on the editable elements
+      (b, j, :, f) -- joint j of ``joints`` (None = all, bool [J] or [B, J]) selected, ``lo_b <= w * S + f < hi_b``, and frame
+      ``w * S + f`` owned by window w (``edit_plan``).  The first ``n_pre`` frames of a later window belong to the window before it
+      and are never editable in it."""
+    T, npre = int(cfg.nframes), int(cfg.n_pre_seq)
+    S, w = T - npre, int(w)
+    B, J, F, N = _shape(timeline)
+    if w < 0 or w * S + T > N:
+        raise ValueError(f"window {w} lies outside a timeline of {N} frames")
+    lo, hi = _edit_ranges(ranges, B, N)
+    sel = _edit_joints(joints, B, cfg)
+    motion = timeline[..., w * S:w * S + T].contiguous()
+    origin_x = th.zeros_like(motion)
+    origin_x[..., :npre] = motion[..., :npre] if w > 0 else th.as_tensor(seed_poses).to(motion)
+    t = w * S + np.arange(T)
+    frame_ok = (t[None, :] >= lo[:, None]) & (t[None, :] < hi[:, None]) & ((np.arange(T) >= npre) | (w == 0))[None, :]       # [B, T]
+    editable = sel[:, :, None, None] & frame_ok[:, None, None, :]
+    mask = th.from_numpy(~np.broadcast_to(editable, (B, J, F, T))).to(motion.device)
+    return origin_x, mask, motion
+
+
+def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices, scale, emo=None, joints=None, sampler='ddim',
+              skip_timesteps=0, eta=0.0, clip_denoised=False, encoder_chunk=None, return_windows=False):
+    """Re-synthesise a stretch of a timeline ``sample_long`` made: the frames ``frames`` -- one ``(lo, hi)`` pair for all clips or a
+    host int array [B, 2], ``lo == hi`` leaves a clip alone -- on the joints ``joints`` (None = all; a bool mask [J] or [B, J]), with
+    the conditioning of the ``sample_long`` call (``audio``, ``seed_poses``, ``vid_indices``, ``scale``, ``emo``).  Returns a new
+    timeline; the caller's tensor is not modified.  ``return_windows=True``: ``(timeline, windows that ran, their raw samples
+    [We, B, J, F, T])``.
+
+    Only the windows of ``edit_plan`` are sampled, in ascending order, all clips each (one engine call: ``ls_long_prepare`` +
+    ``ls_long_edit``; ``k_edit_gather`` / ``k_edit_scatter``, csrc/ls_chain.hip).  Window w runs the sampling loop with the inputs
+    of ``edit_window`` -- the reference's inpainting branch (p_mean_variance, gaussian_diffusion.py:314-320; TED re-noises the kept
+    motion, BEAT mixes it in as it is), ``init_image`` = the slice when ``skip_timesteps > 0`` (the edit starts from the existing
+    motion, re-noised to the first executed step), x_T otherwise -- and its editable elements replace the timeline's; every other
+    element of the result is the input's, bit for bit.  With ``noise_source='torch_cpu'`` the result is bit for bit the loop
+    "for w in edit_plan: edit_window -> ddim_sample_loop / p_sample_loop -> write the editable elements back"
+    (tests/test_gpu_long_edit.py; the draws: ``RefDraws.edit_windows``).  ``'philox'``: clip b draws, in window w, the streams of
+    ``sample_offset + b + (w << 48)`` -- what ``sample_long`` draws there, whichever other windows run.  ``'torch_device'`` is refused.
+
+    To know, not to be surprised by:
+
+    * a window behind the last edited one is NOT resampled, even though its four conditioning frames may have changed; widen the
+      range to have it resampled;
+    * a clip whose range misses a window that runs for another clip still runs in it, with every element kept; its result is discarded.
+
+    Not built: SAG-driven edits (``sag=`` / ``text_features=``), ragged batches (``audio_lengths=``), PLMS, ``const_noise``,
+    ``dump_steps``, and re-encoding only the edited windows' audio (all W windows go through the WavEncoder, as in ``sample_long``)."""
+    from .cfg_sampler import ClassifierFreeSampleModel
+    if not isinstance(model, ClassifierFreeSampleModel):
+        raise TypeError(f"edit_long: pass livelyspeaker_amd.ClassifierFreeSampleModel(RAG), got {type(model).__name__}")
+    if diffusion.noise_source == "torch_device":
+        raise NotImplementedError("edit_long: noise_source='torch_device' is not built for chained windows; use 'torch_cpu' or 'philox'")
+    as_t = lambda a: a if (a is None or th.is_tensor(a)) else th.as_tensor(np.asarray(a))      # noqa: E731
+    timeline, audio, seed_poses, vid_indices, scale, emo = (as_t(a) for a in (timeline, audio, seed_poses, vid_indices, scale, emo))
+    rag = model.model
+    T, npre = int(rag.nframes), int(rag.n_pre_seq)
+    if timeline.ndim != 4 or _shape(timeline)[1:3] != (rag.njoints, rag.nfeats):
+        raise ValueError(f"timeline must be [B, {rag.njoints}, {rag.nfeats}, N], got {list(timeline.shape)}")
+    B, N = int(timeline.shape[0]), int(timeline.shape[3])
+    if T != 34 or N < T or (N - T) % (T - npre):
+        raise ValueError(f"a timeline holds 34 + 30 (W - 1) frames, got {N}")
+    W = (N - T) // (T - npre) + 1
+    lo, hi = _edit_ranges(frames, B, N)
+    sel = _edit_joints(joints, B, rag)
+    if audio.ndim != 2 or int(audio.shape[0]) != B:
+        raise ValueError(f"audio must be [{B}, L], got {list(audio.shape)}")
+    _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, W, sampler, skip_timesteps, None, None, encoder_chunk, {})
+    if diffusion.model_mean_type != gd.ModelMeanType.START_X or diffusion.model_var_type != gd.ModelVarType.FIXED_SMALL:
+        raise NotImplementedError("only START_X + FIXED_SMALL (create_gaussian_diffusion's setting) is built")
+    if rag.cond_mask_prob <= 0:
+        raise ValueError("ClassifierFreeSampleModel returns None when cond_mask_prob == 0 (cfg_sampler.py:24-31)")
+    hi = np.where(sel.any(axis=1), hi, lo).astype(np.int32)           # a clip with no joint selected is not edited
+    windows = edit_plan(np.stack([lo, hi], axis=1), W, rag)
+    out_dev = timeline.device
+    eng = diffusion._bind_schedule(rag.engine())
+    rag._cond_key = rag._prefetched_key = None        # the engine's resident conditioning is this call's from here on
+    if emo is not None:
+        emo = (emo[None, :].expand(W, B) if emo.ndim == 1 else emo.t()).contiguous()
+    eng.long_prepare(audio.float(), seed_poses.float(), vid_indices, scale.float(), emo=emo, n_windows=W, encoder_chunk=encoder_chunk)
+    n_exec = diffusion.num_timesteps - int(skip_timesteps)
+    shape = (B, rag.njoints, rag.nfeats, T)
+    noised = rag.n_prefix_tokens == 1                  # the TED tree re-noises the kept motion, the BEAT tree does not
+    kw = dict(sampler=_lib.LS_SAMPLER_DDIM if sampler == "ddim" else _lib.LS_SAMPLER_DDPM, skip_timesteps=int(skip_timesteps),
+              eta=float(eta) if sampler == "ddim" else 0.0, use_graph=diffusion.use_graph, clip_denoised=clip_denoised,
+              two_pass_always=diffusion.two_pass_always, device_out=out_dev.type == "cuda", return_windows=return_windows,
+              inpaint_noised=noised, channels=np.repeat(sel, rag.nfeats, axis=1))
+    if diffusion.noise_source == "philox":
+        kw.update(diffusion._philox_key())
+    else:
+        per_window = n_exec * (2 * B * eng.D + (2 if noised else 1) * int(np.prod(shape))) * 4
+        if per_window > diffusion.tape_segment_bytes:
+            raise ValueError(f"edit_long: one window's noise tape is {per_window} bytes, tape_segment_bytes is "
+                             f"{diffusion.tape_segment_bytes}; segmented tapes are not built for chained windows (raise "
+                             "tape_segment_bytes or use noise_source='philox')")
+        kw["x_init"], kw["eps_tape"], kw["noise_tape"], kw["inpaint_noise"] = ref_draws.RefDraws("cpu").edit_windows(
+            diffusion, len(windows), n_exec, shape, eng.D, noised)
+        diffusion.last_tape_segments = 1
+    res = eng.long_edit(timeline.float(), lo, hi, **kw)
+    edited = gd._as_tensor(res[0], out_dev)
+    return (edited, res[1], gd._as_tensor(res[2], out_dev)) if return_windows else edited
 
 
 def timeline_clips(x, stride=34, frames=None):

@@ -106,6 +106,23 @@ class RefDraws:
             first += Bw
         return x, eps, nz
 
+    def edit_windows(self, diffusion, n_run, n_exec, shape, D, noised):
+        """Timeline edit (long_form.edit_long): what one public sampling call per window that runs draws, one after the other -- x_T,
+        then that window's steps with the inpainting branch's re-noise draw between the model call and the step noise when ``noised``
+        (the TED tree; its prototype is the window's slice of the timeline, contiguous).  Returns (x [n_run, B, J, F, T], eps
+        [n_run, n_exec, 2, B, D], noise [n_run, n_exec, B, J, F, T], re-noise of the same shape or None)."""
+        shape = tuple(shape)
+        x, eps, nz = th.empty((n_run,) + shape), th.empty(n_run, n_exec, 2, shape[0], D), th.empty((n_run, n_exec) + shape)
+        inz = th.zeros((n_run, n_exec) + shape) if noised else None
+        proto = th.empty(shape, device=self.rdev) if noised else None
+        for i in range(n_run):
+            x[i] = self.x_T(shape)
+            steps = self.steps(shape, D, n_exec, inpainted=proto, diffusion=diffusion)
+            steps.run(0, eps[i], nz[i])
+            if noised:
+                inz[i] = steps.inz
+        return x, eps, nz, inz
+
     def bpd_columns(self, diffusion, nz, eps, proto):
         """nz.shape[0] columns of calc_bpd_loop, per column (:1617, then RAG.py:10-13): randn_like(x_start) in x_start's memory order
         (proto), then the pair.  Natively (ls_trng_randn continues torch's CPU stream per tensor and hands the advanced state back) when

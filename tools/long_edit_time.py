@@ -1,0 +1,81 @@
+"""Editing a long-form timeline (long_form.edit_long: only the windows a frame range touches are sampled) against sampling the whole
+timeline again (long_form.sample_long of the same W), alternated in one process:
+
+    python tools/long_edit_time.py                 # 60 s of speech, 64 clips (profiles/r19_long_edit.md)
+    python tools/long_edit_time.py 20 8            # seconds, clips
+
+TED, ddim100, skip_timesteps = 80 (20 steps per window), guidance 1.5, Philox noise, device-resident inputs, hipGraph replay, warm
+handles.  Three forms: the full call, an edit inside one window, and an edit that spans W // 2 windows.  Each call is timed by a host
+clock around work that ends in a device synchronise; the forms alternate ROUNDS times after a warm-up of all three, the median of a
+round's calls is that round's figure, and the table gives the median over rounds with their min .. max, next to the engine's own
+event times of the last call of each form (prepare: ls_long_prepare, the same for all three; windows: the sampling alone).  The shader
+clock is sampled alongside (long_form_time.ClockSampler).
+
+What to check (derived, not measured): the windows' time scales with |Wset| / W; each step costs about one elementwise launch more
+than in the full call (the inpainting branch runs the denoiser and the update as two launches); prepare is unchanged."""
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, ".")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from livelyspeaker_amd import long_form, synth                                        # noqa: E402
+from long_form_time import DEV, ROUNDS, SKIP, ClockSampler, build, timed              # noqa: E402
+
+
+def main():
+    seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
+    B = int(sys.argv[2]) if len(sys.argv) > 2 else 64
+    cfg, model, diffusion = build()
+    diffusion.noise_source, diffusion.philox_seed = "philox", 1
+    W, _, n_frames = long_form.plan_windows(int(round(seconds * 16000)), cfg)
+    y = {k: torch.from_numpy(v).to(DEV) for k, v in synth.make_long_cond(cfg, B, W).items()}
+    S = cfg.nframes - cfg.n_pre_seq
+    mid = W // 2
+    one = (mid * S + 10, mid * S + 20)                               # inside the frames window `mid` owns
+    half_lo = (W // 4) * S + 10
+    half = (half_lo, half_lo + (W // 2 - 1) * S + 5)                 # the frames W // 2 consecutive windows own
+    plans = {"one": long_form.edit_plan(one, W, cfg), "half": long_form.edit_plan(half, W, cfg)}
+    assert len(plans["one"]) == 1 and len(plans["half"]) == max(1, W // 2), plans
+
+    def full():
+        return long_form.sample_long(diffusion, model, y["audio"], y["seed_poses"], y["vid_indices"], y["scale"], n_windows=W, sampler="ddim",
+                                     skip_timesteps=SKIP)
+
+    timeline = full()
+
+    def edit(frames):
+        return long_form.edit_long(diffusion, model, timeline, frames, y["audio"], y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim",
+                                   skip_timesteps=SKIP)
+
+    forms = (("full", full), ("one", lambda: edit(one)), ("half", lambda: edit(half)))
+    clocks = ClockSampler()
+    clocks.start()
+    for _ in range(2):                                               # warm-up of all forms: allocations, graph capture, clocks
+        for _, fn in forms:
+            timed(fn)
+    clocks.take()
+    reps = 3
+    rounds, engine = {k: [] for k, _ in forms}, {}
+    for _ in range(ROUNDS):
+        for name, fn in forms:
+            rounds[name].append(statistics.median(timed(fn)[0] for _ in range(reps)))
+            engine[name] = model.model.engine().timing()
+    print(f"# TED ddim100 skip {SKIP} (20 steps per window), CFG 1.5, philox, device inputs; {seconds:g} s of speech = {W} windows "
+          f"({n_frames} frames), {B} clips; ms per call, median over {ROUNDS} alternated rounds [min .. max of the rounds]")
+    med = {k: statistics.median(v) for k, v in rounds.items()}
+    for name, _ in forms:
+        t = engine[name]
+        n_run = W if name == "full" else len(plans[name])
+        print(f"{name:5s} {n_run:3d} of {W} windows: {med[name]:9.2f} [{min(rounds[name]):.2f} .. {max(rounds[name]):.2f}]  "
+              f"({med[name] / med['full']:.3f} of the full call; |Wset| / W = {n_run / W:.3f})  | prepare {t['prepare_ms']:.2f} ms, "
+              f"windows {t['total_ms']:.2f} ms ({t['total_ms'] / n_run:.3f} per window), {t['n_step_launches']} steps, graph replayed for "
+              f"{t['graph_replayed']} of {t['n_segments']} windows, step path {t['step_path']}", flush=True)
+    print(f"# {clocks.take()}")
+    clocks.on = False
+
+
+if __name__ == "__main__":
+    main()
