@@ -117,7 +117,8 @@ struct StepArgs {
     unsigned long long* prof;  // [8 waves][kProfPoints] s_memtime stamps of workgroup prof_wg (env LS_PROF)
     int prof_wg;
     unsigned long long* wgt;   // [workgroups][2] s_memtime at the start / end of EVERY workgroup (tools/wg_timeline.py), or null
-    int ablate;              // env LS_ABLATE: 1 skip channel-mix MFMAs, 2 skip token-mix, 4 skip LN stats (results are wrong)
+    int ablate;              // env LS_ABLATE: 1 skip channel-mix MFMAs, 2 skip token-mix, 4 skip LN stats, 8 split channel mixing re-reads k block 0 of
+                             // its pass for every weight fragment (same loads, L1-resident data) -- results are wrong, timing only
 #endif
 };
 

@@ -78,6 +78,23 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
 #define LS_SPLIT_SHARED 1
 #endif
     constexpr bool kSplitShared = PREC == 2 && LS_SPLIT_SHARED != 0;
+    // Weight stream of that channel mixing: how many k blocks of weight fragments (6 x bf8 = 24 VGPRs each) are in flight ahead of the one
+    // being multiplied -- LS_WRING0 in chunk 0 (tiles 0-2), LS_WRING1 in chunk 1 (tiles 3-4).  1 / 1 is the earlier loop (one block ahead,
+    // handed over through copies, every pass fetching its first block after the previous pass's epilogue), kept for same-tree A/B like
+    // LS_SPLIT_SHARED=0.  Anything deeper runs chmix_ring_pass: a register ring of depth + 1 statically addressed slots that keeps
+    // running across the pass boundaries of a layer.  Every form gives the same bits.  Measured (profiles/r20_weight_ring.md): 2 / 2 is
+    // 3.7 % faster than 1 / 1 at TED B = 512; 2 / 3 (255 - 256 VGPRs) and 1 / 2 are within the spread of it.  Carrying the ring across the
+    // layer boundary as well, through LayerNorm 1, token mixing and LayerNorm 2, put 8 - 52 bytes per lane into scratch: not built.
+#ifndef LS_WRING0
+#define LS_WRING0 2
+#endif
+#ifndef LS_WRING1
+#define LS_WRING1 2
+#endif
+    constexpr int kRing0 = LS_WRING0, kRing1 = LS_WRING1;
+    static_assert(kRing0 >= 1 && kRing0 <= 3 && kRing1 >= 1 && kRing1 <= 3, "ring depth: 1, 2 or 3 k blocks");
+    constexpr bool kRing = kSplitShared && (kRing0 > 1 || kRing1 > 1);
+    constexpr int kRingSlots = (kRing0 > kRing1 ? kRing0 : kRing1) + 1;
     constexpr int kChunkTiles = 3;             // token tiles of chunk 0 (rows 0..47); chunk 1 = tiles 3..4 (rows 48..R-1)
     constexpr int kChunkRows = 16 * kChunkTiles;
     constexpr int kPlane = kChunkRows * kUStride;      // bf16 per plane
@@ -465,7 +482,8 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
     };
     // the channel mixing of tiles [t0, t1) of the chunk that ln_store_split has staged, for both channel halves p of this wave; the six
     // terms of every (q, t) in the order of kSplitA / kSplitB (smallest first, c2 innermost), q ascending: each accumulator adds the same
-    // sequence as in the in-register form.  The weight slice is prefetched one k block ahead.
+    // sequence as in the in-register form.  The weight slice is prefetched one k block ahead.  (LS_WRING0 = LS_WRING1 = 1 only: the
+    // default build runs chmix_ring_pass below.)
     auto chmix_split_chunk = [&](int l, auto t0c, auto t1c) {
         constexpr int t0 = decltype(t0c)::value, t1 = decltype(t1c)::value, NTC = t1 - t0;
 #pragma unroll
@@ -500,7 +518,7 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
                 for (int s = 0; s < 3; ++s)
 #pragma unroll
                     for (int c2 = 0; c2 < 2; ++c2) A[s][c2] = An[s][c2];
-                const int qn = (q + 1 < 16) ? q + 1 : 15;
+                const int qn = LS_ABLATED(a, 8) ? 0 : (q + 1 < 16) ? q + 1 : 15;
 #pragma unroll
                 for (int c2 = 0; c2 < 2; ++c2) {
                     An[0][c2] = wload8h(wr0, lane * 16, wsb + (qn * 2 + c2) * 1024);
@@ -526,6 +544,114 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
                 for (int t = 0; t < NTC; ++t)
                     if (valid_of(t0 + t)) X[2 * p + c2][t0 + t] = silu_acc4(acc[c2][t], X[2 * p + c2][t0 + t]);
         }
+    };
+
+    // The same channel mixing with the weight fragments in a register ring (kRing).  One call is ONE pass: channel half p of the tiles
+    // [t0, t1) of the staged chunk.  D k blocks are in flight ahead of the block being multiplied; the ring has D + 1 slots, block q of
+    // a pass always lies in slot q % (D + 1), and the k loop is unrolled by D + 1 so that every slot index is a constant and nothing is
+    // copied.  Step q first refills the slot that block q - 1 has just left -- with block q + D of this pass, or, during the last D
+    // steps and once more after the last one, with the block of the NEXT pass that belongs in that slot (DN = the next pass's depth,
+    // 0 = there is none) -- and then issues the MFMAs of block q: the same six terms per (q, t) in the same order, q ascending, so every
+    // accumulator adds the sequence it always did.  The next pass's first blocks and its bias (BCn) are therefore in flight across the
+    // SiLU epilogue and, between the chunks, across the barriers and ln_store_split: they need no LDS and nothing they read changes.
+    // (With 3 slots, 16 = 5 * 3 + 1: slot 0 is the last to come free, so the next pass's block 0 is fetched after its block 1.  Rotating
+    // each pass's slot numbering so that they come in order measured the same -- profiles/r20_weight_ring.md -- and was not kept.)
+    // The layer's first pass has no predecessor: ring_prime issues its bias and first blocks before LayerNorm 2's output is staged, so
+    // they arrive under that store and its barrier; the layer's last pass fetches nothing beyond its own slice (DN = 0).
+    // No read leaves the images: a pass addresses blocks 0 .. 15 of its own slice (l, w, p), l < layers, and blocks 0 .. DN - 1 of the
+    // slice `nbase` the caller names, which is another pass of the SAME layer and wave; and the three planes are read through
+    // descriptors bounded to the `layers` slices of the image, so that a wrong offset would read zeros -- and fail the bitwise tests --
+    // instead of faulting.
+    bf8 WR[kRingSlots][3][2];
+    f4 BCn[2];
+    struct RingPlanes { wrsrc_t r[3]; };
+    auto ring_planes = [&]() {
+        const int wbytes = a.layers * (kWaves * 2 * 16 * 2 * 1024);
+        return RingPlanes{{uniform_rsrc(a.W->wch_hi_img, wbytes), uniform_rsrc(a.W->wch_lo_img, wbytes), uniform_rsrc(a.W->wch_lo2_img, wbytes)}};
+    };
+    auto ring_base = [&](int l, int p) { return (((l * kWaves + w) * 2 + p) * 16) * 2 * 1024; };      // bytes, the same in all three planes
+    auto ring_bias = [&](int l, int p) { return (l * kD + 32 * p) * 4; };
+    auto ring_fetch = [&](const RingPlanes& wr, int slot, int off) {
+#pragma unroll
+        for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+            for (int s = 0; s < 3; ++s) WR[slot][s][c2] = wload8h(wr.r[s], lane * 16, off + c2 * 1024);
+        // the scheduler must not sink the refill towards its use D blocks later: in the two-tile chunk it gathered the loads of a
+        // whole turn at the loop's end, and the loop's first block then waited for vmcnt(0)
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto ring_prime = [&](int l) {
+        const RingPlanes wr = ring_planes();
+        const wrsrc_t wrb = wrsrc(a.W->bch);
+#pragma unroll
+        for (int c2 = 0; c2 < 2; ++c2) BCn[c2] = wload4(wrb, chw * 4, ring_bias(l, 0) + 64 * c2);
+#pragma unroll
+        for (int i = 0; i < kRing0; ++i) ring_fetch(wr, i, ring_base(l, 0) + (LS_ABLATED(a, 8) ? 0 : i * 2 * 1024));
+    };
+    auto chmix_ring_pass = [&](int l, auto pc, auto t0c, auto t1c, auto dc, auto dnc, int nbase, int nbias) {
+        constexpr int p = decltype(pc)::value, t0 = decltype(t0c)::value, t1 = decltype(t1c)::value, NTC = t1 - t0;
+        constexpr int D = decltype(dc)::value, DN = decltype(dnc)::value, NS = D + 1;
+        constexpr int QM = ((16 - D) / NS) * NS;       // blocks [0, QM): the rolled loop, whole turns of the ring, every refill from this pass
+        static_assert(NS <= kRingSlots && DN <= kRingSlots, "ring slots");
+        fresh();
+        const RingPlanes wr = ring_planes();
+        const wrsrc_t wrb = wrsrc(a.W->bch);
+        const int wsb = ring_base(l, p);
+        const int qb = LS_ABLATED(a, 8) ? 0 : 2 * 1024;                 // bytes from one k block to the next (ablation 8: every load is block 0)
+        const int nsb = LS_ABLATED(a, 8) ? wsb : nbase;
+        auto fetch = [&](int slot, int off) { ring_fetch(wr, slot, off); };
+        f4 acc[2][NTC];
+#pragma unroll
+        for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+            for (int t = 0; t < NTC; ++t) acc[c2][t] = BCn[c2];
+        typedef const __attribute__((address_space(3))) bf8* ldsp8;
+        typedef const __attribute__((address_space(3))) __bf16* ldspb;
+        ldspb pb[NTC];                            // lane (token, g) reads k = 32q + 8g .. +7 of its (clamped) row, per part
+#pragma unroll
+        for (int t = 0; t < NTC; ++t) pb[t] = (ldspb)(reinterpret_cast<const __bf16*>(U) + (rowc_of(t0 + t) - 16 * t0) * kUStride + 8 * g);
+        auto block = [&](int q, int slot) {
+            if (LS_ABLATED(a, 1)) return;
+#pragma unroll
+            for (int t = 0; t < NTC; ++t) {
+                bf8 B[3];
+#pragma unroll
+                for (int s = 0; s < 3; ++s) B[s] = *(ldsp8)(pb[t] + s * kPlane + 32 * q);
+#pragma unroll
+                for (int i = 0; i < kSplitTerms; ++i)
+#pragma unroll
+                    for (int c2 = 0; c2 < 2; ++c2)
+                        acc[c2][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(WR[slot][kSplitA[i]][c2], B[kSplitB[i]], acc[c2][t], 0, 0, 0);
+            }
+        };
+#pragma unroll 1
+        for (int q0 = 0; q0 < QM; q0 += NS) {
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                fetch((j + D) % NS, wsb + (q0 + j + D) * qb);
+                block(q0 + j, j);
+            }
+        }
+        // the last blocks, unrolled: the refills run out of this pass and go on with the next one
+        if constexpr (DN > 0) {
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2) BCn[c2] = wload4(wrb, chw * 4, nbias + 64 * c2);
+#pragma unroll
+            for (int f = NS; f < DN; ++f) fetch(f, nsb + f * qb);          // a deeper next pass: the slots this pass does not use
+        }
+#pragma unroll
+        for (int q = QM; q <= 16; ++q) {
+            const int f = (q + D) % NS;                                      // the slot block q - 1 has left
+            if (q + D < 16) fetch(f, wsb + (q + D) * qb);
+            else if (f < DN) fetch(f, nsb + f * qb);
+            if (q < 16) block(q, q % NS);
+        }
+        fresh();
+#pragma unroll
+        for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+            for (int t = 0; t < NTC; ++t)
+                if (valid_of(t0 + t)) X[2 * p + c2][t0 + t] = silu_acc4(acc[c2][t], X[2 * p + c2][t0 + t]);
     };
 
     // ================= TransMLP: 8 x MLPblock (mlp_module.py:67-91) ================================
@@ -711,16 +837,35 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
             typedef std::integral_constant<int, 0> T0;
             typedef std::integral_constant<int, kChunkTiles> T1;
             typedef std::integral_constant<int, kNT> T2;
+            if constexpr (kRing) ring_prime(l);
             ln_store_split(T0{}, T1{});
             __syncthreads();
             stamp(6 + 8 * l);
-            chmix_split_chunk(l, T0{}, T1{});
-            stamp(7 + 8 * l);
-            __syncthreads();
-            ln_store_split(T1{}, T2{});
-            __syncthreads();
-            stamp(8 + 8 * l);
-            chmix_split_chunk(l, T1{}, T2{});
+            if constexpr (kRing) {
+                // the four passes of the layer as one weight stream: each names the slice that follows it
+                typedef std::integral_constant<int, 0> P0;
+                typedef std::integral_constant<int, 1> P1;
+                typedef std::integral_constant<int, kRing0> D0;
+                typedef std::integral_constant<int, kRing1> D1;
+                typedef std::integral_constant<int, 0> DX;                   // the layer's last pass is followed by nothing: it does not advance
+                chmix_ring_pass(l, P0{}, T0{}, T1{}, D0{}, D0{}, ring_base(l, 1), ring_bias(l, 1));
+                chmix_ring_pass(l, P1{}, T0{}, T1{}, D0{}, D1{}, ring_base(l, 0), ring_bias(l, 0));
+                stamp(7 + 8 * l);
+                __syncthreads();
+                ln_store_split(T1{}, T2{});
+                __syncthreads();
+                stamp(8 + 8 * l);
+                chmix_ring_pass(l, P0{}, T1{}, T2{}, D1{}, D1{}, ring_base(l, 1), ring_bias(l, 1));
+                chmix_ring_pass(l, P1{}, T1{}, T2{}, D1{}, DX{}, ring_base(l, 1), ring_bias(l, 1));
+            } else {
+                chmix_split_chunk(l, T0{}, T1{});
+                stamp(7 + 8 * l);
+                __syncthreads();
+                ln_store_split(T1{}, T2{});
+                __syncthreads();
+                stamp(8 + 8 * l);
+                chmix_split_chunk(l, T1{}, T2{});
+            }
         } else if constexpr (PREC == 1) {
             // ---- bf16x3 split precision: W'.u ~= hi_w.hi_u + hi_w.lo_u + lo_w.hi_u on v_mfma_f32_16x16x32_bf16 (fp32
             // accumulate; bf16 x bf16 products are exact in fp32; the dropped lo.lo term and the split residuals are
