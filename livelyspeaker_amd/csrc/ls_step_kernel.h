@@ -95,6 +95,21 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
     static_assert(kRing0 >= 1 && kRing0 <= 3 && kRing1 >= 1 && kRing1 <= 3, "ring depth: 1, 2 or 3 k blocks");
     constexpr bool kRing = kSplitShared && (kRing0 > 1 || kRing1 > 1);
     constexpr int kRingSlots = (kRing0 > kRing1 ? kRing0 : kRing1) + 1;
+    // Where the ring passes do their non-MFMA work (profiles/r21_layer_overlap.md).  Each switch is its own A/B on one tree
+    // (tools/ab_variants.py build old=LS_EPI_BESIDE=0,... new=) and every combination gives the same bits: no term and no order changes.
+    // Measured at TED B = 512, per launch: the parent 1.0124 ms, the default 0.9909.
+    //   LS_EPI_BESIDE   1 = tile t's SiLU epilogue is issued among the MFMAs of the tile after it in k block 15 and pinned there; only
+    //                   a pass's last tile applies its own after its MFMAs, so no accumulator outlives its pass or crosses a barrier.
+    //                   0 = every epilogue after its pass; the compiler then carries chunk 0's across the mid-layer barriers.  Alone 0.9983.
+    //   LS_PRIO_FLIP    1 = waves 4 - 7 run a chunk's first pass at s_setprio 1.  At equal priority the older wave w wins the issue
+    //                   arbitration and finishes a chunk ~14 k clocks before its SIMD partner w + 4, which then runs on alone.  Alone 1.0046.
+#ifndef LS_EPI_BESIDE
+#define LS_EPI_BESIDE 1
+#endif
+#ifndef LS_PRIO_FLIP
+#define LS_PRIO_FLIP 1
+#endif
+    constexpr bool kEpiBeside = LS_EPI_BESIDE != 0, kPrioFlip = LS_PRIO_FLIP != 0;
     constexpr int kChunkTiles = 3;             // token tiles of chunk 0 (rows 0..47); chunk 1 = tiles 3..4 (rows 48..R-1)
     constexpr int kChunkRows = 16 * kChunkTiles;
     constexpr int kPlane = kChunkRows * kUStride;      // bf16 per plane
@@ -588,12 +603,24 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
 #pragma unroll
         for (int i = 0; i < kRing0; ++i) ring_fetch(wr, i, ring_base(l, 0) + (LS_ABLATED(a, 8) ? 0 : i * 2 * 1024));
     };
+    // kEpiBeside: a block is NTC steps, one per token tile, each fenced with sched_barrier(0) so that the order below is the order
+    // issued; all fragments of a block are read at its head, as in `block`.  In k block 15 the epilogue of tile t - 1, whose accumulators
+    // are final since its own step, is spread over the MFMAs of tile t: 12 packed-f32 VALU and 16 transcendentals (weight 5/3 each), as
+    // one VALU and one or two transcendentals behind every MFMA, which holds vector issue for 8 of its 16 cycles.  Only the pass's last
+    // tile has no MFMAs behind it in its pass: its epilogue follows at once, so no accumulator lives beyond its pass, let alone across a
+    // barrier.
     auto chmix_ring_pass = [&](int l, auto pc, auto t0c, auto t1c, auto dc, auto dnc, int nbase, int nbias) {
         constexpr int p = decltype(pc)::value, t0 = decltype(t0c)::value, t1 = decltype(t1c)::value, NTC = t1 - t0;
         constexpr int D = decltype(dc)::value, DN = decltype(dnc)::value, NS = D + 1;
         constexpr int QM = ((16 - D) / NS) * NS;       // blocks [0, QM): the rolled loop, whole turns of the ring, every refill from this pass
         static_assert(NS <= kRingSlots && DN <= kRingSlots, "ring slots");
+        static_assert(QM > 0, "the rolled loop runs");
         fresh();
+        if constexpr (kPrioFlip) {
+            if (w >= 4) {                              // a scalar branch: s_setprio ignores EXEC
+                __builtin_amdgcn_s_setprio(p == 0 ? 1 : 0);
+            }
+        }
         const RingPlanes wr = ring_planes();
         const wrsrc_t wrb = wrsrc(a.W->bch);
         const int wsb = ring_base(l, p);
@@ -624,12 +651,57 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
                         acc[c2][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(WR[slot][kSplitA[i]][c2], B[kSplitB[i]], acc[c2][t], 0, 0, 0);
             }
         };
+        auto epi = [&](int t, const f4 (&av)[2]) {
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2)
+                if (valid_of(t)) X[2 * p + c2][t] = silu_acc4(av[c2], X[2 * p + c2][t]);
+            // sched_barrier holds the machine scheduler only: without a use here the arithmetic is sunk, before scheduling, to where X is
+            // read next -- behind the barriers
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2) asm volatile("" : "+v"(X[2 * p + c2][t]));
+        };
+        auto block_seq = [&](int q, int slot, bool last) {               // last: k block 15
+            if (LS_ABLATED(a, 1)) return;
+            bf8 B[NTC][3];
+#pragma unroll
+            for (int t = 0; t < NTC; ++t)
+#pragma unroll
+                for (int s = 0; s < 3; ++s) B[t][s] = *(ldsp8)(pb[t] + s * kPlane + 32 * q);
+#pragma unroll
+            for (int t = 0; t < NTC; ++t) {
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < kSplitTerms; ++i)
+#pragma unroll
+                    for (int c2 = 0; c2 < 2; ++c2)
+                        acc[c2][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(WR[slot][kSplitA[i]][c2], B[t][kSplitB[i]], acc[c2][t], 0, 0, 0);
+                if (last && t > 0) {
+                    const int tp = t > 0 ? t - 1 : 0;                    // t = 0 is dead here, but its unrolled copy still needs an index in range
+                    const f4 av[2] = {acc[0][tp], acc[1][tp]};
+                    epi(t0 + tp, av);
+#pragma unroll
+                    for (int i = 0; i < kSplitTerms; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);      // one MFMA,
+                        __builtin_amdgcn_sched_group_barrier(0x2, 1, 0);      // one packed-f32 VALU,
+                        __builtin_amdgcn_sched_group_barrier(0x400, 1, 0);    // one transcendental;
+                        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);      // one MFMA,
+                        __builtin_amdgcn_sched_group_barrier(0x2, 1, 0);      // one VALU,
+                        __builtin_amdgcn_sched_group_barrier(0x400, 2, 0);    // two transcendentals
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        auto run = [&](int q, int slot, bool last) {
+            if constexpr (kEpiBeside) block_seq(q, slot, last);
+            else block(q, slot);
+        };
 #pragma unroll 1
         for (int q0 = 0; q0 < QM; q0 += NS) {
 #pragma unroll
             for (int j = 0; j < NS; ++j) {
                 fetch((j + D) % NS, wsb + (q0 + j + D) * qb);
-                block(q0 + j, j);
+                run(q0 + j, j, false);
             }
         }
         // the last blocks, unrolled: the refills run out of this pass and go on with the next one
@@ -644,14 +716,19 @@ __global__ __launch_bounds__(512) void k_step(const StepArgs a) {
             const int f = (q + D) % NS;                                      // the slot block q - 1 has left
             if (q + D < 16) fetch(f, wsb + (q + D) * qb);
             else if (f < DN) fetch(f, nsb + f * qb);
-            if (q < 16) block(q, q % NS);
+            if (q < 16) run(q, q % NS, q == 15);
         }
-        fresh();
+        if constexpr (kEpiBeside) {
+            const f4 av[2] = {acc[0][NTC - 1], acc[1][NTC - 1]};             // tiles t0 .. t1 - 2 are done
+            epi(t1 - 1, av);
+        } else {
+            fresh();
 #pragma unroll
-        for (int c2 = 0; c2 < 2; ++c2)
+            for (int c2 = 0; c2 < 2; ++c2)
 #pragma unroll
-            for (int t = 0; t < NTC; ++t)
-                if (valid_of(t0 + t)) X[2 * p + c2][t0 + t] = silu_acc4(acc[c2][t], X[2 * p + c2][t0 + t]);
+                for (int t = 0; t < NTC; ++t)
+                    if (valid_of(t0 + t)) X[2 * p + c2][t0 + t] = silu_acc4(acc[c2][t], X[2 * p + c2][t0 + t]);
+        }
     };
 
     // ================= TransMLP: 8 x MLPblock (mlp_module.py:67-91) ================================

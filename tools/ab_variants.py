@@ -2,7 +2,8 @@
 """A/B harness for kernel schedule variants.
 
   python tools/ab_variants.py build NAME=DEF1,DEF2 ...   # here (hipcc cross-compiles): variants/NAME.so
-  python tools/ab_variants.py run [B] [steps]            # on the GPU box: times ls::k_step for every variants/*.so
+  python tools/ab_variants.py run [ds] [B] [steps] [rounds]   # on the GPU box: times ls::k_step for every variants/*.so
+                                                         # (LS_AB_SCALE=1 in the environment: guidance scale 1, the single-pass kernel)
 
 Each variant is timed in its own subprocess (one HIP module per process), `rounds` times interleaved, and the
 median kernel time from HIP events on the engine's stream is reported.  Variants live under variants/
@@ -29,7 +30,7 @@ eng = _lib.Engine(cfg.njoints, cfg.nfeats, cfg.n_prefix_tokens, cfg.audio_len, n
 eng.load_state_dict(synth.make_state_dict(cfg))
 if os.environ.get("LS_PRECISION"): eng.set_precision(os.environ["LS_PRECISION"])
 eng.set_schedule(synth.schedule(steps))
-eng.prepare(synth.make_cond(cfg, B))
+eng.prepare(synth.make_cond(cfg, B, scale=float(os.environ.get("LS_AB_SCALE", "1.5"))))      # LS_AB_SCALE=1: the single-pass kernel
 ts = []
 for i in range(4):
     out = eng.sample(sampler=0, philox_seed=1)
@@ -53,7 +54,8 @@ def build(specs):
 
 
 def run(ds="ted", B=512, steps=40, rounds=3):
-    libs = sorted(glob.glob(os.path.join(VDIR, "*.so")))
+    # debug.so is the -DLS_DEBUG build of tools/phase_profile.py: it stamps, it is never a timing candidate
+    libs = [l for l in sorted(glob.glob(os.path.join(VDIR, "*.so"))) if os.path.basename(l) != "debug.so"]
     res = {os.path.basename(l)[:-3]: [] for l in libs}
     chk = {}
     for _ in range(rounds):
@@ -65,8 +67,9 @@ def run(ds="ted", B=512, steps=40, rounds=3):
                 res[name].append(r["ms"])
                 chk[name] = r["chk"]
             except Exception:
-                res[name].append(float("nan"))
-                print(name, "FAILED:", out.stderr[-400:])
+                # a child that died may have faulted the card: nothing more is started on it
+                print(name, "FAILED with exit status", out.returncode, ":", out.stderr[-400:])
+                sys.exit(1)
     for name, v in sorted(res.items(), key=lambda kv: sorted(kv[1])[len(kv[1]) // 2]):
         print(f"{name:24s} median {sorted(v)[len(v) // 2]:.4f} ms   all {['%.4f' % x for x in v]}   checksum {chk.get(name)}")
 

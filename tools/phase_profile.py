@@ -59,6 +59,36 @@ print(f"  X->U + barrier       : {np.mean(st[:, 2 + 8 * L] - prev):9.0f}")
 print(f"  out-proj MFMA        : {np.mean(st[:, 3 + 8 * L] - st[:, 2 + 8 * L]):9.0f}")
 print(f"  OUT + combine        : {np.mean(st[:, 4 + 8 * L] - st[:, 3 + 8 * L]):9.0f}")
 print("  per-wave totals:", (st[:, 4 + 8 * L] - st[:, 0]).astype(int).tolist())
+if chunked and NWV == 8:
+    # Per wave, not per mean: how long the fastest and the slowest wave take for each phase, separately for waves 0-3 and 4-7 (wave w and
+    # w + 4 share a SIMD), and how long a wave then stands at the barrier that follows the stamp.  A wave's wait is the time from its own
+    # stamp to the last wave's: exact where the barrier follows the stamp directly (7), a lower bound where work lies between (1: temb
+    # add and LN1 partial sums, 4: LN2 partial sums, 5: the store of chunk 0).
+    halves = [("waves 0-3", slice(0, 4)), ("waves 4-7", slice(4, 8))]
+    dur = np.zeros((len(pts), NWV))
+    prev = st[:, 1].copy()
+    for l in range(L):
+        for i, pnt in enumerate(pts):
+            cur = st[:, pnt + 8 * l]
+            dur[i] += (cur - prev) / L
+            prev = cur
+    print("  per phase and layer: mean | earliest wave .. latest wave (its number), by SIMD half")
+    for i in range(len(pts)):
+        row = f"  {names[i]:21s}:"
+        for hname, hs in halves:
+            d = dur[i, hs]
+            row += f"   {hname} {d.mean():8.0f} | {d.min():8.0f} (w{hs.start + int(d.argmin())}) .. {d.max():8.0f} (w{hs.start + int(d.argmax())})"
+        print(row)
+    bars = [(1, "layer end -> LN1 barrier"), (4, "token-mix end -> LN2 barrier"), (5, "LN2 stats -> chunk-0 barrier"), (7, "chunk 0 end -> mid barrier")]
+    print("  arrival at the barriers, per layer: spread = latest - earliest wave; wait = latest wave's stamp - own stamp")
+    for pnt, bname in bars:
+        arr = np.stack([st[:, pnt + 8 * l] for l in range(1 if pnt == 1 else 0, L)])          # [layers][waves]; the first layer's 1 follows the embedding
+        wait = arr.max(axis=1, keepdims=True) - arr
+        spread = (arr.max(axis=1) - arr.min(axis=1)).mean()
+        pair = np.abs(arr[:, :4] - arr[:, 4:]).mean()                                         # |stamp(w) - stamp(w + 4)|: skew between SIMD partners
+        lead = (arr[:, 4:] - arr[:, :4]).mean()                                               # > 0: the younger half arrives later
+        print(f"  {bname:29s}: spread {spread:7.0f}   mean wait " + "  ".join(f"{hname} {wait[:, hs].mean():7.0f}" for hname, hs in halves)
+              + f"   partner skew {pair:7.0f} (w+4 later by {lead:+.0f})   last to arrive: " + ",".join(f"w{int(x)}" for x in arr.argmax(axis=1)))
 if os.environ.get("LS_PROF_RAW"):
     l = 3
     base = st[:, 1 + 8 * l].min()
