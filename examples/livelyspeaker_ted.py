@@ -12,6 +12,7 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py [batch] --long-seconds N
     python examples/livelyspeaker_ted.py --long-seconds A,B,... [--drop-finished]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --edit-frames LO,HI [--edit-joints J0,J1,...]
+    python examples/livelyspeaker_ted.py [batch] --long-seconds N --stream-chunk SECONDS
     python examples/livelyspeaker_ted.py [batch] --clip-text
 --clip-text starts from TOKENS instead of a stand-in feature: synthetic clip.tokenize output -> CLIPTextEncoder (the text tower of CLIP
 on the GPU, synthetic weights) -> text features -> SAG decoder -> the same refinement, with no host wait between the two engines.
@@ -32,6 +33,9 @@ clip-windows that saves.
 --edit-frames LO,HI (with --long-seconds N) then EDITS the timeline it has just made: the frames [LO, HI) -- with --edit-joints only
 the listed joints (0..8) -- are re-synthesised from the existing motion (long_form.edit_long: the inpainting branch on the windows the
 range touches, 20 refinement steps each), everything else is kept bit for bit, and the line printed says how many of the W windows ran.
+--stream-chunk SECONDS (with --long-seconds N) feeds the same waveform to a STREAM instead, SECONDS of audio at a time
+(long_form.open_stream: push() returns a window's new frames as soon as the window's audio is complete, close() the zero-padded rest);
+it prints when each window's frames appeared and checks that the frames, concatenated, are bit for bit the timeline of the one call.
 With real data: load RAG.pt / SAG.pth / the auto-encoder checkpoint with load_model_wo_clip / load_state_dict and build `cond`
 exactly as the reference script does; everything below the weight loading is unchanged.
 """
@@ -173,17 +177,26 @@ def main():
                 raise SystemExit("--edit-joints goes with --edit-frames")
             edit["joints"] = [int(v) for v in sys.argv[j + 1].split(",") if v]
             del sys.argv[j:j + 2]
+        stream_chunk = None
+        if "--stream-chunk" in sys.argv:
+            j = sys.argv.index("--stream-chunk")
+            stream_chunk = float(sys.argv[j + 1])
+            del sys.argv[j:j + 2]
+            if stream_chunk <= 0:
+                raise SystemExit("--stream-chunk takes a positive number of seconds")
         drop = "--drop-finished" in sys.argv
         if drop:
             sys.argv.remove("--drop-finished")
         if edit is not None and ("," in arg or drop):
             raise SystemExit("--edit-frames edits the timeline of --long-seconds N (one duration; ragged batches are not edited)")
+        if stream_chunk is not None and ("," in arg or drop or edit is not None):
+            raise SystemExit("--stream-chunk streams the waveform of --long-seconds N (one duration, no edit)")
         if "," in arg:
             return main_long_ragged([float(v) for v in arg.split(",") if v], noise_source, drop)
         if drop:
             raise SystemExit("--drop-finished goes with a comma list of durations: equally long speeches finish together")
         seconds = float(arg)
-        return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source, edit)
+        return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source, edit, stream_chunk)
     if "--clip-text" in sys.argv:
         sys.argv.remove("--clip-text")
         return main_clip_text(int(sys.argv[1]) if len(sys.argv) > 1 else 64, noise_source)
@@ -302,7 +315,7 @@ def main_clip_text(B, noise_source):
     assert bool(torch.isfinite(sample).all()) and bool(torch.isfinite(decoded).all())
 
 
-def main_long(B, seconds, noise_source, edit=None):
+def main_long(B, seconds, noise_source, edit=None, stream_chunk=None):
     """`seconds` of 16 kHz speech per clip -> one stitched timeline at 15 fps (the LivelySpeaker chain, window after window on the device)."""
     import numpy as np
     from livelyspeaker_amd import long_form
@@ -334,6 +347,32 @@ def main_long(B, seconds, noise_source, edit=None):
     assert tuple(scored["pose"].shape) == (B, n_frames, 10, 3) and bool(torch.isfinite(scored["pose"]).all())
     if edit is not None:
         edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit)
+    if stream_chunk is not None:
+        stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, stream_chunk)
+
+
+def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, chunk_seconds):
+    """The waveform main_long sampled in one call, fed to a stream `chunk_seconds` at a time: every push carries the text feature of the
+    window it would start (a held value), and a window's frames come back from the push that completed its audio."""
+    n, L, W = max(1, int(round(chunk_seconds * 16000))), audio.shape[1], text.shape[1]
+    torch.manual_seed(233)                                                                  # the seed of the one call: the same draws
+    stream = long_form.open_stream(diffusion, model, y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim", skip_timesteps=80,
+                                   sag=sag_decoder)
+    parts, t0 = [], time.perf_counter()
+    for lo in list(range(0, L, n)) + [None]:
+        held = {"text_features": text[:, min(stream.windows_run, W - 1)]}
+        t1 = time.perf_counter()
+        new = stream.close(**held) if lo is None else stream.push(audio[:, lo:lo + n], **held)
+        torch.cuda.synchronize()
+        if new.shape[3]:
+            print(f"  {'close' if lo is None else f'audio {min(lo + n, L) / 16000:6.2f} s'}: window {stream.windows_run - 1} -> frames "
+                  f"{stream.frames_out - new.shape[3]}..{stream.frames_out - 1}, {(time.perf_counter() - t1) * 1e3:.1f} ms after its last sample "
+                  f"arrived ({(time.perf_counter() - t0) * 1e3:.0f} ms into the stream)")
+        parts.append(new)
+    streamed = torch.cat(parts, dim=3)
+    assert torch.equal(streamed, timeline), float((streamed - timeline).abs().max())
+    print(f"streamed in {chunk_seconds:g} s chunks ({len(parts) - 1} pushes + close): {stream.windows_run} windows, {stream.frames_out} frames, "
+          f"bit for bit the timeline of the one call")
 
 
 def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit):

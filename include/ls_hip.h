@@ -422,6 +422,67 @@ typedef struct ls_long_edit_args {
 int ls_long_edit_plan(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const int32_t* lo, const int32_t* hi,
                       int32_t* window_flags, int32_t* n_out);
 int ls_long_edit(ls_handle* h, const ls_long_edit_args* a);
+
+/* ---- Streaming long-form synthesis: the chain of ls_long_sample, fed audio in chunks of any size.  Window w runs as soon as its last
+ * sample has arrived (audio_stride * w + audio_len <= samples fed), conditioned on the last n_pre_seq poses of window w - 1 (window 0:
+ * seed_poses), and leaves T frames (window 0) or T - n_pre_seq frames in the output of the push that ran it.  The frames of all pushes,
+ * concatenated along the frame axis, are bit for bit the timeline ls_long_prepare + ls_long_sample give for the concatenated audio
+ * (without n_windows: the windows that cover it), whatever the chunking.
+ *
+ * ls_long_stream_plan (no handle, no GPU) is the one definition of the windows a call runs: with samples_before samples fed so far and
+ * samples_new more, windows [*first_window, *first_window + *n_windows) run; closing != 0 adds the windows that cover the total with
+ * silence behind its last sample (W = max(1, ceil((total - audio_len) / audio_stride) + 1) in all; the total must be >= 1).
+ *
+ * ls_long_stream_open runs the per-batch stages of ls_long_prepare once at batch B (guidance scales, speaker style, step plan, the
+ * window-0 hand-off from seed_poses) and allocates a per-clip audio ring of audio_len + audio_stride samples.  It REPLACES the handle's
+ * prepared conditioning, as ls_prepare does; in turn any call that replaces it (ls_prepare*, ls_long_prepare*, ls_commit_weights, a
+ * second ls_long_stream_open) ends the stream: the next ls_long_stream_push returns LS_ESTATE and the handle stays usable.
+ *
+ * Device memory does not grow with the stream: the ring, one gathered window [B, audio_len], one window's audio features [B, T, 256].
+ * A chunk larger than the ring's free space is consumed in pieces with the completed windows run in between.  One host wait per call
+ * that ran a window; a call that ran none waits only for the copy of a HOST chunk out of the caller's buffer (a device chunk must stay
+ * valid until the handle's stream has read it: order its reuse with ls_stream_order).
+ * Not built: clips joining or leaving a stream, per-clip lengths, edits of a running stream, PLMS, const_noise, dump_steps, a
+ * non-blocking push. */
+typedef struct ls_long_stream_cond {
+    int32_t batch;
+    int32_t on_device;
+    const float* seed_poses;    /* [B, J, F, n_pre_seq]: origin_x[..., :n_pre_seq] of window 0                        */
+    const int64_t* vid_indices; /* [B]                                                                                */
+    const float* scale;         /* [B]                                                                                */
+} ls_long_stream_cond;
+typedef struct ls_long_stream_push_args {
+    int32_t sampler;            /* LS_SAMPLER_DDPM | LS_SAMPLER_DDIM; these eight fields as in ls_long_sample_args    */
+    int32_t noise_mode;         /* LS_NOISE_TAPE | LS_NOISE_PHILOX                                                    */
+    int32_t skip_timesteps;
+    int32_t on_device;          /* audio, emo, text_features, the tapes and frames are device pointers                */
+    int32_t use_graph;
+    int32_t clip_denoised;
+    int32_t two_pass_always;
+    float eta;
+    int32_t closing;            /* the stream's last call: run the windows still owed, zero-padded; later pushes are refused */
+    int32_t capacity;           /* frames per row of `frames`; at least what the windows of this call produce         */
+    int64_t n_samples;          /* n >= 0: samples per clip in `audio`                                                */
+    const float* audio;         /* [B, n] (NULL with n == 0)                                                          */
+    const int64_t* emo;         /* [B] emotion ids held from this call on (BEAT), or NULL: the ids held so far        */
+    struct ls_sag* sag;         /* LivelySpeaker chain, as in ls_long_sample_args; NULL: none                         */
+    const float* text_features; /* with sag: [B, latent_dim] held from this call on, or NULL: the features held so far */
+    const float* x_init;        /* TAPE: [k, B, J, F, T] x_T of the k windows this call runs (ls_long_stream_plan)    */
+    const float* eps_tape;      /* TAPE: [k, n_exec, 2, B, latent_dim]                                                */
+    const float* noise_tape;    /* TAPE: [k, n_exec, B, J, F, T]                                                      */
+    uint64_t seed;              /* PHILOX: the same key in every call of a stream                                     */
+    uint64_t sample_offset;     /* PHILOX: window w draws at sample_offset + b + (w << 48), as in ls_long_sample      */
+    float* frames;              /* [B, J, F, capacity]: the new frames of this call's windows, in order (NULL with capacity 0) */
+    int32_t* n_frames;          /* HOST, nullable: frames written per row                                             */
+    int32_t* n_windows;         /* HOST, nullable: windows run                                                        */
+} ls_long_stream_push_args;
+int ls_long_stream_plan(int64_t samples_before, int64_t samples_new, int32_t audio_len, int32_t closing, int64_t* first_window,
+                        int64_t* n_windows);
+int ls_long_stream_open(ls_handle* h, const ls_long_stream_cond* c);
+int ls_long_stream_push(ls_handle* h, const ls_long_stream_push_args* a);
+/* out = {samples fed, windows run, frames written, device bytes the stream holds (ring + gathered window + one-window features)} of the
+ * handle's current or last stream (zeros before the first ls_long_stream_open) */
+int ls_long_stream_info(const ls_handle* h, int64_t out[4]);
 int ls_step(ls_handle* h, const ls_step_args* a);
 int ls_plms_step(ls_handle* h, const ls_plms_step_args* a);
 /* elementwise q_sample (gaussian_diffusion.py:240-258) at schedule index i; pointers per on_device */

@@ -72,6 +72,19 @@ class LsLongEditArgs(C.Structure):
         ("seed", C.c_uint64), ("sample_offset", C.c_uint64)]
 
 
+class LsLongStreamCond(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("on_device", C.c_int32), ("seed_poses", C.c_void_p), ("vid_indices", C.c_void_p), ("scale", C.c_void_p)]
+
+
+class LsLongStreamPushArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sampler", "noise_mode", "skip_timesteps", "on_device", "use_graph", "clip_denoised",
+                                         "two_pass_always")] + [
+        ("eta", C.c_float), ("closing", C.c_int32), ("capacity", C.c_int32), ("n_samples", C.c_int64), ("audio", C.c_void_p),
+        ("emo", C.c_void_p), ("sag", C.c_void_p), ("text_features", C.c_void_p), ("x_init", C.c_void_p), ("eps_tape", C.c_void_p),
+        ("noise_tape", C.c_void_p), ("seed", C.c_uint64), ("sample_offset", C.c_uint64), ("frames", C.c_void_p),
+        ("n_frames", c_i32p), ("n_windows", c_i32p)]
+
+
 class LsForwardArgs(C.Structure):
     _fields_ = [("on_device", C.c_int32), ("no_sync", C.c_int32), ("x", C.c_void_p), ("timesteps", C.c_void_p),
                 ("eps_cond", C.c_void_p), ("eps_uncond", C.c_void_p), ("out_cond", C.c_void_p),
@@ -188,7 +201,7 @@ class LsEvalConfig(C.Structure):
 
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
-           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
+           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
@@ -264,6 +277,10 @@ def load_library(build_if_missing: bool = True):
     lib.ls_long_plan_drop.argtypes = [C.c_int32, C.c_int32, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_int32, c_i32p]
     lib.ls_long_edit.argtypes = [C.c_void_p, C.POINTER(LsLongEditArgs)]
     lib.ls_long_edit_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p, c_i32p, c_i32p]
+    lib.ls_long_stream_plan.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_i64p, c_i64p]
+    lib.ls_long_stream_open.argtypes = [C.c_void_p, C.POINTER(LsLongStreamCond)]
+    lib.ls_long_stream_push.argtypes = [C.c_void_p, C.POINTER(LsLongStreamPushArgs)]
+    lib.ls_long_stream_info.argtypes = [C.c_void_p, c_i64p]
     lib.ls_forward.argtypes = [C.c_void_p, C.POINTER(LsForwardArgs)]
     lib.ls_step.argtypes = [C.c_void_p, C.POINTER(LsStepArgs)]
     lib.ls_plms_step.argtypes = [C.c_void_p, C.POINTER(LsPlmsStepArgs)]
@@ -519,6 +536,16 @@ def long_edit_plan(lo, hi, n_windows, n_frames=34, n_pre=4):
         raise ValueError(f"frame ranges must hold one 0 <= lo <= hi <= {int(n_frames) + (W - 1) * (int(n_frames) - int(n_pre))} per clip, "
                          f"got lo {lo.tolist()} hi {hi.tolist()} for {W} windows")
     return [w for w in range(W) if flags[w]]
+
+
+def long_stream_plan(samples_before, samples_new, audio_len, closing=False):
+    """ls_long_stream_plan (no GPU needed): ``(first_window, n_windows)`` a push of ``samples_new`` samples runs on a stream that holds
+    ``samples_before``; ``closing`` adds the zero-padded windows the total still owes.  Closing an empty stream raises ``ValueError``."""
+    first, n = C.c_int64(), C.c_int64()
+    if load_library().ls_long_stream_plan(int(samples_before), int(samples_new), int(audio_len), int(bool(closing)), C.byref(first), C.byref(n)) != 0:
+        raise ValueError(f"no windows for {samples_before} + {samples_new} samples (closing={bool(closing)}): counts must be >= 0, "
+                         "and a stream that is closed must hold a sample")
+    return int(first.value), int(n.value)
 
 
 def plan_coop_slices(groups, dataset="ted", n_cus=256):
@@ -941,6 +968,75 @@ class Engine(_Handle):
         ran = [int(w) for w in ran[:int(n_ran.value)]]
         assert ran == plan, (ran, plan)
         return (out, ran, windows) if return_windows else (out, ran)
+
+    # ---- streaming long-form synthesis -----------------------------------------------------------
+    def long_stream_open(self, seed_poses, vid_indices, scale):
+        """Open a stream at batch B (ls_long_stream_open): the per-batch stages of ``long_prepare`` and the audio ring.  Replaces whatever
+        ``prepare`` / ``long_prepare`` left resident; any of those ends the stream in turn."""
+        B = int(seed_poses.shape[0])
+        m = _Marshal(self.device, seed_poses, vid_indices, scale, stream=self._stream)
+        c = LsLongStreamCond(B, int(m.on_device), m.f32(seed_poses, (B, self.J, self.F, int(self.cfg.n_pre_seq))), m.i64(vid_indices, (B,)),
+                             m.f32(scale, (B,)))
+        m.ready()
+        self._check(self.lib.ls_long_stream_open(self.h, C.byref(c)), "ls_long_stream_open")
+        self.batch, self.n_windows, self.window_batches = B, 0, None
+
+    def long_stream_push(self, audio, closing=False, emo=None, sag=None, text_features=None, sampler=LS_SAMPLER_DDIM, x_init=None,
+                         eps_tape=None, noise_tape=None, skip_timesteps=0, eta=0.0, philox_seed=None, sample_offset=0, use_graph=True,
+                         clip_denoised=False, two_pass_always=False, device_out=False):
+        """Feed ``audio`` [B, n] (n >= 0) to the open stream and run the k windows that complete (ls_long_stream_push; ``closing``: also
+        the zero-padded ones still owed).  ``emo`` [B] / ``text_features`` [B, D] replace the held conditioning.  TAPE mode takes the
+        draws of exactly those k windows (``x_init`` [k, B, J, F, T], ``eps_tape`` [k, n_exec, 2, B, D], ``noise_tape`` [k, n_exec, B, J, F,
+        T]; ``long_stream_plan`` tells k), PHILOX mode ``philox_seed``.  Returns ``(frames [B, J, F, 34 | 30 per window], k)``."""
+        B, D = self.batch, self.D
+        n = int(audio.shape[1])
+        assert tuple(int(s) for s in audio.shape) == (B, n), (tuple(audio.shape), B)
+        info = self.long_stream_info()
+        first, k = long_stream_plan(info["samples_in"], n, self.cfg.audio_len, closing)
+        npre = int(self.cfg.n_pre_seq)
+        cap = k * (self.T - npre) + (npre if (k and first == 0) else 0)
+        members = [audio if n else None, emo, text_features] + ([x_init, eps_tape, noise_tape] if k else [])
+        if device_out:
+            import torch
+            members.append(torch.empty(1, device=torch.device("cuda", self.device)))
+        m = _Marshal(self.device, *members, stream=self._stream)
+        n_exec = self.n_steps - skip_timesteps
+        a = LsLongStreamPushArgs()
+        a.sampler, a.skip_timesteps, a.on_device, a.use_graph = int(sampler), int(skip_timesteps), int(m.on_device), int(bool(use_graph))
+        a.clip_denoised, a.two_pass_always, a.eta = int(bool(clip_denoised)), int(bool(two_pass_always)), float(eta)
+        a.closing, a.capacity, a.n_samples = int(bool(closing)), cap, n
+        if n:
+            a.audio = m.f32(audio, (B, n))
+        a.emo = m.i64(emo, (B,))
+        if sag is not None:
+            a.sag = sag.h
+            a.text_features = m.f32(text_features, (B, D))
+        if philox_seed is None:
+            a.noise_mode = LS_NOISE_TAPE
+            if k:
+                a.x_init = m.f32(x_init, (k,) + self._xshape())
+                a.eps_tape = m.f32(eps_tape, (k, n_exec, 2, B, D))
+                a.noise_tape = m.f32(noise_tape, (k, n_exec) + self._xshape())
+        else:
+            a.noise_mode = LS_NOISE_PHILOX
+            a.seed, a.sample_offset = int(philox_seed), int(sample_offset)
+        frames, pframes = m.out((B, self.J, self.F, cap))
+        if cap:
+            a.frames = pframes
+        n_frames, n_windows = C.c_int32(-1), C.c_int32(-1)
+        a.n_frames, a.n_windows = C.pointer(n_frames), C.pointer(n_windows)
+        m.ready()
+        self._check(self.lib.ls_long_stream_push(self.h, C.byref(a)), "ls_long_stream_push")
+        assert (int(n_frames.value), int(n_windows.value)) == (cap, k), (n_frames.value, n_windows.value, cap, k)
+        if k == 0:          # nothing was waited for: torch's stream must not reuse the chunk before the engine's stream has read it
+            m.done_async()
+        return frames, k
+
+    def long_stream_info(self) -> dict:
+        """ls_long_stream_info of the current (or last) stream: samples_in, windows_run, frames_out, device_bytes."""
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.ls_long_stream_info(self.h, out), "ls_long_stream_info")
+        return {"samples_in": int(out[0]), "windows_run": int(out[1]), "frames_out": int(out[2]), "device_bytes": int(out[3])}
 
     def q_sample(self, index, x_start, noise):
         m = _Marshal(self.device, x_start, noise, stream=self._stream)

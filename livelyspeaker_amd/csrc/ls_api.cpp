@@ -391,6 +391,7 @@ int ls_commit_weights(ls_handle* h) {
     h->weights_version++;
     h->temb_valid = false;
     h->prepared = false;
+    end_stream(h);
     free_graph(h);
     return LS_OK;
 }
@@ -443,6 +444,7 @@ static int prepare_impl(ls_handle* h, const ls_cond* c, bool wait) {
     }
     h->seg_next = -1;       // a new conditioning ends any segmented loop in progress
     h->lg_prepared = false; // ... and replaces a long-form call's
+    end_stream(h);          // ... and a running stream's
     if ((rc = prepare_scale(h, c->scale, B, od)) != LS_OK) return rc;
     if ((rc = run_wav_encoder(h, od ? static_cast<const float*>(c->audio_input) : h->audio.f(), B)) != LS_OK) return rc;
     // ---- static part of input_mapping (RAG.py:110-114): columns JF.. of W_in act on [prefix poses | bit | audio]
@@ -504,6 +506,7 @@ int ls_long_prepare(ls_handle* h, const ls_long_cond* c) {
     hipStream_t st = h->stream;
     int rc;
     h->prepared = h->lg_prepared = h->lg_ragged = false;
+    end_stream(h);
     h->seg_next = -1;
     HIPCHK(h, hipEventRecord(h->ev[4], st));
     HIPCHK(h, h->lg_audio.ensure((size_t)B * L * sizeof(float)));
@@ -626,6 +629,7 @@ int ls_long_prepare_ragged(ls_handle* h, const ls_long_cond* c, const int64_t* a
     hipStream_t st = h->stream;
     int rc;
     h->prepared = h->lg_prepared = h->lg_ragged = false;
+    end_stream(h);
     h->seg_next = -1;
     HIPCHK(h, hipEventRecord(h->ev[4], st));
     // a device-resident waveform is read in place (the call waits before it returns); a host one is uploaded as it is, unpadded
@@ -686,6 +690,69 @@ int ls_long_prepare_ragged(ls_handle* h, const ls_long_cond* c, const int64_t* a
     h->lg_W = W; h->lg_L = (size_t)c->audio_samples;
     h->lg_bw = bw; h->lg_off = off;
     h->lg_prepared = h->lg_ragged = true;
+    return LS_OK;
+}
+
+// Opening a stream (ls_long_stream_cond in ls_hip.h): ls_long_prepare without its audio.  The per-batch stages run once at batch B, the
+// window-0 hand-off (k_chain_window from the seed poses) leaves feat_u / origin_x as ls_long_sample's first window finds them, and the
+// buffers a window needs -- the ring, one gathered window, one window's features -- are sized here, so ls_long_stream_push allocates
+// nothing that a captured loop could hold.
+int ls_long_stream_open(ls_handle* h, const ls_long_stream_cond* c) {
+    if (!h || !c) return fail(h, LS_EINVAL, "ls_long_stream_open: null argument");
+    if (!h->committed) return fail(h, LS_ESTATE, "ls_long_stream_open before ls_commit_weights");
+    if (!h->fused) return fail(h, LS_EUNSUPPORTED, "long-form synthesis chains the reference's %d-frame windows", kT);
+    if (c->batch < 1) return fail(h, LS_EINVAL, "batch must be >= 1");
+    if (!c->seed_poses || !c->vid_indices || !c->scale) return fail(h, LS_EINVAL, "ls_long_stream_open: null conditioning pointer");
+    if (h->cfg.n_pre_seq < 1) return fail(h, LS_EINVAL, "long-form synthesis needs n_pre_seq >= 1 (the hand-off poses)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int B = c->batch, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, od = c->on_device;
+    const int R = (AL + LS_LONG_AUDIO_STRIDE + 3) / 4 * 4;       // a window and the stride to the next; whole float4 groups per clip
+    hipStream_t st = h->stream;
+    int rc;
+    h->prepared = h->lg_prepared = h->lg_ragged = false;
+    h->st_state = ls_handle::kStreamNone;       // a stream that was open ends here; this one opens when everything below has succeeded
+    h->seg_next = -1;
+    HIPCHK(h, hipEventRecord(h->ev[4], st));
+    if ((rc = ingest(h, h->lg_seed, c->seed_poses, (size_t)B * JF * h->cfg.n_pre_seq * sizeof(float), od)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->vid, c->vid_indices, (size_t)B * sizeof(int64_t), od)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->scale, c->scale, (size_t)B * sizeof(float), od)) != LS_OK) return rc;
+    if ((rc = prepare_scale(h, c->scale, B, od)) != LS_OK) return rc;
+    HIPCHK(h, h->st_ring.ensure((size_t)B * R * sizeof(float)));
+    HIPCHK(h, h->lg_clips.ensure((size_t)B * AL * sizeof(float)));
+    HIPCHK(h, h->lg_featc.ensure((size_t)B * T * kAudioFeat * sizeof(float)));
+    HIPCHK(h, h->lg_featp.ensure((size_t)B * T * KPP * sizeof(float)));
+    HIPCHK(h, h->st_text.ensure((size_t)B * kD * sizeof(float)));
+    HIPCHK(h, h->st_emo_ids.ensure((size_t)B * sizeof(int64_t)));
+    HIPCHK(h, h->origin_x.ensure((size_t)B * JF * T * sizeof(float)));
+    HIPCHK(h, hipMemsetAsync(h->origin_x.p, 0, (size_t)B * JF * T * sizeof(float), st));     // frames n_pre.. are zero (RAG.py:110)
+    HIPCHK(h, h->feat_u.ensure((size_t)B * T * KPP * sizeof(float)));
+    HIPCHK(h, hipMemsetAsync(h->feat_u.p, 0, (size_t)B * T * KPP * sizeof(float), st));
+    HIPCHK(h, h->static_c.ensure((size_t)B * T * kD * sizeof(float)));
+    HIPCHK(h, h->static_u.ensure((size_t)B * T * kD * sizeof(float)));
+    if ((rc = prepare_style(h, B)) != LS_OK) return rc;
+    if (h->cfg.n_prefix_tokens == 2) HIPCHK(h, h->emo_tok.ensure((size_t)B * kD * sizeof(float)));
+    if ((rc = prepare_plan(h, B)) != LS_OK) return rc;
+    ChainArgs ca{};         // window 0's prefix poses: the caller's seed poses
+    ca.seed = h->lg_seed.f(); ca.feat_u = h->feat_u.f(); ca.origin_x = h->origin_x.f();
+    ca.JF = JF; ca.T = T; ca.KPP = KPP; ca.n_pre = h->cfg.n_pre_seq; ca.T_total = T; ca.n_next = B;
+    HIPCHK(h, launch_chain_window(ca, B, st));
+    HIPCHK(h, hipEventRecord(h->ev[5], st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    HIPCHK(h, hipEventElapsedTime(&h->timing.prepare_ms, h->ev[4], h->ev[5]));
+    h->prepare_pending = false;
+    if (h->B != B) free_graph(h);
+    h->B = B;
+    h->st_R = R;
+    h->st_samples = h->st_windows = h->st_frames = 0;
+    h->st_have_emo = h->st_have_text = false;
+    h->st_state = ls_handle::kStreamOpen;
+    return LS_OK;
+}
+
+int ls_long_stream_info(const ls_handle* h, int64_t out[4]) {
+    if (!h || !out) return LS_EINVAL;
+    out[0] = h->st_samples; out[1] = h->st_windows; out[2] = h->st_frames;
+    out[3] = h->st_state == ls_handle::kStreamNone ? 0 : (int64_t)(h->st_ring.bytes + h->lg_clips.bytes + h->lg_featc.bytes);      // as allocated
     return LS_OK;
 }
 

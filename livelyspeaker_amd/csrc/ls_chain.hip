@@ -13,6 +13,9 @@
 // k_edit_gather / k_edit_scatter (further down) are the same cut and stitch for a timeline EDIT (ls_long_edit): a window's frames leave
 // the timeline as the loop's inpainting inputs and its editable elements return.  Algorithmic bytes per clip (fp32): gather 15.7 KB TED,
 // 163 KB BEAT (with the init plane); scatter at most 11.0 KB TED, 115 KB BEAT (with the raw window); the terms are spelled out at the kernels.
+// A STREAM (ls_long_stream_push) runs k_chain_window behind every window instead of ahead of it -- the same launch flushes the window into
+// the push's output and leaves the next window's prefix poses in feat_u / origin_x until the push that runs it -- and k_stream_gather
+// (at the end) cuts a window's audio out of the stream's circular ring.
 #include "ls_internal.h"
 
 namespace ls {
@@ -191,6 +194,46 @@ hipError_t launch_long_gather_clips(const float* audio, const int* table, const 
     if (n < 1 || n > 65535 || AL < 1 || L < 1 || stride < 1 || ((size_t)clips & 15)) return hipErrorInvalidValue;
     const int gx = (AL / 4 + 255) / 256;             // >= the float4 groups of a clip, whatever its head
     hipLaunchKernelGGL(k_long_gather_clips, dim3(gx > 0 ? gx : 1, n), dim3(256), 0, st, audio, table, lengths, clips, AL, L, stride);
+    return hipGetLastError();
+}
+
+// The WavEncoder input of one window of a STREAM (ls_long_stream_push): clip b's audio_len samples from its circular ring [R] (sample s
+// of the stream sits at s % R; the window's first sample at pos0 = (w * stride) % R), zero from the stream's last sample on (n_valid
+// samples of the window exist; fewer than AL only in the closing call).  AL <= R, so a window wraps at most once.  The destination
+// layout, the float4 store per thread and the scalar head and tail are k_long_gather_clips'; the load is a float4 when all four samples
+// exist, the ring position is a multiple of four (R is one, and a clip's ring starts 16-byte aligned) and the group does not cross the
+// ring's end, four guarded scalar loads otherwise.  Bytes: reads at most and writes exactly B * AL floats.
+__global__ __launch_bounds__(256) void k_stream_gather(const float* __restrict__ ring, float* __restrict__ clips, int AL, int R, int pos0, int n_valid) {
+    const int b = blockIdx.y;
+    const float* src = ring + (size_t)b * R;
+    float* dst = clips + (size_t)b * AL;
+    const int to_aligned = (int)((4 - ((size_t)b * AL & 3)) & 3), head = to_aligned < AL ? to_aligned : AL;
+    const int nvec = (AL - head) / 4;
+    auto pos = [&](int i) { const int q = pos0 + i; return q >= R ? q - R : q; };      // pos0 < R and i < AL <= R: one wrap at most
+    auto at = [&](int i) { return i < n_valid ? src[pos(i)] : 0.f; };
+    if (blockIdx.x == 0) {                          // scalar head and tail (at most three samples each)
+        const int t = threadIdx.x;
+        if (t < head) dst[t] = at(t);
+        const int tail0 = head + 4 * nvec;
+        if (t >= 4 && t < 4 + (AL - tail0)) dst[tail0 + (t - 4)] = at(tail0 + (t - 4));
+    }
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= nvec) return;
+    const int i = head + 4 * g, q = pos(i);
+    float4 v;
+    if (i + 3 < n_valid && (q & 3) == 0 && q + 3 < R) {
+        v = *reinterpret_cast<const float4*>(src + q);
+    } else {
+        v.x = at(i); v.y = at(i + 1); v.z = at(i + 2); v.w = at(i + 3);
+    }
+    *reinterpret_cast<float4*>(dst + i) = v;
+}
+
+hipError_t launch_stream_gather(const float* ring, float* clips, int B, int AL, int R, int pos0, int n_valid, hipStream_t st) {
+    if (B < 1 || B > 65535 || AL < 1 || R < AL || (R & 3) || pos0 < 0 || pos0 >= R || n_valid < 0 || n_valid > AL) return hipErrorInvalidValue;
+    if (((size_t)clips & 15) || ((size_t)ring & 15)) return hipErrorInvalidValue;
+    const int gx = (AL / 4 + 255) / 256;             // >= the float4 groups of a clip, whatever its head
+    hipLaunchKernelGGL(k_stream_gather, dim3(gx > 0 ? gx : 1, B), dim3(256), 0, st, ring, clips, AL, R, pos0, n_valid);
     return hipGetLastError();
 }
 

@@ -134,6 +134,16 @@ struct ls_handle {
     std::vector<int> lg_bw, lg_off;
     int lg_scale_ones = 0;
     DevBuf lg_row, lg_table, lg_lens;
+    // streaming long-form synthesis (ls_long_stream_open / _push): st_ring [B][st_R] holds sample s of every clip at s % st_R; the
+    // samples below audio_stride * st_windows are dead.  The gathered window is lg_clips [B][audio_len], its features lg_featc
+    // [B][T][256]; the hand-off poses live in feat_u / origin_x between two pushes, the held emotion tokens in emo_tok, the held text
+    // features in st_text.  st_state: kStreamNone, kStreamOpen, or why the stream ended.
+    enum { kStreamNone = 0, kStreamOpen, kStreamReplaced, kStreamClosed, kStreamFailed };
+    int st_state = kStreamNone;
+    int st_R = 0;
+    long long st_samples = 0, st_windows = 0, st_frames = 0;
+    bool st_have_emo = false, st_have_text = false;
+    DevBuf st_ring, st_emo_ids, st_text;
     // Cached graphs of the step loop, by loop key (ls_sample.cpp: loop_key holds everything a captured loop bakes in besides device
     // addresses, the batch and its step plan included).  At most kGraphCacheMax entries: a plain call whose key is missing drops them
     // all and captures its own (one entry, as before the cache); a ragged long-form call keeps one per window batch that serves two or
@@ -196,6 +206,9 @@ inline int egress(ls_handle* h, void* dst, const void* src, size_t bytes, int on
     HIPCHK(h, hipMemcpyAsync(dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
     return LS_OK;
 }
+
+// a call that replaces the handle's prepared conditioning ends a running stream (ls_long_stream_push then reports LS_ESTATE)
+inline void end_stream(ls_handle* h) { if (h->st_state == ls_handle::kStreamOpen) h->st_state = ls_handle::kStreamReplaced; }
 
 inline void free_graph(ls_handle* h) {        // every cached graph: whatever invalidates one invalidates all
     for (auto& g : h->graphs) {

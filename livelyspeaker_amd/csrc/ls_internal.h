@@ -337,6 +337,9 @@ hipError_t launch_edit_scatter(const EditArgs& a, int B, hipStream_t st);
 // that sample index is >= lengths[row] (nothing beyond a clip's length is read).  audio [.][L], clips [n][AL].
 hipError_t launch_long_gather_clips(const float* audio, const int* table, const int* lengths, float* clips, int n, int AL, long long L,
                                     int stride, hipStream_t st);
+// One window of a stream (ls_long_stream_push): clips[b][i] = ring[b][(pos0 + i) % R] for i < n_valid, 0 behind.  ring [B][R] with
+// R % 4 == 0 and AL <= R, 0 <= pos0 < R, 0 <= n_valid <= AL; clips [B][AL].  Both 16-byte aligned.
+hipError_t launch_stream_gather(const float* ring, float* clips, int B, int AL, int R, int pos0, int n_valid, hipStream_t st);
 
 // ---- torch's device normal stream (ls_torch_philox.hip; LS_NOISE_TORCH_DEVICE) ---------------------------------------------
 // One torch.randn / randn_like of n float32 elements per step: written to dst + r * dst_stride for step r of the launch.

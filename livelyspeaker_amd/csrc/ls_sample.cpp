@@ -929,6 +929,206 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
     return LS_OK;
 }
 
+// The windows one call of a stream runs (ls_long_stream_push_args in ls_hip.h): window w is complete once audio_stride * w + audio_len
+// samples have arrived; the closing call adds the windows plan_windows' arithmetic (long_form.py) still owes for the total.  Host only;
+// the single definition for ls_long_stream_push and for Python.
+int ls_long_stream_plan(int64_t samples_before, int64_t samples_new, int32_t audio_len, int32_t closing, int64_t* first_window, int64_t* n_windows) {
+    if (samples_before < 0 || samples_new < 0 || audio_len < 1 || !first_window || !n_windows) return LS_EINVAL;
+    if (samples_before > INT64_MAX - samples_new) return LS_EINVAL;
+    const int64_t S = LS_LONG_AUDIO_STRIDE, AL = audio_len, total = samples_before + samples_new;
+    auto complete = [&](int64_t n) { return n < AL ? (int64_t)0 : (n - AL) / S + 1; };
+    int64_t last = complete(total);
+    if (closing) {
+        if (total < 1) return LS_EINVAL;        // a waveform without a sample has no windows (plan_windows)
+        const int64_t cover = total > AL ? (total - AL + S - 1) / S + 1 : 1;
+        if (cover > last) last = cover;
+    }
+    *first_window = complete(samples_before);
+    *n_windows = last - *first_window;
+    return LS_OK;
+}
+
+namespace {
+// copy `take` samples of every clip from chunk column c0 (rows n apart) into the ring behind the stream's last sample: one strided copy,
+// two where the ring wraps
+int ring_write(ls_handle* h, const float* chunk, long long n, long long c0, int take, int od) {
+    const int B = h->B, R = h->st_R, p = (int)(h->st_samples % R), seg1 = take < R - p ? take : R - p;
+    const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    HIPCHK(h, hipMemcpy2DAsync(h->st_ring.f() + p, (size_t)R * sizeof(float), chunk + c0, (size_t)n * sizeof(float), (size_t)seg1 * sizeof(float), B, kind, h->stream));
+    if (take > seg1)
+        HIPCHK(h, hipMemcpy2DAsync(h->st_ring.p, (size_t)R * sizeof(float), chunk + c0 + seg1, (size_t)n * sizeof(float), (size_t)(take - seg1) * sizeof(float), B, kind, h->stream));
+    return LS_OK;
+}
+
+// Everything of a push behind its argument checks: feed the ring, run the windows that complete.  Per window the body of ls_long_sample
+// with the once-per-call encoder moved in front (k_stream_gather -> WavEncoder -> k_build_feats into the one-window feature buffer) and
+// the hand-off moved behind the loop: k_chain_window flushes the window into the call's output AND writes the next window's prefix poses
+// into feat_u / origin_x, where they wait for the push that runs it (nothing but a call that ends the stream writes either).
+int stream_push_run(ls_handle* h, const ls_long_stream_push_args* a, long long k) {
+    const int B = h->B, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, AL = h->cfg.audio_len, R = h->st_R, od = a->on_device, dev = h->cfg.device;
+    const int cap = a->capacity;
+    ls_sample_args wa{};
+    wa.sampler = a->sampler; wa.noise_mode = a->noise_mode; wa.skip_timesteps = a->skip_timesteps; wa.on_device = 1;
+    wa.use_graph = a->use_graph; wa.clip_denoised = a->clip_denoised; wa.two_pass_always = a->two_pass_always; wa.eta = a->eta;
+    const bool tape = a->noise_mode == LS_NOISE_TAPE;
+    hipStream_t st = h->stream;
+    int rc;
+    const int n_exec = h->n_steps - a->skip_timesteps;
+    const size_t per_x = (size_t)B * JF * T, per_e = (size_t)n_exec * 2 * B * kD, per_n = (size_t)n_exec * per_x, nx = per_x * sizeof(float);
+    // the held conditioning: what this call passes holds for every window started from here on
+    if (a->emo) {
+        if ((rc = ingest(h, h->st_emo_ids, a->emo, (size_t)B * sizeof(int64_t), od)) != LS_OK) return rc;
+        HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->st_emo_ids.p), h->emo_tok.f(), B, kD, h->cfg.n_emotions, st));
+        h->st_have_emo = true;
+    }
+    if (a->text_features) {
+        if ((rc = ingest(h, h->st_text, a->text_features, (size_t)B * kD * sizeof(float), od)) != LS_OK) return rc;
+        h->st_have_text = true;
+    }
+    ls_sag* const sag = a->sag;
+    void* const sag_st = sag ? ls_sag_stream(sag) : nullptr;
+    float* out = a->frames;
+    if (k > 0) {
+        if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
+        h->seg_next = -1;
+        if (sag) {
+            HIPCHK(h, h->lg_init.ensure(nx)); HIPCHK(h, h->lg_mask.ensure((size_t)B * T));
+            HIPCHK(h, hipMemsetAsync(h->lg_mask.p, 1, (size_t)B * T, st));
+            wa.init_image = h->lg_init.f();
+        }
+        if (!od) { HIPCHK(h, h->lg_timeline.ensure((size_t)B * JF * cap * sizeof(float))); out = h->lg_timeline.f(); }
+    }
+    ChainArgs ca{};
+    ca.feat_u = h->feat_u.f(); ca.origin_x = h->origin_x.f(); ca.timeline = out;
+    ca.JF = JF; ca.T = T; ca.KPP = h->KPP; ca.n_pre = npre; ca.T_total = cap; ca.n_next = B;
+    LoopCall c{};
+    int replayed = 0, replays = 0, t_off = 0;
+    long long ran = 0, fed = 0;
+    bool pair0 = false;
+    const long long n = a->n_samples;
+    while (fed < n || ran < k) {
+        // as much of the chunk as the ring has room for: the samples below the next window's first one are dead
+        const long long room = R - (h->st_samples - (long long)LS_LONG_AUDIO_STRIDE * h->st_windows);
+        const int take = (int)(n - fed < room ? n - fed : room);
+        if (take > 0) {
+            if ((rc = ring_write(h, a->audio, n, fed, take, od)) != LS_OK) return rc;
+            fed += take; h->st_samples += take;
+        }
+        int64_t w0 = 0, kw = 0;         // the windows complete now; in the closing call, once the chunk is in, the padded ones too
+        if (ls_long_stream_plan(h->st_samples, 0, AL, a->closing && fed == n, &w0, &kw) != LS_OK) return fail(h, LS_EINVAL, "ls_long_stream_push: closing a stream that was fed no sample");
+        const long long upto = w0 + kw;
+        if (take == 0 && upto <= h->st_windows) return fail(h, LS_ESTATE, "ls_long_stream_push: no room in the ring and no window to run");
+        for (long long w = h->st_windows; w < upto; ++w, ++ran) {
+            if (ran >= k) return fail(h, LS_ESTATE, "ls_long_stream_push: more windows complete than the call was planned for");
+            const long long lo = w * LS_LONG_AUDIO_STRIDE, have = h->st_samples - lo;
+            HIPCHK(h, launch_stream_gather(h->st_ring.f(), h->lg_clips.f(), B, AL, R, (int)(lo % R), (int)(have < AL ? (have < 0 ? 0 : have) : AL), st));
+            if ((rc = run_wav_encoder(h, h->lg_clips.f(), B)) != LS_OK) return rc;
+            HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f(), B, JF, h->KPP, 0, st, T));
+            // the static projections with ls_prepare's arithmetic and shapes, as in ls_long_sample
+            HIPCHK(h, launch_gemm_nt(h->feat_u.f(), h->KPP, h->win_pre.f(), h->KPP, h->win_bias.f(), nullptr, 0, h->static_u.f(), kD, B * T, kD, h->KPP, 0, st));
+            HIPCHK(h, launch_gemm_nt(h->lg_featc.f(), kAudioFeat, h->win_aud.f(), kAudioFeat, nullptr, h->static_u.f(), kD, h->static_c.f(), kD, B * T, kD, kAudioFeat, 0, st));
+            if (sag) {
+                if (ls_stream_order(dev, st, sag_st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
+                if (ls_sag_decode_async(sag, B, h->origin_x.f(), h->st_text.f(), static_cast<const unsigned char*>(h->lg_mask.p), h->lg_init.f()) != LS_OK)
+                    return fail(h, LS_EHIP, "SAG decode of window %lld: %s", w, ls_sag_last_error(sag));
+                if (ls_stream_order(dev, sag_st, st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
+            }
+            if (tape) {     // one window's draws at a time: the staging buffers do not grow with the call
+                const float *xs = a->x_init + (size_t)ran * per_x, *es = a->eps_tape + (size_t)ran * per_e, *ns = a->noise_tape + (size_t)ran * per_n;
+                if (!od) {
+                    if ((rc = ingest(h, h->lg_x, xs, nx, 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, per_e * sizeof(float), 0)) != LS_OK ||
+                        (rc = ingest(h, h->lg_nz, ns, per_n * sizeof(float), 0)) != LS_OK) return rc;
+                    xs = h->lg_x.f(); es = h->lg_eps.f(); ns = h->lg_nz.f();
+                }
+                wa.x_init = xs; wa.eps_tape = es; wa.noise_tape = ns;
+            }
+            c = loop_call(h, &wa);
+            if (ran == 0) pair0 = c.pair;
+            h->call_host = CallParams{a->seed, a->sample_offset + ((unsigned long long)w << 48), h->tag_base, 0u};      // see ls_long_sample
+            if ((rc = begin_loop(h, c, true)) != LS_OK) return rc;
+            if (ran == 0) HIPCHK(h, hipEventRecord(h->ev[6], st));
+            if ((rc = stage_loop_inputs(h, c)) != LS_OK) return rc;
+            if (ran == 0) HIPCHK(h, hipEventRecord(h->ev[1], st));
+            if ((rc = run_loop(h, c, &replayed)) != LS_OK) return rc;
+            replays += replayed;
+            // hand-off: the window leaves through the call's output, the next window's prefix poses enter feat_u / origin_x
+            ca.prev = x_plane(h, n_exec);
+            ca.f0 = w == 0 ? 0 : npre; ca.t_off = t_off;
+            HIPCHK(h, launch_chain_window(ca, B, st));
+            t_off += T - ca.f0;
+            h->st_windows = w + 1;
+        }
+    }
+    h->st_frames += t_off;
+    if (a->n_frames) *a->n_frames = t_off;
+    if (a->n_windows) *a->n_windows = (int32_t)ran;
+    if (a->closing) h->st_state = ls_handle::kStreamClosed;
+    if (ran == 0) {         // no sampling work: a host chunk is the caller's again once its copies are done, a device chunk is read in stream order
+        if (!od && n > 0) { HIPCHK(h, hipEventRecord(h->ev[6], st)); HIPCHK(h, hipEventSynchronize(h->ev[6])); }
+        return LS_OK;
+    }
+    HIPCHK(h, hipEventRecord(h->ev[2], st));
+    if (!od && (rc = egress(h, a->frames, out, (size_t)B * JF * cap * sizeof(float), 0)) != LS_OK) return rc;
+    HIPCHK(h, hipEventRecord(h->ev[3], st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if ((rc = coop_check(h)) != LS_OK) return rc;
+    report_path(h, pair0);
+    HIPCHK(h, hipEventElapsedTime(&h->timing.loop_ms, h->ev[1], h->ev[2]));
+    HIPCHK(h, hipEventElapsedTime(&h->timing.total_ms, h->ev[6], h->ev[3]));
+    h->timing.n_step_launches = (int)ran * n_exec;
+    h->timing.single_pass = pair0 ? 1 : 0;
+    h->timing.graph_replayed = replays;          // windows of this call served by a replay
+    h->timing.tape_upload_ms = 0.f;
+    h->timing.n_segments = (int)ran;
+    return LS_OK;
+}
+}  // namespace
+
+int ls_long_stream_push(ls_handle* h, const ls_long_stream_push_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_stream_push: null argument");
+    switch (h->st_state) {
+    case ls_handle::kStreamOpen: break;
+    case ls_handle::kStreamNone: return fail(h, LS_ESTATE, "ls_long_stream_push before ls_long_stream_open");
+    case ls_handle::kStreamClosed: return fail(h, LS_ESTATE, "ls_long_stream_push: the stream is closed");
+    case ls_handle::kStreamFailed: return fail(h, LS_ESTATE, "ls_long_stream_push: an earlier push of this stream failed; open a new one");
+    default: return fail(h, LS_ESTATE, "ls_long_stream_push: the stream was ended by a call that replaced the handle's prepared conditioning "
+                                       "(ls_prepare, ls_long_prepare, ls_commit_weights or another ls_long_stream_open); open a new one");
+    }
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_stream_push before ls_set_schedule");
+    if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM) return fail(h, LS_EUNSUPPORTED, "ls_long_stream_push: DDPM and DDIM loops only");
+    if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EUNSUPPORTED, "ls_long_stream_push: TAPE and PHILOX noise only");
+    if (a->n_samples < 0 || (a->n_samples > 0 && !a->audio)) return fail(h, LS_EINVAL, "ls_long_stream_push: n_samples %lld with%s audio", (long long)a->n_samples, a->audio ? "" : "out");
+    if (a->capacity < 0 || (a->capacity > 0 && !a->frames)) return fail(h, LS_EINVAL, "ls_long_stream_push: capacity without frames");
+    if (a->text_features && !a->sag) return fail(h, LS_EINVAL, "ls_long_stream_push: text_features without sag");
+    if (a->emo && h->cfg.n_prefix_tokens != 2) return fail(h, LS_EINVAL, "ls_long_stream_push: emo is a BEAT conditioning");
+    ls_sample_args wa{};
+    wa.sampler = a->sampler; wa.noise_mode = a->noise_mode; wa.skip_timesteps = a->skip_timesteps; wa.on_device = 1;
+    wa.use_graph = a->use_graph; wa.clip_denoised = a->clip_denoised; wa.two_pass_always = a->two_pass_always; wa.eta = a->eta;
+    int rc;
+    if ((rc = check_sampler_args(h, &wa)) != LS_OK) return rc;
+    int64_t first = 0, k = 0;
+    if (ls_long_stream_plan(h->st_samples, a->n_samples, h->cfg.audio_len, a->closing, &first, &k) != LS_OK)
+        return fail(h, LS_EINVAL, "ls_long_stream_push: closing a stream that was fed no sample");
+    if (first != h->st_windows) return fail(h, LS_ESTATE, "ls_long_stream_push: %lld windows have run, %lld were complete", h->st_windows, (long long)first);
+    const int T = h->T, npre = h->cfg.n_pre_seq;
+    const int64_t need = k == 0 ? 0 : k * (T - npre) + (first == 0 ? npre : 0);
+    if (need > a->capacity) return fail(h, LS_EINVAL, "ls_long_stream_push: this call runs %lld windows = %lld frames, capacity is %d", (long long)k, (long long)need, a->capacity);
+    if (k > 0) {
+        const bool tape = a->noise_mode == LS_NOISE_TAPE;
+        if (tape && (!a->x_init || !a->eps_tape || !a->noise_tape)) return fail(h, LS_EINVAL, "TAPE mode needs x_init, eps_tape and noise_tape");
+        if (!tape && (a->sample_offset >> 48 || (a->sample_offset + (unsigned long long)h->B) >> 48)) return fail(h, LS_EINVAL, "PHILOX: sample_offset + batch must stay below 2^48 (the window index sits above)");
+        if (h->cfg.n_prefix_tokens == 2 && !a->emo && !h->st_have_emo) return fail(h, LS_EINVAL, "ls_long_stream_push: the BEAT variant's first window needs emo ids");
+        if (a->sag && !a->text_features && !h->st_have_text) return fail(h, LS_EINVAL, "ls_long_stream_push: sag needs text_features for the first window");
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    rc = stream_push_run(h, a, k);
+    if (rc != LS_OK) {      // the ring and the hand-off poses may be half written: the stream is over, the handle is not
+        h->st_state = ls_handle::kStreamFailed;
+        (void)hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
 // The windows a timeline edit runs (ls_long_edit_args in ls_hip.h): window w owns the frames [w S + n_pre, w S + T) ([0, T) for w = 0) and
 // runs when the range of some clip meets them.  Host only; the single definition for ls_long_edit and for Python.
 int ls_long_edit_plan(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const int32_t* lo, const int32_t* hi, int32_t* window_flags,

@@ -22,6 +22,10 @@ A finished timeline is corrected with ``edit_long``: a frame range per clip (opt
 windows that own one of its frames (``edit_plan``), each through the sampling loop's inpainting branch with the window's slice of the
 timeline as the given motion (``edit_window``; ``ls_long_edit``, ``k_edit_gather`` / ``k_edit_scatter``); everything else is kept bit
 for bit.
+
+``open_stream`` is the online form of the same chain: audio arrives in chunks of any size, a window runs as soon as its last sample
+is there, and the frames of all pushes are bit for bit ``sample_long``'s for the concatenated audio (``ls_long_stream_open`` /
+``ls_long_stream_push``; a per-clip audio ring and ``k_stream_gather``).
 """
 from __future__ import annotations
 
@@ -257,6 +261,153 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
         timeline = th.where(keep.to(timeline.device)[:, None, None, :], timeline, th.zeros((), dtype=timeline.dtype, device=timeline.device))
         return (timeline, frames, gd._as_tensor(windows, out_dev)) if return_windows else (timeline, frames)
     return (timeline, gd._as_tensor(windows, out_dev)) if return_windows else timeline
+
+
+class LongStream:
+    """A running ``open_stream`` session; see there.  ``samples_in``, ``windows_run``, ``frames_out``: host ints."""
+
+    def __init__(self, diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag):
+        as_t = lambda a: a if (a is None or th.is_tensor(a)) else th.as_tensor(np.asarray(a))      # noqa: E731
+        seed_poses, vid_indices, scale, emo = (as_t(a) for a in (seed_poses, vid_indices, scale, emo))
+        B = int(seed_poses.shape[0]) if seed_poses.ndim else 0
+        rag = getattr(model, "model", None)
+        beat = getattr(rag, "n_prefix_tokens", 1) == 2
+        # _check_args on a one-window stand-in: a stream has no waveform yet, and its per-window conditioning arrives with the pushes
+        _check_args(diffusion, model, th.empty(max(B, 0), 1), seed_poses, vid_indices, scale,
+                    emo if (emo is not None or not beat) else th.zeros(B, dtype=th.long), None, sampler, skip_timesteps, sag,
+                    None if sag is None else th.empty(B, 1, int(rag.latent_dim)), None, {})
+        if diffusion.model_mean_type != gd.ModelMeanType.START_X or diffusion.model_var_type != gd.ModelVarType.FIXED_SMALL:
+            raise NotImplementedError("only START_X + FIXED_SMALL (create_gaussian_diffusion's setting) is built")
+        if rag.cond_mask_prob <= 0:
+            raise ValueError("ClassifierFreeSampleModel returns None when cond_mask_prob == 0 (cfg_sampler.py:24-31)")
+        if emo is not None and emo.ndim != 1:
+            raise ValueError(f"a stream holds one emotion id per clip: emo must be [{B}], got {list(emo.shape)}")
+        self._diffusion, self._rag, self._sag, self._B = diffusion, rag, sag, B
+        self._cond = (seed_poses.float(), vid_indices, scale.float())
+        self._emo, self._text = emo, None               # held on the host side only until the next engine call takes them
+        self._have_emo = self._have_text = False
+        self._kw = dict(sampler=_lib.LS_SAMPLER_DDIM if sampler == "ddim" else _lib.LS_SAMPLER_DDPM, skip_timesteps=int(skip_timesteps),
+                        eta=float(eta) if sampler == "ddim" else 0.0, use_graph=diffusion.use_graph, clip_denoised=clip_denoised,
+                        two_pass_always=diffusion.two_pass_always)
+        if diffusion.noise_source == "philox":          # one key per stream: window w draws at sample_offset + b + (w << 48)
+            self._kw.update(diffusion._philox_key())
+        self._n_exec = diffusion.num_timesteps - int(skip_timesteps)
+        self._eng = None
+        self._closed = False
+        self._last_dev = th.device("cpu")
+        self.samples_in =self.windows_run = self.frames_out = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self._closed = True        # leaving the block ends the session; the windows a close() would still run are not run
+        return False
+
+    def _engine(self):
+        if self._eng is None:
+            rag = self._rag
+            eng = self._diffusion._bind_schedule(rag.engine())
+            rag._cond_key = rag._prefetched_key = None        # the engine's resident conditioning is this stream's from here on
+            if self._sag is not None and self._sag.engine().device != eng.device:
+                raise ValueError(f"the SAG decoder runs on cuda:{self._sag.engine().device}, the RAG model on cuda:{eng.device}")
+            eng.long_stream_open(*self._cond)
+            self._eng = eng
+        return self._eng
+
+    def _feed(self, chunk, emo, text_features, closing):
+        if self._closed:
+            raise RuntimeError("the stream is closed")
+        rag, B, diffusion = self._rag, self._B, self._diffusion
+        as_t = lambda a: a if (a is None or th.is_tensor(a)) else th.as_tensor(np.asarray(a))      # noqa: E731
+        chunk, emo, text_features = as_t(chunk), as_t(emo), as_t(text_features)
+        if chunk.ndim != 2 or int(chunk.shape[0]) != B:
+            raise ValueError(f"audio_chunk must be [{B}, n], got {list(chunk.shape)}")
+        if emo is not None:
+            if rag.n_prefix_tokens != 2:
+                raise ValueError("emo is a BEAT conditioning; the TED model takes none")
+            if _shape(emo) != (B,):
+                raise ValueError(f"emo must be [{B}], got {list(emo.shape)}")
+        if text_features is not None:
+            if self._sag is None:
+                raise ValueError("text_features without sag: the SAG decoder turns them into every window's init_image")
+            if _shape(text_features) != (B, rag.latent_dim):
+                raise ValueError(f"text_features must be {[B, rag.latent_dim]}, got {list(text_features.shape)}")
+        n = int(chunk.shape[1])
+        first, k = _lib.long_stream_plan(self.samples_in, n, int(rag.audio_len), closing)
+        emo = emo if emo is not None else self._emo
+        text_features = text_features if text_features is not None else self._text
+        if k and rag.n_prefix_tokens == 2 and emo is None and not self._have_emo:
+            raise ValueError("the BEAT model needs emo [B] for the stream's first window: pass it to open_stream or to this push")
+        if k and self._sag is not None and text_features is None and not self._have_text:
+            raise ValueError("sag needs text_features [B, 512] for the stream's first window: pass them to this push")
+        shape = (B, rag.njoints, rag.nfeats, rag.nframes)
+        kw = dict(self._kw)
+        if k and diffusion.noise_source != "philox":
+            per_window = self._n_exec * (2 * B * int(rag.latent_dim) + int(np.prod(shape))) * 4
+            if per_window > diffusion.tape_segment_bytes:
+                raise ValueError(f"open_stream: one window's noise tape is {per_window} bytes, tape_segment_bytes is "
+                                 f"{diffusion.tape_segment_bytes}; segmented tapes are not built for chained windows (raise "
+                                 "tape_segment_bytes or use noise_source='philox')")
+        eng = self._engine()
+        if k and diffusion.noise_source != "philox":
+            kw["x_init"], kw["eps_tape"], kw["noise_tape"] = ref_draws.RefDraws("cpu").windows(diffusion, k, self._n_exec, shape, eng.D)
+            diffusion.last_tape_segments = 1
+        if self._sag is not None:
+            kw["sag"] = self._sag.engine()
+            kw["text_features"] = None if text_features is None else text_features.float()
+        out_dev = self._last_dev = chunk.device
+        frames, ran = eng.long_stream_push(chunk.float(), closing=closing, emo=emo, device_out=out_dev.type == "cuda", **kw)
+        self._have_emo, self._have_text = self._have_emo or emo is not None, self._have_text or text_features is not None
+        self._emo = self._text = None                   # the engine holds them now
+        self._closed = bool(closing)
+        self.samples_in += n
+        self.windows_run += ran
+        self.frames_out += int(frames.shape[3])
+        assert (first, k) == (self.windows_run - ran, ran)
+        return gd._as_tensor(frames, out_dev)
+
+    def push(self, audio_chunk, emo=None, text_features=None):
+        """Feed ``audio_chunk`` [B, n], n >= 0; returns the new frames ``[B, J, F, k]`` of the windows it completed (k may be 0)."""
+        return self._feed(audio_chunk, emo, text_features, False)
+
+    def close(self, emo=None, text_features=None):
+        """End the stream: the frames of the windows ``plan_windows(samples_in)`` still owes, with silence behind the last sample."""
+        return self._feed(th.zeros((self._B, 0), device=self._last_dev), emo, text_features, True)     # on the device of the last chunk
+
+
+def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False,
+                sag=None):
+    """The online form of ``sample_long``: a session that is fed audio in chunks of any size and returns a window's new frames as soon
+    as that window's audio is complete.
+
+        st = open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, sampler='ddim', ...)
+        new = st.push(audio_chunk, emo=None, text_features=None)    # [B, n], n >= 0  ->  [B, J, F, k] on the chunk's device
+        tail = st.close(emo=None, text_features=None)               # the windows plan_windows(total) still owes, zero-padded
+
+    The frames of all pushes and the close, concatenated, are bit for bit what ``sample_long`` gives for the concatenated audio with the
+    same model, schedule, conditioning and seed (no ``n_windows``, no ``audio_lengths``), whatever the chunking
+    (tests/test_gpu_long_stream.py).  A push runs, in order, every window w with ``32000 w + audio_len <= samples_in``
+    (``ls_long_stream_plan``); k is 34 for window 0 and 30 for each later one, and a push that completes no window returns
+    ``[B, J, F, 0]`` and launches no sampling work.  ``close`` on exactly ``audio_len + 32000 m`` samples returns no frame.  After
+    ``close`` (or after leaving the ``with`` block the session also works as) a push raises ``RuntimeError``.
+
+    ``emo`` (BEAT, [B]) and ``text_features`` ([B, 512], with ``sag=``) are HELD: what a push or ``close`` passes applies to every window
+    started from then on.  The first window needs a value.  In ``sample_long`` terms window w sees ``emo[:, w]`` /
+    ``text_features[:, w]`` equal to the value held when it ran.
+
+    Noise (``diffusion.noise_source``): ``'torch_cpu'`` draws a window's tape at the push that runs it, in window order
+    (``RefDraws.windows`` per push; the one-window ``tape_segment_bytes`` bound applies); ``'philox'`` takes its key here, once, and
+    window w draws at ``sample_offset + b + (w << 48)``; ``'torch_device'`` is refused.
+
+    The engine keeps a per-clip ring of ``audio_len + 32000`` samples, one gathered window and one window's features: device memory
+    does not grow with the stream (``ls_long_stream_info``).  The engine is bound at the first push; a ``ddim_sample_loop``,
+    ``sample_long`` or ``edit_long`` on the same model afterwards replaces its conditioning and ends the stream (the next push raises
+    ``_lib.EngineError``).
+
+    Not built: clips joining or leaving a running stream, ``audio_lengths`` / ``drop_finished``, ``edit_long`` on a running stream,
+    PLMS, ``const_noise``, ``dump_steps``, sharded calls, a non-blocking ``push``."""
+    return LongStream(diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag)
 
 
 def _edit_ranges(frames, B, n_frames):
