@@ -27,6 +27,11 @@ def hipcc_path() -> str:
     raise RuntimeError("hipcc not found (need ROCm >= 7.0)")
 
 
+def codegen_flags() -> list:
+    """The library's code-generation flags (tools/gemm_check.cpp is compiled with the same ones around ls_gemm.hip)."""
+    return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
+
+
 def source_hash() -> str:
     h = hashlib.sha256()
     for path in [os.path.join(CSRC, s) for s in SOURCES] + HEADERS:
@@ -82,8 +87,7 @@ def build_library(force: bool = False, verbose: bool = False, defines=(), out: s
     hipcc = hipcc_path()
     # -fno-slp-vectorize: SLP packs adjacent scalar f32 FMAs into v_pk_fma_f32 + v_mov shuffles, which is slower than
     # the scalar form next to MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs").
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize",
-             "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + ["-D" + d for d in defines] + list(extra_flags)
+    flags = codegen_flags() + ["-fPIC"] + ["-D" + d for d in defines] + list(extra_flags)
     variant = list(defines) + list(extra_flags)
     objdir = os.path.join(ROOT, "build", "obj" + ("-" + hashlib.sha256(" ".join(variant).encode()).hexdigest()[:8] if variant else ""))
     os.makedirs(objdir, exist_ok=True)

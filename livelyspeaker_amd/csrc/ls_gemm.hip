@@ -22,6 +22,7 @@
 // FETCHES the chunk that belongs at its position, and the fragment reads apply the same XOR (conflict-free ds_read_b128).
 #include "ls_internal.h"
 #include "ls_train.h"
+#include "ls_gemm_plan.h"
 #include "ls_lanes.h"
 
 namespace ls {
@@ -29,10 +30,7 @@ namespace ls {
 typedef float f4 __attribute__((ext_vector_type(4)));
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-constexpr int kTM = 128, kTK = kGemmTileK, kLdK = kTK + 4, kLdR = kTM + 4;
-#ifndef LS_GEMM_HALF_MAX
-#define LS_GEMM_HALF_MAX 768      // LDS-DMA grids of at most this many 64-row tiles run as 32-row half tiles (see launch_gemm_tr)
-#endif
+constexpr int kTM = kGemmTileM, kTK = kGemmTileK, kLdK = kTK + 4, kLdR = kTM + 4;
 
 // epilogue activations: 0 none, 1 SiLU, 2 exp(0.5 y) (std from log-variance), 3 exact GELU (F.gelu default),
 // 4 QuickGELU v * sigmoid(1.702 v) (the CLIP text tower's MLP), in the form of code 1
@@ -542,59 +540,34 @@ __global__ void k_splitk_reduce(const GemmArgs a, int Z) {
 }
 
 hipError_t launch_gemm_tr(GemmArgs a, bool a_kcontig, bool b_kcontig, int splits, hipStream_t st) {
-    if (splits < 1) splits = 1;
-    // chunk is a multiple of the K tile so that every split starts on a tile boundary
-    int kchunk = ((a.K + splits - 1) / splits + kTK - 1) / kTK * kTK;
-    splits = (a.K + kchunk - 1) / kchunk;
-    a.kchunk = kchunk;
-    a.splits = splits;
-    if (a.nbatch < 1) a.nbatch = 1;
-    if (splits > 1 && (!a.ws || (size_t)a.nbatch * splits * a.M * a.N > a.ws_floats)) return hipErrorInvalidValue;
-    if (splits > 1 && (a.Cpre || a.R || a.act)) return hipErrorInvalidValue;
-    dim3 grid((a.N + kTM - 1) / kTM, (a.M + kTM - 1) / kTM, a.nbatch * splits);
-    // fast staging path: full tiles, whole K tiles in every split, float4-legal operands with a single-level reduction index
-    const bool fast = a.M % kTM == 0 && a.N % kTM == 0 && a.K % kTK == 0 && a.A.vec && a.B.vec && a.A.ki == INT_MAX && a.B.ki == INT_MAX;
-    // 64-row tiles when they balance the 256 CUs better: every CU works through ceil(workgroups / 256) tiles (co-resident ones share
-    // its matrix pipes), so the efficiency of a grid is (workgroups / 256) / ceil(workgroups / 256) -- 544 tiles: 0.71, 1088 half tiles: 0.85
-    auto balance = [](long long wgs) { const double per = (double)wgs / 256.0; return per / (double)((wgs + 255) / 256); };
-    const long long t128 = (long long)grid.x * grid.y * grid.z;
-    const bool half = fast && a_kcontig && b_kcontig && balance(2 * t128) > balance(t128) + 0.05;
-    // LDS-DMA staging: single-level rows and every byte offset of an operand inside 31 bits (buffer addressing)
-    const bool dma = fast && a_kcontig && b_kcontig && a.A.ri == INT_MAX && a.B.ri == INT_MAX &&
-                     (long long)a.M * a.A.rs < (1ll << 29) && (long long)a.N * a.B.rs < (1ll << 29);
-    if (dma) {
-        // always 64-row tiles: 48 KB of double buffer lets three workgroups share a CU (the 128-row form: 64 KB, two); measured over the
-        // sampler's shapes (tools/gemm_bench.cpp) the 128-row DMA tile lost to this one and, at some, to the register-staged kernel
-        grid.y *= 2;
-        if (grid.z == 1 && (long long)grid.x * grid.y <= LS_GEMM_HALF_MAX) {
-            // a grid of at most one 64-row tile per slot: every tile as two 32-row halves -- twice the workgroups, half the MFMAs per wave and
-            // K tile.  A lone workgroup's K tile costs 1.3 us (64 MFMAs per wave + issue + barrier), so what shortens a small product is
-            // fewer MFMAs per wave, not a deeper prefetch (a three-buffer form with tiles k+1 and k+2 in flight measured SLOWER, 29.5 vs
-            // 26.0 us at 384 x 512 x 512; removed).  Measured: 384 x 512 x 512 (a 4-clip batch's channel mixing) 26 -> 13 us, 4608 rows
-            // 43 -> 32 us, 9728 rows 62 -> 55 us; above 768 tiles whole tiles win by 2-3 %.
-            hipLaunchKernelGGL(k_gemm_dma, dim3((unsigned)(2 * grid.x * grid.y)), dim3(256), 0, st, a, (int)grid.x, 0);
-        } else if (grid.z == 1) {
-            // a last round that fills less than ~60 % of the 768 slots runs as half tiles (a half tile takes ~0.6 of a whole one)
-            const long long tiles = (long long)grid.x * grid.y, slots = 768;
-            const long long rem = tiles % slots;
-            const int nbig = (rem > 0 && rem * 10 < slots * 6 && tiles > slots / 2) ? (int)(tiles - rem) : (int)tiles;
-            hipLaunchKernelGGL(k_gemm_dma, dim3((unsigned)(nbig + 2 * (tiles - nbig))), dim3(256), 0, st, a, (int)grid.x, nbig);
-        } else {
-            hipLaunchKernelGGL(k_gemm_dma, grid, dim3(256), 0, st, a, 0, 0);
-        }
-    } else if (half) {
-        grid.y *= 2;
-        hipLaunchKernelGGL((k_gemm_tr<true, true, true, 2>), grid, dim3(256), 0, st, a);
-    } else {
+    const GemmPlan p = gemm_plan(a, a_kcontig, b_kcontig, splits);        // the decision: ls_gemm_plan.h
+    if (p.invalid()) return hipErrorInvalidValue;
+    splits = p.splits;
+    a.kchunk = p.kchunk;
+    a.splits = p.splits;
+    a.nbatch = p.nbatch;
+    const dim3 grid = p.grid;
+    const bool fast = p.fast;
+    switch (p.kind) {
+        case kGemmDmaHalves:
+        case kGemmDmaWholeHalves:
+        case kGemmDmaWhole:
+        case kGemmDma3D:
+            hipLaunchKernelGGL(k_gemm_dma, grid, dim3(256), 0, st, a, p.gx, p.nbig);
+            break;
+        case kGemmFull64:
+            hipLaunchKernelGGL((k_gemm_tr<true, true, true, 2>), grid, dim3(256), 0, st, a);
+            break;
+        default:
 #define LS_GEMM_LAUNCH(AKV, BKV)                                                                             \
     do {                                                                                                     \
         if (fast) hipLaunchKernelGGL((k_gemm_tr<AKV, BKV, true>), grid, dim3(256), 0, st, a);                \
         else hipLaunchKernelGGL((k_gemm_tr<AKV, BKV, false>), grid, dim3(256), 0, st, a);                    \
     } while (0)
-        if (a_kcontig && b_kcontig) LS_GEMM_LAUNCH(true, true);
-        else if (a_kcontig && !b_kcontig) LS_GEMM_LAUNCH(true, false);
-        else if (!a_kcontig && b_kcontig) LS_GEMM_LAUNCH(false, true);
-        else LS_GEMM_LAUNCH(false, false);
+            if (a_kcontig && b_kcontig) LS_GEMM_LAUNCH(true, true);
+            else if (a_kcontig && !b_kcontig) LS_GEMM_LAUNCH(true, false);
+            else if (!a_kcontig && b_kcontig) LS_GEMM_LAUNCH(false, true);
+            else LS_GEMM_LAUNCH(false, false);
 #undef LS_GEMM_LAUNCH
     }
     hipError_t e = hipGetLastError();
