@@ -787,11 +787,7 @@ class Engine(_Handle):
         it draws x_T too; the caller moves the generator on).  Outputs are torch CUDA tensors if any input is one (or ``device_out``),
         else numpy."""
         inp = inpaint or (None, None, None, False)     # (mask, motion, q_sample noise tape or None, re-noise?): the inpainting branch
-        members = [x_init, eps_tape, noise_tape, init_image, inp[1]]
-        if device_out:
-            import torch
-            members.append(torch.empty(1, device=torch.device("cuda", self.device)))
-        m = _Marshal(self.device, *members, stream=self._stream)
+        m = self._marshal([x_init, eps_tape, noise_tape, init_image, inp[1]], device_out)
         a = LsSampleArgs()
         a.sampler, a.skip_timesteps, a.const_noise, a.on_device = sampler, skip_timesteps, int(const_noise), int(m.on_device)
         a.use_graph, a.eta, a.clip_denoised = int(use_graph), eta, int(clip_denoised)
@@ -837,7 +833,37 @@ class Engine(_Handle):
         self._segment_inputs = None
         return (out, dumps) if dump_steps else out
 
+    def _marshal(self, members, device_out=False):
+        """A ``_Marshal`` of one call's arrays; ``device_out`` adds a device member, so that the outputs come back as device tensors."""
+        if device_out:
+            import torch
+            members = list(members) + [torch.empty(1, device=torch.device("cuda", self.device))]
+        return _Marshal(self.device, *members, stream=self._stream)
+
     # ---- long-form synthesis ---------------------------------------------------------------------
+    def _chain_sampler(self, a, m, sampler, skip_timesteps, use_graph, clip_denoised, two_pass_always, eta):
+        """The eight fields every chained-window call opens with (ls_long_sample_args & co.); returns n_exec."""
+        a.sampler, a.skip_timesteps, a.on_device, a.use_graph = int(sampler), int(skip_timesteps), int(m.on_device), int(bool(use_graph))
+        a.clip_denoised, a.two_pass_always, a.eta = int(bool(clip_denoised)), int(bool(two_pass_always)), float(eta)
+        return self.n_steps - skip_timesteps
+
+    def _chain_noise(self, a, m, lead, n_exec, x_init, eps_tape, noise_tape, philox_seed, sample_offset, inpaint_noise=None, packed=False):
+        """TAPE mode (``philox_seed`` None) with the draws of ``lead`` windows -- ``packed``: of ``lead`` clip-windows, window after window
+        at its own batch; ``lead`` None: the call runs no window and takes no tapes -- or PHILOX mode."""
+        if philox_seed is not None:
+            a.noise_mode = LS_NOISE_PHILOX
+            a.seed, a.sample_offset = int(philox_seed), int(sample_offset)
+            return
+        a.noise_mode = LS_NOISE_TAPE
+        if lead is None:
+            return
+        B, D, x = self.batch, self.D, self._xshape()
+        a.x_init = m.f32(x_init, (lead,) + (x[1:] if packed else x))
+        a.eps_tape = m.f32(eps_tape, (lead * n_exec * 2 * D,) if packed else (lead, n_exec, 2, B, D))
+        a.noise_tape = m.f32(noise_tape, (lead * n_exec * self.J * self.F * self.T,) if packed else (lead, n_exec) + x)
+        if inpaint_noise is not None:
+            a.inpaint_noise = m.f32(inpaint_noise, (lead, n_exec) + x)
+
     def long_prepare(self, audio, seed_poses, vid_indices, scale, emo=None, n_windows=1, encoder_chunk=None, audio_lengths=None):
         """Once-per-call stage of a long-form call (ls_long_prepare): ``audio`` [B, L] is encoded once for all ``n_windows`` windows
         (zero-padded at the end when short), ``seed_poses`` [B, J, F, n_pre_seq] condition window 0, ``emo`` [W, B] (BEAT).  Replaces
@@ -872,25 +898,10 @@ class Engine(_Handle):
         (and the raw windows [W, B, J, F, T])."""
         B, W, D = self.batch, self.n_windows, self.D
         bw = getattr(self, "window_batches", None)      # a ragged call: packed tapes, window after window at its own batch
-        total = sum(bw) if bw else W * B
-        members = [x_init, eps_tape, noise_tape, text_features]
-        if device_out:
-            import torch
-            members.append(torch.empty(1, device=torch.device("cuda", self.device)))
-        m = _Marshal(self.device, *members, stream=self._stream)
-        n_exec = self.n_steps - skip_timesteps
+        m = self._marshal([x_init, eps_tape, noise_tape, text_features], device_out)
         a = LsLongSampleArgs()
-        a.sampler, a.skip_timesteps, a.on_device, a.use_graph = int(sampler), int(skip_timesteps), int(m.on_device), int(bool(use_graph))
-        a.clip_denoised, a.two_pass_always, a.eta = int(bool(clip_denoised)), int(bool(two_pass_always)), float(eta)
-        if philox_seed is None:
-            a.noise_mode = LS_NOISE_TAPE
-            per_x = self.J * self.F * self.T
-            a.x_init = m.f32(x_init, (total,) + self._xshape()[1:] if bw else (W,) + self._xshape())
-            a.eps_tape = m.f32(eps_tape, (total * n_exec * 2 * D,) if bw else (W, n_exec, 2, B, D))
-            a.noise_tape = m.f32(noise_tape, (total * n_exec * per_x,) if bw else (W, n_exec) + self._xshape())
-        else:
-            a.noise_mode = LS_NOISE_PHILOX
-            a.seed, a.sample_offset = int(philox_seed), int(sample_offset)
+        n_exec = self._chain_sampler(a, m, sampler, skip_timesteps, use_graph, clip_denoised, two_pass_always, eta)
+        self._chain_noise(a, m, sum(bw) if bw else W, n_exec, x_init, eps_tape, noise_tape, philox_seed, sample_offset, packed=bool(bw))
         if sag is not None:
             a.sag = sag.h
             a.text_features = m.f32(text_features, (W, B, D))
@@ -926,29 +937,15 @@ class Engine(_Handle):
         except ValueError:
             plan = []
         We = len(plan)
-        members = [timeline, x_init, eps_tape, noise_tape, inpaint_noise]
-        if device_out:
-            import torch
-            members.append(torch.empty(1, device=torch.device("cuda", self.device)))
-        m = _Marshal(self.device, *members, stream=self._stream)
-        n_exec = self.n_steps - skip_timesteps
+        m = self._marshal([timeline, x_init, eps_tape, noise_tape, inpaint_noise], device_out)
         a = LsLongEditArgs()
-        a.sampler, a.skip_timesteps, a.on_device, a.use_graph = int(sampler), int(skip_timesteps), int(m.on_device), int(bool(use_graph))
-        a.clip_denoised, a.two_pass_always, a.eta = int(bool(clip_denoised)), int(bool(two_pass_always)), float(eta)
+        n_exec = self._chain_sampler(a, m, sampler, skip_timesteps, use_graph, clip_denoised, two_pass_always, eta)
         a.inpaint_noised = int(bool(inpaint_noised))
         a.frame_lo, a.frame_hi = lo.ctypes.data_as(c_i32p), hi.ctypes.data_as(c_i32p)
         if ch is not None:
             a.channels = ch.ctypes.data_as(C.c_void_p)
-        if philox_seed is None:
-            a.noise_mode = LS_NOISE_TAPE
-            a.x_init = m.f32(x_init, (We,) + self._xshape())
-            a.eps_tape = m.f32(eps_tape, (We, n_exec, 2, B, D))
-            a.noise_tape = m.f32(noise_tape, (We, n_exec) + self._xshape())
-            if inpaint_noised:
-                a.inpaint_noise = m.f32(inpaint_noise, (We, n_exec) + self._xshape())
-        else:
-            a.noise_mode = LS_NOISE_PHILOX
-            a.seed, a.sample_offset = int(philox_seed), int(sample_offset)
+        self._chain_noise(a, m, We, n_exec, x_init, eps_tape, noise_tape, philox_seed, sample_offset,
+                          inpaint_noise=inpaint_noise if inpaint_noised else None)
         shape = (B, self.J, self.F, n_frames)
         assert tuple(int(s) for s in timeline.shape) == shape, (tuple(timeline.shape), shape)
         if m.on_device:         # a copy of the caller's timeline: the engine edits it in place
@@ -995,15 +992,9 @@ class Engine(_Handle):
         first, k = long_stream_plan(info["samples_in"], n, self.cfg.audio_len, closing)
         npre = int(self.cfg.n_pre_seq)
         cap = k * (self.T - npre) + (npre if (k and first == 0) else 0)
-        members = [audio if n else None, emo, text_features] + ([x_init, eps_tape, noise_tape] if k else [])
-        if device_out:
-            import torch
-            members.append(torch.empty(1, device=torch.device("cuda", self.device)))
-        m = _Marshal(self.device, *members, stream=self._stream)
-        n_exec = self.n_steps - skip_timesteps
+        m = self._marshal([audio if n else None, emo, text_features] + ([x_init, eps_tape, noise_tape] if k else []), device_out)
         a = LsLongStreamPushArgs()
-        a.sampler, a.skip_timesteps, a.on_device, a.use_graph = int(sampler), int(skip_timesteps), int(m.on_device), int(bool(use_graph))
-        a.clip_denoised, a.two_pass_always, a.eta = int(bool(clip_denoised)), int(bool(two_pass_always)), float(eta)
+        n_exec = self._chain_sampler(a, m, sampler, skip_timesteps, use_graph, clip_denoised, two_pass_always, eta)
         a.closing, a.capacity, a.n_samples = int(bool(closing)), cap, n
         if n:
             a.audio = m.f32(audio, (B, n))
@@ -1011,15 +1002,7 @@ class Engine(_Handle):
         if sag is not None:
             a.sag = sag.h
             a.text_features = m.f32(text_features, (B, D))
-        if philox_seed is None:
-            a.noise_mode = LS_NOISE_TAPE
-            if k:
-                a.x_init = m.f32(x_init, (k,) + self._xshape())
-                a.eps_tape = m.f32(eps_tape, (k, n_exec, 2, B, D))
-                a.noise_tape = m.f32(noise_tape, (k, n_exec) + self._xshape())
-        else:
-            a.noise_mode = LS_NOISE_PHILOX
-            a.seed, a.sample_offset = int(philox_seed), int(sample_offset)
+        self._chain_noise(a, m, k or None, n_exec, x_init, eps_tape, noise_tape, philox_seed, sample_offset)
         frames, pframes = m.out((B, self.J, self.F, cap))
         if cap:
             a.frames = pframes

@@ -1,7 +1,7 @@
 // Host side of the C-ABI declared in include/ls_hip.h: the handle's life cycle, the commit that uploads the weight images, the schedule,
 // once-per-call preparation and the small utility exports.  The images themselves (MFMA operand order) are built on the host by
-// ls_weights.cpp; the step plan and its launchers are in ls_plan.cpp, the diffusion loop and the single-step entries in ls_sample.cpp;
-// ls_handle.h holds what the three share.  No torch types here; livelyspeaker_amd/_lib.py binds these symbols with ctypes.
+// ls_weights.cpp; the step plan and its launchers are in ls_plan.cpp, the diffusion loop and the single-step entries in ls_sample.cpp,
+// the long-form entries (chained windows) in ls_chain_api.cpp; ls_handle.h holds what they share.  No torch types here; livelyspeaker_amd/_lib.py binds these symbols with ctypes.
 #include "ls_handle.h"
 #include "ls_weights.h"
 
@@ -443,8 +443,7 @@ static int prepare_impl(ls_handle* h, const ls_cond* c, bool wait) {
         HIPCHK(h, hipEventSynchronize(h->ev[6]));
     }
     h->seg_next = -1;       // a new conditioning ends any segmented loop in progress
-    h->lg_prepared = false; // ... and replaces a long-form call's
-    end_stream(h);          // ... and a running stream's
+    end_chain(h);           // ... and replaces a long-form call's, and a running stream's
     if ((rc = prepare_scale(h, c->scale, B, od)) != LS_OK) return rc;
     if ((rc = run_wav_encoder(h, od ? static_cast<const float*>(c->audio_input) : h->audio.f(), B)) != LS_OK) return rc;
     // ---- static part of input_mapping (RAG.py:110-114): columns JF.. of W_in act on [prefix poses | bit | audio]
@@ -484,277 +483,6 @@ int ls_prepare(ls_handle* h, const ls_cond* c) { return prepare_impl(h, c, true)
 // SAG decode, which needs none of it (scripts/test_LivelySpeaker_ted.py:88-113 runs the two back to back).  Device-resident inputs
 // must stay valid until the next call on this handle that synchronises; host inputs are staged as in ls_prepare.
 int ls_prepare_async(ls_handle* h, const ls_cond* c) { return prepare_impl(h, c, false); }
-
-// Once-per-call stage of a long-form call (ls_long_cond in ls_hip.h).  The WavEncoder has no term that couples clips (InstanceNorm is per
-// clip and channel), so the W * B clip-windows go through it in chunks of any size and leave the features ls_prepare would compute for
-// each window at batch B; k_build_feats turns a chunk's conv4 block into its rows of the feature store (its feat_p half goes to a scratch:
-// the prefix rows are k_chain_window's).  Everything else is ls_prepare's own stage at batch B.
-int ls_long_prepare(ls_handle* h, const ls_long_cond* c) {
-    if (!h || !c) return fail(h, LS_EINVAL, "ls_long_prepare: null argument");
-    if (!h->committed) return fail(h, LS_ESTATE, "ls_long_prepare before ls_commit_weights");
-    if (!h->fused) return fail(h, LS_EUNSUPPORTED, "long-form synthesis chains the reference's %d-frame windows", kT);
-    if (c->batch < 1 || c->n_windows < 1) return fail(h, LS_EINVAL, "batch and n_windows must be >= 1");
-    if (c->audio_samples < 1 || c->encoder_chunk < 0) return fail(h, LS_EINVAL, "ls_long_prepare: bad audio_samples / encoder_chunk");
-    if (!c->audio || !c->seed_poses || !c->vid_indices || !c->scale) return fail(h, LS_EINVAL, "ls_long_prepare: null conditioning pointer");
-    if (h->cfg.n_prefix_tokens == 2 && !c->emo) return fail(h, LS_EINVAL, "BEAT variant needs emo ids");
-    if (h->cfg.n_pre_seq < 1) return fail(h, LS_EINVAL, "long-form synthesis needs n_pre_seq >= 1 (the hand-off poses)");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int B = c->batch, W = c->n_windows, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, od = c->on_device;
-    const size_t L = (size_t)AL + (size_t)(W - 1) * LS_LONG_AUDIO_STRIDE, Lin = (size_t)c->audio_samples < L ? (size_t)c->audio_samples : L;
-    const int chunk = c->encoder_chunk > 0 ? c->encoder_chunk : 256;
-    const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    hipStream_t st = h->stream;
-    int rc;
-    h->prepared = h->lg_prepared = h->lg_ragged = false;
-    end_stream(h);
-    h->seg_next = -1;
-    HIPCHK(h, hipEventRecord(h->ev[4], st));
-    HIPCHK(h, h->lg_audio.ensure((size_t)B * L * sizeof(float)));
-    if (Lin < L) HIPCHK(h, hipMemsetAsync(h->lg_audio.p, 0, (size_t)B * L * sizeof(float), st));
-    HIPCHK(h, hipMemcpy2DAsync(h->lg_audio.p, L * sizeof(float), c->audio, (size_t)c->audio_samples * sizeof(float), Lin * sizeof(float), B, kind, st));
-    if ((rc = ingest(h, h->lg_seed, c->seed_poses, (size_t)B * JF * h->cfg.n_pre_seq * sizeof(float), od)) != LS_OK) return rc;
-    if ((rc = ingest(h, h->vid, c->vid_indices, (size_t)B * sizeof(int64_t), od)) != LS_OK) return rc;
-    if ((rc = ingest(h, h->scale, c->scale, (size_t)B * sizeof(float), od)) != LS_OK) return rc;
-    if (c->emo && (rc = ingest(h, h->lg_emo_ids, c->emo, (size_t)W * B * sizeof(int64_t), od)) != LS_OK) return rc;
-    if ((rc = prepare_scale(h, c->scale, B, od)) != LS_OK) return rc;
-    if (!od) HIPCHK(h, hipStreamSynchronize(st));       // host inputs are the caller's again
-    // ---- WavEncoder over the clip-windows cw = w * B + b, `chunk` at a time
-    const int ncw = W * B, nmax = chunk < ncw ? chunk : ncw;
-    HIPCHK(h, h->lg_clips.ensure((size_t)nmax * AL * sizeof(float)));
-    HIPCHK(h, h->lg_featc.ensure((size_t)ncw * T * kAudioFeat * sizeof(float)));
-    HIPCHK(h, h->lg_featp.ensure((size_t)nmax * T * KPP * sizeof(float)));
-    HIPCHK(h, h->origin_x.ensure((size_t)B * JF * T * sizeof(float)));
-    HIPCHK(h, hipMemsetAsync(h->origin_x.p, 0, (size_t)B * JF * T * sizeof(float), st));     // frames n_pre.. are zero (RAG.py:110); also k_build_feats' (unused) pose source
-    for (int cw0 = 0; cw0 < ncw; cw0 += chunk) {
-        const int n = ncw - cw0 < chunk ? ncw - cw0 : chunk;
-        for (int cw = cw0; cw < cw0 + n;) {             // one strided copy per run of clips of the same window
-            const int w = cw / B, b = cw - w * B, run = (B - b) < (cw0 + n - cw) ? (B - b) : (cw0 + n - cw);
-            HIPCHK(h, hipMemcpy2DAsync(h->lg_clips.f() + (size_t)(cw - cw0) * AL, (size_t)AL * sizeof(float),
-                                       h->lg_audio.f() + (size_t)b * L + (size_t)w * LS_LONG_AUDIO_STRIDE, L * sizeof(float), (size_t)AL * sizeof(float), run,
-                                       hipMemcpyDeviceToDevice, st));
-            cw += run;
-        }
-        if ((rc = run_wav_encoder(h, h->lg_clips.f(), n)) != LS_OK) return rc;
-        HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f() + (size_t)cw0 * T * kAudioFeat, n, JF, KPP, 0, st, T));
-    }
-    // ---- per-batch stages, once: feat_u with every row zero (k_chain_window writes the prefix rows per window), style, emotion tokens, plan
-    HIPCHK(h, h->feat_u.ensure((size_t)B * T * KPP * sizeof(float)));
-    HIPCHK(h, hipMemsetAsync(h->feat_u.p, 0, (size_t)B * T * KPP * sizeof(float), st));
-    HIPCHK(h, h->static_c.ensure((size_t)B * T * kD * sizeof(float)));
-    HIPCHK(h, h->static_u.ensure((size_t)B * T * kD * sizeof(float)));
-    if ((rc = prepare_style(h, B)) != LS_OK) return rc;
-    if (h->cfg.n_prefix_tokens == 2) {
-        HIPCHK(h, h->emo_tok.ensure((size_t)B * kD * sizeof(float)));
-        HIPCHK(h, h->lg_emotok.ensure((size_t)W * B * kD * sizeof(float)));
-        HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->lg_emo_ids.p), h->lg_emotok.f(), W * B, kD, h->cfg.n_emotions, st));
-    }
-    if ((rc = prepare_plan(h, B)) != LS_OK) return rc;
-    HIPCHK(h, hipEventRecord(h->ev[5], st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipEventElapsedTime(&h->timing.prepare_ms, h->ev[4], h->ev[5]));
-    h->prepare_pending = false;
-    if (h->B != B) free_graph(h);
-    h->B = B;
-    h->lg_W = W; h->lg_L = L;
-    h->lg_prepared = true;      // `prepared` stays false: the static projections exist per window, inside ls_long_sample only
-    return LS_OK;
-}
-
-// The plan of a ragged long-form call (ls_long_plan_drop): windows per clip from plan_windows' arithmetic (long_form.py), the clips
-// stably sorted by them, longest first, and per window the clips that run it.
-static void long_plan_drop(int B, int AL, const int64_t* lengths, std::vector<int>& row, std::vector<int>& wins, std::vector<int>& bw) {
-    std::vector<int> wb((size_t)B);
-    int wmax = 1;
-    for (int b = 0; b < B; ++b) {
-        const long long over = (long long)lengths[b] - AL;
-        wb[(size_t)b] = over <= 0 ? 1 : (int)((over + LS_LONG_AUDIO_STRIDE - 1) / LS_LONG_AUDIO_STRIDE) + 1;
-        if (wb[(size_t)b] > wmax) wmax = wb[(size_t)b];
-    }
-    row.resize((size_t)B); wins.resize((size_t)B);
-    for (int b = 0; b < B; ++b) row[(size_t)b] = b;
-    std::stable_sort(row.begin(), row.end(), [&](int x, int y) { return wb[(size_t)x] > wb[(size_t)y]; });      // descending; ties keep the caller's order
-    for (int s = 0; s < B; ++s) wins[(size_t)s] = wb[(size_t)row[(size_t)s]];
-    bw.assign((size_t)wmax, 0);                     // B_w = clips with W_b > w: count the clips that END at each w, then a running sum from the back
-    for (int b = 0; b < B; ++b) ++bw[(size_t)wb[(size_t)b] - 1];
-    for (int w = wmax - 2; w >= 0; --w) bw[(size_t)w] += bw[(size_t)w + 1];
-}
-
-int ls_long_plan_drop(int32_t batch, int32_t audio_len, const int64_t* audio_lengths, int32_t* slot_row, int32_t* slot_windows,
-                      int32_t* active, int32_t active_capacity, int32_t* n_windows) {
-    if (batch < 1 || audio_len < 1 || !audio_lengths || !n_windows || active_capacity < 0 || (active_capacity > 0 && !active)) return LS_EINVAL;
-    for (int b = 0; b < batch; ++b)
-        if (audio_lengths[b] < 1 || (audio_lengths[b] - audio_len) / LS_LONG_AUDIO_STRIDE > (1 << 20)) return LS_EINVAL;
-    std::vector<int> row, wins, bw;
-    long_plan_drop(batch, audio_len, audio_lengths, row, wins, bw);
-    for (int s = 0; s < batch; ++s) {
-        if (slot_row) slot_row[s] = row[(size_t)s];
-        if (slot_windows) slot_windows[s] = wins[(size_t)s];
-    }
-    for (int w = 0; w < (int)bw.size() && w < active_capacity; ++w) active[w] = bw[(size_t)w];
-    *n_windows = (int32_t)bw.size();
-    return LS_OK;
-}
-
-// ls_long_prepare for clips of different lengths (ls_hip.h): the encoder sees only the clip-windows that exist, gathered from the
-// caller's waveform by k_long_gather_clips and stored packed, window-major in slot order; every window batch is planned and every
-// workspace a captured loop holds by address is sized for all of them here, so that nothing moves once ls_long_sample has begun.
-// The speaker style is ls_long_sample's (per window batch).
-int ls_long_prepare_ragged(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths) {
-    if (!h || !c || !audio_lengths) return fail(h, LS_EINVAL, "ls_long_prepare_ragged: null argument");
-    if (!h->committed) return fail(h, LS_ESTATE, "ls_long_prepare_ragged before ls_commit_weights");
-    if (!h->fused) return fail(h, LS_EUNSUPPORTED, "long-form synthesis chains the reference's %d-frame windows", kT);
-    if (c->batch < 1 || c->n_windows < 1) return fail(h, LS_EINVAL, "batch and n_windows must be >= 1");
-    if (c->audio_samples < 1 || c->encoder_chunk < 0) return fail(h, LS_EINVAL, "ls_long_prepare_ragged: bad audio_samples / encoder_chunk");
-    if (!c->audio || !c->seed_poses || !c->vid_indices || !c->scale) return fail(h, LS_EINVAL, "ls_long_prepare_ragged: null conditioning pointer");
-    if (h->cfg.n_prefix_tokens == 2 && !c->emo) return fail(h, LS_EINVAL, "BEAT variant needs emo ids");
-    if (h->cfg.n_pre_seq < 1) return fail(h, LS_EINVAL, "long-form synthesis needs n_pre_seq >= 1 (the hand-off poses)");
-    if (c->audio_samples > 0x7fffffffLL) return fail(h, LS_EINVAL, "ls_long_prepare_ragged: audio_samples beyond 2^31 - 1");
-    const int B = c->batch, W = c->n_windows, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, od = c->on_device;
-    for (int b = 0; b < B; ++b)
-        if (audio_lengths[b] < 1 || audio_lengths[b] > c->audio_samples)
-            return fail(h, LS_EINVAL, "audio_lengths[%d] = %lld outside [1, %lld]", b, (long long)audio_lengths[b], (long long)c->audio_samples);
-    std::vector<int> row, wins, bw;
-    long_plan_drop(B, AL, audio_lengths, row, wins, bw);
-    if ((int)bw.size() != W) return fail(h, LS_EINVAL, "n_windows is %d, the longest clip needs %d", W, (int)bw.size());
-    std::vector<int> off((size_t)W + 1, 0);
-    for (int w = 0; w < W; ++w) off[(size_t)w + 1] = off[(size_t)w] + bw[(size_t)w];
-    const int total = off[(size_t)W];
-    std::vector<int> table((size_t)total * 2), lens((size_t)B);
-    for (int w = 0, p = 0; w < W; ++w)
-        for (int s = 0; s < bw[(size_t)w]; ++s, ++p) { table[(size_t)2 * p] = row[(size_t)s]; table[(size_t)2 * p + 1] = w; }
-    for (int b = 0; b < B; ++b) lens[(size_t)b] = (int)audio_lengths[b];          // <= audio_samples, checked; the kernel compares in 64 bits
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    int chunk = c->encoder_chunk > 0 ? c->encoder_chunk : 256;
-    if (chunk > 32768) chunk = 32768;                   // one grid row per clip-window of a chunk
-    hipStream_t st = h->stream;
-    int rc;
-    h->prepared = h->lg_prepared = h->lg_ragged = false;
-    end_stream(h);
-    h->seg_next = -1;
-    HIPCHK(h, hipEventRecord(h->ev[4], st));
-    // a device-resident waveform is read in place (the call waits before it returns); a host one is uploaded as it is, unpadded
-    const float* audio = c->audio;
-    if (!od) {
-        if ((rc = ingest(h, h->lg_audio, c->audio, (size_t)B * (size_t)c->audio_samples * sizeof(float), 0)) != LS_OK) return rc;
-        audio = h->lg_audio.f();
-    }
-    if ((rc = ingest(h, h->lg_seed, c->seed_poses, (size_t)B * JF * h->cfg.n_pre_seq * sizeof(float), od)) != LS_OK) return rc;
-    if ((rc = ingest(h, h->vid, c->vid_indices, (size_t)B * sizeof(int64_t), od)) != LS_OK) return rc;
-    if ((rc = ingest(h, h->scale, c->scale, (size_t)B * sizeof(float), od)) != LS_OK) return rc;
-    if (c->emo && (rc = ingest(h, h->lg_emo_ids, c->emo, (size_t)W * B * sizeof(int64_t), od)) != LS_OK) return rc;
-    if ((rc = prepare_scale(h, c->scale, B, od, &h->lg_scale_ones)) != LS_OK) return rc;
-    if ((rc = ingest(h, h->lg_row, row.data(), (size_t)B * sizeof(int), 0)) != LS_OK) return rc;
-    if ((rc = ingest(h, h->lg_lens, lens.data(), (size_t)B * sizeof(int), 0)) != LS_OK) return rc;
-    if ((rc = upload(h, h->lg_table, table.data(), table.size() * sizeof(int))) != LS_OK) return rc;      // waits: host inputs and these temporaries are free again
-    // ---- WavEncoder over the packed clip-windows p = lg_off[w] + slot, `chunk` at a time
-    const int nmax = chunk < total ? chunk : total;
-    HIPCHK(h, h->lg_clips.ensure((size_t)nmax * AL * sizeof(float)));
-    HIPCHK(h, h->lg_featc.ensure((size_t)total * T * kAudioFeat * sizeof(float)));
-    HIPCHK(h, h->lg_featp.ensure((size_t)nmax * T * KPP * sizeof(float)));
-    HIPCHK(h, h->origin_x.ensure((size_t)B * JF * T * sizeof(float)));
-    HIPCHK(h, hipMemsetAsync(h->origin_x.p, 0, (size_t)B * JF * T * sizeof(float), st));
-    for (int p0 = 0; p0 < total; p0 += chunk) {
-        const int n = total - p0 < chunk ? total - p0 : chunk;
-        HIPCHK(h, launch_long_gather_clips(audio, static_cast<const int*>(h->lg_table.p) + (size_t)2 * p0, static_cast<const int*>(h->lg_lens.p), h->lg_clips.f(), n, AL,
-                                           (long long)c->audio_samples, LS_LONG_AUDIO_STRIDE, st));
-        if ((rc = run_wav_encoder(h, h->lg_clips.f(), n)) != LS_OK) return rc;
-        HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f() + (size_t)p0 * T * kAudioFeat, n, JF, KPP, 0, st, T));
-    }
-    // ---- per-batch stages: the buffers at the whole batch (window 0's), the emotion tokens of every window's active clips
-    HIPCHK(h, h->feat_u.ensure((size_t)B * T * KPP * sizeof(float)));
-    HIPCHK(h, hipMemsetAsync(h->feat_u.p, 0, (size_t)B * T * KPP * sizeof(float), st));
-    HIPCHK(h, h->static_c.ensure((size_t)B * T * kD * sizeof(float)));
-    HIPCHK(h, h->static_u.ensure((size_t)B * T * kD * sizeof(float)));
-    if (h->cfg.n_prefix_tokens == 2) {
-        HIPCHK(h, h->emo_tok.ensure((size_t)B * kD * sizeof(float)));
-        HIPCHK(h, h->lg_emotok.ensure((size_t)W * B * kD * sizeof(float)));
-        for (int w = 0; w < W; ++w)                     // ids of (window, slot) pairs that do not run are never read
-            HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->lg_emo_ids.p) + (size_t)w * B, h->lg_emotok.f() + (size_t)w * B * kD,
-                                         bw[(size_t)w], kD, h->cfg.n_emotions, st));
-    }
-    // every buffer a captured loop reads moves only when the batch changes (as in ls_prepare): drop the graphs then, keep them otherwise --
-    // their keys hold the batch and the plan, so the windows of this call find the graphs of the last one
-    if (h->B != B) free_graph(h);
-    // ---- the plan and the workspaces of every window batch, smallest first: the handle is left planned for the whole batch
-    for (int w = W - 1; w >= 0; --w) {
-        if (w + 1 < W && bw[(size_t)w] == bw[(size_t)w + 1]) continue;
-        h->all_scale_one = h->lg_scale_ones >= bw[(size_t)w];
-        set_plan(h, bw[(size_t)w]);
-        if ((rc = plan_workspaces(h)) != LS_OK) return rc;
-    }
-    HIPCHK(h, hipEventRecord(h->ev[5], st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipEventElapsedTime(&h->timing.prepare_ms, h->ev[4], h->ev[5]));
-    h->prepare_pending = false;
-    h->B = B;
-    h->lg_W = W; h->lg_L = (size_t)c->audio_samples;
-    h->lg_bw = bw; h->lg_off = off;
-    h->lg_prepared = h->lg_ragged = true;
-    return LS_OK;
-}
-
-// Opening a stream (ls_long_stream_cond in ls_hip.h): ls_long_prepare without its audio.  The per-batch stages run once at batch B, the
-// window-0 hand-off (k_chain_window from the seed poses) leaves feat_u / origin_x as ls_long_sample's first window finds them, and the
-// buffers a window needs -- the ring, one gathered window, one window's features -- are sized here, so ls_long_stream_push allocates
-// nothing that a captured loop could hold.
-int ls_long_stream_open(ls_handle* h, const ls_long_stream_cond* c) {
-    if (!h || !c) return fail(h, LS_EINVAL, "ls_long_stream_open: null argument");
-    if (!h->committed) return fail(h, LS_ESTATE, "ls_long_stream_open before ls_commit_weights");
-    if (!h->fused) return fail(h, LS_EUNSUPPORTED, "long-form synthesis chains the reference's %d-frame windows", kT);
-    if (c->batch < 1) return fail(h, LS_EINVAL, "batch must be >= 1");
-    if (!c->seed_poses || !c->vid_indices || !c->scale) return fail(h, LS_EINVAL, "ls_long_stream_open: null conditioning pointer");
-    if (h->cfg.n_pre_seq < 1) return fail(h, LS_EINVAL, "long-form synthesis needs n_pre_seq >= 1 (the hand-off poses)");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int B = c->batch, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, od = c->on_device;
-    const int R = (AL + LS_LONG_AUDIO_STRIDE + 3) / 4 * 4;       // a window and the stride to the next; whole float4 groups per clip
-    hipStream_t st = h->stream;
-    int rc;
-    h->prepared = h->lg_prepared = h->lg_ragged = false;
-    h->st_state = ls_handle::kStreamNone;       // a stream that was open ends here; this one opens when everything below has succeeded
-    h->seg_next = -1;
-    HIPCHK(h, hipEventRecord(h->ev[4], st));
-    if ((rc = ingest(h, h->lg_seed, c->seed_poses, (size_t)B * JF * h->cfg.n_pre_seq * sizeof(float), od)) != LS_OK) return rc;
-    if ((rc = ingest(h, h->vid, c->vid_indices, (size_t)B * sizeof(int64_t), od)) != LS_OK) return rc;
-    if ((rc = ingest(h, h->scale, c->scale, (size_t)B * sizeof(float), od)) != LS_OK) return rc;
-    if ((rc = prepare_scale(h, c->scale, B, od)) != LS_OK) return rc;
-    HIPCHK(h, h->st_ring.ensure((size_t)B * R * sizeof(float)));
-    HIPCHK(h, h->lg_clips.ensure((size_t)B * AL * sizeof(float)));
-    HIPCHK(h, h->lg_featc.ensure((size_t)B * T * kAudioFeat * sizeof(float)));
-    HIPCHK(h, h->lg_featp.ensure((size_t)B * T * KPP * sizeof(float)));
-    HIPCHK(h, h->st_text.ensure((size_t)B * kD * sizeof(float)));
-    HIPCHK(h, h->st_emo_ids.ensure((size_t)B * sizeof(int64_t)));
-    HIPCHK(h, h->origin_x.ensure((size_t)B * JF * T * sizeof(float)));
-    HIPCHK(h, hipMemsetAsync(h->origin_x.p, 0, (size_t)B * JF * T * sizeof(float), st));     // frames n_pre.. are zero (RAG.py:110)
-    HIPCHK(h, h->feat_u.ensure((size_t)B * T * KPP * sizeof(float)));
-    HIPCHK(h, hipMemsetAsync(h->feat_u.p, 0, (size_t)B * T * KPP * sizeof(float), st));
-    HIPCHK(h, h->static_c.ensure((size_t)B * T * kD * sizeof(float)));
-    HIPCHK(h, h->static_u.ensure((size_t)B * T * kD * sizeof(float)));
-    if ((rc = prepare_style(h, B)) != LS_OK) return rc;
-    if (h->cfg.n_prefix_tokens == 2) HIPCHK(h, h->emo_tok.ensure((size_t)B * kD * sizeof(float)));
-    if ((rc = prepare_plan(h, B)) != LS_OK) return rc;
-    ChainArgs ca{};         // window 0's prefix poses: the caller's seed poses
-    ca.seed = h->lg_seed.f(); ca.feat_u = h->feat_u.f(); ca.origin_x = h->origin_x.f();
-    ca.JF = JF; ca.T = T; ca.KPP = KPP; ca.n_pre = h->cfg.n_pre_seq; ca.T_total = T; ca.n_next = B;
-    HIPCHK(h, launch_chain_window(ca, B, st));
-    HIPCHK(h, hipEventRecord(h->ev[5], st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipEventElapsedTime(&h->timing.prepare_ms, h->ev[4], h->ev[5]));
-    h->prepare_pending = false;
-    if (h->B != B) free_graph(h);
-    h->B = B;
-    h->st_R = R;
-    h->st_samples = h->st_windows = h->st_frames = 0;
-    h->st_have_emo = h->st_have_text = false;
-    h->st_state = ls_handle::kStreamOpen;
-    return LS_OK;
-}
-
-int ls_long_stream_info(const ls_handle* h, int64_t out[4]) {
-    if (!h || !out) return LS_EINVAL;
-    out[0] = h->st_samples; out[1] = h->st_windows; out[2] = h->st_frames;
-    out[3] = h->st_state == ls_handle::kStreamNone ? 0 : (int64_t)(h->st_ring.bytes + h->lg_clips.bytes + h->lg_featc.bytes);      // as allocated
-    return LS_OK;
-}
 
 int ls_stream_order(int device, void* first, void* then) {
     if (hipSetDevice(device) != hipSuccess) return LS_EHIP;

@@ -1,4 +1,4 @@
-// Window hand-off of long-form synthesis (ls_long_sample, ls_sample.cpp): the model continues a 34-frame clip by conditioning the next
+// Window hand-off of long-form synthesis (ls_long_sample, ls_chain_api.cpp): the model continues a 34-frame clip by conditioning the next
 // one on its last n_pre_seq poses (origin_x[..., :n_pre_seq], RAG.py:110-112).  k_chain_window does everything of that hand-off that
 // touches device memory, so the host copies nothing from the device and does not synchronise between two windows:
 //   * the n_pre rows per clip of feat_u that change with the window ([poses | 1 | 0 pad]: exactly what k_build_feats writes for them;
@@ -68,7 +68,7 @@ hipError_t launch_chain_window(const ChainArgs& a, int B, hipStream_t st) {
     return hipGetLastError();
 }
 
-// One window of a timeline edit (ls_long_edit, ls_sample.cpp; EditArgs in ls_internal.h): the loop's inpainting inputs are cut out of the
+// One window of a timeline edit (ls_long_edit, ls_chain_api.cpp; EditArgs in ls_internal.h): the loop's inpainting inputs are cut out of the
 // timeline on the device and its result goes back the same way, so a window costs two launches beside its loop and no host round trip.
 // Stream order makes the next window's gather see this window's scatter.  One workgroup per clip, the tile of k_chain_window (row stride
 // JF | 1); the timeline, the init plane and the raw window are walked along the frame axis, the internal-layout planes along the channels,

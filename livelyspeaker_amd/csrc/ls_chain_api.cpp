@@ -1,0 +1,702 @@
+// Host side of ls_chain.hip: the chained-window engine behind the long-form entries of include/ls_hip.h.  A chain is a sequence of
+// 34-frame windows of the prepared batch, each one ls_prepare's two static projections plus ls_sample's loop on device-resident inputs
+// (run_window_loop, ls_sample.cpp), handed the last poses of the window before it.  There is one once-per-call stage (check_cond ->
+// start_prepare -> ingest_cond -> size_batch_buffers -> finish_prepare) and one window runner (chain_args -> chain_begin -> run_window
+// per window -> chain_finish); the entries hold what differs: where a window's audio features come from (all windows encoded ahead,
+// packed for clips of different lengths, or one window at a time from a stream's ring) and what stands around a window (k_chain_window
+// ahead of it, k_chain_window behind it, or k_edit_gather / k_edit_scatter).  The host-only plans are ls_chain_plan.cpp.
+#include "ls_handle.h"
+
+#include <cstdint>
+#include <initializer_list>
+#include <vector>
+
+using namespace ls;
+
+namespace {
+
+// ---- the once-per-call stage ----------------------------------------------------------------------------------------------------
+// the refusals every conditioning shares; n_windows: null for a stream, which has none
+int check_cond(ls_handle* h, const char* entry, int batch, const int32_t* n_windows, bool audio_ok, bool pointers_ok, bool emo_ok) {
+    if (!h->committed) return fail(h, LS_ESTATE, "%s before ls_commit_weights", entry);
+    if (!h->fused) return fail(h, LS_EUNSUPPORTED, "long-form synthesis chains the reference's %d-frame windows", kT);
+    if (batch < 1 || (n_windows && *n_windows < 1)) return fail(h, LS_EINVAL, n_windows ? "batch and n_windows must be >= 1" : "batch must be >= 1");
+    if (!audio_ok) return fail(h, LS_EINVAL, "%s: bad audio_samples / encoder_chunk", entry);
+    if (!pointers_ok) return fail(h, LS_EINVAL, "%s: null conditioning pointer", entry);
+    if (!emo_ok) return fail(h, LS_EINVAL, "BEAT variant needs emo ids");
+    if (h->cfg.n_pre_seq < 1) return fail(h, LS_EINVAL, "long-form synthesis needs n_pre_seq >= 1 (the hand-off poses)");
+    return LS_OK;
+}
+
+// the handle's prepared conditioning is replaced from here on; the stage's clock starts
+int start_prepare(ls_handle* h) {
+    h->prepared = h->lg_prepared = h->lg_ragged = false;
+    h->seg_next = -1;
+    HIPCHK(h, hipEventRecord(h->ev[4], h->stream));
+    return LS_OK;
+}
+
+// seed poses, speaker ids, guidance scales and (emo: [n_emo] ids, nullable) the emotion ids; leading_ones as in prepare_scale
+int ingest_cond(ls_handle* h, int B, int od, const float* seed_poses, const int64_t* vid, const float* scale, const int64_t* emo, size_t n_emo,
+                int* leading_ones = nullptr) {
+    int rc;
+    if ((rc = ingest(h, h->lg_seed, seed_poses, (size_t)B * h->JF * h->cfg.n_pre_seq * sizeof(float), od)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->vid, vid, (size_t)B * sizeof(int64_t), od)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->scale, scale, (size_t)B * sizeof(float), od)) != LS_OK) return rc;
+    if (emo && (rc = ingest(h, h->lg_emo_ids, emo, n_emo * sizeof(int64_t), od)) != LS_OK) return rc;
+    return prepare_scale(h, scale, B, od, leading_ones);
+}
+
+// The per-batch buffers of a window at batch B, in two steps with the encoder between them (ls_long_prepare's order of enqueues).
+// origin_x: frames n_pre.. are zero (RAG.py:110); it is also k_build_feats' (unused) pose source, hence ahead of the encoder
+int zero_origin_x(ls_handle* h, int B) {
+    HIPCHK(h, h->origin_x.ensure((size_t)B * h->JF * h->T * sizeof(float)));
+    HIPCHK(h, hipMemsetAsync(h->origin_x.p, 0, (size_t)B * h->JF * h->T * sizeof(float), h->stream));
+    return LS_OK;
+}
+// feat_u: every row zero, k_chain_window writes the prefix rows per window
+int size_batch_buffers(ls_handle* h, int B) {
+    const int T = h->T;
+    hipStream_t st = h->stream;
+    HIPCHK(h, h->feat_u.ensure((size_t)B * T * h->KPP * sizeof(float)));
+    HIPCHK(h, hipMemsetAsync(h->feat_u.p, 0, (size_t)B * T * h->KPP * sizeof(float), st));
+    HIPCHK(h, h->static_c.ensure((size_t)B * T * kD * sizeof(float)));
+    HIPCHK(h, h->static_u.ensure((size_t)B * T * kD * sizeof(float)));
+    if (h->cfg.n_prefix_tokens == 2) HIPCHK(h, h->emo_tok.ensure((size_t)B * kD * sizeof(float)));
+    return LS_OK;
+}
+
+// wait, prepare_ms, and the prepared batch.  Every buffer a captured loop reads moves only when the batch changes (as in ls_prepare):
+// the graphs are dropped then and kept otherwise -- their keys hold the batch and the plan, so the next call finds them
+int finish_prepare(ls_handle* h, int B) {
+    HIPCHK(h, hipEventRecord(h->ev[5], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipEventElapsedTime(&h->timing.prepare_ms, h->ev[4], h->ev[5]));
+    h->prepare_pending = false;
+    if (h->B != B) free_graph(h);
+    h->B = B;
+    return LS_OK;
+}
+
+// ---- the window runner ----------------------------------------------------------------------------------------------------------
+// One call of the engine.  wa is the ls_sample call every window makes: the eight sampler fields of the entry's arguments, device
+// inputs, and per window its tapes.
+struct ChainCall {
+    ls_sample_args wa{};
+    uint64_t seed = 0, sample_offset = 0;
+    bool tape = false;
+    int n_exec = 0;
+    ls_sag* sag = nullptr;          // LivelySpeaker chain: every window starts from the decoder's output (chain_begin)
+    void* sag_st = nullptr;
+    int windows = 0, replays = 0;   // windows run; those served by a graph replay
+    bool pair0 = false;             // the first window ran the single-pass form
+    bool coop_used = false;         // some window ran the sample-split kernel (a ragged call's plan changes per window)
+};
+
+// One window: what changes from one to the next
+struct Window {
+    long long w = 0;                    // index in the chain: PHILOX draws at sample_offset + b + (w << 48)
+    int Bw = 0;                         // clips that run it: slots [0, Bw) of every per-clip buffer
+    const float* featc = nullptr;       // its audio features [Bw][T][256]
+    const float* emo_tok = nullptr;     // BEAT: its emotion tokens [Bw][512]; null: the ones held in emo_tok (a stream)
+    const float* text = nullptr;        // SAG: its text features [Bw][512]
+    const float *x_init = nullptr, *eps_tape = nullptr, *noise_tape = nullptr, *inpaint_noise = nullptr;      // TAPE: its draws
+    bool host_tapes = false;            // ... in host memory: uploaded here, one window at a time (a stream: the staging does not grow with the call)
+    bool resident_inpaint = false;      // a timeline edit: the inpainting planes are on the device (k_edit_gather)
+    CachePolicy policy = kReplace;
+    bool first = false;                 // the first window of the call
+};
+
+// The call prologue, first half -- nothing here touches the device: the refusals every entry shares, and wa.  runs: the call runs at
+// least one window (a push of a stream may run none, and then needs neither tapes nor counters)
+template <class Args>
+int chain_args(ls_handle* h, const char* entry, const Args* a, bool runs, ChainCall& cc) {
+    if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM) return fail(h, LS_EUNSUPPORTED, "%s: DDPM and DDIM loops only", entry);
+    if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EUNSUPPORTED, "%s: TAPE and PHILOX noise only", entry);
+    ls_sample_args& wa = cc.wa;
+    wa.sampler = a->sampler; wa.noise_mode = a->noise_mode; wa.skip_timesteps = a->skip_timesteps; wa.on_device = 1;
+    wa.use_graph = a->use_graph; wa.clip_denoised = a->clip_denoised; wa.two_pass_always = a->two_pass_always; wa.eta = a->eta;
+    const int rc = check_sampler_args(h, &wa);
+    if (rc != LS_OK) return rc;
+    cc.seed = a->seed; cc.sample_offset = a->sample_offset;
+    cc.tape = a->noise_mode == LS_NOISE_TAPE;
+    cc.n_exec = h->n_steps - a->skip_timesteps;
+    if (!runs) return LS_OK;
+    if (cc.tape && (!a->x_init || !a->eps_tape || !a->noise_tape)) return fail(h, LS_EINVAL, "TAPE mode needs x_init, eps_tape and noise_tape");
+    if (!cc.tape && (a->sample_offset >> 48 || (a->sample_offset + (unsigned long long)h->B) >> 48)) return fail(h, LS_EINVAL, "PHILOX: sample_offset + batch must stay below 2^48 (the window index sits above)");
+    return LS_OK;
+}
+
+// ... second half, on the device: the timestep embeddings, and with a SAG decoder its output plane and its all-ones mask
+int chain_begin(ls_handle* h, ChainCall& cc, ls_sag* sag) {
+    int rc;
+    if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
+    h->seg_next = -1;
+    if (!sag) return LS_OK;
+    cc.sag = sag; cc.sag_st = ls_sag_stream(sag);
+    HIPCHK(h, h->lg_init.ensure((size_t)h->B * h->JF * h->T * sizeof(float))); HIPCHK(h, h->lg_mask.ensure((size_t)h->B * h->T));
+    HIPCHK(h, hipMemsetAsync(h->lg_mask.p, 1, (size_t)h->B * h->T, h->stream));
+    cc.wa.init_image = h->lg_init.f();
+    return LS_OK;
+}
+
+// The window body.  feat_u / origin_x hold the window's prefix poses (whoever ran the window before it wrote them).  The loop's launches
+// read the handle's buffers only (static_c / static_u, the tape buffers, xa / xb, callp), none of which moves between windows, so the
+// graph captured for the first window (or by an earlier call with the same key) is replayed for every later one.  The result is
+// x_plane(h, cc.n_exec).
+int run_window(ls_handle* h, ChainCall& cc, const Window& win) {
+    const int Bw = win.Bw, T = h->T, dev = h->cfg.device;
+    hipStream_t st = h->stream;
+    ls_sample_args& wa = cc.wa;
+    int rc;
+    if (win.first) cc.pair0 = single_pass(h, wa.two_pass_always);
+    cc.coop_used = cc.coop_used || seg_n(h, 2) > 0;
+    // the static projections with ls_prepare's arithmetic and shapes: static_u = feat_u . Wpre^T + b; static_c = static_u + feat_c . Waud^T
+    HIPCHK(h, launch_gemm_nt(h->feat_u.f(), h->KPP, h->win_pre.f(), h->KPP, h->win_bias.f(), nullptr, 0, h->static_u.f(), kD, Bw * T, kD, h->KPP, 0, st));
+    HIPCHK(h, launch_gemm_nt(win.featc, kAudioFeat, h->win_aud.f(), kAudioFeat, nullptr, h->static_u.f(), kD, h->static_c.f(), kD, Bw * T, kD, kAudioFeat, 0, st));
+    if (win.emo_tok)
+        HIPCHK(h, hipMemcpyAsync(h->emo_tok.p, win.emo_tok, (size_t)Bw * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (cc.sag) {       // the decoder runs on its own handle's stream, ordered behind the hand-off and ahead of the loop by events
+        if (ls_stream_order(dev, st, cc.sag_st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
+        if (ls_sag_decode_async(cc.sag, Bw, h->origin_x.f(), win.text, static_cast<const unsigned char*>(h->lg_mask.p), h->lg_init.f()) != LS_OK)
+            return fail(h, LS_EHIP, "SAG decode of window %lld: %s", win.w, ls_sag_last_error(cc.sag));
+        if (ls_stream_order(dev, cc.sag_st, st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
+    }
+    if (cc.tape) {
+        wa.x_init = win.x_init; wa.eps_tape = win.eps_tape; wa.noise_tape = win.noise_tape; wa.inpaint_noise = win.inpaint_noise;
+        if (win.host_tapes) {
+            const size_t per_x = (size_t)Bw * h->JF * T, per_e = (size_t)cc.n_exec * 2 * Bw * kD, per_n = (size_t)cc.n_exec * per_x;
+            if ((rc = ingest(h, h->lg_x, win.x_init, per_x * sizeof(float), 0)) != LS_OK || (rc = ingest(h, h->lg_eps, win.eps_tape, per_e * sizeof(float), 0)) != LS_OK ||
+                (rc = ingest(h, h->lg_nz, win.noise_tape, per_n * sizeof(float), 0)) != LS_OK) return rc;
+            wa.x_init = h->lg_x.f(); wa.eps_tape = h->lg_eps.f(); wa.noise_tape = h->lg_nz.f();
+        }
+    }
+    // The loop's advance_tags uploads call_host (24 bytes of pageable memory) as every ls_sample does: the runtime takes such a source into
+    // its staging memory before hipMemcpyAsync returns, which is what makes rewriting it for the next window safe.  It is the one host ->
+    // device copy per window; whether the runtime waits inside it is the runtime's business (not measured).
+    h->call_host = CallParams{cc.seed, cc.sample_offset + ((unsigned long long)win.w << 48), h->tag_base, 0u};
+    int replayed = 0;
+    if ((rc = run_window_loop(h, &wa, win.resident_inpaint, win.first, win.policy, &replayed)) != LS_OK) return rc;
+    cc.replays += replayed;
+    ++cc.windows;
+    return LS_OK;
+}
+
+// The call epilogue: the outputs of a host caller back (a null dst: none), the one wait of the call, and its ls_timing.  coop_check is
+// forced by coop_used because a ragged call's plan at this point is not the plan its windows ran under; where the plan never changed
+// the two agree.
+struct Egress { void* dst; const void* src; size_t bytes; };
+int chain_finish(ls_handle* h, const ChainCall& cc, std::initializer_list<Egress> outs) {
+    hipStream_t st = h->stream;
+    int rc;
+    HIPCHK(h, hipEventRecord(h->ev[2], st));
+    for (const Egress& o : outs)
+        if (o.dst && (rc = egress(h, o.dst, o.src, o.bytes, 0)) != LS_OK) return rc;
+    HIPCHK(h, hipEventRecord(h->ev[3], st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if ((rc = coop_check(h, cc.coop_used)) != LS_OK) return rc;
+    report_path(h, cc.pair0);
+    HIPCHK(h, hipEventElapsedTime(&h->timing.loop_ms, h->ev[1], h->ev[2]));
+    HIPCHK(h, hipEventElapsedTime(&h->timing.total_ms, h->ev[6], h->ev[3]));       // ev[6]: the first window's start (ev[0] is re-recorded by every window)
+    h->timing.n_step_launches = cc.windows * cc.n_exec;
+    h->timing.single_pass = cc.pair0 ? 1 : 0;
+    h->timing.graph_replayed = cc.replays;       // windows served by a replay: all but the first after a capture, all on a warm handle
+    h->timing.tape_upload_ms = 0.f;
+    h->timing.n_segments = cc.windows;
+    return LS_OK;
+}
+
+// copy `take` samples of every clip from chunk column c0 (rows n apart) into the ring behind the stream's last sample: one strided copy,
+// two where the ring wraps
+int ring_write(ls_handle* h, const float* chunk, long long n, long long c0, int take, int od) {
+    const int B = h->B, R = h->st_R, p = (int)(h->st_samples % R), seg1 = take < R - p ? take : R - p;
+    const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    HIPCHK(h, hipMemcpy2DAsync(h->st_ring.f() + p, (size_t)R * sizeof(float), chunk + c0, (size_t)n * sizeof(float), (size_t)seg1 * sizeof(float), B, kind, h->stream));
+    if (take > seg1)
+        HIPCHK(h, hipMemcpy2DAsync(h->st_ring.p, (size_t)R * sizeof(float), chunk + c0 + seg1, (size_t)n * sizeof(float), (size_t)(take - seg1) * sizeof(float), B, kind, h->stream));
+    return LS_OK;
+}
+
+// Everything of a push behind its argument checks: feed the ring, run the windows that complete.  Per window the encoder stands in
+// front (k_stream_gather -> WavEncoder -> k_build_feats into the one-window feature buffer) and the hand-off behind: k_chain_window
+// flushes the window into the call's output AND writes the next window's prefix poses into feat_u / origin_x, where they wait for the
+// push that runs it (nothing but a call that ends the stream writes either).
+int stream_push_run(ls_handle* h, const ls_long_stream_push_args* a, ChainCall& cc, long long k) {
+    const int B = h->B, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, AL = h->cfg.audio_len, R = h->st_R, od = a->on_device;
+    const int cap = a->capacity;
+    hipStream_t st = h->stream;
+    int rc;
+    const size_t per_x = (size_t)B * JF * T, per_e = (size_t)cc.n_exec * 2 * B * kD, per_n = (size_t)cc.n_exec * per_x;
+    // the held conditioning: what this call passes holds for every window started from here on
+    if (a->emo) {
+        if ((rc = ingest(h, h->st_emo_ids, a->emo, (size_t)B * sizeof(int64_t), od)) != LS_OK) return rc;
+        HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->st_emo_ids.p), h->emo_tok.f(), B, kD, h->cfg.n_emotions, st));
+        h->st_have_emo = true;
+    }
+    if (a->text_features) {
+        if ((rc = ingest(h, h->st_text, a->text_features, (size_t)B * kD * sizeof(float), od)) != LS_OK) return rc;
+        h->st_have_text = true;
+    }
+    float* out = a->frames;
+    if (k > 0) {
+        if ((rc = chain_begin(h, cc, a->sag)) != LS_OK) return rc;
+        if (!od) { HIPCHK(h, h->lg_timeline.ensure((size_t)B * JF * cap * sizeof(float))); out = h->lg_timeline.f(); }
+    }
+    ChainArgs ca{};
+    ca.feat_u = h->feat_u.f(); ca.origin_x = h->origin_x.f(); ca.timeline = out;
+    ca.JF = JF; ca.T = T; ca.KPP = h->KPP; ca.n_pre = npre; ca.T_total = cap; ca.n_next = B;
+    int t_off = 0;
+    long long ran = 0, fed = 0;
+    const long long n = a->n_samples;
+    while (fed < n || ran < k) {
+        // as much of the chunk as the ring has room for: the samples below the next window's first one are dead
+        const long long room = R - (h->st_samples - (long long)LS_LONG_AUDIO_STRIDE * h->st_windows);
+        const int take = (int)(n - fed < room ? n - fed : room);
+        if (take > 0) {
+            if ((rc = ring_write(h, a->audio, n, fed, take, od)) != LS_OK) return rc;
+            fed += take; h->st_samples += take;
+        }
+        int64_t w0 = 0, kw = 0;         // the windows complete now; in the closing call, once the chunk is in, the padded ones too
+        if (ls_long_stream_plan(h->st_samples, 0, AL, a->closing && fed == n, &w0, &kw) != LS_OK) return fail(h, LS_EINVAL, "ls_long_stream_push: closing a stream that was fed no sample");
+        const long long upto = w0 + kw;
+        if (take == 0 && upto <= h->st_windows) return fail(h, LS_ESTATE, "ls_long_stream_push: no room in the ring and no window to run");
+        for (long long w = h->st_windows; w < upto; ++w, ++ran) {
+            if (ran >= k) return fail(h, LS_ESTATE, "ls_long_stream_push: more windows complete than the call was planned for");
+            const long long lo = w * LS_LONG_AUDIO_STRIDE, have = h->st_samples - lo;
+            HIPCHK(h, launch_stream_gather(h->st_ring.f(), h->lg_clips.f(), B, AL, R, (int)(lo % R), (int)(have < AL ? (have < 0 ? 0 : have) : AL), st));
+            if ((rc = run_wav_encoder(h, h->lg_clips.f(), B)) != LS_OK) return rc;
+            HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f(), B, JF, h->KPP, 0, st, T));
+            Window win;
+            win.w = w; win.Bw = B; win.featc = h->lg_featc.f(); win.text = h->st_text.f(); win.first = ran == 0;
+            if (cc.tape) {      // this window's draws; host ones are uploaded by the body
+                win.x_init = a->x_init + (size_t)ran * per_x; win.eps_tape = a->eps_tape + (size_t)ran * per_e; win.noise_tape = a->noise_tape + (size_t)ran * per_n;
+                win.host_tapes = !od;
+            }
+            if ((rc = run_window(h, cc, win)) != LS_OK) return rc;
+            // hand-off: the window leaves through the call's output, the next window's prefix poses enter feat_u / origin_x
+            ca.prev = x_plane(h, cc.n_exec);
+            ca.f0 = w == 0 ? 0 : npre; ca.t_off = t_off;
+            HIPCHK(h, launch_chain_window(ca, B, st));
+            t_off += T - ca.f0;
+            h->st_windows = w + 1;
+        }
+    }
+    h->st_frames += t_off;
+    if (a->n_frames) *a->n_frames = t_off;
+    if (a->n_windows) *a->n_windows = (int32_t)ran;
+    if (a->closing) h->st_state = ls_handle::kStreamClosed;
+    if (ran == 0) {         // no sampling work: a host chunk is the caller's again once its copies are done, a device chunk is read in stream order
+        if (!od && n > 0) { HIPCHK(h, hipEventRecord(h->ev[6], st)); HIPCHK(h, hipEventSynchronize(h->ev[6])); }
+        return LS_OK;
+    }
+    return chain_finish(h, cc, {{od ? nullptr : a->frames, out, (size_t)B * JF * cap * sizeof(float)}});
+}
+
+}  // namespace
+
+extern "C" {
+
+// Once-per-call stage of a long-form call (ls_long_cond in ls_hip.h).  The WavEncoder has no term that couples clips (InstanceNorm is per
+// clip and channel), so the W * B clip-windows go through it in chunks of any size and leave the features ls_prepare would compute for
+// each window at batch B; k_build_feats turns a chunk's conv4 block into its rows of the feature store (its feat_p half goes to a scratch:
+// the prefix rows are k_chain_window's).  Everything else is ls_prepare's own stage at batch B.
+int ls_long_prepare(ls_handle* h, const ls_long_cond* c) {
+    if (!h || !c) return fail(h, LS_EINVAL, "ls_long_prepare: null argument");
+    int rc;
+    if ((rc = check_cond(h, "ls_long_prepare", c->batch, &c->n_windows, c->audio_samples >= 1 && c->encoder_chunk >= 0,
+                         c->audio && c->seed_poses && c->vid_indices && c->scale, h->cfg.n_prefix_tokens != 2 || c->emo)) != LS_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int B = c->batch, W = c->n_windows, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, od = c->on_device;
+    const size_t L = (size_t)AL + (size_t)(W - 1) * LS_LONG_AUDIO_STRIDE, Lin = (size_t)c->audio_samples < L ? (size_t)c->audio_samples : L;
+    const int chunk = c->encoder_chunk > 0 ? c->encoder_chunk : 256;
+    const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    hipStream_t st = h->stream;
+    end_stream(h);
+    if ((rc = start_prepare(h)) != LS_OK) return rc;
+    HIPCHK(h, h->lg_audio.ensure((size_t)B * L * sizeof(float)));
+    if (Lin < L) HIPCHK(h, hipMemsetAsync(h->lg_audio.p, 0, (size_t)B * L * sizeof(float), st));
+    HIPCHK(h, hipMemcpy2DAsync(h->lg_audio.p, L * sizeof(float), c->audio, (size_t)c->audio_samples * sizeof(float), Lin * sizeof(float), B, kind, st));
+    if ((rc = ingest_cond(h, B, od, c->seed_poses, c->vid_indices, c->scale, c->emo, (size_t)W * B)) != LS_OK) return rc;
+    if (!od) HIPCHK(h, hipStreamSynchronize(st));       // host inputs are the caller's again
+    // ---- WavEncoder over the clip-windows cw = w * B + b, `chunk` at a time
+    const int ncw = W * B, nmax = chunk < ncw ? chunk : ncw;
+    HIPCHK(h, h->lg_clips.ensure((size_t)nmax * AL * sizeof(float)));
+    HIPCHK(h, h->lg_featc.ensure((size_t)ncw * T * kAudioFeat * sizeof(float)));
+    HIPCHK(h, h->lg_featp.ensure((size_t)nmax * T * KPP * sizeof(float)));
+    if ((rc = zero_origin_x(h, B)) != LS_OK) return rc;
+    for (int cw0 = 0; cw0 < ncw; cw0 += chunk) {
+        const int n = ncw - cw0 < chunk ? ncw - cw0 : chunk;
+        for (int cw = cw0; cw < cw0 + n;) {             // one strided copy per run of clips of the same window
+            const int w = cw / B, b = cw - w * B, run = (B - b) < (cw0 + n - cw) ? (B - b) : (cw0 + n - cw);
+            HIPCHK(h, hipMemcpy2DAsync(h->lg_clips.f() + (size_t)(cw - cw0) * AL, (size_t)AL * sizeof(float),
+                                       h->lg_audio.f() + (size_t)b * L + (size_t)w * LS_LONG_AUDIO_STRIDE, L * sizeof(float), (size_t)AL * sizeof(float), run,
+                                       hipMemcpyDeviceToDevice, st));
+            cw += run;
+        }
+        if ((rc = run_wav_encoder(h, h->lg_clips.f(), n)) != LS_OK) return rc;
+        HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f() + (size_t)cw0 * T * kAudioFeat, n, JF, KPP, 0, st, T));
+    }
+    // ---- per-batch stages, once: the buffers, style, emotion tokens, plan
+    if ((rc = size_batch_buffers(h, B)) != LS_OK) return rc;
+    if ((rc = prepare_style(h, B)) != LS_OK) return rc;
+    if (h->cfg.n_prefix_tokens == 2) {
+        HIPCHK(h, h->lg_emotok.ensure((size_t)W * B * kD * sizeof(float)));
+        HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->lg_emo_ids.p), h->lg_emotok.f(), W * B, kD, h->cfg.n_emotions, st));
+    }
+    if ((rc = prepare_plan(h, B)) != LS_OK) return rc;
+    if ((rc = finish_prepare(h, B)) != LS_OK) return rc;
+    h->lg_W = W; h->lg_L = L;
+    h->lg_prepared = true;      // `prepared` stays false: the static projections exist per window, inside ls_long_sample only
+    return LS_OK;
+}
+
+// ls_long_prepare for clips of different lengths (ls_hip.h): the encoder sees only the clip-windows that exist, gathered from the
+// caller's waveform by k_long_gather_clips and stored packed, window-major in slot order; every window batch is planned and every
+// workspace a captured loop holds by address is sized for all of them here, so that nothing moves once ls_long_sample has begun.
+// The speaker style is ls_long_sample's (per window batch).
+int ls_long_prepare_ragged(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths) {
+    if (!h || !c || !audio_lengths) return fail(h, LS_EINVAL, "ls_long_prepare_ragged: null argument");
+    int rc;
+    if ((rc = check_cond(h, "ls_long_prepare_ragged", c->batch, &c->n_windows, c->audio_samples >= 1 && c->encoder_chunk >= 0,
+                         c->audio && c->seed_poses && c->vid_indices && c->scale, h->cfg.n_prefix_tokens != 2 || c->emo)) != LS_OK) return rc;
+    if (c->audio_samples > 0x7fffffffLL) return fail(h, LS_EINVAL, "ls_long_prepare_ragged: audio_samples beyond 2^31 - 1");
+    const int B = c->batch, W = c->n_windows, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, od = c->on_device;
+    for (int b = 0; b < B; ++b)
+        if (audio_lengths[b] < 1 || audio_lengths[b] > c->audio_samples)
+            return fail(h, LS_EINVAL, "audio_lengths[%d] = %lld outside [1, %lld]", b, (long long)audio_lengths[b], (long long)c->audio_samples);
+    std::vector<int> row, wins, bw;
+    long_plan_drop(B, AL, audio_lengths, row, wins, bw);
+    if ((int)bw.size() != W) return fail(h, LS_EINVAL, "n_windows is %d, the longest clip needs %d", W, (int)bw.size());
+    std::vector<int> off((size_t)W + 1, 0);
+    for (int w = 0; w < W; ++w) off[(size_t)w + 1] = off[(size_t)w] + bw[(size_t)w];
+    const int total = off[(size_t)W];
+    std::vector<int> table((size_t)total * 2), lens((size_t)B);
+    for (int w = 0, p = 0; w < W; ++w)
+        for (int s = 0; s < bw[(size_t)w]; ++s, ++p) { table[(size_t)2 * p] = row[(size_t)s]; table[(size_t)2 * p + 1] = w; }
+    for (int b = 0; b < B; ++b) lens[(size_t)b] = (int)audio_lengths[b];          // <= audio_samples, checked; the kernel compares in 64 bits
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int chunk = c->encoder_chunk > 0 ? c->encoder_chunk : 256;
+    if (chunk > 32768) chunk = 32768;                   // one grid row per clip-window of a chunk
+    hipStream_t st = h->stream;
+    end_stream(h);
+    if ((rc = start_prepare(h)) != LS_OK) return rc;
+    // a device-resident waveform is read in place (the call waits before it returns); a host one is uploaded as it is, unpadded
+    const float* audio = c->audio;
+    if (!od) {
+        if ((rc = ingest(h, h->lg_audio, c->audio, (size_t)B * (size_t)c->audio_samples * sizeof(float), 0)) != LS_OK) return rc;
+        audio = h->lg_audio.f();
+    }
+    if ((rc = ingest_cond(h, B, od, c->seed_poses, c->vid_indices, c->scale, c->emo, (size_t)W * B, &h->lg_scale_ones)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->lg_row, row.data(), (size_t)B * sizeof(int), 0)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->lg_lens, lens.data(), (size_t)B * sizeof(int), 0)) != LS_OK) return rc;
+    if ((rc = upload(h, h->lg_table, table.data(), table.size() * sizeof(int))) != LS_OK) return rc;      // waits: host inputs and these temporaries are free again
+    // ---- WavEncoder over the packed clip-windows p = lg_off[w] + slot, `chunk` at a time
+    const int nmax = chunk < total ? chunk : total;
+    HIPCHK(h, h->lg_clips.ensure((size_t)nmax * AL * sizeof(float)));
+    HIPCHK(h, h->lg_featc.ensure((size_t)total * T * kAudioFeat * sizeof(float)));
+    HIPCHK(h, h->lg_featp.ensure((size_t)nmax * T * KPP * sizeof(float)));
+    if ((rc = zero_origin_x(h, B)) != LS_OK) return rc;
+    for (int p0 = 0; p0 < total; p0 += chunk) {
+        const int n = total - p0 < chunk ? total - p0 : chunk;
+        HIPCHK(h, launch_long_gather_clips(audio, static_cast<const int*>(h->lg_table.p) + (size_t)2 * p0, static_cast<const int*>(h->lg_lens.p), h->lg_clips.f(), n, AL,
+                                           (long long)c->audio_samples, LS_LONG_AUDIO_STRIDE, st));
+        if ((rc = run_wav_encoder(h, h->lg_clips.f(), n)) != LS_OK) return rc;
+        HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f() + (size_t)p0 * T * kAudioFeat, n, JF, KPP, 0, st, T));
+    }
+    if ((rc = size_batch_buffers(h, B)) != LS_OK) return rc;        // at the whole batch: window 0's
+    if (h->cfg.n_prefix_tokens == 2) {                  // the emotion tokens of every window's active clips
+        HIPCHK(h, h->lg_emotok.ensure((size_t)W * B * kD * sizeof(float)));
+        for (int w = 0; w < W; ++w)                     // ids of (window, slot) pairs that do not run are never read
+            HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->lg_emo_ids.p) + (size_t)w * B, h->lg_emotok.f() + (size_t)w * B * kD,
+                                         bw[(size_t)w], kD, h->cfg.n_emotions, st));
+    }
+    // ---- the plan and the workspaces of every window batch, smallest first: the handle is left planned for the whole batch
+    for (int w = W - 1; w >= 0; --w) {
+        if (w + 1 < W && bw[(size_t)w] == bw[(size_t)w + 1]) continue;
+        h->all_scale_one = h->lg_scale_ones >= bw[(size_t)w];
+        set_plan(h, bw[(size_t)w]);
+        if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+    }
+    if ((rc = finish_prepare(h, B)) != LS_OK) return rc;
+    h->lg_W = W; h->lg_L = (size_t)c->audio_samples;
+    h->lg_bw = bw; h->lg_off = off;
+    h->lg_prepared = h->lg_ragged = true;
+    return LS_OK;
+}
+
+// Opening a stream (ls_long_stream_cond in ls_hip.h): ls_long_prepare without its audio.  The per-batch stages run once at batch B, the
+// window-0 hand-off (k_chain_window from the seed poses) leaves feat_u / origin_x as ls_long_sample's first window finds them, and the
+// buffers a window needs -- the ring, one gathered window, one window's features -- are sized here, so ls_long_stream_push allocates
+// nothing that a captured loop could hold.
+int ls_long_stream_open(ls_handle* h, const ls_long_stream_cond* c) {
+    if (!h || !c) return fail(h, LS_EINVAL, "ls_long_stream_open: null argument");
+    int rc;
+    if ((rc = check_cond(h, "ls_long_stream_open", c->batch, nullptr, true, c->seed_poses && c->vid_indices && c->scale, true)) != LS_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int B = c->batch, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, od = c->on_device;
+    const int R = (AL + LS_LONG_AUDIO_STRIDE + 3) / 4 * 4;       // a window and the stride to the next; whole float4 groups per clip
+    hipStream_t st = h->stream;
+    h->st_state = ls_handle::kStreamNone;       // a stream that was open ends here; this one opens when everything below has succeeded
+    if ((rc = start_prepare(h)) != LS_OK) return rc;
+    if ((rc = ingest_cond(h, B, od, c->seed_poses, c->vid_indices, c->scale, nullptr, 0)) != LS_OK) return rc;
+    HIPCHK(h, h->st_ring.ensure((size_t)B * R * sizeof(float)));
+    HIPCHK(h, h->lg_clips.ensure((size_t)B * AL * sizeof(float)));
+    HIPCHK(h, h->lg_featc.ensure((size_t)B * T * kAudioFeat * sizeof(float)));
+    HIPCHK(h, h->lg_featp.ensure((size_t)B * T * KPP * sizeof(float)));
+    HIPCHK(h, h->st_text.ensure((size_t)B * kD * sizeof(float)));
+    HIPCHK(h, h->st_emo_ids.ensure((size_t)B * sizeof(int64_t)));
+    if ((rc = zero_origin_x(h, B)) != LS_OK || (rc = size_batch_buffers(h, B)) != LS_OK) return rc;
+    if ((rc = prepare_style(h, B)) != LS_OK) return rc;
+    if ((rc = prepare_plan(h, B)) != LS_OK) return rc;
+    ChainArgs ca{};         // window 0's prefix poses: the caller's seed poses
+    ca.seed = h->lg_seed.f(); ca.feat_u = h->feat_u.f(); ca.origin_x = h->origin_x.f();
+    ca.JF = JF; ca.T = T; ca.KPP = KPP; ca.n_pre = h->cfg.n_pre_seq; ca.T_total = T; ca.n_next = B;
+    HIPCHK(h, launch_chain_window(ca, B, st));
+    if ((rc = finish_prepare(h, B)) != LS_OK) return rc;
+    h->st_R = R;
+    h->st_samples = h->st_windows = h->st_frames = 0;
+    h->st_have_emo = h->st_have_text = false;
+    h->st_state = ls_handle::kStreamOpen;
+    return LS_OK;
+}
+
+int ls_long_stream_info(const ls_handle* h, int64_t out[4]) {
+    if (!h || !out) return LS_EINVAL;
+    out[0] = h->st_samples; out[1] = h->st_windows; out[2] = h->st_frames;
+    out[3] = h->st_state == ls_handle::kStreamNone ? 0 : (int64_t)(h->st_ring.bytes + h->lg_clips.bytes + h->lg_featc.bytes);      // as allocated
+    return LS_OK;
+}
+
+// Long-form synthesis (ls_long_sample_args in ls_hip.h): per window the hand-off kernel, then the window body; one wait at the end.
+//
+// After ls_long_prepare_ragged window w runs the lg_bw[w] clips that still have audio: slots [0, lg_bw[w]) of every per-clip buffer
+// (the clips are held longest-first), the packed stores at lg_off[w].  Each window is then, decision for decision, a call at batch
+// lg_bw[w]: its scales decide the single-pass form, its batch the step plan (set_plan), the plan the workspaces' accounting
+// (plan_workspaces; ls_long_prepare_ragged sized them for every window, so nothing a captured loop holds moves here), and the speaker
+// style runs at that batch.  A window batch that serves two or more windows is captured once and replayed; one that serves a single
+// window runs as stream launches unless an earlier call left its graph behind.
+int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_sample: null argument");
+    if (!h->lg_prepared) return fail(h, LS_ESTATE, "ls_long_sample before ls_long_prepare");
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_sample before ls_set_schedule");
+    if (!a->timeline) return fail(h, LS_EINVAL, "ls_long_sample: null timeline");
+    if (a->sag && !a->text_features) return fail(h, LS_EINVAL, "ls_long_sample: sag without text_features");
+    const bool rg = h->lg_ragged, beat = h->cfg.n_prefix_tokens == 2;
+    const int B = h->B, W = h->lg_W, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, od = a->on_device;
+    const int Tt = T + (W - 1) * (T - npre);
+    if (rg && ((int)h->lg_bw.size() != W || (int)h->lg_off.size() != W + 1 || h->lg_bw[0] != B)) return fail(h, LS_ESTATE, "ls_long_sample: the ragged plan does not match the prepared batch");
+    auto batch_of = [&](int w) { return rg ? h->lg_bw[(size_t)w] : B; };                      // clips that run window w
+    auto first_of = [&](int w) { return (size_t)(rg ? h->lg_off[(size_t)w] : w * B); };       // clip-windows ahead of window w in the packed stores
+    ChainCall cc;
+    int rc;
+    if ((rc = chain_args(h, "ls_long_sample", a, true, cc)) != LS_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = chain_begin(h, cc, a->sag)) != LS_OK) return rc;
+    hipStream_t st = h->stream;
+    const int n_exec = cc.n_exec;
+    const size_t per_x = (size_t)JF * T, per_e = (size_t)n_exec * 2 * kD, per_n = (size_t)n_exec * per_x;     // floats per clip-window: x_T, eps tape, noise tape
+    const size_t nelem = (size_t)B * per_x, nx = nelem * sizeof(float), total = first_of(W);
+    // host tapes / text features: one upload per call; device ones are read in place
+    const float *xs = a->x_init, *es = a->eps_tape, *ns = a->noise_tape, *tx = a->text_features;
+    if (cc.tape && !od) {
+        if ((rc = ingest(h, h->lg_x, xs, total * per_x * sizeof(float), 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, total * per_e * sizeof(float), 0)) != LS_OK ||
+            (rc = ingest(h, h->lg_nz, ns, total * per_n * sizeof(float), 0)) != LS_OK) return rc;
+        xs = h->lg_x.f(); es = h->lg_eps.f(); ns = h->lg_nz.f();
+    }
+    if (a->sag && !od) { if ((rc = ingest(h, h->lg_text, tx, (size_t)W * B * kD * sizeof(float), 0)) != LS_OK) return rc; tx = h->lg_text.f(); }
+    float* tl = a->timeline;
+    float* wd = a->windows;
+    if (!od) {
+        HIPCHK(h, h->lg_timeline.ensure((size_t)B * JF * Tt * sizeof(float)));
+        if (wd) HIPCHK(h, h->lg_windows.ensure(W * nx));
+        tl = h->lg_timeline.f();
+        if (wd) wd = h->lg_windows.f();
+    }
+    if (rg) {
+        // what a clip does not reach stays zero: its timeline beyond its own frames, its raw windows from its window count on
+        HIPCHK(h, hipMemsetAsync(tl, 0, (size_t)B * JF * Tt * sizeof(float), st));
+        if (wd) HIPCHK(h, hipMemsetAsync(wd, 0, W * nx, st));
+        // Room in the graph cache for the batches this call captures (at most the cache's bound; the rest run as stream launches), made
+        // now: nothing of this call is in flight yet.  The same window batches as the last ragged call: its graphs are this call's.
+        if (h->graphs_for != h->lg_bw) {
+            int repeated = 0;
+            for (int w = 1; w < W; ++w) if (h->lg_bw[(size_t)w] == h->lg_bw[(size_t)w - 1] && (w < 2 || h->lg_bw[(size_t)w - 1] != h->lg_bw[(size_t)w - 2])) ++repeated;
+            if (repeated > ls_handle::kGraphCacheMax) repeated = ls_handle::kGraphCacheMax;
+            if ((int)h->graphs.size() + repeated > ls_handle::kGraphCacheMax) free_graph(h);
+            h->graphs_for = h->lg_bw;
+        }
+    }
+    ChainArgs ca{};
+    ca.seed = h->lg_seed.f(); ca.timeline = tl;
+    ca.JF = JF; ca.T = T; ca.KPP = h->KPP; ca.n_pre = npre; ca.T_total = Tt;
+    ca.row = rg ? static_cast<const int*>(h->lg_row.p) : nullptr;
+    int styled = 0;
+    for (int w = 0; w <= W; ++w) {
+        const int Bw = w < W ? batch_of(w) : 0, Bprev = w ? batch_of(w - 1) : 0;
+        // hand-off: window w - 1 leaves through the timeline, window w's prefix poses enter feat_u / origin_x
+        ca.prev = w ? x_plane(h, n_exec) : nullptr;
+        ca.feat_u = w < W ? h->feat_u.f() : nullptr; ca.origin_x = h->origin_x.f();
+        ca.f0 = w == 1 ? 0 : npre; ca.t_off = w <= 1 ? 0 : T + (w - 2) * (T - npre);
+        ca.window = (w && wd) ? wd + (size_t)(w - 1) * nelem : nullptr;
+        ca.n_next = Bw;
+        HIPCHK(h, launch_chain_window(ca, w ? Bprev : Bw, st));
+        if (w == W) break;
+        Window win;
+        win.w = w; win.Bw = Bw; win.first = w == 0;
+        if (rg) {           // from here on the handle is prepared for a batch of Bw
+            h->B = Bw;
+            h->all_scale_one = h->lg_scale_ones >= Bw;
+            set_plan(h, Bw);
+            if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+            if (styled != Bw && (rc = prepare_style(h, Bw)) != LS_OK) return rc;
+            styled = Bw;
+            int serves = 0;
+            for (int v = 0; v < W; ++v) serves += h->lg_bw[(size_t)v] == Bw;
+            win.policy = serves >= 2 ? kKeep : kReplayOnly;
+        }
+        win.featc = h->lg_featc.f() + first_of(w) * T * kAudioFeat;
+        if (beat) win.emo_tok = h->lg_emotok.f() + (size_t)w * B * kD;
+        if (a->sag) win.text = tx + (size_t)w * B * kD;
+        if (cc.tape) { win.x_init = xs + first_of(w) * per_x; win.eps_tape = es + first_of(w) * per_e; win.noise_tape = ns + first_of(w) * per_n; }
+        if ((rc = run_window(h, cc, win)) != LS_OK) return rc;
+    }
+    if (rg) {               // leave the handle as ls_long_prepare_ragged left it: prepared for the whole batch
+        h->B = B;
+        h->all_scale_one = h->lg_scale_ones >= B;
+        set_plan(h, B);
+        if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+    }
+    return chain_finish(h, cc, {{od ? nullptr : a->timeline, tl, (size_t)B * JF * Tt * sizeof(float)}, {od || !wd ? nullptr : a->windows, wd, W * nx}});
+}
+
+int ls_long_stream_push(ls_handle* h, const ls_long_stream_push_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_stream_push: null argument");
+    switch (h->st_state) {
+    case ls_handle::kStreamOpen: break;
+    case ls_handle::kStreamNone: return fail(h, LS_ESTATE, "ls_long_stream_push before ls_long_stream_open");
+    case ls_handle::kStreamClosed: return fail(h, LS_ESTATE, "ls_long_stream_push: the stream is closed");
+    case ls_handle::kStreamFailed: return fail(h, LS_ESTATE, "ls_long_stream_push: an earlier push of this stream failed; open a new one");
+    default: return fail(h, LS_ESTATE, "ls_long_stream_push: the stream was ended by a call that replaced the handle's prepared conditioning "
+                                       "(ls_prepare, ls_long_prepare, ls_commit_weights or another ls_long_stream_open); open a new one");
+    }
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_stream_push before ls_set_schedule");
+    if (a->n_samples < 0 || (a->n_samples > 0 && !a->audio)) return fail(h, LS_EINVAL, "ls_long_stream_push: n_samples %lld with%s audio", (long long)a->n_samples, a->audio ? "" : "out");
+    if (a->capacity < 0 || (a->capacity > 0 && !a->frames)) return fail(h, LS_EINVAL, "ls_long_stream_push: capacity without frames");
+    if (a->text_features && !a->sag) return fail(h, LS_EINVAL, "ls_long_stream_push: text_features without sag");
+    if (a->emo && h->cfg.n_prefix_tokens != 2) return fail(h, LS_EINVAL, "ls_long_stream_push: emo is a BEAT conditioning");
+    int64_t first = 0, k = 0;
+    if (ls_long_stream_plan(h->st_samples, a->n_samples, h->cfg.audio_len, a->closing, &first, &k) != LS_OK)
+        return fail(h, LS_EINVAL, "ls_long_stream_push: closing a stream that was fed no sample");
+    if (first != h->st_windows) return fail(h, LS_ESTATE, "ls_long_stream_push: %lld windows have run, %lld were complete", h->st_windows, (long long)first);
+    const int T = h->T, npre = h->cfg.n_pre_seq;
+    const int64_t need = k == 0 ? 0 : k * (T - npre) + (first == 0 ? npre : 0);
+    if (need > a->capacity) return fail(h, LS_EINVAL, "ls_long_stream_push: this call runs %lld windows = %lld frames, capacity is %d", (long long)k, (long long)need, a->capacity);
+    ChainCall cc;
+    int rc;
+    if ((rc = chain_args(h, "ls_long_stream_push", a, k > 0, cc)) != LS_OK) return rc;
+    if (k > 0) {
+        if (h->cfg.n_prefix_tokens == 2 && !a->emo && !h->st_have_emo) return fail(h, LS_EINVAL, "ls_long_stream_push: the BEAT variant's first window needs emo ids");
+        if (a->sag && !a->text_features && !h->st_have_text) return fail(h, LS_EINVAL, "ls_long_stream_push: sag needs text_features for the first window");
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    rc = stream_push_run(h, a, cc, k);
+    if (rc != LS_OK) {      // the ring and the hand-off poses may be half written: the stream is over, the handle is not
+        h->st_state = ls_handle::kStreamFailed;
+        (void)hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+// Timeline edit (ls_long_edit_args in ls_hip.h): the window body over the windows of ls_long_edit_plan, with k_edit_gather ahead of a
+// window and k_edit_scatter behind it in place of the hand-off kernel, and the loop run with the inpainting branch on the planes the
+// gather left on the device.  The loop's key holds the inpainting form.  One wait at the end.
+int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_edit: null argument");
+    if (!h->lg_prepared) return fail(h, LS_ESTATE, "ls_long_edit before ls_long_prepare");
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_edit before ls_set_schedule");
+    if (h->lg_ragged) return fail(h, LS_EUNSUPPORTED, "ls_long_edit: a handle prepared by ls_long_prepare_ragged is not edited (ragged batches are not built)");
+    if (!a->timeline) return fail(h, LS_EINVAL, "ls_long_edit: null timeline");
+    if (!a->frame_lo || !a->frame_hi) return fail(h, LS_EINVAL, "ls_long_edit: null frame_lo / frame_hi");
+    if (a->windows_capacity < 0 || (a->windows_capacity > 0 && !a->windows_run)) return fail(h, LS_EINVAL, "ls_long_edit: windows_capacity without windows_run");
+    const int B = h->B, W = h->lg_W, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, od = a->on_device;
+    const int Tt = T + (W - 1) * (T - npre);
+    // per clip [lo, hi) and the channel bytes; a clip with no channel selected is not edited
+    std::vector<int32_t> lo((size_t)B), hi((size_t)B), range((size_t)2 * B), flags((size_t)W);
+    std::vector<unsigned char> chan((size_t)B * JF, 1);
+    for (int b = 0; b < B; ++b) {
+        lo[(size_t)b] = a->frame_lo[b]; hi[(size_t)b] = a->frame_hi[b];
+        if (lo[(size_t)b] < 0 || lo[(size_t)b] > hi[(size_t)b] || hi[(size_t)b] > Tt)
+            return fail(h, LS_EINVAL, "ls_long_edit: clip %d: frames [%d, %d) are no range inside [0, %d]", b, lo[(size_t)b], hi[(size_t)b], Tt);
+        if (a->channels) {
+            bool any = false;
+            for (int c = 0; c < JF; ++c) any |= (chan[(size_t)b * JF + c] = a->channels[(size_t)b * JF + c] ? 1 : 0) != 0;
+            if (!any) hi[(size_t)b] = lo[(size_t)b];
+        }
+        range[(size_t)2 * b] = lo[(size_t)b]; range[(size_t)2 * b + 1] = hi[(size_t)b];
+    }
+    int32_t We = 0;
+    if (ls_long_edit_plan(B, W, T, npre, lo.data(), hi.data(), flags.data(), &We) != LS_OK) return fail(h, LS_EINVAL, "ls_long_edit: bad frame ranges");
+    if (We < 1) return fail(h, LS_EINVAL, "ls_long_edit: no window holds an editable element (every range is empty)");
+    ChainCall cc;
+    int rc;
+    if ((rc = chain_args(h, "ls_long_edit", a, true, cc)) != LS_OK) return rc;
+    const bool noised = a->inpaint_noised != 0, beat = h->cfg.n_prefix_tokens == 2;
+    if (cc.tape && noised && !a->inpaint_noise) return fail(h, LS_EINVAL, "TAPE mode with inpaint_noised needs inpaint_noise");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = chain_begin(h, cc, nullptr)) != LS_OK) return rc;
+    hipStream_t st = h->stream;
+    const size_t nelem = (size_t)B * JF * T, nx = nelem * sizeof(float);
+    const size_t per_e = (size_t)cc.n_exec * 2 * B * kD, per_n = (size_t)cc.n_exec * nelem;      // floats per window: eps tape, noise tape
+    // the ranges and channel bytes: one upload per call
+    if ((rc = upload(h, h->lg_edit_range, range.data(), range.size() * sizeof(int32_t))) != LS_OK) return rc;
+    if ((rc = upload(h, h->lg_edit_chan, chan.data(), chan.size())) != LS_OK) return rc;
+    const float *xs = a->x_init, *es = a->eps_tape, *ns = a->noise_tape, *iz = noised ? a->inpaint_noise : nullptr;
+    if (cc.tape && !od) {
+        if ((rc = ingest(h, h->lg_x, xs, We * nx, 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, We * per_e * sizeof(float), 0)) != LS_OK ||
+            (rc = ingest(h, h->lg_nz, ns, We * per_n * sizeof(float), 0)) != LS_OK) return rc;
+        xs = h->lg_x.f(); es = h->lg_eps.f(); ns = h->lg_nz.f();
+        if (iz) { if ((rc = ingest(h, h->lg_inz, iz, We * per_n * sizeof(float), 0)) != LS_OK) return rc; iz = h->lg_inz.f(); }
+    }
+    float* tl = a->timeline;
+    float* wd = a->windows;
+    if (!od) {
+        if ((rc = ingest(h, h->lg_timeline, a->timeline, (size_t)B * JF * Tt * sizeof(float), 0)) != LS_OK) return rc;
+        tl = h->lg_timeline.f();
+        if (wd) { HIPCHK(h, h->lg_windows.ensure(We * nx)); wd = h->lg_windows.f(); }
+    }
+    const bool from_image = a->skip_timesteps > 0;
+    if (from_image) HIPCHK(h, h->lg_init.ensure(nx));
+    // the planes k_edit_gather fills are held by address in the captured loop: sized before the first window
+    if ((rc = ensure_pinned(h, h->inp_maskf, nx)) != LS_OK || (rc = ensure_pinned(h, h->inp_motion, nx)) != LS_OK) return rc;
+    EditArgs ea{};
+    ea.timeline = tl; ea.seed = h->lg_seed.f();
+    ea.range = static_cast<const int*>(h->lg_edit_range.p); ea.chan = static_cast<const unsigned char*>(h->lg_edit_chan.p);
+    ea.feat_u = h->feat_u.f(); ea.origin_x = h->origin_x.f(); ea.init = from_image ? h->lg_init.f() : nullptr;
+    ea.JF = JF; ea.T = T; ea.KPP = h->KPP; ea.n_pre = npre; ea.T_total = Tt;
+    cc.wa.init_image = ea.init;
+    cc.wa.inpaint_noised = noised ? 1 : 0;
+    for (int w = 0, e = 0; w < W; ++w) {
+        if (!flags[(size_t)w]) continue;
+        ea.w = w; ea.motion = h->inp_motion.f(); ea.maskf = h->inp_maskf.f();
+        HIPCHK(h, launch_edit_gather(ea, B, st));
+        Window win;
+        win.w = w; win.Bw = B; win.first = e == 0; win.resident_inpaint = true;
+        win.featc = h->lg_featc.f() + (size_t)w * B * T * kAudioFeat;
+        if (beat) win.emo_tok = h->lg_emotok.f() + (size_t)w * B * kD;
+        if (cc.tape) {
+            win.x_init = xs + (size_t)e * nelem; win.eps_tape = es + (size_t)e * per_e; win.noise_tape = ns + (size_t)e * per_n;
+            win.inpaint_noise = iz ? iz + (size_t)e * per_n : nullptr;
+        }
+        if ((rc = run_window(h, cc, win)) != LS_OK) return rc;
+        ea.sample = x_plane(h, cc.n_exec); ea.window = wd ? wd + (size_t)e * nelem : nullptr;
+        HIPCHK(h, launch_edit_scatter(ea, B, st));
+        ++e;
+    }
+    if ((rc = chain_finish(h, cc, {{od ? nullptr : a->timeline, tl, (size_t)B * JF * Tt * sizeof(float)}, {od || !wd ? nullptr : a->windows, wd, We * nx}})) != LS_OK) return rc;
+    for (int w = 0, k = 0; w < W && a->windows_run; ++w)
+        if (flags[(size_t)w] && k < a->windows_capacity) a->windows_run[k++] = w;
+    if (a->n_windows_run) *a->n_windows_run = We;
+    return LS_OK;
+}
+
+}  // extern "C"

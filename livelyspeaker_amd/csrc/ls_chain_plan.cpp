@@ -1,0 +1,89 @@
+// The plans of the chained-window engine (ls_chain_api.cpp): which clips run which window of a ragged call, which windows a timeline
+// edit runs, which windows a push of a stream runs.  Integer arithmetic on host arrays, no HIP in here: each is the single definition
+// for its entry and for Python (long_form.py), and tests/chain_plan_main.cpp runs them on their edges under the host sanitizers.
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "ls_hip.h"
+
+namespace ls {
+
+// The plan of a ragged long-form call (ls_long_plan_drop): windows per clip from plan_windows' arithmetic (long_form.py), the clips
+// stably sorted by them, longest first, and per window the clips that run it.  Declared in ls_handle.h for ls_long_prepare_ragged.
+void long_plan_drop(int B, int AL, const int64_t* lengths, std::vector<int>& row, std::vector<int>& wins, std::vector<int>& bw) {
+    std::vector<int> wb((size_t)B);
+    int wmax = 1;
+    for (int b = 0; b < B; ++b) {
+        const long long over = (long long)lengths[b] - AL;
+        wb[(size_t)b] = over <= 0 ? 1 : (int)((over + LS_LONG_AUDIO_STRIDE - 1) / LS_LONG_AUDIO_STRIDE) + 1;
+        if (wb[(size_t)b] > wmax) wmax = wb[(size_t)b];
+    }
+    row.resize((size_t)B); wins.resize((size_t)B);
+    for (int b = 0; b < B; ++b) row[(size_t)b] = b;
+    std::stable_sort(row.begin(), row.end(), [&](int x, int y) { return wb[(size_t)x] > wb[(size_t)y]; });      // descending; ties keep the caller's order
+    for (int s = 0; s < B; ++s) wins[(size_t)s] = wb[(size_t)row[(size_t)s]];
+    bw.assign((size_t)wmax, 0);                     // B_w = clips with W_b > w: count the clips that END at each w, then a running sum from the back
+    for (int b = 0; b < B; ++b) ++bw[(size_t)wb[(size_t)b] - 1];
+    for (int w = wmax - 2; w >= 0; --w) bw[(size_t)w] += bw[(size_t)w + 1];
+}
+
+}  // namespace ls
+
+extern "C" {
+
+int ls_long_plan_drop(int32_t batch, int32_t audio_len, const int64_t* audio_lengths, int32_t* slot_row, int32_t* slot_windows,
+                      int32_t* active, int32_t active_capacity, int32_t* n_windows) {
+    if (batch < 1 || audio_len < 1 || !audio_lengths || !n_windows || active_capacity < 0 || (active_capacity > 0 && !active)) return LS_EINVAL;
+    for (int b = 0; b < batch; ++b)
+        if (audio_lengths[b] < 1 || (audio_lengths[b] - audio_len) / LS_LONG_AUDIO_STRIDE > (1 << 20)) return LS_EINVAL;
+    std::vector<int> row, wins, bw;
+    ls::long_plan_drop(batch, audio_len, audio_lengths, row, wins, bw);
+    for (int s = 0; s < batch; ++s) {
+        if (slot_row) slot_row[s] = row[(size_t)s];
+        if (slot_windows) slot_windows[s] = wins[(size_t)s];
+    }
+    for (int w = 0; w < (int)bw.size() && w < active_capacity; ++w) active[w] = bw[(size_t)w];
+    *n_windows = (int32_t)bw.size();
+    return LS_OK;
+}
+
+// The windows a timeline edit runs (ls_long_edit_args in ls_hip.h): window w owns the frames [w S + n_pre, w S + T) ([0, T) for w = 0) and
+// runs when the range of some clip meets them.
+int ls_long_edit_plan(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const int32_t* lo, const int32_t* hi, int32_t* window_flags,
+                      int32_t* n_out) {
+    if (batch < 1 || n_windows < 1 || n_pre < 1 || T <= n_pre || !lo || !hi || !n_out) return LS_EINVAL;
+    const long long S = T - n_pre, Tt = T + (long long)(n_windows - 1) * S;
+    for (int b = 0; b < batch; ++b)
+        if (lo[b] < 0 || lo[b] > hi[b] || hi[b] > Tt) return LS_EINVAL;
+    int n = 0;
+    for (int w = 0; w < n_windows; ++w) {
+        const long long own_lo = w ? w * S + n_pre : 0, own_hi = w * S + T;
+        bool run = false;
+        for (int b = 0; b < batch && !run; ++b) run = (lo[b] > own_lo ? lo[b] : own_lo) < (hi[b] < own_hi ? hi[b] : own_hi);
+        if (window_flags) window_flags[w] = run ? 1 : 0;
+        n += run ? 1 : 0;
+    }
+    *n_out = n;
+    return LS_OK;
+}
+
+// The windows one call of a stream runs (ls_long_stream_push_args in ls_hip.h): window w is complete once audio_stride * w + audio_len
+// samples have arrived; the closing call adds the windows plan_windows' arithmetic (long_form.py) still owes for the total.
+int ls_long_stream_plan(int64_t samples_before, int64_t samples_new, int32_t audio_len, int32_t closing, int64_t* first_window, int64_t* n_windows) {
+    if (samples_before < 0 || samples_new < 0 || audio_len < 1 || !first_window || !n_windows) return LS_EINVAL;
+    if (samples_before > INT64_MAX - samples_new) return LS_EINVAL;
+    const int64_t S = LS_LONG_AUDIO_STRIDE, AL = audio_len, total = samples_before + samples_new;
+    auto complete = [&](int64_t n) { return n < AL ? (int64_t)0 : (n - AL) / S + 1; };
+    int64_t last = complete(total);
+    if (closing) {
+        if (total < 1) return LS_EINVAL;        // a waveform without a sample has no windows (plan_windows)
+        const int64_t cover = total > AL ? (total - AL - 1) / S + 2 : 1;      // ceil((total - AL) / S) + 1 without the sum that can pass INT64_MAX
+        if (cover > last) last = cover;
+    }
+    *first_window = complete(samples_before);
+    *n_windows = last - *first_window;
+    return LS_OK;
+}
+
+}  // extern "C"

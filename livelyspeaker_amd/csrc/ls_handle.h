@@ -1,6 +1,6 @@
 // Host-only declarations shared by the translation units behind the sampling ABI of include/ls_hip.h (ls_api.cpp: handle, weight commit,
 // schedule, preparation -- the weight images themselves are built by ls_weights.cpp, which sees neither HIP nor this header; ls_plan.cpp: the step plan and the step launchers; ls_sample.cpp: the diffusion loop and the single-step
-// entries): the handle, copies between caller and internal buffers, and the guard of buffers a captured loop holds by address.
+// entries; ls_chain_api.cpp: the chained windows of the long-form entries): the handle, copies between caller and internal buffers, and the guard of buffers a captured loop holds by address.
 // The device buffer (DevBuf) and the error path (fail, HIPCHK) are those of every handle: ls_host.h.
 #pragma once
 #include "ls_hip.h"
@@ -118,7 +118,7 @@ struct ls_handle {
     bool bpd_coef_valid = false;
     std::string coef_key;   // (sampler, eta, schedule) the per-index coefficient table `coef` was built for
 
-    // long-form synthesis (ls_long_prepare / ls_long_sample): lg_W chained windows of the prepared batch.  The zero-padded waveform [B][lg_L]
+    // long-form synthesis (ls_chain_api.cpp: ls_long_prepare / ls_long_sample): lg_W chained windows of the prepared batch.  The zero-padded waveform [B][lg_L]
     // and one encoder chunk's clip-windows [chunk][audio_len]; per-call stores of the windows' audio features [W][B][T][256] and emotion
     // tokens [W][B][512]; the seed poses [B][JF][n_pre]; the call's tapes, text features, SAG output and outputs when the caller's are host memory
     int lg_W = 0;
@@ -172,7 +172,7 @@ namespace ls {
 int ensure_temb_table(ls_handle* h);
 int build_temb_rows(ls_handle* h, const long long* idx_dev, int n, DevBuf& tmp, DevBuf& out);
 void resolve_prepare_timing(ls_handle* h, bool block);
-// the stages of ls_prepare that ls_long_prepare runs too, on the handle's stream
+// the stages of ls_prepare that the long-form stages (ls_chain_api.cpp) run too, on the handle's stream
 int prepare_scale(ls_handle* h, const float* scale, int B, int on_device, int* leading_ones = nullptr);     // leading_ones: clips ahead of the first scale != 1
 int run_wav_encoder(ls_handle* h, const float* in, int B);
 int prepare_style(ls_handle* h, int B);
@@ -189,6 +189,16 @@ hipError_t coop_reset(ls_handle* h, hipStream_t st);
 int advance_tags(ls_handle* h, hipStream_t st);
 int coop_check(ls_handle* h, bool force = false);      // force: the call ran the sample-split kernel under a plan that is no longer current
 void report_path(ls_handle* h, bool pair);
+// ---- defined in ls_sample.cpp: what a chained window (ls_chain_api.cpp) runs of ls_sample
+// What a loop whose key is not cached does to the graph cache: kReplace drops every cached graph and captures (every call but the ragged
+// long-form one: the handle then holds one graph, as it always did); kKeep captures beside the others while the cache has room and runs
+// stream launches when it has none; kReplayOnly never captures.  The last two never destroy a graph, so they are safe with replays in flight.
+enum CachePolicy { kReplace, kKeep, kReplayOnly };
+int check_sampler_args(ls_handle* h, const ls_sample_args* a);
+int run_window_loop(ls_handle* h, const ls_sample_args* a, bool resident_inpaint, bool first, CachePolicy policy, int* graph_replayed);
+inline float* x_plane(const ls_handle* h, int k) { return (k & 1) ? h->xb.f() : h->xa.f(); }      // x ahead of executed step k (xa / xb ping-pong)
+// ---- defined in ls_chain_plan.cpp (host only): slot -> clip, windows per slot, clips per window of a ragged long-form call
+void long_plan_drop(int B, int AL, const int64_t* lengths, std::vector<int>& row, std::vector<int>& wins, std::vector<int>& bw);
 
 // copy a caller buffer (host or device) into an internal device buffer
 inline int ingest(ls_handle* h, DevBuf& d, const void* src, size_t bytes, int on_device) {
@@ -209,6 +219,7 @@ inline int egress(ls_handle* h, void* dst, const void* src, size_t bytes, int on
 
 // a call that replaces the handle's prepared conditioning ends a running stream (ls_long_stream_push then reports LS_ESTATE)
 inline void end_stream(ls_handle* h) { if (h->st_state == ls_handle::kStreamOpen) h->st_state = ls_handle::kStreamReplaced; }
+inline void end_chain(ls_handle* h) { h->lg_prepared = false; end_stream(h); }       // ls_prepare: a long-form call's conditioning goes too
 
 inline void free_graph(ls_handle* h) {        // every cached graph: whatever invalidates one invalidates all
     for (auto& g : h->graphs) {

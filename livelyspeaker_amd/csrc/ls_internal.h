@@ -1,4 +1,4 @@
-// Internal declarations shared by the host side (ls_api.cpp, ls_plan.cpp, ls_sample.cpp through ls_handle.h) and the gfx950 kernels.
+// Internal declarations shared by the host side (ls_api.cpp, ls_plan.cpp, ls_sample.cpp, ls_chain_api.cpp through ls_handle.h) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

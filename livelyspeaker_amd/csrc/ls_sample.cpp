@@ -1,6 +1,6 @@
 // Host side of the C-ABI declared in include/ls_hip.h: everything that runs diffusion steps.  The sampling loop exists once (begin_loop ->
 // enqueue_loop | enqueue_plms -> finish_loop; stream launches or a captured hipGraph; draws from whole-call tapes, segmented tapes, Philox or
-// torch's GPU stream; per window of a long-form call or of a timeline edit: ls_long_sample, ls_long_edit), next to the single-step entries that enqueue the same launches on caller-held tensors (ls_forward, ls_step, ls_plms_step),
+// torch's GPU stream; run_window_loop is the same loop without its wait, for the chained windows of ls_chain_api.cpp), next to the single-step entries that enqueue the same launches on caller-held tensors (ls_forward, ls_step, ls_plms_step),
 // and the likelihood loop (ls_bpd: per schedule index q_sample, the denoiser alone and k_vb_terms, through the same capture-or-enqueue) with ls_vb_terms.
 #include "ls_handle.h"
 
@@ -63,7 +63,7 @@ void fill_sampler(ls_handle* h, StepArgs& a, int sampler, int i, float eta) {
 
 // p_mean_variance's inpainting inputs (gaussian_diffusion.py:314-320) -> device, mask and motion in the internal [B][T][JF] layout
 // The first half: the two planes the update kernel reads, and the re-noise tape.  It is all of the staging when the planes are filled on
-// the device (ls_long_edit: k_edit_gather wrote them ahead of the loop).
+// the device (a timeline edit, ls_chain_api.cpp: k_edit_gather wrote them ahead of the loop).
 int stage_inpaint_planes(ls_handle* h, const float* noise, size_t noise_elems, int on_device) {
     const size_t nx = (size_t)h->B * h->JF * h->T * sizeof(float);
     int rc;
@@ -145,7 +145,7 @@ struct LoopCall {
     int B, n_exec;                  // n_exec executed steps: ordinal k = 0 .. n_exec - 1 runs schedule index n_exec - 1 - k
     size_t nelem;                   // elements of one x plane
     bool pair, tape, tdev, plms, inpaint, inp_noised;
-    bool inp_resident;              // the inpainting planes were filled on the device ahead of the loop (ls_long_edit): no mask / motion to ingest
+    bool inp_resident;              // the inpainting planes were filled on the device ahead of the loop (run_window_loop): no mask / motion to ingest
     int ring_k;                     // TORCH_DEVICE: steps per ring refill
     size_t plms_stride;             // PLMS: floats between the planes of plms_buf
     TorchDrawArgs tda;              // TORCH_DEVICE: the per-step draws (stage_loop_inputs), and what x_T's draw shares with them
@@ -192,8 +192,6 @@ int refill_ring(ls_handle* h, const LoopCall& c, int k) {
     HIPCHK(h, launch_torch_draws(g, h->stream));
     return LS_OK;
 }
-
-float* x_plane(const ls_handle* h, int k) { return (k & 1) ? h->xb.f() : h->xa.f(); }      // x ahead of executed step k (xa / xb ping-pong)
 
 // The one builder of a loop's StepArgs.  eval_args: the denoiser alone at index i (a PLMS evaluation); step_args: step k of a DDPM / DDIM loop.
 StepArgs eval_args(ls_handle* h, int i, const float* x_in, const Draws& d) {
@@ -404,10 +402,7 @@ std::string loop_key(const ls_handle* h, const LoopCall& c) {
 }
 
 // a chain of launches as stream launches, or as a captured graph (captured when the key is not cached, replayed otherwise).  What a
-// missing key does to the cache (ls_handle.h): kReplace drops every cached graph and captures (every call but the ragged long-form
-// one: the handle then holds one graph, as it always did); kKeep captures beside the others while the cache has room and runs stream
-// launches when it has none; kReplayOnly never captures.  The last two never destroy a graph, so they are safe with replays in flight.
-enum CachePolicy { kReplace, kKeep, kReplayOnly };
+// missing key does to the cache: CachePolicy in ls_handle.h.
 template <class Enqueue>
 int run_captured(ls_handle* h, bool use_graph, const std::string& key, Enqueue enqueue, int* graph_replayed, CachePolicy policy = kReplace) {
     hipStream_t st = h->stream;
@@ -553,8 +548,10 @@ int sample_segment(ls_handle* h, const ls_sample_args* a) {
     return LS_OK;
 }
 
-// the checks of ls_sample that hold for whole-call and segmented loops alike
-int check_sampler_args(ls_handle* h, const ls_sample_args* a) {
+}  // namespace
+
+// the checks of ls_sample that hold for whole-call and segmented loops alike, and for every window of a chain
+int ls::check_sampler_args(ls_handle* h, const ls_sample_args* a) {
     const bool plms = a->sampler == LS_SAMPLER_PLMS;
     if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM && !plms)
         return fail(h, LS_EINVAL, a->sampler == LS_SAMPLER_DDIM_REVERSE ? "ls_sample: DDIM_REVERSE is a single step (ls_step); the reference has no reverse loop" : "bad sampler");
@@ -574,6 +571,23 @@ int check_sampler_args(ls_handle* h, const ls_sample_args* a) {
     }
     return LS_OK;
 }
+
+// The loop of one window of a chain (ls_chain_api.cpp): ls_sample's begin -> stage -> capture-or-enqueue on a filled ls_sample_args,
+// without its wait; the caller has set call_host, and the result is x_plane(h, n_exec).  resident_inpaint: the inpainting branch on
+// planes the caller filled on the device (a->inpaint_noised says whether they are re-noised).  first: the call's first window, whose
+// start (ev[6]; ev[0] is re-recorded by every window's begin_loop) and loop start (ev[1]) time the call.
+int ls::run_window_loop(ls_handle* h, const ls_sample_args* a, bool resident_inpaint, bool first, CachePolicy policy, int* graph_replayed) {
+    LoopCall c = loop_call(h, a);
+    if (resident_inpaint) { c.inpaint = true; c.inp_noised = a->inpaint_noised != 0; c.inp_resident = true; }
+    int rc;
+    if ((rc = begin_loop(h, c, true)) != LS_OK) return rc;
+    if (first) HIPCHK(h, hipEventRecord(h->ev[6], h->stream));
+    if ((rc = stage_loop_inputs(h, c)) != LS_OK) return rc;
+    if (first) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    return run_loop(h, c, graph_replayed, policy);
+}
+
+namespace {
 
 // ls_step with one schedule index per sample: the denoiser with one timestep-embedding row per sample (what ls_forward does),
 // pred_xstart -> fwd_cfg; then the posterior / DDIM update with per-sample coefficients as its own elementwise kernel, both driven by
@@ -767,514 +781,6 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
     HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     if ((rc = run_loop(h, c, &replayed)) != LS_OK) return rc;
     return finish_loop(h, c, c.n_exec + (c.plms ? 1 : 0), replayed, false);      // model evaluations: PLMS's first step makes two
-}
-
-// Long-form synthesis (ls_long_sample_args in ls_hip.h): per window the hand-off kernel, ls_prepare's two static projections at ls_prepare's
-// shapes, and ls_sample's own begin_loop -> stage_loop_inputs -> run_loop on device-resident inputs; one wait at the end.  The loop's
-// launches read the handle's buffers only (static_c / static_u, the tape buffers, xa / xb, callp), none of which moves between windows,
-// so the graph captured for window 0 (or by an earlier call with the same key) is replayed for every later one.
-//
-// After ls_long_prepare_ragged window w runs the lg_bw[w] clips that still have audio: slots [0, lg_bw[w]) of every per-clip buffer
-// (the clips are held longest-first), the packed stores at lg_off[w].  Each window is then, decision for decision, a call at batch
-// lg_bw[w]: its scales decide the single-pass form, its batch the step plan (set_plan), the plan the workspaces' accounting
-// (plan_workspaces; ls_long_prepare_ragged sized them for every window, so nothing a captured loop holds moves here), and the speaker
-// style runs at that batch.  A window batch that serves two or more windows is captured once and replayed; one that serves a single
-// window runs as stream launches unless an earlier call left its graph behind.
-int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
-    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_sample: null argument");
-    if (!h->lg_prepared) return fail(h, LS_ESTATE, "ls_long_sample before ls_long_prepare");
-    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_sample before ls_set_schedule");
-    if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM) return fail(h, LS_EUNSUPPORTED, "ls_long_sample: DDPM and DDIM loops only");
-    if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EUNSUPPORTED, "ls_long_sample: TAPE and PHILOX noise only");
-    if (!a->timeline) return fail(h, LS_EINVAL, "ls_long_sample: null timeline");
-    if (a->sag && !a->text_features) return fail(h, LS_EINVAL, "ls_long_sample: sag without text_features");
-    const bool rg = h->lg_ragged;
-    const int B = h->B, W = h->lg_W, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, od = a->on_device, dev = h->cfg.device;
-    const int Tt = T + (W - 1) * (T - npre);
-    if (rg && ((int)h->lg_bw.size() != W || (int)h->lg_off.size() != W + 1 || h->lg_bw[0] != B)) return fail(h, LS_ESTATE, "ls_long_sample: the ragged plan does not match the prepared batch");
-    auto batch_of = [&](int w) { return rg ? h->lg_bw[(size_t)w] : B; };                      // clips that run window w
-    auto first_of = [&](int w) { return (size_t)(rg ? h->lg_off[(size_t)w] : w * B); };       // clip-windows ahead of window w in the packed stores
-    ls_sample_args wa{};
-    wa.sampler = a->sampler; wa.noise_mode = a->noise_mode; wa.skip_timesteps = a->skip_timesteps; wa.on_device = 1;
-    wa.use_graph = a->use_graph; wa.clip_denoised = a->clip_denoised; wa.two_pass_always = a->two_pass_always; wa.eta = a->eta;
-    int rc;
-    if ((rc = check_sampler_args(h, &wa)) != LS_OK) return rc;
-    const bool tape = a->noise_mode == LS_NOISE_TAPE;
-    if (tape && (!a->x_init || !a->eps_tape || !a->noise_tape)) return fail(h, LS_EINVAL, "TAPE mode needs x_init, eps_tape and noise_tape");
-    if (!tape && (a->sample_offset >> 48 || (a->sample_offset + (unsigned long long)B) >> 48)) return fail(h, LS_EINVAL, "PHILOX: sample_offset + batch must stay below 2^48 (the window index sits above)");
-    HIPCHK(h, hipSetDevice(dev));
-    if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
-    h->seg_next = -1;
-    hipStream_t st = h->stream;
-    const int n_exec = h->n_steps - a->skip_timesteps;
-    const size_t per_x = (size_t)JF * T, per_e = (size_t)n_exec * 2 * kD, per_n = (size_t)n_exec * per_x;     // floats per clip-window: x_T, eps tape, noise tape
-    const size_t nelem = (size_t)B * per_x, nx = nelem * sizeof(float), total = first_of(W);
-    // host tapes / text features: one upload per call; device ones are read in place
-    const float *xs = a->x_init, *es = a->eps_tape, *ns = a->noise_tape, *tx = a->text_features;
-    if (tape && !od) {
-        if ((rc = ingest(h, h->lg_x, xs, total * per_x * sizeof(float), 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, total * per_e * sizeof(float), 0)) != LS_OK ||
-            (rc = ingest(h, h->lg_nz, ns, total * per_n * sizeof(float), 0)) != LS_OK) return rc;
-        xs = h->lg_x.f(); es = h->lg_eps.f(); ns = h->lg_nz.f();
-    }
-    ls_sag* const sag = a->sag;
-    void* const sag_st = sag ? ls_sag_stream(sag) : nullptr;
-    if (sag) {
-        if (!od) { if ((rc = ingest(h, h->lg_text, tx, (size_t)W * B * kD * sizeof(float), 0)) != LS_OK) return rc; tx = h->lg_text.f(); }
-        HIPCHK(h, h->lg_init.ensure(nx)); HIPCHK(h, h->lg_mask.ensure((size_t)B * T));
-        HIPCHK(h, hipMemsetAsync(h->lg_mask.p, 1, (size_t)B * T, st));
-        wa.init_image = h->lg_init.f();
-    }
-    float* tl = a->timeline;
-    float* wd = a->windows;
-    if (!od) {
-        HIPCHK(h, h->lg_timeline.ensure((size_t)B * JF * Tt * sizeof(float)));
-        if (wd) HIPCHK(h, h->lg_windows.ensure(W * nx));
-        tl = h->lg_timeline.f();
-        if (wd) wd = h->lg_windows.f();
-    }
-    if (rg) {
-        // what a clip does not reach stays zero: its timeline beyond its own frames, its raw windows from its window count on
-        HIPCHK(h, hipMemsetAsync(tl, 0, (size_t)B * JF * Tt * sizeof(float), st));
-        if (wd) HIPCHK(h, hipMemsetAsync(wd, 0, W * nx, st));
-        // Room in the graph cache for the batches this call captures (at most the cache's bound; the rest run as stream launches), made
-        // now: nothing of this call is in flight yet.  The same window batches as the last ragged call: its graphs are this call's.
-        if (h->graphs_for != h->lg_bw) {
-            int repeated = 0;
-            for (int w = 1; w < W; ++w) if (h->lg_bw[(size_t)w] == h->lg_bw[(size_t)w - 1] && (w < 2 || h->lg_bw[(size_t)w - 1] != h->lg_bw[(size_t)w - 2])) ++repeated;
-            if (repeated > ls_handle::kGraphCacheMax) repeated = ls_handle::kGraphCacheMax;
-            if ((int)h->graphs.size() + repeated > ls_handle::kGraphCacheMax) free_graph(h);
-            h->graphs_for = h->lg_bw;
-        }
-    }
-    ChainArgs ca{};
-    ca.seed = h->lg_seed.f(); ca.timeline = tl;
-    ca.JF = JF; ca.T = T; ca.KPP = h->KPP; ca.n_pre = npre; ca.T_total = Tt;
-    ca.row = rg ? static_cast<const int*>(h->lg_row.p) : nullptr;
-    LoopCall c{};
-    int replayed = 0, replays = 0, styled = 0;
-    bool pair0 = false, coop_used = false;
-    for (int w = 0; w <= W; ++w) {
-        const int Bw = w < W ? batch_of(w) : 0, Bprev = w ? batch_of(w - 1) : 0;
-        // hand-off: window w - 1 leaves through the timeline, window w's prefix poses enter feat_u / origin_x
-        ca.prev = w ? x_plane(h, n_exec) : nullptr;
-        ca.feat_u = w < W ? h->feat_u.f() : nullptr; ca.origin_x = h->origin_x.f();
-        ca.f0 = w == 1 ? 0 : npre; ca.t_off = w <= 1 ? 0 : T + (w - 2) * (T - npre);
-        ca.window = (w && wd) ? wd + (size_t)(w - 1) * nelem : nullptr;
-        ca.n_next = Bw;
-        HIPCHK(h, launch_chain_window(ca, w ? Bprev : Bw, st));
-        if (w == W) break;
-        if (rg) {           // from here on the handle is prepared for a batch of Bw
-            h->B = Bw;
-            h->all_scale_one = h->lg_scale_ones >= Bw;
-            set_plan(h, Bw);
-            if ((rc = plan_workspaces(h)) != LS_OK) return rc;
-            if (styled != Bw && (rc = prepare_style(h, Bw)) != LS_OK) return rc;
-            styled = Bw;
-        }
-        coop_used = coop_used || seg_n(h, 2) > 0;
-        // the static projections with ls_prepare's arithmetic and shapes: static_u = feat_u . Wpre^T + b; static_c = static_u + feat_c[w] . Waud^T
-        HIPCHK(h, launch_gemm_nt(h->feat_u.f(), h->KPP, h->win_pre.f(), h->KPP, h->win_bias.f(), nullptr, 0, h->static_u.f(), kD, Bw * T, kD, h->KPP, 0, st));
-        HIPCHK(h, launch_gemm_nt(h->lg_featc.f() + first_of(w) * T * kAudioFeat, kAudioFeat, h->win_aud.f(), kAudioFeat, nullptr, h->static_u.f(), kD,
-                                 h->static_c.f(), kD, Bw * T, kD, kAudioFeat, 0, st));
-        if (h->cfg.n_prefix_tokens == 2)
-            HIPCHK(h, hipMemcpyAsync(h->emo_tok.p, h->lg_emotok.f() + (size_t)w * B * kD, (size_t)Bw * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (sag) {      // the decoder runs on its own handle's stream, ordered behind the hand-off and ahead of the loop by events
-            if (ls_stream_order(dev, st, sag_st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
-            if (ls_sag_decode_async(sag, Bw, h->origin_x.f(), tx + (size_t)w * B * kD, static_cast<const unsigned char*>(h->lg_mask.p), h->lg_init.f()) != LS_OK)
-                return fail(h, LS_EHIP, "SAG decode of window %d: %s", w, ls_sag_last_error(sag));
-            if (ls_stream_order(dev, sag_st, st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
-        }
-        if (tape) { wa.x_init = xs + first_of(w) * per_x; wa.eps_tape = es + first_of(w) * per_e; wa.noise_tape = ns + first_of(w) * per_n; }
-        c = loop_call(h, &wa);
-        if (w == 0) pair0 = c.pair;
-        // begin_loop's advance_tags uploads call_host (24 bytes of pageable memory) as every ls_sample does: the runtime takes such a
-        // source into its staging memory before hipMemcpyAsync returns, which is what makes rewriting it for the next window safe.  It is
-        // the one host -> device copy per window; whether the runtime waits inside it is the runtime's business (not measured).
-        h->call_host = CallParams{a->seed, a->sample_offset + ((unsigned long long)w << 48), h->tag_base, 0u};
-        if ((rc = begin_loop(h, c, true)) != LS_OK) return rc;
-        if (w == 0) HIPCHK(h, hipEventRecord(h->ev[6], st));        // ev[0] is re-recorded by every window's begin_loop
-        if ((rc = stage_loop_inputs(h, c)) != LS_OK) return rc;
-        if (w == 0) HIPCHK(h, hipEventRecord(h->ev[1], st));
-        CachePolicy policy = kReplace;
-        if (rg) {
-            int serves = 0;
-            for (int v = 0; v < W; ++v) serves += h->lg_bw[(size_t)v] == Bw;
-            policy = serves >= 2 ? kKeep : kReplayOnly;
-        }
-        if ((rc = run_loop(h, c, &replayed, policy)) != LS_OK) return rc;
-        replays += replayed;
-    }
-    if (rg) {               // leave the handle as ls_long_prepare_ragged left it: prepared for the whole batch
-        h->B = B;
-        h->all_scale_one = h->lg_scale_ones >= B;
-        set_plan(h, B);
-        if ((rc = plan_workspaces(h)) != LS_OK) return rc;
-    }
-    HIPCHK(h, hipEventRecord(h->ev[2], st));
-    if (!od) {
-        if ((rc = egress(h, a->timeline, tl, (size_t)B * JF * Tt * sizeof(float), 0)) != LS_OK) return rc;
-        if (wd && (rc = egress(h, a->windows, wd, W * nx, 0)) != LS_OK) return rc;
-    }
-    HIPCHK(h, hipEventRecord(h->ev[3], st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if ((rc = coop_check(h, coop_used)) != LS_OK) return rc;
-    report_path(h, pair0);
-    HIPCHK(h, hipEventElapsedTime(&h->timing.loop_ms, h->ev[1], h->ev[2]));
-    HIPCHK(h, hipEventElapsedTime(&h->timing.total_ms, h->ev[6], h->ev[3]));
-    h->timing.n_step_launches = W * n_exec;
-    h->timing.single_pass = pair0 ? 1 : 0;
-    h->timing.graph_replayed = replays;          // windows served by a replay: W - 1 after a capture, W on a warm handle
-    h->timing.tape_upload_ms = 0.f;
-    h->timing.n_segments = W;
-    return LS_OK;
-}
-
-// The windows one call of a stream runs (ls_long_stream_push_args in ls_hip.h): window w is complete once audio_stride * w + audio_len
-// samples have arrived; the closing call adds the windows plan_windows' arithmetic (long_form.py) still owes for the total.  Host only;
-// the single definition for ls_long_stream_push and for Python.
-int ls_long_stream_plan(int64_t samples_before, int64_t samples_new, int32_t audio_len, int32_t closing, int64_t* first_window, int64_t* n_windows) {
-    if (samples_before < 0 || samples_new < 0 || audio_len < 1 || !first_window || !n_windows) return LS_EINVAL;
-    if (samples_before > INT64_MAX - samples_new) return LS_EINVAL;
-    const int64_t S = LS_LONG_AUDIO_STRIDE, AL = audio_len, total = samples_before + samples_new;
-    auto complete = [&](int64_t n) { return n < AL ? (int64_t)0 : (n - AL) / S + 1; };
-    int64_t last = complete(total);
-    if (closing) {
-        if (total < 1) return LS_EINVAL;        // a waveform without a sample has no windows (plan_windows)
-        const int64_t cover = total > AL ? (total - AL + S - 1) / S + 1 : 1;
-        if (cover > last) last = cover;
-    }
-    *first_window = complete(samples_before);
-    *n_windows = last - *first_window;
-    return LS_OK;
-}
-
-namespace {
-// copy `take` samples of every clip from chunk column c0 (rows n apart) into the ring behind the stream's last sample: one strided copy,
-// two where the ring wraps
-int ring_write(ls_handle* h, const float* chunk, long long n, long long c0, int take, int od) {
-    const int B = h->B, R = h->st_R, p = (int)(h->st_samples % R), seg1 = take < R - p ? take : R - p;
-    const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    HIPCHK(h, hipMemcpy2DAsync(h->st_ring.f() + p, (size_t)R * sizeof(float), chunk + c0, (size_t)n * sizeof(float), (size_t)seg1 * sizeof(float), B, kind, h->stream));
-    if (take > seg1)
-        HIPCHK(h, hipMemcpy2DAsync(h->st_ring.p, (size_t)R * sizeof(float), chunk + c0 + seg1, (size_t)n * sizeof(float), (size_t)(take - seg1) * sizeof(float), B, kind, h->stream));
-    return LS_OK;
-}
-
-// Everything of a push behind its argument checks: feed the ring, run the windows that complete.  Per window the body of ls_long_sample
-// with the once-per-call encoder moved in front (k_stream_gather -> WavEncoder -> k_build_feats into the one-window feature buffer) and
-// the hand-off moved behind the loop: k_chain_window flushes the window into the call's output AND writes the next window's prefix poses
-// into feat_u / origin_x, where they wait for the push that runs it (nothing but a call that ends the stream writes either).
-int stream_push_run(ls_handle* h, const ls_long_stream_push_args* a, long long k) {
-    const int B = h->B, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, AL = h->cfg.audio_len, R = h->st_R, od = a->on_device, dev = h->cfg.device;
-    const int cap = a->capacity;
-    ls_sample_args wa{};
-    wa.sampler = a->sampler; wa.noise_mode = a->noise_mode; wa.skip_timesteps = a->skip_timesteps; wa.on_device = 1;
-    wa.use_graph = a->use_graph; wa.clip_denoised = a->clip_denoised; wa.two_pass_always = a->two_pass_always; wa.eta = a->eta;
-    const bool tape = a->noise_mode == LS_NOISE_TAPE;
-    hipStream_t st = h->stream;
-    int rc;
-    const int n_exec = h->n_steps - a->skip_timesteps;
-    const size_t per_x = (size_t)B * JF * T, per_e = (size_t)n_exec * 2 * B * kD, per_n = (size_t)n_exec * per_x, nx = per_x * sizeof(float);
-    // the held conditioning: what this call passes holds for every window started from here on
-    if (a->emo) {
-        if ((rc = ingest(h, h->st_emo_ids, a->emo, (size_t)B * sizeof(int64_t), od)) != LS_OK) return rc;
-        HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->st_emo_ids.p), h->emo_tok.f(), B, kD, h->cfg.n_emotions, st));
-        h->st_have_emo = true;
-    }
-    if (a->text_features) {
-        if ((rc = ingest(h, h->st_text, a->text_features, (size_t)B * kD * sizeof(float), od)) != LS_OK) return rc;
-        h->st_have_text = true;
-    }
-    ls_sag* const sag = a->sag;
-    void* const sag_st = sag ? ls_sag_stream(sag) : nullptr;
-    float* out = a->frames;
-    if (k > 0) {
-        if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
-        h->seg_next = -1;
-        if (sag) {
-            HIPCHK(h, h->lg_init.ensure(nx)); HIPCHK(h, h->lg_mask.ensure((size_t)B * T));
-            HIPCHK(h, hipMemsetAsync(h->lg_mask.p, 1, (size_t)B * T, st));
-            wa.init_image = h->lg_init.f();
-        }
-        if (!od) { HIPCHK(h, h->lg_timeline.ensure((size_t)B * JF * cap * sizeof(float))); out = h->lg_timeline.f(); }
-    }
-    ChainArgs ca{};
-    ca.feat_u = h->feat_u.f(); ca.origin_x = h->origin_x.f(); ca.timeline = out;
-    ca.JF = JF; ca.T = T; ca.KPP = h->KPP; ca.n_pre = npre; ca.T_total = cap; ca.n_next = B;
-    LoopCall c{};
-    int replayed = 0, replays = 0, t_off = 0;
-    long long ran = 0, fed = 0;
-    bool pair0 = false;
-    const long long n = a->n_samples;
-    while (fed < n || ran < k) {
-        // as much of the chunk as the ring has room for: the samples below the next window's first one are dead
-        const long long room = R - (h->st_samples - (long long)LS_LONG_AUDIO_STRIDE * h->st_windows);
-        const int take = (int)(n - fed < room ? n - fed : room);
-        if (take > 0) {
-            if ((rc = ring_write(h, a->audio, n, fed, take, od)) != LS_OK) return rc;
-            fed += take; h->st_samples += take;
-        }
-        int64_t w0 = 0, kw = 0;         // the windows complete now; in the closing call, once the chunk is in, the padded ones too
-        if (ls_long_stream_plan(h->st_samples, 0, AL, a->closing && fed == n, &w0, &kw) != LS_OK) return fail(h, LS_EINVAL, "ls_long_stream_push: closing a stream that was fed no sample");
-        const long long upto = w0 + kw;
-        if (take == 0 && upto <= h->st_windows) return fail(h, LS_ESTATE, "ls_long_stream_push: no room in the ring and no window to run");
-        for (long long w = h->st_windows; w < upto; ++w, ++ran) {
-            if (ran >= k) return fail(h, LS_ESTATE, "ls_long_stream_push: more windows complete than the call was planned for");
-            const long long lo = w * LS_LONG_AUDIO_STRIDE, have = h->st_samples - lo;
-            HIPCHK(h, launch_stream_gather(h->st_ring.f(), h->lg_clips.f(), B, AL, R, (int)(lo % R), (int)(have < AL ? (have < 0 ? 0 : have) : AL), st));
-            if ((rc = run_wav_encoder(h, h->lg_clips.f(), B)) != LS_OK) return rc;
-            HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f(), B, JF, h->KPP, 0, st, T));
-            // the static projections with ls_prepare's arithmetic and shapes, as in ls_long_sample
-            HIPCHK(h, launch_gemm_nt(h->feat_u.f(), h->KPP, h->win_pre.f(), h->KPP, h->win_bias.f(), nullptr, 0, h->static_u.f(), kD, B * T, kD, h->KPP, 0, st));
-            HIPCHK(h, launch_gemm_nt(h->lg_featc.f(), kAudioFeat, h->win_aud.f(), kAudioFeat, nullptr, h->static_u.f(), kD, h->static_c.f(), kD, B * T, kD, kAudioFeat, 0, st));
-            if (sag) {
-                if (ls_stream_order(dev, st, sag_st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
-                if (ls_sag_decode_async(sag, B, h->origin_x.f(), h->st_text.f(), static_cast<const unsigned char*>(h->lg_mask.p), h->lg_init.f()) != LS_OK)
-                    return fail(h, LS_EHIP, "SAG decode of window %lld: %s", w, ls_sag_last_error(sag));
-                if (ls_stream_order(dev, sag_st, st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
-            }
-            if (tape) {     // one window's draws at a time: the staging buffers do not grow with the call
-                const float *xs = a->x_init + (size_t)ran * per_x, *es = a->eps_tape + (size_t)ran * per_e, *ns = a->noise_tape + (size_t)ran * per_n;
-                if (!od) {
-                    if ((rc = ingest(h, h->lg_x, xs, nx, 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, per_e * sizeof(float), 0)) != LS_OK ||
-                        (rc = ingest(h, h->lg_nz, ns, per_n * sizeof(float), 0)) != LS_OK) return rc;
-                    xs = h->lg_x.f(); es = h->lg_eps.f(); ns = h->lg_nz.f();
-                }
-                wa.x_init = xs; wa.eps_tape = es; wa.noise_tape = ns;
-            }
-            c = loop_call(h, &wa);
-            if (ran == 0) pair0 = c.pair;
-            h->call_host = CallParams{a->seed, a->sample_offset + ((unsigned long long)w << 48), h->tag_base, 0u};      // see ls_long_sample
-            if ((rc = begin_loop(h, c, true)) != LS_OK) return rc;
-            if (ran == 0) HIPCHK(h, hipEventRecord(h->ev[6], st));
-            if ((rc = stage_loop_inputs(h, c)) != LS_OK) return rc;
-            if (ran == 0) HIPCHK(h, hipEventRecord(h->ev[1], st));
-            if ((rc = run_loop(h, c, &replayed)) != LS_OK) return rc;
-            replays += replayed;
-            // hand-off: the window leaves through the call's output, the next window's prefix poses enter feat_u / origin_x
-            ca.prev = x_plane(h, n_exec);
-            ca.f0 = w == 0 ? 0 : npre; ca.t_off = t_off;
-            HIPCHK(h, launch_chain_window(ca, B, st));
-            t_off += T - ca.f0;
-            h->st_windows = w + 1;
-        }
-    }
-    h->st_frames += t_off;
-    if (a->n_frames) *a->n_frames = t_off;
-    if (a->n_windows) *a->n_windows = (int32_t)ran;
-    if (a->closing) h->st_state = ls_handle::kStreamClosed;
-    if (ran == 0) {         // no sampling work: a host chunk is the caller's again once its copies are done, a device chunk is read in stream order
-        if (!od && n > 0) { HIPCHK(h, hipEventRecord(h->ev[6], st)); HIPCHK(h, hipEventSynchronize(h->ev[6])); }
-        return LS_OK;
-    }
-    HIPCHK(h, hipEventRecord(h->ev[2], st));
-    if (!od && (rc = egress(h, a->frames, out, (size_t)B * JF * cap * sizeof(float), 0)) != LS_OK) return rc;
-    HIPCHK(h, hipEventRecord(h->ev[3], st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if ((rc = coop_check(h)) != LS_OK) return rc;
-    report_path(h, pair0);
-    HIPCHK(h, hipEventElapsedTime(&h->timing.loop_ms, h->ev[1], h->ev[2]));
-    HIPCHK(h, hipEventElapsedTime(&h->timing.total_ms, h->ev[6], h->ev[3]));
-    h->timing.n_step_launches = (int)ran * n_exec;
-    h->timing.single_pass = pair0 ? 1 : 0;
-    h->timing.graph_replayed = replays;          // windows of this call served by a replay
-    h->timing.tape_upload_ms = 0.f;
-    h->timing.n_segments = (int)ran;
-    return LS_OK;
-}
-}  // namespace
-
-int ls_long_stream_push(ls_handle* h, const ls_long_stream_push_args* a) {
-    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_stream_push: null argument");
-    switch (h->st_state) {
-    case ls_handle::kStreamOpen: break;
-    case ls_handle::kStreamNone: return fail(h, LS_ESTATE, "ls_long_stream_push before ls_long_stream_open");
-    case ls_handle::kStreamClosed: return fail(h, LS_ESTATE, "ls_long_stream_push: the stream is closed");
-    case ls_handle::kStreamFailed: return fail(h, LS_ESTATE, "ls_long_stream_push: an earlier push of this stream failed; open a new one");
-    default: return fail(h, LS_ESTATE, "ls_long_stream_push: the stream was ended by a call that replaced the handle's prepared conditioning "
-                                       "(ls_prepare, ls_long_prepare, ls_commit_weights or another ls_long_stream_open); open a new one");
-    }
-    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_stream_push before ls_set_schedule");
-    if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM) return fail(h, LS_EUNSUPPORTED, "ls_long_stream_push: DDPM and DDIM loops only");
-    if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EUNSUPPORTED, "ls_long_stream_push: TAPE and PHILOX noise only");
-    if (a->n_samples < 0 || (a->n_samples > 0 && !a->audio)) return fail(h, LS_EINVAL, "ls_long_stream_push: n_samples %lld with%s audio", (long long)a->n_samples, a->audio ? "" : "out");
-    if (a->capacity < 0 || (a->capacity > 0 && !a->frames)) return fail(h, LS_EINVAL, "ls_long_stream_push: capacity without frames");
-    if (a->text_features && !a->sag) return fail(h, LS_EINVAL, "ls_long_stream_push: text_features without sag");
-    if (a->emo && h->cfg.n_prefix_tokens != 2) return fail(h, LS_EINVAL, "ls_long_stream_push: emo is a BEAT conditioning");
-    ls_sample_args wa{};
-    wa.sampler = a->sampler; wa.noise_mode = a->noise_mode; wa.skip_timesteps = a->skip_timesteps; wa.on_device = 1;
-    wa.use_graph = a->use_graph; wa.clip_denoised = a->clip_denoised; wa.two_pass_always = a->two_pass_always; wa.eta = a->eta;
-    int rc;
-    if ((rc = check_sampler_args(h, &wa)) != LS_OK) return rc;
-    int64_t first = 0, k = 0;
-    if (ls_long_stream_plan(h->st_samples, a->n_samples, h->cfg.audio_len, a->closing, &first, &k) != LS_OK)
-        return fail(h, LS_EINVAL, "ls_long_stream_push: closing a stream that was fed no sample");
-    if (first != h->st_windows) return fail(h, LS_ESTATE, "ls_long_stream_push: %lld windows have run, %lld were complete", h->st_windows, (long long)first);
-    const int T = h->T, npre = h->cfg.n_pre_seq;
-    const int64_t need = k == 0 ? 0 : k * (T - npre) + (first == 0 ? npre : 0);
-    if (need > a->capacity) return fail(h, LS_EINVAL, "ls_long_stream_push: this call runs %lld windows = %lld frames, capacity is %d", (long long)k, (long long)need, a->capacity);
-    if (k > 0) {
-        const bool tape = a->noise_mode == LS_NOISE_TAPE;
-        if (tape && (!a->x_init || !a->eps_tape || !a->noise_tape)) return fail(h, LS_EINVAL, "TAPE mode needs x_init, eps_tape and noise_tape");
-        if (!tape && (a->sample_offset >> 48 || (a->sample_offset + (unsigned long long)h->B) >> 48)) return fail(h, LS_EINVAL, "PHILOX: sample_offset + batch must stay below 2^48 (the window index sits above)");
-        if (h->cfg.n_prefix_tokens == 2 && !a->emo && !h->st_have_emo) return fail(h, LS_EINVAL, "ls_long_stream_push: the BEAT variant's first window needs emo ids");
-        if (a->sag && !a->text_features && !h->st_have_text) return fail(h, LS_EINVAL, "ls_long_stream_push: sag needs text_features for the first window");
-    }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    rc = stream_push_run(h, a, k);
-    if (rc != LS_OK) {      // the ring and the hand-off poses may be half written: the stream is over, the handle is not
-        h->st_state = ls_handle::kStreamFailed;
-        (void)hipStreamSynchronize(h->stream);
-    }
-    return rc;
-}
-
-// The windows a timeline edit runs (ls_long_edit_args in ls_hip.h): window w owns the frames [w S + n_pre, w S + T) ([0, T) for w = 0) and
-// runs when the range of some clip meets them.  Host only; the single definition for ls_long_edit and for Python.
-int ls_long_edit_plan(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const int32_t* lo, const int32_t* hi, int32_t* window_flags,
-                      int32_t* n_out) {
-    if (batch < 1 || n_windows < 1 || n_pre < 1 || T <= n_pre || !lo || !hi || !n_out) return LS_EINVAL;
-    const long long S = T - n_pre, Tt = T + (long long)(n_windows - 1) * S;
-    for (int b = 0; b < batch; ++b)
-        if (lo[b] < 0 || lo[b] > hi[b] || hi[b] > Tt) return LS_EINVAL;
-    int n = 0;
-    for (int w = 0; w < n_windows; ++w) {
-        const long long own_lo = w ? w * S + n_pre : 0, own_hi = w * S + T;
-        bool run = false;
-        for (int b = 0; b < batch && !run; ++b) run = (lo[b] > own_lo ? lo[b] : own_lo) < (hi[b] < own_hi ? hi[b] : own_hi);
-        if (window_flags) window_flags[w] = run ? 1 : 0;
-        n += run ? 1 : 0;
-    }
-    *n_out = n;
-    return LS_OK;
-}
-
-// Timeline edit (ls_long_edit_args in ls_hip.h): ls_long_sample's per-window body over the windows of ls_long_edit_plan, with the
-// hand-off kernel replaced by k_edit_gather ahead of the loop and k_edit_scatter behind it, and the loop run with the inpainting branch
-// on planes that are already on the device.  The loop's launches read the handle's buffers only and none of them moves between windows,
-// so the first window's captured graph (its key holds the inpainting form) is replayed for the others.  One wait at the end.
-int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) {
-    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_edit: null argument");
-    if (!h->lg_prepared) return fail(h, LS_ESTATE, "ls_long_edit before ls_long_prepare");
-    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_edit before ls_set_schedule");
-    if (h->lg_ragged) return fail(h, LS_EUNSUPPORTED, "ls_long_edit: a handle prepared by ls_long_prepare_ragged is not edited (ragged batches are not built)");
-    if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM) return fail(h, LS_EUNSUPPORTED, "ls_long_edit: DDPM and DDIM loops only");
-    if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EUNSUPPORTED, "ls_long_edit: TAPE and PHILOX noise only");
-    if (!a->timeline) return fail(h, LS_EINVAL, "ls_long_edit: null timeline");
-    if (!a->frame_lo || !a->frame_hi) return fail(h, LS_EINVAL, "ls_long_edit: null frame_lo / frame_hi");
-    if (a->windows_capacity < 0 || (a->windows_capacity > 0 && !a->windows_run)) return fail(h, LS_EINVAL, "ls_long_edit: windows_capacity without windows_run");
-    const int B = h->B, W = h->lg_W, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, od = a->on_device;
-    const int Tt = T + (W - 1) * (T - npre);
-    // per clip [lo, hi) and the channel bytes; a clip with no channel selected is not edited
-    std::vector<int32_t> lo((size_t)B), hi((size_t)B), range((size_t)2 * B), flags((size_t)W);
-    std::vector<unsigned char> chan((size_t)B * JF, 1);
-    for (int b = 0; b < B; ++b) {
-        lo[(size_t)b] = a->frame_lo[b]; hi[(size_t)b] = a->frame_hi[b];
-        if (lo[(size_t)b] < 0 || lo[(size_t)b] > hi[(size_t)b] || hi[(size_t)b] > Tt)
-            return fail(h, LS_EINVAL, "ls_long_edit: clip %d: frames [%d, %d) are no range inside [0, %d]", b, lo[(size_t)b], hi[(size_t)b], Tt);
-        if (a->channels) {
-            bool any = false;
-            for (int c = 0; c < JF; ++c) any |= (chan[(size_t)b * JF + c] = a->channels[(size_t)b * JF + c] ? 1 : 0) != 0;
-            if (!any) hi[(size_t)b] = lo[(size_t)b];
-        }
-        range[(size_t)2 * b] = lo[(size_t)b]; range[(size_t)2 * b + 1] = hi[(size_t)b];
-    }
-    int32_t We = 0;
-    if (ls_long_edit_plan(B, W, T, npre, lo.data(), hi.data(), flags.data(), &We) != LS_OK) return fail(h, LS_EINVAL, "ls_long_edit: bad frame ranges");
-    if (We < 1) return fail(h, LS_EINVAL, "ls_long_edit: no window holds an editable element (every range is empty)");
-    ls_sample_args wa{};
-    wa.sampler = a->sampler; wa.noise_mode = a->noise_mode; wa.skip_timesteps = a->skip_timesteps; wa.on_device = 1;
-    wa.use_graph = a->use_graph; wa.clip_denoised = a->clip_denoised; wa.two_pass_always = a->two_pass_always; wa.eta = a->eta;
-    int rc;
-    if ((rc = check_sampler_args(h, &wa)) != LS_OK) return rc;
-    const bool tape = a->noise_mode == LS_NOISE_TAPE, noised = a->inpaint_noised != 0;
-    if (tape && (!a->x_init || !a->eps_tape || !a->noise_tape)) return fail(h, LS_EINVAL, "TAPE mode needs x_init, eps_tape and noise_tape");
-    if (tape && noised && !a->inpaint_noise) return fail(h, LS_EINVAL, "TAPE mode with inpaint_noised needs inpaint_noise");
-    if (!tape && (a->sample_offset >> 48 || (a->sample_offset + (unsigned long long)B) >> 48)) return fail(h, LS_EINVAL, "PHILOX: sample_offset + batch must stay below 2^48 (the window index sits above)");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
-    h->seg_next = -1;
-    hipStream_t st = h->stream;
-    const int n_exec = h->n_steps - a->skip_timesteps;
-    const size_t per_x = (size_t)JF * T, nelem = (size_t)B * per_x, nx = nelem * sizeof(float);
-    const size_t per_e = (size_t)n_exec * 2 * B * kD, per_n = (size_t)n_exec * nelem;      // floats per window: eps tape, noise tape
-    // the ranges and channel bytes: one upload per call
-    if ((rc = upload(h, h->lg_edit_range, range.data(), range.size() * sizeof(int32_t))) != LS_OK) return rc;
-    if ((rc = upload(h, h->lg_edit_chan, chan.data(), chan.size())) != LS_OK) return rc;
-    const float *xs = a->x_init, *es = a->eps_tape, *ns = a->noise_tape, *iz = noised ? a->inpaint_noise : nullptr;
-    if (tape && !od) {
-        if ((rc = ingest(h, h->lg_x, xs, We * nx, 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, We * per_e * sizeof(float), 0)) != LS_OK ||
-            (rc = ingest(h, h->lg_nz, ns, We * per_n * sizeof(float), 0)) != LS_OK) return rc;
-        xs = h->lg_x.f(); es = h->lg_eps.f(); ns = h->lg_nz.f();
-        if (iz) { if ((rc = ingest(h, h->lg_inz, iz, We * per_n * sizeof(float), 0)) != LS_OK) return rc; iz = h->lg_inz.f(); }
-    }
-    float* tl = a->timeline;
-    float* wd = a->windows;
-    if (!od) {
-        if ((rc = ingest(h, h->lg_timeline, a->timeline, (size_t)B * JF * Tt * sizeof(float), 0)) != LS_OK) return rc;
-        tl = h->lg_timeline.f();
-        if (wd) { HIPCHK(h, h->lg_windows.ensure(We * nx)); wd = h->lg_windows.f(); }
-    }
-    const bool from_image = a->skip_timesteps > 0;
-    if (from_image) HIPCHK(h, h->lg_init.ensure(nx));
-    // the planes k_edit_gather fills are held by address in the captured loop: sized before the first window
-    if ((rc = ensure_pinned(h, h->inp_maskf, nx)) != LS_OK || (rc = ensure_pinned(h, h->inp_motion, nx)) != LS_OK) return rc;
-    EditArgs ea{};
-    ea.timeline = tl; ea.seed = h->lg_seed.f();
-    ea.range = static_cast<const int*>(h->lg_edit_range.p); ea.chan = static_cast<const unsigned char*>(h->lg_edit_chan.p);
-    ea.feat_u = h->feat_u.f(); ea.origin_x = h->origin_x.f(); ea.init = from_image ? h->lg_init.f() : nullptr;
-    ea.JF = JF; ea.T = T; ea.KPP = h->KPP; ea.n_pre = npre; ea.T_total = Tt;
-    wa.init_image = ea.init;
-    wa.inpaint_noised = noised ? 1 : 0;
-    LoopCall c{};
-    int replayed = 0, replays = 0, e = 0;
-    for (int w = 0; w < W; ++w) {
-        if (!flags[(size_t)w]) continue;
-        ea.w = w; ea.motion = h->inp_motion.f(); ea.maskf = h->inp_maskf.f();
-        HIPCHK(h, launch_edit_gather(ea, B, st));
-        // the static projections with ls_prepare's arithmetic and shapes, as in ls_long_sample
-        HIPCHK(h, launch_gemm_nt(h->feat_u.f(), h->KPP, h->win_pre.f(), h->KPP, h->win_bias.f(), nullptr, 0, h->static_u.f(), kD, B * T, kD, h->KPP, 0, st));
-        HIPCHK(h, launch_gemm_nt(h->lg_featc.f() + (size_t)w * B * T * kAudioFeat, kAudioFeat, h->win_aud.f(), kAudioFeat, nullptr, h->static_u.f(), kD,
-                                 h->static_c.f(), kD, B * T, kD, kAudioFeat, 0, st));
-        if (h->cfg.n_prefix_tokens == 2)
-            HIPCHK(h, hipMemcpyAsync(h->emo_tok.p, h->lg_emotok.f() + (size_t)w * B * kD, (size_t)B * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (tape) {
-            wa.x_init = xs + (size_t)e * nelem; wa.eps_tape = es + (size_t)e * per_e; wa.noise_tape = ns + (size_t)e * per_n;
-            wa.inpaint_noise = iz ? iz + (size_t)e * per_n : nullptr;
-        }
-        c = loop_call(h, &wa);
-        c.inpaint = true; c.inp_noised = noised; c.inp_resident = true;
-        h->call_host = CallParams{a->seed, a->sample_offset + ((unsigned long long)w << 48), h->tag_base, 0u};      // see ls_long_sample
-        if ((rc = begin_loop(h, c, true)) != LS_OK) return rc;
-        if (e == 0) HIPCHK(h, hipEventRecord(h->ev[6], st));
-        if ((rc = stage_loop_inputs(h, c)) != LS_OK) return rc;
-        if (e == 0) HIPCHK(h, hipEventRecord(h->ev[1], st));
-        if ((rc = run_loop(h, c, &replayed)) != LS_OK) return rc;
-        replays += replayed;
-        ea.sample = x_plane(h, n_exec); ea.window = wd ? wd + (size_t)e * nelem : nullptr;
-        HIPCHK(h, launch_edit_scatter(ea, B, st));
-        ++e;
-    }
-    HIPCHK(h, hipEventRecord(h->ev[2], st));
-    if (!od) {
-        if ((rc = egress(h, a->timeline, tl, (size_t)B * JF * Tt * sizeof(float), 0)) != LS_OK) return rc;
-        if (wd && (rc = egress(h, a->windows, wd, We * nx, 0)) != LS_OK) return rc;
-    }
-    HIPCHK(h, hipEventRecord(h->ev[3], st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if ((rc = coop_check(h)) != LS_OK) return rc;
-    report_path(h, c.pair);
-    HIPCHK(h, hipEventElapsedTime(&h->timing.loop_ms, h->ev[1], h->ev[2]));
-    HIPCHK(h, hipEventElapsedTime(&h->timing.total_ms, h->ev[6], h->ev[3]));
-    h->timing.n_step_launches = We * n_exec;
-    h->timing.single_pass = c.pair ? 1 : 0;
-    h->timing.graph_replayed = replays;
-    h->timing.tape_upload_ms = 0.f;
-    h->timing.n_segments = We;               // the windows that ran
-    for (int w = 0, k = 0; w < W && a->windows_run; ++w)
-        if (flags[(size_t)w] && k < a->windows_capacity) a->windows_run[k++] = w;
-    if (a->n_windows_run) *a->n_windows_run = We;
-    return LS_OK;
 }
 
 // One plms_sample (gaussian_diffusion.py:1016-1098): the launches an LS_SAMPLER_PLMS loop makes for that step, on caller-held tensors.

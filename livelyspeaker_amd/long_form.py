@@ -155,6 +155,48 @@ def _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, n_
     return B, W
 
 
+def _as_tensors(*arrays):
+    return tuple(a if (a is None or th.is_tensor(a)) else th.as_tensor(np.asarray(a)) for a in arrays)
+
+
+def _check_model(diffusion, rag):
+    """What the engine's loop is built for, refused behind ``_check_args``."""
+    if diffusion.model_mean_type != gd.ModelMeanType.START_X or diffusion.model_var_type != gd.ModelVarType.FIXED_SMALL:
+        raise NotImplementedError("only START_X + FIXED_SMALL (create_gaussian_diffusion's setting) is built")
+    if rag.cond_mask_prob <= 0:
+        raise ValueError("ClassifierFreeSampleModel returns None when cond_mask_prob == 0 (cfg_sampler.py:24-31)")
+
+
+def _bind_engine(diffusion, rag):
+    """The model's engine with the diffusion's schedule; its resident conditioning is the caller's from here on."""
+    eng = diffusion._bind_schedule(rag.engine())
+    rag._cond_key = rag._prefetched_key = None
+    return eng
+
+
+def _emo_windows(emo, W, B):
+    """``emo`` [B] or [B, W] (or None) in the engine's [W, B] layout."""
+    if emo is None:
+        return None
+    return (emo[None, :].expand(W, B) if emo.ndim == 1 else emo.t()).contiguous()
+
+
+def _loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised):
+    """The sampler arguments every chained-window engine call takes."""
+    return dict(sampler=_lib.LS_SAMPLER_DDIM if sampler == "ddim" else _lib.LS_SAMPLER_DDPM, skip_timesteps=int(skip_timesteps),
+                eta=float(eta) if sampler == "ddim" else 0.0, use_graph=diffusion.use_graph, clip_denoised=clip_denoised,
+                two_pass_always=diffusion.two_pass_always)
+
+
+def _check_tape_bound(diffusion, who, n_exec, shape, D, renoised=False):
+    """``noise_source='torch_cpu'``: one window's tape (with the re-noise plane of an edit when ``renoised``) must fit tape_segment_bytes."""
+    per_window = n_exec * (2 * shape[0] * D + (2 if renoised else 1) * int(np.prod(shape))) * 4
+    if per_window > diffusion.tape_segment_bytes:
+        raise ValueError(f"{who}: one window's noise tape is {per_window} bytes, tape_segment_bytes is "
+                         f"{diffusion.tape_segment_bytes}; segmented tapes are not built for chained windows (raise "
+                         "tape_segment_bytes or use noise_source='philox')")
+
+
 def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=None, n_windows=None, sampler='ddim', skip_timesteps=0,
                 eta=0.0, clip_denoised=False, sag=None, text_features=None, encoder_chunk=None, return_windows=False, audio_lengths=None,
                 drop_finished=False, **unsupported):
@@ -195,8 +237,7 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
         raise ValueError("sample_long: audio_lengths decide the windows of every clip; pass either n_windows or audio_lengths")
     if drop_finished and audio_lengths is None:
         raise ValueError("sample_long: drop_finished drops a clip when its audio_lengths entry is used up; pass audio_lengths")
-    as_t = lambda a: a if (a is None or th.is_tensor(a)) else th.as_tensor(np.asarray(a))      # noqa: E731
-    audio, seed_poses, vid_indices, scale, emo, text_features = (as_t(a) for a in (audio, seed_poses, vid_indices, scale, emo, text_features))
+    audio, seed_poses, vid_indices, scale, emo, text_features = _as_tensors(audio, seed_poses, vid_indices, scale, emo, text_features)
     frames = None
     if audio_lengths is not None and hasattr(model, "model"):      # another model type is _check_args's to refuse
         if audio.ndim != 2:
@@ -210,16 +251,11 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
             audio = th.where(valid.to(audio.device), audio, th.zeros((), dtype=audio.dtype, device=audio.device))       # a copy; NaN tails become 0
     B, W = _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, n_windows, sampler, skip_timesteps, sag, text_features,
                        encoder_chunk, unsupported)
-    if diffusion.model_mean_type != gd.ModelMeanType.START_X or diffusion.model_var_type != gd.ModelVarType.FIXED_SMALL:
-        raise NotImplementedError("only START_X + FIXED_SMALL (create_gaussian_diffusion's setting) is built")
     rag = model.model
-    if rag.cond_mask_prob <= 0:
-        raise ValueError("ClassifierFreeSampleModel returns None when cond_mask_prob == 0 (cfg_sampler.py:24-31)")
+    _check_model(diffusion, rag)
     out_dev = audio.device
-    eng = diffusion._bind_schedule(rag.engine())
-    rag._cond_key = rag._prefetched_key = None        # the engine's resident conditioning is this call's from here on
-    if emo is not None:
-        emo = (emo[None, :].expand(W, B) if emo.ndim == 1 else emo.t()).contiguous()
+    eng = _bind_engine(diffusion, rag)
+    emo = _emo_windows(emo, W, B)
     batches = None
     if drop_finished:       # the engine reads audio and seed poses through its slot table; the B- and W*B-row inputs are put in slot order here
         order, _, active, _ = plan_drop(lens, rag)
@@ -232,9 +268,7 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
                      audio_lengths=lens if drop_finished else None)
     n_exec = diffusion.num_timesteps - int(skip_timesteps)
     shape = (B, rag.njoints, rag.nfeats, rag.nframes)
-    kw = dict(sampler=_lib.LS_SAMPLER_DDIM if sampler == "ddim" else _lib.LS_SAMPLER_DDPM, skip_timesteps=int(skip_timesteps),
-              eta=float(eta) if sampler == "ddim" else 0.0, use_graph=diffusion.use_graph, clip_denoised=clip_denoised,
-              two_pass_always=diffusion.two_pass_always, device_out=out_dev.type == "cuda", return_windows=return_windows)
+    kw = dict(_loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised), device_out=out_dev.type == "cuda", return_windows=return_windows)
     if sag is not None:
         sag_eng = sag.engine()
         if sag_eng.device != eng.device:
@@ -244,11 +278,7 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
     if diffusion.noise_source == "philox":
         kw.update(diffusion._philox_key())
     else:
-        per_window = n_exec * (2 * B * eng.D + int(np.prod(shape))) * 4
-        if per_window > diffusion.tape_segment_bytes:
-            raise ValueError(f"sample_long: one window's noise tape is {per_window} bytes, tape_segment_bytes is "
-                             f"{diffusion.tape_segment_bytes}; segmented tapes are not built for chained windows (raise "
-                             "tape_segment_bytes or use noise_source='philox')")
+        _check_tape_bound(diffusion, "sample_long", n_exec, shape, eng.D)
         kw["x_init"], kw["eps_tape"], kw["noise_tape"] = ref_draws.RefDraws("cpu").windows(diffusion, W, n_exec, shape, eng.D, batches=batches)
         diffusion.last_tape_segments = 1
     res = eng.long_sample(**kw)
@@ -267,8 +297,7 @@ class LongStream:
     """A running ``open_stream`` session; see there.  ``samples_in``, ``windows_run``, ``frames_out``: host ints."""
 
     def __init__(self, diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag):
-        as_t = lambda a: a if (a is None or th.is_tensor(a)) else th.as_tensor(np.asarray(a))      # noqa: E731
-        seed_poses, vid_indices, scale, emo = (as_t(a) for a in (seed_poses, vid_indices, scale, emo))
+        seed_poses, vid_indices, scale, emo = _as_tensors(seed_poses, vid_indices, scale, emo)
         B = int(seed_poses.shape[0]) if seed_poses.ndim else 0
         rag = getattr(model, "model", None)
         beat = getattr(rag, "n_prefix_tokens", 1) == 2
@@ -276,26 +305,21 @@ class LongStream:
         _check_args(diffusion, model, th.empty(max(B, 0), 1), seed_poses, vid_indices, scale,
                     emo if (emo is not None or not beat) else th.zeros(B, dtype=th.long), None, sampler, skip_timesteps, sag,
                     None if sag is None else th.empty(B, 1, int(rag.latent_dim)), None, {})
-        if diffusion.model_mean_type != gd.ModelMeanType.START_X or diffusion.model_var_type != gd.ModelVarType.FIXED_SMALL:
-            raise NotImplementedError("only START_X + FIXED_SMALL (create_gaussian_diffusion's setting) is built")
-        if rag.cond_mask_prob <= 0:
-            raise ValueError("ClassifierFreeSampleModel returns None when cond_mask_prob == 0 (cfg_sampler.py:24-31)")
+        _check_model(diffusion, rag)
         if emo is not None and emo.ndim != 1:
             raise ValueError(f"a stream holds one emotion id per clip: emo must be [{B}], got {list(emo.shape)}")
         self._diffusion, self._rag, self._sag, self._B = diffusion, rag, sag, B
         self._cond = (seed_poses.float(), vid_indices, scale.float())
         self._emo, self._text = emo, None               # held on the host side only until the next engine call takes them
         self._have_emo = self._have_text = False
-        self._kw = dict(sampler=_lib.LS_SAMPLER_DDIM if sampler == "ddim" else _lib.LS_SAMPLER_DDPM, skip_timesteps=int(skip_timesteps),
-                        eta=float(eta) if sampler == "ddim" else 0.0, use_graph=diffusion.use_graph, clip_denoised=clip_denoised,
-                        two_pass_always=diffusion.two_pass_always)
+        self._kw = _loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised)
         if diffusion.noise_source == "philox":          # one key per stream: window w draws at sample_offset + b + (w << 48)
             self._kw.update(diffusion._philox_key())
         self._n_exec = diffusion.num_timesteps - int(skip_timesteps)
         self._eng = None
         self._closed = False
         self._last_dev = th.device("cpu")
-        self.samples_in =self.windows_run = self.frames_out = 0
+        self.samples_in = self.windows_run = self.frames_out = 0
 
     def __enter__(self):
         return self
@@ -306,9 +330,7 @@ class LongStream:
 
     def _engine(self):
         if self._eng is None:
-            rag = self._rag
-            eng = self._diffusion._bind_schedule(rag.engine())
-            rag._cond_key = rag._prefetched_key = None        # the engine's resident conditioning is this stream's from here on
+            eng = _bind_engine(self._diffusion, self._rag)
             if self._sag is not None and self._sag.engine().device != eng.device:
                 raise ValueError(f"the SAG decoder runs on cuda:{self._sag.engine().device}, the RAG model on cuda:{eng.device}")
             eng.long_stream_open(*self._cond)
@@ -319,8 +341,7 @@ class LongStream:
         if self._closed:
             raise RuntimeError("the stream is closed")
         rag, B, diffusion = self._rag, self._B, self._diffusion
-        as_t = lambda a: a if (a is None or th.is_tensor(a)) else th.as_tensor(np.asarray(a))      # noqa: E731
-        chunk, emo, text_features = as_t(chunk), as_t(emo), as_t(text_features)
+        chunk, emo, text_features = _as_tensors(chunk, emo, text_features)
         if chunk.ndim != 2 or int(chunk.shape[0]) != B:
             raise ValueError(f"audio_chunk must be [{B}, n], got {list(chunk.shape)}")
         if emo is not None:
@@ -344,11 +365,7 @@ class LongStream:
         shape = (B, rag.njoints, rag.nfeats, rag.nframes)
         kw = dict(self._kw)
         if k and diffusion.noise_source != "philox":
-            per_window = self._n_exec * (2 * B * int(rag.latent_dim) + int(np.prod(shape))) * 4
-            if per_window > diffusion.tape_segment_bytes:
-                raise ValueError(f"open_stream: one window's noise tape is {per_window} bytes, tape_segment_bytes is "
-                                 f"{diffusion.tape_segment_bytes}; segmented tapes are not built for chained windows (raise "
-                                 "tape_segment_bytes or use noise_source='philox')")
+            _check_tape_bound(diffusion, "open_stream", self._n_exec, shape, int(rag.latent_dim))
         eng = self._engine()
         if k and diffusion.noise_source != "philox":
             kw["x_init"], kw["eps_tape"], kw["noise_tape"] = ref_draws.RefDraws("cpu").windows(diffusion, k, self._n_exec, shape, eng.D)
@@ -514,8 +531,7 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
         raise TypeError(f"edit_long: pass livelyspeaker_amd.ClassifierFreeSampleModel(RAG), got {type(model).__name__}")
     if diffusion.noise_source == "torch_device":
         raise NotImplementedError("edit_long: noise_source='torch_device' is not built for chained windows; use 'torch_cpu' or 'philox'")
-    as_t = lambda a: a if (a is None or th.is_tensor(a)) else th.as_tensor(np.asarray(a))      # noqa: E731
-    timeline, audio, seed_poses, vid_indices, scale, emo = (as_t(a) for a in (timeline, audio, seed_poses, vid_indices, scale, emo))
+    timeline, audio, seed_poses, vid_indices, scale, emo = _as_tensors(timeline, audio, seed_poses, vid_indices, scale, emo)
     rag = model.model
     T, npre = int(rag.nframes), int(rag.n_pre_seq)
     if timeline.ndim != 4 or _shape(timeline)[1:3] != (rag.njoints, rag.nfeats):
@@ -529,33 +545,22 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
     if audio.ndim != 2 or int(audio.shape[0]) != B:
         raise ValueError(f"audio must be [{B}, L], got {list(audio.shape)}")
     _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, W, sampler, skip_timesteps, None, None, encoder_chunk, {})
-    if diffusion.model_mean_type != gd.ModelMeanType.START_X or diffusion.model_var_type != gd.ModelVarType.FIXED_SMALL:
-        raise NotImplementedError("only START_X + FIXED_SMALL (create_gaussian_diffusion's setting) is built")
-    if rag.cond_mask_prob <= 0:
-        raise ValueError("ClassifierFreeSampleModel returns None when cond_mask_prob == 0 (cfg_sampler.py:24-31)")
+    _check_model(diffusion, rag)
     hi = np.where(sel.any(axis=1), hi, lo).astype(np.int32)           # a clip with no joint selected is not edited
     windows = edit_plan(np.stack([lo, hi], axis=1), W, rag)
     out_dev = timeline.device
-    eng = diffusion._bind_schedule(rag.engine())
-    rag._cond_key = rag._prefetched_key = None        # the engine's resident conditioning is this call's from here on
-    if emo is not None:
-        emo = (emo[None, :].expand(W, B) if emo.ndim == 1 else emo.t()).contiguous()
-    eng.long_prepare(audio.float(), seed_poses.float(), vid_indices, scale.float(), emo=emo, n_windows=W, encoder_chunk=encoder_chunk)
+    eng = _bind_engine(diffusion, rag)
+    eng.long_prepare(audio.float(), seed_poses.float(), vid_indices, scale.float(), emo=_emo_windows(emo, W, B), n_windows=W,
+                     encoder_chunk=encoder_chunk)
     n_exec = diffusion.num_timesteps - int(skip_timesteps)
     shape = (B, rag.njoints, rag.nfeats, T)
     noised = rag.n_prefix_tokens == 1                  # the TED tree re-noises the kept motion, the BEAT tree does not
-    kw = dict(sampler=_lib.LS_SAMPLER_DDIM if sampler == "ddim" else _lib.LS_SAMPLER_DDPM, skip_timesteps=int(skip_timesteps),
-              eta=float(eta) if sampler == "ddim" else 0.0, use_graph=diffusion.use_graph, clip_denoised=clip_denoised,
-              two_pass_always=diffusion.two_pass_always, device_out=out_dev.type == "cuda", return_windows=return_windows,
+    kw = dict(_loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised), device_out=out_dev.type == "cuda", return_windows=return_windows,
               inpaint_noised=noised, channels=np.repeat(sel, rag.nfeats, axis=1))
     if diffusion.noise_source == "philox":
         kw.update(diffusion._philox_key())
     else:
-        per_window = n_exec * (2 * B * eng.D + (2 if noised else 1) * int(np.prod(shape))) * 4
-        if per_window > diffusion.tape_segment_bytes:
-            raise ValueError(f"edit_long: one window's noise tape is {per_window} bytes, tape_segment_bytes is "
-                             f"{diffusion.tape_segment_bytes}; segmented tapes are not built for chained windows (raise "
-                             "tape_segment_bytes or use noise_source='philox')")
+        _check_tape_bound(diffusion, "edit_long", n_exec, shape, eng.D, renoised=noised)
         kw["x_init"], kw["eps_tape"], kw["noise_tape"], kw["inpaint_noise"] = ref_draws.RefDraws("cpu").edit_windows(
             diffusion, len(windows), n_exec, shape, eng.D, noised)
         diffusion.last_tape_segments = 1

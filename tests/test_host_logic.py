@@ -99,7 +99,7 @@ def test_shipped_library_has_no_debug_switches():
     assert "os.environ" not in src
     csrc = os.path.join(ROOT, "livelyspeaker_amd", "csrc")
     host = sorted(f for f in os.listdir(csrc) if f.endswith(".cpp"))
-    assert {"ls_api.cpp", "ls_plan.cpp", "ls_sample.cpp", "ls_sag_api.cpp", "ls_train_api.cpp"} <= set(host)
+    assert {"ls_api.cpp", "ls_plan.cpp", "ls_sample.cpp", "ls_chain_api.cpp", "ls_chain_plan.cpp", "ls_sag_api.cpp", "ls_train_api.cpp"} <= set(host)
     for f in host:
         text = open(os.path.join(csrc, f)).read()
         for m in re.finditer(r"getenv", text):
