@@ -13,6 +13,7 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py --long-seconds A,B,... [--drop-finished]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --edit-frames LO,HI [--edit-joints J0,J1,...]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --stream-chunk SECONDS
+    python examples/livelyspeaker_ted.py --pool SPEAKERS
     python examples/livelyspeaker_ted.py [batch] --clip-text
 --clip-text starts from TOKENS instead of a stand-in feature: synthetic clip.tokenize output -> CLIPTextEncoder (the text tower of CLIP
 on the GPU, synthetic weights) -> text features -> SAG decoder -> the same refinement, with no host wait between the two engines.
@@ -36,6 +37,9 @@ range touches, 20 refinement steps each), everything else is kept bit for bit, a
 --stream-chunk SECONDS (with --long-seconds N) feeds the same waveform to a STREAM instead, SECONDS of audio at a time
 (long_form.open_stream: push() returns a window's new frames as soon as the window's audio is complete, close() the zero-padded rest);
 it prints when each window's frames appeared and checks that the frames, concatenated, are bit for bit the timeline of the one call.
+--pool SPEAKERS serves that many LIVE speakers from one engine (long_form.open_pool): they start 1.3 s apart and talk for different
+times, each joins a slot when it starts and leaves it when its speech ends, audio arrives for all of them every half second, and every
+push runs the windows that are complete -- of whichever speakers -- as one batch.  It prints who joined, which batch ran, and who left.
 With real data: load RAG.pt / SAG.pth / the auto-encoder checkpoint with load_model_wo_clip / load_state_dict and build `cond`
 exactly as the reference script does; everything below the weight loading is unchanged.
 """
@@ -160,6 +164,12 @@ def main():
         i = sys.argv.index("--noise-source")
         noise_source = sys.argv[i + 1]
         del sys.argv[i:i + 2]
+    if "--pool" in sys.argv:
+        i = sys.argv.index("--pool")
+        speakers = int(sys.argv[i + 1])
+        if speakers < 1:
+            raise SystemExit("--pool takes the number of speakers, >= 1")
+        return main_pool(speakers, noise_source)
     if "--long-seconds" in sys.argv:
         i = sys.argv.index("--long-seconds")
         arg = sys.argv[i + 1]
@@ -373,6 +383,53 @@ def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y
     assert torch.equal(streamed, timeline), float((streamed - timeline).abs().max())
     print(f"streamed in {chunk_seconds:g} s chunks ({len(parts) - 1} pushes + close): {stream.windows_run} windows, {stream.frames_out} frames, "
           f"bit for bit the timeline of the one call")
+
+
+def main_pool(speakers, noise_source, tick_seconds=0.5):
+    """`speakers` live speakers on ONE engine (long_form.open_pool): speaker s starts talking 1.3 s after speaker s - 1 and talks for
+    6 + s seconds; audio arrives for all of them every `tick_seconds`.  A speaker joins a free slot when it starts and leaves when its
+    speech ends; every tick is one push, which runs the windows that are complete as one batch."""
+    import numpy as np
+    from livelyspeaker_amd import long_form
+    if noise_source == "torch_device":
+        raise SystemExit("--pool draws with philox or torch_cpu")
+    cfg, model, diffusion, _, _ = build()
+    diffusion.noise_source = noise_source
+    n = int(round(tick_seconds * 16000))
+    start = [int(round(1.3 * s / tick_seconds)) for s in range(speakers)]                       # the tick a speaker joins in
+    length = [int(round((6 + s) * 16000)) for s in range(speakers)]
+    y = {k: torch.from_numpy(v).cuda() for k, v in synth.make_long_cond(cfg, speakers, max(length) // 32000 + 2, scale=2.5).items()}
+    torch.manual_seed(233)
+    pool = long_form.open_pool(diffusion, model, speakers, sampler="ddim", skip_timesteps=80)
+    slot, fed, frames = {}, [0] * speakers, [0] * speakers
+    t0, tick = time.perf_counter(), 0
+    while any(fed[s] < length[s] for s in range(speakers)):
+        for s in range(speakers):
+            if start[s] == tick:
+                slot[s] = pool.join(y["seed_poses"][s], y["vid_indices"][s], y["scale"][s])
+                print(f"tick {tick:3d}: speaker {s} joins slot {slot[s]}")
+        chunk, lengths = torch.zeros(speakers, n, device="cuda"), np.zeros(speakers, np.int64)
+        for s, k in slot.items():
+            take = min(n, length[s] - fed[s])
+            chunk[k, :take] = y["audio"][s, fed[s]:fed[s] + take]
+            lengths[k], fed[s] = take, fed[s] + take
+        t1 = time.perf_counter()
+        new, counts = pool.push(chunk, lengths)
+        torch.cuda.synchronize()
+        done = {s: int(counts[k]) for s, k in slot.items() if counts[k]}
+        if done:
+            print(f"tick {tick:3d}: one batch of {len(done)} -> " + ", ".join(f"speaker {s} +{c} frames" for s, c in done.items()) +
+                  f" in {(time.perf_counter() - t1) * 1e3:.1f} ms")
+        for s, c in done.items():
+            frames[s] += c
+        for s in [s for s in slot if fed[s] == length[s]]:
+            tail = pool.leave(slot.pop(s))
+            frames[s] += int(tail.shape[2])
+            assert frames[s] == long_form.plan_windows(length[s], cfg)[2] and bool(torch.isfinite(tail).all())
+            print(f"tick {tick:3d}: speaker {s} leaves after {length[s] / 16000:g} s of speech with {frames[s]} frames")
+        tick += 1
+    pool.close()
+    print(f"{speakers} speakers, {sum(frames)} frames ({noise_source}) in {(time.perf_counter() - t0) * 1e3:.0f} ms over {tick} pushes on one engine")
 
 
 def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit):

@@ -442,8 +442,8 @@ int ls_long_edit(ls_handle* h, const ls_long_edit_args* a);
  * A chunk larger than the ring's free space is consumed in pieces with the completed windows run in between.  One host wait per call
  * that ran a window; a call that ran none waits only for the copy of a HOST chunk out of the caller's buffer (a device chunk must stay
  * valid until the handle's stream has read it: order its reuse with ls_stream_order).
- * Not built: clips joining or leaving a stream, per-clip lengths, edits of a running stream, PLMS, const_noise, dump_steps, a
- * non-blocking push. */
+ * Clips that join and leave, each with its own lengths: the session pool further down (ls_long_pool_*).
+ * Not built: edits of a running stream, PLMS, const_noise, dump_steps, a non-blocking push. */
 typedef struct ls_long_stream_cond {
     int32_t batch;
     int32_t on_device;
@@ -483,6 +483,85 @@ int ls_long_stream_push(ls_handle* h, const ls_long_stream_push_args* a);
 /* out = {samples fed, windows run, frames written, device bytes the stream holds (ring + gathered window + one-window features)} of the
  * handle's current or last stream (zeros before the first ls_long_stream_open) */
 int ls_long_stream_info(const ls_handle* h, int64_t out[4]);
+
+/* ---- Session pool: streaming long-form synthesis with clips that join and leave.  A pool holds `capacity` SLOTS; each open slot is
+ * one stream of its own (its audio ring, its hand-off poses, its held conditioning, its sample and window counters), fed at its own
+ * rate.  A push takes a ragged chunk -- lengths[s] samples for slot s -- and runs, ROUND after round, the windows that are complete:
+ * round r holds, in ascending slot order, the slots that still have a complete, unrun window after r earlier rounds of this call, and
+ * is ONE sampling call at batch A = its size on those slots (its own step plan, its own single-pass decision from the scales of those
+ * slots, its own captured loop, kept in the graph cache by batch).  Per slot the windows, their audio, their hand-off and their
+ * stitching are those of ls_long_stream_push on that slot alone.
+ *
+ * ls_long_pool_plan (no handle, no GPU) is the one definition of what a call runs.  Per slot it is ls_long_stream_plan(samples_in[s],
+ * samples_new[s], audio_len, closing[s]); n_windows[s] is that call's count, frames[s] the frames slot s gets (34 for its window 0,
+ * 30 for each later one), *n_rounds = max n_windows[s], and round_slots (nullable; round_capacity entries) takes the slots of round 0,
+ * then of round 1, ...: *n_entries = sum of n_windows in all.  LS_EINVAL: a null array, a negative count, windows_run[s] that is not
+ * the number of windows complete on samples_in[s], samples for a slot that is not open, a closing slot that was fed no sample at all,
+ * round_slots too short.  The closing flag of a slot that is not open is ignored.
+ *
+ * ls_long_pool_open allocates everything for `capacity` slots -- rings, hand-off stores, held conditioning, one gathered window, one
+ * window's features, the loop's buffers and the workspaces of the step plans of every batch 1..capacity -- so that no buffer a
+ * captured loop holds by address moves before the pool ends.  It REPLACES the handle's prepared conditioning and ends a running
+ * stream; any call that replaces the conditioning ends the pool in turn (the next push or join returns LS_ESTATE, the handle stays
+ * usable).  ls_long_pool_join fills a free slot (LS_ESTATE on an occupied one) and draws nothing; a slot whose closing flag is set
+ * in a push is free again after the windows it was owed.  A failure inside a push marks the pool failed (LS_ESTATE from then on).
+ *
+ * Noise.  TAPE: the tapes are packed round after round, each round the draws of one sampling call at batch A (x_init [A, J, F, T],
+ * eps_tape [n_exec, 2, A, latent_dim], noise_tape [n_exec, A, J, F, T]).  PHILOX: row r of the pool's q-th round since open draws at
+ * sample_offset + r + (q << 48): the key of ls_long_stream_push whenever the pool is used like a stream (all slots joined in order and
+ * fed alike), and otherwise NOT independent of the push schedule; a push that would take q to 2^16 returns LS_ESTATE.
+ * One host wait per call that ran a round; a call that ran none waits only for the copy of a HOST chunk.
+ * Not built: device-resident lengths, Philox keyed by (slot, window), ls_long_edit on a pool, PLMS, const_noise, dump_steps, sharded
+ * calls, a non-blocking push. */
+typedef struct ls_long_pool_join_args {
+    int32_t slot;
+    int32_t on_device;          /* the five pointers are device pointers                                              */
+    const float* seed_poses;    /* [J, F, n_pre_seq]: origin_x[..., :n_pre_seq] of the slot's window 0                */
+    const int64_t* vid_index;   /* [1]                                                                                */
+    const float* scale;         /* [1]; a device scale costs one read-back                                            */
+    const int64_t* emo;         /* [1] emotion id held from the join on (BEAT: required), or NULL                     */
+    const float* text_features; /* [latent_dim] held from the join on, or NULL                                        */
+} ls_long_pool_join_args;
+typedef struct ls_long_pool_push_args {
+    int32_t sampler;            /* these eight fields as in ls_long_sample_args                                       */
+    int32_t noise_mode;
+    int32_t skip_timesteps;
+    int32_t on_device;          /* audio, emo, text_features, the tapes and frames are device pointers                */
+    int32_t use_graph;
+    int32_t clip_denoised;
+    int32_t two_pass_always;
+    float eta;
+    int32_t capacity;           /* frames per row of `frames`; at least the most any slot gets in this call           */
+    int32_t reserved;
+    int64_t n_max;              /* row stride of `audio` in samples, >= every lengths[s]                              */
+    const float* audio;         /* [S, n_max] (NULL with n_max == 0); row s holds lengths[s] samples for slot s       */
+    const int64_t* lengths;     /* HOST [S], each in [0, n_max]; 0 for a slot that is not open                        */
+    const int32_t* closing;     /* HOST [S], nullable: slot s leaves after the windows it is still owed, zero-padded  */
+    const int32_t* given;       /* HOST [S], nullable: bit 0: emo[s] replaces the held id, bit 1: text_features[s]    */
+    const int64_t* emo;         /* [S] (read where given), nullable                                                   */
+    struct ls_sag* sag;         /* LivelySpeaker chain, as in ls_long_sample_args; NULL: none                         */
+    const float* text_features; /* with sag: [S, latent_dim] (read where given), nullable                             */
+    const float* x_init;        /* TAPE: packed round after round, see above                                          */
+    const float* eps_tape;
+    const float* noise_tape;
+    uint64_t seed;              /* PHILOX: the same key in every call of a pool                                       */
+    uint64_t sample_offset;
+    float* frames;              /* [S, J, F, capacity]: slot s's new frames from column 0 on, zero behind them (NULL with capacity 0) */
+    int32_t* n_frames;          /* HOST [S], nullable: frames written per slot                                        */
+    int32_t* n_rounds;          /* HOST, nullable: rounds run                                                         */
+} ls_long_pool_push_args;
+int ls_long_pool_plan(int32_t n_slots, int32_t audio_len, const int64_t* samples_in, const int64_t* windows_run, const int64_t* samples_new,
+                      const int32_t* closing, const int32_t* open, int32_t* n_windows, int32_t* frames, int32_t* round_slots,
+                      int32_t round_capacity, int32_t* n_rounds, int32_t* n_entries);
+int ls_long_pool_open(ls_handle* h, int32_t capacity);
+int ls_long_pool_join(ls_handle* h, const ls_long_pool_join_args* a);
+int ls_long_pool_push(ls_handle* h, const ls_long_pool_push_args* a);
+/* per slot (arrays of `capacity` entries, each nullable): samples fed, windows run, frames written, open; misc = {slots of the pool,
+ * device bytes the pool holds (rings, hand-off stores, held conditioning, gathered window, one window's features), rounds run since
+ * open, 1 while the pool is open} of the handle's current or last pool (a pool that has ended: as it stood then) -- zeros before the
+ * first ls_long_pool_open */
+int ls_long_pool_info(const ls_handle* h, int32_t capacity, int64_t* samples_in, int64_t* windows_run, int64_t* frames_out, int32_t* open,
+                      int64_t misc[4]);
 int ls_step(ls_handle* h, const ls_step_args* a);
 int ls_plms_step(ls_handle* h, const ls_plms_step_args* a);
 /* elementwise q_sample (gaussian_diffusion.py:240-258) at schedule index i; pointers per on_device */

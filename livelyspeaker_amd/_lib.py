@@ -85,6 +85,20 @@ class LsLongStreamPushArgs(C.Structure):
         ("n_frames", c_i32p), ("n_windows", c_i32p)]
 
 
+class LsLongPoolJoinArgs(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("on_device", C.c_int32), ("seed_poses", C.c_void_p), ("vid_index", C.c_void_p), ("scale", C.c_void_p),
+                ("emo", C.c_void_p), ("text_features", C.c_void_p)]
+
+
+class LsLongPoolPushArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("sampler", "noise_mode", "skip_timesteps", "on_device", "use_graph", "clip_denoised",
+                                         "two_pass_always")] + [
+        ("eta", C.c_float), ("capacity", C.c_int32), ("reserved", C.c_int32), ("n_max", C.c_int64), ("audio", C.c_void_p),
+        ("lengths", c_i64p), ("closing", c_i32p), ("given", c_i32p), ("emo", C.c_void_p), ("sag", C.c_void_p), ("text_features", C.c_void_p),
+        ("x_init", C.c_void_p), ("eps_tape", C.c_void_p), ("noise_tape", C.c_void_p), ("seed", C.c_uint64), ("sample_offset", C.c_uint64),
+        ("frames", C.c_void_p), ("n_frames", c_i32p), ("n_rounds", c_i32p)]
+
+
 class LsForwardArgs(C.Structure):
     _fields_ = [("on_device", C.c_int32), ("no_sync", C.c_int32), ("x", C.c_void_p), ("timesteps", C.c_void_p),
                 ("eps_cond", C.c_void_p), ("eps_uncond", C.c_void_p), ("out_cond", C.c_void_p),
@@ -201,7 +215,7 @@ class LsEvalConfig(C.Structure):
 
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
-           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
+           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_long_pool_plan", "ls_long_pool_open", "ls_long_pool_join", "ls_long_pool_push", "ls_long_pool_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
@@ -281,6 +295,11 @@ def load_library(build_if_missing: bool = True):
     lib.ls_long_stream_open.argtypes = [C.c_void_p, C.POINTER(LsLongStreamCond)]
     lib.ls_long_stream_push.argtypes = [C.c_void_p, C.POINTER(LsLongStreamPushArgs)]
     lib.ls_long_stream_info.argtypes = [C.c_void_p, c_i64p]
+    lib.ls_long_pool_plan.argtypes = [C.c_int32, C.c_int32, c_i64p, c_i64p, c_i64p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int32, c_i32p, c_i32p]
+    lib.ls_long_pool_open.argtypes = [C.c_void_p, C.c_int32]
+    lib.ls_long_pool_join.argtypes = [C.c_void_p, C.POINTER(LsLongPoolJoinArgs)]
+    lib.ls_long_pool_push.argtypes = [C.c_void_p, C.POINTER(LsLongPoolPushArgs)]
+    lib.ls_long_pool_info.argtypes = [C.c_void_p, C.c_int32, c_i64p, c_i64p, c_i64p, c_i32p, c_i64p]
     lib.ls_forward.argtypes = [C.c_void_p, C.POINTER(LsForwardArgs)]
     lib.ls_step.argtypes = [C.c_void_p, C.POINTER(LsStepArgs)]
     lib.ls_plms_step.argtypes = [C.c_void_p, C.POINTER(LsPlmsStepArgs)]
@@ -546,6 +565,39 @@ def long_stream_plan(samples_before, samples_new, audio_len, closing=False):
         raise ValueError(f"no windows for {samples_before} + {samples_new} samples (closing={bool(closing)}): counts must be >= 0, "
                          "and a stream that is closed must hold a sample")
     return int(first.value), int(n.value)
+
+
+def long_pool_plan(samples_in, windows_run, samples_new, closing, open, audio_len):
+    """ls_long_pool_plan (no GPU needed): ``(rounds, frames)`` of one push of a session pool.  ``rounds`` is a list of lists -- round r
+    holds, ascending, the slots that run their window ``windows_run[s] + r`` in it -- and ``frames`` int32 [S] the frames each slot gets.
+    The five arrays are host sequences [S].  Samples for a slot that is not open, closing a slot that was fed no sample, or a negative
+    count raise ``ValueError``."""
+    lib = load_library()
+    i64 = lambda a: np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int64)      # noqa: E731
+    i32 = lambda a: np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int32)      # noqa: E731
+    fed, ran, new, closing, open = i64(samples_in), i64(windows_run), i64(samples_new), i32(closing), i32(open)
+    S = int(fed.size)
+    if not (ran.size == new.size == closing.size == open.size == S):
+        raise ValueError(f"one entry per slot: got {[a.size for a in (fed, ran, new, closing, open)]}")
+    p64, p32 = (lambda a: a.ctypes.data_as(c_i64p)), (lambda a: a.ctypes.data_as(c_i32p))
+    wins, frames, n_rounds, n_entries = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.int32), C.c_int32(), C.c_int32()
+
+    def run(slots, cap):
+        return lib.ls_long_pool_plan(S, int(audio_len), p64(fed), p64(ran), p64(new), p32(closing), p32(open), p32(wins), p32(frames), slots, cap,
+                                     C.byref(n_rounds), C.byref(n_entries))
+
+    if run(None, 0) != 0:
+        raise ValueError(f"no plan for samples_in {fed.tolist()} windows_run {ran.tolist()} + {new.tolist()} (closing {closing.tolist()}, open "
+                         f"{open.tolist()}): counts must be >= 0 and consistent, samples go to open slots only, and a slot that is closed must hold a sample")
+    flat = np.zeros(max(int(n_entries.value), 1), np.int32)
+    if run(p32(flat), int(n_entries.value)) != 0:
+        raise EngineError("ls_long_pool_plan failed")
+    rounds, at = [], 0
+    for r in range(int(n_rounds.value)):
+        A = int((wins[:S] > r).sum())
+        rounds.append([int(s) for s in flat[at:at + A]])
+        at += A
+    return rounds, frames[:S].copy()
 
 
 def plan_coop_slices(groups, dataset="ted", n_cus=256):
@@ -1020,6 +1072,82 @@ class Engine(_Handle):
         out = (C.c_int64 * 4)()
         self._check(self.lib.ls_long_stream_info(self.h, out), "ls_long_stream_info")
         return {"samples_in": int(out[0]), "windows_run": int(out[1]), "frames_out": int(out[2]), "device_bytes": int(out[3])}
+
+    # ---- session pool: streams that join and leave ------------------------------------------------
+    def long_pool_open(self, capacity):
+        """A pool of ``capacity`` slots (ls_long_pool_open): everything a round can touch is allocated here.  Replaces whatever
+        ``prepare`` / ``long_prepare`` / ``long_stream_open`` left resident; any of those ends the pool in turn."""
+        self._check(self.lib.ls_long_pool_open(self.h, int(capacity)), "ls_long_pool_open")
+        self.batch, self.n_windows, self.window_batches = int(capacity), 0, None
+
+    def long_pool_join(self, slot, seed_poses, vid_index, scale, emo=None, text_features=None):
+        """Fill the free slot ``slot`` (ls_long_pool_join): ``seed_poses`` [J, F, n_pre], one speaker id, one scale, and the held
+        ``emo`` id (BEAT) / ``text_features`` [D]."""
+        as1 = lambda a: None if a is None else (a.reshape(1) if hasattr(a, "reshape") else np.asarray(a).reshape(1))      # noqa: E731
+        vid_index, scale, emo = as1(vid_index), as1(scale), as1(emo)
+        m = _Marshal(self.device, seed_poses, vid_index, scale, emo, text_features, stream=self._stream)
+        a = LsLongPoolJoinArgs(int(slot), int(m.on_device), m.f32(seed_poses, (self.J, self.F, int(self.cfg.n_pre_seq))), m.i64(vid_index, (1,)),
+                               m.f32(scale, (1,)), m.i64(emo, (1,)), m.f32(text_features, (self.D,)))
+        m.ready()
+        self._check(self.lib.ls_long_pool_join(self.h, C.byref(a)), "ls_long_pool_join")
+
+    def long_pool_push(self, audio, lengths, closing=None, emo=None, text_features=None, given=None, sag=None, sampler=LS_SAMPLER_DDIM,
+                       x_init=None, eps_tape=None, noise_tape=None, skip_timesteps=0, eta=0.0, philox_seed=None, sample_offset=0,
+                       use_graph=True, clip_denoised=False, two_pass_always=False, device_out=False):
+        """Feed the ragged chunk ``audio`` [S, n_max] -- ``lengths`` [S] (host) samples per slot -- and run the rounds of
+        ``long_pool_plan`` (ls_long_pool_push).  ``closing`` [S] (host): the slot leaves after the windows it is owed.  ``emo`` [S] /
+        ``text_features`` [S, D] replace the held conditioning of the slots whose ``given`` [S] (host) has bit 0 / bit 1 set.  TAPE mode
+        takes the draws packed round after round at each round's batch A (``x_init`` [sum A, J, F, T], flat ``eps_tape`` / ``noise_tape``
+        holding per round [n_exec, 2, A, D] / [n_exec, A, J, F, T]), PHILOX mode ``philox_seed``.  Returns ``(frames [S, J, F, K], counts
+        int32 [S], rounds)`` with K the most frames any slot got; a slot's row is zero behind its own count."""
+        info = self.long_pool_info()        # of the last pool, whatever has been prepared on the handle since
+        S, D = info["capacity"], self.D
+        n = int(audio.shape[1])
+        assert tuple(int(s) for s in audio.shape) == (S, n), (tuple(audio.shape), S)
+        lens = np.ascontiguousarray(np.asarray(lengths).reshape(-1), dtype=np.int64)
+        cl = np.ascontiguousarray(np.zeros(S) if closing is None else np.asarray(closing).reshape(-1), dtype=np.int32)
+        gv = None if given is None else np.ascontiguousarray(np.asarray(given).reshape(-1), dtype=np.int32)
+        assert lens.shape == cl.shape == (S,) and (gv is None or gv.shape == (S,)), (lens.shape, cl.shape, S)
+        rounds, per_slot = long_pool_plan(info["samples_in"], info["windows_run"], lens, cl, info["open"], self.cfg.audio_len)
+        cap, rows = int(per_slot.max()), sum(len(r) for r in rounds)
+        m = self._marshal([audio if n else None, emo, text_features] + ([x_init, eps_tape, noise_tape] if rows else []), device_out)
+        a = LsLongPoolPushArgs()
+        n_exec = self._chain_sampler(a, m, sampler, skip_timesteps, use_graph, clip_denoised, two_pass_always, eta)
+        a.capacity, a.n_max = cap, n
+        if n:
+            a.audio = m.f32(audio, (S, n))
+        a.lengths, a.closing = lens.ctypes.data_as(c_i64p), cl.ctypes.data_as(c_i32p)
+        if gv is not None:
+            a.given = gv.ctypes.data_as(c_i32p)
+        a.emo = m.i64(emo, (S,))
+        if sag is not None:
+            a.sag = sag.h
+        a.text_features = m.f32(text_features, (S, D))
+        self._chain_noise(a, m, rows or None, n_exec, x_init, eps_tape, noise_tape, philox_seed, sample_offset, packed=True)
+        frames, pframes = m.out((S, self.J, self.F, cap))
+        if cap:
+            a.frames = pframes
+        counts, n_rounds = np.full(S, -1, np.int32), C.c_int32(-1)
+        a.n_frames, a.n_rounds = counts.ctypes.data_as(c_i32p), C.pointer(n_rounds)
+        m.ready()
+        self._check(self.lib.ls_long_pool_push(self.h, C.byref(a)), "ls_long_pool_push")
+        assert counts.tolist() == per_slot.tolist() and int(n_rounds.value) == len(rounds), (counts, per_slot, n_rounds.value, rounds)
+        if not rounds:      # nothing was waited for: torch's stream must not reuse the chunk before the engine's stream has read it
+            m.done_async()
+        return frames, counts, rounds
+
+    def long_pool_info(self) -> dict:
+        """ls_long_pool_info of the current (or last) pool: per-slot numpy arrays samples_in, windows_run, frames_out (int64) and open
+        (bool), and the ints capacity, device_bytes, rounds, is_open."""
+        misc = (C.c_int64 * 4)()
+        self._check(self.lib.ls_long_pool_info(self.h, 0, None, None, None, None, misc), "ls_long_pool_info")
+        S = int(misc[0])
+        fed, ran, out = (np.zeros(max(S, 1), np.int64) for _ in range(3))
+        opened = np.zeros(max(S, 1), np.int32)
+        p64 = lambda a: a.ctypes.data_as(c_i64p)      # noqa: E731
+        self._check(self.lib.ls_long_pool_info(self.h, S, p64(fed), p64(ran), p64(out), opened.ctypes.data_as(c_i32p), misc), "ls_long_pool_info")
+        return {"samples_in": fed[:S], "windows_run": ran[:S], "frames_out": out[:S], "open": opened[:S].astype(bool), "capacity": S,
+                "device_bytes": int(misc[1]), "rounds": int(misc[2]), "is_open": bool(misc[3])}
 
     def q_sample(self, index, x_start, noise):
         m = _Marshal(self.device, x_start, noise, stream=self._stream)

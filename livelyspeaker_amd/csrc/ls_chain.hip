@@ -15,7 +15,8 @@
 // 163 KB BEAT (with the init plane); scatter at most 11.0 KB TED, 115 KB BEAT (with the raw window); the terms are spelled out at the kernels.
 // A STREAM (ls_long_stream_push) runs k_chain_window behind every window instead of ahead of it -- the same launch flushes the window into
 // the push's output and leaves the next window's prefix poses in feat_u / origin_x until the push that runs it -- and k_stream_gather
-// (at the end) cuts a window's audio out of the stream's circular ring.
+// cuts a window's audio out of the stream's circular ring.  A SESSION POOL (ls_long_pool_push) keeps all of that per slot: k_pool_gather
+// and k_pool_scatter (at the end) move one round's active slots into and out of the compact rows a sampling call at that batch reads.
 #include "ls_internal.h"
 
 namespace ls {
@@ -203,11 +204,9 @@ hipError_t launch_long_gather_clips(const float* audio, const int* table, const 
 // layout, the float4 store per thread and the scalar head and tail are k_long_gather_clips'; the load is a float4 when all four samples
 // exist, the ring position is a multiple of four (R is one, and a clip's ring starts 16-byte aligned) and the group does not cross the
 // ring's end, four guarded scalar loads otherwise.  Bytes: reads at most and writes exactly B * AL floats.
-__global__ __launch_bounds__(256) void k_stream_gather(const float* __restrict__ ring, float* __restrict__ clips, int AL, int R, int pos0, int n_valid) {
-    const int b = blockIdx.y;
-    const float* src = ring + (size_t)b * R;
-    float* dst = clips + (size_t)b * AL;
-    const int to_aligned = (int)((4 - ((size_t)b * AL & 3)) & 3), head = to_aligned < AL ? to_aligned : AL;
+// the body shared with k_pool_gather: workgroup x of the row whose source ring is src and whose destination is clips row `row` at dst
+__device__ __forceinline__ void gather_ring_window(const float* __restrict__ src, float* __restrict__ dst, int row, int AL, int R, int pos0, int n_valid) {
+    const int to_aligned = (int)((4 - ((size_t)row * AL & 3)) & 3), head = to_aligned < AL ? to_aligned : AL;
     const int nvec = (AL - head) / 4;
     auto pos = [&](int i) { const int q = pos0 + i; return q >= R ? q - R : q; };      // pos0 < R and i < AL <= R: one wrap at most
     auto at = [&](int i) { return i < n_valid ? src[pos(i)] : 0.f; };
@@ -229,11 +228,95 @@ __global__ __launch_bounds__(256) void k_stream_gather(const float* __restrict__
     *reinterpret_cast<float4*>(dst + i) = v;
 }
 
+__global__ __launch_bounds__(256) void k_stream_gather(const float* __restrict__ ring, float* __restrict__ clips, int AL, int R, int pos0, int n_valid) {
+    const int b = blockIdx.y;
+    gather_ring_window(ring + (size_t)b * R, clips + (size_t)b * AL, b, AL, R, pos0, n_valid);
+}
+
 hipError_t launch_stream_gather(const float* ring, float* clips, int B, int AL, int R, int pos0, int n_valid, hipStream_t st) {
     if (B < 1 || B > 65535 || AL < 1 || R < AL || (R & 3) || pos0 < 0 || pos0 >= R || n_valid < 0 || n_valid > AL) return hipErrorInvalidValue;
     if (((size_t)clips & 15) || ((size_t)ring & 15)) return hipErrorInvalidValue;
     const int gx = (AL / 4 + 255) / 256;             // >= the float4 groups of a clip, whatever its head
     hipLaunchKernelGGL(k_stream_gather, dim3(gx > 0 ? gx : 1, B), dim3(256), 0, st, ring, clips, AL, R, pos0, n_valid);
+    return hipGetLastError();
+}
+
+// One round of a SESSION POOL (ls_long_pool_push; PoolArgs in ls_internal.h): the A active slots of the round, in ascending slot order,
+// become the rows 0 .. A-1 of every buffer a sampling call at batch A reads.  Workgroup (x, r) reads its table row once (a uniform
+// load; no other load depends on a loaded value) and, for x below the audio workgroups, is k_stream_gather on slot table[r][0]'s ring
+// at that slot's own position and valid count.  The one workgroup behind them (x == gridDim.x - 1) moves the slot's conditioning: its
+// hand-off poses into the prefix rows of feat_u ([poses | 1 | 0 pad]) and the prefix columns of origin_x -- what k_chain_window
+// writes for a next window; everything outside the prefix is zero from ls_long_pool_open on -- and its speaker id, guidance scale,
+// emotion token and text features into compact row r (512-float rows as float4: every row starts 2 KB-aligned).
+// Bytes per row (fp32): reads at most and writes AL samples; reads JF*n_pre poses, writes n_pre*(KPP + JF); 12 + 2 * 2 KB conditioning.
+__global__ __launch_bounds__(256) void k_pool_gather(const PoolArgs a) {
+    const int r = blockIdx.y, tid = threadIdx.x;
+    const int* row = a.table + (size_t)r * kPoolRow;
+    const int slot = row[0];
+    if (blockIdx.x + 1 < gridDim.x) {
+        gather_ring_window(a.ring + (size_t)slot * a.R, a.clips + (size_t)r * a.AL, r, a.AL, a.R, row[1], row[2]);
+        return;
+    }
+    const int JF = a.JF, T = a.T, npre = a.n_pre;
+    const float* hand = a.hand + (size_t)slot * JF * npre;          // [JF][n_pre]
+    float* fu = a.feat_u + (size_t)r * T * a.KPP;
+    for (int i = tid; i < npre * a.KPP; i += 256) {
+        const int j = i / a.KPP, c = i - j * a.KPP;
+        fu[i] = c < JF ? hand[c * npre + j] : c == JF ? 1.f : 0.f;
+    }
+    float* ox = a.origin_x + (size_t)r * JF * T;
+    for (int i = tid; i < JF * npre; i += 256) {
+        const int c = i / npre, j = i - c * npre;
+        ox[(size_t)c * T + j] = hand[i];
+    }
+    if (tid == 0) { a.vid[r] = a.vid_s[slot]; a.scale[r] = a.scale_s[slot]; }
+    if (a.emo_tok && tid < kD / 4)
+        reinterpret_cast<float4*>(a.emo_tok + (size_t)r * kD)[tid] = reinterpret_cast<const float4*>(a.emo_tok_s + (size_t)slot * kD)[tid];
+    if (a.text && tid >= 128 && tid < 128 + kD / 4)
+        reinterpret_cast<float4*>(a.text + (size_t)r * kD)[tid - 128] = reinterpret_cast<const float4*>(a.text_s + (size_t)slot * kD)[tid - 128];
+}
+
+// ... and the way back: one workgroup per row, k_chain_window's tile (row stride JF | 1: the transposed reads touch every bank once).
+// Row r's frames f0 .. T-1 go to frames[slot] at the slot's own frame offset in this call (stores along the frame axis), its last n_pre
+// poses into the slot's hand-off store, where the gather of the slot's next window -- in this call or a later one -- finds them.
+// Bytes per row (fp32): reads T*JF, writes (T - f0)*JF + n_pre*JF.
+__global__ __launch_bounds__(256) void k_pool_scatter(const PoolArgs a) {
+    extern __shared__ float tile[];                 // [T][JF | 1]
+    const int r = blockIdx.x, tid = threadIdx.x, JF = a.JF, T = a.T, ld = JF | 1, npre = a.n_pre;
+    const int* row = a.table + (size_t)r * kPoolRow;
+    const int slot = row[0], f0 = row[3], t_off = row[4];
+    const float* src = a.prev + (size_t)r * T * JF;
+    for (int i = tid; i < T * JF; i += 256) tile[(i / JF) * ld + i % JF] = src[i];
+    __syncthreads();
+    const int nf = T - f0;
+    float* fr = a.frames + (size_t)slot * JF * a.T_total + t_off;
+    for (int i = tid; i < JF * nf; i += 256) {
+        const int c = i / nf, f = i - c * nf;
+        fr[(size_t)c * a.T_total + f] = tile[(f0 + f) * ld + c];
+    }
+    float* hand = a.hand + (size_t)slot * JF * npre;
+    for (int i = tid; i < JF * npre; i += 256) {
+        const int c = i / npre, j = i - c * npre;
+        hand[i] = tile[(T - npre + j) * ld + c];
+    }
+}
+
+static bool pool_args_ok(const PoolArgs& a, int A) {
+    return A >= 1 && A <= a.S && a.S <= 65535 && a.table && a.hand && a.JF >= 1 && a.T >= 1 && a.n_pre >= 1 && a.n_pre <= a.T;
+}
+hipError_t launch_pool_gather(const PoolArgs& a, int A, hipStream_t st) {
+    if (!pool_args_ok(a, A) || a.AL < 1 || a.R < a.AL || (a.R & 3) || a.KPP <= a.JF) return hipErrorInvalidValue;
+    if (!a.ring || !a.clips || !a.feat_u || !a.origin_x || !a.vid_s || !a.scale_s || !a.vid || !a.scale) return hipErrorInvalidValue;
+    if (((size_t)a.clips & 15) || ((size_t)a.ring & 15) || (a.emo_tok && (!a.emo_tok_s || (((size_t)a.emo_tok | (size_t)a.emo_tok_s) & 15))) ||
+        (a.text && (!a.text_s || (((size_t)a.text | (size_t)a.text_s) & 15)))) return hipErrorInvalidValue;
+    const int gx = (a.AL / 4 + 255) / 256;           // >= the float4 groups of a clip, whatever its head
+    hipLaunchKernelGGL(k_pool_gather, dim3((gx > 0 ? gx : 1) + 1, A), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_pool_scatter(const PoolArgs& a, int A, hipStream_t st) {
+    const size_t lds = (size_t)a.T * (a.JF | 1) * sizeof(float);
+    if (!pool_args_ok(a, A) || lds > 64 * 1024 || !a.prev || !a.frames || a.T_total < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pool_scatter, dim3(A), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 

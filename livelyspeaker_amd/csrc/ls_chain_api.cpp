@@ -3,8 +3,9 @@
 // (run_window_loop, ls_sample.cpp), handed the last poses of the window before it.  There is one once-per-call stage (check_cond ->
 // start_prepare -> ingest_cond -> size_batch_buffers -> finish_prepare) and one window runner (chain_args -> chain_begin -> run_window
 // per window -> chain_finish); the entries hold what differs: where a window's audio features come from (all windows encoded ahead,
-// packed for clips of different lengths, or one window at a time from a stream's ring) and what stands around a window (k_chain_window
-// ahead of it, k_chain_window behind it, or k_edit_gather / k_edit_scatter).  The host-only plans are ls_chain_plan.cpp.
+// packed for clips of different lengths, one window at a time from a stream's ring, or one round at a time from the rings of a session
+// pool's active slots) and what stands around a window (k_chain_window ahead of it, k_chain_window behind it, k_edit_gather /
+// k_edit_scatter, or k_pool_gather / k_pool_scatter).  The host-only plans are ls_chain_plan.cpp.
 #include "ls_handle.h"
 
 #include <cstdint>
@@ -292,6 +293,155 @@ int stream_push_run(ls_handle* h, const ls_long_stream_push_args* a, ChainCall& 
     return chain_finish(h, cc, {{od ? nullptr : a->frames, out, (size_t)B * JF * cap * sizeof(float)}});
 }
 
+// ---- the session pool -----------------------------------------------------------------------------------------------------------
+int pool_is_open(ls_handle* h, const char* entry) {
+    switch (h->pl_state) {
+    case ls_handle::kStreamOpen: return LS_OK;
+    case ls_handle::kStreamNone: return fail(h, LS_ESTATE, "%s before ls_long_pool_open", entry);
+    case ls_handle::kStreamFailed: return fail(h, LS_ESTATE, "%s: an earlier push of this pool failed; open a new one", entry);
+    default: return fail(h, LS_ESTATE, "%s: the pool was ended by a call that replaced the handle's prepared conditioning "
+                                       "(ls_prepare, ls_long_prepare, ls_long_stream_open, ls_commit_weights or another ls_long_pool_open); open a new one", entry);
+    }
+}
+
+// one element or row of a slot's held conditioning from the caller (host or device) into its per-slot store
+int pool_hold(ls_handle* h, void* dst, const void* src, size_t bytes, int od) {
+    HIPCHK(h, hipMemcpyAsync(dst, src, bytes, od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    return LS_OK;
+}
+int pool_hold_emo(ls_handle* h, int s, const int64_t* id, int od) {
+    int64_t* at = static_cast<int64_t*>(h->pl_emo_id.p) + s;
+    const int rc = pool_hold(h, at, id, sizeof(int64_t), od);
+    if (rc != LS_OK) return rc;
+    HIPCHK(h, launch_gather_rows(h->emo_emb.f(), at, h->pl_emotok.f() + (size_t)s * kD, 1, kD, h->cfg.n_emotions, h->stream));
+    h->pl_have_emo[(size_t)s] = 1;
+    return LS_OK;
+}
+int pool_hold_text(ls_handle* h, int s, const float* row, int od) {
+    const int rc = pool_hold(h, h->pl_text.f() + (size_t)s * kD, row, kD * sizeof(float), od);
+    h->pl_have_text[(size_t)s] = 1;
+    return rc;
+}
+
+// Everything of a pool's push behind its argument checks.  win[s]: the windows slot s runs (ls_long_pool_plan), rounds: the plan's
+// slots round after round.  Ahead of every round each slot takes as much of its chunk as its ring has room for -- a slot's next
+// window always fits behind the samples its earlier windows made dead -- so the rounds are the plan's whatever the chunk sizes.  Per
+// round: k_pool_gather -> WavEncoder -> k_build_feats at batch A, the per-batch stages at A, the window body, k_pool_scatter.  Nothing
+// is allocated from the first launch on.
+int pool_push_run(ls_handle* h, const ls_long_pool_push_args* a, ChainCall& cc, const std::vector<int32_t>& win, const std::vector<int32_t>& rounds, int n_rounds) {
+    const int S = h->pl_S, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, AL = h->cfg.audio_len, R = h->pl_R, od = a->on_device, cap = a->capacity;
+    const bool beat = h->cfg.n_prefix_tokens == 2;
+    const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    hipStream_t st = h->stream;
+    int rc;
+    auto closing = [&](int s) { return a->closing && a->closing[s] && h->pl_open[(size_t)s]; };
+    for (int s = 0; s < S && a->given; ++s) {       // the held conditioning: what this call passes holds for every window started from here on
+        if ((a->given[s] & 1) && (rc = pool_hold_emo(h, s, a->emo + s, od)) != LS_OK) return rc;
+        if ((a->given[s] & 2) && (rc = pool_hold_text(h, s, a->text_features + (size_t)s * kD, od)) != LS_OK) return rc;
+    }
+    const size_t out_bytes = (size_t)S * JF * cap * sizeof(float), nxS = (size_t)S * JF * T * sizeof(float);
+    float* out = a->frames;
+    if (n_rounds > 0) {         // what the rounds need beyond ls_long_pool_open's buffers, sized for S slots while nothing is in flight
+        if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
+        h->seg_next = -1;
+        if (cc.tape) {
+            if ((rc = ensure_pinned(h, h->eps_tape, (size_t)cc.n_exec * 2 * S * kD * sizeof(float))) != LS_OK || (rc = ensure_pinned(h, h->noise_tape, cc.n_exec * nxS)) != LS_OK) return rc;
+            if (!od) { HIPCHK(h, h->lg_x.ensure(nxS)); HIPCHK(h, h->lg_eps.ensure((size_t)cc.n_exec * 2 * S * kD * sizeof(float))); HIPCHK(h, h->lg_nz.ensure(cc.n_exec * nxS)); }
+        }
+        if (a->sag) {
+            cc.sag = a->sag; cc.sag_st = ls_sag_stream(a->sag);
+            HIPCHK(h, hipMemsetAsync(h->lg_mask.p, 1, (size_t)S * T, st));
+            cc.wa.init_image = h->lg_init.f();
+        }
+        if (!od) { HIPCHK(h, h->lg_timeline.ensure(out_bytes)); out = h->lg_timeline.f(); }
+        HIPCHK(h, hipMemsetAsync(out, 0, out_bytes, st));      // a slot's row is zero behind its own frames
+    }
+    std::vector<long long> fed((size_t)S, 0);
+    auto feed = [&]() -> int {
+        for (int s = 0; s < S; ++s) {
+            const long long left = a->lengths[s] - fed[(size_t)s], room = R - (h->pl_samples[(size_t)s] - (long long)LS_LONG_AUDIO_STRIDE * h->pl_windows[(size_t)s]);
+            const int take = (int)(left < room ? left : room);
+            if (take <= 0) continue;
+            const int p = (int)(h->pl_samples[(size_t)s] % R), seg1 = take < R - p ? take : R - p;
+            const float* src = a->audio + (size_t)s * (size_t)a->n_max + (size_t)fed[(size_t)s];
+            float* ring = h->pl_ring.f() + (size_t)s * R;
+            HIPCHK(h, hipMemcpyAsync(ring + p, src, (size_t)seg1 * sizeof(float), kind, st));
+            if (take > seg1) HIPCHK(h, hipMemcpyAsync(ring, src + seg1, (size_t)(take - seg1) * sizeof(float), kind, st));
+            fed[(size_t)s] += take; h->pl_samples[(size_t)s] += take;
+        }
+        return LS_OK;
+    };
+    PoolArgs pa{};
+    pa.table = static_cast<const int*>(h->pl_table.p);
+    pa.ring = h->pl_ring.f(); pa.clips = h->lg_clips.f(); pa.hand = h->pl_hand.f(); pa.feat_u = h->feat_u.f(); pa.origin_x = h->origin_x.f();
+    pa.vid_s = static_cast<const int64_t*>(h->pl_vid.p); pa.scale_s = h->pl_scale.f(); pa.vid = static_cast<int64_t*>(h->vid.p); pa.scale = h->scale.f();
+    if (beat) { pa.emo_tok_s = h->pl_emotok.f(); pa.emo_tok = h->emo_tok.f(); }
+    if (a->sag) { pa.text_s = h->pl_text.f(); pa.text = h->pl_ctext.f(); }
+    pa.frames = out;
+    pa.S = S; pa.AL = AL; pa.R = R; pa.JF = JF; pa.T = T; pa.KPP = h->KPP; pa.n_pre = npre; pa.T_total = cap;
+    std::vector<int> t_off((size_t)S, 0), table((size_t)S * kPoolRow, 0);
+    size_t at = 0, rows_before = 0;          // position in `rounds`; rows of the rounds run so far (the packed tapes)
+    for (int r = 0; r < n_rounds; ++r) {
+        if ((rc = feed()) != LS_OK) return rc;
+        int A = 0;
+        for (int s = 0; s < S; ++s) A += win[(size_t)s] > r;
+        bool ones = true;
+        for (int i = 0; i < A; ++i) {
+            const int s = rounds[at + (size_t)i];
+            const long long w = h->pl_windows[(size_t)s], lo = w * LS_LONG_AUDIO_STRIDE, have = h->pl_samples[(size_t)s] - lo;
+            const int valid = (int)(have < AL ? (have < 0 ? 0 : have) : AL), f0 = w == 0 ? 0 : npre;
+            if (valid < AL && !(closing(s) && fed[(size_t)s] == a->lengths[s])) return fail(h, LS_ESTATE, "ls_long_pool_push: window %lld of slot %d is not complete", w, s);
+            if (t_off[(size_t)s] + T - f0 > cap) return fail(h, LS_ESTATE, "ls_long_pool_push: slot %d runs more frames than the call was planned for", s);
+            int* row = &table[(size_t)i * kPoolRow];
+            row[0] = s; row[1] = (int)(lo % R); row[2] = valid; row[3] = f0; row[4] = t_off[(size_t)s];
+            ones = ones && h->pl_scale_host[(size_t)s] == 1.0f;
+        }
+        // the round's table: one upload of pageable memory, taken into the runtime's staging memory before the call returns (as call_host is)
+        HIPCHK(h, hipMemcpyAsync(h->pl_table.p, table.data(), (size_t)A * kPoolRow * sizeof(int), hipMemcpyHostToDevice, st));
+        HIPCHK(h, launch_pool_gather(pa, A, st));
+        if ((rc = run_wav_encoder(h, h->lg_clips.f(), A)) != LS_OK) return rc;
+        HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f(), A, JF, h->KPP, 0, st, T));
+        // from here on the handle is prepared for a batch of A: its scales decide the single-pass form, its size the step plan
+        h->B = A;
+        h->all_scale_one = ones;
+        set_plan(h, A);
+        if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+        if ((rc = prepare_style(h, A)) != LS_OK) return rc;
+        Window wn;
+        wn.w = h->pl_rounds; wn.Bw = A; wn.featc = h->lg_featc.f(); wn.text = a->sag ? h->pl_ctext.f() : nullptr; wn.first = r == 0;
+        wn.policy = kKeep;          // a batch size met once is met again; kKeep never destroys a graph under the replays in flight
+        if (cc.tape) {
+            wn.x_init = a->x_init + rows_before * JF * T; wn.eps_tape = a->eps_tape + rows_before * cc.n_exec * 2 * kD; wn.noise_tape = a->noise_tape + rows_before * cc.n_exec * JF * T;
+            wn.host_tapes = !od;
+        }
+        if ((rc = run_window(h, cc, wn)) != LS_OK) return rc;
+        pa.prev = x_plane(h, cc.n_exec);
+        HIPCHK(h, launch_pool_scatter(pa, A, st));
+        for (int i = 0; i < A; ++i) {
+            const int s = rounds[at + (size_t)i];
+            t_off[(size_t)s] += T - table[(size_t)i * kPoolRow + 3];
+            ++h->pl_windows[(size_t)s];
+        }
+        ++h->pl_rounds;
+        at += (size_t)A; rows_before += (size_t)A;
+    }
+    if ((rc = feed()) != LS_OK) return rc;
+    bool any = false;
+    for (int s = 0; s < S; ++s) {
+        if (fed[(size_t)s] != a->lengths[s]) return fail(h, LS_ESTATE, "ls_long_pool_push: no room in the ring of slot %d and no window to run", s);
+        any = any || fed[(size_t)s] > 0;
+        h->pl_frames[(size_t)s] += t_off[(size_t)s];
+        if (a->n_frames) a->n_frames[s] = t_off[(size_t)s];
+        if (closing(s)) h->pl_open[(size_t)s] = 0;
+    }
+    if (a->n_rounds) *a->n_rounds = n_rounds;
+    if (n_rounds == 0) {        // no sampling work: a host chunk is the caller's again once its copies are done
+        if ((!od && any) || a->given) { HIPCHK(h, hipEventRecord(h->ev[6], st)); HIPCHK(h, hipEventSynchronize(h->ev[6])); }
+        return LS_OK;
+    }
+    return chain_finish(h, cc, {{od ? nullptr : a->frames, out, out_bytes}});
+}
+
 }  // namespace
 
 extern "C" {
@@ -436,7 +586,8 @@ int ls_long_stream_open(ls_handle* h, const ls_long_stream_cond* c) {
     const int B = c->batch, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, od = c->on_device;
     const int R = (AL + LS_LONG_AUDIO_STRIDE + 3) / 4 * 4;       // a window and the stride to the next; whole float4 groups per clip
     hipStream_t st = h->stream;
-    h->st_state = ls_handle::kStreamNone;       // a stream that was open ends here; this one opens when everything below has succeeded
+    end_stream(h);                              // a running session pool ends here ...
+    h->st_state = ls_handle::kStreamNone;       // ... and so does a stream that was open; this one opens when everything below has succeeded
     if ((rc = start_prepare(h)) != LS_OK) return rc;
     if ((rc = ingest_cond(h, B, od, c->seed_poses, c->vid_indices, c->scale, nullptr, 0)) != LS_OK) return rc;
     HIPCHK(h, h->st_ring.ensure((size_t)B * R * sizeof(float)));
@@ -696,6 +847,156 @@ int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) {
     for (int w = 0, k = 0; w < W && a->windows_run; ++w)
         if (flags[(size_t)w] && k < a->windows_capacity) a->windows_run[k++] = w;
     if (a->n_windows_run) *a->n_windows_run = We;
+    return LS_OK;
+}
+
+// Opening a session pool (ls_hip.h): ls_long_stream_open's stages for `capacity` slots without any slot's conditioning.  Every buffer a
+// round touches is sized for S rows here -- the per-slot stores, the compact batch buffers, the WavEncoder's activations (one run on
+// silence), the style buffers (one run on speaker 0), the loop's planes and tape buffers, the SAG plane and mask, and the workspaces of
+// the step plans of every batch 1..S under both forms of a step -- so that a push allocates only what depends on its own arguments (a
+// host caller's tape staging and output; the tape buffers again when the schedule grew after the open), ahead of its first launch, with
+// nothing in flight.  No graph of an earlier call survives: its addresses may predate these buffers.
+int ls_long_pool_open(ls_handle* h, int32_t capacity) {
+    if (!h) return fail(h, LS_EINVAL, "ls_long_pool_open: null argument");
+    int rc;
+    if ((rc = check_cond(h, "ls_long_pool_open", capacity, nullptr, true, true, true)) != LS_OK) return rc;
+    if (capacity > 1024) return fail(h, LS_EINVAL, "ls_long_pool_open: capacity %d beyond 1024 slots", capacity);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int S = capacity, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, npre = h->cfg.n_pre_seq;
+    const int R = (AL + LS_LONG_AUDIO_STRIDE + 3) / 4 * 4;       // as a stream's ring
+    const size_t nxS = (size_t)S * JF * T * sizeof(float), rowS = (size_t)S * kD * sizeof(float);
+    hipStream_t st = h->stream;
+    end_stream(h);
+    h->pl_state = ls_handle::kStreamNone;
+    if ((rc = start_prepare(h)) != LS_OK) return rc;
+    HIPCHK(h, h->pl_ring.ensure((size_t)S * R * sizeof(float)));
+    HIPCHK(h, h->pl_hand.ensure((size_t)S * JF * npre * sizeof(float)));
+    HIPCHK(h, h->pl_vid.ensure((size_t)S * sizeof(int64_t))); HIPCHK(h, h->pl_emo_id.ensure((size_t)S * sizeof(int64_t)));
+    HIPCHK(h, h->pl_scale.ensure((size_t)S * sizeof(float)));
+    HIPCHK(h, h->pl_emotok.ensure(rowS)); HIPCHK(h, h->pl_text.ensure(rowS)); HIPCHK(h, h->pl_ctext.ensure(rowS));
+    HIPCHK(h, h->pl_table.ensure((size_t)S * kPoolRow * sizeof(int)));
+    HIPCHK(h, h->lg_clips.ensure((size_t)S * AL * sizeof(float)));
+    HIPCHK(h, h->lg_featc.ensure((size_t)S * T * kAudioFeat * sizeof(float)));
+    HIPCHK(h, h->lg_featp.ensure((size_t)S * T * KPP * sizeof(float)));
+    HIPCHK(h, h->vid.ensure((size_t)S * sizeof(int64_t))); HIPCHK(h, h->scale.ensure((size_t)S * sizeof(float)));
+    HIPCHK(h, h->xa.ensure(nxS)); HIPCHK(h, h->xb.ensure(nxS)); HIPCHK(h, h->xtmp.ensure(nxS)); HIPCHK(h, h->xio.ensure(nxS));
+    HIPCHK(h, h->lg_init.ensure(nxS)); HIPCHK(h, h->lg_mask.ensure((size_t)S * T));
+    if (h->have_sched) {        // the tape buffers for the longest loop of the schedule (a push checks them again: the schedule may be set later)
+        HIPCHK(h, h->eps_tape.ensure((size_t)h->n_steps * 2 * S * kD * sizeof(float))); HIPCHK(h, h->noise_tape.ensure(h->n_steps * nxS));
+    }
+    for (DevBuf* d : {&h->pl_vid, &h->pl_emo_id, &h->pl_scale, &h->pl_hand, &h->pl_emotok, &h->pl_text, &h->lg_clips, &h->vid, &h->scale})
+        HIPCHK(h, hipMemsetAsync(d->p, 0, d->bytes, st));
+    if ((rc = zero_origin_x(h, S)) != LS_OK || (rc = size_batch_buffers(h, S)) != LS_OK) return rc;
+    if ((rc = run_wav_encoder(h, h->lg_clips.f(), S)) != LS_OK) return rc;
+    if ((rc = prepare_style(h, S)) != LS_OK) return rc;
+    for (int pair = 0; pair < 2; ++pair)
+        for (int b = 1; b <= S; ++b) {      // smallest first: the handle is left planned for S slots
+            h->all_scale_one = pair != 0;
+            set_plan(h, b);
+            if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+        }
+    if ((rc = finish_prepare(h, S)) != LS_OK) return rc;
+    free_graph(h);
+    h->pl_S = S; h->pl_R = R; h->pl_rounds = 0;
+    h->pl_samples.assign((size_t)S, 0); h->pl_windows.assign((size_t)S, 0); h->pl_frames.assign((size_t)S, 0);
+    h->pl_scale_host.assign((size_t)S, 0.f);
+    h->pl_open.assign((size_t)S, 0); h->pl_have_emo.assign((size_t)S, 0); h->pl_have_text.assign((size_t)S, 0);
+    h->pl_state = ls_handle::kStreamOpen;
+    return LS_OK;
+}
+
+int ls_long_pool_join(ls_handle* h, const ls_long_pool_join_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_pool_join: null argument");
+    int rc;
+    if ((rc = pool_is_open(h, "ls_long_pool_join")) != LS_OK) return rc;
+    if (a->slot < 0 || a->slot >= h->pl_S) return fail(h, LS_EINVAL, "ls_long_pool_join: slot %d outside [0, %d)", a->slot, h->pl_S);
+    if (h->pl_open[(size_t)a->slot]) return fail(h, LS_ESTATE, "ls_long_pool_join: slot %d is occupied", a->slot);
+    if (!a->seed_poses || !a->vid_index || !a->scale) return fail(h, LS_EINVAL, "ls_long_pool_join: null conditioning pointer");
+    if (h->cfg.n_prefix_tokens == 2 ? !a->emo : a->emo != nullptr) return fail(h, LS_EINVAL, h->cfg.n_prefix_tokens == 2 ? "BEAT variant needs emo ids" : "ls_long_pool_join: emo is a BEAT conditioning");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int s = a->slot, od = a->on_device;
+    const size_t hand = (size_t)h->JF * h->cfg.n_pre_seq;
+    if ((rc = pool_hold(h, h->pl_hand.f() + (size_t)s * hand, a->seed_poses, hand * sizeof(float), od)) != LS_OK) return rc;
+    if ((rc = pool_hold(h, static_cast<int64_t*>(h->pl_vid.p) + s, a->vid_index, sizeof(int64_t), od)) != LS_OK) return rc;
+    if ((rc = pool_hold(h, h->pl_scale.f() + s, a->scale, sizeof(float), od)) != LS_OK) return rc;
+    h->pl_have_emo[(size_t)s] = h->pl_have_text[(size_t)s] = 0;
+    if (a->emo && (rc = pool_hold_emo(h, s, a->emo, od)) != LS_OK) return rc;
+    if (a->text_features && (rc = pool_hold_text(h, s, a->text_features, od)) != LS_OK) return rc;
+    float sc = 0.f;
+    if (od) HIPCHK(h, hipMemcpyAsync(&sc, h->pl_scale.f() + s, sizeof(float), hipMemcpyDeviceToHost, h->stream));      // the one read-back, as in prepare_scale
+    else sc = *a->scale;
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // the caller's arrays are its own again
+    h->pl_scale_host[(size_t)s] = sc;
+    h->pl_samples[(size_t)s] = h->pl_windows[(size_t)s] = h->pl_frames[(size_t)s] = 0;     // the ring position with them: sample n sits at n % R
+    h->pl_open[(size_t)s] = 1;
+    return LS_OK;
+}
+
+int ls_long_pool_push(ls_handle* h, const ls_long_pool_push_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_pool_push: null argument");
+    int rc;
+    if ((rc = pool_is_open(h, "ls_long_pool_push")) != LS_OK) return rc;
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_pool_push before ls_set_schedule");
+    const int S = h->pl_S;
+    if (!a->lengths || a->n_max < 0 || (a->n_max > 0 && !a->audio)) return fail(h, LS_EINVAL, "ls_long_pool_push: lengths, and audio with n_max > 0");
+    if (a->capacity < 0 || (a->capacity > 0 && !a->frames)) return fail(h, LS_EINVAL, "ls_long_pool_push: capacity without frames");
+    if (a->emo && h->cfg.n_prefix_tokens != 2) return fail(h, LS_EINVAL, "ls_long_pool_push: emo is a BEAT conditioning");
+    if (a->text_features && !a->sag) return fail(h, LS_EINVAL, "ls_long_pool_push: text_features without sag");
+    std::vector<int32_t> closing((size_t)S, 0), open((size_t)S, 0), win((size_t)S, 0), frames((size_t)S, 0);
+    for (int s = 0; s < S; ++s) {
+        if (a->lengths[s] < 0 || a->lengths[s] > a->n_max) return fail(h, LS_EINVAL, "ls_long_pool_push: lengths[%d] = %lld outside [0, %lld]", s, (long long)a->lengths[s], (long long)a->n_max);
+        open[(size_t)s] = h->pl_open[(size_t)s];
+        closing[(size_t)s] = a->closing && a->closing[s];
+        if (a->given && ((a->given[s] & ~3) || ((a->given[s] & 1) && !a->emo) || ((a->given[s] & 2) && !a->text_features) || (a->given[s] && !open[(size_t)s])))
+            return fail(h, LS_EINVAL, "ls_long_pool_push: given[%d] = %d names conditioning that was not passed, or a slot that is not open", s, a->given[s]);
+    }
+    int32_t n_rounds = 0, n_entries = 0;
+    const std::vector<int64_t> before(h->pl_samples.begin(), h->pl_samples.end()), ran(h->pl_windows.begin(), h->pl_windows.end());
+    if (ls_long_pool_plan(S, h->cfg.audio_len, before.data(), ran.data(), a->lengths, closing.data(), open.data(), win.data(), frames.data(), nullptr, 0, &n_rounds, &n_entries) != LS_OK)
+        return fail(h, LS_EINVAL, "ls_long_pool_push: samples for a slot that is not open, or closing a slot that was fed no sample");
+    std::vector<int32_t> rounds((size_t)n_entries);
+    if (ls_long_pool_plan(S, h->cfg.audio_len, before.data(), ran.data(), a->lengths, closing.data(), open.data(), win.data(), nullptr, rounds.data(), n_entries, &n_rounds, &n_entries) != LS_OK)
+        return fail(h, LS_EINVAL, "ls_long_pool_push: ls_long_pool_plan failed");
+    for (int s = 0; s < S; ++s) {
+        if (frames[(size_t)s] > a->capacity) return fail(h, LS_EINVAL, "ls_long_pool_push: slot %d runs %d windows = %d frames, capacity is %d", s, win[(size_t)s], frames[(size_t)s], a->capacity);
+        if (win[(size_t)s] > 0 && ran[(size_t)s] == 0) {        // the slot's first window: what it needs must be held by now
+            const int g = a->given ? a->given[s] : 0;
+            if (h->cfg.n_prefix_tokens == 2 && !h->pl_have_emo[(size_t)s] && !(g & 1)) return fail(h, LS_EINVAL, "ls_long_pool_push: the BEAT variant's first window needs emo ids (slot %d)", s);
+            if (a->sag && !h->pl_have_text[(size_t)s] && !(g & 2)) return fail(h, LS_EINVAL, "ls_long_pool_push: sag needs text_features for the first window (slot %d)", s);
+        }
+    }
+    ChainCall cc;
+    if ((rc = chain_args(h, "ls_long_pool_push", a, n_rounds > 0, cc)) != LS_OK) return rc;
+    if (n_rounds > 0 && !cc.tape) {
+        if ((a->sample_offset + (unsigned long long)S) >> 48) return fail(h, LS_EINVAL, "PHILOX: sample_offset + capacity must stay below 2^48 (the round index sits above)");
+        if (h->pl_rounds + n_rounds > (1 << 16)) return fail(h, LS_ESTATE, "ls_long_pool_push: PHILOX keys a round by its index since open, which stays below 2^16; open a new pool");
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    rc = pool_push_run(h, a, cc, win, rounds, n_rounds);
+    if (rc != LS_OK) {      // rings and hand-off stores may be half written: the pool is over, the handle is not
+        h->pl_state = ls_handle::kStreamFailed;
+        (void)hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+int ls_long_pool_info(const ls_handle* h, int32_t capacity, int64_t* samples_in, int64_t* windows_run, int64_t* frames_out, int32_t* open, int64_t misc[4]) {
+    if (!h || capacity < 0) return LS_EINVAL;
+    const int S = h->pl_state == ls_handle::kStreamNone ? 0 : h->pl_S;
+    for (int s = 0; s < capacity; ++s) {
+        const bool in = s < S;
+        if (samples_in) samples_in[s] = in ? h->pl_samples[(size_t)s] : 0;
+        if (windows_run) windows_run[s] = in ? h->pl_windows[(size_t)s] : 0;
+        if (frames_out) frames_out[s] = in ? h->pl_frames[(size_t)s] : 0;
+        if (open) open[s] = in ? h->pl_open[(size_t)s] : 0;        // of a pool that has ended: as it stood then (misc[3] tells)
+    }
+    if (misc) {
+        misc[0] = S;
+        misc[1] = S == 0 ? 0 : (int64_t)(h->pl_ring.bytes + h->pl_hand.bytes + h->pl_vid.bytes + h->pl_emo_id.bytes + h->pl_scale.bytes + h->pl_emotok.bytes +
+                                         h->pl_text.bytes + h->pl_ctext.bytes + h->pl_table.bytes + h->lg_clips.bytes + h->lg_featc.bytes);      // as allocated
+        misc[2] = S == 0 ? 0 : h->pl_rounds;
+        misc[3] = h->pl_state == ls_handle::kStreamOpen;
+    }
     return LS_OK;
 }
 

@@ -1,6 +1,7 @@
 // The plans of the chained-window engine (ls_chain_api.cpp): which clips run which window of a ragged call, which windows a timeline
-// edit runs, which windows a push of a stream runs.  Integer arithmetic on host arrays, no HIP in here: each is the single definition
-// for its entry and for Python (long_form.py), and tests/chain_plan_main.cpp runs them on their edges under the host sanitizers.
+// edit runs, which windows a push of a stream runs, which rounds a push of a session pool runs.  Integer arithmetic on host arrays, no
+// HIP in here: each is the single definition for its entry and for Python (long_form.py), and tests/chain_plan_main.cpp and
+// tests/pool_plan_main.cpp run them on their edges under the host sanitizers.
 #include <algorithm>
 #include <cstdint>
 #include <vector>
@@ -83,6 +84,42 @@ int ls_long_stream_plan(int64_t samples_before, int64_t samples_new, int32_t aud
     }
     *first_window = complete(samples_before);
     *n_windows = last - *first_window;
+    return LS_OK;
+}
+
+// The rounds one push of a session pool runs (ls_long_pool_push_args in ls_hip.h).  Each open slot is a stream of its own, and its
+// windows are ls_long_stream_plan's; round r holds the slots that run at least r + 1 windows, in ascending slot order.
+int ls_long_pool_plan(int32_t n_slots, int32_t audio_len, const int64_t* samples_in, const int64_t* windows_run, const int64_t* samples_new,
+                      const int32_t* closing, const int32_t* open, int32_t* n_windows, int32_t* frames, int32_t* round_slots,
+                      int32_t round_capacity, int32_t* n_rounds, int32_t* n_entries) {
+    if (n_slots < 1 || audio_len < 1 || !samples_in || !windows_run || !samples_new || !closing || !open || !n_windows || !n_rounds || !n_entries) return LS_EINVAL;
+    if (round_capacity < 0 || (round_capacity > 0 && !round_slots)) return LS_EINVAL;
+    const int64_t kMost = 1 << 20;              // windows of one slot in one call (ls_long_plan_drop's cap on a clip)
+    int64_t rounds = 0, entries = 0;
+    for (int s = 0; s < n_slots; ++s) {
+        if (samples_in[s] < 0 || windows_run[s] < 0 || samples_new[s] < 0) return LS_EINVAL;
+        int64_t first = 0, k = 0;
+        if (!open[s]) {
+            if (samples_new[s] > 0) return LS_EINVAL;           // samples for a slot that is not open
+        } else {
+            if (ls_long_stream_plan(samples_in[s], samples_new[s], audio_len, closing[s] ? 1 : 0, &first, &k) != LS_OK) return LS_EINVAL;
+            if (first != windows_run[s] || k > kMost) return LS_EINVAL;
+        }
+        n_windows[s] = (int32_t)k;
+        if (frames) frames[s] = (int32_t)(k == 0 ? 0 : 30 * k + (first == 0 ? 4 : 0));     // 34 for window 0, 30 for each later one
+        if (k > rounds) rounds = k;
+        entries += k;
+        if (entries > INT32_MAX) return LS_EINVAL;
+    }
+    if (round_slots) {
+        if (entries > round_capacity) return LS_EINVAL;
+        int64_t p = 0;
+        for (int64_t r = 0; r < rounds; ++r)
+            for (int s = 0; s < n_slots; ++s)
+                if (n_windows[s] > r) round_slots[p++] = s;
+    }
+    *n_rounds = (int32_t)rounds;
+    *n_entries = (int32_t)entries;
     return LS_OK;
 }
 

@@ -144,6 +144,18 @@ struct ls_handle {
     long long st_samples = 0, st_windows = 0, st_frames = 0;
     bool st_have_emo = false, st_have_text = false;
     DevBuf st_ring, st_emo_ids, st_text;
+    // session pool (ls_long_pool_open / _join / _push): pl_S slots, each a stream of its own.  Per slot on the device: the ring
+    // pl_ring [S][pl_R], the hand-off poses pl_hand [S][JF][n_pre] (seed poses until the slot's window 0 has run), the held conditioning
+    // pl_vid / pl_scale / pl_emotok [S][512] / pl_text [S][512]; per slot on the host: the counters, the scale and what is held.  A round
+    // gathers its active slots into rows [0, A) of lg_clips, feat_u, origin_x, vid, scale, emo_tok and pl_ctext (k_pool_gather) by
+    // pl_table [S][kPoolRow].  pl_state: as st_state.  pl_rounds: rounds run since open (the PHILOX window index).
+    int pl_state = kStreamNone;
+    int pl_S = 0, pl_R = 0;
+    long long pl_rounds = 0;
+    std::vector<long long> pl_samples, pl_windows, pl_frames;
+    std::vector<float> pl_scale_host;
+    std::vector<char> pl_open, pl_have_emo, pl_have_text;
+    DevBuf pl_ring, pl_hand, pl_vid, pl_scale, pl_emo_id, pl_emotok, pl_text, pl_ctext, pl_table;
     // Cached graphs of the step loop, by loop key (ls_sample.cpp: loop_key holds everything a captured loop bakes in besides device
     // addresses, the batch and its step plan included).  At most kGraphCacheMax entries: a plain call whose key is missing drops them
     // all and captures its own (one entry, as before the cache); a ragged long-form call keeps one per window batch that serves two or
@@ -218,7 +230,10 @@ inline int egress(ls_handle* h, void* dst, const void* src, size_t bytes, int on
 }
 
 // a call that replaces the handle's prepared conditioning ends a running stream (ls_long_stream_push then reports LS_ESTATE)
-inline void end_stream(ls_handle* h) { if (h->st_state == ls_handle::kStreamOpen) h->st_state = ls_handle::kStreamReplaced; }
+inline void end_stream(ls_handle* h) {        // ... and a running session pool
+    if (h->st_state == ls_handle::kStreamOpen) h->st_state = ls_handle::kStreamReplaced;
+    if (h->pl_state == ls_handle::kStreamOpen) h->pl_state = ls_handle::kStreamReplaced;
+}
 inline void end_chain(ls_handle* h) { h->lg_prepared = false; end_stream(h); }       // ls_prepare: a long-form call's conditioning goes too
 
 inline void free_graph(ls_handle* h) {        // every cached graph: whatever invalidates one invalidates all

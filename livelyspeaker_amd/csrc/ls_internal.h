@@ -340,6 +340,26 @@ hipError_t launch_long_gather_clips(const float* audio, const int* table, const 
 // One window of a stream (ls_long_stream_push): clips[b][i] = ring[b][(pos0 + i) % R] for i < n_valid, 0 behind.  ring [B][R] with
 // R % 4 == 0 and AL <= R, 0 <= pos0 < R, 0 <= n_valid <= AL; clips [B][AL].  Both 16-byte aligned.
 hipError_t launch_stream_gather(const float* ring, float* clips, int B, int AL, int R, int pos0, int n_valid, hipStream_t st);
+// ---- one round of a session pool (ls_long_pool_push; ls_chain.hip).  table [A][kPoolRow] on the device, one row per active slot in
+// ascending slot order: {slot, ring position of the window's first sample, valid samples of the window, first new frame f0, frame
+// offset of the slot in the call's output}.  launch_pool_gather: row r of the compact buffers <- slot table[r][0] of the per-slot
+// stores: the window's audio (k_stream_gather's arithmetic), the hand-off poses hand [S][JF][n_pre] as the prefix rows of feat_u and
+// prefix columns of origin_x, and the held conditioning (vid, scale; emo_tok_s / text_s [S][kD] into emo_tok / text, each pair nullable).
+// launch_pool_scatter: row r of prev (internal layout) -> frames [S][JF][T_total] of its slot at its frame offset, from frame f0 on,
+// and its last n_pre poses -> hand.  The launchers check the geometry; the table's entries are the caller's to check before upload.
+constexpr int kPoolRow = 8;
+struct PoolArgs {
+    const int* table;
+    const float* ring; float* clips;                                                 // gather: [S][R] -> [A][AL]
+    float* hand;                                                                     // [S][JF][n_pre]: read by the gather, written by the scatter
+    float* feat_u; float* origin_x;                                                  // gather
+    const int64_t* vid_s; const float* scale_s; const float* emo_tok_s; const float* text_s;      // gather: per-slot stores ...
+    int64_t* vid; float* scale; float* emo_tok; float* text;                         // ... and their compact rows
+    const float* prev; float* frames;                                                // scatter
+    int S, AL, R, JF, T, KPP, n_pre, T_total;
+};
+hipError_t launch_pool_gather(const PoolArgs& a, int A, hipStream_t st);
+hipError_t launch_pool_scatter(const PoolArgs& a, int A, hipStream_t st);
 
 // ---- torch's device normal stream (ls_torch_philox.hip; LS_NOISE_TORCH_DEVICE) ---------------------------------------------
 // One torch.randn / randn_like of n float32 elements per step: written to dst + r * dst_stride for step r of the launch.

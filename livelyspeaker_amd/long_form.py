@@ -26,6 +26,10 @@ for bit.
 ``open_stream`` is the online form of the same chain: audio arrives in chunks of any size, a window runs as soon as its last sample
 is there, and the frames of all pushes are bit for bit ``sample_long``'s for the concatenated audio (``ls_long_stream_open`` /
 ``ls_long_stream_push``; a per-clip audio ring and ``k_stream_gather``).
+
+``open_pool`` is a pool of such streams on one engine: clips join and leave slot by slot and are fed at their own rates, and a push
+runs the windows that are complete in rounds, each one sampling call on the slots that have one (``pool_plan``; ``ls_long_pool_*``,
+``k_pool_gather`` / ``k_pool_scatter``).
 """
 from __future__ import annotations
 
@@ -422,9 +426,231 @@ def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, samp
     ``sample_long`` or ``edit_long`` on the same model afterwards replaces its conditioning and ends the stream (the next push raises
     ``_lib.EngineError``).
 
-    Not built: clips joining or leaving a running stream, ``audio_lengths`` / ``drop_finished``, ``edit_long`` on a running stream,
-    PLMS, ``const_noise``, ``dump_steps``, sharded calls, a non-blocking ``push``."""
+    Clips that join or leave while others run, each fed at its own rate: ``open_pool``.
+
+    Not built: ``audio_lengths`` / ``drop_finished``, ``edit_long`` on a running stream, PLMS, ``const_noise``, ``dump_steps``,
+    sharded calls, a non-blocking ``push``."""
     return LongStream(diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag)
+
+
+def pool_plan(samples_in, windows_run, new, closing, open, cfg):
+    """What one ``LongPool.push`` runs, from host counts alone (no GPU): ``(rounds, frames)``.
+
+    Each of the S slots is a stream of its own: slot s, open, with ``samples_in[s]`` samples fed and ``windows_run[s]`` windows run so
+    far, receives ``new[s]`` samples, and runs the windows ``_lib.long_stream_plan(samples_in[s], new[s], audio_len, closing[s])`` names.
+    ``rounds[r]`` lists, ascending, the slots that still have a window to run after r earlier rounds of the call; slot s runs its window
+    ``windows_run[s] + r`` there, and the round is one sampling call at batch ``len(rounds[r])``.  ``frames`` (int32 [S]): 34 frames for
+    a slot's window 0, 30 for each later one.  ``ValueError``: samples for a slot that is not open, closing a slot that was never fed,
+    negative counts.  One definition for the engine and for this module (``ls_long_pool_plan``)."""
+    return _lib.long_pool_plan(samples_in, windows_run, new, closing, open, int(cfg.audio_len))
+
+
+class LongPool:
+    """A running ``open_pool`` session; see there.  ``slots``: per-slot host arrays ``samples_in``, ``windows_run``, ``frames_out``, ``open``."""
+
+    def __init__(self, diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag):
+        S = int(capacity)
+        if S < 1:
+            raise ValueError(f"capacity must be >= 1, got {capacity}")
+        rag = getattr(model, "model", None)
+        beat = getattr(rag, "n_prefix_tokens", 1) == 2
+        npre, J, F = (int(getattr(rag, k, 1)) for k in ("n_pre_seq", "njoints", "nfeats"))
+        # _check_args on a one-window stand-in at batch S: the slots' own conditioning arrives with the joins
+        _check_args(diffusion, model, th.empty(S, 1), th.empty(S, J, F, npre), th.zeros(S, dtype=th.long), th.ones(S),
+                    th.zeros(S, dtype=th.long) if beat else None, None, sampler, skip_timesteps, sag,
+                    None if sag is None else th.empty(S, 1, int(rag.latent_dim)), None, {})
+        _check_model(diffusion, rag)
+        self._diffusion, self._rag, self._sag, self._S = diffusion, rag, sag, S
+        self._kw = _loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised)
+        if diffusion.noise_source == "philox":          # one key per pool: row r of round q draws at sample_offset + r + (q << 48)
+            self._kw.update(diffusion._philox_key())
+        else:                                           # the largest round a push can run
+            _check_tape_bound(diffusion, "open_pool", diffusion.num_timesteps - int(skip_timesteps), (S, J, F, int(rag.nframes)), int(rag.latent_dim))
+        self._n_exec = diffusion.num_timesteps - int(skip_timesteps)
+        self._eng = None
+        self._closed = False
+        self._last_dev = th.device("cpu")
+        self._state = {"samples_in": np.zeros(S, np.int64), "windows_run": np.zeros(S, np.int64), "frames_out": np.zeros(S, np.int64),
+                       "open": np.zeros(S, bool)}
+        self._have_text = np.zeros(S, bool)
+
+    @property
+    def slots(self):
+        return {k: v.copy() for k, v in self._state.items()}
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self._closed = True        # leaving the block ends the session; the windows a close() would still run are not run
+        return False
+
+    def _engine(self):
+        if self._eng is None:
+            eng = _bind_engine(self._diffusion, self._rag)
+            if self._sag is not None and self._sag.engine().device != eng.device:
+                raise ValueError(f"the SAG decoder runs on cuda:{self._sag.engine().device}, the RAG model on cuda:{eng.device}")
+            eng.long_pool_open(self._S)
+            self._eng = eng
+        return self._eng
+
+    def _refresh(self):
+        info = self._eng.long_pool_info()
+        for k in self._state:
+            self._state[k] = np.array(info[k])
+
+    def join(self, seed_poses, vid_index, scale, emo=None, text_features=None, slot=None):
+        """Open a slot for a new clip: ``seed_poses`` [J, F, n_pre], its speaker id and guidance scale, ``emo`` (BEAT: required) and
+        ``text_features`` [512] (with ``sag=``; may also come with the push that runs the slot's first window).  Returns the slot: the
+        lowest free one unless ``slot`` names one.  Nothing is sampled and nothing is drawn."""
+        if self._closed:
+            raise RuntimeError("the pool is closed")
+        rag, S = self._rag, self._S
+        seed_poses, text_features = _as_tensors(seed_poses, text_features)
+        if _shape(seed_poses) != (rag.njoints, rag.nfeats, rag.n_pre_seq):
+            raise ValueError(f"seed_poses must be {[rag.njoints, rag.nfeats, rag.n_pre_seq]}, got {list(seed_poses.shape)}")
+        if rag.n_prefix_tokens == 2:
+            if emo is None:
+                raise ValueError("the BEAT model needs emo: one id for the clip that joins")
+        elif emo is not None:
+            raise ValueError("emo is a BEAT conditioning; the TED model takes none")
+        if text_features is not None:
+            if self._sag is None:
+                raise ValueError("text_features without sag: the SAG decoder turns them into every window's init_image")
+            if _shape(text_features) != (rag.latent_dim,):
+                raise ValueError(f"text_features must be [{rag.latent_dim}], got {list(text_features.shape)}")
+        free = [s for s in range(S) if not self._state["open"][s]]
+        if slot is None:
+            if not free:
+                raise ValueError(f"all {S} slots of the pool are occupied")
+            slot = free[0]
+        slot = int(slot)
+        if not 0 <= slot < S:
+            raise ValueError(f"slot {slot} outside [0, {S})")
+        if slot not in free:
+            raise ValueError(f"slot {slot} is occupied")
+        one = lambda v, dt: (v.detach().reshape(1).to(dt) if th.is_tensor(v) else th.tensor([v], dtype=dt))      # noqa: E731
+        eng = self._engine()
+        eng.long_pool_join(slot, seed_poses.float(), one(vid_index, th.long), one(scale, th.float32), None if emo is None else one(emo, th.long),
+                           None if text_features is None else text_features.float())
+        self._refresh()
+        self._have_text[slot] = text_features is not None
+        return slot
+
+    def _feed(self, audio, lengths, closing, emo, text_features, given):
+        if self._closed:
+            raise RuntimeError("the pool is closed")
+        rag, S, diffusion = self._rag, self._S, self._diffusion
+        audio, emo, text_features = _as_tensors(audio, emo, text_features)
+        if audio.ndim != 2 or int(audio.shape[0]) != S:
+            raise ValueError(f"audio must be [{S}, n_max], got {list(audio.shape)}")
+        n_max = int(audio.shape[1])
+        lens = _lib.host_lengths(lengths, S, 0, n_max, "lengths").astype(np.int64)
+        if emo is not None:
+            if rag.n_prefix_tokens != 2:
+                raise ValueError("emo is a BEAT conditioning; the TED model takes none")
+            if _shape(emo) != (S,):
+                raise ValueError(f"emo must be [{S}], got {list(emo.shape)}")
+        if text_features is not None:
+            if self._sag is None:
+                raise ValueError("text_features without sag: the SAG decoder turns them into every window's init_image")
+            if _shape(text_features) != (S, rag.latent_dim):
+                raise ValueError(f"text_features must be {[S, rag.latent_dim]}, got {list(text_features.shape)}")
+        st = self._state
+        if given is None:                               # what is passed holds for every open slot
+            given = st["open"].copy()
+        given = np.asarray(given.detach().cpu().numpy() if hasattr(given, "detach") else given).reshape(-1).astype(bool)
+        if given.shape != (S,) or (given & ~st["open"]).any():
+            raise ValueError(f"given must mark open slots only, one entry per slot: got {given.tolist()} for open {st['open'].tolist()}")
+        bits = given.astype(np.int32) * ((1 if emo is not None else 0) | (2 if text_features is not None else 0))
+        rounds, _ = pool_plan(st["samples_in"], st["windows_run"], lens, closing, st["open"], rag)
+        for s in {s for r in rounds for s in r}:
+            if self._sag is not None and st["windows_run"][s] == 0 and not self._have_text[s] and not bits[s] & 2:
+                raise ValueError(f"sag needs text_features [512] for slot {s}'s first window: pass them to join or to this push")
+        kw = dict(self._kw)
+        eng = self._engine()
+        if rounds and diffusion.noise_source != "philox":           # one public sampling call per round, at its batch, in round order
+            draws = [ref_draws.RefDraws("cpu").windows(diffusion, 1, self._n_exec, (len(r), rag.njoints, rag.nfeats, rag.nframes), eng.D) for r in rounds]
+            kw["x_init"] = th.cat([d[0][0] for d in draws], dim=0)
+            kw["eps_tape"], kw["noise_tape"] = (th.cat([d[i].reshape(-1) for d in draws]) for i in (1, 2))
+            diffusion.last_tape_segments = 1
+        if self._sag is not None:
+            kw["sag"] = self._sag.engine()
+        out_dev = self._last_dev = audio.device
+        frames, counts, ran = eng.long_pool_push(audio.float(), lens, closing=closing, emo=emo if bits.any() else None,
+                                                 text_features=None if text_features is None or not bits.any() else text_features.float(),
+                                                 given=bits if bits.any() else None, device_out=out_dev.type == "cuda", **kw)
+        assert ran == rounds
+        self._have_text |= (bits & 2).astype(bool)
+        self._refresh()
+        self._have_text &= self._state["open"]
+        return gd._as_tensor(frames, out_dev), counts
+
+    def push(self, audio, lengths, emo=None, text_features=None, given=None):
+        """Feed ``audio`` [S, n_max]: ``lengths[s]`` samples for slot s (0 for a slot that is free or has nothing new).  Returns
+        ``(frames [S, J, F, K], counts)``: slot s's new frames in ``frames[s, ..., :counts[s]]``, zero behind them; K = max(counts)."""
+        return self._feed(audio, lengths, np.zeros(self._S, np.int32), emo, text_features, given)
+
+    def _leave(self, which):
+        closing = np.zeros(self._S, np.int32)
+        closing[which] = 1
+        J, F = int(self._rag.njoints), int(self._rag.nfeats)
+        if not closing.any():
+            return th.zeros((self._S, J, F, 0), device=self._last_dev), np.zeros(self._S, np.int32)
+        return self._feed(th.zeros((self._S, 0), device=self._last_dev), np.zeros(self._S, np.int64), closing, None, None, None)
+
+    def leave(self, slot):
+        """End slot ``slot``'s clip: the frames ``[J, F, k]`` of the windows ``plan_windows(samples_in)`` still owes it, with silence
+        behind its last sample.  The slot is free afterwards."""
+        slot = int(slot)
+        if not 0 <= slot < self._S or not self._state["open"][slot]:
+            raise ValueError(f"slot {slot} is not open")
+        frames, counts = self._leave([slot])
+        return frames[slot, :, :, :int(counts[slot])]
+
+    def close(self):
+        """Leave every open slot and end the session: ``(frames [S, J, F, K], counts)`` as from ``push``."""
+        res = self._leave(np.nonzero(self._state["open"])[0])
+        self._closed = True
+        return res
+
+
+def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False, sag=None):
+    """``open_stream`` for clips that start and stop at different times and arrive at different rates: a session pool of ``capacity``
+    slots on ONE engine.
+
+        pool = open_pool(diffusion, model, capacity, sampler='ddim', ...)
+        slot = pool.join(seed_poses, vid_index, scale, emo=None, text_features=None, slot=None)     # the lowest free slot unless given
+        frames, counts = pool.push(audio, lengths, emo=None, text_features=None, given=None)        # [S, n_max], [S] -> [S, J, F, K], [S]
+        tail = pool.leave(slot)                                                                     # [J, F, k]; frees the slot
+        frames, counts = pool.close()                                                               # leaves every open slot
+
+    Every slot is a stream of its own: its frames, concatenated over the pushes and its ``leave``, are the chain ``open_stream`` defines
+    for its audio (34 frames for its window 0, 30 for each later one, window w as soon as ``32000 w + audio_len`` of ITS samples are
+    in).  What a push runs is ``pool_plan``: round r holds, ascending, the slots that still have a complete window after r earlier rounds
+    of the call, and is one sampling call at batch A = the slots in it -- its own kernel plan, the single-pass shortcut when the scales
+    of THOSE slots are all 1, its own captured loop (kept per batch size and replayed).  So S live speakers run at batch up to S, not as
+    S engines at batch 1.
+
+    ``emo`` (BEAT) is needed at ``join``; ``text_features`` (with ``sag=``) before a slot's first window, at ``join`` or with a push.
+    Both are HELD per slot; a push replaces them for the slots marked in ``given`` (bool [S]; default: every open slot).
+
+    Noise (``diffusion.noise_source``): ``'torch_cpu'`` draws, per round and in round order, what one public sampling call at batch A
+    draws (``RefDraws.windows(diffusion, 1, n_exec, (A, J, F, T), D)``), and the result is bit for bit that loop of public calls on the
+    active slots' windows (tests/test_gpu_long_pool.py); the one-window tape bound is checked at ``capacity``.  ``'philox'`` takes its
+    key here, once: row r of the pool's q-th round since it was opened draws at ``sample_offset + r + (q << 48)``.  That is
+    ``open_stream``'s key -- and its bits -- when the pool is used like a stream (all slots joined in order, fed alike); otherwise a
+    clip's draws depend on the push schedule and on which slots run beside it.  A pool runs at most 2^16 rounds under ``'philox'``.
+    ``'torch_device'`` is refused.
+
+    Device memory is allocated for ``capacity`` slots when the engine is bound (the first ``join``) and does not grow
+    (``Engine.long_pool_info()['device_bytes']``).  A ``ddim_sample_loop``, ``sample_long``, ``edit_long`` or ``open_stream`` push on the
+    same model replaces the engine's conditioning and ends the pool (the next call raises ``_lib.EngineError``).  ``close`` and
+    ``leave`` refuse a slot that was never fed a sample (``ValueError``), as ``LongStream.close`` does.
+
+    Not built: device-resident ``lengths``, Philox keyed by (slot, window), ``edit_long`` on a pool, PLMS, ``const_noise``,
+    ``dump_steps``, sharded calls, a non-blocking ``push``."""
+    return LongPool(diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag)
 
 
 def _edit_ranges(frames, B, n_frames):
