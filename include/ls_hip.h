@@ -433,15 +433,21 @@ int ls_long_edit(ls_handle* h, const ls_long_edit_args* a);
  * samples_new more, windows [*first_window, *first_window + *n_windows) run; closing != 0 adds the windows that cover the total with
  * silence behind its last sample (W = max(1, ceil((total - audio_len) / audio_stride) + 1) in all; the total must be >= 1).
  *
- * ls_long_stream_open runs the per-batch stages of ls_long_prepare once at batch B (guidance scales, speaker style, step plan, the
- * window-0 hand-off from seed_poses) and allocates a per-clip audio ring of audio_len + audio_stride samples.  It REPLACES the handle's
- * prepared conditioning, as ls_prepare does; in turn any call that replaces it (ls_prepare*, ls_long_prepare*, ls_commit_weights, a
- * second ls_long_stream_open) ends the stream: the next ls_long_stream_push returns LS_ESTATE and the handle stays usable.
+ * ls_long_stream_open opens a session of B slots (the session pool further down, at capacity B) and joins every slot from the arrays of
+ * ls_long_stream_cond; a stream is that pool with all slots fed, given and closed alike, planned for batch B alone under the form its
+ * own guidance scales choose.  It REPLACES the handle's prepared conditioning, as ls_prepare does; in turn any call that replaces it
+ * (ls_prepare*, ls_long_prepare*, ls_commit_weights, ls_long_pool_open, a second ls_long_stream_open) ends the stream: the next
+ * ls_long_stream_push returns LS_ESTATE and the handle stays usable.  A stream opened again at a batch whose buffers are in place
+ * replays the loop the last one captured from its first window on.
  *
- * Device memory does not grow with the stream: the ring, one gathered window [B, audio_len], one window's audio features [B, T, 256].
+ * Device memory does not grow with the stream: per clip a ring of audio_len + audio_stride samples, the hand-off poses and the held
+ * conditioning; one gathered window [B, audio_len], one window's audio features [B, T, 256].
  * A chunk larger than the ring's free space is consumed in pieces with the completed windows run in between.  One host wait per call
- * that ran a window; a call that ran none waits only for the copy of a HOST chunk out of the caller's buffer (a device chunk must stay
- * valid until the handle's stream has read it: order its reuse with ls_stream_order).
+ * that ran a window; a call that ran none waits only for the copy of a HOST chunk (or of emo / text_features) out of the caller's
+ * buffer (a device chunk must stay valid until the handle's stream has read it: order its reuse with ls_stream_order).  A row of
+ * `frames` is zero behind the frames the call wrote.
+ * PHILOX keys window w at w << 48 and the key must not repeat: a push that would run window 2^16 returns LS_ESTATE (about 36 hours of
+ * audio; open a new stream).
  * Clips that join and leave, each with its own lengths: the session pool further down (ls_long_pool_*).
  * Not built: edits of a running stream, PLMS, const_noise, dump_steps, a non-blocking push. */
 typedef struct ls_long_stream_cond {
@@ -471,7 +477,7 @@ typedef struct ls_long_stream_push_args {
     const float* eps_tape;      /* TAPE: [k, n_exec, 2, B, latent_dim]                                                */
     const float* noise_tape;    /* TAPE: [k, n_exec, B, J, F, T]                                                      */
     uint64_t seed;              /* PHILOX: the same key in every call of a stream                                     */
-    uint64_t sample_offset;     /* PHILOX: window w draws at sample_offset + b + (w << 48), as in ls_long_sample      */
+    uint64_t sample_offset;     /* PHILOX: window w < 2^16 draws at sample_offset + b + (w << 48), as in ls_long_sample */
     float* frames;              /* [B, J, F, capacity]: the new frames of this call's windows, in order (NULL with capacity 0) */
     int32_t* n_frames;          /* HOST, nullable: frames written per row                                             */
     int32_t* n_windows;         /* HOST, nullable: windows run                                                        */
@@ -480,8 +486,10 @@ int ls_long_stream_plan(int64_t samples_before, int64_t samples_new, int32_t aud
                         int64_t* n_windows);
 int ls_long_stream_open(ls_handle* h, const ls_long_stream_cond* c);
 int ls_long_stream_push(ls_handle* h, const ls_long_stream_push_args* a);
-/* out = {samples fed, windows run, frames written, device bytes the stream holds (ring + gathered window + one-window features)} of the
- * handle's current or last stream (zeros before the first ls_long_stream_open) */
+/* out = {samples fed, windows run, frames written, device bytes the stream holds} of the handle's current or last stream (zeros before
+ * the first ls_long_stream_open, and once a pool has been opened since).  The bytes are the session's count, as ls_long_pool_info's
+ * misc[1] at capacity B: rings, hand-off stores, held conditioning (speaker ids, scales, emotion ids and tokens, text features and
+ * their compact rows), the round table, the gathered windows and one window's features, as allocated */
 int ls_long_stream_info(const ls_handle* h, int64_t out[4]);
 
 /* ---- Session pool: streaming long-form synthesis with clips that join and leave.  A pool holds `capacity` SLOTS; each open slot is
@@ -502,7 +510,7 @@ int ls_long_stream_info(const ls_handle* h, int64_t out[4]);
  * ls_long_pool_open allocates everything for `capacity` slots -- rings, hand-off stores, held conditioning, one gathered window, one
  * window's features, the loop's buffers and the workspaces of the step plans of every batch 1..capacity -- so that no buffer a
  * captured loop holds by address moves before the pool ends.  It REPLACES the handle's prepared conditioning and ends a running
- * stream; any call that replaces the conditioning ends the pool in turn (the next push or join returns LS_ESTATE, the handle stays
+ * stream (the two are one kind of session, and a handle holds one); any call that replaces the conditioning ends the pool in turn (the next push or join returns LS_ESTATE, the handle stays
  * usable).  ls_long_pool_join fills a free slot (LS_ESTATE on an occupied one) and draws nothing; a slot whose closing flag is set
  * in a push is free again after the windows it was owed.  A failure inside a push marks the pool failed (LS_ESTATE from then on).
  *

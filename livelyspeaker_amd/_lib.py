@@ -916,6 +916,13 @@ class Engine(_Handle):
         if inpaint_noise is not None:
             a.inpaint_noise = m.f32(inpaint_noise, (lead, n_exec) + x)
 
+    def _chain_frames(self, a, m, rows, cap):
+        """The output of a session's push, ``frames`` [rows, J, F, cap]: the call gets its address unless it has no column."""
+        frames, pframes = m.out((rows, self.J, self.F, cap))
+        if cap:
+            a.frames = pframes
+        return frames
+
     def long_prepare(self, audio, seed_poses, vid_indices, scale, emo=None, n_windows=1, encoder_chunk=None, audio_lengths=None):
         """Once-per-call stage of a long-form call (ls_long_prepare): ``audio`` [B, L] is encoded once for all ``n_windows`` windows
         (zero-padded at the end when short), ``seed_poses`` [B, J, F, n_pre_seq] condition window 0, ``emo`` [W, B] (BEAT).  Replaces
@@ -1020,8 +1027,8 @@ class Engine(_Handle):
 
     # ---- streaming long-form synthesis -----------------------------------------------------------
     def long_stream_open(self, seed_poses, vid_indices, scale):
-        """Open a stream at batch B (ls_long_stream_open): the per-batch stages of ``long_prepare`` and the audio ring.  Replaces whatever
-        ``prepare`` / ``long_prepare`` left resident; any of those ends the stream in turn."""
+        """Open a stream at batch B (ls_long_stream_open): a session of B slots, every slot joined here.  Replaces whatever ``prepare`` /
+        ``long_prepare`` / ``long_pool_open`` left resident; any of those ends the stream in turn."""
         B = int(seed_poses.shape[0])
         m = _Marshal(self.device, seed_poses, vid_indices, scale, stream=self._stream)
         c = LsLongStreamCond(B, int(m.on_device), m.f32(seed_poses, (B, self.J, self.F, int(self.cfg.n_pre_seq))), m.i64(vid_indices, (B,)),
@@ -1055,9 +1062,7 @@ class Engine(_Handle):
             a.sag = sag.h
             a.text_features = m.f32(text_features, (B, D))
         self._chain_noise(a, m, k or None, n_exec, x_init, eps_tape, noise_tape, philox_seed, sample_offset)
-        frames, pframes = m.out((B, self.J, self.F, cap))
-        if cap:
-            a.frames = pframes
+        frames = self._chain_frames(a, m, B, cap)
         n_frames, n_windows = C.c_int32(-1), C.c_int32(-1)
         a.n_frames, a.n_windows = C.pointer(n_frames), C.pointer(n_windows)
         m.ready()
@@ -1068,7 +1073,8 @@ class Engine(_Handle):
         return frames, k
 
     def long_stream_info(self) -> dict:
-        """ls_long_stream_info of the current (or last) stream: samples_in, windows_run, frames_out, device_bytes."""
+        """ls_long_stream_info of the current (or last) stream: samples_in, windows_run, frames_out, and device_bytes -- what the
+        session holds for its B slots, as ``long_pool_info`` counts it."""
         out = (C.c_int64 * 4)()
         self._check(self.lib.ls_long_stream_info(self.h, out), "ls_long_stream_info")
         return {"samples_in": int(out[0]), "windows_run": int(out[1]), "frames_out": int(out[2]), "device_bytes": int(out[3])}
@@ -1124,9 +1130,7 @@ class Engine(_Handle):
             a.sag = sag.h
         a.text_features = m.f32(text_features, (S, D))
         self._chain_noise(a, m, rows or None, n_exec, x_init, eps_tape, noise_tape, philox_seed, sample_offset, packed=True)
-        frames, pframes = m.out((S, self.J, self.F, cap))
-        if cap:
-            a.frames = pframes
+        frames = self._chain_frames(a, m, S, cap)
         counts, n_rounds = np.full(S, -1, np.int32), C.c_int32(-1)
         a.n_frames, a.n_rounds = counts.ctypes.data_as(c_i32p), C.pointer(n_rounds)
         m.ready()

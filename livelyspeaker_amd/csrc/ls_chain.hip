@@ -13,10 +13,9 @@
 // k_edit_gather / k_edit_scatter (further down) are the same cut and stitch for a timeline EDIT (ls_long_edit): a window's frames leave
 // the timeline as the loop's inpainting inputs and its editable elements return.  Algorithmic bytes per clip (fp32): gather 15.7 KB TED,
 // 163 KB BEAT (with the init plane); scatter at most 11.0 KB TED, 115 KB BEAT (with the raw window); the terms are spelled out at the kernels.
-// A STREAM (ls_long_stream_push) runs k_chain_window behind every window instead of ahead of it -- the same launch flushes the window into
-// the push's output and leaves the next window's prefix poses in feat_u / origin_x until the push that runs it -- and k_stream_gather
-// cuts a window's audio out of the stream's circular ring.  A SESSION POOL (ls_long_pool_push) keeps all of that per slot: k_pool_gather
-// and k_pool_scatter (at the end) move one round's active slots into and out of the compact rows a sampling call at that batch reads.
+// A streaming SESSION (ls_long_pool_push; ls_long_stream_push: the pool whose slots move together) keeps the hand-off per slot:
+// k_pool_gather and k_pool_scatter (at the end) move one round's active slots -- a window of audio out of each slot's circular ring,
+// its hand-off poses, its held conditioning -- into and out of the compact rows a sampling call at that batch reads.
 #include "ls_internal.h"
 
 namespace ls {
@@ -198,13 +197,13 @@ hipError_t launch_long_gather_clips(const float* audio, const int* table, const 
     return hipGetLastError();
 }
 
-// The WavEncoder input of one window of a STREAM (ls_long_stream_push): clip b's audio_len samples from its circular ring [R] (sample s
-// of the stream sits at s % R; the window's first sample at pos0 = (w * stride) % R), zero from the stream's last sample on (n_valid
+// The WavEncoder input of one window of a streaming SESSION's slot: its audio_len samples from the slot's circular ring [R] (sample s
+// of the slot sits at s % R; the window's first sample at pos0 = (w * stride) % R), zero from the slot's last sample on (n_valid
 // samples of the window exist; fewer than AL only in the closing call).  AL <= R, so a window wraps at most once.  The destination
 // layout, the float4 store per thread and the scalar head and tail are k_long_gather_clips'; the load is a float4 when all four samples
-// exist, the ring position is a multiple of four (R is one, and a clip's ring starts 16-byte aligned) and the group does not cross the
-// ring's end, four guarded scalar loads otherwise.  Bytes: reads at most and writes exactly B * AL floats.
-// the body shared with k_pool_gather: workgroup x of the row whose source ring is src and whose destination is clips row `row` at dst
+// exist, the ring position is a multiple of four (R is one, and a slot's ring starts 16-byte aligned) and the group does not cross the
+// ring's end, four guarded scalar loads otherwise.  Bytes: reads at most and writes exactly AL floats per row.
+// Workgroup x of the row whose source ring is src and whose destination is clips row `row` at dst (k_pool_gather)
 __device__ __forceinline__ void gather_ring_window(const float* __restrict__ src, float* __restrict__ dst, int row, int AL, int R, int pos0, int n_valid) {
     const int to_aligned = (int)((4 - ((size_t)row * AL & 3)) & 3), head = to_aligned < AL ? to_aligned : AL;
     const int nvec = (AL - head) / 4;
@@ -228,23 +227,10 @@ __device__ __forceinline__ void gather_ring_window(const float* __restrict__ src
     *reinterpret_cast<float4*>(dst + i) = v;
 }
 
-__global__ __launch_bounds__(256) void k_stream_gather(const float* __restrict__ ring, float* __restrict__ clips, int AL, int R, int pos0, int n_valid) {
-    const int b = blockIdx.y;
-    gather_ring_window(ring + (size_t)b * R, clips + (size_t)b * AL, b, AL, R, pos0, n_valid);
-}
-
-hipError_t launch_stream_gather(const float* ring, float* clips, int B, int AL, int R, int pos0, int n_valid, hipStream_t st) {
-    if (B < 1 || B > 65535 || AL < 1 || R < AL || (R & 3) || pos0 < 0 || pos0 >= R || n_valid < 0 || n_valid > AL) return hipErrorInvalidValue;
-    if (((size_t)clips & 15) || ((size_t)ring & 15)) return hipErrorInvalidValue;
-    const int gx = (AL / 4 + 255) / 256;             // >= the float4 groups of a clip, whatever its head
-    hipLaunchKernelGGL(k_stream_gather, dim3(gx > 0 ? gx : 1, B), dim3(256), 0, st, ring, clips, AL, R, pos0, n_valid);
-    return hipGetLastError();
-}
-
-// One round of a SESSION POOL (ls_long_pool_push; PoolArgs in ls_internal.h): the A active slots of the round, in ascending slot order,
-// become the rows 0 .. A-1 of every buffer a sampling call at batch A reads.  Workgroup (x, r) reads its table row once (a uniform
-// load; no other load depends on a loaded value) and, for x below the audio workgroups, is k_stream_gather on slot table[r][0]'s ring
-// at that slot's own position and valid count.  The one workgroup behind them (x == gridDim.x - 1) moves the slot's conditioning: its
+// One round of a streaming SESSION (ls_long_pool_push, ls_long_stream_push; PoolArgs in ls_internal.h): the A active slots of the round,
+// in ascending slot order, become the rows 0 .. A-1 of every buffer a sampling call at batch A reads.  Workgroup (x, r) reads its table
+// row once (a uniform load; no other load depends on a loaded value) and, for x below the audio workgroups, is gather_ring_window on
+// slot table[r][0]'s ring at that slot's own position and valid count.  The one workgroup behind them (x == gridDim.x - 1) moves the slot's conditioning: its
 // hand-off poses into the prefix rows of feat_u ([poses | 1 | 0 pad]) and the prefix columns of origin_x -- what k_chain_window
 // writes for a next window; everything outside the prefix is zero from ls_long_pool_open on -- and its speaker id, guidance scale,
 // emotion token and text features into compact row r (512-float rows as float4: every row starts 2 KB-aligned).

@@ -3,12 +3,15 @@
 // (run_window_loop, ls_sample.cpp), handed the last poses of the window before it.  There is one once-per-call stage (check_cond ->
 // start_prepare -> ingest_cond -> size_batch_buffers -> finish_prepare) and one window runner (chain_args -> chain_begin -> run_window
 // per window -> chain_finish); the entries hold what differs: where a window's audio features come from (all windows encoded ahead,
-// packed for clips of different lengths, one window at a time from a stream's ring, or one round at a time from the rings of a session
-// pool's active slots) and what stands around a window (k_chain_window ahead of it, k_chain_window behind it, k_edit_gather /
-// k_edit_scatter, or k_pool_gather / k_pool_scatter).  The host-only plans are ls_chain_plan.cpp.
+// packed for clips of different lengths, or one round at a time from the rings of a streaming session's active slots) and what stands
+// around a window (k_chain_window ahead of it, k_edit_gather / k_edit_scatter, or k_pool_gather / k_pool_scatter).  There is one
+// streaming session (session_open -> session_push -> session_push_run): a pool of slots that join and leave, and a stream, which is
+// the pool whose slots were all joined at the open and are fed, given and closed alike.  The host-only plans are ls_chain_plan.cpp.
 #include "ls_handle.h"
 
+#include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <initializer_list>
 #include <vector>
 
@@ -17,7 +20,7 @@ using namespace ls;
 namespace {
 
 // ---- the once-per-call stage ----------------------------------------------------------------------------------------------------
-// the refusals every conditioning shares; n_windows: null for a stream, which has none
+// the refusals every conditioning shares; n_windows: null for a streaming session, which has none
 int check_cond(ls_handle* h, const char* entry, int batch, const int32_t* n_windows, bool audio_ok, bool pointers_ok, bool emo_ok) {
     if (!h->committed) return fail(h, LS_ESTATE, "%s before ls_commit_weights", entry);
     if (!h->fused) return fail(h, LS_EUNSUPPORTED, "long-form synthesis chains the reference's %d-frame windows", kT);
@@ -67,13 +70,19 @@ int size_batch_buffers(ls_handle* h, int B) {
     return LS_OK;
 }
 
-// wait, prepare_ms, and the prepared batch.  Every buffer a captured loop reads moves only when the batch changes (as in ls_prepare):
-// the graphs are dropped then and kept otherwise -- their keys hold the batch and the plan, so the next call finds them
-int finish_prepare(ls_handle* h, int B) {
+// the stage's wait and prepare_ms
+int finish_clock(ls_handle* h) {
     HIPCHK(h, hipEventRecord(h->ev[5], h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipEventElapsedTime(&h->timing.prepare_ms, h->ev[4], h->ev[5]));
     h->prepare_pending = false;
+    return LS_OK;
+}
+// ... and the prepared batch of ls_long_prepare*.  Every buffer a captured loop reads moves only when the batch changes (as in
+// ls_prepare): the graphs are dropped then and kept otherwise -- their keys hold the batch and the plan, so the next call finds them
+int finish_prepare(ls_handle* h, int B) {
+    const int rc = finish_clock(h);
+    if (rc != LS_OK) return rc;
     if (h->B != B) free_graph(h);
     h->B = B;
     return LS_OK;
@@ -99,17 +108,17 @@ struct Window {
     long long w = 0;                    // index in the chain: PHILOX draws at sample_offset + b + (w << 48)
     int Bw = 0;                         // clips that run it: slots [0, Bw) of every per-clip buffer
     const float* featc = nullptr;       // its audio features [Bw][T][256]
-    const float* emo_tok = nullptr;     // BEAT: its emotion tokens [Bw][512]; null: the ones held in emo_tok (a stream)
+    const float* emo_tok = nullptr;     // BEAT: its emotion tokens [Bw][512]; null: the ones in emo_tok (a session's round: k_pool_gather wrote them)
     const float* text = nullptr;        // SAG: its text features [Bw][512]
     const float *x_init = nullptr, *eps_tape = nullptr, *noise_tape = nullptr, *inpaint_noise = nullptr;      // TAPE: its draws
-    bool host_tapes = false;            // ... in host memory: uploaded here, one window at a time (a stream: the staging does not grow with the call)
+    bool host_tapes = false;            // ... in host memory: uploaded here, one window at a time (a session's round: the staging does not grow with the call)
     bool resident_inpaint = false;      // a timeline edit: the inpainting planes are on the device (k_edit_gather)
     CachePolicy policy = kReplace;
     bool first = false;                 // the first window of the call
 };
 
 // The call prologue, first half -- nothing here touches the device: the refusals every entry shares, and wa.  runs: the call runs at
-// least one window (a push of a stream may run none, and then needs neither tapes nor counters)
+// least one window (a push of a session may run none, and then needs neither tapes nor counters)
 template <class Args>
 int chain_args(ls_handle* h, const char* entry, const Args* a, bool runs, ChainCall& cc) {
     if (a->sampler != LS_SAMPLER_DDPM && a->sampler != LS_SAMPLER_DDIM) return fail(h, LS_EUNSUPPORTED, "%s: DDPM and DDIM loops only", entry);
@@ -207,141 +216,151 @@ int chain_finish(ls_handle* h, const ChainCall& cc, std::initializer_list<Egress
     return LS_OK;
 }
 
-// copy `take` samples of every clip from chunk column c0 (rows n apart) into the ring behind the stream's last sample: one strided copy,
-// two where the ring wraps
-int ring_write(ls_handle* h, const float* chunk, long long n, long long c0, int take, int od) {
-    const int B = h->B, R = h->st_R, p = (int)(h->st_samples % R), seg1 = take < R - p ? take : R - p;
-    const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    HIPCHK(h, hipMemcpy2DAsync(h->st_ring.f() + p, (size_t)R * sizeof(float), chunk + c0, (size_t)n * sizeof(float), (size_t)seg1 * sizeof(float), B, kind, h->stream));
-    if (take > seg1)
-        HIPCHK(h, hipMemcpy2DAsync(h->st_ring.p, (size_t)R * sizeof(float), chunk + c0 + seg1, (size_t)n * sizeof(float), (size_t)(take - seg1) * sizeof(float), B, kind, h->stream));
-    return LS_OK;
+// ---- streaming sessions ---------------------------------------------------------------------------------------------------------
+// A session pool, and a stream: the pool whose slots were all joined at the open and are fed and closed together (pl_lockstep).
+int session_is_open(ls_handle* h, const char* entry, bool stream) {
+    const char* what = stream ? "stream" : "pool";
+    if (h->pl_state == ls_handle::kStreamNone) return fail(h, LS_ESTATE, "%s before ls_long_%s_open", entry, what);
+    if ((h->pl_lockstep != ls_handle::kPool) == stream) {       // otherwise: a session of the other kind has replaced it
+        if (h->pl_lockstep == ls_handle::kLockstepClosed) return fail(h, LS_ESTATE, "%s: the stream is closed", entry);
+        if (h->pl_state == ls_handle::kStreamOpen) return LS_OK;
+        if (h->pl_state == ls_handle::kStreamFailed) return fail(h, LS_ESTATE, "%s: an earlier push of this %s failed; open a new one", entry, what);
+    }
+    return fail(h, LS_ESTATE, "%s: the %s was ended by a call that replaced the handle's prepared conditioning (ls_prepare, ls_long_prepare, "
+                              "ls_commit_weights, ls_long_stream_open or ls_long_pool_open); open a new one", entry, what);
 }
 
-// Everything of a push behind its argument checks: feed the ring, run the windows that complete.  Per window the encoder stands in
-// front (k_stream_gather -> WavEncoder -> k_build_feats into the one-window feature buffer) and the hand-off behind: k_chain_window
-// flushes the window into the call's output AND writes the next window's prefix poses into feat_u / origin_x, where they wait for the
-// push that runs it (nothing but a call that ends the stream writes either).
-int stream_push_run(ls_handle* h, const ls_long_stream_push_args* a, ChainCall& cc, long long k) {
-    const int B = h->B, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, AL = h->cfg.audio_len, R = h->st_R, od = a->on_device;
-    const int cap = a->capacity;
-    hipStream_t st = h->stream;
-    int rc;
-    const size_t per_x = (size_t)B * JF * T, per_e = (size_t)cc.n_exec * 2 * B * kD, per_n = (size_t)cc.n_exec * per_x;
-    // the held conditioning: what this call passes holds for every window started from here on
-    if (a->emo) {
-        if ((rc = ingest(h, h->st_emo_ids, a->emo, (size_t)B * sizeof(int64_t), od)) != LS_OK) return rc;
-        HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->st_emo_ids.p), h->emo_tok.f(), B, kD, h->cfg.n_emotions, st));
-        h->st_have_emo = true;
-    }
-    if (a->text_features) {
-        if ((rc = ingest(h, h->st_text, a->text_features, (size_t)B * kD * sizeof(float), od)) != LS_OK) return rc;
-        h->st_have_text = true;
-    }
-    float* out = a->frames;
-    if (k > 0) {
-        if ((rc = chain_begin(h, cc, a->sag)) != LS_OK) return rc;
-        if (!od) { HIPCHK(h, h->lg_timeline.ensure((size_t)B * JF * cap * sizeof(float))); out = h->lg_timeline.f(); }
-    }
-    ChainArgs ca{};
-    ca.feat_u = h->feat_u.f(); ca.origin_x = h->origin_x.f(); ca.timeline = out;
-    ca.JF = JF; ca.T = T; ca.KPP = h->KPP; ca.n_pre = npre; ca.T_total = cap; ca.n_next = B;
-    int t_off = 0;
-    long long ran = 0, fed = 0;
-    const long long n = a->n_samples;
-    while (fed < n || ran < k) {
-        // as much of the chunk as the ring has room for: the samples below the next window's first one are dead
-        const long long room = R - (h->st_samples - (long long)LS_LONG_AUDIO_STRIDE * h->st_windows);
-        const int take = (int)(n - fed < room ? n - fed : room);
-        if (take > 0) {
-            if ((rc = ring_write(h, a->audio, n, fed, take, od)) != LS_OK) return rc;
-            fed += take; h->st_samples += take;
-        }
-        int64_t w0 = 0, kw = 0;         // the windows complete now; in the closing call, once the chunk is in, the padded ones too
-        if (ls_long_stream_plan(h->st_samples, 0, AL, a->closing && fed == n, &w0, &kw) != LS_OK) return fail(h, LS_EINVAL, "ls_long_stream_push: closing a stream that was fed no sample");
-        const long long upto = w0 + kw;
-        if (take == 0 && upto <= h->st_windows) return fail(h, LS_ESTATE, "ls_long_stream_push: no room in the ring and no window to run");
-        for (long long w = h->st_windows; w < upto; ++w, ++ran) {
-            if (ran >= k) return fail(h, LS_ESTATE, "ls_long_stream_push: more windows complete than the call was planned for");
-            const long long lo = w * LS_LONG_AUDIO_STRIDE, have = h->st_samples - lo;
-            HIPCHK(h, launch_stream_gather(h->st_ring.f(), h->lg_clips.f(), B, AL, R, (int)(lo % R), (int)(have < AL ? (have < 0 ? 0 : have) : AL), st));
-            if ((rc = run_wav_encoder(h, h->lg_clips.f(), B)) != LS_OK) return rc;
-            HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f(), B, JF, h->KPP, 0, st, T));
-            Window win;
-            win.w = w; win.Bw = B; win.featc = h->lg_featc.f(); win.text = h->st_text.f(); win.first = ran == 0;
-            if (cc.tape) {      // this window's draws; host ones are uploaded by the body
-                win.x_init = a->x_init + (size_t)ran * per_x; win.eps_tape = a->eps_tape + (size_t)ran * per_e; win.noise_tape = a->noise_tape + (size_t)ran * per_n;
-                win.host_tapes = !od;
-            }
-            if ((rc = run_window(h, cc, win)) != LS_OK) return rc;
-            // hand-off: the window leaves through the call's output, the next window's prefix poses enter feat_u / origin_x
-            ca.prev = x_plane(h, cc.n_exec);
-            ca.f0 = w == 0 ? 0 : npre; ca.t_off = t_off;
-            HIPCHK(h, launch_chain_window(ca, B, st));
-            t_off += T - ca.f0;
-            h->st_windows = w + 1;
-        }
-    }
-    h->st_frames += t_off;
-    if (a->n_frames) *a->n_frames = t_off;
-    if (a->n_windows) *a->n_windows = (int32_t)ran;
-    if (a->closing) h->st_state = ls_handle::kStreamClosed;
-    if (ran == 0) {         // no sampling work: a host chunk is the caller's again once its copies are done, a device chunk is read in stream order
-        if (!od && n > 0) { HIPCHK(h, hipEventRecord(h->ev[6], st)); HIPCHK(h, hipEventSynchronize(h->ev[6])); }
-        return LS_OK;
-    }
-    return chain_finish(h, cc, {{od ? nullptr : a->frames, out, (size_t)B * JF * cap * sizeof(float)}});
+// what a session holds on the device, as allocated: rings, hand-off stores, held conditioning, round table, gathered windows, features
+int64_t session_bytes(const ls_handle* h) {
+    return (int64_t)(h->pl_ring.bytes + h->pl_hand.bytes + h->pl_vid.bytes + h->pl_emo_id.bytes + h->pl_scale.bytes + h->pl_emotok.bytes +
+                     h->pl_text.bytes + h->pl_ctext.bytes + h->pl_table.bytes + h->lg_clips.bytes + h->lg_featc.bytes);
 }
 
-// ---- the session pool -----------------------------------------------------------------------------------------------------------
-int pool_is_open(ls_handle* h, const char* entry) {
-    switch (h->pl_state) {
-    case ls_handle::kStreamOpen: return LS_OK;
-    case ls_handle::kStreamNone: return fail(h, LS_ESTATE, "%s before ls_long_pool_open", entry);
-    case ls_handle::kStreamFailed: return fail(h, LS_ESTATE, "%s: an earlier push of this pool failed; open a new one", entry);
-    default: return fail(h, LS_ESTATE, "%s: the pool was ended by a call that replaced the handle's prepared conditioning "
-                                       "(ls_prepare, ls_long_prepare, ls_long_stream_open, ls_commit_weights or another ls_long_pool_open); open a new one", entry);
-    }
-}
-
-// one element or row of a slot's held conditioning from the caller (host or device) into its per-slot store
+// the held conditioning of the n slots from s on, from the caller (host or device) into the per-slot stores
 int pool_hold(ls_handle* h, void* dst, const void* src, size_t bytes, int od) {
     HIPCHK(h, hipMemcpyAsync(dst, src, bytes, od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     return LS_OK;
 }
-int pool_hold_emo(ls_handle* h, int s, const int64_t* id, int od) {
+int pool_hold_emo(ls_handle* h, int s, int n, const int64_t* ids, int od) {
     int64_t* at = static_cast<int64_t*>(h->pl_emo_id.p) + s;
-    const int rc = pool_hold(h, at, id, sizeof(int64_t), od);
+    const int rc = pool_hold(h, at, ids, (size_t)n * sizeof(int64_t), od);
     if (rc != LS_OK) return rc;
-    HIPCHK(h, launch_gather_rows(h->emo_emb.f(), at, h->pl_emotok.f() + (size_t)s * kD, 1, kD, h->cfg.n_emotions, h->stream));
-    h->pl_have_emo[(size_t)s] = 1;
+    HIPCHK(h, launch_gather_rows(h->emo_emb.f(), at, h->pl_emotok.f() + (size_t)s * kD, n, kD, h->cfg.n_emotions, h->stream));
+    for (int i = s; i < s + n; ++i) h->pl_have_emo[(size_t)i] = 1;
     return LS_OK;
 }
-int pool_hold_text(ls_handle* h, int s, const float* row, int od) {
-    const int rc = pool_hold(h, h->pl_text.f() + (size_t)s * kD, row, kD * sizeof(float), od);
-    h->pl_have_text[(size_t)s] = 1;
-    return rc;
+int pool_hold_text(ls_handle* h, int s, int n, const float* rows, int od) {
+    for (int i = s; i < s + n; ++i) h->pl_have_text[(size_t)i] = 1;
+    return pool_hold(h, h->pl_text.f() + (size_t)s * kD, rows, (size_t)n * kD * sizeof(float), od);
 }
 
-// Everything of a pool's push behind its argument checks.  win[s]: the windows slot s runs (ls_long_pool_plan), rounds: the plan's
-// slots round after round.  Ahead of every round each slot takes as much of its chunk as its ring has room for -- a slot's next
-// window always fits behind the samples its earlier windows made dead -- so the rounds are the plan's whatever the chunk sizes.  Per
-// round: k_pool_gather -> WavEncoder -> k_build_feats at batch A, the per-batch stages at A, the window body, k_pool_scatter.  Nothing
-// is allocated from the first launch on.
-int pool_push_run(ls_handle* h, const ls_long_pool_push_args* a, ChainCall& cc, const std::vector<int32_t>& win, const std::vector<int32_t>& rounds, int n_rounds) {
+// The buffers a captured loop holds by address among those a session's open sizes (the workspaces of the step plans and whatever a
+// push sizes go through ensure_pinned).  THE GRAPH RULE of a session's open: the cached graphs are dropped exactly when one of these
+// moved -- a graph's key holds the batch and the plan, its nodes hold these addresses, so a stream opened where nothing moved (again
+// at the same batch, or at a smaller one) replays the loop the last one captured from its first window on.  A pool's open drops them
+// whatever moved, for a reason of its own (session_open).
+std::vector<const void*> loop_held(const ls_handle* h) {
+    return {h->static_c.p, h->static_u.p, h->emo_tok.p, h->z_mu.p, h->z_std.p, h->scale.p, h->xa.p, h->xb.p, h->xtmp.p, h->xio.p,
+            h->lg_init.p, h->eps_tape.p, h->noise_tape.p};
+}
+
+// Opening a session of S slots.  Every buffer a round touches is sized for S rows here -- the per-slot stores, the compact batch
+// buffers, the WavEncoder's activations (one run on silence), the style buffers (one run on speaker 0), the loop's planes and tape
+// buffers, the SAG plane and mask, and the workspaces of the step plans -- so that a push allocates only what depends on its own
+// arguments (a host caller's tape staging and output; the tape buffers again when the schedule grew after the open), ahead of its
+// first launch, with nothing in flight.  c: a stream (ls_long_stream_cond) -- its B clips join the B slots here, in batched copies, and
+// only batch B is planned, under the form its own scales choose; null: a pool -- the slots are free, and every batch 1..S is planned
+// under both forms of a step.
+int session_open(ls_handle* h, int S, const ls_long_stream_cond* c) {
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, npre = h->cfg.n_pre_seq;
+    const int R = (AL + LS_LONG_AUDIO_STRIDE + 3) / 4 * 4;       // a window and the stride to the next; whole float4 groups per slot
+    const size_t nxS = (size_t)S * JF * T * sizeof(float), rowS = (size_t)S * kD * sizeof(float);
+    hipStream_t st = h->stream;
+    int rc;
+    end_stream(h);
+    h->pl_state = ls_handle::kStreamNone;       // a session that was open has ended; this one opens when everything below has succeeded
+    if ((rc = start_prepare(h)) != LS_OK) return rc;
+    const std::vector<const void*> was = loop_held(h);
+    HIPCHK(h, h->pl_ring.ensure((size_t)S * R * sizeof(float)));
+    HIPCHK(h, h->pl_hand.ensure((size_t)S * JF * npre * sizeof(float)));
+    HIPCHK(h, h->pl_vid.ensure((size_t)S * sizeof(int64_t))); HIPCHK(h, h->pl_emo_id.ensure((size_t)S * sizeof(int64_t)));
+    HIPCHK(h, h->pl_scale.ensure((size_t)S * sizeof(float)));
+    HIPCHK(h, h->pl_emotok.ensure(rowS)); HIPCHK(h, h->pl_text.ensure(rowS)); HIPCHK(h, h->pl_ctext.ensure(rowS));
+    HIPCHK(h, h->pl_table.ensure((size_t)S * kPoolRow * sizeof(int)));
+    HIPCHK(h, h->lg_clips.ensure((size_t)S * AL * sizeof(float)));
+    HIPCHK(h, h->lg_featc.ensure((size_t)S * T * kAudioFeat * sizeof(float)));
+    HIPCHK(h, h->lg_featp.ensure((size_t)S * T * KPP * sizeof(float)));
+    HIPCHK(h, h->vid.ensure((size_t)S * sizeof(int64_t))); HIPCHK(h, h->scale.ensure((size_t)S * sizeof(float)));
+    HIPCHK(h, h->xa.ensure(nxS)); HIPCHK(h, h->xb.ensure(nxS)); HIPCHK(h, h->xtmp.ensure(nxS)); HIPCHK(h, h->xio.ensure(nxS));
+    HIPCHK(h, h->lg_init.ensure(nxS)); HIPCHK(h, h->lg_mask.ensure((size_t)S * T));
+    if (h->have_sched) {        // the tape buffers for the longest loop of the schedule (a push checks them again: the schedule may be set later)
+        HIPCHK(h, h->eps_tape.ensure((size_t)h->n_steps * 2 * S * kD * sizeof(float))); HIPCHK(h, h->noise_tape.ensure(h->n_steps * nxS));
+    }
+    for (DevBuf* d : {&h->pl_vid, &h->pl_emo_id, &h->pl_scale, &h->pl_hand, &h->pl_emotok, &h->pl_text, &h->lg_clips, &h->vid, &h->scale})
+        HIPCHK(h, hipMemsetAsync(d->p, 0, d->bytes, st));
+    if ((rc = zero_origin_x(h, S)) != LS_OK || (rc = size_batch_buffers(h, S)) != LS_OK) return rc;
+    if ((rc = run_wav_encoder(h, h->lg_clips.f(), S)) != LS_OK) return rc;
+    if ((rc = prepare_style(h, S)) != LS_OK) return rc;
+    std::vector<float> sc((size_t)S, 0.f);
+    if (c) {            // the join of every slot: seed poses [B][JF][n_pre] are the hand-off store's layout
+        const int od = c->on_device;
+        if ((rc = pool_hold(h, h->pl_hand.p, c->seed_poses, (size_t)S * JF * npre * sizeof(float), od)) != LS_OK) return rc;
+        if ((rc = pool_hold(h, h->pl_vid.p, c->vid_indices, (size_t)S * sizeof(int64_t), od)) != LS_OK) return rc;
+        if ((rc = pool_hold(h, h->pl_scale.p, c->scale, (size_t)S * sizeof(float), od)) != LS_OK) return rc;
+        if (od) HIPCHK(h, hipMemcpyAsync(sc.data(), h->pl_scale.p, (size_t)S * sizeof(float), hipMemcpyDeviceToHost, st));      // the one read-back, as in prepare_scale
+        else memcpy(sc.data(), c->scale, (size_t)S * sizeof(float));
+        HIPCHK(h, hipStreamSynchronize(st));          // the scales are read below; the caller's arrays are its own again
+        h->all_scale_one = true;
+        for (float v : sc) h->all_scale_one = h->all_scale_one && v == 1.0f;
+        set_plan(h, S);
+        if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+    } else {
+        for (int pair = 0; pair < 2; ++pair)
+            for (int b = 1; b <= S; ++b) {      // smallest first: the handle is left planned for S slots
+                h->all_scale_one = pair != 0;
+                set_plan(h, b);
+                if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+            }
+    }
+    if ((rc = finish_clock(h)) != LS_OK) return rc;
+    // the graph rule (loop_held).  A pool's rounds keep one loop per batch and form and never evict (kKeep), so a pool starts with the
+    // whole cache to itself: its first round at a batch captures (tests/test_gpu_long_pool.py counts on it)
+    if (!c || loop_held(h) != was) free_graph(h);
+    h->B = S;
+    h->pl_S = S; h->pl_R = R; h->pl_rounds = 0;
+    h->pl_samples.assign((size_t)S, 0); h->pl_windows.assign((size_t)S, 0); h->pl_frames.assign((size_t)S, 0);
+    h->pl_scale_host = sc;
+    h->pl_open.assign((size_t)S, c ? 1 : 0); h->pl_have_emo.assign((size_t)S, 0); h->pl_have_text.assign((size_t)S, 0);
+    h->pl_styled.clear();
+    h->pl_lockstep = c ? ls_handle::kLockstep : ls_handle::kPool;
+    h->pl_state = ls_handle::kStreamOpen;
+    return LS_OK;
+}
+
+// Everything of a push behind its argument checks.  win[s]: the windows slot s runs (ls_long_pool_plan), rounds: the plan's slots
+// round after round.  Ahead of every round each slot takes as much of its chunk as its ring has room for -- a slot's next window
+// always fits behind the samples its earlier windows made dead -- so the rounds are the plan's whatever the chunk sizes.  Per round:
+// k_pool_gather -> WavEncoder -> k_build_feats at batch A, the per-batch stages at A, the window body, k_pool_scatter.  Nothing is
+// allocated from the first launch on.
+int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_args* a, ChainCall& cc, const std::vector<int32_t>& win,
+                     const std::vector<int32_t>& rounds, int n_rounds) {
     const int S = h->pl_S, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, AL = h->cfg.audio_len, R = h->pl_R, od = a->on_device, cap = a->capacity;
-    const bool beat = h->cfg.n_prefix_tokens == 2;
+    const bool beat = h->cfg.n_prefix_tokens == 2, lockstep = h->pl_lockstep != ls_handle::kPool;
     const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipStream_t st = h->stream;
     int rc;
     auto closing = [&](int s) { return a->closing && a->closing[s] && h->pl_open[(size_t)s]; };
-    for (int s = 0; s < S && a->given; ++s) {       // the held conditioning: what this call passes holds for every window started from here on
-        if ((a->given[s] & 1) && (rc = pool_hold_emo(h, s, a->emo + s, od)) != LS_OK) return rc;
-        if ((a->given[s] & 2) && (rc = pool_hold_text(h, s, a->text_features + (size_t)s * kD, od)) != LS_OK) return rc;
+    // the held conditioning: what this call passes holds for every window started from here on; consecutive slots given alike go in one copy
+    for (int s = 0, n; s < S && a->given; s += n) {
+        const int g = a->given[s];
+        for (n = 1; s + n < S && a->given[s + n] == g;) ++n;
+        if ((g & 1) && (rc = pool_hold_emo(h, s, n, a->emo + s, od)) != LS_OK) return rc;
+        if ((g & 2) && (rc = pool_hold_text(h, s, n, a->text_features + (size_t)s * kD, od)) != LS_OK) return rc;
     }
     const size_t out_bytes = (size_t)S * JF * cap * sizeof(float), nxS = (size_t)S * JF * T * sizeof(float);
     float* out = a->frames;
-    if (n_rounds > 0) {         // what the rounds need beyond ls_long_pool_open's buffers, sized for S slots while nothing is in flight
+    if (n_rounds > 0) {         // what the rounds need beyond the open's buffers, sized for S slots while nothing is in flight
         if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
         h->seg_next = -1;
         if (cc.tape) {
@@ -357,18 +376,22 @@ int pool_push_run(ls_handle* h, const ls_long_pool_push_args* a, ChainCall& cc, 
         HIPCHK(h, hipMemsetAsync(out, 0, out_bytes, st));      // a slot's row is zero behind its own frames
     }
     std::vector<long long> fed((size_t)S, 0);
-    auto feed = [&]() -> int {
+    std::vector<int> pos((size_t)S), take((size_t)S), copies;
+    auto feed = [&]() -> int {          // feed_copies: one strided copy per run of slots fed alike (a stream: one run)
         for (int s = 0; s < S; ++s) {
             const long long left = a->lengths[s] - fed[(size_t)s], room = R - (h->pl_samples[(size_t)s] - (long long)LS_LONG_AUDIO_STRIDE * h->pl_windows[(size_t)s]);
-            const int take = (int)(left < room ? left : room);
-            if (take <= 0) continue;
-            const int p = (int)(h->pl_samples[(size_t)s] % R), seg1 = take < R - p ? take : R - p;
-            const float* src = a->audio + (size_t)s * (size_t)a->n_max + (size_t)fed[(size_t)s];
-            float* ring = h->pl_ring.f() + (size_t)s * R;
-            HIPCHK(h, hipMemcpyAsync(ring + p, src, (size_t)seg1 * sizeof(float), kind, st));
-            if (take > seg1) HIPCHK(h, hipMemcpyAsync(ring, src + seg1, (size_t)(take - seg1) * sizeof(float), kind, st));
-            fed[(size_t)s] += take; h->pl_samples[(size_t)s] += take;
+            take[(size_t)s] = (int)(left < room ? left : room);
+            pos[(size_t)s] = (int)(h->pl_samples[(size_t)s] % R);
         }
+        feed_copies(S, R, pos.data(), fed.data(), take.data(), copies);
+        for (size_t i = 0; i < copies.size(); i += 5) {
+            const int s = copies[i], n = copies[i + 1];
+            const float* src = a->audio + (size_t)s * (size_t)a->n_max + (size_t)fed[(size_t)s] + (size_t)copies[i + 3];
+            HIPCHK(h, hipMemcpy2DAsync(h->pl_ring.f() + (size_t)s * R + copies[i + 2], (size_t)R * sizeof(float), src, (size_t)a->n_max * sizeof(float),
+                                       (size_t)copies[i + 4] * sizeof(float), (size_t)n, kind, st));
+        }
+        for (int s = 0; s < S; ++s)
+            if (take[(size_t)s] > 0) { fed[(size_t)s] += take[(size_t)s]; h->pl_samples[(size_t)s] += take[(size_t)s]; }
         return LS_OK;
     };
     PoolArgs pa{};
@@ -380,18 +403,19 @@ int pool_push_run(ls_handle* h, const ls_long_pool_push_args* a, ChainCall& cc, 
     pa.frames = out;
     pa.S = S; pa.AL = AL; pa.R = R; pa.JF = JF; pa.T = T; pa.KPP = h->KPP; pa.n_pre = npre; pa.T_total = cap;
     std::vector<int> t_off((size_t)S, 0), table((size_t)S * kPoolRow, 0);
-    size_t at = 0, rows_before = 0;          // position in `rounds`; rows of the rounds run so far (the packed tapes)
+    size_t at = 0;              // position in `rounds` = rows of the rounds run so far (the packed tapes)
     for (int r = 0; r < n_rounds; ++r) {
         if ((rc = feed()) != LS_OK) return rc;
         int A = 0;
         for (int s = 0; s < S; ++s) A += win[(size_t)s] > r;
+        const int32_t* slots = rounds.data() + at;
         bool ones = true;
         for (int i = 0; i < A; ++i) {
-            const int s = rounds[at + (size_t)i];
+            const int s = slots[i];
             const long long w = h->pl_windows[(size_t)s], lo = w * LS_LONG_AUDIO_STRIDE, have = h->pl_samples[(size_t)s] - lo;
             const int valid = (int)(have < AL ? (have < 0 ? 0 : have) : AL), f0 = w == 0 ? 0 : npre;
-            if (valid < AL && !(closing(s) && fed[(size_t)s] == a->lengths[s])) return fail(h, LS_ESTATE, "ls_long_pool_push: window %lld of slot %d is not complete", w, s);
-            if (t_off[(size_t)s] + T - f0 > cap) return fail(h, LS_ESTATE, "ls_long_pool_push: slot %d runs more frames than the call was planned for", s);
+            if (valid < AL && !(closing(s) && fed[(size_t)s] == a->lengths[s])) return fail(h, LS_ESTATE, "%s: window %lld of slot %d is not complete", entry, w, s);
+            if (t_off[(size_t)s] + T - f0 > cap) return fail(h, LS_ESTATE, "%s: slot %d runs more frames than the call was planned for", entry, s);
             int* row = &table[(size_t)i * kPoolRow];
             row[0] = s; row[1] = (int)(lo % R); row[2] = valid; row[3] = f0; row[4] = t_off[(size_t)s];
             ones = ones && h->pl_scale_host[(size_t)s] == 1.0f;
@@ -406,40 +430,96 @@ int pool_push_run(ls_handle* h, const ls_long_pool_push_args* a, ChainCall& cc, 
         h->all_scale_one = ones;
         set_plan(h, A);
         if ((rc = plan_workspaces(h)) != LS_OK) return rc;
-        if ((rc = prepare_style(h, A)) != LS_OK) return rc;
+        // The speaker style of rows [0, A) is a function of the round's slots and their speaker ids.  Only prepare_style writes the style
+        // buffers (z, z_ml, z_mu, z_logvar, z_std: the step kernels read them), and every caller of it but this one and session_open
+        // ends the session first (ls_prepare*, ls_long_prepare); a join that changes a slot's speaker empties pl_styled.  So the style
+        // of the same slots as last time is in place, and a stream styles once.
+        if (h->pl_styled.size() != (size_t)A || !std::equal(slots, slots + A, h->pl_styled.begin())) {
+            h->pl_styled.clear();
+            if ((rc = prepare_style(h, A)) != LS_OK) return rc;
+            h->pl_styled.assign(slots, slots + A);
+        }
         Window wn;
         wn.w = h->pl_rounds; wn.Bw = A; wn.featc = h->lg_featc.f(); wn.text = a->sag ? h->pl_ctext.f() : nullptr; wn.first = r == 0;
-        wn.policy = kKeep;          // a batch size met once is met again; kKeep never destroys a graph under the replays in flight
+        // a pool: a batch size met once is met again, and kKeep never destroys a graph under the replays in flight.  A stream has one
+        // batch and one key per call: a key that is not cached replaces what is
+        wn.policy = lockstep ? kReplace : kKeep;
         if (cc.tape) {
-            wn.x_init = a->x_init + rows_before * JF * T; wn.eps_tape = a->eps_tape + rows_before * cc.n_exec * 2 * kD; wn.noise_tape = a->noise_tape + rows_before * cc.n_exec * JF * T;
+            wn.x_init = a->x_init + at * JF * T; wn.eps_tape = a->eps_tape + at * cc.n_exec * 2 * kD; wn.noise_tape = a->noise_tape + at * cc.n_exec * JF * T;
             wn.host_tapes = !od;
         }
         if ((rc = run_window(h, cc, wn)) != LS_OK) return rc;
         pa.prev = x_plane(h, cc.n_exec);
         HIPCHK(h, launch_pool_scatter(pa, A, st));
         for (int i = 0; i < A; ++i) {
-            const int s = rounds[at + (size_t)i];
-            t_off[(size_t)s] += T - table[(size_t)i * kPoolRow + 3];
-            ++h->pl_windows[(size_t)s];
+            t_off[(size_t)slots[i]] += T - table[(size_t)i * kPoolRow + 3];
+            ++h->pl_windows[(size_t)slots[i]];
         }
         ++h->pl_rounds;
-        at += (size_t)A; rows_before += (size_t)A;
+        at += (size_t)A;
     }
     if ((rc = feed()) != LS_OK) return rc;
     bool any = false;
     for (int s = 0; s < S; ++s) {
-        if (fed[(size_t)s] != a->lengths[s]) return fail(h, LS_ESTATE, "ls_long_pool_push: no room in the ring of slot %d and no window to run", s);
+        if (fed[(size_t)s] != a->lengths[s]) return fail(h, LS_ESTATE, "%s: no room in the ring of slot %d and no window to run", entry, s);
         any = any || fed[(size_t)s] > 0;
         h->pl_frames[(size_t)s] += t_off[(size_t)s];
         if (a->n_frames) a->n_frames[s] = t_off[(size_t)s];
         if (closing(s)) h->pl_open[(size_t)s] = 0;
     }
     if (a->n_rounds) *a->n_rounds = n_rounds;
-    if (n_rounds == 0) {        // no sampling work: a host chunk is the caller's again once its copies are done
+    if (n_rounds == 0) {        // no sampling work: a host chunk is the caller's again once its copies are done, a device chunk is read in stream order
         if ((!od && any) || a->given) { HIPCHK(h, hipEventRecord(h->ev[6], st)); HIPCHK(h, hipEventSynchronize(h->ev[6])); }
         return LS_OK;
     }
     return chain_finish(h, cc, {{od ? nullptr : a->frames, out, out_bytes}});
+}
+
+// A push of a session behind its entry's own refusals: the plan, the refusals the plan decides, the sampler arguments, the rounds.
+// Nothing ahead of session_push_run touches the device.
+int session_push(ls_handle* h, const char* entry, const ls_long_pool_push_args* a) {
+    const int S = h->pl_S;
+    if (!a->lengths || a->n_max < 0 || (a->n_max > 0 && !a->audio)) return fail(h, LS_EINVAL, "%s: lengths, and audio with n_max > 0", entry);
+    if (a->capacity < 0 || (a->capacity > 0 && !a->frames)) return fail(h, LS_EINVAL, "%s: capacity without frames", entry);
+    if (a->emo && h->cfg.n_prefix_tokens != 2) return fail(h, LS_EINVAL, "%s: emo is a BEAT conditioning", entry);
+    if (a->text_features && !a->sag) return fail(h, LS_EINVAL, "%s: text_features without sag", entry);
+    std::vector<int32_t> closing((size_t)S, 0), open((size_t)S, 0), win((size_t)S, 0), frames((size_t)S, 0);
+    for (int s = 0; s < S; ++s) {
+        if (a->lengths[s] < 0 || a->lengths[s] > a->n_max) return fail(h, LS_EINVAL, "%s: lengths[%d] = %lld outside [0, %lld]", entry, s, (long long)a->lengths[s], (long long)a->n_max);
+        open[(size_t)s] = h->pl_open[(size_t)s];
+        closing[(size_t)s] = a->closing && a->closing[s];
+        if (a->given && ((a->given[s] & ~3) || ((a->given[s] & 1) && !a->emo) || ((a->given[s] & 2) && !a->text_features) || (a->given[s] && !open[(size_t)s])))
+            return fail(h, LS_EINVAL, "%s: given[%d] = %d names conditioning that was not passed, or a slot that is not open", entry, s, a->given[s]);
+    }
+    int32_t n_rounds = 0, n_entries = 0;
+    const std::vector<int64_t> before(h->pl_samples.begin(), h->pl_samples.end()), ran(h->pl_windows.begin(), h->pl_windows.end());
+    if (ls_long_pool_plan(S, h->cfg.audio_len, before.data(), ran.data(), a->lengths, closing.data(), open.data(), win.data(), frames.data(), nullptr, 0, &n_rounds, &n_entries) != LS_OK)
+        return fail(h, LS_EINVAL, "%s: samples for a slot that is not open, or closing a slot that was fed no sample", entry);
+    std::vector<int32_t> rounds((size_t)n_entries);
+    if (ls_long_pool_plan(S, h->cfg.audio_len, before.data(), ran.data(), a->lengths, closing.data(), open.data(), win.data(), nullptr, rounds.data(), n_entries, &n_rounds, &n_entries) != LS_OK)
+        return fail(h, LS_EINVAL, "%s: ls_long_pool_plan failed", entry);
+    for (int s = 0; s < S; ++s) {
+        if (frames[(size_t)s] > a->capacity) return fail(h, LS_EINVAL, "%s: slot %d runs %d windows = %d frames, capacity is %d", entry, s, win[(size_t)s], frames[(size_t)s], a->capacity);
+        if (win[(size_t)s] > 0 && ran[(size_t)s] == 0) {        // the slot's first window: what it needs must be held by now
+            const int g = a->given ? a->given[s] : 0;
+            if (h->cfg.n_prefix_tokens == 2 && !h->pl_have_emo[(size_t)s] && !(g & 1)) return fail(h, LS_EINVAL, "%s: the BEAT variant's first window needs emo ids (slot %d)", entry, s);
+            if (a->sag && !h->pl_have_text[(size_t)s] && !(g & 2)) return fail(h, LS_EINVAL, "%s: sag needs text_features for the first window (slot %d)", entry, s);
+        }
+    }
+    ChainCall cc;
+    int rc;
+    if ((rc = chain_args(h, entry, a, n_rounds > 0, cc)) != LS_OK) return rc;
+    if (n_rounds > 0 && !cc.tape) {
+        if ((a->sample_offset + (unsigned long long)S) >> 48) return fail(h, LS_EINVAL, "PHILOX: sample_offset + capacity must stay below 2^48 (the round index sits above)");
+        if (h->pl_rounds + n_rounds > (1 << 16)) return fail(h, LS_ESTATE, "%s: PHILOX keys a round by its index since open, which stays below 2^16; open a new session", entry);
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    rc = session_push_run(h, entry, a, cc, win, rounds, n_rounds);
+    if (rc != LS_OK) {      // rings and hand-off stores may be half written: the session is over, the handle is not
+        h->pl_state = ls_handle::kStreamFailed;
+        (void)hipStreamSynchronize(h->stream);
+    }
+    return rc;
 }
 
 }  // namespace
@@ -574,50 +654,6 @@ int ls_long_prepare_ragged(ls_handle* h, const ls_long_cond* c, const int64_t* a
     return LS_OK;
 }
 
-// Opening a stream (ls_long_stream_cond in ls_hip.h): ls_long_prepare without its audio.  The per-batch stages run once at batch B, the
-// window-0 hand-off (k_chain_window from the seed poses) leaves feat_u / origin_x as ls_long_sample's first window finds them, and the
-// buffers a window needs -- the ring, one gathered window, one window's features -- are sized here, so ls_long_stream_push allocates
-// nothing that a captured loop could hold.
-int ls_long_stream_open(ls_handle* h, const ls_long_stream_cond* c) {
-    if (!h || !c) return fail(h, LS_EINVAL, "ls_long_stream_open: null argument");
-    int rc;
-    if ((rc = check_cond(h, "ls_long_stream_open", c->batch, nullptr, true, c->seed_poses && c->vid_indices && c->scale, true)) != LS_OK) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int B = c->batch, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, od = c->on_device;
-    const int R = (AL + LS_LONG_AUDIO_STRIDE + 3) / 4 * 4;       // a window and the stride to the next; whole float4 groups per clip
-    hipStream_t st = h->stream;
-    end_stream(h);                              // a running session pool ends here ...
-    h->st_state = ls_handle::kStreamNone;       // ... and so does a stream that was open; this one opens when everything below has succeeded
-    if ((rc = start_prepare(h)) != LS_OK) return rc;
-    if ((rc = ingest_cond(h, B, od, c->seed_poses, c->vid_indices, c->scale, nullptr, 0)) != LS_OK) return rc;
-    HIPCHK(h, h->st_ring.ensure((size_t)B * R * sizeof(float)));
-    HIPCHK(h, h->lg_clips.ensure((size_t)B * AL * sizeof(float)));
-    HIPCHK(h, h->lg_featc.ensure((size_t)B * T * kAudioFeat * sizeof(float)));
-    HIPCHK(h, h->lg_featp.ensure((size_t)B * T * KPP * sizeof(float)));
-    HIPCHK(h, h->st_text.ensure((size_t)B * kD * sizeof(float)));
-    HIPCHK(h, h->st_emo_ids.ensure((size_t)B * sizeof(int64_t)));
-    if ((rc = zero_origin_x(h, B)) != LS_OK || (rc = size_batch_buffers(h, B)) != LS_OK) return rc;
-    if ((rc = prepare_style(h, B)) != LS_OK) return rc;
-    if ((rc = prepare_plan(h, B)) != LS_OK) return rc;
-    ChainArgs ca{};         // window 0's prefix poses: the caller's seed poses
-    ca.seed = h->lg_seed.f(); ca.feat_u = h->feat_u.f(); ca.origin_x = h->origin_x.f();
-    ca.JF = JF; ca.T = T; ca.KPP = KPP; ca.n_pre = h->cfg.n_pre_seq; ca.T_total = T; ca.n_next = B;
-    HIPCHK(h, launch_chain_window(ca, B, st));
-    if ((rc = finish_prepare(h, B)) != LS_OK) return rc;
-    h->st_R = R;
-    h->st_samples = h->st_windows = h->st_frames = 0;
-    h->st_have_emo = h->st_have_text = false;
-    h->st_state = ls_handle::kStreamOpen;
-    return LS_OK;
-}
-
-int ls_long_stream_info(const ls_handle* h, int64_t out[4]) {
-    if (!h || !out) return LS_EINVAL;
-    out[0] = h->st_samples; out[1] = h->st_windows; out[2] = h->st_frames;
-    out[3] = h->st_state == ls_handle::kStreamNone ? 0 : (int64_t)(h->st_ring.bytes + h->lg_clips.bytes + h->lg_featc.bytes);      // as allocated
-    return LS_OK;
-}
-
 // Long-form synthesis (ls_long_sample_args in ls_hip.h): per window the hand-off kernel, then the window body; one wait at the end.
 //
 // After ls_long_prepare_ragged window w runs the lg_bw[w] clips that still have audio: slots [0, lg_bw[w]) of every per-clip buffer
@@ -720,44 +756,6 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
     return chain_finish(h, cc, {{od ? nullptr : a->timeline, tl, (size_t)B * JF * Tt * sizeof(float)}, {od || !wd ? nullptr : a->windows, wd, W * nx}});
 }
 
-int ls_long_stream_push(ls_handle* h, const ls_long_stream_push_args* a) {
-    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_stream_push: null argument");
-    switch (h->st_state) {
-    case ls_handle::kStreamOpen: break;
-    case ls_handle::kStreamNone: return fail(h, LS_ESTATE, "ls_long_stream_push before ls_long_stream_open");
-    case ls_handle::kStreamClosed: return fail(h, LS_ESTATE, "ls_long_stream_push: the stream is closed");
-    case ls_handle::kStreamFailed: return fail(h, LS_ESTATE, "ls_long_stream_push: an earlier push of this stream failed; open a new one");
-    default: return fail(h, LS_ESTATE, "ls_long_stream_push: the stream was ended by a call that replaced the handle's prepared conditioning "
-                                       "(ls_prepare, ls_long_prepare, ls_commit_weights or another ls_long_stream_open); open a new one");
-    }
-    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_stream_push before ls_set_schedule");
-    if (a->n_samples < 0 || (a->n_samples > 0 && !a->audio)) return fail(h, LS_EINVAL, "ls_long_stream_push: n_samples %lld with%s audio", (long long)a->n_samples, a->audio ? "" : "out");
-    if (a->capacity < 0 || (a->capacity > 0 && !a->frames)) return fail(h, LS_EINVAL, "ls_long_stream_push: capacity without frames");
-    if (a->text_features && !a->sag) return fail(h, LS_EINVAL, "ls_long_stream_push: text_features without sag");
-    if (a->emo && h->cfg.n_prefix_tokens != 2) return fail(h, LS_EINVAL, "ls_long_stream_push: emo is a BEAT conditioning");
-    int64_t first = 0, k = 0;
-    if (ls_long_stream_plan(h->st_samples, a->n_samples, h->cfg.audio_len, a->closing, &first, &k) != LS_OK)
-        return fail(h, LS_EINVAL, "ls_long_stream_push: closing a stream that was fed no sample");
-    if (first != h->st_windows) return fail(h, LS_ESTATE, "ls_long_stream_push: %lld windows have run, %lld were complete", h->st_windows, (long long)first);
-    const int T = h->T, npre = h->cfg.n_pre_seq;
-    const int64_t need = k == 0 ? 0 : k * (T - npre) + (first == 0 ? npre : 0);
-    if (need > a->capacity) return fail(h, LS_EINVAL, "ls_long_stream_push: this call runs %lld windows = %lld frames, capacity is %d", (long long)k, (long long)need, a->capacity);
-    ChainCall cc;
-    int rc;
-    if ((rc = chain_args(h, "ls_long_stream_push", a, k > 0, cc)) != LS_OK) return rc;
-    if (k > 0) {
-        if (h->cfg.n_prefix_tokens == 2 && !a->emo && !h->st_have_emo) return fail(h, LS_EINVAL, "ls_long_stream_push: the BEAT variant's first window needs emo ids");
-        if (a->sag && !a->text_features && !h->st_have_text) return fail(h, LS_EINVAL, "ls_long_stream_push: sag needs text_features for the first window");
-    }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    rc = stream_push_run(h, a, cc, k);
-    if (rc != LS_OK) {      // the ring and the hand-off poses may be half written: the stream is over, the handle is not
-        h->st_state = ls_handle::kStreamFailed;
-        (void)hipStreamSynchronize(h->stream);
-    }
-    return rc;
-}
-
 // Timeline edit (ls_long_edit_args in ls_hip.h): the window body over the windows of ls_long_edit_plan, with k_edit_gather ahead of a
 // window and k_edit_scatter behind it in place of the hand-off kernel, and the loop run with the inpainting branch on the planes the
 // gather left on the device.  The loop's key holds the inpainting form.  One wait at the end.
@@ -850,65 +848,26 @@ int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) {
     return LS_OK;
 }
 
-// Opening a session pool (ls_hip.h): ls_long_stream_open's stages for `capacity` slots without any slot's conditioning.  Every buffer a
-// round touches is sized for S rows here -- the per-slot stores, the compact batch buffers, the WavEncoder's activations (one run on
-// silence), the style buffers (one run on speaker 0), the loop's planes and tape buffers, the SAG plane and mask, and the workspaces of
-// the step plans of every batch 1..S under both forms of a step -- so that a push allocates only what depends on its own arguments (a
-// host caller's tape staging and output; the tape buffers again when the schedule grew after the open), ahead of its first launch, with
-// nothing in flight.  No graph of an earlier call survives: its addresses may predate these buffers.
+// Opening a stream (ls_long_stream_cond in ls_hip.h): a session of `batch` slots, every slot joined from the caller's arrays
+int ls_long_stream_open(ls_handle* h, const ls_long_stream_cond* c) {
+    if (!h || !c) return fail(h, LS_EINVAL, "ls_long_stream_open: null argument");
+    const int rc = check_cond(h, "ls_long_stream_open", c->batch, nullptr, true, c->seed_poses && c->vid_indices && c->scale, true);
+    return rc != LS_OK ? rc : session_open(h, c->batch, c);
+}
+
+// Opening a session pool (ls_hip.h): a session of `capacity` free slots
 int ls_long_pool_open(ls_handle* h, int32_t capacity) {
     if (!h) return fail(h, LS_EINVAL, "ls_long_pool_open: null argument");
-    int rc;
-    if ((rc = check_cond(h, "ls_long_pool_open", capacity, nullptr, true, true, true)) != LS_OK) return rc;
+    const int rc = check_cond(h, "ls_long_pool_open", capacity, nullptr, true, true, true);
+    if (rc != LS_OK) return rc;
     if (capacity > 1024) return fail(h, LS_EINVAL, "ls_long_pool_open: capacity %d beyond 1024 slots", capacity);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int S = capacity, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, npre = h->cfg.n_pre_seq;
-    const int R = (AL + LS_LONG_AUDIO_STRIDE + 3) / 4 * 4;       // as a stream's ring
-    const size_t nxS = (size_t)S * JF * T * sizeof(float), rowS = (size_t)S * kD * sizeof(float);
-    hipStream_t st = h->stream;
-    end_stream(h);
-    h->pl_state = ls_handle::kStreamNone;
-    if ((rc = start_prepare(h)) != LS_OK) return rc;
-    HIPCHK(h, h->pl_ring.ensure((size_t)S * R * sizeof(float)));
-    HIPCHK(h, h->pl_hand.ensure((size_t)S * JF * npre * sizeof(float)));
-    HIPCHK(h, h->pl_vid.ensure((size_t)S * sizeof(int64_t))); HIPCHK(h, h->pl_emo_id.ensure((size_t)S * sizeof(int64_t)));
-    HIPCHK(h, h->pl_scale.ensure((size_t)S * sizeof(float)));
-    HIPCHK(h, h->pl_emotok.ensure(rowS)); HIPCHK(h, h->pl_text.ensure(rowS)); HIPCHK(h, h->pl_ctext.ensure(rowS));
-    HIPCHK(h, h->pl_table.ensure((size_t)S * kPoolRow * sizeof(int)));
-    HIPCHK(h, h->lg_clips.ensure((size_t)S * AL * sizeof(float)));
-    HIPCHK(h, h->lg_featc.ensure((size_t)S * T * kAudioFeat * sizeof(float)));
-    HIPCHK(h, h->lg_featp.ensure((size_t)S * T * KPP * sizeof(float)));
-    HIPCHK(h, h->vid.ensure((size_t)S * sizeof(int64_t))); HIPCHK(h, h->scale.ensure((size_t)S * sizeof(float)));
-    HIPCHK(h, h->xa.ensure(nxS)); HIPCHK(h, h->xb.ensure(nxS)); HIPCHK(h, h->xtmp.ensure(nxS)); HIPCHK(h, h->xio.ensure(nxS));
-    HIPCHK(h, h->lg_init.ensure(nxS)); HIPCHK(h, h->lg_mask.ensure((size_t)S * T));
-    if (h->have_sched) {        // the tape buffers for the longest loop of the schedule (a push checks them again: the schedule may be set later)
-        HIPCHK(h, h->eps_tape.ensure((size_t)h->n_steps * 2 * S * kD * sizeof(float))); HIPCHK(h, h->noise_tape.ensure(h->n_steps * nxS));
-    }
-    for (DevBuf* d : {&h->pl_vid, &h->pl_emo_id, &h->pl_scale, &h->pl_hand, &h->pl_emotok, &h->pl_text, &h->lg_clips, &h->vid, &h->scale})
-        HIPCHK(h, hipMemsetAsync(d->p, 0, d->bytes, st));
-    if ((rc = zero_origin_x(h, S)) != LS_OK || (rc = size_batch_buffers(h, S)) != LS_OK) return rc;
-    if ((rc = run_wav_encoder(h, h->lg_clips.f(), S)) != LS_OK) return rc;
-    if ((rc = prepare_style(h, S)) != LS_OK) return rc;
-    for (int pair = 0; pair < 2; ++pair)
-        for (int b = 1; b <= S; ++b) {      // smallest first: the handle is left planned for S slots
-            h->all_scale_one = pair != 0;
-            set_plan(h, b);
-            if ((rc = plan_workspaces(h)) != LS_OK) return rc;
-        }
-    if ((rc = finish_prepare(h, S)) != LS_OK) return rc;
-    free_graph(h);
-    h->pl_S = S; h->pl_R = R; h->pl_rounds = 0;
-    h->pl_samples.assign((size_t)S, 0); h->pl_windows.assign((size_t)S, 0); h->pl_frames.assign((size_t)S, 0);
-    h->pl_scale_host.assign((size_t)S, 0.f);
-    h->pl_open.assign((size_t)S, 0); h->pl_have_emo.assign((size_t)S, 0); h->pl_have_text.assign((size_t)S, 0);
-    h->pl_state = ls_handle::kStreamOpen;
-    return LS_OK;
+    return session_open(h, capacity, nullptr);
 }
 
 int ls_long_pool_join(ls_handle* h, const ls_long_pool_join_args* a) {
     if (!h || !a) return fail(h, LS_EINVAL, "ls_long_pool_join: null argument");
     int rc;
-    if ((rc = pool_is_open(h, "ls_long_pool_join")) != LS_OK) return rc;
+    if ((rc = session_is_open(h, "ls_long_pool_join", false)) != LS_OK) return rc;
     if (a->slot < 0 || a->slot >= h->pl_S) return fail(h, LS_EINVAL, "ls_long_pool_join: slot %d outside [0, %d)", a->slot, h->pl_S);
     if (h->pl_open[(size_t)a->slot]) return fail(h, LS_ESTATE, "ls_long_pool_join: slot %d is occupied", a->slot);
     if (!a->seed_poses || !a->vid_index || !a->scale) return fail(h, LS_EINVAL, "ls_long_pool_join: null conditioning pointer");
@@ -916,12 +875,13 @@ int ls_long_pool_join(ls_handle* h, const ls_long_pool_join_args* a) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int s = a->slot, od = a->on_device;
     const size_t hand = (size_t)h->JF * h->cfg.n_pre_seq;
+    if (std::find(h->pl_styled.begin(), h->pl_styled.end(), s) != h->pl_styled.end()) h->pl_styled.clear();       // the slot's speaker changes
     if ((rc = pool_hold(h, h->pl_hand.f() + (size_t)s * hand, a->seed_poses, hand * sizeof(float), od)) != LS_OK) return rc;
     if ((rc = pool_hold(h, static_cast<int64_t*>(h->pl_vid.p) + s, a->vid_index, sizeof(int64_t), od)) != LS_OK) return rc;
     if ((rc = pool_hold(h, h->pl_scale.f() + s, a->scale, sizeof(float), od)) != LS_OK) return rc;
     h->pl_have_emo[(size_t)s] = h->pl_have_text[(size_t)s] = 0;
-    if (a->emo && (rc = pool_hold_emo(h, s, a->emo, od)) != LS_OK) return rc;
-    if (a->text_features && (rc = pool_hold_text(h, s, a->text_features, od)) != LS_OK) return rc;
+    if (a->emo && (rc = pool_hold_emo(h, s, 1, a->emo, od)) != LS_OK) return rc;
+    if (a->text_features && (rc = pool_hold_text(h, s, 1, a->text_features, od)) != LS_OK) return rc;
     float sc = 0.f;
     if (od) HIPCHK(h, hipMemcpyAsync(&sc, h->pl_scale.f() + s, sizeof(float), hipMemcpyDeviceToHost, h->stream));      // the one read-back, as in prepare_scale
     else sc = *a->scale;
@@ -934,55 +894,57 @@ int ls_long_pool_join(ls_handle* h, const ls_long_pool_join_args* a) {
 
 int ls_long_pool_push(ls_handle* h, const ls_long_pool_push_args* a) {
     if (!h || !a) return fail(h, LS_EINVAL, "ls_long_pool_push: null argument");
-    int rc;
-    if ((rc = pool_is_open(h, "ls_long_pool_push")) != LS_OK) return rc;
+    const int rc = session_is_open(h, "ls_long_pool_push", false);
+    if (rc != LS_OK) return rc;
     if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_pool_push before ls_set_schedule");
-    const int S = h->pl_S;
-    if (!a->lengths || a->n_max < 0 || (a->n_max > 0 && !a->audio)) return fail(h, LS_EINVAL, "ls_long_pool_push: lengths, and audio with n_max > 0");
-    if (a->capacity < 0 || (a->capacity > 0 && !a->frames)) return fail(h, LS_EINVAL, "ls_long_pool_push: capacity without frames");
-    if (a->emo && h->cfg.n_prefix_tokens != 2) return fail(h, LS_EINVAL, "ls_long_pool_push: emo is a BEAT conditioning");
-    if (a->text_features && !a->sag) return fail(h, LS_EINVAL, "ls_long_pool_push: text_features without sag");
-    std::vector<int32_t> closing((size_t)S, 0), open((size_t)S, 0), win((size_t)S, 0), frames((size_t)S, 0);
-    for (int s = 0; s < S; ++s) {
-        if (a->lengths[s] < 0 || a->lengths[s] > a->n_max) return fail(h, LS_EINVAL, "ls_long_pool_push: lengths[%d] = %lld outside [0, %lld]", s, (long long)a->lengths[s], (long long)a->n_max);
-        open[(size_t)s] = h->pl_open[(size_t)s];
-        closing[(size_t)s] = a->closing && a->closing[s];
-        if (a->given && ((a->given[s] & ~3) || ((a->given[s] & 1) && !a->emo) || ((a->given[s] & 2) && !a->text_features) || (a->given[s] && !open[(size_t)s])))
-            return fail(h, LS_EINVAL, "ls_long_pool_push: given[%d] = %d names conditioning that was not passed, or a slot that is not open", s, a->given[s]);
-    }
-    int32_t n_rounds = 0, n_entries = 0;
-    const std::vector<int64_t> before(h->pl_samples.begin(), h->pl_samples.end()), ran(h->pl_windows.begin(), h->pl_windows.end());
-    if (ls_long_pool_plan(S, h->cfg.audio_len, before.data(), ran.data(), a->lengths, closing.data(), open.data(), win.data(), frames.data(), nullptr, 0, &n_rounds, &n_entries) != LS_OK)
-        return fail(h, LS_EINVAL, "ls_long_pool_push: samples for a slot that is not open, or closing a slot that was fed no sample");
-    std::vector<int32_t> rounds((size_t)n_entries);
-    if (ls_long_pool_plan(S, h->cfg.audio_len, before.data(), ran.data(), a->lengths, closing.data(), open.data(), win.data(), nullptr, rounds.data(), n_entries, &n_rounds, &n_entries) != LS_OK)
-        return fail(h, LS_EINVAL, "ls_long_pool_push: ls_long_pool_plan failed");
-    for (int s = 0; s < S; ++s) {
-        if (frames[(size_t)s] > a->capacity) return fail(h, LS_EINVAL, "ls_long_pool_push: slot %d runs %d windows = %d frames, capacity is %d", s, win[(size_t)s], frames[(size_t)s], a->capacity);
-        if (win[(size_t)s] > 0 && ran[(size_t)s] == 0) {        // the slot's first window: what it needs must be held by now
-            const int g = a->given ? a->given[s] : 0;
-            if (h->cfg.n_prefix_tokens == 2 && !h->pl_have_emo[(size_t)s] && !(g & 1)) return fail(h, LS_EINVAL, "ls_long_pool_push: the BEAT variant's first window needs emo ids (slot %d)", s);
-            if (a->sag && !h->pl_have_text[(size_t)s] && !(g & 2)) return fail(h, LS_EINVAL, "ls_long_pool_push: sag needs text_features for the first window (slot %d)", s);
-        }
-    }
-    ChainCall cc;
-    if ((rc = chain_args(h, "ls_long_pool_push", a, n_rounds > 0, cc)) != LS_OK) return rc;
-    if (n_rounds > 0 && !cc.tape) {
-        if ((a->sample_offset + (unsigned long long)S) >> 48) return fail(h, LS_EINVAL, "PHILOX: sample_offset + capacity must stay below 2^48 (the round index sits above)");
-        if (h->pl_rounds + n_rounds > (1 << 16)) return fail(h, LS_ESTATE, "ls_long_pool_push: PHILOX keys a round by its index since open, which stays below 2^16; open a new pool");
-    }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    rc = pool_push_run(h, a, cc, win, rounds, n_rounds);
-    if (rc != LS_OK) {      // rings and hand-off stores may be half written: the pool is over, the handle is not
-        h->pl_state = ls_handle::kStreamFailed;
-        (void)hipStreamSynchronize(h->stream);
-    }
-    return rc;
+    return session_push(h, "ls_long_pool_push", a);
+}
+
+// A push of a stream: its own refusals, then the session's push with every slot fed, given and closed alike.  The packed tapes of
+// rounds at batch B are the stream's [k, B, ...] tapes, the round index is the window index.
+int ls_long_stream_push(ls_handle* h, const ls_long_stream_push_args* a) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_stream_push: null argument");
+    int rc;
+    if ((rc = session_is_open(h, "ls_long_stream_push", true)) != LS_OK) return rc;
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_stream_push before ls_set_schedule");
+    if (a->n_samples < 0 || (a->n_samples > 0 && !a->audio)) return fail(h, LS_EINVAL, "ls_long_stream_push: n_samples %lld with%s audio", (long long)a->n_samples, a->audio ? "" : "out");
+    int64_t first = 0, k = 0;
+    if (ls_long_stream_plan(h->pl_samples[0], a->n_samples, h->cfg.audio_len, a->closing, &first, &k) != LS_OK)
+        return fail(h, LS_EINVAL, "ls_long_stream_push: closing a stream that was fed no sample");
+    if (first != h->pl_windows[0]) return fail(h, LS_ESTATE, "ls_long_stream_push: %lld windows have run, %lld were complete", h->pl_windows[0], (long long)first);
+    const int64_t need = k == 0 ? 0 : k * (h->T - h->cfg.n_pre_seq) + (first == 0 ? h->cfg.n_pre_seq : 0);
+    if (need > a->capacity) return fail(h, LS_EINVAL, "ls_long_stream_push: this call runs %lld windows = %lld frames, capacity is %d", (long long)k, (long long)need, a->capacity);
+    const size_t B = (size_t)h->pl_S;
+    const std::vector<int64_t> lengths(B, a->n_samples);
+    const std::vector<int32_t> closing(B, a->closing ? 1 : 0), given(B, (a->emo ? 1 : 0) | (a->text_features ? 2 : 0));
+    std::vector<int32_t> n_frames(B, 0);
+    int32_t n_rounds = 0;
+    ls_long_pool_push_args pa{};
+    pa.sampler = a->sampler; pa.noise_mode = a->noise_mode; pa.skip_timesteps = a->skip_timesteps; pa.on_device = a->on_device;
+    pa.use_graph = a->use_graph; pa.clip_denoised = a->clip_denoised; pa.two_pass_always = a->two_pass_always; pa.eta = a->eta;
+    pa.capacity = a->capacity; pa.n_max = a->n_samples; pa.audio = a->audio;
+    pa.lengths = lengths.data(); pa.closing = closing.data(); pa.given = given[0] ? given.data() : nullptr;
+    pa.emo = a->emo; pa.sag = a->sag; pa.text_features = a->text_features;
+    pa.x_init = a->x_init; pa.eps_tape = a->eps_tape; pa.noise_tape = a->noise_tape; pa.seed = a->seed; pa.sample_offset = a->sample_offset;
+    pa.frames = a->frames; pa.n_frames = n_frames.data(); pa.n_rounds = &n_rounds;
+    if ((rc = session_push(h, "ls_long_stream_push", &pa)) != LS_OK) return rc;
+    if (a->n_frames) *a->n_frames = n_frames[0];
+    if (a->n_windows) *a->n_windows = n_rounds;
+    if (a->closing) h->pl_lockstep = ls_handle::kLockstepClosed;
+    return LS_OK;
+}
+
+int ls_long_stream_info(const ls_handle* h, int64_t out[4]) {
+    if (!h || !out) return LS_EINVAL;
+    const bool stream = h->pl_state != ls_handle::kStreamNone && h->pl_lockstep != ls_handle::kPool;       // slot 0 speaks for all
+    out[0] = stream ? h->pl_samples[0] : 0; out[1] = stream ? h->pl_windows[0] : 0; out[2] = stream ? h->pl_frames[0] : 0;
+    out[3] = stream ? session_bytes(h) : 0;
+    return LS_OK;
 }
 
 int ls_long_pool_info(const ls_handle* h, int32_t capacity, int64_t* samples_in, int64_t* windows_run, int64_t* frames_out, int32_t* open, int64_t misc[4]) {
     if (!h || capacity < 0) return LS_EINVAL;
-    const int S = h->pl_state == ls_handle::kStreamNone ? 0 : h->pl_S;
+    const int S = h->pl_state == ls_handle::kStreamNone || h->pl_lockstep != ls_handle::kPool ? 0 : h->pl_S;
     for (int s = 0; s < capacity; ++s) {
         const bool in = s < S;
         if (samples_in) samples_in[s] = in ? h->pl_samples[(size_t)s] : 0;
@@ -992,10 +954,9 @@ int ls_long_pool_info(const ls_handle* h, int32_t capacity, int64_t* samples_in,
     }
     if (misc) {
         misc[0] = S;
-        misc[1] = S == 0 ? 0 : (int64_t)(h->pl_ring.bytes + h->pl_hand.bytes + h->pl_vid.bytes + h->pl_emo_id.bytes + h->pl_scale.bytes + h->pl_emotok.bytes +
-                                         h->pl_text.bytes + h->pl_ctext.bytes + h->pl_table.bytes + h->lg_clips.bytes + h->lg_featc.bytes);      // as allocated
+        misc[1] = S == 0 ? 0 : session_bytes(h);
         misc[2] = S == 0 ? 0 : h->pl_rounds;
-        misc[3] = h->pl_state == ls_handle::kStreamOpen;
+        misc[3] = S != 0 && h->pl_state == ls_handle::kStreamOpen;
     }
     return LS_OK;
 }

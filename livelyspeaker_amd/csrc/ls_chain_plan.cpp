@@ -1,5 +1,6 @@
 // The plans of the chained-window engine (ls_chain_api.cpp): which clips run which window of a ragged call, which windows a timeline
-// edit runs, which windows a push of a stream runs, which rounds a push of a session pool runs.  Integer arithmetic on host arrays, no
+// edit runs, which windows a push of a stream runs, which rounds a push of a session pool runs, which copies feed the slots' rings.
+// Integer arithmetic on host arrays, no
 // HIP in here: each is the single definition for its entry and for Python (long_form.py), and tests/chain_plan_main.cpp and
 // tests/pool_plan_main.cpp run them on their edges under the host sanitizers.
 #include <algorithm>
@@ -27,6 +28,22 @@ void long_plan_drop(int B, int AL, const int64_t* lengths, std::vector<int>& row
     bw.assign((size_t)wmax, 0);                     // B_w = clips with W_b > w: count the clips that END at each w, then a running sum from the back
     for (int b = 0; b < B; ++b) ++bw[(size_t)wb[(size_t)b] - 1];
     for (int w = wmax - 2; w >= 0; --w) bw[(size_t)w] += bw[(size_t)w + 1];
+}
+
+// The copies that feed a session's rings (ls_chain_api.cpp: feed): slot s takes take[s] new samples, from column from[s] of its row of
+// the caller's chunk to position pos[s] of its ring of R samples.  Consecutive slots with the same (pos, from, take), take > 0, form
+// a run, and a run is one strided copy -- two where it passes the ring's end.  Every run is maximal, so a stream (all slots alike) is
+// one run whatever its batch.  Five ints per copy: first slot, slots, ring position, offset into the take, samples.  Declared in
+// ls_handle.h.
+void feed_copies(int S, int R, const int* pos, const long long* from, const int* take, std::vector<int>& copies) {
+    copies.clear();
+    for (int s = 0, n; s < S; s += n) {
+        for (n = 1; take[s] > 0 && s + n < S && pos[s + n] == pos[s] && from[s + n] == from[s] && take[s + n] == take[s];) ++n;
+        if (take[s] <= 0) continue;
+        const int seg1 = take[s] < R - pos[s] ? take[s] : R - pos[s];
+        copies.insert(copies.end(), {s, n, pos[s], 0, seg1});
+        if (take[s] > seg1) copies.insert(copies.end(), {s, n, 0, seg1, take[s] - seg1});
+    }
 }
 
 }  // namespace ls

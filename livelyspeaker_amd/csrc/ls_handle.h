@@ -134,27 +134,24 @@ struct ls_handle {
     std::vector<int> lg_bw, lg_off;
     int lg_scale_ones = 0;
     DevBuf lg_row, lg_table, lg_lens;
-    // streaming long-form synthesis (ls_long_stream_open / _push): st_ring [B][st_R] holds sample s of every clip at s % st_R; the
-    // samples below audio_stride * st_windows are dead.  The gathered window is lg_clips [B][audio_len], its features lg_featc
-    // [B][T][256]; the hand-off poses live in feat_u / origin_x between two pushes, the held emotion tokens in emo_tok, the held text
-    // features in st_text.  st_state: kStreamNone, kStreamOpen, or why the stream ended.
-    enum { kStreamNone = 0, kStreamOpen, kStreamReplaced, kStreamClosed, kStreamFailed };
-    int st_state = kStreamNone;
-    int st_R = 0;
-    long long st_samples = 0, st_windows = 0, st_frames = 0;
-    bool st_have_emo = false, st_have_text = false;
-    DevBuf st_ring, st_emo_ids, st_text;
-    // session pool (ls_long_pool_open / _join / _push): pl_S slots, each a stream of its own.  Per slot on the device: the ring
-    // pl_ring [S][pl_R], the hand-off poses pl_hand [S][JF][n_pre] (seed poses until the slot's window 0 has run), the held conditioning
-    // pl_vid / pl_scale / pl_emotok [S][512] / pl_text [S][512]; per slot on the host: the counters, the scale and what is held.  A round
-    // gathers its active slots into rows [0, A) of lg_clips, feat_u, origin_x, vid, scale, emo_tok and pl_ctext (k_pool_gather) by
-    // pl_table [S][kPoolRow].  pl_state: as st_state.  pl_rounds: rounds run since open (the PHILOX window index).
-    int pl_state = kStreamNone;
+    // Streaming sessions (ls_long_pool_open / _join / _push; ls_long_stream_open / _push): pl_S slots, each a stream of its own.  Per
+    // slot on the device: the ring pl_ring [S][pl_R] (sample n of the slot at n % pl_R; the samples below audio_stride * pl_windows[s]
+    // are dead), the hand-off poses pl_hand [S][JF][n_pre] (seed poses until the slot's window 0 has run), the held conditioning pl_vid /
+    // pl_scale / pl_emotok [S][512] / pl_text [S][512]; per slot on the host: the counters, the scale and what is held.  A round gathers
+    // its active slots into rows [0, A) of lg_clips, feat_u, origin_x, vid, scale, emo_tok and pl_ctext (k_pool_gather) by pl_table
+    // [S][kPoolRow].  pl_state: kStreamNone, kStreamOpen, or why the session ended.  pl_rounds: rounds run since open (the PHILOX window
+    // index).  pl_lockstep: the session was opened by ls_long_stream_open -- every slot joined there, all fed and closed together by
+    // ls_long_stream_push; kLockstepClosed once its closing push has run.  pl_styled: the slots of the round prepare_style last ran for
+    // (emptied by a join of one of them): a round of the same slots finds its speaker style in place.
+    enum { kStreamNone = 0, kStreamOpen, kStreamReplaced, kStreamFailed };
+    enum { kPool = 0, kLockstep, kLockstepClosed };
+    int pl_state = kStreamNone, pl_lockstep = kPool;
     int pl_S = 0, pl_R = 0;
     long long pl_rounds = 0;
     std::vector<long long> pl_samples, pl_windows, pl_frames;
     std::vector<float> pl_scale_host;
     std::vector<char> pl_open, pl_have_emo, pl_have_text;
+    std::vector<int32_t> pl_styled;
     DevBuf pl_ring, pl_hand, pl_vid, pl_scale, pl_emo_id, pl_emotok, pl_text, pl_ctext, pl_table;
     // Cached graphs of the step loop, by loop key (ls_sample.cpp: loop_key holds everything a captured loop bakes in besides device
     // addresses, the batch and its step plan included).  At most kGraphCacheMax entries: a plain call whose key is missing drops them
@@ -211,6 +208,8 @@ int run_window_loop(ls_handle* h, const ls_sample_args* a, bool resident_inpaint
 inline float* x_plane(const ls_handle* h, int k) { return (k & 1) ? h->xb.f() : h->xa.f(); }      // x ahead of executed step k (xa / xb ping-pong)
 // ---- defined in ls_chain_plan.cpp (host only): slot -> clip, windows per slot, clips per window of a ragged long-form call
 void long_plan_drop(int B, int AL, const int64_t* lengths, std::vector<int>& row, std::vector<int>& wins, std::vector<int>& bw);
+// ... and the strided copies that feed a session's rings, five ints each: first slot, slots, ring position, offset into the take, samples
+void feed_copies(int S, int R, const int* pos, const long long* from, const int* take, std::vector<int>& copies);
 
 // copy a caller buffer (host or device) into an internal device buffer
 inline int ingest(ls_handle* h, DevBuf& d, const void* src, size_t bytes, int on_device) {
@@ -229,9 +228,8 @@ inline int egress(ls_handle* h, void* dst, const void* src, size_t bytes, int on
     return LS_OK;
 }
 
-// a call that replaces the handle's prepared conditioning ends a running stream (ls_long_stream_push then reports LS_ESTATE)
-inline void end_stream(ls_handle* h) {        // ... and a running session pool
-    if (h->st_state == ls_handle::kStreamOpen) h->st_state = ls_handle::kStreamReplaced;
+// a call that replaces the handle's prepared conditioning ends a running session, stream or pool (its next push reports LS_ESTATE)
+inline void end_stream(ls_handle* h) {
     if (h->pl_state == ls_handle::kStreamOpen) h->pl_state = ls_handle::kStreamReplaced;
 }
 inline void end_chain(ls_handle* h) { h->lg_prepared = false; end_stream(h); }       // ls_prepare: a long-form call's conditioning goes too

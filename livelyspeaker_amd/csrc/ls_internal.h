@@ -337,13 +337,11 @@ hipError_t launch_edit_scatter(const EditArgs& a, int B, hipStream_t st);
 // that sample index is >= lengths[row] (nothing beyond a clip's length is read).  audio [.][L], clips [n][AL].
 hipError_t launch_long_gather_clips(const float* audio, const int* table, const int* lengths, float* clips, int n, int AL, long long L,
                                     int stride, hipStream_t st);
-// One window of a stream (ls_long_stream_push): clips[b][i] = ring[b][(pos0 + i) % R] for i < n_valid, 0 behind.  ring [B][R] with
-// R % 4 == 0 and AL <= R, 0 <= pos0 < R, 0 <= n_valid <= AL; clips [B][AL].  Both 16-byte aligned.
-hipError_t launch_stream_gather(const float* ring, float* clips, int B, int AL, int R, int pos0, int n_valid, hipStream_t st);
-// ---- one round of a session pool (ls_long_pool_push; ls_chain.hip).  table [A][kPoolRow] on the device, one row per active slot in
-// ascending slot order: {slot, ring position of the window's first sample, valid samples of the window, first new frame f0, frame
-// offset of the slot in the call's output}.  launch_pool_gather: row r of the compact buffers <- slot table[r][0] of the per-slot
-// stores: the window's audio (k_stream_gather's arithmetic), the hand-off poses hand [S][JF][n_pre] as the prefix rows of feat_u and
+// ---- one round of a streaming session (ls_long_pool_push, ls_long_stream_push; ls_chain.hip).  table [A][kPoolRow] on the device, one
+// row per active slot in ascending slot order: {slot, ring position pos0 of the window's first sample, valid samples of the window,
+// first new frame f0, frame offset of the slot in the call's output}.  launch_pool_gather: row r of the compact buffers <- slot
+// table[r][0] of the per-slot stores: the window's audio (clips[r][i] = ring[slot][(pos0 + i) % R] for i < valid, 0 behind; R % 4 == 0,
+// AL <= R, both 16-byte aligned), the hand-off poses hand [S][JF][n_pre] as the prefix rows of feat_u and
 // prefix columns of origin_x, and the held conditioning (vid, scale; emo_tok_s / text_s [S][kD] into emo_tok / text, each pair nullable).
 // launch_pool_scatter: row r of prev (internal layout) -> frames [S][JF][T_total] of its slot at its frame offset, from frame f0 on,
 // and its last n_pre poses -> hand.  The launchers check the geometry; the table's entries are the caller's to check before upload.

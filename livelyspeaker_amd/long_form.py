@@ -25,7 +25,7 @@ for bit.
 
 ``open_stream`` is the online form of the same chain: audio arrives in chunks of any size, a window runs as soon as its last sample
 is there, and the frames of all pushes are bit for bit ``sample_long``'s for the concatenated audio (``ls_long_stream_open`` /
-``ls_long_stream_push``; a per-clip audio ring and ``k_stream_gather``).
+``ls_long_stream_push``; the session pool's engine with every slot fed alike).
 
 ``open_pool`` is a pool of such streams on one engine: clips join and leave slot by slot and are fed at their own rates, and a push
 runs the windows that are complete in rounds, each one sampling call on the slots that have one (``pool_plan``; ``ls_long_pool_*``,
@@ -297,7 +297,42 @@ def sample_long(diffusion, model, audio, seed_poses, vid_indices, scale, emo=Non
     return (timeline, gd._as_tensor(windows, out_dev)) if return_windows else timeline
 
 
-class LongStream:
+class _Session:
+    """What ``LongStream`` and ``LongPool`` share: the ``with`` form, the engine bound at the first engine call (``_open(eng)`` opens the
+    session on it), and the refusals of the held conditioning a push passes."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self._closed = True        # leaving the block ends the session; the windows a close() would still run are not run
+        return False
+
+    def _engine(self):
+        if self._eng is None:
+            eng = _bind_engine(self._diffusion, self._rag)
+            if self._sag is not None and self._sag.engine().device != eng.device:
+                raise ValueError(f"the SAG decoder runs on cuda:{self._sag.engine().device}, the RAG model on cuda:{eng.device}")
+            self._open(eng)
+            self._eng = eng
+        return self._eng
+
+    def _check_held(self, emo, text_features, rows):
+        """``emo`` [rows] (BEAT) and ``text_features`` [rows, latent_dim] (with ``sag=``), each None or one row per clip."""
+        rag = self._rag
+        if emo is not None:
+            if rag.n_prefix_tokens != 2:
+                raise ValueError("emo is a BEAT conditioning; the TED model takes none")
+            if _shape(emo) != (rows,):
+                raise ValueError(f"emo must be [{rows}], got {list(emo.shape)}")
+        if text_features is not None:
+            if self._sag is None:
+                raise ValueError("text_features without sag: the SAG decoder turns them into every window's init_image")
+            if _shape(text_features) != (rows, rag.latent_dim):
+                raise ValueError(f"text_features must be {[rows, rag.latent_dim]}, got {list(text_features.shape)}")
+
+
+class LongStream(_Session):
     """A running ``open_stream`` session; see there.  ``samples_in``, ``windows_run``, ``frames_out``: host ints."""
 
     def __init__(self, diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag):
@@ -325,21 +360,8 @@ class LongStream:
         self._last_dev = th.device("cpu")
         self.samples_in = self.windows_run = self.frames_out = 0
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self._closed = True        # leaving the block ends the session; the windows a close() would still run are not run
-        return False
-
-    def _engine(self):
-        if self._eng is None:
-            eng = _bind_engine(self._diffusion, self._rag)
-            if self._sag is not None and self._sag.engine().device != eng.device:
-                raise ValueError(f"the SAG decoder runs on cuda:{self._sag.engine().device}, the RAG model on cuda:{eng.device}")
-            eng.long_stream_open(*self._cond)
-            self._eng = eng
-        return self._eng
+    def _open(self, eng):
+        eng.long_stream_open(*self._cond)
 
     def _feed(self, chunk, emo, text_features, closing):
         if self._closed:
@@ -348,16 +370,7 @@ class LongStream:
         chunk, emo, text_features = _as_tensors(chunk, emo, text_features)
         if chunk.ndim != 2 or int(chunk.shape[0]) != B:
             raise ValueError(f"audio_chunk must be [{B}, n], got {list(chunk.shape)}")
-        if emo is not None:
-            if rag.n_prefix_tokens != 2:
-                raise ValueError("emo is a BEAT conditioning; the TED model takes none")
-            if _shape(emo) != (B,):
-                raise ValueError(f"emo must be [{B}], got {list(emo.shape)}")
-        if text_features is not None:
-            if self._sag is None:
-                raise ValueError("text_features without sag: the SAG decoder turns them into every window's init_image")
-            if _shape(text_features) != (B, rag.latent_dim):
-                raise ValueError(f"text_features must be {[B, rag.latent_dim]}, got {list(text_features.shape)}")
+        self._check_held(emo, text_features, B)
         n = int(chunk.shape[1])
         first, k = _lib.long_stream_plan(self.samples_in, n, int(rag.audio_len), closing)
         emo = emo if emo is not None else self._emo
@@ -419,10 +432,13 @@ def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, samp
 
     Noise (``diffusion.noise_source``): ``'torch_cpu'`` draws a window's tape at the push that runs it, in window order
     (``RefDraws.windows`` per push; the one-window ``tape_segment_bytes`` bound applies); ``'philox'`` takes its key here, once, and
-    window w draws at ``sample_offset + b + (w << 48)``; ``'torch_device'`` is refused.
+    window w draws at ``sample_offset + b + (w << 48)`` -- a key must not repeat, so a stream runs at most 2^16 windows under
+    ``'philox'`` (about 36 hours of audio; the push that would run the next one raises ``_lib.EngineError``); ``'torch_device'`` is
+    refused.
 
-    The engine keeps a per-clip ring of ``audio_len + 32000`` samples, one gathered window and one window's features: device memory
-    does not grow with the stream (``ls_long_stream_info``).  The engine is bound at the first push; a ``ddim_sample_loop``,
+    The engine runs a stream as an ``open_pool`` session whose B slots are joined at the open and fed alike: per clip a ring of
+    ``audio_len + 32000`` samples, the hand-off poses and the held conditioning, plus one gathered window and one window's features.
+    Device memory does not grow with the stream (``ls_long_stream_info``).  The engine is bound at the first push; a ``ddim_sample_loop``,
     ``sample_long`` or ``edit_long`` on the same model afterwards replaces its conditioning and ends the stream (the next push raises
     ``_lib.EngineError``).
 
@@ -445,7 +461,7 @@ def pool_plan(samples_in, windows_run, new, closing, open, cfg):
     return _lib.long_pool_plan(samples_in, windows_run, new, closing, open, int(cfg.audio_len))
 
 
-class LongPool:
+class LongPool(_Session):
     """A running ``open_pool`` session; see there.  ``slots``: per-slot host arrays ``samples_in``, ``windows_run``, ``frames_out``, ``open``."""
 
     def __init__(self, diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag):
@@ -478,21 +494,8 @@ class LongPool:
     def slots(self):
         return {k: v.copy() for k, v in self._state.items()}
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self._closed = True        # leaving the block ends the session; the windows a close() would still run are not run
-        return False
-
-    def _engine(self):
-        if self._eng is None:
-            eng = _bind_engine(self._diffusion, self._rag)
-            if self._sag is not None and self._sag.engine().device != eng.device:
-                raise ValueError(f"the SAG decoder runs on cuda:{self._sag.engine().device}, the RAG model on cuda:{eng.device}")
-            eng.long_pool_open(self._S)
-            self._eng = eng
-        return self._eng
+    def _open(self, eng):
+        eng.long_pool_open(self._S)
 
     def _refresh(self):
         info = self._eng.long_pool_info()
@@ -546,16 +549,7 @@ class LongPool:
             raise ValueError(f"audio must be [{S}, n_max], got {list(audio.shape)}")
         n_max = int(audio.shape[1])
         lens = _lib.host_lengths(lengths, S, 0, n_max, "lengths").astype(np.int64)
-        if emo is not None:
-            if rag.n_prefix_tokens != 2:
-                raise ValueError("emo is a BEAT conditioning; the TED model takes none")
-            if _shape(emo) != (S,):
-                raise ValueError(f"emo must be [{S}], got {list(emo.shape)}")
-        if text_features is not None:
-            if self._sag is None:
-                raise ValueError("text_features without sag: the SAG decoder turns them into every window's init_image")
-            if _shape(text_features) != (S, rag.latent_dim):
-                raise ValueError(f"text_features must be {[S, rag.latent_dim]}, got {list(text_features.shape)}")
+        self._check_held(emo, text_features, S)
         st = self._state
         if given is None:                               # what is passed holds for every open slot
             given = st["open"].copy()

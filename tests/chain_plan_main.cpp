@@ -2,6 +2,7 @@
 // it links that unit alone, is built with the host sanitizers by tests/test_chain_plan_host.py, and exits non-zero on a wrong answer.
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 
 #include "ls_hip.h"
@@ -123,10 +124,54 @@ static void test_edit_plan() {
     CHECK(ls_long_edit_plan(0, W, T, P, lo, hi, flags, &n) == LS_EINVAL);
 }
 
-int main() {
+// feed_copies is internal to the library (declared in csrc/ls_handle.h, which needs HIP); its five ints per copy are
+// {first slot, slots, ring position, offset into the take, samples}
+namespace ls { void feed_copies(int S, int R, const int* pos, const long long* from, const int* take, std::vector<int>& copies); }
+using Ints = std::vector<int>;
+static Ints feed(int R, const Ints& pos, const Ints& take, const std::vector<long long>& from = {}) {
+    const std::vector<long long> zero(pos.size(), 0);
+    Ints copies{-1, -1};
+    ls::feed_copies((int)pos.size(), R, pos.data(), (from.empty() ? zero : from).data(), take.data(), copies);
+    return copies;
+}
+
+static void test_feed_copies() {
+    const int R = 68268;
+    CHECK(feed(R, {5}, {100}) == (Ints{0, 1, 5, 0, 100}));                                      // S = 1
+    CHECK(feed(R, {5}, {0}).empty() && feed(R, {5, 5, 9}, {0, 0, 0}).empty());                  // nothing to take: no copy, the output is cleared
+    CHECK(feed(R, {7, 7, 7, 7}, {40, 40, 40, 40}) == (Ints{0, 4, 7, 0, 40}));                   // a stream: one run whatever its batch
+    CHECK(feed(R, {7, 3, 3}, {40, 9, 9}) == (Ints{0, 1, 7, 0, 40, 1, 2, 3, 0, 9}));             // a run that ends at the last slot
+    CHECK(feed(R, {3, 3, 3}, {9, 0, 9}) == (Ints{0, 1, 3, 0, 9, 2, 1, 3, 0, 9}));               // an idle slot splits what it stands between
+    CHECK(feed(R, {3, 3}, {9, 8}) == (Ints{0, 1, 3, 0, 9, 1, 1, 3, 0, 8}));
+    CHECK(feed(R, {3, 3}, {9, 9}, {0, 4}) == (Ints{0, 1, 3, 0, 9, 1, 1, 3, 0, 9}));             // alike in the ring, not in the chunk: two copies
+    CHECK(feed(R, {R - 10, R - 10}, {10, 10}) == (Ints{0, 2, R - 10, 0, 10}));                  // a run that ends exactly at R does not wrap
+    CHECK(feed(R, {R - 10, R - 10}, {11, 11}) == (Ints{0, 2, R - 10, 0, 10, 0, 2, 0, 10, 1}));  // one sample more does
+    CHECK(feed(R, {R - 1}, {R}) == (Ints{0, 1, R - 1, 0, 1, 0, 1, 0, 1, R - 1}));               // a whole ring from its last position
+    CHECK(feed(R, {0}, {R}) == (Ints{0, 1, 0, 0, R}));
+}
+
+// with arguments: R, then per case S, S ring positions, S takes -> one line of feed_copies' ints per case (tests/test_chain_plan_host.py)
+static int print_feed_copies(int argc, char** argv) {
+    const int R = std::atoi(argv[1]);
+    for (int i = 2; i < argc;) {
+        const int S = std::atoi(argv[i++]);
+        if (S < 1 || i + 2 * S > argc) return 2;
+        Ints pos, take;
+        for (int s = 0; s < S; ++s) pos.push_back(std::atoi(argv[i + s]));
+        for (int s = 0; s < S; ++s) take.push_back(std::atoi(argv[i + S + s]));
+        i += 2 * S;
+        for (int v : feed(R, pos, take)) std::printf("%d ", v);
+        std::printf("\n");
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1) return print_feed_copies(argc, argv);
     test_stream_plan();
     test_plan_drop();
     test_edit_plan();
+    test_feed_copies();
     if (failures) std::fprintf(stderr, "%d checks failed\n", failures);
     return failures ? 1 : 0;
 }

@@ -101,16 +101,19 @@ def _log(AL):
 
 
 @functools.lru_cache(maxsize=None)
-def _oracle(ds, schedule, seed):
+def _oracle(ds, schedule, seed, log=None):
     """One public sampling call per logged round, at its batch: the active slots' windows (zero-padded behind a speaker's last sample),
-    their previous result's last four frames (or seed poses) as the origin_x prefix, their speaker ids, scales and (BEAT) emotion ids."""
+    their previous result's last four frames (or seed poses) as the origin_x prefix, their speaker ids, scales and (BEAT) emotion ids.
+    ``log``: the rounds as a tuple of tuples of rows (default: the staggered schedule's).  Under ``'philox'`` round q draws at the
+    pool's key: ``sample_offset = q << 48``."""
     parts, y = _parts(ds, schedule), _speakers(ds)
     cfg, model, diffusion, sampler, skip, _ = parts
-    log = _log(cfg.audio_len)
+    log = _log(cfg.audio_len) if log is None else log
     loop = diffusion.ddim_sample_loop if sampler == "ddim" else diffusion.p_sample_loop
     last, frames = {}, {k: [] for k in SPEAKERS}
     torch.manual_seed(seed)
-    for rows in log:
+    for q, rows in enumerate(log):
+        diffusion.sample_offset = q << 48
         idx = torch.tensor([SPEAKERS[k] for k, _, _ in rows], device=DEV)
         shape = (len(rows), cfg.njoints, cfg.nfeats, T)
         origin_x = torch.zeros(shape, device=DEV)
@@ -126,7 +129,8 @@ def _oracle(ds, schedule, seed):
         for i, (k, w, _) in enumerate(rows):
             last[k] = x[i]
             frames[k].append(x[i] if w == 0 else x[i, :, :, cfg.n_pre_seq:])
-    return {k: torch.cat(v, dim=2) for k, v in frames.items()}, [len(r) for r in log]
+    diffusion.sample_offset = 0
+    return {k: torch.cat(v, dim=2) for k, v in frames.items() if v}, [len(r) for r in log]
 
 
 @pytest.mark.parametrize("schedule", ["ddim", "ddpm"])

@@ -1,5 +1,5 @@
-"""Streaming long-form synthesis on the GPU (long_form.open_stream -> ls_long_stream_open / ls_long_stream_push, k_stream_gather in
-csrc/ls_chain.hip).
+"""Streaming long-form synthesis on the GPU (long_form.open_stream -> ls_long_stream_open / ls_long_stream_push, the session of
+csrc/ls_chain_api.cpp with all slots fed alike).
 
 The contract: the frames of all pushes and the close, concatenated, are BIT FOR BIT the timeline ``sample_long`` gives for the concatenated
 audio (same model, schedule, conditioning and seed; no n_windows, no audio_lengths), whatever the chunking.  B = 3 (odd: per-clip
