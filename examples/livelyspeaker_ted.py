@@ -11,7 +11,7 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py [batch] --from-motion [--raw-poses]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N
     python examples/livelyspeaker_ted.py --long-seconds A,B,... [--drop-finished]
-    python examples/livelyspeaker_ted.py [batch] --long-seconds N --edit-frames LO,HI [--edit-joints J0,J1,...]
+    python examples/livelyspeaker_ted.py [batch] --long-seconds N --edit-frames LO,HI [--edit-joints J0,J1,...] [--edit-text [--clip-text]]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --stream-chunk SECONDS
     python examples/livelyspeaker_ted.py --pool SPEAKERS
     python examples/livelyspeaker_ted.py [batch] --clip-text
@@ -34,6 +34,9 @@ clip-windows that saves.
 --edit-frames LO,HI (with --long-seconds N) then EDITS the timeline it has just made: the frames [LO, HI) -- with --edit-joints only
 the listed joints (0..8) -- are re-synthesised from the existing motion (long_form.edit_long: the inpainting branch on the windows the
 range touches, 20 refinement steps each), everything else is kept bit for bit, and the line printed says how many of the W windows ran.
+--edit-text makes that edit SCRIPT-GUIDED (edit_long(sag=, text_features=)): the edited frames start from the SAG decoder's output for
+one text feature [B, 512] -- a synthetic stand-in, or with --clip-text a sentence of synthetic tokens through CLIPTextEncoder -- and the
+kept ones from the existing motion; it prints how far the edited frames moved from the unscripted edit with the same seed.
 --stream-chunk SECONDS (with --long-seconds N) feeds the same waveform to a STREAM instead, SECONDS of audio at a time
 (long_form.open_stream: push() returns a window's new frames as soon as the window's audio is complete, close() the zero-padded rest);
 it prints when each window's frames appeared and checks that the frames, concatenated, are bit for bit the timeline of the one call.
@@ -187,6 +190,13 @@ def main():
                 raise SystemExit("--edit-joints goes with --edit-frames")
             edit["joints"] = [int(v) for v in sys.argv[j + 1].split(",") if v]
             del sys.argv[j:j + 2]
+        if "--edit-text" in sys.argv:
+            sys.argv.remove("--edit-text")
+            if edit is None:
+                raise SystemExit("--edit-text goes with --edit-frames")
+            edit["text"] = "clip" if "--clip-text" in sys.argv else "synthetic"
+            if edit["text"] == "clip":
+                sys.argv.remove("--clip-text")
         stream_chunk = None
         if "--stream-chunk" in sys.argv:
             j = sys.argv.index("--stream-chunk")
@@ -356,7 +366,7 @@ def main_long(B, seconds, noise_source, edit=None, stream_chunk=None):
           f"not quality)")
     assert tuple(scored["pose"].shape) == (B, n_frames, 10, 3) and bool(torch.isfinite(scored["pose"]).all())
     if edit is not None:
-        edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit)
+        edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit, sag_decoder)
     if stream_chunk is not None:
         stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, stream_chunk)
 
@@ -432,9 +442,10 @@ def main_pool(speakers, noise_source, tick_seconds=0.5):
     print(f"{speakers} speakers, {sum(frames)} frames ({noise_source}) in {(time.perf_counter() - t0) * 1e3:.0f} ms over {tick} pushes on one engine")
 
 
-def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit):
+def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit, sag_decoder=None):
     """Re-synthesise the frames [lo, hi) of the timeline main_long made (on the listed joints, or all): only the windows that own a
-    frame of the range are sampled, starting from the existing motion."""
+    frame of the range are sampled, starting from the existing motion -- and with edit['text'] from the SAG decoder's output for one
+    script on the edited elements."""
     import numpy as np
     lo, hi = edit["frames"]
     joints = None
@@ -453,6 +464,25 @@ def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit)
     changed = int((edited != timeline).sum())
     print(f"edit of frames [{lo}, {hi}){'' if joints is None else ' on joints ' + str(edit['joints'])}: {len(ran)} of {W} windows ran "
           f"({ran}) in {dt * 1e3:.1f} ms; {changed} of {timeline.numel()} values changed, every other one kept bit for bit")
+    if not edit.get("text"):
+        return
+    B = timeline.shape[0]
+    if edit["text"] == "clip":                  # a sentence as clip.tokenize returns it (synthetic tokens) -> CLIPTextEncoder on the GPU
+        from livelyspeaker_amd.motionclip import get_clip
+        clip_model = get_clip({k: torch.from_numpy(v) for k, v in synth.synth_clip_text_state().items()}, "cuda:0")
+        z = clip_model.encode_text(torch.from_numpy(synth.synth_clip_tokens([12] * B))).float()
+    else:
+        z = torch.from_numpy(synth.make_text_features(B, seed=synth.SEED_COND + 3000)).cuda()
+    torch.manual_seed(377)                      # the seed of the unscripted edit: the same draws
+    t0 = time.perf_counter()
+    scripted = long_form.edit_long(diffusion, model, timeline, (lo, hi), audio, y["seed_poses"], y["vid_indices"], y["scale"], joints=joints,
+                                   sampler="ddim", skip_timesteps=80, sag=sag_decoder, text_features=z)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert torch.equal(scripted[kept], timeline[kept]) and bool(torch.isfinite(scripted).all())
+    moved = (scripted - edited)[~kept].abs()
+    print(f"the same edit guided by one script ({edit['text']} text feature): {dt * 1e3:.1f} ms; the edited values moved by "
+          f"{float(moved.mean()):.4f} on average (max {float(moved.max()):.4f}) from the unscripted edit with the same seed")
 
 
 def main_long_ragged(seconds, noise_source, drop_finished=False):

@@ -389,7 +389,7 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a);
  * editable elements of its result are stored into the timeline and nothing else of the timeline is written.  A window behind the last
  * one that ran is not resampled even where its conditioning frames changed (widen the range to have it resampled), and a clip whose
  * range misses a running window runs in it with every element kept.
- * Not built: handles of ls_long_prepare_ragged, a SAG decoder, PLMS, const_noise, dump_steps, encoding only the edited windows' audio. */
+ * Not built: handles of ls_long_prepare_ragged, PLMS, const_noise, dump_steps, encoding only the edited windows' audio. */
 typedef struct ls_long_edit_args {
     int32_t sampler;            /* LS_SAMPLER_DDPM | LS_SAMPLER_DDIM                                                  */
     int32_t noise_mode;         /* LS_NOISE_TAPE | LS_NOISE_PHILOX                                                    */
@@ -422,6 +422,22 @@ typedef struct ls_long_edit_args {
 int ls_long_edit_plan(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const int32_t* lo, const int32_t* hi,
                       int32_t* window_flags, int32_t* n_out);
 int ls_long_edit(ls_handle* h, const ls_long_edit_args* a);
+
+/* ---- ls_long_edit with the LivelySpeaker start: a script-guided edit.  The windows, their order, inpaint_mask / inpainted_motion /
+ * origin_x, the draws (the decoder draws nothing) and the scatter of the editable elements are ls_long_edit's.  What changes is the
+ * image a window that runs starts from: with sag_out = decoder(x = origin_x_w, z = text_features[w], mask = ones) [B, J, F, T],
+ *     init_w = editable ? sag_out : the window's slice of the timeline
+ * is ls_sample's init_image at EVERY skip_timesteps >= 0 (at 0: q_sample(init_w, n_steps - 1, x_T), gaussian_diffusion.py:709-716, as
+ * in ls_long_sample with sag).  origin_x_w holds the first n_pre_seq frames of the slice as the earlier windows of this call left the
+ * timeline (window 0: the seed poses), so the decoder of window w + 1 sees what window w has just written.  A clip whose range misses
+ * a running window starts from its slice there (its decoder output is unused), and with `channels` only the selected channels start
+ * from the decoder.  text_features is [W, B, latent_dim], W the prepared windows; rows of windows that do not run are not read; a
+ * host array (device iff a->on_device) is uploaded once per call.  Per window: k_edit_gather, the decoder on its own stream, ordered
+ * by events, k_edit_start (ls_chain.hip), the loop, k_edit_scatter; one wait at the end; the captured loop is the one ls_long_edit
+ * with the same arguments captures.  sag == NULL and text_features == NULL: ls_long_edit.  One without the other: LS_EINVAL, ahead of
+ * any launch, as is everything ls_long_edit refuses.
+ * Not built: what ls_long_edit does not build; the SAG encoder as the source of text_features. */
+int ls_long_edit_sag(ls_handle* h, const ls_long_edit_args* a, struct ls_sag* sag, const float* text_features);
 
 /* ---- Streaming long-form synthesis: the chain of ls_long_sample, fed audio in chunks of any size.  Window w runs as soon as its last
  * sample has arrived (audio_stride * w + audio_len <= samples fed), conditioned on the last n_pre_seq poses of window w - 1 (window 0:

@@ -215,7 +215,7 @@ class LsEvalConfig(C.Structure):
 
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
-           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_long_pool_plan", "ls_long_pool_open", "ls_long_pool_join", "ls_long_pool_push", "ls_long_pool_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
+           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_edit_sag", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_long_pool_plan", "ls_long_pool_open", "ls_long_pool_join", "ls_long_pool_push", "ls_long_pool_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
@@ -290,6 +290,7 @@ def load_library(build_if_missing: bool = True):
     lib.ls_long_prepare_ragged.argtypes = [C.c_void_p, C.POINTER(LsLongCond), C.c_void_p]
     lib.ls_long_plan_drop.argtypes = [C.c_int32, C.c_int32, C.c_void_p, c_i32p, c_i32p, c_i32p, C.c_int32, c_i32p]
     lib.ls_long_edit.argtypes = [C.c_void_p, C.POINTER(LsLongEditArgs)]
+    lib.ls_long_edit_sag.argtypes = [C.c_void_p, C.POINTER(LsLongEditArgs), C.c_void_p, C.c_void_p]
     lib.ls_long_edit_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p, c_i32p, c_i32p]
     lib.ls_long_stream_plan.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_i64p, c_i64p]
     lib.ls_long_stream_open.argtypes = [C.c_void_p, C.POINTER(LsLongStreamCond)]
@@ -975,13 +976,17 @@ class Engine(_Handle):
 
     def long_edit(self, timeline, frame_lo, frame_hi, channels=None, sampler=LS_SAMPLER_DDIM, x_init=None, eps_tape=None, noise_tape=None,
                   inpaint_noise=None, inpaint_noised=False, skip_timesteps=0, eta=0.0, philox_seed=None, sample_offset=0, use_graph=True,
-                  clip_denoised=False, two_pass_always=False, device_out=False, return_windows=False):
+                  clip_denoised=False, two_pass_always=False, device_out=False, return_windows=False, sag=None, text_features=None):
         """Re-synthesise the frames [frame_lo[b], frame_hi[b]) (host int [B]) of ``timeline`` [B, J, F, T + (W-1)(T-n_pre)] on the
         channels ``channels`` (host bytes [B, J*F]; None = all) with the conditioning of the last ``long_prepare`` (ls_long_edit): only
         the windows of ``long_edit_plan`` run, everything else is kept bit for bit.  TAPE mode takes the draws of those We windows,
         ascending: ``x_init`` [We, B, J, F, T], ``eps_tape`` [We, n_exec, 2, B, D], ``noise_tape`` and (``inpaint_noised``)
         ``inpaint_noise`` [We, n_exec, B, J, F, T]; PHILOX mode ``philox_seed``.  Returns (a new timeline, the windows that ran) and, with
-        ``return_windows``, their raw samples [We, B, J, F, T]; the caller's timeline is not written."""
+        ``return_windows``, their raw samples [We, B, J, F, T]; the caller's timeline is not written.
+
+        ``sag`` (a SagEngine) with ``text_features`` [W, B, D]: the scripted edit (ls_long_edit_sag) -- every window that runs starts
+        from the decoder's output on its editable elements and from its slice elsewhere, at every ``skip_timesteps``; rows of
+        ``text_features`` for windows that do not run are not read.  One without the other is the engine's to refuse."""
         B, W, D = self.batch, self.n_windows, self.D
         npre = int(self.cfg.n_pre_seq)
         n_frames = self.T + (W - 1) * (self.T - npre)
@@ -996,7 +1001,7 @@ class Engine(_Handle):
         except ValueError:
             plan = []
         We = len(plan)
-        m = self._marshal([timeline, x_init, eps_tape, noise_tape, inpaint_noise], device_out)
+        m = self._marshal([timeline, x_init, eps_tape, noise_tape, inpaint_noise, text_features], device_out)
         a = LsLongEditArgs()
         n_exec = self._chain_sampler(a, m, sampler, skip_timesteps, use_graph, clip_denoised, two_pass_always, eta)
         a.inpaint_noised = int(bool(inpaint_noised))
@@ -1019,8 +1024,12 @@ class Engine(_Handle):
             windows, a.windows = m.out((We,) + self._xshape())
         ran, n_ran = np.full(max(W, 1), -1, np.int32), C.c_int32(0)
         a.windows_run, a.windows_capacity, a.n_windows_run = ran.ctypes.data_as(c_i32p), W, C.pointer(n_ran)
+        text = m.f32(text_features, (W, B, D))
         m.ready()
-        self._check(self.lib.ls_long_edit(self.h, C.byref(a)), "ls_long_edit")
+        if sag is None and text_features is None:
+            self._check(self.lib.ls_long_edit(self.h, C.byref(a)), "ls_long_edit")
+        else:
+            self._check(self.lib.ls_long_edit_sag(self.h, C.byref(a), None if sag is None else sag.h, text), "ls_long_edit_sag")
         ran = [int(w) for w in ran[:int(n_ran.value)]]
         assert ran == plan, (ran, plan)
         return (out, ran, windows) if return_windows else (out, ran)

@@ -13,6 +13,7 @@
 // k_edit_gather / k_edit_scatter (further down) are the same cut and stitch for a timeline EDIT (ls_long_edit): a window's frames leave
 // the timeline as the loop's inpainting inputs and its editable elements return.  Algorithmic bytes per clip (fp32): gather 15.7 KB TED,
 // 163 KB BEAT (with the init plane); scatter at most 11.0 KB TED, 115 KB BEAT (with the raw window); the terms are spelled out at the kernels.
+// k_edit_start puts the SAG decoder's output under the editable elements of the init plane (ls_long_edit_sag): at most 7.4 KB TED, 77 KB BEAT.
 // A streaming SESSION (ls_long_pool_push; ls_long_stream_push: the pool whose slots move together) keeps the hand-off per slot:
 // k_pool_gather and k_pool_scatter (at the end) move one round's active slots -- a window of audio out of each slot's circular ring,
 // its hand-off poses, its held conditioning -- into and out of the compact rows a sampling call at that batch reads.
@@ -140,6 +141,23 @@ __global__ __launch_bounds__(256) void k_edit_scatter(const EditArgs a) {
     }
 }
 
+// The start of a SCRIPTED edit window (ls_long_edit_sag): init = where(keep, slice, decoder output).  k_edit_gather has left the slice
+// in init; this stores sag_out over it exactly on the editable elements, so a kept element is never touched.  Both planes are in the
+// reference layout [B][JF][T]: no tile, the frame axis innermost in both, one writer per element, no atomics.
+// Algorithmic bytes per clip (fp32): read and write the editable elements (at most (T - n_pre)*JF each, window 0: T*JF) + JF channel
+// bytes + 8: at most 7.4 KB TED, 77 KB BEAT.
+__global__ __launch_bounds__(256) void k_edit_start(const EditArgs a, const float* __restrict__ sag_out) {
+    const int b = blockIdx.x, tid = threadIdx.x, JF = a.JF, T = a.T;
+    const int lo = a.range[2 * b], hi = a.range[2 * b + 1];
+    const unsigned char* ch = a.chan + (size_t)b * JF;
+    const float* src = sag_out + (size_t)b * JF * T;
+    float* init = a.init + (size_t)b * JF * T;
+    for (int i = tid; i < JF * T; i += 256) {
+        const int c = i / T, f = i - c * T;
+        if (edit_editable(a, lo, hi, ch[c] != 0, f)) init[i] = src[i];
+    }
+}
+
 static bool edit_args_ok(const EditArgs& a, int B, int rows) {
     const size_t lds = (size_t)rows * (a.JF | 1) * sizeof(float);
     return B >= 1 && lds <= 64 * 1024 && a.n_pre >= 1 && a.n_pre <= a.T && a.w >= 0 && (long long)a.w * (a.T - a.n_pre) + a.T <= a.T_total &&
@@ -149,6 +167,11 @@ hipError_t launch_edit_gather(const EditArgs& a, int B, hipStream_t st) {
     const int rows = a.T + (a.w == 0 ? a.n_pre : 0);
     if (!edit_args_ok(a, B, rows) || a.KPP <= a.JF || !a.motion || !a.maskf || !a.feat_u || !a.origin_x || (a.w == 0 && !a.seed)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_edit_gather, dim3(B), dim3(256), (size_t)rows * (a.JF | 1) * sizeof(float), st, a);
+    return hipGetLastError();
+}
+hipError_t launch_edit_start(const EditArgs& a, const float* sag_out, int B, hipStream_t st) {
+    if (!edit_args_ok(a, B, 0) || a.JF < 1 || a.T < 1 || !a.init || !sag_out || sag_out == a.init) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_edit_start, dim3(B), dim3(256), 0, st, a, sag_out);
     return hipGetLastError();
 }
 hipError_t launch_edit_scatter(const EditArgs& a, int B, hipStream_t st) {

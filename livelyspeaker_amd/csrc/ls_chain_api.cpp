@@ -4,7 +4,8 @@
 // start_prepare -> ingest_cond -> size_batch_buffers -> finish_prepare) and one window runner (chain_args -> chain_begin -> run_window
 // per window -> chain_finish); the entries hold what differs: where a window's audio features come from (all windows encoded ahead,
 // packed for clips of different lengths, or one round at a time from the rings of a streaming session's active slots) and what stands
-// around a window (k_chain_window ahead of it, k_edit_gather / k_edit_scatter, or k_pool_gather / k_pool_scatter).  There is one
+// around a window (k_chain_window ahead of it, k_edit_gather / k_edit_scatter -- with k_edit_start behind the decoder of a scripted
+// edit -- or k_pool_gather / k_pool_scatter).  There is one
 // streaming session (session_open -> session_push -> session_push_run): a pool of slots that join and leave, and a stream, which is
 // the pool whose slots were all joined at the open and are fed, given and closed alike.  The host-only plans are ls_chain_plan.cpp.
 #include "ls_handle.h"
@@ -98,6 +99,7 @@ struct ChainCall {
     int n_exec = 0;
     ls_sag* sag = nullptr;          // LivelySpeaker chain: every window starts from the decoder's output (chain_begin)
     void* sag_st = nullptr;
+    float* sag_out = nullptr;       // where the decoder writes [B][JF][T]: the init plane itself, or a scripted edit's plane of its own
     int windows = 0, replays = 0;   // windows run; those served by a graph replay
     bool pair0 = false;             // the first window ran the single-pass form
     bool coop_used = false;         // some window ran the sample-split kernel (a ragged call's plan changes per window)
@@ -113,6 +115,7 @@ struct Window {
     const float *x_init = nullptr, *eps_tape = nullptr, *noise_tape = nullptr, *inpaint_noise = nullptr;      // TAPE: its draws
     bool host_tapes = false;            // ... in host memory: uploaded here, one window at a time (a session's round: the staging does not grow with the call)
     bool resident_inpaint = false;      // a timeline edit: the inpainting planes are on the device (k_edit_gather)
+    const EditArgs* edit_start = nullptr;       // a scripted edit: behind the decode, k_edit_start puts cc.sag_out under the editable elements of the init plane
     CachePolicy policy = kReplace;
     bool first = false;                 // the first window of the call
 };
@@ -146,7 +149,7 @@ int chain_begin(ls_handle* h, ChainCall& cc, ls_sag* sag) {
     cc.sag = sag; cc.sag_st = ls_sag_stream(sag);
     HIPCHK(h, h->lg_init.ensure((size_t)h->B * h->JF * h->T * sizeof(float))); HIPCHK(h, h->lg_mask.ensure((size_t)h->B * h->T));
     HIPCHK(h, hipMemsetAsync(h->lg_mask.p, 1, (size_t)h->B * h->T, h->stream));
-    cc.wa.init_image = h->lg_init.f();
+    cc.wa.init_image = cc.sag_out = h->lg_init.f();
     return LS_OK;
 }
 
@@ -168,9 +171,10 @@ int run_window(ls_handle* h, ChainCall& cc, const Window& win) {
         HIPCHK(h, hipMemcpyAsync(h->emo_tok.p, win.emo_tok, (size_t)Bw * kD * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (cc.sag) {       // the decoder runs on its own handle's stream, ordered behind the hand-off and ahead of the loop by events
         if (ls_stream_order(dev, st, cc.sag_st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
-        if (ls_sag_decode_async(cc.sag, Bw, h->origin_x.f(), win.text, static_cast<const unsigned char*>(h->lg_mask.p), h->lg_init.f()) != LS_OK)
+        if (ls_sag_decode_async(cc.sag, Bw, h->origin_x.f(), win.text, static_cast<const unsigned char*>(h->lg_mask.p), cc.sag_out) != LS_OK)
             return fail(h, LS_EHIP, "SAG decode of window %lld: %s", win.w, ls_sag_last_error(cc.sag));
         if (ls_stream_order(dev, cc.sag_st, st) != LS_OK) return fail(h, LS_EHIP, "ls_stream_order failed");
+        if (win.edit_start) HIPCHK(h, launch_edit_start(*win.edit_start, cc.sag_out, Bw, st));
     }
     if (cc.tape) {
         wa.x_init = win.x_init; wa.eps_tape = win.eps_tape; wa.noise_tape = win.noise_tape; wa.inpaint_noise = win.inpaint_noise;
@@ -370,7 +374,7 @@ int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_ar
         if (a->sag) {
             cc.sag = a->sag; cc.sag_st = ls_sag_stream(a->sag);
             HIPCHK(h, hipMemsetAsync(h->lg_mask.p, 1, (size_t)S * T, st));
-            cc.wa.init_image = h->lg_init.f();
+            cc.wa.init_image = cc.sag_out = h->lg_init.f();
         }
         if (!od) { HIPCHK(h, h->lg_timeline.ensure(out_bytes)); out = h->lg_timeline.f(); }
         HIPCHK(h, hipMemsetAsync(out, 0, out_bytes, st));      // a slot's row is zero behind its own frames
@@ -759,8 +763,16 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
 // Timeline edit (ls_long_edit_args in ls_hip.h): the window body over the windows of ls_long_edit_plan, with k_edit_gather ahead of a
 // window and k_edit_scatter behind it in place of the hand-off kernel, and the loop run with the inpainting branch on the planes the
 // gather left on the device.  The loop's key holds the inpainting form.  One wait at the end.
-int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) {
+//
+// With a SAG decoder (a scripted edit) the gather always leaves the slice in the init plane, the window body decodes (x = the
+// window's origin_x, z = its text features, mask = ones) into a plane of its own, lg_sag, and k_edit_start stores that plane's
+// editable elements over the init plane behind the decode: the loop starts from q_sample(where(keep, slice, decoder output)) at
+// every skip_timesteps >= 0.  The start's q_sample is enqueued ahead of the captured loop (begin_loop), so the loop's key is the
+// unscripted edit's.  ls_long_edit is this entry with no decoder.
+int ls_long_edit_sag(ls_handle* h, const ls_long_edit_args* a, ls_sag* sag, const float* text_features) {
     if (!h || !a) return fail(h, LS_EINVAL, "ls_long_edit: null argument");
+    if (sag && !text_features) return fail(h, LS_EINVAL, "ls_long_edit_sag: sag without text_features");
+    if (text_features && !sag) return fail(h, LS_EINVAL, "ls_long_edit_sag: text_features without sag");
     if (!h->lg_prepared) return fail(h, LS_ESTATE, "ls_long_edit before ls_long_prepare");
     if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_edit before ls_set_schedule");
     if (h->lg_ragged) return fail(h, LS_EUNSUPPORTED, "ls_long_edit: a handle prepared by ls_long_prepare_ragged is not edited (ragged batches are not built)");
@@ -792,7 +804,7 @@ int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) {
     const bool noised = a->inpaint_noised != 0, beat = h->cfg.n_prefix_tokens == 2;
     if (cc.tape && noised && !a->inpaint_noise) return fail(h, LS_EINVAL, "TAPE mode with inpaint_noised needs inpaint_noise");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = chain_begin(h, cc, nullptr)) != LS_OK) return rc;
+    if ((rc = chain_begin(h, cc, sag)) != LS_OK) return rc;
     hipStream_t st = h->stream;
     const size_t nelem = (size_t)B * JF * T, nx = nelem * sizeof(float);
     const size_t per_e = (size_t)cc.n_exec * 2 * B * kD, per_n = (size_t)cc.n_exec * nelem;      // floats per window: eps tape, noise tape
@@ -806,6 +818,8 @@ int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) {
         xs = h->lg_x.f(); es = h->lg_eps.f(); ns = h->lg_nz.f();
         if (iz) { if ((rc = ingest(h, h->lg_inz, iz, We * per_n * sizeof(float), 0)) != LS_OK) return rc; iz = h->lg_inz.f(); }
     }
+    const float* tx = text_features;        // host text features: one upload per call, as in ls_long_sample
+    if (sag && !od) { if ((rc = ingest(h, h->lg_text, tx, (size_t)W * B * kD * sizeof(float), 0)) != LS_OK) return rc; tx = h->lg_text.f(); }
     float* tl = a->timeline;
     float* wd = a->windows;
     if (!od) {
@@ -813,8 +827,9 @@ int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) {
         tl = h->lg_timeline.f();
         if (wd) { HIPCHK(h, h->lg_windows.ensure(We * nx)); wd = h->lg_windows.f(); }
     }
-    const bool from_image = a->skip_timesteps > 0;
+    const bool from_image = a->skip_timesteps > 0 || sag;
     if (from_image) HIPCHK(h, h->lg_init.ensure(nx));
+    if (sag) { HIPCHK(h, h->lg_sag.ensure(nx)); cc.sag_out = h->lg_sag.f(); }      // the decoder's own plane, sized before the first window
     // the planes k_edit_gather fills are held by address in the captured loop: sized before the first window
     if ((rc = ensure_pinned(h, h->inp_maskf, nx)) != LS_OK || (rc = ensure_pinned(h, h->inp_motion, nx)) != LS_OK) return rc;
     EditArgs ea{};
@@ -832,6 +847,7 @@ int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) {
         win.w = w; win.Bw = B; win.first = e == 0; win.resident_inpaint = true;
         win.featc = h->lg_featc.f() + (size_t)w * B * T * kAudioFeat;
         if (beat) win.emo_tok = h->lg_emotok.f() + (size_t)w * B * kD;
+        if (sag) { win.text = tx + (size_t)w * B * kD; win.edit_start = &ea; }
         if (cc.tape) {
             win.x_init = xs + (size_t)e * nelem; win.eps_tape = es + (size_t)e * per_e; win.noise_tape = ns + (size_t)e * per_n;
             win.inpaint_noise = iz ? iz + (size_t)e * per_n : nullptr;
@@ -847,6 +863,8 @@ int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) {
     if (a->n_windows_run) *a->n_windows_run = We;
     return LS_OK;
 }
+
+int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) { return ls_long_edit_sag(h, a, nullptr, nullptr); }
 
 // Opening a stream (ls_long_stream_cond in ls_hip.h): a session of `batch` slots, every slot joined from the caller's arrays
 int ls_long_stream_open(ls_handle* h, const ls_long_stream_cond* c) {

@@ -127,6 +127,7 @@ struct ls_handle {
     DevBuf lg_audio, lg_clips, lg_featc, lg_featp, lg_emo_ids, lg_emotok, lg_seed;
     DevBuf lg_x, lg_eps, lg_nz, lg_text, lg_init, lg_mask, lg_timeline, lg_windows;
     DevBuf lg_inz, lg_edit_range, lg_edit_chan;     // ls_long_edit: a host caller's re-noise tape; per clip [lo, hi) int32 [B][2] and the channel bytes [B][JF]
+    DevBuf lg_sag;          // ls_long_edit_sag: the SAG decoder's output [B][JF][T] of the window in flight (k_edit_start reads it)
     // a ragged long-form call (ls_long_prepare_ragged): clips held longest-first.  lg_bw[w] clips run window w (slots [0, lg_bw[w]) of
     // every per-clip buffer), lg_off[w] = sum of lg_bw[v], v < w, is window w's offset in the packed stores (lg_featc, the tapes);
     // lg_row [B] on the device maps slot -> the caller's clip; lg_scale_ones = leading slots whose guidance scale is 1.

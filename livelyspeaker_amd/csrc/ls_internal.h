@@ -324,7 +324,9 @@ hipError_t launch_chain_window(const ChainArgs& a, int B, hipStream_t st);
 // of timeline [B][JF][T_total] from frame w * (T - n_pre) and writes what the loop reads: motion and maskf (1 = keep) in the internal
 // layout [B][T][JF], the prefix rows of feat_u / prefix columns of origin_x (w == 0: from seed [B][JF][n_pre]), and the slice itself in
 // the reference layout [B][JF][T] to init (nullable).  launch_edit_scatter stores the editable elements of `sample` (internal layout)
-// into the timeline and the whole sample to window [B][JF][T] (nullable).
+// into the timeline and the whole sample to window [B][JF][T] (nullable).  launch_edit_start (a scripted edit, ls_long_edit_sag) stores
+// the editable elements of sag_out [B][JF][T] (the SAG decoder's output, reference layout) into init, which holds the slice: init =
+// where(keep, slice, sag_out).
 struct EditArgs {
     float* timeline; const float* seed; const int* range; const unsigned char* chan;
     float* motion; float* maskf; float* feat_u; float* origin_x; float* init;      // gather
@@ -332,6 +334,7 @@ struct EditArgs {
     int JF, T, KPP, n_pre, T_total, w;
 };
 hipError_t launch_edit_gather(const EditArgs& a, int B, hipStream_t st);
+hipError_t launch_edit_start(const EditArgs& a, const float* sag_out, int B, hipStream_t st);
 hipError_t launch_edit_scatter(const EditArgs& a, int B, hipStream_t st);
 // One encoder chunk of a ragged long-form call: clips[p][i] = audio[row][w * stride + i] for the n (row, w) pairs of `table`, 0 where
 // that sample index is >= lengths[row] (nothing beyond a clip's length is read).  audio [.][L], clips [n][AL].

@@ -387,7 +387,10 @@ int stage_loop_inputs(ls_handle* h, LoopCall& c) {
     return LS_OK;
 }
 
-// everything a captured loop bakes in besides device addresses (those: ensure_pinned)
+// everything a captured loop bakes in besides device addresses (those: ensure_pinned).  Whether the call has an init_image is NOT
+// among it, at skip_timesteps == 0 or otherwise: x_T and the init image's q_sample are begin_loop's, enqueued ahead of the capture
+// on every path, and the captured chain starts from whatever they left in xa.  A scripted timeline edit (ls_long_edit_sag) at
+// skip_timesteps == 0 counts on this: it replays the loop an unscripted edit with the same arguments captured, and the reverse.
 std::string loop_key(const ls_handle* h, const LoopCall& c) {
     const ls_sample_args* a = c.a;
     char keybuf[256];

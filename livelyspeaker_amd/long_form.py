@@ -21,7 +21,8 @@ its own audio has ended (``plan_drop``; ``ls_long_prepare_ragged``), and window 
 A finished timeline is corrected with ``edit_long``: a frame range per clip (optionally some joints only) is re-synthesised by the
 windows that own one of its frames (``edit_plan``), each through the sampling loop's inpainting branch with the window's slice of the
 timeline as the given motion (``edit_window``; ``ls_long_edit``, ``k_edit_gather`` / ``k_edit_scatter``); everything else is kept bit
-for bit.
+for bit.  With ``sag=`` / ``text_features=`` the edit is script-guided: every window that runs starts from the SAG decoder's output on
+its editable elements (``edit_start``; ``ls_long_edit_sag``, ``k_edit_start``).
 
 ``open_stream`` is the online form of the same chain: audio arrives in chunks of any size, a window runs as soon as its last sample
 is there, and the frames of all pushes are bit for bit ``sample_long``'s for the concatenated audio (``ls_long_stream_open`` /
@@ -720,8 +721,19 @@ def edit_window(timeline, w, ranges, joints, seed_poses, cfg):
     return origin_x, mask, motion
 
 
+def edit_start(motion, mask, sag_out):
+    """The image a window of a SCRIPTED edit starts from, in plain torch on any device: ``where(mask, motion, sag_out)`` -- the
+    existing motion where it is kept, the SAG decoder's output on the editable elements.  ``motion`` and ``mask`` are
+    ``edit_window``'s ``inpainted_motion`` and ``inpainting_mask`` (True = kept), ``sag_out`` is the decoder's ``['output']``, all
+    [B, J, F, T].  A clip that keeps everything starts from its slice, bit for bit.  On the device: ``k_edit_start``."""
+    if _shape(motion) != _shape(mask) or _shape(motion) != _shape(sag_out) or mask.dtype != th.bool:
+        raise ValueError(f"edit_start: motion, mask (bool) and sag_out share one shape, got {list(motion.shape)}, {list(mask.shape)} "
+                         f"of {mask.dtype}, {list(sag_out.shape)}")
+    return th.where(mask, motion, sag_out)
+
+
 def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices, scale, emo=None, joints=None, sampler='ddim',
-              skip_timesteps=0, eta=0.0, clip_denoised=False, encoder_chunk=None, return_windows=False):
+              skip_timesteps=0, eta=0.0, clip_denoised=False, encoder_chunk=None, return_windows=False, sag=None, text_features=None):
     """Re-synthesise a stretch of a timeline ``sample_long`` made: the frames ``frames`` -- one ``(lo, hi)`` pair for all clips or a
     host int array [B, 2], ``lo == hi`` leaves a clip alone -- on the joints ``joints`` (None = all; a bool mask [J] or [B, J]), with
     the conditioning of the ``sample_long`` call (``audio``, ``seed_poses``, ``vid_indices``, ``scale``, ``emo``).  Returns a new
@@ -738,20 +750,40 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
     (tests/test_gpu_long_edit.py; the draws: ``RefDraws.edit_windows``).  ``'philox'``: clip b draws, in window w, the streams of
     ``sample_offset + b + (w << 48)`` -- what ``sample_long`` draws there, whichever other windows run.  ``'torch_device'`` is refused.
 
+    ``sag`` (a ``Decoder_TRANSFORMER``) with ``text_features`` is the SCRIPTED edit -- "re-do these frames, and make them mean this
+    sentence" (the reference's test_LivelySpeaker_ted.py:85-113, on a stretch of a timeline).  Windows, order, ``edit_window``'s
+    inputs, draws (the decoder in eval mode draws nothing) and the write-back are the same; only the image window w starts from
+    changes::
+
+        sag_out = sag({'x': origin_x_w, 'z': text_features[:, w], 'mask': ones[B, T]})['output']
+        init_w  = edit_start(inpainted_motion_w, inpainting_mask_w, sag_out)        # kept: the existing motion; editable: the decoder's
+
+    and ``init_image=init_w`` is passed at EVERY ``skip_timesteps >= 0`` (at 0 the loops use it as ``q_sample(init_image, T - 1,
+    x_T)``, gaussian_diffusion.py:709-716, as ``sample_long(sag=)`` does).  ``origin_x_w`` is ``edit_window``'s, so the decoder of
+    window w + 1 sees the frames window w has just written.  ``text_features`` is [B, W, 512], sized by the timeline's W windows as in
+    ``sample_long`` (entries of windows that do not run are ignored), or [B, 512]: one script for the whole stretch.  A clip whose
+    range misses a running window starts from its slice there; with ``joints`` only the selected joints start from the decoder.  The
+    bitwise contract holds with ``edit_start`` in the loop above (tests/test_gpu_long_edit_sag.py); on the device it is one more
+    kernel per window (``ls_long_edit_sag``; ``k_edit_start``).  One of ``sag`` / ``text_features`` without the other, a wrong
+    shape, a decoder whose geometry is not the RAG model's or that sits on another device: ``ValueError``.
+
     To know, not to be surprised by:
 
     * a window behind the last edited one is NOT resampled, even though its four conditioning frames may have changed; widen the
       range to have it resampled;
     * a clip whose range misses a window that runs for another clip still runs in it, with every element kept; its result is discarded.
 
-    Not built: SAG-driven edits (``sag=`` / ``text_features=``), ragged batches (``audio_lengths=``), PLMS, ``const_noise``,
-    ``dump_steps``, and re-encoding only the edited windows' audio (all W windows go through the WavEncoder, as in ``sample_long``)."""
+    Not built: edits of a running stream or pool, ragged batches (``audio_lengths=``), PLMS, ``const_noise``, ``dump_steps``,
+    ``'torch_device'``, re-encoding only the edited windows' audio (all W windows go through the WavEncoder, as in ``sample_long``),
+    resampling windows behind the last edited one, and the SAG encoder (motion -> latent) as the source of ``text_features``
+    (chain ``MOTIONCLIP`` yourself)."""
     from .cfg_sampler import ClassifierFreeSampleModel
     if not isinstance(model, ClassifierFreeSampleModel):
         raise TypeError(f"edit_long: pass livelyspeaker_amd.ClassifierFreeSampleModel(RAG), got {type(model).__name__}")
     if diffusion.noise_source == "torch_device":
         raise NotImplementedError("edit_long: noise_source='torch_device' is not built for chained windows; use 'torch_cpu' or 'philox'")
-    timeline, audio, seed_poses, vid_indices, scale, emo = _as_tensors(timeline, audio, seed_poses, vid_indices, scale, emo)
+    timeline, audio, seed_poses, vid_indices, scale, emo, text_features = _as_tensors(timeline, audio, seed_poses, vid_indices, scale, emo,
+                                                                                      text_features)
     rag = model.model
     T, npre = int(rag.nframes), int(rag.n_pre_seq)
     if timeline.ndim != 4 or _shape(timeline)[1:3] != (rag.njoints, rag.nfeats):
@@ -764,7 +796,9 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
     sel = _edit_joints(joints, B, rag)
     if audio.ndim != 2 or int(audio.shape[0]) != B:
         raise ValueError(f"audio must be [{B}, L], got {list(audio.shape)}")
-    _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, W, sampler, skip_timesteps, None, None, encoder_chunk, {})
+    if text_features is not None and text_features.ndim == 2 and _shape(text_features) == (B, rag.latent_dim):
+        text_features = text_features[:, None, :].expand(B, W, rag.latent_dim)         # one script for the whole stretch
+    _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, W, sampler, skip_timesteps, sag, text_features, encoder_chunk, {})
     _check_model(diffusion, rag)
     hi = np.where(sel.any(axis=1), hi, lo).astype(np.int32)           # a clip with no joint selected is not edited
     windows = edit_plan(np.stack([lo, hi], axis=1), W, rag)
@@ -777,6 +811,12 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
     noised = rag.n_prefix_tokens == 1                  # the TED tree re-noises the kept motion, the BEAT tree does not
     kw = dict(_loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised), device_out=out_dev.type == "cuda", return_windows=return_windows,
               inpaint_noised=noised, channels=np.repeat(sel, rag.nfeats, axis=1))
+    if sag is not None:
+        sag_eng = sag.engine()
+        if sag_eng.device != eng.device:
+            raise ValueError(f"the SAG decoder runs on cuda:{sag_eng.device}, the RAG model on cuda:{eng.device}")
+        kw["sag"] = sag_eng
+        kw["text_features"] = text_features.float().permute(1, 0, 2).contiguous()
     if diffusion.noise_source == "philox":
         kw.update(diffusion._philox_key())
     else:

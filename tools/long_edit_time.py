@@ -3,6 +3,7 @@ timeline again (long_form.sample_long of the same W), alternated in one process:
 
     python tools/long_edit_time.py                 # 60 s of speech, 64 clips (profiles/r19_long_edit.md)
     python tools/long_edit_time.py 20 8            # seconds, clips
+    python tools/long_edit_time.py --sag [20 8]    # the SCRIPTED edit two ways (profiles/r26_long_edit_sag.md)
 
 TED, ddim100, skip_timesteps = 80 (20 steps per window), guidance 1.5, Philox noise, device-resident inputs, hipGraph replay, warm
 handles.  Three forms: the full call, an edit inside one window, and an edit that spans W // 2 windows.  Each call is timed by a host
@@ -12,7 +13,12 @@ event times of the last call of each form (prepare: ls_long_prepare, the same fo
 clock is sampled alongside (long_form_time.ClockSampler).
 
 What to check (derived, not measured): the windows' time scales with |Wset| / W; each step costs about one elementwise launch more
-than in the full call (the inpainting branch runs the denoiser and the update as two launches); prepare is unchanged."""
+than in the full call (the inpainting branch runs the denoiser and the update as two launches); prepare is unchanged.
+
+--sag times the script-guided edit of the `one` and `half` ranges two ways, alternated in the same manner: edit_long(sag=,
+text_features=) -- one engine call -- and the host loop it replaces, "for w in edit_plan: edit_window -> decoder -> edit_start ->
+ddim_sample_loop(init_image=) -> write-back", through the public per-clip API (which encodes a window's audio when it samples it,
+where edit_long encodes all W windows ahead; both are part of what a caller waits for and both are inside the timed call)."""
 import os
 import statistics
 import sys
@@ -25,7 +31,77 @@ from livelyspeaker_amd import long_form, synth                                  
 from long_form_time import DEV, ROUNDS, SKIP, ClockSampler, build, timed              # noqa: E402
 
 
+def host_loop(diffusion, model, sag, text, cfg, y, timeline, frames, W):
+    """The scripted edit through the public API: one sampling call per window of edit_plan."""
+    tl = timeline.clone()
+    B, T, S = tl.shape[0], cfg.nframes, cfg.nframes - cfg.n_pre_seq
+    shape = (B, cfg.njoints, cfg.nfeats, T)
+    ones = torch.ones(B, T, device=DEV).bool()
+    for w in long_form.edit_plan(frames, W, cfg):
+        origin_x, mask, motion = long_form.edit_window(tl, w, frames, None, y["seed_poses"], cfg)
+        init = long_form.edit_start(motion, mask, sag({"x": origin_x.clone(), "z": text[:, w].contiguous(), "mask": ones})["output"])
+        yy = {"audio_input": long_form.window_audio(y["audio"], w, cfg).contiguous(), "origin_x": origin_x, "vid_indices": y["vid_indices"],
+              "scale": y["scale"], "inpainting_mask": mask, "inpainted_motion": motion}
+        s = diffusion.ddim_sample_loop(model, shape, clip_denoised=False, model_kwargs={"y": yy}, skip_timesteps=SKIP, init_image=init,
+                                       progress=False, dump_steps=None, noise=None, const_noise=False)
+        tl[..., w * S:w * S + T] = torch.where(mask, motion, s)
+    return tl
+
+
+def main_sag(seconds, B):
+    from livelyspeaker_amd.motionclip_module import Decoder_TRANSFORMER
+    cfg, model, diffusion = build()
+    diffusion.noise_source, diffusion.philox_seed = "philox", 1
+    sag = Decoder_TRANSFORMER(njoints=cfg.njoints, nfeats=cfg.nfeats, latent_dim=512, n_pre_poses=cfg.n_pre_seq, use_style=False)
+    sag.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_sag_state_dict(cfg).items()}, strict=False)
+    sag.to(DEV).eval()
+    W, _, n_frames = long_form.plan_windows(int(round(seconds * 16000)), cfg)
+    y = {k: torch.from_numpy(v).to(DEV) for k, v in synth.make_long_cond(cfg, B, W).items()}
+    text = torch.from_numpy(synth.make_text_features(B * W).reshape(B, W, 512)).to(DEV)
+    S = cfg.nframes - cfg.n_pre_seq
+    mid, half_lo = W // 2, (W // 4) * S + 10
+    ranges = {"one": (mid * S + 10, mid * S + 20), "half": (half_lo, half_lo + (W // 2 - 1) * S + 5)}
+    timeline = long_form.sample_long(diffusion, model, y["audio"], y["seed_poses"], y["vid_indices"], y["scale"], n_windows=W, sampler="ddim",
+                                     skip_timesteps=SKIP, sag=sag, text_features=text)
+
+    def call(frames):
+        return long_form.edit_long(diffusion, model, timeline, frames, y["audio"], y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim",
+                                   skip_timesteps=SKIP, sag=sag, text_features=text)
+
+    forms = []
+    for name, frames in ranges.items():
+        forms.append((name, "loop", lambda frames=frames: host_loop(diffusion, model, sag, text, cfg, y, timeline, frames, W)))
+        forms.append((name, "call", lambda frames=frames: call(frames)))
+    clocks = ClockSampler()
+    clocks.start()
+    for _ in range(2):                                               # warm-up of all forms: allocations, graph capture, clocks
+        for _, _, fn in forms:
+            timed(fn)
+    clocks.take()
+    reps = 3
+    rounds, engine = {(n, k): [] for n, k, _ in forms}, {}
+    for _ in range(ROUNDS):
+        for name, kind, fn in forms:
+            rounds[name, kind].append(statistics.median(timed(fn)[0] for _ in range(reps)))
+            if kind == "call":
+                engine[name] = model.model.engine().timing()
+    print(f"# scripted edit; TED ddim100 skip {SKIP} (20 steps per window), CFG 1.5, philox, device inputs; {seconds:g} s of speech = {W} "
+          f"windows ({n_frames} frames), {B} clips; ms per call, median over {ROUNDS} alternated rounds [min .. max of the rounds]")
+    for name, frames in ranges.items():
+        lp, cl, t = rounds[name, "loop"], rounds[name, "call"], engine[name]
+        n_run = len(long_form.edit_plan(frames, W, cfg))
+        print(f"{name:5s} {n_run:3d} of {W} windows: host loop {statistics.median(lp):9.2f} [{min(lp):.2f} .. {max(lp):.2f}]  edit_long(sag=) "
+              f"{statistics.median(cl):9.2f} [{min(cl):.2f} .. {max(cl):.2f}]  ratio {statistics.median(lp) / statistics.median(cl):.2f}x  | edit_long: "
+              f"prepare {t['prepare_ms']:.2f} ms, windows {t['total_ms']:.2f} ms ({t['total_ms'] / n_run:.3f} per window), graph replayed for "
+              f"{t['graph_replayed']} of {t['n_segments']} windows, step path {t['step_path']}", flush=True)
+    print(f"# {clocks.take()}")
+    clocks.on = False
+
+
 def main():
+    if "--sag" in sys.argv:
+        sys.argv.remove("--sag")
+        return main_sag(float(sys.argv[1]) if len(sys.argv) > 1 else 60.0, int(sys.argv[2]) if len(sys.argv) > 2 else 64)
     seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     cfg, model, diffusion = build()
