@@ -40,6 +40,8 @@ kept ones from the existing motion; it prints how far the edited frames moved fr
 --stream-chunk SECONDS (with --long-seconds N) feeds the same waveform to a STREAM instead, SECONDS of audio at a time
 (long_form.open_stream: push() returns a window's new frames as soon as the window's audio is complete, close() the zero-padded rest);
 it prints when each window's frames appeared and checks that the frames, concatenated, are bit for bit the timeline of the one call.
+--post (with --stream-chunk) lets the stream own a post-processing stream (open_stream(post='ted')): every push also returns the new
+frames' joint positions and the motion beats that have just become decidable, and it prints the pose shape and the beat times per push.
 --pool SPEAKERS serves that many LIVE speakers from one engine (long_form.open_pool): they start 1.3 s apart and talk for different
 times, each joins a slot when it starts and leaves it when its speech ends, audio arrives for all of them every half second, and every
 push runs the windows that are complete -- of whichever speakers -- as one batch.  It prints who joined, which batch ran, and who left.
@@ -204,6 +206,11 @@ def main():
             del sys.argv[j:j + 2]
             if stream_chunk <= 0:
                 raise SystemExit("--stream-chunk takes a positive number of seconds")
+        post = "--post" in sys.argv
+        if post:
+            sys.argv.remove("--post")
+            if stream_chunk is None:
+                raise SystemExit("--post goes with --stream-chunk: the stream's frames are post-processed as they arrive")
         drop = "--drop-finished" in sys.argv
         if drop:
             sys.argv.remove("--drop-finished")
@@ -216,7 +223,7 @@ def main():
         if drop:
             raise SystemExit("--drop-finished goes with a comma list of durations: equally long speeches finish together")
         seconds = float(arg)
-        return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source, edit, stream_chunk)
+        return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source, edit, stream_chunk, post)
     if "--clip-text" in sys.argv:
         sys.argv.remove("--clip-text")
         return main_clip_text(int(sys.argv[1]) if len(sys.argv) > 1 else 64, noise_source)
@@ -335,7 +342,7 @@ def main_clip_text(B, noise_source):
     assert bool(torch.isfinite(sample).all()) and bool(torch.isfinite(decoded).all())
 
 
-def main_long(B, seconds, noise_source, edit=None, stream_chunk=None):
+def main_long(B, seconds, noise_source, edit=None, stream_chunk=None, post=False):
     """`seconds` of 16 kHz speech per clip -> one stitched timeline at 15 fps (the LivelySpeaker chain, window after window on the device)."""
     import numpy as np
     from livelyspeaker_amd import long_form
@@ -368,22 +375,32 @@ def main_long(B, seconds, noise_source, edit=None, stream_chunk=None):
     if edit is not None:
         edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit, sag_decoder)
     if stream_chunk is not None:
-        stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, stream_chunk)
+        stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, stream_chunk, scored if post else None)
 
 
-def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, chunk_seconds):
+def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, chunk_seconds, scored=None):
     """The waveform main_long sampled in one call, fed to a stream `chunk_seconds` at a time: every push carries the text feature of the
-    window it would start (a held value), and a window's frames come back from the push that completed its audio."""
+    window it would start (a held value), and a window's frames come back from the push that completed its audio.  `scored` (the
+    timeline's post-processing, --post): the stream post-processes its frames as they arrive, and the pushes' poses and beats,
+    concatenated, are checked against it."""
     n, L, W = max(1, int(round(chunk_seconds * 16000))), audio.shape[1], text.shape[1]
     torch.manual_seed(233)                                                                  # the seed of the one call: the same draws
     stream = long_form.open_stream(diffusion, model, y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim", skip_timesteps=80,
-                                   sag=sag_decoder)
-    parts, t0 = [], time.perf_counter()
+                                   sag=sag_decoder, post=None if scored is None else "ted")
+    parts, poses, beats, t0 = [], [], [[] for _ in range(audio.shape[0])], time.perf_counter()
     for lo in list(range(0, L, n)) + [None]:
         held = {"text_features": text[:, min(stream.windows_run, W - 1)]}
         t1 = time.perf_counter()
         new = stream.close(**held) if lo is None else stream.push(audio[:, lo:lo + n], **held)
         torch.cuda.synchronize()
+        if scored is not None:
+            new, posted = new
+            poses.append(posted["pose"])
+            for b, times in enumerate(posted["motion_beat_times"]):
+                beats[b] += times
+            if new.shape[3] or any(posted["motion_beat_times"]):
+                print(f"  post: pose {tuple(posted['pose'].shape)}, beats decided (clip 0, seconds): "
+                      + (", ".join(f"{t:.2f}" for t in posted["motion_beat_times"][0]) or "none"))
         if new.shape[3]:
             print(f"  {'close' if lo is None else f'audio {min(lo + n, L) / 16000:6.2f} s'}: window {stream.windows_run - 1} -> frames "
                   f"{stream.frames_out - new.shape[3]}..{stream.frames_out - 1}, {(time.perf_counter() - t1) * 1e3:.1f} ms after its last sample "
@@ -393,6 +410,9 @@ def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y
     assert torch.equal(streamed, timeline), float((streamed - timeline).abs().max())
     print(f"streamed in {chunk_seconds:g} s chunks ({len(parts) - 1} pushes + close): {stream.windows_run} windows, {stream.frames_out} frames, "
           f"bit for bit the timeline of the one call")
+    if scored is not None:
+        assert torch.equal(torch.cat(poses, dim=1), scored["pose"]) and beats == scored["motion_beat_times"]
+        print(f"post-processed as they arrived: {sum(len(b) for b in beats)} motion beats, poses and beats bit for bit those of the whole timeline")
 
 
 def main_pool(speakers, noise_source, tick_seconds=0.5):

@@ -953,6 +953,73 @@ int ls_beat_metrics_timeline_ragged(int device, int n_frames, const int32_t* fra
  * The outputs may be NULL to ask for the count alone.  LS_EINVAL: batch < 1, a NULL frames, tile < 1, an entry < 1, cap too small. */
 int ls_ragged_tiles(int batch, const int32_t* frames, int tile, int32_t* clip_out, int32_t* start_out, int32_t cap, int32_t* n_out);
 
+/* ---- Post-processing stream: the timeline entries' outputs as frames arrive ----------------------------------
+ * A handle of `capacity` SLOTS; each slot is one series of unbounded length that is fed in chunks (the frames ls_long_pool_push
+ * returns, or any other source in its [S, J, F, K] layout).  A push post-processes the new frames of every slot and returns the motion
+ * beats that have just become decidable; per slot, the outputs concatenated over the pushes and the finish are bit for bit what
+ * ls_ted_post_timeline (TED), ls_beat_post_timeline and ls_beat_metrics_timeline's beat_mask (BEAT) give for the whole series, under
+ * any chunking and beyond LS_TIMELINE_MAX_FRAMES.  The kernels call the timeline kernels' per-frame functions; what a frame needs from
+ * its left is CARRIED per slot on the device and recomputed from there: TED keeps the last 3 raw frames (angle_diff[f] needs frame
+ * f - 1, the beat at f needs angle_diff[f - 1 .. f + 1], so the beat output lags the frames by one), BEAT the last 2 order + 1 Euler
+ * triples of the six series joints (v[f] = |e[f + 1] - e[f]|; the minimum at f is decided once v[f + order] exists, a lag of
+ * order + 1 frames; mode='clip' clamps at 0 and, at the finish, at V - 1 = N - 2).
+ *
+ * ls_post_stream_plan (no handle, no GPU) is the one definition of the beat entries a push decides: with n_before frames in the
+ * series and n_new more, entries [*beat_first, *beat_first + *beat_count) -- frames of beat_mask (TED, dataset 0) or velocity indices
+ * (BEAT, dataset 1).  TED: [max(0, n - 1), N - 1) with N = n_before + n_new, and up to N when finishing (frame N - 1 is never a beat).
+ * BEAT: [max(0, n - order - 1), max(0, N - order - 1)), and up to max(0, N - 1) when finishing.  Over the pushes and the finish the
+ * ranges tile [0, N) (TED) or [0, N - 1) (BEAT) once, in order.  LS_EINVAL: dataset outside {0, 1}, BEAT order outside
+ * [1, LS_POST_STREAM_MAX_ORDER], a negative count, a sum above 2^62, finishing a series without a frame, NULL outputs.
+ * ls_post_stream_check (no handle, no GPU) is the check a push runs ahead of any launch, slot by slot on that plan: LS_EINVAL for a
+ * NULL counts, capacity < 1, K outside [0, LS_POST_STREAM_MAX_CHUNK], counts[s] outside [0, K], beat_capacity below a slot's
+ * beat_count; LS_ESTATE for finish on a slot with no frames.  beat_first / beat_count [capacity] may be NULL.
+ *
+ * ls_post_stream_open allocates everything for `capacity` slots and LS_POST_STREAM_MAX_CHUNK frames per push (the carries, the slot
+ * table, and the staging of a host-side push); nothing grows afterwards.  cfg: the TED configuration (dataset 0; njoints comes from
+ * it); njoints, order, series_joint: BEAT (dataset 1).  LS_EINVAL ahead of any HIP call: what the plan refuses, capacity < 1, what
+ * ls_ted_post refuses of a configuration, njoints < 1, a series joint outside [0, njoints).
+ * ls_post_stream_push: frames [S, J, F, K] (F = 3 TED, 6 BEAT; frame-innermost) holds counts[s] new frames of slot s in
+ * frames[s, :, :, :counts[s]]; what lies behind counts[s] is never read.  Outputs, any of them NULL, rows behind counts[s] zeroed:
+ * TED aligned [S,K,J*3], pose [S,K,n_pose_joints,3], angle_diff [S,K], beat_mask [S,beat_capacity]; BEAT decoded [S,K,J*6],
+ * euler_deg [S,K,J*3], beat_mask [S,6,beat_capacity].  Entry q of slot s's beat_mask row is series entry beat_first[s] + q, for
+ * q < beat_count[s]; the rest of the row is 0.  finish[s] != 0 ends slot s's series with this push (counts[s] may be 0): the pending
+ * entries are emitted and the slot is free -- its next frames start a new series at frame 0.  A failed launch marks the handle failed
+ * (LS_ESTATE from then on).  frames and the tensor outputs are device pointers iff on_device; counts, finish, beat_first and
+ * beat_count are HOST arrays in both modes.
+ * Not built: device-resident counts, chunks above LS_POST_STREAM_MAX_CHUNK frames per push, SRGR (it needs targets), audio onsets and
+ * the alignment scores online (librosa normalises the onset envelope by the whole signal's extrema). */
+#define LS_POST_STREAM_MAX_CHUNK 256
+#define LS_POST_STREAM_MAX_ORDER 8
+typedef struct ls_post_stream ls_post_stream;
+typedef struct ls_post_stream_push_args {
+    int32_t on_device;
+    int32_t K;                  /* row stride of frames and of the per-frame outputs: 0 .. LS_POST_STREAM_MAX_CHUNK   */
+    int32_t beat_capacity;      /* row stride of beat_mask                                                            */
+    int32_t reserved;
+    const float* frames;        /* [S, J, F, K]; may be NULL when K == 0                                              */
+    const int32_t* counts;      /* [S] HOST                                                                           */
+    const int32_t* finish;      /* [S] HOST or NULL                                                                   */
+    float* aligned;             /* TED                                                                                */
+    float* pose;
+    float* angle_diff;
+    float* decoded;             /* BEAT                                                                               */
+    float* euler_deg;
+    unsigned char* beat_mask;
+    int64_t* beat_first;        /* [S] HOST or NULL                                                                   */
+    int32_t* beat_count;        /* [S] HOST or NULL                                                                   */
+} ls_post_stream_push_args;
+int ls_post_stream_plan(int32_t dataset, int32_t order, int64_t n_before, int64_t n_new, int32_t finishing, int64_t* beat_first,
+                        int32_t* beat_count);
+int ls_post_stream_check(int32_t dataset, int32_t order, int32_t capacity, const int64_t* frames_in, int32_t K, const int32_t* counts,
+                         const int32_t* finish, int32_t beat_capacity, int64_t* beat_first, int32_t* beat_count);
+int ls_post_stream_open(int device, int32_t dataset, int32_t capacity, const ls_post_config* cfg, int32_t njoints, int32_t order,
+                        const int32_t* series_joint, ls_post_stream** out);
+int ls_post_stream_push(ls_post_stream* h, const ls_post_stream_push_args* a);
+/* frames_in [capacity] (nullable): the frames of each slot's running series; *device_bytes (nullable): what the handle holds */
+int ls_post_stream_info(const ls_post_stream* h, int64_t* frames_in, int64_t* device_bytes);
+void ls_post_stream_close(ls_post_stream* h);
+const char* ls_post_stream_last_error(const ls_post_stream* h);
+
 /* ---- audio onsets for the beat-alignment scores ------------------------------------------------------------
  * What the reference's scripts take from librosa 0.9.2 (scripts/test_RAG_ted.py:113 onset_detect(y, sr=16000, units='time');
  * scripts_beat/utils/metric.py:60-74 alignment.load_audio), for a batch of equally long clips (ls_onsets_ragged: of any lengths):

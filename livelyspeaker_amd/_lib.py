@@ -166,6 +166,12 @@ class LsTedAlignArgs(C.Structure):
         (n, C.c_void_p) for n in ("beat_mask", "onset_frames", "onset_count", "align_sum", "n_beats")]
 
 
+class LsPostStreamPushArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("on_device", "K", "beat_capacity", "reserved")] + [
+        (n, C.c_void_p) for n in ("frames", "counts", "finish", "aligned", "pose", "angle_diff", "decoded", "euler_deg", "beat_mask",
+                                  "beat_first", "beat_count")]
+
+
 class LsIngestPlanArgs(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("batch", "n_poses", "n_ext", "stride", "beat", "frame_cap", "window_cap", "n_frames",
                                          "n_windows", "reserved")] + [("fps", C.c_double), ("sr", C.c_double)] + [
@@ -224,6 +230,8 @@ EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set
            "ls_clip_text_encode", "ls_clip_text_encode_async", "ls_clip_text_last_encode_ms", "ls_clip_text_stream", "ls_clip_text_plan", "ls_ted_post", "ls_beat_post", "ls_beat_metrics", "ls_beat_ldiv", "ls_onsets", "ls_onsets_tables",
            "ls_ted_post_timeline", "ls_beat_post_timeline", "ls_beat_metrics_timeline", "ls_ted_beat_align",
            "ls_onsets_ragged", "ls_ted_post_timeline_ragged", "ls_beat_post_timeline_ragged", "ls_beat_metrics_timeline_ragged", "ls_ragged_tiles",
+           "ls_post_stream_plan", "ls_post_stream_check", "ls_post_stream_open", "ls_post_stream_push", "ls_post_stream_info", "ls_post_stream_close",
+           "ls_post_stream_last_error",
            "ls_ingest_plan", "ls_ted_ingest", "ls_beat_ingest",
            "ls_train_create", "ls_train_destroy", "ls_train_last_error", "ls_train_set_schedule", "ls_train_param_count",
            "ls_train_flat_size", "ls_train_param_info", "ls_train_set_weight", "ls_train_get_weight", "ls_train_forward_backward",
@@ -301,6 +309,15 @@ def load_library(build_if_missing: bool = True):
     lib.ls_long_pool_join.argtypes = [C.c_void_p, C.POINTER(LsLongPoolJoinArgs)]
     lib.ls_long_pool_push.argtypes = [C.c_void_p, C.POINTER(LsLongPoolPushArgs)]
     lib.ls_long_pool_info.argtypes = [C.c_void_p, C.c_int32, c_i64p, c_i64p, c_i64p, c_i32p, c_i64p]
+    lib.ls_post_stream_plan.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, c_i64p, c_i32p]
+    lib.ls_post_stream_check.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_i64p, C.c_int32, c_i32p, c_i32p, C.c_int32, c_i64p, c_i32p]
+    lib.ls_post_stream_open.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(LsPostConfig), C.c_int32, C.c_int32, c_i32p, C.POINTER(C.c_void_p)]
+    lib.ls_post_stream_push.argtypes = [C.c_void_p, C.POINTER(LsPostStreamPushArgs)]
+    lib.ls_post_stream_info.argtypes = [C.c_void_p, c_i64p, c_i64p]
+    lib.ls_post_stream_close.argtypes = [C.c_void_p]
+    lib.ls_post_stream_close.restype = None
+    lib.ls_post_stream_last_error.argtypes = [C.c_void_p]
+    lib.ls_post_stream_last_error.restype = C.c_char_p
     lib.ls_forward.argtypes = [C.c_void_p, C.POINTER(LsForwardArgs)]
     lib.ls_step.argtypes = [C.c_void_p, C.POINTER(LsStepArgs)]
     lib.ls_plms_step.argtypes = [C.c_void_p, C.POINTER(LsPlmsStepArgs)]
@@ -599,6 +616,84 @@ def long_pool_plan(samples_in, windows_run, samples_new, closing, open, audio_le
         rounds.append([int(s) for s in flat[at:at + A]])
         at += A
     return rounds, frames[:S].copy()
+
+
+POST_STREAM_MAX_CHUNK = 256      # LS_POST_STREAM_MAX_CHUNK
+POST_STREAM_MAX_ORDER = 8        # LS_POST_STREAM_MAX_ORDER
+
+
+def post_stream_plan(dataset, n_before, n_new, finishing=False, order=2):
+    """ls_post_stream_plan (no GPU needed): ``(beat_first, beat_count)``, the beat entries a push of ``n_new`` frames decides on a
+    series that holds ``n_before`` -- frames of the TED beat mask, velocity indices of the BEAT series.  A negative count, an order
+    outside [1, 8] (BEAT) or finishing a series without a frame raise ``ValueError``."""
+    first, count = C.c_int64(), C.c_int32()
+    if dataset not in ("ted", "beat") or load_library().ls_post_stream_plan(int(dataset == "beat"), int(order), int(n_before), int(n_new),
+                                                                           int(bool(finishing)), C.byref(first), C.byref(count)) != 0:
+        raise ValueError(f"no plan for dataset {dataset!r}, order {order}, {n_before} + {n_new} frames (finishing={bool(finishing)}): counts "
+                         "must be >= 0, a BEAT order in [1, 8], and a series that is finished must hold a frame")
+    return int(first.value), int(count.value)
+
+
+def post_stream_check(dataset, order, frames_in, K, counts, finish, beat_capacity=None):
+    """ls_post_stream_check (no GPU needed): what a push refuses ahead of any launch.  Returns ``(beat_first int64 [S], beat_count int32
+    [S])``; ``beat_capacity=None`` asks for the counts alone.  Raises ``ValueError`` for what the engine answers with LS_EINVAL or
+    LS_ESTATE."""
+    n = np.ascontiguousarray(np.asarray(frames_in).reshape(-1), dtype=np.int64)
+    S = int(n.size)
+    k = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.int64)
+    fin = np.zeros(S, np.int32) if finish is None else np.ascontiguousarray(np.asarray(finish).reshape(-1)).astype(bool).astype(np.int32)
+    if k.shape != (S,) or fin.shape != (S,):
+        raise ValueError(f"one count and one finish flag per slot: got {k.size} and {fin.size} for {S} slots")
+    if k.size and (k.min() < 0 or k.max() > int(K)):
+        raise ValueError(f"counts must lie in [0, {int(K)}], got {k.min()} .. {k.max()}")
+    k = k.astype(np.int32)
+    first, count = np.zeros(max(S, 1), np.int64), np.zeros(max(S, 1), np.int32)
+    cap = (POST_STREAM_MAX_CHUNK + POST_STREAM_MAX_ORDER) if beat_capacity is None else int(beat_capacity)
+    rc = load_library().ls_post_stream_check(int(dataset == "beat"), int(order), S, n.ctypes.data_as(c_i64p), int(K), k.ctypes.data_as(c_i32p),
+                                             fin.ctypes.data_as(c_i32p), cap, first.ctypes.data_as(c_i64p), count.ctypes.data_as(c_i32p))
+    if rc == -2:
+        raise ValueError(f"finish on a slot without a frame: frames_in {n.tolist()}, counts {k.tolist()}, finish {fin.tolist()}")
+    if rc != 0:
+        raise ValueError(f"refused: at most {POST_STREAM_MAX_CHUNK} frames per push (got K = {int(K)}), counts in [0, K], a BEAT order in [1, 8], "
+                         f"beat_capacity {cap} >= every slot's entries")
+    return first[:S].copy(), count[:S].copy()
+
+
+class PostStreamEngine:
+    """One ``ls_post_stream`` handle: ``capacity`` slots of post-processing state on one GPU (see ``postprocess.open_post_stream``)."""
+
+    def __init__(self, dataset, capacity, device=0, cfg=None, njoints=47, order=2, series_joints=(0,) * 6):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        self.device, self.S = int(device), int(capacity)
+        joints = (C.c_int32 * 6)(*[int(j) for j in series_joints])
+        rc = self.lib.ls_post_stream_open(self.device, int(dataset == "beat"), self.S, C.byref(cfg) if cfg is not None else None, int(njoints),
+                                          int(order), joints, C.byref(self.h))
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise EngineError(f"ls_post_stream_open failed ({rc}): {self.lib.ls_post_stream_last_error(None).decode()}")
+
+    def push(self, args: "LsPostStreamPushArgs"):
+        rc = self.lib.ls_post_stream_push(self.h, C.byref(args))
+        if rc != 0:
+            raise EngineError(f"ls_post_stream_push failed ({rc}): {self.lib.ls_post_stream_last_error(self.h).decode()}")
+
+    def info(self) -> dict:
+        n, nbytes = np.zeros(self.S, np.int64), C.c_int64()
+        if self.lib.ls_post_stream_info(self.h, n.ctypes.data_as(c_i64p), C.byref(nbytes)) != 0:
+            raise EngineError("ls_post_stream_info failed")
+        return {"frames_in": n, "device_bytes": int(nbytes.value)}
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.ls_post_stream_close(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def plan_coop_slices(groups, dataset="ted", n_cus=256):

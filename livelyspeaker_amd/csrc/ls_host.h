@@ -1,4 +1,4 @@
-// Host-only plumbing shared by the six handles behind include/ls_hip.h (ls_handle, ls_sag, ls_sag_enc, ls_clip_text, ls_trainer, ls_eval): the
+// Host-only plumbing shared by the seven handles behind include/ls_hip.h (ls_handle, ls_sag, ls_sag_enc, ls_clip_text, ls_trainer, ls_eval, ls_post_stream): the
 // device buffer every handle owns its memory through, the one error path (message formatter, HIP-status check, *_last_error) and
 // the sinusoidal position table.
 #pragma once

@@ -37,7 +37,7 @@ from __future__ import annotations
 import numpy as np
 import torch as th
 
-from . import _lib, ref_draws
+from . import _lib, postprocess, ref_draws
 from . import gaussian_diffusion as gd
 
 AUDIO_STRIDE = 32000        # audio samples between two windows: T - n_pre_seq = 30 frames at 15 fps of 16 kHz audio
@@ -318,6 +318,31 @@ class _Session:
             self._eng = eng
         return self._eng
 
+    def _init_post(self, post, rag, slots):
+        """``post=``: None, or the dataset whose post-processing stream the session owns ('ted' / 'beat', the model's own)."""
+        if post is not None:
+            want = "beat" if getattr(rag, "n_prefix_tokens", 1) == 2 else "ted"
+            if post != want:
+                raise ValueError(f"post must be None or the model's dataset {want!r}, got {post!r}")
+        self._post_kind, self._post_slots, self._post = post, slots, None
+
+    def _check_post_frames(self, most):
+        """Ahead of the sampling: a push of the post-processing stream takes at most 256 frames per slot."""
+        if self._post_kind is not None and most > postprocess.POST_STREAM_MAX_CHUNK:
+            raise ValueError(f"with post=, a call may complete at most {postprocess.POST_STREAM_MAX_CHUNK} frames per clip (8 windows), this one "
+                             f"would complete {most}: feed the audio in smaller chunks")
+
+    def _post_push(self, frames, counts, finish):
+        """The session's frames into its post-processing stream (opened on the engine's device at the first call): a device tensor
+        goes in as it is, without a host copy."""
+        if self._post is None:
+            rag = self._rag
+            self._post = postprocess.open_post_stream(self._post_kind, self._post_slots, device=self._eng.device, joints=int(rag.njoints))
+        res = self._post.push(frames, counts, finish)
+        if self._closed:                  # the session's last call has finished every series: the handle goes with it
+            self._post.close()
+        return res
+
     def _check_held(self, emo, text_features, rows):
         """``emo`` [rows] (BEAT) and ``text_features`` [rows, latent_dim] (with ``sag=``), each None or one row per clip."""
         rag = self._rag
@@ -336,7 +361,7 @@ class _Session:
 class LongStream(_Session):
     """A running ``open_stream`` session; see there.  ``samples_in``, ``windows_run``, ``frames_out``: host ints."""
 
-    def __init__(self, diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag):
+    def __init__(self, diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag, post=None):
         seed_poses, vid_indices, scale, emo = _as_tensors(seed_poses, vid_indices, scale, emo)
         B = int(seed_poses.shape[0]) if seed_poses.ndim else 0
         rag = getattr(model, "model", None)
@@ -349,6 +374,7 @@ class LongStream(_Session):
         if emo is not None and emo.ndim != 1:
             raise ValueError(f"a stream holds one emotion id per clip: emo must be [{B}], got {list(emo.shape)}")
         self._diffusion, self._rag, self._sag, self._B = diffusion, rag, sag, B
+        self._init_post(post, rag, B)
         self._cond = (seed_poses.float(), vid_indices, scale.float())
         self._emo, self._text = emo, None               # held on the host side only until the next engine call takes them
         self._have_emo = self._have_text = False
@@ -381,6 +407,7 @@ class LongStream(_Session):
         if k and self._sag is not None and text_features is None and not self._have_text:
             raise ValueError("sag needs text_features [B, 512] for the stream's first window: pass them to this push")
         shape = (B, rag.njoints, rag.nfeats, rag.nframes)
+        self._check_post_frames(k * (rag.nframes - rag.n_pre_seq) + (rag.n_pre_seq if k and first == 0 else 0))
         kw = dict(self._kw)
         if k and diffusion.noise_source != "philox":
             _check_tape_bound(diffusion, "open_stream", self._n_exec, shape, int(rag.latent_dim))
@@ -400,10 +427,14 @@ class LongStream(_Session):
         self.windows_run += ran
         self.frames_out += int(frames.shape[3])
         assert (first, k) == (self.windows_run - ran, ran)
-        return gd._as_tensor(frames, out_dev)
+        frames = gd._as_tensor(frames, out_dev)
+        if self._post_kind is None:
+            return frames
+        return frames, self._post_push(frames, None, np.full(B, bool(closing)))
 
     def push(self, audio_chunk, emo=None, text_features=None):
-        """Feed ``audio_chunk`` [B, n], n >= 0; returns the new frames ``[B, J, F, k]`` of the windows it completed (k may be 0)."""
+        """Feed ``audio_chunk`` [B, n], n >= 0; returns the new frames ``[B, J, F, k]`` of the windows it completed (k may be 0); with
+        ``post=``, ``(frames, post_dict)``."""
         return self._feed(audio_chunk, emo, text_features, False)
 
     def close(self, emo=None, text_features=None):
@@ -412,7 +443,7 @@ class LongStream(_Session):
 
 
 def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False,
-                sag=None):
+                sag=None, post=None):
     """The online form of ``sample_long``: a session that is fed audio in chunks of any size and returns a window's new frames as soon
     as that window's audio is complete.
 
@@ -443,11 +474,17 @@ def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, samp
     ``sample_long`` or ``edit_long`` on the same model afterwards replaces its conditioning and ends the stream (the next push raises
     ``_lib.EngineError``).
 
+    ``post='ted'`` / ``'beat'`` (the model's own dataset): the session owns a ``postprocess.open_post_stream`` of B slots, and ``push``
+    and ``close`` return ``(frames, post_dict)`` -- ``PostStream.push``'s dict for the new frames (poses, the change curve or the Euler
+    planes, and the motion beats that have just become decidable); ``close`` finishes every series.  The frames go from the engine to
+    the post-processing kernels on the device when the audio was on the device.  The frames themselves are bit for bit those of
+    ``post=None``, which changes nothing.  A call may complete at most 256 frames per clip then (8 windows).
+
     Clips that join or leave while others run, each fed at its own rate: ``open_pool``.
 
     Not built: ``audio_lengths`` / ``drop_finished``, ``edit_long`` on a running stream, PLMS, ``const_noise``, ``dump_steps``,
     sharded calls, a non-blocking ``push``."""
-    return LongStream(diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag)
+    return LongStream(diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag, post)
 
 
 def pool_plan(samples_in, windows_run, new, closing, open, cfg):
@@ -465,7 +502,7 @@ def pool_plan(samples_in, windows_run, new, closing, open, cfg):
 class LongPool(_Session):
     """A running ``open_pool`` session; see there.  ``slots``: per-slot host arrays ``samples_in``, ``windows_run``, ``frames_out``, ``open``."""
 
-    def __init__(self, diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag):
+    def __init__(self, diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post=None):
         S = int(capacity)
         if S < 1:
             raise ValueError(f"capacity must be >= 1, got {capacity}")
@@ -478,6 +515,7 @@ class LongPool(_Session):
                     None if sag is None else th.empty(S, 1, int(rag.latent_dim)), None, {})
         _check_model(diffusion, rag)
         self._diffusion, self._rag, self._sag, self._S = diffusion, rag, sag, S
+        self._init_post(post, rag, S)
         self._kw = _loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised)
         if diffusion.noise_source == "philox":          # one key per pool: row r of round q draws at sample_offset + r + (q << 48)
             self._kw.update(diffusion._philox_key())
@@ -558,7 +596,9 @@ class LongPool(_Session):
         if given.shape != (S,) or (given & ~st["open"]).any():
             raise ValueError(f"given must mark open slots only, one entry per slot: got {given.tolist()} for open {st['open'].tolist()}")
         bits = given.astype(np.int32) * ((1 if emo is not None else 0) | (2 if text_features is not None else 0))
-        rounds, _ = pool_plan(st["samples_in"], st["windows_run"], lens, closing, st["open"], rag)
+        rounds, owed = pool_plan(st["samples_in"], st["windows_run"], lens, closing, st["open"], rag)
+        self._check_post_frames(int(owed.max()) if len(owed) else 0)
+        ending = np.asarray(closing).astype(bool) & st["open"]
         for s in {s for r in rounds for s in r}:
             if self._sag is not None and st["windows_run"][s] == 0 and not self._have_text[s] and not bits[s] & 2:
                 raise ValueError(f"sag needs text_features [512] for slot {s}'s first window: pass them to join or to this push")
@@ -579,11 +619,15 @@ class LongPool(_Session):
         self._have_text |= (bits & 2).astype(bool)
         self._refresh()
         self._have_text &= self._state["open"]
-        return gd._as_tensor(frames, out_dev), counts
+        frames = gd._as_tensor(frames, out_dev)
+        if self._post_kind is None:
+            return frames, counts
+        return frames, counts, self._post_push(frames, counts, ending)
 
     def push(self, audio, lengths, emo=None, text_features=None, given=None):
         """Feed ``audio`` [S, n_max]: ``lengths[s]`` samples for slot s (0 for a slot that is free or has nothing new).  Returns
-        ``(frames [S, J, F, K], counts)``: slot s's new frames in ``frames[s, ..., :counts[s]]``, zero behind them; K = max(counts)."""
+        ``(frames [S, J, F, K], counts)``: slot s's new frames in ``frames[s, ..., :counts[s]]``, zero behind them; K = max(counts).
+        With ``post=``: ``(frames, counts, post_dict)``."""
         return self._feed(audio, lengths, np.zeros(self._S, np.int32), emo, text_features, given)
 
     def _leave(self, which):
@@ -591,26 +635,33 @@ class LongPool(_Session):
         closing[which] = 1
         J, F = int(self._rag.njoints), int(self._rag.nfeats)
         if not closing.any():
-            return th.zeros((self._S, J, F, 0), device=self._last_dev), np.zeros(self._S, np.int32)
+            frames, counts = th.zeros((self._S, J, F, 0), device=self._last_dev), np.zeros(self._S, np.int32)
+            if self._post_kind is None:
+                return frames, counts
+            return frames, counts, (self._post_push(frames, counts, None) if self._eng is not None else None)      # no engine: nothing was ever fed
         return self._feed(th.zeros((self._S, 0), device=self._last_dev), np.zeros(self._S, np.int64), closing, None, None, None)
 
     def leave(self, slot):
         """End slot ``slot``'s clip: the frames ``[J, F, k]`` of the windows ``plan_windows(samples_in)`` still owes it, with silence
-        behind its last sample.  The slot is free afterwards."""
+        behind its last sample.  The slot is free afterwards.  With ``post=``: ``(frames, counts, post_dict)`` -- the slot's frames, the
+        call's counts [S] and the post-processing of the call (rows of the other slots are empty), which finishes the slot's series."""
         slot = int(slot)
         if not 0 <= slot < self._S or not self._state["open"][slot]:
             raise ValueError(f"slot {slot} is not open")
-        frames, counts = self._leave([slot])
-        return frames[slot, :, :, :int(counts[slot])]
+        res = self._leave([slot])
+        frames = res[0][slot, :, :, :int(res[1][slot])]
+        return frames if self._post_kind is None else (frames, res[1], res[2])
 
     def close(self):
         """Leave every open slot and end the session: ``(frames [S, J, F, K], counts)`` as from ``push``."""
         res = self._leave(np.nonzero(self._state["open"])[0])
         self._closed = True
+        if self._post is not None:
+            self._post.close()            # every series has been finished by the call above
         return res
 
 
-def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False, sag=None):
+def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False, sag=None, post=None):
     """``open_stream`` for clips that start and stop at different times and arrive at different rates: a session pool of ``capacity``
     slots on ONE engine.
 
@@ -643,9 +694,14 @@ def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=
     same model replaces the engine's conditioning and ends the pool (the next call raises ``_lib.EngineError``).  ``close`` and
     ``leave`` refuse a slot that was never fed a sample (``ValueError``), as ``LongStream.close`` does.
 
+    ``post='ted'`` / ``'beat'`` (the model's own dataset): the pool owns a ``postprocess.open_post_stream`` of ``capacity`` slots;
+    ``push``, ``leave`` and ``close`` return ``(frames, counts, post_dict)`` with ``PostStream.push``'s dict for the call's frames.
+    ``leave`` and ``close`` finish the series of the slots they end, and a ``join`` into a freed slot starts a fresh one.  A call may
+    complete at most 256 frames per slot then.  With ``post=None`` nothing changes.
+
     Not built: device-resident ``lengths``, Philox keyed by (slot, window), ``edit_long`` on a pool, PLMS, ``const_noise``,
     ``dump_steps``, sharded calls, a non-blocking ``push``."""
-    return LongPool(diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag)
+    return LongPool(diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post)
 
 
 def _edit_ranges(frames, B, n_frames):

@@ -142,6 +142,162 @@ def beat_postprocess_timeline(timeline, device: int = 0, want_euler: bool = True
     return {"decoded_motions": dec, "pred_euler": eul}
 
 
+POST_STREAM_MAX_CHUNK = _lib.POST_STREAM_MAX_CHUNK      # frames per slot and push (LS_POST_STREAM_MAX_CHUNK)
+BEAT_SERIES_JOINTS = (4, 3, 5, 26, 25, 27)              # beat_metrics.BEAT_SERIES_JOINTS: right arm, shoulder, wrist; left arm, shoulder, wrist
+
+
+def post_stream_plan(dataset, n_before, n_new, finishing=False, order=2):
+    """The beat entries a ``PostStream.push`` of ``n_new`` frames decides on a series that holds ``n_before`` (no GPU):
+    ``(beat_first, beat_count)``.  TED entries are frames of ``beat_mask``: ``[max(0, n - 1), N - 1)`` with ``N = n_before + n_new``
+    (the beat at f needs ``angle_diff[f + 1]``), up to ``N`` when finishing.  BEAT entries are velocity indices:
+    ``[max(0, n - order - 1), max(0, N - order - 1))``, up to ``N - 1`` when finishing.  One definition for the engine and for this
+    module (``ls_post_stream_plan``)."""
+    return _lib.post_stream_plan(dataset, n_before, n_new, finishing, order)
+
+
+class PostStream:
+    """A running ``open_post_stream``; see there.  ``frames_in``: the frames of each slot's running series (host int64 [S])."""
+
+    def __init__(self, dataset, capacity, device, order, series_joints, joints):
+        if dataset not in ("ted", "beat"):
+            raise ValueError(f"dataset must be 'ted' or 'beat', got {dataset!r}")
+        S = int(capacity)
+        if S < 1:
+            raise ValueError(f"capacity must be >= 1, got {capacity}")
+        self.dataset, self.capacity, self.device = dataset, S, int(device)
+        self._beat = dataset == "beat"
+        self.order = int(order) if self._beat else 1
+        self.joints = int(joints) if self._beat else 9
+        self._series = tuple(int(j) for j in series_joints)
+        if self._beat:
+            if not 1 <= self.order <= _lib.POST_STREAM_MAX_ORDER:
+                raise ValueError(f"order must lie in [1, {_lib.POST_STREAM_MAX_ORDER}], got {order}")
+            if self.joints < 1 or len(self._series) != 6 or any(not 0 <= j < self.joints for j in self._series):
+                raise ValueError(f"series_joints must name six of the {self.joints} joints, got {list(series_joints)}")
+        self._n = np.zeros(S, np.int64)
+        self._eng = None
+        self._closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    @property
+    def frames_in(self):
+        return self._n.copy()
+
+    def _engine(self):
+        if self._eng is None:         # bound at the first push: every refusal above and in push comes before a device is touched
+            self._eng = _lib.PostStreamEngine(self.dataset, self.capacity, self.device, None if self._beat else ted_post_config(), self.joints,
+                                              self.order, self._series if self._beat else (0,) * 6)
+        return self._eng
+
+    def device_bytes(self) -> int:
+        """What the handle holds on the device (``ls_post_stream_info``); constant from the first push on."""
+        return self._engine().info()["device_bytes"]
+
+    def push(self, frames, counts=None, finish=None) -> dict:
+        """``frames`` [S, J, F, K], K <= 256 (numpy, CPU or CUDA tensor): slot s's new frames in ``frames[s, ..., :counts[s]]``
+        (``counts=None``: K for every slot).  ``finish`` (bool [S]): the slots whose series end with this push."""
+        if self._closed:
+            raise RuntimeError("the post-processing stream is closed")
+        S, J, F = self.capacity, self.joints, 6 if self._beat else 3
+        if len(frames.shape) != 4 or tuple(int(v) for v in frames.shape[:3]) != (S, J, F):
+            raise ValueError(f"frames must be [{S}, {J}, {F}, K], got {list(frames.shape)}")
+        K = int(frames.shape[3])
+        if K > POST_STREAM_MAX_CHUNK:
+            raise ValueError(f"a push takes at most {POST_STREAM_MAX_CHUNK} frames per slot, got {K} (larger chunks are not built)")
+        if counts is None:
+            counts = np.full(S, K, np.int64)
+        if hasattr(counts, "detach"):
+            counts = counts.detach().cpu().numpy()
+        if finish is not None and hasattr(finish, "detach"):
+            finish = finish.detach().cpu().numpy()
+        first, count = _lib.post_stream_check(self.dataset, self.order, self._n, K, counts, finish)
+        k = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.int32)
+        fin = np.zeros(S, np.int32) if finish is None else np.asarray(finish).reshape(-1).astype(bool).astype(np.int32)
+        Kb = int(count.max())
+        m = _lib._Marshal(self.device, frames)
+        a = _lib.LsPostStreamPushArgs()
+        a.on_device, a.K, a.beat_capacity = int(m.on_device), K, Kb
+        a.counts, a.finish = k.ctypes.data, fin.ctypes.data
+        if self._beat:
+            dec, a.decoded = m.out((S, K, J * 6))
+            eul, a.euler_deg = m.out((S, K, J * 3))
+            mask, a.beat_mask = m.out((S, 6, Kb), np.uint8)
+            res = {"decoded_motions": dec, "pred_euler": eul}
+        else:
+            aligned, a.aligned = m.out((S, K, 27))
+            pose, a.pose = m.out((S, K, 10, 3))
+            diff, a.angle_diff = m.out((S, K))
+            mask, a.beat_mask = m.out((S, Kb), np.uint8)
+            res = {"aligned_motions": aligned, "pose": pose, "angle_diff": diff}
+        a.frames = m.f32(frames, (S, J, F, K)) if K else None
+        eng = self._engine()
+        m.ready()
+        eng.push(a)
+        self._n = np.where(fin != 0, 0, self._n + k)
+        res.update(beat_mask=mask.bool() if m.on_device else mask.astype(bool), beat_first=first, beat_count=count)
+        if not self._beat:
+            host = mask.cpu().numpy() if m.on_device else mask
+            res["motion_beat_times"] = [[float(first[s] + q) / TED_FPS for q in np.nonzero(host[s, :count[s]])[0]] for s in range(S)]
+        return res
+
+    def finish(self, slot) -> dict:
+        """End slot ``slot``'s series: a push without frames that emits its pending beat entries.  The slot is free afterwards."""
+        slot = int(slot)
+        if not 0 <= slot < self.capacity or self._n[slot] < 1:
+            raise ValueError(f"slot {slot} holds no running series")
+        fin = np.zeros(self.capacity, bool)
+        fin[slot] = True
+        return self._finish(fin)
+
+    def _finish(self, fin):
+        empty = np.zeros((self.capacity, self.joints, 6 if self._beat else 3, 0), np.float32)       # no frames: the entries come back on the host
+        return self.push(empty, np.zeros(self.capacity, np.int64), fin)
+
+    def close(self):
+        """Finish every slot that holds a series (returns that push's dict, or None when there was none) and release the handle."""
+        if self._closed:
+            return None
+        res = self._finish(self._n > 0) if (self._n > 0).any() else None
+        self._closed = True
+        if self._eng is not None:
+            self._eng.close()
+        return res
+
+
+def open_post_stream(dataset, capacity, device=0, order=2, series_joints=BEAT_SERIES_JOINTS, joints=47) -> PostStream:
+    """The online form of ``ted_postprocess_timeline`` / ``beat_postprocess_timeline`` + ``beat_metrics_timeline``'s motion beats: a
+    device-resident stream of ``capacity`` slots that is fed model-space frames as they arrive (``open_stream`` / ``open_pool``'s
+    output, or any source in that layout) and returns their post-processed rows at once, plus the beats that have just become decidable.
+
+        ps = open_post_stream('ted', capacity)
+        out = ps.push(frames, counts=None, finish=None)     # [S, J, F, K], K <= 256
+        tail = ps.finish(slot)                              # the slot's pending beat entries; its next frames start a new series
+        ps.close()
+
+    ``push`` returns, all ``[S, K, ...]`` with rows behind ``counts[s]`` zero and on the device for device input: TED
+    ``aligned_motions`` [S,K,27], ``pose`` [S,K,10,3], ``angle_diff`` [S,K]; BEAT ``decoded_motions`` [S,K,J*6], ``pred_euler``
+    [S,K,J*3].  And the beats: ``beat_mask`` (TED bool [S,Kb]; BEAT [S,6,Kb], one row per series of ``series_joints``) whose entry q of
+    slot s is series entry ``beat_first[s] + q`` for ``q < beat_count[s]`` (``post_stream_plan``; Kb = the largest count), and for TED
+    ``motion_beat_times``: per slot the seconds ``frame / 15`` of the beats decided in this push.  TED beats lag the frames by one, BEAT
+    minima by ``order + 1``; ``finish`` emits what is pending.
+
+    Per slot, everything concatenated over the pushes and the finish is bit for bit what the timeline entries give for the whole
+    series, whatever the chunking and for series of any length (tests/test_gpu_post_stream.py): the kernels run the timeline kernels'
+    per-frame functions, and what a frame needs from its left is carried on the device (TED: 3 raw frames per slot; BEAT: 2 order + 1
+    Euler triples of the six joints).  Device memory is allocated at the first push and does not grow (``device_bytes``).
+
+    Not built: online audio onsets and the BC / BeatAlign scores (librosa normalises the onset envelope by the whole signal's extrema
+    and clamps at the global maximum - 80 dB, so they are not causal), SRGR (it needs targets), device-resident ``counts``, chunks over
+    256 frames per push."""
+    return PostStream(dataset, capacity, device, order, series_joints, joints)
+
+
 def ted_beat_align(beat_mask, onset_frames, onset_count, sigma=TED_BEAT_SIGMA, fps=TED_FPS, sr=16000, hop=512, device=0):
     """``ls_ted_beat_align``: per clip, the beat-consistency sum and the number of motion beats.  beat_mask [B, N] (bool or bytes),
     onset_frames [B, F] int32 and onset_count [B] int32 as ``audio_onsets`` returns them (numpy, or CUDA tensors: then nothing but
