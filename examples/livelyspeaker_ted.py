@@ -45,6 +45,10 @@ frames' joint positions and the motion beats that have just become decidable, an
 --pool SPEAKERS serves that many LIVE speakers from one engine (long_form.open_pool): they start 1.3 s apart and talk for different
 times, each joins a slot when it starts and leaves it when its speech ends, audio arrives for all of them every half second, and every
 push runs the windows that are complete -- of whichever speakers -- as one batch.  It prints who joined, which batch ran, and who left.
+--keyed (with --pool, philox) opens the pool with noise_keys='clip': speaker s draws at key 100 + s whatever runs beside it.  After
+serving the staggered speakers it runs one of them again, alone, in a fresh keyed pool under the same seed and key, and prints the
+max-abs difference between the two runs of that speaker (0 where both ran the same kernel family at the same batch; a kernel family's
+distance otherwise).
 With real data: load RAG.pt / SAG.pth / the auto-encoder checkpoint with load_model_wo_clip / load_state_dict and build `cond`
 exactly as the reference script does; everything below the weight loading is unchanged.
 """
@@ -174,7 +178,7 @@ def main():
         speakers = int(sys.argv[i + 1])
         if speakers < 1:
             raise SystemExit("--pool takes the number of speakers, >= 1")
-        return main_pool(speakers, noise_source)
+        return main_pool(speakers, noise_source, keyed="--keyed" in sys.argv)
     if "--long-seconds" in sys.argv:
         i = sys.argv.index("--long-seconds")
         arg = sys.argv[i + 1]
@@ -415,7 +419,7 @@ def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y
         print(f"post-processed as they arrived: {sum(len(b) for b in beats)} motion beats, poses and beats bit for bit those of the whole timeline")
 
 
-def main_pool(speakers, noise_source, tick_seconds=0.5):
+def main_pool(speakers, noise_source, tick_seconds=0.5, keyed=False):
     """`speakers` live speakers on ONE engine (long_form.open_pool): speaker s starts talking 1.3 s after speaker s - 1 and talks for
     6 + s seconds; audio arrives for all of them every `tick_seconds`.  A speaker joins a free slot when it starts and leaves when its
     speech ends; every tick is one push, which runs the windows that are complete as one batch."""
@@ -423,21 +427,27 @@ def main_pool(speakers, noise_source, tick_seconds=0.5):
     from livelyspeaker_amd import long_form
     if noise_source == "torch_device":
         raise SystemExit("--pool draws with philox or torch_cpu")
+    if keyed and noise_source != "philox":
+        raise SystemExit("--keyed keys philox draws")
     cfg, model, diffusion, _, _ = build()
     diffusion.noise_source = noise_source
+    if keyed:
+        diffusion.philox_seed = 0x5EED_2026             # one seed for the session and for its replay
+    opts = {"noise_keys": "clip"} if keyed else {}
     n = int(round(tick_seconds * 16000))
     start = [int(round(1.3 * s / tick_seconds)) for s in range(speakers)]                       # the tick a speaker joins in
     length = [int(round((6 + s) * 16000)) for s in range(speakers)]
     y = {k: torch.from_numpy(v).cuda() for k, v in synth.make_long_cond(cfg, speakers, max(length) // 32000 + 2, scale=2.5).items()}
     torch.manual_seed(233)
-    pool = long_form.open_pool(diffusion, model, speakers, sampler="ddim", skip_timesteps=80)
+    pool = long_form.open_pool(diffusion, model, speakers, sampler="ddim", skip_timesteps=80, **opts)
     slot, fed, frames = {}, [0] * speakers, [0] * speakers
+    kept = [[] for _ in range(speakers)]
     t0, tick = time.perf_counter(), 0
     while any(fed[s] < length[s] for s in range(speakers)):
         for s in range(speakers):
             if start[s] == tick:
-                slot[s] = pool.join(y["seed_poses"][s], y["vid_indices"][s], y["scale"][s])
-                print(f"tick {tick:3d}: speaker {s} joins slot {slot[s]}")
+                slot[s] = pool.join(y["seed_poses"][s], y["vid_indices"][s], y["scale"][s], **({"key": 100 + s} if keyed else {}))
+                print(f"tick {tick:3d}: speaker {s} joins slot {slot[s]}" + (f" under key {100 + s}" if keyed else ""))
         chunk, lengths = torch.zeros(speakers, n, device="cuda"), np.zeros(speakers, np.int64)
         for s, k in slot.items():
             take = min(n, length[s] - fed[s])
@@ -452,14 +462,26 @@ def main_pool(speakers, noise_source, tick_seconds=0.5):
                   f" in {(time.perf_counter() - t1) * 1e3:.1f} ms")
         for s, c in done.items():
             frames[s] += c
+            kept[s].append(new[slot[s], :, :, :c])
         for s in [s for s in slot if fed[s] == length[s]]:
             tail = pool.leave(slot.pop(s))
             frames[s] += int(tail.shape[2])
+            kept[s].append(tail)
             assert frames[s] == long_form.plan_windows(length[s], cfg)[2] and bool(torch.isfinite(tail).all())
             print(f"tick {tick:3d}: speaker {s} leaves after {length[s] / 16000:g} s of speech with {frames[s]} frames")
         tick += 1
     pool.close()
     print(f"{speakers} speakers, {sum(frames)} frames ({noise_source}) in {(time.perf_counter() - t0) * 1e3:.0f} ms over {tick} pushes on one engine")
+    if keyed:           # the session replayed for one speaker: alone, in one chunk, in slot 0 of a fresh pool -- same seed, same key
+        s = speakers // 2
+        solo = long_form.open_pool(diffusion, model, 1, sampler="ddim", skip_timesteps=80, noise_keys="clip")
+        solo.join(y["seed_poses"][s], y["vid_indices"][s], y["scale"][s], key=100 + s)
+        head, _ = solo.push(y["audio"][s:s + 1, :length[s]].contiguous(), [length[s]])
+        again = torch.cat([head[0], solo.leave(0)], dim=2)
+        served = torch.cat(kept[s], dim=2)
+        assert again.shape == served.shape
+        print(f"speaker {s} (key {100 + s}) run again alone in a fresh keyed pool: max |served - replayed| = {float((served - again).abs().max()):.3e} "
+              f"over {served.shape[2]} frames")
 
 
 def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit, sag_decoder=None):

@@ -534,8 +534,21 @@ int ls_long_stream_info(const ls_handle* h, int64_t out[4]);
  * eps_tape [n_exec, 2, A, latent_dim], noise_tape [n_exec, A, J, F, T]).  PHILOX: row r of the pool's q-th round since open draws at
  * sample_offset + r + (q << 48): the key of ls_long_stream_push whenever the pool is used like a stream (all slots joined in order and
  * fed alike), and otherwise NOT independent of the push schedule; a push that would take q to 2^16 returns LS_ESTATE.
+ * PHILOX on a KEYED pool (ls_long_pool_keyed(h, 1) after the open, ahead of the first join): every slot holds a key in [0, 2^48) --
+ * the number of joins since the open until ls_long_pool_set_key replaces it, after the slot's join and ahead of its first window
+ * (LS_ESTATE later) -- and the clip in slot s draws in its OWN window w (windows_run[s], 0 again after a join) at key[s] + (w << 48)
+ * under the pool's one seed; sample_offset is not read.  A clip's frames are then a function of the weights, the schedule, its own
+ * audio and conditioning, the seed and its key: not of the other slots, the slot index, the chunking or the pool's age.  They are
+ * what ls_long_sample gives for that audio at sample_offset = key -- bit for bit where both run the same kernel family at the same
+ * batch, and otherwise as far apart as two kernel families are.  Two open slots may hold the same key (same audio and conditioning:
+ * same frames); nothing polices it.  A clip runs at most 2^16 windows (LS_ESTATE beyond); the pool's round count is no limit.
+ * ls_long_pool_keys (no handle, no GPU) is the one definition of a round's key table, in ls_long_pool_plan's row order: the row of
+ * slot s in round r draws at keys[s] + ((windows_run[s] + r) << 48); LS_EINVAL for a key >= 2^48, LS_ESTATE for a window >= 2^16 (of
+ * slots with n_windows[s] > 0; the others are not looked at), row_keys nullable (row_capacity entries), *n_entries = sum of n_windows.
+ * The draws of a keyed round are written by ls_philox_rows.hip into the ring LS_NOISE_TORCH_DEVICE uses (ls_set_torch_ring_bytes),
+ * sized at ls_long_pool_keyed for every batch up to the capacity, from a key table the captured loop reads at a fixed address.
  * One host wait per call that ran a round; a call that ran none waits only for the copy of a HOST chunk.
- * Not built: device-resident lengths, Philox keyed by (slot, window), ls_long_edit on a pool, PLMS, const_noise, dump_steps, sharded
+ * Not built: device-resident lengths, ls_long_edit on a pool, PLMS, const_noise, dump_steps, sharded
  * calls, a non-blocking push. */
 typedef struct ls_long_pool_join_args {
     int32_t slot;
@@ -580,6 +593,10 @@ int ls_long_pool_plan(int32_t n_slots, int32_t audio_len, const int64_t* samples
 int ls_long_pool_open(ls_handle* h, int32_t capacity);
 int ls_long_pool_join(ls_handle* h, const ls_long_pool_join_args* a);
 int ls_long_pool_push(ls_handle* h, const ls_long_pool_push_args* a);
+int ls_long_pool_keyed(ls_handle* h, int32_t on);
+int ls_long_pool_set_key(ls_handle* h, int32_t slot, uint64_t key);
+int ls_long_pool_keys(int32_t n_slots, const uint64_t* keys, const int64_t* windows_run, const int32_t* n_windows, uint64_t* row_keys,
+                      int32_t row_capacity, int32_t* n_entries);
 /* per slot (arrays of `capacity` entries, each nullable): samples fed, windows run, frames written, open; misc = {slots of the pool,
  * device bytes the pool holds (rings, hand-off stores, held conditioning, gathered window, one window's features), rounds run since
  * open, 1 while the pool is open} of the handle's current or last pool (a pool that has ended: as it stood then) -- zeros before the
@@ -655,6 +672,15 @@ int ls_bpd(ls_handle* h, const ls_bpd_args* a);
 /* The x_T draw of PHILOX mode on its own (what ls_sample uses when x_init == NULL): out [batch,J,F,T] ~ N(0,1),
  * stream keyed by (seed, sample_offset + b). Lets tests check the device RNG's moments and shard-invariance. */
 int ls_philox_x_init(ls_handle* h, int batch, uint64_t seed, uint64_t sample_offset, int on_device, float* out);
+/* Per-row Philox keys of ls_sample: row b of the next PHILOX calls at batch n draws every stream (x_T, the two style eps per step, the
+ * step noise) at gidx = keys[b] -- the whole 64-bit value ls_philox.h puts into c[2], c[3] -- in place of sample_offset + b, so any
+ * subset of a larger call's rows, in any order, can be drawn again.  keys: HOST [n], copied before the call returns.  They hold
+ * until (NULL, 0) clears them or ls_prepare runs at another batch.  With keys set ls_sample returns LS_EINVAL for a batch other
+ * than n, a noise mode other than PHILOX or a nonzero sample_offset, and LS_EUNSUPPORTED for PLMS and the inpainting branch (ls_bpd
+ * under PHILOX: LS_EUNSUPPORTED); the long-form entries do not read them.  The draws are written by ls_philox_rows.hip into the
+ * ring LS_NOISE_TORCH_DEVICE uses (ls_set_torch_ring_bytes) with ls_philox.h's own arithmetic: keys[b] = o + b gives the bits of
+ * sample_offset = o. */
+int ls_set_row_keys(ls_handle* h, const uint64_t* keys, int32_t n);
 
 /* ---- torch's device normal stream (LS_NOISE_TORCH_DEVICE) -----------------------------------------------------------------
  * ls_torch_randn_advance: how far torch.randn(n) (float32) on a device of n_cu compute units and max_threads_per_cu threads per CU

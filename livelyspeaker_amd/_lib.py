@@ -222,7 +222,7 @@ class LsEvalConfig(C.Structure):
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
            "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_edit_sag", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_long_pool_plan", "ls_long_pool_open", "ls_long_pool_join", "ls_long_pool_push", "ls_long_pool_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
-           "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
+           "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_set_row_keys", "ls_long_pool_keyed", "ls_long_pool_set_key", "ls_long_pool_keys", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
            "ls_sag_enc_encode", "ls_sag_enc_encode_async", "ls_sag_enc_last_encode_ms", "ls_sag_enc_stream",
@@ -308,6 +308,10 @@ def load_library(build_if_missing: bool = True):
     lib.ls_long_pool_open.argtypes = [C.c_void_p, C.c_int32]
     lib.ls_long_pool_join.argtypes = [C.c_void_p, C.POINTER(LsLongPoolJoinArgs)]
     lib.ls_long_pool_push.argtypes = [C.c_void_p, C.POINTER(LsLongPoolPushArgs)]
+    lib.ls_long_pool_keyed.argtypes = [C.c_void_p, C.c_int32]
+    lib.ls_long_pool_set_key.argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
+    lib.ls_long_pool_keys.argtypes = [C.c_int32, C.POINTER(C.c_uint64), c_i64p, c_i32p, C.POINTER(C.c_uint64), C.c_int32, c_i32p]
+    lib.ls_set_row_keys.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32]
     lib.ls_long_pool_info.argtypes = [C.c_void_p, C.c_int32, c_i64p, c_i64p, c_i64p, c_i32p, c_i64p]
     lib.ls_post_stream_plan.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, c_i64p, c_i32p]
     lib.ls_post_stream_check.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_i64p, C.c_int32, c_i32p, c_i32p, C.c_int32, c_i64p, c_i32p]
@@ -616,6 +620,33 @@ def long_pool_plan(samples_in, windows_run, samples_new, closing, open, audio_le
         rounds.append([int(s) for s in flat[at:at + A]])
         at += A
     return rounds, frames[:S].copy()
+
+
+def long_pool_keys(keys, windows_run, n_windows):
+    """ls_long_pool_keys (no GPU needed): the key table of one push of a keyed session pool, uint64 [sum n_windows], in
+    ``long_pool_plan``'s row order -- the row of slot s in round r draws at ``keys[s] + ((windows_run[s] + r) << 48)``.  A key of
+    a slot that runs a window outside ``[0, 2^48)`` raises ``ValueError``, a window index that reaches 2^16 ``EngineError``."""
+    lib = load_library()
+    for k in keys:
+        if not 0 <= int(k) < 1 << 64:
+            raise ValueError(f"key {k} outside [0, 2^64)")
+    k64 = np.ascontiguousarray([int(k) for k in keys], dtype=np.uint64)
+    ran = np.ascontiguousarray(np.asarray(windows_run).reshape(-1), dtype=np.int64)
+    wins = np.ascontiguousarray(np.asarray(n_windows).reshape(-1), dtype=np.int32)
+    S = int(k64.size)
+    if not (ran.size == wins.size == S):
+        raise ValueError(f"one entry per slot: got {[a.size for a in (k64, ran, wins)]}")
+    pu64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))      # noqa: E731
+    n = C.c_int32()
+    rc = lib.ls_long_pool_keys(S, pu64(k64), ran.ctypes.data_as(c_i64p), wins.ctypes.data_as(c_i32p), None, 0, C.byref(n))
+    if rc == -2:        # LS_ESTATE
+        raise EngineError("ls_long_pool_keys: a clip of a keyed pool runs at most 2^16 windows")
+    if rc != 0:
+        raise ValueError(f"no key table for keys {k64.tolist()} windows_run {ran.tolist()} n_windows {wins.tolist()}: keys stay below 2^48, counts are >= 0")
+    out = np.zeros(max(int(n.value), 1), np.uint64)
+    if lib.ls_long_pool_keys(S, pu64(k64), ran.ctypes.data_as(c_i64p), wins.ctypes.data_as(c_i32p), pu64(out), int(n.value), C.byref(n)) != 0:
+        raise EngineError("ls_long_pool_keys failed")
+    return out[:int(n.value)].copy()
 
 
 POST_STREAM_MAX_CHUNK = 256      # LS_POST_STREAM_MAX_CHUNK
@@ -929,10 +960,11 @@ class Engine(_Handle):
     def sample(self, sampler=LS_SAMPLER_DDPM, x_init=None, eps_tape=None, noise_tape=None, init_image=None,
                skip_timesteps=0, eta=0.0, const_noise=False, dump_steps=None, philox_seed=None, sample_offset=0,
                use_graph=True, clip_denoised=False, device_out=False, two_pass_always=False, segment=None, inpaint=None,
-               torch_state=None, torch_ring_bytes=256 << 20, plms_order=0):
+               torch_state=None, torch_ring_bytes=256 << 20, plms_order=0, row_keys=None):
         """Run the whole loop. TAPE mode when tapes are given, PHILOX mode when ``philox_seed`` is, TORCH_DEVICE mode when
         ``torch_state`` = (seed, offset) of torch's device generator is (the loop makes torch's device draws itself; ``x_init`` None =
-        it draws x_T too; the caller moves the generator on).  Outputs are torch CUDA tensors if any input is one (or ``device_out``),
+        it draws x_T too; the caller moves the generator on).  ``row_keys`` uint64 [B] (PHILOX): row b draws at ``row_keys[b]`` in place of
+        ``sample_offset + b`` (ls_set_row_keys; set for this call alone, its draws go through the ring of ``torch_ring_bytes``).  Outputs are torch CUDA tensors if any input is one (or ``device_out``),
         else numpy."""
         inp = inpaint or (None, None, None, False)     # (mask, motion, q_sample noise tape or None, re-noise?): the inpainting branch
         m = self._marshal([x_init, eps_tape, noise_tape, init_image, inp[1]], device_out)
@@ -974,7 +1006,15 @@ class Engine(_Handle):
             a.n_dump, a.dump_steps = len(ds), ds.ctypes.data_as(c_i32p)
             m.keep.append(ds)
         m.ready()
-        self._check(self.lib.ls_sample(self.h, C.byref(a)), "ls_sample")
+        if row_keys is not None:
+            rk = np.ascontiguousarray(row_keys, dtype=np.uint64).reshape(-1)
+            self._check(self.lib.ls_set_torch_ring_bytes(self.h, int(torch_ring_bytes)), "ls_set_torch_ring_bytes")
+            self._check(self.lib.ls_set_row_keys(self.h, rk.ctypes.data_as(C.POINTER(C.c_uint64)), int(rk.size)), "ls_set_row_keys")
+        try:
+            self._check(self.lib.ls_sample(self.h, C.byref(a)), "ls_sample")
+        finally:
+            if row_keys is not None:
+                self._check(self.lib.ls_set_row_keys(self.h, None, 0), "ls_set_row_keys")
         if not last:
             self._segment_inputs = m     # page-locked host tapes of this segment: referenced until the next segment call has returned
             return None
@@ -1190,6 +1230,14 @@ class Engine(_Handle):
         self._check(self.lib.ls_long_pool_open(self.h, int(capacity)), "ls_long_pool_open")
         self.batch, self.n_windows, self.window_batches = int(capacity), 0, None
 
+    def long_pool_keyed(self, on=True):
+        """PHILOX draws that follow the clip (ls_long_pool_keyed): on a pool nobody has joined yet."""
+        self._check(self.lib.ls_long_pool_keyed(self.h, int(bool(on))), "ls_long_pool_keyed")
+
+    def long_pool_set_key(self, slot, key):
+        """The key in [0, 2^48) of the clip in ``slot`` of a keyed pool (ls_long_pool_set_key): after its join, ahead of its first window."""
+        self._check(self.lib.ls_long_pool_set_key(self.h, int(slot), int(key)), "ls_long_pool_set_key")
+
     def long_pool_join(self, slot, seed_poses, vid_index, scale, emo=None, text_features=None):
         """Fill the free slot ``slot`` (ls_long_pool_join): ``seed_poses`` [J, F, n_pre], one speaker id, one scale, and the held
         ``emo`` id (BEAT) / ``text_features`` [D]."""
@@ -1208,7 +1256,8 @@ class Engine(_Handle):
         ``long_pool_plan`` (ls_long_pool_push).  ``closing`` [S] (host): the slot leaves after the windows it is owed.  ``emo`` [S] /
         ``text_features`` [S, D] replace the held conditioning of the slots whose ``given`` [S] (host) has bit 0 / bit 1 set.  TAPE mode
         takes the draws packed round after round at each round's batch A (``x_init`` [sum A, J, F, T], flat ``eps_tape`` / ``noise_tape``
-        holding per round [n_exec, 2, A, D] / [n_exec, A, J, F, T]), PHILOX mode ``philox_seed``.  Returns ``(frames [S, J, F, K], counts
+        holding per round [n_exec, 2, A, D] / [n_exec, A, J, F, T]), PHILOX mode ``philox_seed`` (a keyed pool, ``long_pool_keyed``, draws
+        at the slots' keys and does not read ``sample_offset``).  Returns ``(frames [S, J, F, K], counts
         int32 [S], rounds)`` with K the most frames any slot got; a slot's row is zero behind its own count."""
         info = self.long_pool_info()        # of the last pool, whatever has been prepared on the handle since
         S, D = info["capacity"], self.D

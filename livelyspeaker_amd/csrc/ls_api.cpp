@@ -471,7 +471,7 @@ static int prepare_impl(ls_handle* h, const ls_cond* c, bool wait) {
         h->timing.prepare_ms = -1.0f;          // until the work is known to be done (next synchronising call / ls_get_timing)
         h->prepare_pending = true;
     }
-    if (h->B != B) free_graph(h);
+    if (h->B != B) { free_graph(h); h->rk_n = 0; }      // row keys (ls_set_row_keys) hold for one batch size
     h->B = B;
     h->prepared = true;
     return LS_OK;

@@ -118,6 +118,7 @@ struct Window {
     const EditArgs* edit_start = nullptr;       // a scripted edit: behind the decode, k_edit_start puts cc.sag_out under the editable elements of the init plane
     CachePolicy policy = kReplace;
     bool first = false;                 // the first window of the call
+    bool keyed = false;                 // a keyed pool's round: PHILOX rows draw at row_gidx (written ahead of the window), w is not used
 };
 
 // The call prologue, first half -- nothing here touches the device: the refusals every entry shares, and wa.  runs: the call runs at
@@ -188,9 +189,9 @@ int run_window(ls_handle* h, ChainCall& cc, const Window& win) {
     // The loop's advance_tags uploads call_host (24 bytes of pageable memory) as every ls_sample does: the runtime takes such a source into
     // its staging memory before hipMemcpyAsync returns, which is what makes rewriting it for the next window safe.  It is the one host ->
     // device copy per window; whether the runtime waits inside it is the runtime's business (not measured).
-    h->call_host = CallParams{cc.seed, cc.sample_offset + ((unsigned long long)win.w << 48), h->tag_base, 0u};
+    h->call_host = CallParams{cc.seed, win.keyed ? 0ull : cc.sample_offset + ((unsigned long long)win.w << 48), h->tag_base, 0u};
     int replayed = 0;
-    if ((rc = run_window_loop(h, &wa, win.resident_inpaint, win.first, win.policy, &replayed)) != LS_OK) return rc;
+    if ((rc = run_window_loop(h, &wa, win.resident_inpaint, win.first, win.policy, &replayed, win.keyed)) != LS_OK) return rc;
     cc.replays += replayed;
     ++cc.windows;
     return LS_OK;
@@ -337,6 +338,7 @@ int session_open(ls_handle* h, int S, const ls_long_stream_cond* c) {
     h->pl_scale_host = sc;
     h->pl_open.assign((size_t)S, c ? 1 : 0); h->pl_have_emo.assign((size_t)S, 0); h->pl_have_text.assign((size_t)S, 0);
     h->pl_styled.clear();
+    h->pl_keyed = false; h->pl_joins = 0; h->pl_key.assign((size_t)S, 0);
     h->pl_lockstep = c ? ls_handle::kLockstep : ls_handle::kPool;
     h->pl_state = ls_handle::kStreamOpen;
     return LS_OK;
@@ -348,7 +350,7 @@ int session_open(ls_handle* h, int S, const ls_long_stream_cond* c) {
 // k_pool_gather -> WavEncoder -> k_build_feats at batch A, the per-batch stages at A, the window body, k_pool_scatter.  Nothing is
 // allocated from the first launch on.
 int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_args* a, ChainCall& cc, const std::vector<int32_t>& win,
-                     const std::vector<int32_t>& rounds, int n_rounds) {
+                     const std::vector<int32_t>& rounds, int n_rounds, const std::vector<uint64_t>& row_keys) {
     const int S = h->pl_S, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, AL = h->cfg.audio_len, R = h->pl_R, od = a->on_device, cap = a->capacity;
     const bool beat = h->cfg.n_prefix_tokens == 2, lockstep = h->pl_lockstep != ls_handle::kPool;
     const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -371,6 +373,7 @@ int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_ar
             if ((rc = ensure_pinned(h, h->eps_tape, (size_t)cc.n_exec * 2 * S * kD * sizeof(float))) != LS_OK || (rc = ensure_pinned(h, h->noise_tape, cc.n_exec * nxS)) != LS_OK) return rc;
             if (!od) { HIPCHK(h, h->lg_x.ensure(nxS)); HIPCHK(h, h->lg_eps.ensure((size_t)cc.n_exec * 2 * S * kD * sizeof(float))); HIPCHK(h, h->lg_nz.ensure(cc.n_exec * nxS)); }
         }
+        if (!row_keys.empty() && (rc = size_key_ring(h, S, cc.n_exec)) != LS_OK) return rc;       // grows only when the schedule or the ring's budget did since the pool was keyed
         if (a->sag) {
             cc.sag = a->sag; cc.sag_st = ls_sag_stream(a->sag);
             HIPCHK(h, hipMemsetAsync(h->lg_mask.p, 1, (size_t)S * T, st));
@@ -426,6 +429,8 @@ int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_ar
         }
         // the round's table: one upload of pageable memory, taken into the runtime's staging memory before the call returns (as call_host is)
         HIPCHK(h, hipMemcpyAsync(h->pl_table.p, table.data(), (size_t)A * kPoolRow * sizeof(int), hipMemcpyHostToDevice, st));
+        // a keyed pool: the round's rows of the key table, likewise; the captured loop of batch A reads them from row_gidx
+        if (!row_keys.empty()) HIPCHK(h, hipMemcpyAsync(h->row_gidx.p, row_keys.data() + at, (size_t)A * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         HIPCHK(h, launch_pool_gather(pa, A, st));
         if ((rc = run_wav_encoder(h, h->lg_clips.f(), A)) != LS_OK) return rc;
         HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f(), A, JF, h->KPP, 0, st, T));
@@ -448,6 +453,7 @@ int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_ar
         // a pool: a batch size met once is met again, and kKeep never destroys a graph under the replays in flight.  A stream has one
         // batch and one key per call: a key that is not cached replaces what is
         wn.policy = lockstep ? kReplace : kKeep;
+        wn.keyed = !row_keys.empty();
         if (cc.tape) {
             wn.x_init = a->x_init + at * JF * T; wn.eps_tape = a->eps_tape + at * cc.n_exec * 2 * kD; wn.noise_tape = a->noise_tape + at * cc.n_exec * JF * T;
             wn.host_tapes = !od;
@@ -513,12 +519,19 @@ int session_push(ls_handle* h, const char* entry, const ls_long_pool_push_args* 
     ChainCall cc;
     int rc;
     if ((rc = chain_args(h, entry, a, n_rounds > 0, cc)) != LS_OK) return rc;
-    if (n_rounds > 0 && !cc.tape) {
+    std::vector<uint64_t> row_keys;         // a keyed pool under PHILOX: one gidx per row of every round (ls_long_pool_keys); empty otherwise
+    if (n_rounds > 0 && !cc.tape && h->pl_keyed) {
+        row_keys.resize((size_t)n_entries);
+        int32_t n_keys = 0;
+        const int krc = ls_long_pool_keys(S, h->pl_key.data(), ran.data(), win.data(), row_keys.data(), n_entries, &n_keys);
+        if (krc == LS_ESTATE) return fail(h, LS_ESTATE, "%s: a clip of a keyed pool runs at most 2^16 windows; let it leave and join again under another key", entry);
+        if (krc != LS_OK || n_keys != n_entries) return fail(h, LS_EINVAL, "%s: ls_long_pool_keys failed", entry);
+    } else if (n_rounds > 0 && !cc.tape) {
         if ((a->sample_offset + (unsigned long long)S) >> 48) return fail(h, LS_EINVAL, "PHILOX: sample_offset + capacity must stay below 2^48 (the round index sits above)");
         if (h->pl_rounds + n_rounds > (1 << 16)) return fail(h, LS_ESTATE, "%s: PHILOX keys a round by its index since open, which stays below 2^16; open a new session", entry);
     }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    rc = session_push_run(h, entry, a, cc, win, rounds, n_rounds);
+    rc = session_push_run(h, entry, a, cc, win, rounds, n_rounds, row_keys);
     if (rc != LS_OK) {      // rings and hand-off stores may be half written: the session is over, the handle is not
         h->pl_state = ls_handle::kStreamFailed;
         (void)hipStreamSynchronize(h->stream);
@@ -907,6 +920,32 @@ int ls_long_pool_join(ls_handle* h, const ls_long_pool_join_args* a) {
     h->pl_scale_host[(size_t)s] = sc;
     h->pl_samples[(size_t)s] = h->pl_windows[(size_t)s] = h->pl_frames[(size_t)s] = 0;     // the ring position with them: sample n sits at n % R
     h->pl_open[(size_t)s] = 1;
+    h->pl_key[(size_t)s] = (uint64_t)h->pl_joins++ & ((1ull << 48) - 1);       // a keyed pool's default: joins since open
+    return LS_OK;
+}
+
+// A pool whose PHILOX draws follow the clip (ls_hip.h): on a pool nobody has joined yet.  The draws' ring and the key table are sized
+// here for every batch up to the pool's capacity, like everything else a pool's captured loops hold.
+int ls_long_pool_keyed(ls_handle* h, int32_t on) {
+    if (!h) return fail(h, LS_EINVAL, "ls_long_pool_keyed: null argument");
+    int rc;
+    if ((rc = session_is_open(h, "ls_long_pool_keyed", false)) != LS_OK) return rc;
+    if (h->pl_joins != 0) return fail(h, LS_ESTATE, "ls_long_pool_keyed: after the pool's first join");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (on && (rc = size_key_ring(h, h->pl_S, h->have_sched ? h->n_steps : 1)) != LS_OK) return rc;
+    h->pl_keyed = on != 0;
+    return LS_OK;
+}
+
+int ls_long_pool_set_key(ls_handle* h, int32_t slot, uint64_t key) {
+    if (!h) return fail(h, LS_EINVAL, "ls_long_pool_set_key: null argument");
+    const int rc = session_is_open(h, "ls_long_pool_set_key", false);
+    if (rc != LS_OK) return rc;
+    if (slot < 0 || slot >= h->pl_S) return fail(h, LS_EINVAL, "ls_long_pool_set_key: slot %d outside [0, %d)", slot, h->pl_S);
+    if (key >> 48) return fail(h, LS_EINVAL, "ls_long_pool_set_key: key %llu is not below 2^48 (the window index sits above)", (unsigned long long)key);
+    if (!h->pl_keyed) return fail(h, LS_ESTATE, "ls_long_pool_set_key: the pool is not keyed (ls_long_pool_keyed)");
+    if (!h->pl_open[(size_t)slot] || h->pl_windows[(size_t)slot] != 0) return fail(h, LS_ESTATE, "ls_long_pool_set_key: slot %d is not open, or has run a window", slot);
+    h->pl_key[(size_t)slot] = key;
     return LS_OK;
 }
 

@@ -1,8 +1,8 @@
 // The plans of the chained-window engine (ls_chain_api.cpp): which clips run which window of a ragged call, which windows a timeline
-// edit runs, which windows a push of a stream runs, which rounds a push of a session pool runs, which copies feed the slots' rings.
+// edit runs, which windows a push of a stream runs, which rounds a push of a session pool runs and at which keys its rows draw, which copies feed the slots' rings.
 // Integer arithmetic on host arrays, no
 // HIP in here: each is the single definition for its entry and for Python (long_form.py), and tests/chain_plan_main.cpp and
-// tests/pool_plan_main.cpp run them on their edges under the host sanitizers.
+// tests/pool_plan_main.cpp and tests/pool_keys_main.cpp run them on their edges under the host sanitizers.
 #include <algorithm>
 #include <cstdint>
 #include <vector>
@@ -136,6 +136,33 @@ int ls_long_pool_plan(int32_t n_slots, int32_t audio_len, const int64_t* samples
                 if (n_windows[s] > r) round_slots[p++] = s;
     }
     *n_rounds = (int32_t)rounds;
+    *n_entries = (int32_t)entries;
+    return LS_OK;
+}
+
+// The key table of a keyed pool's push (ls_long_pool_keyed in ls_hip.h), in ls_long_pool_plan's order: round r holds the slots with
+// n_windows[s] > r, ascending, and the row of slot s there draws at keys[s] + ((windows_run[s] + r) << 48) -- the slot's key and the
+// slot's OWN window, whatever runs beside it and however many rounds the pool has run.  Only slots that run a window are looked at.
+int ls_long_pool_keys(int32_t n_slots, const uint64_t* keys, const int64_t* windows_run, const int32_t* n_windows, uint64_t* row_keys,
+                      int32_t row_capacity, int32_t* n_entries) {
+    if (n_slots < 1 || !keys || !windows_run || !n_windows || !n_entries || row_capacity < 0 || (row_capacity > 0 && !row_keys)) return LS_EINVAL;
+    int64_t rounds = 0, entries = 0;
+    for (int s = 0; s < n_slots; ++s) {
+        if (n_windows[s] < 0 || windows_run[s] < 0) return LS_EINVAL;
+        if (n_windows[s] == 0) continue;
+        if (keys[s] >> 48) return LS_EINVAL;                                    // the window index sits above bit 47
+        if (windows_run[s] > (1 << 16) - (int64_t)n_windows[s]) return LS_ESTATE;       // a clip's windows stay below 2^16
+        if (n_windows[s] > rounds) rounds = n_windows[s];
+        entries += n_windows[s];
+        if (entries > INT32_MAX) return LS_EINVAL;
+    }
+    if (row_keys) {
+        if (entries > row_capacity) return LS_EINVAL;
+        int64_t p = 0;
+        for (int64_t r = 0; r < rounds; ++r)
+            for (int s = 0; s < n_slots; ++s)
+                if (n_windows[s] > r) row_keys[p++] = keys[s] + ((uint64_t)(windows_run[s] + r) << 48);
+    }
     *n_entries = (int32_t)entries;
     return LS_OK;
 }

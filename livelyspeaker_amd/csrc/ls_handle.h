@@ -111,6 +111,11 @@ struct ls_handle {
     // refilled by one generator launch per K steps inside the loop; K = what fits in trng_ring_bytes (ls_set_torch_ring_bytes)
     DevBuf trng_eps, trng_noise, trng_inz;
     size_t trng_ring_bytes = (size_t)256 << 20;
+    // Philox keyed per row (ls_philox_rows.hip): row_gidx [n] uint64 on the device, the gidx every stream of row b draws at; a keyed
+    // loop holds its address and fills the ring above from it.  rk_n: rows ls_set_row_keys set for ls_sample (0: none).  A keyed
+    // session pool (pl_keyed) rewrites the table ahead of every round from pl_key [S], the slots' keys.
+    DevBuf row_gidx;
+    int rk_n = 0;
     // ls_bpd / ls_vb_terms: x_start, the column's q_sample noise and x_t (internal layout), the noise tape in the internal layout, the
     // per-index coefficient table of k_vb_terms (built for schedule bpd_coef_version) and the [3][B][n_steps] results
     DevBuf bpd_x0, bpd_nz, bpd_xt, bpd_tape, bpd_coef, bpd_out;
@@ -153,6 +158,9 @@ struct ls_handle {
     std::vector<float> pl_scale_host;
     std::vector<char> pl_open, pl_have_emo, pl_have_text;
     std::vector<int32_t> pl_styled;
+    bool pl_keyed = false;              // ls_long_pool_keyed: PHILOX draws at pl_key[slot] + (the slot's own window << 48)
+    long long pl_joins = 0;             // joins since open: a keyed slot's default key
+    std::vector<uint64_t> pl_key;
     DevBuf pl_ring, pl_hand, pl_vid, pl_scale, pl_emo_id, pl_emotok, pl_text, pl_ctext, pl_table;
     // Cached graphs of the step loop, by loop key (ls_sample.cpp: loop_key holds everything a captured loop bakes in besides device
     // addresses, the batch and its step plan included).  At most kGraphCacheMax entries: a plain call whose key is missing drops them
@@ -205,7 +213,10 @@ void report_path(ls_handle* h, bool pair);
 // stream launches when it has none; kReplayOnly never captures.  The last two never destroy a graph, so they are safe with replays in flight.
 enum CachePolicy { kReplace, kKeep, kReplayOnly };
 int check_sampler_args(ls_handle* h, const ls_sample_args* a);
-int run_window_loop(ls_handle* h, const ls_sample_args* a, bool resident_inpaint, bool first, CachePolicy policy, int* graph_replayed);
+// keyed: PHILOX rows draw at row_gidx (the caller wrote rows [0, B) in stream order) in place of sample_offset + b
+int run_window_loop(ls_handle* h, const ls_sample_args* a, bool resident_inpaint, bool first, CachePolicy policy, int* graph_replayed, bool keyed = false);
+// the ring of a keyed loop for batches up to B and loops up to n_exec steps, so that no loop at a smaller batch moves it
+int size_key_ring(ls_handle* h, int B, int n_exec);
 inline float* x_plane(const ls_handle* h, int k) { return (k & 1) ? h->xb.f() : h->xa.f(); }      // x ahead of executed step k (xa / xb ping-pong)
 // ---- defined in ls_chain_plan.cpp (host only): slot -> clip, windows per slot, clips per window of a ragged long-form call
 void long_plan_drop(int B, int AL, const int64_t* lengths, std::vector<int>& row, std::vector<int>& wins, std::vector<int>& bw);

@@ -390,6 +390,19 @@ unsigned long long torch_randn_advance(long long n, int n_cu, int max_threads_pe
 TorchDraw torch_draw(float* dst, size_t dst_stride, long long n, int n_cu, int max_threads_per_cu, int perm, int skip_last);
 hipError_t launch_bcast_first(float* x, int B, int per, hipStream_t st);
 
+// ---- Philox draws keyed per row (ls_philox_rows.hip; ls_set_row_keys, a keyed session pool) ---------------------------------
+// Row b draws at gidx[b] (a device table at a fixed address, rewritten in stream order ahead of a loop) under call->seed.
+// launch_row_xt: x_T [B][T][JF] into x.  launch_row_draws: executed steps [k0, k0 + nsteps) into slots 0 .. nsteps - 1 of
+// eps [.][2][B][D] and noise [.][B][J][F][T]; step last_step draws no noise.
+struct RowDrawArgs {
+    const CallParams* call;
+    const unsigned long long* gidx;
+    float* x; float* eps; float* noise;
+    int B, JF, T, k0, nsteps, last_step;
+};
+hipError_t launch_row_xt(const RowDrawArgs& a, hipStream_t st);
+hipError_t launch_row_draws(const RowDrawArgs& a, hipStream_t st);
+
 // ---- SAG decoder kernels (ls_sag.hip) ----------------------------------------------------------
 hipError_t launch_sag_queries(const float* x, const float* wmap, const float* bmap, const float* pe, float* q, float* qc, int B,
                               int JF, int n_pre, int D, hipStream_t st);

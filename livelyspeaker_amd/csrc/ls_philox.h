@@ -35,6 +35,8 @@ __device__ __forceinline__ void box_muller(unsigned a, unsigned b, float& zc, fl
 // A ragged long-form call (ls_long_prepare_ragged) holds its clips longest-first and runs window w on the slots [0, B_w): b above is the
 // SLOT, in every kernel family, so the streams follow the slot and not the caller's row.  A batch that is already longest-first draws
 // what the equal-length call draws; another order draws what the call on the slot-ordered batch draws.  No table reaches the step kernels.
+// Keys per ROW (ls_set_row_keys; a keyed session pool: gidx = the clip's key + (the clip's own window << 48)) do not reach them either:
+// ls_philox_rows.hip draws such rows with the functions below from a table of whole gidx values and hands the loop tapes.
 // Elements 4*blk .. 4*blk+3 of stream (step_id, stream) of global sample gidx: ONE Philox block, two Box-Muller pairs.
 // Keyed by the global sample index, so the streams are invariant to how the batch is sharded over GPUs.
 __device__ __forceinline__ void philox_normal4(const CallParams* cp, unsigned long long gidx, unsigned step_id, unsigned stream,

@@ -1,9 +1,10 @@
 // Host side of the C-ABI declared in include/ls_hip.h: everything that runs diffusion steps.  The sampling loop exists once (begin_loop ->
-// enqueue_loop | enqueue_plms -> finish_loop; stream launches or a captured hipGraph; draws from whole-call tapes, segmented tapes, Philox or
+// enqueue_loop | enqueue_plms -> finish_loop; stream launches or a captured hipGraph; draws from whole-call tapes, segmented tapes, Philox (in the step kernels, or keyed per row through the ring: ls_philox_rows.hip) or
 // torch's GPU stream; run_window_loop is the same loop without its wait, for the chained windows of ls_chain_api.cpp), next to the single-step entries that enqueue the same launches on caller-held tensors (ls_forward, ls_step, ls_plms_step),
 // and the likelihood loop (ls_bpd: per schedule index q_sample, the denoiser alone and k_vb_terms, through the same capture-or-enqueue) with ls_vb_terms.
 #include "ls_handle.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -145,8 +146,9 @@ struct LoopCall {
     int B, n_exec;                  // n_exec executed steps: ordinal k = 0 .. n_exec - 1 runs schedule index n_exec - 1 - k
     size_t nelem;                   // elements of one x plane
     bool pair, tape, tdev, plms, inpaint, inp_noised;
+    bool keyed;                     // PHILOX with per-row keys: the draws come from row_gidx through the ring (ls_philox_rows.hip)
     bool inp_resident;              // the inpainting planes were filled on the device ahead of the loop (run_window_loop): no mask / motion to ingest
-    int ring_k;                     // TORCH_DEVICE: steps per ring refill
+    int ring_k;                     // TORCH_DEVICE / keyed: steps per ring refill
     size_t plms_stride;             // PLMS: floats between the planes of plms_buf
     TorchDrawArgs tda;              // TORCH_DEVICE: the per-step draws (stage_loop_inputs), and what x_T's draw shares with them
     unsigned long long x_adv;       // TORCH_DEVICE: generator offset x_T's draw consumed ahead of the steps'
@@ -181,13 +183,28 @@ Draws draws_at(const LoopCall& c, const DevBuf& eps, const DevBuf& noise, const 
 Draws slot_draws(const ls_handle* h, const LoopCall& c, int slot, int r, int k) { return draws_at(c, h->eps_slot[slot], h->noise_slot[slot], nullptr, r, r, (unsigned)k); }
 Draws loop_draws(const ls_handle* h, const LoopCall& c, unsigned e, int k) {
     if (c.tape) return draws_at(c, h->eps_tape, h->noise_tape, h->inp_tape.f(), e, k, e);
-    if (c.tdev) return draws_at(c, h->trng_eps, h->trng_noise, c.inp_noised ? h->trng_inz.f() : nullptr, k % c.ring_k, k % c.ring_k, (unsigned)k);
+    if (c.tdev || c.keyed) return draws_at(c, h->trng_eps, h->trng_noise, c.inp_noised ? h->trng_inz.f() : nullptr, k % c.ring_k, k % c.ring_k, (unsigned)k);
     return {nullptr, nullptr, nullptr, nullptr, e};
+}
+// what a keyed loop's two draw launches share (ls_philox_rows.hip): the key table, the ring, the shapes
+RowDrawArgs row_draw_args(const ls_handle* h, const LoopCall& c) {
+    RowDrawArgs r{};
+    r.call = static_cast<const CallParams*>(h->callp.p); r.gidx = static_cast<const unsigned long long*>(h->row_gidx.p);
+    r.eps = h->trng_eps.f(); r.noise = h->trng_noise.f();
+    r.B = c.B; r.JF = h->JF; r.T = h->T; r.last_step = c.n_exec - 1;
+    return r;
 }
 // refill the ring with steps k .. k + K - 1 (stream order: the steps that read it before are done)
 int refill_ring(ls_handle* h, const LoopCall& c, int k) {
+    const int nsteps = c.n_exec - k < c.ring_k ? c.n_exec - k : c.ring_k;
+    if (c.keyed) {
+        RowDrawArgs r = row_draw_args(h, c);
+        r.k0 = k; r.nsteps = nsteps;
+        HIPCHK(h, launch_row_draws(r, h->stream));
+        return LS_OK;
+    }
     TorchDrawArgs g = c.tda;
-    g.k0 = k; g.nsteps = c.n_exec - k < c.ring_k ? c.n_exec - k : c.ring_k;
+    g.k0 = k; g.nsteps = nsteps;
     g.rel0 = c.x_adv + (unsigned long long)k * c.tda.step_adv;
     HIPCHK(h, launch_torch_draws(g, h->stream));
     return LS_OK;
@@ -238,6 +255,10 @@ int begin_loop(ls_handle* h, const LoopCall& c, bool tags_first) {
         HIPCHK(h, launch_torch_draws(xa, st));
         if (a->const_noise) HIPCHK(h, launch_bcast_first(h->xio.f(), B, JF * h->T, st));
         HIPCHK(h, launch_to_internal(h->xio.f(), h->xa.f(), B, JF, st, h->T));
+    } else if (c.keyed) {
+        RowDrawArgs r = row_draw_args(h, c);
+        r.x = h->xa.f();
+        HIPCHK(h, launch_row_xt(r, st));
     } else {
         HIPCHK(h, launch_randn_fill(h->xa.f(), B, JF, static_cast<const CallParams*>(h->callp.p), 0u, st, h->T));
     }
@@ -287,7 +308,7 @@ int enqueue_loop(ls_handle* h, const LoopCall& c) {
     int rc;
     HIPCHK(h, coop_reset(h, st));              // a memset node at the head of the captured loop: replays start from zeroed granules
     for (int k = 0; k < c.n_exec; ++k) {
-        if (c.tdev && k % c.ring_k == 0 && (rc = refill_ring(h, c, k)) != LS_OK) return rc;
+        if ((c.tdev || c.keyed) && k % c.ring_k == 0 && (rc = refill_ring(h, c, k)) != LS_OK) return rc;
         const Draws d = loop_draws(h, c, (unsigned)k, k);
         StepArgs s = step_args(h, c, k, d);
         if (c.inpaint) {
@@ -341,6 +362,13 @@ int enqueue_plms(ls_handle* h, const LoopCall& c) {
     return LS_OK;
 }
 
+// steps of a batch of B that fit in the ring's budget (ls_set_torch_ring_bytes): at least one, at most the loop
+int ring_steps(const ls_handle* h, int B, bool inp_noised, int n_exec) {
+    const size_t per_step = ((size_t)2 * B * kD + (size_t)B * h->JF * h->T * (inp_noised ? 2 : 1)) * sizeof(float);
+    const size_t fit = h->trng_ring_bytes / per_step;
+    return fit < 1 ? 1 : fit > (size_t)n_exec ? n_exec : (int)fit;
+}
+
 // What the loop reads besides x: whole-call tapes, the PLMS planes, the inpainting inputs, the TORCH_DEVICE rings and their draws.
 // Every buffer here is held by address in a captured loop, hence ensure_pinned / ingest_pinned throughout.
 int stage_loop_inputs(ls_handle* h, LoopCall& c) {
@@ -363,14 +391,15 @@ int stage_loop_inputs(ls_handle* h, LoopCall& c) {
         if (rc != LS_OK) return rc;
     }
     if ((c.plms || c.inpaint) && (rc = ensure_pinned(h, h->fwd_cfg, nx)) != LS_OK) return rc;      // the denoiser alone leaves the model output here
-    if (c.tdev) {
+    if (c.tdev || c.keyed) {
         const size_t eps_step = (size_t)2 * B * kD;
-        const size_t per_step = (eps_step + nelem * (c.inp_noised ? 2 : 1)) * sizeof(float);
-        const size_t fit = h->trng_ring_bytes / per_step;
-        c.ring_k = fit < 1 ? 1 : fit > (size_t)c.n_exec ? c.n_exec : (int)fit;
+        c.ring_k = ring_steps(h, B, c.inp_noised, c.n_exec);
         if ((rc = ensure_pinned(h, h->trng_eps, eps_step * c.ring_k * sizeof(float))) != LS_OK) return rc;
         if ((rc = ensure_pinned(h, h->trng_noise, nx * c.ring_k)) != LS_OK) return rc;
         if (c.inp_noised && (rc = ensure_pinned(h, h->trng_inz, nx * c.ring_k)) != LS_OK) return rc;
+    }
+    if (c.tdev) {
+        const size_t eps_step = (size_t)2 * B * kD;
         // per step, in the reference's order: the style eps of the cond and the uncond pass (RAG.py:10-13, 120: randn_like of a
         // [B, 1, 512] std), the inpainting branch's q_sample re-noise while t > 0 (gaussian_diffusion.py:318), the step noise randn_like(x)
         // in x's memory order (:543 / :787; [T][B][J][F] from the second step on, _ref_strides in gaussian_diffusion.py)
@@ -400,6 +429,7 @@ std::string loop_key(const ls_handle* h, const LoopCall& c) {
     if (c.inpaint) key += c.inp_noised ? " I2" : " I1";
     if (c.plms) key += " O" + std::to_string(a->plms_order);
     if (c.tdev) key += " R" + std::to_string(c.ring_k) + (a->x_init ? "x" : "X");
+    if (c.keyed) key += " K" + std::to_string(c.ring_k);        // the draws come from row_gidx: never the loop an unkeyed call captured
     for (int d = 0; d < a->n_dump; ++d) key += "," + std::to_string(a->dump_steps[d]);      // the whole list, however long
     return key;
 }
@@ -579,8 +609,9 @@ int ls::check_sampler_args(ls_handle* h, const ls_sample_args* a) {
 // without its wait; the caller has set call_host, and the result is x_plane(h, n_exec).  resident_inpaint: the inpainting branch on
 // planes the caller filled on the device (a->inpaint_noised says whether they are re-noised).  first: the call's first window, whose
 // start (ev[6]; ev[0] is re-recorded by every window's begin_loop) and loop start (ev[1]) time the call.
-int ls::run_window_loop(ls_handle* h, const ls_sample_args* a, bool resident_inpaint, bool first, CachePolicy policy, int* graph_replayed) {
+int ls::run_window_loop(ls_handle* h, const ls_sample_args* a, bool resident_inpaint, bool first, CachePolicy policy, int* graph_replayed, bool keyed) {
     LoopCall c = loop_call(h, a);
+    c.keyed = keyed && a->noise_mode == LS_NOISE_PHILOX;
     if (resident_inpaint) { c.inpaint = true; c.inp_noised = a->inpaint_noised != 0; c.inp_resident = true; }
     int rc;
     if ((rc = begin_loop(h, c, true)) != LS_OK) return rc;
@@ -588,6 +619,17 @@ int ls::run_window_loop(ls_handle* h, const ls_sample_args* a, bool resident_inp
     if ((rc = stage_loop_inputs(h, c)) != LS_OK) return rc;
     if (first) HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
     return run_loop(h, c, graph_replayed, policy);
+}
+
+int ls::size_key_ring(ls_handle* h, int B, int n_exec) {
+    size_t eps = 0, nz = 0;
+    for (int b = 1; b <= B; ++b) {
+        const size_t k = (size_t)ring_steps(h, b, false, n_exec);
+        eps = std::max(eps, k * 2 * b * kD * sizeof(float)); nz = std::max(nz, k * b * h->JF * h->T * sizeof(float));
+    }
+    int rc;
+    if ((rc = ensure_pinned(h, h->trng_eps, eps)) != LS_OK || (rc = ensure_pinned(h, h->trng_noise, nz)) != LS_OK) return rc;
+    return ensure_pinned(h, h->row_gidx, (size_t)B * sizeof(unsigned long long));
 }
 
 namespace {
@@ -760,6 +802,19 @@ int ls_q_sample(ls_handle* h, int index, int on_device, size_t n, const float* x
     return LS_OK;
 }
 
+// Per-row Philox keys of ls_sample (ls_hip.h): the table a keyed loop reads, uploaded here; rk_n says for how many rows it holds
+int ls_set_row_keys(ls_handle* h, const uint64_t* keys, int32_t n) {
+    if (!h || n < 0 || (n > 0 && !keys)) return fail(h, LS_EINVAL, "ls_set_row_keys: null argument or negative count");
+    h->rk_n = 0;
+    if (n == 0) return LS_OK;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc;
+    if ((rc = ensure_pinned(h, h->row_gidx, (size_t)n * sizeof(uint64_t))) != LS_OK) return rc;
+    if ((rc = upload(h, h->row_gidx, keys, (size_t)n * sizeof(uint64_t))) != LS_OK) return rc;      // waits: the keys are the caller's again
+    h->rk_n = n;
+    return LS_OK;
+}
+
 // validate -> begin -> stage tapes / rings -> capture-or-enqueue -> finish
 int ls_sample(ls_handle* h, const ls_sample_args* a) {
     if (!h || !a) return fail(h, LS_EINVAL, "ls_sample: null argument");
@@ -767,6 +822,7 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
     if (!h->have_sched) return fail(h, LS_ESTATE, "ls_sample before ls_set_schedule");
     int rc;
     if ((rc = check_sampler_args(h, a)) != LS_OK) return rc;
+    if (h->rk_n > 0 && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EINVAL, "ls_sample: row keys are set (ls_set_row_keys) and the noise mode is not PHILOX");
     if (a->seg_count > 0) return sample_segment(h, a);
     h->seg_next = -1;
     if (!a->out) return fail(h, LS_EINVAL, "ls_sample: null out");
@@ -775,6 +831,12 @@ int ls_sample(ls_handle* h, const ls_sample_args* a) {
     if (!c.tape && !c.tdev && a->const_noise) return fail(h, LS_EUNSUPPORTED, "const_noise is supported in TAPE and TORCH_DEVICE modes only");
     if (c.tdev && (a->sample_offset & 3)) return fail(h, LS_EINVAL, "TORCH_DEVICE: the generator offset %llu is not a multiple of 4", (unsigned long long)a->sample_offset);
     if ((rc = check_dump_args(h, a)) != LS_OK) return rc;
+    if (h->rk_n > 0) {          // ls_set_row_keys
+        if (h->rk_n != c.B) return fail(h, LS_EINVAL, "ls_sample: %d row keys are set, the prepared batch is %d", h->rk_n, c.B);
+        if (a->sample_offset != 0) return fail(h, LS_EINVAL, "ls_sample: row keys replace sample_offset + b; sample_offset must be 0");
+        if (c.plms || c.inpaint) return fail(h, LS_EUNSUPPORTED, "ls_sample: row keys are not combined with PLMS or the inpainting branch");
+        c.keyed = true;
+    }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if ((rc = ensure_temb_table(h)) != LS_OK) return rc;
     h->call_host = CallParams{a->seed, a->sample_offset, h->tag_base, 0u};      // uploaded by begin_loop's advance_tags with this call's tag base
@@ -882,6 +944,7 @@ int ls_bpd(ls_handle* h, const ls_bpd_args* a) {
     if (!h->prepared) return fail(h, LS_ESTATE, "ls_bpd before ls_prepare");
     if (!h->have_sched) return fail(h, LS_ESTATE, "ls_bpd before ls_set_schedule");
     if (a->noise_mode == LS_NOISE_TORCH_DEVICE) return fail(h, LS_EUNSUPPORTED, "ls_bpd: TORCH_DEVICE draws are not generated in the column loop");
+    if (h->rk_n > 0 && a->noise_mode == LS_NOISE_PHILOX) return fail(h, LS_EUNSUPPORTED, "ls_bpd: row keys (ls_set_row_keys) are not built for the column loop");
     if (a->noise_mode != LS_NOISE_TAPE && a->noise_mode != LS_NOISE_PHILOX) return fail(h, LS_EINVAL, "bad noise_mode");
     if (a->col_begin < 0 || a->col_count < 1 || a->col_count > h->n_steps - a->col_begin)
         return fail(h, LS_EINVAL, "columns [%d, %d + %d) outside the schedule's %d", a->col_begin, a->col_begin, a->col_count, h->n_steps);

@@ -156,6 +156,13 @@ class GaussianDiffusion:
     device_ring_bytes = 256 << 20
     philox_seed = None              # philox mode: None = draw the key from torch's generator per call
     last_philox_seed = None
+    #: philox mode, p_sample_loop / ddim_sample_loop: None, or one key in [0, 2^64) per row of the batch (tensor, array or list [B]).  Row b
+    #: then draws every one of its streams -- x_T, the two style eps per step, the step noise -- at gidx = row_keys[b] in place of
+    #: sample_offset + b (the counter layout of csrc/ls_philox.h / oracle/philox_oracle.py), so rows {3, 17, 42} of an earlier call can be
+    #: drawn again by themselves: row_keys = o + arange(B) is bit for bit the call at sample_offset = o.  ValueError: another noise source,
+    #: a wrong length, a nonzero sample_offset beside it, sharded sampling.  NotImplementedError: plms_sample_loop, the inpainting branch,
+    #: calc_bpd_loop, sample_long / edit_long / open_stream / open_pool (a pool has keys of its own: open_pool(noise_keys='clip')).
+    row_keys = None
 
     def __init__(self, *, betas, model_mean_type, model_var_type, loss_type, rescale_timesteps=False,
                  lambda_rcxyz=0., lambda_vel=0., lambda_pose=1., lambda_orient=1., lambda_loc=1.,
@@ -254,6 +261,27 @@ class GaussianDiffusion:
         drawn = ref_draws.philox_key()
         self.last_philox_seed = drawn if self.philox_seed is None else int(self.philox_seed)
         return {"philox_seed": self.last_philox_seed, "sample_offset": int(getattr(self, "sample_offset", 0))}
+
+    def _row_keys(self, batch):
+        """`row_keys` as uint64 [batch], or None; the refusals that need no engine."""
+        if self.row_keys is None:
+            return None
+        self._check_noise_source()
+        if self.noise_source != "philox":
+            raise ValueError(f"row_keys are Philox keys: noise_source is {self.noise_source!r}, not 'philox'")
+        keys = self.row_keys.detach().cpu().tolist() if th.is_tensor(self.row_keys) else np.asarray(self.row_keys).reshape(-1).tolist()
+        if len(keys) != int(batch):
+            raise ValueError(f"row_keys holds {len(keys)} keys, the batch is {int(batch)}")
+        if int(getattr(self, "sample_offset", 0)) != 0:
+            raise ValueError("row_keys replace sample_offset + b: leave sample_offset at 0 (a key is the whole gidx)")
+        keys = [int(k) for k in keys]
+        if any(k < 0 or k >= 1 << 64 for k in keys):
+            raise ValueError("row_keys outside [0, 2^64)")
+        return np.asarray(keys, dtype=np.uint64)
+
+    def _no_row_keys(self, what):
+        if self.row_keys is not None:
+            raise NotImplementedError(f"{what}: row_keys are built for p_sample_loop and ddim_sample_loop only")
 
     @staticmethod
     def _dump_steps(dump_steps, n_exec):
@@ -473,6 +501,7 @@ class GaussianDiffusion:
         order = self._plms_order(order, True, n_exec)
         self._reject(denoised_fn, cond_fn, randomize_class, cond_fn_with_grad)
         self._no_inpainting(model_kwargs, "plms_sample_loop")
+        self._no_row_keys("plms_sample_loop")
         self._check_noise_source()
         tdev = self.noise_source == "torch_device"
         if tdev:                                    # refused before the engine is touched
@@ -546,6 +575,7 @@ class GaussianDiffusion:
         on x_start's device.  noise_source 'torch_cpu' makes the reference's draws from torch's CPU generator (tapes larger than
         tape_segment_bytes go through in column segments), 'philox' draws on the device; 'torch_device' is not built for this loop."""
         self._no_inpainting(model_kwargs, "calc_bpd_loop")
+        self._no_row_keys("calc_bpd_loop")
         self._check_noise_source()
         if self.noise_source == "torch_device":
             raise NotImplementedError("calc_bpd_loop: noise_source='torch_device' is not built for the likelihood loop; use "
@@ -583,7 +613,8 @@ class GaussianDiffusion:
     def _loop(self, sampler, model, shape, noise, clip_denoised, model_kwargs, device, skip_timesteps, init_image,
               dump_steps, const_noise, eta):
         tdev, philox = self.noise_source == "torch_device", self.noise_source == "philox"
-        if tdev:                                    # refused before the engine is touched
+        row_keys = self._row_keys(shape[0])         # refused before the engine is touched
+        if tdev:
             _torch_device(device if device is not None else next(model.parameters()).device, "sample loop")
         eng = self._engine_for(model, model_kwargs, "sample loop")
         shape = self._prepared_shape(eng, shape)
@@ -606,6 +637,10 @@ class GaussianDiffusion:
             if const_noise:
                 raise NotImplementedError("const_noise needs noise_source='torch_cpu'")
             kw.update(self._philox_key())
+            if row_keys is not None:
+                if inp is not None:
+                    raise NotImplementedError("row_keys are not built for the inpainting branch (its re-noise stream)")
+                kw.update(row_keys=row_keys, torch_ring_bytes=self.device_ring_bytes)
             if inp is not None:
                 kw["inpaint"] = (inp[0], inp[1], None, inp[2])           # the re-noising draws come from the device stream too
         else:

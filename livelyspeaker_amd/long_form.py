@@ -118,6 +118,9 @@ def _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, n_
     if diffusion.noise_source == "torch_device":
         raise NotImplementedError("sample_long: noise_source='torch_device' is not built for chained windows; use 'torch_cpu' or 'philox'")
     diffusion._check_noise_source()
+    if getattr(diffusion, "row_keys", None) is not None:
+        raise NotImplementedError("sample_long: diffusion.row_keys key the rows of p_sample_loop / ddim_sample_loop; chained windows draw at "
+                                  "sample_offset + b + (w << 48), and a pool's clips at their own keys (open_pool(noise_keys='clip'))")
     if sampler not in ("ddim", "ddpm"):
         raise ValueError(f"sampler must be 'ddim' or 'ddpm', got {sampler!r}")
     rag = model.model
@@ -464,7 +467,8 @@ def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, samp
 
     Noise (``diffusion.noise_source``): ``'torch_cpu'`` draws a window's tape at the push that runs it, in window order
     (``RefDraws.windows`` per push; the one-window ``tape_segment_bytes`` bound applies); ``'philox'`` takes its key here, once, and
-    window w draws at ``sample_offset + b + (w << 48)`` -- a key must not repeat, so a stream runs at most 2^16 windows under
+    window w draws at ``sample_offset + b + (w << 48)`` -- clip b is keyed as a clip of a keyed pool is (``open_pool(noise_keys='clip')``),
+    with ``key = sample_offset + b`` -- and a key must not repeat, so a stream runs at most 2^16 windows under
     ``'philox'`` (about 36 hours of audio; the push that would run the next one raises ``_lib.EngineError``); ``'torch_device'`` is
     refused.
 
@@ -500,12 +504,17 @@ def pool_plan(samples_in, windows_run, new, closing, open, cfg):
 
 
 class LongPool(_Session):
-    """A running ``open_pool`` session; see there.  ``slots``: per-slot host arrays ``samples_in``, ``windows_run``, ``frames_out``, ``open``."""
+    """A running ``open_pool`` session; see there.  ``slots``: per-slot host arrays ``samples_in``, ``windows_run``, ``frames_out``, ``open``,
+    and in a keyed pool ``key`` (uint64; of a free slot: its last clip's)."""
 
-    def __init__(self, diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post=None):
+    def __init__(self, diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post=None, noise_keys=None):
         S = int(capacity)
         if S < 1:
             raise ValueError(f"capacity must be >= 1, got {capacity}")
+        if noise_keys not in (None, "clip"):
+            raise ValueError(f"noise_keys must be None or 'clip', got {noise_keys!r}")
+        if noise_keys == "clip" and diffusion.noise_source != "philox":
+            raise ValueError(f"noise_keys='clip' keys Philox draws: noise_source is {diffusion.noise_source!r}, not 'philox'")
         rag = getattr(model, "model", None)
         beat = getattr(rag, "n_prefix_tokens", 1) == 2
         npre, J, F = (int(getattr(rag, k, 1)) for k in ("n_pre_seq", "njoints", "nfeats"))
@@ -517,8 +526,12 @@ class LongPool(_Session):
         self._diffusion, self._rag, self._sag, self._S = diffusion, rag, sag, S
         self._init_post(post, rag, S)
         self._kw = _loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised)
-        if diffusion.noise_source == "philox":          # one key per pool: row r of round q draws at sample_offset + r + (q << 48)
+        self._keyed, self._joins = noise_keys == "clip", 0
+        if diffusion.noise_source == "philox":          # one seed per pool: row r of round q draws at sample_offset + r + (q << 48); keyed: at the clip's key
             self._kw.update(diffusion._philox_key())
+            self._offset = int(self._kw["sample_offset"])
+            if self._keyed and not 0 <= self._offset < 1 << 48:
+                raise ValueError(f"noise_keys='clip': sample_offset {self._offset} outside [0, 2^48) (the default keys start there)")
         else:                                           # the largest round a push can run
             _check_tape_bound(diffusion, "open_pool", diffusion.num_timesteps - int(skip_timesteps), (S, J, F, int(rag.nframes)), int(rag.latent_dim))
         self._n_exec = diffusion.num_timesteps - int(skip_timesteps)
@@ -527,6 +540,8 @@ class LongPool(_Session):
         self._last_dev = th.device("cpu")
         self._state = {"samples_in": np.zeros(S, np.int64), "windows_run": np.zeros(S, np.int64), "frames_out": np.zeros(S, np.int64),
                        "open": np.zeros(S, bool)}
+        if self._keyed:
+            self._state["key"] = np.zeros(S, np.uint64)
         self._have_text = np.zeros(S, bool)
 
     @property
@@ -535,18 +550,28 @@ class LongPool(_Session):
 
     def _open(self, eng):
         eng.long_pool_open(self._S)
+        if self._keyed:
+            eng.long_pool_keyed(True)
 
     def _refresh(self):
         info = self._eng.long_pool_info()
         for k in self._state:
-            self._state[k] = np.array(info[k])
+            if k != "key":          # the keys are held here: the engine has what join set
+                self._state[k] = np.array(info[k])
 
-    def join(self, seed_poses, vid_index, scale, emo=None, text_features=None, slot=None):
+    def join(self, seed_poses, vid_index, scale, emo=None, text_features=None, slot=None, key=None):
         """Open a slot for a new clip: ``seed_poses`` [J, F, n_pre], its speaker id and guidance scale, ``emo`` (BEAT: required) and
         ``text_features`` [512] (with ``sag=``; may also come with the push that runs the slot's first window).  Returns the slot: the
-        lowest free one unless ``slot`` names one.  Nothing is sampled and nothing is drawn."""
+        lowest free one unless ``slot`` names one.  Nothing is sampled and nothing is drawn.  ``key`` (a pool opened with
+        ``noise_keys='clip'`` only; ``ValueError`` otherwise): the clip's Philox key, an int in [0, 2^48); default
+        ``diffusion.sample_offset`` + the joins since the pool was opened."""
         if self._closed:
             raise RuntimeError("the pool is closed")
+        if key is not None:
+            if not self._keyed:
+                raise ValueError("join(key=) needs a keyed pool: open_pool(..., noise_keys='clip')")
+            if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < 1 << 48:
+                raise ValueError(f"key must be an int in [0, 2^48), got {key!r}")
         rag, S = self._rag, self._S
         seed_poses, text_features = _as_tensors(seed_poses, text_features)
         if _shape(seed_poses) != (rag.njoints, rag.nfeats, rag.n_pre_seq):
@@ -575,6 +600,11 @@ class LongPool(_Session):
         eng = self._engine()
         eng.long_pool_join(slot, seed_poses.float(), one(vid_index, th.long), one(scale, th.float32), None if emo is None else one(emo, th.long),
                            None if text_features is None else text_features.float())
+        if self._keyed:
+            k = (self._offset + self._joins) % (1 << 48) if key is None else int(key)
+            eng.long_pool_set_key(slot, k)
+            self._state["key"][slot] = k
+        self._joins += 1
         self._refresh()
         self._have_text[slot] = text_features is not None
         return slot
@@ -661,7 +691,16 @@ class LongPool(_Session):
         return res
 
 
-def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False, sag=None, post=None):
+def pool_keys(keys, windows_run, n_windows):
+    """The key table of one push of a keyed pool (``open_pool(noise_keys='clip')``), from host counts alone (no GPU): uint64
+    [sum n_windows] in ``pool_plan``'s row order.  Slot s, holding ``keys[s]`` in [0, 2^48) with ``windows_run[s]`` windows run, runs
+    ``n_windows[s]`` windows in this push; its row in round r draws every Philox stream at ``gidx = keys[s] + ((windows_run[s] + r) <<
+    48)``.  ``ValueError``: a key of a running slot at or above 2^48; ``_lib.EngineError``: a clip's window index would reach 2^16.  One
+    definition for the engine and for this module (``ls_long_pool_keys``)."""
+    return _lib.long_pool_keys(keys, windows_run, n_windows)
+
+
+def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False, sag=None, post=None, noise_keys=None):
     """``open_stream`` for clips that start and stop at different times and arrive at different rates: a session pool of ``capacity``
     slots on ONE engine.
 
@@ -689,6 +728,19 @@ def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=
     clip's draws depend on the push schedule and on which slots run beside it.  A pool runs at most 2^16 rounds under ``'philox'``.
     ``'torch_device'`` is refused.
 
+    ``noise_keys='clip'`` (needs ``'philox'``; ``ValueError`` otherwise) makes a clip's noise its own.  Every clip has a KEY, an int in
+    [0, 2^48): ``join(key=)``, default ``diffusion.sample_offset`` + the joins since the pool was opened (a pool joined in order holds
+    ``o, o + 1, ...``); ``pool.slots['key']`` lists them.  The clip in slot s draws in its own window w (``slots['windows_run'][s]``, 0
+    again after a ``join``) at ``gidx = key + (w << 48)`` under the pool's one seed (``pool_keys`` is the table of a push).  THE CONTRACT:
+    a clip's frames are a function of the model, the schedule, its own audio and conditioning, the seed and its key -- not of the other
+    slots, the slot index, the chunking or the pool's age.  They are what ``sample_long`` gives for that audio with
+    ``diffusion.sample_offset = key`` and the same seed: bit for bit where both runs go through the same kernel family at the same
+    batch, and otherwise as far apart as two of the project's kernel families are.  So a session can be replayed or regenerated offline,
+    one clip at a time.  Two open slots may hold the same key: same audio and conditioning then give the same frames; nothing polices
+    it.  A clip may run 2^16 windows (the push that would run the next raises ``_lib.EngineError``); the pool's round count is no
+    limit.  ``join(key=)`` on a pool that is not keyed raises ``ValueError``.  The draws of a keyed round are written to device tapes
+    by one small launch per ring refill (csrc/ls_philox_rows.hip) and the step kernels read them as they read ``'torch_device'`` draws.
+
     Device memory is allocated for ``capacity`` slots when the engine is bound (the first ``join``) and does not grow
     (``Engine.long_pool_info()['device_bytes']``).  A ``ddim_sample_loop``, ``sample_long``, ``edit_long`` or ``open_stream`` push on the
     same model replaces the engine's conditioning and ends the pool (the next call raises ``_lib.EngineError``).  ``close`` and
@@ -699,9 +751,9 @@ def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=
     ``leave`` and ``close`` finish the series of the slots they end, and a ``join`` into a freed slot starts a fresh one.  A call may
     complete at most 256 frames per slot then.  With ``post=None`` nothing changes.
 
-    Not built: device-resident ``lengths``, Philox keyed by (slot, window), ``edit_long`` on a pool, PLMS, ``const_noise``,
+    Not built: device-resident ``lengths``, ``edit_long`` on a pool, PLMS, ``const_noise``,
     ``dump_steps``, sharded calls, a non-blocking ``push``."""
-    return LongPool(diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post)
+    return LongPool(diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post, noise_keys)
 
 
 def _edit_ranges(frames, B, n_frames):

@@ -303,6 +303,8 @@ def sample_sharded(sample_fn, model, global_shape, y_global: dict, diffusion=Non
     if getattr(owner, "noise_source", None) == "torch_device":
         raise NotImplementedError("noise_source='torch_device' reproduces a single-GPU run of the reference (which has no multi-GPU "
                                   "sampling); sharded sampling runs noise_source='philox'")
+    if getattr(owner, "row_keys", None) is not None:
+        raise ValueError("row_keys key the rows of ONE call; a sharded call keys its rows by sample_offset = the shard's first global index")
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     total = int(global_shape[0])

@@ -2,6 +2,8 @@
 
     python tools/long_pool_time.py               # S = 4 and 8 speakers (profiles/r23_long_pool.md)
     python tools/long_pool_time.py 4             # one pool size
+    python tools/long_pool_time.py --keyed       # a keyed pool (noise_keys='clip') against an unkeyed one at 1, 4, 8 and 32 speakers
+                                                 # (profiles/r28_pool_keys.md); sizes may follow
 
 TED, Philox noise, guidance 1.5, device-resident inputs, hipGraph replay, ddim100 skip 80 (20 steps per window).  S speakers talk at the
 same rate but started at different times: speaker s is s * 32000 / S samples ahead of speaker 0, so their windows complete at staggered
@@ -13,7 +15,11 @@ times.  Audio arrives in TICKS: every tick brings every speaker the same number 
 The pool takes a tick as ONE push on one model; the baseline is what the interface offered before it: S models with the same weights,
 one open_stream at batch 1 each, pushed in turn.  Per tick the two are timed back to back (host clock around calls that end in the
 engine's own wait), pool first on even ticks and baseline first on odd ones; WARM ticks warm up, TICKS ticks are timed; median and
-worst per tick, and per completed window.  The shader clock is sampled alongside (long_form_time.ClockSampler)."""
+worst per tick, and per completed window.  The shader clock is sampled alongside (long_form_time.ClockSampler).
+
+--keyed: two pools with the same weights on two models, one opened with noise_keys='clip', fed the same ticks and timed the same way,
+keyed first on even ticks.  What the keys add to a round: the upload of its rows of the key table, one draw launch per ring refill
+(csrc/ls_philox_rows.hip) and the step kernels reading their draws from the ring in place of computing them."""
 import os
 import statistics
 import sys
@@ -90,7 +96,63 @@ def run(S, per_tick, cfg, pool_model, stream_models, diffusion, clocks):
         st.close()
 
 
+def run_keyed(S, per_tick, cfg, models, diffusion, clocks):
+    AL = cfg.audio_len
+    n_ticks = WARM + TICKS
+    lead = [s * STRIDE // S for s in range(S)]
+    total = AL + max(lead) + n_ticks * per_tick
+    y = {k: torch.from_numpy(v).to(DEV) for k, v in synth.make_long_cond(cfg, S, -(-total // STRIDE) + 1).items()}
+    pools = [long_form.open_pool(diffusion, m, S, sampler="ddim", skip_timesteps=SKIP, noise_keys=nk) for m, nk in zip(models, ("clip", None))]
+    fed = [AL + lead[s] for s in range(S)]
+    head = torch.zeros(S, max(fed), device=DEV)
+    for s in range(S):
+        head[s, :fed[s]] = y["audio"][s, :fed[s]]
+    for pool in pools:
+        for s in range(S):
+            assert pool.join(y["seed_poses"][s], y["vid_indices"][s], y["scale"][s]) == s
+        pool.push(head, fed)
+    torch.cuda.synchronize()
+    clocks.take()
+    ms, windows = ([], []), 0
+    for t in range(n_ticks):
+        chunk = torch.stack([y["audio"][s, fed[s]:fed[s] + per_tick] for s in range(S)]).contiguous()
+        order = (0, 1) if t % 2 == 0 else (1, 0)
+        got = {}
+        for i in order:
+            got[i] = timed(lambda: pools[i].push(chunk, [per_tick] * S)[1])
+        assert got[0][1].tolist() == got[1][1].tolist()
+        fed = [n + per_tick for n in fed]
+        if t >= WARM:
+            for i in (0, 1):
+                ms[i].append(got[i][0])
+            windows += sum(1 for c in got[0][1] if c)
+    tm = models[0].model.engine().timing()
+    med_k, med_u = statistics.median(ms[0]), statistics.median(ms[1])
+    print(f"S={S:2d}, {per_tick:5d} samples per tick ({windows / TICKS:.2f} windows per tick): keyed push {med_k:8.2f} / {max(ms[0]):8.2f}   "
+          f"unkeyed push {med_u:8.2f} / {max(ms[1]):8.2f}   ratio of medians {med_k / med_u:.3f}   per completed window: keyed "
+          f"{sum(ms[0]) / windows:.3f}, unkeyed {sum(ms[1]) / windows:.3f} ms   | last keyed push: graph replayed {tm['graph_replayed']} of "
+          f"{tm['n_segments']}, step path {tm['step_path']} | {clocks.take()}", flush=True)
+    for pool in pools:
+        pool.close()
+
+
+def main_keyed(sizes):
+    cfg, model_k, diffusion = build()
+    model_u = build()[1]
+    diffusion.noise_source, diffusion.philox_seed = "philox", 1
+    clocks = ClockSampler()
+    clocks.start()
+    print(f"# TED ddim100 skip {SKIP}, CFG 1.5, philox, device inputs, graph replay; {TICKS} ticks after {WARM} warm-up ticks, a push of a keyed "
+          f"pool alternated with the same push of an unkeyed one; ms per tick, median / worst")
+    for S in sizes or [1, 4, 8, 32]:
+        for per_tick in sorted({STRIDE, STRIDE // S}, reverse=True):
+            run_keyed(S, per_tick, cfg, (model_k, model_u), diffusion, clocks)
+    clocks.on = False
+
+
 def main():
+    if "--keyed" in sys.argv[1:]:
+        return main_keyed([int(a) for a in sys.argv[1:] if a != "--keyed"])
     sizes = [int(sys.argv[1])] if len(sys.argv) > 1 else [4, 8]
     cfg, pool_model, diffusion = build()
     stream_models = [build()[1] for _ in range(max(sizes))]
