@@ -12,7 +12,8 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py [batch] --long-seconds N
     python examples/livelyspeaker_ted.py --long-seconds A,B,... [--drop-finished]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --edit-frames LO,HI [--edit-joints J0,J1,...] [--edit-text [--clip-text]]
-    python examples/livelyspeaker_ted.py [batch] --long-seconds N --stream-chunk SECONDS
+    python examples/livelyspeaker_ted.py [batch] --long-seconds N --stream-chunk SECONDS [--post [--score]]
+    python examples/livelyspeaker_ted.py [batch] --long-seconds N --score-talk
     python examples/livelyspeaker_ted.py --pool SPEAKERS
     python examples/livelyspeaker_ted.py [batch] --clip-text
 --clip-text starts from TOKENS instead of a stand-in feature: synthetic clip.tokenize output -> CLIPTextEncoder (the text tower of CLIP
@@ -42,6 +43,10 @@ kept ones from the existing motion; it prints how far the edited frames moved fr
 it prints when each window's frames appeared and checks that the frames, concatenated, are bit for bit the timeline of the one call.
 --post (with --stream-chunk) lets the stream own a post-processing stream (open_stream(post='ted')): every push also returns the new
 frames' joint positions and the motion beats that have just become decidable, and it prints the pose shape and the beat times per push.
+--score (with --post) lets it own a score stream as well (open_stream(post='ted', score=True, max_seconds=N)): the audio of every push and
+the beats of the post stream go in, and the close prints the beat-consistency score, which is the one call's BC bit for bit.
+--score-talk (with --long-seconds N) scores the timeline with long_form.score_talk, which has no limit of 4096 frames: --long-seconds 900
+--score-talk makes and scores a quarter of an hour (without it, the scoring of the one call stops at 131 s of audio).
 --pool SPEAKERS serves that many LIVE speakers from one engine (long_form.open_pool): they start 1.3 s apart and talk for different
 times, each joins a slot when it starts and leaves it when its speech ends, audio arrives for all of them every half second, and every
 push runs the windows that are complete -- of whichever speakers -- as one batch.  It prints who joined, which batch ran, and who left.
@@ -215,6 +220,14 @@ def main():
             sys.argv.remove("--post")
             if stream_chunk is None:
                 raise SystemExit("--post goes with --stream-chunk: the stream's frames are post-processed as they arrive")
+        score = "--score" in sys.argv
+        if score:
+            sys.argv.remove("--score")
+            if not post:
+                raise SystemExit("--score goes with --stream-chunk --post: it scores the beats of the post-processing stream")
+        score_talk = "--score-talk" in sys.argv
+        if score_talk:
+            sys.argv.remove("--score-talk")
         drop = "--drop-finished" in sys.argv
         if drop:
             sys.argv.remove("--drop-finished")
@@ -227,7 +240,7 @@ def main():
         if drop:
             raise SystemExit("--drop-finished goes with a comma list of durations: equally long speeches finish together")
         seconds = float(arg)
-        return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source, edit, stream_chunk, post)
+        return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source, edit, stream_chunk, post, score, score_talk)
     if "--clip-text" in sys.argv:
         sys.argv.remove("--clip-text")
         return main_clip_text(int(sys.argv[1]) if len(sys.argv) > 1 else 64, noise_source)
@@ -346,7 +359,7 @@ def main_clip_text(B, noise_source):
     assert bool(torch.isfinite(sample).all()) and bool(torch.isfinite(decoded).all())
 
 
-def main_long(B, seconds, noise_source, edit=None, stream_chunk=None, post=False):
+def main_long(B, seconds, noise_source, edit=None, stream_chunk=None, post=False, score=False, score_talk=False):
     """`seconds` of 16 kHz speech per clip -> one stitched timeline at 15 fps (the LivelySpeaker chain, window after window on the device)."""
     import numpy as np
     from livelyspeaker_amd import long_form
@@ -371,18 +384,18 @@ def main_long(B, seconds, noise_source, edit=None, stream_chunk=None, post=False
     print(f"B={B} ({noise_source}): {seconds:g} s of speech -> {W} chained windows, {n_frames} frames ({n_frames / 15:.1f} s of gesture) in "
           f"{dt * 1e3:.1f} ms ({B * n_frames / dt:.0f} pose-frames/s)")
     # the timeline as one series per clip: joint positions, motion beats and the beat-consistency score against the speech, on the device
-    scored = long_form.score_timeline(timeline, audio)
+    scored = long_form.score_talk(timeline, audio) if score_talk else long_form.score_timeline(timeline, audio)
     n_beats = sum(len(b) for b in scored["motion_beat_times"])
     print(f"pose {tuple(scored['pose'].shape)}, motion beats {n_beats}, BC {scored['bc']:.4f} (synthetic weights and audio: numbers are "
-          f"not quality)")
+          f"not quality)" + (f"; score_talk: {int(scored['onset_count'].sum())} audio onsets in {audio.shape[1] // 512 + 1} audio frames" if score_talk else ""))
     assert tuple(scored["pose"].shape) == (B, n_frames, 10, 3) and bool(torch.isfinite(scored["pose"]).all())
     if edit is not None:
         edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit, sag_decoder)
     if stream_chunk is not None:
-        stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, stream_chunk, scored if post else None)
+        stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, stream_chunk, scored if post else None, score)
 
 
-def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, chunk_seconds, scored=None):
+def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, chunk_seconds, scored=None, score=False):
     """The waveform main_long sampled in one call, fed to a stream `chunk_seconds` at a time: every push carries the text feature of the
     window it would start (a held value), and a window's frames come back from the push that completed its audio.  `scored` (the
     timeline's post-processing, --post): the stream post-processes its frames as they arrive, and the pushes' poses and beats,
@@ -390,7 +403,8 @@ def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y
     n, L, W = max(1, int(round(chunk_seconds * 16000))), audio.shape[1], text.shape[1]
     torch.manual_seed(233)                                                                  # the seed of the one call: the same draws
     stream = long_form.open_stream(diffusion, model, y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim", skip_timesteps=80,
-                                   sag=sag_decoder, post=None if scored is None else "ted")
+                                   sag=sag_decoder, post=None if scored is None else "ted",
+                                   **({"score": True, "max_seconds": L / 16000 + 1} if score else {}))
     parts, poses, beats, t0 = [], [], [[] for _ in range(audio.shape[0])], time.perf_counter()
     for lo in list(range(0, L, n)) + [None]:
         held = {"text_features": text[:, min(stream.windows_run, W - 1)]}
@@ -417,6 +431,11 @@ def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y
     if scored is not None:
         assert torch.equal(torch.cat(poses, dim=1), scored["pose"]) and beats == scored["motion_beat_times"]
         print(f"post-processed as they arrived: {sum(len(b) for b in beats)} motion beats, poses and beats bit for bit those of the whole timeline")
+    if score:
+        result = posted["score"]                                                            # the close finished every clip's series
+        assert result["bc"] == scored["bc"] or (result["bc"] != result["bc"] and scored["bc"] != scored["bc"])
+        print(f"scored at the close: {sum(r['count'] for r in result['slots'].values())} audio onsets, BC {result['bc']:.4f}, bit for bit the "
+              f"one call's")
 
 
 def main_pool(speakers, noise_source, tick_seconds=0.5, keyed=False):

@@ -1012,8 +1012,8 @@ int ls_ragged_tiles(int batch, const int32_t* frames, int tile, int32_t* clip_ou
  * entries are emitted and the slot is free -- its next frames start a new series at frame 0.  A failed launch marks the handle failed
  * (LS_ESTATE from then on).  frames and the tensor outputs are device pointers iff on_device; counts, finish, beat_first and
  * beat_count are HOST arrays in both modes.
- * Not built: device-resident counts, chunks above LS_POST_STREAM_MAX_CHUNK frames per push, SRGR (it needs targets), audio onsets and
- * the alignment scores online (librosa normalises the onset envelope by the whole signal's extrema). */
+ * Audio onsets and the alignment scores: at the finish, score stream (ls_score_stream_*).  Not built: device-resident counts, chunks
+ * above LS_POST_STREAM_MAX_CHUNK frames per push, SRGR (it needs targets). */
 #define LS_POST_STREAM_MAX_CHUNK 256
 #define LS_POST_STREAM_MAX_ORDER 8
 typedef struct ls_post_stream ls_post_stream;
@@ -1096,6 +1096,19 @@ int ls_onsets(int device, const ls_onsets_args* a);
  * runs one wave per valid frame (sum of F_b).  LS_EINVAL without a launch: a NULL lengths, an entry outside [1, length], reflect
  * padding with an entry <= 1024, and whatever ls_onsets refuses.  Not built: device-resident length arrays. */
 int ls_onsets_ragged(int device, const ls_onsets_args* a, const int32_t* lengths);
+/* ls_onsets for an equal-length batch of clips of ANY length (a talk of a quarter of an hour has 28 000 frames): the arguments and
+ * the meaning of ls_onsets -- audio or a given envelope, every output nullable, kernel_ms -- without LS_ONSETS_MAX_FRAMES.  The
+ * spectrum is ls_onsets' kernel.  What follows it runs over (clip, tile of LS_SCORE_TILE frames) with nothing in LDS sized by the
+ * clip: tile partials and a combine for the clip maximum of mel_db and the envelope's extrema (exact in any order), the flux and
+ * the detection flag per frame with the windows read from global memory, the flagged frames compacted per tile and walked by one
+ * wave per clip (n > last + wait is sequential in the candidates, not the frames), one thread per onset searching left for both
+ * backtracks.  Every float is a per-frame expression or an exact reduction: up to LS_ONSETS_MAX_FRAMES frames every output equals
+ * ls_onsets' bit for bit.  kernel_ms[1] covers all launches of the pick.  Device memory beyond the outputs: mel_db (512 B per
+ * frame) and 12 B per frame of candidates and slabs where the caller leaves them out.  LS_EINVAL without a launch: whatever
+ * ls_onsets refuses except the frame count, length > 2^31 - 2048, and B * F frames beyond the grid (2^33 - 4).  Not built: the
+ * ragged form. */
+#define LS_SCORE_TILE 256
+int ls_onsets_long(int device, const ls_onsets_args* a);
 
 /* The tables ls_onsets computes with, built on the host in double and rounded to float32: window [n_fft] (periodic Hann), twiddle
  * [n_fft][2] (exp(-2 pi i n / n_fft)), and librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax, htk=False, norm='slaney') in CSR
@@ -1104,6 +1117,100 @@ int ls_onsets_ragged(int device, const ls_onsets_args* a, const int32_t* lengths
  * n_mels < 1, nnz_cap < nnz when the CSR arrays are asked for.  No device is touched. */
 int ls_onsets_tables(float sr, int n_fft, int n_mels, float fmin, float fmax, float* window, float* twiddle, int32_t* mel_ptr,
                      int32_t* mel_col, float* mel_w, int32_t nnz_cap, int32_t* nnz_out);
+
+/* ---- Score stream: audio onsets and the beat-alignment scores for series of any length -----------------------
+ * Only two steps of librosa's onset chain need the whole signal -- the clamp at (max - 80 dB) and the envelope's min / max
+ * normalisation -- and both are order-independent reductions.  The spectrum is causal.  So the chain splits: spectra as audio
+ * arrives (ls_score_stream_push), the tiled pick of ls_onsets_long and the alignment sums when a series ends
+ * (ls_score_stream_finish).  A handle has `capacity` SLOTS; a slot is one series (a talk).  Everything is allocated at open for
+ * max_audio_frames and max_beat_entries per slot and nothing grows afterwards.  Per slot the handle keeps mel_db
+ * [max_audio_frames, 128] and rms (516 B per audio frame: about 16 KB per second of 16 kHz audio), the motion-beat bytes
+ * [max_beat_entries], an audio carry of the samples a pending frame still needs (below 2048 + 512; two copies, written in turn)
+ * and the workspace of the finish (envelope, candidates and the three slabs: 20 B per audio frame; a beat list of 4 B per entry).
+ *
+ * ls_score_stream_plan (no handle, no GPU) is the one definition of the audio frames a push decides: with samples_before samples
+ * in the series and n_new more, frames [*frame_first, *frame_first + *frame_count).  Frame f is decided once the series holds
+ * 512 f + 1024 samples, and under reflect padding 1025; a finish decides every frame below 1 + L / 512 (L the total).  Over the
+ * pushes and the finish the ranges tile [0, 1 + L / 512) once, in order.  LS_EINVAL: NULL outputs, an unknown pad_mode, a negative
+ * count, a total above 2^31 - 2048, finishing an empty series, finishing with reflect padding and L <= 1024.
+ *
+ * ls_score_stream_open: dataset 0 (TED: the beat-consistency sum of ls_ted_beat_align) or 1 (BEAT: the align of
+ * ls_beat_metrics_timeline).  LS_EINVAL ahead of any HIP call: a NULL config or out, dataset outside {0, 1}, capacity < 1,
+ * max_audio_frames < 1 or above 2^22 - 3, max_beat_entries < 0, max_chunk < 1, what ls_onsets refuses of sr, sr_pick, pad_mode,
+ * fmax, and fps, sigma, time_rate <= 0, hop < 1, onset_source outside {0, 1, 2}.
+ * ls_score_stream_push: per slot s, lengths[s] new samples in audio[s, :lengths[s]] (row stride n_max <= max_chunk) and / or
+ * beat_count[s] motion-beat bytes in beats[s, :beat_count[s]] (row stride beat_capacity) that continue the slot's entries at
+ * beat_first[s] -- what ls_post_stream_push returns (TED: beat_mask; BEAT: the row of the series the alignment uses).  The spectrum
+ * kernel runs over the (slot, frame) table of the newly decided frames, reads carry + chunk and stores the rows; the carries roll;
+ * the bytes are appended.  Everything is refused ahead of any launch, slot by slot, and leaves the handle untouched: LS_EINVAL for
+ * a NULL argument, n_max outside [0, max_chunk], a length outside [0, n_max], audio without lengths, a negative beat_count or one
+ * above beat_capacity, beats without beat_first / beat_count; LS_ESTATE for a frame beyond max_audio_frames, an entry beyond
+ * max_beat_entries, beat_first[s] different from the entries the slot holds (with beat_count[s] > 0).  A failed launch marks the
+ * handle failed (LS_ESTATE from then on).
+ * ls_score_stream_finish: for every slot with finish[s] != 0 the remaining frames are decided (end padding at the slot's own
+ * last sample), the tiled pick runs on its F = 1 + L / 512 frames, the alignment sum runs against its beats, and the slot is free.
+ * Outputs, any of them NULL: count [S], onset_raw, onset_bt, onset_bt_rms [S, cols] int32, oenv, rms [S, cols], mel_db
+ * [S, cols, 128] -- row s holds the slot's F entries (for F <= LS_ONSETS_MAX_FRAMES bit for bit those of ls_onsets on the slot's
+ * samples alone, under any chunking), the slabs -1 behind count[s]; what lies behind F and the rows of slots that do not finish
+ * are not written.  TED: align_sum [S] double and n_beats [S] as ls_ted_beat_align forms them from onset_raw (up to
+ * LS_TIMELINE_MAX_FRAMES entries bit for bit: onset i stays on thread i % 256, added in index order; the beats are compacted to
+ * a sorted list and the nearest is found by binary search -- the minimum over the same set is the same value).  BEAT: align [S]
+ * float as ls_beat_metrics_timeline forms it from the slab `onset_source` at frame * hop / time_rate (NaN for a slot without an
+ * onset).  n_frames [S] (HOST) receives F, 0 for a slot that does not finish.  LS_EINVAL: NULL finish or outputs, cols below a
+ * finishing slot's F; LS_ESTATE: a finishing slot without audio, or with too little for its padding (reflect, L <= 1024).
+ * Lengths, counts, firsts and flags are HOST arrays in both modes; tensor arguments are device pointers iff on_device.
+ * Not built: a causal approximation of the normalisation, SRGR online, device-resident lengths, growing a slot. */
+#define LS_SCORE_STREAM_MAX_BEATS 4096   /* beat_capacity of a push, at most */
+typedef struct ls_score_stream ls_score_stream;
+typedef struct ls_score_config {
+    float sr;                /* of the audio: 16000                                                              */
+    float sr_pick;           /* of the picking windows: 16000 on TED, 22050 on BEAT                              */
+    int32_t pad_mode;        /* LS_ONSETS_PAD_CONSTANT | LS_ONSETS_PAD_REFLECT                                   */
+    float fmax;
+    float delta;
+    int32_t hop;             /* samples per onset frame in the scores' time axis: 512                            */
+    int32_t onset_source;    /* BEAT: 0 onset_raw, 1 onset_bt, 2 onset_bt_rms (score_timeline's)                 */
+    int32_t max_chunk;       /* samples per slot and push, at most: sizes the staging of host-side pushes        */
+    double fps;              /* of the motion-beat entries: 15                                                   */
+    double sigma;            /* TED 0.1 (beat consistency), BEAT 0.3                                             */
+    double time_rate;        /* BEAT: onset time = frame * hop / time_rate, 22050 (librosa's default rate)       */
+} ls_score_config;
+typedef struct ls_score_stream_push_args {
+    int32_t on_device;
+    int32_t n_max;              /* row stride of audio                                                                */
+    int32_t beat_capacity;      /* row stride of beats                                                                */
+    int32_t reserved;
+    const float* audio;         /* [S, n_max] or NULL                                                                 */
+    const int32_t* lengths;     /* [S] HOST                                                                           */
+    const unsigned char* beats; /* [S, beat_capacity] or NULL                                                         */
+    const int64_t* beat_first;  /* [S] HOST                                                                           */
+    const int32_t* beat_count;  /* [S] HOST                                                                           */
+} ls_score_stream_push_args;
+typedef struct ls_score_stream_outputs {
+    int32_t on_device;
+    int32_t cols;               /* row stride of the per-frame outputs                                                */
+    int32_t* n_frames;          /* [S] HOST                                                                           */
+    int32_t* count;             /* [S]                                                                                */
+    int32_t* onset_raw;         /* [S, cols]                                                                          */
+    int32_t* onset_bt;
+    int32_t* onset_bt_rms;
+    float* oenv;                /* [S, cols]                                                                          */
+    float* mel_db;              /* [S, cols, 128]                                                                     */
+    float* rms;                 /* [S, cols]                                                                          */
+    double* align_sum;          /* [S] TED                                                                            */
+    int32_t* n_beats;           /* [S] TED                                                                            */
+    float* align;               /* [S] BEAT                                                                           */
+} ls_score_stream_outputs;
+int ls_score_stream_plan(int32_t pad_mode, int64_t samples_before, int64_t n_new, int32_t finishing, int64_t* frame_first,
+                         int32_t* frame_count);
+int ls_score_stream_open(int device, int32_t dataset, int32_t capacity, int32_t max_audio_frames, int32_t max_beat_entries,
+                         const ls_score_config* cfg, ls_score_stream** out);
+int ls_score_stream_push(ls_score_stream* h, const ls_score_stream_push_args* a);
+int ls_score_stream_finish(ls_score_stream* h, const int32_t* finish, const ls_score_stream_outputs* out);
+/* samples_in, frames_done, beats_in [capacity] (nullable): each slot's samples, decided audio frames and beat entries */
+int ls_score_stream_info(const ls_score_stream* h, int64_t* samples_in, int64_t* frames_done, int64_t* beats_in, int64_t* device_bytes);
+void ls_score_stream_close(ls_score_stream* h);
+const char* ls_score_stream_last_error(const ls_score_stream* h);
 
 /* ---- dataset ingest: recorded poses and audio -> model inputs ----------------------------------------------
  * The forward direction of the pose transforms above, as the reference's offline pipeline computes it: TED

@@ -220,6 +220,22 @@ class LsEvalConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("pose_dim", "n_frames", "base", "hidden1", "hidden2", "device")]
 
 
+class LsScoreConfig(C.Structure):
+    _fields_ = [("sr", C.c_float), ("sr_pick", C.c_float), ("pad_mode", C.c_int32), ("fmax", C.c_float), ("delta", C.c_float),
+                ("hop", C.c_int32), ("onset_source", C.c_int32), ("max_chunk", C.c_int32), ("fps", C.c_double), ("sigma", C.c_double),
+                ("time_rate", C.c_double)]
+
+
+class LsScoreStreamPushArgs(C.Structure):
+    _fields_ = [("on_device", C.c_int32), ("n_max", C.c_int32), ("beat_capacity", C.c_int32), ("reserved", C.c_int32),
+                ("audio", C.c_void_p), ("lengths", C.c_void_p), ("beats", C.c_void_p), ("beat_first", C.c_void_p), ("beat_count", C.c_void_p)]
+
+
+class LsScoreStreamOutputs(C.Structure):
+    _fields_ = [("on_device", C.c_int32), ("cols", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "n_frames", "count", "onset_raw", "onset_bt", "onset_bt_rms", "oenv", "mel_db", "rms", "align_sum", "n_beats", "align")]
+
+
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
            "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_edit_sag", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_long_pool_plan", "ls_long_pool_open", "ls_long_pool_join", "ls_long_pool_push", "ls_long_pool_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_set_row_keys", "ls_long_pool_keyed", "ls_long_pool_set_key", "ls_long_pool_keys", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
@@ -229,9 +245,11 @@ EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set
            "ls_clip_text_create", "ls_clip_text_destroy", "ls_clip_text_last_error", "ls_clip_text_set_weight", "ls_clip_text_commit_weights",
            "ls_clip_text_encode", "ls_clip_text_encode_async", "ls_clip_text_last_encode_ms", "ls_clip_text_stream", "ls_clip_text_plan", "ls_ted_post", "ls_beat_post", "ls_beat_metrics", "ls_beat_ldiv", "ls_onsets", "ls_onsets_tables",
            "ls_ted_post_timeline", "ls_beat_post_timeline", "ls_beat_metrics_timeline", "ls_ted_beat_align",
-           "ls_onsets_ragged", "ls_ted_post_timeline_ragged", "ls_beat_post_timeline_ragged", "ls_beat_metrics_timeline_ragged", "ls_ragged_tiles",
+           "ls_onsets_ragged", "ls_onsets_long", "ls_ted_post_timeline_ragged", "ls_beat_post_timeline_ragged", "ls_beat_metrics_timeline_ragged", "ls_ragged_tiles",
            "ls_post_stream_plan", "ls_post_stream_check", "ls_post_stream_open", "ls_post_stream_push", "ls_post_stream_info", "ls_post_stream_close",
            "ls_post_stream_last_error",
+           "ls_score_stream_plan", "ls_score_stream_open", "ls_score_stream_push", "ls_score_stream_finish", "ls_score_stream_info",
+           "ls_score_stream_close", "ls_score_stream_last_error",
            "ls_ingest_plan", "ls_ted_ingest", "ls_beat_ingest",
            "ls_train_create", "ls_train_destroy", "ls_train_last_error", "ls_train_set_schedule", "ls_train_param_count",
            "ls_train_flat_size", "ls_train_param_info", "ls_train_set_weight", "ls_train_get_weight", "ls_train_forward_backward",
@@ -322,6 +340,15 @@ def load_library(build_if_missing: bool = True):
     lib.ls_post_stream_close.restype = None
     lib.ls_post_stream_last_error.argtypes = [C.c_void_p]
     lib.ls_post_stream_last_error.restype = C.c_char_p
+    lib.ls_score_stream_plan.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int32, c_i64p, c_i32p]
+    lib.ls_score_stream_open.argtypes = [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LsScoreConfig), C.POINTER(C.c_void_p)]
+    lib.ls_score_stream_push.argtypes = [C.c_void_p, C.POINTER(LsScoreStreamPushArgs)]
+    lib.ls_score_stream_finish.argtypes = [C.c_void_p, c_i32p, C.POINTER(LsScoreStreamOutputs)]
+    lib.ls_score_stream_info.argtypes = [C.c_void_p, c_i64p, c_i64p, c_i64p, c_i64p]
+    lib.ls_score_stream_close.argtypes = [C.c_void_p]
+    lib.ls_score_stream_close.restype = None
+    lib.ls_score_stream_last_error.argtypes = [C.c_void_p]
+    lib.ls_score_stream_last_error.restype = C.c_char_p
     lib.ls_forward.argtypes = [C.c_void_p, C.POINTER(LsForwardArgs)]
     lib.ls_step.argtypes = [C.c_void_p, C.POINTER(LsStepArgs)]
     lib.ls_plms_step.argtypes = [C.c_void_p, C.POINTER(LsPlmsStepArgs)]
@@ -384,6 +411,7 @@ def load_library(build_if_missing: bool = True):
     lib.ls_beat_metrics_timeline.argtypes = [C.c_int, C.c_int, C.POINTER(LsBeatMetricsArgs)]
     lib.ls_ted_beat_align.argtypes = [C.c_int, C.POINTER(LsTedAlignArgs)]
     lib.ls_onsets_ragged.argtypes = [C.c_int, C.POINTER(LsOnsetsArgs), C.c_void_p]
+    lib.ls_onsets_long.argtypes = [C.c_int, C.POINTER(LsOnsetsArgs)]
     lib.ls_ted_post_timeline_ragged.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(LsPostConfig), C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ls_beat_post_timeline_ragged.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -688,6 +716,61 @@ def post_stream_check(dataset, order, frames_in, K, counts, finish, beat_capacit
         raise ValueError(f"refused: at most {POST_STREAM_MAX_CHUNK} frames per push (got K = {int(K)}), counts in [0, K], a BEAT order in [1, 8], "
                          f"beat_capacity {cap} >= every slot's entries")
     return first[:S].copy(), count[:S].copy()
+
+
+SCORE_STREAM_MAX_BEATS = 4096    # LS_SCORE_STREAM_MAX_BEATS
+
+
+def score_stream_plan(pad_mode, samples_before, n_new, finishing=False):
+    """ls_score_stream_plan (no GPU needed): ``(frame_first, frame_count)``, the audio frames a push of ``n_new`` samples decides on a
+    series that holds ``samples_before``.  ``pad_mode``: 0 constant, 1 reflect.  Raises ``ValueError`` for what the engine refuses."""
+    first, count = C.c_int64(), C.c_int32()
+    if load_library().ls_score_stream_plan(int(pad_mode), int(samples_before), int(n_new), int(bool(finishing)), C.byref(first), C.byref(count)) != 0:
+        raise ValueError(f"no plan for pad_mode {pad_mode}, {samples_before} + {n_new} samples (finishing={bool(finishing)}): counts must be >= 0 "
+                         "and at most 2^31 - 2048 in all, a series that is finished must hold a sample, and more than 1024 under reflect padding")
+    return int(first.value), int(count.value)
+
+
+class ScoreStreamEngine:
+    """One ``ls_score_stream`` handle: ``capacity`` slots of spectra and motion beats on one GPU (``postprocess.open_score_stream``)."""
+
+    def __init__(self, dataset, capacity, max_audio_frames, max_beat_entries, cfg, device=0):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        self.device, self.S = int(device), int(capacity)
+        rc = self.lib.ls_score_stream_open(self.device, int(dataset == "beat"), self.S, int(max_audio_frames), int(max_beat_entries), C.byref(cfg),
+                                           C.byref(self.h))
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise EngineError(f"ls_score_stream_open failed ({rc}): {self.lib.ls_score_stream_last_error(None).decode()}")
+
+    def _check(self, name, rc):
+        if rc != 0:
+            msg = self.lib.ls_score_stream_last_error(self.h).decode()
+            raise (ValueError if rc in (-1, -2) else EngineError)(f"{name} failed ({rc}): {msg}")
+
+    def push(self, args: "LsScoreStreamPushArgs"):
+        self._check("ls_score_stream_push", self.lib.ls_score_stream_push(self.h, C.byref(args)))
+
+    def finish(self, flags, outputs: "LsScoreStreamOutputs"):
+        self._check("ls_score_stream_finish", self.lib.ls_score_stream_finish(self.h, flags.ctypes.data_as(c_i32p), C.byref(outputs)))
+
+    def info(self) -> dict:
+        a, b, c, nbytes = np.zeros(self.S, np.int64), np.zeros(self.S, np.int64), np.zeros(self.S, np.int64), C.c_int64()
+        if self.lib.ls_score_stream_info(self.h, a.ctypes.data_as(c_i64p), b.ctypes.data_as(c_i64p), c.ctypes.data_as(c_i64p), C.byref(nbytes)) != 0:
+            raise EngineError("ls_score_stream_info failed")
+        return {"samples_in": a, "frames_done": b, "beats_in": c, "device_bytes": int(nbytes.value)}
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.ls_score_stream_close(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class PostStreamEngine:

@@ -20,6 +20,8 @@ from . import _lib, beat_metrics
 
 N_FFT, HOP, N_MELS = 2048, 512, 128
 MAX_FRAMES = 4096
+SCORE_TILE = 256            # LS_SCORE_TILE: the frames per tile of the any-length pick (ls_onsets_long)
+MAX_LENGTH_LONG = 2 ** 31 - N_FFT
 PAD_MODES = {"constant": 0, "reflect": 1}
 OUTPUTS = ("mel_db", "rms", "oenv", "count", "onset_raw", "onset_bt", "onset_bt_rms")
 
@@ -63,6 +65,21 @@ def audio_onsets(audio=None, sr=16000, sr_pick=None, *, onset_envelope=None, pad
     samples (frames, with ``onset_envelope``) of its row; what follows them is never read.  The outputs keep their [B, F] shapes; on
     clip b's own ``1 + lengths[b] // 512`` frames they are bit for bit those of the clip alone at its own length, beyond them 0 (floats)
     and -1 (the slabs).  ``None`` is the equal-length call."""
+    return _onsets(MAX_FRAMES, audio, sr, sr_pick, onset_envelope, pad_mode, fmax, delta, device, want, timing, lengths)
+
+
+def audio_onsets_long(audio=None, sr=16000, sr_pick=None, *, onset_envelope=None, pad_mode="constant", fmax=11025.0, delta=0.07,
+                      device=0, want=("oenv", "count", "onset_raw", "onset_bt", "onset_bt_rms"), timing=None):
+    """``audio_onsets`` for an equal-length batch of clips of ANY length (``ls_onsets_long``): the same arguments and the same dict,
+    without the limit of ``MAX_FRAMES`` frames (131 s of audio) -- a quarter of an hour of speech is 28 126 frames.  The spectrum is
+    the same kernel; the pick runs tiled over ``SCORE_TILE`` frames with nothing on chip sized by the clip, and every float is a
+    per-frame expression or an exact reduction, so up to ``MAX_FRAMES`` frames every output equals ``audio_onsets``' bit for bit.
+    ``timing`` receives the spectrum's time and that of all launches of the pick.  Not built: ``lengths=`` (the ragged form)."""
+    return _onsets(None, audio, sr, sr_pick, onset_envelope, pad_mode, fmax, delta, device, want, timing, None)
+
+
+def _onsets(max_frames, audio, sr, sr_pick, onset_envelope, pad_mode, fmax, delta, device, want, timing, lengths):
+    """Both entries: ``max_frames`` None is the any-length one."""
     if (audio is None) == (onset_envelope is None):
         raise ValueError("pass either audio or onset_envelope")
     if pad_mode not in PAD_MODES:
@@ -78,8 +95,10 @@ def audio_onsets(audio=None, sr=16000, sr_pick=None, *, onset_envelope=None, pad
     F = L if given else 1 + L // HOP
     if given and {"mel_db", "rms", "onset_bt_rms"} & set(want):
         want = tuple(w for w in want if w not in ("mel_db", "rms", "onset_bt_rms"))
-    if B < 1 or L < 1 or F > MAX_FRAMES:
+    if B < 1 or L < 1 or (max_frames is not None and F > max_frames):
         raise ValueError(f"need at least one clip and one sample, and at most {MAX_FRAMES} frames: got B={B}, length {L}")
+    if max_frames is None and (L > MAX_LENGTH_LONG or -(-B * F // 4) > 2 ** 31 - 1):
+        raise ValueError(f"at most {MAX_LENGTH_LONG} samples per clip and 2^33 - 4 frames per call: got B={B}, length {L}")
     if not given and pad_mode == "reflect" and L <= N_FFT // 2:
         raise ValueError(f"reflect padding needs more than {N_FFT // 2} samples, got {L}")
     lens = None
@@ -106,7 +125,7 @@ def audio_onsets(audio=None, sr=16000, sr_pick=None, *, onset_envelope=None, pad
         a.kernel_ms = C.cast(ms, C.c_void_p)
     m.ready()
     if lens is None:
-        _lib.call("ls_onsets", device, C.byref(a))
+        _lib.call("ls_onsets" if max_frames is not None else "ls_onsets_long", device, C.byref(a))
     else:
         _lib.call("ls_onsets_ragged", device, C.byref(a), lens.ctypes.data_as(C.c_void_p))
     if timing is not None:

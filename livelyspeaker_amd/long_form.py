@@ -321,13 +321,26 @@ class _Session:
             self._eng = eng
         return self._eng
 
-    def _init_post(self, post, rag, slots):
-        """``post=``: None, or the dataset whose post-processing stream the session owns ('ted' / 'beat', the model's own)."""
+    def _init_post(self, post, rag, slots, score=None, max_seconds=None):
+        """``post=``: None, or the dataset whose post-processing stream the session owns ('ted' / 'beat', the model's own).  ``score=``:
+        None, True or a dict of ``postprocess.open_score_stream``'s options: the session also owns a score stream of as many slots,
+        sized for ``max_seconds`` of audio per clip."""
         if post is not None:
             want = "beat" if getattr(rag, "n_prefix_tokens", 1) == 2 else "ted"
             if post != want:
                 raise ValueError(f"post must be None or the model's dataset {want!r}, got {post!r}")
-        self._post_kind, self._post_slots, self._post = post, slots, None
+        self._post_kind, self._post_slots, self._post, self._score = post, slots, None, None
+        if score is not None and score is not False:
+            if post is None:
+                raise ValueError("score= scores the motion beats of the post-processing stream: pass post= as well")
+            if score is not True and not isinstance(score, dict):
+                raise ValueError(f"score must be None, True or a dict of open_score_stream's options, got {score!r}")
+            if max_seconds is None or not float(max_seconds) > 0:
+                raise ValueError(f"score= needs max_seconds > 0 (the audio a clip may hold: the score stream's memory), got {max_seconds!r}")
+            # no device yet: the handle is bound, on the engine's device, by the first call that feeds it
+            self._score = postprocess.open_score_stream(post, slots, max_seconds, **(score if isinstance(score, dict) else {}))
+        elif max_seconds is not None:
+            raise ValueError("max_seconds sizes the score stream: pass score=True as well")
 
     def _check_post_frames(self, most):
         """Ahead of the sampling: a push of the post-processing stream takes at most 256 frames per slot."""
@@ -335,16 +348,35 @@ class _Session:
             raise ValueError(f"with post=, a call may complete at most {postprocess.POST_STREAM_MAX_CHUNK} frames per clip (8 windows), this one "
                              f"would complete {most}: feed the audio in smaller chunks")
 
-    def _post_push(self, frames, counts, finish):
+    def _post_push(self, frames, counts, finish, audio=None, lengths=None):
         """The session's frames into its post-processing stream (opened on the engine's device at the first call): a device tensor
-        goes in as it is, without a host copy."""
+        goes in as it is, without a host copy.  With ``score=``: the call's ``audio`` and the beats of that push into the score stream,
+        and for the slots that ``finish`` the result under ``'score'``."""
         if self._post is None:
             rag = self._rag
             self._post = postprocess.open_post_stream(self._post_kind, self._post_slots, device=self._eng.device, joints=int(rag.njoints))
         res = self._post.push(frames, counts, finish)
-        if self._closed:                  # the session's last call has finished every series: the handle goes with it
+        if self._score is not None:
+            self._score_push(res, finish, audio, lengths)
+        if self._closed:                  # the session's last call has finished every series: the handles go with it
             self._post.close()
+            if self._score is not None:
+                self._score.close()
         return res
+
+    def _score_push(self, res, finish, audio, lengths):
+        sc = self._score
+        sc.device = self._eng.device
+        if audio is not None and int(audio.shape[1]):
+            n = int(audio.shape[1])
+            lens = np.full(self._post_slots, n, np.int64) if lengths is None else np.asarray(lengths, np.int64)
+            for c0 in range(0, n, sc.max_chunk):      # a push of the score stream takes max_chunk samples per slot
+                piece = audio[:, c0:c0 + sc.max_chunk]
+                sc.push(audio=piece, lengths=np.clip(lens - c0, 0, int(piece.shape[1])))
+        sc.push(beats=res)
+        ending = [] if finish is None else [s for s in np.nonzero(np.asarray(finish).reshape(-1))[0] if sc.samples_in[s] > 0]
+        if ending:
+            res["score"] = score_summary(sc, sc._finish([int(s) for s in ending]))
 
     def _check_held(self, emo, text_features, rows):
         """``emo`` [rows] (BEAT) and ``text_features`` [rows, latent_dim] (with ``sag=``), each None or one row per clip."""
@@ -361,10 +393,26 @@ class _Session:
                 raise ValueError(f"text_features must be {[rows, rag.latent_dim]}, got {list(text_features.shape)}")
 
 
+def score_summary(stream, finished):
+    """What a session reports for the slots a call finished: ``{'slots': {slot: ScoreStream.finish dict}}`` plus, on TED, ``'bc'`` -- the
+    beat-consistency score over those slots, accumulated as ``BeatConsistency.push_timeline`` does (nan without an onset) -- and on BEAT
+    ``'align'``, the slots' BeatAlign scores in slot order."""
+    out = {"slots": finished}
+    order = sorted(finished)
+    if stream.dataset == "ted":
+        acc = postprocess.BeatConsistency(sigma=stream.sigma)
+        acc.push_score({s: finished[s] for s in order})
+        out["bc"] = acc.score() if acc.num_beats else float("nan")
+    else:
+        out["align"] = np.array([finished[s]["align"] for s in order], np.float32)
+    return out
+
+
 class LongStream(_Session):
     """A running ``open_stream`` session; see there.  ``samples_in``, ``windows_run``, ``frames_out``: host ints."""
 
-    def __init__(self, diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag, post=None):
+    def __init__(self, diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag, post=None,
+                 score=None, max_seconds=None):
         seed_poses, vid_indices, scale, emo = _as_tensors(seed_poses, vid_indices, scale, emo)
         B = int(seed_poses.shape[0]) if seed_poses.ndim else 0
         rag = getattr(model, "model", None)
@@ -377,7 +425,7 @@ class LongStream(_Session):
         if emo is not None and emo.ndim != 1:
             raise ValueError(f"a stream holds one emotion id per clip: emo must be [{B}], got {list(emo.shape)}")
         self._diffusion, self._rag, self._sag, self._B = diffusion, rag, sag, B
-        self._init_post(post, rag, B)
+        self._init_post(post, rag, B, score, max_seconds)
         self._cond = (seed_poses.float(), vid_indices, scale.float())
         self._emo, self._text = emo, None               # held on the host side only until the next engine call takes them
         self._have_emo = self._have_text = False
@@ -433,7 +481,7 @@ class LongStream(_Session):
         frames = gd._as_tensor(frames, out_dev)
         if self._post_kind is None:
             return frames
-        return frames, self._post_push(frames, None, np.full(B, bool(closing)))
+        return frames, self._post_push(frames, None, np.full(B, bool(closing)), chunk)
 
     def push(self, audio_chunk, emo=None, text_features=None):
         """Feed ``audio_chunk`` [B, n], n >= 0; returns the new frames ``[B, J, F, k]`` of the windows it completed (k may be 0); with
@@ -446,7 +494,7 @@ class LongStream(_Session):
 
 
 def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False,
-                sag=None, post=None):
+                sag=None, post=None, score=None, max_seconds=None):
     """The online form of ``sample_long``: a session that is fed audio in chunks of any size and returns a window's new frames as soon
     as that window's audio is complete.
 
@@ -484,11 +532,17 @@ def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, samp
     the post-processing kernels on the device when the audio was on the device.  The frames themselves are bit for bit those of
     ``post=None``, which changes nothing.  A call may complete at most 256 frames per clip then (8 windows).
 
+    ``score=True`` (or a dict of ``postprocess.open_score_stream``'s options) with ``post=`` and ``max_seconds=`` (the audio a clip may
+    hold): the session also owns a score stream of B slots.  It is fed the audio of every push and the beats of the post stream, and
+    ``close`` adds ``'score'`` to its post dict: ``{'slots': {b: count, onset_raw, align_sum, n_beats | align, ...}, 'bc': ...}`` (BEAT:
+    ``'align'`` [B]), which is what ``score_timeline`` gives for the concatenated frames and audio -- without its limits of 4096 frames.
+    ``score=True`` without ``post=`` raises; with ``score`` unset nothing changes.
+
     Clips that join or leave while others run, each fed at its own rate: ``open_pool``.
 
     Not built: ``audio_lengths`` / ``drop_finished``, ``edit_long`` on a running stream, PLMS, ``const_noise``, ``dump_steps``,
     sharded calls, a non-blocking ``push``."""
-    return LongStream(diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag, post)
+    return LongStream(diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag, post, score, max_seconds)
 
 
 def pool_plan(samples_in, windows_run, new, closing, open, cfg):
@@ -507,7 +561,8 @@ class LongPool(_Session):
     """A running ``open_pool`` session; see there.  ``slots``: per-slot host arrays ``samples_in``, ``windows_run``, ``frames_out``, ``open``,
     and in a keyed pool ``key`` (uint64; of a free slot: its last clip's)."""
 
-    def __init__(self, diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post=None, noise_keys=None):
+    def __init__(self, diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post=None, noise_keys=None, score=None,
+                 max_seconds=None):
         S = int(capacity)
         if S < 1:
             raise ValueError(f"capacity must be >= 1, got {capacity}")
@@ -524,7 +579,7 @@ class LongPool(_Session):
                     None if sag is None else th.empty(S, 1, int(rag.latent_dim)), None, {})
         _check_model(diffusion, rag)
         self._diffusion, self._rag, self._sag, self._S = diffusion, rag, sag, S
-        self._init_post(post, rag, S)
+        self._init_post(post, rag, S, score, max_seconds)
         self._kw = _loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised)
         self._keyed, self._joins = noise_keys == "clip", 0
         if diffusion.noise_source == "philox":          # one seed per pool: row r of round q draws at sample_offset + r + (q << 48); keyed: at the clip's key
@@ -652,7 +707,7 @@ class LongPool(_Session):
         frames = gd._as_tensor(frames, out_dev)
         if self._post_kind is None:
             return frames, counts
-        return frames, counts, self._post_push(frames, counts, ending)
+        return frames, counts, self._post_push(frames, counts, ending, audio, lens)
 
     def push(self, audio, lengths, emo=None, text_features=None, given=None):
         """Feed ``audio`` [S, n_max]: ``lengths[s]`` samples for slot s (0 for a slot that is free or has nothing new).  Returns
@@ -688,6 +743,8 @@ class LongPool(_Session):
         self._closed = True
         if self._post is not None:
             self._post.close()            # every series has been finished by the call above
+        if self._score is not None:
+            self._score.close()
         return res
 
 
@@ -700,7 +757,8 @@ def pool_keys(keys, windows_run, n_windows):
     return _lib.long_pool_keys(keys, windows_run, n_windows)
 
 
-def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False, sag=None, post=None, noise_keys=None):
+def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False, sag=None, post=None, noise_keys=None,
+              score=None, max_seconds=None):
     """``open_stream`` for clips that start and stop at different times and arrive at different rates: a session pool of ``capacity``
     slots on ONE engine.
 
@@ -749,11 +807,14 @@ def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=
     ``post='ted'`` / ``'beat'`` (the model's own dataset): the pool owns a ``postprocess.open_post_stream`` of ``capacity`` slots;
     ``push``, ``leave`` and ``close`` return ``(frames, counts, post_dict)`` with ``PostStream.push``'s dict for the call's frames.
     ``leave`` and ``close`` finish the series of the slots they end, and a ``join`` into a freed slot starts a fresh one.  A call may
-    complete at most 256 frames per slot then.  With ``post=None`` nothing changes.
+    complete at most 256 frames per slot then.  With ``post=None`` nothing changes.  ``score=True`` (or a dict of
+    ``postprocess.open_score_stream``'s options) with ``post=`` and ``max_seconds=``: the pool also owns a score stream of ``capacity``
+    slots, fed the audio of every push and the post stream's beats; the post dict of a ``leave`` (and of ``close``) carries ``'score'``
+    for the slots it finished -- each clip's own onsets and alignment score, as in ``open_stream``.
 
     Not built: device-resident ``lengths``, ``edit_long`` on a pool, PLMS, ``const_noise``,
     ``dump_steps``, sharded calls, a non-blocking ``push``."""
-    return LongPool(diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post, noise_keys)
+    return LongPool(diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post, noise_keys, score, max_seconds)
 
 
 def _edit_ranges(frames, B, n_frames):
@@ -974,7 +1035,8 @@ def timeline_clips(x, stride=34, frames=None):
 def score_timeline(timeline, audio, dataset="ted", sr=16000, device=0, target_euler=None, semantic=None, bc=None, frames=None,
                    audio_lengths=None, **options):
     """The whole chain behind ``sample_long``: post-process a stitched timeline [B, J, F, N] and score it against the ``audio`` [B, L] it
-    was generated from, on the device (N up to 4096 frames; audio up to the onset detector's 4096 audio frames, 131 s at 16 kHz).
+    was generated from, on the device (N up to 4096 frames; audio up to the onset detector's 4096 audio frames, 131 s at 16 kHz; longer
+    talks: ``score_talk``).
 
     ``dataset='ted'``: ``ted_postprocess_timeline``, onsets as ``librosa.onset.onset_detect(y, sr=16000)`` finds them, and the
     beat-consistency score; returns pose, beat_mask, motion_beat_times and bc (this call's score, or the running score of the
@@ -1025,4 +1087,79 @@ def score_timeline(timeline, audio, dataset="ted", sr=16000, device=0, target_eu
         s = s.detach().cpu().numpy() if hasattr(s, "detach") else np.asarray(s)
         total_frames = B * int(timeline.shape[3]) if frames is None else int(frames.astype(np.int64).sum())
         res["srgr"] = float(s.astype(np.float64).sum()) / (total_frames * int(timeline.shape[1]))
+    return res
+
+
+def score_talk(timeline, audio, dataset="ted", frames=None, audio_lengths=None, sr=16000, device=0, bc=None, chunk_seconds=4.0, **options):
+    """``score_timeline`` without its limits: a stitched timeline [B, J, F, N] of ANY length against the ``audio`` [B, L] it was
+    generated from -- a talk of a quarter of an hour is 13 500 pose frames and 28 126 audio frames.  It drives a
+    ``postprocess.open_post_stream`` in 256-frame pushes and a ``postprocess.open_score_stream`` in chunks of ``chunk_seconds``, one slot
+    per clip, so ``frames`` [B] and ``audio_lengths`` [B] (the clips' valid frames and samples; either may be None: all of them) make
+    the call ragged for free.  Returns what ``score_timeline`` returns -- TED: pose, beat_mask [B, N], motion_beat_times, bc (this
+    call's, or the running score of ``bc``); BEAT: pred_euler, beat_mask [B, 6, N - 1], align [B] -- zero beyond a clip's own frames,
+    plus ``onset_count`` [B] and ``slots`` (the score stream's per-clip dicts).  Where ``score_timeline`` applies the numbers are the
+    same bits.  ``options``: the score stream's (pad_mode, fmax, delta, sigma, ...) and, for BEAT, ``order`` and ``series_joints``.
+    SRGR is not part of it (it needs targets frame by frame: ``beat_metrics_timeline`` up to 4096 frames)."""
+    from . import postprocess as pp
+    if dataset not in ("ted", "beat"):
+        raise ValueError(f"dataset must be 'ted' or 'beat', got {dataset!r}")
+    if len(timeline.shape) != 4:
+        raise ValueError(f"expected a timeline [B, J, F, N], got {list(timeline.shape)}")
+    B, J, _, N = (int(v) for v in timeline.shape)
+    if len(audio.shape) != 2 or int(audio.shape[0]) != B:
+        raise ValueError(f"audio must be [B, L] with one row per timeline clip, got {list(audio.shape)}")
+    L = int(audio.shape[1])
+    beat = dataset == "beat"
+    order = int(options.pop("order", 2))
+    series = options.pop("series_joints", pp.BEAT_SERIES_JOINTS)
+    least = 2 * order + 2 if beat else 4
+    frames = np.full(B, N, np.int64) if frames is None else _lib.host_lengths(frames, B, least, N, "frames").astype(np.int64)
+    lens = np.full(B, L, np.int64) if audio_lengths is None else _lib.host_lengths(audio_lengths, B, 1, L, "audio_lengths").astype(np.int64)
+    if N < least or L < 1:
+        raise ValueError(f"need at least {least} frames and one sample per clip, got N = {N}, L = {L}")
+    step = max(1, int(round(float(chunk_seconds) * float(sr))))
+    ps = pp.open_post_stream(dataset, B, device=device, order=order, series_joints=series, joints=J)
+    fps = float(options.get("fps", pp.TED_FPS))
+    seconds = max(int(lens.max()) / float(sr), (int(frames.max()) + 1) / fps)          # the slots hold the audio and the motion beats
+    ss = pp.open_score_stream(dataset, B, seconds, sr=sr, device=device, max_chunk=step, **options)
+    rows, masks, firsts, counts = [], [], [], []
+    try:
+        for c0 in range(0, int(lens.max()), step):
+            piece = audio[:, c0:c0 + step]
+            ss.push(audio=piece, lengths=np.clip(lens - c0, 0, int(piece.shape[1])))
+        K = pp.POST_STREAM_MAX_CHUNK
+        for t0 in range(0, int(frames.max()), K):
+            k = np.clip(frames - t0, 0, K)
+            got = ps.push(timeline[..., t0:t0 + K], k, (frames > t0) & (frames <= t0 + K))
+            ss.push(beats=got)
+            rows.append(got["pred_euler" if beat else "pose"])
+            masks.append(got["beat_mask"]), firsts.append(got["beat_first"]), counts.append(got["beat_count"])
+        finished = ss.close()
+    finally:
+        ps.close()
+        if not ss._closed:
+            ss._closed = True
+            if ss._eng is not None:
+                ss._eng.close()
+    host = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)      # noqa: E731
+    mask = np.zeros((B, 6, N - 1) if beat else (B, N), bool)
+    for m, first, count in zip(masks, firsts, counts):
+        m = host(m)
+        for b in range(B):
+            mask[b, ..., int(first[b]):int(first[b]) + int(count[b])] = m[b, ..., :int(count[b])]
+    if hasattr(rows[0], "detach"):
+        import torch
+        body, mask_out = torch.cat(rows, dim=1), torch.from_numpy(mask).to(rows[0].device)
+    else:
+        body, mask_out = np.concatenate(rows, axis=1), mask
+    res = {"beat_mask": mask_out, "slots": finished, "onset_count": np.array([finished[b]["count"] for b in range(B)], np.int64)}
+    if beat:
+        res["pred_euler"] = body
+        res["align"] = np.array([finished[b]["align"] for b in range(B)], np.float32)
+        return res
+    acc = bc if bc is not None else pp.BeatConsistency(sigma=ss.sigma)
+    acc.push_score(finished)
+    res["pose"] = body
+    res["motion_beat_times"] = [[float(t) / pp.TED_FPS for t in np.nonzero(mask[b])[0]] for b in range(B)]
+    res["bc"] = acc.score() if acc.num_beats else float("nan")
     return res

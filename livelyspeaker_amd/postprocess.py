@@ -292,10 +292,254 @@ def open_post_stream(dataset, capacity, device=0, order=2, series_joints=BEAT_SE
     per-frame functions, and what a frame needs from its left is carried on the device (TED: 3 raw frames per slot; BEAT: 2 order + 1
     Euler triples of the six joints).  Device memory is allocated at the first push and does not grow (``device_bytes``).
 
-    Not built: online audio onsets and the BC / BeatAlign scores (librosa normalises the onset envelope by the whole signal's extrema
-    and clamps at the global maximum - 80 dB, so they are not causal), SRGR (it needs targets), device-resident ``counts``, chunks over
-    256 frames per push."""
+    Audio onsets and the BC / BeatAlign scores come at the finish: ``open_score_stream`` (librosa normalises the onset envelope by the
+    whole signal's extrema and clamps at the global maximum - 80 dB, so they are not causal).  Not built: SRGR (it needs targets),
+    device-resident ``counts``, chunks over 256 frames per push."""
     return PostStream(dataset, capacity, device, order, series_joints, joints)
+
+
+SCORE_OUTPUTS = ("count", "onset_raw", "onset_bt", "onset_bt_rms", "oenv", "mel_db", "rms")
+
+
+def score_stream_plan(samples_before, n_new, finishing=False, pad_mode="constant"):
+    """The audio frames a ``ScoreStream.push`` of ``n_new`` samples decides on a series that holds ``samples_before`` (no GPU):
+    ``(frame_first, frame_count)``.  Frame f covers samples [512 f - 1024, 512 f + 1024): it is decided once the series holds
+    512 f + 1024 samples (and, under reflect padding, 1025); a finish decides every frame below 1 + L // 512.  One definition for the
+    engine and for this module (``ls_score_stream_plan``)."""
+    from .audio_onsets import PAD_MODES
+    if pad_mode not in PAD_MODES:
+        raise ValueError(f"pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
+    return _lib.score_stream_plan(PAD_MODES[pad_mode], samples_before, n_new, finishing)
+
+
+class ScoreStream:
+    """A running ``open_score_stream``; see there.  ``frames_in``: the decided audio frames of each slot's series, ``samples_in`` its
+    samples, ``beats_in`` its motion-beat entries (host int64 [S])."""
+
+    def __init__(self, dataset, capacity, max_seconds, sr=16000, device=0, *, sr_pick=None, pad_mode="constant", fmax=11025.0, delta=0.07,
+                 sigma=None, fps=TED_FPS, max_chunk=65536, align_series=2, onset_source="onset_bt_rms", time_rate=22050.0,
+                 want=("count", "onset_raw")):
+        from . import audio_onsets as ao
+        if dataset not in ("ted", "beat"):
+            raise ValueError(f"dataset must be 'ted' or 'beat', got {dataset!r}")
+        S = int(capacity)
+        if S < 1:
+            raise ValueError(f"capacity must be >= 1, got {capacity}")
+        if pad_mode not in ao.PAD_MODES:
+            raise ValueError(f"pad_mode must be 'constant' or 'reflect', got {pad_mode!r}")
+        if not float(max_seconds) > 0 or not float(sr) > 0 or not float(fps) > 0:
+            raise ValueError(f"max_seconds, sr and fps must be > 0, got {max_seconds}, {sr}, {fps}")
+        unknown = set(want) - set(SCORE_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        sources = ("onset_raw", "onset_bt", "onset_bt_rms")
+        if onset_source not in sources:
+            raise ValueError(f"onset_source must be one of {sources}, got {onset_source!r}")
+        if not 0 <= int(align_series) < 6:
+            raise ValueError(f"align_series must name one of the six series, got {align_series}")
+        if int(max_chunk) < 1:
+            raise ValueError(f"max_chunk must be >= 1, got {max_chunk}")
+        self.dataset, self.capacity, self.device, self.sr = dataset, S, int(device), float(sr)
+        self._beat = dataset == "beat"
+        self.align_series = int(align_series)
+        self.want = tuple(want)
+        self.max_samples = int(round(float(max_seconds) * float(sr)))
+        self.max_audio_frames = 1 + self.max_samples // ao.HOP
+        self.max_beat_entries = int(np.ceil(float(max_seconds) * float(fps))) + 1
+        if self.max_samples < 1 or self.max_samples > ao.MAX_LENGTH_LONG:
+            raise ValueError(f"max_seconds * sr must lie in [1, {ao.MAX_LENGTH_LONG}] samples, got {self.max_samples}")
+        c = _lib.LsScoreConfig()
+        c.sr, c.pad_mode, c.fmax, c.delta = float(sr), ao.PAD_MODES[pad_mode], float(fmax), float(delta)
+        c.sr_pick = float(sr_pick) if sr_pick is not None else (22050.0 if self._beat else float(sr))
+        c.hop, c.onset_source, c.max_chunk = ao.HOP, sources.index(onset_source), int(max_chunk)
+        c.fps, c.time_rate = float(fps), float(time_rate)
+        c.sigma = float(sigma) if sigma is not None else (0.3 if self._beat else TED_BEAT_SIGMA)
+        if not (c.fmax > 0 and c.sr_pick > 0 and c.sigma > 0 and c.time_rate > 0):
+            raise ValueError("fmax, sr_pick, sigma and time_rate must be > 0")
+        self._cfg, self.max_chunk, self.pad_mode, self.sigma = c, int(max_chunk), pad_mode, float(c.sigma)
+        self._samples = np.zeros(S, np.int64)
+        self._frames = np.zeros(S, np.int64)
+        self._beats = np.zeros(S, np.int64)
+        self._eng = None
+        self._closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    @property
+    def frames_in(self):
+        return self._frames.copy()
+
+    @property
+    def samples_in(self):
+        return self._samples.copy()
+
+    @property
+    def beats_in(self):
+        return self._beats.copy()
+
+    def _engine(self):
+        if self._eng is None:         # bound at the first push: every refusal above and in push comes before a device is touched
+            self._eng = _lib.ScoreStreamEngine(self.dataset, self.capacity, self.max_audio_frames, self.max_beat_entries, self._cfg, self.device)
+        return self._eng
+
+    @property
+    def device_bytes(self) -> int:
+        """What the handle holds on the device (``ls_score_stream_info``); constant from the first push on."""
+        return self._engine().info()["device_bytes"]
+
+    def push(self, audio=None, lengths=None, beats=None):
+        """``audio`` [S, n] (numpy, CPU or CUDA tensor; n <= max_chunk): slot s's new samples in ``audio[s, :lengths[s]]`` (``lengths=None``:
+        n for every slot).  ``beats``: the dict a ``PostStream.push`` (or ``finish`` / ``close``) of the same slots returned -- its
+        ``beat_mask``, ``beat_first`` and ``beat_count``; for BEAT the row ``align_series`` of the mask is taken.  Either may be left out.
+        What would not fit a slot is refused (``ValueError``) before anything runs, and the stream stays as it was."""
+        if self._closed:
+            raise RuntimeError("the score stream is closed")
+        if audio is None and beats is None:
+            raise ValueError("pass audio, beats or both")
+        S = self.capacity
+        a = _lib.LsScoreStreamPushArgs()
+        members, fresh, new_frames, k = [], np.zeros(S, np.int64), np.zeros(S, np.int64), np.zeros(S, np.int64)
+        if audio is not None:
+            if len(audio.shape) != 2 or int(audio.shape[0]) != S:
+                raise ValueError(f"audio must be [{S}, n], got {list(audio.shape)}")
+            n_max = int(audio.shape[1])
+            if n_max > self.max_chunk:
+                raise ValueError(f"a push takes at most max_chunk = {self.max_chunk} samples per slot, got {n_max}")
+            fresh = np.full(S, n_max, np.int64) if lengths is None else _lib.host_lengths(lengths, S, 0, n_max, "lengths").astype(np.int64)
+            for s in range(S):
+                if 1 + (self._samples[s] + fresh[s]) // 512 > self.max_audio_frames:
+                    raise ValueError(f"slot {s} would hold {self._samples[s] + fresh[s]} samples, above the {self.max_samples} of max_seconds")
+                new_frames[s] = score_stream_plan(self._samples[s], fresh[s], False, self.pad_mode)[1]
+            members.append(audio)
+        elif lengths is not None:
+            raise ValueError("lengths are the valid samples of audio: pass audio")
+        if beats is not None:
+            mask, first, k = beats["beat_mask"], np.asarray(beats["beat_first"]).reshape(-1), np.asarray(beats["beat_count"]).reshape(-1).astype(np.int64)
+            if self._beat:
+                if len(mask.shape) != 3 or int(mask.shape[1]) != 6:
+                    raise ValueError(f"a BEAT beat_mask is [S, 6, Kb], got {list(mask.shape)}")
+                mask = mask[:, self.align_series]
+            if len(mask.shape) != 2 or int(mask.shape[0]) != S or first.shape != (S,) or k.shape != (S,):
+                raise ValueError(f"beat_mask [{S}, Kb] with beat_first and beat_count [{S}], got {list(mask.shape)}, {first.shape}, {k.shape}")
+            Kb = int(mask.shape[1])
+            if Kb > _lib.SCORE_STREAM_MAX_BEATS or (k < 0).any() or (k > Kb).any():
+                raise ValueError(f"beat_count must lie in [0, Kb] and Kb <= {_lib.SCORE_STREAM_MAX_BEATS}, got {k.tolist()} for Kb = {Kb}")
+            for s in range(S):
+                if k[s] and int(first[s]) != int(self._beats[s]):
+                    raise ValueError(f"slot {s} holds {self._beats[s]} beat entries, the chunk starts at {int(first[s])}")
+                if self._beats[s] + k[s] > self.max_beat_entries:
+                    raise ValueError(f"slot {s} would hold {self._beats[s] + k[s]} beat entries, above the {self.max_beat_entries} of max_seconds")
+            members.append(mask)
+        m = _lib._Marshal(self.device, *members)
+        a.on_device = int(m.on_device)
+        keep = []
+        if audio is not None:
+            lens32 = np.ascontiguousarray(fresh, np.int32)
+            keep.append(lens32)
+            a.n_max, a.audio, a.lengths = n_max, m.f32(members[0], (S, n_max)), lens32.ctypes.data
+        if beats is not None:
+            first64, k32 = np.ascontiguousarray(first, np.int64), np.ascontiguousarray(k, np.int32)
+            keep += [first64, k32]
+            a.beat_capacity, a.beats = Kb, m.u8(members[-1], (S, Kb))
+            a.beat_first, a.beat_count = first64.ctypes.data, k32.ctypes.data
+        if (audio is None or n_max == 0 or not fresh.any()) and (beats is None or Kb == 0 or not k.any()):
+            return
+        eng = self._engine()
+        m.ready()
+        eng.push(a)
+        self._samples += fresh
+        self._frames += new_frames
+        if beats is not None:
+            self._beats += k
+
+    def finish(self, slot) -> dict:
+        """End slot ``slot``'s series and score it.  Returns ``n_frames`` (audio frames), ``count`` (onsets), the outputs named in the
+        stream's ``want`` cut to the slot's own frames ([F], mel_db [F, 128]; host arrays, also for a stream that was fed device
+        tensors), and TED ``align_sum`` (float), ``n_beats``; BEAT ``align``.  The slot is free afterwards."""
+        slot = int(slot)
+        if not 0 <= slot < self.capacity or self._samples[slot] < 1:
+            raise ValueError(f"slot {slot} holds no audio")
+        return self._finish([slot])[slot]
+
+    def _finish(self, slots) -> dict:
+        if self._closed:
+            raise RuntimeError("the score stream is closed")
+        S = self.capacity
+        flags = np.zeros(S, np.int32)
+        flags[list(slots)] = 1
+        F = [1 + int(self._samples[s]) // 512 for s in range(S)]
+        for s in slots:
+            score_stream_plan(self._samples[s], 0, True, self.pad_mode)          # raises for what the engine refuses
+        cols = max(F[s] for s in slots)
+        o = _lib.LsScoreStreamOutputs()
+        o.on_device, o.cols = 0, cols
+        bufs = {"n_frames": np.zeros(S, np.int32), "count": np.zeros(S, np.int32)}
+        for name in self.want:
+            if name != "count":
+                bufs[name] = np.zeros((S, cols, 128) if name == "mel_db" else (S, cols), np.float32 if name in ("oenv", "mel_db", "rms") else np.int32)
+        if self._beat:
+            bufs["align"] = np.zeros(S, np.float32)
+        else:
+            bufs["align_sum"], bufs["n_beats"] = np.zeros(S, np.float64), np.zeros(S, np.int32)
+        for name, arr in bufs.items():
+            setattr(o, name, arr.ctypes.data)
+        self._engine().finish(flags, o)
+        res = {}
+        for s in slots:
+            r = {"n_frames": int(bufs["n_frames"][s]), "count": int(bufs["count"][s])}
+            for name in self.want:
+                if name != "count":
+                    r[name] = bufs[name][s, :F[s]].copy()
+            if self._beat:
+                r["align"] = float(bufs["align"][s])
+            else:
+                r["align_sum"], r["n_beats"] = float(bufs["align_sum"][s]), int(bufs["n_beats"][s])
+            res[s] = r
+            self._samples[s] = self._frames[s] = self._beats[s] = 0
+        return res
+
+    def close(self) -> dict:
+        """Finish every slot that holds audio (returns {slot: its ``finish`` dict}) and release the handle."""
+        if self._closed:
+            return {}
+        slots = [s for s in range(self.capacity) if self._samples[s] > 0]
+        res = self._finish(slots) if slots else {}
+        self._closed = True
+        if self._eng is not None:
+            self._eng.close()
+        return res
+
+
+def open_score_stream(dataset, capacity, max_seconds, sr=16000, device=0, **options) -> ScoreStream:
+    """Audio onsets and the beat-alignment scores for talks of any length: the scoring half of ``open_post_stream``.
+
+        ss = open_score_stream('ted', capacity, max_seconds=900)
+        ss.push(audio=chunk, lengths=None, beats=ps.push(frames))     # audio [S, n]; beats: a PostStream.push dict
+        res = ss.finish(slot)                                          # count, onset_raw, align_sum, n_beats (TED) / align (BEAT)
+        ss.close()
+
+    Only two steps of librosa's onset chain need the whole signal -- the clamp at max - 80 dB and the envelope's min / max
+    normalisation -- and both are order-independent reductions; the spectrum is causal.  A push computes the mel spectra of the audio
+    frames its samples decide (``score_stream_plan``) and appends the motion beats; ``finish`` pads the end at the slot's own last
+    sample, runs the tiled pick of ``audio_onsets_long`` on the slot's frames and the alignment sum against its beats.  Up to
+    4096 audio frames every output equals ``audio_onsets`` on the slot's samples alone bit for bit, under any chunking; up to 4096
+    pose frames ``align_sum`` / ``n_beats`` equal ``ted_beat_align`` and ``align`` ``beat_metrics_timeline``'s bit for bit
+    (tests/test_gpu_score_stream.py).  A slot does not depend on the other slots.
+
+    Everything is allocated at the first push for ``max_seconds`` per slot -- 516 B per audio frame (about 16 KB per second at 16 kHz),
+    one byte per pose frame, one slot's workspace for the finish -- and nothing grows (``device_bytes``).  ``options``: ``sr_pick``
+    (default ``sr`` on TED, 22050 on BEAT), ``pad_mode``, ``fmax``, ``delta``, ``sigma`` (0.1 / 0.3), ``fps`` (15), ``max_chunk``
+    (samples per slot and push, 65536), ``want`` (the per-frame outputs a finish returns), and for BEAT ``align_series`` (2),
+    ``onset_source`` ('onset_bt_rms') and ``time_rate`` (22050): ``score_timeline``'s choices.
+
+    Not built: a causal approximation of the normalisation (scores appear at the finish), SRGR online, device-resident lengths,
+    growing a slot beyond ``max_seconds``, results left on the device."""
+    return ScoreStream(dataset, capacity, max_seconds, sr, device, **options)
 
 
 def ted_beat_align(beat_mask, onset_frames, onset_count, sigma=TED_BEAT_SIGMA, fps=TED_FPS, sr=16000, hop=512, device=0):
@@ -394,6 +638,21 @@ class BeatConsistency:
         self.align_sum += float(total.sum())
         self.num_beats += int(counts[beats > 0].sum())
         return total, beats, counts
+
+    def push_score(self, result):
+        """A finished TED slot of a ``ScoreStream`` (the dict ``finish`` returns, or every dict of ``close``'s) into the running score,
+        with ``push_timeline``'s rule: a slot without a motion beat contributes neither its sum nor its onsets."""
+        if not result:
+            return
+        results = [result[k] for k in sorted(result)] if all(isinstance(v, dict) for v in result.values()) else [result]
+        if any("align_sum" not in r or "n_beats" not in r or "count" not in r for r in results):
+            raise ValueError("push_score takes the finish dict of a TED score stream (align_sum, n_beats, count)")
+        total = np.array([r["align_sum"] for r in results], np.float64)
+        beats = np.array([r["n_beats"] for r in results], np.int64)
+        counts = np.array([r["count"] for r in results], np.int64)
+        self.motion_beats_sum += int(beats.sum())             # push_timeline's accumulation, call for call
+        self.align_sum += float(total.sum())
+        self.num_beats += int(counts[beats > 0].sum())
 
     def score(self) -> float:
         return self.align_sum / self.num_beats
