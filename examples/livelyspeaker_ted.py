@@ -12,7 +12,7 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py [batch] --long-seconds N
     python examples/livelyspeaker_ted.py --long-seconds A,B,... [--drop-finished]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --edit-frames LO,HI [--edit-joints J0,J1,...] [--edit-text [--clip-text]]
-    python examples/livelyspeaker_ted.py [batch] --long-seconds N --stream-chunk SECONDS [--post [--score]]
+    python examples/livelyspeaker_ted.py [batch] --long-seconds N --stream-chunk SECONDS [--post [--score]] [--input-sr RATE]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --score-talk
     python examples/livelyspeaker_ted.py --pool SPEAKERS
     python examples/livelyspeaker_ted.py [batch] --clip-text
@@ -41,6 +41,8 @@ kept ones from the existing motion; it prints how far the edited frames moved fr
 --stream-chunk SECONDS (with --long-seconds N) feeds the same waveform to a STREAM instead, SECONDS of audio at a time
 (long_form.open_stream: push() returns a window's new frames as soon as the window's audio is complete, close() the zero-padded rest);
 it prints when each window's frames appeared and checks that the frames, concatenated, are bit for bit the timeline of the one call.
+--input-sr RATE (with --stream-chunk) makes the speech a RATE Hz int16 stereo signal, as a microphone delivers it: the one call samples
+audio_io.resample(signal, RATE), the stream is opened with input_sr=RATE, input_channels=2 and fed the int16 chunks themselves;
 --post (with --stream-chunk) lets the stream own a post-processing stream (open_stream(post='ted')): every push also returns the new
 frames' joint positions and the motion beats that have just become decidable, and it prints the pose shape and the beat times per push.
 --score (with --post) lets it own a score stream as well (open_stream(post='ted', score=True, max_seconds=N)): the audio of every push and
@@ -215,6 +217,13 @@ def main():
             del sys.argv[j:j + 2]
             if stream_chunk <= 0:
                 raise SystemExit("--stream-chunk takes a positive number of seconds")
+        input_sr = None
+        if "--input-sr" in sys.argv:
+            j = sys.argv.index("--input-sr")
+            input_sr = int(sys.argv[j + 1])
+            del sys.argv[j:j + 2]
+            if stream_chunk is None or input_sr < 1:
+                raise SystemExit("--input-sr takes a rate in Hz and goes with --stream-chunk: the stream is fed at that rate")
         post = "--post" in sys.argv
         if post:
             sys.argv.remove("--post")
@@ -240,7 +249,7 @@ def main():
         if drop:
             raise SystemExit("--drop-finished goes with a comma list of durations: equally long speeches finish together")
         seconds = float(arg)
-        return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source, edit, stream_chunk, post, score, score_talk)
+        return main_long(int(sys.argv[1]) if len(sys.argv) > 1 else 1, seconds, noise_source, edit, stream_chunk, post, score, score_talk, input_sr)
     if "--clip-text" in sys.argv:
         sys.argv.remove("--clip-text")
         return main_clip_text(int(sys.argv[1]) if len(sys.argv) > 1 else 64, noise_source)
@@ -359,7 +368,7 @@ def main_clip_text(B, noise_source):
     assert bool(torch.isfinite(sample).all()) and bool(torch.isfinite(decoded).all())
 
 
-def main_long(B, seconds, noise_source, edit=None, stream_chunk=None, post=False, score=False, score_talk=False):
+def main_long(B, seconds, noise_source, edit=None, stream_chunk=None, post=False, score=False, score_talk=False, input_sr=None):
     """`seconds` of 16 kHz speech per clip -> one stitched timeline at 15 fps (the LivelySpeaker chain, window after window on the device)."""
     import numpy as np
     from livelyspeaker_amd import long_form
@@ -367,6 +376,12 @@ def main_long(B, seconds, noise_source, edit=None, stream_chunk=None, post=False
     diffusion.noise_source = noise_source
     g = np.random.Generator(np.random.PCG64(synth.SEED_COND))
     audio = torch.from_numpy(0.1 * g.standard_normal((B, max(1, int(round(seconds * 16000))))).astype(np.float32)).cuda()
+    mic = None
+    if input_sr is not None:                                                                # a microphone's signal: int16 stereo at input_sr
+        from livelyspeaker_amd import audio_io
+        mic = torch.from_numpy((3000 * g.standard_normal((B, max(1, int(round(seconds * input_sr))), 2))).astype(np.int16)).cuda()
+        audio, _ = audio_io.resample(mic, input_sr)                                         # what the one call below samples
+        print(f"{input_sr} Hz int16 stereo {tuple(mic.shape)} -> 16 kHz mono {tuple(audio.shape)} on the device")
     W, _, n_frames = long_form.plan_windows(audio.shape[1], cfg)
     y = {k: torch.from_numpy(v).cuda() for k, v in synth.make_long_cond(cfg, B, W, scale=2.5).items()}
     text = torch.from_numpy(synth.make_text_features(B * W).reshape(B, W, 512)).cuda()          # one text feature per window
@@ -392,24 +407,27 @@ def main_long(B, seconds, noise_source, edit=None, stream_chunk=None, post=False
     if edit is not None:
         edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit, sag_decoder)
     if stream_chunk is not None:
-        stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, stream_chunk, scored if post else None, score)
+        stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, stream_chunk, scored if post else None, score, mic, input_sr)
 
 
-def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, chunk_seconds, scored=None, score=False):
+def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y, text, chunk_seconds, scored=None, score=False, mic=None,
+                    input_sr=None):
     """The waveform main_long sampled in one call, fed to a stream `chunk_seconds` at a time: every push carries the text feature of the
     window it would start (a held value), and a window's frames come back from the push that completed its audio.  `scored` (the
     timeline's post-processing, --post): the stream post-processes its frames as they arrive, and the pushes' poses and beats,
-    concatenated, are checked against it."""
-    n, L, W = max(1, int(round(chunk_seconds * 16000))), audio.shape[1], text.shape[1]
+    concatenated, are checked against it.  `mic` (--input-sr): the stream is fed that signal at `input_sr` instead, through its own resampler."""
+    rate, fed = (16000, audio) if mic is None else (input_sr, mic)
+    n, L, W = max(1, int(round(chunk_seconds * rate))), fed.shape[1], text.shape[1]
     torch.manual_seed(233)                                                                  # the seed of the one call: the same draws
     stream = long_form.open_stream(diffusion, model, y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim", skip_timesteps=80,
                                    sag=sag_decoder, post=None if scored is None else "ted",
-                                   **({"score": True, "max_seconds": L / 16000 + 1} if score else {}))
+                                   **({"score": True, "max_seconds": L / rate + 1} if score else {}),
+                                   **({} if mic is None else {"input_sr": input_sr, "input_channels": 2}))
     parts, poses, beats, t0 = [], [], [[] for _ in range(audio.shape[0])], time.perf_counter()
     for lo in list(range(0, L, n)) + [None]:
         held = {"text_features": text[:, min(stream.windows_run, W - 1)]}
         t1 = time.perf_counter()
-        new = stream.close(**held) if lo is None else stream.push(audio[:, lo:lo + n], **held)
+        new = stream.close(**held) if lo is None else stream.push(fed[:, lo:lo + n], **held)
         torch.cuda.synchronize()
         if scored is not None:
             new, posted = new
@@ -420,7 +438,7 @@ def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y
                 print(f"  post: pose {tuple(posted['pose'].shape)}, beats decided (clip 0, seconds): "
                       + (", ".join(f"{t:.2f}" for t in posted["motion_beat_times"][0]) or "none"))
         if new.shape[3]:
-            print(f"  {'close' if lo is None else f'audio {min(lo + n, L) / 16000:6.2f} s'}: window {stream.windows_run - 1} -> frames "
+            print(f"  {'close' if lo is None else f'audio {min(lo + n, L) / rate:6.2f} s'}: window {stream.windows_run - 1} -> frames "
                   f"{stream.frames_out - new.shape[3]}..{stream.frames_out - 1}, {(time.perf_counter() - t1) * 1e3:.1f} ms after its last sample "
                   f"arrived ({(time.perf_counter() - t0) * 1e3:.0f} ms into the stream)")
         parts.append(new)

@@ -1212,6 +1212,100 @@ int ls_score_stream_info(const ls_score_stream* h, int64_t* samples_in, int64_t*
 void ls_score_stream_close(ls_score_stream* h);
 const char* ls_score_stream_last_error(const ls_score_stream* h);
 
+/* ---- Audio front end: resample any integer rate to the model's rate on the device ---------------------------
+ * A polyphase windowed-sinc resampler, one-shot (ls_resample) and streaming (ls_resample_stream_*), with the mixdown of interleaved
+ * channels in front of the filter.  ONE DEFINITION: with g = gcd(in_sr, out_sr), up = out_sr / g, down = in_sr / g, q = max(up, down)
+ * and half = zeros * q,
+ *   h[i] = up * (rolloff / q) * sinc(rolloff * (i - half) / q) * kaiser(2 half + 1, beta)[i],   i = 0 .. 2 half
+ * (sinc and kaiser as numpy defines them; computed in double on the host, rounded to float32 once), and output m of x[0 .. n) is
+ *   y[m] = sum_k h[m down - k up + half] x[k],   m in [0, ceil(n up / down)),
+ * over the k in [0, n) whose tap exists.  This is scipy.signal.resample_poly(x, up, down, window = h / up).  The sum of one output is
+ * a chain of float32 fused multiply-adds in an order that depends on (up, down, half) alone -- not on the chunking, the slot, the
+ * batch or the output's place in a launch -- and a tap whose sample does not exist contributes nothing, so the streaming form gives
+ * bit for bit the whole-series call under any chunking.  in_sr == out_sr is a pass-through: the mixdown alone.
+ * Mixdown: audio is mono [.., n] or interleaved [.., n, C], 1 <= C <= LS_RESAMPLE_MAX_CHANNELS.  float32: the float32 sum in channel
+ * order times float(1 / C); int16: the exact int32 sum, converted, times float(1 / (32768 C)).
+ *
+ * ls_resample_ratio, ls_resample_plan and ls_resample_taps touch no device.
+ * ls_resample_ratio: up, down, half, n_taps = 2 half + 1, taps_per_output = floor(2 half / up) + 1 and carry_len =
+ * ceil((2 half + down) / up) + 1, the samples before a push that its outputs may read.  LS_EINVAL: a rate or zeros < 1, a NULL
+ * output; LS_EUNSUPPORTED: n_taps above 2^22.
+ * ls_resample_plan is the one definition of what a push emits: with n samples of a running series in, outputs [0, D(n)) are decided,
+ * D(n) = max(0, floor((n up - 1 - half) / down) + 1), and D(n) = ceil(n up / down) at the finish; a push from n_before to
+ * n_before + n_new emits [D(n_before), D(n_before + n_new)).  Over the pushes and the finish the ranges tile the whole-series output
+ * once, in order.  A pass-through plans with half = 0.  LS_EINVAL: NULL outputs, up or down < 1, a negative half or count, counts or
+ * products above 2^62, finishing a series without a sample.
+ * ls_resample_taps: h64 and / or h32 [2 half + 1] (one of them may be NULL).  LS_EINVAL: both NULL, up, down or zeros < 1, beta < 0,
+ * rolloff outside (0, 1]; LS_EUNSUPPORTED: more than 2^22 taps.
+ *
+ * ls_resample: audio [batch, row_stride] elements of dtype, clip b's lengths[b] frames of `channels` samples at its row's start;
+ * out [batch, out_stride] receives clip b's ceil(lengths[b] up / down) outputs and 0 behind them; out_lengths (HOST, nullable) those
+ * counts.  Nothing beyond a clip's own frames is read.  audio and out are device pointers iff on_device; lengths is a HOST array.
+ * Every refusal sits ahead of any HIP call.  LS_EINVAL: NULL args, audio, lengths or out, batch outside [1, 65535], an unknown dtype,
+ * channels outside [1, 8], a length outside [1, 2^31 - 1] or beyond row_stride / channels, out_stride below a clip's outputs, what
+ * ls_resample_ratio and ls_resample_taps refuse; LS_EUNSUPPORTED as they do (ls_resample_stream_last_error(NULL) names the count).
+ *
+ * ls_resample_stream_open allocates everything for `capacity` slots and max_chunk frames per slot and push: the tap table, two mono
+ * carries of carry_len + 3 samples per slot (written in turn; the 3: what a tap row padded to a multiple of 4 reaches), the slot table and the staging of host-side pushes.  Nothing grows
+ * afterwards.  LS_EINVAL ahead of any HIP call: capacity < 1, max_chunk < 1, what ls_resample refuses of the rates, dtype, channels
+ * and filter.
+ * ls_resample_stream_push: audio [S, n_max (, C)], slot s's lengths[s] new frames at its row's start; finish[s] != 0 ends slot s's
+ * series with this push (finish may be NULL).  out [S, out_capacity] receives slot s's new outputs from column 0 on; out_first and
+ * out_count [S] (HOST, nullable) the plan's range, filled before anything is launched.  A slot that finishes is empty afterwards: its
+ * next samples start a new series at sample 0.  Refused ahead of any launch, leaving the handle untouched -- LS_EINVAL: NULL args,
+ * lengths, or audio / out where a slot has frames / outputs, n_max outside [0, max_chunk], a length outside [0, n_max], a push the
+ * plan refuses (a finish on a slot without a sample), out_capacity below a slot's count; LS_ESTATE: a handle after a failed launch.
+ * ls_resample_stream_reset drops slot's series without emitting what is pending (no samples in, no carry); idempotent.  LS_EINVAL:
+ * a slot outside [0, capacity).
+ * Not built: non-integer rates, time-varying rates, device-resident lengths. */
+#define LS_RESAMPLE_F32 0
+#define LS_RESAMPLE_I16 1
+#define LS_RESAMPLE_MAX_CHANNELS 8
+typedef struct ls_resample_stream ls_resample_stream;
+typedef struct ls_resample_args {
+    int32_t batch;
+    int32_t on_device;
+    int32_t dtype;              /* LS_RESAMPLE_F32 | LS_RESAMPLE_I16                                                  */
+    int32_t channels;
+    int64_t row_stride;         /* elements between the rows of audio                                                 */
+    const void* audio;          /* [batch, row_stride]                                                                */
+    const int64_t* lengths;     /* [batch] HOST: frames per clip                                                      */
+    int32_t in_sr;
+    int32_t out_sr;
+    int32_t zeros;
+    int32_t reserved;
+    double beta;
+    double rolloff;
+    float* out;                 /* [batch, out_stride]                                                                */
+    int64_t out_stride;
+    int64_t* out_lengths;       /* [batch] HOST or NULL                                                               */
+} ls_resample_args;
+typedef struct ls_resample_stream_push_args {
+    int32_t on_device;
+    int32_t n_max;              /* frames per row of audio                                                            */
+    int64_t out_capacity;       /* row stride of out                                                                  */
+    const void* audio;          /* [S, n_max (, C)] or NULL when no slot has a frame                                  */
+    const int32_t* lengths;     /* [S] HOST                                                                           */
+    const int32_t* finish;      /* [S] HOST or NULL                                                                   */
+    float* out;                 /* [S, out_capacity] or NULL when no slot has an output                               */
+    int64_t* out_first;         /* [S] HOST or NULL                                                                   */
+    int64_t* out_count;         /* [S] HOST or NULL                                                                   */
+} ls_resample_stream_push_args;
+int ls_resample_ratio(int32_t in_sr, int32_t out_sr, int32_t zeros, int64_t* up, int64_t* down, int64_t* half, int64_t* taps_per_output,
+                      int64_t* carry_len, int64_t* n_taps);
+int ls_resample_plan(int64_t up, int64_t down, int64_t half, int64_t n_before, int64_t n_new, int32_t finishing, int64_t* out_first,
+                     int64_t* out_count);
+int ls_resample_taps(int64_t up, int64_t down, int32_t zeros, double beta, double rolloff, double* h64, float* h32);
+int ls_resample(int device, const ls_resample_args* a);
+int ls_resample_stream_open(int device, int32_t capacity, int32_t in_sr, int32_t out_sr, int32_t channels, int32_t dtype, int32_t zeros,
+                            double beta, double rolloff, int32_t max_chunk, ls_resample_stream** out);
+int ls_resample_stream_push(ls_resample_stream* h, const ls_resample_stream_push_args* a);
+int ls_resample_stream_reset(ls_resample_stream* h, int32_t slot);
+/* samples_in, outputs_done [capacity] (nullable): each slot's input frames and outputs so far */
+int ls_resample_stream_info(const ls_resample_stream* h, int64_t* samples_in, int64_t* outputs_done, int64_t* device_bytes);
+void ls_resample_stream_close(ls_resample_stream* h);
+const char* ls_resample_stream_last_error(const ls_resample_stream* h);
+
 /* ---- dataset ingest: recorded poses and audio -> model inputs ----------------------------------------------
  * The forward direction of the pose transforms above, as the reference's offline pipeline computes it: TED
  * DataPreprocessor._sample_from_clip (scripts/data_loader/data_preprocessor.py:69-167) with resample_pose_seq,

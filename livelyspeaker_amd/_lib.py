@@ -236,6 +236,17 @@ class LsScoreStreamOutputs(C.Structure):
         "n_frames", "count", "onset_raw", "onset_bt", "onset_bt_rms", "oenv", "mel_db", "rms", "align_sum", "n_beats", "align")]
 
 
+class LsResampleArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("batch", "on_device", "dtype", "channels")] + [
+        ("row_stride", C.c_int64), ("audio", C.c_void_p), ("lengths", c_i64p)] + [(n, C.c_int32) for n in ("in_sr", "out_sr", "zeros", "reserved")] + [
+        ("beta", C.c_double), ("rolloff", C.c_double), ("out", C.c_void_p), ("out_stride", C.c_int64), ("out_lengths", c_i64p)]
+
+
+class LsResampleStreamPushArgs(C.Structure):
+    _fields_ = [("on_device", C.c_int32), ("n_max", C.c_int32), ("out_capacity", C.c_int64), ("audio", C.c_void_p), ("lengths", c_i32p),
+                ("finish", c_i32p), ("out", C.c_void_p), ("out_first", c_i64p), ("out_count", c_i64p)]
+
+
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
            "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_edit_sag", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_long_pool_plan", "ls_long_pool_open", "ls_long_pool_join", "ls_long_pool_push", "ls_long_pool_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_set_row_keys", "ls_long_pool_keyed", "ls_long_pool_set_key", "ls_long_pool_keys", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
@@ -250,6 +261,8 @@ EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set
            "ls_post_stream_last_error",
            "ls_score_stream_plan", "ls_score_stream_open", "ls_score_stream_push", "ls_score_stream_finish", "ls_score_stream_info",
            "ls_score_stream_close", "ls_score_stream_last_error",
+           "ls_resample_ratio", "ls_resample_plan", "ls_resample_taps", "ls_resample", "ls_resample_stream_open", "ls_resample_stream_push",
+           "ls_resample_stream_reset", "ls_resample_stream_info", "ls_resample_stream_close", "ls_resample_stream_last_error",
            "ls_ingest_plan", "ls_ted_ingest", "ls_beat_ingest",
            "ls_train_create", "ls_train_destroy", "ls_train_last_error", "ls_train_set_schedule", "ls_train_param_count",
            "ls_train_flat_size", "ls_train_param_info", "ls_train_set_weight", "ls_train_get_weight", "ls_train_forward_backward",
@@ -349,6 +362,18 @@ def load_library(build_if_missing: bool = True):
     lib.ls_score_stream_close.restype = None
     lib.ls_score_stream_last_error.argtypes = [C.c_void_p]
     lib.ls_score_stream_last_error.restype = C.c_char_p
+    lib.ls_resample_ratio.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [c_i64p] * 6
+    lib.ls_resample_plan.argtypes = [C.c_int64] * 5 + [C.c_int32, c_i64p, c_i64p]
+    lib.ls_resample_taps.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, c_f64p, c_f32p]
+    lib.ls_resample.argtypes = [C.c_int, C.POINTER(LsResampleArgs)]
+    lib.ls_resample_stream_open.argtypes = [C.c_int] + [C.c_int32] * 6 + [C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.ls_resample_stream_push.argtypes = [C.c_void_p, C.POINTER(LsResampleStreamPushArgs)]
+    lib.ls_resample_stream_reset.argtypes = [C.c_void_p, C.c_int32]
+    lib.ls_resample_stream_info.argtypes = [C.c_void_p, c_i64p, c_i64p, c_i64p]
+    lib.ls_resample_stream_close.argtypes = [C.c_void_p]
+    lib.ls_resample_stream_close.restype = None
+    lib.ls_resample_stream_last_error.argtypes = [C.c_void_p]
+    lib.ls_resample_stream_last_error.restype = C.c_char_p
     lib.ls_forward.argtypes = [C.c_void_p, C.POINTER(LsForwardArgs)]
     lib.ls_step.argtypes = [C.c_void_p, C.POINTER(LsStepArgs)]
     lib.ls_plms_step.argtypes = [C.c_void_p, C.POINTER(LsPlmsStepArgs)]
@@ -764,6 +789,91 @@ class ScoreStreamEngine:
     def close(self):
         if getattr(self, "h", None) and self.h.value:
             self.lib.ls_score_stream_close(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+RESAMPLE_MAX_CHANNELS = 8        # LS_RESAMPLE_MAX_CHANNELS
+RESAMPLE_DTYPES = {"float32": 0, "int16": 1}      # LS_RESAMPLE_F32, LS_RESAMPLE_I16
+
+
+def resample_ratio(in_sr, out_sr, zeros=32) -> dict:
+    """ls_resample_ratio (no GPU needed): ``up``, ``down``, ``half``, ``taps_per_output``, ``carry_len`` and ``n_taps`` of a rate pair.
+    ``ValueError`` for a rate or ``zeros`` below 1, ``EngineError`` for more than 2^22 taps."""
+    v = [C.c_int64() for _ in range(6)]
+    for name, x in (("in_sr", in_sr), ("out_sr", out_sr), ("zeros", zeros)):
+        if isinstance(x, bool) or int(x) != x or not 1 <= int(x) < 1 << 31:
+            raise ValueError(f"{name} must be an integer in [1, 2^31), got {x!r}")
+    rc = load_library().ls_resample_ratio(int(in_sr), int(out_sr), int(zeros), *[C.byref(x) for x in v])
+    if rc == -5:        # LS_EUNSUPPORTED
+        raise EngineError(f"{in_sr} -> {out_sr} Hz with {zeros} zeros needs more than 2^22 taps")
+    if rc != 0:
+        raise ValueError(f"no ratio for {in_sr} -> {out_sr} Hz with {zeros} zeros: all three must be >= 1")
+    return dict(zip(("up", "down", "half", "taps_per_output", "carry_len", "n_taps"), (int(x.value) for x in v)))
+
+
+def resample_ratio_plan(up, down, half, n_before, n_new, finishing=False):
+    """ls_resample_plan (no GPU needed): ``(out_first, out_count)``, the outputs a push of ``n_new`` samples decides on a series that
+    holds ``n_before``; ``finishing`` adds what the end of the series still owes.  ``ValueError`` for what the engine refuses."""
+    first, count = C.c_int64(), C.c_int64()
+    args = [int(v) for v in (up, down, half, n_before, n_new)]
+    if any(not -(1 << 63) <= v < 1 << 63 for v in args) or load_library().ls_resample_plan(*args, int(bool(finishing)), C.byref(first), C.byref(count)) != 0:
+        raise ValueError(f"no plan for up {up}, down {down}, half {half}, {n_before} + {n_new} samples (finishing={bool(finishing)}): up and down "
+                         "must be >= 1, half and the counts >= 0 and at most 2^62 (also times up), and a series that is finished must hold a sample")
+    return int(first.value), int(count.value)
+
+
+def resample_taps(up, down, zeros=32, beta=12.0, rolloff=0.95):
+    """ls_resample_taps (no GPU needed): ``(h64, h32)``, the ``2 * zeros * max(up, down) + 1`` taps in double and rounded to float32."""
+    q = max(int(up), int(down))
+    if int(up) < 1 or int(down) < 1 or int(zeros) < 1 or not float(beta) >= 0 or not 0 < float(rolloff) <= 1:
+        raise ValueError(f"up, down and zeros must be >= 1, beta >= 0 and rolloff in (0, 1]: got {up}, {down}, {zeros}, {beta}, {rolloff}")
+    if 2 * int(zeros) * q + 1 > 1 << 22:
+        raise EngineError(f"up {up}, down {down} with {zeros} zeros needs {2 * int(zeros) * q + 1} taps, above 2^22")
+    h64, h32 = np.empty(2 * int(zeros) * q + 1, np.float64), np.empty(2 * int(zeros) * q + 1, np.float32)
+    rc = load_library().ls_resample_taps(int(up), int(down), int(zeros), float(beta), float(rolloff), h64.ctypes.data_as(c_f64p), h32.ctypes.data_as(c_f32p))
+    if rc != 0:
+        raise EngineError(f"ls_resample_taps failed ({rc})")
+    return h64, h32
+
+
+class ResampleStreamEngine:
+    """One ``ls_resample_stream`` handle: ``capacity`` slots of resampler state on one GPU (``audio_io.open_resample_stream``)."""
+
+    def __init__(self, capacity, in_sr, out_sr, channels, dtype, zeros, beta, rolloff, max_chunk, device=0):
+        self.lib = load_library()
+        self.h = C.c_void_p()
+        self.device, self.S = int(device), int(capacity)
+        rc = self.lib.ls_resample_stream_open(self.device, self.S, int(in_sr), int(out_sr), int(channels), RESAMPLE_DTYPES[dtype], int(zeros), float(beta),
+                                              float(rolloff), int(max_chunk), C.byref(self.h))
+        if rc != 0:
+            self.h = C.c_void_p()
+            raise EngineError(f"ls_resample_stream_open failed ({rc}): {self.lib.ls_resample_stream_last_error(None).decode()}")
+
+    def push(self, args: "LsResampleStreamPushArgs"):
+        rc = self.lib.ls_resample_stream_push(self.h, C.byref(args))
+        if rc != 0:
+            msg = self.lib.ls_resample_stream_last_error(self.h).decode()
+            raise (ValueError if rc == -1 else EngineError)(f"ls_resample_stream_push failed ({rc}): {msg}")
+
+    def reset(self, slot):
+        if self.lib.ls_resample_stream_reset(self.h, int(slot)) != 0:
+            raise ValueError(f"ls_resample_stream_reset: {self.lib.ls_resample_stream_last_error(self.h).decode()}")
+
+    def info(self) -> dict:
+        a, b, nbytes = np.zeros(self.S, np.int64), np.zeros(self.S, np.int64), C.c_int64()
+        if self.lib.ls_resample_stream_info(self.h, a.ctypes.data_as(c_i64p), b.ctypes.data_as(c_i64p), C.byref(nbytes)) != 0:
+            raise EngineError("ls_resample_stream_info failed")
+        return {"samples_in": a, "outputs_done": b, "device_bytes": int(nbytes.value)}
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.ls_resample_stream_close(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

@@ -15,7 +15,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libls_hip.so")
-SOURCES = ["ls_api.cpp", "ls_weights.cpp", "ls_chain.hip", "ls_chain_api.cpp", "ls_chain_plan.cpp", "ls_plan.cpp", "ls_sample.cpp", "ls_torch_rng.cpp", "ls_sag_api.cpp", "ls_sag_enc_api.cpp", "ls_clip_text_api.cpp", "ls_step.hip", "ls_step_beat.hip", "ls_coop.hip", "ls_pass.hip", "ls_mix.hip", "ls_long.hip", "ls_prepare.hip", "ls_sag.hip", "ls_sag_enc.hip", "ls_clip_text.hip", "ls_post.hip", "ls_timeline.hip", "ls_post_stream.hip", "ls_post_stream_api.cpp", "ls_post_stream_plan.cpp", "ls_beat_metrics.hip", "ls_onsets.hip", "ls_onsets_long.hip", "ls_score_stream.hip", "ls_score_stream_api.cpp", "ls_score_plan.cpp", "ls_onsets_tables.cpp", "ls_ingest.hip", "ls_ingest_api.cpp", "ls_ingest_plan.cpp", "ls_conv.hip", "ls_train_api.cpp", "ls_gemm.hip", "ls_train_kernels.hip", "ls_train_bwd.hip", "ls_eval.hip", "ls_torch_philox.hip", "ls_philox_rows.hip", "ls_plms.hip", "ls_bpd.hip"]
+SOURCES = ["ls_api.cpp", "ls_weights.cpp", "ls_chain.hip", "ls_chain_api.cpp", "ls_chain_plan.cpp", "ls_plan.cpp", "ls_sample.cpp", "ls_torch_rng.cpp", "ls_sag_api.cpp", "ls_sag_enc_api.cpp", "ls_clip_text_api.cpp", "ls_step.hip", "ls_step_beat.hip", "ls_coop.hip", "ls_pass.hip", "ls_mix.hip", "ls_long.hip", "ls_prepare.hip", "ls_sag.hip", "ls_sag_enc.hip", "ls_clip_text.hip", "ls_post.hip", "ls_timeline.hip", "ls_post_stream.hip", "ls_post_stream_api.cpp", "ls_post_stream_plan.cpp", "ls_beat_metrics.hip", "ls_onsets.hip", "ls_onsets_long.hip", "ls_score_stream.hip", "ls_score_stream_api.cpp", "ls_score_plan.cpp", "ls_onsets_tables.cpp", "ls_resample.hip", "ls_resample_api.cpp", "ls_resample_plan.cpp", "ls_ingest.hip", "ls_ingest_api.cpp", "ls_ingest_plan.cpp", "ls_conv.hip", "ls_train_api.cpp", "ls_gemm.hip", "ls_train_kernels.hip", "ls_train_bwd.hip", "ls_eval.hip", "ls_torch_philox.hip", "ls_philox_rows.hip", "ls_plms.hip", "ls_bpd.hip"]
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "ls_hip.h")]
 STAMP = LIB + ".srchash"          # hash of the sources the library was built from (travels with it; git-ignored)
 

@@ -37,7 +37,7 @@ from __future__ import annotations
 import numpy as np
 import torch as th
 
-from . import _lib, postprocess, ref_draws
+from . import _lib, audio_io, postprocess, ref_draws
 from . import gaussian_diffusion as gd
 
 AUDIO_STRIDE = 32000        # audio samples between two windows: T - n_pre_seq = 30 frames at 15 fps of 16 kHz audio
@@ -342,6 +342,37 @@ class _Session:
         elif max_seconds is not None:
             raise ValueError("max_seconds sizes the score stream: pass score=True as well")
 
+    def _init_input(self, input_sr, input_channels, resample, slots):
+        """``input_sr=``: None, or the rate of the audio the session is fed: it then owns an ``audio_io.ResampleStream`` of as many slots
+        (``input_channels`` interleaved channels, float32 or int16 as the first push has it; ``resample``: a dict of ``zeros``, ``beta``,
+        ``rolloff``, ``max_chunk``) whose 16 kHz output is what the windows see.  No device is touched here."""
+        self._in = None
+        if input_sr is None:
+            if input_channels != 1 or resample is not None:
+                raise ValueError("input_channels and resample describe the audio of input_sr=: pass input_sr as well")
+            return
+        opts = dict(resample or {})
+        unknown = set(opts) - {"zeros", "beta", "rolloff", "max_chunk"}
+        if unknown:
+            raise ValueError(f"resample takes zeros, beta, rolloff and max_chunk, got {sorted(unknown)}")
+        self._in = audio_io.open_resample_stream(slots, input_sr, audio_io.OUT_SR, channels=input_channels, dtype=None, **opts)
+
+    def _input_plan(self, audio, lengths=None, finish=None):
+        """What a chunk at the input rate (or the finish of the slots flagged) will give the windows, ahead of anything that runs:
+        ``(out_count [S], feed)``.  The resampler checks the chunk and plans its outputs on the host and is left as it is; ``feed()``
+        pushes the chunk through it on the engine's device and returns the 16 kHz samples ``[S, K]`` on the chunk's side.  ``_feed``
+        calls it once every refusal of the session has passed, so a refused call leaves session and resampler as they were."""
+        count = self._in.check(audio, lengths, finish)[5]
+        cuda = self._last_dev.type == "cuda" if audio is None else _lib._is_cuda(audio)
+
+        def feed():
+            self._in.device = self._engine().device
+            got = self._in.push(audio, lengths, finish, device_out=cuda)
+            assert (got["out_count"] == count).all()
+            return gd._as_tensor(got["audio"], th.device("cuda", self._in.device) if cuda else th.device("cpu"))
+
+        return count, feed
+
     def _check_post_frames(self, most):
         """Ahead of the sampling: a push of the post-processing stream takes at most 256 frames per slot."""
         if self._post_kind is not None and most > postprocess.POST_STREAM_MAX_CHUNK:
@@ -412,7 +443,7 @@ class LongStream(_Session):
     """A running ``open_stream`` session; see there.  ``samples_in``, ``windows_run``, ``frames_out``: host ints."""
 
     def __init__(self, diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag, post=None,
-                 score=None, max_seconds=None):
+                 score=None, max_seconds=None, input_sr=None, input_channels=1, resample=None):
         seed_poses, vid_indices, scale, emo = _as_tensors(seed_poses, vid_indices, scale, emo)
         B = int(seed_poses.shape[0]) if seed_poses.ndim else 0
         rag = getattr(model, "model", None)
@@ -426,6 +457,8 @@ class LongStream(_Session):
             raise ValueError(f"a stream holds one emotion id per clip: emo must be [{B}], got {list(emo.shape)}")
         self._diffusion, self._rag, self._sag, self._B = diffusion, rag, sag, B
         self._init_post(post, rag, B, score, max_seconds)
+        self._init_input(input_sr, input_channels, resample, B)
+        self.input_samples_in = 0                       # frames at input_sr; samples_in counts the 16 kHz samples the windows see
         self._cond = (seed_poses.float(), vid_indices, scale.float())
         self._emo, self._text = emo, None               # held on the host side only until the next engine call takes them
         self._have_emo = self._have_text = False
@@ -441,15 +474,17 @@ class LongStream(_Session):
     def _open(self, eng):
         eng.long_stream_open(*self._cond)
 
-    def _feed(self, chunk, emo, text_features, closing):
+    def _feed(self, chunk, emo, text_features, closing, lazy=None):
+        """``lazy`` (with ``input_sr=``): ``(n, feed)`` in place of ``chunk`` -- its 16 kHz samples per clip, known ahead, and the call that
+        makes it (``_input_plan``), which runs behind every refusal."""
         if self._closed:
             raise RuntimeError("the stream is closed")
         rag, B, diffusion = self._rag, self._B, self._diffusion
         chunk, emo, text_features = _as_tensors(chunk, emo, text_features)
-        if chunk.ndim != 2 or int(chunk.shape[0]) != B:
+        if lazy is None and (chunk.ndim != 2 or int(chunk.shape[0]) != B):
             raise ValueError(f"audio_chunk must be [{B}, n], got {list(chunk.shape)}")
         self._check_held(emo, text_features, B)
-        n = int(chunk.shape[1])
+        n = int(chunk.shape[1]) if lazy is None else int(lazy[0])
         first, k = _lib.long_stream_plan(self.samples_in, n, int(rag.audio_len), closing)
         emo = emo if emo is not None else self._emo
         text_features = text_features if text_features is not None else self._text
@@ -469,6 +504,8 @@ class LongStream(_Session):
         if self._sag is not None:
             kw["sag"] = self._sag.engine()
             kw["text_features"] = None if text_features is None else text_features.float()
+        if lazy is not None:
+            chunk = lazy[1]()
         out_dev = self._last_dev = chunk.device
         frames, ran = eng.long_stream_push(chunk.float(), closing=closing, emo=emo, device_out=out_dev.type == "cuda", **kw)
         self._have_emo, self._have_text = self._have_emo or emo is not None, self._have_text or text_features is not None
@@ -485,16 +522,29 @@ class LongStream(_Session):
 
     def push(self, audio_chunk, emo=None, text_features=None):
         """Feed ``audio_chunk`` [B, n], n >= 0; returns the new frames ``[B, J, F, k]`` of the windows it completed (k may be 0); with
-        ``post=``, ``(frames, post_dict)``."""
-        return self._feed(audio_chunk, emo, text_features, False)
+        ``post=``, ``(frames, post_dict)``.  With ``input_sr=``: ``[B, n]`` or ``[B, n, C]`` at that rate."""
+        if self._in is None:
+            return self._feed(audio_chunk, emo, text_features, False)
+        if self._closed:
+            raise RuntimeError("the stream is closed")
+        count, feed = self._input_plan(audio_chunk)                 # every clip is fed alike: the counts are equal
+        res = self._feed(None, emo, text_features, False, lazy=(count[0], feed))
+        self.input_samples_in = int(self._in.samples_in[0])
+        return res
 
     def close(self, emo=None, text_features=None):
         """End the stream: the frames of the windows ``plan_windows(samples_in)`` still owes, with silence behind the last sample."""
-        return self._feed(th.zeros((self._B, 0), device=self._last_dev), emo, text_features, True)     # on the device of the last chunk
+        tail = th.zeros((self._B, 0), device=self._last_dev)       # on the device of the last chunk
+        if self._in is None or self._closed or not self.input_samples_in:
+            return self._feed(tail, emo, text_features, True)
+        count, feed = self._input_plan(None, finish=np.ones(self._B, bool))       # the resampler's last outputs come first
+        res = self._feed(None, emo, text_features, True, lazy=(count[0], feed))
+        self._in.close()
+        return res
 
 
 def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False,
-                sag=None, post=None, score=None, max_seconds=None):
+                sag=None, post=None, score=None, max_seconds=None, input_sr=None, input_channels=1, resample=None):
     """The online form of ``sample_long``: a session that is fed audio in chunks of any size and returns a window's new frames as soon
     as that window's audio is complete.
 
@@ -538,11 +588,20 @@ def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, samp
     ``'align'`` [B]), which is what ``score_timeline`` gives for the concatenated frames and audio -- without its limits of 4096 frames.
     ``score=True`` without ``post=`` raises; with ``score`` unset nothing changes.
 
+    ``input_sr=`` (an integer rate in Hz; with it ``input_channels=`` and ``resample=``, a dict of ``audio_io.resample``'s ``zeros``, ``beta``,
+    ``rolloff`` and of ``max_chunk``): ``push`` takes chunks at THAT rate, ``[B, n]`` or interleaved ``[B, n, C]``, float32 or int16 (as the
+    first push has it), at most ``max_chunk`` (65536) frames each.  The session owns an ``audio_io.ResampleStream`` of B slots on the
+    engine's device; what it emits is what the windows see, so the frames are bit for bit those of a plain stream fed
+    ``audio_io.resample(whole, input_sr)`` (tests/test_gpu_long_stream_sr.py).  A chunk on the device stays there; ``close`` finishes the
+    resampler first.  ``samples_in`` stays in 16 kHz samples, ``input_samples_in`` counts the frames fed.  ``score=True`` sees the resampled
+    audio.  ``input_sr=None``: nothing changes.
+
     Clips that join or leave while others run, each fed at its own rate: ``open_pool``.
 
     Not built: ``audio_lengths`` / ``drop_finished``, ``edit_long`` on a running stream, PLMS, ``const_noise``, ``dump_steps``,
     sharded calls, a non-blocking ``push``."""
-    return LongStream(diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag, post, score, max_seconds)
+    return LongStream(diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag, post, score, max_seconds,
+                      input_sr, input_channels, resample)
 
 
 def pool_plan(samples_in, windows_run, new, closing, open, cfg):
@@ -562,7 +621,7 @@ class LongPool(_Session):
     and in a keyed pool ``key`` (uint64; of a free slot: its last clip's)."""
 
     def __init__(self, diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post=None, noise_keys=None, score=None,
-                 max_seconds=None):
+                 max_seconds=None, input_sr=None, input_channels=1, resample=None):
         S = int(capacity)
         if S < 1:
             raise ValueError(f"capacity must be >= 1, got {capacity}")
@@ -580,6 +639,7 @@ class LongPool(_Session):
         _check_model(diffusion, rag)
         self._diffusion, self._rag, self._sag, self._S = diffusion, rag, sag, S
         self._init_post(post, rag, S, score, max_seconds)
+        self._init_input(input_sr, input_channels, resample, S)
         self._kw = _loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised)
         self._keyed, self._joins = noise_keys == "clip", 0
         if diffusion.noise_source == "philox":          # one seed per pool: row r of round q draws at sample_offset + r + (q << 48); keyed: at the clip's key
@@ -601,7 +661,10 @@ class LongPool(_Session):
 
     @property
     def slots(self):
-        return {k: v.copy() for k, v in self._state.items()}
+        out = {k: v.copy() for k, v in self._state.items()}
+        if self._in is not None:
+            out["input_samples_in"] = self._in.samples_in          # frames at input_sr of each slot's running clip
+        return out
 
     def _open(self, eng):
         eng.long_pool_open(self._S)
@@ -660,18 +723,22 @@ class LongPool(_Session):
             eng.long_pool_set_key(slot, k)
             self._state["key"][slot] = k
         self._joins += 1
+        if self._in is not None:
+            self._in.reset(slot)          # a new series at sample 0 (a slot that left or was closed is empty already)
         self._refresh()
         self._have_text[slot] = text_features is not None
         return slot
 
-    def _feed(self, audio, lengths, closing, emo, text_features, given):
+    def _feed(self, audio, lengths, closing, emo, text_features, given, lazy=None):
+        """``lazy`` (with ``input_sr=``): the call that makes ``audio`` (``_input_plan``) -- ``lengths`` are then its 16 kHz counts, known
+        ahead -- which runs behind every refusal."""
         if self._closed:
             raise RuntimeError("the pool is closed")
         rag, S, diffusion = self._rag, self._S, self._diffusion
         audio, emo, text_features = _as_tensors(audio, emo, text_features)
-        if audio.ndim != 2 or int(audio.shape[0]) != S:
+        if lazy is None and (audio.ndim != 2 or int(audio.shape[0]) != S):
             raise ValueError(f"audio must be [{S}, n_max], got {list(audio.shape)}")
-        n_max = int(audio.shape[1])
+        n_max = int(audio.shape[1]) if lazy is None else int(np.max(lengths))
         lens = _lib.host_lengths(lengths, S, 0, n_max, "lengths").astype(np.int64)
         self._check_held(emo, text_features, S)
         st = self._state
@@ -696,6 +763,8 @@ class LongPool(_Session):
             diffusion.last_tape_segments = 1
         if self._sag is not None:
             kw["sag"] = self._sag.engine()
+        if lazy is not None:
+            audio = lazy()
         out_dev = self._last_dev = audio.device
         frames, counts, ran = eng.long_pool_push(audio.float(), lens, closing=closing, emo=emo if bits.any() else None,
                                                  text_features=None if text_features is None or not bits.any() else text_features.float(),
@@ -712,13 +781,29 @@ class LongPool(_Session):
     def push(self, audio, lengths, emo=None, text_features=None, given=None):
         """Feed ``audio`` [S, n_max]: ``lengths[s]`` samples for slot s (0 for a slot that is free or has nothing new).  Returns
         ``(frames [S, J, F, K], counts)``: slot s's new frames in ``frames[s, ..., :counts[s]]``, zero behind them; K = max(counts).
-        With ``post=``: ``(frames, counts, post_dict)``."""
-        return self._feed(audio, lengths, np.zeros(self._S, np.int32), emo, text_features, given)
+        With ``post=``: ``(frames, counts, post_dict)``.  With ``input_sr=``: ``[S, n_max]`` or ``[S, n_max, C]`` at that rate, ``lengths`` in its
+        frames."""
+        if self._in is None:
+            return self._feed(audio, lengths, np.zeros(self._S, np.int32), emo, text_features, given)
+        if self._closed:
+            raise RuntimeError("the pool is closed")
+        n_max = int(audio.shape[1]) if hasattr(audio, "shape") and len(audio.shape) >= 2 else 0
+        lens = _lib.host_lengths(lengths, self._S, 0, n_max, "lengths")
+        if (lens[~self._state["open"]] > 0).any():
+            raise ValueError(f"samples for a slot that is not open: lengths {lens.tolist()}, open {self._state['open'].tolist()}")
+        count, feed = self._input_plan(audio, lens)
+        return self._feed(None, count, np.zeros(self._S, np.int32), emo, text_features, given, lazy=feed)
 
     def _leave(self, which):
         closing = np.zeros(self._S, np.int32)
         closing[which] = 1
         J, F = int(self._rag.njoints), int(self._rag.nfeats)
+        if self._in is not None and closing.any():      # the resampler's last outputs of the slots that leave come first
+            held = self._in.samples_in > 0
+            if not held[closing.astype(bool)].all():
+                raise ValueError(f"closing a slot that was fed no sample: slots {np.nonzero(closing.astype(bool) & ~held)[0].tolist()}")
+            count, feed = self._input_plan(None, finish=closing.astype(bool))
+            return self._feed(None, count, closing, None, None, None, lazy=feed)
         if not closing.any():
             frames, counts = th.zeros((self._S, J, F, 0), device=self._last_dev), np.zeros(self._S, np.int32)
             if self._post_kind is None:
@@ -745,6 +830,8 @@ class LongPool(_Session):
             self._post.close()            # every series has been finished by the call above
         if self._score is not None:
             self._score.close()
+        if self._in is not None:
+            self._in.close()
         return res
 
 
@@ -758,7 +845,7 @@ def pool_keys(keys, windows_run, n_windows):
 
 
 def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False, sag=None, post=None, noise_keys=None,
-              score=None, max_seconds=None):
+              score=None, max_seconds=None, input_sr=None, input_channels=1, resample=None):
     """``open_stream`` for clips that start and stop at different times and arrive at different rates: a session pool of ``capacity``
     slots on ONE engine.
 
@@ -812,9 +899,16 @@ def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=
     slots, fed the audio of every push and the post stream's beats; the post dict of a ``leave`` (and of ``close``) carries ``'score'``
     for the slots it finished -- each clip's own onsets and alignment score, as in ``open_stream``.
 
+    ``input_sr=``, ``input_channels=``, ``resample=``: as in ``open_stream`` -- ``push`` takes ``[S, n_max]`` or ``[S, n_max, C]`` at that rate with
+    ``lengths`` in its frames, through an ``audio_io.ResampleStream`` of ``capacity`` slots on the engine's device.  ``leave`` and ``close``
+    finish the resampler of the slots they end before the windows those still owe; ``join`` resets its slot's resampler
+    (``ResampleStream.reset``; a no-op for a slot that left).  ``slots['samples_in']`` stays in 16 kHz samples,
+    ``slots['input_samples_in']`` is added beside it.
+
     Not built: device-resident ``lengths``, ``edit_long`` on a pool, PLMS, ``const_noise``,
     ``dump_steps``, sharded calls, a non-blocking ``push``."""
-    return LongPool(diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post, noise_keys, score, max_seconds)
+    return LongPool(diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post, noise_keys, score, max_seconds, input_sr,
+                    input_channels, resample)
 
 
 def _edit_ranges(frames, B, n_frames):
