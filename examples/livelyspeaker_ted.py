@@ -12,6 +12,7 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py [batch] --long-seconds N
     python examples/livelyspeaker_ted.py --long-seconds A,B,... [--drop-finished]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --edit-frames LO,HI [--edit-joints J0,J1,...] [--edit-text [--clip-text]]
+    python examples/livelyspeaker_ted.py --long-seconds 20,45.5,8 --edit-frames LO,HI [--edit-clip K] [...]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --stream-chunk SECONDS [--post [--score]] [--input-sr RATE]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --score-talk
     python examples/livelyspeaker_ted.py --pool SPEAKERS
@@ -38,6 +39,9 @@ range touches, 20 refinement steps each), everything else is kept bit for bit, a
 --edit-text makes that edit SCRIPT-GUIDED (edit_long(sag=, text_features=)): the edited frames start from the SAG decoder's output for
 one text feature [B, 512] -- a synthetic stand-in, or with --clip-text a sentence of synthetic tokens through CLIPTextEncoder -- and the
 kept ones from the existing motion; it prints how far the edited frames moved from the unscripted edit with the same seed.
+--edit-clip K edits clip K of the batch alone, and --edit-frames after a comma list of durations edits the RAGGED batch (every clip on
+the part of [LO, HI) that lies inside its own frames): both through the compact form (edit_long(compact=True / audio_lengths=)), which
+runs only the clip-windows the edit touches; the line printed lists them.
 --stream-chunk SECONDS (with --long-seconds N) feeds the same waveform to a STREAM instead, SECONDS of audio at a time
 (long_form.open_stream: push() returns a window's new frames as soon as the window's audio is complete, close() the zero-padded rest);
 it prints when each window's frames appeared and checks that the frames, concatenated, are bit for bit the timeline of the one call.
@@ -203,6 +207,12 @@ def main():
                 raise SystemExit("--edit-joints goes with --edit-frames")
             edit["joints"] = [int(v) for v in sys.argv[j + 1].split(",") if v]
             del sys.argv[j:j + 2]
+        if "--edit-clip" in sys.argv:
+            j = sys.argv.index("--edit-clip")
+            if edit is None:
+                raise SystemExit("--edit-clip goes with --edit-frames")
+            edit["clip"] = int(sys.argv[j + 1])
+            del sys.argv[j:j + 2]
         if "--edit-text" in sys.argv:
             sys.argv.remove("--edit-text")
             if edit is None:
@@ -240,12 +250,10 @@ def main():
         drop = "--drop-finished" in sys.argv
         if drop:
             sys.argv.remove("--drop-finished")
-        if edit is not None and ("," in arg or drop):
-            raise SystemExit("--edit-frames edits the timeline of --long-seconds N (one duration; ragged batches are not edited)")
         if stream_chunk is not None and ("," in arg or drop or edit is not None):
             raise SystemExit("--stream-chunk streams the waveform of --long-seconds N (one duration, no edit)")
         if "," in arg:
-            return main_long_ragged([float(v) for v in arg.split(",") if v], noise_source, drop)
+            return main_long_ragged([float(v) for v in arg.split(",") if v], noise_source, drop, edit)
         if drop:
             raise SystemExit("--drop-finished goes with a comma list of durations: equally long speeches finish together")
         seconds = float(arg)
@@ -521,31 +529,46 @@ def main_pool(speakers, noise_source, tick_seconds=0.5, keyed=False):
               f"over {served.shape[2]} frames")
 
 
-def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit, sag_decoder=None):
+def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit, sag_decoder=None, lengths=None, frames=None):
     """Re-synthesise the frames [lo, hi) of the timeline main_long made (on the listed joints, or all): only the windows that own a
     frame of the range are sampled, starting from the existing motion -- and with edit['text'] from the SAG decoder's output for one
-    script on the edited elements."""
+    script on the edited elements.  edit['clip'] edits that clip of the batch alone, and lengths / frames (main_long_ragged) edit a
+    ragged batch, every clip inside its own frames: both through the compact form, which runs only the clip-windows it touches."""
     import numpy as np
     lo, hi = edit["frames"]
+    B = timeline.shape[0]
     joints = None
     if edit.get("joints"):
         joints = np.zeros(cfg.njoints, bool)
         joints[edit["joints"]] = True
+    most = np.full(B, timeline.shape[3]) if frames is None else np.asarray(frames)
+    ranges = np.stack([np.minimum(lo, most), np.minimum(hi, most)], axis=1).astype(np.int64)
+    if edit.get("clip") is not None:
+        if not 0 <= edit["clip"] < B:
+            raise SystemExit(f"--edit-clip takes a clip of the batch, 0 .. {B - 1}")
+        ranges[np.arange(B) != edit["clip"]] = 0
+    form = dict(compact=True) if edit.get("clip") is not None or lengths is not None else {}
+    if lengths is not None:
+        form["audio_lengths"] = lengths
     torch.manual_seed(377)
     t0 = time.perf_counter()
-    edited, ran, _ = long_form.edit_long(diffusion, model, timeline, (lo, hi), audio, y["seed_poses"], y["vid_indices"], y["scale"],
-                                         joints=joints, sampler="ddim", skip_timesteps=80, return_windows=True)
+    edited, ran, _ = long_form.edit_long(diffusion, model, timeline, ranges, audio, y["seed_poses"], y["vid_indices"], y["scale"],
+                                         joints=joints, sampler="ddim", skip_timesteps=80, return_windows=True, **form)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     kept = torch.ones_like(timeline, dtype=torch.bool)
-    kept[:, :, :, lo:hi] = False if joints is None else torch.from_numpy(~joints).to(kept.device)[None, :, None, None]
+    for b, (lo_b, hi_b) in enumerate(ranges):
+        kept[b, :, :, lo_b:hi_b] = False if joints is None else torch.from_numpy(~joints).to(kept.device)[:, None, None]
     assert torch.equal(edited[kept], timeline[kept]) and bool(torch.isfinite(edited).all())
     changed = int((edited != timeline).sum())
-    print(f"edit of frames [{lo}, {hi}){'' if joints is None else ' on joints ' + str(edit['joints'])}: {len(ran)} of {W} windows ran "
-          f"({ran}) in {dt * 1e3:.1f} ms; {changed} of {timeline.numel()} values changed, every other one kept bit for bit")
+    what = f"{len(ran)} of {W} windows ran ({ran})"
+    if form:            # the compact form returns its plan: (w, rows)
+        what = f"{sum(len(rows) for _, rows in ran)} clip-windows of {B * W} ran ({', '.join(f'window {w}: clips {rows}' for w, rows in ran)})"
+    print(f"edit of frames [{lo}, {hi}){'' if joints is None else ' on joints ' + str(edit['joints'])}"
+          f"{'' if edit.get('clip') is None else ' of clip ' + str(edit['clip'])}: {what} in {dt * 1e3:.1f} ms; {changed} of {timeline.numel()} "
+          f"values changed, every other one kept bit for bit")
     if not edit.get("text"):
         return
-    B = timeline.shape[0]
     if edit["text"] == "clip":                  # a sentence as clip.tokenize returns it (synthetic tokens) -> CLIPTextEncoder on the GPU
         from livelyspeaker_amd.motionclip import get_clip
         clip_model = get_clip({k: torch.from_numpy(v) for k, v in synth.synth_clip_text_state().items()}, "cuda:0")
@@ -554,8 +577,8 @@ def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit,
         z = torch.from_numpy(synth.make_text_features(B, seed=synth.SEED_COND + 3000)).cuda()
     torch.manual_seed(377)                      # the seed of the unscripted edit: the same draws
     t0 = time.perf_counter()
-    scripted = long_form.edit_long(diffusion, model, timeline, (lo, hi), audio, y["seed_poses"], y["vid_indices"], y["scale"], joints=joints,
-                                   sampler="ddim", skip_timesteps=80, sag=sag_decoder, text_features=z)
+    scripted = long_form.edit_long(diffusion, model, timeline, ranges, audio, y["seed_poses"], y["vid_indices"], y["scale"], joints=joints,
+                                   sampler="ddim", skip_timesteps=80, sag=sag_decoder, text_features=z, **form)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert torch.equal(scripted[kept], timeline[kept]) and bool(torch.isfinite(scripted).all())
@@ -564,7 +587,7 @@ def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit,
           f"{float(moved.mean()):.4f} on average (max {float(moved.max()):.4f}) from the unscripted edit with the same seed")
 
 
-def main_long_ragged(seconds, noise_source, drop_finished=False):
+def main_long_ragged(seconds, noise_source, drop_finished=False, edit=None):
     """One speech per entry of `seconds`, each of its own length, through one sample_long call and one score_timeline call."""
     import numpy as np
     from livelyspeaker_amd import long_form
@@ -593,6 +616,8 @@ def main_long_ragged(seconds, noise_source, drop_finished=False):
               f"{len(scored['motion_beat_times'][b])} motion beats")
     print(f"BC {scored['bc']:.4f} over the batch (synthetic weights and audio: numbers are not quality)")
     assert all(not bool(scored["pose"][b, int(frames[b]):].any()) for b in range(B))
+    if edit is not None:
+        edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit, sag_decoder, lengths, frames)
 
 
 def main_pipelined(B, N):

@@ -389,7 +389,8 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a);
  * editable elements of its result are stored into the timeline and nothing else of the timeline is written.  A window behind the last
  * one that ran is not resampled even where its conditioning frames changed (widen the range to have it resampled), and a clip whose
  * range misses a running window runs in it with every element kept.
- * Not built: handles of ls_long_prepare_ragged, PLMS, const_noise, dump_steps, encoding only the edited windows' audio. */
+ * Not built: PLMS, const_noise, dump_steps; in this dense form also handles of ls_long_prepare_ragged and encoding only the edited
+ * windows' audio -- both are ls_long_prepare_edit / ls_long_edit_compact's, further down. */
 typedef struct ls_long_edit_args {
     int32_t sampler;            /* LS_SAMPLER_DDPM | LS_SAMPLER_DDIM                                                  */
     int32_t noise_mode;         /* LS_NOISE_TAPE | LS_NOISE_PHILOX                                                    */
@@ -438,6 +439,86 @@ int ls_long_edit(ls_handle* h, const ls_long_edit_args* a);
  * any launch, as is everything ls_long_edit refuses.
  * Not built: what ls_long_edit does not build; the SAG encoder as the source of text_features. */
 int ls_long_edit_sag(ls_handle* h, const ls_long_edit_args* a, struct ls_sag* sag, const float* text_features);
+
+/* ---- The COMPACT timeline edit: only the clip-windows an edit touches run, and clips of different lengths are edited in one call.
+ * ls_long_edit runs every clip in every window that runs and needs all W * B clip-windows of audio encoded; here the unit is the PAIR
+ * (clip b, window w).  The pair is in the plan iff clip b has an editable element in window w by ls_long_edit's rule (frame_lo[b] <=
+ * w S + f < frame_hi[b] on a frame that w OWNS, and at least one channel of the clip selected) and, with `frames`, w < W_b = (frames[b]
+ * - T) / S + 1.  Window w runs iff some pair names it; its ROWS are the clips of its pairs in ascending clip order; the windows run
+ * in ascending order.  ls_long_edit_plan_compact is that plan (no handle, no GPU): windows [n_run] and counts [n_run] (the windows
+ * that run and their row counts |A_w|), rows [n_pairs] (the row tables, window after window), *n_windows_run, *n_pairs = sum |A_w|.
+ * A call with windows == counts == NULL (window_capacity 0) and rows == NULL (row_capacity 0) returns the two counts alone.
+ * channels: bytes [batch, n_channels], or NULL = every channel.  frames: [batch] or NULL (every clip has all n_windows windows).
+ * LS_EINVAL: a range outside [0, T + (W - 1) S] -- outside [0, frames[b]] with frames --, lo > hi, a frames[b] that is not T + k S
+ * with 0 <= k < n_windows, a capacity that does not hold the plan.  A plan without a pair is no error here (the entries below refuse
+ * it).  Property: without frames the windows that run are ls_long_edit_plan's for the same ranges.
+ *
+ * ls_long_prepare_edit is the once-per-call stage, everything in the CALLER's clip order (no slots, no reordering).  c as for
+ * ls_long_prepare (c->emo [W, B]); audio_lengths (HOST [B], each in [1, c->audio_samples]) or NULL = every clip holds c->audio_samples
+ * samples.  With audio_lengths, c->n_windows must be the longest clip's window count and frames[b] = T + (W_b - 1) S follows from
+ * audio_lengths[b] as in ls_long_prepare_ragged.  Seed poses, speaker ids, guidance scales and emotion tokens are held per clip at
+ * batch B; the WavEncoder runs over the n_pairs clip-windows of the plan alone, gathered from the caller's waveform through a (clip,
+ * window) table in chunks of c->encoder_chunk (nothing at or beyond a clip's length is read: it counts as zero), its features packed in
+ * plan order.  Every window batch is planned and its workspaces sized here.  An empty plan: LS_EINVAL.
+ *
+ * ls_long_edit_compact runs the planned windows.  Window w is ONE sampling call at batch |A_w| on its rows, decision for decision:
+ * its own step plan, its own single-pass decision (the scales of its rows), the speaker style computed at that batch from its rows'
+ * speaker ids (three small launches; it is not gathered from a batch-B result, because the projection's kernel is chosen by shape
+ * and the contract is the call at batch |A_w|, bit for bit), the inpainting planes cut from the timeline by the row-table forms of
+ * k_edit_gather / k_edit_start / k_edit_scatter.  Arguments:
+ *   - frame_lo / frame_hi / channels must repeat what ls_long_prepare_edit was given (LS_EINVAL otherwise);
+ *   - TAPE: the tapes are packed window after window at batch |A_w| -- x_init [n_pairs, J, F, T], then per window eps [n_exec, 2,
+ *     |A_w|, latent_dim], noise and (inpaint_noised) inpaint_noise [n_exec, |A_w|, J, F, T], each concatenated over the windows that
+ *     run: the packing ls_long_prepare_ragged documents;
+ *   - PHILOX: row r of window w draws EVERY stream at global index sample_offset + rows_w[r] + (w << 48) -- the clip's index, not the
+ *     row's -- so a clip draws what ls_long_edit and ls_long_sample draw for it, whichever other clips run beside it.  The draws come
+ *     from a key table through device tapes (ls_philox_rows.hip), the inpainting branch's re-noise stream included;
+ *   - windows (nullable): [n_pairs, J, F, T] the raw samples, row after row in plan order;
+ *   - windows_run / n_windows_run as in ls_long_edit; *rows_run = n_pairs;
+ *   - sag with text_features [W, B, latent_dim] (clip order): the scripted edit of ls_long_edit_sag; rows of pairs outside the plan
+ *     are not used.  One without the other: LS_EINVAL.
+ *   - ls_timing: n_segments = We (windows that ran), n_step_launches = We * n_exec, graph_replayed = the windows served by a replay.
+ * GRAPH CACHE: one captured loop per (batch size, single-pass form) is kept and replayed by every window and every later call with
+ * that key (the cache holds a few; a key that does not fit runs as stream launches, which give the same bits).  Room is made before
+ * the first window, while nothing is in flight, and no graph is destroyed under a replay.  Every buffer a captured loop holds by
+ * address is sized for the largest window batch before the first capture, so an identical second call replays every window.
+ * Refusals come ahead of any launch and leave the handle usable: a handle not prepared by ls_long_prepare_edit (LS_ESTATE; ls_long_edit
+ * and ls_long_sample refuse such a handle in turn), other ranges or channels than the prepared ones (LS_EINVAL), samplers other than
+ * DDPM / DDIM and noise other than TAPE / PHILOX (LS_EUNSUPPORTED).
+ * Not built: PLMS, const_noise, dump_steps, device-resident lengths, resampling the windows behind the last edited one. */
+typedef struct ls_long_edit_compact_args {
+    int32_t sampler;            /* the fields of ls_long_edit_args, with the same meanings ...                        */
+    int32_t noise_mode;
+    int32_t skip_timesteps;
+    int32_t on_device;
+    int32_t use_graph;
+    int32_t clip_denoised;
+    int32_t two_pass_always;
+    float eta;
+    int32_t inpaint_noised;
+    int32_t windows_capacity;
+    const int32_t* frame_lo;    /* HOST [B]                                                                           */
+    const int32_t* frame_hi;    /* HOST [B]                                                                           */
+    const unsigned char* channels; /* HOST bytes [B, J*F] or NULL                                                     */
+    float* timeline;            /* [B, J, F, T + (W - 1) S], edited in place                                          */
+    float* windows;             /* [n_pairs, J, F, T] or NULL                                                         */
+    int32_t* windows_run;       /* HOST, nullable                                                                     */
+    int32_t* n_windows_run;     /* HOST, nullable: We                                                                 */
+    const float* x_init;        /* TAPE, packed: [n_pairs, J, F, T]                                                   */
+    const float* eps_tape;      /* per window [n_exec, 2, |A_w|, latent_dim], concatenated                            */
+    const float* noise_tape;    /* per window [n_exec, |A_w|, J, F, T], concatenated                                  */
+    const float* inpaint_noise; /* likewise, with inpaint_noised                                                      */
+    uint64_t seed;
+    uint64_t sample_offset;     /* PHILOX: clip b draws, in window w, at sample_offset + b + (w << 48)                */
+    int32_t* rows_run;          /* ... and, HOST, nullable: n_pairs, the clip-windows that ran                        */
+} ls_long_edit_compact_args;
+int ls_long_edit_plan_compact(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const int32_t* lo, const int32_t* hi,
+                              const unsigned char* channels, int32_t n_channels, const int32_t* frames, int32_t* windows,
+                              int32_t* counts, int32_t window_capacity, int32_t* rows, int32_t row_capacity, int32_t* n_windows_run,
+                              int32_t* n_pairs);
+int ls_long_prepare_edit(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths, const int32_t* frame_lo,
+                         const int32_t* frame_hi, const unsigned char* channels);
+int ls_long_edit_compact(ls_handle* h, const ls_long_edit_compact_args* a, struct ls_sag* sag, const float* text_features);
 
 /* ---- Streaming long-form synthesis: the chain of ls_long_sample, fed audio in chunks of any size.  Window w runs as soon as its last
  * sample has arrived (audio_stride * w + audio_len <= samples fed), conditioned on the last n_pre_seq poses of window w - 1 (window 0:

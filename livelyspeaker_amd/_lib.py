@@ -72,6 +72,10 @@ class LsLongEditArgs(C.Structure):
         ("seed", C.c_uint64), ("sample_offset", C.c_uint64)]
 
 
+class LsLongEditCompactArgs(C.Structure):
+    _fields_ = LsLongEditArgs._fields_ + [("rows_run", c_i32p)]
+
+
 class LsLongStreamCond(C.Structure):
     _fields_ = [("batch", C.c_int32), ("on_device", C.c_int32), ("seed_poses", C.c_void_p), ("vid_indices", C.c_void_p), ("scale", C.c_void_p)]
 
@@ -248,7 +252,7 @@ class LsResampleStreamPushArgs(C.Structure):
 
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
-           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_edit_sag", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_long_pool_plan", "ls_long_pool_open", "ls_long_pool_join", "ls_long_pool_push", "ls_long_pool_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
+           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_edit_sag", "ls_long_edit_plan_compact", "ls_long_prepare_edit", "ls_long_edit_compact", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_long_pool_plan", "ls_long_pool_open", "ls_long_pool_join", "ls_long_pool_push", "ls_long_pool_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_set_row_keys", "ls_long_pool_keyed", "ls_long_pool_set_key", "ls_long_pool_keys", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
@@ -331,6 +335,10 @@ def load_library(build_if_missing: bool = True):
     lib.ls_long_edit.argtypes = [C.c_void_p, C.POINTER(LsLongEditArgs)]
     lib.ls_long_edit_sag.argtypes = [C.c_void_p, C.POINTER(LsLongEditArgs), C.c_void_p, C.c_void_p]
     lib.ls_long_edit_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p, c_i32p, c_i32p]
+    lib.ls_long_edit_plan_compact.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p, C.c_void_p, C.c_int32, c_i32p, c_i32p,
+                                              c_i32p, C.c_int32, c_i32p, C.c_int32, c_i32p, c_i32p]
+    lib.ls_long_prepare_edit.argtypes = [C.c_void_p, C.POINTER(LsLongCond), C.c_void_p, c_i32p, c_i32p, C.c_void_p]
+    lib.ls_long_edit_compact.argtypes = [C.c_void_p, C.POINTER(LsLongEditCompactArgs), C.c_void_p, C.c_void_p]
     lib.ls_long_stream_plan.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_i64p, c_i64p]
     lib.ls_long_stream_open.argtypes = [C.c_void_p, C.POINTER(LsLongStreamCond)]
     lib.ls_long_stream_push.argtypes = [C.c_void_p, C.POINTER(LsLongStreamPushArgs)]
@@ -630,6 +638,34 @@ def long_edit_plan(lo, hi, n_windows, n_frames=34, n_pre=4):
         raise ValueError(f"frame ranges must hold one 0 <= lo <= hi <= {int(n_frames) + (W - 1) * (int(n_frames) - int(n_pre))} per clip, "
                          f"got lo {lo.tolist()} hi {hi.tolist()} for {W} windows")
     return [w for w in range(W) if flags[w]]
+
+
+def long_edit_plan_compact(lo, hi, n_windows, channels=None, frames=None, n_frames=34, n_pre=4):
+    """ls_long_edit_plan_compact (no GPU needed): the clip-windows a COMPACT timeline edit runs, as a list of ``(w, rows)`` -- the
+    windows that run, ascending, each with the clips that have an editable element in it, ascending (int32 arrays).  ``channels``: bool /
+    byte [B, C] or None (every channel; a clip without a selected channel is in no window); ``frames``: int [B] or None -- clip b has
+    only the windows its own ``frames[b]`` frames hold.  A range outside its clip's timeline, ``lo > hi`` or a ``frames[b]`` that is no
+    stitched length raises ``ValueError``.  The list is empty when no clip has an editable element."""
+    lib = load_library()
+    lo = np.ascontiguousarray(np.asarray(lo).reshape(-1), dtype=np.int32)
+    hi = np.ascontiguousarray(np.asarray(hi).reshape(-1), dtype=np.int32)
+    B, W = int(lo.size), int(n_windows)
+    ch = None if channels is None else np.ascontiguousarray(np.asarray(channels).reshape(B, -1) != 0, dtype=np.uint8)
+    fr = None if frames is None else np.ascontiguousarray(np.asarray(frames).reshape(-1), dtype=np.int32)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(c_i32p)      # noqa: E731
+    chp, nch = (None, 0) if ch is None else (ch.ctypes.data_as(C.c_void_p), int(ch.shape[1]))
+    nw, npairs = C.c_int32(), C.c_int32()
+    head = (B, W, int(n_frames), int(n_pre), ptr(lo), ptr(hi), chp, nch, ptr(fr))
+    if lo.shape != hi.shape or (fr is not None and fr.shape != lo.shape) or \
+            lib.ls_long_edit_plan_compact(*head, None, None, 0, None, 0, C.byref(nw), C.byref(npairs)) != 0:
+        raise ValueError(f"frame ranges must hold one 0 <= lo <= hi <= frames[b] per clip (frames[b] = 34 + 30 k, at most "
+                         f"{int(n_frames) + (W - 1) * (int(n_frames) - int(n_pre))}), got lo {lo.tolist()} hi {hi.tolist()} frames "
+                         f"{None if fr is None else fr.tolist()} for {W} windows")
+    wins, counts, rows = np.empty(max(nw.value, 1), np.int32), np.empty(max(nw.value, 1), np.int32), np.empty(max(npairs.value, 1), np.int32)
+    if lib.ls_long_edit_plan_compact(*head, ptr(wins), ptr(counts), int(nw.value), ptr(rows), int(npairs.value), C.byref(nw), C.byref(npairs)) != 0:
+        raise EngineError("ls_long_edit_plan_compact failed")
+    offs = np.concatenate([[0], np.cumsum(counts[:nw.value])]).astype(np.int64)
+    return [(int(wins[e]), rows[offs[e]:offs[e + 1]].copy()) for e in range(nw.value)]
 
 
 def long_stream_plan(samples_before, samples_new, audio_len, closing=False):
@@ -1361,6 +1397,87 @@ class Engine(_Handle):
         ran = [int(w) for w in ran[:int(n_ran.value)]]
         assert ran == plan, (ran, plan)
         return (out, ran, windows) if return_windows else (out, ran)
+
+    def long_prepare_edit(self, audio, seed_poses, vid_indices, scale, frame_lo, frame_hi, channels=None, emo=None, n_windows=1,
+                          encoder_chunk=None, audio_lengths=None):
+        """Once-per-call stage of a COMPACT timeline edit (ls_long_prepare_edit): the conditioning of ``long_prepare``, everything in
+        the caller's clip order, plus the edit's ranges (host int [B]) and ``channels`` (host bytes [B, J*F]; None = all).  Only the
+        clip-windows of ``long_edit_plan_compact`` go through the WavEncoder.  ``audio_lengths`` (host [B]): clips of different
+        lengths -- ``n_windows`` is the longest clip's count, a clip has only its own windows, and ``audio`` at and beyond a clip's
+        length is never read.  Sets ``edit_plan``: the list of ``(w, rows)``."""
+        B, W = int(audio.shape[0]), int(n_windows)
+        npre = int(self.cfg.n_pre_seq)
+        lo = np.ascontiguousarray(np.asarray(frame_lo).reshape(-1), dtype=np.int32)
+        hi = np.ascontiguousarray(np.asarray(frame_hi).reshape(-1), dtype=np.int32)
+        assert lo.shape == hi.shape == (B,), (lo.shape, hi.shape, B)
+        ch = None if channels is None else np.ascontiguousarray(np.asarray(channels).reshape(B, self.J * self.F) != 0, dtype=np.uint8)
+        lens = frames = None
+        if audio_lengths is not None:
+            lens = np.ascontiguousarray(np.asarray(audio_lengths).reshape(-1), dtype=np.int64)
+            assert lens.shape == (B,), (lens.shape, B)
+        m = _Marshal(self.device, audio, seed_poses, vid_indices, scale, emo, stream=self._stream)
+        c = LsLongCond(B, W, int(m.on_device), int(encoder_chunk or 0), int(audio.shape[1]), m.f32(audio, (B, int(audio.shape[1]))),
+                       m.f32(seed_poses, (B, self.J, self.F, npre)), m.i64(vid_indices, (B,)), m.i64(emo, (W, B)), m.f32(scale, (B,)))
+        m.ready()
+        self._check(self.lib.ls_long_prepare_edit(self.h, C.byref(c), None if lens is None else lens.ctypes.data_as(C.c_void_p),
+                                                  lo.ctypes.data_as(c_i32p), hi.ctypes.data_as(c_i32p),
+                                                  None if ch is None else ch.ctypes.data_as(C.c_void_p)), "ls_long_prepare_edit")
+        if lens is not None:        # frames per clip: what ls_long_plan_drop's window counts stitch to
+            row, wins, _ = long_plan_drop(lens, self.cfg.audio_len)
+            frames = np.empty(B, np.int32)
+            frames[row] = self.T + (wins - 1) * (self.T - npre)
+        self.edit_plan = long_edit_plan_compact(lo, hi, W, ch, frames, self.T, npre)
+        self.batch, self.n_windows, self.window_batches = B, W, None
+
+    def long_edit_compact(self, timeline, frame_lo, frame_hi, channels=None, sampler=LS_SAMPLER_DDIM, x_init=None, eps_tape=None,
+                          noise_tape=None, inpaint_noise=None, inpaint_noised=False, skip_timesteps=0, eta=0.0, philox_seed=None,
+                          sample_offset=0, use_graph=True, clip_denoised=False, two_pass_always=False, device_out=False, return_windows=False,
+                          sag=None, text_features=None):
+        """The planned clip-windows of the last ``long_prepare_edit`` (ls_long_edit_compact): window w is one sampling call at batch
+        ``len(rows)`` on its rows.  ``frame_lo`` / ``frame_hi`` / ``channels`` repeat the prepared ones.  TAPE mode takes packed
+        tapes, window after window at its own batch: ``x_init`` [n_pairs, J, F, T], flat ``eps_tape`` / ``noise_tape`` /
+        ``inpaint_noise`` holding per window [n_exec, 2, A_w, D] / [n_exec, A_w, J, F, T]; PHILOX mode ``philox_seed`` (clip b of
+        window w draws at ``sample_offset + b + (w << 48)``).  ``sag`` with ``text_features`` [W, B, D] in clip order: the scripted
+        edit.  Returns (a new timeline, the plan ``[(w, rows)]``) and, with ``return_windows``, the raw samples [n_pairs, J, F, T]."""
+        B, W, D = self.batch, self.n_windows, self.D
+        n_frames = self.T + (W - 1) * (self.T - int(self.cfg.n_pre_seq))
+        lo = np.ascontiguousarray(np.asarray(frame_lo).reshape(-1), dtype=np.int32)
+        hi = np.ascontiguousarray(np.asarray(frame_hi).reshape(-1), dtype=np.int32)
+        assert lo.shape == hi.shape == (B,), (lo.shape, hi.shape, B)
+        ch = None if channels is None else np.ascontiguousarray(np.asarray(channels).reshape(B, self.J * self.F) != 0, dtype=np.uint8)
+        plan = getattr(self, "edit_plan", None) or []
+        n_pairs = sum(len(rows) for _, rows in plan)
+        m = self._marshal([timeline, x_init, eps_tape, noise_tape, inpaint_noise, text_features], device_out)
+        a = LsLongEditCompactArgs()
+        n_exec = self._chain_sampler(a, m, sampler, skip_timesteps, use_graph, clip_denoised, two_pass_always, eta)
+        a.inpaint_noised = int(bool(inpaint_noised))
+        a.frame_lo, a.frame_hi = lo.ctypes.data_as(c_i32p), hi.ctypes.data_as(c_i32p)
+        if ch is not None:
+            a.channels = ch.ctypes.data_as(C.c_void_p)
+        self._chain_noise(a, m, n_pairs, n_exec, x_init, eps_tape, noise_tape, philox_seed, sample_offset, packed=True)
+        if philox_seed is None and inpaint_noised:
+            a.inpaint_noise = m.f32(inpaint_noise, (n_pairs * n_exec * self.J * self.F * self.T,))
+        shape = (B, self.J, self.F, n_frames)
+        assert tuple(int(s) for s in timeline.shape) == shape, (tuple(timeline.shape), shape)
+        if m.on_device:         # a copy of the caller's timeline: the engine edits it in place
+            out = m.torch.empty(shape, dtype=m.torch.float32, device=m.dev)
+            out.copy_(m.torch.as_tensor(timeline))
+            a.timeline = C.c_void_p(out.data_ptr())
+        else:
+            out = np.array(timeline.detach().cpu().numpy() if hasattr(timeline, "detach") else timeline, dtype=np.float32, order="C", copy=True)
+            a.timeline = out.ctypes.data_as(C.c_void_p)
+        windows = None
+        if return_windows and n_pairs:
+            windows, a.windows = m.out((n_pairs, self.J, self.F, self.T))
+        ran, n_ran, n_rows = np.full(max(W, 1), -1, np.int32), C.c_int32(0), C.c_int32(0)
+        a.windows_run, a.windows_capacity, a.n_windows_run, a.rows_run = ran.ctypes.data_as(c_i32p), W, C.pointer(n_ran), C.pointer(n_rows)
+        text = m.f32(text_features, (W, B, D))
+        m.ready()
+        self._check(self.lib.ls_long_edit_compact(self.h, C.byref(a), None if sag is None else sag.h, text), "ls_long_edit_compact")
+        ran = [int(w) for w in ran[:int(n_ran.value)]]
+        self.rows_run = int(n_rows.value)          # the clip-windows that ran (ls_long_edit_compact_args.rows_run)
+        assert ran == [w for w, _ in plan] and self.rows_run == n_pairs, (ran, plan, self.rows_run)
+        return (out, plan, windows) if return_windows else (out, plan)
 
     # ---- streaming long-form synthesis -----------------------------------------------------------
     def long_stream_open(self, seed_poses, vid_indices, scale):

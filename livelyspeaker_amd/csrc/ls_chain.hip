@@ -14,6 +14,8 @@
 // the timeline as the loop's inpainting inputs and its editable elements return.  Algorithmic bytes per clip (fp32): gather 15.7 KB TED,
 // 163 KB BEAT (with the init plane); scatter at most 11.0 KB TED, 115 KB BEAT (with the raw window); the terms are spelled out at the kernels.
 // k_edit_start puts the SAG decoder's output under the editable elements of the init plane (ls_long_edit_sag): at most 7.4 KB TED, 77 KB BEAT.
+// The COMPACT edit (ls_long_edit_compact) runs the same three kernels on the rows of a table, one per clip that has an editable element
+// in the window, and k_cond_gather moves those clips' held conditioning into the rows.
 // A streaming SESSION (ls_long_pool_push; ls_long_stream_push: the pool whose slots move together) keeps the hand-off per slot:
 // k_pool_gather and k_pool_scatter (at the end) move one round's active slots -- a window of audio out of each slot's circular ring,
 // its hand-off poses, its held conditioning -- into and out of the compact rows a sampling call at that batch reads.
@@ -74,6 +76,10 @@ hipError_t launch_chain_window(const ChainArgs& a, int B, hipStream_t st) {
 // Stream order makes the next window's gather see this window's scatter.  One workgroup per clip, the tile of k_chain_window (row stride
 // JF | 1); the timeline, the init plane and the raw window are walked along the frame axis, the internal-layout planes along the channels,
 // the seed poses along their n_pre axis (window 0 stages them in n_pre more tile rows).  No atomics: every element has one writer.
+// With a row table (EditArgs::rows; the COMPACT edit, ls_long_edit_compact) workgroup r serves clip rows[r]: the timeline, the ranges,
+// the channel bytes and the seed poses are the clip's, every compact plane is row r's.  One body for both: a null table is the
+// identity, so the dense edit runs the code it always ran, and the rows of a table are distinct clips, so every element keeps one
+// writer.  The table costs 4 bytes per row on top of the bytes below, which hold per ROW as they held per clip.
 // Algorithmic bytes per clip (fp32), k_edit_gather: read T*JF (+ n_pre*JF seed poses in window 0) + JF channel bytes + 8, write 2*T*JF
 // (motion, mask) + n_pre*(KPP + JF) (+ T*JF init plane with skip_timesteps > 0): 15.7 KB TED, 163 KB BEAT with the init plane.
 // k_edit_scatter: read T*JF + JF bytes + 8, write the editable elements (at most (T - n_pre)*JF, window 0: T*JF) (+ T*JF raw window): at
@@ -85,9 +91,10 @@ __device__ __forceinline__ bool edit_editable(const EditArgs& a, int lo, int hi,
 
 __global__ __launch_bounds__(256) void k_edit_gather(const EditArgs a) {
     extern __shared__ float tile[];                 // [T (+ n_pre in window 0)][JF | 1]
-    const int b = blockIdx.x, tid = threadIdx.x, JF = a.JF, T = a.T, ld = JF | 1, npre = a.n_pre;
+    const int r = blockIdx.x, tid = threadIdx.x, JF = a.JF, T = a.T, ld = JF | 1, npre = a.n_pre;
+    const int b = a.rows ? a.rows[r] : r;           // the clip behind row r (a uniform load; the dense edit: the row itself)
     const float* tl = a.timeline + (size_t)b * JF * a.T_total + a.w * (T - npre);
-    float* init = a.init ? a.init + (size_t)b * JF * T : nullptr;
+    float* init = a.init ? a.init + (size_t)r * JF * T : nullptr;
     for (int i = tid; i < JF * T; i += 256) {
         const int c = i / T, f = i - c * T;
         const float v = tl[(size_t)c * a.T_total + f];
@@ -104,19 +111,19 @@ __global__ __launch_bounds__(256) void k_edit_gather(const EditArgs a) {
     __syncthreads();
     const int lo = a.range[2 * b], hi = a.range[2 * b + 1];
     const unsigned char* ch = a.chan + (size_t)b * JF;
-    float* mo = a.motion + (size_t)b * T * JF;
-    float* mk = a.maskf + (size_t)b * T * JF;
+    float* mo = a.motion + (size_t)r * T * JF;
+    float* mk = a.maskf + (size_t)r * T * JF;
     for (int i = tid; i < T * JF; i += 256) {
         const int f = i / JF, c = i - f * JF;
         mo[i] = tile[f * ld + c];
         mk[i] = edit_editable(a, lo, hi, ch[c] != 0, f) ? 0.f : 1.f;      // inpainting_mask: true = keep the given motion
     }
-    float* fu = a.feat_u + (size_t)b * T * a.KPP;
+    float* fu = a.feat_u + (size_t)r * T * a.KPP;
     for (int i = tid; i < npre * a.KPP; i += 256) {
         const int j = i / a.KPP, c = i - j * a.KPP;
         fu[i] = c < JF ? pre[j * ld + c] : c == JF ? 1.f : 0.f;
     }
-    float* ox = a.origin_x + (size_t)b * JF * T;
+    float* ox = a.origin_x + (size_t)r * JF * T;
     for (int i = tid; i < JF * npre; i += 256) {
         const int c = i / npre, j = i - c * npre;
         ox[(size_t)c * T + j] = pre[j * ld + c];
@@ -125,14 +132,15 @@ __global__ __launch_bounds__(256) void k_edit_gather(const EditArgs a) {
 
 __global__ __launch_bounds__(256) void k_edit_scatter(const EditArgs a) {
     extern __shared__ float tile[];                 // [T][JF | 1]
-    const int b = blockIdx.x, tid = threadIdx.x, JF = a.JF, T = a.T, ld = JF | 1;
-    const float* src = a.sample + (size_t)b * T * JF;
+    const int r = blockIdx.x, tid = threadIdx.x, JF = a.JF, T = a.T, ld = JF | 1;
+    const int b = a.rows ? a.rows[r] : r;
+    const float* src = a.sample + (size_t)r * T * JF;
     for (int i = tid; i < T * JF; i += 256) tile[(i / JF) * ld + i % JF] = src[i];
     __syncthreads();
     const int lo = a.range[2 * b], hi = a.range[2 * b + 1];
     const unsigned char* ch = a.chan + (size_t)b * JF;
     float* tl = a.timeline + (size_t)b * JF * a.T_total + a.w * (T - a.n_pre);
-    float* wd = a.window ? a.window + (size_t)b * JF * T : nullptr;
+    float* wd = a.window ? a.window + (size_t)r * JF * T : nullptr;
     for (int i = tid; i < JF * T; i += 256) {
         const int c = i / T, f = i - c * T;
         const float v = tile[f * ld + c];
@@ -147,11 +155,12 @@ __global__ __launch_bounds__(256) void k_edit_scatter(const EditArgs a) {
 // Algorithmic bytes per clip (fp32): read and write the editable elements (at most (T - n_pre)*JF each, window 0: T*JF) + JF channel
 // bytes + 8: at most 7.4 KB TED, 77 KB BEAT.
 __global__ __launch_bounds__(256) void k_edit_start(const EditArgs a, const float* __restrict__ sag_out) {
-    const int b = blockIdx.x, tid = threadIdx.x, JF = a.JF, T = a.T;
+    const int r = blockIdx.x, tid = threadIdx.x, JF = a.JF, T = a.T;
+    const int b = a.rows ? a.rows[r] : r;
     const int lo = a.range[2 * b], hi = a.range[2 * b + 1];
     const unsigned char* ch = a.chan + (size_t)b * JF;
-    const float* src = sag_out + (size_t)b * JF * T;
-    float* init = a.init + (size_t)b * JF * T;
+    const float* src = sag_out + (size_t)r * JF * T;
+    float* init = a.init + (size_t)r * JF * T;
     for (int i = tid; i < JF * T; i += 256) {
         const int c = i / T, f = i - c * T;
         if (edit_editable(a, lo, hi, ch[c] != 0, f)) init[i] = src[i];
@@ -250,6 +259,20 @@ __device__ __forceinline__ void gather_ring_window(const float* __restrict__ src
     *reinterpret_cast<float4*>(dst + i) = v;
 }
 
+// The held conditioning of source row `from` (a session's slot, a compact edit's clip) into compact row r: speaker id and guidance
+// scale by thread 0, the emotion token and the text features as float4 by 128 threads each (512-float rows: every row starts
+// 2 KB-aligned).  emo_tok / text null: that row is not moved.  256 threads.
+__device__ __forceinline__ void gather_cond_row(int r, int from, const int64_t* __restrict__ vid_s, const float* __restrict__ scale_s,
+                                                const float* __restrict__ emo_tok_s, const float* __restrict__ text_s, int64_t* __restrict__ vid,
+                                                float* __restrict__ scale, float* __restrict__ emo_tok, float* __restrict__ text) {
+    const int tid = threadIdx.x;
+    if (tid == 0) { vid[r] = vid_s[from]; scale[r] = scale_s[from]; }
+    if (emo_tok && tid < kD / 4)
+        reinterpret_cast<float4*>(emo_tok + (size_t)r * kD)[tid] = reinterpret_cast<const float4*>(emo_tok_s + (size_t)from * kD)[tid];
+    if (text && tid >= 128 && tid < 128 + kD / 4)
+        reinterpret_cast<float4*>(text + (size_t)r * kD)[tid - 128] = reinterpret_cast<const float4*>(text_s + (size_t)from * kD)[tid - 128];
+}
+
 // One round of a streaming SESSION (ls_long_pool_push, ls_long_stream_push; PoolArgs in ls_internal.h): the A active slots of the round,
 // in ascending slot order, become the rows 0 .. A-1 of every buffer a sampling call at batch A reads.  Workgroup (x, r) reads its table
 // row once (a uniform load; no other load depends on a loaded value) and, for x below the audio workgroups, is gather_ring_window on
@@ -278,11 +301,14 @@ __global__ __launch_bounds__(256) void k_pool_gather(const PoolArgs a) {
         const int c = i / npre, j = i - c * npre;
         ox[(size_t)c * T + j] = hand[i];
     }
-    if (tid == 0) { a.vid[r] = a.vid_s[slot]; a.scale[r] = a.scale_s[slot]; }
-    if (a.emo_tok && tid < kD / 4)
-        reinterpret_cast<float4*>(a.emo_tok + (size_t)r * kD)[tid] = reinterpret_cast<const float4*>(a.emo_tok_s + (size_t)slot * kD)[tid];
-    if (a.text && tid >= 128 && tid < 128 + kD / 4)
-        reinterpret_cast<float4*>(a.text + (size_t)r * kD)[tid - 128] = reinterpret_cast<const float4*>(a.text_s + (size_t)slot * kD)[tid - 128];
+    gather_cond_row(r, slot, a.vid_s, a.scale_s, a.emo_tok_s, a.text_s, a.vid, a.scale, a.emo_tok, a.text);
+}
+
+// One window of a COMPACT timeline edit (ls_long_edit_compact): the held conditioning of clip rows[r] into compact row r, one
+// workgroup per row -- gather_cond_row with clips in place of slots.  Bytes per row: 4 (table) + 12 + 2 KB per 512-float row moved.
+__global__ __launch_bounds__(256) void k_cond_gather(const CondGatherArgs a) {
+    const int r = blockIdx.x;
+    gather_cond_row(r, a.rows[r], a.vid_c, a.scale_c, a.emo_tok_c, a.text_c, a.vid, a.scale, a.emo_tok, a.text);
 }
 
 // ... and the way back: one workgroup per row, k_chain_window's tile (row stride JF | 1: the transposed reads touch every bank once).
@@ -320,6 +346,13 @@ hipError_t launch_pool_gather(const PoolArgs& a, int A, hipStream_t st) {
         (a.text && (!a.text_s || (((size_t)a.text | (size_t)a.text_s) & 15)))) return hipErrorInvalidValue;
     const int gx = (a.AL / 4 + 255) / 256;           // >= the float4 groups of a clip, whatever its head
     hipLaunchKernelGGL(k_pool_gather, dim3((gx > 0 ? gx : 1) + 1, A), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_cond_gather(const CondGatherArgs& a, int A, hipStream_t st) {
+    if (A < 1 || A > 65535 || !a.rows || !a.vid_c || !a.scale_c || !a.vid || !a.scale) return hipErrorInvalidValue;
+    if ((a.emo_tok && (!a.emo_tok_c || (((size_t)a.emo_tok | (size_t)a.emo_tok_c) & 15))) ||
+        (a.text && (!a.text_c || (((size_t)a.text | (size_t)a.text_c) & 15)))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_cond_gather, dim3(A), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 hipError_t launch_pool_scatter(const PoolArgs& a, int A, hipStream_t st) {

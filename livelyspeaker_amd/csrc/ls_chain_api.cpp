@@ -5,7 +5,8 @@
 // per window -> chain_finish); the entries hold what differs: where a window's audio features come from (all windows encoded ahead,
 // packed for clips of different lengths, or one round at a time from the rings of a streaming session's active slots) and what stands
 // around a window (k_chain_window ahead of it, k_edit_gather / k_edit_scatter -- with k_edit_start behind the decoder of a scripted
-// edit -- or k_pool_gather / k_pool_scatter).  There is one
+// edit; the compact edit runs them on a row table, one row per clip the window touches, behind k_cond_gather -- or k_pool_gather /
+// k_pool_scatter).  There is one
 // streaming session (session_open -> session_push -> session_push_run): a pool of slots that join and leave, and a stream, which is
 // the pool whose slots were all joined at the open and are fed, given and closed alike.  The host-only plans are ls_chain_plan.cpp.
 #include "ls_handle.h"
@@ -35,7 +36,7 @@ int check_cond(ls_handle* h, const char* entry, int batch, const int32_t* n_wind
 
 // the handle's prepared conditioning is replaced from here on; the stage's clock starts
 int start_prepare(ls_handle* h) {
-    h->prepared = h->lg_prepared = h->lg_ragged = false;
+    h->prepared = h->lg_prepared = h->lg_ragged = h->lg_compact = false;
     h->seg_next = -1;
     HIPCHK(h, hipEventRecord(h->ev[4], h->stream));
     return LS_OK;
@@ -878,6 +879,270 @@ int ls_long_edit_sag(ls_handle* h, const ls_long_edit_args* a, ls_sag* sag, cons
 }
 
 int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) { return ls_long_edit_sag(h, a, nullptr, nullptr); }
+
+// Once-per-call stage of a COMPACT timeline edit (ls_hip.h): the plan of ls_long_edit_plan_compact from the ranges, the channels and
+// (audio_lengths) the clips' own window counts; the per-clip conditioning held at batch B in the caller's order; the WavEncoder over
+// the plan's clip-windows alone, gathered by k_long_gather_clips from a (clip, window) table and stored packed in plan order; every
+// window batch planned under the single-pass decision of its own rows and its workspaces sized, so that nothing a captured loop holds
+// by address moves once ls_long_edit_compact has begun.  The speaker style is ls_long_edit_compact's (per window batch).
+int ls_long_prepare_edit(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths, const int32_t* frame_lo, const int32_t* frame_hi,
+                         const unsigned char* channels) {
+    if (!h || !c || !frame_lo || !frame_hi) return fail(h, LS_EINVAL, "ls_long_prepare_edit: null argument");
+    int rc;
+    if ((rc = check_cond(h, "ls_long_prepare_edit", c->batch, &c->n_windows, c->audio_samples >= 1 && c->encoder_chunk >= 0,
+                         c->audio && c->seed_poses && c->vid_indices && c->scale, h->cfg.n_prefix_tokens != 2 || c->emo)) != LS_OK) return rc;
+    if (c->audio_samples > 0x7fffffffLL) return fail(h, LS_EINVAL, "ls_long_prepare_edit: audio_samples beyond 2^31 - 1");
+    const int B = c->batch, W = c->n_windows, JF = h->JF, T = h->T, AL = h->cfg.audio_len, KPP = h->KPP, npre = h->cfg.n_pre_seq, od = c->on_device;
+    std::vector<int> lens((size_t)B, (int)c->audio_samples);
+    std::vector<int32_t> frames;
+    if (audio_lengths) {
+        for (int b = 0; b < B; ++b)
+            if (audio_lengths[b] < 1 || audio_lengths[b] > c->audio_samples)
+                return fail(h, LS_EINVAL, "audio_lengths[%d] = %lld outside [1, %lld]", b, (long long)audio_lengths[b], (long long)c->audio_samples);
+        std::vector<int> row, wins, bw;
+        long_plan_drop(B, AL, audio_lengths, row, wins, bw);
+        if ((int)bw.size() != W) return fail(h, LS_EINVAL, "n_windows is %d, the longest clip needs %d", W, (int)bw.size());
+        frames.resize((size_t)B);
+        for (int s = 0; s < B; ++s) frames[(size_t)row[(size_t)s]] = T + (wins[(size_t)s] - 1) * (T - npre);
+        for (int b = 0; b < B; ++b) lens[(size_t)b] = (int)audio_lengths[b];
+    }
+    std::vector<unsigned char> chan;
+    if (channels) { chan.resize((size_t)B * JF); for (size_t i = 0; i < chan.size(); ++i) chan[i] = channels[i] ? 1 : 0; }
+    const int32_t* fr = audio_lengths ? frames.data() : nullptr;
+    const unsigned char* ch = channels ? chan.data() : nullptr;
+    int32_t We = 0, np = 0;
+    if (ls_long_edit_plan_compact(B, W, T, npre, frame_lo, frame_hi, ch, JF, fr, nullptr, nullptr, 0, nullptr, 0, &We, &np) != LS_OK)
+        return fail(h, LS_EINVAL, "ls_long_prepare_edit: a frame range is no range inside its clip's timeline (0 <= lo <= hi <= %s)", audio_lengths ? "frames[b]" : "T_total");
+    if (np < 1) return fail(h, LS_EINVAL, "ls_long_prepare_edit: no window holds an editable element (every range is empty)");
+    std::vector<int32_t> cw((size_t)We), cn((size_t)We), crows((size_t)np), coff((size_t)We + 1, 0);
+    if (ls_long_edit_plan_compact(B, W, T, npre, frame_lo, frame_hi, ch, JF, fr, cw.data(), cn.data(), We, crows.data(), np, &We, &np) != LS_OK)
+        return fail(h, LS_EINVAL, "ls_long_prepare_edit: ls_long_edit_plan_compact failed");
+    for (int e = 0; e < We; ++e) coff[(size_t)e + 1] = coff[(size_t)e] + cn[(size_t)e];
+    std::vector<int> table((size_t)np * 2);
+    for (int e = 0, p = 0; e < We; ++e)
+        for (int r = 0; r < cn[(size_t)e]; ++r, ++p) { table[(size_t)2 * p] = crows[(size_t)p]; table[(size_t)2 * p + 1] = cw[(size_t)e]; }
+    // the editable test of the kernels: a clip without a selected channel is not edited
+    std::vector<int32_t> range((size_t)2 * B);
+    std::vector<unsigned char> chan_dev((size_t)B * JF, 1);
+    for (int b = 0; b < B; ++b) {
+        range[(size_t)2 * b] = frame_lo[b]; range[(size_t)2 * b + 1] = frame_hi[b];
+        if (channels) memcpy(&chan_dev[(size_t)b * JF], &chan[(size_t)b * JF], (size_t)JF);
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int chunk = c->encoder_chunk > 0 ? c->encoder_chunk : 256;
+    if (chunk > 32768) chunk = 32768;                   // one grid row per clip-window of a chunk
+    hipStream_t st = h->stream;
+    end_stream(h);
+    if ((rc = start_prepare(h)) != LS_OK) return rc;
+    // a device-resident waveform is read in place (the call waits before it returns); a host one is uploaded as it is, unpadded
+    const float* audio = c->audio;
+    if (!od) {
+        if ((rc = ingest(h, h->lg_audio, c->audio, (size_t)B * (size_t)c->audio_samples * sizeof(float), 0)) != LS_OK) return rc;
+        audio = h->lg_audio.f();
+    }
+    if ((rc = ingest_cond(h, B, od, c->seed_poses, c->vid_indices, c->scale, c->emo, (size_t)W * B)) != LS_OK) return rc;
+    // the per-clip stores: h->vid / h->scale are the rows of the window in flight from here on (k_cond_gather)
+    if ((rc = ingest(h, h->lg_cvid, h->vid.p, (size_t)B * sizeof(int64_t), 1)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->lg_cscale_dev, h->scale.p, (size_t)B * sizeof(float), 1)) != LS_OK) return rc;
+    std::vector<float> sc((size_t)B);
+    if (od) HIPCHK(h, hipMemcpyAsync(sc.data(), h->lg_cscale_dev.p, (size_t)B * sizeof(float), hipMemcpyDeviceToHost, st));
+    else memcpy(sc.data(), c->scale, (size_t)B * sizeof(float));
+    if ((rc = ingest(h, h->lg_lens, lens.data(), (size_t)B * sizeof(int), 0)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->lg_crows_dev, crows.data(), (size_t)np * sizeof(int32_t), 0)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->lg_edit_range, range.data(), range.size() * sizeof(int32_t), 0)) != LS_OK) return rc;
+    if ((rc = ingest(h, h->lg_edit_chan, chan_dev.data(), chan_dev.size(), 0)) != LS_OK) return rc;
+    if ((rc = upload(h, h->lg_table, table.data(), table.size() * sizeof(int))) != LS_OK) return rc;      // waits: host inputs and these temporaries are free again
+    // ---- WavEncoder over the plan's clip-windows, `chunk` at a time
+    const int nmax = chunk < np ? chunk : np;
+    HIPCHK(h, h->lg_clips.ensure((size_t)nmax * AL * sizeof(float)));
+    HIPCHK(h, h->lg_featc.ensure((size_t)np * T * kAudioFeat * sizeof(float)));
+    HIPCHK(h, h->lg_featp.ensure((size_t)nmax * T * KPP * sizeof(float)));
+    if ((rc = zero_origin_x(h, B)) != LS_OK) return rc;
+    for (int p0 = 0; p0 < np; p0 += chunk) {
+        const int n = np - p0 < chunk ? np - p0 : chunk;
+        HIPCHK(h, launch_long_gather_clips(audio, static_cast<const int*>(h->lg_table.p) + (size_t)2 * p0, static_cast<const int*>(h->lg_lens.p), h->lg_clips.f(), n, AL,
+                                           (long long)c->audio_samples, LS_LONG_AUDIO_STRIDE, st));
+        if ((rc = run_wav_encoder(h, h->lg_clips.f(), n)) != LS_OK) return rc;
+        HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f() + (size_t)p0 * T * kAudioFeat, n, JF, KPP, 0, st, T));
+    }
+    // ---- per-batch stages at batch B: the buffers, the style buffers' room, the emotion tokens of every (window, clip)
+    if ((rc = size_batch_buffers(h, B)) != LS_OK) return rc;
+    if ((rc = prepare_style(h, B)) != LS_OK) return rc;          // sizes z .. z_std for B rows (a window's own style overwrites its rows)
+    if (h->cfg.n_prefix_tokens == 2) {
+        HIPCHK(h, h->lg_emotok.ensure((size_t)W * B * kD * sizeof(float)));
+        HIPCHK(h, launch_gather_rows(h->emo_emb.f(), static_cast<const int64_t*>(h->lg_emo_ids.p), h->lg_emotok.f(), W * B, kD, h->cfg.n_emotions, st));
+    }
+    // ---- the plan and the workspaces of every window batch under its own rows' scales; the handle is left planned for the whole batch
+    bool all_ones = true;
+    for (float v : sc) all_ones = all_ones && v == 1.0f;
+    for (int e = 0; e < We; ++e) {
+        bool ones = true;
+        for (int r = 0; r < cn[(size_t)e]; ++r) ones = ones && sc[(size_t)crows[(size_t)coff[(size_t)e] + r]] == 1.0f;
+        h->all_scale_one = ones;
+        set_plan(h, cn[(size_t)e]);
+        if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+    }
+    h->all_scale_one = all_ones;
+    set_plan(h, B);
+    if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+    if ((rc = finish_prepare(h, B)) != LS_OK) return rc;
+    h->lg_W = W; h->lg_L = (size_t)c->audio_samples;
+    h->lg_cw = cw; h->lg_cn = cn; h->lg_coff = coff; h->lg_crows = crows; h->lg_cscale = sc;
+    h->lg_clo.assign(frame_lo, frame_lo + B); h->lg_chi.assign(frame_hi, frame_hi + B); h->lg_cchan = chan;
+    h->lg_compact = true;       // lg_prepared stays false: ls_long_sample and ls_long_edit need the features of all W * B clip-windows
+    return LS_OK;
+}
+
+// The compact timeline edit (ls_long_edit_compact_args in ls_hip.h): per planned window k_cond_gather, the style at the window's
+// batch, k_edit_gather on the window's row table, the window body (keyed PHILOX rows: the clip's index, not the row's), k_edit_scatter.
+// One wait at the end.
+int ls_long_edit_compact(ls_handle* h, const ls_long_edit_compact_args* a, ls_sag* sag, const float* text_features) {
+    if (!h || !a) return fail(h, LS_EINVAL, "ls_long_edit_compact: null argument");
+    if (sag && !text_features) return fail(h, LS_EINVAL, "ls_long_edit_compact: sag without text_features");
+    if (text_features && !sag) return fail(h, LS_EINVAL, "ls_long_edit_compact: text_features without sag");
+    if (!h->lg_compact) return fail(h, LS_ESTATE, "ls_long_edit_compact before ls_long_prepare_edit");
+    if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_edit_compact before ls_set_schedule");
+    if (!a->timeline) return fail(h, LS_EINVAL, "ls_long_edit_compact: null timeline");
+    if (!a->frame_lo || !a->frame_hi) return fail(h, LS_EINVAL, "ls_long_edit_compact: null frame_lo / frame_hi");
+    if (a->windows_capacity < 0 || (a->windows_capacity > 0 && !a->windows_run)) return fail(h, LS_EINVAL, "ls_long_edit_compact: windows_capacity without windows_run");
+    const int B = h->B, W = h->lg_W, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, od = a->on_device;
+    const int Tt = T + (W - 1) * (T - npre), We = (int)h->lg_cw.size(), np = h->lg_coff[(size_t)We];
+    if ((int)h->lg_clo.size() != B || !std::equal(h->lg_clo.begin(), h->lg_clo.end(), a->frame_lo) || !std::equal(h->lg_chi.begin(), h->lg_chi.end(), a->frame_hi))
+        return fail(h, LS_EINVAL, "ls_long_edit_compact: the frame ranges differ from the ones ls_long_prepare_edit planned");
+    if ((a->channels != nullptr) != !h->lg_cchan.empty())
+        return fail(h, LS_EINVAL, "ls_long_edit_compact: the channels differ from the ones ls_long_prepare_edit planned");
+    for (size_t i = 0; i < h->lg_cchan.size(); ++i)
+        if ((a->channels[i] != 0) != (h->lg_cchan[i] != 0)) return fail(h, LS_EINVAL, "ls_long_edit_compact: the channels differ from the ones ls_long_prepare_edit planned");
+    ChainCall cc;
+    int rc;
+    if ((rc = chain_args(h, "ls_long_edit_compact", a, true, cc)) != LS_OK) return rc;
+    const bool noised = a->inpaint_noised != 0, beat = h->cfg.n_prefix_tokens == 2;
+    if (cc.tape && noised && !a->inpaint_noise) return fail(h, LS_EINVAL, "TAPE mode with inpaint_noised needs inpaint_noise");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = chain_begin(h, cc, sag)) != LS_OK) return rc;
+    hipStream_t st = h->stream;
+    const int n_exec = cc.n_exec;
+    int Amax = 0;
+    for (int n : h->lg_cn) Amax = n > Amax ? n : Amax;
+    const size_t per_x = (size_t)JF * T, per_e = (size_t)n_exec * 2 * kD, per_n = (size_t)n_exec * per_x;     // floats per clip-window: x_T, eps tape, noise tape
+    const size_t nxA = (size_t)Amax * per_x * sizeof(float);
+    const float *xs = a->x_init, *es = a->eps_tape, *ns = a->noise_tape, *iz = noised ? a->inpaint_noise : nullptr;
+    if (cc.tape && !od) {
+        if ((rc = ingest(h, h->lg_x, xs, np * per_x * sizeof(float), 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, np * per_e * sizeof(float), 0)) != LS_OK ||
+            (rc = ingest(h, h->lg_nz, ns, np * per_n * sizeof(float), 0)) != LS_OK) return rc;
+        xs = h->lg_x.f(); es = h->lg_eps.f(); ns = h->lg_nz.f();
+        if (iz) { if ((rc = ingest(h, h->lg_inz, iz, np * per_n * sizeof(float), 0)) != LS_OK) return rc; iz = h->lg_inz.f(); }
+    }
+    const float* tx = text_features;        // host text features: one upload per call, as in ls_long_edit_sag
+    if (sag && !od) { if ((rc = ingest(h, h->lg_text, tx, (size_t)W * B * kD * sizeof(float), 0)) != LS_OK) return rc; tx = h->lg_text.f(); }
+    float* tl = a->timeline;
+    float* wd = a->windows;
+    if (!od) {
+        if ((rc = ingest(h, h->lg_timeline, a->timeline, (size_t)B * JF * Tt * sizeof(float), 0)) != LS_OK) return rc;
+        tl = h->lg_timeline.f();
+        if (wd) { HIPCHK(h, h->lg_windows.ensure(np * per_x * sizeof(float))); wd = h->lg_windows.f(); }
+    }
+    const bool from_image = a->skip_timesteps > 0 || sag;
+    if (from_image) HIPCHK(h, h->lg_init.ensure(nxA));
+    if (sag) { HIPCHK(h, h->lg_sag.ensure(nxA)); HIPCHK(h, h->lg_ctext.ensure((size_t)B * kD * sizeof(float))); cc.sag_out = h->lg_sag.f(); }
+    // Everything a captured loop holds by address, for the largest window batch, before the first window: the x planes, the inpainting
+    // planes, the denoiser's output, the tape buffers or the keyed ring.  Nothing is in flight yet, so a buffer that moves may drop
+    // the cached graphs here; none moves from the first window on, and none at all in an identical second call.
+    HIPCHK(h, h->xtmp.ensure(nxA)); HIPCHK(h, h->xio.ensure(nxA));      // begin_loop's staging planes: grown now, not under a window in flight
+    if ((rc = ensure_pinned(h, h->xa, nxA)) != LS_OK || (rc = ensure_pinned(h, h->xb, nxA)) != LS_OK || (rc = ensure_pinned(h, h->fwd_cfg, nxA)) != LS_OK ||
+        (rc = ensure_pinned(h, h->inp_maskf, nxA)) != LS_OK || (rc = ensure_pinned(h, h->inp_motion, nxA)) != LS_OK) return rc;
+    if (cc.tape) {
+        if ((rc = ensure_pinned(h, h->eps_tape, (size_t)Amax * per_e * sizeof(float))) != LS_OK || (rc = ensure_pinned(h, h->noise_tape, (size_t)Amax * per_n * sizeof(float))) != LS_OK) return rc;
+        if (iz && (rc = ensure_pinned(h, h->inp_tape, (size_t)Amax * per_n * sizeof(float))) != LS_OK) return rc;
+    } else if ((rc = size_key_ring(h, Amax, n_exec, noised)) != LS_OK) return rc;
+    // room in the graph cache for this plan's window batches (one loop per batch size and form), made now; the same batches as the
+    // last compact call: its graphs are this call's
+    {
+        std::vector<int> sizes(h->lg_cn.begin(), h->lg_cn.end());
+        std::sort(sizes.begin(), sizes.end());
+        sizes.erase(std::unique(sizes.begin(), sizes.end()), sizes.end());
+        sizes.push_back(-1);                            // never a ragged ls_long_sample's batches
+        if (h->graphs_for != sizes) {
+            const int want = (int)sizes.size() - 1 < ls_handle::kGraphCacheMax ? (int)sizes.size() - 1 : ls_handle::kGraphCacheMax;
+            if ((int)h->graphs.size() + want > ls_handle::kGraphCacheMax) free_graph(h);
+            h->graphs_for = sizes;
+        }
+    }
+    // PHILOX: the key of every row of every window, in plan order; a window's rows go to row_gidx ahead of its loop (pageable memory,
+    // taken into the runtime's staging memory before the copy call returns, as call_host is)
+    std::vector<uint64_t> keys;
+    if (!cc.tape) {
+        keys.resize((size_t)np);
+        for (int e = 0; e < We; ++e)
+            for (int r = h->lg_coff[(size_t)e]; r < h->lg_coff[(size_t)e + 1]; ++r)
+                keys[(size_t)r] = a->sample_offset + (uint64_t)h->lg_crows[(size_t)r] + ((uint64_t)h->lg_cw[(size_t)e] << 48);
+    }
+    EditArgs ea{};
+    ea.timeline = tl; ea.seed = h->lg_seed.f();
+    ea.range = static_cast<const int*>(h->lg_edit_range.p); ea.chan = static_cast<const unsigned char*>(h->lg_edit_chan.p);
+    ea.feat_u = h->feat_u.f(); ea.origin_x = h->origin_x.f(); ea.init = from_image ? h->lg_init.f() : nullptr;
+    ea.motion = h->inp_motion.f(); ea.maskf = h->inp_maskf.f();
+    ea.JF = JF; ea.T = T; ea.KPP = h->KPP; ea.n_pre = npre; ea.T_total = Tt;
+    cc.wa.init_image = ea.init;
+    cc.wa.inpaint_noised = noised ? 1 : 0;
+    CondGatherArgs ga{};
+    ga.vid_c = static_cast<const int64_t*>(h->lg_cvid.p); ga.scale_c = h->lg_cscale_dev.f();
+    ga.vid = static_cast<int64_t*>(h->vid.p); ga.scale = h->scale.f();
+    const int32_t* styled = nullptr;        // the rows the style buffers hold: a window with the rows of the one before it keeps them
+    int styled_n = 0;
+    // however the windows end, the handle is left as ls_long_prepare_edit left it: planned for the whole batch (its workspaces exist)
+    struct WholeBatch {
+        ls_handle* h; int B;
+        void restore() const {
+            h->B = B;
+            h->all_scale_one = true;
+            for (float v : h->lg_cscale) h->all_scale_one = h->all_scale_one && v == 1.0f;
+            set_plan(h, B);
+        }
+        ~WholeBatch() { restore(); }
+    } whole{h, B};
+    for (int e = 0; e < We; ++e) {
+        const int w = h->lg_cw[(size_t)e], A = h->lg_cn[(size_t)e];
+        const size_t off = (size_t)h->lg_coff[(size_t)e];
+        const int32_t* rows = h->lg_crows.data() + off;
+        const int* rows_dev = static_cast<const int*>(h->lg_crows_dev.p) + off;
+        // from here on the handle is prepared for a batch of A: its rows' scales decide the single-pass form, its size the step plan
+        bool ones = true;
+        for (int r = 0; r < A; ++r) ones = ones && h->lg_cscale[(size_t)rows[r]] == 1.0f;
+        h->B = A;
+        h->all_scale_one = ones;
+        set_plan(h, A);
+        if ((rc = plan_workspaces(h)) != LS_OK) return rc;
+        ga.rows = rows_dev;
+        if (beat) { ga.emo_tok_c = h->lg_emotok.f() + (size_t)w * B * kD; ga.emo_tok = h->emo_tok.f(); }
+        if (sag) { ga.text_c = tx + (size_t)w * B * kD; ga.text = h->lg_ctext.f(); }
+        HIPCHK(h, launch_cond_gather(ga, A, st));
+        if (styled_n != A || !std::equal(rows, rows + A, styled)) {
+            if ((rc = prepare_style(h, A)) != LS_OK) return rc;
+            styled = rows; styled_n = A;
+        }
+        ea.w = w; ea.rows = rows_dev;
+        HIPCHK(h, launch_edit_gather(ea, A, st));
+        if (!cc.tape) HIPCHK(h, hipMemcpyAsync(h->row_gidx.p, keys.data() + off, (size_t)A * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        Window win;
+        win.w = w; win.Bw = A; win.first = e == 0; win.resident_inpaint = true; win.policy = kKeep; win.keyed = !cc.tape;
+        win.featc = h->lg_featc.f() + off * T * kAudioFeat;
+        if (sag) { win.text = h->lg_ctext.f(); win.edit_start = &ea; }
+        if (cc.tape) {
+            win.x_init = xs + off * per_x; win.eps_tape = es + off * per_e; win.noise_tape = ns + off * per_n;
+            win.inpaint_noise = iz ? iz + off * per_n : nullptr;
+        }
+        if ((rc = run_window(h, cc, win)) != LS_OK) return rc;
+        ea.sample = x_plane(h, n_exec); ea.window = wd ? wd + off * per_x : nullptr;
+        HIPCHK(h, launch_edit_scatter(ea, A, st));
+    }
+    whole.restore();
+    if ((rc = chain_finish(h, cc, {{od ? nullptr : a->timeline, tl, (size_t)B * JF * Tt * sizeof(float)}, {od || !wd ? nullptr : a->windows, wd, np * per_x * sizeof(float)}})) != LS_OK) return rc;
+    for (int k = 0; k < We && a->windows_run && k < a->windows_capacity; ++k) a->windows_run[k] = h->lg_cw[(size_t)k];
+    if (a->n_windows_run) *a->n_windows_run = We;
+    if (a->rows_run) *a->rows_run = np;
+    return LS_OK;
+}
 
 // Opening a stream (ls_long_stream_cond in ls_hip.h): a session of `batch` slots, every slot joined from the caller's arrays
 int ls_long_stream_open(ls_handle* h, const ls_long_stream_cond* c) {

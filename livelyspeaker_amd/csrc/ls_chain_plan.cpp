@@ -1,8 +1,8 @@
 // The plans of the chained-window engine (ls_chain_api.cpp): which clips run which window of a ragged call, which windows a timeline
-// edit runs, which windows a push of a stream runs, which rounds a push of a session pool runs and at which keys its rows draw, which copies feed the slots' rings.
+// edit runs (and which clips run each of them in its compact form), which windows a push of a stream runs, which rounds a push of a session pool runs and at which keys its rows draw, which copies feed the slots' rings.
 // Integer arithmetic on host arrays, no
 // HIP in here: each is the single definition for its entry and for Python (long_form.py), and tests/chain_plan_main.cpp and
-// tests/pool_plan_main.cpp and tests/pool_keys_main.cpp run them on their edges under the host sanitizers.
+// tests/pool_plan_main.cpp, tests/pool_keys_main.cpp and tests/edit_plan_main.cpp run them on their edges under the host sanitizers.
 #include <algorithm>
 #include <cstdint>
 #include <vector>
@@ -83,6 +83,54 @@ int ls_long_edit_plan(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre
         n += run ? 1 : 0;
     }
     *n_out = n;
+    return LS_OK;
+}
+
+// The clip-windows a COMPACT timeline edit runs (ls_long_edit_compact_args in ls_hip.h).  The pair (b, w) is in the plan iff clip b has
+// an editable element in window w by ls_long_edit_plan's rule -- its range meets the frames w owns, and one of its channels is
+// selected -- and, with `frames`, w is one of the clip's own W_b = (frames[b] - T) / S + 1 windows.  Window w runs iff some pair names
+// it; its rows are the clips of its pairs, ascending; the windows run ascending.  Property: without `frames` the windows that run
+// are exactly ls_long_edit_plan's for the same ranges (a clip without a selected channel folded to lo == hi), since both test the
+// same intersection clip by clip.
+int ls_long_edit_plan_compact(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const int32_t* lo, const int32_t* hi,
+                              const unsigned char* channels, int32_t n_channels, const int32_t* frames, int32_t* windows, int32_t* counts,
+                              int32_t window_capacity, int32_t* rows, int32_t row_capacity, int32_t* n_windows_run, int32_t* n_pairs) {
+    if (batch < 1 || n_windows < 1 || n_pre < 1 || T <= n_pre || !lo || !hi || !n_windows_run || !n_pairs) return LS_EINVAL;
+    if ((channels && n_channels < 1) || window_capacity < 0 || row_capacity < 0) return LS_EINVAL;
+    if ((window_capacity > 0 && (!windows || !counts)) || (row_capacity > 0 && !rows)) return LS_EINVAL;
+    const long long S = T - n_pre, Tt = T + (long long)(n_windows - 1) * S;
+    std::vector<int> wb((size_t)batch, n_windows);
+    std::vector<char> any((size_t)batch, 1);
+    for (int b = 0; b < batch; ++b) {
+        long long most = Tt;
+        if (frames) {
+            if (frames[b] < T || frames[b] > Tt || (frames[b] - T) % S) return LS_EINVAL;
+            most = frames[b];
+            wb[(size_t)b] = (int)((frames[b] - T) / S) + 1;
+        }
+        if (lo[b] < 0 || lo[b] > hi[b] || hi[b] > most) return LS_EINVAL;
+        if (channels) {
+            any[(size_t)b] = 0;
+            for (int c = 0; c < n_channels && !any[(size_t)b]; ++c) any[(size_t)b] = channels[(size_t)b * n_channels + c] != 0;
+        }
+    }
+    long long nw = 0, np = 0;
+    for (int w = 0; w < n_windows; ++w) {
+        const long long own_lo = w ? w * S + n_pre : 0, own_hi = w * S + T;
+        int n = 0;
+        for (int b = 0; b < batch; ++b) {
+            const bool in = any[(size_t)b] && w < wb[(size_t)b] && (lo[b] > own_lo ? lo[b] : own_lo) < (hi[b] < own_hi ? hi[b] : own_hi);
+            if (!in) continue;
+            if (rows) { if (np + n >= row_capacity) return LS_EINVAL; rows[np + n] = b; }
+            ++n;
+        }
+        if (n == 0) continue;
+        if (windows) { if (nw >= window_capacity) return LS_EINVAL; windows[nw] = w; counts[nw] = n; }
+        ++nw; np += n;
+        if (np > INT32_MAX) return LS_EINVAL;
+    }
+    *n_windows_run = (int32_t)nw;
+    *n_pairs = (int32_t)np;
     return LS_OK;
 }
 

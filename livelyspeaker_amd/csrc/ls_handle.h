@@ -140,6 +140,17 @@ struct ls_handle {
     std::vector<int> lg_bw, lg_off;
     int lg_scale_ones = 0;
     DevBuf lg_row, lg_table, lg_lens;
+    // a compact timeline edit (ls_long_prepare_edit -> ls_long_edit_compact): clips in the caller's order.  The plan of
+    // ls_long_edit_plan_compact: window lg_cw[e] runs the lg_cn[e] clips lg_crows[lg_coff[e] ..], and lg_coff[e] is its offset in the
+    // packed stores (lg_featc, the tapes, the raw windows); lg_crows_dev holds the row tables on the device.  The arguments the plan
+    // was made from (lg_clo / lg_chi as given, lg_cchan folded to 0 / 1; empty: every channel), which the edit must repeat.  The held
+    // per-clip conditioning: lg_cvid / lg_cscale_dev [B], the scales on the host (a window's single-pass decision), the emotion
+    // tokens in lg_emotok [W][B][512]; lg_ctext [B][512]: the text features of the window in flight, by row.
+    bool lg_compact = false;
+    std::vector<int32_t> lg_cw, lg_cn, lg_coff, lg_crows, lg_clo, lg_chi;
+    std::vector<unsigned char> lg_cchan;
+    std::vector<float> lg_cscale;
+    DevBuf lg_crows_dev, lg_cvid, lg_cscale_dev, lg_ctext;
     // Streaming sessions (ls_long_pool_open / _join / _push; ls_long_stream_open / _push): pl_S slots, each a stream of its own.  Per
     // slot on the device: the ring pl_ring [S][pl_R] (sample n of the slot at n % pl_R; the samples below audio_stride * pl_windows[s]
     // are dead), the hand-off poses pl_hand [S][JF][n_pre] (seed poses until the slot's window 0 has run), the held conditioning pl_vid /
@@ -215,8 +226,9 @@ enum CachePolicy { kReplace, kKeep, kReplayOnly };
 int check_sampler_args(ls_handle* h, const ls_sample_args* a);
 // keyed: PHILOX rows draw at row_gidx (the caller wrote rows [0, B) in stream order) in place of sample_offset + b
 int run_window_loop(ls_handle* h, const ls_sample_args* a, bool resident_inpaint, bool first, CachePolicy policy, int* graph_replayed, bool keyed = false);
-// the ring of a keyed loop for batches up to B and loops up to n_exec steps, so that no loop at a smaller batch moves it
-int size_key_ring(ls_handle* h, int B, int n_exec);
+// the ring of a keyed loop for batches up to B and loops up to n_exec steps, so that no loop at a smaller batch moves it;
+// inp_noised: with the re-noise plane of the inpainting branch (a compact timeline edit of the TED tree)
+int size_key_ring(ls_handle* h, int B, int n_exec, bool inp_noised = false);
 inline float* x_plane(const ls_handle* h, int k) { return (k & 1) ? h->xb.f() : h->xa.f(); }      // x ahead of executed step k (xa / xb ping-pong)
 // ---- defined in ls_chain_plan.cpp (host only): slot -> clip, windows per slot, clips per window of a ragged long-form call
 void long_plan_drop(int B, int AL, const int64_t* lengths, std::vector<int>& row, std::vector<int>& wins, std::vector<int>& bw);
@@ -244,7 +256,7 @@ inline int egress(ls_handle* h, void* dst, const void* src, size_t bytes, int on
 inline void end_stream(ls_handle* h) {
     if (h->pl_state == ls_handle::kStreamOpen) h->pl_state = ls_handle::kStreamReplaced;
 }
-inline void end_chain(ls_handle* h) { h->lg_prepared = false; end_stream(h); }       // ls_prepare: a long-form call's conditioning goes too
+inline void end_chain(ls_handle* h) { h->lg_prepared = h->lg_compact = false; end_stream(h); }      // ls_prepare: a long-form call's conditioning goes too
 
 inline void free_graph(ls_handle* h) {        // every cached graph: whatever invalidates one invalidates all
     for (auto& g : h->graphs) {

@@ -327,15 +327,30 @@ hipError_t launch_chain_window(const ChainArgs& a, int B, hipStream_t st);
 // into the timeline and the whole sample to window [B][JF][T] (nullable).  launch_edit_start (a scripted edit, ls_long_edit_sag) stores
 // the editable elements of sag_out [B][JF][T] (the SAG decoder's output, reference layout) into init, which holds the slice: init =
 // where(keep, slice, sag_out).
+// The COMPACT edit (ls_long_edit_compact) runs a window on the clips that have an editable element in it: `rows` [B] on the device,
+// ascending, names the clip behind each of the B launched rows.  Workgroup r then serves clip rows[r]: timeline, range, chan and seed
+// are indexed by CLIP; the planes a sampling call at batch B reads and writes (motion, maskf, feat_u, origin_x, init, sag_out, sample,
+// window) by ROW.  rows == nullptr: row r is clip r, the dense edit.  The launchers cannot check a device table: its entries
+// (0 <= rows[r] < clips of the clip-indexed arrays) are the caller's to check before upload.
 struct EditArgs {
     float* timeline; const float* seed; const int* range; const unsigned char* chan;
     float* motion; float* maskf; float* feat_u; float* origin_x; float* init;      // gather
     const float* sample; float* window;                                             // scatter
     int JF, T, KPP, n_pre, T_total, w;
+    const int* rows;
 };
 hipError_t launch_edit_gather(const EditArgs& a, int B, hipStream_t st);
 hipError_t launch_edit_start(const EditArgs& a, const float* sag_out, int B, hipStream_t st);
 hipError_t launch_edit_scatter(const EditArgs& a, int B, hipStream_t st);
+// The held per-clip conditioning of one window of a compact edit into rows [0, A): row r <- clip rows[r] of vid_c / scale_c [clips] and
+// of emo_tok_c / text_c [clips][kD] (each of the two pairs nullable; 16-byte aligned).  k_pool_gather's conditioning move with clips
+// in place of slots.
+struct CondGatherArgs {
+    const int* rows;
+    const int64_t* vid_c; const float* scale_c; const float* emo_tok_c; const float* text_c;
+    int64_t* vid; float* scale; float* emo_tok; float* text;
+};
+hipError_t launch_cond_gather(const CondGatherArgs& a, int A, hipStream_t st);
 // One encoder chunk of a ragged long-form call: clips[p][i] = audio[row][w * stride + i] for the n (row, w) pairs of `table`, 0 where
 // that sample index is >= lengths[row] (nothing beyond a clip's length is read).  audio [.][L], clips [n][AL].
 hipError_t launch_long_gather_clips(const float* audio, const int* table, const int* lengths, float* clips, int n, int AL, long long L,
@@ -393,11 +408,13 @@ hipError_t launch_bcast_first(float* x, int B, int per, hipStream_t st);
 // ---- Philox draws keyed per row (ls_philox_rows.hip; ls_set_row_keys, a keyed session pool) ---------------------------------
 // Row b draws at gidx[b] (a device table at a fixed address, rewritten in stream order ahead of a loop) under call->seed.
 // launch_row_xt: x_T [B][T][JF] into x.  launch_row_draws: executed steps [k0, k0 + nsteps) into slots 0 .. nsteps - 1 of
-// eps [.][2][B][D] and noise [.][B][J][F][T]; step last_step draws no noise.
+// eps [.][2][B][D] and noise [.][B][J][F][T]; step last_step draws no noise.  inz (nullable) [.][B][J][F][T]: the inpainting branch's
+// re-noise of the kept motion (stream 4, what k_inpaint_update draws itself where it is given no tape), not drawn at last_step
+// either (t == 0 re-noises nothing).
 struct RowDrawArgs {
     const CallParams* call;
     const unsigned long long* gidx;
-    float* x; float* eps; float* noise;
+    float* x; float* eps; float* noise; float* inz;
     int B, JF, T, k0, nsteps, last_step;
 };
 hipError_t launch_row_xt(const RowDrawArgs& a, hipStream_t st);

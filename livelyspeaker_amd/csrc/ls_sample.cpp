@@ -190,7 +190,7 @@ Draws loop_draws(const ls_handle* h, const LoopCall& c, unsigned e, int k) {
 RowDrawArgs row_draw_args(const ls_handle* h, const LoopCall& c) {
     RowDrawArgs r{};
     r.call = static_cast<const CallParams*>(h->callp.p); r.gidx = static_cast<const unsigned long long*>(h->row_gidx.p);
-    r.eps = h->trng_eps.f(); r.noise = h->trng_noise.f();
+    r.eps = h->trng_eps.f(); r.noise = h->trng_noise.f(); r.inz = c.inp_noised ? h->trng_inz.f() : nullptr;
     r.B = c.B; r.JF = h->JF; r.T = h->T; r.last_step = c.n_exec - 1;
     return r;
 }
@@ -621,14 +621,15 @@ int ls::run_window_loop(ls_handle* h, const ls_sample_args* a, bool resident_inp
     return run_loop(h, c, graph_replayed, policy);
 }
 
-int ls::size_key_ring(ls_handle* h, int B, int n_exec) {
+int ls::size_key_ring(ls_handle* h, int B, int n_exec, bool inp_noised) {
     size_t eps = 0, nz = 0;
     for (int b = 1; b <= B; ++b) {
-        const size_t k = (size_t)ring_steps(h, b, false, n_exec);
+        const size_t k = (size_t)ring_steps(h, b, inp_noised, n_exec);
         eps = std::max(eps, k * 2 * b * kD * sizeof(float)); nz = std::max(nz, k * b * h->JF * h->T * sizeof(float));
     }
     int rc;
     if ((rc = ensure_pinned(h, h->trng_eps, eps)) != LS_OK || (rc = ensure_pinned(h, h->trng_noise, nz)) != LS_OK) return rc;
+    if (inp_noised && (rc = ensure_pinned(h, h->trng_inz, nz)) != LS_OK) return rc;
     return ensure_pinned(h, h->row_gidx, (size_t)B * sizeof(unsigned long long));
 }
 

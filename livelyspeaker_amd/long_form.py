@@ -22,7 +22,10 @@ A finished timeline is corrected with ``edit_long``: a frame range per clip (opt
 windows that own one of its frames (``edit_plan``), each through the sampling loop's inpainting branch with the window's slice of the
 timeline as the given motion (``edit_window``; ``ls_long_edit``, ``k_edit_gather`` / ``k_edit_scatter``); everything else is kept bit
 for bit.  With ``sag=`` / ``text_features=`` the edit is script-guided: every window that runs starts from the SAG decoder's output on
-its editable elements (``edit_start``; ``ls_long_edit_sag``, ``k_edit_start``).
+its editable elements (``edit_start``; ``ls_long_edit_sag``, ``k_edit_start``).  ``edit_long(compact=True)`` runs only the
+clip-windows the edit touches (``edit_plan_compact``; ``ls_long_prepare_edit`` + ``ls_long_edit_compact``): window w is a sampling call
+on the clips that have an editable element in it, and only those clip-windows of audio are encoded; ``audio_lengths=`` edits the
+timeline of a ragged ``sample_long`` call that way.
 
 ``open_stream`` is the online form of the same chain: audio arrives in chunks of any size, a window runs as soon as its last sample
 is there, and the frames of all pushes are bit for bit ``sample_long``'s for the concatenated audio (``ls_long_stream_open`` /
@@ -955,6 +958,22 @@ def edit_plan(ranges, n_windows, cfg):
     return windows
 
 
+def edit_plan_compact(ranges, n_windows, cfg, joints=None, frames=None):
+    """The clip-windows the COMPACT ``edit_long`` runs, as a list of ``(w, rows)``: the windows that run, ascending, each with the
+    clips that have an editable element in it, ascending (``rows``, a list of clip indices).  The pair (clip b, window w) is in the
+    plan iff b's range meets the frames w OWNS (``edit_plan``'s rule), at least one joint of b is selected by ``joints`` (None = all,
+    bool [J] or [B, J]), and -- with ``frames`` (int [B], a ragged batch: ``plan_lengths``) -- ``w`` is one of the clip's own
+    ``(frames[b] - T) / S + 1`` windows.  Without ``frames`` the windows are exactly ``edit_plan``'s.  A range outside
+    ``[0, frames[b]]``, ``lo > hi`` or a ``frames[b]`` that is no stitched length (34 + 30 k): ``ValueError``.  No pair at all is an
+    empty list, which ``edit_long`` refuses.  One definition for the engine and for this module (``ls_long_edit_plan_compact``)."""
+    T, npre, W = int(cfg.nframes), int(cfg.n_pre_seq), int(n_windows)
+    fr = np.asarray(ranges.detach().cpu().numpy() if hasattr(ranges, "detach") else ranges)
+    B = int(fr.shape[0]) if fr.ndim == 2 else 1 if frames is None else int(np.asarray(frames).size)      # one pair: for every clip of `frames`
+    lo, hi = _edit_ranges(fr, B, _window_sizes(W, cfg)[1])
+    sel = _edit_joints(joints, B, cfg)
+    return [(w, [int(b) for b in rows]) for w, rows in _lib.long_edit_plan_compact(lo, hi, W, sel, frames, T, npre)]
+
+
 def edit_window(timeline, w, ranges, joints, seed_poses, cfg):
     """Window ``w`` of a timeline edit in plain torch: ``(origin_x, inpainting_mask, inpainted_motion)``, each [B, J, F, T], as
     ``edit_long`` hands them to the sampling loop.
@@ -996,7 +1015,8 @@ def edit_start(motion, mask, sag_out):
 
 
 def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices, scale, emo=None, joints=None, sampler='ddim',
-              skip_timesteps=0, eta=0.0, clip_denoised=False, encoder_chunk=None, return_windows=False, sag=None, text_features=None):
+              skip_timesteps=0, eta=0.0, clip_denoised=False, encoder_chunk=None, return_windows=False, sag=None, text_features=None,
+              compact=None, audio_lengths=None):
     """Re-synthesise a stretch of a timeline ``sample_long`` made: the frames ``frames`` -- one ``(lo, hi)`` pair for all clips or a
     host int array [B, 2], ``lo == hi`` leaves a clip alone -- on the joints ``joints`` (None = all; a bool mask [J] or [B, J]), with
     the conditioning of the ``sample_long`` call (``audio``, ``seed_poses``, ``vid_indices``, ``scale``, ``emo``).  Returns a new
@@ -1030,21 +1050,47 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
     kernel per window (``ls_long_edit_sag``; ``k_edit_start``).  One of ``sag`` / ``text_features`` without the other, a wrong
     shape, a decoder whose geometry is not the RAG model's or that sits on another device: ``ValueError``.
 
+    ``compact=True`` runs only the CLIP-WINDOWS the edit touches (``edit_plan_compact``; ``ls_long_prepare_edit`` +
+    ``ls_long_edit_compact``): window w is one sampling call at batch ``len(rows)`` on the clips that have an editable element in
+    it -- its own kernel plan, the single-pass shortcut when the scales of THOSE clips are all 1 -- and only those clip-windows of
+    audio go through the WavEncoder.  A clip outside a window's rows does not run in it; a clip in no window is returned as given.
+    ``return_windows=True`` then returns ``(timeline, plan, raw samples [sum len(rows), J, F, T])`` with ``plan`` the list of
+    ``(w, rows)``, the samples row after row in plan order.  The noise contract:
+
+    * ``'torch_cpu'``: the draws of one public sampling call per planned window at batch ``len(rows)``, window after window
+      (``RefDraws.edit_windows(batches=)``); the result is bit for bit the loop above run on ``timeline[rows]`` with those clips'
+      ranges, joints, seed poses and conditioning (tests/test_gpu_long_edit_compact.py);
+    * ``'philox'``: clip b draws, in window w, EVERY stream at ``sample_offset + b + (w << 48)`` -- the clip's index, not its row --
+      so its edited frames do not depend on which other clips share its windows, and where every clip is in every running window the
+      result is the dense call's, bit for bit.
+
+    ``audio_lengths`` (a host sequence [B], each in [1, L]) edits a RAGGED batch, the timeline of ``sample_long(audio_lengths=...)``
+    with or without ``drop_finished``; it implies the compact form (together with ``compact=False``: ``ValueError``).  Clip b has
+    ``frames[b]`` frames and ``W_b`` windows (``plan_lengths``); its range must lie inside ``[0, frames[b]]`` (``ValueError``
+    otherwise), windows ``w >= W_b`` never run for it, ``audio[b, audio_lengths[b]:]`` is never read and counts as silence, and the
+    frames beyond ``frames[b]`` are returned bit for bit as given.  ``emo`` [B, W] and ``text_features`` [B, W, 512] are sized by the
+    longest clip's W, in the caller's clip order; entries of pairs outside the plan are not used.
+
     To know, not to be surprised by:
 
     * a window behind the last edited one is NOT resampled, even though its four conditioning frames may have changed; widen the
       range to have it resampled;
-    * a clip whose range misses a window that runs for another clip still runs in it, with every element kept; its result is discarded.
+    * in the dense form (``compact`` unset) a clip whose range misses a window that runs for another clip still runs in it, with every
+      element kept; its result is discarded, and all W windows of every clip go through the WavEncoder.  The compact form does neither;
+    * ``compact=None`` (the default) means the dense form unless ``audio_lengths`` is given.
 
-    Not built: edits of a running stream or pool, ragged batches (``audio_lengths=``), PLMS, ``const_noise``, ``dump_steps``,
-    ``'torch_device'``, re-encoding only the edited windows' audio (all W windows go through the WavEncoder, as in ``sample_long``),
-    resampling windows behind the last edited one, and the SAG encoder (motion -> latent) as the source of ``text_features``
-    (chain ``MOTIONCLIP`` yourself)."""
+    Not built: edits of a running stream or pool, PLMS, ``const_noise``, ``dump_steps``, ``'torch_device'``, resampling windows behind
+    the last edited one, the SAG encoder (motion -> latent) as the source of ``text_features`` (chain ``MOTIONCLIP`` yourself) and
+    device-resident length arrays; in the dense form also ragged batches (``audio_lengths=``) and re-encoding only the edited windows'
+    audio (all W windows go through the WavEncoder, as in ``sample_long``)."""
     from .cfg_sampler import ClassifierFreeSampleModel
     if not isinstance(model, ClassifierFreeSampleModel):
         raise TypeError(f"edit_long: pass livelyspeaker_amd.ClassifierFreeSampleModel(RAG), got {type(model).__name__}")
     if diffusion.noise_source == "torch_device":
         raise NotImplementedError("edit_long: noise_source='torch_device' is not built for chained windows; use 'torch_cpu' or 'philox'")
+    if audio_lengths is not None and compact is not None and not compact:
+        raise ValueError("edit_long: audio_lengths edits a ragged batch, which only the compact form does; drop compact=False")
+    compact = bool(compact) or audio_lengths is not None
     timeline, audio, seed_poses, vid_indices, scale, emo, text_features = _as_tensors(timeline, audio, seed_poses, vid_indices, scale, emo,
                                                                                       text_features)
     rag = model.model
@@ -1064,16 +1110,38 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
     _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, W, sampler, skip_timesteps, sag, text_features, encoder_chunk, {})
     _check_model(diffusion, rag)
     hi = np.where(sel.any(axis=1), hi, lo).astype(np.int32)           # a clip with no joint selected is not edited
-    windows = edit_plan(np.stack([lo, hi], axis=1), W, rag)
+    lens = frames = None
+    if audio_lengths is not None:
+        lens = _lib.host_lengths(audio_lengths, B, 1, int(audio.shape[1]), "audio_lengths")
+        plans = plan_lengths(lens, rag)
+        frames = np.array([f for _, f in plans], np.int32)
+        if max(Wb for Wb, _ in plans) != W:
+            raise ValueError(f"the timeline holds {W} windows, the longest of audio_lengths needs {max(Wb for Wb, _ in plans)}")
+        if (hi > frames).any():
+            raise ValueError(f"every frame range must lie inside its own clip, 0 <= lo <= hi <= frames[b] = {frames.tolist()}, got "
+                             f"{np.stack([lo, hi], axis=1).tolist()}")
+    channels = np.repeat(sel, rag.nfeats, axis=1)
+    if compact:
+        plan = edit_plan_compact(np.stack([lo, hi], axis=1), W, rag, joints=sel, frames=frames)
+        if not plan:
+            raise ValueError("edit_long: every frame range is empty, no window would run")
+        batches = [len(rows) for _, rows in plan]
+    else:
+        windows = edit_plan(np.stack([lo, hi], axis=1), W, rag)
     out_dev = timeline.device
     eng = _bind_engine(diffusion, rag)
-    eng.long_prepare(audio.float(), seed_poses.float(), vid_indices, scale.float(), emo=_emo_windows(emo, W, B), n_windows=W,
-                     encoder_chunk=encoder_chunk)
+    if compact:
+        eng.long_prepare_edit(audio.float(), seed_poses.float(), vid_indices, scale.float(), lo, hi, channels=channels,
+                              emo=_emo_windows(emo, W, B), n_windows=W, encoder_chunk=encoder_chunk, audio_lengths=lens)
+        assert [(w, [int(b) for b in rows]) for w, rows in eng.edit_plan] == plan, (eng.edit_plan, plan)
+    else:
+        eng.long_prepare(audio.float(), seed_poses.float(), vid_indices, scale.float(), emo=_emo_windows(emo, W, B), n_windows=W,
+                         encoder_chunk=encoder_chunk)
     n_exec = diffusion.num_timesteps - int(skip_timesteps)
-    shape = (B, rag.njoints, rag.nfeats, T)
+    shape = (max(batches) if compact else B, rag.njoints, rag.nfeats, T)       # the compact form: its largest window batch
     noised = rag.n_prefix_tokens == 1                  # the TED tree re-noises the kept motion, the BEAT tree does not
     kw = dict(_loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised), device_out=out_dev.type == "cuda", return_windows=return_windows,
-              inpaint_noised=noised, channels=np.repeat(sel, rag.nfeats, axis=1))
+              inpaint_noised=noised, channels=channels)
     if sag is not None:
         sag_eng = sag.engine()
         if sag_eng.device != eng.device:
@@ -1085,9 +1153,11 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
     else:
         _check_tape_bound(diffusion, "edit_long", n_exec, shape, eng.D, renoised=noised)
         kw["x_init"], kw["eps_tape"], kw["noise_tape"], kw["inpaint_noise"] = ref_draws.RefDraws("cpu").edit_windows(
-            diffusion, len(windows), n_exec, shape, eng.D, noised)
+            diffusion, len(plan) if compact else len(windows), n_exec, shape, eng.D, noised, batches=batches if compact else None)
         diffusion.last_tape_segments = 1
-    res = eng.long_edit(timeline.float(), lo, hi, **kw)
+    res = (eng.long_edit_compact if compact else eng.long_edit)(timeline.float(), lo, hi, **kw)
+    if compact:
+        res = (res[0], plan) + tuple(res[2:])
     edited = gd._as_tensor(res[0], out_dev)
     return (edited, res[1], gd._as_tensor(res[2], out_dev)) if return_windows else edited
 

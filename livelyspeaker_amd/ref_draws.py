@@ -106,12 +106,35 @@ class RefDraws:
             first += Bw
         return x, eps, nz
 
-    def edit_windows(self, diffusion, n_run, n_exec, shape, D, noised):
+    def edit_windows(self, diffusion, n_run, n_exec, shape, D, noised, batches=None):
         """Timeline edit (long_form.edit_long): what one public sampling call per window that runs draws, one after the other -- x_T,
         then that window's steps with the inpainting branch's re-noise draw between the model call and the step noise when ``noised``
         (the TED tree; its prototype is the window's slice of the timeline, contiguous).  Returns (x [n_run, B, J, F, T], eps
-        [n_run, n_exec, 2, B, D], noise [n_run, n_exec, B, J, F, T], re-noise of the same shape or None)."""
+        [n_run, n_exec, 2, B, D], noise [n_run, n_exec, B, J, F, T], re-noise of the same shape or None).
+
+        ``batches`` (one batch size per window that runs; ``shape[0]`` is then ignored): the compact edit -- window i is a call at
+        batch ``batches[i]``, and the tapes come back packed as in ``windows(batches=)``: x [sum batches, J, F, T], and flat eps /
+        noise / re-noise holding per window [n_exec, 2, A_i, D] / [n_exec, A_i, J, F, T], concatenated."""
         shape = tuple(shape)
+        if batches is not None:
+            batches = [int(b) for b in batches]
+            if len(batches) != n_run or min(batches) < 1:
+                raise ValueError(f"batches must hold {n_run} batch sizes >= 1, got {batches}")
+            rest, total = shape[1:], sum(batches)
+            per_x = int(np.prod(rest))
+            x, eps, nz = th.empty((total,) + rest), th.empty(total * n_exec * 2 * D), th.empty(total * n_exec * per_x)
+            inz = th.zeros(total * n_exec * per_x) if noised else None
+            first = 0
+            for A in batches:
+                wshape = (A,) + rest
+                x[first:first + A] = self.x_T(wshape)
+                steps = self.steps(wshape, D, n_exec, inpainted=th.empty(wshape, device=self.rdev) if noised else None, diffusion=diffusion)
+                steps.run(0, eps[first * n_exec * 2 * D:(first + A) * n_exec * 2 * D].view(n_exec, 2, A, D),
+                          nz[first * n_exec * per_x:(first + A) * n_exec * per_x].view((n_exec,) + wshape))
+                if noised:
+                    inz[first * n_exec * per_x:(first + A) * n_exec * per_x].view((n_exec,) + wshape).copy_(steps.inz)
+                first += A
+            return x, eps, nz, inz
         x, eps, nz = th.empty((n_run,) + shape), th.empty(n_run, n_exec, 2, shape[0], D), th.empty((n_run, n_exec) + shape)
         inz = th.zeros((n_run, n_exec) + shape) if noised else None
         proto = th.empty(shape, device=self.rdev) if noised else None

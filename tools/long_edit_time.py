@@ -4,6 +4,7 @@ timeline again (long_form.sample_long of the same W), alternated in one process:
     python tools/long_edit_time.py                 # 60 s of speech, 64 clips (profiles/r19_long_edit.md)
     python tools/long_edit_time.py 20 8            # seconds, clips
     python tools/long_edit_time.py --sag [20 8]    # the SCRIPTED edit two ways (profiles/r26_long_edit_sag.md)
+    python tools/long_edit_time.py --compact [--sag] [20 8]    # the dense against the COMPACT edit (profiles/r31_edit_compact.md)
 
 TED, ddim100, skip_timesteps = 80 (20 steps per window), guidance 1.5, Philox noise, device-resident inputs, hipGraph replay, warm
 handles.  Three forms: the full call, an edit inside one window, and an edit that spans W // 2 windows.  Each call is timed by a host
@@ -18,7 +19,11 @@ than in the full call (the inpainting branch runs the denoiser and the update as
 --sag times the script-guided edit of the `one` and `half` ranges two ways, alternated in the same manner: edit_long(sag=,
 text_features=) -- one engine call -- and the host loop it replaces, "for w in edit_plan: edit_window -> decoder -> edit_start ->
 ddim_sample_loop(init_image=) -> write-back", through the public per-clip API (which encodes a window's audio when it samples it,
-where edit_long encodes all W windows ahead; both are part of what a caller waits for and both are inside the timed call)."""
+where edit_long encodes all W windows ahead; both are part of what a caller waits for and both are inside the timed call).
+
+--compact alternates edit_long(compact=False) and edit_long(compact=True) of the same ranges, round by round, in three cases: (a) one
+clip in one window, (b) 8 clips each in a window of its own, (c) every clip in W // 2 windows, where the compact plan is the dense one
+and the results are checked to be the same bits.  With --sag the edits are scripted, and (a) is timed against the host loop too."""
 import os
 import statistics
 import sys
@@ -98,7 +103,95 @@ def main_sag(seconds, B):
     clocks.on = False
 
 
+def main_compact(seconds, B, scripted):
+    """The dense and the compact form of the same edit, alternated round by round (profiles/r31_edit_compact.md): (a) one clip, one
+    window; (b) 8 clips, each in a window of its own; (c) every clip in W // 2 windows (the identity plan).  scripted: with the SAG
+    decoder, and (a) against the host loop of main_sag as well."""
+    import numpy as np
+    cfg, model, diffusion = build()
+    diffusion.noise_source, diffusion.philox_seed = "philox", 1
+    W, _, n_frames = long_form.plan_windows(int(round(seconds * 16000)), cfg)
+    y = {k: torch.from_numpy(v).to(DEV) for k, v in synth.make_long_cond(cfg, B, W).items()}
+    S = cfg.nframes - cfg.n_pre_seq
+    mid, half_lo, n8 = W // 2, (W // 4) * S + 10, min(8, B, W)
+    a = np.zeros((B, 2), np.int64)
+    a[0] = (mid * S + 10, mid * S + 20)
+    b = np.zeros((B, 2), np.int64)
+    for k in range(n8):                                              # clip k inside the frames window first + k owns
+        w = max(0, mid - n8 // 2) + k
+        b[k] = (w * S + 10, w * S + 20)
+    c = np.tile(np.array([(half_lo, half_lo + (W // 2 - 1) * S + 5)], np.int64), (B, 1))
+    cases = {"a": a, "b": b, "c": c}
+    kw, sag, text = {}, None, None
+    if scripted:
+        from livelyspeaker_amd.motionclip_module import Decoder_TRANSFORMER
+        sag = Decoder_TRANSFORMER(njoints=cfg.njoints, nfeats=cfg.nfeats, latent_dim=512, n_pre_poses=cfg.n_pre_seq, use_style=False)
+        sag.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_sag_state_dict(cfg).items()}, strict=False)
+        sag.to(DEV).eval()
+        text = torch.from_numpy(synth.make_text_features(B * W).reshape(B, W, 512)).to(DEV)
+        kw = dict(sag=sag, text_features=text)
+    timeline = long_form.sample_long(diffusion, model, y["audio"], y["seed_poses"], y["vid_indices"], y["scale"], n_windows=W, sampler="ddim",
+                                     skip_timesteps=SKIP, **kw)
+
+    def call(frames, compact):
+        return long_form.edit_long(diffusion, model, timeline, frames, y["audio"], y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim",
+                                   skip_timesteps=SKIP, compact=compact, **kw)
+
+    forms = []
+    for name, frames in cases.items():
+        if scripted and name == "a":
+            forms.append((name, "loop", lambda frames=frames: host_loop(diffusion, model, sag, text, cfg, y, timeline, frames, W)))
+        forms.append((name, "dense", lambda frames=frames: call(frames, False)))
+        forms.append((name, "compact", lambda frames=frames: call(frames, True)))
+    # the identity plan gives the dense call's bits; elsewhere the compact form changes the same elements and no other
+    assert torch.equal(call(c, True), call(c, False))
+    for frames in (a, b):
+        got, ref = call(frames, True), call(frames, False)
+        assert torch.equal(got != timeline, ref != timeline) and bool(torch.isfinite(got).all())
+    clocks = ClockSampler()
+    clocks.start()
+    for _ in range(2):                                               # warm-up of all forms: allocations, graph capture, clocks
+        for _, _, fn in forms:
+            timed(fn)
+    clocks.take()
+    reps = 3
+    rounds, engine = {(n, k): [] for n, k, _ in forms}, {}
+    for _ in range(ROUNDS):
+        for name, kind, fn in forms:
+            rounds[name, kind].append(statistics.median(timed(fn)[0] for _ in range(reps)))
+            if kind != "loop":
+                engine[name, kind] = model.model.engine().timing()
+    print(f"# dense against compact edit_long{' (scripted)' if scripted else ''}; TED ddim100 skip {SKIP} (20 steps per window), CFG 1.5, philox, "
+          f"device inputs; {seconds:g} s of speech = {W} windows ({n_frames} frames), {B} clips; ms per call, median over {ROUNDS} alternated "
+          f"rounds [min .. max of the rounds]; prepare / windows: the engine's event times of the last call")
+    for name, frames in cases.items():
+        plan = long_form.edit_plan_compact(frames, W, cfg)
+        pairs = sum(len(rows) for _, rows in plan)
+        print(f"case {name}: {len(plan)} windows, {pairs} clip-windows of {len(plan) * B} dense ({W * B} encoded by the dense form)")
+        for kind in ("loop", "dense", "compact"):
+            if (name, kind) not in rounds:
+                continue
+            r = rounds[name, kind]
+            line = f"  {kind:8s} {statistics.median(r):9.2f} [{min(r):.2f} .. {max(r):.2f}]"
+            if kind != "loop":
+                t = engine[name, kind]
+                line += (f"  | prepare {t['prepare_ms']:.2f} ms, windows {t['total_ms']:.2f} ms, {t['n_step_launches']} steps, graph replayed for "
+                         f"{t['graph_replayed']} of {t['n_segments']} windows, step path {t['step_path']}")
+            print(line, flush=True)
+        d, cpt = rounds[name, "dense"], rounds[name, "compact"]
+        print(f"  dense / compact {statistics.median(d) / statistics.median(cpt):.2f}x; compact faster in {sum(p < q for p, q in zip(cpt, d))} of"
+              f"{ROUNDS} rounds; dense spread {max(d) - min(d):.2f} ms, median difference {statistics.median(cpt) - statistics.median(d):+.2f} ms")
+    print(f"# {clocks.take()}")
+    clocks.on = False
+
+
 def main():
+    if "--compact" in sys.argv:
+        sys.argv.remove("--compact")
+        scripted = "--sag" in sys.argv
+        if scripted:
+            sys.argv.remove("--sag")
+        return main_compact(float(sys.argv[1]) if len(sys.argv) > 1 else 60.0, int(sys.argv[2]) if len(sys.argv) > 2 else 64, scripted)
     if "--sag" in sys.argv:
         sys.argv.remove("--sag")
         return main_sag(float(sys.argv[1]) if len(sys.argv) > 1 else 60.0, int(sys.argv[2]) if len(sys.argv) > 2 else 64)
