@@ -13,6 +13,7 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py --long-seconds A,B,... [--drop-finished]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --edit-frames LO,HI [--edit-joints J0,J1,...] [--edit-text [--clip-text]]
     python examples/livelyspeaker_ted.py --long-seconds 20,45.5,8 --edit-frames LO,HI [--edit-clip K] [...]
+    python examples/livelyspeaker_ted.py [batch] --long-seconds N --edit-frames "LO,HI;LO,HI" [--edit-pin N[,N]] [--edit-joints ...] [--edit-clip K]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --stream-chunk SECONDS [--post [--score]] [--input-sr RATE]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --score-talk
     python examples/livelyspeaker_ted.py --pool SPEAKERS
@@ -39,6 +40,9 @@ range touches, 20 refinement steps each), everything else is kept bit for bit, a
 --edit-text makes that edit SCRIPT-GUIDED (edit_long(sag=, text_features=)): the edited frames start from the SAG decoder's output for
 one text feature [B, 512] -- a synthetic stand-in, or with --clip-text a sentence of synthetic tokens through CLIPTextEncoder -- and the
 kept ones from the existing motion; it prints how far the edited frames moved from the unscripted edit with the same seed.
+--edit-frames "LO,HI;LO,HI;..." edits SEVERAL stretches in one call and --edit-pin N[,N...] pins keyframes inside them (those frames
+are kept and the motion is re-synthesised around them): both through edit_long(mask=), where "editable" is a mask over the timeline's
+elements instead of one rectangle per clip (--edit-text is not wired to this form).
 --edit-clip K edits clip K of the batch alone, and --edit-frames after a comma list of durations edits the RAGGED batch (every clip on
 the part of [LO, HI) that lies inside its own frames): both through the compact form (edit_long(compact=True / audio_lengths=)), which
 runs only the clip-windows the edit touches; the line printed lists them.
@@ -197,7 +201,10 @@ def main():
         edit = None
         if "--edit-frames" in sys.argv:
             j = sys.argv.index("--edit-frames")
-            edit = {"frames": tuple(int(v) for v in sys.argv[j + 1].split(","))}
+            stretches = [tuple(int(v) for v in part.split(",")) for part in sys.argv[j + 1].split(";") if part]
+            if not stretches or any(len(st) != 2 for st in stretches):
+                raise SystemExit("--edit-frames takes LO,HI or several stretches LO,HI;LO,HI;... (quote the semicolons)")
+            edit = {"frames": stretches[0], "stretches": stretches}
             del sys.argv[j:j + 2]
             if len(edit["frames"]) != 2:
                 raise SystemExit("--edit-frames takes LO,HI")
@@ -206,6 +213,12 @@ def main():
             if edit is None:
                 raise SystemExit("--edit-joints goes with --edit-frames")
             edit["joints"] = [int(v) for v in sys.argv[j + 1].split(",") if v]
+            del sys.argv[j:j + 2]
+        if "--edit-pin" in sys.argv:
+            j = sys.argv.index("--edit-pin")
+            if edit is None:
+                raise SystemExit("--edit-pin goes with --edit-frames")
+            edit["pins"] = [int(v) for v in sys.argv[j + 1].split(",") if v]
             del sys.argv[j:j + 2]
         if "--edit-clip" in sys.argv:
             j = sys.argv.index("--edit-clip")
@@ -535,6 +548,8 @@ def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit,
     script on the edited elements.  edit['clip'] edits that clip of the batch alone, and lengths / frames (main_long_ragged) edit a
     ragged batch, every clip inside its own frames: both through the compact form, which runs only the clip-windows it touches."""
     import numpy as np
+    if len(edit.get("stretches", ())) > 1 or edit.get("pins"):
+        return edit_timeline_by_mask(long_form, cfg, model, diffusion, timeline, audio, y, W, edit, lengths, frames)
     lo, hi = edit["frames"]
     B = timeline.shape[0]
     joints = None
@@ -585,6 +600,47 @@ def edit_timeline(long_form, cfg, model, diffusion, timeline, audio, y, W, edit,
     moved = (scripted - edited)[~kept].abs()
     print(f"the same edit guided by one script ({edit['text']} text feature): {dt * 1e3:.1f} ms; the edited values moved by "
           f"{float(moved.mean()):.4f} on average (max {float(moved.max()):.4f}) from the unscripted edit with the same seed")
+
+
+def edit_timeline_by_mask(long_form, cfg, model, diffusion, timeline, audio, y, W, edit, lengths=None, frames=None):
+    """Several stretches in ONE call, with keyframes pinned inside them: edit_long(mask=), True = editable.  The mask holds every
+    stretch of --edit-frames (on the listed joints, or all; on edit['clip'] alone, or on every clip inside its own frames) except the
+    frames of --edit-pin, which are kept -- the motion is re-synthesised around those poses and passes through them."""
+    import numpy as np
+    B, N = timeline.shape[0], timeline.shape[3]
+    joints = None
+    if edit.get("joints"):
+        joints = np.zeros(cfg.njoints, bool)
+        joints[edit["joints"]] = True
+    pins = edit.get("pins", [])
+    one = long_form.keyframe_mask(N, pins, cfg, within=edit["stretches"])[0]            # [J, F, N]: the stretches without the pinned frames
+    if joints is not None:
+        one &= joints[:, None, None]
+    mask = np.broadcast_to(one, (B,) + one.shape).copy()
+    if edit.get("clip") is not None:
+        if not 0 <= edit["clip"] < B:
+            raise SystemExit(f"--edit-clip takes a clip of the batch, 0 .. {B - 1}")
+        mask[np.arange(B) != edit["clip"]] = False
+    for b in range(B if frames is not None else 0):                                    # a ragged batch: every clip inside its own frames
+        mask[b, :, :, int(frames[b]):] = False
+    form = dict(compact=True) if edit.get("clip") is not None or lengths is not None else {}
+    if lengths is not None:
+        form["audio_lengths"] = lengths
+    torch.manual_seed(377)
+    t0 = time.perf_counter()
+    edited, ran, _ = long_form.edit_long(diffusion, model, timeline, None, audio, y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim",
+                                         skip_timesteps=80, return_windows=True, mask=mask, **form)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    kept = ~torch.from_numpy(mask).to(timeline.device)
+    assert torch.equal(edited[kept], timeline[kept]) and bool(torch.isfinite(edited).all())
+    what = f"{len(ran)} of {W} windows ran ({ran})"
+    if form:            # the compact form returns its plan: (w, rows)
+        what = f"{sum(len(rows) for _, rows in ran)} clip-windows of {B * W} ran ({', '.join(f'window {w}: clips {rows}' for w, rows in ran)})"
+    print(f"one edit of the stretches {edit['stretches']}{'' if not pins else ' around the pinned frames ' + str(pins)}"
+          f"{'' if joints is None else ' on joints ' + str(edit['joints'])}{'' if edit.get('clip') is None else ' of clip ' + str(edit['clip'])}: "
+          f"{what} in {dt * 1e3:.1f} ms; {int((edited != timeline).sum())} of {timeline.numel()} values changed, every other one -- the pinned "
+          f"frames included -- kept bit for bit")
 
 
 def main_long_ragged(seconds, noise_source, drop_finished=False, edit=None):

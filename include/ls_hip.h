@@ -390,7 +390,8 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a);
  * one that ran is not resampled even where its conditioning frames changed (widen the range to have it resampled), and a clip whose
  * range misses a running window runs in it with every element kept.
  * Not built: PLMS, const_noise, dump_steps; in this dense form also handles of ls_long_prepare_ragged and encoding only the edited
- * windows' audio -- both are ls_long_prepare_edit / ls_long_edit_compact's, further down. */
+ * windows' audio -- both are ls_long_prepare_edit / ls_long_edit_compact's, further down.  Anything but one rectangle per clip --
+ * several stretches, pinned keyframes, joints per stretch -- is ls_long_edit_mask's, further down still. */
 typedef struct ls_long_edit_args {
     int32_t sampler;            /* LS_SAMPLER_DDPM | LS_SAMPLER_DDIM                                                  */
     int32_t noise_mode;         /* LS_NOISE_TAPE | LS_NOISE_PHILOX                                                    */
@@ -519,6 +520,43 @@ int ls_long_edit_plan_compact(int32_t batch, int32_t n_windows, int32_t T, int32
 int ls_long_prepare_edit(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths, const int32_t* frame_lo,
                          const int32_t* frame_hi, const unsigned char* channels);
 int ls_long_edit_compact(ls_handle* h, const ls_long_edit_compact_args* a, struct ls_sag* sag, const float* text_features);
+
+/* ---- Timeline edits by ELEMENT MASK: "editable" as data instead of as a rectangle.  element_mask is bytes [B, J*F, N] in the
+ * timeline's own layout (N = T + (W - 1) S), NON-ZERO = EDITABLE (the opposite of ls_sample's inpaint_mask, which marks what is kept).
+ * Element (b, c, f) of window w is editable iff element_mask[b, c, w S + f] != 0 and frame w S + f is OWNED by w ([0, T) for w = 0,
+ * [w S + n_pre_seq, w S + T) otherwise: ls_long_edit's ownership, unchanged); with frames (a ragged batch) additionally w < W_b, and a
+ * set byte at or beyond frames[b] is LS_EINVAL, not a silent no-op.  Several stretches per clip, pinned keyframes inside a stretch,
+ * other joints in other stretches and single features are all masks.  The range form is the mask channels[b][c] && lo_b <= n < hi_b:
+ * for such a mask every output of every entry below equals the range entry's bit for bit.
+ *
+ * The entries are the range entries' own code with the rule swapped: the same window body, the same three kernels (k_edit_gather /
+ * k_edit_start / k_edit_scatter read the mask when EditArgs::emask is set), the same captured loop, graph cache, tapes, PHILOX keys,
+ * outputs and refusals.  A kept element of the timeline is never written, nor is a kept element of a scripted edit's start plane.
+ *   - ls_long_edit_plan_mask (no handle, no GPU): ls_long_edit_plan_compact for a HOST mask [batch, n_channels, N]; the pair (b, w) is
+ *     in the plan iff the clip has a set byte on a frame w owns.  Every plan, range or mask, is made from such PAIR FLAGS [W][B] by one
+ *     definition.  LS_EINVAL: a set byte at or beyond frames[b], a frames[b] that is no stitched length, a capacity that does not
+ *     hold the plan.  An empty plan is no error here; the run entries refuse it.
+ *   - ls_long_edit_mask: ls_long_edit / ls_long_edit_sag (sag and text_features both NULL or both set).  The dense form: window w runs
+ *     iff SOME clip has an editable element in it.
+ *   - ls_long_prepare_edit_mask / ls_long_edit_compact_mask: ls_long_prepare_edit / ls_long_edit_compact.  The run must be given the
+ *     mask the prepare was given: its pair flags are made again and compared (LS_EINVAL where they differ -- the plan, which is all the
+ *     prepare derived from the mask, would be another one).  A handle prepared by ls_long_prepare_edit is refused here and vice versa.
+ *   - in all of them a->frame_lo, a->frame_hi and a->channels must be NULL (LS_EINVAL otherwise), and element_mask is a DEVICE
+ *     pointer iff on_device (a->on_device; c->on_device for the prepare).  A host mask is reduced to flags by a host loop and uploaded
+ *     once per call.  A device mask stays on the device: k_edit_mask_pairs (ls_chain.hip; one workgroup per clip-window) reduces it
+ *     and only W * B flag bytes cross to the host -- the one host wait a device mask adds ahead of the call's own.
+ *   - ls_long_edit_mask_pairs: those flags [n_windows, batch] to the HOST as the kernel computes them (a host mask is uploaded first),
+ *     geometry from the handle (after ls_commit_weights).  A set byte beyond frames[b]: flag 2 and LS_EINVAL.
+ * Not built: masks on a running stream or pool, bit-packed masks, soft (fractional) masks. */
+int ls_long_edit_plan_mask(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const unsigned char* element_mask, int32_t n_channels,
+                           const int32_t* frames, int32_t* windows, int32_t* counts, int32_t window_capacity, int32_t* rows,
+                           int32_t row_capacity, int32_t* n_windows_run, int32_t* n_pairs);
+int ls_long_edit_mask(ls_handle* h, const ls_long_edit_args* a, struct ls_sag* sag, const float* text_features, const unsigned char* element_mask);
+int ls_long_prepare_edit_mask(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths, const unsigned char* element_mask);
+int ls_long_edit_compact_mask(ls_handle* h, const ls_long_edit_compact_args* a, struct ls_sag* sag, const float* text_features,
+                              const unsigned char* element_mask);
+int ls_long_edit_mask_pairs(ls_handle* h, const unsigned char* element_mask, int32_t on_device, int32_t batch, int32_t n_windows,
+                            const int32_t* frames, unsigned char* flags);
 
 /* ---- Streaming long-form synthesis: the chain of ls_long_sample, fed audio in chunks of any size.  Window w runs as soon as its last
  * sample has arrived (audio_stride * w + audio_len <= samples fed), conditioned on the last n_pre_seq poses of window w - 1 (window 0:

@@ -252,7 +252,7 @@ class LsResampleStreamPushArgs(C.Structure):
 
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
-           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_edit_sag", "ls_long_edit_plan_compact", "ls_long_prepare_edit", "ls_long_edit_compact", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_long_pool_plan", "ls_long_pool_open", "ls_long_pool_join", "ls_long_pool_push", "ls_long_pool_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
+           "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_edit_sag", "ls_long_edit_plan_compact", "ls_long_prepare_edit", "ls_long_edit_compact", "ls_long_edit_plan_mask", "ls_long_edit_mask", "ls_long_prepare_edit_mask", "ls_long_edit_compact_mask", "ls_long_edit_mask_pairs", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_long_pool_plan", "ls_long_pool_open", "ls_long_pool_join", "ls_long_pool_push", "ls_long_pool_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
            "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_set_row_keys", "ls_long_pool_keyed", "ls_long_pool_set_key", "ls_long_pool_keys", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
@@ -339,6 +339,12 @@ def load_library(build_if_missing: bool = True):
                                               c_i32p, C.c_int32, c_i32p, C.c_int32, c_i32p, c_i32p]
     lib.ls_long_prepare_edit.argtypes = [C.c_void_p, C.POINTER(LsLongCond), C.c_void_p, c_i32p, c_i32p, C.c_void_p]
     lib.ls_long_edit_compact.argtypes = [C.c_void_p, C.POINTER(LsLongEditCompactArgs), C.c_void_p, C.c_void_p]
+    lib.ls_long_edit_plan_mask.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, c_i32p, c_i32p, c_i32p, C.c_int32,
+                                           c_i32p, C.c_int32, c_i32p, c_i32p]
+    lib.ls_long_edit_mask.argtypes = [C.c_void_p, C.POINTER(LsLongEditArgs), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ls_long_prepare_edit_mask.argtypes = [C.c_void_p, C.POINTER(LsLongCond), C.c_void_p, C.c_void_p]
+    lib.ls_long_edit_compact_mask.argtypes = [C.c_void_p, C.POINTER(LsLongEditCompactArgs), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ls_long_edit_mask_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, C.c_void_p]
     lib.ls_long_stream_plan.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_i64p, c_i64p]
     lib.ls_long_stream_open.argtypes = [C.c_void_p, C.POINTER(LsLongStreamCond)]
     lib.ls_long_stream_push.argtypes = [C.c_void_p, C.POINTER(LsLongStreamPushArgs)]
@@ -664,6 +670,33 @@ def long_edit_plan_compact(lo, hi, n_windows, channels=None, frames=None, n_fram
     wins, counts, rows = np.empty(max(nw.value, 1), np.int32), np.empty(max(nw.value, 1), np.int32), np.empty(max(npairs.value, 1), np.int32)
     if lib.ls_long_edit_plan_compact(*head, ptr(wins), ptr(counts), int(nw.value), ptr(rows), int(npairs.value), C.byref(nw), C.byref(npairs)) != 0:
         raise EngineError("ls_long_edit_plan_compact failed")
+    offs = np.concatenate([[0], np.cumsum(counts[:nw.value])]).astype(np.int64)
+    return [(int(wins[e]), rows[offs[e]:offs[e + 1]].copy()) for e in range(nw.value)]
+
+
+def long_edit_plan_mask(mask, n_windows, frames=None, n_frames=34, n_pre=4):
+    """ls_long_edit_plan_mask (no GPU needed): the clip-windows a timeline edit by ELEMENT MASK runs, as ``long_edit_plan_compact``'s
+    list of ``(w, rows)``.  ``mask``: host bool / bytes [B, C, N] with N = n_frames + (n_windows - 1)(n_frames - n_pre), non-zero =
+    editable; the pair (b, w) is in the plan iff clip b has a set element on a frame w owns.  ``frames``: int [B] or None.  A set
+    element at or beyond ``frames[b]`` or a ``frames[b]`` that is no stitched length raises ``ValueError``."""
+    lib = load_library()
+    W = int(n_windows)
+    N = int(n_frames) + (W - 1) * (int(n_frames) - int(n_pre))
+    m = np.asarray(mask)
+    if m.ndim != 3 or m.shape[0] < 1 or m.shape[1] < 1 or m.shape[2] != N:
+        raise ValueError(f"an element mask is [B, channels, {N}] for {W} windows, got {list(m.shape)}")
+    m = np.ascontiguousarray(m != 0, dtype=np.uint8)
+    B = int(m.shape[0])
+    fr = None if frames is None else np.ascontiguousarray(np.asarray(frames).reshape(-1), dtype=np.int32)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(c_i32p)      # noqa: E731
+    nw, npairs = C.c_int32(), C.c_int32()
+    head = (B, W, int(n_frames), int(n_pre), m.ctypes.data_as(C.c_void_p), int(m.shape[1]), ptr(fr))
+    if (fr is not None and fr.shape != (B,)) or lib.ls_long_edit_plan_mask(*head, None, None, 0, None, 0, C.byref(nw), C.byref(npairs)) != 0:
+        raise ValueError(f"an element mask must not be set at or beyond its clip's frames[b] (frames[b] = 34 + 30 k, at most {N}); frames "
+                         f"{None if fr is None else fr.tolist()} for {W} windows")
+    wins, counts, rows = np.empty(max(nw.value, 1), np.int32), np.empty(max(nw.value, 1), np.int32), np.empty(max(npairs.value, 1), np.int32)
+    if lib.ls_long_edit_plan_mask(*head, ptr(wins), ptr(counts), int(nw.value), ptr(rows), int(npairs.value), C.byref(nw), C.byref(npairs)) != 0:
+        raise EngineError("ls_long_edit_plan_mask failed")
     offs = np.concatenate([[0], np.cumsum(counts[:nw.value])]).astype(np.int64)
     return [(int(wins[e]), rows[offs[e]:offs[e + 1]].copy()) for e in range(nw.value)]
 
@@ -1340,7 +1373,7 @@ class Engine(_Handle):
 
     def long_edit(self, timeline, frame_lo, frame_hi, channels=None, sampler=LS_SAMPLER_DDIM, x_init=None, eps_tape=None, noise_tape=None,
                   inpaint_noise=None, inpaint_noised=False, skip_timesteps=0, eta=0.0, philox_seed=None, sample_offset=0, use_graph=True,
-                  clip_denoised=False, two_pass_always=False, device_out=False, return_windows=False, sag=None, text_features=None):
+                  clip_denoised=False, two_pass_always=False, device_out=False, return_windows=False, sag=None, text_features=None, mask=None):
         """Re-synthesise the frames [frame_lo[b], frame_hi[b]) (host int [B]) of ``timeline`` [B, J, F, T + (W-1)(T-n_pre)] on the
         channels ``channels`` (host bytes [B, J*F]; None = all) with the conditioning of the last ``long_prepare`` (ls_long_edit): only
         the windows of ``long_edit_plan`` run, everything else is kept bit for bit.  TAPE mode takes the draws of those We windows,
@@ -1350,28 +1383,38 @@ class Engine(_Handle):
 
         ``sag`` (a SagEngine) with ``text_features`` [W, B, D]: the scripted edit (ls_long_edit_sag) -- every window that runs starts
         from the decoder's output on its editable elements and from its slice elsewhere, at every ``skip_timesteps``; rows of
-        ``text_features`` for windows that do not run are not read.  One without the other is the engine's to refuse."""
+        ``text_features`` for windows that do not run are not read.  One without the other is the engine's to refuse.
+
+        ``mask`` (bool / bytes [B, J*F, N], host or device, NON-ZERO = EDITABLE; with ``frame_lo = frame_hi = channels = None``): the
+        edit by element mask (ls_long_edit_mask) -- window w runs iff some clip has a set element on a frame it owns
+        (``long_edit_mask_plan``), and everything above holds with that rule in place of the rectangle."""
         B, W, D = self.batch, self.n_windows, self.D
         npre = int(self.cfg.n_pre_seq)
         n_frames = self.T + (W - 1) * (self.T - npre)
-        lo = np.ascontiguousarray(np.asarray(frame_lo).reshape(-1), dtype=np.int32)
-        hi = np.ascontiguousarray(np.asarray(frame_hi).reshape(-1), dtype=np.int32)
-        assert lo.shape == hi.shape == (B,), (lo.shape, hi.shape, B)
-        ch = None
+        lo = hi = ch = None
+        if frame_lo is not None or mask is None:        # together with a mask: the engine's to refuse
+            lo = np.ascontiguousarray(np.asarray(frame_lo).reshape(-1), dtype=np.int32)
+            hi = np.ascontiguousarray(np.asarray(frame_hi).reshape(-1), dtype=np.int32)
+            assert lo.shape == hi.shape == (B,), (lo.shape, hi.shape, B)
         if channels is not None:
             ch = np.ascontiguousarray(np.asarray(channels).reshape(B, self.J * self.F) != 0, dtype=np.uint8)
-        try:        # a clip without a selected channel is not edited; what the plan cannot take is the engine's to refuse
-            plan = long_edit_plan(lo, np.where(ch.any(axis=1), hi, lo) if ch is not None else hi, W, self.T, npre)
-        except ValueError:
-            plan = []
+        if mask is not None:
+            plan = [w for w, _ in self.long_edit_mask_plan(mask, W)]
+        else:
+            try:        # a clip without a selected channel is not edited; what the plan cannot take is the engine's to refuse
+                plan = long_edit_plan(lo, np.where(ch.any(axis=1), hi, lo) if ch is not None else hi, W, self.T, npre)
+            except ValueError:
+                plan = []
         We = len(plan)
-        m = self._marshal([timeline, x_init, eps_tape, noise_tape, inpaint_noise, text_features], device_out)
+        m = self._marshal([timeline, x_init, eps_tape, noise_tape, inpaint_noise, text_features, mask], device_out)
         a = LsLongEditArgs()
         n_exec = self._chain_sampler(a, m, sampler, skip_timesteps, use_graph, clip_denoised, two_pass_always, eta)
         a.inpaint_noised = int(bool(inpaint_noised))
-        a.frame_lo, a.frame_hi = lo.ctypes.data_as(c_i32p), hi.ctypes.data_as(c_i32p)
+        if lo is not None:
+            a.frame_lo, a.frame_hi = lo.ctypes.data_as(c_i32p), hi.ctypes.data_as(c_i32p)
         if ch is not None:
             a.channels = ch.ctypes.data_as(C.c_void_p)
+        maskp = m.u8(mask, (B, self.J * self.F, n_frames))
         self._chain_noise(a, m, We, n_exec, x_init, eps_tape, noise_tape, philox_seed, sample_offset,
                           inpaint_noise=inpaint_noise if inpaint_noised else None)
         shape = (B, self.J, self.F, n_frames)
@@ -1390,7 +1433,9 @@ class Engine(_Handle):
         a.windows_run, a.windows_capacity, a.n_windows_run = ran.ctypes.data_as(c_i32p), W, C.pointer(n_ran)
         text = m.f32(text_features, (W, B, D))
         m.ready()
-        if sag is None and text_features is None:
+        if mask is not None:
+            self._check(self.lib.ls_long_edit_mask(self.h, C.byref(a), None if sag is None else sag.h, text, maskp), "ls_long_edit_mask")
+        elif sag is None and text_features is None:
             self._check(self.lib.ls_long_edit(self.h, C.byref(a)), "ls_long_edit")
         else:
             self._check(self.lib.ls_long_edit_sag(self.h, C.byref(a), None if sag is None else sag.h, text), "ls_long_edit_sag")
@@ -1398,62 +1443,106 @@ class Engine(_Handle):
         assert ran == plan, (ran, plan)
         return (out, ran, windows) if return_windows else (out, ran)
 
+    def long_edit_mask_pairs(self, mask, n_windows, frames=None):
+        """The pair flags of an element mask as the device computes them (ls_long_edit_mask_pairs; ``k_edit_mask_pairs``): uint8
+        [n_windows, B], 1 where clip b has a set element on a frame window w owns.  ``mask``: bool / bytes [B, J*F, N], host (uploaded
+        first) or device (read in place; only the flags cross to the host).  ``frames``: host int [B] or None.  A set element at or
+        beyond ``frames[b]`` is the engine's to refuse."""
+        B, W = int(mask.shape[0]), int(n_windows)
+        n_frames = self.T + (W - 1) * (self.T - int(self.cfg.n_pre_seq))
+        fr = None if frames is None else np.ascontiguousarray(np.asarray(frames).reshape(-1), dtype=np.int32)
+        assert fr is None or fr.shape == (B,), (fr.shape, B)
+        m = _Marshal(self.device, mask, stream=self._stream)
+        maskp = m.u8(mask, (B, self.J * self.F, n_frames))
+        flags = np.zeros((W, B), np.uint8)
+        m.ready()
+        self._check(self.lib.ls_long_edit_mask_pairs(self.h, maskp, int(m.on_device), B, W, None if fr is None else fr.ctypes.data_as(c_i32p),
+                                                     flags.ctypes.data_as(C.c_void_p)), "ls_long_edit_mask_pairs")
+        return flags
+
+    def long_edit_mask_plan(self, mask, n_windows, frames=None):
+        """The clip-windows of an element mask [B, J*F, N] as ``[(w, rows)]``.  A host mask: ``long_edit_plan_mask`` (no GPU; a set
+        element beyond ``frames[b]``: ``ValueError``).  A device mask stays on the device: the plan is read off the W * B pair flags
+        of ``long_edit_mask_pairs``, as the engine reads it."""
+        if _is_cuda(mask):
+            flags = self.long_edit_mask_pairs(mask, n_windows, frames)
+            return [(w, np.flatnonzero(flags[w]).astype(np.int32)) for w in range(int(n_windows)) if flags[w].any()]
+        host = mask.detach().numpy() if hasattr(mask, "detach") else np.asarray(mask)
+        return long_edit_plan_mask(host, n_windows, frames, self.T, int(self.cfg.n_pre_seq))
+
     def long_prepare_edit(self, audio, seed_poses, vid_indices, scale, frame_lo, frame_hi, channels=None, emo=None, n_windows=1,
-                          encoder_chunk=None, audio_lengths=None):
+                          encoder_chunk=None, audio_lengths=None, mask=None):
         """Once-per-call stage of a COMPACT timeline edit (ls_long_prepare_edit): the conditioning of ``long_prepare``, everything in
         the caller's clip order, plus the edit's ranges (host int [B]) and ``channels`` (host bytes [B, J*F]; None = all).  Only the
         clip-windows of ``long_edit_plan_compact`` go through the WavEncoder.  ``audio_lengths`` (host [B]): clips of different
         lengths -- ``n_windows`` is the longest clip's count, a clip has only its own windows, and ``audio`` at and beyond a clip's
-        length is never read.  Sets ``edit_plan``: the list of ``(w, rows)``."""
+        length is never read.  Sets ``edit_plan``: the list of ``(w, rows)``.
+
+        ``mask`` (bool / bytes [B, J*F, N], host or device, non-zero = editable; with ``frame_lo = frame_hi = channels = None``): the
+        plan of the element mask (ls_long_prepare_edit_mask; ``long_edit_mask_plan``)."""
         B, W = int(audio.shape[0]), int(n_windows)
         npre = int(self.cfg.n_pre_seq)
-        lo = np.ascontiguousarray(np.asarray(frame_lo).reshape(-1), dtype=np.int32)
-        hi = np.ascontiguousarray(np.asarray(frame_hi).reshape(-1), dtype=np.int32)
-        assert lo.shape == hi.shape == (B,), (lo.shape, hi.shape, B)
-        ch = None if channels is None else np.ascontiguousarray(np.asarray(channels).reshape(B, self.J * self.F) != 0, dtype=np.uint8)
+        assert mask is None or (frame_lo is None and frame_hi is None and channels is None), "the prepare takes a mask or ranges"
+        lo = hi = ch = None
+        if mask is None:
+            lo = np.ascontiguousarray(np.asarray(frame_lo).reshape(-1), dtype=np.int32)
+            hi = np.ascontiguousarray(np.asarray(frame_hi).reshape(-1), dtype=np.int32)
+            assert lo.shape == hi.shape == (B,), (lo.shape, hi.shape, B)
+            ch = None if channels is None else np.ascontiguousarray(np.asarray(channels).reshape(B, self.J * self.F) != 0, dtype=np.uint8)
         lens = frames = None
         if audio_lengths is not None:
             lens = np.ascontiguousarray(np.asarray(audio_lengths).reshape(-1), dtype=np.int64)
             assert lens.shape == (B,), (lens.shape, B)
-        m = _Marshal(self.device, audio, seed_poses, vid_indices, scale, emo, stream=self._stream)
+        m = _Marshal(self.device, audio, seed_poses, vid_indices, scale, emo, mask, stream=self._stream)
         c = LsLongCond(B, W, int(m.on_device), int(encoder_chunk or 0), int(audio.shape[1]), m.f32(audio, (B, int(audio.shape[1]))),
                        m.f32(seed_poses, (B, self.J, self.F, npre)), m.i64(vid_indices, (B,)), m.i64(emo, (W, B)), m.f32(scale, (B,)))
+        maskp = m.u8(mask, (B, self.J * self.F, self.T + (W - 1) * (self.T - npre)))
         m.ready()
-        self._check(self.lib.ls_long_prepare_edit(self.h, C.byref(c), None if lens is None else lens.ctypes.data_as(C.c_void_p),
-                                                  lo.ctypes.data_as(c_i32p), hi.ctypes.data_as(c_i32p),
-                                                  None if ch is None else ch.ctypes.data_as(C.c_void_p)), "ls_long_prepare_edit")
+        lensp = None if lens is None else lens.ctypes.data_as(C.c_void_p)
+        if mask is not None:
+            self._check(self.lib.ls_long_prepare_edit_mask(self.h, C.byref(c), lensp, maskp), "ls_long_prepare_edit_mask")
+        else:
+            self._check(self.lib.ls_long_prepare_edit(self.h, C.byref(c), lensp, lo.ctypes.data_as(c_i32p), hi.ctypes.data_as(c_i32p),
+                                                      None if ch is None else ch.ctypes.data_as(C.c_void_p)), "ls_long_prepare_edit")
         if lens is not None:        # frames per clip: what ls_long_plan_drop's window counts stitch to
             row, wins, _ = long_plan_drop(lens, self.cfg.audio_len)
             frames = np.empty(B, np.int32)
             frames[row] = self.T + (wins - 1) * (self.T - npre)
-        self.edit_plan = long_edit_plan_compact(lo, hi, W, ch, frames, self.T, npre)
+        self.edit_plan = self.long_edit_mask_plan(mask, W, frames) if mask is not None else long_edit_plan_compact(lo, hi, W, ch, frames, self.T, npre)
         self.batch, self.n_windows, self.window_batches = B, W, None
 
     def long_edit_compact(self, timeline, frame_lo, frame_hi, channels=None, sampler=LS_SAMPLER_DDIM, x_init=None, eps_tape=None,
                           noise_tape=None, inpaint_noise=None, inpaint_noised=False, skip_timesteps=0, eta=0.0, philox_seed=None,
                           sample_offset=0, use_graph=True, clip_denoised=False, two_pass_always=False, device_out=False, return_windows=False,
-                          sag=None, text_features=None):
+                          sag=None, text_features=None, mask=None):
         """The planned clip-windows of the last ``long_prepare_edit`` (ls_long_edit_compact): window w is one sampling call at batch
         ``len(rows)`` on its rows.  ``frame_lo`` / ``frame_hi`` / ``channels`` repeat the prepared ones.  TAPE mode takes packed
         tapes, window after window at its own batch: ``x_init`` [n_pairs, J, F, T], flat ``eps_tape`` / ``noise_tape`` /
         ``inpaint_noise`` holding per window [n_exec, 2, A_w, D] / [n_exec, A_w, J, F, T]; PHILOX mode ``philox_seed`` (clip b of
         window w draws at ``sample_offset + b + (w << 48)``).  ``sag`` with ``text_features`` [W, B, D] in clip order: the scripted
-        edit.  Returns (a new timeline, the plan ``[(w, rows)]``) and, with ``return_windows``, the raw samples [n_pairs, J, F, T]."""
+        edit.  Returns (a new timeline, the plan ``[(w, rows)]``) and, with ``return_windows``, the raw samples [n_pairs, J, F, T].
+
+        ``mask`` (with ``frame_lo = frame_hi = channels = None``): the element mask ``long_prepare_edit(mask=)`` was given
+        (ls_long_edit_compact_mask); one whose clip-windows differ from the prepared ones is the engine's to refuse."""
         B, W, D = self.batch, self.n_windows, self.D
         n_frames = self.T + (W - 1) * (self.T - int(self.cfg.n_pre_seq))
-        lo = np.ascontiguousarray(np.asarray(frame_lo).reshape(-1), dtype=np.int32)
-        hi = np.ascontiguousarray(np.asarray(frame_hi).reshape(-1), dtype=np.int32)
-        assert lo.shape == hi.shape == (B,), (lo.shape, hi.shape, B)
+        lo = hi = None
+        if frame_lo is not None or mask is None:        # together with a mask: the engine's to refuse
+            lo = np.ascontiguousarray(np.asarray(frame_lo).reshape(-1), dtype=np.int32)
+            hi = np.ascontiguousarray(np.asarray(frame_hi).reshape(-1), dtype=np.int32)
+            assert lo.shape == hi.shape == (B,), (lo.shape, hi.shape, B)
         ch = None if channels is None else np.ascontiguousarray(np.asarray(channels).reshape(B, self.J * self.F) != 0, dtype=np.uint8)
         plan = getattr(self, "edit_plan", None) or []
         n_pairs = sum(len(rows) for _, rows in plan)
-        m = self._marshal([timeline, x_init, eps_tape, noise_tape, inpaint_noise, text_features], device_out)
+        m = self._marshal([timeline, x_init, eps_tape, noise_tape, inpaint_noise, text_features, mask], device_out)
         a = LsLongEditCompactArgs()
         n_exec = self._chain_sampler(a, m, sampler, skip_timesteps, use_graph, clip_denoised, two_pass_always, eta)
         a.inpaint_noised = int(bool(inpaint_noised))
-        a.frame_lo, a.frame_hi = lo.ctypes.data_as(c_i32p), hi.ctypes.data_as(c_i32p)
+        if lo is not None:
+            a.frame_lo, a.frame_hi = lo.ctypes.data_as(c_i32p), hi.ctypes.data_as(c_i32p)
         if ch is not None:
             a.channels = ch.ctypes.data_as(C.c_void_p)
+        maskp = m.u8(mask, (B, self.J * self.F, n_frames))
         self._chain_noise(a, m, n_pairs, n_exec, x_init, eps_tape, noise_tape, philox_seed, sample_offset, packed=True)
         if philox_seed is None and inpaint_noised:
             a.inpaint_noise = m.f32(inpaint_noise, (n_pairs * n_exec * self.J * self.F * self.T,))
@@ -1473,7 +1562,10 @@ class Engine(_Handle):
         a.windows_run, a.windows_capacity, a.n_windows_run, a.rows_run = ran.ctypes.data_as(c_i32p), W, C.pointer(n_ran), C.pointer(n_rows)
         text = m.f32(text_features, (W, B, D))
         m.ready()
-        self._check(self.lib.ls_long_edit_compact(self.h, C.byref(a), None if sag is None else sag.h, text), "ls_long_edit_compact")
+        if mask is not None:
+            self._check(self.lib.ls_long_edit_compact_mask(self.h, C.byref(a), None if sag is None else sag.h, text, maskp), "ls_long_edit_compact_mask")
+        else:
+            self._check(self.lib.ls_long_edit_compact(self.h, C.byref(a), None if sag is None else sag.h, text), "ls_long_edit_compact")
         ran = [int(w) for w in ran[:int(n_ran.value)]]
         self.rows_run = int(n_rows.value)          # the clip-windows that ran (ls_long_edit_compact_args.rows_run)
         assert ran == [w for w, _ in plan] and self.rows_run == n_pairs, (ran, plan, self.rows_run)

@@ -16,6 +16,9 @@
 // k_edit_start puts the SAG decoder's output under the editable elements of the init plane (ls_long_edit_sag): at most 7.4 KB TED, 77 KB BEAT.
 // The COMPACT edit (ls_long_edit_compact) runs the same three kernels on the rows of a table, one per clip that has an editable element
 // in the window, and k_cond_gather moves those clips' held conditioning into the rows.
+// An edit by ELEMENT MASK (ls_long_edit_mask and its kin) runs the same three kernels again: "editable" is read from a byte per element of
+// the timeline (EditArgs::emask) in place of the clip's rectangle, through the one rule edit_editable; k_edit_mask_pairs reduces a mask
+// that lives on the device to one flag per (clip, window), which is all of it the host's plan needs.
 // A streaming SESSION (ls_long_pool_push; ls_long_stream_push: the pool whose slots move together) keeps the hand-off per slot:
 // k_pool_gather and k_pool_scatter (at the end) move one round's active slots -- a window of audio out of each slot's circular ring,
 // its hand-off poses, its held conditioning -- into and out of the compact rows a sampling call at that batch reads.
@@ -84,9 +87,20 @@ hipError_t launch_chain_window(const ChainArgs& a, int B, hipStream_t st) {
 // (motion, mask) + n_pre*(KPP + JF) (+ T*JF init plane with skip_timesteps > 0): 15.7 KB TED, 163 KB BEAT with the init plane.
 // k_edit_scatter: read T*JF + JF bytes + 8, write the editable elements (at most (T - n_pre)*JF, window 0: T*JF) (+ T*JF raw window): at
 // most 11.0 KB TED, 115 KB BEAT.
-__device__ __forceinline__ bool edit_editable(const EditArgs& a, int lo, int hi, bool chan, int f) {
+// "Editable" is DATA: with an element mask (EditArgs::emask, bytes [clips][JF][T_total] in the timeline's own layout; ls_long_edit_mask)
+// element (c, f) of window w is editable iff its byte is set and w owns the frame; without one the rule is the rectangle it always was
+// (the clip's range times its channel bytes).  One rule for the three kernels below in both of their forms; the mask, like the ranges,
+// belongs to the CLIP (rows[r]), not to the row.  A mask costs JF * T byte loads per clip in place of JF + 8 bytes.
+struct EditRule { const unsigned char* em; const unsigned char* ch; int lo, hi; };
+__device__ __forceinline__ EditRule edit_rule(const EditArgs& a, int b) {
+    if (a.emask) return {a.emask + (size_t)b * a.JF * a.T_total + a.w * (a.T - a.n_pre), nullptr, 0, 0};
+    return {nullptr, a.chan + (size_t)b * a.JF, a.range[2 * b], a.range[2 * b + 1]};
+}
+__device__ __forceinline__ bool edit_editable(const EditArgs& a, const EditRule& r, int c, int f) {
+    if (a.w != 0 && f < a.n_pre) return false;      // the frame is owned by the window before
+    if (r.em) return r.em[(size_t)c * a.T_total + f] != 0;
     const int t = a.w * (a.T - a.n_pre) + f;
-    return chan && t >= lo && t < hi && (a.w == 0 || f >= a.n_pre);
+    return r.ch[c] != 0 && t >= r.lo && t < r.hi;
 }
 
 __global__ __launch_bounds__(256) void k_edit_gather(const EditArgs a) {
@@ -109,14 +123,13 @@ __global__ __launch_bounds__(256) void k_edit_gather(const EditArgs a) {
         pre = sp;
     }
     __syncthreads();
-    const int lo = a.range[2 * b], hi = a.range[2 * b + 1];
-    const unsigned char* ch = a.chan + (size_t)b * JF;
+    const EditRule rule = edit_rule(a, b);
     float* mo = a.motion + (size_t)r * T * JF;
     float* mk = a.maskf + (size_t)r * T * JF;
     for (int i = tid; i < T * JF; i += 256) {
         const int f = i / JF, c = i - f * JF;
         mo[i] = tile[f * ld + c];
-        mk[i] = edit_editable(a, lo, hi, ch[c] != 0, f) ? 0.f : 1.f;      // inpainting_mask: true = keep the given motion
+        mk[i] = edit_editable(a, rule, c, f) ? 0.f : 1.f;      // inpainting_mask: true = keep the given motion
     }
     float* fu = a.feat_u + (size_t)r * T * a.KPP;
     for (int i = tid; i < npre * a.KPP; i += 256) {
@@ -137,15 +150,14 @@ __global__ __launch_bounds__(256) void k_edit_scatter(const EditArgs a) {
     const float* src = a.sample + (size_t)r * T * JF;
     for (int i = tid; i < T * JF; i += 256) tile[(i / JF) * ld + i % JF] = src[i];
     __syncthreads();
-    const int lo = a.range[2 * b], hi = a.range[2 * b + 1];
-    const unsigned char* ch = a.chan + (size_t)b * JF;
+    const EditRule rule = edit_rule(a, b);
     float* tl = a.timeline + (size_t)b * JF * a.T_total + a.w * (T - a.n_pre);
     float* wd = a.window ? a.window + (size_t)r * JF * T : nullptr;
     for (int i = tid; i < JF * T; i += 256) {
         const int c = i / T, f = i - c * T;
         const float v = tile[f * ld + c];
         if (wd) wd[i] = v;
-        if (edit_editable(a, lo, hi, ch[c] != 0, f)) tl[(size_t)c * a.T_total + f] = v;
+        if (edit_editable(a, rule, c, f)) tl[(size_t)c * a.T_total + f] = v;
     }
 }
 
@@ -157,20 +169,19 @@ __global__ __launch_bounds__(256) void k_edit_scatter(const EditArgs a) {
 __global__ __launch_bounds__(256) void k_edit_start(const EditArgs a, const float* __restrict__ sag_out) {
     const int r = blockIdx.x, tid = threadIdx.x, JF = a.JF, T = a.T;
     const int b = a.rows ? a.rows[r] : r;
-    const int lo = a.range[2 * b], hi = a.range[2 * b + 1];
-    const unsigned char* ch = a.chan + (size_t)b * JF;
+    const EditRule rule = edit_rule(a, b);
     const float* src = sag_out + (size_t)r * JF * T;
     float* init = a.init + (size_t)r * JF * T;
     for (int i = tid; i < JF * T; i += 256) {
         const int c = i / T, f = i - c * T;
-        if (edit_editable(a, lo, hi, ch[c] != 0, f)) init[i] = src[i];
+        if (edit_editable(a, rule, c, f)) init[i] = src[i];
     }
 }
 
 static bool edit_args_ok(const EditArgs& a, int B, int rows) {
     const size_t lds = (size_t)rows * (a.JF | 1) * sizeof(float);
     return B >= 1 && lds <= 64 * 1024 && a.n_pre >= 1 && a.n_pre <= a.T && a.w >= 0 && (long long)a.w * (a.T - a.n_pre) + a.T <= a.T_total &&
-           a.timeline && a.range && a.chan;
+           a.timeline && (a.emask || (a.range && a.chan));
 }
 hipError_t launch_edit_gather(const EditArgs& a, int B, hipStream_t st) {
     const int rows = a.T + (a.w == 0 ? a.n_pre : 0);
@@ -186,6 +197,39 @@ hipError_t launch_edit_start(const EditArgs& a, const float* sag_out, int B, hip
 hipError_t launch_edit_scatter(const EditArgs& a, int B, hipStream_t st) {
     if (!edit_args_ok(a, B, a.T) || !a.sample) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_edit_scatter, dim3(B), dim3(256), (size_t)a.T * (a.JF | 1) * sizeof(float), st, a);
+    return hipGetLastError();
+}
+
+// The pair flags of an element mask that lives on the device (ls_long_edit_mask and its kin): flags[w][b] = 1 iff clip b has a set byte
+// on a frame window w OWNS ([0, T) for w = 0, [w S + n_pre, w S + T) otherwise), any of the JF channels.  With frames [B] (a ragged
+// batch) clip b has the windows w < W_b = (frames[b] - T) / S + 1 only; a set byte on a frame a later window owns is the caller's
+// error and is reported as 2, never dropped.  Only these W * B bytes cross to the host; the plan is made from them there
+// (edit_plan_of_flags, ls_chain_plan.cpp).  One workgroup per (clip, window): thread i walks the owned frames of a channel, so a wave
+// reads consecutive bytes along N; the OR goes through one ballot per wave and four LDS words, one thread stores the byte.  Reads
+// JF * (T - n_pre) bytes per pair (window 0: JF * T), writes one; not measured.
+__global__ __launch_bounds__(256) void k_edit_mask_pairs(const unsigned char* __restrict__ mask, const int* __restrict__ frames,
+                                                         unsigned char* __restrict__ flags, int B, int JF, int T, int n_pre, int T_total) {
+    __shared__ int any_wave[4];
+    const int b = blockIdx.x, w = blockIdx.y, tid = threadIdx.x, S = T - n_pre;
+    const int f0 = w ? n_pre : 0, nf = T - f0;
+    const unsigned char* m = mask + (size_t)b * JF * T_total + w * S + f0;
+    int any = 0;
+    for (int i = tid; i < JF * nf; i += 256) {
+        const int c = i / nf, f = i - c * nf;
+        any |= m[(size_t)c * T_total + f];
+    }
+    const unsigned long long vote = __ballot(any != 0);
+    if ((tid & 63) == 0) any_wave[tid >> 6] = vote != 0ull;
+    __syncthreads();
+    if (tid == 0) {
+        const bool set = (any_wave[0] | any_wave[1] | any_wave[2] | any_wave[3]) != 0;
+        const bool has = !frames || w < (frames[b] - T) / S + 1;
+        flags[(size_t)w * B + b] = set ? (has ? 1 : 2) : 0;
+    }
+}
+hipError_t launch_edit_mask_pairs(const unsigned char* mask, const int* frames, unsigned char* flags, int B, int W, int JF, int T, int n_pre, hipStream_t st) {
+    if (!mask || !flags || B < 1 || W < 1 || W > 65535 || JF < 1 || n_pre < 1 || T <= n_pre) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_edit_mask_pairs, dim3(B, W), dim3(256), 0, st, mask, frames, flags, B, JF, T, n_pre, T + (W - 1) * (T - n_pre));
     return hipGetLastError();
 }
 

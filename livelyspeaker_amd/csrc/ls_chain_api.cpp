@@ -222,6 +222,34 @@ int chain_finish(ls_handle* h, const ChainCall& cc, std::initializer_list<Egress
     return LS_OK;
 }
 
+// ---- the element mask of a timeline edit ----------------------------------------------------------------------------------------
+// The pair flags [W][B] of an element mask [B][JF][T_total] (ls_long_edit_mask and its kin), from which every mask plan is made.  A
+// host mask is reduced by the host loop (edit_mask_flags).  A device mask stays where it is: k_edit_mask_pairs reduces it on the
+// handle's stream and W * B bytes come back -- the one host wait a device mask adds to a call.  frames [B] (HOST, nullable): a ragged
+// batch.  LS_EINVAL: a set byte at or beyond its clip's frames[b].
+int mask_pair_flags(ls_handle* h, const char* entry, const unsigned char* mask, int on_device, int B, int W, const int32_t* frames,
+                    std::vector<unsigned char>& flags) {
+    const int JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq;
+    if (!on_device) {
+        if (edit_mask_flags(B, W, T, npre, JF, mask, frames, flags) != LS_OK)
+            return fail(h, LS_EINVAL, "%s: the element mask has a set byte at or beyond its clip's own frames[b]", entry);
+        return LS_OK;
+    }
+    if (W > 65535) return fail(h, LS_EINVAL, "%s: a device mask of %d windows (at most 65535)", entry, W);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc;
+    if (frames && (rc = upload(h, h->lg_edit_frames, frames, (size_t)B * sizeof(int32_t))) != LS_OK) return rc;
+    HIPCHK(h, h->lg_edit_flags.ensure((size_t)W * B));
+    HIPCHK(h, launch_edit_mask_pairs(mask, frames ? static_cast<const int*>(h->lg_edit_frames.p) : nullptr, static_cast<unsigned char*>(h->lg_edit_flags.p),
+                                     B, W, JF, T, npre, h->stream));
+    flags.assign((size_t)W * B, 0);
+    HIPCHK(h, hipMemcpyAsync(flags.data(), h->lg_edit_flags.p, flags.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (unsigned char f : flags)
+        if (f > 1) return fail(h, LS_EINVAL, "%s: the element mask has a set byte at or beyond its clip's own frames[b]", entry);
+    return LS_OK;
+}
+
 // ---- streaming sessions ---------------------------------------------------------------------------------------------------------
 // A session pool, and a stream: the pool whose slots were all joined at the open and are fed and closed together (pl_lockstep).
 int session_is_open(ls_handle* h, const char* entry, bool stream) {
@@ -783,7 +811,11 @@ int ls_long_sample(ls_handle* h, const ls_long_sample_args* a) {
 // editable elements over the init plane behind the decode: the loop starts from q_sample(where(keep, slice, decoder output)) at
 // every skip_timesteps >= 0.  The start's q_sample is enqueued ahead of the captured loop (begin_loop), so the loop's key is the
 // unscripted edit's.  ls_long_edit is this entry with no decoder.
-int ls_long_edit_sag(ls_handle* h, const ls_long_edit_args* a, ls_sag* sag, const float* text_features) {
+//
+// With an ELEMENT MASK (ls_long_edit_mask) the same code runs: the windows come from the mask's pair flags in place of the ranges,
+// and the three edit kernels read the mask (EditArgs::emask) in place of the rectangle.  Nothing else differs; the range entries
+// are the mask-less case.
+static int long_edit_run(ls_handle* h, const ls_long_edit_args* a, ls_sag* sag, const float* text_features, const unsigned char* emask, bool mask_form) {
     if (!h || !a) return fail(h, LS_EINVAL, "ls_long_edit: null argument");
     if (sag && !text_features) return fail(h, LS_EINVAL, "ls_long_edit_sag: sag without text_features");
     if (text_features && !sag) return fail(h, LS_EINVAL, "ls_long_edit_sag: text_features without sag");
@@ -791,14 +823,28 @@ int ls_long_edit_sag(ls_handle* h, const ls_long_edit_args* a, ls_sag* sag, cons
     if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_edit before ls_set_schedule");
     if (h->lg_ragged) return fail(h, LS_EUNSUPPORTED, "ls_long_edit: a handle prepared by ls_long_prepare_ragged is not edited (ragged batches are not built)");
     if (!a->timeline) return fail(h, LS_EINVAL, "ls_long_edit: null timeline");
-    if (!a->frame_lo || !a->frame_hi) return fail(h, LS_EINVAL, "ls_long_edit: null frame_lo / frame_hi");
+    if (mask_form && !emask) return fail(h, LS_EINVAL, "ls_long_edit_mask: null element_mask");
+    if (mask_form && (a->frame_lo || a->frame_hi || a->channels))
+        return fail(h, LS_EINVAL, "ls_long_edit_mask: the element mask and frame_lo / frame_hi / channels exclude each other");
+    if (!mask_form && (!a->frame_lo || !a->frame_hi)) return fail(h, LS_EINVAL, "ls_long_edit: null frame_lo / frame_hi");
     if (a->windows_capacity < 0 || (a->windows_capacity > 0 && !a->windows_run)) return fail(h, LS_EINVAL, "ls_long_edit: windows_capacity without windows_run");
     const int B = h->B, W = h->lg_W, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, od = a->on_device;
     const int Tt = T + (W - 1) * (T - npre);
     // per clip [lo, hi) and the channel bytes; a clip with no channel selected is not edited
     std::vector<int32_t> lo((size_t)B), hi((size_t)B), range((size_t)2 * B), flags((size_t)W);
     std::vector<unsigned char> chan((size_t)B * JF, 1);
-    for (int b = 0; b < B; ++b) {
+    int rc;
+    int32_t We = 0;
+    if (mask_form) {        // window w runs iff some clip has an editable element in it
+        std::vector<unsigned char> pairs;
+        if ((rc = mask_pair_flags(h, "ls_long_edit_mask", emask, od, B, W, nullptr, pairs)) != LS_OK) return rc;
+        for (int w = 0; w < W; ++w) {
+            for (int b = 0; b < B; ++b) flags[(size_t)w] |= pairs[(size_t)w * B + b] ? 1 : 0;
+            We += flags[(size_t)w];
+        }
+        if (We < 1) return fail(h, LS_EINVAL, "ls_long_edit_mask: no window holds an editable element (the mask is empty)");
+    }
+    for (int b = 0; b < B && !mask_form; ++b) {
         lo[(size_t)b] = a->frame_lo[b]; hi[(size_t)b] = a->frame_hi[b];
         if (lo[(size_t)b] < 0 || lo[(size_t)b] > hi[(size_t)b] || hi[(size_t)b] > Tt)
             return fail(h, LS_EINVAL, "ls_long_edit: clip %d: frames [%d, %d) are no range inside [0, %d]", b, lo[(size_t)b], hi[(size_t)b], Tt);
@@ -809,11 +855,11 @@ int ls_long_edit_sag(ls_handle* h, const ls_long_edit_args* a, ls_sag* sag, cons
         }
         range[(size_t)2 * b] = lo[(size_t)b]; range[(size_t)2 * b + 1] = hi[(size_t)b];
     }
-    int32_t We = 0;
-    if (ls_long_edit_plan(B, W, T, npre, lo.data(), hi.data(), flags.data(), &We) != LS_OK) return fail(h, LS_EINVAL, "ls_long_edit: bad frame ranges");
-    if (We < 1) return fail(h, LS_EINVAL, "ls_long_edit: no window holds an editable element (every range is empty)");
+    if (!mask_form) {
+        if (ls_long_edit_plan(B, W, T, npre, lo.data(), hi.data(), flags.data(), &We) != LS_OK) return fail(h, LS_EINVAL, "ls_long_edit: bad frame ranges");
+        if (We < 1) return fail(h, LS_EINVAL, "ls_long_edit: no window holds an editable element (every range is empty)");
+    }
     ChainCall cc;
-    int rc;
     if ((rc = chain_args(h, "ls_long_edit", a, true, cc)) != LS_OK) return rc;
     const bool noised = a->inpaint_noised != 0, beat = h->cfg.n_prefix_tokens == 2;
     if (cc.tape && noised && !a->inpaint_noise) return fail(h, LS_EINVAL, "TAPE mode with inpaint_noised needs inpaint_noise");
@@ -822,9 +868,14 @@ int ls_long_edit_sag(ls_handle* h, const ls_long_edit_args* a, ls_sag* sag, cons
     hipStream_t st = h->stream;
     const size_t nelem = (size_t)B * JF * T, nx = nelem * sizeof(float);
     const size_t per_e = (size_t)cc.n_exec * 2 * B * kD, per_n = (size_t)cc.n_exec * nelem;      // floats per window: eps tape, noise tape
-    // the ranges and channel bytes: one upload per call
-    if ((rc = upload(h, h->lg_edit_range, range.data(), range.size() * sizeof(int32_t))) != LS_OK) return rc;
-    if ((rc = upload(h, h->lg_edit_chan, chan.data(), chan.size())) != LS_OK) return rc;
+    // the ranges and channel bytes, or a host caller's mask: one upload per call (a device mask is read where it is)
+    if (!mask_form) {
+        if ((rc = upload(h, h->lg_edit_range, range.data(), range.size() * sizeof(int32_t))) != LS_OK) return rc;
+        if ((rc = upload(h, h->lg_edit_chan, chan.data(), chan.size())) != LS_OK) return rc;
+    } else if (!od) {
+        if ((rc = ingest(h, h->lg_edit_mask, emask, (size_t)B * JF * Tt, 0)) != LS_OK) return rc;
+        emask = static_cast<const unsigned char*>(h->lg_edit_mask.p);
+    }
     const float *xs = a->x_init, *es = a->eps_tape, *ns = a->noise_tape, *iz = noised ? a->inpaint_noise : nullptr;
     if (cc.tape && !od) {
         if ((rc = ingest(h, h->lg_x, xs, We * nx, 0)) != LS_OK || (rc = ingest(h, h->lg_eps, es, We * per_e * sizeof(float), 0)) != LS_OK ||
@@ -848,7 +899,8 @@ int ls_long_edit_sag(ls_handle* h, const ls_long_edit_args* a, ls_sag* sag, cons
     if ((rc = ensure_pinned(h, h->inp_maskf, nx)) != LS_OK || (rc = ensure_pinned(h, h->inp_motion, nx)) != LS_OK) return rc;
     EditArgs ea{};
     ea.timeline = tl; ea.seed = h->lg_seed.f();
-    ea.range = static_cast<const int*>(h->lg_edit_range.p); ea.chan = static_cast<const unsigned char*>(h->lg_edit_chan.p);
+    if (mask_form) ea.emask = emask;
+    else { ea.range = static_cast<const int*>(h->lg_edit_range.p); ea.chan = static_cast<const unsigned char*>(h->lg_edit_chan.p); }
     ea.feat_u = h->feat_u.f(); ea.origin_x = h->origin_x.f(); ea.init = from_image ? h->lg_init.f() : nullptr;
     ea.JF = JF; ea.T = T; ea.KPP = h->KPP; ea.n_pre = npre; ea.T_total = Tt;
     cc.wa.init_image = ea.init;
@@ -878,16 +930,47 @@ int ls_long_edit_sag(ls_handle* h, const ls_long_edit_args* a, ls_sag* sag, cons
     return LS_OK;
 }
 
-int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) { return ls_long_edit_sag(h, a, nullptr, nullptr); }
+int ls_long_edit_sag(ls_handle* h, const ls_long_edit_args* a, ls_sag* sag, const float* text_features) {
+    return long_edit_run(h, a, sag, text_features, nullptr, false);
+}
+int ls_long_edit(ls_handle* h, const ls_long_edit_args* a) { return long_edit_run(h, a, nullptr, nullptr, nullptr, false); }
+int ls_long_edit_mask(ls_handle* h, const ls_long_edit_args* a, ls_sag* sag, const float* text_features, const unsigned char* element_mask) {
+    return long_edit_run(h, a, sag, text_features, element_mask, true);
+}
+
+// The pair flags of an element mask as k_edit_mask_pairs computes them (ls_hip.h): a host mask is uploaded first, so the kernel runs
+// either way.  flags: HOST [n_windows][batch].
+int ls_long_edit_mask_pairs(ls_handle* h, const unsigned char* element_mask, int32_t on_device, int32_t batch, int32_t n_windows, const int32_t* frames,
+                            unsigned char* flags) {
+    if (!h || !element_mask || !flags) return fail(h, LS_EINVAL, "ls_long_edit_mask_pairs: null argument");
+    if (!h->committed) return fail(h, LS_ESTATE, "ls_long_edit_mask_pairs before ls_commit_weights");
+    const int T = h->T, npre = h->cfg.n_pre_seq;
+    if (batch < 1 || n_windows < 1 || npre < 1 || T <= npre) return fail(h, LS_EINVAL, "ls_long_edit_mask_pairs: batch and n_windows must be >= 1");
+    const long long S = T - npre, Tt = T + (long long)(n_windows - 1) * S;
+    for (int b = 0; b < batch && frames; ++b)
+        if (frames[b] < T || frames[b] > Tt || (frames[b] - T) % S) return fail(h, LS_EINVAL, "ls_long_edit_mask_pairs: frames[%d] = %d is no stitched length", b, frames[b]);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc;
+    if (!on_device) {
+        if ((rc = ingest(h, h->lg_edit_mask, element_mask, (size_t)batch * h->JF * (size_t)Tt, 0)) != LS_OK) return rc;
+        element_mask = static_cast<const unsigned char*>(h->lg_edit_mask.p);
+    }
+    std::vector<unsigned char> got;
+    rc = mask_pair_flags(h, "ls_long_edit_mask_pairs", element_mask, 1, batch, n_windows, frames, got);
+    if (got.size() == (size_t)n_windows * batch) memcpy(flags, got.data(), got.size());
+    return rc;
+}
 
 // Once-per-call stage of a COMPACT timeline edit (ls_hip.h): the plan of ls_long_edit_plan_compact from the ranges, the channels and
 // (audio_lengths) the clips' own window counts; the per-clip conditioning held at batch B in the caller's order; the WavEncoder over
 // the plan's clip-windows alone, gathered by k_long_gather_clips from a (clip, window) table and stored packed in plan order; every
 // window batch planned under the single-pass decision of its own rows and its workspaces sized, so that nothing a captured loop holds
 // by address moves once ls_long_edit_compact has begun.  The speaker style is ls_long_edit_compact's (per window batch).
-int ls_long_prepare_edit(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths, const int32_t* frame_lo, const int32_t* frame_hi,
-                         const unsigned char* channels) {
-    if (!h || !c || !frame_lo || !frame_hi) return fail(h, LS_EINVAL, "ls_long_prepare_edit: null argument");
+// With an ELEMENT MASK (ls_long_prepare_edit_mask; host or device as c->on_device says) the plan comes from the mask's pair flags
+// through the same edit_plan_of_flags; the flags are kept, and the run's mask must give them again.
+static int long_prepare_edit_run(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths, const int32_t* frame_lo, const int32_t* frame_hi,
+                                 const unsigned char* channels, const unsigned char* emask, bool mask_form) {
+    if (!h || !c || (mask_form ? !emask : (!frame_lo || !frame_hi))) return fail(h, LS_EINVAL, "ls_long_prepare_edit: null argument");
     int rc;
     if ((rc = check_cond(h, "ls_long_prepare_edit", c->batch, &c->n_windows, c->audio_samples >= 1 && c->encoder_chunk >= 0,
                          c->audio && c->seed_poses && c->vid_indices && c->scale, h->cfg.n_prefix_tokens != 2 || c->emo)) != LS_OK) return rc;
@@ -911,11 +994,19 @@ int ls_long_prepare_edit(ls_handle* h, const ls_long_cond* c, const int64_t* aud
     const int32_t* fr = audio_lengths ? frames.data() : nullptr;
     const unsigned char* ch = channels ? chan.data() : nullptr;
     int32_t We = 0, np = 0;
-    if (ls_long_edit_plan_compact(B, W, T, npre, frame_lo, frame_hi, ch, JF, fr, nullptr, nullptr, 0, nullptr, 0, &We, &np) != LS_OK)
-        return fail(h, LS_EINVAL, "ls_long_prepare_edit: a frame range is no range inside its clip's timeline (0 <= lo <= hi <= %s)", audio_lengths ? "frames[b]" : "T_total");
-    if (np < 1) return fail(h, LS_EINVAL, "ls_long_prepare_edit: no window holds an editable element (every range is empty)");
+    std::vector<unsigned char> pairs;       // the mask form: its pair flags [W][B]
+    if (mask_form) {
+        if ((rc = mask_pair_flags(h, "ls_long_prepare_edit_mask", emask, od, B, W, fr, pairs)) != LS_OK) return rc;
+        if (edit_plan_of_flags(B, W, pairs.data(), nullptr, nullptr, 0, nullptr, 0, &We, &np) != LS_OK) return fail(h, LS_EINVAL, "ls_long_prepare_edit_mask: the plan does not fit");
+        if (np < 1) return fail(h, LS_EINVAL, "ls_long_prepare_edit_mask: no window holds an editable element (the mask is empty)");
+    } else {
+        if (ls_long_edit_plan_compact(B, W, T, npre, frame_lo, frame_hi, ch, JF, fr, nullptr, nullptr, 0, nullptr, 0, &We, &np) != LS_OK)
+            return fail(h, LS_EINVAL, "ls_long_prepare_edit: a frame range is no range inside its clip's timeline (0 <= lo <= hi <= %s)", audio_lengths ? "frames[b]" : "T_total");
+        if (np < 1) return fail(h, LS_EINVAL, "ls_long_prepare_edit: no window holds an editable element (every range is empty)");
+    }
     std::vector<int32_t> cw((size_t)We), cn((size_t)We), crows((size_t)np), coff((size_t)We + 1, 0);
-    if (ls_long_edit_plan_compact(B, W, T, npre, frame_lo, frame_hi, ch, JF, fr, cw.data(), cn.data(), We, crows.data(), np, &We, &np) != LS_OK)
+    if ((mask_form ? edit_plan_of_flags(B, W, pairs.data(), cw.data(), cn.data(), We, crows.data(), np, &We, &np)
+                   : ls_long_edit_plan_compact(B, W, T, npre, frame_lo, frame_hi, ch, JF, fr, cw.data(), cn.data(), We, crows.data(), np, &We, &np)) != LS_OK)
         return fail(h, LS_EINVAL, "ls_long_prepare_edit: ls_long_edit_plan_compact failed");
     for (int e = 0; e < We; ++e) coff[(size_t)e + 1] = coff[(size_t)e] + cn[(size_t)e];
     std::vector<int> table((size_t)np * 2);
@@ -924,7 +1015,7 @@ int ls_long_prepare_edit(ls_handle* h, const ls_long_cond* c, const int64_t* aud
     // the editable test of the kernels: a clip without a selected channel is not edited
     std::vector<int32_t> range((size_t)2 * B);
     std::vector<unsigned char> chan_dev((size_t)B * JF, 1);
-    for (int b = 0; b < B; ++b) {
+    for (int b = 0; b < B && !mask_form; ++b) {
         range[(size_t)2 * b] = frame_lo[b]; range[(size_t)2 * b + 1] = frame_hi[b];
         if (channels) memcpy(&chan_dev[(size_t)b * JF], &chan[(size_t)b * JF], (size_t)JF);
     }
@@ -988,33 +1079,53 @@ int ls_long_prepare_edit(ls_handle* h, const ls_long_cond* c, const int64_t* aud
     if ((rc = finish_prepare(h, B)) != LS_OK) return rc;
     h->lg_W = W; h->lg_L = (size_t)c->audio_samples;
     h->lg_cw = cw; h->lg_cn = cn; h->lg_coff = coff; h->lg_crows = crows; h->lg_cscale = sc;
-    h->lg_clo.assign(frame_lo, frame_lo + B); h->lg_chi.assign(frame_hi, frame_hi + B); h->lg_cchan = chan;
+    if (mask_form) { h->lg_clo.clear(); h->lg_chi.clear(); h->lg_cchan.clear(); }
+    else { h->lg_clo.assign(frame_lo, frame_lo + B); h->lg_chi.assign(frame_hi, frame_hi + B); h->lg_cchan = chan; }
+    h->lg_cflags = pairs; h->lg_cframes = frames;
     h->lg_compact = true;       // lg_prepared stays false: ls_long_sample and ls_long_edit need the features of all W * B clip-windows
     return LS_OK;
 }
 
+int ls_long_prepare_edit(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths, const int32_t* frame_lo, const int32_t* frame_hi,
+                         const unsigned char* channels) {
+    return long_prepare_edit_run(h, c, audio_lengths, frame_lo, frame_hi, channels, nullptr, false);
+}
+int ls_long_prepare_edit_mask(ls_handle* h, const ls_long_cond* c, const int64_t* audio_lengths, const unsigned char* element_mask) {
+    return long_prepare_edit_run(h, c, audio_lengths, nullptr, nullptr, nullptr, element_mask, true);
+}
+
 // The compact timeline edit (ls_long_edit_compact_args in ls_hip.h): per planned window k_cond_gather, the style at the window's
 // batch, k_edit_gather on the window's row table, the window body (keyed PHILOX rows: the clip's index, not the row's), k_edit_scatter.
-// One wait at the end.
-int ls_long_edit_compact(ls_handle* h, const ls_long_edit_compact_args* a, ls_sag* sag, const float* text_features) {
+// One wait at the end.  With an ELEMENT MASK (ls_long_edit_compact_mask) the kernels read the mask in place of the rectangle; the
+// mask's pair flags are made again (host loop, or k_edit_mask_pairs and W * B bytes back) and must be the prepared ones.
+static int long_edit_compact_run(ls_handle* h, const ls_long_edit_compact_args* a, ls_sag* sag, const float* text_features, const unsigned char* emask,
+                                 bool mask_form) {
     if (!h || !a) return fail(h, LS_EINVAL, "ls_long_edit_compact: null argument");
     if (sag && !text_features) return fail(h, LS_EINVAL, "ls_long_edit_compact: sag without text_features");
     if (text_features && !sag) return fail(h, LS_EINVAL, "ls_long_edit_compact: text_features without sag");
     if (!h->lg_compact) return fail(h, LS_ESTATE, "ls_long_edit_compact before ls_long_prepare_edit");
     if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_edit_compact before ls_set_schedule");
     if (!a->timeline) return fail(h, LS_EINVAL, "ls_long_edit_compact: null timeline");
-    if (!a->frame_lo || !a->frame_hi) return fail(h, LS_EINVAL, "ls_long_edit_compact: null frame_lo / frame_hi");
+    if (mask_form && !emask) return fail(h, LS_EINVAL, "ls_long_edit_compact_mask: null element_mask");
+    if (mask_form && (a->frame_lo || a->frame_hi || a->channels))
+        return fail(h, LS_EINVAL, "ls_long_edit_compact_mask: the element mask and frame_lo / frame_hi / channels exclude each other");
+    if (!mask_form && (!a->frame_lo || !a->frame_hi)) return fail(h, LS_EINVAL, "ls_long_edit_compact: null frame_lo / frame_hi");
     if (a->windows_capacity < 0 || (a->windows_capacity > 0 && !a->windows_run)) return fail(h, LS_EINVAL, "ls_long_edit_compact: windows_capacity without windows_run");
     const int B = h->B, W = h->lg_W, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, od = a->on_device;
     const int Tt = T + (W - 1) * (T - npre), We = (int)h->lg_cw.size(), np = h->lg_coff[(size_t)We];
-    if ((int)h->lg_clo.size() != B || !std::equal(h->lg_clo.begin(), h->lg_clo.end(), a->frame_lo) || !std::equal(h->lg_chi.begin(), h->lg_chi.end(), a->frame_hi))
+    int rc;
+    if (mask_form) {
+        if (h->lg_cflags.size() != (size_t)W * B) return fail(h, LS_EINVAL, "ls_long_edit_compact_mask: the handle was prepared by ls_long_prepare_edit (ranges), not by ls_long_prepare_edit_mask");
+        std::vector<unsigned char> pairs;
+        if ((rc = mask_pair_flags(h, "ls_long_edit_compact_mask", emask, od, B, W, h->lg_cframes.empty() ? nullptr : h->lg_cframes.data(), pairs)) != LS_OK) return rc;
+        if (pairs != h->lg_cflags) return fail(h, LS_EINVAL, "ls_long_edit_compact_mask: the element mask differs from the one ls_long_prepare_edit_mask planned (other clip-windows hold its editable elements)");
+    } else if ((int)h->lg_clo.size() != B || !std::equal(h->lg_clo.begin(), h->lg_clo.end(), a->frame_lo) || !std::equal(h->lg_chi.begin(), h->lg_chi.end(), a->frame_hi))
         return fail(h, LS_EINVAL, "ls_long_edit_compact: the frame ranges differ from the ones ls_long_prepare_edit planned");
-    if ((a->channels != nullptr) != !h->lg_cchan.empty())
+    if (!mask_form && (a->channels != nullptr) != !h->lg_cchan.empty())
         return fail(h, LS_EINVAL, "ls_long_edit_compact: the channels differ from the ones ls_long_prepare_edit planned");
-    for (size_t i = 0; i < h->lg_cchan.size(); ++i)
+    for (size_t i = 0; i < h->lg_cchan.size() && !mask_form; ++i)
         if ((a->channels[i] != 0) != (h->lg_cchan[i] != 0)) return fail(h, LS_EINVAL, "ls_long_edit_compact: the channels differ from the ones ls_long_prepare_edit planned");
     ChainCall cc;
-    int rc;
     if ((rc = chain_args(h, "ls_long_edit_compact", a, true, cc)) != LS_OK) return rc;
     const bool noised = a->inpaint_noised != 0, beat = h->cfg.n_prefix_tokens == 2;
     if (cc.tape && noised && !a->inpaint_noise) return fail(h, LS_EINVAL, "TAPE mode with inpaint_noised needs inpaint_noise");
@@ -1041,6 +1152,10 @@ int ls_long_edit_compact(ls_handle* h, const ls_long_edit_compact_args* a, ls_sa
         if ((rc = ingest(h, h->lg_timeline, a->timeline, (size_t)B * JF * Tt * sizeof(float), 0)) != LS_OK) return rc;
         tl = h->lg_timeline.f();
         if (wd) { HIPCHK(h, h->lg_windows.ensure(np * per_x * sizeof(float))); wd = h->lg_windows.f(); }
+        if (mask_form) {        // a host caller's mask: one upload per call
+            if ((rc = ingest(h, h->lg_edit_mask, emask, (size_t)B * JF * Tt, 0)) != LS_OK) return rc;
+            emask = static_cast<const unsigned char*>(h->lg_edit_mask.p);
+        }
     }
     const bool from_image = a->skip_timesteps > 0 || sag;
     if (from_image) HIPCHK(h, h->lg_init.ensure(nxA));
@@ -1079,7 +1194,8 @@ int ls_long_edit_compact(ls_handle* h, const ls_long_edit_compact_args* a, ls_sa
     }
     EditArgs ea{};
     ea.timeline = tl; ea.seed = h->lg_seed.f();
-    ea.range = static_cast<const int*>(h->lg_edit_range.p); ea.chan = static_cast<const unsigned char*>(h->lg_edit_chan.p);
+    if (mask_form) ea.emask = emask;
+    else { ea.range = static_cast<const int*>(h->lg_edit_range.p); ea.chan = static_cast<const unsigned char*>(h->lg_edit_chan.p); }
     ea.feat_u = h->feat_u.f(); ea.origin_x = h->origin_x.f(); ea.init = from_image ? h->lg_init.f() : nullptr;
     ea.motion = h->inp_motion.f(); ea.maskf = h->inp_maskf.f();
     ea.JF = JF; ea.T = T; ea.KPP = h->KPP; ea.n_pre = npre; ea.T_total = Tt;
@@ -1142,6 +1258,13 @@ int ls_long_edit_compact(ls_handle* h, const ls_long_edit_compact_args* a, ls_sa
     if (a->n_windows_run) *a->n_windows_run = We;
     if (a->rows_run) *a->rows_run = np;
     return LS_OK;
+}
+
+int ls_long_edit_compact(ls_handle* h, const ls_long_edit_compact_args* a, ls_sag* sag, const float* text_features) {
+    return long_edit_compact_run(h, a, sag, text_features, nullptr, false);
+}
+int ls_long_edit_compact_mask(ls_handle* h, const ls_long_edit_compact_args* a, ls_sag* sag, const float* text_features, const unsigned char* element_mask) {
+    return long_edit_compact_run(h, a, sag, text_features, element_mask, true);
 }
 
 // Opening a stream (ls_long_stream_cond in ls_hip.h): a session of `batch` slots, every slot joined from the caller's arrays

@@ -1,8 +1,10 @@
 // The plans of the chained-window engine (ls_chain_api.cpp): which clips run which window of a ragged call, which windows a timeline
-// edit runs (and which clips run each of them in its compact form), which windows a push of a stream runs, which rounds a push of a session pool runs and at which keys its rows draw, which copies feed the slots' rings.
-// Integer arithmetic on host arrays, no
-// HIP in here: each is the single definition for its entry and for Python (long_form.py), and tests/chain_plan_main.cpp and
-// tests/pool_plan_main.cpp, tests/pool_keys_main.cpp and tests/edit_plan_main.cpp run them on their edges under the host sanitizers.
+// edit runs (and which clips run each of them in its compact form), which windows a push of a stream runs, which rounds a push of a
+// session pool runs and at which keys its rows draw, which copies feed the slots' rings.  Every edit plan is made from PAIR FLAGS
+// (edit_plan_of_flags): the range form and the element-mask form (ls_long_edit_plan_mask) differ only in how the flags come about.
+// Integer arithmetic on host arrays, no HIP in here: each is the single definition for its entry and for Python (long_form.py), and
+// tests/chain_plan_main.cpp, tests/pool_plan_main.cpp, tests/pool_keys_main.cpp, tests/edit_plan_main.cpp and
+// tests/edit_mask_plan_main.cpp run them on their edges under the host sanitizers.
 #include <algorithm>
 #include <cstdint>
 #include <vector>
@@ -46,6 +48,78 @@ void feed_copies(int S, int R, const int* pos, const long long* from, const int*
     }
 }
 
+// ---- The plan of a timeline edit FROM PAIR FLAGS: flags [W][B], non-zero where clip b has an editable element in window w.  The one
+// definition every edit entry shares -- a range, a host mask and a device mask (k_edit_mask_pairs) all reduce to flags first: the
+// windows that run are those some clip flags, ascending; the rows of a window are its flagged clips, ascending; counts per window,
+// n_pairs = sum.  Capacities as in ls_long_edit_plan_compact: null arrays with zero capacities count alone, LS_EINVAL where an
+// array does not hold the plan.  Declared in ls_handle.h.
+int edit_plan_of_flags(int B, int W, const unsigned char* flags, int32_t* windows, int32_t* counts, int32_t window_capacity, int32_t* rows,
+                       int32_t row_capacity, int32_t* n_windows_run, int32_t* n_pairs) {
+    long long nw = 0, np = 0;
+    for (int w = 0; w < W; ++w) {
+        const unsigned char* fw = flags + (size_t)w * B;
+        int n = 0;
+        for (int b = 0; b < B; ++b) {
+            if (!fw[b]) continue;
+            if (rows) { if (np + n >= row_capacity) return LS_EINVAL; rows[np + n] = b; }
+            ++n;
+        }
+        if (n == 0) continue;
+        if (windows) { if (nw >= window_capacity) return LS_EINVAL; windows[nw] = w; counts[nw] = n; }
+        ++nw; np += n;
+        if (np > INT32_MAX) return LS_EINVAL;
+    }
+    *n_windows_run = (int32_t)nw;
+    *n_pairs = (int32_t)np;
+    return LS_OK;
+}
+
+// the windows of each clip: all W, or with frames (a ragged batch) W_b = (frames[b] - T) / S + 1; false: a frames[b] that is no
+// stitched length T + k S with 0 <= k < W
+static bool clip_windows(int B, int W, int T, int n_pre, const int32_t* frames, std::vector<int>& wb) {
+    const long long S = T - n_pre, Tt = T + (long long)(W - 1) * S;
+    wb.assign((size_t)B, W);
+    for (int b = 0; b < B && frames; ++b) {
+        if (frames[b] < T || frames[b] > Tt || (frames[b] - T) % S) return false;
+        wb[(size_t)b] = (int)((frames[b] - T) / S) + 1;
+    }
+    return true;
+}
+
+// The flags of the RANGE form: clip b, window w iff [lo_b, hi_b) meets the frames w owns, the clip has a selected channel (any[b]) and
+// w < wb[b].  The ranges are the caller's to check.
+static void range_flags(int B, int W, int T, int n_pre, const int32_t* lo, const int32_t* hi, const char* any, const int* wb, std::vector<unsigned char>& flags) {
+    const long long S = T - n_pre;
+    flags.assign((size_t)W * B, 0);
+    for (int w = 0; w < W; ++w) {
+        const long long own_lo = w ? w * S + n_pre : 0, own_hi = w * S + T;
+        for (int b = 0; b < B; ++b)
+            flags[(size_t)w * B + b] = (!any || any[b]) && w < wb[b] && (lo[b] > own_lo ? lo[b] : own_lo) < (hi[b] < own_hi ? hi[b] : own_hi);
+    }
+}
+
+// The flags of a HOST element mask [B][JF][T + (W - 1) S]: the OR over the frames w owns and all channels -- what k_edit_mask_pairs
+// computes for a mask on the device.  Every frame has one owner, so one pass over the mask's rows does it.  LS_EINVAL: a frames[b]
+// that is no stitched length, or a set byte at or beyond frames[b].  Declared in ls_handle.h.
+int edit_mask_flags(int B, int W, int T, int n_pre, int JF, const unsigned char* mask, const int32_t* frames, std::vector<unsigned char>& flags) {
+    std::vector<int> wb;
+    if (!clip_windows(B, W, T, n_pre, frames, wb)) return LS_EINVAL;
+    const long long S = T - n_pre, Tt = T + (long long)(W - 1) * S;
+    flags.assign((size_t)W * B, 0);
+    for (int b = 0; b < B; ++b) {
+        const long long most = T + (long long)(wb[(size_t)b] - 1) * S;
+        for (int c = 0; c < JF; ++c) {
+            const unsigned char* m = mask + ((size_t)b * JF + c) * (size_t)Tt;
+            for (long long n = 0; n < Tt; ++n) {
+                if (!m[n]) continue;
+                if (n >= most) return LS_EINVAL;
+                flags[(size_t)(n < T ? 0 : (n - n_pre) / S) * B + b] = 1;      // the owner of frame n
+            }
+        }
+    }
+    return LS_OK;
+}
+
 }  // namespace ls
 
 extern "C" {
@@ -71,14 +145,16 @@ int ls_long_plan_drop(int32_t batch, int32_t audio_len, const int64_t* audio_len
 int ls_long_edit_plan(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const int32_t* lo, const int32_t* hi, int32_t* window_flags,
                       int32_t* n_out) {
     if (batch < 1 || n_windows < 1 || n_pre < 1 || T <= n_pre || !lo || !hi || !n_out) return LS_EINVAL;
-    const long long S = T - n_pre, Tt = T + (long long)(n_windows - 1) * S;
+    const long long Tt = T + (long long)(n_windows - 1) * (T - n_pre);
     for (int b = 0; b < batch; ++b)
         if (lo[b] < 0 || lo[b] > hi[b] || hi[b] > Tt) return LS_EINVAL;
+    std::vector<unsigned char> flags;
+    const std::vector<int> wb((size_t)batch, n_windows);
+    ls::range_flags(batch, n_windows, T, n_pre, lo, hi, nullptr, wb.data(), flags);
     int n = 0;
     for (int w = 0; w < n_windows; ++w) {
-        const long long own_lo = w ? w * S + n_pre : 0, own_hi = w * S + T;
         bool run = false;
-        for (int b = 0; b < batch && !run; ++b) run = (lo[b] > own_lo ? lo[b] : own_lo) < (hi[b] < own_hi ? hi[b] : own_hi);
+        for (int b = 0; b < batch && !run; ++b) run = flags[(size_t)w * batch + b] != 0;
         if (window_flags) window_flags[w] = run ? 1 : 0;
         n += run ? 1 : 0;
     }
@@ -98,40 +174,34 @@ int ls_long_edit_plan_compact(int32_t batch, int32_t n_windows, int32_t T, int32
     if (batch < 1 || n_windows < 1 || n_pre < 1 || T <= n_pre || !lo || !hi || !n_windows_run || !n_pairs) return LS_EINVAL;
     if ((channels && n_channels < 1) || window_capacity < 0 || row_capacity < 0) return LS_EINVAL;
     if ((window_capacity > 0 && (!windows || !counts)) || (row_capacity > 0 && !rows)) return LS_EINVAL;
-    const long long S = T - n_pre, Tt = T + (long long)(n_windows - 1) * S;
-    std::vector<int> wb((size_t)batch, n_windows);
+    const long long Tt = T + (long long)(n_windows - 1) * (T - n_pre);
+    std::vector<int> wb;
+    if (!ls::clip_windows(batch, n_windows, T, n_pre, frames, wb)) return LS_EINVAL;
     std::vector<char> any((size_t)batch, 1);
     for (int b = 0; b < batch; ++b) {
-        long long most = Tt;
-        if (frames) {
-            if (frames[b] < T || frames[b] > Tt || (frames[b] - T) % S) return LS_EINVAL;
-            most = frames[b];
-            wb[(size_t)b] = (int)((frames[b] - T) / S) + 1;
-        }
+        const long long most = frames ? frames[b] : Tt;
         if (lo[b] < 0 || lo[b] > hi[b] || hi[b] > most) return LS_EINVAL;
         if (channels) {
             any[(size_t)b] = 0;
             for (int c = 0; c < n_channels && !any[(size_t)b]; ++c) any[(size_t)b] = channels[(size_t)b * n_channels + c] != 0;
         }
     }
-    long long nw = 0, np = 0;
-    for (int w = 0; w < n_windows; ++w) {
-        const long long own_lo = w ? w * S + n_pre : 0, own_hi = w * S + T;
-        int n = 0;
-        for (int b = 0; b < batch; ++b) {
-            const bool in = any[(size_t)b] && w < wb[(size_t)b] && (lo[b] > own_lo ? lo[b] : own_lo) < (hi[b] < own_hi ? hi[b] : own_hi);
-            if (!in) continue;
-            if (rows) { if (np + n >= row_capacity) return LS_EINVAL; rows[np + n] = b; }
-            ++n;
-        }
-        if (n == 0) continue;
-        if (windows) { if (nw >= window_capacity) return LS_EINVAL; windows[nw] = w; counts[nw] = n; }
-        ++nw; np += n;
-        if (np > INT32_MAX) return LS_EINVAL;
-    }
-    *n_windows_run = (int32_t)nw;
-    *n_pairs = (int32_t)np;
-    return LS_OK;
+    std::vector<unsigned char> flags;
+    ls::range_flags(batch, n_windows, T, n_pre, lo, hi, any.data(), wb.data(), flags);
+    return ls::edit_plan_of_flags(batch, n_windows, flags.data(), windows, counts, window_capacity, rows, row_capacity, n_windows_run, n_pairs);
+}
+
+// The plan of a timeline edit by ELEMENT MASK (ls_long_edit_mask and its kin in ls_hip.h): mask bytes [batch][n_channels][T + (W - 1) S]
+// on the HOST, non-zero = editable.  The pair (b, w) is in the plan iff the clip has a set byte on a frame w owns; the rest is
+// ls_long_edit_plan_compact's, through the same flags.
+int ls_long_edit_plan_mask(int32_t batch, int32_t n_windows, int32_t T, int32_t n_pre, const unsigned char* mask, int32_t n_channels,
+                           const int32_t* frames, int32_t* windows, int32_t* counts, int32_t window_capacity, int32_t* rows, int32_t row_capacity,
+                           int32_t* n_windows_run, int32_t* n_pairs) {
+    if (batch < 1 || n_windows < 1 || n_pre < 1 || T <= n_pre || !mask || n_channels < 1 || !n_windows_run || !n_pairs) return LS_EINVAL;
+    if (window_capacity < 0 || row_capacity < 0 || (window_capacity > 0 && (!windows || !counts)) || (row_capacity > 0 && !rows)) return LS_EINVAL;
+    std::vector<unsigned char> flags;
+    if (ls::edit_mask_flags(batch, n_windows, T, n_pre, n_channels, mask, frames, flags) != LS_OK) return LS_EINVAL;
+    return ls::edit_plan_of_flags(batch, n_windows, flags.data(), windows, counts, window_capacity, rows, row_capacity, n_windows_run, n_pairs);
 }
 
 // The windows one call of a stream runs (ls_long_stream_push_args in ls_hip.h): window w is complete once audio_stride * w + audio_len

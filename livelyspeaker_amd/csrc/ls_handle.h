@@ -132,6 +132,7 @@ struct ls_handle {
     DevBuf lg_audio, lg_clips, lg_featc, lg_featp, lg_emo_ids, lg_emotok, lg_seed;
     DevBuf lg_x, lg_eps, lg_nz, lg_text, lg_init, lg_mask, lg_timeline, lg_windows;
     DevBuf lg_inz, lg_edit_range, lg_edit_chan;     // ls_long_edit: a host caller's re-noise tape; per clip [lo, hi) int32 [B][2] and the channel bytes [B][JF]
+    DevBuf lg_edit_mask, lg_edit_flags, lg_edit_frames;     // an edit by element mask: a host caller's mask [B][JF][T_total], the pair flags [W][B] of k_edit_mask_pairs and the clips' frames [B]
     DevBuf lg_sag;          // ls_long_edit_sag: the SAG decoder's output [B][JF][T] of the window in flight (k_edit_start reads it)
     // a ragged long-form call (ls_long_prepare_ragged): clips held longest-first.  lg_bw[w] clips run window w (slots [0, lg_bw[w]) of
     // every per-clip buffer), lg_off[w] = sum of lg_bw[v], v < w, is window w's offset in the packed stores (lg_featc, the tapes);
@@ -149,6 +150,10 @@ struct ls_handle {
     bool lg_compact = false;
     std::vector<int32_t> lg_cw, lg_cn, lg_coff, lg_crows, lg_clo, lg_chi;
     std::vector<unsigned char> lg_cchan;
+    // ... or, prepared by ls_long_prepare_edit_mask, the pair flags [W][B] of its mask (lg_clo / lg_chi / lg_cchan empty), which the
+    // flags of the run's mask must repeat, and the clips' frames the flags were made with (empty: every clip has all W windows)
+    std::vector<unsigned char> lg_cflags;
+    std::vector<int32_t> lg_cframes;
     std::vector<float> lg_cscale;
     DevBuf lg_crows_dev, lg_cvid, lg_cscale_dev, lg_ctext;
     // Streaming sessions (ls_long_pool_open / _join / _push; ls_long_stream_open / _push): pl_S slots, each a stream of its own.  Per
@@ -232,6 +237,11 @@ int size_key_ring(ls_handle* h, int B, int n_exec, bool inp_noised = false);
 inline float* x_plane(const ls_handle* h, int k) { return (k & 1) ? h->xb.f() : h->xa.f(); }      // x ahead of executed step k (xa / xb ping-pong)
 // ---- defined in ls_chain_plan.cpp (host only): slot -> clip, windows per slot, clips per window of a ragged long-form call
 void long_plan_drop(int B, int AL, const int64_t* lengths, std::vector<int>& row, std::vector<int>& wins, std::vector<int>& bw);
+// ... the plan of a timeline edit from pair flags [W][B] (the one definition the range and the element-mask entries share), and the
+// flags of a HOST element mask [B][JF][T + (W - 1)(T - n_pre)] (LS_EINVAL: a bad frames[b], a set byte at or beyond frames[b])
+int edit_plan_of_flags(int B, int W, const unsigned char* flags, int32_t* windows, int32_t* counts, int32_t window_capacity, int32_t* rows,
+                       int32_t row_capacity, int32_t* n_windows_run, int32_t* n_pairs);
+int edit_mask_flags(int B, int W, int T, int n_pre, int JF, const unsigned char* mask, const int32_t* frames, std::vector<unsigned char>& flags);
 // ... and the strided copies that feed a session's rings, five ints each: first slot, slots, ring position, offset into the take, samples
 void feed_copies(int S, int R, const int* pos, const long long* from, const int* take, std::vector<int>& copies);
 

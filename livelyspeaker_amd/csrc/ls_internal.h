@@ -338,10 +338,17 @@ struct EditArgs {
     const float* sample; float* window;                                             // scatter
     int JF, T, KPP, n_pre, T_total, w;
     const int* rows;
+    // an ELEMENT MASK (ls_long_edit_mask and its kin): bytes [clips][JF][T_total] on the device, non-zero = editable, indexed by CLIP as
+    // the timeline is.  Set: element (c, f) of window w is editable iff emask[b][c][w * (T - n_pre) + f] != 0 and w == 0 or f >= n_pre;
+    // range and chan are not read (and may be null).  Null: the rectangle above.
+    const unsigned char* emask;
 };
 hipError_t launch_edit_gather(const EditArgs& a, int B, hipStream_t st);
 hipError_t launch_edit_start(const EditArgs& a, const float* sag_out, int B, hipStream_t st);
 hipError_t launch_edit_scatter(const EditArgs& a, int B, hipStream_t st);
+// flags [W][B] (bytes) <- the pair flags of an element mask [B][JF][T + (W - 1)(T - n_pre)], all on the device: 1 where clip b has a
+// set byte on a frame window w owns; with frames [B] (nullable) 2 where it has one and w is not one of the clip's own windows.
+hipError_t launch_edit_mask_pairs(const unsigned char* mask, const int* frames, unsigned char* flags, int B, int W, int JF, int T, int n_pre, hipStream_t st);
 // The held per-clip conditioning of one window of a compact edit into rows [0, A): row r <- clip rows[r] of vid_c / scale_c [clips] and
 // of emo_tok_c / text_c [clips][kD] (each of the two pairs nullable; 16-byte aligned).  k_pool_gather's conditioning move with clips
 // in place of slots.

@@ -25,7 +25,9 @@ for bit.  With ``sag=`` / ``text_features=`` the edit is script-guided: every wi
 its editable elements (``edit_start``; ``ls_long_edit_sag``, ``k_edit_start``).  ``edit_long(compact=True)`` runs only the
 clip-windows the edit touches (``edit_plan_compact``; ``ls_long_prepare_edit`` + ``ls_long_edit_compact``): window w is a sampling call
 on the clips that have an editable element in it, and only those clip-windows of audio are encoded; ``audio_lengths=`` edits the
-timeline of a ragged ``sample_long`` call that way.
+timeline of a ragged ``sample_long`` call that way.  ``edit_long(mask=)`` takes "editable" as a bool mask over the timeline's elements
+(True = editable) in place of the rectangle: several stretches, pinned keyframes (``keyframe_mask``), joints per stretch, constrained
+generation; the same windows' body, kernels and captured loop (``ls_long_edit_mask`` & co.; ``k_edit_mask_pairs`` plans a device mask).
 
 ``open_stream`` is the online form of the same chain: audio arrives in chunks of any size, a window runs as soon as its last sample
 is there, and the frames of all pushes are bit for bit ``sample_long``'s for the concatenated audio (``ls_long_stream_open`` /
@@ -944,12 +946,86 @@ def _edit_joints(joints, B, cfg):
     return np.ascontiguousarray(sel)
 
 
-def edit_plan(ranges, n_windows, cfg):
+def _edit_mask(mask, B, cfg, n_frames):
+    """An element mask of ``edit_long`` -- bool, True = EDITABLE, numpy or torch on any device, shaped [N], [B, N], [B, J, N] or
+    [B, J, F, N] (a leading 1 stands for every clip) -- as a contiguous bool tensor [B, J * F, N] on the mask's own device."""
+    J, F, N = int(cfg.njoints), int(cfg.nfeats), int(n_frames)
+    m = mask if hasattr(mask, "detach") else th.from_numpy(np.ascontiguousarray(mask))
+    if m.dtype != th.bool:
+        raise ValueError(f"mask must be bool (True = editable), got {m.dtype}")
+    shape = _shape(m)
+    lead = (1, B)
+    ok = {1: shape == (N,), 2: len(shape) == 2 and shape[0] in lead and shape[1] == N,
+          3: len(shape) == 3 and shape[0] in lead and shape[1:] == (J, N),
+          4: len(shape) == 4 and shape[0] in lead and shape[1:] == (J, F, N)}.get(m.ndim, False)
+    if not ok:
+        raise ValueError(f"mask must be [{N}], [{B}, {N}], [{B}, {J}, {N}] or [{B}, {J}, {F}, {N}], got {list(shape)}")
+    m = m.reshape({1: (1, 1, 1, N), 2: (shape[0], 1, 1, N), 3: (shape[0], J, 1, N), 4: shape}[m.ndim])
+    return m.expand(B, J, F, N).reshape(B, J * F, N).contiguous()
+
+
+def edit_mask(ranges, joints, n_frames, cfg):
+    """The rectangle of the range form as an element mask: numpy bool [B, J, F, n_frames], True (= editable) on the joints ``joints``
+    (None = all, bool [J] or [B, J]) and the frames ``lo_b <= n < hi_b`` of ``ranges`` ((lo, hi) or [B, 2]).  B is the ranges' or the
+    joints' leading size (1 when neither has one).  ``edit_long(mask=edit_mask(r, j, N, cfg))`` is ``edit_long(frames=r, joints=j)``,
+    bit for bit."""
+    fr = np.asarray(ranges.detach().cpu().numpy() if hasattr(ranges, "detach") else ranges)
+    sel = None if joints is None else np.asarray(joints.detach().cpu().numpy() if hasattr(joints, "detach") else joints)
+    B = int(fr.shape[0]) if fr.ndim == 2 else int(sel.shape[0]) if sel is not None and sel.ndim == 2 else 1
+    lo, hi = _edit_ranges(fr, B, int(n_frames))
+    sel = _edit_joints(sel, B, cfg)
+    n = np.arange(int(n_frames))
+    inside = (n[None, :] >= lo[:, None]) & (n[None, :] < hi[:, None])
+    return np.ascontiguousarray(np.broadcast_to(sel[:, :, None, None] & inside[:, None, None, :], (B, int(cfg.njoints), int(cfg.nfeats), int(n_frames))))
+
+
+def keyframe_mask(n_frames, pinned_frames, cfg, joints=None, within=None):
+    """The mask of in-betweening and of constrained generation: numpy bool [1, J, F, n_frames] (one mask for every clip), True
+    (= editable) everywhere -- with ``within`` (one (lo, hi) pair or a list of them) only inside those frame ranges -- except on the
+    ``pinned_frames`` (a sequence of frame indices), where the joints ``joints`` (bool [J]; None = all) are KEPT.  A timeline that
+    holds poses at the pinned frames, this mask and ``skip_timesteps=0``: "generate a talk that passes through these poses"."""
+    N, J, F = int(n_frames), int(cfg.njoints), int(cfg.nfeats)
+    pins = np.asarray(list(pinned_frames), dtype=np.int64).reshape(-1)
+    if ((pins < 0) | (pins >= N)).any():
+        raise ValueError(f"pinned_frames must lie in [0, {N}), got {pins.tolist()}")
+    sel = _edit_joints(joints, 1, cfg)[0]
+    frames = np.ones(N, bool)
+    if within is not None:
+        pairs = np.asarray(within, dtype=np.int64).reshape(-1, 2)
+        frames[:] = False
+        for lo, hi in pairs:
+            if lo < 0 or lo > hi or hi > N:
+                raise ValueError(f"every range of `within` must satisfy 0 <= lo <= hi <= {N}, got {pairs.tolist()}")
+            frames[lo:hi] = True
+    mask = np.broadcast_to(frames[None, None, :], (J, F, N)).copy()
+    mask[np.ix_(np.flatnonzero(sel), np.arange(F), pins)] = False
+    return mask[None]
+
+
+def _host_mask(mask, n_windows, cfg, frames=None):
+    """``mask`` on the host as [B, J * F, N] for the plans: B from the mask ([N]: from ``frames``, else 1)."""
+    N = _window_sizes(int(n_windows), cfg)[1]
+    m = mask.detach().cpu() if hasattr(mask, "detach") else th.from_numpy(np.ascontiguousarray(mask))
+    B = int(m.shape[0]) if m.ndim > 1 and int(m.shape[0]) != 1 else 1 if frames is None else int(np.asarray(frames).size)
+    return _edit_mask(m, B, cfg, N).numpy()
+
+
+def edit_plan(ranges, n_windows, cfg, mask=None):
     """The windows ``edit_long`` runs for the per-clip frame ranges ``ranges`` ((lo, hi) or [B, 2]) of a timeline of ``n_windows``
     windows, as a sorted list: window w runs when some clip's range meets the frames it OWNS -- [0, T) for w = 0,
     [w * S + n_pre, w * S + T) with S = T - n_pre otherwise, the frames it contributes to the stitched timeline.  No range meets any
-    (all are empty): ``ValueError``.  One definition for the engine and for this module (``ls_long_edit_plan``)."""
+    (all are empty): ``ValueError``.  One definition for the engine and for this module (``ls_long_edit_plan``).
+
+    ``mask=`` (with ``ranges=None``; ``edit_long``'s element mask, True = editable): window w runs when some clip has a True element
+    on a frame w owns (``ls_long_edit_plan_mask``).  An empty mask: ``ValueError``."""
     T, npre, W = int(cfg.nframes), int(cfg.n_pre_seq), int(n_windows)
+    if mask is not None:
+        if ranges is not None:
+            raise ValueError("edit_plan: mask excludes ranges")
+        windows = [w for w, _ in _lib.long_edit_plan_mask(_host_mask(mask, W, cfg), W, None, T, npre)]
+        if not windows:
+            raise ValueError("edit_plan: the mask is empty, no window would run")
+        return windows
     fr = np.asarray(ranges.detach().cpu().numpy() if hasattr(ranges, "detach") else ranges)
     lo, hi = _edit_ranges(fr, 1 if fr.ndim == 1 else int(fr.shape[0]), _window_sizes(W, cfg)[1])
     windows = _lib.long_edit_plan(lo, hi, W, T, npre)
@@ -958,15 +1034,23 @@ def edit_plan(ranges, n_windows, cfg):
     return windows
 
 
-def edit_plan_compact(ranges, n_windows, cfg, joints=None, frames=None):
+def edit_plan_compact(ranges, n_windows, cfg, joints=None, frames=None, mask=None):
     """The clip-windows the COMPACT ``edit_long`` runs, as a list of ``(w, rows)``: the windows that run, ascending, each with the
     clips that have an editable element in it, ascending (``rows``, a list of clip indices).  The pair (clip b, window w) is in the
     plan iff b's range meets the frames w OWNS (``edit_plan``'s rule), at least one joint of b is selected by ``joints`` (None = all,
     bool [J] or [B, J]), and -- with ``frames`` (int [B], a ragged batch: ``plan_lengths``) -- ``w`` is one of the clip's own
     ``(frames[b] - T) / S + 1`` windows.  Without ``frames`` the windows are exactly ``edit_plan``'s.  A range outside
     ``[0, frames[b]]``, ``lo > hi`` or a ``frames[b]`` that is no stitched length (34 + 30 k): ``ValueError``.  No pair at all is an
-    empty list, which ``edit_long`` refuses.  One definition for the engine and for this module (``ls_long_edit_plan_compact``)."""
+    empty list, which ``edit_long`` refuses.  One definition for the engine and for this module (``ls_long_edit_plan_compact``).
+
+    ``mask=`` (with ``ranges=None`` and ``joints=None``; ``edit_long``'s element mask, True = editable): the pair (b, w) is in the plan
+    iff clip b has a True element on a frame w owns and, with ``frames``, w is one of its own windows; a True element at or beyond
+    ``frames[b]``: ``ValueError`` (``ls_long_edit_plan_mask``).  Both forms reduce to pair flags and share the rest."""
     T, npre, W = int(cfg.nframes), int(cfg.n_pre_seq), int(n_windows)
+    if mask is not None:
+        if ranges is not None or joints is not None:
+            raise ValueError("edit_plan_compact: mask excludes ranges and joints")
+        return [(w, [int(b) for b in rows]) for w, rows in _lib.long_edit_plan_mask(_host_mask(mask, W, cfg, frames), W, frames, T, npre)]
     fr = np.asarray(ranges.detach().cpu().numpy() if hasattr(ranges, "detach") else ranges)
     B = int(fr.shape[0]) if fr.ndim == 2 else 1 if frames is None else int(np.asarray(frames).size)      # one pair: for every clip of `frames`
     lo, hi = _edit_ranges(fr, B, _window_sizes(W, cfg)[1])
@@ -974,7 +1058,7 @@ def edit_plan_compact(ranges, n_windows, cfg, joints=None, frames=None):
     return [(w, [int(b) for b in rows]) for w, rows in _lib.long_edit_plan_compact(lo, hi, W, sel, frames, T, npre)]
 
 
-def edit_window(timeline, w, ranges, joints, seed_poses, cfg):
+def edit_window(timeline, w, ranges, joints, seed_poses, cfg, mask=None):
     """Window ``w`` of a timeline edit in plain torch: ``(origin_x, inpainting_mask, inpainted_motion)``, each [B, J, F, T], as
     ``edit_long`` hands them to the sampling loop.
 
@@ -985,17 +1069,26 @@ def edit_window(timeline, w, ranges, joints, seed_poses, cfg):
     * ``inpainting_mask`` is True where the given motion is KEPT (the reference's meaning): False exactly on the editable elements
       (b, j, :, f) -- joint j of ``joints`` (None = all, bool [J] or [B, J]) selected, ``lo_b <= w * S + f < hi_b``, and frame
       ``w * S + f`` owned by window w (``edit_plan``).  The first ``n_pre`` frames of a later window belong to the window before it
-      and are never editable in it."""
+      and are never editable in it.
+    * ``mask=`` (with ``ranges=None`` and ``joints=None``): ``edit_long``'s element mask for these clips, True = EDITABLE -- the
+      opposite of the ``inpainting_mask`` returned.  Element (b, j, k, f) is editable iff ``mask[b, j, k, w * S + f]`` and frame
+      ``w * S + f`` is owned by window w; nothing else changes."""
     T, npre = int(cfg.nframes), int(cfg.n_pre_seq)
     S, w = T - npre, int(w)
     B, J, F, N = _shape(timeline)
     if w < 0 or w * S + T > N:
         raise ValueError(f"window {w} lies outside a timeline of {N} frames")
-    lo, hi = _edit_ranges(ranges, B, N)
-    sel = _edit_joints(joints, B, cfg)
     motion = timeline[..., w * S:w * S + T].contiguous()
     origin_x = th.zeros_like(motion)
     origin_x[..., :npre] = motion[..., :npre] if w > 0 else th.as_tensor(seed_poses).to(motion)
+    if mask is not None:
+        if ranges is not None or joints is not None:
+            raise ValueError("edit_window: mask excludes ranges and joints")
+        own = th.from_numpy((np.arange(T) >= npre) | (w == 0)).to(motion.device)
+        editable = _edit_mask(mask, B, cfg, N).reshape(B, J, F, N)[..., w * S:w * S + T].to(motion.device) & own
+        return origin_x, ~editable, motion
+    lo, hi = _edit_ranges(ranges, B, N)
+    sel = _edit_joints(joints, B, cfg)
     t = w * S + np.arange(T)
     frame_ok = (t[None, :] >= lo[:, None]) & (t[None, :] < hi[:, None]) & ((np.arange(T) >= npre) | (w == 0))[None, :]       # [B, T]
     editable = sel[:, :, None, None] & frame_ok[:, None, None, :]
@@ -1016,7 +1109,7 @@ def edit_start(motion, mask, sag_out):
 
 def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices, scale, emo=None, joints=None, sampler='ddim',
               skip_timesteps=0, eta=0.0, clip_denoised=False, encoder_chunk=None, return_windows=False, sag=None, text_features=None,
-              compact=None, audio_lengths=None):
+              compact=None, audio_lengths=None, mask=None):
     """Re-synthesise a stretch of a timeline ``sample_long`` made: the frames ``frames`` -- one ``(lo, hi)`` pair for all clips or a
     host int array [B, 2], ``lo == hi`` leaves a clip alone -- on the joints ``joints`` (None = all; a bool mask [J] or [B, J]), with
     the conditioning of the ``sample_long`` call (``audio``, ``seed_poses``, ``vid_indices``, ``scale``, ``emo``).  Returns a new
@@ -1079,7 +1172,24 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
       element kept; its result is discarded, and all W windows of every clip go through the WavEncoder.  The compact form does neither;
     * ``compact=None`` (the default) means the dense form unless ``audio_lengths`` is given.
 
-    Not built: edits of a running stream or pool, PLMS, ``const_noise``, ``dump_steps``, ``'torch_device'``, resampling windows behind
+    ``mask=`` (with ``frames=None`` and ``joints=None``; combined with either: ``ValueError``) makes "editable" DATA instead of a
+    rectangle.  **In ``mask``, True means EDITABLE -- re-synthesise this element.**  That is the OPPOSITE of ``edit_window``'s
+    ``inpainting_mask`` (and the reference's), where True means KEEP.  ``mask`` is bool, numpy or torch, host or device, shaped ``[N]``,
+    ``[B, N]``, ``[B, J, N]`` or ``[B, J, F, N]`` in the timeline's own frame axis.  Element (b, j, k, f) of window w is editable iff
+    ``mask[b, j, k, w * S + f]`` and frame ``w * S + f`` is owned by w (``edit_plan``'s ownership); with ``audio_lengths`` a True
+    element at or beyond ``frames[b]`` is a ``ValueError``, not a silent no-op.  Several stretches in one call, keyframes pinned
+    inside a stretch (``keyframe_mask``), other joints in other stretches and constrained generation (a timeline of pinned poses,
+    everything else editable, ``skip_timesteps=0``) are all masks; ``edit_mask(ranges, joints, N, cfg)`` is the range form, and gives
+    the range call's result bit for bit.  Everything above holds with the mask in place of the rectangle -- ``compact=``,
+    ``audio_lengths=``, ``sag=`` / ``text_features=``, ``return_windows=``, both noise sources; the dense form runs window w iff some
+    clip has an editable element in it, the compact form the pair (b, w) iff clip b has one (``edit_plan(mask=)`` /
+    ``edit_plan_compact(mask=)``) -- and with ``'torch_cpu'`` the result is bit for bit the loop above with ``edit_window(mask=)``
+    (tests/test_gpu_long_edit_mask.py).  The engine runs the same kernels and the same captured loop (``ls_long_edit_mask`` & co.).  A
+    device mask stays on the device: ``k_edit_mask_pairs`` reduces it to one flag per clip-window and only those W * B bytes reach the
+    host for planning.
+
+    Not built: edits of a running stream or pool (masks on them included), bit-packed masks, soft (fractional) masks, PLMS,
+    ``const_noise``, ``dump_steps``, ``'torch_device'``, resampling windows behind
     the last edited one, the SAG encoder (motion -> latent) as the source of ``text_features`` (chain ``MOTIONCLIP`` yourself) and
     device-resident length arrays; in the dense form also ragged batches (``audio_lengths=``) and re-encoding only the edited windows'
     audio (all W windows go through the WavEncoder, as in ``sample_long``)."""
@@ -1101,15 +1211,23 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
     if T != 34 or N < T or (N - T) % (T - npre):
         raise ValueError(f"a timeline holds 34 + 30 (W - 1) frames, got {N}")
     W = (N - T) // (T - npre) + 1
-    lo, hi = _edit_ranges(frames, B, N)
-    sel = _edit_joints(joints, B, rag)
+    if mask is not None and (frames is not None or joints is not None):
+        raise ValueError("edit_long: mask (True = editable) says which frames and joints are edited; pass frames=None and joints=None with it")
+    if mask is None and frames is None:
+        raise ValueError("edit_long: pass the frames to edit, or mask=")
+    if mask is not None:
+        emask = _edit_mask(mask, B, rag, N)                            # bool [B, J * F, N] on the mask's device
+    else:
+        lo, hi = _edit_ranges(frames, B, N)
+        sel = _edit_joints(joints, B, rag)
     if audio.ndim != 2 or int(audio.shape[0]) != B:
         raise ValueError(f"audio must be [{B}, L], got {list(audio.shape)}")
     if text_features is not None and text_features.ndim == 2 and _shape(text_features) == (B, rag.latent_dim):
         text_features = text_features[:, None, :].expand(B, W, rag.latent_dim)         # one script for the whole stretch
     _check_args(diffusion, model, audio, seed_poses, vid_indices, scale, emo, W, sampler, skip_timesteps, sag, text_features, encoder_chunk, {})
     _check_model(diffusion, rag)
-    hi = np.where(sel.any(axis=1), hi, lo).astype(np.int32)           # a clip with no joint selected is not edited
+    if mask is None:
+        hi = np.where(sel.any(axis=1), hi, lo).astype(np.int32)       # a clip with no joint selected is not edited
     lens = frames = None
     if audio_lengths is not None:
         lens = _lib.host_lengths(audio_lengths, B, 1, int(audio.shape[1]), "audio_lengths")
@@ -1117,22 +1235,41 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
         frames = np.array([f for _, f in plans], np.int32)
         if max(Wb for Wb, _ in plans) != W:
             raise ValueError(f"the timeline holds {W} windows, the longest of audio_lengths needs {max(Wb for Wb, _ in plans)}")
-        if (hi > frames).any():
+        if mask is None and (hi > frames).any():
             raise ValueError(f"every frame range must lie inside its own clip, 0 <= lo <= hi <= frames[b] = {frames.tolist()}, got "
                              f"{np.stack([lo, hi], axis=1).tolist()}")
-    channels = np.repeat(sel, rag.nfeats, axis=1)
-    if compact:
-        plan = edit_plan_compact(np.stack([lo, hi], axis=1), W, rag, joints=sel, frames=frames)
-        if not plan:
-            raise ValueError("edit_long: every frame range is empty, no window would run")
-        batches = [len(rows) for _, rows in plan]
+        if mask is not None:
+            beyond = th.arange(N, device=emask.device)[None, None, :] >= th.from_numpy(frames).to(emask.device)[:, None, None]
+            if bool((emask & beyond).any()):
+                raise ValueError(f"mask is True at or beyond a clip's own frames[b] = {frames.tolist()}; nothing is edited there")
+    plan = None
+    if mask is not None:
+        channels, rect = None, dict(mask=emask)
+        if emask.device.type == "cpu":                                 # a device mask is planned by the engine, from its pair flags
+            plan = [(w, [int(b) for b in rows]) for w, rows in _lib.long_edit_plan_mask(emask.numpy(), W, frames, T, npre)]      # edit_plan_compact(mask=)
     else:
-        windows = edit_plan(np.stack([lo, hi], axis=1), W, rag)
+        channels = np.repeat(sel, rag.nfeats, axis=1)
+        rect = dict(channels=channels)
+        if compact:
+            plan = edit_plan_compact(np.stack([lo, hi], axis=1), W, rag, joints=sel, frames=frames)
+        else:
+            windows = edit_plan(np.stack([lo, hi], axis=1), W, rag)
+    if plan is not None and not plan:
+        raise ValueError("edit_long: the mask is empty, no window would run" if mask is not None else
+                         "edit_long: every frame range is empty, no window would run")
     out_dev = timeline.device
     eng = _bind_engine(diffusion, rag)
+    if mask is not None:
+        if plan is None:
+            plan = [(w, [int(b) for b in rows]) for w, rows in eng.long_edit_mask_plan(emask, W, frames)]
+            if not plan:
+                raise ValueError("edit_long: the mask is empty, no window would run")
+        windows = [w for w, _ in plan]
+        lo = hi = None
     if compact:
-        eng.long_prepare_edit(audio.float(), seed_poses.float(), vid_indices, scale.float(), lo, hi, channels=channels,
-                              emo=_emo_windows(emo, W, B), n_windows=W, encoder_chunk=encoder_chunk, audio_lengths=lens)
+        batches = [len(rows) for _, rows in plan]
+        eng.long_prepare_edit(audio.float(), seed_poses.float(), vid_indices, scale.float(), lo, hi, emo=_emo_windows(emo, W, B), n_windows=W,
+                              encoder_chunk=encoder_chunk, audio_lengths=lens, **rect)
         assert [(w, [int(b) for b in rows]) for w, rows in eng.edit_plan] == plan, (eng.edit_plan, plan)
     else:
         eng.long_prepare(audio.float(), seed_poses.float(), vid_indices, scale.float(), emo=_emo_windows(emo, W, B), n_windows=W,
@@ -1141,7 +1278,7 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
     shape = (max(batches) if compact else B, rag.njoints, rag.nfeats, T)       # the compact form: its largest window batch
     noised = rag.n_prefix_tokens == 1                  # the TED tree re-noises the kept motion, the BEAT tree does not
     kw = dict(_loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised), device_out=out_dev.type == "cuda", return_windows=return_windows,
-              inpaint_noised=noised, channels=channels)
+              inpaint_noised=noised, **rect)
     if sag is not None:
         sag_eng = sag.engine()
         if sag_eng.device != eng.device:

@@ -5,6 +5,7 @@ timeline again (long_form.sample_long of the same W), alternated in one process:
     python tools/long_edit_time.py 20 8            # seconds, clips
     python tools/long_edit_time.py --sag [20 8]    # the SCRIPTED edit two ways (profiles/r26_long_edit_sag.md)
     python tools/long_edit_time.py --compact [--sag] [20 8]    # the dense against the COMPACT edit (profiles/r31_edit_compact.md)
+    python tools/long_edit_time.py --mask [20 8]   # two stretches as ONE mask call against TWO range calls (profiles/r32_edit_mask.md)
 
 TED, ddim100, skip_timesteps = 80 (20 steps per window), guidance 1.5, Philox noise, device-resident inputs, hipGraph replay, warm
 handles.  Three forms: the full call, an edit inside one window, and an edit that spans W // 2 windows.  Each call is timed by a host
@@ -23,7 +24,12 @@ where edit_long encodes all W windows ahead; both are part of what a caller wait
 
 --compact alternates edit_long(compact=False) and edit_long(compact=True) of the same ranges, round by round, in three cases: (a) one
 clip in one window, (b) 8 clips each in a window of its own, (c) every clip in W // 2 windows, where the compact plan is the dense one
-and the results are checked to be the same bits.  With --sag the edits are scripted, and (a) is timed against the host loop too."""
+and the results are checked to be the same bits.  With --sag the edits are scripted, and (a) is timed against the host loop too.
+
+--mask alternates, round by round, two stretches of clip 0 (ten frames each, in two windows a quarter of the timeline apart) edited as
+ONE call of edit_long(mask=) and as TWO calls of edit_long(frames=) -- the second on the first one's result --, each in the compact and
+in the dense form.  The mask lives on the device, as the timeline does.  Under Philox the two ways draw the same streams, so the tool
+checks, form by form, that they give the same bits before it times them."""
 import os
 import statistics
 import sys
@@ -185,7 +191,78 @@ def main_compact(seconds, B, scripted):
     clocks.on = False
 
 
+def main_mask(seconds, B):
+    """Two stretches of one clip as one mask call against two range calls, compact and dense (profiles/r32_edit_mask.md)."""
+    import numpy as np
+    cfg, model, diffusion = build()
+    diffusion.noise_source, diffusion.philox_seed = "philox", 1
+    W, _, n_frames = long_form.plan_windows(int(round(seconds * 16000)), cfg)
+    y = {k: torch.from_numpy(v).to(DEV) for k, v in synth.make_long_cond(cfg, B, W).items()}
+    S = cfg.nframes - cfg.n_pre_seq
+    w1, w2 = W // 4, (3 * W) // 4
+    stretches = [(w1 * S + 10, w1 * S + 20), (w2 * S + 10, w2 * S + 20)]
+    ranges = []
+    for lo, hi in stretches:
+        r = np.zeros((B, 2), np.int64)
+        r[0] = (lo, hi)
+        ranges.append(r)
+    host_mask = np.zeros((B, n_frames), bool)
+    for lo, hi in stretches:
+        host_mask[0, lo:hi] = True
+    mask = torch.from_numpy(host_mask).to(DEV)
+    timeline = long_form.sample_long(diffusion, model, y["audio"], y["seed_poses"], y["vid_indices"], y["scale"], n_windows=W, sampler="ddim",
+                                     skip_timesteps=SKIP)
+
+    def call(tl, compact, **what):
+        return long_form.edit_long(diffusion, model, tl, what.get("frames"), y["audio"], y["seed_poses"], y["vid_indices"], y["scale"], sampler="ddim",
+                                   skip_timesteps=SKIP, compact=compact, mask=what.get("mask"))
+
+    def one_call(compact):
+        return call(timeline, compact, mask=mask)
+
+    def two_calls(compact):
+        return call(call(timeline, compact, frames=ranges[0]), compact, frames=ranges[1])
+
+    forms = [("compact", "mask", lambda: one_call(True)), ("compact", "ranges", lambda: two_calls(True)),
+             ("dense", "mask", lambda: one_call(False)), ("dense", "ranges", lambda: two_calls(False))]
+    plan = long_form.edit_plan_compact(None, W, cfg, mask=host_mask)
+    assert plan == [(w1, [0]), (w2, [0])] and w1 != w2, plan
+    for compact in (True, False):                                    # the same keys, the same windows at the same batch: the same bits
+        ref = two_calls(compact)
+        assert torch.equal(one_call(compact), ref) and not torch.equal(ref, timeline), compact
+    clocks = ClockSampler()
+    clocks.start()
+    for _ in range(2):                                               # warm-up of all forms: allocations, graph capture, clocks
+        for _, _, fn in forms:
+            timed(fn)
+    clocks.take()
+    reps = 3
+    rounds, engine = {(f, k): [] for f, k, _ in forms}, {}
+    for _ in range(ROUNDS):
+        for form, kind, fn in forms:
+            rounds[form, kind].append(statistics.median(timed(fn)[0] for _ in range(reps)))
+            engine[form, kind] = model.model.engine().timing()
+    print(f"# one mask call against two range calls; TED ddim100 skip {SKIP} (20 steps per window), CFG 1.5, philox, device inputs and a device "
+          f"mask; {seconds:g} s of speech = {W} windows ({n_frames} frames), {B} clips; clip 0 on frames {stretches}: windows {w1} and {w2}; ms, "
+          f"median over {ROUNDS} alternated rounds [min .. max of the rounds]; prepare / windows: the engine's event times of the LAST call "
+          f"(of two range calls: the second, one window)")
+    for form in ("compact", "dense"):
+        for kind in ("mask", "ranges"):
+            r, t = rounds[form, kind], engine[form, kind]
+            print(f"  {form:8s} {'one mask call  ' if kind == 'mask' else 'two range calls'} {statistics.median(r):9.2f} [{min(r):.2f} .. {max(r):.2f}]  | "
+                  f"prepare {t['prepare_ms']:.2f} ms, windows {t['total_ms']:.2f} ms, {t['n_step_launches']} steps, graph replayed for "
+                  f"{t['graph_replayed']} of {t['n_segments']} windows, step path {t['step_path']}", flush=True)
+        m, r = rounds[form, "mask"], rounds[form, "ranges"]
+        print(f"  {form}: two calls - one call = {statistics.median(r) - statistics.median(m):+.2f} ms ({statistics.median(r) / statistics.median(m):.2f}x); "
+              f"the mask call faster in {sum(p < q for p, q in zip(m, r))} of {ROUNDS} rounds; spread of the mask call {max(m) - min(m):.2f} ms")
+    print(f"# {clocks.take()}")
+    clocks.on = False
+
+
 def main():
+    if "--mask" in sys.argv:
+        sys.argv.remove("--mask")
+        return main_mask(float(sys.argv[1]) if len(sys.argv) > 1 else 60.0, int(sys.argv[2]) if len(sys.argv) > 2 else 64)
     if "--compact" in sys.argv:
         sys.argv.remove("--compact")
         scripted = "--sag" in sys.argv
