@@ -16,7 +16,7 @@ scripts/test_LivelySpeaker_ted.py:57-113 + :176-224 of the reference on SYNTHETI
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --edit-frames "LO,HI;LO,HI" [--edit-pin N[,N]] [--edit-joints ...] [--edit-clip K]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --stream-chunk SECONDS [--post [--score]] [--input-sr RATE]
     python examples/livelyspeaker_ted.py [batch] --long-seconds N --score-talk
-    python examples/livelyspeaker_ted.py --pool SPEAKERS
+    python examples/livelyspeaker_ted.py --pool SPEAKERS [--keyed] [--pin 60,95]
     python examples/livelyspeaker_ted.py [batch] --clip-text
 --clip-text starts from TOKENS instead of a stand-in feature: synthetic clip.tokenize output -> CLIPTextEncoder (the text tower of CLIP
 on the GPU, synthetic weights) -> text features -> SAG decoder -> the same refinement, with no host wait between the two engines.
@@ -60,6 +60,9 @@ the beats of the post stream go in, and the close prints the beat-consistency sc
 --pool SPEAKERS serves that many LIVE speakers from one engine (long_form.open_pool): they start 1.3 s apart and talk for different
 times, each joins a slot when it starts and leaves it when its speech ends, audio arrives for all of them every half second, and every
 push runs the windows that are complete -- of whichever speakers -- as one batch.  It prints who joined, which batch ran, and who left.
+--pin 60,95 (with --pool) opens the pool with pins=128 and pins two poses of the speaker who talks longest at those frames of its
+series (long_form.LongPool.pin); the windows that own them run through the inpainting branch, and the distance of the returned frames
+from the pinned poses is printed at the end.
 --keyed (with --pool, philox) opens the pool with noise_keys='clip': speaker s draws at key 100 + s whatever runs beside it.  After
 serving the staggered speakers it runs one of them again, alone, in a fresh keyed pool under the same seed and key, and prints the
 max-abs difference between the two runs of that speaker (0 where both ran the same kernel family at the same batch; a kernel family's
@@ -193,7 +196,12 @@ def main():
         speakers = int(sys.argv[i + 1])
         if speakers < 1:
             raise SystemExit("--pool takes the number of speakers, >= 1")
-        return main_pool(speakers, noise_source, keyed="--keyed" in sys.argv)
+        pin = None
+        if "--pin" in sys.argv:                                                             # --pin 60,95: frames of the last speaker to pin
+            pin = sorted({int(v) for v in sys.argv[sys.argv.index("--pin") + 1].split(",")})
+            if not pin or pin[0] < 0 or pin[-1] >= 128:
+                raise SystemExit("--pin takes frames in [0, 128), comma-separated")
+        return main_pool(speakers, noise_source, keyed="--keyed" in sys.argv, pin=pin)
     if "--long-seconds" in sys.argv:
         i = sys.argv.index("--long-seconds")
         arg = sys.argv[i + 1]
@@ -477,10 +485,12 @@ def stream_timeline(long_form, model, diffusion, sag_decoder, timeline, audio, y
               f"one call's")
 
 
-def main_pool(speakers, noise_source, tick_seconds=0.5, keyed=False):
+def main_pool(speakers, noise_source, tick_seconds=0.5, keyed=False, pin=None):
     """`speakers` live speakers on ONE engine (long_form.open_pool): speaker s starts talking 1.3 s after speaker s - 1 and talks for
     6 + s seconds; audio arrives for all of them every `tick_seconds`.  A speaker joins a free slot when it starts and leaves when its
-    speech ends; every tick is one push, which runs the windows that are complete as one batch."""
+    speech ends; every tick is one push, which runs the windows that are complete as one batch.  `pin` (--pin 60,95): the pool is
+    opened with pins=128 and the last speaker -- the one who talks longest -- is told, when it joins, which pose to be in at those
+    frames; at the end the distance of its returned frames from those poses is printed."""
     import numpy as np
     from livelyspeaker_amd import long_form
     if noise_source == "torch_device":
@@ -492,6 +502,10 @@ def main_pool(speakers, noise_source, tick_seconds=0.5, keyed=False):
     if keyed:
         diffusion.philox_seed = 0x5EED_2026             # one seed for the session and for its replay
     opts = {"noise_keys": "clip"} if keyed else {}
+    if pin:
+        opts["pins"] = 128                              # the horizon: a pin may lie up to 128 frames ahead of the frames returned
+        pinned = speakers - 1
+        poses = (torch.rand(cfg.njoints, cfg.nfeats, len(pin), generator=torch.Generator().manual_seed(95)) * 2 - 1).cuda()
     n = int(round(tick_seconds * 16000))
     start = [int(round(1.3 * s / tick_seconds)) for s in range(speakers)]                       # the tick a speaker joins in
     length = [int(round((6 + s) * 16000)) for s in range(speakers)]
@@ -506,6 +520,9 @@ def main_pool(speakers, noise_source, tick_seconds=0.5, keyed=False):
             if start[s] == tick:
                 slot[s] = pool.join(y["seed_poses"][s], y["vid_indices"][s], y["scale"][s], **({"key": 100 + s} if keyed else {}))
                 print(f"tick {tick:3d}: speaker {s} joins slot {slot[s]}" + (f" under key {100 + s}" if keyed else ""))
+                if pin and s == pinned:
+                    pool.pin(slot[s], pin, poses)
+                    print(f"tick {tick:3d}: speaker {s} is pinned at frames {pin}: {int(pool.slots['pins'][slot[s]])} pinned frames to come")
         chunk, lengths = torch.zeros(speakers, n, device="cuda"), np.zeros(speakers, np.int64)
         for s, k in slot.items():
             take = min(n, length[s] - fed[s])
@@ -530,6 +547,13 @@ def main_pool(speakers, noise_source, tick_seconds=0.5, keyed=False):
         tick += 1
     pool.close()
     print(f"{speakers} speakers, {sum(frames)} frames ({noise_source}) in {(time.perf_counter() - t0) * 1e3:.0f} ms over {tick} pushes on one engine")
+    if pin:
+        served = torch.cat(kept[pinned], dim=2)
+        for k, f in enumerate(pin):
+            if f < served.shape[2]:
+                print(f"speaker {pinned}, frame {f}: max |returned - pinned pose| = {float((served[:, :, f] - poses[:, :, k]).abs().max()):.3e}")
+            else:
+                print(f"speaker {pinned}, frame {f}: never reached ({served.shape[2]} frames); the pin was dropped when the speaker left")
     if keyed:           # the session replayed for one speaker: alone, in one chunk, in slot 0 of a fresh pool -- same seed, same key
         s = speakers // 2
         solo = long_form.open_pool(diffusion, model, 1, sampler="ddim", skip_timesteps=80, noise_keys="clip")

@@ -584,7 +584,8 @@ int ls_long_edit_mask_pairs(ls_handle* h, const unsigned char* element_mask, int
  * PHILOX keys window w at w << 48 and the key must not repeat: a push that would run window 2^16 returns LS_ESTATE (about 36 hours of
  * audio; open a new stream).
  * Clips that join and leave, each with its own lengths: the session pool further down (ls_long_pool_*).
- * Not built: edits of a running stream, PLMS, const_noise, dump_steps, a non-blocking push. */
+ * Not built: edits of frames a running stream has already returned (frames still to come can be pinned: ls_long_pool_pins further
+ * down serves a stream too), PLMS, const_noise, dump_steps, a non-blocking push. */
 typedef struct ls_long_stream_cond {
     int32_t batch;
     int32_t on_device;
@@ -667,7 +668,8 @@ int ls_long_stream_info(const ls_handle* h, int64_t out[4]);
  * The draws of a keyed round are written by ls_philox_rows.hip into the ring LS_NOISE_TORCH_DEVICE uses (ls_set_torch_ring_bytes),
  * sized at ls_long_pool_keyed for every batch up to the capacity, from a key table the captured loop reads at a fixed address.
  * One host wait per call that ran a round; a call that ran none waits only for the copy of a HOST chunk.
- * Not built: device-resident lengths, ls_long_edit on a pool, PLMS, const_noise, dump_steps, sharded
+ * Not built: device-resident lengths, ls_long_edit on frames a pool has already returned (frames still to come can be pinned:
+ * ls_long_pool_pins below), PLMS, const_noise, dump_steps, sharded
  * calls, a non-blocking push. */
 typedef struct ls_long_pool_join_args {
     int32_t slot;
@@ -722,6 +724,56 @@ int ls_long_pool_keys(int32_t n_slots, const uint64_t* keys, const int64_t* wind
  * first ls_long_pool_open */
 int ls_long_pool_info(const ls_handle* h, int32_t capacity, int64_t* samples_in, int64_t* windows_run, int64_t* frames_out, int32_t* open,
                       int64_t misc[4]);
+/* ---- Pinned poses for frames a session has yet to make: "be in this pose at frame 412".  Slot s has a series of frames n = 0, 1, ...
+ * (the numbering of frames_out).  Window w covers series frames 30 w .. 30 w + 33 and OWNS all 34 of them for w = 0 and the frames
+ * 30 w + 4 .. otherwise (the ownership of a timeline edit).  A PIN is a target value for one element (c, n) of a frame the slot has
+ * not returned yet.  When the window that owns n runs, it runs through the inpainting branch of p_mean_variance
+ * (gaussian_diffusion.py:314-320; the TED tree re-noises the kept motion, the BEAT tree does not: n_prefix_tokens decides, as in
+ * edit_long) with inpainting_mask = true exactly on the pinned elements of the frames the window owns -- the prefix frames of a
+ * window w > 0 are never kept, the window before owned them -- and inpainted_motion = the pinned values there, zero elsewhere.  A
+ * window whose owned frames carry no pin runs exactly as without pins.
+ *
+ * A push still runs ls_long_pool_plan's rounds; each round is split into at most two sampling CALLS: first its unpinned rows, in
+ * ascending slot order, as a plain call, then its pinned rows, in ascending slot order, as an inpainting call; an empty half is
+ * skipped.  So a clip without a pin never enters the inpainting kernels because a neighbour has one, and a session with no pending
+ * pin makes precisely the calls it makes without pins.  ls_long_pool_pin_plan (no handle, no GPU) is the one definition: from
+ * windows_run [S], n_windows [S] (ls_long_pool_plan's) and the pending pinned frames of each slot (CSR: slot s holds pin_frames
+ * [pin_first[s], pin_first[s + 1]), in any order; both null: no pins) it gives the calls in order -- call_counts / call_pinned /
+ * call_rounds [call_capacity] (rows, 1 = inpainting call, the round it belongs to; each nullable) and the slots of call 0, then of
+ * call 1, ... in call_rows [row_capacity] (nullable) -- *n_calls and *n_entries = sum of n_windows.  LS_EINVAL: a null count array,
+ * a negative count or frame, a CSR that does not ascend from 0, an output array too short.
+ * Every call is one public sampling call: the tapes of a TAPE push are packed CALL after call (each the draws of one sampling call
+ * at its batch; the re-noise tape of the pinned calls, [n_exec, A, J, F, T] each, is handed over by ls_long_pool_pin_tape ahead of
+ * the next push of the session -- the handle forgets the pointer when that push returns, run or refused -- and read by it alone), un-keyed PHILOX draws row r of the q-th call since the open at sample_offset + r + (q << 48)
+ * with the re-noise on the inpainting stream (4), as ls_sample does, and a keyed pool keeps the clip's key and its own window, the
+ * re-noise being the third tape of ls_philox_rows.hip.  misc[2] of ls_long_pool_info counts calls.
+ *
+ * ls_long_pool_pins(h, horizon) enables pins on an open pool ahead of its first join (on a stream: ahead of its first push) and is
+ * where everything they need is allocated, for every batch 1..S, while nothing is in flight: the store -- per slot a ring of P =
+ * horizon rounded up to a multiple of 4 frames, [S][P][J F] values and bytes, frame n at n % P -- the inpainting planes and the
+ * denoiser's output plane -- and, where the schedule is set by then, the TED tree's re-noise tape buffer for its longest loop (the
+ * number of executed steps is a push's argument: a push checks that buffer again ahead of its first launch, as it does for the
+ * other tape buffers).  horizon >= nframes (LS_EINVAL otherwise).  A session that never calls it allocates nothing new.
+ * ls_long_pool_pin(h, slot, n, frames, poses, mask, on_device): frames HOST [n], distinct, each in [frames_out[slot],
+ * frames_out[slot] + horizon); poses [J, F, n]; mask [J, F, n] bytes, non-zero = pinned, NULL = the whole pose; on_device: poses
+ * and mask are device pointers.  Elements the mask leaves out keep what an earlier call pinned.  LS_EINVAL / LS_ESTATE before
+ * anything is uploaded: pins not enabled, a slot that is not open, n outside [1, horizon], a frame out of range or named twice.
+ * ls_long_pool_unpin(h, slot, n, frames) drops the pins of those frames (same range; a frame that holds none is no error), frames
+ * NULL with n == 0: of the whole slot.  ls_long_pool_join clears the slot's pins, and a slot that leaves drops the pins its clip
+ * never reached.  ls_long_pool_pin_info: pending pinned frames per slot (nullable, `capacity` entries), misc = {horizon, P}; zeros
+ * where the session has no pins.  With sag= a push that would run a pinned window returns LS_EUNSUPPORTED.
+ * Not built: pins on frames already returned, pins with sag= (a pinned window would start from edit_start(motion, mask, sag_out)
+ * at the pinned elements: a kernel form of its own), soft (fractional) pins, device-resident frame lists. */
+int ls_long_pool_pin_plan(int32_t n_slots, int32_t T, int32_t n_pre, const int64_t* windows_run, const int32_t* n_windows,
+                          const int32_t* pin_first, const int64_t* pin_frames, int32_t* call_rows, int32_t row_capacity,
+                          int32_t* call_counts, int32_t* call_pinned, int32_t* call_rounds, int32_t call_capacity, int32_t* n_calls,
+                          int32_t* n_entries);
+int ls_long_pool_pins(ls_handle* h, int32_t horizon);
+int ls_long_pool_pin(ls_handle* h, int32_t slot, int32_t n, const int64_t* frames, const float* poses, const unsigned char* mask,
+                     int32_t on_device);
+int ls_long_pool_unpin(ls_handle* h, int32_t slot, int32_t n, const int64_t* frames);
+int ls_long_pool_pin_tape(ls_handle* h, const float* inpaint_noise, int64_t n_floats, int32_t on_device);
+int ls_long_pool_pin_info(const ls_handle* h, int32_t capacity, int32_t* pending, int64_t misc[2]);
 int ls_step(ls_handle* h, const ls_step_args* a);
 int ls_plms_step(ls_handle* h, const ls_plms_step_args* a);
 /* elementwise q_sample (gaussian_diffusion.py:240-258) at schedule index i; pointers per on_device */

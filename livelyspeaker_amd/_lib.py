@@ -253,7 +253,7 @@ class LsResampleStreamPushArgs(C.Structure):
 
 EXPORTS = ("ls_abi_version", "ls_create", "ls_destroy", "ls_last_error", "ls_set_weight", "ls_commit_weights",
            "ls_set_schedule", "ls_prepare", "ls_prepare_async", "ls_long_prepare", "ls_long_prepare_ragged", "ls_long_plan_drop", "ls_long_sample", "ls_long_edit_plan", "ls_long_edit", "ls_long_edit_sag", "ls_long_edit_plan_compact", "ls_long_prepare_edit", "ls_long_edit_compact", "ls_long_edit_plan_mask", "ls_long_edit_mask", "ls_long_prepare_edit_mask", "ls_long_edit_compact_mask", "ls_long_edit_mask_pairs", "ls_long_stream_plan", "ls_long_stream_open", "ls_long_stream_push", "ls_long_stream_info", "ls_long_pool_plan", "ls_long_pool_open", "ls_long_pool_join", "ls_long_pool_push", "ls_long_pool_info", "ls_sample", "ls_forward", "ls_step", "ls_plms_step", "ls_q_sample", "ls_vb_terms", "ls_bpd", "ls_read",
-           "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_set_row_keys", "ls_long_pool_keyed", "ls_long_pool_set_key", "ls_long_pool_keys", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
+           "ls_get_timing", "ls_synchronize", "ls_stream_order", "ls_stream", "ls_sag_stream", "ls_train_stream", "ls_eval_stream", "ls_philox_x_init", "ls_set_row_keys", "ls_long_pool_keyed", "ls_long_pool_set_key", "ls_long_pool_keys", "ls_long_pool_pin_plan", "ls_long_pool_pins", "ls_long_pool_pin", "ls_long_pool_unpin", "ls_long_pool_pin_tape", "ls_long_pool_pin_info", "ls_torch_randn_advance", "ls_torch_randn", "ls_set_torch_ring_bytes", "ls_shard_range", "ls_set_precision", "ls_set_path", "ls_plan_query", "ls_plan_coop_slices", "ls_trng_randn", "ls_trng_fill_steps", "ls_trng_stats", "ls_trng_set_jump", "ls_trng_jump_check", "ls_trng_pairs_debug", "ls_sag_create", "ls_sag_destroy", "ls_sag_last_error",
            "ls_sag_set_weight", "ls_sag_commit_weights", "ls_sag_decode", "ls_sag_decode_async", "ls_sag_last_decode_ms",
            "ls_sag_enc_create", "ls_sag_enc_destroy", "ls_sag_enc_last_error", "ls_sag_enc_set_weight", "ls_sag_enc_commit_weights",
            "ls_sag_enc_encode", "ls_sag_enc_encode_async", "ls_sag_enc_last_encode_ms", "ls_sag_enc_stream",
@@ -356,6 +356,12 @@ def load_library(build_if_missing: bool = True):
     lib.ls_long_pool_keyed.argtypes = [C.c_void_p, C.c_int32]
     lib.ls_long_pool_set_key.argtypes = [C.c_void_p, C.c_int32, C.c_uint64]
     lib.ls_long_pool_keys.argtypes = [C.c_int32, C.POINTER(C.c_uint64), c_i64p, c_i32p, C.POINTER(C.c_uint64), C.c_int32, c_i32p]
+    lib.ls_long_pool_pin_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_i64p, c_i32p, c_i32p, c_i64p, c_i32p, C.c_int32, c_i32p, c_i32p, c_i32p, C.c_int32, c_i32p, c_i32p]
+    lib.ls_long_pool_pins.argtypes = [C.c_void_p, C.c_int32]
+    lib.ls_long_pool_pin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, c_i64p, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.ls_long_pool_unpin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, c_i64p]
+    lib.ls_long_pool_pin_tape.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    lib.ls_long_pool_pin_info.argtypes = [C.c_void_p, C.c_int32, c_i32p, c_i64p]
     lib.ls_set_row_keys.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32]
     lib.ls_long_pool_info.argtypes = [C.c_void_p, C.c_int32, c_i64p, c_i64p, c_i64p, c_i32p, c_i64p]
     lib.ls_post_stream_plan.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, c_i64p, c_i32p]
@@ -742,6 +748,44 @@ def long_pool_plan(samples_in, windows_run, samples_new, closing, open, audio_le
         rounds.append([int(s) for s in flat[at:at + A]])
         at += A
     return rounds, frames[:S].copy()
+
+
+def long_pool_pin_plan(windows_run, n_windows, pins, n_frames=34, n_pre=4):
+    """ls_long_pool_pin_plan (no GPU needed): the sampling calls of one push of a session with pinned poses, as a list of ``(round,
+    pinned, slots)`` in the order they run.  ``windows_run`` / ``n_windows``: host sequences [S] (``n_windows[s]``: the windows slot s
+    runs in the push, ``len([r for r in rounds if s in r])`` of ``long_pool_plan``); ``pins``: per slot the pending pinned frames, a
+    sequence of S sequences of series frames in any order (None: no pins).  Round r is its unpinned slots, ascending, as one plain
+    call, then its pinned ones, ascending, as one inpainting call; an empty half is no call.  Negative counts or frames, or a wrong
+    number of entries, raise ``ValueError``."""
+    lib = load_library()
+    ran = np.ascontiguousarray(np.asarray(windows_run).reshape(-1), dtype=np.int64)
+    wins = np.ascontiguousarray(np.asarray(n_windows).reshape(-1), dtype=np.int32)
+    S = int(ran.size)
+    if wins.size != S or (pins is not None and len(pins) != S):
+        raise ValueError(f"one entry per slot: got {[ran.size, wins.size] + ([] if pins is None else [len(pins)])}")
+    first = frames = None
+    if pins is not None:
+        per = [np.asarray(list(p), dtype=np.int64).reshape(-1) for p in pins]
+        first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([p.size for p in per])]), dtype=np.int32)
+        frames = np.ascontiguousarray(np.concatenate(per + [np.zeros(1, np.int64)]), dtype=np.int64)      # never empty: the pointer is real
+    p64, p32 = (lambda a: None if a is None else a.ctypes.data_as(c_i64p)), (lambda a: None if a is None else a.ctypes.data_as(c_i32p))
+    n_calls, n_entries = C.c_int32(), C.c_int32()
+
+    def run(rows, counts, pinned, rounds):
+        return lib.ls_long_pool_pin_plan(S, int(n_frames), int(n_pre), p64(ran), p32(wins), p32(first), p64(frames), p32(rows), 0 if rows is None else rows.size,
+                                         p32(counts), p32(pinned), p32(rounds), 0 if counts is None else counts.size, C.byref(n_calls), C.byref(n_entries))
+
+    if S < 1 or run(None, None, None, None) != 0:
+        raise ValueError(f"no pin plan for windows_run {ran.tolist()} n_windows {wins.tolist()} pins {pins!r}: counts and frames must be >= 0")
+    rows = np.zeros(max(int(n_entries.value), 1), np.int32)
+    counts, pinned, rounds = (np.zeros(max(int(n_calls.value), 1), np.int32) for _ in range(3))
+    if run(rows, counts, pinned, rounds) != 0:
+        raise EngineError("ls_long_pool_pin_plan failed")
+    calls, at = [], 0
+    for q in range(int(n_calls.value)):
+        calls.append((int(rounds[q]), bool(pinned[q]), [int(s) for s in rows[at:at + int(counts[q])]]))
+        at += int(counts[q])
+    return calls
 
 
 def long_pool_keys(keys, windows_run, n_windows):
@@ -1585,11 +1629,13 @@ class Engine(_Handle):
 
     def long_stream_push(self, audio, closing=False, emo=None, sag=None, text_features=None, sampler=LS_SAMPLER_DDIM, x_init=None,
                          eps_tape=None, noise_tape=None, skip_timesteps=0, eta=0.0, philox_seed=None, sample_offset=0, use_graph=True,
-                         clip_denoised=False, two_pass_always=False, device_out=False):
+                         clip_denoised=False, two_pass_always=False, device_out=False, inpaint_noise=None):
         """Feed ``audio`` [B, n] (n >= 0) to the open stream and run the k windows that complete (ls_long_stream_push; ``closing``: also
         the zero-padded ones still owed).  ``emo`` [B] / ``text_features`` [B, D] replace the held conditioning.  TAPE mode takes the
         draws of exactly those k windows (``x_init`` [k, B, J, F, T], ``eps_tape`` [k, n_exec, 2, B, D], ``noise_tape`` [k, n_exec, B, J, F,
-        T]; ``long_stream_plan`` tells k), PHILOX mode ``philox_seed``.  Returns ``(frames [B, J, F, 34 | 30 per window], k)``."""
+        T]; ``long_stream_plan`` tells k), PHILOX mode ``philox_seed``.  ``inpaint_noise`` (TAPE mode on the TED model, a stream with pins):
+        the re-noise draws of the kp windows that run pinned, [kp, n_exec, B, J, F, T] (``long_pool_pin_tape``).  Returns
+        ``(frames [B, J, F, 34 | 30 per window], k)``."""
         B, D = self.batch, self.D
         n = int(audio.shape[1])
         assert tuple(int(s) for s in audio.shape) == (B, n), (tuple(audio.shape), B)
@@ -1597,7 +1643,7 @@ class Engine(_Handle):
         first, k = long_stream_plan(info["samples_in"], n, self.cfg.audio_len, closing)
         npre = int(self.cfg.n_pre_seq)
         cap = k * (self.T - npre) + (npre if (k and first == 0) else 0)
-        m = self._marshal([audio if n else None, emo, text_features] + ([x_init, eps_tape, noise_tape] if k else []), device_out)
+        m = self._marshal([audio if n else None, emo, text_features] + ([x_init, eps_tape, noise_tape, inpaint_noise] if k else []), device_out)
         a = LsLongStreamPushArgs()
         n_exec = self._chain_sampler(a, m, sampler, skip_timesteps, use_graph, clip_denoised, two_pass_always, eta)
         a.closing, a.capacity, a.n_samples = int(bool(closing)), cap, n
@@ -1611,7 +1657,9 @@ class Engine(_Handle):
         frames = self._chain_frames(a, m, B, cap)
         n_frames, n_windows = C.c_int32(-1), C.c_int32(-1)
         a.n_frames, a.n_windows = C.pointer(n_frames), C.pointer(n_windows)
+        renoise = self._pin_tape(m, inpaint_noise if k else None)
         m.ready()
+        renoise()
         self._check(self.lib.ls_long_stream_push(self.h, C.byref(a)), "ls_long_stream_push")
         assert (int(n_frames.value), int(n_windows.value)) == (cap, k), (n_frames.value, n_windows.value, cap, k)
         if k == 0:          # nothing was waited for: torch's stream must not reuse the chunk before the engine's stream has read it
@@ -1653,13 +1701,15 @@ class Engine(_Handle):
 
     def long_pool_push(self, audio, lengths, closing=None, emo=None, text_features=None, given=None, sag=None, sampler=LS_SAMPLER_DDIM,
                        x_init=None, eps_tape=None, noise_tape=None, skip_timesteps=0, eta=0.0, philox_seed=None, sample_offset=0,
-                       use_graph=True, clip_denoised=False, two_pass_always=False, device_out=False):
+                       use_graph=True, clip_denoised=False, two_pass_always=False, device_out=False, inpaint_noise=None):
         """Feed the ragged chunk ``audio`` [S, n_max] -- ``lengths`` [S] (host) samples per slot -- and run the rounds of
         ``long_pool_plan`` (ls_long_pool_push).  ``closing`` [S] (host): the slot leaves after the windows it is owed.  ``emo`` [S] /
         ``text_features`` [S, D] replace the held conditioning of the slots whose ``given`` [S] (host) has bit 0 / bit 1 set.  TAPE mode
         takes the draws packed round after round at each round's batch A (``x_init`` [sum A, J, F, T], flat ``eps_tape`` / ``noise_tape``
         holding per round [n_exec, 2, A, D] / [n_exec, A, J, F, T]), PHILOX mode ``philox_seed`` (a keyed pool, ``long_pool_keyed``, draws
-        at the slots' keys and does not read ``sample_offset``).  Returns ``(frames [S, J, F, K], counts
+        at the slots' keys and does not read ``sample_offset``).  A pool with pending pins (``long_pool_pin``) runs the calls of
+        ``long_pool_pin_plan`` in place of bare rounds: the tapes are then packed call after call, and ``inpaint_noise`` (TAPE mode on
+        the TED model) holds the re-noise draws of the pinned calls, flat, per call [n_exec, A, J, F, T].  Returns ``(frames [S, J, F, K], counts
         int32 [S], rounds)`` with K the most frames any slot got; a slot's row is zero behind its own count."""
         info = self.long_pool_info()        # of the last pool, whatever has been prepared on the handle since
         S, D = info["capacity"], self.D
@@ -1671,7 +1721,7 @@ class Engine(_Handle):
         assert lens.shape == cl.shape == (S,) and (gv is None or gv.shape == (S,)), (lens.shape, cl.shape, S)
         rounds, per_slot = long_pool_plan(info["samples_in"], info["windows_run"], lens, cl, info["open"], self.cfg.audio_len)
         cap, rows = int(per_slot.max()), sum(len(r) for r in rounds)
-        m = self._marshal([audio if n else None, emo, text_features] + ([x_init, eps_tape, noise_tape] if rows else []), device_out)
+        m = self._marshal([audio if n else None, emo, text_features] + ([x_init, eps_tape, noise_tape, inpaint_noise] if rows else []), device_out)
         a = LsLongPoolPushArgs()
         n_exec = self._chain_sampler(a, m, sampler, skip_timesteps, use_graph, clip_denoised, two_pass_always, eta)
         a.capacity, a.n_max = cap, n
@@ -1688,12 +1738,55 @@ class Engine(_Handle):
         frames = self._chain_frames(a, m, S, cap)
         counts, n_rounds = np.full(S, -1, np.int32), C.c_int32(-1)
         a.n_frames, a.n_rounds = counts.ctypes.data_as(c_i32p), C.pointer(n_rounds)
+        renoise = self._pin_tape(m, inpaint_noise if rows else None)
         m.ready()
+        renoise()
         self._check(self.lib.ls_long_pool_push(self.h, C.byref(a)), "ls_long_pool_push")
         assert counts.tolist() == per_slot.tolist() and int(n_rounds.value) == len(rounds), (counts, per_slot, n_rounds.value, rounds)
         if not rounds:      # nothing was waited for: torch's stream must not reuse the chunk before the engine's stream has read it
             m.done_async()
         return frames, counts, rounds
+
+    # ---- pinned poses for frames a session has yet to make (a pool and a stream alike) -----------
+    def long_pool_pins(self, horizon):
+        """Enable pins on the open session (ls_long_pool_pins): a pool nobody has joined, a stream nothing was pushed to.  ``horizon``
+        >= nframes: a pin may name a frame in ``[frames_out, frames_out + horizon)``.  The store and the inpainting planes are allocated here."""
+        self._check(self.lib.ls_long_pool_pins(self.h, int(horizon)), "ls_long_pool_pins")
+
+    def long_pool_pin(self, slot, frames, poses, mask=None):
+        """Pin elements of K frames the clip in ``slot`` has not returned yet (ls_long_pool_pin): ``frames`` [K] host ints (series
+        frames, distinct), ``poses`` [J, F, K], ``mask`` [J, F, K] bool (True = pinned; None: the whole pose), host or device."""
+        fr = np.ascontiguousarray(np.asarray(frames).reshape(-1), dtype=np.int64)
+        K = int(fr.size)
+        m = _Marshal(self.device, poses, mask, stream=self._stream)
+        pp, pm = m.f32(poses, (self.J, self.F, K)), m.u8(mask, (self.J, self.F, K))
+        m.ready()
+        self._check(self.lib.ls_long_pool_pin(self.h, int(slot), K, fr.ctypes.data_as(c_i64p), pp, pm, int(m.on_device)), "ls_long_pool_pin")
+
+    def long_pool_unpin(self, slot, frames=None):
+        """Drop the pins of ``frames`` (host ints) of ``slot``, or with None all of them (ls_long_pool_unpin)."""
+        if frames is None:
+            self._check(self.lib.ls_long_pool_unpin(self.h, int(slot), 0, None), "ls_long_pool_unpin")
+            return
+        fr = np.ascontiguousarray(np.asarray(frames).reshape(-1), dtype=np.int64)
+        self._check(self.lib.ls_long_pool_unpin(self.h, int(slot), int(fr.size), fr.ctypes.data_as(c_i64p)), "ls_long_pool_unpin")
+
+    def _pin_tape(self, m, inpaint_noise):
+        """The re-noise tape of the coming push's pinned calls through ``m``; returns the call that hands it over (ls_long_pool_pin_tape),
+        to be made once ``m`` is ready.  None: nothing to hand over."""
+        if inpaint_noise is None:
+            return lambda: None
+        n = int(np.prod(tuple(inpaint_noise.shape)))
+        ptr = m.f32(inpaint_noise)
+        return lambda: self._check(self.lib.ls_long_pool_pin_tape(self.h, ptr, n, int(m.on_device)), "ls_long_pool_pin_tape")
+
+    def long_pool_pin_info(self) -> dict:
+        """ls_long_pool_pin_info: ``pending`` int32 [S] -- the pinned frames of each slot whose window has yet to run -- and the ints
+        ``horizon`` and ``ring`` (0 where the session has no pins)."""
+        S = self.long_pool_info()["capacity"] or int(self.batch or 0)
+        pend, misc = np.zeros(max(S, 1), np.int32), (C.c_int64 * 2)()
+        self._check(self.lib.ls_long_pool_pin_info(self.h, S, pend.ctypes.data_as(c_i32p), misc), "ls_long_pool_pin_info")
+        return {"pending": pend[:S].copy(), "horizon": int(misc[0]), "ring": int(misc[1])}
 
     def long_pool_info(self) -> dict:
         """ls_long_pool_info of the current (or last) pool: per-slot numpy arrays samples_in, windows_run, frames_out (int64) and open

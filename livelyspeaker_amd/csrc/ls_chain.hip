@@ -22,6 +22,8 @@
 // A streaming SESSION (ls_long_pool_push; ls_long_stream_push: the pool whose slots move together) keeps the hand-off per slot:
 // k_pool_gather and k_pool_scatter (at the end) move one round's active slots -- a window of audio out of each slot's circular ring,
 // its hand-off poses, its held conditioning -- into and out of the compact rows a sampling call at that batch reads.
+// PINNED POSES of frames a slot has yet to return (ls_long_pool_pin) live in a ring per slot: k_pool_pin_store / k_pool_pin_clear
+// write it, k_pool_pin_gather turns it into the inpainting planes of the rows of a pinned call (at the end).
 #include "ls_internal.h"
 
 namespace ls {
@@ -403,6 +405,74 @@ hipError_t launch_pool_scatter(const PoolArgs& a, int A, hipStream_t st) {
     const size_t lds = (size_t)a.T * (a.JF | 1) * sizeof(float);
     if (!pool_args_ok(a, A) || lds > 64 * 1024 || !a.prev || !a.frames || a.T_total < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_pool_scatter, dim3(A), dim3(256), lds, st, a);
+    return hipGetLastError();
+}
+
+// Pinned poses of a session's slots (ls_long_pool_pin; PinArgs in ls_internal.h): a ring of P series frames per slot, frame n at
+// n % P, values and one byte per element, both [S][P][JF] -- JF innermost, so the store's writes and both sides of the gather run
+// along the channels, as the internal-layout planes [A][T][JF] do.
+// k_pool_pin_store: one workgroup per frame k of the call.  The caller's [J, F, K] layout is transposed on the way in: the reads of
+// poses / mask walk a column (stride K), the writes a row of the ring.  An element the mask leaves out is not touched.
+// Algorithmic bytes per frame (fp32, whole pose): reads 4 + 4 JF (+ JF mask bytes), writes 5 JF: 0.25 KB TED, 2.5 KB BEAT; not measured.
+__global__ __launch_bounds__(256) void k_pool_pin_store(const PinArgs a) {
+    const int k = blockIdx.x, JF = a.JF, K = a.K;
+    const size_t at = ((size_t)a.slot * a.P + a.pos[k]) * JF;
+    for (int c = threadIdx.x; c < JF; c += 256) {
+        if (a.mask && !a.mask[(size_t)c * K + k]) continue;
+        a.val[at + c] = a.poses[(size_t)c * K + k];
+        a.bit[at + c] = 1;
+    }
+}
+// The un-pin: the bytes of the K frames at pos (null: of frames 0 .. K-1 = the whole ring of the slot) become 0; the values stay, no
+// byte names them.  Writes JF bytes per frame; not measured.
+__global__ __launch_bounds__(256) void k_pool_pin_clear(const PinArgs a) {
+    const int k = blockIdx.x, JF = a.JF;
+    const size_t at = ((size_t)a.slot * a.P + (a.pos ? a.pos[k] : k)) * JF;
+    for (int c = threadIdx.x; c < JF; c += 256) a.bit[at + c] = 0;
+}
+// One workgroup per row of a pinned call.  It reads its table row once (slot, f0 and the ring position of the window's frame 0: uniform
+// loads, nothing else depends on a loaded value but the byte that selects), and writes the row's motion and maskf planes: for the
+// frames f0 .. T-1 the window owns, the pinned value and 1 where the ring's byte is set, 0 and 0 elsewhere -- the prefix frames of a
+// window w > 0 are never kept.  A byte it found set is cleared, so the position is free for frame n + P.  T <= P: the window's frames
+// wrap at most once and sit at distinct positions, the rows of a call are distinct slots, so every element has one writer; no atomics.
+// Algorithmic bytes per row (fp32): reads 32 (table) + (T - f0) JF bytes + 4 per pinned element, writes 2 * 4 T JF (the planes) + 1
+// per pinned element: at most 8.3 KB TED, 86 KB BEAT; not measured.
+__global__ __launch_bounds__(256) void k_pool_pin_gather(const PinArgs a) {
+    const int r = blockIdx.x, JF = a.JF, T = a.T, P = a.P;
+    const int* row = a.table + (size_t)r * kPoolRow;
+    const int slot = row[0], f0 = row[3], p0 = row[5];
+    float* mo = a.motion + (size_t)r * T * JF;
+    float* mk = a.maskf + (size_t)r * T * JF;
+    const size_t base = (size_t)slot * P;
+    for (int i = threadIdx.x; i < T * JF; i += 256) {
+        const int f = i / JF, c = i - f * JF;
+        float v = 0.f, m = 0.f;
+        if (f >= f0) {
+            const int p = p0 + f >= P ? p0 + f - P : p0 + f;
+            const size_t at = (base + p) * JF + c;
+            if (a.bit[at]) { v = a.val[at]; m = 1.f; a.bit[at] = 0; }
+        }
+        mo[i] = v;
+        mk[i] = m;                                      // inpainting_mask: true = keep the given motion
+    }
+}
+
+static bool pin_args_ok(const PinArgs& a) {
+    return a.val && a.bit && a.S >= 1 && a.S <= 65535 && a.JF >= 1 && a.T >= 1 && a.P >= a.T && (a.P & 3) == 0;
+}
+hipError_t launch_pool_pin_store(const PinArgs& a, hipStream_t st) {
+    if (!pin_args_ok(a) || a.slot < 0 || a.slot >= a.S || a.K < 1 || a.K > a.P || !a.poses || !a.pos) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pool_pin_store, dim3(a.K), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_pool_pin_clear(const PinArgs& a, hipStream_t st) {
+    if (!pin_args_ok(a) || a.slot < 0 || a.slot >= a.S || a.K < 1 || a.K > a.P || (!a.pos && a.K != a.P)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pool_pin_clear, dim3(a.K), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_pool_pin_gather(const PinArgs& a, int A, hipStream_t st) {
+    if (!pin_args_ok(a) || A < 1 || A > a.S || !a.table || !a.motion || !a.maskf) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pool_pin_gather, dim3(A), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

@@ -115,6 +115,7 @@ struct Window {
     const float* text = nullptr;        // SAG: its text features [Bw][512]
     const float *x_init = nullptr, *eps_tape = nullptr, *noise_tape = nullptr, *inpaint_noise = nullptr;      // TAPE: its draws
     bool host_tapes = false;            // ... in host memory: uploaded here, one window at a time (a session's round: the staging does not grow with the call)
+    bool host_inz = false;              // inpaint_noise is in host memory (a session's pinned call: ls_long_pool_pin_tape), uploaded likewise
     bool resident_inpaint = false;      // a timeline edit: the inpainting planes are on the device (k_edit_gather)
     const EditArgs* edit_start = nullptr;       // a scripted edit: behind the decode, k_edit_start puts cc.sag_out under the editable elements of the init plane
     CachePolicy policy = kReplace;
@@ -185,6 +186,10 @@ int run_window(ls_handle* h, ChainCall& cc, const Window& win) {
             if ((rc = ingest(h, h->lg_x, win.x_init, per_x * sizeof(float), 0)) != LS_OK || (rc = ingest(h, h->lg_eps, win.eps_tape, per_e * sizeof(float), 0)) != LS_OK ||
                 (rc = ingest(h, h->lg_nz, win.noise_tape, per_n * sizeof(float), 0)) != LS_OK) return rc;
             wa.x_init = h->lg_x.f(); wa.eps_tape = h->lg_eps.f(); wa.noise_tape = h->lg_nz.f();
+        }
+        if (win.inpaint_noise && win.host_inz) {
+            if ((rc = ingest(h, h->lg_inz, win.inpaint_noise, (size_t)cc.n_exec * Bw * h->JF * T * sizeof(float), 0)) != LS_OK) return rc;
+            wa.inpaint_noise = h->lg_inz.f();
         }
     }
     // The loop's advance_tags uploads call_host (24 bytes of pageable memory) as every ls_sample does: the runtime takes such a source into
@@ -266,8 +271,9 @@ int session_is_open(ls_handle* h, const char* entry, bool stream) {
 
 // what a session holds on the device, as allocated: rings, hand-off stores, held conditioning, round table, gathered windows, features
 int64_t session_bytes(const ls_handle* h) {
+    const size_t pins = h->pl_pin_P ? h->pl_pin_val.bytes + h->pl_pin_bit.bytes : 0;      // the pin store, where the session has one
     return (int64_t)(h->pl_ring.bytes + h->pl_hand.bytes + h->pl_vid.bytes + h->pl_emo_id.bytes + h->pl_scale.bytes + h->pl_emotok.bytes +
-                     h->pl_text.bytes + h->pl_ctext.bytes + h->pl_table.bytes + h->lg_clips.bytes + h->lg_featc.bytes);
+                     h->pl_text.bytes + h->pl_ctext.bytes + h->pl_table.bytes + h->lg_clips.bytes + h->lg_featc.bytes + pins);
 }
 
 // the held conditioning of the n slots from s on, from the caller (host or device) into the per-slot stores
@@ -368,20 +374,52 @@ int session_open(ls_handle* h, int S, const ls_long_stream_cond* c) {
     h->pl_open.assign((size_t)S, c ? 1 : 0); h->pl_have_emo.assign((size_t)S, 0); h->pl_have_text.assign((size_t)S, 0);
     h->pl_styled.clear();
     h->pl_keyed = false; h->pl_joins = 0; h->pl_key.assign((size_t)S, 0);
+    h->pl_pin_H = h->pl_pin_P = 0; h->pl_pin_frames.clear(); h->pl_pin_tape = nullptr; h->pl_pin_tape_floats = 0;
     h->pl_lockstep = c ? ls_handle::kLockstep : ls_handle::kPool;
     h->pl_state = ls_handle::kStreamOpen;
     return LS_OK;
 }
 
-// Everything of a push behind its argument checks.  win[s]: the windows slot s runs (ls_long_pool_plan), rounds: the plan's slots
-// round after round.  Ahead of every round each slot takes as much of its chunk as its ring has room for -- a slot's next window
-// always fits behind the samples its earlier windows made dead -- so the rounds are the plan's whatever the chunk sizes.  Per round:
-// k_pool_gather -> WavEncoder -> k_build_feats at batch A, the per-batch stages at A, the window body, k_pool_scatter.  Nothing is
-// allocated from the first launch on.
+// The sampling calls of a push (ls_long_pool_pin_plan): the slots of call 0, then of call 1, ... in rows; per call its rows, whether
+// it is a pinned (inpainting) call, and the round of ls_long_pool_plan it belongs to.  Without a pending pin the calls are the rounds.
+struct PoolCalls { std::vector<int32_t> rows, counts, pinned, round; };
+
+// the pending pinned frames of slot s that window w owns leave the host mirror: k_pool_pin_gather has cleared their bytes
+void pins_consumed(ls_handle* h, int s, long long w) {
+    const long long S = h->T - h->cfg.n_pre_seq, lo = w ? w * S + h->cfg.n_pre_seq : 0, hi = w * S + h->T;
+    std::vector<long long>& v = h->pl_pin_frames[(size_t)s];
+    v.erase(std::remove_if(v.begin(), v.end(), [&](long long n) { return n >= lo && n < hi; }), v.end());
+}
+PinArgs pin_args(const ls_handle* h) {
+    PinArgs p{};
+    p.val = h->pl_pin_val.f(); p.bit = static_cast<unsigned char*>(h->pl_pin_bit.p);
+    p.S = h->pl_S; p.P = h->pl_pin_P; p.JF = h->JF; p.T = h->T;
+    return p;
+}
+// every pin of slot s goes: the bytes of its whole ring, and the mirror
+int pins_drop(ls_handle* h, int s) {
+    if (!h->pl_pin_P || h->pl_pin_frames[(size_t)s].empty()) return LS_OK;
+    PinArgs p = pin_args(h);
+    p.slot = s; p.K = p.P;
+    HIPCHK(h, launch_pool_pin_clear(p, h->stream));
+    h->pl_pin_frames[(size_t)s].clear();
+    return LS_OK;
+}
+
+// Everything of a push behind its argument checks.  win[s]: the windows slot s runs (ls_long_pool_plan), pc: the plan's calls, round
+// after round (a round is one call, or with pinned poses two: its unpinned rows, then its pinned ones).  Ahead of every round each
+// slot takes as much of its chunk as its ring has room for -- a slot's next window
+// always fits behind the samples its earlier windows made dead -- so the rounds are the plan's whatever the chunk sizes.  Per call:
+// k_pool_gather (a pinned call: and k_pool_pin_gather) -> WavEncoder -> k_build_feats at batch A, the per-batch stages at A, the
+// window body, k_pool_scatter.  Nothing is allocated from the first launch on.
 int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_args* a, ChainCall& cc, const std::vector<int32_t>& win,
-                     const std::vector<int32_t>& rounds, int n_rounds, const std::vector<uint64_t>& row_keys) {
+                     const PoolCalls& pc, int n_rounds, const std::vector<uint64_t>& row_keys) {
     const int S = h->pl_S, JF = h->JF, T = h->T, npre = h->cfg.n_pre_seq, AL = h->cfg.audio_len, R = h->pl_R, od = a->on_device, cap = a->capacity;
     const bool beat = h->cfg.n_prefix_tokens == 2, lockstep = h->pl_lockstep != ls_handle::kPool;
+    const int n_calls = (int)pc.counts.size();
+    const bool noised = !beat;          // the TED tree re-noises the kept motion of a pinned window, the BEAT tree does not
+    bool any_pinned = false;
+    for (int32_t p : pc.pinned) any_pinned = any_pinned || p != 0;
     const hipMemcpyKind kind = od ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     hipStream_t st = h->stream;
     int rc;
@@ -401,8 +439,15 @@ int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_ar
         if (cc.tape) {
             if ((rc = ensure_pinned(h, h->eps_tape, (size_t)cc.n_exec * 2 * S * kD * sizeof(float))) != LS_OK || (rc = ensure_pinned(h, h->noise_tape, cc.n_exec * nxS)) != LS_OK) return rc;
             if (!od) { HIPCHK(h, h->lg_x.ensure(nxS)); HIPCHK(h, h->lg_eps.ensure((size_t)cc.n_exec * 2 * S * kD * sizeof(float))); HIPCHK(h, h->lg_nz.ensure(cc.n_exec * nxS)); }
+            if (any_pinned && noised) {     // the re-noise tape of a pinned call
+                if ((rc = ensure_pinned(h, h->inp_tape, cc.n_exec * nxS)) != LS_OK) return rc;
+                if (!h->pl_pin_tape_od) HIPCHK(h, h->lg_inz.ensure(cc.n_exec * nxS));
+            }
         }
         if (!row_keys.empty() && (rc = size_key_ring(h, S, cc.n_exec)) != LS_OK) return rc;       // grows only when the schedule or the ring's budget did since the pool was keyed
+        if (!row_keys.empty() && h->pl_pin_P && noised && (rc = size_key_ring(h, S, cc.n_exec, true)) != LS_OK) return rc;     // ... the re-noise tape beside them, likewise
+        if (h->pl_pin_P && ((rc = ensure_pinned(h, h->inp_maskf, nxS)) != LS_OK || (rc = ensure_pinned(h, h->inp_motion, nxS)) != LS_OK ||
+                            (rc = ensure_pinned(h, h->fwd_cfg, nxS)) != LS_OK)) return rc;       // in place since ls_long_pool_pins
         if (a->sag) {
             cc.sag = a->sag; cc.sag_st = ls_sag_stream(a->sag);
             HIPCHK(h, hipMemsetAsync(h->lg_mask.p, 1, (size_t)S * T, st));
@@ -439,12 +484,19 @@ int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_ar
     pa.frames = out;
     pa.S = S; pa.AL = AL; pa.R = R; pa.JF = JF; pa.T = T; pa.KPP = h->KPP; pa.n_pre = npre; pa.T_total = cap;
     std::vector<int> t_off((size_t)S, 0), table((size_t)S * kPoolRow, 0);
-    size_t at = 0;              // position in `rounds` = rows of the rounds run so far (the packed tapes)
-    for (int r = 0; r < n_rounds; ++r) {
-        if ((rc = feed()) != LS_OK) return rc;
-        int A = 0;
-        for (int s = 0; s < S; ++s) A += win[(size_t)s] > r;
-        const int32_t* slots = rounds.data() + at;
+    PinArgs pin = pin_args(h);
+    pin.table = pa.table; pin.motion = h->inp_motion.f(); pin.maskf = h->inp_maskf.f();
+    const size_t per_n = (size_t)cc.n_exec * JF * T;        // floats of one row's noise tape
+    size_t at = 0, at_inz = 0;  // position in pc.rows = rows of the calls run so far (the packed tapes); likewise among the pinned calls' rows (the re-noise tape)
+    int fed_round = -1;
+    for (int q = 0; q < n_calls; ++q) {
+        const int A = pc.counts[(size_t)q];
+        const bool pinned = pc.pinned[(size_t)q] != 0;
+        if (pc.round[(size_t)q] != fed_round) {         // once per round, ahead of its first call
+            if ((rc = feed()) != LS_OK) return rc;
+            fed_round = pc.round[(size_t)q];
+        }
+        const int32_t* slots = pc.rows.data() + at;
         bool ones = true;
         for (int i = 0; i < A; ++i) {
             const int s = slots[i];
@@ -454,6 +506,7 @@ int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_ar
             if (t_off[(size_t)s] + T - f0 > cap) return fail(h, LS_ESTATE, "%s: slot %d runs more frames than the call was planned for", entry, s);
             int* row = &table[(size_t)i * kPoolRow];
             row[0] = s; row[1] = (int)(lo % R); row[2] = valid; row[3] = f0; row[4] = t_off[(size_t)s];
+            row[5] = pinned ? (int)(w * (T - npre) % h->pl_pin_P) : 0;         // a pinned call: where the window's frame 0 sits in the slot's pin ring
             ones = ones && h->pl_scale_host[(size_t)s] == 1.0f;
         }
         // the round's table: one upload of pageable memory, taken into the runtime's staging memory before the call returns (as call_host is)
@@ -461,6 +514,7 @@ int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_ar
         // a keyed pool: the round's rows of the key table, likewise; the captured loop of batch A reads them from row_gidx
         if (!row_keys.empty()) HIPCHK(h, hipMemcpyAsync(h->row_gidx.p, row_keys.data() + at, (size_t)A * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         HIPCHK(h, launch_pool_gather(pa, A, st));
+        if (pinned) HIPCHK(h, launch_pool_pin_gather(pin, A, st));      // the inpainting planes of rows [0, A); the bytes it reads set are cleared
         if ((rc = run_wav_encoder(h, h->lg_clips.f(), A)) != LS_OK) return rc;
         HIPCHK(h, launch_build_feats(h->origin_x.f(), h->c4.f(), h->lg_featp.f(), h->lg_featc.f(), A, JF, h->KPP, 0, st, T));
         // from here on the handle is prepared for a batch of A: its scales decide the single-pass form, its size the step plan
@@ -478,24 +532,31 @@ int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_ar
             h->pl_styled.assign(slots, slots + A);
         }
         Window wn;
-        wn.w = h->pl_rounds; wn.Bw = A; wn.featc = h->lg_featc.f(); wn.text = a->sag ? h->pl_ctext.f() : nullptr; wn.first = r == 0;
-        // a pool: a batch size met once is met again, and kKeep never destroys a graph under the replays in flight.  A stream has one
-        // batch and one key per call: a key that is not cached replaces what is
-        wn.policy = lockstep ? kReplace : kKeep;
+        wn.w = h->pl_rounds; wn.Bw = A; wn.featc = h->lg_featc.f(); wn.text = a->sag ? h->pl_ctext.f() : nullptr; wn.first = q == 0;
+        wn.resident_inpaint = pinned;       // the reference's inpainting branch on the planes k_pool_pin_gather filled; its own captured loop
+        cc.wa.inpaint_noised = pinned && noised ? 1 : 0;
+        // a pool: a batch size met once is met again, and kKeep never destroys a graph under the replays in flight.  A stream without
+        // pins has one batch and one key per call: a key that is not cached replaces what is.  A stream WITH pins has two loops at its
+        // batch, the plain one and the inpainting one, and one push may run both with no host wait between them: it keeps both, like a
+        // pool (ls_long_pool_pins emptied the cache, so both fit)
+        wn.policy = lockstep && !h->pl_pin_P ? kReplace : kKeep;
         wn.keyed = !row_keys.empty();
         if (cc.tape) {
             wn.x_init = a->x_init + at * JF * T; wn.eps_tape = a->eps_tape + at * cc.n_exec * 2 * kD; wn.noise_tape = a->noise_tape + at * cc.n_exec * JF * T;
             wn.host_tapes = !od;
+            if (pinned && noised) { wn.inpaint_noise = h->pl_pin_tape + at_inz * per_n; wn.host_inz = !h->pl_pin_tape_od; }
         }
         if ((rc = run_window(h, cc, wn)) != LS_OK) return rc;
         pa.prev = x_plane(h, cc.n_exec);
         HIPCHK(h, launch_pool_scatter(pa, A, st));
         for (int i = 0; i < A; ++i) {
+            if (pinned) pins_consumed(h, slots[i], h->pl_windows[(size_t)slots[i]]);
             t_off[(size_t)slots[i]] += T - table[(size_t)i * kPoolRow + 3];
             ++h->pl_windows[(size_t)slots[i]];
         }
-        ++h->pl_rounds;
+        ++h->pl_rounds;         // sampling calls since the open: the PHILOX window index of the next one
         at += (size_t)A;
+        if (pinned) at_inz += (size_t)A;
     }
     if ((rc = feed()) != LS_OK) return rc;
     bool any = false;
@@ -504,7 +565,10 @@ int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_ar
         any = any || fed[(size_t)s] > 0;
         h->pl_frames[(size_t)s] += t_off[(size_t)s];
         if (a->n_frames) a->n_frames[s] = t_off[(size_t)s];
-        if (closing(s)) h->pl_open[(size_t)s] = 0;
+        if (closing(s)) {
+            if ((rc = pins_drop(h, s)) != LS_OK) return rc;        // the pins the clip never reached
+            h->pl_open[(size_t)s] = 0;
+        }
     }
     if (a->n_rounds) *a->n_rounds = n_rounds;
     if (n_rounds == 0) {        // no sampling work: a host chunk is the caller's again once its copies are done, a device chunk is read in stream order
@@ -514,10 +578,18 @@ int session_push_run(ls_handle* h, const char* entry, const ls_long_pool_push_ar
     return chain_finish(h, cc, {{od ? nullptr : a->frames, out, out_bytes}});
 }
 
+// The re-noise tape ls_long_pool_pin_tape handed over is the next push's alone: however that push ends -- refused by its entry, refused
+// here, or run -- the handle forgets the caller's pointer
+struct ForgetTape {
+    ls_handle* h;
+    ~ForgetTape() { h->pl_pin_tape = nullptr; h->pl_pin_tape_floats = 0; }
+};
+
 // A push of a session behind its entry's own refusals: the plan, the refusals the plan decides, the sampler arguments, the rounds.
 // Nothing ahead of session_push_run touches the device.
 int session_push(ls_handle* h, const char* entry, const ls_long_pool_push_args* a) {
     const int S = h->pl_S;
+    const ForgetTape forget_tape{h};
     if (!a->lengths || a->n_max < 0 || (a->n_max > 0 && !a->audio)) return fail(h, LS_EINVAL, "%s: lengths, and audio with n_max > 0", entry);
     if (a->capacity < 0 || (a->capacity > 0 && !a->frames)) return fail(h, LS_EINVAL, "%s: capacity without frames", entry);
     if (a->emo && h->cfg.n_prefix_tokens != 2) return fail(h, LS_EINVAL, "%s: emo is a BEAT conditioning", entry);
@@ -545,22 +617,62 @@ int session_push(ls_handle* h, const char* entry, const ls_long_pool_push_args* 
             if (a->sag && !h->pl_have_text[(size_t)s] && !(g & 2)) return fail(h, LS_EINVAL, "%s: sag needs text_features for the first window (slot %d)", entry, s);
         }
     }
+    // the sampling calls: the rounds, each split where pending pins say so (ls_long_pool_pin_plan; without pins: the rounds themselves)
+    PoolCalls pc;
+    int32_t n_calls = 0;
+    long long pinned_rows = 0;
+    {
+        std::vector<int32_t> first;
+        std::vector<int64_t> pend;
+        if (h->pl_pin_P) {
+            first.assign((size_t)S + 1, 0);
+            for (int s = 0; s < S; ++s) {
+                pend.insert(pend.end(), h->pl_pin_frames[(size_t)s].begin(), h->pl_pin_frames[(size_t)s].end());
+                first[(size_t)s + 1] = (int32_t)pend.size();
+            }
+        }
+        const int32_t* pf = h->pl_pin_P ? first.data() : nullptr;
+        const int64_t* pn = pend.empty() ? nullptr : pend.data();
+        int32_t n_rows = 0;
+        if (ls_long_pool_pin_plan(S, h->T, h->cfg.n_pre_seq, ran.data(), win.data(), pf, pn, nullptr, 0, nullptr, nullptr, nullptr, 0, &n_calls, &n_rows) != LS_OK || n_rows != n_entries)
+            return fail(h, LS_EINVAL, "%s: ls_long_pool_pin_plan failed", entry);
+        pc.rows.resize((size_t)n_entries); pc.counts.resize((size_t)n_calls); pc.pinned.resize((size_t)n_calls); pc.round.resize((size_t)n_calls);
+        if (n_calls > 0 && ls_long_pool_pin_plan(S, h->T, h->cfg.n_pre_seq, ran.data(), win.data(), pf, pn, pc.rows.data(), n_entries, pc.counts.data(), pc.pinned.data(),
+                                                 pc.round.data(), n_calls, &n_calls, &n_rows) != LS_OK)
+            return fail(h, LS_EINVAL, "%s: ls_long_pool_pin_plan failed", entry);
+        for (int q = 0; q < n_calls; ++q) pinned_rows += pc.pinned[(size_t)q] ? pc.counts[(size_t)q] : 0;
+    }
+    if (pinned_rows > 0 && a->sag) return fail(h, LS_EUNSUPPORTED, "%s: a pinned window with sag is not built (it would start from edit_start(motion, mask, sag_out))", entry);
     ChainCall cc;
     int rc;
     if ((rc = chain_args(h, entry, a, n_rounds > 0, cc)) != LS_OK) return rc;
-    std::vector<uint64_t> row_keys;         // a keyed pool under PHILOX: one gidx per row of every round (ls_long_pool_keys); empty otherwise
+    if (pinned_rows > 0 && cc.tape && h->cfg.n_prefix_tokens != 2) {       // TED re-noises the kept motion: the pinned calls' third tape
+        const long long need = pinned_rows * cc.n_exec * h->JF * h->T;
+        if (!h->pl_pin_tape || h->pl_pin_tape_floats != need)
+            return fail(h, LS_EINVAL, "%s: TAPE mode with pinned windows needs the re-noise tape of its %lld pinned rows (%lld floats, ls_long_pool_pin_tape), got %lld",
+                        entry, pinned_rows, need, h->pl_pin_tape ? h->pl_pin_tape_floats : 0ll);
+    }
+    std::vector<uint64_t> row_keys;         // a keyed pool under PHILOX: one gidx per row of every call (ls_long_pool_keys); empty otherwise
     if (n_rounds > 0 && !cc.tape && h->pl_keyed) {
-        row_keys.resize((size_t)n_entries);
+        std::vector<uint64_t> round_keys((size_t)n_entries);
         int32_t n_keys = 0;
-        const int krc = ls_long_pool_keys(S, h->pl_key.data(), ran.data(), win.data(), row_keys.data(), n_entries, &n_keys);
+        const int krc = ls_long_pool_keys(S, h->pl_key.data(), ran.data(), win.data(), round_keys.data(), n_entries, &n_keys);
         if (krc == LS_ESTATE) return fail(h, LS_ESTATE, "%s: a clip of a keyed pool runs at most 2^16 windows; let it leave and join again under another key", entry);
         if (krc != LS_OK || n_keys != n_entries) return fail(h, LS_EINVAL, "%s: ls_long_pool_keys failed", entry);
+        // the table is in round order; a round's calls hold the same rows, the unpinned ones first: each row keeps its slot's key
+        std::vector<uint64_t> of_slot((size_t)n_rounds * S, 0);
+        for (size_t i = 0, r = 0; r < (size_t)n_rounds; ++r)
+            for (int s = 0; s < S; ++s)
+                if (win[(size_t)s] > (int)r) of_slot[r * S + (size_t)s] = round_keys[i++];
+        row_keys.resize((size_t)n_entries);
+        for (size_t q = 0, i = 0; q < (size_t)n_calls; ++q)
+            for (int k = 0; k < pc.counts[q]; ++k, ++i) row_keys[i] = of_slot[(size_t)pc.round[q] * S + pc.rows[i]];
     } else if (n_rounds > 0 && !cc.tape) {
         if ((a->sample_offset + (unsigned long long)S) >> 48) return fail(h, LS_EINVAL, "PHILOX: sample_offset + capacity must stay below 2^48 (the round index sits above)");
-        if (h->pl_rounds + n_rounds > (1 << 16)) return fail(h, LS_ESTATE, "%s: PHILOX keys a round by its index since open, which stays below 2^16; open a new session", entry);
+        if (h->pl_rounds + n_calls > (1 << 16)) return fail(h, LS_ESTATE, "%s: PHILOX keys a round by its index since open, which stays below 2^16; open a new session", entry);
     }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    rc = session_push_run(h, entry, a, cc, win, rounds, n_rounds, row_keys);
+    rc = session_push_run(h, entry, a, cc, win, pc, n_rounds, row_keys);
     if (rc != LS_OK) {      // rings and hand-off stores may be half written: the session is over, the handle is not
         h->pl_state = ls_handle::kStreamFailed;
         (void)hipStreamSynchronize(h->stream);
@@ -1295,6 +1407,7 @@ int ls_long_pool_join(ls_handle* h, const ls_long_pool_join_args* a) {
     const int s = a->slot, od = a->on_device;
     const size_t hand = (size_t)h->JF * h->cfg.n_pre_seq;
     if (std::find(h->pl_styled.begin(), h->pl_styled.end(), s) != h->pl_styled.end()) h->pl_styled.clear();       // the slot's speaker changes
+    if ((rc = pins_drop(h, s)) != LS_OK) return rc;         // a new clip starts with no pin
     if ((rc = pool_hold(h, h->pl_hand.f() + (size_t)s * hand, a->seed_poses, hand * sizeof(float), od)) != LS_OK) return rc;
     if ((rc = pool_hold(h, static_cast<int64_t*>(h->pl_vid.p) + s, a->vid_index, sizeof(int64_t), od)) != LS_OK) return rc;
     if ((rc = pool_hold(h, h->pl_scale.f() + s, a->scale, sizeof(float), od)) != LS_OK) return rc;
@@ -1337,8 +1450,142 @@ int ls_long_pool_set_key(ls_handle* h, int32_t slot, uint64_t key) {
     return LS_OK;
 }
 
+// Pinned poses (ls_hip.h): the entries serve a pool and a stream alike -- a stream is the pool whose slots move together
+static int pins_session(ls_handle* h, const char* entry, bool enabled) {
+    const int rc = session_is_open(h, entry, h->pl_lockstep != ls_handle::kPool);
+    if (rc != LS_OK) return rc;
+    if (enabled && !h->pl_pin_P) return fail(h, LS_ESTATE, "%s: the session has no pins (ls_long_pool_pins)", entry);
+    return LS_OK;
+}
+
+// Enabling pins: where ls_long_pool_keyed acts -- an open pool nobody has joined, a stream nothing has been pushed to.  The store,
+// the staging of a pin call, the inpainting planes and the denoiser's output plane are sized here for the session's S slots: no
+// buffer a captured loop holds by address moves later, and a session without pins allocates none of them.
+int ls_long_pool_pins(ls_handle* h, int32_t horizon) {
+    if (!h) return fail(h, LS_EINVAL, "ls_long_pool_pins: null argument");
+    int rc;
+    if ((rc = pins_session(h, "ls_long_pool_pins", false)) != LS_OK) return rc;
+    const bool stream = h->pl_lockstep != ls_handle::kPool;
+    if (stream ? (h->pl_rounds != 0 || h->pl_samples[0] != 0) : h->pl_joins != 0)
+        return fail(h, LS_ESTATE, "ls_long_pool_pins: after the %s", stream ? "stream's first push" : "pool's first join");
+    if (h->pl_pin_P) return fail(h, LS_ESTATE, "ls_long_pool_pins: the session has pins already (horizon %d)", h->pl_pin_H);
+    if (horizon < h->T || horizon > (1 << 20)) return fail(h, LS_EINVAL, "ls_long_pool_pins: horizon %d outside [%d, 2^20]", horizon, h->T);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int S = h->pl_S, P = (horizon + 3) / 4 * 4;
+    const size_t elems = (size_t)S * P * h->JF, nxS = (size_t)S * h->JF * h->T * sizeof(float);
+    HIPCHK(h, h->pl_pin_val.ensure(elems * sizeof(float))); HIPCHK(h, h->pl_pin_bit.ensure(elems));
+    HIPCHK(h, hipMemsetAsync(h->pl_pin_val.p, 0, h->pl_pin_val.bytes, h->stream)); HIPCHK(h, hipMemsetAsync(h->pl_pin_bit.p, 0, h->pl_pin_bit.bytes, h->stream));
+    HIPCHK(h, h->pl_pin_poses.ensure((size_t)P * h->JF * sizeof(float))); HIPCHK(h, h->pl_pin_mask.ensure((size_t)P * h->JF));
+    HIPCHK(h, h->pl_pin_pos.ensure((size_t)P * sizeof(int)));
+    if ((rc = ensure_pinned(h, h->inp_maskf, nxS)) != LS_OK || (rc = ensure_pinned(h, h->inp_motion, nxS)) != LS_OK || (rc = ensure_pinned(h, h->fwd_cfg, nxS)) != LS_OK) return rc;
+    if (h->pl_keyed && h->cfg.n_prefix_tokens != 2 && (rc = size_key_ring(h, S, h->have_sched ? h->n_steps : 1, true)) != LS_OK) return rc;
+    // the TED tree's re-noise tape of a pinned TAPE call and its host staging, for the longest loop of the schedule -- as session_open
+    // sizes the other tape buffers; a push checks them again, ahead of its first launch, because the schedule may be set (or grow) later
+    if (h->cfg.n_prefix_tokens != 2 && h->have_sched) {
+        if ((rc = ensure_pinned(h, h->inp_tape, h->n_steps * nxS)) != LS_OK) return rc;
+        HIPCHK(h, h->lg_inz.ensure(h->n_steps * nxS));
+    }
+    // a stream keeps its plain and its inpainting loop side by side from here on (kKeep in session_push_run): both fit in an empty cache
+    if (stream) free_graph(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->pl_pin_H = horizon; h->pl_pin_P = P;
+    h->pl_pin_frames.assign((size_t)S, {});
+    h->pl_pin_tape = nullptr; h->pl_pin_tape_floats = 0;
+    return LS_OK;
+}
+
+// the refusals of a frame list, none of which touches the device: n frames, distinct, each in [frames_out, frames_out + horizon)
+static int pin_frames_ok(ls_handle* h, const char* entry, int slot, int n, const int64_t* frames, std::vector<int>& pos) {
+    if (slot < 0 || slot >= h->pl_S) return fail(h, LS_EINVAL, "%s: slot %d outside [0, %d)", entry, slot, h->pl_S);
+    if (!h->pl_open[(size_t)slot]) return fail(h, LS_ESTATE, "%s: slot %d is not open", entry, slot);
+    if (n < 1 || n > h->pl_pin_H || !frames) return fail(h, LS_EINVAL, "%s: %d frames (1 .. the horizon %d), or a null list", entry, n, h->pl_pin_H);
+    const long long lo = h->pl_frames[(size_t)slot], hi = lo + h->pl_pin_H;
+    std::vector<int64_t> sorted(frames, frames + n);
+    std::sort(sorted.begin(), sorted.end());
+    for (int k = 0; k < n; ++k) {
+        if (sorted[(size_t)k] < lo || sorted[(size_t)k] >= hi)
+            return fail(h, LS_EINVAL, "%s: frame %lld of slot %d outside [%lld, %lld): frames_out .. frames_out + horizon", entry, (long long)sorted[(size_t)k], slot, lo, hi);
+        if (k && sorted[(size_t)k] == sorted[(size_t)k - 1]) return fail(h, LS_EINVAL, "%s: frame %lld is named twice", entry, (long long)sorted[(size_t)k]);
+    }
+    pos.resize((size_t)n);
+    for (int k = 0; k < n; ++k) pos[(size_t)k] = (int)(frames[k] % h->pl_pin_P);
+    return LS_OK;
+}
+
+int ls_long_pool_pin(ls_handle* h, int32_t slot, int32_t n, const int64_t* frames, const float* poses, const unsigned char* mask, int32_t on_device) {
+    if (!h) return fail(h, LS_EINVAL, "ls_long_pool_pin: null argument");
+    int rc;
+    std::vector<int> pos;
+    if ((rc = pins_session(h, "ls_long_pool_pin", true)) != LS_OK || (rc = pin_frames_ok(h, "ls_long_pool_pin", slot, n, frames, pos)) != LS_OK) return rc;
+    if (!poses) return fail(h, LS_EINVAL, "ls_long_pool_pin: null poses");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    const size_t elems = (size_t)h->JF * n;
+    PinArgs p = pin_args(h);
+    p.slot = slot; p.K = n; p.poses = poses; p.mask = mask; p.pos = static_cast<const int*>(h->pl_pin_pos.p);
+    if (!on_device) {
+        HIPCHK(h, hipMemcpyAsync(h->pl_pin_poses.p, poses, elems * sizeof(float), hipMemcpyHostToDevice, st));
+        p.poses = h->pl_pin_poses.f();
+        if (mask) {
+            HIPCHK(h, hipMemcpyAsync(h->pl_pin_mask.p, mask, elems, hipMemcpyHostToDevice, st));
+            p.mask = static_cast<const unsigned char*>(h->pl_pin_mask.p);
+        }
+    }
+    HIPCHK(h, hipMemcpyAsync(h->pl_pin_pos.p, pos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(h, launch_pool_pin_store(p, st));
+    HIPCHK(h, hipStreamSynchronize(st));            // the caller's arrays are its own again
+    std::vector<long long>& v = h->pl_pin_frames[(size_t)slot];
+    v.insert(v.end(), frames, frames + n);
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    return LS_OK;
+}
+
+int ls_long_pool_unpin(ls_handle* h, int32_t slot, int32_t n, const int64_t* frames) {
+    if (!h) return fail(h, LS_EINVAL, "ls_long_pool_unpin: null argument");
+    int rc;
+    if ((rc = pins_session(h, "ls_long_pool_unpin", true)) != LS_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!frames && n == 0) {                        // the whole slot, open or not
+        if (slot < 0 || slot >= h->pl_S) return fail(h, LS_EINVAL, "ls_long_pool_unpin: slot %d outside [0, %d)", slot, h->pl_S);
+        if ((rc = pins_drop(h, slot)) != LS_OK) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return LS_OK;
+    }
+    std::vector<int> pos;
+    if ((rc = pin_frames_ok(h, "ls_long_pool_unpin", slot, n, frames, pos)) != LS_OK) return rc;
+    PinArgs p = pin_args(h);
+    p.slot = slot; p.K = n; p.pos = static_cast<const int*>(h->pl_pin_pos.p);
+    HIPCHK(h, hipMemcpyAsync(h->pl_pin_pos.p, pos.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, launch_pool_pin_clear(p, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<long long>& v = h->pl_pin_frames[(size_t)slot];
+    v.erase(std::remove_if(v.begin(), v.end(), [&](long long f) { return std::find(frames, frames + n, (int64_t)f) != frames + n; }), v.end());
+    return LS_OK;
+}
+
+// the re-noise tape of the NEXT push's pinned calls (TAPE mode, the TED tree): packed call after call, [n_exec, A, J, F, T] each; the
+// push checks its size against its plan and forgets it.  A null tape takes one back.
+int ls_long_pool_pin_tape(ls_handle* h, const float* inpaint_noise, int64_t n_floats, int32_t on_device) {
+    if (!h) return fail(h, LS_EINVAL, "ls_long_pool_pin_tape: null argument");
+    const int rc = pins_session(h, "ls_long_pool_pin_tape", true);
+    if (rc != LS_OK) return rc;
+    if (n_floats < 0 || (n_floats > 0) != (inpaint_noise != nullptr)) return fail(h, LS_EINVAL, "ls_long_pool_pin_tape: %lld floats with%s a tape", (long long)n_floats, inpaint_noise ? "" : "out");
+    h->pl_pin_tape = inpaint_noise; h->pl_pin_tape_floats = n_floats; h->pl_pin_tape_od = on_device ? 1 : 0;
+    return LS_OK;
+}
+
+int ls_long_pool_pin_info(const ls_handle* h, int32_t capacity, int32_t* pending, int64_t misc[2]) {
+    if (!h || capacity < 0) return LS_EINVAL;
+    const bool in = h->pl_state != ls_handle::kStreamNone && h->pl_pin_P > 0;
+    for (int s = 0; s < capacity && pending; ++s) pending[s] = in && s < h->pl_S ? (int32_t)h->pl_pin_frames[(size_t)s].size() : 0;
+    if (misc) { misc[0] = in ? h->pl_pin_H : 0; misc[1] = in ? h->pl_pin_P : 0; }
+    return LS_OK;
+}
+
 int ls_long_pool_push(ls_handle* h, const ls_long_pool_push_args* a) {
     if (!h || !a) return fail(h, LS_EINVAL, "ls_long_pool_push: null argument");
+    const ForgetTape forget_tape{h};
     const int rc = session_is_open(h, "ls_long_pool_push", false);
     if (rc != LS_OK) return rc;
     if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_pool_push before ls_set_schedule");
@@ -1349,6 +1596,7 @@ int ls_long_pool_push(ls_handle* h, const ls_long_pool_push_args* a) {
 // rounds at batch B are the stream's [k, B, ...] tapes, the round index is the window index.
 int ls_long_stream_push(ls_handle* h, const ls_long_stream_push_args* a) {
     if (!h || !a) return fail(h, LS_EINVAL, "ls_long_stream_push: null argument");
+    const ForgetTape forget_tape{h};
     int rc;
     if ((rc = session_is_open(h, "ls_long_stream_push", true)) != LS_OK) return rc;
     if (!h->have_sched) return fail(h, LS_ESTATE, "ls_long_stream_push before ls_set_schedule");

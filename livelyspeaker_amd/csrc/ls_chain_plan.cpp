@@ -1,9 +1,9 @@
 // The plans of the chained-window engine (ls_chain_api.cpp): which clips run which window of a ragged call, which windows a timeline
 // edit runs (and which clips run each of them in its compact form), which windows a push of a stream runs, which rounds a push of a
-// session pool runs and at which keys its rows draw, which copies feed the slots' rings.  Every edit plan is made from PAIR FLAGS
+// session pool runs, at which keys its rows draw and into which sampling calls pinned poses split them, which copies feed the slots' rings.  Every edit plan is made from PAIR FLAGS
 // (edit_plan_of_flags): the range form and the element-mask form (ls_long_edit_plan_mask) differ only in how the flags come about.
 // Integer arithmetic on host arrays, no HIP in here: each is the single definition for its entry and for Python (long_form.py), and
-// tests/chain_plan_main.cpp, tests/pool_plan_main.cpp, tests/pool_keys_main.cpp, tests/edit_plan_main.cpp and
+// tests/chain_plan_main.cpp, tests/pool_plan_main.cpp, tests/pool_keys_main.cpp, tests/pool_pin_plan_main.cpp, tests/edit_plan_main.cpp and
 // tests/edit_mask_plan_main.cpp run them on their edges under the host sanitizers.
 #include <algorithm>
 #include <cstdint>
@@ -281,6 +281,60 @@ int ls_long_pool_keys(int32_t n_slots, const uint64_t* keys, const int64_t* wind
             for (int s = 0; s < n_slots; ++s)
                 if (n_windows[s] > r) row_keys[p++] = keys[s] + ((uint64_t)(windows_run[s] + r) << 48);
     }
+    *n_entries = (int32_t)entries;
+    return LS_OK;
+}
+
+// The sampling calls of a push of a session with pinned poses (ls_long_pool_pins in ls_hip.h), in ls_long_pool_plan's round order:
+// in round r slot s (n_windows[s] > r) runs its window w = windows_run[s] + r, which owns the series frames [0, T) for w = 0 and
+// [w S + n_pre, w S + T) otherwise (S = T - n_pre); its row is PINNED iff one of the slot's pending pinned frames is among them.
+// The round becomes its unpinned rows, ascending, as one call, then its pinned rows, ascending, as another; an empty half is no
+// call.  Without a pending frame the calls are the rounds.
+int ls_long_pool_pin_plan(int32_t n_slots, int32_t T, int32_t n_pre, const int64_t* windows_run, const int32_t* n_windows,
+                          const int32_t* pin_first, const int64_t* pin_frames, int32_t* call_rows, int32_t row_capacity,
+                          int32_t* call_counts, int32_t* call_pinned, int32_t* call_rounds, int32_t call_capacity, int32_t* n_calls,
+                          int32_t* n_entries) {
+    if (n_slots < 1 || n_pre < 1 || T <= n_pre || !windows_run || !n_windows || !n_calls || !n_entries) return LS_EINVAL;
+    if (row_capacity < 0 || call_capacity < 0 || (row_capacity > 0 && !call_rows)) return LS_EINVAL;
+    if (!pin_first && pin_frames) return LS_EINVAL;
+    if (pin_first && !pin_frames && pin_first[n_slots] != pin_first[0]) return LS_EINVAL;
+    const int64_t S = T - n_pre;
+    int64_t rounds = 0, entries = 0;
+    for (int s = 0; s < n_slots; ++s) {
+        if (n_windows[s] < 0 || n_windows[s] > (1 << 20) || windows_run[s] < 0 || windows_run[s] > (INT64_MAX - T) / S - n_windows[s]) return LS_EINVAL;
+        if (n_windows[s] > rounds) rounds = n_windows[s];
+        entries += n_windows[s];
+        if (entries > INT32_MAX) return LS_EINVAL;
+        if (pin_first) {
+            if ((s == 0 && pin_first[0] != 0) || pin_first[s + 1] < pin_first[s]) return LS_EINVAL;
+            for (int32_t i = pin_first[s]; i < pin_first[s + 1]; ++i)
+                if (pin_frames[i] < 0) return LS_EINVAL;
+        }
+    }
+    int64_t calls = 0, p = 0;
+    for (int64_t r = 0; r < rounds; ++r)
+        for (int half = 0; half < 2; ++half) {          // the unpinned rows, then the pinned ones
+            int32_t n = 0;
+            for (int s = 0; s < n_slots; ++s) {
+                if (n_windows[s] <= r) continue;
+                const int64_t w = windows_run[s] + r, lo = w ? w * S + n_pre : 0, hi = w * S + T;
+                bool pinned = false;
+                for (int32_t i = pin_first ? pin_first[s] : 0; pin_first && i < pin_first[s + 1] && !pinned; ++i)
+                    pinned = pin_frames[i] >= lo && pin_frames[i] < hi;
+                if (pinned != (half == 1)) continue;
+                if (call_rows) { if (p + n >= row_capacity) return LS_EINVAL; call_rows[p + n] = s; }
+                ++n;
+            }
+            if (n == 0) continue;
+            if (call_counts || call_pinned || call_rounds) {
+                if (calls >= call_capacity) return LS_EINVAL;
+                if (call_counts) call_counts[calls] = n;
+                if (call_pinned) call_pinned[calls] = half;
+                if (call_rounds) call_rounds[calls] = (int32_t)r;
+            }
+            ++calls; p += n;
+        }
+    *n_calls = (int32_t)calls;
     *n_entries = (int32_t)entries;
     return LS_OK;
 }

@@ -178,6 +178,19 @@ struct ls_handle {
     long long pl_joins = 0;             // joins since open: a keyed slot's default key
     std::vector<uint64_t> pl_key;
     DevBuf pl_ring, pl_hand, pl_vid, pl_scale, pl_emo_id, pl_emotok, pl_text, pl_ctext, pl_table;
+    // Pinned poses of frames a slot has yet to return (ls_long_pool_pins / _pin / _unpin).  pl_pin_P == 0: the session has none and
+    // holds nothing of the following.  Otherwise per slot a ring of pl_pin_P series frames, frame n at n % pl_pin_P: the values
+    // pl_pin_val [S][P][JF] and one byte per element pl_pin_bit [S][P][JF] (1 = pinned).  pl_pin_frames [S]: the pending pinned frames
+    // of each slot, ascending -- the host mirror the plan is made from (ls_long_pool_pin_plan); a frame leaves it when the window that
+    // owns it has run (k_pool_pin_gather cleared its bytes), at ls_long_pool_unpin, and when its slot leaves or is joined.
+    // pl_pin_poses / pl_pin_mask / pl_pin_pos: staging of one ls_long_pool_pin call (a host caller's arrays; the ring positions).
+    // pl_pin_tape: the re-noise tape the next push's pinned calls read (ls_long_pool_pin_tape), taken by that push.
+    int pl_pin_H = 0, pl_pin_P = 0;
+    std::vector<std::vector<long long>> pl_pin_frames;
+    DevBuf pl_pin_val, pl_pin_bit, pl_pin_poses, pl_pin_mask, pl_pin_pos;
+    const float* pl_pin_tape = nullptr;
+    long long pl_pin_tape_floats = 0;
+    int pl_pin_tape_od = 0;
     // Cached graphs of the step loop, by loop key (ls_sample.cpp: loop_key holds everything a captured loop bakes in besides device
     // addresses, the batch and its step plan included).  At most kGraphCacheMax entries: a plain call whose key is missing drops them
     // all and captures its own (one entry, as before the cache); a ragged long-form call keeps one per window batch that serves two or

@@ -383,6 +383,23 @@ struct PoolArgs {
 };
 hipError_t launch_pool_gather(const PoolArgs& a, int A, hipStream_t st);
 hipError_t launch_pool_scatter(const PoolArgs& a, int A, hipStream_t st);
+// ---- pinned poses of a session's slots (ls_long_pool_pin; ls_chain.hip).  Per slot a ring of P series frames, frame n at n % P:
+// val [S][P][JF] (fp32) and bit [S][P][JF] (bytes, 1 = pinned), JF innermost like the internal-layout planes [A][T][JF].
+// launch_pool_pin_store: the K frames at ring positions pos [K] (device) of slot `slot` take, where mask [JF][K] (bytes, the caller's
+// [J, F, K] layout; null: everywhere) is set, the value of poses [JF][K] and byte 1.  launch_pool_pin_clear: the bytes of those K frames
+// become 0 (pos null: of all P frames of the slot, K == P).  launch_pool_pin_gather: row r of a pinned call -- table[r] = {slot, ., .,
+// f0, ., ring position of the window's frame 0} in the round's kPoolRow table -- gets motion / maskf [A][T][JF] (maskf 1 = keep) from
+// the ring for its frames f0 .. T-1 and zero elsewhere, and the bytes it read set are cleared.  The launchers check the geometry; pos
+// and the table's entries (0 <= slot < S, 0 <= position < P) are the caller's to check before upload.
+struct PinArgs {
+    float* val; unsigned char* bit;
+    const int* table; float* motion; float* maskf;                  // gather
+    const float* poses; const unsigned char* mask; const int* pos;  // store / clear
+    int S, P, JF, T, slot, K;
+};
+hipError_t launch_pool_pin_store(const PinArgs& a, hipStream_t st);
+hipError_t launch_pool_pin_clear(const PinArgs& a, hipStream_t st);
+hipError_t launch_pool_pin_gather(const PinArgs& a, int A, hipStream_t st);
 
 // ---- torch's device normal stream (ls_torch_philox.hip; LS_NOISE_TORCH_DEVICE) ---------------------------------------------
 // One torch.randn / randn_like of n float32 elements per step: written to dst + r * dst_stride for step r of the launch.

@@ -429,6 +429,108 @@ class _Session:
                 raise ValueError(f"text_features must be {[rows, rag.latent_dim]}, got {list(text_features.shape)}")
 
 
+    # ---- pinned poses for frames the session has yet to make (open_pool(pins=), open_stream(pins=)) ----
+    def _init_pins(self, pins, rag, slots):
+        """``pins=``: None, or the horizon H -- an int of at least nframes: a pin may name a frame in ``[frames_out, frames_out + H)``.
+        ``self._pending[s]``: the pinned frames of slot s whose window has yet to run (the engine holds the same list)."""
+        if pins is not None:
+            T = int(getattr(rag, "nframes", 34))
+            if isinstance(pins, bool) or not isinstance(pins, (int, np.integer)) or not T <= int(pins) <= 1 << 20:
+                raise ValueError(f"pins must be None or the horizon in frames, an int in [{T}, 2^20], got {pins!r}")
+            pins = int(pins)
+        self._pins, self._pending = pins, [set() for _ in range(slots)]
+
+    def _check_pin(self, frames, poses, mask, lead, frames_out):
+        """The refusals of ``pin``, ahead of any engine call: ``frames`` [K] distinct host ints in ``[frames_out, frames_out + H)``,
+        ``poses`` ``lead + [J, F, K]`` and ``mask`` None or bool of that shape.  Returns (frames int64 [K], poses, mask)."""
+        rag = self._rag
+        if self._pins is None:
+            raise ValueError("pin needs a session opened with pins=H (the horizon in frames)")
+        if self._sag is not None:
+            raise ValueError("pins with sag= are not built: a pinned window would start from edit_start(motion, mask, sag_out)")
+        if hasattr(frames, "detach"):
+            frames = frames.detach().cpu().numpy()
+        fr = np.asarray(frames)
+        if fr.ndim != 1 or fr.size < 1 or fr.dtype.kind not in "iu":
+            raise ValueError(f"frames must be a host sequence [K] of ints, K >= 1, got {frames!r}")
+        fr = fr.astype(np.int64)
+        if len(set(fr.tolist())) != fr.size:
+            raise ValueError(f"frames names a frame twice: {fr.tolist()}")
+        if fr.min() < frames_out or fr.max() >= frames_out + self._pins:
+            raise ValueError(f"frames {fr.tolist()} outside [{frames_out}, {frames_out + self._pins}): a pin names a frame that has not been "
+                             f"returned yet (frames_out) and lies within the horizon pins={self._pins}")
+        poses, mask = _as_tensors(poses, mask)
+        want = tuple(lead) + (rag.njoints, rag.nfeats, int(fr.size))
+        if _shape(poses) != want:
+            raise ValueError(f"poses must be {list(want)}, got {list(poses.shape)}")
+        if mask is not None and (_shape(mask) != want or mask.dtype != th.bool):
+            raise ValueError(f"mask must be bool {list(want)} (True = pinned), got {mask.dtype} {list(mask.shape)}")
+        return fr, poses.float(), mask
+
+    def _check_unpin(self, frames, frames_out):
+        if self._pins is None:
+            raise ValueError("unpin needs a session opened with pins=H")
+        if frames is None:
+            return None
+        fr = np.asarray(frames.detach().cpu().numpy() if hasattr(frames, "detach") else frames)
+        if fr.ndim != 1 or fr.size < 1 or fr.dtype.kind not in "iu" or len(set(fr.tolist())) != fr.size:
+            raise ValueError(f"frames must be None or a host sequence [K] of distinct ints, got {frames!r}")
+        if fr.min() < frames_out or fr.max() >= frames_out + self._pins:
+            raise ValueError(f"frames {fr.tolist()} outside [{frames_out}, {frames_out + self._pins})")
+        return fr.astype(np.int64)
+
+    def _calls(self, rounds, windows_run):
+        """The sampling calls of a push that runs ``rounds``: ``pool_pin_plan`` on the pending pins (without pins: the rounds)."""
+        if self._pins is None or not any(self._pending):
+            return [(r, False, list(slots)) for r, slots in enumerate(rounds)]
+        n_windows = [sum(s in r for r in rounds) for s in range(len(self._pending))]
+        return pool_pin_plan(windows_run, n_windows, self._pending, self._rag)
+
+    def _consume(self, calls, windows_run, leaving):
+        """After a push: the pins of the windows that ran pinned are spent, and a slot that leaves drops the rest."""
+        for r, pinned, slots in calls:
+            for s in slots if pinned else ():
+                lo, hi = _owned(int(windows_run[s]) + r, self._rag)
+                self._pending[s] -= {n for n in self._pending[s] if lo <= n < hi}
+        for s in leaving:
+            self._pending[int(s)].clear()
+
+
+def _owned(w, cfg):
+    """The series frames ``[lo, hi)`` window w owns: all 34 for w = 0, the 30 behind its prefix otherwise (``edit_plan``'s ownership)."""
+    T, S = int(cfg.nframes), int(cfg.nframes) - int(cfg.n_pre_seq)
+    return (0 if w == 0 else w * S + int(cfg.n_pre_seq)), w * S + T
+
+
+def pool_pin_plan(windows_run, n_windows, pins, cfg):
+    """The sampling calls of one push of a session with pinned poses, from host counts alone (no GPU): a list of ``(round, pinned,
+    slots)`` in the order they run.  Slot s runs ``n_windows[s]`` windows in the push (``pool_plan``'s rounds: round r holds the slots
+    with ``n_windows[s] > r``), its window ``windows_run[s] + r`` in round r; ``pins[s]`` holds the slot's pending pinned frames (series
+    frames, any order).  The slot's row in round r is PINNED iff one of them is a frame that window owns (all 34 frames for window 0,
+    ``30 w + 4 .. 30 w + 33`` otherwise).  Round r becomes its unpinned slots, ascending, as one plain call, then its pinned slots,
+    ascending, as one inpainting call; an empty half is skipped -- without pins the calls are ``pool_plan``'s rounds.  One definition for
+    the engine and for this module (``ls_long_pool_pin_plan``)."""
+    return _lib.long_pool_pin_plan(windows_run, n_windows, pins, int(cfg.nframes), int(cfg.n_pre_seq))
+
+
+def _call_draws(diffusion, rag, calls, n_exec, D):
+    """``'torch_cpu'``: what one public sampling call per call of the plan draws, in order (``RefDraws.windows`` for a plain call,
+    ``RefDraws.edit_windows`` for a pinned one; the TED tree re-noises the kept motion), packed as the engine reads them: x
+    [sum A, J, F, T], flat eps / noise, and the flat re-noise tape of the pinned calls (None without one)."""
+    noised = rag.n_prefix_tokens == 1
+    xs, eps, nz, inz = [], [], [], []
+    for _, pinned, slots in calls:
+        shape = (len(slots), rag.njoints, rag.nfeats, rag.nframes)
+        if pinned:
+            d = ref_draws.RefDraws("cpu").edit_windows(diffusion, 1, n_exec, shape, D, noised)
+            if noised:
+                inz.append(d[3].reshape(-1))
+        else:
+            d = ref_draws.RefDraws("cpu").windows(diffusion, 1, n_exec, shape, D)
+        xs.append(d[0][0]); eps.append(d[1].reshape(-1)); nz.append(d[2].reshape(-1))
+    return th.cat(xs, dim=0), th.cat(eps), th.cat(nz), (th.cat(inz) if inz else None)
+
+
 def score_summary(stream, finished):
     """What a session reports for the slots a call finished: ``{'slots': {slot: ScoreStream.finish dict}}`` plus, on TED, ``'bc'`` -- the
     beat-consistency score over those slots, accumulated as ``BeatConsistency.push_timeline`` does (nan without an onset) -- and on BEAT
@@ -448,7 +550,7 @@ class LongStream(_Session):
     """A running ``open_stream`` session; see there.  ``samples_in``, ``windows_run``, ``frames_out``: host ints."""
 
     def __init__(self, diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag, post=None,
-                 score=None, max_seconds=None, input_sr=None, input_channels=1, resample=None):
+                 score=None, max_seconds=None, input_sr=None, input_channels=1, resample=None, pins=None):
         seed_poses, vid_indices, scale, emo = _as_tensors(seed_poses, vid_indices, scale, emo)
         B = int(seed_poses.shape[0]) if seed_poses.ndim else 0
         rag = getattr(model, "model", None)
@@ -463,6 +565,7 @@ class LongStream(_Session):
         self._diffusion, self._rag, self._sag, self._B = diffusion, rag, sag, B
         self._init_post(post, rag, B, score, max_seconds)
         self._init_input(input_sr, input_channels, resample, B)
+        self._init_pins(pins, rag, B)
         self.input_samples_in = 0                       # frames at input_sr; samples_in counts the 16 kHz samples the windows see
         self._cond = (seed_poses.float(), vid_indices, scale.float())
         self._emo, self._text = emo, None               # held on the host side only until the next engine call takes them
@@ -478,6 +581,44 @@ class LongStream(_Session):
 
     def _open(self, eng):
         eng.long_stream_open(*self._cond)
+        if self._pins is not None:
+            eng.long_pool_pins(self._pins)
+
+    @property
+    def pins(self):
+        """The pinned frames whose window has yet to run (every clip holds the same ones); 0 without ``pins=``."""
+        return len(self._pending[0]) if self._pending else 0
+
+    def pin(self, frames, poses, mask=None):
+        """Pin poses of frames the stream has yet to return (opened with ``pins=H``), every clip alike: ``frames`` [K], distinct host
+        ints in ``[frames_out, frames_out + H)``; ``poses`` [B, J, F, K]; ``mask`` [B, J, F, K] bool, True = pinned, default the whole
+        pose.  The same as ``LongPool.pin`` on each of the B slots of the pool the stream runs on."""
+        if self._closed:
+            raise RuntimeError("the stream is closed")
+        fr, poses, mask = self._check_pin(frames, poses, mask, (self._B,), self.frames_out)
+        eng = self._engine()
+        done = []
+        try:                            # every clip or none: a call that fails midway takes back what the clips before it were given
+            for b in range(self._B):
+                eng.long_pool_pin(b, fr, poses[b], None if mask is None else mask[b])
+                done.append(b)
+        except Exception:
+            fresh = np.array(sorted(set(fr.tolist()) - self._pending[0]), np.int64)     # frames pinned before keep their pins
+            for b in done if fresh.size else ():
+                eng.long_pool_unpin(b, fresh)
+            raise
+        for b in range(self._B):        # the mirror moves only once the engine holds the pins of all clips
+            self._pending[b] |= set(fr.tolist())
+
+    def unpin(self, frames=None):
+        """Drop the pins of ``frames`` (None: all of them) of every clip."""
+        if self._closed:
+            raise RuntimeError("the stream is closed")
+        fr = self._check_unpin(frames, self.frames_out)
+        eng = self._engine()
+        for b in range(self._B):        # an un-pin only clears: a clip it has reached stays cleared, and the mirror follows clip by clip
+            eng.long_pool_unpin(b, fr)
+            self._pending[b] = set() if fr is None else self._pending[b] - set(fr.tolist())
 
     def _feed(self, chunk, emo, text_features, closing, lazy=None):
         """``lazy`` (with ``input_sr=``): ``(n, feed)`` in place of ``chunk`` -- its 16 kHz samples per clip, known ahead, and the call that
@@ -503,8 +644,17 @@ class LongStream(_Session):
         if k and diffusion.noise_source != "philox":
             _check_tape_bound(diffusion, "open_stream", self._n_exec, shape, int(rag.latent_dim))
         eng = self._engine()
+        calls = self._calls([list(range(B))] * k, np.full(B, first))       # every clip alike: a window is one call, plain or pinned
+        if self._sag is not None and any(pinned for _, pinned, _ in calls):
+            raise ValueError("a pinned window with sag= is not built")
         if k and diffusion.noise_source != "philox":
-            kw["x_init"], kw["eps_tape"], kw["noise_tape"] = ref_draws.RefDraws("cpu").windows(diffusion, k, self._n_exec, shape, eng.D)
+            if any(pinned for _, pinned, _ in calls):
+                x, eps, nz, renoise = _call_draws(diffusion, rag, calls, self._n_exec, eng.D)
+                kw["x_init"], kw["eps_tape"], kw["noise_tape"] = x.view((k,) + shape), eps.view(k, self._n_exec, 2, B, eng.D), nz.view((k, self._n_exec) + shape)
+                if renoise is not None:
+                    kw["inpaint_noise"] = renoise
+            else:
+                kw["x_init"], kw["eps_tape"], kw["noise_tape"] = ref_draws.RefDraws("cpu").windows(diffusion, k, self._n_exec, shape, eng.D)
             diffusion.last_tape_segments = 1
         if self._sag is not None:
             kw["sag"] = self._sag.engine()
@@ -516,6 +666,7 @@ class LongStream(_Session):
         self._have_emo, self._have_text = self._have_emo or emo is not None, self._have_text or text_features is not None
         self._emo = self._text = None                   # the engine holds them now
         self._closed = bool(closing)
+        self._consume(calls, np.full(B, first), range(B) if closing else ())
         self.samples_in += n
         self.windows_run += ran
         self.frames_out += int(frames.shape[3])
@@ -549,7 +700,7 @@ class LongStream(_Session):
 
 
 def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False,
-                sag=None, post=None, score=None, max_seconds=None, input_sr=None, input_channels=1, resample=None):
+                sag=None, post=None, score=None, max_seconds=None, input_sr=None, input_channels=1, resample=None, pins=None):
     """The online form of ``sample_long``: a session that is fed audio in chunks of any size and returns a window's new frames as soon
     as that window's audio is complete.
 
@@ -603,10 +754,14 @@ def open_stream(diffusion, model, seed_poses, vid_indices, scale, emo=None, samp
 
     Clips that join or leave while others run, each fed at its own rate: ``open_pool``.
 
-    Not built: ``audio_lengths`` / ``drop_finished``, ``edit_long`` on a running stream, PLMS, ``const_noise``, ``dump_steps``,
+    ``pins=H`` (an int >= 34; None: nothing changes) lets ``stream.pin(frames [K], poses [B, J, F, K], mask=None)`` pin poses of frames the
+    stream has yet to return, every clip alike, and ``stream.unpin(frames=None)`` drop them: ``open_pool``'s pins on the B slots the
+    stream runs on (see there; ``stream.pins`` counts the pinned frames still to come).
+
+    Not built: ``audio_lengths`` / ``drop_finished``, ``edit_long`` on frames a running stream has already returned, pins with ``sag=``, PLMS, ``const_noise``, ``dump_steps``,
     sharded calls, a non-blocking ``push``."""
     return LongStream(diffusion, model, seed_poses, vid_indices, scale, emo, sampler, skip_timesteps, eta, clip_denoised, sag, post, score, max_seconds,
-                      input_sr, input_channels, resample)
+                      input_sr, input_channels, resample, pins)
 
 
 def pool_plan(samples_in, windows_run, new, closing, open, cfg):
@@ -626,7 +781,7 @@ class LongPool(_Session):
     and in a keyed pool ``key`` (uint64; of a free slot: its last clip's)."""
 
     def __init__(self, diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post=None, noise_keys=None, score=None,
-                 max_seconds=None, input_sr=None, input_channels=1, resample=None):
+                 max_seconds=None, input_sr=None, input_channels=1, resample=None, pins=None):
         S = int(capacity)
         if S < 1:
             raise ValueError(f"capacity must be >= 1, got {capacity}")
@@ -645,6 +800,7 @@ class LongPool(_Session):
         self._diffusion, self._rag, self._sag, self._S = diffusion, rag, sag, S
         self._init_post(post, rag, S, score, max_seconds)
         self._init_input(input_sr, input_channels, resample, S)
+        self._init_pins(pins, rag, S)
         self._kw = _loop_kw(diffusion, sampler, skip_timesteps, eta, clip_denoised)
         self._keyed, self._joins = noise_keys == "clip", 0
         if diffusion.noise_source == "philox":          # one seed per pool: row r of round q draws at sample_offset + r + (q << 48); keyed: at the clip's key
@@ -652,8 +808,9 @@ class LongPool(_Session):
             self._offset = int(self._kw["sample_offset"])
             if self._keyed and not 0 <= self._offset < 1 << 48:
                 raise ValueError(f"noise_keys='clip': sample_offset {self._offset} outside [0, 2^48) (the default keys start there)")
-        else:                                           # the largest round a push can run
-            _check_tape_bound(diffusion, "open_pool", diffusion.num_timesteps - int(skip_timesteps), (S, J, F, int(rag.nframes)), int(rag.latent_dim))
+        else:                                           # the largest round a push can run (with pins on TED: and its re-noise tape)
+            _check_tape_bound(diffusion, "open_pool", diffusion.num_timesteps - int(skip_timesteps), (S, J, F, int(rag.nframes)), int(rag.latent_dim),
+                              renoised=self._pins is not None and not beat)
         self._n_exec = diffusion.num_timesteps - int(skip_timesteps)
         self._eng = None
         self._closed = False
@@ -662,6 +819,8 @@ class LongPool(_Session):
                        "open": np.zeros(S, bool)}
         if self._keyed:
             self._state["key"] = np.zeros(S, np.uint64)
+        if self._pins is not None:
+            self._state["pins"] = np.zeros(S, np.int64)
         self._have_text = np.zeros(S, bool)
 
     @property
@@ -675,12 +834,17 @@ class LongPool(_Session):
         eng.long_pool_open(self._S)
         if self._keyed:
             eng.long_pool_keyed(True)
+        if self._pins is not None:
+            eng.long_pool_pins(self._pins)
 
     def _refresh(self):
         info = self._eng.long_pool_info()
         for k in self._state:
-            if k != "key":          # the keys are held here: the engine has what join set
+            if k not in ("key", "pins"):        # the keys are held here: the engine has what join set
                 self._state[k] = np.array(info[k])
+        if self._pins is not None:              # the engine's count of pending pinned frames; the frames themselves are mirrored here
+            self._state["pins"] = self._eng.long_pool_pin_info()["pending"].astype(np.int64)
+            assert self._state["pins"].tolist() == [len(p) for p in self._pending], (self._state["pins"], self._pending)
 
     def join(self, seed_poses, vid_index, scale, emo=None, text_features=None, slot=None, key=None):
         """Open a slot for a new clip: ``seed_poses`` [J, F, n_pre], its speaker id and guidance scale, ``emo`` (BEAT: required) and
@@ -730,6 +894,8 @@ class LongPool(_Session):
         self._joins += 1
         if self._in is not None:
             self._in.reset(slot)          # a new series at sample 0 (a slot that left or was closed is empty already)
+        if self._pins is not None:
+            self._pending[slot].clear()   # a new clip starts with no pin (the engine's join drops them too)
         self._refresh()
         self._have_text[slot] = text_features is not None
         return slot
@@ -760,11 +926,14 @@ class LongPool(_Session):
             if self._sag is not None and st["windows_run"][s] == 0 and not self._have_text[s] and not bits[s] & 2:
                 raise ValueError(f"sag needs text_features [512] for slot {s}'s first window: pass them to join or to this push")
         kw = dict(self._kw)
+        calls = self._calls(rounds, st["windows_run"])              # the rounds, split where pending pins say so
+        if self._sag is not None and any(pinned for _, pinned, _ in calls):
+            raise ValueError("a pinned window with sag= is not built: unpin the frames, or open the pool without sag")
         eng = self._engine()
-        if rounds and diffusion.noise_source != "philox":           # one public sampling call per round, at its batch, in round order
-            draws = [ref_draws.RefDraws("cpu").windows(diffusion, 1, self._n_exec, (len(r), rag.njoints, rag.nfeats, rag.nframes), eng.D) for r in rounds]
-            kw["x_init"] = th.cat([d[0][0] for d in draws], dim=0)
-            kw["eps_tape"], kw["noise_tape"] = (th.cat([d[i].reshape(-1) for d in draws]) for i in (1, 2))
+        if calls and diffusion.noise_source != "philox":            # one public sampling call per call of the plan, at its batch, in order
+            kw["x_init"], kw["eps_tape"], kw["noise_tape"], renoise = _call_draws(diffusion, rag, calls, self._n_exec, eng.D)
+            if renoise is not None:
+                kw["inpaint_noise"] = renoise
             diffusion.last_tape_segments = 1
         if self._sag is not None:
             kw["sag"] = self._sag.engine()
@@ -776,6 +945,7 @@ class LongPool(_Session):
                                                  given=bits if bits.any() else None, device_out=out_dev.type == "cuda", **kw)
         assert ran == rounds
         self._have_text |= (bits & 2).astype(bool)
+        self._consume(calls, st["windows_run"], np.nonzero(ending)[0])
         self._refresh()
         self._have_text &= self._state["open"]
         frames = gd._as_tensor(frames, out_dev)
@@ -798,6 +968,34 @@ class LongPool(_Session):
             raise ValueError(f"samples for a slot that is not open: lengths {lens.tolist()}, open {self._state['open'].tolist()}")
         count, feed = self._input_plan(audio, lens)
         return self._feed(None, count, np.zeros(self._S, np.int32), emo, text_features, given, lazy=feed)
+
+    def pin(self, slot, frames, poses, mask=None):
+        """Pin poses of frames the clip in ``slot`` has yet to return (a pool opened with ``pins=H``): ``frames`` [K], distinct host
+        ints in ``[slots['frames_out'][slot], ... + H)`` in the numbering of the slot's returned frames; ``poses`` [J, F, K]; ``mask``
+        [J, F, K] bool, True = pinned, default the whole pose; host or device.  The window that owns a pinned frame runs through the
+        reference's inpainting branch and keeps the pinned elements (``open_pool``).  Elements a later call's mask leaves out keep what
+        an earlier call pinned.  ``ValueError`` ahead of any engine call for every refusal."""
+        if self._closed:
+            raise RuntimeError("the pool is closed")
+        slot = int(slot)
+        if not 0 <= slot < self._S or not self._state["open"][slot]:
+            raise ValueError(f"slot {slot} is not open")
+        fr, poses, mask = self._check_pin(frames, poses, mask, (), int(self._state["frames_out"][slot]))
+        self._engine().long_pool_pin(slot, fr, poses, mask)
+        self._pending[slot] |= set(fr.tolist())
+        self._refresh()
+
+    def unpin(self, slot, frames=None):
+        """Drop the pins of ``frames`` (same range as in ``pin``; a frame that holds none is no error) of ``slot``, or all of them."""
+        if self._closed:
+            raise RuntimeError("the pool is closed")
+        slot = int(slot)
+        if not 0 <= slot < self._S or (frames is not None and not self._state["open"][slot]):
+            raise ValueError(f"slot {slot} is not open")
+        fr = self._check_unpin(frames, int(self._state["frames_out"][slot]))
+        self._engine().long_pool_unpin(slot, fr)
+        self._pending[slot] = set() if fr is None else self._pending[slot] - set(fr.tolist())
+        self._refresh()
 
     def _leave(self, which):
         closing = np.zeros(self._S, np.int32)
@@ -850,7 +1048,7 @@ def pool_keys(keys, windows_run, n_windows):
 
 
 def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=0.0, clip_denoised=False, sag=None, post=None, noise_keys=None,
-              score=None, max_seconds=None, input_sr=None, input_channels=1, resample=None):
+              score=None, max_seconds=None, input_sr=None, input_channels=1, resample=None, pins=None):
     """``open_stream`` for clips that start and stop at different times and arrive at different rates: a session pool of ``capacity``
     slots on ONE engine.
 
@@ -910,10 +1108,39 @@ def open_pool(diffusion, model, capacity, sampler='ddim', skip_timesteps=0, eta=
     (``ResampleStream.reset``; a no-op for a slot that left).  ``slots['samples_in']`` stays in 16 kHz samples,
     ``slots['input_samples_in']`` is added beside it.
 
-    Not built: device-resident ``lengths``, ``edit_long`` on a pool, PLMS, ``const_noise``,
+    ``pins=H`` (an int >= 34, the horizon in frames; None: nothing changes, nothing is allocated) -- "be in this pose at frame 412", for
+    frames a clip has yet to return::
+
+        pool.pin(slot, frames [K], poses [J, F, K], mask=None)      # mask [J, F, K] bool, True = pinned; default: the whole pose
+        pool.unpin(slot, frames=None)                               # None: every pin of the slot
+        pool.slots['pins']                                          # pinned frames per slot whose window has yet to run
+
+    ``frames`` are in the numbering of the slot's returned frames (``slots['frames_out']``), distinct, each in ``[frames_out,
+    frames_out + H)``; host or device ``poses`` / ``mask``.  Window w of a slot covers its frames ``30 w .. 30 w + 33`` and OWNS all 34 for
+    w = 0 and ``30 w + 4 ..`` otherwise (``edit_plan``'s ownership).  When the window that owns a pinned frame runs, it runs through the
+    reference's inpainting branch (p_mean_variance, gaussian_diffusion.py:314-320; TED re-noises the kept motion, BEAT does not) with
+    ``inpainting_mask`` True exactly on the pinned elements of the frames it owns -- its prefix frames are never kept, even when they
+    carry a pin: the window before owned them and has honoured it -- and ``inpainted_motion`` the pinned values there, zero elsewhere.
+    A window whose owned frames carry no pin runs exactly as without pins.  Each of ``pool_plan``'s rounds is split into at most two
+    sampling calls (``pool_pin_plan``): its unpinned slots, ascending, as a plain call, then its pinned slots, ascending, as an
+    inpainting call; an empty half is skipped.  So a clip without a pin never enters the inpainting kernels because a neighbour has
+    one, and a pool with no pending pin makes precisely the calls it made before.  Every call is one public sampling call:
+    ``'torch_cpu'`` draws what that call draws, in call order (``RefDraws.windows`` for a plain call, ``RefDraws.edit_windows`` for a pinned
+    one), and the result is bit for bit that loop of public calls (tests/test_gpu_long_pool_pins.py); un-keyed ``'philox'`` draws row r
+    of the q-th CALL since the open at ``sample_offset + r + (q << 48)``; ``noise_keys='clip'`` keeps the clip's key and its own window,
+    so a pinned clip's frames still do not depend on its neighbours.  ``join`` starts a clip with no pin and ``leave`` drops the pins
+    its clip never reached.  On the device: a ring of H (rounded up to a multiple of 4) frames of values and bytes per slot, written by
+    ``k_pool_pin_store``, turned into a pinned call's inpainting planes by ``k_pool_pin_gather`` (csrc/ls_chain.hip), allocated when the
+    engine is bound.  ``ValueError`` ahead of any engine call: a pool opened without ``pins=``, a slot that is not open, a frame below
+    ``frames_out`` or at or beyond ``frames_out + H``, a frame named twice, wrong shapes, ``sag=``.  What a pinned round costs beside a
+    plain one has not been measured.
+
+    Not built: device-resident ``lengths``, ``edit_long`` on frames a pool has already returned, pins with ``sag=`` (a pinned window would
+    start from ``edit_start(motion, mask, sag_out)``: a kernel form of its own), soft (fractional) pins, device-resident frame lists,
+    PLMS, ``const_noise``,
     ``dump_steps``, sharded calls, a non-blocking ``push``."""
     return LongPool(diffusion, model, capacity, sampler, skip_timesteps, eta, clip_denoised, sag, post, noise_keys, score, max_seconds, input_sr,
-                    input_channels, resample)
+                    input_channels, resample, pins)
 
 
 def _edit_ranges(frames, B, n_frames):
@@ -1188,7 +1415,8 @@ def edit_long(diffusion, model, timeline, frames, audio, seed_poses, vid_indices
     device mask stays on the device: ``k_edit_mask_pairs`` reduces it to one flag per clip-window and only those W * B bytes reach the
     host for planning.
 
-    Not built: edits of a running stream or pool (masks on them included), bit-packed masks, soft (fractional) masks, PLMS,
+    Not built: edits of frames a running stream or pool has already returned (frames still to come can be pinned: ``open_pool(pins=)``,
+    ``open_stream(pins=)``), bit-packed masks, soft (fractional) masks, PLMS,
     ``const_noise``, ``dump_steps``, ``'torch_device'``, resampling windows behind
     the last edited one, the SAG encoder (motion -> latent) as the source of ``text_features`` (chain ``MOTIONCLIP`` yourself) and
     device-resident length arrays; in the dense form also ragged batches (``audio_lengths=``) and re-encoding only the edited windows'

@@ -4,6 +4,8 @@
     python tools/long_pool_time.py 4             # one pool size
     python tools/long_pool_time.py --keyed       # a keyed pool (noise_keys='clip') against an unkeyed one at 1, 4, 8 and 32 speakers
                                                  # (profiles/r28_pool_keys.md); sizes may follow
+    python tools/long_pool_time.py --pins        # a pinned round against a plain round of the same pool at 1, 4 and 8 speakers
+                                                 # (profiles/r33_pool_pins.md); sizes may follow
 
 TED, Philox noise, guidance 1.5, device-resident inputs, hipGraph replay, ddim100 skip 80 (20 steps per window).  S speakers talk at the
 same rate but started at different times: speaker s is s * 32000 / S samples ahead of speaker 0, so their windows complete at staggered
@@ -19,7 +21,15 @@ worst per tick, and per completed window.  The shader clock is sampled alongside
 
 --keyed: two pools with the same weights on two models, one opened with noise_keys='clip', fed the same ticks and timed the same way,
 keyed first on even ticks.  What the keys add to a round: the upload of its rows of the key table, one draw launch per ring refill
-(csrc/ls_philox_rows.hip) and the step kernels reading their draws from the ring in place of computing them."""
+(csrc/ls_philox_rows.hip) and the step kernels reading their draws from the ring in place of computing them.
+
+--pins: ONE pool opened with pins=64, every speaker fed 32000 samples per tick, so every tick is one round at batch S.  Ahead of every
+other tick each speaker's coming window is pinned (one whole pose, ten frames ahead of the frames returned), which makes that tick's
+round an inpainting call at batch S; the ticks between are plain calls at the same batch, in the same process, on the same handle.
+Timed per tick: the push, and on pinned ticks the S pin calls ahead of it (each ends in a host wait).  Reported: median / worst of a
+plain push and of a pinned push, their difference, the plain pushes' own spread (worst - best, and the median absolute deviation), and
+the pin calls.  What a pinned round adds: k_pool_pin_gather, and per step the denoiser alone plus the inpainting update in place of
+the fused step with its update."""
 import os
 import statistics
 import sys
@@ -136,6 +146,54 @@ def run_keyed(S, per_tick, cfg, models, diffusion, clocks):
         pool.close()
 
 
+def run_pins(S, cfg, model, diffusion, clocks):
+    AL, per_tick, n_ticks = cfg.audio_len, STRIDE, WARM + 2 * TICKS
+    total = AL + n_ticks * per_tick
+    y = {k: torch.from_numpy(v).to(DEV) for k, v in synth.make_long_cond(cfg, S, -(-total // STRIDE) + 1).items()}
+    pool = long_form.open_pool(diffusion, model, S, sampler="ddim", skip_timesteps=SKIP, pins=64)
+    for s in range(S):
+        assert pool.join(y["seed_poses"][s], y["vid_indices"][s], y["scale"][s]) == s
+    pose = (torch.rand(cfg.njoints, cfg.nfeats, 1, generator=torch.Generator().manual_seed(33)) * 2 - 1).to(DEV)
+    pool.push(y["audio"][:, :AL].contiguous(), [AL] * S)            # before the clock starts: window 0 of every speaker
+    torch.cuda.synchronize()
+    clocks.take()
+    fed, ms, pin_ms = AL, {False: [], True: []}, []
+    for t in range(n_ticks):
+        chunk = y["audio"][:, fed:fed + per_tick].contiguous()
+        pinned = t % 2 == 1
+        if pinned:
+            at = int(pool.slots["frames_out"][0]) + 10              # owned by the window this tick completes
+            ms_pin, _ = timed(lambda: [pool.pin(s, [at], pose) for s in range(S)])
+        ms_push, counts = timed(lambda: pool.push(chunk, [per_tick] * S)[1])
+        assert counts.tolist() == [30] * S and pool.slots["pins"].tolist() == [0] * S
+        fed += per_tick
+        if t >= WARM:
+            ms[pinned].append(ms_push)
+            if pinned:
+                pin_ms.append(ms_pin)
+    tm = model.model.engine().timing()
+    plain, pins = ms[False], ms[True]
+    med_p, med_i = statistics.median(plain), statistics.median(pins)
+    mad = statistics.median(abs(v - med_p) for v in plain)
+    print(f"S={S:2d}, one round at batch {S} per tick, {len(plain)} plain and {len(pins)} pinned ticks: plain push {med_p:7.3f} / {max(plain):7.3f}   "
+          f"pinned push {med_i:7.3f} / {max(pins):7.3f}   pinned - plain {med_i - med_p:+.3f} ms ({med_i / med_p:.3f}x)   plain spread: worst - best "
+          f"{max(plain) - min(plain):.3f}, median abs deviation {mad:.3f}   {S} pin calls {statistics.median(pin_ms):.3f} / {max(pin_ms):.3f}   | last push: "
+          f"graph replayed {tm['graph_replayed']} of {tm['n_segments']}, step path {tm['step_path']} | {clocks.take()}", flush=True)
+    pool.close()
+
+
+def main_pins(sizes):
+    cfg, model, diffusion = build()
+    diffusion.noise_source, diffusion.philox_seed = "philox", 1
+    clocks = ClockSampler()
+    clocks.start()
+    print(f"# TED ddim100 skip {SKIP}, CFG 1.5, philox, device inputs, graph replay; one pool with pins=64, {WARM} warm-up ticks, then plain and "
+          f"pinned ticks in turn ({TICKS} each); ms per push, median / worst")
+    for S in sizes or [1, 4, 8]:
+        run_pins(S, cfg, model, diffusion, clocks)
+    clocks.on = False
+
+
 def main_keyed(sizes):
     cfg, model_k, diffusion = build()
     model_u = build()[1]
@@ -153,6 +211,8 @@ def main_keyed(sizes):
 def main():
     if "--keyed" in sys.argv[1:]:
         return main_keyed([int(a) for a in sys.argv[1:] if a != "--keyed"])
+    if "--pins" in sys.argv[1:]:
+        return main_pins([int(a) for a in sys.argv[1:] if a != "--pins"])
     sizes = [int(sys.argv[1])] if len(sys.argv) > 1 else [4, 8]
     cfg, pool_model, diffusion = build()
     stream_models = [build()[1] for _ in range(max(sizes))]
